@@ -26,6 +26,13 @@ The timed region is exactly K steps bracketed by barrier + device synchronise, M
 the launching stream, taken in a second, untimed pass).  `cpu_baseline` = the reference's own g2o compiled verbatim (oracle/_ref/libg2o_ref.so,
 thirdparty/g2o built -O2 -g as its CMake default does, look-alike Eigen; the graph built as Optimizer::MapFusionGBA builds it by
 oracle/ref_g2o_driver.cpp — NOT through the class API) on optimize(1) and optimize(4) of the same map, the CPU port beside it.
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, print the line (`config` then holds the figures of the
+timed region alone).  `--full` adds everything else named above — the host-to-host call, the per-kernel pass and both rooflines, the CPU
+baseline, the class API, the tracking / local-BA / pose-graph / Hamming / concurrency legs and config 5; `--gba-only`, `--no-cpu-baseline`
+and `--no-large-map` trim a full run.  `--dump-outputs DIR` writes what the last timed step returns to its caller (optimised cameras and
+landmarks, chi2 per edge, depth-positive flags, the run's statistics and chi2 history) as DIR/<name>.npy in float64 / float32; the inputs
+are seeded, so two builds can be compared array by array.
 """
 from __future__ import annotations
 
@@ -808,7 +815,69 @@ def reference_cpu_leg(prob):
             "trials": int(s4.lm_trials), "iterations": int(s4.iters_done)}
 
 
-def compact_line(full, extra_path, workload="gba_c4", cpu_iters=3):
+DUMP_CAP_BYTES = 64 << 20
+
+
+ROW_SPACES = {"pt": ("pt_xyz",), "edge": ("chi2_per_edge", "depth_positive")}   # arrays indexed by landmark / by observation
+
+
+def cap_outputs(arrays, cap=DUMP_CAP_BYTES):
+    """`arrays` as written, within `cap` bytes of .npy files in all.  Above it, every row space of ROW_SPACES keeps the same fraction of its rows — a
+    fixed, seeded sample, the same in every run — and its row indices go beside it as <space>_rows (float64, counted against the cap)."""
+    import numpy as np
+    header = 128                                                   # bytes of one .npy header for these shapes
+    files = len(arrays) + len(ROW_SPACES)
+    if sum(a.nbytes for a in arrays.values()) + header * len(arrays) <= cap:
+        return dict(arrays)
+    sampled = {n for names in ROW_SPACES.values() for n in names}
+    fixed = sum(a.nbytes for n, a in arrays.items() if n not in sampled) + header * files
+    per_all_rows = sum(sum(arrays[n].nbytes for n in names) + 8 * arrays[names[0]].shape[0] for names in ROW_SPACES.values())
+    frac = (cap - fixed) / per_all_rows
+    assert frac > 0, "the unsampled outputs alone exceed the cap"
+    out = {n: a for n, a in arrays.items() if n not in sampled}
+    for space, names in ROW_SPACES.items():
+        n_rows = arrays[names[0]].shape[0]
+        rows = np.sort(np.random.default_rng(12345).choice(n_rows, int(n_rows * frac), replace=False))
+        for n in names:
+            out[n] = arrays[n][rows]
+        out[space + "_rows"] = rows.astype(np.float64)
+    return out
+
+
+def dump_outputs(out_dir, h, st, chi_hist):
+    """--dump-outputs (one rank): what the last timed step hands its caller (ccm_ba_download + ccm_ba_depth_positive + the run's statistics), one .npy
+    per array, within DUMP_CAP_BYTES (cap_outputs)."""
+    import numpy as np
+    cam, pts, chi2, dpos = h.download()
+    arrays = {"cam_qt": cam, "pt_xyz": pts, "chi2_per_edge": chi2, "depth_positive": dpos.astype(np.float32),
+              "stats": np.array([st.iters_done, st.lm_trials, st.pcg_iters, st.stop_reason, st.chi2_initial, st.chi2_final, st.lambda_final], np.float64),
+              "chi2_per_iteration": np.asarray(chi_hist, np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in cap_outputs(arrays).items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
+def open_side_file(name):
+    """(fd, path) of a side file of this run: `name` next to bench.py, or — where the checkout cannot be written — a new file of this run's own in
+    the temporary directory.  The measurement never depends on write access to the checkout."""
+    path = os.path.join(ROOT, name)
+    try:
+        return os.open(path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644), path
+    except OSError:
+        import tempfile
+        stem, ext = os.path.splitext(name)
+        return tempfile.mkstemp(prefix=stem + "_", suffix=ext)
+
+
+def shown_path(path):
+    """a side file's path as the result line names it: relative to the checkout when it lies inside it"""
+    if not os.path.isabs(path):
+        return path
+    rel = os.path.relpath(path, ROOT)
+    return path if rel.startswith("..") else rel
+
+
+def compact_line(full, extra_path, workload="gba_c4", cpu_iters=3, log_path="bench_log.txt"):
     """The ONE stdout line: the headline figures of the long record `full` (which goes to bench_extra.json) as compact JSON, always < 4 KB — the driver's
     parser lost round 5's 21 KB line.  tests/test_bench_line.py feeds it the committed long records of earlier rounds."""
     def pick(dct, keys):
@@ -841,8 +910,8 @@ def compact_line(full, extra_path, workload="gba_c4", cpu_iters=3):
         for k in ("speedup_vs_cpu_port_per_trial", "speedup_vs_reference_per_iteration"):
             if k in full:
                 compact[k] = full[k]
-    compact["extra_file"] = os.path.relpath(extra_path, ROOT) if os.path.isabs(extra_path) else extra_path
-    compact["log_file"] = "bench_log.txt"
+    compact["extra_file"] = shown_path(extra_path)
+    compact["log_file"] = shown_path(log_path)
     line = json.dumps(compact, separators=(",", ":"))
     if len(line) > 4000:     # never let an over-long field break the parser again: drop the optional parts
         for k in ("roofline_trial", "speedup_vs_cpu_port_per_trial", "speedup_vs_reference_per_iteration"):
@@ -867,18 +936,28 @@ def main():
     ap.add_argument("--no-large-map", action="store_true", help="skip the extra.gba_c5 leg (BASELINE config 5)")
     ap.add_argument("--pcg-max-iters", type=int, default=0)
     ap.add_argument("--plumbing-only", action="store_true", help="N-rank launch path up to (not including) the first device call; runs without a GPU")
+    ap.add_argument("--full", action="store_true", help="besides the timed steps: host-to-host call, per-kernel pass, rooflines, CPU baseline, class API, "
+                                                         "tracking / local-BA / pose-graph / Hamming / concurrency legs, config 5")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        # ccm_ba_download is collective across the ranks of a sharded handle and each rank holds the chi2 of its own edges only: refused before any device work
+        ap.error("--dump-outputs needs a single rank (--gpus 1)")
     if args.gba_only:
         args.no_cpu_baseline = True
     # Output contract: the LAST line of stdout is ONE compact JSON line (< 4 KB) written with plain print(); everything else this run produces goes to files next
-    # to bench.py — the long record (kernel table, class API, tracking / local-BA / pose-graph / Hamming / concurrency legs, config 5) to bench_extra.json, whatever
+    # to bench.py (in the temporary directory where the checkout is read-only) — the long record (kernel table, class API, tracking / local-BA / pose-graph / Hamming / concurrency legs, config 5) to bench_extra.json, whatever
     # native code prints meanwhile (HIP / libdrm notices, the reference's own "+++++ Map 0 Initialized +++++" greeting of Map.cpp:67 in the class-API leg) to
     # bench_log.txt.  File descriptors 1 and 2 point at that log from here until the line is printed; a failing run restores them and reports on stderr.
     rank_env = int(os.environ.get("RANK", "0"))
-    log_path = os.path.join(ROOT, "bench_log.txt" if rank_env == 0 else f"bench_log.rank{rank_env}.txt")
     sys.stdout.flush(); sys.stderr.flush()
     fds = {"out": os.dup(1), "err": os.dup(2)}
-    log_fd = os.open(log_path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
+    log_fd, log_path = open_side_file("bench_log.txt" if rank_env == 0 else f"bench_log.rank{rank_env}.txt")
+    args.log_path = log_path
     os.dup2(log_fd, 1); os.dup2(log_fd, 2); os.close(log_fd)
 
     def restore_fds():
@@ -1012,15 +1091,17 @@ def run(args):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     chi_hist, lam_hist, tr_hist = h.history()
+    if args.dump_outputs:      # one rank only (main)
+        dump_outputs(args.dump_outputs, h, st, chi_hist)
     h.close()
-    steps = max(args.steps, 1)
+    steps = args.steps
     call_ms = elapsed * 1e3 / steps
     create_ms, run_ms = tm["create"] * 1e3 / steps, tm["run"] * 1e3 / steps
     trial_ms = elapsed * 1e3 / max(trials, 1)
 
     # ---- the same call from host arrays to host arrays (PCIe both ways): create + run + download, best of 3 (rank-local figure, N = 1 only)
     h2h_ms = None
-    if world == 1:
+    if args.full and world == 1:
         for _ in range(3):
             t0 = time.perf_counter()
             hh = optimizer.BAHandle(ctx, prob)
@@ -1030,55 +1111,57 @@ def run(args):
             dt = (time.perf_counter() - t0) * 1e3
             h2h_ms = dt if h2h_ms is None else min(h2h_ms, dt)
 
-    # ---- per-kernel pass (untimed): the same call once more with HIP events around every launch, on the launching stream
-    ctx.prof_enable(-1)
-    ctx.prof_reset()
-    t0 = time.perf_counter()
-    one_call()
-    ctx.sync()
-    prof_call_ms = (time.perf_counter() - t0) * 1e3
-    prof = {name: ctx.prof_read(k) for name, k in K.items() if name.startswith("BA_")}
-    ctx.prof_enable(-2)
-    kb = ba_kernel_bytes(counts)
-    pmc = pmc_lookup(args.workload) if world == 1 else {}
-    kernels = []
-    for name, (n, ms) in sorted(prof.items(), key=lambda kv: -kv[1][1]):
-        if not n:
-            continue
-        avg_us = ms * 1e3 / n
-        ach = kb[name] / (avg_us * 1e-6) / 1e9
-        kname = KERNEL_OF_CLASS[name].split("+")[0]
-        ent = pmc.get(kname) or pmc.get(kname + "_t")   # templated kernels appear as name_t in the rocprofv3 tables
-        kernels.append({"class": name.lower(), "kernel": KERNEL_OF_CLASS[name], "launches_per_call": n, "avg_us": round(avg_us, 2),
-                        "ms_per_call": round(ms, 4), "algorithmic_bytes_per_launch": kb[name], "achieved_GBps": round(ach, 1),
-                        "frac_of_hbm_peak": round(ach / HBM_PEAK_GBS, 5), "limiter": LIMITER.get(name, "hbm"),
-                        "pmc_hbm_bytes_per_launch": ent["hbm_bytes_per_launch"] if ent else None,
-                        "pmc_avg_us": ent.get("avg_us") if ent else None, "pmc_grid": ent["grid"] if ent else None})
-    dom = kernels[0] if kernels else None
-    roofline = None
-    if dom:
-        # dominant kernel (largest share of the call).  `bound` names what limits it; achieved / frac are its ALGORITHMIC bytes
-        # over its measured duration against the HBM peak whatever the limiter, so the number stays comparable across rounds.
-        roofline = {"kernel": dom["kernel"], "bound": "hbm" if dom["limiter"] == "hbm" else dom["limiter"], "achieved": dom["achieved_GBps"],
-                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": dom["frac_of_hbm_peak"], "traffic": dom["pmc_hbm_bytes_per_launch"],
-                    "traffic_source": pmc_source(args.workload),
-                    "launches": dom["launches_per_call"], "avg_us": dom["avg_us"], "algorithmic_bytes_per_launch": dom["algorithmic_bytes_per_launch"],
-                    "share_of_call": round(dom["ms_per_call"] / max(sum(k["ms_per_call"] for k in kernels), 1e-9), 3)}
-    # whole LM trial against the HBM roofline, SURVEY §8(d): bytes(trial) = 656 E + 312 L + 700 C + 576 S
     E, L, C, B = counts["edges"], counts["points"], counts["free_cams"], counts["blocks"]
-    trial_bytes = 656.0 * E + 312.0 * L + 700.0 * C + 576.0 * B
-    trial_gbs = trial_bytes / (trial_ms * 1e-3) / 1e9
-    roofline_trial = {"what": "one LM trial (the step, structure build included, over its trials), SURVEY 8(d) byte formula 656 E + 312 L + 700 C + 576 S",
-                      "bound": "hbm", "algorithmic_bytes_per_trial": trial_bytes, "ms_per_trial": round(trial_ms, 4),
-                      "achieved": round(trial_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(trial_gbs / HBM_PEAK_GBS, 5),
-                      "frac_of_achievable_6300": round(trial_gbs / 6300.0, 5),
-                      "kernel_ms_per_call": round(sum(k["ms_per_call"] for k in kernels), 3), "profiled_call_ms": round(prof_call_ms, 3)}
+    prof, kernels, roofline, roofline_trial = {}, [], None, None
+    # ---- per-kernel pass (untimed): the same call once more with HIP events around every launch, on the launching stream (--full)
+    if args.full:
+        ctx.prof_enable(-1)
+        ctx.prof_reset()
+        t0 = time.perf_counter()
+        one_call()
+        ctx.sync()
+        prof_call_ms = (time.perf_counter() - t0) * 1e3
+        prof = {name: ctx.prof_read(k) for name, k in K.items() if name.startswith("BA_")}
+        ctx.prof_enable(-2)
+        kb = ba_kernel_bytes(counts)
+        pmc = pmc_lookup(args.workload) if world == 1 else {}
+        kernels = []
+        for name, (n, ms) in sorted(prof.items(), key=lambda kv: -kv[1][1]):
+            if not n:
+                continue
+            avg_us = ms * 1e3 / n
+            ach = kb[name] / (avg_us * 1e-6) / 1e9
+            kname = KERNEL_OF_CLASS[name].split("+")[0]
+            ent = pmc.get(kname) or pmc.get(kname + "_t")   # templated kernels appear as name_t in the rocprofv3 tables
+            kernels.append({"class": name.lower(), "kernel": KERNEL_OF_CLASS[name], "launches_per_call": n, "avg_us": round(avg_us, 2),
+                            "ms_per_call": round(ms, 4), "algorithmic_bytes_per_launch": kb[name], "achieved_GBps": round(ach, 1),
+                            "frac_of_hbm_peak": round(ach / HBM_PEAK_GBS, 5), "limiter": LIMITER.get(name, "hbm"),
+                            "pmc_hbm_bytes_per_launch": ent["hbm_bytes_per_launch"] if ent else None,
+                            "pmc_avg_us": ent.get("avg_us") if ent else None, "pmc_grid": ent["grid"] if ent else None})
+        dom = kernels[0] if kernels else None
+        roofline = None
+        if dom:
+            # dominant kernel (largest share of the call).  `bound` names what limits it; achieved / frac are its ALGORITHMIC bytes
+            # over its measured duration against the HBM peak whatever the limiter, so the number stays comparable across rounds.
+            roofline = {"kernel": dom["kernel"], "bound": "hbm" if dom["limiter"] == "hbm" else dom["limiter"], "achieved": dom["achieved_GBps"],
+                        "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": dom["frac_of_hbm_peak"], "traffic": dom["pmc_hbm_bytes_per_launch"],
+                        "traffic_source": pmc_source(args.workload),
+                        "launches": dom["launches_per_call"], "avg_us": dom["avg_us"], "algorithmic_bytes_per_launch": dom["algorithmic_bytes_per_launch"],
+                        "share_of_call": round(dom["ms_per_call"] / max(sum(k["ms_per_call"] for k in kernels), 1e-9), 3)}
+        # whole LM trial against the HBM roofline, SURVEY §8(d): bytes(trial) = 656 E + 312 L + 700 C + 576 S
+        trial_bytes = 656.0 * E + 312.0 * L + 700.0 * C + 576.0 * B
+        trial_gbs = trial_bytes / (trial_ms * 1e-3) / 1e9
+        roofline_trial = {"what": "one LM trial (the step, structure build included, over its trials), SURVEY 8(d) byte formula 656 E + 312 L + 700 C + 576 S",
+                          "bound": "hbm", "algorithmic_bytes_per_trial": trial_bytes, "ms_per_trial": round(trial_ms, 4),
+                          "achieved": round(trial_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(trial_gbs / HBM_PEAK_GBS, 5),
+                          "frac_of_achievable_6300": round(trial_gbs / 6300.0, 5),
+                          "kernel_ms_per_call": round(sum(k["ms_per_call"] for k in kernels), 3), "profiled_call_ms": round(prof_call_ms, 3)}
 
     # ---- CPU baseline on this box's host cores (rank 0, N = 1): the REFERENCE's own g2o compiled verbatim (libg2o_ref.so), optimize(1) and optimize(4) of the same
     # map (graph built by oracle/ref_g2o_driver.cpp the way MapFusionGBA builds it; bounded sample: ~25 s); the CPU port (oracle/ba_ref.cpp) beside it
     cpu = None
     n_agents = int(synth.BA_CONFIGS.get(args.workload, {}).get("n_agents", 1))
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import oracle
         oracle.build()
         _, _, _, _, ost = oracle.ba_optimize(prob, args.cpu_iters)
@@ -1117,14 +1200,14 @@ def run(args):
 
     # ---- the other half of the metric: tracked fps / agent (rank 0 only; one agent = one GPU)
     class_api = None
-    if rank == 0 and world == 1 and not args.gba_only:
+    if args.full and rank == 0 and world == 1 and not args.gba_only:
         try:
             class_api = class_api_leg(args.workload, prob, n_agents)
         except Exception as e:
             class_api = {"error": str(e)}
     extra = None
     agents = None
-    if world > 1 and not args.gba_only:
+    if args.full and world > 1 and not args.gba_only:
         # N > 1: the part of the metric that partitions naturally (SURVEY 8e bullet 1: one agent = one process = one GPU, no exchange step).  EVERY rank runs its own
         # agent's tracked-frame leg and local bundle adjustments at the same time on its own GPU; rank 0 reports the sum (weak scaling: per-GPU work fixed) next
         # to the strong-scaling global-BA figure above.  Single-rank handles never enter a collective (ba.hip: ba_allreduce_sum), so the sharded job's communicator is idle here.
@@ -1145,7 +1228,7 @@ def run(args):
         agents = {"what": "every rank = one agent on its own GPU running the tracked-frame leg and the local bundle adjustments at the same time (weak scaling; no data-path collective)",
                   "agents": len(ok), "agents_total_fps": round(sum(g["tracked_fps"] for g in ok), 1), "agents_total_orb_batch_fps": round(sum(g["orb_batch_fps"] for g in ok), 1),
                   "local_ba_per_s_total": round(sum(1e3 / g["local_ba_ms"] for g in ok), 1), "per_rank": gathered}
-    if rank == 0 and not args.gba_only:
+    if args.full and rank == 0 and not args.gba_only:
         if extra is None:
             extra = tracking_leg(ctx, with_cpu=(world == 1 and not args.no_cpu_baseline))
         if agents:
@@ -1172,10 +1255,10 @@ def run(args):
         def grp(names):
             return sum(prof[n][1] for n in names if n in prof)
         prof_trials = max(trials // steps, 1)
-        per_trial = {"shard_ms": round(grp(("BA_LINEARIZE", "BA_CAM", "BA_DINV", "BA_SCHUR_DIAG", "BA_SCHUR_OFF", "BA_BACKSUB", "BA_CHI2")) / prof_trials, 4),
-                     "solve_ms": round(grp(("BA_PCG_PERSIST", "BA_PCG_SPMV", "BA_PCG_UPDATE", "BA_COARSE", "BA_UPDATE")) / prof_trials, 4),
-                     "allreduce_ms": round(grp(("BA_ALLREDUCE",)) / prof_trials, 4),
-                     "other_ms": round(grp(("BA_REDUCE",)) / prof_trials, 4)}
+        per_trial = None if not prof else {"shard_ms": round(grp(("BA_LINEARIZE", "BA_CAM", "BA_DINV", "BA_SCHUR_DIAG", "BA_SCHUR_OFF", "BA_BACKSUB", "BA_CHI2")) / prof_trials, 4),
+                                           "solve_ms": round(grp(("BA_PCG_PERSIST", "BA_PCG_SPMV", "BA_PCG_UPDATE", "BA_COARSE", "BA_UPDATE")) / prof_trials, 4),
+                                           "allreduce_ms": round(grp(("BA_ALLREDUCE",)) / prof_trials, 4),
+                                           "other_ms": round(grp(("BA_REDUCE",)) / prof_trials, 4)}
         full = {
             "metric": "global-BA LM iterations/s (4-agent merged map)",
             "value": round(iters / elapsed, 4), "unit": "LM iter/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1209,14 +1292,14 @@ def run(args):
             full["speedup_vs_cpu_port_per_trial"] = round(port["ms_per_trial"] / trial_ms, 1)
             if cpu.get("kind") == "reference":
                 full["speedup_vs_reference_per_iteration"] = round(cpu["ms_per_iter"] / (elapsed * 1e3 / max(iters, 1)), 1)
-        extra_path = os.path.join(ROOT, "bench_extra.json")
         try:
-            with open(extra_path, "w") as f:
+            fd, extra_path = open_side_file("bench_extra.json")
+            with os.fdopen(fd, "w") as f:
                 json.dump(full, f, indent=1)
         except OSError as e:
             extra_path = f"(not written: {e})"
 
-        line = compact_line(full, extra_path, args.workload, args.cpu_iters)
+        line = compact_line(full, extra_path, args.workload, args.cpu_iters, log_path=args.log_path)
     res.close()
     if dist is not None:
         dist.barrier()   # rank 0 is still busy with the tracking leg / JSON while the others arrive here

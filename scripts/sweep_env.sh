@@ -3,7 +3,7 @@
 # usage: sweep_env.sh VAR "v1 v2 ..." "gba_c4 gba_c3" [steps]
 VAR=$1; VALS=$2; WLS=$3; STEPS=${4:-10}
 for wl in $WLS; do for v in $VALS; do
-  env $VAR=$v timeout 300 python bench.py --gba-only --workload $wl --steps $STEPS --warmup 2 2>/dev/null | grep '^{' | python -c "
+  env $VAR=$v timeout 300 python bench.py --full --gba-only --workload $wl --steps $STEPS --warmup 2 2>/dev/null | grep '^{' | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); c = d['config']
 k = {x['class']: x for x in d['kernels']}

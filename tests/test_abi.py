@@ -48,12 +48,15 @@ def test_version_and_error_strings():
 
 
 def test_no_gpu_means_no_context():
-    import torch
-    if torch.cuda.is_available():
-        pytest.skip("a GPU is visible")
+    # The library's own runtime decides whether a GPU is visible: torch bundles a second HIP runtime, and initialising that one first
+    # (torch.cuda.is_available()) leaves the library's runtime without a device for the rest of the process — the GPU tests after this file.
     from ccm_slam_amd._lib import CcmError, Context
-    with pytest.raises(CcmError, match="no HIP device|no CPU fallback|device"):
-        Context(0)
+    try:
+        Context(0).close()
+    except CcmError as e:
+        assert re.search("no HIP device|no CPU fallback|device", str(e)), str(e)
+    else:
+        pytest.skip("a GPU is visible")
 
 
 def test_partition_balances_weights():

@@ -81,7 +81,8 @@ def test_bench_n_rank_launch_path_up_to_the_first_device_call():
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--plumbing-only"]
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    # no GPU for the ranks on any machine: with one visible, rank 1 of two would select a second device that a one-GPU machine does not have
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     import re
