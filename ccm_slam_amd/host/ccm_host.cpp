@@ -1,6 +1,7 @@
 // ccm_host.cpp — implementation of the host-side mirror (see ccm_host.h).  Plain C++17, no HIP headers:
 // everything device-side goes through the C ABI.
 #include "ccm_host.h"
+#include "kfdb_resolve.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -821,6 +822,45 @@ std::vector<int32_t> ComputeDistinctiveDescriptors(HipContext& ctx, const uint8_
   return best;
 }
 
+// ---- KeyFrameDatabase --------------------------------------------------------------------------------
+KeyFrameDatabase::KeyFrameDatabase(HipContext& ctx, int n_words, int log_capacity) {
+  check(ccm_kfdb_create(ctx.get(), n_words, log_capacity, &db_), ctx.get(), "ccm_kfdb_create");
+}
+KeyFrameDatabase::KeyFrameDatabase(ccm_kfdb* borrowed) : db_(borrowed), owned_(false) {}
+KeyFrameDatabase::~KeyFrameDatabase() { if (owned_) ccm_kfdb_destroy(db_); }
+void KeyFrameDatabase::add(HipContext& ctx, int64_t key, int32_t client, const BowVector& v) {
+  check(ccm_kfdb_add(db_, ctx.get(), key, client, (int)v.word.size(), v.word.data(), v.value.data()), ctx.get(), "ccm_kfdb_add");
+}
+void KeyFrameDatabase::erase(HipContext& ctx, int64_t key) { check(ccm_kfdb_erase(db_, ctx.get(), key), ctx.get(), "ccm_kfdb_erase"); }
+void KeyFrameDatabase::clear(HipContext& ctx) { check(ccm_kfdb_clear(db_, ctx.get()), ctx.get(), "ccm_kfdb_clear"); }
+
+std::vector<int64_t> KeyFrameDatabase::detect(HipContext& ctx, const BowVector& v, float minScore, const ccm_kfdb_filter* f, const Neighbours& neighbours) {
+  std::vector<int64_t> key(64); std::vector<int32_t> cnt(64); std::vector<float> si(64); std::vector<double> s64(64);
+  int n = 0;
+  for (;;) {   // the table rarely outgrows the first guess; then once more with its size
+    check(ccm_kfdb_query(db_, ctx.get(), (int)v.word.size(), v.word.data(), v.value.data(), f, (int)key.size(), key.data(), cnt.data(), si.data(), s64.data(),
+                         &n, nullptr, nullptr, nullptr), ctx.get(), "ccm_kfdb_query");
+    if (n <= (int)key.size()) break;
+    key.resize(n); cnt.resize(n); si.resize(n); s64.resize(n);
+  }
+  key.resize(n); si.resize(n);
+  return kfdb::resolve(key, si, minScore, neighbours);
+}
+std::vector<int64_t> KeyFrameDatabase::DetectLoopCandidates(HipContext& ctx, int64_t key, const BowVector& v, float minScore, const std::vector<int64_t>* map_keys,
+                                                            const std::vector<int64_t>& connected, const Neighbours& neighbours) {
+  ccm_kfdb_filter f{key, map_keys ? map_keys->data() : nullptr, map_keys ? (int)map_keys->size() : 0, connected.data(), (int)connected.size(), 0};
+  static const int64_t none = 0;
+  if (map_keys && map_keys->empty()) f.allow = &none;   // an empty map admits nothing
+  return detect(ctx, v, minScore, &f, neighbours);
+}
+std::vector<int64_t> KeyFrameDatabase::DetectMapMatchCandidates(HipContext& ctx, const BowVector& v, float minScore, uint64_t ass_clients, const Neighbours& neighbours) {
+  ccm_kfdb_filter f{-1, nullptr, 0, nullptr, 0, ass_clients};
+  return detect(ctx, v, minScore, &f, neighbours);
+}
+std::vector<int64_t> KeyFrameDatabase::DetectRelocalizationCandidates(HipContext& ctx, const BowVector& v, const Neighbours& neighbours) {
+  return detect(ctx, v, 0.0f, nullptr, neighbours);   // kfdb_resolve.h: relocalisation = the same phase 2 with minScore 0
+}
+
 // ---- Optimizer ---------------------------------------------------------------------------------------
 int Optimizer::PoseOptimizationClient(HipContext& ctx, double cam_qt[7], int n, const double* Xw, const double* obs,
                                       const double* invSigma2, const double K[4], std::vector<uint8_t>& outlier) {
@@ -1251,6 +1291,37 @@ extern "C" int ccmh_bow_transform(int device, int n_nodes, int L, const int32_t*
     std::memcpy(fv_idx, fv.idx.data(), fv.idx.size() * 4);
     sizes[0] = (int32_t)v.word.size(); sizes[1] = (int32_t)fv.node.size(); sizes[2] = (int32_t)fv.idx.size();
     return 0;
+  } catch (const std::exception&) { return -1000; }
+}
+
+// KeyFrameDatabase::Detect*Candidates through the mirror on a database handle of libccm_hip.so (the Python KeyFrameDatabase's).  kind 0 = loop
+// (self_key, allow / n_allow (n_allow < 0: every keyframe), exclude), 1 = map match (exclude_groups), 2 = relocalisation.  Neighbours as a table:
+// nb_key[i] has the neighbours nb_list[nb_off[i] .. nb_off[i+1]); keys absent from it have none.  Returns the number of candidates (<= cap written).
+extern "C" int ccmh_kfdb_detect(void* db, int device, int kind, int n, const int32_t* word, const double* value, float min_score, int64_t self_key,
+                                const int64_t* allow, int n_allow, const int64_t* exclude, int n_exclude, uint64_t exclude_groups, int n_nb_keys,
+                                const int64_t* nb_key, const int32_t* nb_off, const int64_t* nb_list, int64_t* out, int cap) {
+  try {
+    cslam::HipContext& ctx = thread_context(device);
+    cslam::KeyFrameDatabase kfdb((ccm_kfdb*)db);
+    cslam::BowVector v; v.word.assign(word, word + n); v.value.assign(value, value + n);
+    std::map<int64_t, int> row;
+    for (int i = 0; i < n_nb_keys; i++) row[nb_key[i]] = i;
+    auto nbs = [&](int64_t k, std::vector<int64_t>& o) {
+      auto it = row.find(k);
+      if (it != row.end()) o.assign(nb_list + nb_off[it->second], nb_list + nb_off[it->second + 1]);
+    };
+    std::vector<int64_t> r;
+    if (kind == 0) {
+      std::vector<int64_t> ex(exclude, exclude + n_exclude), al;
+      if (n_allow >= 0) al.assign(allow, allow + n_allow);
+      r = kfdb.DetectLoopCandidates(ctx, self_key, v, min_score, n_allow >= 0 ? &al : nullptr, ex, nbs);
+    } else if (kind == 1) {
+      r = kfdb.DetectMapMatchCandidates(ctx, v, min_score, exclude_groups, nbs);
+    } else {
+      r = kfdb.DetectRelocalizationCandidates(ctx, v, nbs);
+    }
+    for (int i = 0; i < (int)r.size() && i < cap; i++) out[i] = r[i];
+    return (int)r.size();
   } catch (const std::exception&) { return -1000; }
 }
 

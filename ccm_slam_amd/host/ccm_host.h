@@ -9,6 +9,7 @@
 // ORBextractor additionally offers the cv::InputArray / cv::OutputArray operator() of the reference.
 #pragma once
 #include <cstdint>
+#include <functional>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -234,6 +235,34 @@ class ORBVocabulary {
 };
 // best descriptor per map point: desc rows off[p]..off[p+1] are the observations of point p; returns local indices
 std::vector<int32_t> ComputeDistinctiveDescriptors(HipContext& ctx, const uint8_t* desc, const std::vector<int32_t>& off);
+
+// ---------------------------------------------------------------------------------------------------
+// KeyFrameDatabase — cslam/include/cslam/Database.h, cslam/src/Database.cpp.  Keyframes are keys (int64) with a client id; the
+// map objects' accessors become arguments: map_keys = GetMapptr()->GetMmpKeyFrames() (nullptr: every keyframe), connected =
+// GetConnectedKeyFrames(), ass_clients = bit c for every c in pMap->msuAssClients, neighbours(key, out) = GetBestCovisibilityKeyFrames(10).
+// Phase 1 on the device (ccm_kfdb_query), phase 2 in kfdb_resolve.h.  One database may be shared by threads, each with its own context.
+// ---------------------------------------------------------------------------------------------------
+class KeyFrameDatabase {
+ public:
+  using Neighbours = std::function<void(int64_t, std::vector<int64_t>&)>;
+  KeyFrameDatabase(HipContext& ctx, int n_words, int log_capacity = 0);
+  explicit KeyFrameDatabase(ccm_kfdb* borrowed);   // a handle owned elsewhere (not destroyed here)
+  ~KeyFrameDatabase();
+  KeyFrameDatabase(const KeyFrameDatabase&) = delete;
+  KeyFrameDatabase& operator=(const KeyFrameDatabase&) = delete;
+  void add(HipContext& ctx, int64_t key, int32_t client, const BowVector& v);
+  void erase(HipContext& ctx, int64_t key);
+  void clear(HipContext& ctx);
+  std::vector<int64_t> DetectLoopCandidates(HipContext& ctx, int64_t key, const BowVector& v, float minScore, const std::vector<int64_t>* map_keys,
+                                            const std::vector<int64_t>& connected, const Neighbours& neighbours);
+  std::vector<int64_t> DetectMapMatchCandidates(HipContext& ctx, const BowVector& v, float minScore, uint64_t ass_clients, const Neighbours& neighbours);
+  std::vector<int64_t> DetectRelocalizationCandidates(HipContext& ctx, const BowVector& v, const Neighbours& neighbours);
+  ccm_kfdb* handle() const { return db_; }
+ private:
+  std::vector<int64_t> detect(HipContext& ctx, const BowVector& v, float minScore, const ccm_kfdb_filter* f, const Neighbours& neighbours);
+  ccm_kfdb* db_ = nullptr;
+  bool owned_ = true;
+};
 
 // ---------------------------------------------------------------------------------------------------
 // Optimizer — cslam/include/cslam/Optimizer.h:84-112 (numerics; graph walking is the integrator's glue)

@@ -29,6 +29,10 @@ void ccmh_fuse_batch_destroy(void* h);
 int ccmh_projected_window_search_cand(int device, const float* kx, const float* ky, const int32_t* oct, const uint8_t* kdesc, int N, const float* inv_sigma2, int n_pts, const uint8_t* valid, const float* u, const float* v, const int32_t* level, const uint8_t* pdesc, const int32_t* cand_off, const int32_t* cand_idx, int chi2_gate, int dist_threshold, int32_t* matched, int claim, const uint8_t* no_claim, int32_t* best_idx, int32_t* best_dist);
 int ccmh_projected_window_search_dev(int device, const float* kx, const float* ky, const int32_t* oct, const uint8_t* kdesc, int N, float maxX, float maxY, const float* scale_factors, const float* inv_sigma2, int n_pts, const uint8_t* valid, const float* u, const float* v, const int32_t* level, const uint8_t* pdesc, float th, int chi2_gate, int dist_threshold, int32_t* matched, int claim, const uint8_t* no_claim, int32_t* best_idx, int32_t* best_dist);
 int ccmh_bow_transform(int device, int n_nodes, int L, const int32_t* child_off, const int32_t* child_id, const uint8_t* node_desc, const int32_t* word_id, const double* weight, const uint8_t* desc, int N, int levelsup, int32_t* bow_ids, double* bow_vals, int32_t* fv_nodes, int32_t* fv_off, int32_t* fv_idx, int32_t* sizes );
+/* KeyFrameDatabase::DetectLoopCandidates / DetectMapMatchCandidates / DetectRelocalizationCandidates (Database.cpp:72-439) through the host mirror, on a
+ * ccm_kfdb handle: kind 0 loop, 1 map match, 2 relocalisation; n_allow < 0 = every keyframe; neighbours = GetBestCovisibilityKeyFrames(10) as a table over
+ * nb_key.  Returns the number of candidates (min(that, cap) written to out), -1000 on a device error. */
+int ccmh_kfdb_detect(void* db, int device, int kind, int n, const int32_t* word, const double* value, float min_score, int64_t self_key, const int64_t* allow, int n_allow, const int64_t* exclude, int n_exclude, uint64_t exclude_groups, int n_nb_keys, const int64_t* nb_key, const int32_t* nb_off, const int64_t* nb_list, int64_t* out, int cap);
 void ccmh_to_se3quat(const float* Tcw16, double* qt7);
 void ccmh_se3quat_to_cvmat(const double* qt7, float* Tcw16);
 void ccmh_sim3_to_cvse3(const double* s8, float* Tcw16);

@@ -375,6 +375,47 @@ int  ccm_pose_graph_optimize(ccm_ctx* ctx, int n_vert, double* sim3 /* n_vert x 
                              const double* meas /* n_edge x 8 */, int max_iters, double lambda_init,
                              const volatile unsigned char* stop_flag /* nullable */, ccm_pg_stats* stats /* nullable */);
 
+/* ---- keyframe database (place recognition) ---------------------------------------------
+ * Replaces the inverted file of cslam::KeyFrameDatabase (cslam/src/Database.cpp:29-70) and phase 1 of DetectLoopCandidates /
+ * DetectMapMatchCandidates / DetectRelocalizationCandidates (:74-146, :206-271, :331-385): which keyframes share words with the query,
+ * how many, and the L1 score (thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-66, bit-identical in f64) of those with count > minCommonWords.
+ * Phase 2 (covisibility accumulation, :148-201) is host work on the returned table: ccm_slam_amd/host/kfdb_resolve.h.
+ * A keyframe is a key (the shim packs mId as id << 8 | client) with a client id `group` and its BowVector (word ids ascending, unique,
+ * < n_words; at most 4096 words in a query).  Threading: one handle is shared by all threads, each call uses the caller's context and stream
+ * (same device as the handle, else CCM_E_ARG); add / erase / clear are serialised and finished when they return, queries run concurrently
+ * under a reader lock.  Contract: every query is computed on fresh state — equal to the reference when a keyframe is queried at most once per
+ * query kind, which is how LoopFinder.cpp:142 and MapMatcher.cpp:150 call it (the reference's per-KeyFrame scratch fields mLoopQuery /
+ * mnLoopWords / mLoopScore are not reproduced). */
+typedef struct ccm_kfdb ccm_kfdb;
+/* log_capacity: keyframes added after the last rebuild of the device inverted file that are scanned directly (0: 64) */
+int  ccm_kfdb_create(ccm_ctx* ctx, int n_words, int log_capacity, ccm_kfdb** out);
+void ccm_kfdb_destroy(ccm_kfdb* db);
+/* KeyFrameDatabase::add (:37-43); a live key added twice: CCM_E_STATE (the reference never does it) */
+int  ccm_kfdb_add(ccm_kfdb* db, ccm_ctx* ctx, int64_t key, int32_t group, int n, const int32_t* word, const double* value);
+/* KeyFrameDatabase::erase (:45-64); an unknown key is a no-op, as there */
+int  ccm_kfdb_erase(ccm_kfdb* db, ccm_ctx* ctx, int64_t key);
+/* KeyFrameDatabase::clear (:66-70) */
+int  ccm_kfdb_clear(ccm_kfdb* db, ccm_ctx* ctx);
+/* Exclusions of phase 1.  DetectLoopCandidates: self_key = the query (pKFi->mId == pKF->mId), allow = GetMmpKeyFrames() of its map, exclude =
+ * GetConnectedKeyFrames().  DetectMapMatchCandidates: exclude_groups = bit c set for every client id c in pMap->msuAssClients (ids >= 64 are
+ * never excluded).  DetectRelocalizationCandidates: none (f = NULL). */
+typedef struct {
+  int64_t self_key;                          /* -1: none */
+  const int64_t* allow; int n_allow;         /* NULL: every keyframe */
+  const int64_t* exclude; int n_exclude;
+  uint64_t exclude_groups;
+} ccm_kfdb_filter;
+/* Phase 1 of one query: the keyframes of lKFsSharingWords with count > minCommonWords, in that list's order, with their shared-word count and
+ * score (f32 as the reference's `float si`, and the f64 it was rounded from).  Writes min(*n_out, cap) rows; *n_out = rows of the full table
+ * (call again with cap >= *n_out if it was larger); n_sharing = size of lKFsSharingWords, max_common = maxCommonWords, generation = number of
+ * mutations the query saw.  Empty database or no shared word: *n_out = 0.  Output pointers after n_out are nullable. */
+int  ccm_kfdb_query(ccm_kfdb* db, ccm_ctx* ctx, int n, const int32_t* word, const double* value, const ccm_kfdb_filter* f,
+                    int cap, int64_t* key_out, int32_t* count_out, float* score_out, double* score64_out,
+                    int* n_out, int* n_sharing_out, int* max_common_out, uint64_t* generation_out);
+/* mpVoc->score(q, kf) in f64 for m listed keys (LoopFinder.cpp:124-137); a key that is not in the database: CCM_E_ARG */
+int  ccm_kfdb_score(ccm_kfdb* db, ccm_ctx* ctx, int n, const int32_t* word, const double* value,
+                    const int64_t* keys, int m, double* out);
+
 #ifdef __cplusplus
 }
 #endif
