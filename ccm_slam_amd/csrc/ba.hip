@@ -1386,7 +1386,9 @@ struct PersArgs {
   unsigned* bar;        // [1] abort flag
   int test_abort;              // CCM_BA_TEST_ABORT: the last workgroup leaves at once (exercises the abort -> multi-kernel fallback)
   const int* coff; const int* cij; const uint32_t* cblk;   // per cluster: entries inside its own 16x16 block (local row << 4 | column, S block)
-  unsigned long long* slots;   // [2][2][grid]: p.q exchange, r.z exchange (word-major 16-byte slots)
+  unsigned long long* slots;   // [2][3][grid]: the exchanges alternate between two slot sets (epoch parity), word-major 24-byte slots
+  unsigned long long* utag;    // [6 Cp][2]: u of every unknown as {bits, bits ^ key(epoch)} (the halo exchange validates itself)
+  double* wbuf[2];             // [6 Cp] each: w = (S + lambda I) u of the own rows for the partner unit, by epoch parity
   unsigned long long epoch_base;   // unique per launch: stale slots of earlier solves never validate
   const int* uoff;      // [n_clu+1] offsets into ucol
   const int* ucol;      // distinct columns of each cluster's rows, ascending
@@ -1394,7 +1396,7 @@ struct PersArgs {
   long long* dbg;       // optional [16] phase clocks of workgroup 0 (wall_clock64 ticks, 10 ns), accumulated over iterations
   // coarse level (nullptr = cluster-Jacobi only): explicit inverse [Nc x Nc], prolongation blocks [Cp][36], aggregates
   const double* Ainv; const double* Pm; int na, Nc;   // na camera intervals, na + 1 coarse nodes
-  double* cparts;              // [12][grid]: the units' parts of the coarse restriction P^T q (6 for the first node of the unit's interval, 6 for the second), component-major; exchanged like p, q and z
+  double* cparts;              // [2][12][grid]: the units' parts of the coarse restriction P^T w (6 for the first node of the unit's interval, 6 for the second), component-major, by epoch parity
   // the cluster inverse across trials (round 4): [grid][96 * 48] the unit's own 48 rows of W, transposed, as the kernel keeps them in LDS.  w_load != 0: this
   // launch takes them from here instead of assembling and factoring the cluster block (a stale W — another lambda, an earlier linearisation — is still a
   // symmetric positive definite block-Jacobi preconditioner: PCG stays exact, only the iteration count moves; the host decides, lm_trial)
@@ -1411,44 +1413,46 @@ __device__ __forceinline__ double pers_uniform(double v) {
 __device__ __forceinline__ double coh_load(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void coh_store(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// Grid-wide "barrier + deterministic sum" in one step, without atomics (256 arrivals on one counter serialise at the
-// memory side: measured 6 us per barrier): every workgroup publishes its partial in its own 16-byte slot as
-// {bits(value), bits(value) ^ key(epoch)} and then polls ALL slots (one per thread) until every slot validates against
-// the current epoch's key; the xor check also rejects torn 16-byte reads.  The values are then summed in a fixed order,
-// so every workgroup obtains bit-identical totals.  All cross-workgroup data (z, p, q, slots) moves with device-coherent
-// accesses, so the only ordering needed is: drain this workgroup's stores, meet, publish.
-__device__ __forceinline__ bool pers_exchange(int t /* threadIdx.x */, unsigned long long* slots /* [2][nwg] */, int nwg, int me, double v_thread, bool force_nan,
-                                              unsigned long long epoch, unsigned* abort_flag, double* red /* [kPersWaves + 4] */,
-                                              double* total, int* poll_fail /* LDS, sticky: an aborted exchange ends the solve */) {
-  // v_thread: this thread's share of the unit's partial.  The unit sum, the publish and the grid-wide sum share two block
-  // barriers: wave sums -> LDS, (drain stores, barrier), thread 0 adds the 16 wave sums in a fixed order and publishes,
-  // wave 0 polls (lane = source units t, t+64, ...; nwg <= 256), (barrier), everybody reads the grid total.
-  // The slot words are stored WORD-MAJOR (word w of unit i at slots[w * nwg + i]) so that a wave's load of one word is
-  // 512 contiguous bytes.  Variants measured and dropped: polling with 4 or 16 waves (slows the units still computing),
-  // wide slots that also carried the coarse components (8-12 us per exchange; they now travel like p, q and z), and
-  // pushing the value into per-unit inboxes (64K scattered write-through stores per exchange).
+// Grid-wide "barrier + deterministic sum" of TWO values in one step, without atomics (256 arrivals on one counter
+// serialise at the memory side: measured 6 us per barrier): every workgroup publishes its partials (a, b) in its own
+// 24-byte slot as {bits(a), bits(b), bits(a) ^ bits(b) ^ key(epoch)} and then polls ALL slots (one per thread) until
+// every slot validates against the current epoch's key; the xor check also rejects torn reads.  The values are then
+// summed in a fixed order, so every workgroup obtains bit-identical totals.  All cross-workgroup data (u, w, slots,
+// coarse parts) moves with device-coherent accesses, so the only ordering needed is: drain this workgroup's stores,
+// meet, publish.
+__device__ __forceinline__ bool pers_exchange(int t /* threadIdx.x */, unsigned long long* slots /* [3][nwg] */, int nwg, int me, double a_thread, double b_thread,
+                                              bool force_nan, unsigned long long epoch, unsigned* abort_flag, double* red /* [2 kPersWaves + 4] */,
+                                              double* total_a, double* total_b, int* poll_fail /* LDS, sticky: an aborted exchange ends the solve */) {
+  // a_thread, b_thread: this thread's shares of the unit's partials.  The unit sums, the publish and the grid-wide sums
+  // share two block barriers: wave sums -> LDS, (drain stores, barrier), thread 0 adds the 16 wave sums of each value in
+  // a fixed order and publishes, wave 0 polls (lane = source units t, t+64, ...; nwg <= 256), (barrier), everybody reads
+  // the grid totals.  The slot words are stored WORD-MAJOR (word w of unit i at slots[w * nwg + i]) so that a wave's load
+  // of one word is 512 contiguous bytes.  Variants measured and dropped: polling with 4 or 16 waves (slows the units
+  // still computing), wide slots that also carried the coarse components (8-12 us per exchange; they travel like u and
+  // w), and pushing the value into per-unit inboxes (64K scattered write-through stores per exchange).
   const unsigned long long key = 0x9E3779B97F4A7C15ull * epoch;
   {
-    const double ws = wave_sum(v_thread);
-    if ((t & (kWave - 1)) == 0) red[t / kWave] = ws;
+    const double wa = wave_sum(a_thread), wb = wave_sum(b_thread);
+    if ((t & (kWave - 1)) == 0) { red[t / kWave] = wa; red[kPersWaves + t / kWave] = wb; }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (t == 0) {
-    double mine = 0;
+    double ma = 0, mb = 0;
 #pragma unroll
-    for (int w = 0; w < kPersWaves; w++) mine += red[w];
-    if (force_nan) mine = __longlong_as_double(0x7ff8000000000000ll);
-    const unsigned long long bits = (unsigned long long)__double_as_longlong(mine);
-    __hip_atomic_store(slots + me, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(slots + nwg + me, bits ^ key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (int w = 0; w < kPersWaves; w++) { ma += red[w]; mb += red[kPersWaves + w]; }
+    if (force_nan) ma = __longlong_as_double(0x7ff8000000000000ll);
+    const unsigned long long ba = (unsigned long long)__double_as_longlong(ma), bb = (unsigned long long)__double_as_longlong(mb);
+    __hip_atomic_store(slots + me, ba, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(slots + nwg + me, bb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(slots + 2 * nwg + me, ba ^ bb ^ key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   if (t < kWave) {
     constexpr int kPer = 4;    // slots per lane
     unsigned done = 0;
-    double val[kPer];
+    double va[kPer], vb[kPer];
 #pragma unroll
-    for (int j = 0; j < kPer; j++) { val[j] = 0; if (t + j * kWave >= nwg) done |= 1u << j; }
+    for (int j = 0; j < kPer; j++) { va[j] = 0; vb[j] = 0; if (t + j * kWave >= nwg) done |= 1u << j; }
     bool ok_w = true;
     // (measured and dropped, round 3: a second poll request ~0.25 us behind the first so that an incomplete first answer does not cost a whole further round
     // trip: the per-unit time inside an exchange went from 3.4 to 4.1-4.4 us — twice the polling traffic on the slot lines slows every answer down)
@@ -1459,22 +1463,25 @@ __device__ __forceinline__ bool pers_exchange(int t /* threadIdx.x */, unsigned 
         const unsigned long long* in = slots + t + j * kWave;
         const unsigned long long b0 = __hip_atomic_load(in, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const unsigned long long b1 = __hip_atomic_load(in + nwg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((b0 ^ b1) == key) { done |= 1u << j; val[j] = __longlong_as_double((long long)b0); }
+        const unsigned long long b2 = __hip_atomic_load(in + 2 * nwg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if ((b0 ^ b1 ^ b2) == key) { done |= 1u << j; va[j] = __longlong_as_double((long long)b0); vb[j] = __longlong_as_double((long long)b1); }
       }
       if (__all(done == (1u << kPer) - 1u)) break;
       if (spins > kPersMaxSpins || __hip_atomic_load(abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) { ok_w = false; break; }
       __builtin_amdgcn_s_sleep(2);
     }
-    const double v = wave_sum(((val[0] + val[1]) + val[2]) + val[3]);
+    const double sa = wave_sum(((va[0] + va[1]) + va[2]) + va[3]);
+    const double sb = wave_sum(((vb[0] + vb[1]) + vb[2]) + vb[3]);
     if (t == 0) {
-      red[kPersWaves] = v;
+      red[2 * kPersWaves] = sa; red[2 * kPersWaves + 1] = sb;
       if (!ok_w) { *poll_fail = 1; __hip_atomic_store(abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
     }
   }
   __syncthreads();
   const bool alive = *poll_fail == 0;
-  *total = pers_uniform(red[kPersWaves]);
-  // no trailing barrier: red[0..15] is rewritten only after every thread has passed the barrier above, red[16] only
+  *total_a = pers_uniform(red[2 * kPersWaves]);
+  *total_b = pers_uniform(red[2 * kPersWaves + 1]);
+  // no trailing barrier: red[0..31] is rewritten only after every thread has passed the barrier above, red[32..33] only
   // after the first barrier of the next exchange
   return alive;
 }
@@ -2200,22 +2207,24 @@ __global__ __launch_bounds__(kPersTPB) void ba_pcg_persist(BaDev d, PersArgs a) 
   constexpr int N = kCluN;
   double* A = sm;                          // [96][96]: dense cluster block -> Cholesky factor -> W = inverse
   double* Li = sm + N * N;                 // [96][96]: inverse factor during init, then staged structure + neighbour p
-  double* rc = Li + N * N;                 // r of the own rows
-  double* xs = rc + N;                     // x
-  double* ps = xs + N;                     // p
-  double* qs = ps + N;                     // q
-  double* zs = qs + N;                     // z
-  double* zpart = zs + N;                  // [8][96]
-  double* red = zpart + 8 * N;             // [16]
-  int* ibuf = reinterpret_cast<int*>(red + kPersWaves + 4);   // [0]=ok flag of the barrier, [1]=bad pivot
+  double* rc = Li + N * N;                 // r of the cluster
+  double* xs = rc + N;                     // x (own rows)
+  double* ps = xs + N / 2;                 // p (own rows)
+  double* ss = ps + N / 2;                 // s = (S + lambda I) p of the cluster
+  double* zs = ss + N;                     // u = M^-1 r (own rows)
+  double* zpart = zs + N;                  // [8][96]: the column parts of W r ([0, 4N)); w of the own rows at [4N, 4N + 48)
+  double* wl = zpart + 4 * N;
+  double* pso = zpart + 8 * N;             // [kPersNcCap]: P^T s
+  double* red = pso + kPersNcCap;          // [2 * 16 + 4]
+  int* ibuf = reinterpret_cast<int*>(red + 2 * kPersWaves + 4);   // [0]=ok flag of the barrier, [1]=bad pivot
   if (a.test_abort && blockIdx.x == gridDim.x - 1) return;
   const int t = threadIdx.x, lane = t & (kWave - 1);
   const int wv = __builtin_amdgcn_readfirstlane(t / kWave);
   const int nwg = gridDim.x;               // padded to a multiple of 8
   const int per_xcd = nwg >> 3;
-  // TWO workgroups per cluster: unit u owns rows [8u, 8u+8) (x, p, q, z of those rows and their S blocks in registers);
-  // both units of a cluster factor the same 96x96 block redundantly and keep the full r of the cluster, so the only
-  // extra exchange is the partner's q (48 values) after the first barrier.
+  // TWO workgroups per cluster: unit u owns rows [8u, 8u+8) (x, p, u, w of those rows and their S blocks in registers);
+  // both units of a cluster factor the same 96x96 block redundantly and keep the full r and s of the cluster, so the
+  // only extra data is the partner's w (48 values) after the exchange.
   const int u = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
   const int c = u >> 1, hu = u & 1;
   const bool has = c < a.n_clu;
@@ -2226,8 +2235,6 @@ __global__ __launch_bounds__(kPersTPB) void ba_pcg_persist(BaDev d, PersArgs a) 
   const int nown = o1 - o0;
   const int mo = 6 * nown;                 // own unknowns
   const int ob = 6 * (o0 - s0);            // their offset inside the cluster vectors
-  unsigned long long* slots_pq = a.slots;
-  unsigned long long* slots_rz = a.slots + 2 * (size_t)nwg;
   unsigned long long epoch = a.epoch_base;
   const double lambda = a.lambda;
   if (t < 4) ibuf[t] = (t == 0) ? 1 : 0;   // [2] = exchange failure flag
@@ -2264,7 +2271,7 @@ __global__ __launch_bounds__(kPersTPB) void ba_pcg_persist(BaDev d, PersArgs a) 
   double* rco = Li + (32 + 2 * kPersIdxCap + kPersColCap) / 2 + 6 * kPersColCap + 256;   // [Nc]
   double* pown = rco + Nc;                   // [8][36]
   double* ypart = pown + 8 * 36;             // [12]
-  static_assert((32 + 2 * kPersIdxCap + kPersColCap) % 2 == 0 && (32 + 2 * kPersIdxCap + kPersColCap) / 2 + 6 * kPersColCap + 256 + 768 + 8 * 36 + 12 <= kCluN * kCluN,
+  static_assert((32 + 2 * kPersIdxCap + kPersColCap) % 2 == 0 && (32 + 2 * kPersIdxCap + kPersColCap) / 2 + 6 * kPersColCap + 256 + kPersNcCap + 8 * 36 + 12 <= kCluN * kCluN,
                 "coarse vectors do not fit behind the staged structure");
   const int aggu = d.agg >> 3;               // units per interval (an interval is a multiple of the 8 cameras of a unit)
   const int agg = u / aggu;                  // interval of the unit's cameras: nodes agg and agg + 1
@@ -2277,7 +2284,7 @@ __global__ __launch_bounds__(kPersTPB) void ba_pcg_persist(BaDev d, PersArgs a) 
 #pragma unroll
       for (int q = 0; q < 9; q++) { const int e = t + q * kPersTPB; if (e < 12 * Nc) ainv_l[e] = (float)tmpa[q]; }
     }
-    for (int e = t; e < Nc; e += kPersTPB) rco[e] = 0.0;
+    for (int e = t; e < Nc; e += kPersTPB) { rco[e] = 0.0; pso[e] = 0.0; }
     for (int e = t; e < 8 * 36; e += kPersTPB) pown[e] = (e / 36 < nown) ? a.Pm[36 * (size_t)o0 + e] : 0.0;
   }
   __syncthreads();
@@ -2289,7 +2296,7 @@ __global__ __launch_bounds__(kPersTPB) void ba_pcg_persist(BaDev d, PersArgs a) 
   // unit part of the coarse restriction P^T v for the own rows: wave 0, lane = (component c, camera k); the 8 camera
   // terms of a component sit in 8 neighbouring lanes; every camera's term goes with weight 1 - t to the first node of the unit's interval and with t
   // to the second.  Published component-major for the other units.
-  auto coarse_restrict = [&](const double* vec /* LDS, own 48 entries */) {
+  auto coarse_restrict = [&](const double* vec /* LDS, own 48 entries */, double* cpo /* the parts buffer of the coming exchange */) {
     if (wv == 0) {
       const int cc = lq >> 3, kk = lq & 7;
       double sv = 0;
@@ -2302,17 +2309,17 @@ __global__ __launch_bounds__(kPersTPB) void ba_pcg_persist(BaDev d, PersArgs a) 
       s0v = lanex::add_partner<1>(s0v); s1v = lanex::add_partner<1>(s1v);
       s0v = lanex::add_partner<2>(s0v); s1v = lanex::add_partner<2>(s1v);
       s0v = lanex::add_partner<4>(s0v); s1v = lanex::add_partner<4>(s1v);
-      if (cc < 6 && kk == 0) { coh_store(a.cparts + (size_t)cc * nwg + u, s0v); coh_store(a.cparts + (size_t)(6 + cc) * nwg + u, s1v); }
+      if (cc < 6 && kk == 0) { coh_store(cpo + (size_t)cc * nwg + u, s0v); coh_store(cpo + (size_t)(6 + cc) * nwg + u, s1v); }
     }
   };
   // component tq % 6 of node tq / 6: the first-node parts of the 4 units of interval n plus the second-node parts of the 4 units of interval n - 1
   // (valid after the exchange that follows coarse_restrict)
-  auto coarse_gather = [&]() {
+  auto coarse_gather = [&](const double* cpi /* the parts buffer of the exchange just passed */) {
     double sgm = 0;
     if (coarse && tq < nca) {
       const int n = tq / 6, cc = tq % 6;
-      const double* c0 = a.cparts + (size_t)cc * nwg + aggu * n;
-      const double* c1 = a.cparts + (size_t)(6 + cc) * nwg + aggu * (n - 1);
+      const double* c0 = cpi + (size_t)cc * nwg + aggu * n;
+      const double* c1 = cpi + (size_t)(6 + cc) * nwg + aggu * (n - 1);
       for (int mm = 0; mm < aggu; mm++) {
         if (n < a.na && aggu * n + mm < nwg) sgm += coh_load(c0 + mm);
         if (n >= 1 && aggu * (n - 1) + mm < nwg) sgm += coh_load(c1 + mm);
@@ -2320,8 +2327,9 @@ __global__ __launch_bounds__(kPersTPB) void ba_pcg_persist(BaDev d, PersArgs a) 
     }
     return sgm;
   };
-  // PCG start: x = 0, r = bs, z = W r, p_{-1} = 0
-  if (t < N) { xs[t] = 0; ps[t] = 0; qs[t] = 0; zs[t] = 0; rc[t] = (t < m) ? d.bs[6 * (size_t)s0 + t] : 0.0; }   // xs/ps/zs: own rows; rc/qs: cluster
+  // PCG start: x = 0, r = bs, p_{-1} = s_{-1} = 0, P^T s_{-1} = 0
+  if (t < N / 2) { xs[t] = 0; ps[t] = 0; }   // own rows
+  if (t < N) { ss[t] = 0; zs[t] = 0; rc[t] = (t < m) ? d.bs[6 * (size_t)s0 + t] : 0.0; }   // rc/ss: cluster
   __syncthreads();
   PERS_TICK(10)
   // the Li region is dead now: off[32] | loc[kPersIdxCap] | blk[kPersIdxCap] | ucol[kPersColCap] ints, then p of the
@@ -2367,7 +2375,7 @@ __global__ __launch_bounds__(kPersTPB) void ba_pcg_persist(BaDev d, PersArgs a) 
       for (int q = 0; q < 6; q++) sreg[k][q] = v ? ((bt & kTransposeBit) ? B[q * 6 + r] : B[r * 6 + q]) : 0.0;
     }
   }
-  auto apply_W = [&]() {          // z(own rows) = W[own rows, :] rc (+ coarse correction); publishes them; returns this thread's share of r.z
+  auto apply_W = [&](unsigned long long ukey) {   // u(own rows) = W[own rows, :] rc (+ coarse correction); publishes them tagged with ukey; returns this thread's share of r.u
     {
       const int row = tq % (N / 2), prt = tq / (N / 2);       // 48 rows x 8 column parts (12 columns each) = waves 0..5
       if (prt < 8) {
@@ -2400,116 +2408,159 @@ __global__ __launch_bounds__(kPersTPB) void ba_pcg_persist(BaDev d, PersArgs a) 
         for (int cc = 0; cc < 6; cc++) z += pown[kk * 36 + rr * 6 + cc] * (w0 * ypart[cc] + w1 * ypart[6 + cc]);
       }
       zs[tq] = z;
-      coh_store(d.z + 6 * (size_t)o0 + tq, z);
+      const unsigned long long zb = (unsigned long long)__double_as_longlong(z);
+      unsigned long long* dst = a.utag + 2 * (6 * (size_t)o0 + tq);
+      __hip_atomic_store(dst, zb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(dst + 1, zb ^ ukey, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       rz = rc[ob + tq] * z;
     }
     return rz;
   };
+  // ---- halo exchange: u of every neighbour column into LDS.  No grid barrier orders these reads: every value carries its
+  // own check ({bits, bits ^ key}, key of the exchange that follows) and only the entries that do not validate yet are
+  // read again.  ONE buffer for u is enough: a unit publishes u for exchange e + 1 only after it has passed exchange e,
+  // and every neighbour finished reading u of exchange e before it took part in exchange e (its halo load precedes its
+  // publish there).  The spin is bounded and watches the abort flag like pers_exchange's, so a missing workgroup still
+  // ends the solve (pcg_flag[3], multi-kernel retry).  Returns false (grid-wide abort raised) when it gave up.
+  auto halo_load = [&](unsigned long long ukey) {
+    constexpr int kPer = (6 * kPersColCap + kPersTPB - 1) / kPersTPB;   // values per thread
+    unsigned done = 0;
+#pragma unroll
+    for (int i = 0; i < kPer; i++) if (tq + i * kPersTPB >= 6 * nu) done |= 1u << i;
+    bool ok = true;
+    for (long spins = 0; done != (1u << kPer) - 1u; spins++) {
+#pragma unroll
+      for (int i = 0; i < kPer; i++) {
+        if (done & (1u << i)) continue;
+        const int idx = tq + i * kPersTPB;
+        const unsigned long long* src = a.utag + 2 * (6 * (size_t)l_ucol[idx / 6] + idx % 6);
+        const unsigned long long b0 = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned long long b1 = __hip_atomic_load(src + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if ((b0 ^ b1) == ukey) { done |= 1u << i; pl[idx] = __longlong_as_double((long long)b0); }
+      }
+      if (done == (1u << kPer) - 1u) break;
+      if (spins > kPersMaxSpins || __hip_atomic_load(a.bar + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) { ok = false; break; }
+      __builtin_amdgcn_s_sleep(1);
+    }
+    if (!ok) { ibuf[2] = 1; __hip_atomic_store(a.bar + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+    __syncthreads();
+    return ibuf[2] == 0;
+  };
+  // ---- w = (S + lambda I) u for the own rows: registers x LDS; publishes w for the partner unit; stores this thread's
+  // share of (w, u) in *wu ----
+  auto spmv_w = [&](double* wdst, double* wu) {
+    double acc = 0;
+#pragma unroll
+    for (int kk = 0; kk < kPersRegEnt; kk++) {
+      // tie the entry's LDS address to the running sum: left alone, the compiler hoists all 30 u loads (60 VGPRs) above
+      // the first multiply and pushes half of the S registers into scratch; the other three waves of the SIMD cover
+      // the LDS latency of one entry at a time
+      int jo = jreg[kk];
+      asm volatile("" : "+v"(jo), "+v"(acc));
+      const double* pj = pl + jo;
+#pragma unroll
+      for (int q = 0; q < 6; q++) acc += sreg[kk][q] * pj[q];
+    }
+    {   // tail of very long rows (bounds re-read from LDS: two broadcast loads instead of two live registers)
+      const int gq = lq / 6, rq = lq - 6 * gq;
+      const bool rowq = has && row_l < nown && gq < 10;
+      const int e_endq = rowq ? l_off[row_l + 1] : 0;
+      for (int s = (rowq ? l_off[row_l] : 0) + half * 10 + gq + 20 * kPersRegEnt; s < e_endq; s += 20) {
+        const uint32_t bt = l_blk[s];
+        const double* B = d.S + 36 * (size_t)(bt & ~kTransposeBit);
+        const double* pj = pl + 6 * l_loc[s];
+#pragma unroll
+        for (int q = 0; q < 6; q++) acc += ((bt & kTransposeBit) ? B[q * 6 + rq] : B[rq * 6 + q]) * pj[q];
+      }
+    }
+    acc += __shfl_down(acc, 30, kWave);                    // groups g and g + 5
+    const double pr = acc + __shfl_down(acc, 6, kWave);     // (0,1) at g = 0, (2,3) at g = 2
+    acc = (pr + __shfl_down(pr, 12, kWave)) + __shfl_down(acc, 24, kWave);
+    if (lq < 6) half_sum[(row_l * 2 + half) * 8 + lq] = acc;
+    __syncthreads();
+    double wu_t = 0;
+    if (tq < mo) {
+      const int rw = tq / 6, cc = tq % 6;
+      const double ui = zs[tq];
+      const double wv_ = (half_sum[(rw * 2) * 8 + cc] + half_sum[(rw * 2 + 1) * 8 + cc]) + lambda * ui;
+      wl[tq] = wv_;
+      coh_store(wdst + 6 * (size_t)o0 + tq, wv_);     // the partner unit needs it for its copy of s and r
+      wu_t = wv_ * ui;
+    }
+    *wu = wu_t;
+  };
+  // Preconditioned CG in the Chronopoulos-Gear form: ONE grid-wide exchange per iteration, carrying gamma = (r, u) and
+  // delta = (w, u) with u = M^-1 r, w = (S + lambda I) u; p and s = (S + lambda I) p follow by recurrence, and so does
+  // the coarse residual P^T r (P^T s = P^T w + beta P^T s).  Exchanges alternate between two slot sets, two coarse-part
+  // buffers and two w buffers by epoch parity: a unit writes those of exchange e + 2 only after it has passed exchange
+  // e + 1, which every reader of exchange e's data joined after its reads.
+  const size_t cstride = 12 * (size_t)nwg;
+  auto slots_of = [&](unsigned long long e) { return a.slots + 3 * (size_t)nwg * (e & 1); };
+  auto cparts_of = [&](unsigned long long e) { return a.cparts + cstride * (e & 1); };
+  auto key_of = [](unsigned long long e) { return 0x9E3779B97F4A7C15ull * e; };
   int fail = 0, k = 0;
-  double rz = 0;
+  double gam = 0, del = 0;
   bool alive = true;
   if (coarse) {   // coarse residual of r0 = b: one extra exchange before the first preconditioner application
-    coarse_restrict(rc + ob);
-    double dummy = 0;
-    alive = pers_exchange(tq, slots_rz, nwg, u, 0.0, false, ++epoch, a.bar + 1, red, &dummy, ibuf + 2);
-    const double cg0 = coarse_gather();
+    coarse_restrict(rc + ob, cparts_of(epoch + 1));
+    double dummy = 0, dummy2 = 0;
+    alive = pers_exchange(tq, slots_of(epoch + 1), nwg, u, 0.0, 0.0, false, epoch + 1, a.bar + 1, red, &dummy, &dummy2, ibuf + 2);
+    ++epoch;
+    const double cg0 = coarse_gather(cparts_of(epoch));
     if (t < nca) rco[t] += cg0;
     __syncthreads();
   }
-  {
-    const double rz_t = apply_W();
-    if (t < mo) coh_store(d.p[0] + 6 * (size_t)o0 + t, 0.0);
-    const bool alive2 = pers_exchange(tq, slots_rz, nwg, u, rz_t, has && ibuf[1], ++epoch, a.bar + 1, red, &rz, ibuf + 2);   // bad pivot -> NaN -> grid-wide failure
+  if (alive) {   // u0 = M^-1 r0, w0 = (S + lambda I) u0, gamma0, delta0
+    const double ru_t = apply_W(key_of(epoch + 1));
+    alive = halo_load(key_of(epoch + 1));
+    double wu_t = 0;
+    spmv_w(a.wbuf[(epoch + 1) & 1], &wu_t);
+    if (coarse) { __syncthreads(); coarse_restrict(wl, cparts_of(epoch + 1)); }
+    const bool alive2 = pers_exchange(tq, slots_of(epoch + 1), nwg, u, ru_t, wu_t, has && ibuf[1], epoch + 1, a.bar + 1, red, &gam, &del, ibuf + 2);   // bad pivot -> NaN -> grid-wide failure
+    ++epoch;
     alive = alive && alive2;
   }
-  const double rz0 = rz;
+  const double gam0 = gam;
   const double thresh = a.rel_tol * a.rel_tol;
-  double rz_prev = rz;
+  double gam_prev = gam, alpha_prev = 1.0;
   if (!alive) fail = 1;
   PERS_TICK(11)
   for (; alive && k < a.max_it; k++) {
     tq = t; asm volatile("" : "+v"(tq)); lq = tq & (kWave - 1);
-    if (rz <= thresh * rz0 || !(rz > 0.0)) { if (rz != rz) fail = 1; break; }
-    const double beta = pers_uniform((k == 0) ? 0.0 : rz / rz_prev);
-    const double* pold = d.p[k & 1];
-    double* pnew = d.p[(k + 1) & 1];
-    // ---- p = z + beta p_old of every neighbour column, once, into LDS ----
-    for (int idx = tq; idx < 6 * nu; idx += kPersTPB) {
-      const int j = l_ucol[idx / 6], q = idx % 6;
-      pl[idx] = coh_load(d.z + 6 * (size_t)j + q) + beta * coh_load(pold + 6 * (size_t)j + q);
+    if (gam <= thresh * gam0 || !(gam > 0.0)) { if (gam != gam) fail = 1; break; }
+    const double beta = pers_uniform((k == 0) ? 0.0 : gam / gam_prev);
+    const double pap = (k == 0) ? del : del - beta * gam / alpha_prev;   // = p^T (S + lambda I) p
+    if (!(pap > 0.0)) { fail = 1; break; }   // not positive definite (or NaN): solver failure -> LM rejects the step
+    const double alpha = pers_uniform(gam / pap);
+    // ---- p = u + beta p, s = w + beta s, x += alpha p, r -= alpha s, P^T s = P^T w + beta P^T s, P^T r -= alpha P^T s ----
+    {
+      const double w_partner = (tq < m && !(tq >= ob && tq < ob + mo)) ? coh_load(a.wbuf[epoch & 1] + 6 * (size_t)s0 + tq) : 0.0;
+      const double cg = coarse_gather(cparts_of(epoch));       // P^T w of every aggregate
+      if (tq < mo) { const double pi = zs[tq] + beta * ps[tq]; ps[tq] = pi; xs[tq] += alpha * pi; }
+      if (tq < m) { const double si = ((tq >= ob && tq < ob + mo) ? wl[tq - ob] : w_partner) + beta * ss[tq]; ss[tq] = si; rc[tq] -= alpha * si; }
+      if (coarse && tq < nca) { const double sc = cg + beta * pso[tq]; pso[tq] = sc; rco[tq] -= alpha * sc; }
     }
     __syncthreads();
     PERS_TICK(0)
-    // ---- q = (S + lambda I) p for the own rows: registers x LDS ----
-    {
-      double acc = 0;
-#pragma unroll
-      for (int kk = 0; kk < kPersRegEnt; kk++) {
-        // tie the entry's LDS address to the running sum: left alone, the compiler hoists all 30 p loads (60 VGPRs) above
-        // the first multiply and pushes half of the S registers into scratch; the other three waves of the SIMD cover
-        // the LDS latency of one entry at a time
-        int jo = jreg[kk];
-        asm volatile("" : "+v"(jo), "+v"(acc));
-        const double* pj = pl + jo;
-#pragma unroll
-        for (int q = 0; q < 6; q++) acc += sreg[kk][q] * pj[q];
-      }
-      {   // tail of very long rows (bounds re-read from LDS: two broadcast loads instead of two live registers)
-        const int gq = lq / 6, rq = lq - 6 * gq;
-        const bool rowq = has && row_l < nown && gq < 10;
-        const int e_endq = rowq ? l_off[row_l + 1] : 0;
-        for (int s = (rowq ? l_off[row_l] : 0) + half * 10 + gq + 20 * kPersRegEnt; s < e_endq; s += 20) {
-          const uint32_t bt = l_blk[s];
-          const double* B = d.S + 36 * (size_t)(bt & ~kTransposeBit);
-          const double* pj = pl + 6 * l_loc[s];
-#pragma unroll
-          for (int q = 0; q < 6; q++) acc += ((bt & kTransposeBit) ? B[q * 6 + rq] : B[rq * 6 + q]) * pj[q];
-        }
-      }
-      acc += __shfl_down(acc, 30, kWave);                    // groups g and g + 5
-      const double pr = acc + __shfl_down(acc, 6, kWave);     // (0,1) at g = 0, (2,3) at g = 2
-      acc = (pr + __shfl_down(pr, 12, kWave)) + __shfl_down(acc, 24, kWave);
-      if (lq < 6) half_sum[(row_l * 2 + half) * 8 + lq] = acc;
-    }
-    __syncthreads();
-    double pq_t = 0;
-    if (tq < mo) {
-      const int rw = tq / 6, cc = tq % 6;
-      const double pi = zs[tq] + beta * ps[tq];
-      const double qv = (half_sum[(rw * 2) * 8 + cc] + half_sum[(rw * 2 + 1) * 8 + cc]) + lambda * pi;
-      ps[tq] = pi;
-      qs[ob + tq] = qv;
-      coh_store(pnew + 6 * (size_t)o0 + tq, pi);
-      coh_store(d.q + 6 * (size_t)o0 + tq, qv);     // the partner unit needs it for its copy of r
-      pq_t = pi * qv;
-    }
-    if (coarse) { __syncthreads(); coarse_restrict(qs + ob); }
+    const double ru_t = apply_W(key_of(epoch + 1));
     PERS_TICK(1)
-    double pq = 0;
     long long tw0 = 0;
     if (a.dbg && t == 0) tw0 = wall_clock64();
-    alive = pers_exchange(tq, slots_pq, nwg, u, pq_t, false, ++epoch, a.bar + 1, red, &pq, ibuf + 2);
-    if (a.dbg && t == 0) a.dbg[32 + 2 * u] += wall_clock64() - tw0;   // per unit: time inside exchange 1 (its own wait for the slowest unit + the exchange latency)
+    alive = halo_load(key_of(epoch + 1));
+    if (a.dbg && t == 0) a.dbg[33 + 2 * u] += wall_clock64() - tw0;   // per unit: halo wait (own u published -> every neighbour's u in LDS)
     PERS_TICK(2)
     if (!alive) { fail = 1; break; }
-    const double q_partner = (tq < m && !(tq >= ob && tq < ob + mo)) ? coh_load(d.q + 6 * (size_t)s0 + tq) : 0.0;
-    const double cg = coarse_gather();       // P^T q of every aggregate
-    if (!(pq > 0.0)) { fail = 1; break; }   // not positive definite (or NaN): solver failure -> LM rejects the step
+    double wu_t = 0;
+    spmv_w(a.wbuf[(epoch + 1) & 1], &wu_t);
+    if (coarse) { __syncthreads(); coarse_restrict(wl, cparts_of(epoch + 1)); }
     PERS_TICK(3)
-    const double alpha = pers_uniform(rz / pq);
-    if (tq < mo) xs[tq] += alpha * ps[tq];
-    if (tq < m) rc[tq] -= alpha * ((tq >= ob && tq < ob + mo) ? qs[tq] : q_partner);
-    if (coarse && tq < nca) rco[tq] -= alpha * cg;  // P^T r follows the recurrence of r: no second gather per iteration
-    __syncthreads();
-    const double rz_t2 = apply_W();
-    PERS_TICK(4)
-    rz_prev = rz;
+    gam_prev = gam; alpha_prev = alpha;
     if (a.dbg && t == 0) tw0 = wall_clock64();
-    alive = pers_exchange(tq, slots_rz, nwg, u, rz_t2, false, ++epoch, a.bar + 1, red, &rz, ibuf + 2);
-    if (a.dbg && t == 0) a.dbg[33 + 2 * u] += wall_clock64() - tw0;
-    PERS_TICK(5)
+    alive = pers_exchange(tq, slots_of(epoch + 1), nwg, u, ru_t, wu_t, false, epoch + 1, a.bar + 1, red, &gam, &del, ibuf + 2);
+    ++epoch;
+    if (a.dbg && t == 0) a.dbg[32 + 2 * u] += wall_clock64() - tw0;   // per unit: time inside the exchange (its own wait for the slowest unit + the exchange latency)
+    PERS_TICK(4)
     if (!alive) { fail = 1; break; }
-    PERS_TICK(6)
   }
 #undef PERS_TICK
   if (timing) { for (int q = 0; q < 12; q++) a.dbg[q] += tacc[q]; a.dbg[12] += k; a.dbg[13] += 1; }
@@ -2563,9 +2614,10 @@ __global__ __launch_bounds__(kPersTPB) void ba_pcg_init_tiles(BaDev d, double la
   if (d.mk_on) mk_restrict(d, c, s0, m, rc, Li);
 }
 
-static inline size_t pers_lds_bytes() {
-  return (size_t)(2 * kCluN * kCluN + 5 * kCluN + 8 * kCluN + kPersWaves + 4) * sizeof(double) + 16 + 14 * sizeof(long long);
-}
+// A | Li | rc, xs + ps, ss, zs | zpart | P^T s | red | ibuf, phase clocks (ba_pcg_persist)
+constexpr size_t kPersLdsBytes = (size_t)(2 * kCluN * kCluN + 4 * kCluN + 8 * kCluN + kPersNcCap + 2 * kPersWaves + 4) * sizeof(double) + 16 + 14 * sizeof(long long);
+static_assert(kPersLdsBytes <= 160 * 1024, "persistent PCG: LDS of one workgroup exceeds the 160 KB of a CU");
+static inline size_t pers_lds_bytes() { return kPersLdsBytes; }
 
 // ---- very small reduced systems (<= 16 free cameras: initial maps, tiny local windows): the whole PCG in ONE workgroup ----
 // Vectors and the 6x6 block-Jacobi preconditioner live in LDS and an iteration is a few block barriers (~2 us).  Typical
@@ -3258,6 +3310,7 @@ int lm_trial(ccm_ba* ba, double lambda, const ccm_ba_options& opt, double* temp_
       PersArgs pa;
       pa.lambda = lambda; pa.rel_tol = tol; pa.max_it = max_it; pa.n_clu = ccm_div_up(d.Cp, kClu);
       pa.bar = ba->d_pers_bar; pa.slots = (unsigned long long*)ba->d_pers_part;
+      pa.utag = (unsigned long long*)ba->d_pers_u; pa.wbuf[0] = d.p[0]; pa.wbuf[1] = d.p[1];   // (d.p: the multi-kernel path re-initialises it before use)
       pa.epoch_base = (++ba->pers_launch) << 20;
       pa.uoff = ba->d_pers_uoff; pa.ucol = ba->d_pers_ucol; pa.loc = ba->d_pers_loc;
       pa.coff = ba->d_pers_coff; pa.cij = ba->d_pers_cij; pa.cblk = ba->d_pers_cblk;
@@ -3534,6 +3587,43 @@ int ccm_internal::ba_debug_partial_reduced(ccm_ba* ba, double lambda, double* ou
   return CCM_OK;
 }
 
+// Test hook: ONE persistent PCG solve of (S + lambda I) x = b_schur at the current state, the coarse level on (coarse != 0, freshly built at this
+// lambda) or off, the cluster inverse factored in the launch.  x_out: [6 Cp]; flags: pcg_flag of the launch ([1] iterations, [2] numeric failure,
+// [3] the launch gave up waiting for its peers).  CCM_E_STATE when the handle has no persistent solver (or no coarse level and coarse != 0).
+int ccm_internal::ba_debug_pcg_solve(ccm_ba* ba, double lambda, int coarse, double rel_tol, int max_it, double* x_out, size_t cap, int* flags) {
+  if (!ba || !x_out || !flags) return CCM_E_ARG;
+  ccm_ctx* ctx = ba->ctx;
+  BaDev& d = ba->d;
+  if (!ba->pers_grid) return ccm_set_error(ctx, CCM_E_STATE, "ccm_ba_debug_pcg_solve: the handle has no persistent PCG");
+  if (coarse && !ba->coarse_na) return ccm_set_error(ctx, CCM_E_STATE, "ccm_ba_debug_pcg_solve: the handle has no coarse level");
+  if (cap < 6 * (size_t)d.Cp) return ccm_set_error(ctx, CCM_E_ARG, "ccm_ba_debug_pcg_solve: buffer too small");
+  CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  RC(build_system(ba));
+  if (d.Lloc) hipLaunchKernelGGL(ba_dinv, dim3(d.n_wg_pt), dim3(kTPB), 0, ctx->stream, d, lambda);
+  RC(launch_schur(ba));
+  PersArgs pa{};
+  pa.lambda = lambda; pa.rel_tol = rel_tol; pa.max_it = max_it; pa.n_clu = ccm_div_up(d.Cp, kClu);
+  pa.bar = ba->d_pers_bar; pa.slots = (unsigned long long*)ba->d_pers_part;
+  pa.utag = (unsigned long long*)ba->d_pers_u; pa.wbuf[0] = d.p[0]; pa.wbuf[1] = d.p[1];
+  pa.epoch_base = (++ba->pers_launch) << 20;
+  pa.uoff = ba->d_pers_uoff; pa.ucol = ba->d_pers_ucol; pa.loc = ba->d_pers_loc;
+  pa.coff = ba->d_pers_coff; pa.cij = ba->d_pers_cij; pa.cblk = ba->d_pers_cblk;
+  pa.test_abort = 0; pa.dbg = nullptr; pa.wsave = nullptr; pa.w_load = 0;
+  if (coarse) {
+    RC(coarse_build(ba, lambda));
+    ba->coarse_valid = false;   // (built for this hook: the LM loop's reuse policy must not take it for one of its own)
+    pa.Ainv = ba->d_cAinv; pa.Pm = ba->d_cP; pa.na = ba->coarse_na; pa.Nc = ba->coarse_Nc; pa.cparts = ba->d_cparts;
+  }
+  CCM_HIP_CHECK(ctx, hipMemsetAsync(ba->d_pers_bar + 1, 0, sizeof(unsigned), ctx->stream));   // abort flag
+  hipLaunchKernelGGL(ba_pcg_persist, dim3(ba->pers_grid), dim3(kPersTPB), pers_lds_bytes(), ctx->stream, d, pa);
+  CCM_HIP_CHECK(ctx, hipGetLastError());
+  CCM_HIP_CHECK(ctx, hipMemcpyAsync(flags, d.pcg_flag, 4 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  CCM_HIP_CHECK(ctx, hipMemcpyAsync(x_out, d.x, 6 * (size_t)d.Cp * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  CCM_HIP_CHECK(ctx, hipMemsetAsync(ba->d_pers_bar + 1, 0, sizeof(unsigned), ctx->stream));
+  CCM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  return CCM_OK;
+}
+
 static void pers_dbg_dump(ccm_ba* ba) {
   if (ba->d.row_dbg) {
     long long h[8];
@@ -3567,14 +3657,14 @@ static void pers_dbg_dump(ccm_ba* ba) {
       std::vector<double> v;
       for (int g = 0; g < ba->pers_grid; g++) if (w[2 * g + x] > 0) v.push_back(w[2 * g + x] * 0.01 / itn);
       std::sort(v.begin(), v.end());
-      if (!v.empty()) fprintf(stderr, "[ccm_ba] persistent PCG, time inside exchange %d per unit and iteration (us): min %.2f  p10 %.2f  median %.2f  p90 %.2f  max %.2f  (%zu units)\n",
-                              x + 1, v.front(), v[v.size() / 10], v[v.size() / 2], v[v.size() * 9 / 10], v.back(), v.size());
+      if (!v.empty()) fprintf(stderr, "[ccm_ba] persistent PCG, %s per unit and iteration (us): min %.2f  p10 %.2f  median %.2f  p90 %.2f  max %.2f  (%zu units)\n",
+                              x == 0 ? "time inside the exchange" : "halo wait", v.front(), v[v.size() / 10], v[v.size() / 2], v[v.size() * 9 / 10], v.back(), v.size());
     }
   }
   const double it = (double)std::max<long long>(h[12], 1), nl = (double)std::max<long long>(h[13], 1);
-  fprintf(stderr, "[ccm_ba] persistent PCG, workgroup 0: %lld iterations in %lld launches; us/iteration: stage_p %.2f spmv+dot %.2f barrier1 %.2f "
-          "sum_pq %.2f update+W %.2f barrier2 %.2f sum_rz %.2f | us/launch: assemble %.1f cholesky %.1f inverse %.1f W %.1f start %.1f\n",
-          h[12], h[13], h[0] * 0.01 / it, h[1] * 0.01 / it, h[2] * 0.01 / it, h[3] * 0.01 / it, h[4] * 0.01 / it, h[5] * 0.01 / it, h[6] * 0.01 / it,
+  fprintf(stderr, "[ccm_ba] persistent PCG, workgroup 0: %lld iterations in %lld launches; us/iteration: update %.2f W %.2f halo %.2f "
+          "spmv+dot %.2f exchange %.2f | us/launch: assemble %.1f cholesky %.1f inverse %.1f W %.1f start %.1f\n",
+          h[12], h[13], h[0] * 0.01 / it, h[1] * 0.01 / it, h[2] * 0.01 / it, h[3] * 0.01 / it, h[4] * 0.01 / it,
           h[7] * 0.01 / nl, h[8] * 0.01 / nl, h[9] * 0.01 / nl, h[10] * 0.01 / nl, h[11] * 0.01 / nl);
 }
 

@@ -857,7 +857,7 @@ extern "C" int ccm_ba_create(ccm_ctx* ctx, const ccm_ba_problem* P, int rank, in
       BB_RC(keep_get(ba, (size_t)Nc * Nc, &ba->d_cA, true)); BB_RC(keep_get(ba, (size_t)Nc * Nc, &ba->d_cX, true));
       BB_RC(keep_get(ba, (size_t)Nc * Nc, &ba->d_cAinv, true)); BB_RC(keep_get(ba, (size_t)Nc * 64, &ba->d_cLinv, true));
       BB_RC(keep_get(ba, 4, &ba->d_cinfo, true));
-      BB_RC(keep_get(ba, 12 * (size_t)std::max(n_units, 1), &ba->d_cparts, true));
+      BB_RC(keep_get(ba, 24 * (size_t)std::max(n_units, 1), &ba->d_cparts, true));   // [2][12][units]
       ba->coarse_na = na; ba->coarse_Nc = Nc; ba->coarse_ncb = hs.ncb;
       if (const char* cf = getenv("CCM_BA_COARSE")) ba->coarse_force = !strcmp(cf, "always") ? 1 : !strcmp(cf, "never") ? -1 : 0;
       return CCM_OK;
@@ -866,8 +866,9 @@ extern "C" int ccm_ba_create(ccm_ctx* ctx, const ccm_ba_problem* P, int rank, in
     ba->pers_grid = 0;
     d.mk_cpart = nullptr; d.mk_cry[0] = d.mk_cry[1] = nullptr; d.mk_P = nullptr; d.mk_Ainv = nullptr; d.mk_Ainv32 = nullptr; d.mk_on = 0; d.mk_Nc = 0; d.mk_na = 0;
     if (pers_try && !hs.pers_bad) {
-      BB_RC(keep_get(ba, 4 + 2 * 16 + 4 * 512, &ba->d_pers_bar, true));   // abort flag + debug clocks (workgroup 0's phases; then per workgroup the time spent in the two exchanges)
-      BB_RC(keep_get(ba, 4 * (size_t)pers_grid_want, &ba->d_pers_part, true));   // [2][2][grid] slot words
+      BB_RC(keep_get(ba, 4 + 2 * 16 + 4 * 512, &ba->d_pers_bar, true));   // abort flag + debug clocks (workgroup 0's phases; then per workgroup the time spent in the exchange and in the halo wait)
+      BB_RC(keep_get(ba, 6 * (size_t)pers_grid_want, &ba->d_pers_part, true));   // [2][3][grid] slot words
+      BB_RC(keep_get(ba, 12 * (size_t)Cp, &ba->d_pers_u, true));   // [6 Cp][2] tagged u
       ba->pers_grid = pers_grid_want; ba->pers_grid_built = pers_grid_want;
       BB_RC(keep_get(ba, (size_t)pers_grid_want * (kCluN * (kCluN / 2)), &ba->d_pers_wsave, false));   // the units' halves of the cluster inverse, carried from trial to trial (written before read)
       if (coarse_pers) BB_RC(coarse_buffers(pers_grid_want));

@@ -22,6 +22,7 @@ constexpr int kPersTPB = 1024;
 constexpr int kPersWaves = kPersTPB / kWave;
 constexpr int kPersIdxCap = 3072;    // CSR entries of one persistent unit's rows (staged in LDS)
 constexpr int kPersColCap = 640;     // distinct neighbour columns of one persistent unit
+constexpr int kPersNcCap = 768;      // coarse unknowns of the persistent solver (12 Nc floats in half of its 96x96 LDS block)
 constexpr int kSmallMaxCp = 16;      // one cluster: the single-workgroup kernel; above, the persistent kernel with its 16-camera cluster preconditioner
 constexpr int kDense2MaxCp = 2 * kClu;
 constexpr int kCholRegMaxCp = 50;    // (round 6) exact register-resident Cholesky in one workgroup: 19 x 19 tiles of 16 x 16 (n = 6 Cp <= 304), ba_solve_cholreg
@@ -160,6 +161,7 @@ struct ccm_ba {
   // operator needed clearly more iterations than the solve right after the last build (counts are deterministic => so is the policy).
   // cluster inverse of the persistent solver carried from trial to trial (ba.hip, lm_trial): what it was built at, and the iteration guard
   double* d_pers_wsave = nullptr;   // [pers_grid][96 * 48]
+  double* d_pers_u = nullptr;       // [6 Cp][2] u of the persistent solver's halo exchange as {bits, bits ^ key}
   float* d_cAinv32 = nullptr;       // [Nc][Nc] multi-kernel path
   bool w_valid = false, w_loaded = false, w_stale_bad = false; double w_lambda_built = 0; int w_fresh_iters = 0, lin_id = 0, w_lin_id = -1;
   bool coarse_valid = false, coarse_fresh = false, coarse_stale_bad = false, coarse_reuse = true;

@@ -79,6 +79,9 @@ extern "C" int ccm_ba_debug_array(ccm_ba* ba, const char* name, void* out, size_
 // ---- C wrappers of the C++-linkage test entry points that live next to the file-local kernels they exercise (test_internal.h) ----
 extern "C" int ccm_ba_debug_partial_reduced(ccm_ba* ba, double lambda, double* out, size_t cap, size_t* count) { return ccm_internal::ba_debug_partial_reduced(ba, lambda, out, cap, count); }
 extern "C" int ccm_ba_debug_coarse(ccm_ba* ba, double lambda, int* na, double* Ac, double* Ainv, double* Pm, size_t cap) { return ccm_internal::ba_debug_coarse(ba, lambda, na, Ac, Ainv, Pm, cap); }
+extern "C" int ccm_ba_debug_pcg_solve(ccm_ba* ba, double lambda, int coarse, double rel_tol, int max_it, double* x_out, size_t cap, int* flags) {
+  return ccm_internal::ba_debug_pcg_solve(ba, lambda, coarse, rel_tol, max_it, x_out, cap, flags);
+}
 extern "C" int ccm_comm_loopback_create(int nranks, void** group) { return ccm_internal::comm_loopback_create(nranks, group); }
 extern "C" void ccm_comm_loopback_destroy(void* group) { ccm_internal::comm_loopback_destroy(group); }
 extern "C" int ccm_comm_init_loopback(ccm_ctx* ctx, void* group, int rank) { return ccm_internal::comm_init_loopback(ctx, group, rank); }

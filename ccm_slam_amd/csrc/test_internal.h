@@ -8,6 +8,7 @@
 namespace ccm_internal {
 int  ba_debug_partial_reduced(ccm_ba* ba, double lambda, double* out, size_t cap, size_t* count);
 int  ba_debug_coarse(ccm_ba* ba, double lambda, int* na, double* Ac, double* Ainv, double* Pm, size_t cap);
+int  ba_debug_pcg_solve(ccm_ba* ba, double lambda, int coarse, double rel_tol, int max_it, double* x_out, size_t cap, int* flags);
 int  comm_loopback_create(int nranks, void** group);
 void comm_loopback_destroy(void* group);
 int  comm_init_loopback(ccm_ctx* ctx, void* group, int rank);

@@ -34,6 +34,11 @@ int  ccm_ba_debug_partial_reduced(ccm_ba* ba, double lambda, double* out, size_t
  * its inverse [6 na x 6 na], prolongation blocks P_k = Ad(T_cw,k) [n_free_cams x 36]; cap = doubles available in Ac / Ainv. */
 int  ccm_ba_debug_coarse(ccm_ba* ba, double lambda, int* na, double* Ac, double* Ainv, double* Pm, size_t cap);
 
+/* test hook: ONE solve of the persistent PCG (ba_pcg_persist) of (S + lambda I) x = b at the current state, the coarse level on (coarse != 0, built at
+ * this lambda) or off; x_out: [6 n_free_cams]; flags: [0] done, [1] CG iterations, [2] numeric failure, [3] the launch gave up waiting for its peers.
+ * CCM_E_STATE when the handle has no persistent solver (or no coarse level although one is asked for). */
+int  ccm_ba_debug_pcg_solve(ccm_ba* ba, double lambda, int coarse, double rel_tol, int max_it, double* x_out, size_t cap, int* flags);
+
 /* TEST-ONLY in-process communicator: the ranks are threads of one process sharing one GPU, each with its own ccm_ctx; an all-reduce is
  * a rendezvous plus one reduction kernel that leaves the same bits in every rank's buffer (RCCL's contract).  Lets a single-GPU box
  * execute the complete multi-rank control flow of the sharded global BA (tests/test_sharded_loopback_gpu.py). */
