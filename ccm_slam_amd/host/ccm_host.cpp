@@ -929,6 +929,71 @@ void Optimizer::GlobalBundleAdjustment(HipContext& ctx, BAProblem& p, int nItera
         ctx.get(), "ccm_ba_optimize");
 }
 
+// ---- Sim3RansacBatch ------------------------------------------------------------------------------
+static std::vector<int> sim3_sizes(const std::vector<Sim3Candidate>& c) {
+  std::vector<int> n;
+  for (const auto& x : c) {
+    if (x.X3Dc1.size() != 3 * x.indices1.size() || x.X3Dc2.size() != x.X3Dc1.size() || x.max_err1.size() != x.indices1.size() ||
+        x.max_err2.size() != x.indices1.size())
+      throw std::invalid_argument("Sim3Candidate: inconsistent sizes");
+    for (int32_t i : x.indices1)
+      if (i < 0 || i >= x.n1) throw std::invalid_argument("Sim3Candidate: mvnIndices1 outside [0, mN1)");
+    n.push_back((int)x.indices1.size());
+  }
+  return n;
+}
+
+Sim3RansacBatch::Sim3RansacBatch(HipContext& ctx, std::vector<Sim3Candidate> cands, const ccm_sim3::Params& p, bool fix_scale, ccm_sim3::DrawSource src)
+    : cands_(std::move(cands)), sched_(sim3_sizes(cands_), p, std::move(src)) {
+  eval_.ctx = &ctx;
+  eval_.fix_scale = fix_scale ? 1 : 0;
+  eval_.pt_off.push_back(0);
+  for (const auto& c : cands_) {
+    const int N = (int)c.indices1.size();
+    if (N < 3) { eval_.remap.push_back(-1); continue; }   // never evaluated (N < minInliers, checked by the schedule)
+    eval_.remap.push_back((int)eval_.pt_off.size() - 1);
+    eval_.pt_off.push_back(eval_.pt_off.back() + N);
+    eval_.X1.insert(eval_.X1.end(), c.X3Dc1.begin(), c.X3Dc1.end());
+    eval_.X2.insert(eval_.X2.end(), c.X3Dc2.begin(), c.X3Dc2.end());
+    eval_.K1.insert(eval_.K1.end(), c.K1, c.K1 + 4);
+    eval_.K2.insert(eval_.K2.end(), c.K2, c.K2 + 4);
+    eval_.t1.insert(eval_.t1.end(), c.max_err1.begin(), c.max_err1.end());
+    eval_.t2.insert(eval_.t2.end(), c.max_err2.begin(), c.max_err2.end());
+  }
+}
+
+void Sim3RansacBatch::Eval::operator()(const std::vector<int32_t>& hyp_cand, const std::vector<int32_t>& hyp_idx, std::vector<int32_t>& n_inl,
+                                       std::vector<float>& rts, std::vector<int32_t>& mask_off, std::vector<uint32_t>& mask) {
+  const int H = (int)hyp_cand.size();
+  cand_buf.resize(H);
+  int64_t words = 0;
+  for (int h = 0; h < H; h++) {
+    const int r = remap[hyp_cand[h]];
+    cand_buf[h] = r;
+    words += (pt_off[r + 1] - pt_off[r] + 31) / 32;
+  }
+  n_inl.resize(H); rts.resize(13 * (size_t)H); mask_off.resize(H + 1); mask.resize((size_t)words);
+  const int K = (int)pt_off.size() - 1;
+  check(ccm_sim3_ransac_eval(ctx->get(), K, pt_off.data(), X1.data(), X2.data(), K1.data(), K2.data(), t1.data(), t2.data(), H, cand_buf.data(),
+                             hyp_idx.data(), fix_scale, n_inl.data(), rts.data(), mask_off.data(), mask.data()),
+        ctx->get(), "ccm_sim3_ransac_eval");
+}
+
+bool Sim3RansacBatch::next(int& cand, float R[9], float t[3], float& s, std::vector<bool>& vbInliers, int& nInliers) {
+  ccm_sim3::Event ev;
+  if (!sched_.next(eval_, ev)) return false;
+  const Sim3Candidate& c = cands_[ev.cand];
+  cand = ev.cand;
+  for (int i = 0; i < 9; i++) R[i] = ev.R[i];
+  for (int i = 0; i < 3; i++) t[i] = ev.t[i];
+  s = ev.s;
+  nInliers = ev.n_inliers;
+  vbInliers.assign(c.n1, false);
+  for (size_t i = 0; i < c.indices1.size(); i++)
+    if (ev.mask[i >> 5] >> (i & 31) & 1u) vbInliers[c.indices1[i]] = true;
+  return true;
+}
+
 }  // namespace cslam
 
 // ---- C entry points (ccm_host_c.h): the Python test-suite and the drop-in translation units under shim/ ---------------------------------------
@@ -1324,6 +1389,116 @@ extern "C" int ccmh_kfdb_detect(void* db, int device, int kind, int n, const int
     return (int)r.size();
   } catch (const std::exception&) { return -1000; }
 }
+
+// Sim3RansacBatch over flat arrays: candidate c has the correspondences pt_off[c] .. pt_off[c+1] (X3Dc1 / X3Dc2 3 per correspondence, thresholds,
+// idx1 = mvnIndices1) and n1[c] = mN1, K1 / K2 4 per candidate.  draws != NULL: the raw rand() values come from draws[0 .. n_draws) (after the
+// thread's FIFO) instead of ::rand().
+namespace {
+struct Sim3BatchHandle {
+  std::vector<int32_t> draws;
+  size_t cursor = 0;
+  std::unique_ptr<cslam::Sim3RansacBatch> batch;
+};
+}  // namespace
+extern "C" void* ccmh_sim3_ransac_create(int device, int K, const int32_t* pt_off, const float* X3Dc1, const float* X3Dc2, const float* K1, const float* K2,
+                                         const uint32_t* max_err1, const uint32_t* max_err2, const int32_t* n1, const int32_t* idx1, double probability,
+                                         int min_inliers, int max_iterations, int solver_iterations, int fix_scale, const int32_t* draws, int64_t n_draws) {
+  try {
+    if (K < 0 || !pt_off || (K > 0 && (!n1 || !K1 || !K2)) || (draws == nullptr && n_draws != 0) || n_draws < 0 || solver_iterations < 1) return nullptr;
+    std::vector<cslam::Sim3Candidate> cands(K);
+    for (int c = 0; c < K; c++) {
+      const int a = pt_off[c], b = pt_off[c + 1];
+      if (b < a) return nullptr;
+      if (b > a && (!X3Dc1 || !X3Dc2 || !max_err1 || !max_err2 || !idx1)) return nullptr;
+      auto& x = cands[c];
+      x.n1 = n1[c];
+      x.indices1.assign(idx1 + a, idx1 + b);
+      x.X3Dc1.assign(X3Dc1 + 3 * (size_t)a, X3Dc1 + 3 * (size_t)b);
+      x.X3Dc2.assign(X3Dc2 + 3 * (size_t)a, X3Dc2 + 3 * (size_t)b);
+      x.max_err1.assign(max_err1 + a, max_err1 + b);
+      x.max_err2.assign(max_err2 + a, max_err2 + b);
+      for (int k = 0; k < 4; k++) { x.K1[k] = K1[4 * c + k]; x.K2[k] = K2[4 * c + k]; }
+    }
+    ccm_sim3::Params p;
+    p.probability = probability; p.min_inliers = min_inliers; p.max_iterations = max_iterations; p.solver_iterations = solver_iterations;
+    std::unique_ptr<Sim3BatchHandle> h(new Sim3BatchHandle);
+    ccm_sim3::DrawSource src = ccm_sim3::rand_source();
+    if (draws) {
+      h->draws.assign(draws, draws + n_draws);
+      Sim3BatchHandle* hp = h.get();
+      src = [hp](int& v) { if (hp->cursor >= hp->draws.size()) return false; v = hp->draws[hp->cursor++]; return true; };
+    }
+    h->batch.reset(new cslam::Sim3RansacBatch(thread_context(device), std::move(cands), p, fix_scale != 0, src));
+    return h.release();
+  } catch (const std::exception&) { return nullptr; }
+}
+// 1: an event (inliers[0 .. min(cap, mN1)) = vbInliers), 0: every candidate discarded, -1: the supplied draws ran out, -1000: device error
+extern "C" int ccmh_sim3_ransac_next(void* hv, int32_t* cand, float* R9, float* t3, float* s, uint8_t* inliers, int cap, int32_t* n_inliers) {
+  if (!hv) return -1000;
+  try {
+    Sim3BatchHandle* h = (Sim3BatchHandle*)hv;
+    int c = -1, n = 0; float sc = 0; std::vector<bool> vb;
+    float R[9], t[3];
+    try {
+      if (!h->batch->next(c, R, t, sc, vb, n)) return 0;
+    } catch (const ccm_sim3::DrawsExhausted&) {
+      return -1;
+    }
+    if (cand) *cand = c;
+    if (R9) std::memcpy(R9, R, sizeof R);
+    if (t3) std::memcpy(t3, t, sizeof t);
+    if (s) *s = sc;
+    if (n_inliers) *n_inliers = n;
+    if (inliers) for (int i = 0; i < cap && i < (int)vb.size(); i++) inliers[i] = vb[i] ? 1 : 0;
+    return 1;
+  } catch (const std::exception&) { return -1000; }
+}
+// [values taken from the draw source, hypotheses evaluated, passes (device calls)]
+extern "C" int ccmh_sim3_ransac_stats(void* hv, int64_t* out3) {
+  if (!hv || !out3) return -1000;
+  const auto& sc = ((Sim3BatchHandle*)hv)->batch->schedule();
+  out3[0] = sc.source_draws(); out3[1] = sc.hyps_evaluated(); out3[2] = sc.passes();
+  return 0;
+}
+extern "C" void ccmh_sim3_ransac_destroy(void* hv) { delete (Sim3BatchHandle*)hv; }
+// One Sim3Solver::iterate(n_iterations) of the drop-in shim/Sim3Solver_hip.cpp: N correspondences (X3Dc1 / X3Dc2, thresholds, cameras), state = [mnIterations,
+// mnBestInliers] in / out, draws from ::rand() through the calling thread's FIFO.  flags = [success, bNoMore, best moved, inliers of the best]; when the best
+// moved, best_rts = R (9) t (3) s and best_mask = its inlier bits (ceil(N / 32) words).  0, or -1000 on a device error.
+extern "C" int ccmh_sim3_solver_iterate(int device, int N, const float* X3Dc1, const float* X3Dc2, const float* K1, const float* K2, const uint32_t* max_err1,
+                                        const uint32_t* max_err2, int fix_scale, int min_inliers, int max_iterations, int n_iterations, int32_t* state,
+                                        float* best_rts, uint32_t* best_mask, int32_t* flags) {
+  try {
+    if (N < 0 || !state || !flags || !best_rts || (N > 0 && (!X3Dc1 || !X3Dc2 || !K1 || !K2 || !max_err1 || !max_err2 || !best_mask))) return -1000;
+    cslam::Sim3RansacBatch::Eval ev;
+    ev.ctx = &thread_context(device);
+    ev.fix_scale = fix_scale ? 1 : 0;
+    ev.pt_off = {0, N}; ev.remap = {0};
+    ev.X1.assign(X3Dc1, X3Dc1 + 3 * (size_t)N); ev.X2.assign(X3Dc2, X3Dc2 + 3 * (size_t)N);
+    ev.K1.assign(K1, K1 + 4); ev.K2.assign(K2, K2 + 4);
+    ev.t1.assign(max_err1, max_err1 + N); ev.t2.assign(max_err2, max_err2 + N);
+    ccm_sim3::SolverState st;
+    st.N = N; st.max_its = max_iterations; st.min_inliers = min_inliers; st.its = state[0]; st.best = state[1];
+    bool no_more = false, moved = false;
+    ccm_sim3::Event best;
+    const bool ok = ccm_sim3::iterate_one(ev, st, n_iterations, ccm_sim3::rand_source(), no_more, moved, best);
+    state[0] = st.its; state[1] = st.best;
+    flags[0] = ok; flags[1] = no_more; flags[2] = moved; flags[3] = moved ? best.n_inliers : 0;
+    if (moved) {
+      for (int i = 0; i < 9; i++) best_rts[i] = best.R[i];
+      for (int i = 0; i < 3; i++) best_rts[9 + i] = best.t[i];
+      best_rts[12] = best.s;
+      std::memcpy(best_mask, best.mask.data(), best.mask.size() * 4);
+    }
+    return 0;
+  } catch (const std::exception&) { return -1000; }
+}
+// the calling thread's FIFO of drawn, unused rand() values: returns its length, copies min(length, cap) values front first
+extern "C" int ccmh_sim3_draws_pending(int32_t* out, int cap) {
+  const auto& q = ccm_sim3::draw_fifo();
+  for (int i = 0; i < cap && i < (int)q.size(); i++) out[i] = q[i];
+  return (int)q.size();
+}
+extern "C" void ccmh_sim3_draws_clear(void) { ccm_sim3::draw_fifo().clear(); }
 
 // C entry points of the f32 <-> f64 boundary (ccm_convert.h) for the tests and for non-C++ callers
 #include "ccm_convert.h"

@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 #include "../../include/ccm_hip.h"
+#include "sim3_schedule.h"
 
 namespace cslam {
 
@@ -262,6 +263,44 @@ class KeyFrameDatabase {
   std::vector<int64_t> detect(HipContext& ctx, const BowVector& v, float minScore, const ccm_kfdb_filter* f, const Neighbours& neighbours);
   ccm_kfdb* db_ = nullptr;
   bool owned_ = true;
+};
+
+// ---------------------------------------------------------------------------------------------------
+// Sim3RansacBatch — the vpSim3Solvers loop of LoopFinder::ComputeSim3 (cslam/src/LoopFinder.cpp:288-346) and MapMatcher::ComputeSim3: one
+// Sim3Solver per candidate (the correspondences its constructor gathers, Sim3Solver.cpp:5-92), iterate(mSolverIterations) round-robin until a
+// call returns a Sim3.  next() returns that event (candidate, R, t, s = GetEstimated*, vbInliers in the candidate's mN1 numbering) and the
+// caller runs SearchBySim3 + OptimizeSim3; on rejection it calls next() again, which goes on where the reference's loop goes on.  false: every
+// candidate is discarded.  Hypotheses are evaluated in passes on the device (ccm_sim3_ransac_eval, schedule in sim3_schedule.h); the draws come
+// from ::rand() through the calling thread's FIFO (or a supplied source), so the events are the sequential reference's.
+// ---------------------------------------------------------------------------------------------------
+struct Sim3Candidate {
+  int n1 = 0;                       // mN1 = vpMatched12.size()
+  std::vector<int32_t> indices1;    // mvnIndices1 (size N)
+  std::vector<float> X3Dc1, X3Dc2;  // mvX3Dc1 / mvX3Dc2, 3 per correspondence
+  std::vector<uint32_t> max_err1, max_err2;   // mvnMaxError1 / mvnMaxError2
+  float K1[4] = {0, 0, 0, 0}, K2[4] = {0, 0, 0, 0};   // fx fy cx cy of pKF1->mK / pKF2->mK
+};
+
+class Sim3RansacBatch {
+ public:
+  struct Eval {
+    HipContext* ctx = nullptr;
+    int fix_scale = 0;
+    std::vector<int32_t> pt_off, remap;   // device CSR over the candidates with N >= 3; remap: candidate -> CSR row
+    std::vector<float> X1, X2, K1, K2;
+    std::vector<uint32_t> t1, t2;
+    std::vector<int32_t> cand_buf;
+    void operator()(const std::vector<int32_t>& hyp_cand, const std::vector<int32_t>& hyp_idx, std::vector<int32_t>& n_inl, std::vector<float>& rts,
+                    std::vector<int32_t>& mask_off, std::vector<uint32_t>& mask);
+  };
+  Sim3RansacBatch(HipContext& ctx, std::vector<Sim3Candidate> cands, const ccm_sim3::Params& p = ccm_sim3::Params(), bool fix_scale = false,
+                  ccm_sim3::DrawSource src = ccm_sim3::rand_source());
+  bool next(int& cand, float R[9], float t[3], float& s, std::vector<bool>& vbInliers, int& nInliers);
+  const ccm_sim3::Schedule<Eval>& schedule() const { return sched_; }
+ private:
+  std::vector<Sim3Candidate> cands_;
+  Eval eval_;
+  ccm_sim3::Schedule<Eval> sched_;
 };
 
 // ---------------------------------------------------------------------------------------------------

@@ -33,6 +33,19 @@ int ccmh_bow_transform(int device, int n_nodes, int L, const int32_t* child_off,
  * ccm_kfdb handle: kind 0 loop, 1 map match, 2 relocalisation; n_allow < 0 = every keyframe; neighbours = GetBestCovisibilityKeyFrames(10) as a table over
  * nb_key.  Returns the number of candidates (min(that, cap) written to out), -1000 on a device error. */
 int ccmh_kfdb_detect(void* db, int device, int kind, int n, const int32_t* word, const double* value, float min_score, int64_t self_key, const int64_t* allow, int n_allow, const int64_t* exclude, int n_exclude, uint64_t exclude_groups, int n_nb_keys, const int64_t* nb_key, const int32_t* nb_off, const int64_t* nb_list, int64_t* out, int cap);
+/* Sim3 RANSAC of LoopFinder / MapMatcher::ComputeSim3 (cslam::Sim3RansacBatch): candidate c = correspondences pt_off[c] .. pt_off[c+1] (mvX3Dc1 / mvX3Dc2 3 floats each,
+ * mvnMaxError1 / 2, idx1 = mvnIndices1), n1[c] = mN1, K1 / K2 = fx fy cx cy per candidate.  draws: raw rand() values to use instead of ::rand() (NULL: ::rand()), after
+ * the calling thread's FIFO.  next: 1 = a Sim3 (inliers[0 .. min(cap, mN1)) = vbInliers), 0 = every candidate discarded, -1 = the supplied draws ran out, -1000 = device
+ * error.  draws_pending: the calling thread's FIFO of drawn but unused values (length returned, min(length, cap) copied front first). */
+void* ccmh_sim3_ransac_create(int device, int K, const int32_t* pt_off, const float* X3Dc1, const float* X3Dc2, const float* K1, const float* K2, const uint32_t* max_err1, const uint32_t* max_err2, const int32_t* n1, const int32_t* idx1, double probability, int min_inliers, int max_iterations, int solver_iterations, int fix_scale, const int32_t* draws, int64_t n_draws);
+int ccmh_sim3_ransac_next(void* h, int32_t* cand, float* R9, float* t3, float* s, uint8_t* inliers, int cap, int32_t* n_inliers);
+int ccmh_sim3_ransac_stats(void* h, int64_t* out3);
+void ccmh_sim3_ransac_destroy(void* h);
+/* one Sim3Solver::iterate(n_iterations) of a single solver (shim/Sim3Solver_hip.cpp): state = [mnIterations, mnBestInliers] in / out, draws from ::rand()
+ * through the thread's FIFO; flags = [success, bNoMore, best moved, its inliers], best_rts / best_mask written when the best moved.  0, or -1000 on a device error. */
+int ccmh_sim3_solver_iterate(int device, int N, const float* X3Dc1, const float* X3Dc2, const float* K1, const float* K2, const uint32_t* max_err1, const uint32_t* max_err2, int fix_scale, int min_inliers, int max_iterations, int n_iterations, int32_t* state, float* best_rts, uint32_t* best_mask, int32_t* flags);
+int ccmh_sim3_draws_pending(int32_t* out, int cap);
+void ccmh_sim3_draws_clear(void);
 void ccmh_to_se3quat(const float* Tcw16, double* qt7);
 void ccmh_se3quat_to_cvmat(const double* qt7, float* Tcw16);
 void ccmh_sim3_to_cvse3(const double* s8, float* Tcw16);

@@ -556,3 +556,42 @@ def make_vocabulary(k: int = 10, L: int = 4, seed: int = 0, stop_frac: float = 0
     weight[n_inner:] = rng.uniform(0.5, 6.0, n_nodes - n_inner)
     weight[n_inner:][rng.random(n_nodes - n_inner) < stop_frac] = 0.0
     return dict(n_nodes=n_nodes, L=L, child_off=child_off, child_id=child_id, node_desc=desc, word_id=word_id, weight=weight)
+
+
+def make_sim3_candidates(seed: int = 0, n_true: int = 1, n_false: int = 3, n_points=200, outlier_frac: float = 0.3, fix_scale: bool = False,
+                         noise: float = 0.003):
+    """Loop / map-match candidate sets for the Sim3 RANSAC (Sim3Solver's constructor state, one dict per candidate with the fields of
+    ccm_slam_amd.sim3.Sim3Candidate).  True candidates: a planted Sim3 S12 (X1 = s R X2 + t, both in their keyframe's camera frame, small
+    noise), a fraction `outlier_frac` of the pairs replaced by unrelated points.  False candidates: no consistent Sim3 (X1 drawn independently of
+    X2).  Octaves over all 8 levels give the thresholds 9.210 * mvLevelSigma2 (size_t); the two keyframes have different cameras.
+    n_points: one size for all, or a sequence with one size per candidate (true candidates first).  Planted values in meta."""
+    rng = np.random.default_rng(seed)
+    n_c = n_true + n_false
+    sizes = [int(n_points)] * n_c if np.isscalar(n_points) else [int(x) for x in n_points]
+    _, _, sigma2, _ = scale_tables()
+    out = []
+    for c in range(n_c):
+        N = sizes[c]
+        K1 = (EUROC_K[0] * rng.uniform(0.9, 1.1), EUROC_K[1] * rng.uniform(0.9, 1.1), EUROC_K[2], EUROC_K[3])
+        K2 = (EUROC_K[0] * rng.uniform(0.9, 1.1), EUROC_K[1] * rng.uniform(0.9, 1.1), EUROC_K[2] + 5.0, EUROC_K[3] - 3.0)
+        s = 1.0 if fix_scale else float(rng.uniform(0.7, 1.4))
+        R = rodrigues(rng.normal(size=(1, 3)) * np.deg2rad(10.0))[0]
+        t = rng.uniform(-0.5, 0.5, 3)
+        depth = rng.uniform(1.5, 9.0, N)
+        u, v = rng.uniform(40, IMG_W - 40, N), rng.uniform(40, IMG_H - 40, N)
+        X2 = np.stack([(u - K2[2]) / K2[0] * depth, (v - K2[3]) / K2[1] * depth, depth], 1)
+        X1 = s * X2 @ R.T + t
+        X1[:, 2] = np.maximum(X1[:, 2], 0.5)
+        is_true = c < n_true
+        out_m = (rng.random(N) < outlier_frac) if is_true else np.ones(N, bool)
+        d1 = rng.uniform(1.5, 9.0, N)
+        u1, v1 = rng.uniform(40, IMG_W - 40, N), rng.uniform(40, IMG_H - 40, N)
+        Xr = np.stack([(u1 - K1[2]) / K1[0] * d1, (v1 - K1[3]) / K1[1] * d1, d1], 1)
+        X1 = np.where(out_m[:, None], Xr, X1 + rng.normal(size=X1.shape) * noise)
+        oct1, oct2 = rng.integers(0, N_LEVELS, N), rng.integers(0, N_LEVELS, N)
+        thr = lambda o: (9.210 * sigma2[o].astype(np.float64)).astype(np.uint32)
+        n1 = N + int(rng.integers(0, 20))
+        idx1 = np.sort(rng.choice(n1, N, replace=False)).astype(np.int32)
+        out.append(dict(X1=X1.astype(np.float32), X2=X2.astype(np.float32), thr1=thr(oct1), thr2=thr(oct2), K1=K1, K2=K2, n1=n1, idx1=idx1,
+                        meta=dict(true=is_true, R=R, t=t, s=s, outlier=out_m, oct1=oct1, oct2=oct2)))
+    return out

@@ -416,6 +416,26 @@ int  ccm_kfdb_query(ccm_kfdb* db, ccm_ctx* ctx, int n, const int32_t* word, cons
 int  ccm_kfdb_score(ccm_kfdb* db, ccm_ctx* ctx, int n, const int32_t* word, const double* value,
                     const int64_t* keys, int m, double* out);
 
+/* ---- Sim3 RANSAC (loop / map-match verification) ------------------------------------------
+ * The hypotheses of cslam::Sim3Solver::iterate (cslam/src/Sim3Solver.cpp:120-197): per hypothesis ComputeSim3 on three correspondences
+ * (:199-321) and CheckInliers (:324-348) over all of its candidate's points, bit-identical to the reference's f32 / f64 arithmetic under
+ * OpenCV 4.2 baseline-build semantics.  Stateless: the RANSAC state, the round-robin of LoopFinder / MapMatcher::ComputeSim3
+ * and the random draws stay on the host (ccm_slam_amd/host/sim3_schedule.h).
+ * K candidates in CSR over pt_off[K + 1] (pt_off[0] = 0, every candidate >= 3 points): X3Dc1 / X3Dc2 = mvX3Dc1 / mvX3Dc2 (f32 x 3 per point),
+ * K1 / K2 = fx fy cx cy per candidate, max_err1 / max_err2 = mvnMaxError1 / mvnMaxError2 (the reference's size_t thresholds).
+ * H hypotheses: hyp_cand[h] and three distinct candidate-local point indices hyp_idx[3h .. 3h+2] (the sample order of the reference).
+ * fix_scale = mbFixScale.  Out: n_inl[h] = mnInliersi, rts[13h ..] = mR12i (9, row-major), mt12i (3), ms12i; mask_off[H + 1] (written by the
+ * call) = word offsets of the inlier masks, mask[mask_off[h] ..] = mvbInliersi, one bit per point (bit i % 32 of word i / 32), mask must hold
+ * sum over h of ceil(N / 32) words.  CCM_E_ARG: null pointers, K < 1, H < 0, a candidate with N < 3, an index outside [0, N) or repeated in a
+ * hypothesis.  One H2D copy, one launch and one D2H copy on the context's stream, scratch of the context; threads calling with their own
+ * contexts run concurrently.
+ * Contract of the host schedule built on it (cslam::Sim3RansacBatch): its events equal those of the sequential reference on the same sequence
+ * of rand() values; values drawn for hypotheses after an event are kept in a per-thread FIFO and used first by the next draw, so the equality
+ * holds across calls — only WHEN glibc's global stream advances differs. */
+int  ccm_sim3_ransac_eval(ccm_ctx* ctx, int K, const int32_t* pt_off, const float* X3Dc1, const float* X3Dc2, const float* K1, const float* K2,
+                          const uint32_t* max_err1, const uint32_t* max_err2, int H, const int32_t* hyp_cand, const int32_t* hyp_idx,
+                          int fix_scale, int32_t* n_inl, float* rts, int32_t* mask_off, uint32_t* mask);
+
 #ifdef __cplusplus
 }
 #endif

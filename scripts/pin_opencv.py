@@ -13,7 +13,8 @@ liboracle.so bit for bit (integers) / exactly (fastAtan2, undistortPoints: f32).
 `tests/test_golden.py::test_oracle_matches_the_opencv_vectors_when_present` consumes every tests/golden/opencv_*.npz it finds, so a vector file produced once on a
 maintainer's box keeps the pin alive here.  Exit code: 0 all equal (or cv2 absent: nothing to do), 1 a primitive differs (the report says where).
 
-Reference call sites (cslam/src/ORBextractor.cpp): resize :1293, FAST :978 / :983, GaussianBlur :1259, fastAtan2 :113 (IC_Angle); Frame.cpp:131-160 undistortPoints.
+Reference call sites (cslam/src/ORBextractor.cpp): resize :1293, FAST :978 / :983, GaussianBlur :1259, fastAtan2 :113 (IC_Angle); Frame.cpp:131-160 undistortPoints;
+Sim3Solver.cpp:266 eigen (4x4 f32 symmetric; hal::Jacobi when OpenCV is built without Eigen) and :276 Rodrigues, compared with the Sim3 RANSAC's restatements.
 """
 from __future__ import annotations
 
@@ -68,6 +69,21 @@ def cv2_vectors(cv2):
     und = cv2.undistortPoints(pts.reshape(-1, 1, 2), Kmat, D4, None, Kmat)       # Frame.cpp:150
     vec["undistort_in"] = pts
     vec["undistort_out"] = und.reshape(-1, 2).astype(np.float32)
+    # Sim3Solver.cpp:266 cv::eigen of Horn's 4x4 f32 symmetric matrix, :276 cv::Rodrigues of an f32 rotation vector into an f32 3x3
+    # (skipped for a stand-in cv2 that does not carry them)
+    if not (hasattr(cv2, "eigen") and hasattr(cv2, "Rodrigues")):
+        return vec
+    S = rng.normal(size=(300, 4, 4)).astype(np.float32)
+    S = (S + np.transpose(S, (0, 2, 1))).astype(np.float32)
+    S[:8] = np.diag([1.0, 3.0, 2.0, 3.0]).astype(np.float32)                         # ties and already-diagonal input
+    vec["eigen_in"] = S
+    ev = [cv2.eigen(m) for m in S]
+    vec["eigen_val"] = np.stack([e[1].reshape(4) for e in ev]).astype(np.float32)
+    vec["eigen_vec"] = np.stack([e[2] for e in ev]).astype(np.float32)
+    rv = (rng.normal(size=(2000, 3)) * rng.choice([1e-9, 1e-3, 0.3, 2.5], (2000, 1))).astype(np.float32)
+    rv[:4] = 0
+    vec["rodrigues_in"] = rv
+    vec["rodrigues_out"] = np.stack([cv2.Rodrigues(v.reshape(1, 3))[0] for v in rv]).astype(np.float32)   # f32 in -> f32 out
     return vec
 
 
@@ -102,6 +118,13 @@ def compare(vec, report=print):
     yx = np.asarray(vec["atan2_in"])
     same("fastAtan2", np.array([oracle.fast_atan2(float(y), float(x)) for y, x in yx], np.float32), np.asarray(vec["atan2_out"]))
     same("undistortPoints", oracle.undistort_points(K4, D4, np.asarray(vec["undistort_in"])), np.asarray(vec["undistort_out"]))
+    if "eigen_in" in vec:   # the Sim3 RANSAC's restatements (the numpy checker of tests/test_sim3_ransac_gpu.py, the lines of csrc/sim3_ransac_math.h)
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        from test_sim3_ransac_gpu import jacobi, rodrigues
+        res = [jacobi(m) for m in np.asarray(vec["eigen_in"])]
+        same("eigen (4x4 f32 symmetric): eigenvalues", np.stack([w for w, _ in res]), np.asarray(vec["eigen_val"]))
+        same("eigen (4x4 f32 symmetric): eigenvectors", np.stack([v for _, v in res]), np.asarray(vec["eigen_vec"]))
+        same("Rodrigues (f32)", np.stack([rodrigues(v) for v in np.asarray(vec["rodrigues_in"])]), np.asarray(vec["rodrigues_out"]))
     return bad
 
 
