@@ -125,6 +125,17 @@ class BAHandle:
               self.ctx.handle)
         return out
 
+    SIZES = ("Cp", "Lp", "Lloc", "Eloc", "nOff", "max_cam_edges", "row_units_max", "pers_grid", "coarse_na", "coarse_ncb", "n_chunk", "lp_begin")
+
+    def debug_sizes(self) -> dict:
+        """Test hook: the twelve `sizes` fields of ccm_ba_debug_array by name (row_units_max > 0: the row Schur kernel is in use; n_chunk > 0: the
+        edge-parallel linearisation / back-substitution; lp_begin, Lloc: this rank's landmark slots)."""
+        v = np.zeros(len(self.SIZES), np.int32)
+        n = C.c_size_t(0)
+        check(hooks().ccm_ba_debug_array(self._h, b"sizes", C.c_void_p(_vp(v)), C.c_size_t(v.nbytes), C.byref(n)), self.ctx.handle)
+        assert n.value == v.nbytes
+        return dict(zip(self.SIZES, (int(x) for x in v)))
+
     def coarse_level(self, lam: float):
         """Test hook (ccm_ba_debug_coarse): (na camera intervals, Ac, Ainv over the na + 1 coarse nodes, P) of the two-level preconditioner, or (0, None, None, None)."""
         na = C.c_int(0)
