@@ -2,6 +2,7 @@
 // everything device-side goes through the C ABI.
 #include "ccm_host.h"
 #include "kfdb_resolve.h"
+#include "../csrc/triangulate_math.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -994,6 +995,106 @@ bool Sim3RansacBatch::next(int& cand, float R[9], float t[3], float& s, std::vec
   return true;
 }
 
+// ---- NewMapPointBatch ---------------------------------------------------------------------------------
+static_assert(sizeof(CamRecord) == sizeof(TriCam) && sizeof(TriCam) == TRI_CAM_FLOATS * sizeof(float), "camera record layout");
+
+static TriCam to_tricam(const CamRecord& c) { TriCam t; std::memcpy(&t, &c, sizeof t); return t; }
+
+NewMapPointBatch::NewMapPointBatch(HipContext* ctx, const CamRecord& cam1, std::vector<KeyPoint> keys1, std::vector<Neighbour> nb, LevelTables lv, float ratioFactor)
+    : cam1_(cam1), keys1_(std::move(keys1)), lv_(std::move(lv)), ratio_(ratioFactor) {
+  nb_.resize(nb.size());
+  for (size_t j = 0; j < nb.size(); j++) { nb_[j].cam = nb[j].cam; nb_[j].keys = std::move(nb[j].keys); nb_[j].pred = std::move(nb[j].predicted); }
+  build(ctx);
+}
+
+NewMapPointBatch::NewMapPointBatch(HipContext& ctx, const TriangulationBatch& tb, const CamRecord& cam1, const std::vector<CamRecord>& cam2,
+                                   const std::vector<Epipolar>& ep, LevelTables lv, float ratioFactor, const int32_t* octave1)
+    : cam1_(cam1), keys1_(tb.keys1()), lv_(std::move(lv)), ratio_(ratioFactor) {
+  if ((int)cam2.size() != tb.neighbours() || (int)ep.size() != tb.neighbours()) throw infrastructure_ex("NewMapPointBatch: one camera and one F12 per neighbour");
+  if (octave1) for (size_t i = 0; i < keys1_.size(); i++) keys1_[i].octave = octave1[i];
+  nb_.resize(cam2.size());
+  std::vector<int32_t> m12;
+  for (size_t j = 0; j < nb_.size(); j++) {
+    nb_[j].cam = cam2[j];
+    nb_[j].keys = tb.keys2((int)j);
+    tb.resolve((int)j, nullptr, nullptr, ep[j].F12, ep[j].ex, ep[j].ey, lv_.sigma2_2.data(), lv_.sf_2.data(), m12);
+    for (size_t i = 0; i < m12.size(); i++)   // vMatchedIndices: ascending idx1 (ORBmatcher.cpp:842-849)
+      if (m12[i] >= 0) nb_[j].pred.emplace_back((int32_t)i, m12[i]);
+  }
+  build(&ctx);
+}
+
+void NewMapPointBatch::build(HipContext* ctx) {
+  const size_t L = (size_t)lv_.nlevels;
+  if (lv_.nlevels < 1 || lv_.sigma2_1.size() != L || lv_.sf_1.size() != L || lv_.sigma2_2.size() != L || lv_.sf_2.size() != L)
+    throw infrastructure_ex("NewMapPointBatch: level tables");
+  std::vector<int32_t> off(1, 0), oct;
+  std::vector<float> xy, cam2;
+  for (Nb& nb : nb_) {
+    for (const auto& pr : nb.pred) {
+      if (pr.first < 0 || pr.first >= (int)keys1_.size() || pr.second < 0 || pr.second >= (int)nb.keys.size()) throw infrastructure_ex("NewMapPointBatch: feature index out of range");
+      const KeyPoint& k1 = keys1_[pr.first]; const KeyPoint& k2 = nb.keys[pr.second];
+      if (k1.octave < 0 || k1.octave >= lv_.nlevels || k2.octave < 0 || k2.octave >= lv_.nlevels) throw infrastructure_ex("NewMapPointBatch: octave outside the level tables");
+      xy.insert(xy.end(), {k1.x, k1.y, k2.x, k2.y});
+      oct.push_back(k1.octave); oct.push_back(k2.octave);
+    }
+    off.push_back((int32_t)(oct.size() / 2));
+    const float* c = reinterpret_cast<const float*>(&nb.cam);
+    cam2.insert(cam2.end(), c, c + TRI_CAM_FLOATS);
+    nb.order.resize(nb.pred.size());
+    for (size_t i = 0; i < nb.order.size(); i++) nb.order[i] = (int32_t)i;
+    std::sort(nb.order.begin(), nb.order.end(), [&](int32_t a, int32_t b) { return nb.pred[a] < nb.pred[b]; });
+  }
+  const size_t P = oct.size() / 2;
+  n_pred_ = (int64_t)P;
+  std::vector<uint8_t> status(std::max<size_t>(P, 1));
+  std::vector<float> x3d(std::max<size_t>(3 * P, 1));
+  if (P > 0 && ctx) {
+    std::vector<int32_t> nacc(nb_.size());
+    check(ccm_triangulate_pairs(ctx->get(), reinterpret_cast<const float*>(&cam1_), (int)nb_.size(), cam2.data(), off.data(), xy.data(), oct.data(), lv_.nlevels,
+                                lv_.sigma2_1.data(), lv_.sf_1.data(), lv_.sigma2_2.data(), lv_.sf_2.data(), ratio_, status.data(), x3d.data(), nacc.data()),
+          ctx->get(), "ccm_triangulate_pairs");
+  } else if (P > 0) {
+    const TriCam c1 = to_tricam(cam1_);
+    for (size_t j = 0; j < nb_.size(); j++) {
+      const TriCam c2 = to_tricam(nb_[j].cam);
+      for (int i = off[j]; i < off[j + 1]; i++)
+        status[i] = (uint8_t)tri_pair(c1, c2, xy[4 * i], xy[4 * i + 1], oct[2 * i], xy[4 * i + 2], xy[4 * i + 3], oct[2 * i + 1], lv_.sigma2_1.data(), lv_.sf_1.data(),
+                                      lv_.sigma2_2.data(), lv_.sf_2.data(), ratio_, &x3d[3 * (size_t)i]);
+    }
+  }
+  for (size_t j = 0; j < nb_.size(); j++) {
+    nb_[j].status.assign(status.begin() + off[j], status.begin() + off[j + 1]);
+    nb_[j].x3d.assign(x3d.begin() + 3 * (size_t)off[j], x3d.begin() + 3 * (size_t)off[j + 1]);
+  }
+}
+
+int NewMapPointBatch::points(int j, const Pairs& pairs_now, std::vector<uint8_t>& status, std::vector<float>& x3d) {
+  Nb& nb = nb_.at((size_t)j);
+  status.assign(pairs_now.size(), 0);
+  x3d.assign(3 * pairs_now.size(), 0.f);
+  const TriCam c1 = to_tricam(cam1_), c2 = to_tricam(nb.cam);
+  int n_ok = 0;
+  for (size_t i = 0; i < pairs_now.size(); i++) {
+    const auto& pr = pairs_now[i];
+    auto it = std::lower_bound(nb.order.begin(), nb.order.end(), pr, [&](int32_t a, const std::pair<int32_t, int32_t>& v) { return nb.pred[a] < v; });
+    if (it != nb.order.end() && nb.pred[*it] == pr) {
+      status[i] = nb.status[*it];
+      std::memcpy(&x3d[3 * i], &nb.x3d[3 * (size_t)*it], 3 * sizeof(float));
+      n_hit_++;
+    } else {
+      if (pr.first < 0 || pr.first >= (int)keys1_.size() || pr.second < 0 || pr.second >= (int)nb.keys.size()) throw infrastructure_ex("NewMapPointBatch: feature index out of range");
+      const KeyPoint& k1 = keys1_[pr.first]; const KeyPoint& k2 = nb.keys[pr.second];
+      if (k1.octave < 0 || k1.octave >= lv_.nlevels || k2.octave < 0 || k2.octave >= lv_.nlevels) throw infrastructure_ex("NewMapPointBatch: octave outside the level tables");
+      status[i] = (uint8_t)tri_pair(c1, c2, k1.x, k1.y, k1.octave, k2.x, k2.y, k2.octave, lv_.sigma2_1.data(), lv_.sf_1.data(), lv_.sigma2_2.data(), lv_.sf_2.data(),
+                                    ratio_, &x3d[3 * i]);
+      n_miss_++;
+    }
+    n_ok += status[i] == TRI_OK;
+  }
+  return n_ok;
+}
+
 }  // namespace cslam
 
 // ---- C entry points (ccm_host_c.h): the Python test-suite and the drop-in translation units under shim/ ---------------------------------------
@@ -1190,6 +1291,89 @@ int ccmh_tri_batch_resolve(void* h, int j, const uint8_t* has1_now, const uint8_
 }
 long long ccmh_tri_batch_candidates(void* h) { return h ? (long long)static_cast<cslam::TriangulationBatch*>(h)->candidates() : 0; }
 void ccmh_tri_batch_destroy(void* h) { delete static_cast<cslam::TriangulationBatch*>(h); }
+
+// NewMapPointBatch through C.  cam records: 21 floats each (include/ccm_hip.h, ccm_triangulate_pairs); tables: nlevels floats each.
+static cslam::LevelTables mk_tables(int nlevels, const float* s1, const float* f1, const float* s2, const float* f2) {
+  cslam::LevelTables lv;
+  if (nlevels < 1 || !s1 || !f1 || !s2 || !f2) throw cslam::infrastructure_ex("level tables");
+  lv.nlevels = nlevels;
+  lv.sigma2_1.assign(s1, s1 + nlevels); lv.sf_1.assign(f1, f1 + nlevels); lv.sigma2_2.assign(s2, s2 + nlevels); lv.sf_2.assign(f2, f2 + nlevels);
+  return lv;
+}
+void* ccmh_newpts_create(int device, const float* cam1, int N1, const float* x1, const float* y1, const int32_t* oct1, int n_nb, const float* cam2,
+                         const int32_t* N2, const float* const* x2, const float* const* y2, const int32_t* const* oct2, const int32_t* pair_off,
+                         const int32_t* idx12, int nlevels, const float* sigma2_1, const float* sf_1, const float* sigma2_2, const float* sf_2,
+                         float ratio_factor) {
+  try {
+    if (!cam1 || n_nb < 0 || (n_nb > 0 && (!cam2 || !N2 || !x2 || !y2 || !oct2 || !pair_off))) return nullptr;
+    cslam::CamRecord c1; std::memcpy(&c1, cam1, sizeof c1);
+    std::vector<cslam::NewMapPointBatch::Neighbour> nb((size_t)n_nb);
+    for (int j = 0; j < n_nb; j++) {
+      std::memcpy(&nb[j].cam, cam2 + 21 * (size_t)j, sizeof(cslam::CamRecord));
+      nb[j].keys = mk_keys(x2[j], y2[j], oct2[j], nullptr, N2[j]);
+      for (int i = pair_off[j]; i < pair_off[j + 1]; i++) nb[j].predicted.emplace_back(idx12[2 * i], idx12[2 * i + 1]);
+    }
+    return new cslam::NewMapPointBatch(device < 0 ? nullptr : &thread_context(device), c1, mk_keys(x1, y1, oct1, nullptr, N1), std::move(nb),
+                                       mk_tables(nlevels, sigma2_1, sf_1, sigma2_2, sf_2), ratio_factor);
+  } catch (const std::exception&) { return nullptr; }
+}
+void* ccmh_newpts_create_tri(int device, void* tri_batch, const int32_t* oct1, const float* cam1, const float* cam2, const float* F12, const float* exy,
+                             int nlevels, const float* sigma2_1, const float* sf_1, const float* sigma2_2, const float* sf_2, float ratio_factor) {
+  try {
+    if (!tri_batch || !cam1 || !cam2 || !F12 || !exy) return nullptr;
+    const cslam::TriangulationBatch& tb = *static_cast<cslam::TriangulationBatch*>(tri_batch);
+    const int n = tb.neighbours();
+    cslam::CamRecord c1; std::memcpy(&c1, cam1, sizeof c1);
+    std::vector<cslam::CamRecord> c2((size_t)n);
+    std::vector<cslam::NewMapPointBatch::Epipolar> ep((size_t)n);
+    for (int j = 0; j < n; j++) {
+      std::memcpy(&c2[j], cam2 + 21 * (size_t)j, sizeof(cslam::CamRecord));
+      std::memcpy(ep[j].F12, F12 + 9 * (size_t)j, 9 * sizeof(float));
+      ep[j].ex = exy[2 * j]; ep[j].ey = exy[2 * j + 1];
+    }
+    return new cslam::NewMapPointBatch(thread_context(device), tb, c1, c2, ep, mk_tables(nlevels, sigma2_1, sf_1, sigma2_2, sf_2), ratio_factor, oct1);
+  } catch (const std::exception&) { return nullptr; }
+}
+int ccmh_newpts_points(void* h, int j, int n, const int32_t* idx12, uint8_t* status, float* x3d) {
+  try {
+    if (!h || n < 0 || (n > 0 && (!idx12 || !status || !x3d))) return -1;
+    cslam::NewMapPointBatch::Pairs p((size_t)n);
+    for (int i = 0; i < n; i++) p[i] = {idx12[2 * i], idx12[2 * i + 1]};
+    std::vector<uint8_t> st; std::vector<float> x;
+    const int ok = static_cast<cslam::NewMapPointBatch*>(h)->points(j, p, st, x);
+    if (n > 0) { std::memcpy(status, st.data(), st.size()); std::memcpy(x3d, x.data(), x.size() * sizeof(float)); }
+    return ok;
+  } catch (const std::exception&) { return -1000; }
+}
+int ccmh_newpts_stats(void* h, int64_t* out3) {
+  if (!h || !out3) return -1;
+  const cslam::NewMapPointBatch& b = *static_cast<cslam::NewMapPointBatch*>(h);
+  out3[0] = b.predicted(); out3[1] = b.hits(); out3[2] = b.misses();
+  return 0;
+}
+void ccmh_newpts_destroy(void* h) { delete static_cast<cslam::NewMapPointBatch*>(h); }
+// the arguments of ccm_triangulate_pairs through the host's tri_pair on the calling thread (what points() runs for a miss; scripts/triangulate_profile.py times it)
+int ccmh_triangulate_pairs_host(const float* cam1, int S, const float* cam2, const int32_t* pair_off, const float* xy, const int32_t* oct, int nlevels,
+                                const float* sigma2_1, const float* sf_1, const float* sigma2_2, const float* sf_2, float ratio_factor, uint8_t* status,
+                                float* x3d, int32_t* n_accepted) {
+  if (S < 1 || nlevels < 1 || !cam1 || !cam2 || !pair_off || !sigma2_1 || !sf_1 || !sigma2_2 || !sf_2 || !n_accepted || pair_off[0] != 0) return -1;
+  for (int s = 0; s < S; s++) if (pair_off[s + 1] < pair_off[s]) return -1;
+  const int P = pair_off[S];
+  if (P > 0 && (!xy || !oct || !status || !x3d)) return -1;
+  for (int i = 0; i < 2 * P; i++) if (oct[i] < 0 || oct[i] >= nlevels) return -1;
+  TriCam c1; std::memcpy(&c1, cam1, sizeof c1);
+  for (int s = 0; s < S; s++) {
+    TriCam c2; std::memcpy(&c2, cam2 + 21 * (size_t)s, sizeof c2);
+    int32_t n = 0;
+    for (int i = pair_off[s]; i < pair_off[s + 1]; i++) {
+      status[i] = (uint8_t)tri_pair(c1, c2, xy[4 * i], xy[4 * i + 1], oct[2 * i], xy[4 * i + 2], xy[4 * i + 3], oct[2 * i + 1], sigma2_1, sf_1, sigma2_2, sf_2,
+                                    ratio_factor, x3d + 3 * (size_t)i);
+      n += status[i] == TRI_OK;
+    }
+    n_accepted[s] = n;
+  }
+  return 0;
+}
 
 int ccmh_search_for_initialization(int device, const float* x1, const float* y1, const int32_t* oct1, const float* a1, const uint8_t* d1, int N1,
                                    const float* x2, const float* y2, const int32_t* oct2, const float* a2, const uint8_t* d2, int N2,

@@ -187,6 +187,8 @@ class TriangulationBatch {
   // has1_now / has2_now: nullptr = the flags of the build
   int resolve(int j, const uint8_t* has1_now, const uint8_t* has2_now, const float F12[9], float ex, float ey, const float* sigma2_2, const float* scaleFactors2,
               std::vector<int32_t>& matches12) const;
+  const std::vector<KeyPoint>& keys1() const { return keys1_; }
+  const std::vector<KeyPoint>& keys2(int j) const { return nb_.at((size_t)j).keys; }
  private:
   struct Nb { std::vector<KeyPoint> keys; std::vector<uint8_t> has; std::vector<int32_t> q_of, off, idx; std::vector<uint16_t> dist; };
   std::vector<KeyPoint> keys1_; std::vector<uint8_t> has1_;
@@ -215,6 +217,42 @@ class FuseBatch {
   std::vector<Tg> tg_;
   int64_t n_cand_ = 0;
   int dist_threshold_;
+};
+
+// The arithmetic between SearchForTriangulation and `new MapPoint` in LocalMapping::CreateNewMapPoints (cslam/src/Mapping.cpp:353-448): per match the ray-parallax
+// gate, the linear triangulation (cv::SVD::compute on a 4x4 f32 matrix), two depth tests, two chi2 reprojection gates and the scale-consistency gate.  The reference's
+// loop is sequential across neighbours — a match accepted for neighbour j gives feature idx1 a map point, which changes the matches of neighbour j + 1 — so the batch
+// predicts, then answers exactly, as FuseBatch does: at build time the matches of EVERY neighbour (as the flags of that moment give them) go to the device as ONE
+// ccm_triangulate_pairs launch; points(j, pairs_now) then takes the matches the caller's real, sequential resolve(j, ...) returned, answers those that are in the table
+// (key (j, idx1, idx2)) from it and computes the others on the host with the same tri_pair (csrc/triangulate_math.h compiled by g++).  tri_pair is a pure function of
+// the match, so the answers equal the per-neighbour sequence bit for bit.  Everything the batch needs is copied at build time.
+struct CamRecord { float Rcw[9], tcw[3], Ow[3], fx, fy, cx, cy, invfx, invfy; };   // GetRotation / GetTranslation / GetCameraCenter (row-major) and the intrinsics
+struct LevelTables { int nlevels = 0; std::vector<float> sigma2_1, sf_1, sigma2_2, sf_2; };   // mvLevelSigma2 / mvScaleFactors of the new keyframe (1) and the neighbours (2)
+class NewMapPointBatch {
+ public:
+  using Pairs = std::vector<std::pair<int32_t, int32_t>>;   // vMatchedIndices: (idx1, idx2)
+  struct Neighbour { CamRecord cam; std::vector<KeyPoint> keys; Pairs predicted; };
+  struct Epipolar { float F12[9]; float ex, ey; };
+  // ctx == nullptr asks for the host evaluator by name (a machine without a device, the CPU tests): the predicted matches are then computed by the host's tri_pair.
+  // With a context, a device error throws — there is no fall-back.
+  NewMapPointBatch(HipContext* ctx, const CamRecord& cam1, std::vector<KeyPoint> keys1, std::vector<Neighbour> nb, LevelTables lv, float ratioFactor);
+  // the prediction taken from a TriangulationBatch: resolve(j, flags of the build, ...) of every neighbour.  octave1 (nullable, [N1]): the octaves of the new
+  // keyframe's features where the batch's keys carry none (a batch created through ccmh_tri_batch_create)
+  NewMapPointBatch(HipContext& ctx, const TriangulationBatch& tb, const CamRecord& cam1, const std::vector<CamRecord>& cam2, const std::vector<Epipolar>& ep,
+                   LevelTables lv, float ratioFactor, const int32_t* octave1 = nullptr);
+  int neighbours() const { return (int)nb_.size(); }
+  // status[n] / x3d[3n] of the matches of neighbour j as they are NOW (codes of ccm_triangulate_pairs); returns the number accepted
+  int points(int j, const Pairs& pairs_now, std::vector<uint8_t>& status, std::vector<float>& x3d);
+  int64_t predicted() const { return n_pred_; }
+  int64_t hits() const { return n_hit_; }
+  int64_t misses() const { return n_miss_; }
+ private:
+  void build(HipContext* ctx);
+  struct Nb { CamRecord cam; std::vector<KeyPoint> keys; Pairs pred; std::vector<uint8_t> status; std::vector<float> x3d; std::vector<int32_t> order; };
+  CamRecord cam1_; std::vector<KeyPoint> keys1_;
+  std::vector<Nb> nb_;
+  LevelTables lv_; float ratio_;
+  int64_t n_pred_ = 0, n_hit_ = 0, n_miss_ = 0;
 };
 
 // ---------------------------------------------------------------------------------------------------

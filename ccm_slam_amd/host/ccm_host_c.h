@@ -21,6 +21,18 @@ void* ccmh_tri_batch_create(int device, float nnratio, int check_ori, const int3
 int ccmh_tri_batch_resolve(void* h, int j, const uint8_t* has1_now, const uint8_t* has2_now, const float* F12, float ex, float ey, const float* sigma2_2, const float* sf2, int32_t* matches12);
 long long ccmh_tri_batch_candidates(void* h);
 void ccmh_tri_batch_destroy(void* h);
+/* the arithmetic between SearchForTriangulation and `new MapPoint` (Mapping.cpp:353-448) for every neighbour of a new keyframe (cslam::NewMapPointBatch): create sends the
+ * predicted matches (idx12 = idx1 idx2 per match, CSR over pair_off[n_nb + 1]) out as ONE ccm_triangulate_pairs launch; points answers the matches neighbour j has NOW from
+ * that table, the others through the same arithmetic on the host, and returns the number accepted (status / x3d as ccm_triangulate_pairs).  cam records: 21 floats each.
+ * device < 0 asks for the host evaluator by name (no device is touched); with a device, a device error makes create return NULL.  create_tri takes the prediction from a
+ * ccmh_tri_batch handle resolved with the flags of its build (F12 9 floats and exy = epipole x y per neighbour; oct1 = octaves of keyframe 1's features).
+ * stats: out3 = predicted, hit, missed matches. */
+void* ccmh_newpts_create(int device, const float* cam1, int N1, const float* x1, const float* y1, const int32_t* oct1, int n_nb, const float* cam2, const int32_t* N2, const float* const* x2, const float* const* y2, const int32_t* const* oct2, const int32_t* pair_off, const int32_t* idx12, int nlevels, const float* sigma2_1, const float* sf_1, const float* sigma2_2, const float* sf_2, float ratio_factor);
+void* ccmh_newpts_create_tri(int device, void* tri_batch, const int32_t* oct1, const float* cam1, const float* cam2, const float* F12, const float* exy, int nlevels, const float* sigma2_1, const float* sf_1, const float* sigma2_2, const float* sf_2, float ratio_factor);
+int ccmh_newpts_points(void* h, int j, int n, const int32_t* idx12, uint8_t* status, float* x3d);
+int ccmh_newpts_stats(void* h, int64_t* out3);
+void ccmh_newpts_destroy(void* h);
+int ccmh_triangulate_pairs_host(const float* cam1, int S, const float* cam2, const int32_t* pair_off, const float* xy, const int32_t* oct, int nlevels, const float* sigma2_1, const float* sf_1, const float* sigma2_2, const float* sf_2, float ratio_factor, uint8_t* status, float* x3d, int32_t* n_accepted);
 int ccmh_search_for_initialization(int device, const float* x1, const float* y1, const int32_t* oct1, const float* a1, const uint8_t* d1, int N1, const float* x2, const float* y2, const int32_t* oct2, const float* a2, const uint8_t* d2, int N2, float minX, float minY, float maxX, float maxY, float* prev_xy, int window, float nnratio, int check_ori, int32_t* matches12);
 int ccmh_projected_window_search(int device, const float* kx, const float* ky, const int32_t* oct, const uint8_t* kdesc, int N, float minX, float minY, float maxX, float maxY, const float* scale_factors, const float* inv_sigma2, int n_pts, const uint8_t* valid, const float* u, const float* v, const int32_t* level, const uint8_t* pdesc, float th, int chi2_gate, int dist_threshold, int32_t* matched, int claim, const uint8_t* no_claim, int32_t* best_idx, int32_t* best_dist);
 void* ccmh_fuse_batch_create_cand(int device, int S, const int32_t* kf_off, const float* kx, const float* ky, const int32_t* oct, const uint8_t* kdesc, const float* const* inv_sigma2, const int32_t* pt_off, const uint8_t* valid, const float* u, const float* v, const int32_t* level, const uint8_t* pdesc, const int32_t* cand_off, const int32_t* cand_base, const int32_t* cand_idx, int chi2_gate, int dist_threshold);

@@ -436,6 +436,24 @@ int  ccm_sim3_ransac_eval(ccm_ctx* ctx, int K, const int32_t* pt_off, const floa
                           const uint32_t* max_err1, const uint32_t* max_err2, int H, const int32_t* hyp_cand, const int32_t* hyp_idx,
                           int fix_scale, int32_t* n_inl, float* rts, int32_t* mask_off, uint32_t* mask);
 
+/* ---- triangulation of new map points ---------------------------------------------------------
+ * The per-match arithmetic of LocalMapping::CreateNewMapPoints (cslam/src/Mapping.cpp:353-448) for every match of up to 20 neighbours in ONE
+ * launch: ray-parallax gate, linear triangulation (cv::SVD::compute on a 4x4 f32 matrix), the two depth tests, the two chi2 reprojection gates
+ * and the scale-consistency gate, bit-identical to the reference's f32 / f64 arithmetic under OpenCV 4.2 baseline-build semantics
+ * (the lines are ccm_slam_amd/csrc/triangulate_math.h, which also compiles for the host).  Stateless.
+ * A camera record is 21 floats: Rcw (9, row-major), tcw (3), Ow (3), fx fy cx cy invfx invfy.  cam1 = the new keyframe, cam2 = one record per
+ * neighbour group.  S groups in CSR over pair_off[S + 1] (pair_off[0] = 0, groups may be empty), P = pair_off[S] matches: xy = x1 y1 x2 y2 of
+ * mvKeysUn per match, oct = octave1 octave2 per match.  sigma2_* / sf_* = mvLevelSigma2 / mvScaleFactors of the new keyframe (1) and of the
+ * neighbours (2), nlevels entries each.  ratioFactor = 1.5f * mfScaleFactor.
+ * Out: status[P] = the first gate at which the reference's loop `continue`s — 0 accepted, 1 parallax, 2 x3D(3) == 0, 3 z1 <= 0, 4 z2 <= 0,
+ * 5 / 6 reprojection in keyframe 1 / 2, 7 a zero distance, 8 scale ratio; x3d[3P] = the point reached so far (NaN for status 1);
+ * n_accepted[S] = matches with status 0 per group.
+ * CCM_E_ARG: null pointers, S < 1, a decreasing pair_off, an octave outside [0, nlevels).  P == 0 succeeds with no launch.  One H2D copy, one
+ * launch and one D2H copy on the context's stream, scratch of the context; threads calling with their own contexts run concurrently. */
+int  ccm_triangulate_pairs(ccm_ctx* ctx, const float* cam1 /* 21 */, int S, const float* cam2 /* 21 S */, const int32_t* pair_off /* S+1 */,
+                           const float* xy /* 4 P */, const int32_t* oct /* 2 P */, int nlevels, const float* sigma2_1, const float* sf_1,
+                           const float* sigma2_2, const float* sf_2, float ratioFactor, uint8_t* status, float* x3d, int32_t* n_accepted);
+
 #ifdef __cplusplus
 }
 #endif

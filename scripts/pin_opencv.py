@@ -14,7 +14,8 @@ liboracle.so bit for bit (integers) / exactly (fastAtan2, undistortPoints: f32).
 maintainer's box keeps the pin alive here.  Exit code: 0 all equal (or cv2 absent: nothing to do), 1 a primitive differs (the report says where).
 
 Reference call sites (cslam/src/ORBextractor.cpp): resize :1293, FAST :978 / :983, GaussianBlur :1259, fastAtan2 :113 (IC_Angle); Frame.cpp:131-160 undistortPoints;
-Sim3Solver.cpp:266 eigen (4x4 f32 symmetric; hal::Jacobi when OpenCV is built without Eigen) and :276 Rodrigues, compared with the Sim3 RANSAC's restatements.
+Sim3Solver.cpp:266 eigen (4x4 f32 symmetric; hal::Jacobi when OpenCV is built without Eigen) and :276 Rodrigues, compared with the Sim3 RANSAC's restatements;
+Mapping.cpp:383 SVD::compute on the 4x4 f32 matrix of the linear triangulation (cv2.SVDecomp: w and vt), compared with jacobi_svd4 of tests/test_triangulate_cpu.py.
 """
 from __future__ import annotations
 
@@ -84,7 +85,31 @@ def cv2_vectors(cv2):
     rv[:4] = 0
     vec["rodrigues_in"] = rv
     vec["rodrigues_out"] = np.stack([cv2.Rodrigues(v.reshape(1, 3))[0] for v in rv]).astype(np.float32)   # f32 in -> f32 out
+    # Mapping.cpp:383 cv::SVD::compute(A, w, u, vt, MODIFY_A | FULL_UV) on the 4x4 f32 matrix of the linear triangulation: w and vt (u is not used by the reference)
+    if hasattr(cv2, "SVDecomp"):
+        vec.update(svd4_vectors(cv2))
     return vec
+
+
+def svd4_inputs():
+    """4x4 f32 matrices for the SVDecomp comparison: the triangulation matrices of two synthetic scenes, random matrices, diagonal / tied / rank-deficient ones"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from ccm_slam_amd import triangulate as T
+    from test_triangulate_cpu import ref_pairs
+    rng = np.random.default_rng(13)
+    A = [ref_pairs(*T.flat(T.make_pair_scene(seed=s, S=4, n_pairs=100)), details=True)[2]["A"] for s in (300, 301)]
+    A.append(rng.normal(size=(200, 4, 4)).astype(np.float32))
+    special = np.zeros((4, 4, 4), np.float32)
+    special[0] = np.diag([1.0, 3.0, 2.0, 3.0]); special[1] = np.diag([0.0, 2.0, 0.0, 1.0])
+    special[2] = np.outer([1, 2, 3, 4], [1, -1, 2, 0.5]); special[3, :, :3] = rng.normal(size=(4, 3))
+    A.append(special)
+    return np.ascontiguousarray(np.concatenate(A), np.float32)
+
+
+def svd4_vectors(cv2):
+    A = svd4_inputs()
+    res = [cv2.SVDecomp(m.copy(), flags=cv2.SVD_MODIFY_A | cv2.SVD_FULL_UV) for m in A]
+    return {"svd4_in": A, "svd4_w": np.stack([r[0].reshape(4) for r in res]).astype(np.float32), "svd4_vt": np.stack([r[2] for r in res]).astype(np.float32)}
 
 
 def compare(vec, report=print):
@@ -125,6 +150,12 @@ def compare(vec, report=print):
         same("eigen (4x4 f32 symmetric): eigenvalues", np.stack([w for w, _ in res]), np.asarray(vec["eigen_val"]))
         same("eigen (4x4 f32 symmetric): eigenvectors", np.stack([v for _, v in res]), np.asarray(vec["eigen_vec"]))
         same("Rodrigues (f32)", np.stack([rodrigues(v) for v in np.asarray(vec["rodrigues_in"])]), np.asarray(vec["rodrigues_out"]))
+    if "svd4_in" in vec:    # the triangulation's restatement (jacobi_svd4 of tests/test_triangulate_cpu.py, the lines of csrc/triangulate_math.h)
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        from test_triangulate_cpu import jacobi_svd4
+        w, vt = jacobi_svd4(np.asarray(vec["svd4_in"]))
+        same("SVDecomp (4x4 f32): singular values", w.astype(np.float32), np.asarray(vec["svd4_w"]))
+        same("SVDecomp (4x4 f32): vt", vt, np.asarray(vec["svd4_vt"]))
     return bad
 
 
