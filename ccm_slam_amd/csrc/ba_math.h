@@ -5,10 +5,15 @@
 //   RobustKernelHuber::robustify                          core/robust_kernel_impl.cpp:78-90
 // Eigen's Quaterniond(R), q*v and toRotationMatrix are restated from their published algorithms.
 #pragma once
-#include <hip/hip_runtime.h>
 #include <math.h>
 
+// the host mirror (host/ccm_host.cpp) compiles these lines with g++ through sim3_correct_math.h
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
 #define BA_HD __host__ __device__ __forceinline__
+#else
+#define BA_HD static inline
+#endif
 
 struct BaPose { double qx, qy, qz, qw, tx, ty, tz; };
 

@@ -3,6 +3,8 @@
 #include "ccm_host.h"
 #include "kfdb_resolve.h"
 #include "../csrc/triangulate_math.h"
+#include "../csrc/sim3_correct_math.h"
+#include <climits>
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -1095,6 +1097,120 @@ int NewMapPointBatch::points(int j, const Pairs& pairs_now, std::vector<uint8_t>
   return n_ok;
 }
 
+// ---- Sim3MapCorrection ----------------------------------------------------------------------------------
+// ccm_sim3_correct_map's arguments after the context through csrc/sim3_correct_math.h on the calling thread: same checks, same lines, same order of work
+// (every keyframe first, then every point).  -1 where the device entry returns CCM_E_ARG.
+int sim3_correct_map_host(int n_kf, const float* Tiw, int cur, const float* Twc, const double* Scw, double* S_non, double* S_cor, int n_obs_kf, const float* kf_center,
+                          const int32_t* kf_rank, int n_pt, const float* pos, const int32_t* owner, const int32_t* owner_rank, const int32_t* obs_off,
+                          const int32_t* obs_kf, const int32_t* ref_kf, const int32_t* ref_level, const float* scale_factors, int n_levels, float* pos_out, float* normal,
+                          float* min_dist, float* max_dist, float* Tiw_new, float* center_new) {
+  if (n_kf < 1 || n_obs_kf < n_kf || n_pt < 0 || n_levels < 1 || !S_non || !S_cor || !kf_center || !kf_rank || !scale_factors || !Tiw_new || !center_new) return -1;
+  if (Tiw && (!Twc || !Scw || cur < 0 || cur >= n_kf)) return -1;
+  if (n_pt > 0) {
+    if (!pos || !owner || !owner_rank || !obs_off || !ref_kf || !ref_level || !pos_out || !normal || !min_dist || !max_dist || obs_off[0] != 0) return -1;
+    for (int i = 0; i < n_pt; i++)
+      if (obs_off[i + 1] < obs_off[i] || owner[i] < 0 || owner[i] >= n_kf || ref_kf[i] < 0 || ref_kf[i] >= n_obs_kf || ref_level[i] < 0 || ref_level[i] >= n_levels) return -1;
+    if (obs_off[n_pt] && !obs_kf) return -1;
+    for (int k = 0; k < obs_off[n_pt]; k++) if (obs_kf[k] < 0 || obs_kf[k] >= n_obs_kf) return -1;
+  }
+  std::vector<Sim3d> swi((size_t)n_kf);
+  const Sim3d scw = Tiw ? sim3_load(Scw) : Sim3d{0, 0, 0, 1, 0, 0, 0, 1};
+  for (int i = 0; i < n_kf; i++) {
+    Sim3d non = sim3_load(S_non + 8 * (size_t)i), cor = sim3_load(S_cor + 8 * (size_t)i);
+    s3c_keyframe(Tiw ? Tiw + 12 * (size_t)i : nullptr, i == cur, Twc, scw, non, cor, swi[i], Tiw_new + 12 * (size_t)i, center_new + 3 * (size_t)i);
+    if (Tiw) { sim3_store(S_non + 8 * (size_t)i, non); sim3_store(S_cor + 8 * (size_t)i, cor); }
+  }
+  for (int i = 0; i < n_pt; i++) {
+    float p[3];
+    s3c_point(sim3_load(S_non + 8 * (size_t)owner[i]), swi[owner[i]], pos + 3 * (size_t)i, p);
+    s3c_normal_depth(p, obs_off[i], obs_off[i + 1], obs_kf, n_kf, kf_rank, owner_rank[i], kf_center, center_new, ref_kf[i], ref_level[i], scale_factors, n_levels,
+                     normal + 3 * (size_t)i, min_dist[i], max_dist[i]);
+    pos_out[3 * (size_t)i] = p[0]; pos_out[3 * (size_t)i + 1] = p[1]; pos_out[3 * (size_t)i + 2] = p[2];
+  }
+  return 0;
+}
+
+static void s3c_check_points(const Sim3MapCorrection::Points& p) {
+  const size_t n = p.min_dist.size();
+  if (p.pos.size() != 3 * n || p.normal.size() != 3 * n || p.max_dist.size() != n || p.ref_kf.size() != n || p.ref_level.size() != n || p.obs_off.size() != n + 1 ||
+      p.obs_off[0] != 0 || (size_t)p.obs_off[n] != p.obs_kf.size())
+    throw infrastructure_ex("Sim3MapCorrection: point arrays");
+}
+
+Sim3MapCorrection::Sim3MapCorrection(HipContext* ctx, int n_kf, std::vector<float> Tiw, std::vector<float> center, int cur, const float Twc[12], const double Scw[8],
+                                     const std::vector<int32_t>& list_off, const std::vector<int32_t>& list_pt, const std::vector<uint8_t>& list_skip, Points pts,
+                                     std::vector<float> scale_factors)
+    : n_kf_(n_kf), pts_(std::move(pts)), sf_(std::move(scale_factors)) {
+  s3c_check_points(pts_);
+  if (n_kf < 1 || Tiw.size() != 12 * (size_t)n_kf || center.size() < 3 * (size_t)n_kf || center.size() % 3 || list_off.size() != (size_t)n_kf + 1 || list_off[0] != 0 ||
+      (size_t)list_off[n_kf] != list_pt.size() || list_skip.size() != list_pt.size() || !Twc || !Scw)
+    throw infrastructure_ex("Sim3MapCorrection: keyframe arrays");
+  // the walk: a point belongs to the first keyframe that lists it through an entry that is not skipped (a second entry of the same keyframe finds it tagged)
+  tag_.assign(pts_.min_dist.size(), -1);
+  for (int i = 0; i < n_kf; i++) {
+    if (list_off[i + 1] < list_off[i]) throw infrastructure_ex("Sim3MapCorrection: list_off decreases");
+    for (int e = list_off[i]; e < list_off[i + 1]; e++) {
+      const int32_t p = list_pt[e];
+      if (p < 0 || list_skip[e]) continue;
+      if ((size_t)p >= tag_.size()) throw infrastructure_ex("Sim3MapCorrection: point index out of range");
+      if (tag_[p] < 0) tag_[p] = i;
+    }
+  }
+  run(ctx, Tiw.data(), cur, Twc, Scw, center, -1);
+}
+
+Sim3MapCorrection::Sim3MapCorrection(HipContext* ctx, int n_kf, std::vector<float> center, std::vector<double> S_non, std::vector<double> S_cor,
+                                     const std::vector<int32_t>& pt_kf, Points pts, std::vector<float> scale_factors)
+    : n_kf_(n_kf), pts_(std::move(pts)), sf_(std::move(scale_factors)), S_non_(std::move(S_non)), S_cor_(std::move(S_cor)) {
+  s3c_check_points(pts_);
+  if (n_kf < 1 || center.size() < 3 * (size_t)n_kf || center.size() % 3 || S_non_.size() != 8 * (size_t)n_kf || S_cor_.size() != 8 * (size_t)n_kf ||
+      pt_kf.size() != pts_.min_dist.size())
+    throw infrastructure_ex("Sim3MapCorrection: keyframe arrays");
+  tag_.assign(pt_kf.begin(), pt_kf.end());
+  for (int32_t& t : tag_) { if (t >= n_kf) throw infrastructure_ex("Sim3MapCorrection: keyframe index out of range"); if (t < 0) t = -1; }
+  run(ctx, nullptr, 0, nullptr, nullptr, center, INT32_MAX);
+}
+
+// epilogue_rank < 0: loop form, a point's rank is its owner's
+void Sim3MapCorrection::run(HipContext* ctx, const float* Tiw, int cur, const float* Twc, const double* Scw, const std::vector<float>& center, int32_t epilogue_rank) {
+  const int n_obs_kf = (int)(center.size() / 3);
+  std::vector<int32_t> rank((size_t)n_obs_kf, INT32_MAX);
+  for (int i = 0; i < n_kf_; i++) rank[i] = i;
+  // the owned points, compacted in point order
+  std::vector<int32_t> sel, owner, owner_rank, off(1, 0), okf, ref, lvl;
+  std::vector<float> pos, nrm, dmin, dmax;
+  for (size_t p = 0; p < tag_.size(); p++) {
+    if (tag_[p] < 0) continue;
+    sel.push_back((int32_t)p);
+    owner.push_back(tag_[p]); owner_rank.push_back(epilogue_rank < 0 ? rank[tag_[p]] : epilogue_rank);
+    if (pts_.obs_off[p + 1] < pts_.obs_off[p]) throw infrastructure_ex("Sim3MapCorrection: obs_off decreases");
+    okf.insert(okf.end(), pts_.obs_kf.begin() + pts_.obs_off[p], pts_.obs_kf.begin() + pts_.obs_off[p + 1]);
+    off.push_back((int32_t)okf.size());
+    ref.push_back(pts_.ref_kf[p]); lvl.push_back(pts_.ref_level[p]);
+    pos.insert(pos.end(), pts_.pos.begin() + 3 * p, pts_.pos.begin() + 3 * p + 3);
+    nrm.insert(nrm.end(), pts_.normal.begin() + 3 * p, pts_.normal.begin() + 3 * p + 3);
+    dmin.push_back(pts_.min_dist[p]); dmax.push_back(pts_.max_dist[p]);
+  }
+  const int n = (int)sel.size();
+  S_non_.resize(8 * (size_t)n_kf_); S_cor_.resize(8 * (size_t)n_kf_);
+  Tiw_new_.assign(12 * (size_t)n_kf_, 0.f); center_new_.assign(3 * (size_t)n_kf_, 0.f);
+  if (ctx) {
+    check(ccm_sim3_correct_map(ctx->get(), n_kf_, Tiw, cur, Twc, Scw, S_non_.data(), S_cor_.data(), n_obs_kf, center.data(), rank.data(), n, pos.data(), owner.data(),
+                               owner_rank.data(), off.data(), okf.data(), ref.data(), lvl.data(), sf_.data(), (int)sf_.size(), pos.data(), nrm.data(), dmin.data(),
+                               dmax.data(), Tiw_new_.data(), center_new_.data()),
+          ctx->get(), "ccm_sim3_correct_map");
+  } else if (sim3_correct_map_host(n_kf_, Tiw, cur, Twc, Scw, S_non_.data(), S_cor_.data(), n_obs_kf, center.data(), rank.data(), n, pos.data(), owner.data(),
+                                   owner_rank.data(), off.data(), okf.data(), ref.data(), lvl.data(), sf_.data(), (int)sf_.size(), pos.data(), nrm.data(), dmin.data(),
+                                   dmax.data(), Tiw_new_.data(), center_new_.data())) {
+    throw infrastructure_ex("Sim3MapCorrection: bad arguments");
+  }
+  for (int i = 0; i < n; i++) {
+    const size_t p = (size_t)sel[i];
+    std::memcpy(&pts_.pos[3 * p], &pos[3 * (size_t)i], 12); std::memcpy(&pts_.normal[3 * p], &nrm[3 * (size_t)i], 12);
+    pts_.min_dist[p] = dmin[i]; pts_.max_dist[p] = dmax[i];
+  }
+}
+
 }  // namespace cslam
 
 // ---- C entry points (ccm_host_c.h): the Python test-suite and the drop-in translation units under shim/ ---------------------------------------
@@ -1373,6 +1489,65 @@ int ccmh_triangulate_pairs_host(const float* cam1, int S, const float* cam2, con
     n_accepted[s] = n;
   }
   return 0;
+}
+
+// Sim3MapCorrection through C
+static cslam::Sim3MapCorrection::Points mk_s3c_points(int n_pt, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const int32_t* obs_off,
+                                                      const int32_t* obs_kf, const int32_t* ref_kf, const int32_t* ref_level) {
+  cslam::Sim3MapCorrection::Points p;
+  if (n_pt < 0 || (n_pt > 0 && (!pos || !normal || !min_dist || !max_dist || !obs_off || !ref_kf || !ref_level))) throw cslam::infrastructure_ex("points");
+  const size_t n = (size_t)n_pt;
+  p.obs_off.assign(1, 0);
+  if (n) {
+    p.pos.assign(pos, pos + 3 * n); p.normal.assign(normal, normal + 3 * n); p.min_dist.assign(min_dist, min_dist + n); p.max_dist.assign(max_dist, max_dist + n);
+    p.obs_off.assign(obs_off, obs_off + n + 1); p.ref_kf.assign(ref_kf, ref_kf + n); p.ref_level.assign(ref_level, ref_level + n);
+    if (obs_off[n] < 0 || (obs_off[n] > 0 && !obs_kf)) throw cslam::infrastructure_ex("points");
+    p.obs_kf.assign(obs_kf, obs_kf + obs_off[n]);
+  }
+  return p;
+}
+void* ccmh_sim3corr_create_loop(int device, int n_kf, int n_obs_kf, const float* Tiw, const float* center, int cur, const float* Twc, const double* Scw,
+                                const int32_t* list_off, const int32_t* list_pt, const uint8_t* list_skip, int n_pt, const float* pos, const float* normal,
+                                const float* min_dist, const float* max_dist, const int32_t* obs_off, const int32_t* obs_kf, const int32_t* ref_kf, const int32_t* ref_level,
+                                const float* scale_factors, int n_levels) {
+  try {
+    if (n_kf < 1 || n_obs_kf < n_kf || !Tiw || !center || !Twc || !Scw || !list_off || n_levels < 1 || !scale_factors) return nullptr;
+    const int ne = list_off[n_kf];
+    if (ne < 0 || (ne > 0 && (!list_pt || !list_skip))) return nullptr;
+    return new cslam::Sim3MapCorrection(device < 0 ? nullptr : &thread_context(device), n_kf, std::vector<float>(Tiw, Tiw + 12 * (size_t)n_kf),
+                                        std::vector<float>(center, center + 3 * (size_t)n_obs_kf), cur, Twc, Scw, std::vector<int32_t>(list_off, list_off + n_kf + 1),
+                                        std::vector<int32_t>(list_pt, list_pt + ne), std::vector<uint8_t>(list_skip, list_skip + ne),
+                                        mk_s3c_points(n_pt, pos, normal, min_dist, max_dist, obs_off, obs_kf, ref_kf, ref_level),
+                                        std::vector<float>(scale_factors, scale_factors + n_levels));
+  } catch (const std::exception&) { return nullptr; }
+}
+void* ccmh_sim3corr_create_epilogue(int device, int n_kf, int n_obs_kf, const float* center, const double* S_non, const double* S_cor, const int32_t* pt_kf, int n_pt,
+                                    const float* pos, const float* normal, const float* min_dist, const float* max_dist, const int32_t* obs_off, const int32_t* obs_kf,
+                                    const int32_t* ref_kf, const int32_t* ref_level, const float* scale_factors, int n_levels) {
+  try {
+    if (n_kf < 1 || n_obs_kf < n_kf || !center || !S_non || !S_cor || n_pt < 0 || (n_pt > 0 && !pt_kf) || n_levels < 1 || !scale_factors) return nullptr;
+    return new cslam::Sim3MapCorrection(device < 0 ? nullptr : &thread_context(device), n_kf, std::vector<float>(center, center + 3 * (size_t)n_obs_kf),
+                                        std::vector<double>(S_non, S_non + 8 * (size_t)n_kf), std::vector<double>(S_cor, S_cor + 8 * (size_t)n_kf),
+                                        std::vector<int32_t>(pt_kf, pt_kf + n_pt), mk_s3c_points(n_pt, pos, normal, min_dist, max_dist, obs_off, obs_kf, ref_kf, ref_level),
+                                        std::vector<float>(scale_factors, scale_factors + n_levels));
+  } catch (const std::exception&) { return nullptr; }
+}
+int ccmh_sim3corr_results(void* h, float* pos, float* normal, float* min_dist, float* max_dist, int32_t* tag, float* Tiw_new, float* center_new, double* S_non,
+                          double* S_cor) {
+  if (!h) return -1;
+  const cslam::Sim3MapCorrection& c = *static_cast<cslam::Sim3MapCorrection*>(h);
+  auto out = [](auto* dst, const auto& v) { if (dst && !v.empty()) std::memcpy(dst, v.data(), v.size() * sizeof(v[0])); };
+  out(pos, c.points().pos); out(normal, c.points().normal); out(min_dist, c.points().min_dist); out(max_dist, c.points().max_dist);
+  out(tag, c.tag()); out(Tiw_new, c.poses()); out(center_new, c.centers()); out(S_non, c.nonCorrectedSim3()); out(S_cor, c.correctedSim3());
+  return 0;
+}
+void ccmh_sim3corr_destroy(void* h) { delete static_cast<cslam::Sim3MapCorrection*>(h); }
+int ccmh_sim3_correct_map_host(int n_kf, const float* Tiw, int cur, const float* Twc, const double* Scw, double* S_non, double* S_cor, int n_obs_kf, const float* kf_center,
+                               const int32_t* kf_rank, int n_pt, const float* pos, const int32_t* owner, const int32_t* owner_rank, const int32_t* obs_off,
+                               const int32_t* obs_kf, const int32_t* ref_kf, const int32_t* ref_level, const float* scale_factors, int n_levels, float* pos_out,
+                               float* normal, float* min_dist, float* max_dist, float* Tiw_new, float* center_new) {
+  return cslam::sim3_correct_map_host(n_kf, Tiw, cur, Twc, Scw, S_non, S_cor, n_obs_kf, kf_center, kf_rank, n_pt, pos, owner, owner_rank, obs_off, obs_kf, ref_kf, ref_level,
+                                      scale_factors, n_levels, pos_out, normal, min_dist, max_dist, Tiw_new, center_new);
 }
 
 int ccmh_search_for_initialization(int device, const float* x1, const float* y1, const int32_t* oct1, const float* a1, const uint8_t* d1, int N1,

@@ -255,6 +255,45 @@ class NewMapPointBatch {
   int64_t n_pred_ = 0, n_hit_ = 0, n_miss_ = 0;
 };
 
+// The Sim3 correction of a closed loop's or merged map's keyframes and map points (LoopFinder.cpp:543-613, MapMerger.cpp:289-395) and the write-back of the
+// essential-graph optimisers (Optimizer.cpp:1279-1330) as ONE ccm_sim3_correct_map call.  The reference's loop is sequential: keyframe i of the walk corrects
+// the points it lists that no earlier keyframe corrected, each point updating its normal and depth at once, and only then takes its new pose.  So a point is
+// OWNED by the first keyframe of the walk that lists it (entry not null, not bad, not tagged already), and the camera centre keyframe k shows to that point's
+// normal is the corrected one iff rank(k) < rank(owner).  The class flattens the caller's lists into owners and ranks; the graph calls
+// (SetWorldPos, the tags, SetPose, UpdateConnections) stay the caller's.  The walk order is the caller's: the reference walks a std::map keyed by pointer.
+// ctx == nullptr asks for the host evaluator by name (csrc/sim3_correct_math.h compiled by g++); with a context, a device error throws — there is no fall-back.
+class Sim3MapCorrection {
+ public:
+  struct Points {                                    // every map point the lists name, by id 0 .. n - 1
+    std::vector<float> pos, normal, min_dist, max_dist;          // GetWorldPos (3 n), GetNormal (3 n), mfMinDistance, mfMaxDistance
+    std::vector<int32_t> obs_off, obs_kf, ref_kf, ref_level;     // non-bad observers in CSR (keyframe indices), reference keyframe and the feature's octave in it
+  };
+  // loop / merge form.  Keyframes 0 .. n_kf - 1 are the set in walk order (Tiw: 12 floats each), center holds theirs and then those of the observers outside
+  // the set.  Keyframe i lists the points list_pt[list_off[i] .. list_off[i + 1]) (GetMapPointMatches; an entry < 0 is a null pointer), list_skip[e] != 0 marks an
+  // entry whose point is bad or carries this loop's tag already.
+  Sim3MapCorrection(HipContext* ctx, int n_kf, std::vector<float> Tiw, std::vector<float> center, int cur, const float Twc[12], const double Scw[8],
+                    const std::vector<int32_t>& list_off, const std::vector<int32_t>& list_pt, const std::vector<uint8_t>& list_skip, Points pts,
+                    std::vector<float> scale_factors);
+  // essential-graph epilogue: S_non = vScw, S_cor = the optimised Sim3 per keyframe (8 doubles each); pt_kf[p] = index of the keyframe whose pair moves point p
+  // (its reference keyframe, or mCorrectedReference_LC), < 0 for a bad point.  Every pose is set before any point moves, so every observer of the set shows its
+  // new centre.
+  Sim3MapCorrection(HipContext* ctx, int n_kf, std::vector<float> center, std::vector<double> S_non, std::vector<double> S_cor, const std::vector<int32_t>& pt_kf,
+                    Points pts, std::vector<float> scale_factors);
+  const Points& points() const { return pts_; }                      // pos / normal / bounds after the correction (points nobody owns: as passed in)
+  const std::vector<int32_t>& tag() const { return tag_; }           // per point: the keyframe (index in the set) that corrected it, -1 none
+  const std::vector<float>& poses() const { return Tiw_new_; }       // 12 n_kf
+  const std::vector<float>& centers() const { return center_new_; }  // 3 n_kf
+  const std::vector<double>& nonCorrectedSim3() const { return S_non_; }
+  const std::vector<double>& correctedSim3() const { return S_cor_; }
+ private:
+  void run(HipContext* ctx, const float* Tiw, int cur, const float* Twc, const double* Scw, const std::vector<float>& center, int32_t epilogue_rank);
+  int n_kf_;
+  Points pts_;
+  std::vector<float> sf_, Tiw_new_, center_new_;
+  std::vector<double> S_non_, S_cor_;
+  std::vector<int32_t> tag_;
+};
+
 // ---------------------------------------------------------------------------------------------------
 // ORBVocabulary::transform (DBoW2 TemplatedVocabulary<FORB>, thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1127-1260) as
 // KeyFrame::ComputeBoW / Frame::ComputeBoW call it (levelsup = 4), and MapPoint::ComputeDistinctiveDescriptors

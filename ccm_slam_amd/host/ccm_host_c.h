@@ -33,6 +33,16 @@ int ccmh_newpts_points(void* h, int j, int n, const int32_t* idx12, uint8_t* sta
 int ccmh_newpts_stats(void* h, int64_t* out3);
 void ccmh_newpts_destroy(void* h);
 int ccmh_triangulate_pairs_host(const float* cam1, int S, const float* cam2, const int32_t* pair_off, const float* xy, const int32_t* oct, int nlevels, const float* sigma2_1, const float* sf_1, const float* sigma2_2, const float* sf_2, float ratio_factor, uint8_t* status, float* x3d, int32_t* n_accepted);
+/* the Sim3 correction of a loop's / merged map's keyframes and points (cslam::Sim3MapCorrection, ONE ccm_sim3_correct_map call).  Keyframes 0 .. n_kf - 1: the set in walk
+ * order, center[3 n_obs_kf]: theirs, then the outside observers'.  loop form: keyframe i lists list_pt[list_off[i] .. list_off[i + 1]) (< 0: null), list_skip[e] != 0: bad or
+ * tagged already.  epilogue form: pt_kf[p] = keyframe whose Sim3 pair moves point p (< 0: skip).  Points 0 .. n_pt - 1 as ccm_sim3_correct_map.  device < 0 asks for the host
+ * evaluator by name (no device is touched); with a device, a device error makes create return NULL.  results: any pointer may be NULL; tag[p] = keyframe that corrected p, -1 none.
+ * ccmh_sim3_correct_map_host: the arguments of ccm_sim3_correct_map after the context through the same header on the calling thread (0, or -1 for its CCM_E_ARG cases). */
+void* ccmh_sim3corr_create_loop(int device, int n_kf, int n_obs_kf, const float* Tiw, const float* center, int cur, const float* Twc, const double* Scw, const int32_t* list_off, const int32_t* list_pt, const uint8_t* list_skip, int n_pt, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const int32_t* obs_off, const int32_t* obs_kf, const int32_t* ref_kf, const int32_t* ref_level, const float* scale_factors, int n_levels);
+void* ccmh_sim3corr_create_epilogue(int device, int n_kf, int n_obs_kf, const float* center, const double* S_non, const double* S_cor, const int32_t* pt_kf, int n_pt, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const int32_t* obs_off, const int32_t* obs_kf, const int32_t* ref_kf, const int32_t* ref_level, const float* scale_factors, int n_levels);
+int ccmh_sim3corr_results(void* h, float* pos, float* normal, float* min_dist, float* max_dist, int32_t* tag, float* Tiw_new, float* center_new, double* S_non, double* S_cor);
+void ccmh_sim3corr_destroy(void* h);
+int ccmh_sim3_correct_map_host(int n_kf, const float* Tiw, int cur, const float* Twc, const double* Scw, double* S_non, double* S_cor, int n_obs_kf, const float* kf_center, const int32_t* kf_rank, int n_pt, const float* pos, const int32_t* owner, const int32_t* owner_rank, const int32_t* obs_off, const int32_t* obs_kf, const int32_t* ref_kf, const int32_t* ref_level, const float* scale_factors, int n_levels, float* pos_out, float* normal, float* min_dist, float* max_dist, float* Tiw_new, float* center_new);
 int ccmh_search_for_initialization(int device, const float* x1, const float* y1, const int32_t* oct1, const float* a1, const uint8_t* d1, int N1, const float* x2, const float* y2, const int32_t* oct2, const float* a2, const uint8_t* d2, int N2, float minX, float minY, float maxX, float maxY, float* prev_xy, int window, float nnratio, int check_ori, int32_t* matches12);
 int ccmh_projected_window_search(int device, const float* kx, const float* ky, const int32_t* oct, const uint8_t* kdesc, int N, float minX, float minY, float maxX, float maxY, const float* scale_factors, const float* inv_sigma2, int n_pts, const uint8_t* valid, const float* u, const float* v, const int32_t* level, const uint8_t* pdesc, float th, int chi2_gate, int dist_threshold, int32_t* matched, int claim, const uint8_t* no_claim, int32_t* best_idx, int32_t* best_dist);
 void* ccmh_fuse_batch_create_cand(int device, int S, const int32_t* kf_off, const float* kx, const float* ky, const int32_t* oct, const uint8_t* kdesc, const float* const* inv_sigma2, const int32_t* pt_off, const uint8_t* valid, const float* u, const float* v, const int32_t* level, const uint8_t* pdesc, const int32_t* cand_off, const int32_t* cand_base, const int32_t* cand_idx, int chi2_gate, int dist_threshold);

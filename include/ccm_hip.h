@@ -454,6 +454,38 @@ int  ccm_triangulate_pairs(ccm_ctx* ctx, const float* cam1 /* 21 */, int S, cons
                            const float* xy /* 4 P */, const int32_t* oct /* 2 P */, int nlevels, const float* sigma2_1, const float* sf_1,
                            const float* sigma2_2, const float* sf_2, float ratioFactor, uint8_t* status, float* x3d, int32_t* n_accepted);
 
+/* ---- Sim3 correction of a closed loop's or merged map's keyframes and points ---------------------
+ * The arithmetic of the correction loops of LoopFinder::CorrectLoop (cslam/src/LoopFinder.cpp:543-613) and MapMerger::MergeMaps
+ * (cslam/src/MapMerger.cpp:289-395), and of the tail of both essential-graph optimisers (cslam/src/Optimizer.cpp:1279-1330), in TWO launches:
+ * per keyframe the two Sim3s, the new pose [R | t / s] and its camera centre (KeyFrame::SetPose), per map point
+ * CorrectedSwi.map(Siw.map(P)) and MapPoint::UpdateNormalAndDepth on the new position, bit-identical to the reference's f32 / f64 arithmetic
+ * under OpenCV 4.2 baseline-build semantics (the lines are ccm_slam_amd/csrc/sim3_correct_math.h, which also compiles for the
+ * host).  Stateless; no graph is touched: SetWorldPos, the tags, SetPose and UpdateConnections stay the caller's.
+ * Keyframes: the set of n_kf >= 1 corrected keyframes IN THE ORDER THE REFERENCE'S LOOP WALKS THEM, followed by the observers outside the set,
+ * n_obs_kf >= n_kf in all.  kf_center[3 n_obs_kf] = GetCameraCenter() before the call, kf_rank[n_obs_kf] = position in the walk (INT32_MAX
+ * outside the set).  A pose is 12 floats: rows 0..2 of the 4x4, row-major; a Sim3 is 8 doubles: qx qy qz qw tx ty tz s.
+ *   loop / merge form (Tiw != NULL): Tiw[12 n_kf] = GetPose(), cur = index of the current keyframe in the set, Twc = its GetPoseInverse(),
+ *     Scw = the accepted mg2oScw.  S_non / S_cor [8 n_kf] are OUTPUTS: NonCorrectedSim3 and CorrectedSim3 (keyframe cur takes Scw itself).
+ *   epilogue form (Tiw == NULL): S_non / S_cor are INPUTS (vScw and the optimised CorrectedSiw per keyframe); cur, Twc and Scw are not read.
+ * Points (n_pt >= 0; 0 corrects the keyframes only and the per-point pointers may be NULL): pos[3 n_pt] = GetWorldPos(); owner = index in the
+ * set of the keyframe whose two Sim3s move the point (loop form: the FIRST keyframe of the walk that lists it; epilogue form: its reference
+ * keyframe, or mCorrectedReference_LC); owner_rank = kf_rank[owner] in the loop form, INT32_MAX in the epilogue form; observers in CSR over
+ * obs_off[n_pt + 1] (obs_off[0] = 0; the non-bad keyframes of mObservations, summed in list order), ref_kf / ref_level = the reference
+ * keyframe and the octave of the point's feature in it; scale_factors[n_levels] = mvScaleFactors.
+ * Rule for the centres: the reference updates a point's normal and depth immediately, inside the walk, so observer k (and the reference
+ * keyframe) shows its NEW centre iff k < n_kf and kf_rank[k] < owner_rank, its old centre otherwise.
+ * Out: pos_out[3 n_pt] (may be pos), normal[3 n_pt] / min_dist / max_dist (in / out: a point with an empty observation list keeps what was
+ * passed in; the bounds are mfMinDistance / mfMaxDistance), Tiw_new[12 n_kf], center_new[3 n_kf], and the two Sim3 tables in the loop form.
+ * CCM_E_ARG: null pointers, n_kf < 1, n_obs_kf < n_kf, a decreasing obs_off, an owner outside [0, n_kf), an observer or reference keyframe
+ * outside [0, n_obs_kf), a level outside [0, n_levels), cur outside [0, n_kf) in the loop form.  NaN / Inf positions propagate.  One H2D copy,
+ * two launches and one D2H copy on the context's stream, scratch of the context; threads calling with their own contexts run concurrently. */
+int  ccm_sim3_correct_map(ccm_ctx* ctx, int n_kf, const float* Tiw /* 12 n_kf or NULL */, int cur, const float* Twc /* 12 */, const double* Scw /* 8 */,
+                          double* S_non /* 8 n_kf */, double* S_cor /* 8 n_kf */, int n_obs_kf, const float* kf_center /* 3 n_obs_kf */,
+                          const int32_t* kf_rank /* n_obs_kf */, int n_pt, const float* pos /* 3 n_pt */, const int32_t* owner, const int32_t* owner_rank,
+                          const int32_t* obs_off /* n_pt + 1 */, const int32_t* obs_kf, const int32_t* ref_kf, const int32_t* ref_level,
+                          const float* scale_factors, int n_levels, float* pos_out, float* normal, float* min_dist, float* max_dist,
+                          float* Tiw_new /* 12 n_kf */, float* center_new /* 3 n_kf */);
+
 #ifdef __cplusplus
 }
 #endif

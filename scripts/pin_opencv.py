@@ -88,7 +88,21 @@ def cv2_vectors(cv2):
     # Mapping.cpp:383 cv::SVD::compute(A, w, u, vt, MODIFY_A | FULL_UV) on the 4x4 f32 matrix of the linear triangulation: w and vt (u is not used by the reference)
     if hasattr(cv2, "SVDecomp"):
         vec.update(svd4_vectors(cv2))
+    # LoopFinder.cpp:551 `Tiw * Twc` and KeyFrame.cpp:302 `-Rwc * tcw`: the small-matrix path of cv::gemm on CV_32F poses (csrc/sim3_correct_math.h)
+    if hasattr(cv2, "gemm"):
+        vec.update(gemm4_vectors(cv2))
     return vec
+
+
+def gemm4_vectors(cv2):
+    """4x4 f32 pose products and the centre of SetPose, through cv2.gemm (what the MatExprs `A * B` and `-A * b` end in)"""
+    from ccm_slam_amd import sim3_correct as S
+    sc = S.make_scene(seed=17, n_kf=200, n_pt=10)
+    T = np.zeros((200, 4, 4), np.float32); T[:, :3] = sc["Tiw"].reshape(200, 3, 4); T[:, 3, 3] = 1
+    Twc = np.zeros((4, 4), np.float32); Twc[:3] = sc["Twc"].reshape(3, 4); Twc[3, 3] = 1
+    prod = np.stack([cv2.gemm(t, Twc, 1.0, None, 0.0) for t in T]).astype(np.float32)
+    cen = np.stack([cv2.gemm(np.ascontiguousarray(t[:3, :3].T), np.ascontiguousarray(t[:3, 3:4]), -1.0, None, 0.0).reshape(3) for t in T]).astype(np.float32)
+    return {"gemm4_a": T, "gemm4_b": Twc, "gemm4_out": prod, "gemm4_center": cen}
 
 
 def svd4_inputs():
@@ -156,6 +170,12 @@ def compare(vec, report=print):
         w, vt = jacobi_svd4(np.asarray(vec["svd4_in"]))
         same("SVDecomp (4x4 f32): singular values", w.astype(np.float32), np.asarray(vec["svd4_w"]))
         same("SVDecomp (4x4 f32): vt", vt, np.asarray(vec["svd4_vt"]))
+    if "gemm4_a" in vec:    # the map correction's restatement (gemm44 / center_of_pose of tests/test_sim3_correct_cpu.py, the lines of csrc/sim3_correct_math.h)
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        from test_sim3_correct_cpu import center_of_pose, gemm44
+        A = np.asarray(vec["gemm4_a"], np.float32); B = np.asarray(vec["gemm4_b"], np.float32)
+        same("gemm (4x4 f32 poses)", gemm44(A[:, :3].reshape(-1, 12), np.broadcast_to(B[:3].reshape(1, 12), (A.shape[0], 12))).reshape(-1, 3, 4), np.asarray(vec["gemm4_out"])[:, :3])
+        same("gemm (-Rwc * tcw)", center_of_pose(A[:, :3].reshape(-1, 12)), np.asarray(vec["gemm4_center"]))
     return bad
 
 
