@@ -94,6 +94,13 @@ extern "C" int ccm_orb_debug_candidates(ccm_orb* o, int level, ccm_keypoint* out
 extern "C" int ccm_orb_debug_octree_dev(ccm_ctx* ctx, const int32_t* x, const int32_t* y, const int32_t* response, int n, int W, int H, int N, int32_t* sel_out, int cap, int* n_out, int* overflow) {
   return ccm_internal::orb_debug_octree_dev(ctx, x, y, response, n, W, H, N, sel_out, cap, n_out, overflow);
 }
+// ccm_covis_update with a histogram window of 64 keyframe indices instead of the product's: the multi-window path at a small n_all (tests/test_covis_gpu.py)
+extern "C" int ccm_debug_covis_update_small(ccm_ctx* ctx, int n_kf, int n_all, const int32_t* order_key, const int32_t* list_off, const int32_t* list_pt, const uint8_t* list_skip,
+                                            int n_pt, const int32_t* obs_off, const int32_t* obs_kf, int th, int cap, int32_t* row_off, int32_t* col, int32_t* count,
+                                            int32_t* fw_off, int32_t* fw_col, int32_t* fw_w, int32_t* ord_off, int32_t* ord_kf, int32_t* ord_w, int32_t* flags, int32_t* needed) {
+  return ccm_internal::covis_update_window(ctx, 1, n_kf, n_all, order_key, list_off, list_pt, list_skip, n_pt, obs_off, obs_kf, th, cap, row_off, col, count, fw_off, fw_col,
+                                           fw_w, ord_off, ord_kf, ord_w, flags, needed);
+}
 
 // lane_xor.h against __shfl_xor: out[6][3][64] doubles — for MASK = 1, 2, 4, 8, 16, 32: from_partner<MASK>(v), add_partner<MASK>(v) and __shfl_xor(v, MASK) of the 64 lanes'
 // values in[64]; sum_out[0] = lanex::wave_sum, sum_out[1] = the __shfl_xor butterfly 32 ... 1, sum_out[2] = lanex::wave_incl_scan_i32 of the pattern (37 lane mod 101) - 20.  tests/test_lane_xor_gpu.py.

@@ -20,4 +20,8 @@ int  orb_debug_level(ccm_orb* o, int level, uint8_t* score_out, uint8_t* blur_ou
 int  orb_debug_candidates(ccm_orb* o, int level, ccm_keypoint* out, int cap, int* n_out);
 int  orb_debug_octree_dev(ccm_ctx* ctx, const int32_t* x, const int32_t* y, const int32_t* response, int n, int W, int H, int N,
                           int32_t* sel_out, int cap, int* n_out, int* overflow);
+int  covis_update_window(ccm_ctx* ctx, int small_window, int n_kf, int n_all, const int32_t* order_key, const int32_t* list_off, const int32_t* list_pt,
+                         const uint8_t* list_skip, int n_pt, const int32_t* obs_off, const int32_t* obs_kf, int th, int cap, int32_t* row_off, int32_t* col,
+                         int32_t* count, int32_t* fw_off, int32_t* fw_col, int32_t* fw_w, int32_t* ord_off, int32_t* ord_kf, int32_t* ord_w, int32_t* flags,
+                         int32_t* needed);
 }  // namespace ccm_internal

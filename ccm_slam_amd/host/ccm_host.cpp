@@ -4,6 +4,7 @@
 #include "kfdb_resolve.h"
 #include "../csrc/triangulate_math.h"
 #include "../csrc/sim3_correct_math.h"
+#include "../csrc/covis_math.h"
 #include <climits>
 #include <algorithm>
 #include <cmath>
@@ -1211,6 +1212,154 @@ void Sim3MapCorrection::run(HipContext* ctx, const float* Tiw, int cur, const fl
   }
 }
 
+// ---- CovisibilityBatch ----------------------------------------------------------------------------------
+// ccm_covis_update on the calling thread: the same checks and the rules of csrc/covis_math.h, one keyframe after the other
+int covis_update_host(int n_kf, int n_all, const int32_t* order_key, const int32_t* list_off, const int32_t* list_pt, const uint8_t* list_skip, int n_pt,
+                      const int32_t* obs_off, const int32_t* obs_kf, int th, int cap, int32_t* row_off, int32_t* col, int32_t* count, int32_t* fw_off, int32_t* fw_col,
+                      int32_t* fw_w, int32_t* ord_off, int32_t* ord_kf, int32_t* ord_w, int32_t* flags, int32_t* needed) {
+  if (!row_off || !fw_off || !ord_off || !flags || !needed || (cap > 0 && (!col || !count || !fw_col || !fw_w || !ord_kf || !ord_w))) return -1;
+  if (covis_check_args(n_kf, n_all, order_key, list_off, list_pt, list_skip, n_pt, obs_off, obs_kf, th, cap)) return -1;
+  const uint32_t uth = (uint32_t)th;
+  // own counts: a dense counter over the keyframe indices and the list of those touched
+  std::vector<uint32_t> cnt((size_t)n_all, 0);
+  std::vector<int32_t> touched, roff((size_t)n_kf + 1, 0), rcol, rcnt, nge((size_t)n_kf, 0), fb((size_t)n_kf, -1), fl((size_t)n_kf, 0);
+  for (int i = 0; i < n_kf; i++) {
+    touched.clear();
+    for (int32_t e = list_off[i]; e < list_off[i + 1]; e++) {
+      if (!covis_entry_counts(list_pt[e], list_skip[e])) continue;
+      for (int32_t o = obs_off[list_pt[e]]; o < obs_off[list_pt[e] + 1]; o++) {
+        const int32_t j = obs_kf[o];
+        if (!covis_observer_counts(j, i)) continue;
+        if (cnt[j]++ == 0) touched.push_back(j);
+      }
+    }
+    std::sort(touched.begin(), touched.end());
+    uint32_t best_c = 0; int32_t best_key = 0, best_col = -1;
+    for (int32_t j : touched) {
+      const uint32_t c = cnt[j];
+      rcol.push_back(j); rcnt.push_back((int32_t)c);
+      if (c >= uth) nge[i]++;
+      if (best_col < 0 || covis_fallback_better(c, order_key[j], best_c, best_key)) { best_c = c; best_key = order_key[j]; best_col = j; }
+      cnt[j] = 0;
+    }
+    roff[i + 1] = (int32_t)rcol.size();
+    fb[i] = nge[i] > 0 ? -1 : best_col;
+    fl[i] = touched.empty() ? COVIS_EMPTY : nge[i] == 0 ? COVIS_FALLBACK : 0;
+  }
+  // the calls that reach a keyframe whose own row lacks the caller, and the rows whose list is rebuilt
+  std::vector<std::vector<std::pair<int32_t, int32_t>>> extra((size_t)n_kf);
+  for (int i = 0; i < n_kf; i++)
+    for (int32_t e = roff[i]; e < roff[i + 1]; e++) {
+      const int32_t t = rcol[e];
+      if (t >= n_kf) continue;
+      const uint32_t c = (uint32_t)rcnt[e];
+      const int32_t pos = covis_find(rcol.data(), roff[t], roff[t + 1], i);
+      if (pos < 0 && covis_is_event(c, t, uth, nge[i], fb[i]) && covis_reaches(i, t, roff[t + 1] == roff[t])) extra[t].push_back({i, (int32_t)c});
+      if (pos >= 0 && covis_reaches(t, i, false) && (uint32_t)rcnt[pos] != c && covis_is_event((uint32_t)rcnt[pos], i, uth, nge[t], fb[t])) fl[i] |= COVIS_CHANGED;
+    }
+  std::vector<int32_t> foff((size_t)n_kf + 1, 0), fcol, fw, ooff((size_t)n_kf + 1, 0), okf, ow;
+  std::vector<std::pair<uint64_t, int32_t>> keys;
+  for (int i = 0; i < n_kf; i++) {
+    if (!extra[i].empty()) fl[i] |= COVIS_CHANGED;
+    const bool changed = (fl[i] & COVIS_CHANGED) != 0;
+    // final weights: the row with the weights that reached it, merged with the extras (already ascending: their sources were walked in order)
+    size_t x = 0;
+    for (int32_t e = roff[i]; e <= roff[i + 1]; e++) {
+      const int32_t c = e < roff[i + 1] ? rcol[e] : INT32_MAX;
+      while (x < extra[i].size() && extra[i][x].first < c) { fcol.push_back(extra[i][x].first); fw.push_back(extra[i][x].second); x++; }
+      if (e == roff[i + 1]) break;
+      int32_t w = rcnt[e];
+      if (c < n_kf && covis_reaches(c, i, false)) {
+        const int32_t pos = covis_find(rcol.data(), roff[c], roff[c + 1], i);
+        if (pos >= 0 && covis_is_event((uint32_t)rcnt[pos], i, uth, nge[c], fb[c])) w = rcnt[pos];
+      }
+      fcol.push_back(c); fw.push_back(w);
+    }
+    foff[i + 1] = (int32_t)fcol.size();
+    keys.clear();
+    for (int32_t e = foff[i]; e < foff[i + 1]; e++)
+      if (changed || covis_is_event((uint32_t)fw[e], fcol[e], uth, nge[i], fb[i])) keys.push_back({covis_sort_key((uint32_t)fw[e], order_key[fcol[e]]), e});
+    std::sort(keys.begin(), keys.end(), [](const auto& a, const auto& b) { return a.first > b.first; });
+    for (const auto& k : keys) { okf.push_back(fcol[k.second]); ow.push_back(fw[k.second]); }
+    ooff[i + 1] = (int32_t)okf.size();
+  }
+  needed[0] = (int32_t)rcol.size(); needed[1] = (int32_t)fcol.size(); needed[2] = (int32_t)okf.size();
+  if (needed[0] > cap || needed[1] > cap || needed[2] > cap) return 0;
+  auto out = [](int32_t* dst, const std::vector<int32_t>& v) { if (!v.empty()) std::memcpy(dst, v.data(), v.size() * 4); };
+  out(flags, fl); out(row_off, roff); out(col, rcol); out(count, rcnt); out(fw_off, foff); out(fw_col, fcol); out(fw_w, fw); out(ord_off, ooff); out(ord_kf, okf); out(ord_w, ow);
+  return 0;
+}
+
+CovisibilityBatch::CovisibilityBatch(HipContext* ctx, int n_kf, std::vector<int32_t> order_key, const std::vector<int32_t>& list_off, const std::vector<int32_t>& list_pt,
+                                     const std::vector<uint8_t>& list_skip, const std::vector<int32_t>& obs_off, const std::vector<int32_t>& obs_kf, int th)
+    : n_kf_(n_kf), key_(std::move(order_key)) {
+  const int n_all = (int)key_.size();
+  if (n_kf < 1 || n_all < n_kf || list_off.size() != (size_t)n_kf + 1 || list_off[0] != 0 || list_off[n_kf] < 0 || (size_t)list_off[n_kf] != list_pt.size() ||
+      list_skip.size() != list_pt.size() || obs_off.empty() || obs_off[0] != 0 || obs_off.back() < 0 || (size_t)obs_off.back() != obs_kf.size())
+    throw infrastructure_ex("CovisibilityBatch: arrays");
+  const int n_pt = (int)obs_off.size() - 1;
+  flags_.assign((size_t)n_kf, 0); row_off_.assign((size_t)n_kf + 1, 0); fw_off_ = row_off_; ord_off_ = row_off_;
+  // capacity: a first guess from the set's size, then what the call says it needs
+  int cap = std::max(4096, 96 * n_kf);
+  for (int attempt = 0;; attempt++) {
+    col_.assign((size_t)cap, 0); count_ = col_; fw_col_ = col_; fw_w_ = col_; ord_kf_ = col_; ord_w_ = col_;
+    int32_t needed[3] = {0, 0, 0};
+    if (ctx) {
+      check(ccm_covis_update(ctx->get(), n_kf, n_all, key_.data(), list_off.data(), list_pt.data(), list_skip.data(), n_pt, obs_off.data(), obs_kf.data(), th, cap,
+                             row_off_.data(), col_.data(), count_.data(), fw_off_.data(), fw_col_.data(), fw_w_.data(), ord_off_.data(), ord_kf_.data(), ord_w_.data(),
+                             flags_.data(), needed),
+            ctx->get(), "ccm_covis_update");
+    } else if (covis_update_host(n_kf, n_all, key_.data(), list_off.data(), list_pt.data(), list_skip.data(), n_pt, obs_off.data(), obs_kf.data(), th, cap, row_off_.data(),
+                                 col_.data(), count_.data(), fw_off_.data(), fw_col_.data(), fw_w_.data(), ord_off_.data(), ord_kf_.data(), ord_w_.data(), flags_.data(),
+                                 needed)) {
+      throw infrastructure_ex("CovisibilityBatch: bad arguments");
+    }
+    const int most = std::max(needed[0], std::max(needed[1], needed[2]));
+    if (most <= cap) {
+      col_.resize((size_t)needed[0]); count_.resize((size_t)needed[0]); fw_col_.resize((size_t)needed[1]); fw_w_.resize((size_t)needed[1]);
+      ord_kf_.resize((size_t)needed[2]); ord_w_.resize((size_t)needed[2]);
+      break;
+    }
+    if (attempt >= 3 || most > INT32_MAX / 2) throw infrastructure_ex("CovisibilityBatch: capacity");
+    cap = 2 * most;   // the final rows are at most twice the count rows
+  }
+  // AddConnection calls on keyframes outside the set: walk order, then the map's key order.  The events of an unchanged row are its ordered list; a rebuilt
+  // list holds the whole map, so there the row's own counts decide (a FALLBACK row's single event is then its best entry under covis_fallback_better)
+  for (int i = 0; i < n_kf; i++) {
+    const size_t first = outside_.size();
+    if (!(flags_[i] & COVIS_CHANGED)) {
+      for (int32_t e = ord_off_[i]; e < ord_off_[i + 1]; e++)
+        if (ord_kf_[e] >= n_kf) outside_.push_back({ord_kf_[e], i, ord_w_[e]});
+    } else if (flags_[i] & COVIS_FALLBACK) {
+      int32_t best = -1;
+      for (int32_t e = row_off_[i]; e < row_off_[i + 1]; e++)
+        if (best < 0 || covis_fallback_better((uint32_t)count_[e], key_[col_[e]], (uint32_t)count_[best], key_[col_[best]])) best = e;
+      if (best >= 0 && col_[best] >= n_kf) outside_.push_back({col_[best], i, count_[best]});
+    } else {
+      for (int32_t e = row_off_[i]; e < row_off_[i + 1]; e++)
+        if (col_[e] >= n_kf && count_[e] >= th) outside_.push_back({col_[e], i, count_[e]});
+    }
+    std::sort(outside_.begin() + first, outside_.end(), [&](const AddCall& a, const AddCall& b) { return key_[a.target] < key_[b.target]; });
+  }
+}
+
+std::map<int32_t, int> CovisibilityBatch::GetConnectedKeyFrameWeights(int i) const {
+  std::map<int32_t, int> m;
+  for (int32_t e = fw_off_[i]; e < fw_off_[i + 1]; e++) m[fw_col_[e]] = fw_w_[e];
+  return m;
+}
+std::vector<int32_t> CovisibilityBatch::GetBestCovisibilityKeyFrames(int i, int N) const {
+  const int n = ord_off_[i + 1] - ord_off_[i];
+  return std::vector<int32_t>(ord_kf_.begin() + ord_off_[i], ord_kf_.begin() + ord_off_[i] + (n < N ? n : std::max(N, 0)));
+}
+std::vector<int32_t> CovisibilityBatch::GetCovisiblesByWeight(int i, int w) const {
+  const auto b = ord_w_.begin() + ord_off_[i], e = ord_w_.begin() + ord_off_[i + 1];
+  if (b == e) return {};
+  const auto it = std::upper_bound(b, e, w, [](int a, int c) { return a > c; });
+  if (it == e) return {};
+  return std::vector<int32_t>(ord_kf_.begin() + ord_off_[i], ord_kf_.begin() + ord_off_[i] + (it - b));
+}
+
 }  // namespace cslam
 
 // ---- C entry points (ccm_host_c.h): the Python test-suite and the drop-in translation units under shim/ ---------------------------------------
@@ -1548,6 +1697,55 @@ int ccmh_sim3_correct_map_host(int n_kf, const float* Tiw, int cur, const float*
                                float* normal, float* min_dist, float* max_dist, float* Tiw_new, float* center_new) {
   return cslam::sim3_correct_map_host(n_kf, Tiw, cur, Twc, Scw, S_non, S_cor, n_obs_kf, kf_center, kf_rank, n_pt, pos, owner, owner_rank, obs_off, obs_kf, ref_kf, ref_level,
                                       scale_factors, n_levels, pos_out, normal, min_dist, max_dist, Tiw_new, center_new);
+}
+
+// CovisibilityBatch through C
+void* ccmh_covis_create(int device, int n_kf, int n_all, const int32_t* order_key, const int32_t* list_off, const int32_t* list_pt, const uint8_t* list_skip, int n_pt,
+                        const int32_t* obs_off, const int32_t* obs_kf, int th) {
+  try {
+    if (n_kf < 1 || n_all < n_kf || n_pt < 0 || !order_key || !list_off || (n_pt > 0 && !obs_off)) return nullptr;
+    const int ne = list_off[n_kf], no = n_pt ? obs_off[n_pt] : 0;
+    if (ne < 0 || no < 0 || (ne > 0 && (!list_pt || !list_skip)) || (no > 0 && !obs_kf)) return nullptr;
+    return new cslam::CovisibilityBatch(device < 0 ? nullptr : &thread_context(device), n_kf, std::vector<int32_t>(order_key, order_key + n_all),
+                                        std::vector<int32_t>(list_off, list_off + n_kf + 1), std::vector<int32_t>(list_pt, list_pt + ne),
+                                        std::vector<uint8_t>(list_skip, list_skip + ne), n_pt ? std::vector<int32_t>(obs_off, obs_off + n_pt + 1) : std::vector<int32_t>(1, 0),
+                                        std::vector<int32_t>(obs_kf, obs_kf + no), th);
+  } catch (const std::exception&) { return nullptr; }
+}
+int ccmh_covis_sizes(void* h, int64_t* out5) {
+  if (!h || !out5) return -1;
+  const cslam::CovisibilityBatch& c = *static_cast<cslam::CovisibilityBatch*>(h);
+  out5[0] = c.size(); out5[1] = (int64_t)c.rowKf().size(); out5[2] = (int64_t)c.weightKf().size(); out5[3] = (int64_t)c.orderedKf().size(); out5[4] = (int64_t)c.outsideCalls().size();
+  return 0;
+}
+int ccmh_covis_results(void* h, int32_t* flags, int32_t* row_off, int32_t* col, int32_t* count, int32_t* fw_off, int32_t* fw_col, int32_t* fw_w, int32_t* ord_off,
+                       int32_t* ord_kf, int32_t* ord_w, int32_t* outside) {
+  if (!h) return -1;
+  const cslam::CovisibilityBatch& c = *static_cast<cslam::CovisibilityBatch*>(h);
+  auto out = [](int32_t* dst, const std::vector<int32_t>& v) { if (dst && !v.empty()) std::memcpy(dst, v.data(), v.size() * 4); };
+  out(flags, c.allFlags()); out(row_off, c.rowOff()); out(col, c.rowKf()); out(count, c.rowCount()); out(fw_off, c.weightOff()); out(fw_col, c.weightKf());
+  out(fw_w, c.weight()); out(ord_off, c.orderedOff()); out(ord_kf, c.orderedKf()); out(ord_w, c.orderedWeight());
+  if (outside) for (size_t k = 0; k < c.outsideCalls().size(); k++) { outside[3 * k] = c.outsideCalls()[k].target; outside[3 * k + 1] = c.outsideCalls()[k].source; outside[3 * k + 2] = c.outsideCalls()[k].weight; }
+  return 0;
+}
+static int covis_view(const std::vector<int32_t>& v, int32_t* out, int cap) {
+  if (out) for (int k = 0; k < (int)v.size() && k < cap; k++) out[k] = v[k];
+  return (int)v.size();
+}
+int ccmh_covis_best(void* h, int i, int N, int32_t* out, int cap) {
+  if (!h || i < 0 || i >= static_cast<cslam::CovisibilityBatch*>(h)->size()) return -1;
+  return covis_view(static_cast<cslam::CovisibilityBatch*>(h)->GetBestCovisibilityKeyFrames(i, N), out, cap);
+}
+int ccmh_covis_by_weight(void* h, int i, int w, int32_t* out, int cap) {
+  if (!h || i < 0 || i >= static_cast<cslam::CovisibilityBatch*>(h)->size()) return -1;
+  return covis_view(static_cast<cslam::CovisibilityBatch*>(h)->GetCovisiblesByWeight(i, w), out, cap);
+}
+void ccmh_covis_destroy(void* h) { delete static_cast<cslam::CovisibilityBatch*>(h); }
+int ccmh_covis_update_host(int n_kf, int n_all, const int32_t* order_key, const int32_t* list_off, const int32_t* list_pt, const uint8_t* list_skip, int n_pt,
+                           const int32_t* obs_off, const int32_t* obs_kf, int th, int cap, int32_t* row_off, int32_t* col, int32_t* count, int32_t* fw_off, int32_t* fw_col,
+                           int32_t* fw_w, int32_t* ord_off, int32_t* ord_kf, int32_t* ord_w, int32_t* flags, int32_t* needed) {
+  return cslam::covis_update_host(n_kf, n_all, order_key, list_off, list_pt, list_skip, n_pt, obs_off, obs_kf, th, cap, row_off, col, count, fw_off, fw_col, fw_w, ord_off,
+                                  ord_kf, ord_w, flags, needed);
 }
 
 int ccmh_search_for_initialization(int device, const float* x1, const float* y1, const int32_t* oct1, const float* a1, const uint8_t* d1, int N1,

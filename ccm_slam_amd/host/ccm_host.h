@@ -15,6 +15,7 @@
 #include <vector>
 #include "../../include/ccm_hip.h"
 #include "sim3_schedule.h"
+#include <map>
 
 namespace cslam {
 
@@ -293,6 +294,49 @@ class Sim3MapCorrection {
   std::vector<double> S_non_, S_cor_;
   std::vector<int32_t> tag_;
 };
+
+// KeyFrame::UpdateConnections (KeyFrame.cpp:629-711) for every keyframe of a corrected set (LoopFinder.cpp:612 / :655, MapMerger.cpp:392 / :487, Map.cpp:614) as ONE
+// ccm_covis_update call, with the AddConnection / UpdateBestCovisibles calls (:392-426) the set's keyframes make on each other: per keyframe the final
+// mConnectedKeyFrameWeights, mvpOrderedConnectedKeyFrames and mvOrderedWeights, identical to the sequential walk.  Keyframes 0 .. n_kf - 1 are the
+// set in walk order, the others observers outside it; order_key (distinct, one per keyframe) stands for the pointer order of the reference's std::map and sort.
+// The lists are those of Sim3MapCorrection: keyframe i lists list_pt[list_off[i] .. list_off[i + 1]) (< 0: null), list_skip[e] != 0: a bad point; point p is
+// observed by obs_kf[obs_off[p] .. obs_off[p + 1]).  Keyframes outside the set keep state only the caller knows: outsideCalls() are the AddConnection calls they
+// receive, in the reference's order (walk order, then order_key).  A keyframe flagged EMPTY returns early in the reference and keeps its previous state: its rows
+// hold what the set's calls build on an empty state, i.e. the AddConnection calls to apply to the state the caller has.  The spanning tree stays the caller's.
+// ctx == nullptr asks for the host evaluator by name (csrc/covis_math.h compiled by g++); with a context, a device error throws — there is no fall-back.
+class CovisibilityBatch {
+ public:
+  struct AddCall { int32_t target, source, weight; };
+  CovisibilityBatch(HipContext* ctx, int n_kf, std::vector<int32_t> order_key, const std::vector<int32_t>& list_off, const std::vector<int32_t>& list_pt,
+                    const std::vector<uint8_t>& list_skip, const std::vector<int32_t>& obs_off, const std::vector<int32_t>& obs_kf, int th = 15);
+  int size() const { return n_kf_; }
+  int flags(int i) const { return flags_[i]; }                                   // COVIS_EMPTY 1, COVIS_FALLBACK 2, COVIS_CHANGED 4
+  std::map<int32_t, int> GetConnectedKeyFrameWeights(int i) const;               // mConnectedKeyFrameWeights, keyed by keyframe index
+  std::vector<int32_t> GetVectorCovisibleKeyFrames(int i) const { return std::vector<int32_t>(ord_kf_.begin() + ord_off_[i], ord_kf_.begin() + ord_off_[i + 1]); }
+  std::vector<int32_t> GetOrderedWeights(int i) const { return std::vector<int32_t>(ord_w_.begin() + ord_off_[i], ord_w_.begin() + ord_off_[i + 1]); }
+  std::vector<int32_t> GetBestCovisibilityKeyFrames(int i, int N) const;         // KeyFrame.cpp:443-451
+  std::vector<int32_t> GetCovisiblesByWeight(int i, int w) const;                // KeyFrame.cpp:453-468 (empty when every weight is >= w, as there)
+  const std::vector<AddCall>& outsideCalls() const { return outside_; }
+  // the flat tables: own counts, final weights (both by ascending keyframe index), ordered lists
+  const std::vector<int32_t>& rowOff() const { return row_off_; }
+  const std::vector<int32_t>& rowKf() const { return col_; }
+  const std::vector<int32_t>& rowCount() const { return count_; }
+  const std::vector<int32_t>& weightOff() const { return fw_off_; }
+  const std::vector<int32_t>& weightKf() const { return fw_col_; }
+  const std::vector<int32_t>& weight() const { return fw_w_; }
+  const std::vector<int32_t>& orderedOff() const { return ord_off_; }
+  const std::vector<int32_t>& orderedKf() const { return ord_kf_; }
+  const std::vector<int32_t>& orderedWeight() const { return ord_w_; }
+  const std::vector<int32_t>& allFlags() const { return flags_; }
+ private:
+  int n_kf_;
+  std::vector<int32_t> key_, flags_, row_off_, col_, count_, fw_off_, fw_col_, fw_w_, ord_off_, ord_kf_, ord_w_;
+  std::vector<AddCall> outside_;
+};
+// ccm_covis_update's arguments after the context through csrc/covis_math.h on the calling thread; -1 where the device entry returns CCM_E_ARG
+int covis_update_host(int n_kf, int n_all, const int32_t* order_key, const int32_t* list_off, const int32_t* list_pt, const uint8_t* list_skip, int n_pt,
+                      const int32_t* obs_off, const int32_t* obs_kf, int th, int cap, int32_t* row_off, int32_t* col, int32_t* count, int32_t* fw_off, int32_t* fw_col,
+                      int32_t* fw_w, int32_t* ord_off, int32_t* ord_kf, int32_t* ord_w, int32_t* flags, int32_t* needed);
 
 // ---------------------------------------------------------------------------------------------------
 // ORBVocabulary::transform (DBoW2 TemplatedVocabulary<FORB>, thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1127-1260) as

@@ -43,6 +43,18 @@ void* ccmh_sim3corr_create_epilogue(int device, int n_kf, int n_obs_kf, const fl
 int ccmh_sim3corr_results(void* h, float* pos, float* normal, float* min_dist, float* max_dist, int32_t* tag, float* Tiw_new, float* center_new, double* S_non, double* S_cor);
 void ccmh_sim3corr_destroy(void* h);
 int ccmh_sim3_correct_map_host(int n_kf, const float* Tiw, int cur, const float* Twc, const double* Scw, double* S_non, double* S_cor, int n_obs_kf, const float* kf_center, const int32_t* kf_rank, int n_pt, const float* pos, const int32_t* owner, const int32_t* owner_rank, const int32_t* obs_off, const int32_t* obs_kf, const int32_t* ref_kf, const int32_t* ref_level, const float* scale_factors, int n_levels, float* pos_out, float* normal, float* min_dist, float* max_dist, float* Tiw_new, float* center_new);
+/* KeyFrame::UpdateConnections over a corrected set (cslam::CovisibilityBatch, ONE ccm_covis_update call; arguments as there).  device < 0 asks for the host evaluator by
+ * name (no device is touched); with a device, a device error makes create return NULL.  sizes: out5 = n_kf, entries of the count rows, of the final rows, of the ordered
+ * lists, outside AddConnection calls.  results: any pointer may be NULL; outside = target source weight per call, in the reference's order.  best / by_weight:
+ * GetBestCovisibilityKeyFrames(N) / GetCovisiblesByWeight(w) of keyframe i, returns the length (min(length, cap) written).
+ * ccmh_covis_update_host: the arguments of ccm_covis_update after the context through the same header on the calling thread (0, or -1 for its CCM_E_ARG cases). */
+void* ccmh_covis_create(int device, int n_kf, int n_all, const int32_t* order_key, const int32_t* list_off, const int32_t* list_pt, const uint8_t* list_skip, int n_pt, const int32_t* obs_off, const int32_t* obs_kf, int th);
+int ccmh_covis_sizes(void* h, int64_t* out5);
+int ccmh_covis_results(void* h, int32_t* flags, int32_t* row_off, int32_t* col, int32_t* count, int32_t* fw_off, int32_t* fw_col, int32_t* fw_w, int32_t* ord_off, int32_t* ord_kf, int32_t* ord_w, int32_t* outside);
+int ccmh_covis_best(void* h, int i, int N, int32_t* out, int cap);
+int ccmh_covis_by_weight(void* h, int i, int w, int32_t* out, int cap);
+void ccmh_covis_destroy(void* h);
+int ccmh_covis_update_host(int n_kf, int n_all, const int32_t* order_key, const int32_t* list_off, const int32_t* list_pt, const uint8_t* list_skip, int n_pt, const int32_t* obs_off, const int32_t* obs_kf, int th, int cap, int32_t* row_off, int32_t* col, int32_t* count, int32_t* fw_off, int32_t* fw_col, int32_t* fw_w, int32_t* ord_off, int32_t* ord_kf, int32_t* ord_w, int32_t* flags, int32_t* needed);
 int ccmh_search_for_initialization(int device, const float* x1, const float* y1, const int32_t* oct1, const float* a1, const uint8_t* d1, int N1, const float* x2, const float* y2, const int32_t* oct2, const float* a2, const uint8_t* d2, int N2, float minX, float minY, float maxX, float maxY, float* prev_xy, int window, float nnratio, int check_ori, int32_t* matches12);
 int ccmh_projected_window_search(int device, const float* kx, const float* ky, const int32_t* oct, const uint8_t* kdesc, int N, float minX, float minY, float maxX, float maxY, const float* scale_factors, const float* inv_sigma2, int n_pts, const uint8_t* valid, const float* u, const float* v, const int32_t* level, const uint8_t* pdesc, float th, int chi2_gate, int dist_threshold, int32_t* matched, int claim, const uint8_t* no_claim, int32_t* best_idx, int32_t* best_dist);
 void* ccmh_fuse_batch_create_cand(int device, int S, const int32_t* kf_off, const float* kx, const float* ky, const int32_t* oct, const uint8_t* kdesc, const float* const* inv_sigma2, const int32_t* pt_off, const uint8_t* valid, const float* u, const float* v, const int32_t* level, const uint8_t* pdesc, const int32_t* cand_off, const int32_t* cand_base, const int32_t* cand_idx, int chi2_gate, int dist_threshold);

@@ -486,6 +486,32 @@ int  ccm_sim3_correct_map(ccm_ctx* ctx, int n_kf, const float* Tiw /* 12 n_kf or
                           const float* scale_factors, int n_levels, float* pos_out, float* normal, float* min_dist, float* max_dist,
                           float* Tiw_new /* 12 n_kf */, float* center_new /* 3 n_kf */);
 
+/* ---- covisibility graph of a corrected map ------------------------------------------------------------
+ * KeyFrame::UpdateConnections (cslam/src/KeyFrame.cpp:629-711) run over a set of keyframes in a given walk order, with the AddConnection /
+ * UpdateBestCovisibles calls (:392-426) the set's keyframes make on each other: what LoopFinder.cpp:612 / :655, MapMerger.cpp:392 / :487 and
+ * Map.cpp:614 leave in mConnectedKeyFrameWeights, mvpOrderedConnectedKeyFrames and mvOrderedWeights, identical to the sequential walk (DESIGN.md
+ * §14; the rules are ccm_slam_amd/csrc/covis_math.h, which also compiles for the host).  Integers only, stateless; the spanning tree (:713-833)
+ * stays the caller's and reads the ordered list returned here.
+ * Keyframes 0 .. n_kf - 1: the set IN WALK ORDER, n_kf .. n_all - 1: observers outside it.  order_key[n_all]: distinct values standing for the
+ * pointer order of std::map<kfptr, ...> and of sort on pair<int, kfptr>.  Keyframe i lists list_pt[list_off[i] .. list_off[i + 1]) (< 0: a null
+ * entry; an entry listed twice counts twice), list_skip[e] != 0: the point is bad.  Point p is observed by obs_kf[obs_off[p] .. obs_off[p + 1]).
+ * th: the weight from which a connection is made (the reference's 15), >= 1.
+ * Out, all CSR over the set: (row_off, col, count) = the own counts C_i by ascending keyframe index; (fw_off, fw_col, fw_w) = the final
+ * mConnectedKeyFrameWeights by ascending keyframe index; (ord_off, ord_kf, ord_w) = mvpOrderedConnectedKeyFrames / mvOrderedWeights;
+ * flags[n_kf]: 1 EMPTY (no counted observer: the keyframe's own step returns early, and its rows hold what the set's AddConnection calls
+ * build on an EMPTY state — the state it had before stays with the caller), 2 FALLBACK (no count reached th: the one maximal neighbour),
+ * 4 CHANGED (a later keyframe's AddConnection rebuilt the ordered list from the whole map).
+ * cap = entries each of the six variable-size arrays can hold; needed[3] = entries of the count rows, the final rows and the ordered lists
+ * (-1: not reached).  When a needed value exceeds cap the call returns CCM_OK with only `needed` defined: call again with a larger cap.
+ * CCM_E_ARG: null pointers, n_kf < 1, n_all < n_kf, th < 1, cap < 0, offsets that do not start at 0 or decrease, a point index >= n_pt, an
+ * observer outside [0, n_all), a repeated order_key; nothing is launched.  One H2D copy, seven launches and one D2H copy (sized by cap) on the
+ * context's stream, scratch of the context; threads calling with their own contexts run concurrently. */
+int  ccm_covis_update(ccm_ctx* ctx, int n_kf, int n_all, const int32_t* order_key /* n_all */, const int32_t* list_off /* n_kf + 1 */,
+                      const int32_t* list_pt, const uint8_t* list_skip, int n_pt, const int32_t* obs_off /* n_pt + 1 */, const int32_t* obs_kf,
+                      int th, int cap, int32_t* row_off /* n_kf + 1 */, int32_t* col, int32_t* count, int32_t* fw_off /* n_kf + 1 */,
+                      int32_t* fw_col, int32_t* fw_w, int32_t* ord_off /* n_kf + 1 */, int32_t* ord_kf, int32_t* ord_w, int32_t* flags /* n_kf */,
+                      int32_t* needed /* 3 */);
+
 #ifdef __cplusplus
 }
 #endif

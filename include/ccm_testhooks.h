@@ -61,6 +61,12 @@ int  ccm_debug_dense_inverse(ccm_ctx* ctx, const double* A, int n, double* Ainv,
  * lanex::wave_incl_scan_i32 of the integer pattern (37 lane mod 101) - 20. */
 int  ccm_debug_lane_xor(ccm_ctx* ctx, const double* in64, double* out_6x3x64, double* sums_3x64);
 
+/* test hook for ccm_covis_update: the same call with a histogram window of 64 keyframe indices, so that a small n_all spans several windows */
+int  ccm_debug_covis_update_small(ccm_ctx* ctx, int n_kf, int n_all, const int32_t* order_key, const int32_t* list_off, const int32_t* list_pt,
+                                  const uint8_t* list_skip, int n_pt, const int32_t* obs_off, const int32_t* obs_kf, int th, int cap, int32_t* row_off,
+                                  int32_t* col, int32_t* count, int32_t* fw_off, int32_t* fw_col, int32_t* fw_w, int32_t* ord_off, int32_t* ord_kf,
+                                  int32_t* ord_w, int32_t* flags, int32_t* needed);
+
 #ifdef __cplusplus
 }
 #endif
