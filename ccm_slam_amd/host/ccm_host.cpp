@@ -5,6 +5,7 @@
 #include "../csrc/triangulate_math.h"
 #include "../csrc/sim3_correct_math.h"
 #include "../csrc/covis_math.h"
+#include "../csrc/kfcull_math.h"
 #include <climits>
 #include <algorithm>
 #include <cmath>
@@ -1360,6 +1361,146 @@ std::vector<int32_t> CovisibilityBatch::GetCovisiblesByWeight(int i, int w) cons
   return std::vector<int32_t>(ord_kf_.begin() + ord_off_[i], ord_kf_.begin() + ord_off_[i] + (it - b));
 }
 
+// ---- KeyFrameCullingBatch -------------------------------------------------------------------------------
+// ccm_kfcull_walk on the calling thread: the same checks and the rules of csrc/kfcull_math.h, one candidate after the other, every slot counted against the
+// current state (no volatile / non-volatile split: that is the device's shortcut, and n_reeval reports when it would have had to count again)
+int kfcull_walk_host(int n_cand, int n_all, const uint8_t* cand_flags, const int32_t* list_off, const int32_t* list_pt, const uint8_t* list_level, int n_pt,
+                     const int32_t* pt_nobs, const uint8_t* pt_bad, const int32_t* obs_off, const int32_t* obs_kf, const uint8_t* obs_level, const uint8_t* obs_bad,
+                     int th_obs, double thres, int n_levels, uint8_t* verdict, int32_t* n_mps, int32_t* n_red, uint8_t* pt_gone, int32_t* pt_nobs_out, int32_t* n_reeval) {
+  if (!verdict || !n_mps || !n_red || !n_reeval || (n_pt > 0 && (!pt_gone || !pt_nobs_out))) return -1;
+  if (kfcull_check_args(n_cand, n_all, cand_flags, list_off, list_pt, list_level, n_pt, pt_nobs, pt_bad, obs_off, obs_kf, obs_level, obs_bad, th_obs, thres, n_levels)) return -1;
+  std::vector<int32_t> flags((size_t)n_cand), n(pt_nobs, pt_nobs + n_pt), gone((size_t)n_pt), stamp((size_t)n_pt, 0);
+  for (int k = 0; k < n_cand; k++) flags[k] = cand_flags[k] & (KFCULL_SKIP | KFCULL_NOT_ERASE);
+  for (int p = 0; p < n_pt; p++) gone[p] = pt_bad[p] != 0;
+  std::vector<uint32_t> erased(((size_t)n_cand + 31) / 32, 0u);
+  bool erased_before = false;
+  *n_reeval = 0;
+  for (int k = 0; k < n_cand; k++) {
+    if (flags[k] & KFCULL_SKIP) { verdict[k] = KFCULL_SKIPPED; n_mps[k] = 0; n_red[k] = 0; continue; }
+    int32_t m = 0, r = 0, n_vol = 0;
+    for (int32_t e = list_off[k]; e < list_off[k + 1]; e++) {
+      const int32_t p = list_pt[e];
+      if (p < 0) continue;
+      if (!pt_bad[p]) {
+        bool vol = false;
+        for (int32_t o = obs_off[p]; o < obs_off[p + 1] && !vol; o++) vol = kfcull_observer_is_volatile(obs_kf[o], k, flags.data());
+        n_vol += vol;
+      }
+      if (!kfcull_slot_counts(p, gone[p])) continue;
+      m++;
+      if (kfcull_point_is_checked(n[p], th_obs))
+        r += kfcull_count_observers(obs_kf, obs_level, obs_bad, obs_off[p], obs_off[p + 1], erased.data(), n_cand, k, list_level[e], th_obs) >= th_obs;
+    }
+    if (kfcull_reevaluated(erased_before, n_vol)) ++*n_reeval;
+    n_mps[k] = m; n_red[k] = r;
+    verdict[k] = (uint8_t)kfcull_verdict(kfcull_redundant(r, m, thres), flags[k]);
+    if (verdict[k] != KFCULL_CULLED) continue;
+    erased[k >> 5] |= 1u << (k & 31);
+    erased_before = true;
+    for (int32_t e = list_off[k]; e < list_off[k + 1]; e++) {
+      const int32_t p = list_pt[e];
+      if (p < 0 || gone[p] || stamp[p] == k + 1) continue;
+      bool lists_back = false, live = false;
+      for (int32_t o = obs_off[p]; o < obs_off[p + 1]; o++) {
+        lists_back |= obs_kf[o] == k;
+        live |= !obs_bad[o] && !kfcull_erased(erased.data(), n_cand, obs_kf[o]);
+      }
+      if (!lists_back) continue;
+      stamp[p] = k + 1;
+      if (kfcull_point_goes(--n[p], live)) gone[p] = 1;
+    }
+  }
+  for (int p = 0; p < n_pt; p++) { pt_gone[p] = (uint8_t)gone[p]; pt_nobs_out[p] = n[p]; }
+  return 0;
+}
+
+// The walk the way the reference's data structures make it: a std::map of observations per point that GetObservations() copies for every checked slot of every
+// candidate (Mapping.cpp:829), keyframe bad flags behind a pointer, EraseObservation / SetBadFlag on the maps.  A MODEL of the reference's cost for
+// scripts/kfcull_profile.py (no mutexes, no shared_ptr counts, no graph updates), not the reference; its verdicts equal the evaluator's.
+int kfcull_walk_mapcopy_model(int n_cand, int n_all, const uint8_t* cand_flags, const int32_t* list_off, const int32_t* list_pt, const uint8_t* list_level, int n_pt,
+                              const int32_t* pt_nobs, const uint8_t* pt_bad, const int32_t* obs_off, const int32_t* obs_kf, const uint8_t* obs_level,
+                              const uint8_t* obs_bad, int th_obs, double thres, int n_levels, uint8_t* verdict) {
+  if (!verdict) return -1;
+  if (kfcull_check_args(n_cand, n_all, cand_flags, list_off, list_pt, list_level, n_pt, pt_nobs, pt_bad, obs_off, obs_kf, obs_level, obs_bad, th_obs, thres, n_levels)) return -1;
+  struct Kf { bool bad = false; };
+  struct Pt { std::map<Kf*, size_t> obs; int n = 0; bool bad = false; };
+  std::vector<Kf> kfs((size_t)n_all);
+  std::vector<Pt> pts((size_t)n_pt);
+  for (int p = 0; p < n_pt; p++) {
+    pts[p].n = pt_nobs[p]; pts[p].bad = pt_bad[p] != 0;
+    for (int32_t o = obs_off[p]; o < obs_off[p + 1]; o++) { pts[p].obs[&kfs[obs_kf[o]]] = obs_level[o]; if (obs_bad[o]) kfs[obs_kf[o]].bad = true; }
+  }
+  for (int k = 0; k < n_cand; k++) {
+    if (cand_flags[k] & KFCULL_SKIP) { verdict[k] = KFCULL_SKIPPED; continue; }
+    Kf* const me = &kfs[k];
+    int n_red = 0, n_mps = 0;
+    for (int32_t e = list_off[k]; e < list_off[k + 1]; e++) {
+      if (list_pt[e] < 0) continue;
+      Pt& pt = pts[list_pt[e]];
+      if (pt.bad) continue;
+      n_mps++;
+      if (pt.n <= th_obs) continue;
+      const std::map<Kf*, size_t> observations = pt.obs;      // the copy of GetObservations()
+      int n = 0;
+      for (const auto& ob : observations) {
+        if (ob.first->bad || ob.first == me) continue;
+        if ((int)ob.second <= (int)list_level[e] + 1 && ++n >= th_obs) break;
+      }
+      n_red += n >= th_obs;
+    }
+    verdict[k] = (uint8_t)kfcull_verdict(kfcull_redundant(n_red, n_mps, thres), cand_flags[k]);
+    if (verdict[k] != KFCULL_CULLED) continue;
+    for (int32_t e = list_off[k]; e < list_off[k + 1]; e++) {
+      if (list_pt[e] < 0) continue;
+      Pt& pt = pts[list_pt[e]];
+      if (pt.bad || !pt.obs.erase(me)) continue;
+      pt.n--;
+      bool live = false;
+      for (const auto& ob : pt.obs) live |= !ob.first->bad;
+      if (kfcull_point_goes(pt.n, live)) { pt.bad = true; pt.obs.clear(); }
+    }
+    me->bad = true;
+  }
+  return 0;
+}
+
+KeyFrameCullingBatch::KeyFrameCullingBatch(HipContext* ctx, int n_all, const std::vector<uint8_t>& cand_flags, const std::vector<int32_t>& list_off,
+                                           const std::vector<int32_t>& list_pt, const std::vector<uint8_t>& list_level, const std::vector<int32_t>& pt_nobs,
+                                           const std::vector<uint8_t>& pt_bad, const std::vector<int32_t>& obs_off, const std::vector<int32_t>& obs_kf,
+                                           const std::vector<uint8_t>& obs_level, const std::vector<uint8_t>& obs_bad, double thres, int n_levels, int th_obs)
+    : bad_before_(pt_bad) {
+  const int n_cand = (int)cand_flags.size(), n_pt = (int)pt_nobs.size();
+  if (n_cand < 1 || list_off.size() != (size_t)n_cand + 1 || list_off[0] != 0 || list_off[n_cand] < 0 || (size_t)list_off[n_cand] != list_pt.size() ||
+      list_level.size() != list_pt.size() || pt_bad.size() != (size_t)n_pt || obs_off.size() != (size_t)n_pt + 1 || obs_off[0] != 0 || obs_off.back() < 0 ||
+      (size_t)obs_off.back() != obs_kf.size() || obs_level.size() != obs_kf.size() || obs_bad.size() != obs_kf.size())
+    throw infrastructure_ex("KeyFrameCullingBatch: arrays");
+  verdict_.assign((size_t)n_cand, 0); n_mps_.assign((size_t)n_cand, 0); n_red_.assign((size_t)n_cand, 0);
+  gone_.assign((size_t)n_pt, 0); n_obs_.assign((size_t)n_pt, 0);
+  if (ctx) {
+    check(ccm_kfcull_walk(ctx->get(), n_cand, n_all, cand_flags.data(), list_off.data(), list_pt.data(), list_level.data(), n_pt, pt_nobs.data(), pt_bad.data(),
+                          obs_off.data(), obs_kf.data(), obs_level.data(), obs_bad.data(), th_obs, thres, n_levels, verdict_.data(), n_mps_.data(), n_red_.data(),
+                          gone_.data(), n_obs_.data(), &n_reeval_),
+          ctx->get(), "ccm_kfcull_walk");
+  } else if (kfcull_walk_host(n_cand, n_all, cand_flags.data(), list_off.data(), list_pt.data(), list_level.data(), n_pt, pt_nobs.data(), pt_bad.data(), obs_off.data(),
+                              obs_kf.data(), obs_level.data(), obs_bad.data(), th_obs, thres, n_levels, verdict_.data(), n_mps_.data(), n_red_.data(), gone_.data(),
+                              n_obs_.data(), &n_reeval_)) {
+    throw infrastructure_ex("KeyFrameCullingBatch: bad arguments");
+  }
+}
+
+std::vector<int32_t> KeyFrameCullingBatch::culled() const {
+  std::vector<int32_t> v;
+  for (size_t k = 0; k < verdict_.size(); k++)
+    if (verdict_[k] == KFCULL_CULLED || verdict_[k] == KFCULL_REDUNDANT_NOT_ERASED) v.push_back((int32_t)k);
+  return v;
+}
+std::vector<int32_t> KeyFrameCullingBatch::pointsGone() const {
+  std::vector<int32_t> v;
+  for (size_t p = 0; p < gone_.size(); p++)
+    if (gone_[p] && !bad_before_[p]) v.push_back((int32_t)p);
+  return v;
+}
+
 }  // namespace cslam
 
 // ---- C entry points (ccm_host_c.h): the Python test-suite and the drop-in translation units under shim/ ---------------------------------------
@@ -1746,6 +1887,53 @@ int ccmh_covis_update_host(int n_kf, int n_all, const int32_t* order_key, const 
                            int32_t* fw_w, int32_t* ord_off, int32_t* ord_kf, int32_t* ord_w, int32_t* flags, int32_t* needed) {
   return cslam::covis_update_host(n_kf, n_all, order_key, list_off, list_pt, list_skip, n_pt, obs_off, obs_kf, th, cap, row_off, col, count, fw_off, fw_col, fw_w, ord_off,
                                   ord_kf, ord_w, flags, needed);
+}
+
+// KeyFrameCullingBatch through C
+void* ccmh_kfcull_create(int device, int n_cand, int n_all, const uint8_t* cand_flags, const int32_t* list_off, const int32_t* list_pt, const uint8_t* list_level, int n_pt,
+                         const int32_t* pt_nobs, const uint8_t* pt_bad, const int32_t* obs_off, const int32_t* obs_kf, const uint8_t* obs_level, const uint8_t* obs_bad,
+                         int th_obs, double thres, int n_levels) {
+  try {
+    if (n_cand < 1 || n_pt < 0 || !cand_flags || !list_off || (n_pt > 0 && (!obs_off || !pt_nobs || !pt_bad))) return nullptr;
+    const int ne = list_off[n_cand], no = n_pt ? obs_off[n_pt] : 0;
+    if (ne < 0 || no < 0 || (ne > 0 && (!list_pt || !list_level)) || (no > 0 && (!obs_kf || !obs_level || !obs_bad))) return nullptr;
+    return new cslam::KeyFrameCullingBatch(device < 0 ? nullptr : &thread_context(device), n_all, std::vector<uint8_t>(cand_flags, cand_flags + n_cand),
+                                           std::vector<int32_t>(list_off, list_off + n_cand + 1), std::vector<int32_t>(list_pt, list_pt + ne),
+                                           std::vector<uint8_t>(list_level, list_level + ne), std::vector<int32_t>(pt_nobs, pt_nobs + n_pt),
+                                           std::vector<uint8_t>(pt_bad, pt_bad + n_pt), n_pt ? std::vector<int32_t>(obs_off, obs_off + n_pt + 1) : std::vector<int32_t>(1, 0),
+                                           std::vector<int32_t>(obs_kf, obs_kf + no), std::vector<uint8_t>(obs_level, obs_level + no),
+                                           std::vector<uint8_t>(obs_bad, obs_bad + no), thres, n_levels, th_obs);
+  } catch (const std::exception&) { return nullptr; }
+}
+int ccmh_kfcull_results(void* h, uint8_t* verdict, int32_t* n_mps, int32_t* n_red, uint8_t* pt_gone, int32_t* pt_nobs, int32_t* n_reeval) {
+  if (!h) return -1;
+  const cslam::KeyFrameCullingBatch& c = *static_cast<cslam::KeyFrameCullingBatch*>(h);
+  if (verdict) for (int k = 0; k < c.size(); k++) verdict[k] = (uint8_t)c.verdict(k);
+  if (n_mps && c.size()) std::memcpy(n_mps, c.nMPs().data(), (size_t)c.size() * 4);
+  if (n_red && c.size()) std::memcpy(n_red, c.nRedundant().data(), (size_t)c.size() * 4);
+  if (pt_gone && !c.gone().empty()) std::memcpy(pt_gone, c.gone().data(), c.gone().size());
+  if (pt_nobs && !c.observations().empty()) std::memcpy(pt_nobs, c.observations().data(), c.observations().size() * 4);
+  if (n_reeval) *n_reeval = c.reevaluated();
+  return 0;
+}
+static int kfcull_view(const std::vector<int32_t>& v, int32_t* out, int cap) {
+  if (out) for (int k = 0; k < (int)v.size() && k < cap; k++) out[k] = v[k];
+  return (int)v.size();
+}
+int ccmh_kfcull_culled(void* h, int32_t* out, int cap) { return h ? kfcull_view(static_cast<cslam::KeyFrameCullingBatch*>(h)->culled(), out, cap) : -1; }
+int ccmh_kfcull_points_gone(void* h, int32_t* out, int cap) { return h ? kfcull_view(static_cast<cslam::KeyFrameCullingBatch*>(h)->pointsGone(), out, cap) : -1; }
+void ccmh_kfcull_destroy(void* h) { delete static_cast<cslam::KeyFrameCullingBatch*>(h); }
+int ccmh_kfcull_walk_host(int n_cand, int n_all, const uint8_t* cand_flags, const int32_t* list_off, const int32_t* list_pt, const uint8_t* list_level, int n_pt,
+                          const int32_t* pt_nobs, const uint8_t* pt_bad, const int32_t* obs_off, const int32_t* obs_kf, const uint8_t* obs_level, const uint8_t* obs_bad,
+                          int th_obs, double thres, int n_levels, uint8_t* verdict, int32_t* n_mps, int32_t* n_red, uint8_t* pt_gone, int32_t* pt_nobs_out, int32_t* n_reeval) {
+  return cslam::kfcull_walk_host(n_cand, n_all, cand_flags, list_off, list_pt, list_level, n_pt, pt_nobs, pt_bad, obs_off, obs_kf, obs_level, obs_bad, th_obs, thres,
+                                 n_levels, verdict, n_mps, n_red, pt_gone, pt_nobs_out, n_reeval);
+}
+int ccmh_kfcull_walk_mapcopy_model(int n_cand, int n_all, const uint8_t* cand_flags, const int32_t* list_off, const int32_t* list_pt, const uint8_t* list_level, int n_pt,
+                                   const int32_t* pt_nobs, const uint8_t* pt_bad, const int32_t* obs_off, const int32_t* obs_kf, const uint8_t* obs_level,
+                                   const uint8_t* obs_bad, int th_obs, double thres, int n_levels, uint8_t* verdict) {
+  return cslam::kfcull_walk_mapcopy_model(n_cand, n_all, cand_flags, list_off, list_pt, list_level, n_pt, pt_nobs, pt_bad, obs_off, obs_kf, obs_level, obs_bad, th_obs,
+                                          thres, n_levels, verdict);
 }
 
 int ccmh_search_for_initialization(int device, const float* x1, const float* y1, const int32_t* oct1, const float* a1, const uint8_t* d1, int N1,

@@ -338,6 +338,43 @@ int covis_update_host(int n_kf, int n_all, const int32_t* order_key, const int32
                       const int32_t* obs_off, const int32_t* obs_kf, int th, int cap, int32_t* row_off, int32_t* col, int32_t* count, int32_t* fw_off, int32_t* fw_col,
                       int32_t* fw_w, int32_t* ord_off, int32_t* ord_kf, int32_t* ord_w, int32_t* flags, int32_t* needed);
 
+// LocalMapping::KeyFrameCullingV3's walk over the covisible keyframes of the picked keyframe (Mapping.cpp:804-862) as ONE ccm_kfcull_walk call: the verdict of every
+// candidate, identical to the sequential walk in which culling a keyframe erases its observations, lowers Observations() of its points and turns points with <= 2
+// observations bad before the next candidate is looked at.  The candidates are cand_flags.size() keyframes 0 .. in walk order (flag 1 SKIP: mId.first
+// 0 or 1 or in mlpRecentAddedKFs; 2 NOT_ERASE: mbNotErase), n_all - n_cand other observers follow.  Candidate k lists list_pt[list_off[k] .. list_off[k + 1]) (< 0:
+// null) with list_level = mvKeysUn[slot].octave; ONE record per distinct point: pt_nobs = Observations(), pt_bad = isBad(), its observers obs_kf[obs_off[p] ..
+// obs_off[p + 1]) with the octave of the point's feature there and the observer's isBad().  thres = params::mapping::mfRedundancyThres.  The pick (GetRandKfPtr,
+// mspKFsCheckedForCulling) and the calls `pKF->SetBadFlag(); ++mCulledKfs;` stay the caller's: for every keyframe of culled(), in that order.
+// ctx == nullptr asks for the host evaluator by name (csrc/kfcull_math.h compiled by g++); with a context, a device error throws — there is no fall-back.
+class KeyFrameCullingBatch {
+ public:
+  KeyFrameCullingBatch(HipContext* ctx, int n_all, const std::vector<uint8_t>& cand_flags, const std::vector<int32_t>& list_off, const std::vector<int32_t>& list_pt,
+                       const std::vector<uint8_t>& list_level, const std::vector<int32_t>& pt_nobs, const std::vector<uint8_t>& pt_bad, const std::vector<int32_t>& obs_off,
+                       const std::vector<int32_t>& obs_kf, const std::vector<uint8_t>& obs_level, const std::vector<uint8_t>& obs_bad, double thres, int n_levels,
+                       int th_obs = 3);
+  int size() const { return (int)verdict_.size(); }
+  int verdict(int k) const { return verdict_[k]; }          // 0 kept, 1 culled, 2 skipped, 3 redundant but mbNotErase
+  std::vector<int32_t> culled() const;                      // the candidates SetBadFlag is called on (verdicts 1 and 3), in walk order
+  std::vector<int32_t> pointsGone() const;                  // the points the walk turned bad (not those that were bad before), ascending
+  int reevaluated() const { return n_reeval_; }             // candidates counted again because an earlier erasure could reach one of their points
+  const std::vector<int32_t>& nMPs() const { return n_mps_; }              // as counted at the candidate's own turn
+  const std::vector<int32_t>& nRedundant() const { return n_red_; }
+  const std::vector<uint8_t>& gone() const { return gone_; }               // isBad() of every point after the walk
+  const std::vector<int32_t>& observations() const { return n_obs_; }      // Observations() of every point after the walk
+ private:
+  std::vector<uint8_t> verdict_, gone_, bad_before_;
+  std::vector<int32_t> n_mps_, n_red_, n_obs_;
+  int32_t n_reeval_ = 0;
+};
+// ccm_kfcull_walk's arguments after the context through csrc/kfcull_math.h on the calling thread; -1 where the device entry returns CCM_E_ARG
+int kfcull_walk_host(int n_cand, int n_all, const uint8_t* cand_flags, const int32_t* list_off, const int32_t* list_pt, const uint8_t* list_level, int n_pt,
+                     const int32_t* pt_nobs, const uint8_t* pt_bad, const int32_t* obs_off, const int32_t* obs_kf, const uint8_t* obs_level, const uint8_t* obs_bad,
+                     int th_obs, double thres, int n_levels, uint8_t* verdict, int32_t* n_mps, int32_t* n_red, uint8_t* pt_gone, int32_t* pt_nobs_out, int32_t* n_reeval);
+// the same walk on std::map observations copied per checked slot, as the reference's containers make it: a cost model for scripts/kfcull_profile.py; verdicts only
+int kfcull_walk_mapcopy_model(int n_cand, int n_all, const uint8_t* cand_flags, const int32_t* list_off, const int32_t* list_pt, const uint8_t* list_level, int n_pt,
+                              const int32_t* pt_nobs, const uint8_t* pt_bad, const int32_t* obs_off, const int32_t* obs_kf, const uint8_t* obs_level,
+                              const uint8_t* obs_bad, int th_obs, double thres, int n_levels, uint8_t* verdict);
+
 // ---------------------------------------------------------------------------------------------------
 // ORBVocabulary::transform (DBoW2 TemplatedVocabulary<FORB>, thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1127-1260) as
 // KeyFrame::ComputeBoW / Frame::ComputeBoW call it (levelsup = 4), and MapPoint::ComputeDistinctiveDescriptors

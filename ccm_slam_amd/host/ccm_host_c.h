@@ -55,6 +55,18 @@ int ccmh_covis_best(void* h, int i, int N, int32_t* out, int cap);
 int ccmh_covis_by_weight(void* h, int i, int w, int32_t* out, int cap);
 void ccmh_covis_destroy(void* h);
 int ccmh_covis_update_host(int n_kf, int n_all, const int32_t* order_key, const int32_t* list_off, const int32_t* list_pt, const uint8_t* list_skip, int n_pt, const int32_t* obs_off, const int32_t* obs_kf, int th, int cap, int32_t* row_off, int32_t* col, int32_t* count, int32_t* fw_off, int32_t* fw_col, int32_t* fw_w, int32_t* ord_off, int32_t* ord_kf, int32_t* ord_w, int32_t* flags, int32_t* needed);
+/* LocalMapping::KeyFrameCullingV3's walk (cslam::KeyFrameCullingBatch, ONE ccm_kfcull_walk call; arguments as there).  device < 0 asks for the host evaluator by name (no
+ * device is touched); with a device, a device error makes create return NULL.  results: any pointer may be NULL.  culled / points_gone: the candidates SetBadFlag is
+ * called on in walk order / the points the walk turned bad; returns the length (min(length, cap) written).
+ * ccmh_kfcull_walk_host: the arguments of ccm_kfcull_walk after the context through the same header on the calling thread (0, or -1 for its CCM_E_ARG cases).
+ * ccmh_kfcull_walk_mapcopy_model: the walk on std::map observations copied per checked slot, a cost model of the reference's containers; verdicts only. */
+void* ccmh_kfcull_create(int device, int n_cand, int n_all, const uint8_t* cand_flags, const int32_t* list_off, const int32_t* list_pt, const uint8_t* list_level, int n_pt, const int32_t* pt_nobs, const uint8_t* pt_bad, const int32_t* obs_off, const int32_t* obs_kf, const uint8_t* obs_level, const uint8_t* obs_bad, int th_obs, double thres, int n_levels);
+int ccmh_kfcull_results(void* h, uint8_t* verdict, int32_t* n_mps, int32_t* n_red, uint8_t* pt_gone, int32_t* pt_nobs, int32_t* n_reeval);
+int ccmh_kfcull_culled(void* h, int32_t* out, int cap);
+int ccmh_kfcull_points_gone(void* h, int32_t* out, int cap);
+void ccmh_kfcull_destroy(void* h);
+int ccmh_kfcull_walk_host(int n_cand, int n_all, const uint8_t* cand_flags, const int32_t* list_off, const int32_t* list_pt, const uint8_t* list_level, int n_pt, const int32_t* pt_nobs, const uint8_t* pt_bad, const int32_t* obs_off, const int32_t* obs_kf, const uint8_t* obs_level, const uint8_t* obs_bad, int th_obs, double thres, int n_levels, uint8_t* verdict, int32_t* n_mps, int32_t* n_red, uint8_t* pt_gone, int32_t* pt_nobs_out, int32_t* n_reeval);
+int ccmh_kfcull_walk_mapcopy_model(int n_cand, int n_all, const uint8_t* cand_flags, const int32_t* list_off, const int32_t* list_pt, const uint8_t* list_level, int n_pt, const int32_t* pt_nobs, const uint8_t* pt_bad, const int32_t* obs_off, const int32_t* obs_kf, const uint8_t* obs_level, const uint8_t* obs_bad, int th_obs, double thres, int n_levels, uint8_t* verdict);
 int ccmh_search_for_initialization(int device, const float* x1, const float* y1, const int32_t* oct1, const float* a1, const uint8_t* d1, int N1, const float* x2, const float* y2, const int32_t* oct2, const float* a2, const uint8_t* d2, int N2, float minX, float minY, float maxX, float maxY, float* prev_xy, int window, float nnratio, int check_ori, int32_t* matches12);
 int ccmh_projected_window_search(int device, const float* kx, const float* ky, const int32_t* oct, const uint8_t* kdesc, int N, float minX, float minY, float maxX, float maxY, const float* scale_factors, const float* inv_sigma2, int n_pts, const uint8_t* valid, const float* u, const float* v, const int32_t* level, const uint8_t* pdesc, float th, int chi2_gate, int dist_threshold, int32_t* matched, int claim, const uint8_t* no_claim, int32_t* best_idx, int32_t* best_dist);
 void* ccmh_fuse_batch_create_cand(int device, int S, const int32_t* kf_off, const float* kx, const float* ky, const int32_t* oct, const uint8_t* kdesc, const float* const* inv_sigma2, const int32_t* pt_off, const uint8_t* valid, const float* u, const float* v, const int32_t* level, const uint8_t* pdesc, const int32_t* cand_off, const int32_t* cand_base, const int32_t* cand_idx, int chi2_gate, int dist_threshold);
