@@ -6,9 +6,12 @@ CPU test-suite can check the exported symbols); creating a context without a gfx
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 import subprocess
 import weakref
+
+import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libccm_hip.so")
@@ -75,20 +78,33 @@ def lib():
     return _lib
 
 
-_hooks = None
+@functools.lru_cache(maxsize=None)
+def _load(name: str):
+    lib()   # the product library first: the others link against it
+    path = os.path.join(_HERE, name)
+    if not os.path.exists(path):
+        raise CcmError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
+    return C.CDLL(path)
 
 
 def hooks():
     """libccm_testhooks.so: the TEST-ONLY entry points (include/ccm_testhooks.h).  A separate library on top of the product; tests/ and scripts/ only."""
-    global _hooks
-    if _hooks is None:
-        lib()   # the product library first: the hooks link against it
-        path = os.path.join(_HERE, "libccm_testhooks.so")
-        if not os.path.exists(path):
-            raise CcmError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
-        _hooks = C.CDLL(path)
-        _hooks.ccm_comm_loopback_destroy.restype = None
-    return _hooks
+    h = _load("libccm_testhooks.so")
+    h.ccm_comm_loopback_destroy.restype = None
+    return h
+
+
+def host():
+    """libccm_host.so: the host mirrors of the reference's classes and the kernels' arithmetic compiled for the host; each module sets its own argtypes, once"""
+    return _load("libccm_host.so")
+
+
+def _p(a):
+    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def _arr(a, dt):
+    return None if a is None else np.ascontiguousarray(np.asarray(a, dt).reshape(-1))
 
 
 def check(rc: int, ctx=None):

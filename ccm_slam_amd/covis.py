@@ -9,12 +9,12 @@ repeated, null and bad list entries; a shuffled order_key) at the sizes of sim3_
 from __future__ import annotations
 
 import ctypes as C
-import os
+import functools
 from typing import Optional
 
 import numpy as np
 
-from ._lib import CcmError, Context, check, hooks, lib
+from ._lib import CcmError, Context, _arr, _p, check, hooks, host, lib
 from .sim3_correct import SIZES  # noqa: F401  (the three sizes the profile runs at)
 
 EMPTY, FALLBACK, CHANGED = 1, 2, 4
@@ -23,28 +23,19 @@ _OUT = ("row_off", "col", "count", "fw_off", "fw_col", "fw_w", "ord_off", "ord_k
 # ccm_covis_update after the context
 _FLAT_ARGTYPES = [C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 2 + [C.c_int, C.c_int] + [C.c_void_p] * 11
 
-_HOST = None
-
-
+@functools.lru_cache(maxsize=None)
 def _host():
-    global _HOST
-    if _HOST is None:
-        lib()
-        path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libccm_host.so")
-        if not os.path.exists(path):
-            raise CcmError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
-        h = C.CDLL(path)
-        h.ccmh_covis_create.restype = C.c_void_p
-        h.ccmh_covis_create.argtypes = [C.c_int] * 3 + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 2 + [C.c_int]
-        h.ccmh_covis_sizes.argtypes = [C.c_void_p] * 2
-        h.ccmh_covis_results.argtypes = [C.c_void_p] * 12
-        h.ccmh_covis_best.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
-        h.ccmh_covis_by_weight.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
-        h.ccmh_covis_destroy.argtypes = [C.c_void_p]
-        h.ccmh_covis_destroy.restype = None
-        h.ccmh_covis_update_host.argtypes = _FLAT_ARGTYPES
-        _HOST = h
-    return _HOST
+    h = host()
+    h.ccmh_covis_create.restype = C.c_void_p
+    h.ccmh_covis_create.argtypes = [C.c_int] * 3 + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 2 + [C.c_int]
+    h.ccmh_covis_sizes.argtypes = [C.c_void_p] * 2
+    h.ccmh_covis_results.argtypes = [C.c_void_p] * 12
+    h.ccmh_covis_best.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    h.ccmh_covis_by_weight.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    h.ccmh_covis_destroy.argtypes = [C.c_void_p]
+    h.ccmh_covis_destroy.restype = None
+    h.ccmh_covis_update_host.argtypes = _FLAT_ARGTYPES
+    return h
 
 
 _DEVICE = {}
@@ -57,14 +48,6 @@ def _device(small_window: bool):
         fn.argtypes = [C.c_void_p] + _FLAT_ARGTYPES
         _DEVICE[small_window] = fn
     return _DEVICE[small_window]
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
-
-
-def _arr(a, dt):
-    return None if a is None else np.ascontiguousarray(np.asarray(a, dt).reshape(-1))
 
 
 def _inputs(sc: dict):

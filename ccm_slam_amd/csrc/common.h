@@ -15,6 +15,7 @@
 #include <vector>
 #include <mutex>
 #include "../../include/ccm_hip.h"
+#include "staged_block.h"
 
 struct ccm_prof_slot {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
@@ -98,6 +99,11 @@ struct ccm_prof_scope {
 int ccm_scratch(ccm_ctx* ctx, size_t bytes, void** out);
 int ccm_io_scratch(ccm_ctx* ctx, size_t bytes, void** out);
 int ccm_pin_scratch(ccm_ctx* ctx, size_t bytes, void** out);
+// A staged block (staged_block.h) on the context's scratch, pinned block and stream.  begin: closes the declaration (CCM_E_ARG when it is none),
+// sizes both buffers, drains the stream and binds the block for the stage to fill.  upload: the ONE H2D copy.  download: the ONE D2H copy and the synchronise.
+int ccm_staged_begin(ccm_ctx* ctx, StagedBlock& b, const char* who);
+int ccm_staged_upload(ccm_ctx* ctx, const StagedBlock& b);
+int ccm_staged_download(ccm_ctx* ctx, const StagedBlock& b);
 // pooled device blocks: *actual receives the bucket size to hand back to ccm_pool_put
 int ccm_pool_get(ccm_ctx* ctx, size_t bytes, void** out, size_t* actual);
 void ccm_pool_put(ccm_ctx* ctx, void* p, size_t actual);

@@ -15,6 +15,7 @@
 // stage whose size exceeds cap is skipped together with what follows it.
 #include "common.h"
 #include "covis_math.h"
+#include "stage_blocks.h"
 #include "test_internal.h"
 #include <limits.h>
 
@@ -258,58 +259,32 @@ int covis_update_window(ccm_ctx* ctx, int small_window, int n_kf, int n_all, con
     return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + "bad args");
   if (const char* why = covis_check_args(n_kf, n_all, order_key, list_off, list_pt, list_skip, n_pt, obs_off, obs_kf, th, cap))
     return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + why);
-  CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  // device block in 4-byte words.  inputs: [order_key n_all | list_off n_kf + 1 | list_pt NL (null and skipped entries: -1) | obs_off n_pt + 1 | obs_kf NO];
-  // work: 6 arrays of n_kf, extra_off n_kf + 1, extra_src / extra_w cap; outputs: [hdr 4 | flags n_kf | row_off, fw_off, ord_off n_kf + 1 each | six arrays of
-  // cap].  One H2D of the inputs, one D2H of the outputs, both through the pinned staging buffer.
-  const size_t K = (size_t)n_kf, A = (size_t)n_all, P = (size_t)n_pt, NL = (size_t)list_off[n_kf], NO = n_pt ? (size_t)obs_off[n_pt] : 0, C = (size_t)cap;
-  const size_t n_in = A + (K + 1) + NL + (P + 1) + NO;
-  const size_t n_work = 6 * K + (K + 1) + 2 * C;
-  const size_t n_out = 4 + K + 3 * (K + 1) + 6 * C;
-  void* scratch = nullptr;
-  int rc = ccm_scratch(ctx, (n_in + n_work + n_out) * 4 + 64, &scratch);
-  if (rc) return rc;
-  void* pin = nullptr;
-  rc = ccm_pin_scratch(ctx, (n_in > n_out ? n_in : n_out) * 4 + 64, &pin);
-  if (rc) return rc;
-  CCM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));   // the block may still feed an earlier copy
-  int32_t* hp = (int32_t*)pin;
-  size_t o = 0;
-  auto put = [&](const void* src, size_t n) { const size_t at = o; if (n) memcpy(hp + o, src, n * 4); o += n; return at; };
-  const size_t o_key = put(order_key, A);
-  const size_t o_loff = put(list_off, K + 1);
-  const size_t o_lpt = o;
-  for (size_t e = 0; e < NL; e++) hp[o++] = covis_entry_counts(list_pt[e], list_skip[e]) ? list_pt[e] : -1;
-  const size_t o_ooff = o;
-  if (n_pt) put(obs_off, P + 1); else hp[o++] = 0;
-  const size_t o_okf = put(obs_kf, NO);
-  int32_t* d = (int32_t*)scratch;
-  CCM_HIP_CHECK(ctx, hipMemcpyAsync(d, hp, n_in * 4, hipMemcpyHostToDevice, ctx->stream));
+  const size_t NL = (size_t)list_off[n_kf];
+  CovisBlock b((size_t)n_kf, (size_t)n_all, (size_t)n_pt, NL, n_pt ? (size_t)obs_off[n_pt] : 0, (size_t)cap);
+  if (int rc = ccm_staged_begin(ctx, b, me)) return rc;
+  b.put(b.order_key, order_key); b.put(b.list_off, list_off);
+  int32_t* h_lpt = b.up(b.list_pt);
+  for (size_t e = 0; e < NL; e++) h_lpt[e] = covis_entry_counts(list_pt[e], list_skip[e]) ? list_pt[e] : -1;
+  if (n_pt) b.put(b.obs_off, obs_off);
+  b.put(b.obs_kf, obs_kf);
+  if (int rc = ccm_staged_upload(ctx, b)) return rc;
   CovisArgs a;
   a.n_kf = n_kf; a.n_all = n_all; a.cap = cap; a.th = (uint32_t)th;
-  a.order_key = d + o_key; a.list_off = d + o_loff; a.list_pt = d + o_lpt; a.obs_off = d + o_ooff; a.obs_kf = d + o_okf;
-  int32_t* w = d + n_in;
-  a.row_size = w; a.n_ge = w + K; a.fb_col = w + 2 * K; a.extra_cnt = w + 3 * K; a.cursor = w + 4 * K; a.chg = w + 5 * K; a.extra_off = w + 6 * K;
-  a.extra_src = a.extra_off + K + 1; a.extra_w = a.extra_src + C;
-  int32_t* dout = w + n_work;
-  a.hdr = dout; a.flags = dout + 4; a.row_off = a.flags + K; a.fw_off = a.row_off + K + 1; a.ord_off = a.fw_off + K + 1;
-  a.col = a.ord_off + K + 1; a.count = a.col + C; a.fw_col = a.count + C; a.fw_w = a.fw_col + C; a.ord_kf = a.fw_w + C; a.ord_w = a.ord_kf + C;
+  a.order_key = b.dev(b.order_key); a.list_off = b.dev(b.list_off); a.list_pt = b.dev(b.list_pt); a.obs_off = b.dev(b.obs_off); a.obs_kf = b.dev(b.obs_kf);
+  a.row_size = b.dev(b.row_size); a.n_ge = b.dev(b.n_ge); a.fb_col = b.dev(b.fb_col); a.extra_cnt = b.dev(b.extra_cnt); a.cursor = b.dev(b.cursor);
+  a.chg = b.dev(b.chg); a.extra_off = b.dev(b.extra_off); a.extra_src = b.dev(b.extra_src); a.extra_w = b.dev(b.extra_w);
+  a.hdr = b.dev(b.hdr); a.flags = b.dev(b.flags); a.row_off = b.dev(b.row_off); a.fw_off = b.dev(b.fw_off); a.ord_off = b.dev(b.ord_off);
+  a.col = b.dev(b.col); a.count = b.dev(b.count); a.fw_col = b.dev(b.fw_col); a.fw_w = b.dev(b.fw_w); a.ord_kf = b.dev(b.ord_kf); a.ord_w = b.dev(b.ord_w);
   if (small_window) covis_launch<kCvWindowSmall>(ctx, a); else covis_launch<kCvWindow>(ctx, a);
   CCM_HIP_CHECK(ctx, hipGetLastError());
-  CCM_HIP_CHECK(ctx, hipMemcpyAsync(hp, dout, n_out * 4, hipMemcpyDeviceToHost, ctx->stream));
-  CCM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  const int32_t* h = hp;
-  needed[0] = h[0]; needed[1] = h[1]; needed[2] = h[2];
+  if (int rc = ccm_staged_download(ctx, b)) return rc;
+  b.get(b.hdr, needed, 3);
   if (needed[0] > cap || needed[1] > cap || needed[2] > cap) return CCM_OK;   // nothing else is defined: the caller comes back with a larger cap
-  h += 4;
-  memcpy(flags, h, K * 4); h += K;
-  memcpy(row_off, h, (K + 1) * 4); h += K + 1;
-  memcpy(fw_off, h, (K + 1) * 4); h += K + 1;
-  memcpy(ord_off, h, (K + 1) * 4); h += K + 1;
+  b.get(b.flags, flags); b.get(b.row_off, row_off); b.get(b.fw_off, fw_off); b.get(b.ord_off, ord_off);
   const size_t n0 = (size_t)needed[0], n1 = (size_t)needed[1], n2 = (size_t)needed[2];
-  if (n0) { memcpy(col, h, n0 * 4); memcpy(count, h + C, n0 * 4); }
-  if (n1) { memcpy(fw_col, h + 2 * C, n1 * 4); memcpy(fw_w, h + 3 * C, n1 * 4); }
-  if (n2) { memcpy(ord_kf, h + 4 * C, n2 * 4); memcpy(ord_w, h + 5 * C, n2 * 4); }
+  b.get(b.col, col, n0); b.get(b.count, count, n0);
+  b.get(b.fw_col, fw_col, n1); b.get(b.fw_w, fw_w, n1);
+  b.get(b.ord_kf, ord_kf, n2); b.get(b.ord_w, ord_w, n2);
   return CCM_OK;
 }
 }  // namespace ccm_internal

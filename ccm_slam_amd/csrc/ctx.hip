@@ -277,6 +277,31 @@ int ccm_pin_scratch(ccm_ctx* ctx, size_t bytes, void** out) {
   return CCM_OK;
 }
 
+int ccm_staged_begin(ccm_ctx* ctx, StagedBlock& b, const char* who) {
+  if (const char* why = b.finish()) return ccm_set_error(ctx, CCM_E_ARG, std::string(who) + why);
+  CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  void *dev = nullptr, *pin = nullptr;
+  if (int rc = ccm_scratch(ctx, b.bytes(), &dev)) return rc;
+  if (int rc = ccm_pin_scratch(ctx, b.pin_bytes(), &pin)) return rc;
+  // THE rule for the pinned block: drain the stream before the first host write into it.  An earlier call on this context may have returned with work in flight
+  // that still reads or writes the block (the keypoint upload of ccm_frame_set_keypoints, the ticket-polled kernel of ccm_pose_optimize).  The device side
+  // needs no such rule: everything that touches the scratch is ordered on this one stream.
+  CCM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  b.bind(pin, dev);
+  return CCM_OK;
+}
+
+int ccm_staged_upload(ccm_ctx* ctx, const StagedBlock& b) {
+  if (b.up_bytes()) CCM_HIP_CHECK(ctx, hipMemcpyAsync((char*)b.device() + b.up_begin(), b.host(), b.up_bytes(), hipMemcpyHostToDevice, ctx->stream));
+  return CCM_OK;
+}
+
+int ccm_staged_download(ccm_ctx* ctx, const StagedBlock& b) {
+  if (b.down_bytes()) CCM_HIP_CHECK(ctx, hipMemcpyAsync(b.host(), (char*)b.device() + b.down_begin(), b.down_bytes(), hipMemcpyDeviceToHost, ctx->stream));
+  CCM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  return CCM_OK;
+}
+
 // buckets: 4 KiB, then {1, 1.5} x 2^k — at most 50 % slack, few distinct sizes
 static size_t pool_bucket(size_t bytes) {
   for (size_t b = 4096;; b *= 2) {

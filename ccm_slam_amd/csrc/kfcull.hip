@@ -14,6 +14,7 @@
 // Nothing waits on another workgroup: the ordered part is one workgroup, and the kernel boundary orders eval before walk.
 #include "common.h"
 #include "kfcull_math.h"
+#include "stage_blocks.h"
 #include <algorithm>
 
 namespace {
@@ -188,50 +189,24 @@ extern "C" int ccm_kfcull_walk(ccm_ctx* ctx, int n_cand, int n_all, const uint8_
   if (const char* why = kfcull_check_args(n_cand, n_all, cand_flags, list_off, list_pt, list_level, n_pt, pt_nobs, pt_bad, obs_off, obs_kf, obs_level, obs_bad, th_obs,
                                           thres, n_levels))
     return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + why);
-  CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  // device block in 4-byte words.  outputs: [hdr 4 | verdict, n_mps, n_red n_cand each | gone, nobs n_pt each]; work: [sums 4 n_cand | erased bits | stamp n_pt];
-  // inputs: [cand_flags n_cand | list_off n_cand + 1 | list_pt NL | obs_off n_pt + 1 | obs_kf NO | list_level NL bytes | obs_level, obs_bad NO bytes each]; then
-  // the slot bytes.  gone / nobs arrive as pt_bad / pt_nobs and the work arrays as zeros, so ONE H2D copy carries everything up to the slot bytes; one D2H copy
-  // of the outputs.  Both go through the pinned staging buffer.
-  const size_t K = (size_t)n_cand, P = (size_t)n_pt, NL = (size_t)list_off[n_cand], NO = n_pt ? (size_t)obs_off[n_pt] : 0;
-  const size_t EW = (K + 31) / 32, WL = (NL + 3) / 4, WO = (NO + 3) / 4;
-  const size_t n_out = 4 + 3 * K + 2 * P;
-  const size_t n_work = 4 * K + EW + P;
-  const size_t n_in = K + (K + 1) + NL + (P + 1) + NO + WL + 2 * WO;
-  const size_t n_up = n_out + n_work + n_in;
-  void* scratch = nullptr;
-  int rc = ccm_scratch(ctx, (n_up + WL) * 4 + 64, &scratch);
-  if (rc) return rc;
-  void* pin = nullptr;
-  rc = ccm_pin_scratch(ctx, n_up * 4 + 64, &pin);
-  if (rc) return rc;
-  CCM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));   // the block may still feed an earlier copy
-  int32_t* hp = (int32_t*)pin;
-  memset(hp, 0, (n_out + n_work) * 4);
-  int32_t* d = (int32_t*)scratch;
+  const size_t K = (size_t)n_cand, P = (size_t)n_pt, NL = (size_t)list_off[n_cand];
+  KfcullBlock b(K, P, NL, n_pt ? (size_t)obs_off[n_pt] : 0);
+  if (int rc = ccm_staged_begin(ctx, b, me)) return rc;
+  int32_t* h_gone = b.up(b.gone);
+  for (size_t p = 0; p < P; p++) h_gone[p] = pt_bad[p] != 0;
+  b.put(b.nobs, pt_nobs);
+  int32_t* h_flags = b.up(b.cand_flags);
+  for (size_t k = 0; k < K; k++) h_flags[k] = cand_flags[k] & (KFCULL_SKIP | KFCULL_NOT_ERASE);
+  b.put(b.list_off, list_off); b.put(b.list_pt, list_pt);
+  if (n_pt) b.put(b.obs_off, obs_off);
+  b.put(b.obs_kf, obs_kf); b.put(b.list_level, list_level); b.put(b.obs_level, obs_level); b.put(b.obs_bad, obs_bad);
+  if (int rc = ccm_staged_upload(ctx, b)) return rc;
   KfcullArgs a;
   a.n_cand = n_cand; a.th_obs = th_obs; a.thres = thres;
-  size_t o = 0;
-  a.hdr = d + o; o += 4;
-  a.verdict = d + o; o += K;
-  a.n_mps = d + o; o += K;
-  a.n_red = d + o; o += K;
-  a.gone = d + o; for (size_t p = 0; p < P; p++) hp[o + p] = pt_bad[p] != 0; o += P;
-  a.nobs = d + o; if (P) memcpy(hp + o, pt_nobs, P * 4); o += P;
-  a.sums = d + o; o += 4 * K;
-  a.erased = (uint32_t*)(d + o); o += EW;
-  a.stamp = d + o; o += P;
-  a.cand_flags = d + o; for (size_t k = 0; k < K; k++) hp[o + k] = cand_flags[k] & (KFCULL_SKIP | KFCULL_NOT_ERASE); o += K;
-  a.list_off = d + o; memcpy(hp + o, list_off, (K + 1) * 4); o += K + 1;
-  a.list_pt = d + o; if (NL) memcpy(hp + o, list_pt, NL * 4); o += NL;
-  a.obs_off = d + o; if (P) memcpy(hp + o, obs_off, (P + 1) * 4); else hp[o] = 0; o += P + 1;
-  a.obs_kf = d + o; if (NO) memcpy(hp + o, obs_kf, NO * 4); o += NO;
-  auto bytes = [&](const uint8_t* src, size_t n, size_t words) { const uint8_t* at = (const uint8_t*)(d + o); if (words) { hp[o + words - 1] = 0; memcpy(hp + o, src, n); } o += words; return at; };
-  a.list_level = bytes(list_level, NL, WL);
-  a.obs_level = bytes(obs_level, NO, WO);
-  a.obs_bad = bytes(obs_bad, NO, WO);
-  a.slot = (uint8_t*)(d + o);
-  CCM_HIP_CHECK(ctx, hipMemcpyAsync(d, hp, n_up * 4, hipMemcpyHostToDevice, ctx->stream));
+  a.hdr = b.dev(b.hdr); a.verdict = b.dev(b.verdict); a.n_mps = b.dev(b.n_mps); a.n_red = b.dev(b.n_red); a.gone = b.dev(b.gone); a.nobs = b.dev(b.nobs);
+  a.sums = b.dev(b.sums); a.erased = b.dev(b.erased); a.stamp = b.dev(b.stamp);
+  a.cand_flags = b.dev(b.cand_flags); a.list_off = b.dev(b.list_off); a.list_pt = b.dev(b.list_pt); a.obs_off = b.dev(b.obs_off); a.obs_kf = b.dev(b.obs_kf);
+  a.list_level = b.dev(b.list_level); a.obs_level = b.dev(b.obs_level); a.obs_bad = b.dev(b.obs_bad); a.slot = b.dev(b.slot);
   int32_t longest = 0;
   for (int k = 0; k < n_cand; k++) longest = std::max(longest, list_off[k + 1] - list_off[k]);
   a.chunks = std::min(kKcMaxChunks, std::max(1, (longest + kKcBlock - 1) / kKcBlock));
@@ -240,15 +215,12 @@ extern "C" int ccm_kfcull_walk(ccm_ctx* ctx, int n_cand, int n_all, const uint8_
   if (NL) hipLaunchKernelGGL(kfcull_eval_kernel, dim3((unsigned)(K * (size_t)a.chunks)), dim3(kKcBlock), 0, ctx->stream, a);
   hipLaunchKernelGGL(kfcull_walk_kernel, dim3(1), dim3(kKcWalkBlock), 0, ctx->stream, a);
   CCM_HIP_CHECK(ctx, hipGetLastError());
-  CCM_HIP_CHECK(ctx, hipMemcpyAsync(hp, d, n_out * 4, hipMemcpyDeviceToHost, ctx->stream));
-  CCM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  *n_reeval = hp[0];
-  const int32_t* h = hp + 4;
-  for (size_t k = 0; k < K; k++) verdict[k] = (uint8_t)h[k];
-  memcpy(n_mps, h + K, K * 4);
-  memcpy(n_red, h + 2 * K, K * 4);
-  h += 3 * K;
-  for (size_t p = 0; p < P; p++) pt_gone[p] = (uint8_t)h[p];
-  if (P) memcpy(pt_nobs_out, h + P, P * 4);
+  if (int rc = ccm_staged_download(ctx, b)) return rc;
+  *n_reeval = b.down(b.hdr)[0];
+  const int32_t *h_verdict = b.down(b.verdict), *h_gone_out = b.down(b.gone);
+  for (size_t k = 0; k < K; k++) verdict[k] = (uint8_t)h_verdict[k];
+  b.get(b.n_mps, n_mps); b.get(b.n_red, n_red);
+  for (size_t p = 0; p < P; p++) pt_gone[p] = (uint8_t)h_gone_out[p];
+  b.get(b.nobs, pt_nobs_out);
   return CCM_OK;
 }

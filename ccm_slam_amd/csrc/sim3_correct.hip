@@ -9,6 +9,7 @@
 // The rank and centre tables are a few thousand keyframes x 12 bytes and stay in L2.
 #include "common.h"
 #include "sim3_correct_math.h"
+#include "stage_blocks.h"
 #include <limits.h>
 
 namespace {
@@ -107,80 +108,38 @@ extern "C" int ccm_sim3_correct_map(ccm_ctx* ctx, int n_kf, const float* Tiw, in
     for (size_t k = 0; k < NO; k++)
       if (obs_kf[k] < 0 || obs_kf[k] >= n_obs_kf) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + "observer out of range");
   }
-  CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  // device block in 4-byte words, the doubles first (8-byte aligned).  inputs: [Scw 8d | S_non 8d n_kf | S_cor 8d n_kf (epilogue form only)] [Twc 12 |
-  // Tiw 12 n_kf | centres 3 n_obs_kf | scale n_levels | pos 3P | normal 3P | dmin P | dmax P] [rank n_obs_kf | owner P | owner_rank P | obs_off P+1 |
-  // obs_kf NO | ref_kf P | ref_level P]; outputs: [S_non 8d n_kf | S_cor 8d n_kf] [pose 12 n_kf | centre 3 n_kf | pos 3P | normal 3P | dmin P | dmax P], then
-  // S_swi 8d n_kf, which stays on the device.  One H2D of the inputs, one D2H of the outputs, both through the pinned staging buffer.
-  const size_t K = (size_t)n_kf, KO = (size_t)n_obs_kf, P = (size_t)n_pt, L = (size_t)n_levels;
+  const size_t K = (size_t)n_kf, P = (size_t)n_pt;
   const bool loop = Tiw != nullptr;
-  const size_t n_in_d = 8 + (loop ? 0 : 16 * K);
-  const size_t n_in = (2 * n_in_d + 12 + (loop ? 12 * K : 0) + 3 * KO + L + 8 * P + KO + 2 * P + (P ? P + 1 : 0) + NO + 2 * P + 1) & ~(size_t)1;
-  const size_t n_out = (2 * 16 * K + 15 * K + 8 * P + 1) & ~(size_t)1;
-  void* scratch = nullptr;
-  int rc = ccm_scratch(ctx, (n_in + n_out + 2 * 8 * K) * 4 + 64, &scratch);
-  if (rc) return rc;
-  void* pin = nullptr;
-  rc = ccm_pin_scratch(ctx, (n_in > n_out ? n_in : n_out) * 4 + 64, &pin);
-  if (rc) return rc;
-  uint32_t* hp = (uint32_t*)pin;
-  size_t o = 0;
-  auto put = [&](const void* src, size_t n) { const size_t at = o; if (n) memcpy(hp + o, src, n * 4); o += n; return at; };
-  auto skip = [&](size_t n) { const size_t at = o; memset(hp + o, 0, n * 4); o += n; return at; };
-  const size_t o_scw = loop ? put(Scw, 16) : skip(16);
-  const size_t o_snon = loop ? 0 : put(S_non, 16 * K);
-  const size_t o_scor = loop ? 0 : put(S_cor, 16 * K);
-  const size_t o_twc = loop ? put(Twc, 12) : skip(12);
-  const size_t o_tiw = loop ? put(Tiw, 12 * K) : 0;
-  const size_t o_cen = put(kf_center, 3 * KO);
-  const size_t o_sf = put(scale_factors, L);
-  const size_t o_pos = put(pos, 3 * P);
-  const size_t o_nrm = put(normal, 3 * P);
-  const size_t o_dmin = put(min_dist, P);
-  const size_t o_dmax = put(max_dist, P);
-  const size_t o_rank = put(kf_rank, KO);
-  const size_t o_own = put(owner, P);
-  const size_t o_ork = put(owner_rank, P);
-  const size_t o_off = put(obs_off, P ? P + 1 : 0);
-  const size_t o_okf = put(obs_kf, NO);
-  const size_t o_ref = put(ref_kf, P);
-  const size_t o_lvl = put(ref_level, P);
-  uint32_t* d = (uint32_t*)scratch;
-  CCM_HIP_CHECK(ctx, hipMemcpyAsync(d, hp, n_in * 4, hipMemcpyHostToDevice, ctx->stream));
-  uint32_t* dout = d + n_in;
+  S3cBlock b(K, (size_t)n_obs_kf, P, (size_t)n_levels, NO, loop);
+  if (int rc = ccm_staged_begin(ctx, b, me)) return rc;
+  if (loop) { b.put(b.Scw, Scw); b.put(b.Twc, Twc); }
+  b.put(b.S_non_in, S_non); b.put(b.S_cor_in, S_cor); b.put(b.Tiw, Tiw);
+  b.put(b.c_old, kf_center); b.put(b.scale_factors, scale_factors);
+  b.put(b.pos, pos); b.put(b.normal_in, normal); b.put(b.dmin_in, min_dist); b.put(b.dmax_in, max_dist);
+  b.put(b.kf_rank, kf_rank); b.put(b.owner, owner); b.put(b.owner_rank, owner_rank);
+  b.put(b.obs_off, obs_off); b.put(b.obs_kf, obs_kf); b.put(b.ref_kf, ref_kf); b.put(b.ref_level, ref_level);
+  if (int rc = ccm_staged_upload(ctx, b)) return rc;
   S3cArgs a;
   a.n_kf = n_kf; a.n_pt = n_pt; a.cur = cur; a.n_levels = n_levels;
-  a.Tiw = loop ? (const float*)(d + o_tiw) : nullptr;
-  a.Twc = (const float*)(d + o_twc); a.Scw = (const double*)(d + o_scw);
-  // the epilogue form reads the caller's tables where the H2D copy put them; the loop form writes them into the output block
-  a.S_non = loop ? (double*)dout : (double*)(d + o_snon);
-  a.S_cor = loop ? (double*)(dout + 16 * K) : (double*)(d + o_scor);
-  a.S_swi = (double*)(dout + n_out);
-  a.T_new = (float*)(dout + 32 * K); a.c_new = a.T_new + 12 * K;
-  a.pos_out = a.c_new + 3 * K; a.normal_out = a.pos_out + 3 * P; a.dmin_out = a.normal_out + 3 * P; a.dmax_out = a.dmin_out + P;
-  a.c_old = (const float*)(d + o_cen); a.kf_rank = (const int32_t*)(d + o_rank); a.scale_factors = (const float*)(d + o_sf);
-  a.pos = (const float*)(d + o_pos); a.normal_in = (const float*)(d + o_nrm); a.dmin_in = (const float*)(d + o_dmin); a.dmax_in = (const float*)(d + o_dmax);
-  a.owner = (const int32_t*)(d + o_own); a.owner_rank = (const int32_t*)(d + o_ork); a.obs_off = (const int32_t*)(d + o_off);
-  a.obs_kf = (const int32_t*)(d + o_okf); a.ref_kf = (const int32_t*)(d + o_ref); a.ref_level = (const int32_t*)(d + o_lvl);
+  a.Tiw = loop ? b.dev(b.Tiw) : nullptr;
+  a.Twc = b.dev(b.Twc); a.Scw = b.dev(b.Scw);
+  // the epilogue form reads the caller's tables where the upload put them; the loop form writes them among the outputs
+  a.S_non = b.dev(loop ? b.S_non : b.S_non_in); a.S_cor = b.dev(loop ? b.S_cor : b.S_cor_in); a.S_swi = b.dev(b.S_swi);
+  a.T_new = b.dev(b.T_new); a.c_new = b.dev(b.c_new);
+  a.pos_out = b.dev(b.pos_out); a.normal_out = b.dev(b.normal_out); a.dmin_out = b.dev(b.dmin_out); a.dmax_out = b.dev(b.dmax_out);
+  a.c_old = b.dev(b.c_old); a.kf_rank = b.dev(b.kf_rank); a.scale_factors = b.dev(b.scale_factors);
+  a.pos = b.dev(b.pos); a.normal_in = b.dev(b.normal_in); a.dmin_in = b.dev(b.dmin_in); a.dmax_in = b.dev(b.dmax_in);
+  a.owner = b.dev(b.owner); a.owner_rank = b.dev(b.owner_rank); a.obs_off = b.dev(b.obs_off);
+  a.obs_kf = b.dev(b.obs_kf); a.ref_kf = b.dev(b.ref_kf); a.ref_level = b.dev(b.ref_level);
   hipLaunchKernelGGL(sim3_correct_kf_kernel, dim3((unsigned)((K + kS3cBlock - 1) / kS3cBlock)), dim3(kS3cBlock), 0, ctx->stream, a);
   CCM_HIP_CHECK(ctx, hipGetLastError());
   if (P) {
     hipLaunchKernelGGL(sim3_correct_pt_kernel, dim3((unsigned)((P + kS3cBlock - 1) / kS3cBlock)), dim3(kS3cBlock), 0, ctx->stream, a);
     CCM_HIP_CHECK(ctx, hipGetLastError());
   }
-  // the loop form copies the two Sim3 tables back with the rest; the epilogue form's are the caller's own and are skipped
-  const size_t skip_out = loop ? 0 : 32 * K;
-  CCM_HIP_CHECK(ctx, hipMemcpyAsync(hp, dout + skip_out, (n_out - skip_out) * 4, hipMemcpyDeviceToHost, ctx->stream));
-  CCM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  const uint32_t* h = hp;
-  if (loop) { memcpy(S_non, h, 16 * K * 4); memcpy(S_cor, h + 16 * K, 16 * K * 4); h += 32 * K; }
-  memcpy(Tiw_new, h, 12 * K * 4); h += 12 * K;
-  memcpy(center_new, h, 3 * K * 4); h += 3 * K;
-  if (P) {
-    memcpy(pos_out, h, 3 * P * 4); h += 3 * P;
-    memcpy(normal, h, 3 * P * 4); h += 3 * P;
-    memcpy(min_dist, h, P * 4); h += P;
-    memcpy(max_dist, h, P * 4);
-  }
+  if (int rc = ccm_staged_download(ctx, b)) return rc;
+  if (loop) { b.get(b.S_non, S_non); b.get(b.S_cor, S_cor); }   // the epilogue form's tables are the caller's own
+  b.get(b.T_new, Tiw_new); b.get(b.c_new, center_new);
+  b.get(b.pos_out, pos_out); b.get(b.normal_out, normal); b.get(b.dmin_out, min_dist); b.get(b.dmax_out, max_dist);
   return CCM_OK;
 }

@@ -8,6 +8,7 @@
 // Points are read from global memory: a candidate holds a few thousand points at most, which the hypotheses of one launch share through L2.
 #include "common.h"
 #include "sim3_ransac_math.h"
+#include "stage_blocks.h"
 
 namespace {
 
@@ -101,46 +102,19 @@ extern "C" int ccm_sim3_ransac_eval(ccm_ctx* ctx, int K, const int32_t* pt_off, 
     mask_off[h + 1] = (int32_t)words;
   }
   if (H == 0) return CCM_OK;
-  CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const size_t Nt = (size_t)pt_off[K];
-  // device block (4-byte elements): inputs [pt_off K+1 | X1 3Nt | X2 3Nt | K1 4K | K2 4K | thr1 Nt | thr2 Nt | hyp_cand H | hyp_idx 3H | mask_off H+1],
-  // then outputs [n_inl H | rts 13H | mask words].  One H2D of the inputs, one D2H of the outputs, both through the pinned staging buffer.
-  const size_t n_in = (K + 1) + 6 * Nt + 8 * (size_t)K + 2 * Nt + 4 * (size_t)H + (H + 1);
-  const size_t n_out = 14 * (size_t)H + (size_t)words;
-  void* scratch = nullptr;
-  int rc = ccm_scratch(ctx, (n_in + n_out) * 4 + 64, &scratch);
-  if (rc) return rc;
-  void* pin = nullptr;
-  rc = ccm_pin_scratch(ctx, (n_in > n_out ? n_in : n_out) * 4 + 64, &pin);
-  if (rc) return rc;
-  uint32_t* hp = (uint32_t*)pin;
-  size_t o = 0;
-  auto put = [&](const void* src, size_t n) { memcpy(hp + o, src, n * 4); o += n; };
-  const size_t o_pt = o; put(pt_off, K + 1);
-  const size_t o_x1 = o; put(X3Dc1, 3 * Nt);
-  const size_t o_x2 = o; put(X3Dc2, 3 * Nt);
-  const size_t o_k1 = o; put(K1, 4 * (size_t)K);
-  const size_t o_k2 = o; put(K2, 4 * (size_t)K);
-  const size_t o_t1 = o; put(max_err1, Nt);
-  const size_t o_t2 = o; put(max_err2, Nt);
-  const size_t o_hc = o; put(hyp_cand, H);
-  const size_t o_hi = o; put(hyp_idx, 3 * (size_t)H);
-  const size_t o_mo = o; put(mask_off, H + 1);
-  uint32_t* d = (uint32_t*)scratch;
-  CCM_HIP_CHECK(ctx, hipMemcpyAsync(d, hp, n_in * 4, hipMemcpyHostToDevice, ctx->stream));
+  Sim3RansacBlock b((size_t)K, (size_t)pt_off[K], (size_t)H, (size_t)words);
+  if (int rc = ccm_staged_begin(ctx, b, "ccm_sim3_ransac_eval: ")) return rc;
+  b.put(b.pt_off, pt_off); b.put(b.X1, X3Dc1); b.put(b.X2, X3Dc2); b.put(b.K1, K1); b.put(b.K2, K2); b.put(b.thr1, max_err1); b.put(b.thr2, max_err2);
+  b.put(b.hyp_cand, hyp_cand); b.put(b.hyp_idx, hyp_idx); b.put(b.mask_off, mask_off);
+  if (int rc = ccm_staged_upload(ctx, b)) return rc;
   Sim3RansacArgs a;
   a.K = K; a.H = H; a.fix_scale = fix_scale ? 1 : 0;
-  a.pt_off = (const int32_t*)(d + o_pt); a.X1 = (const float*)(d + o_x1); a.X2 = (const float*)(d + o_x2);
-  a.K1 = (const float*)(d + o_k1); a.K2 = (const float*)(d + o_k2); a.thr1 = d + o_t1; a.thr2 = d + o_t2;
-  a.hyp_cand = (const int32_t*)(d + o_hc); a.hyp_idx = (const int32_t*)(d + o_hi); a.mask_off = (const int32_t*)(d + o_mo);
-  uint32_t* dout = d + n_in;
-  a.n_inl = (int32_t*)dout; a.rts = (float*)(dout + H); a.mask = dout + 14 * (size_t)H;
+  a.pt_off = b.dev(b.pt_off); a.X1 = b.dev(b.X1); a.X2 = b.dev(b.X2); a.K1 = b.dev(b.K1); a.K2 = b.dev(b.K2); a.thr1 = b.dev(b.thr1); a.thr2 = b.dev(b.thr2);
+  a.hyp_cand = b.dev(b.hyp_cand); a.hyp_idx = b.dev(b.hyp_idx); a.mask_off = b.dev(b.mask_off);
+  a.n_inl = b.dev(b.n_inl); a.rts = b.dev(b.rts); a.mask = b.dev(b.mask);
   hipLaunchKernelGGL(sim3_ransac_kernel, dim3((H + kWavesPerBlock - 1) / kWavesPerBlock), dim3(64 * kWavesPerBlock), 0, ctx->stream, a);
   CCM_HIP_CHECK(ctx, hipGetLastError());
-  CCM_HIP_CHECK(ctx, hipMemcpyAsync(hp, dout, n_out * 4, hipMemcpyDeviceToHost, ctx->stream));
-  CCM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  memcpy(n_inl, hp, (size_t)H * 4);
-  memcpy(rts, hp + H, 13 * (size_t)H * 4);
-  memcpy(mask, hp + 14 * (size_t)H, (size_t)words * 4);
+  if (int rc = ccm_staged_download(ctx, b)) return rc;
+  b.get(b.n_inl, n_inl); b.get(b.rts, rts); b.get(b.mask, mask);
   return CCM_OK;
 }

@@ -1,0 +1,83 @@
+// stage_blocks.h — the staged blocks (staged_block.h) of the five map stages, one declaration per segment, in device order.  Plain C++:
+// tests/host/staged_block_check.cpp rebuilds them on the CPU.  The members are initialised in the order they are written, the counts first.
+#pragma once
+#include "staged_block.h"
+#include "triangulate_math.h"
+
+// ccm_sim3_ransac_eval: the inputs, then the outputs.
+struct Sim3RansacBlock : StagedBlock {
+  const size_t K, Nt, H, words;
+  Sim3RansacBlock(size_t K, size_t Nt, size_t H, size_t words) : K(K), Nt(Nt), H(H), words(words) {}
+  StagedSeg<int32_t> pt_off = add<int32_t>(K + 1, SB_COPY);
+  StagedSeg<float> X1 = add<float>(3 * Nt, SB_COPY), X2 = add<float>(3 * Nt, SB_COPY), K1 = add<float>(4 * K, SB_COPY), K2 = add<float>(4 * K, SB_COPY);
+  StagedSeg<uint32_t> thr1 = add<uint32_t>(Nt, SB_COPY), thr2 = add<uint32_t>(Nt, SB_COPY);
+  StagedSeg<int32_t> hyp_cand = add<int32_t>(H, SB_COPY), hyp_idx = add<int32_t>(3 * H, SB_COPY), mask_off = add<int32_t>(H + 1, SB_COPY);
+  StagedSeg<int32_t> n_inl = add<int32_t>(H, SB_OUT);
+  StagedSeg<float> rts = add<float>(13 * H, SB_OUT);
+  StagedSeg<uint32_t> mask = add<uint32_t>(words, SB_OUT);
+};
+
+// ccm_triangulate_pairs: the inputs, then the outputs.  xy comes first and on 16 bytes for the kernel's float4 reads; the outputs start on 16 bytes as well.
+struct TriBlock : StagedBlock {
+  const size_t P, S, L;
+  TriBlock(size_t P, size_t S, size_t L) : P(P), S(S), L(L) {}
+  StagedSeg<float> xy = add<float>(4 * P, SB_COPY, 16);
+  StagedSeg<float> cam1 = add<float>(TRI_CAM_FLOATS, SB_COPY), cam2 = add<float>(TRI_CAM_FLOATS * S, SB_COPY);
+  StagedSeg<float> sigma2_1 = add<float>(L, SB_COPY), sf_1 = add<float>(L, SB_COPY), sigma2_2 = add<float>(L, SB_COPY), sf_2 = add<float>(L, SB_COPY);
+  StagedSeg<uint32_t> oct = add<uint32_t>(P, SB_GEN);   // oct1 | oct2 << 16
+  StagedSeg<int32_t> grp = add<int32_t>(P, SB_GEN);
+  StagedSeg<float> x3d = add<float>(3 * P, SB_OUT, 16);
+  StagedSeg<uint8_t> status = add<uint8_t>(P, SB_OUT);
+};
+
+// ccm_sim3_correct_map: the doubles lead the inputs and the outputs.  The loop form uploads Scw, Twc and Tiw and downloads the two Sim3 tables it computes; the
+// epilogue form uploads the caller's tables instead, and the tables' place among the outputs stays on the device, so the download starts behind it.  S_swi is
+// read by the point kernel only.
+struct S3cBlock : StagedBlock {
+  const size_t K, KO, P, L, NO; const bool loop;
+  S3cBlock(size_t K, size_t KO, size_t P, size_t L, size_t NO, bool loop) : K(K), KO(KO), P(P), L(L), NO(NO), loop(loop) {}
+  StagedSeg<double> Scw = add<double>(8, loop ? SB_COPY : SB_ZERO), S_non_in = add<double>(loop ? 0 : 8 * K, SB_COPY), S_cor_in = add<double>(loop ? 0 : 8 * K, SB_COPY);
+  StagedSeg<float> Twc = add<float>(12, loop ? SB_COPY : SB_ZERO), Tiw = add<float>(loop ? 12 * K : 0, SB_COPY);
+  StagedSeg<float> c_old = add<float>(3 * KO, SB_COPY), scale_factors = add<float>(L, SB_COPY);
+  StagedSeg<float> pos = add<float>(3 * P, SB_COPY), normal_in = add<float>(3 * P, SB_COPY), dmin_in = add<float>(P, SB_COPY), dmax_in = add<float>(P, SB_COPY);
+  StagedSeg<int32_t> kf_rank = add<int32_t>(KO, SB_COPY), owner = add<int32_t>(P, SB_COPY), owner_rank = add<int32_t>(P, SB_COPY);
+  StagedSeg<int32_t> obs_off = add<int32_t>(P ? P + 1 : 0, SB_COPY), obs_kf = add<int32_t>(NO, SB_COPY), ref_kf = add<int32_t>(P, SB_COPY), ref_level = add<int32_t>(P, SB_COPY);
+  StagedSeg<double> S_non = add<double>(8 * K, loop ? SB_OUT : SB_WORK), S_cor = add<double>(8 * K, loop ? SB_OUT : SB_WORK);
+  StagedSeg<float> T_new = add<float>(12 * K, SB_OUT), c_new = add<float>(3 * K, SB_OUT);
+  StagedSeg<float> pos_out = add<float>(3 * P, SB_OUT), normal_out = add<float>(3 * P, SB_OUT), dmin_out = add<float>(P, SB_OUT), dmax_out = add<float>(P, SB_OUT);
+  StagedSeg<double> S_swi = add<double>(8 * K, SB_WORK);
+};
+
+// ccm_covis_update: the inputs, the work arrays, the outputs.  An empty map still has obs_off[0] = 0.
+struct CovisBlock : StagedBlock {
+  const size_t K, A, P, NL, NO, C;
+  CovisBlock(size_t K, size_t A, size_t P, size_t NL, size_t NO, size_t C) : K(K), A(A), P(P), NL(NL), NO(NO), C(C) {}
+  typedef StagedSeg<int32_t> Seg;
+  Seg order_key = add<int32_t>(A, SB_COPY), list_off = add<int32_t>(K + 1, SB_COPY);
+  Seg list_pt = add<int32_t>(NL, SB_GEN);   // null and skipped entries: -1
+  Seg obs_off = add<int32_t>(P + 1, P ? SB_COPY : SB_ZERO), obs_kf = add<int32_t>(NO, SB_COPY);
+  Seg row_size = add<int32_t>(K, SB_WORK), n_ge = add<int32_t>(K, SB_WORK), fb_col = add<int32_t>(K, SB_WORK), extra_cnt = add<int32_t>(K, SB_WORK);
+  Seg cursor = add<int32_t>(K, SB_WORK), chg = add<int32_t>(K, SB_WORK), extra_off = add<int32_t>(K + 1, SB_WORK);
+  Seg extra_src = add<int32_t>(C, SB_WORK), extra_w = add<int32_t>(C, SB_WORK);
+  Seg hdr = add<int32_t>(4, SB_OUT), flags = add<int32_t>(K, SB_OUT);
+  Seg row_off = add<int32_t>(K + 1, SB_OUT), fw_off = add<int32_t>(K + 1, SB_OUT), ord_off = add<int32_t>(K + 1, SB_OUT);
+  Seg col = add<int32_t>(C, SB_OUT), count = add<int32_t>(C, SB_OUT), fw_col = add<int32_t>(C, SB_OUT), fw_w = add<int32_t>(C, SB_OUT);
+  Seg ord_kf = add<int32_t>(C, SB_OUT), ord_w = add<int32_t>(C, SB_OUT);
+};
+
+// ccm_kfcull_walk: the outputs lead, so that the download is the head of the block; gone / nobs go up as the caller's pt_bad / pt_nobs and the work arrays as
+// zeros, so one upload carries everything up to the slot bytes, which the eval kernel writes.
+struct KfcullBlock : StagedBlock {
+  const size_t K, P, NL, NO;
+  KfcullBlock(size_t K, size_t P, size_t NL, size_t NO) : K(K), P(P), NL(NL), NO(NO) {}
+  typedef StagedSeg<int32_t> Seg;
+  Seg hdr = add<int32_t>(4, SB_OUT | SB_ZERO), verdict = add<int32_t>(K, SB_OUT | SB_ZERO), n_mps = add<int32_t>(K, SB_OUT | SB_ZERO), n_red = add<int32_t>(K, SB_OUT | SB_ZERO);
+  Seg gone = add<int32_t>(P, SB_OUT | SB_GEN), nobs = add<int32_t>(P, SB_OUT | SB_COPY);
+  Seg sums = add<int32_t>(4 * K, SB_ZERO);
+  StagedSeg<uint32_t> erased = add<uint32_t>((K + 31) / 32, SB_ZERO);   // one bit per candidate
+  Seg stamp = add<int32_t>(P, SB_ZERO);
+  Seg cand_flags = add<int32_t>(K, SB_GEN), list_off = add<int32_t>(K + 1, SB_COPY), list_pt = add<int32_t>(NL, SB_COPY);
+  Seg obs_off = add<int32_t>(P + 1, P ? SB_COPY : SB_ZERO), obs_kf = add<int32_t>(NO, SB_COPY);
+  StagedSeg<uint8_t> list_level = add<uint8_t>(NL, SB_COPY), obs_level = add<uint8_t>(NO, SB_COPY), obs_bad = add<uint8_t>(NO, SB_COPY);
+  StagedSeg<uint8_t> slot = add<uint8_t>(NL, SB_WORK);
+};

@@ -6,6 +6,7 @@
 // the 4x4 Jacobi state has fixed indices only and stays in registers.  Lanes whose match fails the parallax gate leave before the SVD.
 #include "common.h"
 #include "triangulate_math.h"
+#include "stage_blocks.h"
 
 namespace {
 
@@ -65,49 +66,27 @@ extern "C" int ccm_triangulate_pairs(ccm_ctx* ctx, const float* cam1, int S, con
   if (!xy || !oct || !status || !x3d) return ccm_set_error(ctx, CCM_E_ARG, "ccm_triangulate_pairs: bad args");
   for (size_t i = 0; i < 2 * P; i++)
     if (oct[i] < 0 || oct[i] >= nlevels) return ccm_set_error(ctx, CCM_E_ARG, "ccm_triangulate_pairs: octave outside [0, nlevels)");
-  CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  // device block (4-byte words): inputs [xy 4P | cam1 21 | cam2 21S | four tables nlevels each | oct P | grp P], then outputs [x3d 3P | status P bytes].
-  // xy comes first so that its float4 reads are 16-byte aligned.  One H2D of the inputs, one D2H of the outputs, both through the pinned staging buffer.
-  const size_t L = (size_t)nlevels;
-  const size_t n_in = (4 * P + TRI_CAM_FLOATS * (size_t)(S + 1) + 4 * L + 2 * P + 3) & ~(size_t)3;
-  const size_t n_out = 3 * P + (P + 3) / 4;
-  void* scratch = nullptr;
-  int rc = ccm_scratch(ctx, (n_in + n_out) * 4 + 64, &scratch);
-  if (rc) return rc;
-  void* pin = nullptr;
-  rc = ccm_pin_scratch(ctx, (n_in > n_out ? n_in : n_out) * 4 + 64, &pin);
-  if (rc) return rc;
-  uint32_t* hp = (uint32_t*)pin;
-  size_t o = 0;
-  auto put = [&](const void* src, size_t n) { memcpy(hp + o, src, n * 4); o += n; };
-  const size_t o_xy = o; put(xy, 4 * P);
-  const size_t o_c1 = o; put(cam1, TRI_CAM_FLOATS);
-  const size_t o_c2 = o; put(cam2, TRI_CAM_FLOATS * (size_t)S);
-  const size_t o_s1 = o; put(sigma2_1, L);
-  const size_t o_f1 = o; put(sf_1, L);
-  const size_t o_s2 = o; put(sigma2_2, L);
-  const size_t o_f2 = o; put(sf_2, L);
-  const size_t o_oc = o;
-  for (size_t i = 0; i < P; i++) hp[o++] = (uint32_t)oct[2 * i] | ((uint32_t)oct[2 * i + 1] << 16);
-  const size_t o_gr = o;
+  TriBlock b(P, (size_t)S, (size_t)nlevels);
+  if (int rc = ccm_staged_begin(ctx, b, "ccm_triangulate_pairs: ")) return rc;
+  b.put(b.xy, xy); b.put(b.cam1, cam1); b.put(b.cam2, cam2);
+  b.put(b.sigma2_1, sigma2_1); b.put(b.sf_1, sf_1); b.put(b.sigma2_2, sigma2_2); b.put(b.sf_2, sf_2);
+  uint32_t* h_oct = b.up(b.oct);
+  for (size_t i = 0; i < P; i++) h_oct[i] = (uint32_t)oct[2 * i] | ((uint32_t)oct[2 * i + 1] << 16);
+  int32_t* h_grp = b.up(b.grp);
   for (int s = 0; s < S; s++)
-    for (int i = pair_off[s]; i < pair_off[s + 1]; i++) hp[o++] = (uint32_t)s;
-  uint32_t* d = (uint32_t*)scratch;
-  CCM_HIP_CHECK(ctx, hipMemcpyAsync(d, hp, n_in * 4, hipMemcpyHostToDevice, ctx->stream));
+    for (int i = pair_off[s]; i < pair_off[s + 1]; i++) h_grp[i] = s;
+  if (int rc = ccm_staged_upload(ctx, b)) return rc;
   TriArgs a;
   a.P = (int)P;
-  a.xy = (const float*)(d + o_xy); a.cam1 = (const float*)(d + o_c1); a.cam2 = (const float*)(d + o_c2);
-  a.sigma2_1 = (const float*)(d + o_s1); a.sf_1 = (const float*)(d + o_f1); a.sigma2_2 = (const float*)(d + o_s2); a.sf_2 = (const float*)(d + o_f2);
-  a.oct = d + o_oc; a.grp = (const int32_t*)(d + o_gr);
+  a.xy = b.dev(b.xy); a.cam1 = b.dev(b.cam1); a.cam2 = b.dev(b.cam2);
+  a.sigma2_1 = b.dev(b.sigma2_1); a.sf_1 = b.dev(b.sf_1); a.sigma2_2 = b.dev(b.sigma2_2); a.sf_2 = b.dev(b.sf_2);
+  a.oct = b.dev(b.oct); a.grp = b.dev(b.grp);
   a.ratioFactor = ratioFactor;
-  uint32_t* dout = d + n_in;
-  a.x3d = (float*)dout; a.status = (uint8_t*)(dout + 3 * P);
+  a.x3d = b.dev(b.x3d); a.status = b.dev(b.status);
   hipLaunchKernelGGL(triangulate_kernel, dim3((unsigned)((P + kTriBlock - 1) / kTriBlock)), dim3(kTriBlock), 0, ctx->stream, a);
   CCM_HIP_CHECK(ctx, hipGetLastError());
-  CCM_HIP_CHECK(ctx, hipMemcpyAsync(hp, dout, n_out * 4, hipMemcpyDeviceToHost, ctx->stream));
-  CCM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  memcpy(x3d, hp, 3 * P * 4);
-  memcpy(status, hp + 3 * P, P);
+  if (int rc = ccm_staged_download(ctx, b)) return rc;
+  b.get(b.x3d, x3d); b.get(b.status, status);
   // n_accepted: counted from the status bytes that have just come back (a device count would need a zeroing pass and atomics for a few thousand bytes)
   for (int s = 0; s < S; s++) {
     int32_t n = 0;

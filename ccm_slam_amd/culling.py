@@ -10,12 +10,12 @@ NOT_ERASE candidates and a pt_nobs that differs from the list's length; reorder 
 from __future__ import annotations
 
 import ctypes as C
-import os
+import functools
 from typing import Optional
 
 import numpy as np
 
-from ._lib import CcmError, Context, check, lib
+from ._lib import CcmError, Context, _arr, _p, check, host, lib
 
 SKIP, NOT_ERASE = 1, 2
 KEPT, CULLED, SKIPPED, REDUNDANT_NOT_ERASED = 0, 1, 2, 3
@@ -29,28 +29,19 @@ _OUT = (("verdict", np.uint8, "c"), ("n_mps", np.int32, "c"), ("n_red", np.int32
 _IN_ARGTYPES = [C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_double, C.c_int]
 _FLAT_ARGTYPES = _IN_ARGTYPES + [C.c_void_p] * 6
 
-_HOST = None
-
-
+@functools.lru_cache(maxsize=None)
 def _host():
-    global _HOST
-    if _HOST is None:
-        lib()
-        path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libccm_host.so")
-        if not os.path.exists(path):
-            raise CcmError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
-        h = C.CDLL(path)
-        h.ccmh_kfcull_create.restype = C.c_void_p
-        h.ccmh_kfcull_create.argtypes = [C.c_int] + _IN_ARGTYPES
-        h.ccmh_kfcull_results.argtypes = [C.c_void_p] * 7
-        h.ccmh_kfcull_culled.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-        h.ccmh_kfcull_points_gone.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-        h.ccmh_kfcull_destroy.argtypes = [C.c_void_p]
-        h.ccmh_kfcull_destroy.restype = None
-        h.ccmh_kfcull_walk_host.argtypes = _FLAT_ARGTYPES
-        h.ccmh_kfcull_walk_mapcopy_model.argtypes = _IN_ARGTYPES + [C.c_void_p]
-        _HOST = h
-    return _HOST
+    h = host()
+    h.ccmh_kfcull_create.restype = C.c_void_p
+    h.ccmh_kfcull_create.argtypes = [C.c_int] + _IN_ARGTYPES
+    h.ccmh_kfcull_results.argtypes = [C.c_void_p] * 7
+    h.ccmh_kfcull_culled.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    h.ccmh_kfcull_points_gone.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    h.ccmh_kfcull_destroy.argtypes = [C.c_void_p]
+    h.ccmh_kfcull_destroy.restype = None
+    h.ccmh_kfcull_walk_host.argtypes = _FLAT_ARGTYPES
+    h.ccmh_kfcull_walk_mapcopy_model.argtypes = _IN_ARGTYPES + [C.c_void_p]
+    return h
 
 
 _DEVICE = None
@@ -64,14 +55,6 @@ def _device():
         fn.argtypes = [C.c_void_p] + _FLAT_ARGTYPES
         _DEVICE = fn
     return _DEVICE
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
-
-
-def _arr(a, dt):
-    return None if a is None else np.ascontiguousarray(np.asarray(a, dt).reshape(-1))
 
 
 def _inputs(sc: dict, th_obs, thres, n_levels):

@@ -7,13 +7,9 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import Context, check, lib
+from ._lib import Context, _p, check, lib
 
 GRID_COLS, GRID_ROWS = 75, 48
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
 class FrameGrid:

@@ -9,36 +9,24 @@ One database may be queried from several threads at once, each with its own Cont
 from __future__ import annotations
 
 import ctypes as C
-import os
+import functools
 from typing import Dict, Iterable, Optional, Sequence
 
 import numpy as np
 
-from ._lib import CcmError, Context, check, lib
-
-_HOST = None
-
+from ._lib import CcmError, Context, _p, check, host, lib
 
 class KfdbFilter(C.Structure):
     _fields_ = [("self_key", C.c_int64), ("allow", C.c_void_p), ("n_allow", C.c_int), ("exclude", C.c_void_p), ("n_exclude", C.c_int),
                 ("exclude_groups", C.c_uint64)]
 
 
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
-
-
+@functools.lru_cache(maxsize=None)
 def _host():
-    global _HOST
-    if _HOST is None:
-        lib()
-        path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libccm_host.so")
-        if not os.path.exists(path):
-            raise CcmError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
-        _HOST = C.CDLL(path)
-        _HOST.ccmh_kfdb_detect.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_void_p, C.c_int,
-                                           C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    return _HOST
+    h = host()
+    h.ccmh_kfdb_detect.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_void_p, C.c_int,
+                                   C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    return h
 
 
 def _bow(word, value):

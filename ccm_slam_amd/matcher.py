@@ -12,11 +12,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import Context, check, lib
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+from ._lib import Context, _p, check, lib
 
 
 def hamming_dense_best2(ctx: Context, q: np.ndarray, t: np.ndarray):

@@ -8,41 +8,28 @@ thread's FIFO (draws_pending), or from a supplied array of raw rand() values.
 from __future__ import annotations
 
 import ctypes as C
-import os
+import functools
 from dataclasses import dataclass, field
 from typing import Optional, Sequence
 
 import numpy as np
 
-from ._lib import CcmError, Context, check, lib
+from ._lib import CcmError, Context, _p, check, host, lib
 
-_HOST = None
-
-
+@functools.lru_cache(maxsize=None)
 def _host():
-    global _HOST
-    if _HOST is None:
-        lib()
-        path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libccm_host.so")
-        if not os.path.exists(path):
-            raise CcmError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
-        h = C.CDLL(path)
-        h.ccmh_sim3_ransac_create.restype = C.c_void_p
-        h.ccmh_sim3_ransac_create.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 9 + [C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                                                      C.c_void_p, C.c_int64]
-        h.ccmh_sim3_ransac_next.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
-        h.ccmh_sim3_ransac_stats.argtypes = [C.c_void_p, C.c_void_p]
-        h.ccmh_sim3_ransac_destroy.argtypes = [C.c_void_p]
-        h.ccmh_sim3_ransac_destroy.restype = None
-        h.ccmh_sim3_draws_pending.argtypes = [C.c_void_p, C.c_int]
-        h.ccmh_sim3_draws_clear.restype = None
-        h.ccmh_sim3_solver_iterate.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4
-        _HOST = h
-    return _HOST
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+    h = host()
+    h.ccmh_sim3_ransac_create.restype = C.c_void_p
+    h.ccmh_sim3_ransac_create.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 9 + [C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                                                  C.c_void_p, C.c_int64]
+    h.ccmh_sim3_ransac_next.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
+    h.ccmh_sim3_ransac_stats.argtypes = [C.c_void_p, C.c_void_p]
+    h.ccmh_sim3_ransac_destroy.argtypes = [C.c_void_p]
+    h.ccmh_sim3_ransac_destroy.restype = None
+    h.ccmh_sim3_draws_pending.argtypes = [C.c_void_p, C.c_int]
+    h.ccmh_sim3_draws_clear.restype = None
+    h.ccmh_sim3_solver_iterate.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4
+    return h
 
 
 def max_error_thresholds(sigma2) -> np.ndarray:

@@ -9,51 +9,34 @@ flatten_epilogue turn a scene into the flat arguments.
 from __future__ import annotations
 
 import ctypes as C
-import os
+import functools
 from typing import Optional
 
 import numpy as np
 
 from . import synth
-from ._lib import CcmError, Context, check, lib
+from ._lib import CcmError, Context, _arr, _p, check, host, lib
 
 INT32_MAX = np.int32(2**31 - 1)
 # keyframes of the corrected set, map points: a loop neighbourhood, one agent's map, the 4-agent map (about 6.4 observations per point)
 SIZES = {"loop": (30, 3000), "agent": (500, 37500), "agents4": (2000, 150000)}
 
-_HOST = None
-
-
+@functools.lru_cache(maxsize=None)
 def _host():
-    global _HOST
-    if _HOST is None:
-        lib()
-        path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libccm_host.so")
-        if not os.path.exists(path):
-            raise CcmError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
-        h = C.CDLL(path)
-        h.ccmh_sim3corr_create_loop.restype = C.c_void_p
-        h.ccmh_sim3corr_create_loop.argtypes = [C.c_int] * 3 + [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 9 + [C.c_int]
-        h.ccmh_sim3corr_create_epilogue.restype = C.c_void_p
-        h.ccmh_sim3corr_create_epilogue.argtypes = [C.c_int] * 3 + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 9 + [C.c_int]
-        h.ccmh_sim3corr_results.argtypes = [C.c_void_p] * 10
-        h.ccmh_sim3corr_destroy.argtypes = [C.c_void_p]
-        h.ccmh_sim3corr_destroy.restype = None
-        h.ccmh_sim3_correct_map_host.argtypes = _FLAT_ARGTYPES
-        _HOST = h
-    return _HOST
+    h = host()
+    h.ccmh_sim3corr_create_loop.restype = C.c_void_p
+    h.ccmh_sim3corr_create_loop.argtypes = [C.c_int] * 3 + [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 9 + [C.c_int]
+    h.ccmh_sim3corr_create_epilogue.restype = C.c_void_p
+    h.ccmh_sim3corr_create_epilogue.argtypes = [C.c_int] * 3 + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 9 + [C.c_int]
+    h.ccmh_sim3corr_results.argtypes = [C.c_void_p] * 10
+    h.ccmh_sim3corr_destroy.argtypes = [C.c_void_p]
+    h.ccmh_sim3corr_destroy.restype = None
+    h.ccmh_sim3_correct_map_host.argtypes = _FLAT_ARGTYPES
+    return h
 
 
 # ccm_sim3_correct_map after the context
 _FLAT_ARGTYPES = [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 8 + [C.c_int] + [C.c_void_p] * 6
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
-
-
-def _arr(a, dt):
-    return None if a is None else np.ascontiguousarray(np.asarray(a, dt).reshape(-1))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------

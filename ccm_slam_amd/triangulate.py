@@ -11,43 +11,30 @@ points behind a camera, neighbours with a tiny baseline, and planted on-threshol
 from __future__ import annotations
 
 import ctypes as C
-import os
+import functools
 from typing import Optional, Sequence
 
 import numpy as np
 
 from . import synth
-from ._lib import CcmError, Context, check, lib
+from ._lib import CcmError, Context, _p, check, host, lib
 
 STATUS = ("accepted", "parallax", "w == 0", "z1 <= 0", "z2 <= 0", "reprojection 1", "reprojection 2", "zero distance", "scale ratio")
 CAM_FLOATS = 21
 
-_HOST = None
-
-
+@functools.lru_cache(maxsize=None)
 def _host():
-    global _HOST
-    if _HOST is None:
-        lib()
-        path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libccm_host.so")
-        if not os.path.exists(path):
-            raise CcmError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
-        h = C.CDLL(path)
-        h.ccmh_newpts_create.restype = C.c_void_p
-        h.ccmh_newpts_create.argtypes = [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 7 + [C.c_int] + [C.c_void_p] * 4 + [C.c_float]
-        h.ccmh_newpts_create_tri.restype = C.c_void_p
-        h.ccmh_newpts_create_tri.argtypes = [C.c_int] + [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 4 + [C.c_float]
-        h.ccmh_newpts_points.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3
-        h.ccmh_newpts_stats.argtypes = [C.c_void_p, C.c_void_p]
-        h.ccmh_newpts_destroy.argtypes = [C.c_void_p]
-        h.ccmh_newpts_destroy.restype = None
-        h.ccmh_triangulate_pairs_host.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4 + [C.c_float] + [C.c_void_p] * 3
-        _HOST = h
-    return _HOST
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+    h = host()
+    h.ccmh_newpts_create.restype = C.c_void_p
+    h.ccmh_newpts_create.argtypes = [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 7 + [C.c_int] + [C.c_void_p] * 4 + [C.c_float]
+    h.ccmh_newpts_create_tri.restype = C.c_void_p
+    h.ccmh_newpts_create_tri.argtypes = [C.c_int] + [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 4 + [C.c_float]
+    h.ccmh_newpts_points.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3
+    h.ccmh_newpts_stats.argtypes = [C.c_void_p, C.c_void_p]
+    h.ccmh_newpts_destroy.argtypes = [C.c_void_p]
+    h.ccmh_newpts_destroy.restype = None
+    h.ccmh_triangulate_pairs_host.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4 + [C.c_float] + [C.c_void_p] * 3
+    return h
 
 
 def _f32(a, shape=(-1,)):
