@@ -3900,3 +3900,21 @@ extern "C" int ccm_ba_optimize(ccm_ctx* ctx, ccm_ba_problem* prob, const ccm_ba_
   ccm_ba_destroy(ba);
   return rc;
 }
+
+// The device state of a handle in the caller's numbering, for ccm_gba_apply_map (gba_apply.hip): what ccm_ba_download copies out, left where it is.  Not part
+// of the C ABI.  stage_points == 0 only reports (nothing is launched); otherwise the optimised landmarks are brought into the caller's order in d_raw_pt on the
+// context's stream, as the download does.  Cameras: ccm_ba_download hands out the estimate of the Cp cameras that were vertices with a free pose (slot_cam,
+// ascending) and leaves the caller's values for the others, so both tables are returned: d_cam_qt (the estimate) and d_cam_raw (as uploaded).  One rank only: a
+// sharded handle's landmarks need the collective.
+namespace ccm_internal {
+int ba_gba_state(ccm_ba* ba, int stage_points, ccm_ctx** ctx, int* nranks, int* n_cam, int* n_lm, const double** d_cam_qt, const double** d_cam_raw,
+                 const int** d_slot_cam, int* n_slot, const double** d_pt_xyz) {
+  if (!ba || !ctx || !nranks || !n_cam || !n_lm) return CCM_E_ARG;
+  *ctx = ba->ctx; *nranks = ba->nranks; *n_cam = ba->n_cam; *n_lm = ba->n_pt;
+  if (!stage_points) return CCM_OK;
+  if (ba->nranks > 1 || !d_cam_qt || !d_cam_raw || !d_slot_cam || !n_slot || !d_pt_xyz) return CCM_E_ARG;
+  if (ba->Lp) RC(ccm_ba_points_to_raw_order(ba, ba->d.pt[ba->cur]));
+  *d_cam_qt = ba->d.cam[ba->cur]; *d_cam_raw = ba->d_raw_cam; *d_slot_cam = ba->d.slot_cam; *n_slot = ba->Cp; *d_pt_xyz = ba->d_raw_pt;
+  return CCM_OK;
+}
+}  // namespace ccm_internal

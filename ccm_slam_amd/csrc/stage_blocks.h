@@ -1,4 +1,4 @@
-// stage_blocks.h — the staged blocks (staged_block.h) of the five map stages, one declaration per segment, in device order.  Plain C++:
+// stage_blocks.h — the staged blocks (staged_block.h) of the map stages, one declaration per segment, in device order.  Plain C++:
 // tests/host/staged_block_check.cpp rebuilds them on the CPU.  The members are initialised in the order they are written, the counts first.
 #pragma once
 #include "staged_block.h"
@@ -80,4 +80,17 @@ struct KfcullBlock : StagedBlock {
   Seg obs_off = add<int32_t>(P + 1, P ? SB_COPY : SB_ZERO), obs_kf = add<int32_t>(NO, SB_COPY);
   StagedSeg<uint8_t> list_level = add<uint8_t>(NL, SB_COPY), obs_level = add<uint8_t>(NO, SB_COPY), obs_bad = add<uint8_t>(NO, SB_COPY);
   StagedSeg<uint8_t> slot = add<uint8_t>(NL, SB_WORK);
+};
+
+// ccm_gba_apply_map: the doubles lead the inputs.  The host form uploads the optimised state (C cameras, L landmarks); the handle form declares both with zero
+// length and reads the handle's own buffers.  NT keyframes that were no vertices in NL levels: tree_kf / lvl_off are written by the stage while it validates.
+struct GbaApplyBlock : StagedBlock {
+  const size_t K, P, C, L, NT, NL;
+  GbaApplyBlock(size_t K, size_t P, size_t C, size_t L, size_t NT, size_t NL) : K(K), P(P), C(C), L(L), NT(NT), NL(NL) {}
+  StagedSeg<double> cam_qt = add<double>(7 * C, SB_COPY), pt_xyz = add<double>(3 * L, SB_COPY);
+  StagedSeg<float> Tcw_old = add<float>(12 * K, SB_COPY), Twc_old = add<float>(12 * K, SB_COPY), pos = add<float>(3 * P, SB_COPY);
+  StagedSeg<int32_t> kf_parent = add<int32_t>(K, SB_COPY), kf_cam = add<int32_t>(K, SB_COPY), pt_vert = add<int32_t>(P, SB_COPY), pt_ref = add<int32_t>(P, SB_COPY);
+  StagedSeg<int32_t> tree_kf = add<int32_t>(NT, SB_GEN), lvl_off = add<int32_t>(NT ? NL + 1 : 0, SB_GEN);
+  StagedSeg<float> T_new = add<float>(12 * K, SB_OUT), Twc_new = add<float>(12 * K, SB_OUT), pos_out = add<float>(3 * P, SB_OUT);
+  StagedSeg<uint8_t> status = add<uint8_t>(P, SB_OUT);
 };

@@ -4,6 +4,7 @@
 #include "kfdb_resolve.h"
 #include "../csrc/triangulate_math.h"
 #include "../csrc/sim3_correct_math.h"
+#include "../csrc/gba_apply_math.h"
 #include "../csrc/covis_math.h"
 #include "../csrc/kfcull_math.h"
 #include <climits>
@@ -1213,6 +1214,77 @@ void Sim3MapCorrection::run(HipContext* ctx, const float* Tiw, int cur, const fl
   }
 }
 
+// ---- GbaMapUpdate ---------------------------------------------------------------------------------------
+// ccm_gba_apply_map's host form after the context through csrc/gba_apply_math.h on the calling thread: same checks, same lines.  The keyframes are taken in walk
+// order, which finishes every parent before its child.
+int gba_apply_map_host(int n_kf, const int32_t* kf_parent, const int32_t* kf_cam, const float* Tcw_old, const float* Twc_old, int n_pt, const float* pos,
+                       const int32_t* pt_vert, const int32_t* pt_ref, int n_cam, const double* cam_qt, int n_lm, const double* pt_xyz, float* T_new, float* Twc_new,
+                       float* pos_out, uint8_t* pt_status) {
+  if (n_kf < 1 || n_pt < 0 || !kf_parent || !kf_cam || !Tcw_old || !Twc_old || !T_new || !Twc_new || !cam_qt || n_cam < 1 || n_lm < 0 || (n_lm > 0 && !pt_xyz)) return -1;
+  if (n_pt > 0 && (!pos || !pt_vert || !pt_ref || !pos_out || !pt_status)) return -1;
+  std::vector<int32_t> depth((size_t)n_kf);
+  int n_tree = 0, n_lvl = 0;
+  if (gba_check_walk(n_kf, kf_parent, kf_cam, n_cam, depth.data(), &n_tree, &n_lvl) || gba_check_points(n_pt, pt_vert, pt_ref, n_lm, n_kf)) return -1;
+  for (int k = 0; k < n_kf; k++) {
+    float* T = T_new + 12 * (size_t)k;
+    if (kf_cam[k] >= 0) gba_pose_of_se3(cam_qt + 7 * (size_t)kf_cam[k], T);
+    else gba_child_pose(Tcw_old + 12 * (size_t)k, Twc_old + 12 * (size_t)kf_parent[k], T_new + 12 * (size_t)kf_parent[k], T);
+    gba_twc(T, Twc_new + 12 * (size_t)k);
+  }
+  for (int i = 0; i < n_pt; i++) {
+    const float P[3] = {pos[3 * (size_t)i], pos[3 * (size_t)i + 1], pos[3 * (size_t)i + 2]};
+    float out[3];
+    pt_status[i] = gba_point(pt_vert[i], pt_ref[i], pt_xyz, Tcw_old, Twc_new, P, out);
+    pos_out[3 * (size_t)i] = out[0]; pos_out[3 * (size_t)i + 1] = out[1]; pos_out[3 * (size_t)i + 2] = out[2];
+  }
+  return 0;
+}
+
+GbaMapUpdate::GbaMapUpdate(HipContext* ctx, Graph g, Points p, const std::vector<double>& cam_qt, const std::vector<double>& pt_xyz) : pts_(std::move(p)) {
+  const size_t n = g.kf_cam.size(), np = pts_.vert.size();
+  if (!n || g.origins.empty() || g.child_off.size() != n + 1 || g.child_off[0] != 0 || (size_t)g.child_off[n] != g.child_kf.size() || g.Tcw.size() != 12 * n ||
+      g.Twc.size() != 12 * n || pts_.pos.size() != 3 * np || pts_.ref_kf.size() != np || cam_qt.empty() || cam_qt.size() % 7 || pt_xyz.size() % 3)
+    throw infrastructure_ex("GbaMapUpdate: arrays");
+  // the list walk: a keyframe's position is the order in which it is pushed, which is the order in which it is popped
+  std::vector<int32_t> at(n, -1);
+  auto push = [&](int32_t kf, int32_t parent) {
+    if (kf < 0 || (size_t)kf >= n) throw infrastructure_ex("GbaMapUpdate: keyframe id out of range");
+    if (at[kf] >= 0) { n_twice_++; return; }
+    at[kf] = (int32_t)order_.size(); order_.push_back(kf); parent_.push_back(parent);
+  };
+  for (int32_t o : g.origins) push(o, -1);
+  for (size_t head = 0; head < order_.size(); head++) {
+    const int32_t kf = order_[head];
+    if (g.child_off[kf + 1] < g.child_off[kf]) throw infrastructure_ex("GbaMapUpdate: child_off decreases");
+    for (int32_t e = g.child_off[kf]; e < g.child_off[kf + 1]; e++) push(g.child_kf[e], (int32_t)head);
+  }
+  status_.assign(np, 0);
+  if (n_twice_) return;
+  const size_t K = order_.size();
+  std::vector<int32_t> cam(K), ref(np);
+  std::vector<float> Tcw(12 * K), Twc(12 * K);
+  for (size_t k = 0; k < K; k++) {
+    cam[k] = g.kf_cam[order_[k]];
+    std::memcpy(&Tcw[12 * k], &g.Tcw[12 * (size_t)order_[k]], 48); std::memcpy(&Twc[12 * k], &g.Twc[12 * (size_t)order_[k]], 48);
+  }
+  for (size_t i = 0; i < np; i++) {
+    const int32_t r = pts_.ref_kf[i];
+    if (r >= 0 && (size_t)r >= n) throw infrastructure_ex("GbaMapUpdate: reference keyframe out of range");
+    ref[i] = r < 0 ? -1 : at[r];   // reached: tagged, as a vertex or by the walk
+    if (r >= 0 && at[r] < 0 && g.kf_cam[r] >= 0 && pts_.vert[i] < 0) n_stale_++;
+  }
+  T_new_.assign(12 * K, 0.f); Twc_new_.assign(12 * K, 0.f);
+  const int n_cam = (int)(cam_qt.size() / 7), n_lm = (int)(pt_xyz.size() / 3);
+  if (ctx) {
+    check(ccm_gba_apply_map(ctx->get(), (int)K, parent_.data(), cam.data(), Tcw.data(), Twc.data(), (int)np, pts_.pos.data(), pts_.vert.data(), ref.data(), n_cam,
+                            cam_qt.data(), n_lm, pt_xyz.data(), nullptr, T_new_.data(), Twc_new_.data(), pts_.pos.data(), status_.data()),
+          ctx->get(), "ccm_gba_apply_map");
+  } else if (gba_apply_map_host((int)K, parent_.data(), cam.data(), Tcw.data(), Twc.data(), (int)np, pts_.pos.data(), pts_.vert.data(), ref.data(), n_cam, cam_qt.data(),
+                                n_lm, pt_xyz.data(), T_new_.data(), Twc_new_.data(), pts_.pos.data(), status_.data())) {
+    throw infrastructure_ex("GbaMapUpdate: bad arguments");
+  }
+}
+
 // ---- CovisibilityBatch ----------------------------------------------------------------------------------
 // ccm_covis_update on the calling thread: the same checks and the rules of csrc/covis_math.h, one keyframe after the other
 int covis_update_host(int n_kf, int n_all, const int32_t* order_key, const int32_t* list_off, const int32_t* list_pt, const uint8_t* list_skip, int n_pt,
@@ -1838,6 +1910,45 @@ int ccmh_sim3_correct_map_host(int n_kf, const float* Tiw, int cur, const float*
                                float* normal, float* min_dist, float* max_dist, float* Tiw_new, float* center_new) {
   return cslam::sim3_correct_map_host(n_kf, Tiw, cur, Twc, Scw, S_non, S_cor, n_obs_kf, kf_center, kf_rank, n_pt, pos, owner, owner_rank, obs_off, obs_kf, ref_kf, ref_level,
                                       scale_factors, n_levels, pos_out, normal, min_dist, max_dist, Tiw_new, center_new);
+}
+
+// GbaMapUpdate through C
+void* ccmh_gbaupd_create(int device, int n_kf, int n_origins, const int32_t* origins, const int32_t* child_off, const int32_t* child_kf, const int32_t* kf_cam, const float* Tcw,
+                         const float* Twc, int n_pt, const float* pos, const int32_t* vert, const int32_t* ref_kf, int n_cam, const double* cam_qt, int n_lm,
+                         const double* pt_xyz) {
+  try {
+    if (n_kf < 1 || n_origins < 1 || !origins || !child_off || !kf_cam || !Tcw || !Twc || n_pt < 0 || (n_pt > 0 && (!pos || !vert || !ref_kf)) || n_cam < 1 || !cam_qt ||
+        n_lm < 0 || (n_lm > 0 && !pt_xyz))
+      return nullptr;
+    const int ne = child_off[n_kf];
+    if (ne < 0 || (ne > 0 && !child_kf)) return nullptr;
+    cslam::GbaMapUpdate::Graph g;
+    g.origins.assign(origins, origins + n_origins); g.child_off.assign(child_off, child_off + n_kf + 1); g.child_kf.assign(child_kf, child_kf + ne);
+    g.kf_cam.assign(kf_cam, kf_cam + n_kf); g.Tcw.assign(Tcw, Tcw + 12 * (size_t)n_kf); g.Twc.assign(Twc, Twc + 12 * (size_t)n_kf);
+    cslam::GbaMapUpdate::Points p;
+    if (n_pt) { p.pos.assign(pos, pos + 3 * (size_t)n_pt); p.vert.assign(vert, vert + n_pt); p.ref_kf.assign(ref_kf, ref_kf + n_pt); }
+    return new cslam::GbaMapUpdate(device < 0 ? nullptr : &thread_context(device), std::move(g), std::move(p), std::vector<double>(cam_qt, cam_qt + 7 * (size_t)n_cam),
+                                   n_lm ? std::vector<double>(pt_xyz, pt_xyz + 3 * (size_t)n_lm) : std::vector<double>());
+  } catch (const std::exception&) { return nullptr; }
+}
+int ccmh_gbaupd_sizes(void* h, int64_t* out4) {
+  if (!h || !out4) return -1;
+  const cslam::GbaMapUpdate& u = *static_cast<cslam::GbaMapUpdate*>(h);
+  out4[0] = (int64_t)u.order().size(); out4[1] = u.reachedTwice(); out4[2] = u.staleReferences(); out4[3] = (int64_t)u.status().size();
+  return 0;
+}
+int ccmh_gbaupd_results(void* h, int32_t* order, int32_t* parent, float* T_new, float* Twc_new, float* pos, uint8_t* status) {
+  if (!h) return -1;
+  const cslam::GbaMapUpdate& u = *static_cast<cslam::GbaMapUpdate*>(h);
+  auto out = [](auto* dst, const auto& v) { if (dst && !v.empty()) std::memcpy(dst, v.data(), v.size() * sizeof(v[0])); };
+  out(order, u.order()); out(parent, u.parents()); out(T_new, u.poses()); out(Twc_new, u.inverses()); out(pos, u.positions()); out(status, u.status());
+  return 0;
+}
+void ccmh_gbaupd_destroy(void* h) { delete static_cast<cslam::GbaMapUpdate*>(h); }
+int ccmh_gba_apply_map_host(int n_kf, const int32_t* kf_parent, const int32_t* kf_cam, const float* Tcw_old, const float* Twc_old, int n_pt, const float* pos,
+                            const int32_t* pt_vert, const int32_t* pt_ref, int n_cam, const double* cam_qt, int n_lm, const double* pt_xyz, float* T_new, float* Twc_new,
+                            float* pos_out, uint8_t* pt_status) {
+  return cslam::gba_apply_map_host(n_kf, kf_parent, kf_cam, Tcw_old, Twc_old, n_pt, pos, pt_vert, pt_ref, n_cam, cam_qt, n_lm, pt_xyz, T_new, Twc_new, pos_out, pt_status);
 }
 
 // CovisibilityBatch through C

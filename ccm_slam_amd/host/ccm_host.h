@@ -295,6 +295,48 @@ class Sim3MapCorrection {
   std::vector<int32_t> tag_;
 };
 
+// A finished global BA applied to the map (Optimizer.cpp:803-857, then the walk of RunGBA: Map.cpp:1441-1568, LoopFinder.cpp ~895-1010, MapMerger.cpp ~640-755) as
+// ONE ccm_gba_apply_map call.  The reference walks a list from mvpKeyFrameOrigins, pushing every child behind its parent; a child that was no vertex of the BA
+// takes (GetPose() * Twc_parent) * mTcwGBA_parent, f32 products that do not re-associate, so it needs its parent's finished pose.  The class
+// flattens the graph into that walk order.  A keyframe reached twice (a child in two child sets, or a cycle) would be visited twice by the reference, the second
+// time with the pose the first visit set: nothing is evaluated then, and reachedTwice() tells the caller to take the sequential walk.  A point that was no
+// landmark moves with its reference keyframe if that keyframe is tagged (a vertex, or reached by the walk as none); a vertex the walk did not reach has a stale
+// mTcwBefGBA in the reference: such points are counted (staleReferences()) and left untouched.  SetPose, SetWorldPos, the tags and mbLoopCorrected stay the
+// caller's.  ctx == nullptr asks for the host evaluator by name (csrc/gba_apply_math.h compiled by g++); with a context, a device error throws — there is no
+// fall-back.
+class GbaMapUpdate {
+ public:
+  struct Graph {                                       // keyframes by id 0 .. n - 1
+    std::vector<int32_t> origins;                      // mvpKeyFrameOrigins, in order
+    std::vector<int32_t> child_off, child_kf;          // GetChilds() in the order the caller's set iterates, CSR over n + 1
+    std::vector<int32_t> kf_cam;                       // camera in the BA problem, -1: no vertex
+    std::vector<float> Tcw, Twc;                       // GetPose() / GetPoseInverse(), 12 floats each
+  };
+  struct Points {                                      // the non-bad points
+    std::vector<float> pos;                            // GetWorldPos, 3 n
+    std::vector<int32_t> vert, ref_kf;                 // BA landmark or -1; reference keyframe id or -1
+  };
+  GbaMapUpdate(HipContext* ctx, Graph g, Points p, const std::vector<double>& cam_qt, const std::vector<double>& pt_xyz);
+  int reachedTwice() const { return n_twice_; }        // > 0: nothing was evaluated
+  int staleReferences() const { return n_stale_; }
+  const std::vector<int32_t>& order() const { return order_; }      // keyframe id per walk position
+  const std::vector<int32_t>& parents() const { return parent_; }   // walk position of the parent, -1 for an origin
+  const std::vector<float>& poses() const { return T_new_; }        // 12 per walk position
+  const std::vector<float>& inverses() const { return Twc_new_; }   // 12 per walk position
+  const std::vector<float>& positions() const { return pts_.pos; }  // after the update
+  const std::vector<uint8_t>& status() const { return status_; }    // per point: 0 untouched, 1 optimised value, 2 moved
+ private:
+  Points pts_;
+  std::vector<int32_t> order_, parent_;
+  std::vector<float> T_new_, Twc_new_;
+  std::vector<uint8_t> status_;
+  int n_twice_ = 0, n_stale_ = 0;
+};
+// ccm_gba_apply_map's host form after the context through csrc/gba_apply_math.h on the calling thread; -1 where the device entry returns CCM_E_ARG
+int gba_apply_map_host(int n_kf, const int32_t* kf_parent, const int32_t* kf_cam, const float* Tcw_old, const float* Twc_old, int n_pt, const float* pos,
+                       const int32_t* pt_vert, const int32_t* pt_ref, int n_cam, const double* cam_qt, int n_lm, const double* pt_xyz, float* T_new, float* Twc_new,
+                       float* pos_out, uint8_t* pt_status);
+
 // KeyFrame::UpdateConnections (KeyFrame.cpp:629-711) for every keyframe of a corrected set (LoopFinder.cpp:612 / :655, MapMerger.cpp:392 / :487, Map.cpp:614) as ONE
 // ccm_covis_update call, with the AddConnection / UpdateBestCovisibles calls (:392-426) the set's keyframes make on each other: per keyframe the final
 // mConnectedKeyFrameWeights, mvpOrderedConnectedKeyFrames and mvOrderedWeights, identical to the sequential walk.  Keyframes 0 .. n_kf - 1 are the

@@ -43,6 +43,17 @@ void* ccmh_sim3corr_create_epilogue(int device, int n_kf, int n_obs_kf, const fl
 int ccmh_sim3corr_results(void* h, float* pos, float* normal, float* min_dist, float* max_dist, int32_t* tag, float* Tiw_new, float* center_new, double* S_non, double* S_cor);
 void ccmh_sim3corr_destroy(void* h);
 int ccmh_sim3_correct_map_host(int n_kf, const float* Tiw, int cur, const float* Twc, const double* Scw, double* S_non, double* S_cor, int n_obs_kf, const float* kf_center, const int32_t* kf_rank, int n_pt, const float* pos, const int32_t* owner, const int32_t* owner_rank, const int32_t* obs_off, const int32_t* obs_kf, const int32_t* ref_kf, const int32_t* ref_level, const float* scale_factors, int n_levels, float* pos_out, float* normal, float* min_dist, float* max_dist, float* Tiw_new, float* center_new);
+/* a finished global BA applied to the map (cslam::GbaMapUpdate, ONE ccm_gba_apply_map call).  Keyframes by id 0 .. n_kf - 1 with origins[n_origins], the child sets in CSR over
+ * child_off[n_kf + 1], kf_cam (-1: no vertex), Tcw / Twc 12 floats each; points with pos, vert (landmark or -1) and ref_kf (keyframe id or -1); the optimised state as
+ * ccm_ba_download returns it.  device < 0 asks for the host evaluator by name (no device is touched); with a device, a device error makes create return NULL.
+ * sizes: out4 = keyframes the walk reached, keyframes reached twice (> 0: nothing evaluated, take the sequential walk), points whose reference keyframe is tagged but unreached
+ * (left untouched), points.  results: any pointer may be NULL; order / parent / T_new / Twc_new per walk position.
+ * ccmh_gba_apply_map_host: the host form of ccm_gba_apply_map after the context through the same header on the calling thread (0, or -1 for its CCM_E_ARG cases). */
+void* ccmh_gbaupd_create(int device, int n_kf, int n_origins, const int32_t* origins, const int32_t* child_off, const int32_t* child_kf, const int32_t* kf_cam, const float* Tcw, const float* Twc, int n_pt, const float* pos, const int32_t* vert, const int32_t* ref_kf, int n_cam, const double* cam_qt, int n_lm, const double* pt_xyz);
+int ccmh_gbaupd_sizes(void* h, int64_t* out4);
+int ccmh_gbaupd_results(void* h, int32_t* order, int32_t* parent, float* T_new, float* Twc_new, float* pos, uint8_t* status);
+void ccmh_gbaupd_destroy(void* h);
+int ccmh_gba_apply_map_host(int n_kf, const int32_t* kf_parent, const int32_t* kf_cam, const float* Tcw_old, const float* Twc_old, int n_pt, const float* pos, const int32_t* pt_vert, const int32_t* pt_ref, int n_cam, const double* cam_qt, int n_lm, const double* pt_xyz, float* T_new, float* Twc_new, float* pos_out, uint8_t* pt_status);
 /* KeyFrame::UpdateConnections over a corrected set (cslam::CovisibilityBatch, ONE ccm_covis_update call; arguments as there).  device < 0 asks for the host evaluator by
  * name (no device is touched); with a device, a device error makes create return NULL.  sizes: out5 = n_kf, entries of the count rows, of the final rows, of the ordered
  * lists, outside AddConnection calls.  results: any pointer may be NULL; outside = target source weight per call, in the reference's order.  best / by_weight:

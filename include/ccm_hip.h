@@ -539,6 +539,36 @@ int  ccm_kfcull_walk(ccm_ctx* ctx, int n_cand, int n_all, const uint8_t* cand_fl
                      double thres, int n_levels, uint8_t* verdict /* n_cand */, int32_t* n_mps /* n_cand */, int32_t* n_red /* n_cand */,
                      uint8_t* pt_gone /* n_pt */, int32_t* pt_nobs_out /* n_pt */, int32_t* n_reeval /* 1 */);
 
+/* ---- a finished global BA applied to the map ---------------------------------------------------------------
+ * What follows optimize() in MapFusionGBA and RunGBA: the recovery of the f64 estimates into f32 (cslam/src/Optimizer.cpp:803-857, Converter.cc:52-74)
+ * and the map walk the reference carries three times (Map.cpp:1441-1568, LoopFinder.cpp ~895-1010, MapMerger.cpp ~640-755), bit-identical to the
+ * reference's f32 / f64 arithmetic under OpenCV 4.2 baseline-build semantics (the lines are ccm_slam_amd/csrc/gba_apply_math.h, which
+ * also compiles for the host).  Stateless except for the optional handle; no graph is touched: SetPose, SetWorldPos, the tags and mbLoopCorrected
+ * stay the caller's.  A pose is 12 floats: rows 0..2 of the 4x4, row-major.
+ * Keyframes: n_kf >= 1 IN THE ORDER THE REFERENCE'S LIST WALK VISITS THEM (breadth first from mvpKeyFrameOrigins, each child behind its parent).
+ * kf_parent[k] = index in that order of the keyframe from whose child set k was reached, -1 for an origin; kf_cam[k] = its camera in the BA problem,
+ * -1 if it was no vertex (mBAGlobalForKF != nLoopKF); Tcw_old / Twc_old = GetPose() / GetPoseInverse() before the walk.  A vertex takes
+ * toCvMat(estimate); any other keyframe takes (Tcw_old[k] * Twc_old[parent]) * T_new[parent], the two 4x4 f32 products in that order.  A vertex under
+ * a parent that was none keeps its own estimate.  An origin that was no vertex has no mTcwGBA and is refused.
+ * Points (n_pt >= 0 non-bad points; 0 is legal with the per-point pointers NULL): pos = GetWorldPos(); pt_vert = the BA landmark, or -1;
+ * pt_ref = the reference keyframe's index in the walk, or -1 when there is none, it was never tagged, or the walk did not reach it.  A landmark is
+ * cast; any other point with pt_ref >= 0 moves as Xc = Rcw_old X + tcw_old, X' = Rwc_new Xc + Ow_new (one gemm each); the others are copied.
+ * The optimised state comes in ONE of two forms that give the same bits:
+ *   host form: cam_qt[7 n_cam] (qx qy qz qw tx ty tz) and pt_xyz[3 n_lm] as ccm_ba_download returns them, ba = NULL;
+ *   handle form: ba = a ccm_ba of THIS context with one rank, cam_qt = pt_xyz = NULL (n_cam / n_lm are the handle's; the arguments are not read).  The
+ *     state is read where it lies on the device; the handle is left as ccm_ba_download leaves it.
+ * Out: T_new[12 n_kf], Twc_new[12 n_kf] = rows 0..2 of [Rwc | Ow] as KeyFrame::SetPose leaves them, pos_out[3 n_pt] (may be pos), pt_status[n_pt]:
+ * 0 untouched, 1 took the optimised value, 2 moved with its reference keyframe.
+ * CCM_E_ARG, with nothing launched: null pointers, n_kf < 1, n_pt < 0, kf_parent[k] >= k or < -1, a camera, landmark or reference index out of range,
+ * an origin that was no vertex, both or neither state form, a handle of another context or with nranks > 1.  NaN / Inf propagate.  One H2D copy, at most
+ * three launches (the keyframes that were no vertices get ONE workgroup, not launched when there is none; the handle form adds the handle's own
+ * landmark reorder, as its download does) and one D2H copy on the context's stream, scratch of the context; threads calling with their own contexts run concurrently. */
+int  ccm_gba_apply_map(ccm_ctx* ctx, int n_kf, const int32_t* kf_parent /* n_kf */, const int32_t* kf_cam /* n_kf */, const float* Tcw_old /* 12 n_kf */,
+                       const float* Twc_old /* 12 n_kf */, int n_pt, const float* pos /* 3 n_pt */, const int32_t* pt_vert /* n_pt */,
+                       const int32_t* pt_ref /* n_pt */, int n_cam, const double* cam_qt /* 7 n_cam or NULL */, int n_lm,
+                       const double* pt_xyz /* 3 n_lm or NULL */, ccm_ba* ba /* or NULL */, float* T_new /* 12 n_kf */, float* Twc_new /* 12 n_kf */,
+                       float* pos_out /* 3 n_pt */, uint8_t* pt_status /* n_pt */);
+
 #ifdef __cplusplus
 }
 #endif
