@@ -94,3 +94,25 @@ struct GbaApplyBlock : StagedBlock {
   StagedSeg<float> T_new = add<float>(12 * K, SB_OUT), Twc_new = add<float>(12 * K, SB_OUT), pos_out = add<float>(3 * P, SB_OUT);
   StagedSeg<uint8_t> status = add<uint8_t>(P, SB_OUT);
 };
+
+// ccm_twoview_ransac_eval: the inputs, the models the solve kernel leaves for the score kernel, the outputs.  words = ceil(N / 32) per hypothesis and model.
+struct TwoViewRansacBlock : StagedBlock {
+  const size_t N, H, words;
+  TwoViewRansacBlock(size_t N, size_t H) : N(N), H(H), words((N + 31) / 32) {}
+  StagedSeg<float> xy1 = add<float>(2 * N, SB_COPY), xy2 = add<float>(2 * N, SB_COPY), pn1 = add<float>(2 * N, SB_COPY), pn2 = add<float>(2 * N, SB_COPY);
+  StagedSeg<float> T = add<float>(27, SB_GEN);   // T1, T2inv, T2t
+  StagedSeg<int32_t> sets = add<int32_t>(8 * H, SB_COPY);
+  StagedSeg<float> H12 = add<float>(9 * H, SB_WORK);
+  StagedSeg<float> scoreH = add<float>(H, SB_OUT), scoreF = add<float>(H, SB_OUT), H21 = add<float>(9 * H, SB_OUT), F21 = add<float>(9 * H, SB_OUT);
+  StagedSeg<uint32_t> maskH = add<uint32_t>(words * H, SB_OUT), maskF = add<uint32_t>(words * H, SB_OUT);
+};
+
+// ccm_twoview_check_rt: the inputs, then the outputs.  Q motion hypotheses of 27 floats each; one inlier mask of ceil(N / 32) words.
+struct TwoViewCheckRtBlock : StagedBlock {
+  const size_t N, Q;
+  TwoViewCheckRtBlock(size_t N, size_t Q) : N(N), Q(Q) {}
+  StagedSeg<float> xy1 = add<float>(2 * N, SB_COPY), xy2 = add<float>(2 * N, SB_COPY), rec = add<float>(27 * Q, SB_COPY), K = add<float>(9, SB_COPY);
+  StagedSeg<uint32_t> inl = add<uint32_t>((N + 31) / 32, SB_COPY);
+  StagedSeg<float> x3d = add<float>(3 * N * Q, SB_OUT), cosp = add<float>(N * Q, SB_OUT);
+  StagedSeg<uint8_t> status = add<uint8_t>(N * Q, SB_OUT);
+};

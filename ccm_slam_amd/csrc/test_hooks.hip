@@ -137,3 +137,38 @@ extern "C" int ccm_debug_lane_xor(ccm_ctx* ctx, const double* in64, double* out_
   CCM_HIP_CHECK(ctx, hipFree(d));
   return CCM_OK;
 }
+
+// tv_score of twoview_math.h on the device for GIVEN models (one lane per model; model 0: homographies, their inverses by tv_inv33 on the device; 1: fundamental
+// matrices): plants a match whose chi2 sits on a threshold float.  tests/test_twoview_gpu.py compares with ccmh_twoview_score_host.
+#include "twoview_math.h"
+namespace {
+__global__ __launch_bounds__(64) void twoview_score_probe(int model, int n_models, const float* M, int N, const float* xy1, const float* xy2, float sigma, float* score,
+                                                          uint32_t* mask) {
+  const int h = blockIdx.x * 64 + threadIdx.x;
+  if (h >= n_models) return;
+  float m[9], inv[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int k = 0; k < 9; k++) m[k] = M[9 * (size_t)h + k];
+  if (model == 0) tv_inv33(m, inv);
+  score[h] = tv_score(model == 0, m, inv, N, xy1, xy2, sigma, mask + (size_t)h * ((N + 31) / 32));
+}
+}  // namespace
+extern "C" int ccm_debug_twoview_score(ccm_ctx* ctx, int model, int n_models, const float* M, int N, const float* xy1, const float* xy2, float sigma, float* score,
+                                       uint32_t* mask) {
+  if (!ctx || model < 0 || model > 1 || n_models < 1 || N < 1 || !M || !xy1 || !xy2 || !score || !mask) return CCM_E_ARG;
+  CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const size_t words = ((size_t)N + 31) / 32, nM = 9 * (size_t)n_models, nxy = 2 * (size_t)N;
+  float* d = nullptr;   // M, xy1, xy2, score, mask
+  CCM_HIP_CHECK(ctx, hipMalloc(&d, (nM + 2 * nxy + n_models + words * n_models) * sizeof(float)));
+  float *d_xy1 = d + nM, *d_xy2 = d_xy1 + nxy, *d_score = d_xy2 + nxy;
+  uint32_t* d_mask = reinterpret_cast<uint32_t*>(d_score + n_models);
+  CCM_HIP_CHECK(ctx, hipMemcpy(d, M, nM * sizeof(float), hipMemcpyHostToDevice));
+  CCM_HIP_CHECK(ctx, hipMemcpy(d_xy1, xy1, nxy * sizeof(float), hipMemcpyHostToDevice));
+  CCM_HIP_CHECK(ctx, hipMemcpy(d_xy2, xy2, nxy * sizeof(float), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(twoview_score_probe, dim3((unsigned)((n_models + 63) / 64)), dim3(64), 0, ctx->stream, model, n_models, d, N, d_xy1, d_xy2, sigma, d_score, d_mask);
+  CCM_HIP_CHECK(ctx, hipGetLastError());
+  CCM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  CCM_HIP_CHECK(ctx, hipMemcpy(score, d_score, n_models * sizeof(float), hipMemcpyDeviceToHost));
+  CCM_HIP_CHECK(ctx, hipMemcpy(mask, d_mask, words * n_models * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  CCM_HIP_CHECK(ctx, hipFree(d));
+  return CCM_OK;
+}

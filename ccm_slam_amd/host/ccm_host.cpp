@@ -3,6 +3,7 @@
 #include "ccm_host.h"
 #include "kfdb_resolve.h"
 #include "../csrc/triangulate_math.h"
+#include "../csrc/twoview_math.h"
 #include "../csrc/sim3_correct_math.h"
 #include "../csrc/gba_apply_math.h"
 #include "../csrc/covis_math.h"
@@ -1000,6 +1001,169 @@ bool Sim3RansacBatch::next(int& cand, float R[9], float t[3], float& s, std::vec
   return true;
 }
 
+// ---- TwoViewInitializer -------------------------------------------------------------------------------
+// twoview_math.h on the calling thread with the arguments of ccm_twoview_ransac_eval; model: 0 both, 1 the homography only, 2 the fundamental matrix only
+static int twoview_ransac_host(int N, const float* xy1, const float* xy2, const float* pn1, const float* pn2, const float* T1, const float* T2inv, const float* T2t,
+                               float sigma, int H, const int32_t* sets, int model, float* scoreH, float* scoreF, float* H21, float* F21, uint32_t* maskH,
+                               uint32_t* maskF) {
+  if (N < 8 || H < 1 || !xy1 || !xy2 || !pn1 || !pn2 || !T1 || !T2inv || !T2t || !sets) return -1;
+  if (model != 2 && (!scoreH || !H21 || !maskH)) return -1;
+  if (model != 1 && (!scoreF || !F21 || !maskF)) return -1;
+  const size_t words = ((size_t)N + 31) / 32;
+  for (int h = 0; h < H; h++) {
+    float p1[16], p2[16];
+    for (int j = 0; j < 8; j++) {
+      const int32_t idx = sets[8 * (size_t)h + j];
+      if (idx < 0 || idx >= N) return -1;
+      for (int k = 0; k < j; k++) if (sets[8 * (size_t)h + k] == idx) return -1;
+      p1[2 * j] = pn1[2 * idx]; p1[2 * j + 1] = pn1[2 * idx + 1]; p2[2 * j] = pn2[2 * idx]; p2[2 * j + 1] = pn2[2 * idx + 1];
+    }
+    if (model != 2) {
+      float H12[9];
+      tv_model_h(p1, p2, T1, T2inv, H21 + 9 * (size_t)h, H12);
+      scoreH[h] = tv_score(true, H21 + 9 * (size_t)h, H12, N, xy1, xy2, sigma, maskH + words * h);
+    }
+    if (model != 1) {
+      tv_model_f(p1, p2, T1, T2t, F21 + 9 * (size_t)h);
+      scoreF[h] = tv_score(false, F21 + 9 * (size_t)h, nullptr, N, xy1, xy2, sigma, maskF + words * h);
+    }
+  }
+  return 0;
+}
+
+static int twoview_check_rt_host(int n_hyp, const float* rec, const float* K, int N, const float* xy1, const float* xy2, const uint32_t* inl, float th2,
+                                 uint8_t* status, float* x3d, float* cosp) {
+  if (n_hyp < 1 || n_hyp > 8 || N < 1 || !rec || !K || !xy1 || !xy2 || !inl || !status || !x3d || !cosp) return -1;
+  for (int q = 0; q < n_hyp; q++) {
+    TvMotion m;
+    std::memcpy(&m, rec + TV_REC_FLOATS * (size_t)q, sizeof m);
+    for (int i = 0; i < N; i++) {
+      const size_t o = (size_t)q * N + i;
+      x3d[3 * o] = x3d[3 * o + 1] = x3d[3 * o + 2] = cosp[o] = NAN;
+      status[o] = TV_NOT_INLIER;
+      if ((inl[i >> 5] >> (i & 31)) & 1u) status[o] = (uint8_t)tv_check_rt(K, m, xy1[2 * i], xy1[2 * i + 1], xy2[2 * i], xy2[2 * i + 1], th2, x3d + 3 * o, cosp[o]);
+    }
+  }
+  return 0;
+}
+
+TwoViewInitializer::TwoViewInitializer(HipContext* ctx, const float K[9], std::vector<float> keys1, float sigma) : ctx_(ctx), sigma_(sigma), keys1_(std::move(keys1)) {
+  if (!K || keys1_.size() % 2) throw infrastructure_ex("TwoViewInitializer: K and x y pairs");
+  std::memcpy(K_, K, sizeof K_);
+}
+
+TwoViewInitializer::Sets TwoViewInitializer::DrawSets(int N, int iterations, const std::function<int()>& rand) {
+  if (N < 8 || iterations < 0) throw infrastructure_ex("TwoViewInitializer::DrawSets: fewer than 8 matches");
+  Sets sets((size_t)iterations * 8, 0);
+  std::vector<int32_t> all((size_t)N), avail;
+  for (int i = 0; i < N; i++) all[i] = i;
+  for (int it = 0; it < iterations; it++) {
+    avail = all;
+    for (int j = 0; j < 8; j++) {
+      const int randi = ccm_sim3::random_int(rand(), (int)avail.size());   // DUtils::Random::RandomInt(0, size - 1)
+      sets[8 * (size_t)it + j] = avail[randi];
+      avail[randi] = avail.back();
+      avail.pop_back();
+    }
+  }
+  return sets;
+}
+
+TwoViewInitializer::Models TwoViewInitializer::FindModels(std::vector<float> keys2, const std::vector<int>& vMatches12, const Sets& sets) {
+  if (keys2.size() % 2 || vMatches12.size() > keys1_.size() / 2 || sets.empty() || sets.size() % 8) throw infrastructure_ex("TwoViewInitializer::FindModels: bad arguments");
+  keys2_ = std::move(keys2);
+  first_.clear(); xy1_.clear(); xy2_.clear();
+  const int N1 = (int)(keys1_.size() / 2), N2 = (int)(keys2_.size() / 2);
+  // Normalize runs over ALL keypoints of each frame; the matched ones are then picked in match order
+  std::vector<float> n1(keys1_.size()), n2(keys2_.size()), pn1, pn2;
+  float T1[9], T2[9], T2inv[9], T2t[9];
+  tv_normalize(keys1_.data(), N1, n1.data(), T1);
+  tv_normalize(keys2_.data(), N2, n2.data(), T2);
+  tv_inv33(T2, T2inv);
+  for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) T2t[3 * r + c] = T2[3 * c + r];
+  for (size_t i = 0; i < vMatches12.size(); i++) {
+    const int j = vMatches12[i];
+    if (j < 0) continue;
+    if (j >= N2) throw infrastructure_ex("TwoViewInitializer::FindModels: match out of range");
+    first_.push_back((int32_t)i);
+    xy1_.insert(xy1_.end(), {keys1_[2 * i], keys1_[2 * i + 1]}); xy2_.insert(xy2_.end(), {keys2_[2 * j], keys2_[2 * j + 1]});
+    pn1.insert(pn1.end(), {n1[2 * i], n1[2 * i + 1]}); pn2.insert(pn2.end(), {n2[2 * j], n2[2 * j + 1]});
+  }
+  const int N = (int)first_.size(), H = (int)(sets.size() / 8);
+  if (N < 8) throw infrastructure_ex("TwoViewInitializer::FindModels: fewer than 8 matches");
+  const size_t words = ((size_t)N + 31) / 32;
+  std::vector<float> sH((size_t)H), sF((size_t)H), H21(9 * (size_t)H), F21(9 * (size_t)H);
+  std::vector<uint32_t> mH(words * H), mF(words * H);
+  if (ctx_) {
+    const int rc = ccm_twoview_ransac_eval(ctx_->get(), N, xy1_.data(), xy2_.data(), pn1.data(), pn2.data(), T1, T2inv, T2t, sigma_, H, sets.data(), sH.data(), sF.data(),
+                                           H21.data(), F21.data(), mH.data(), mF.data());
+    if (rc != CCM_OK) throw infrastructure_ex(std::string("ccm_twoview_ransac_eval: ") + ccm_last_error(ctx_->get()));
+  } else if (twoview_ransac_host(N, xy1_.data(), xy2_.data(), pn1.data(), pn2.data(), T1, T2inv, T2t, sigma_, H, sets.data(), 0, sH.data(), sF.data(), H21.data(),
+                                 F21.data(), mH.data(), mF.data()) != 0) {
+    throw infrastructure_ex("TwoViewInitializer::FindModels: a set index out of range or repeated");
+  }
+  // `if(currentScore>score)` from score = 0, in order: the first strictly greater score wins; a NaN or zero score never does
+  Models m;
+  m.vbMatchesInliersH.assign((size_t)N, false); m.vbMatchesInliersF.assign((size_t)N, false);
+  for (int h = 0; h < H; h++) {
+    if (sH[h] > m.SH) { m.SH = sH[h]; m.bestH = h; }
+    if (sF[h] > m.SF) { m.SF = sF[h]; m.bestF = h; }
+  }
+  if (m.bestH >= 0) {
+    std::memcpy(m.H21, &H21[9 * (size_t)m.bestH], sizeof m.H21);
+    for (int i = 0; i < N; i++) m.vbMatchesInliersH[i] = (mH[words * m.bestH + (i >> 5)] >> (i & 31)) & 1u;
+  }
+  if (m.bestF >= 0) {
+    std::memcpy(m.F21, &F21[9 * (size_t)m.bestF], sizeof m.F21);
+    for (int i = 0; i < N; i++) m.vbMatchesInliersF[i] = (mF[words * m.bestF + (i >> 5)] >> (i & 31)) & 1u;
+  }
+  m.RH = m.SH / (m.SH + m.SF);
+  return m;
+}
+
+std::vector<TwoViewInitializer::Reconstruction> TwoViewInitializer::CheckRTBatch(const std::vector<Motion>& hyp, const std::vector<bool>& inliers, float th2) {
+  const int N = (int)first_.size(), Q = (int)hyp.size();
+  if (N < 1 || Q < 1 || Q > 8 || (int)inliers.size() != N) throw infrastructure_ex("TwoViewInitializer::CheckRTBatch: 1 to 8 hypotheses, one inlier flag per match");
+  std::vector<float> rec((size_t)TV_REC_FLOATS * Q);
+  for (int q = 0; q < Q; q++) {
+    TvMotion m;
+    tv_prepare_rt(K_, hyp[q].R, hyp[q].t, m);
+    std::memcpy(&rec[(size_t)TV_REC_FLOATS * q], &m, sizeof m);
+  }
+  std::vector<uint32_t> mask(((size_t)N + 31) / 32, 0u);
+  for (int i = 0; i < N; i++) if (inliers[i]) mask[i >> 5] |= 1u << (i & 31);
+  std::vector<uint8_t> status((size_t)N * Q);
+  std::vector<float> x3d(3 * (size_t)N * Q), cosp((size_t)N * Q);
+  if (ctx_) {
+    const int rc = ccm_twoview_check_rt(ctx_->get(), Q, rec.data(), K_, N, xy1_.data(), xy2_.data(), mask.data(), th2, status.data(), x3d.data(), cosp.data());
+    if (rc != CCM_OK) throw infrastructure_ex(std::string("ccm_twoview_check_rt: ") + ccm_last_error(ctx_->get()));
+  } else {
+    twoview_check_rt_host(Q, rec.data(), K_, N, xy1_.data(), xy2_.data(), mask.data(), th2, status.data(), x3d.data(), cosp.data());
+  }
+  std::vector<Reconstruction> out((size_t)Q);
+  const size_t N1 = keys1_.size() / 2;
+  for (int q = 0; q < Q; q++) {
+    Reconstruction& r = out[q];
+    r.vP3D.assign(3 * N1, 0.f); r.vbGood.assign(N1, false);
+    r.status.assign(status.begin() + (size_t)q * N, status.begin() + (size_t)(q + 1) * N);
+    std::vector<float> vCosParallax;
+    for (int i = 0; i < N; i++) {
+      const size_t o = (size_t)q * N + i;
+      if (status[o] < TV_COUNTED) continue;
+      vCosParallax.push_back(cosp[o]);
+      for (int k = 0; k < 3; k++) r.vP3D[3 * (size_t)first_[i] + k] = x3d[3 * o + k];
+      r.nGood++;
+      if (status[o] == TV_GOOD) r.vbGood[first_[i]] = true;
+    }
+    if (r.nGood > 0) {
+      std::sort(vCosParallax.begin(), vCosParallax.end());
+      const size_t idx = std::min(50, int(vCosParallax.size() - 1));
+      r.parallax = (float)((double)(acosf(vCosParallax[idx]) * 180) / 3.1415926535897932384626433832795);   // acos(...) * 180 / CV_PI
+    }
+  }
+  return out;
+}
+
 // ---- NewMapPointBatch ---------------------------------------------------------------------------------
 static_assert(sizeof(CamRecord) == sizeof(TriCam) && sizeof(TriCam) == TRI_CAM_FLOATS * sizeof(float), "camera record layout");
 
@@ -1849,6 +2013,94 @@ int ccmh_triangulate_pairs_host(const float* cam1, int S, const float* cam2, con
       n += status[i] == TRI_OK;
     }
     n_accepted[s] = n;
+  }
+  return 0;
+}
+
+// TwoViewInitializer through C, and twoview_math.h compiled for the host
+void* ccmh_twoview_create(int device, const float* K9, int N1, const float* keys1, float sigma) {
+  try {
+    if (!K9 || N1 < 0 || (N1 > 0 && !keys1)) return nullptr;
+    return new cslam::TwoViewInitializer(device < 0 ? nullptr : &thread_context(device), K9, std::vector<float>(keys1, keys1 + 2 * (size_t)N1), sigma);
+  } catch (const std::exception&) { return nullptr; }
+}
+int ccmh_twoview_find(void* h, int N2, const float* keys2, const int32_t* matches12, int n_sets, const int32_t* sets, float* scores3, int32_t* best2, float* H21,
+                      float* F21, uint8_t* inl_h, uint8_t* inl_f) {
+  if (!h || N2 < 0 || (N2 > 0 && !keys2) || !matches12 || n_sets < 1 || !sets || !scores3 || !best2 || !H21 || !F21 || !inl_h || !inl_f) return -1;
+  cslam::TwoViewInitializer& tv = *static_cast<cslam::TwoViewInitializer*>(h);
+  try {
+    // matches12 has one entry per keypoint of frame 1; the mirror knows how many that is from its own keys
+    const cslam::TwoViewInitializer::Models m = tv.FindModels(std::vector<float>(keys2, keys2 + 2 * (size_t)N2), std::vector<int>(matches12, matches12 + tv.keys1()),
+                                                              cslam::TwoViewInitializer::Sets(sets, sets + 8 * (size_t)n_sets));
+    scores3[0] = m.SH; scores3[1] = m.SF; scores3[2] = m.RH;
+    best2[0] = m.bestH; best2[1] = m.bestF;
+    std::memcpy(H21, m.H21, sizeof m.H21); std::memcpy(F21, m.F21, sizeof m.F21);
+    for (int i = 0; i < tv.matches(); i++) { inl_h[i] = m.vbMatchesInliersH[i]; inl_f[i] = m.vbMatchesInliersF[i]; }
+    return tv.matches();
+  } catch (const cslam::infrastructure_ex& e) {
+    return std::strncmp(e.what(), "ccm_", 4) == 0 ? -1000 : -1;
+  } catch (const std::exception&) { return -1000; }
+}
+int ccmh_twoview_check_rt(void* h, int n_hyp, const float* Rt, const uint8_t* inliers, float th2, int32_t* n_good, float* parallax, float* p3d, uint8_t* good,
+                          uint8_t* status) {
+  if (!h || n_hyp < 1 || n_hyp > 8 || !Rt || !inliers || !n_good || !parallax || !p3d || !good || !status) return -1;
+  cslam::TwoViewInitializer& tv = *static_cast<cslam::TwoViewInitializer*>(h);
+  try {
+    std::vector<cslam::TwoViewInitializer::Motion> hyp((size_t)n_hyp);
+    for (int q = 0; q < n_hyp; q++) { std::memcpy(hyp[q].R, Rt + 12 * (size_t)q, 9 * sizeof(float)); std::memcpy(hyp[q].t, Rt + 12 * (size_t)q + 9, 3 * sizeof(float)); }
+    const auto out = tv.CheckRTBatch(hyp, std::vector<bool>(inliers, inliers + tv.matches()), th2);
+    const size_t N1 = (size_t)tv.keys1(), N = (size_t)tv.matches();
+    for (int q = 0; q < n_hyp; q++) {
+      n_good[q] = out[q].nGood; parallax[q] = out[q].parallax;
+      std::memcpy(p3d + 3 * N1 * q, out[q].vP3D.data(), 3 * N1 * sizeof(float));
+      for (size_t i = 0; i < N1; i++) good[N1 * q + i] = out[q].vbGood[i];
+      std::memcpy(status + N * q, out[q].status.data(), N);
+    }
+    return 0;
+  } catch (const cslam::infrastructure_ex& e) {
+    return std::strncmp(e.what(), "ccm_", 4) == 0 ? -1000 : -1;
+  } catch (const std::exception&) { return -1000; }
+}
+void ccmh_twoview_destroy(void* h) { delete static_cast<cslam::TwoViewInitializer*>(h); }
+int ccmh_twoview_draw_sets(int N, int iterations, const int32_t* raw, int32_t* sets) {
+  if (N < 8 || iterations < 0 || (iterations > 0 && (!raw || !sets))) return -1;
+  size_t at = 0;
+  const cslam::TwoViewInitializer::Sets s = cslam::TwoViewInitializer::DrawSets(N, iterations, [&] { return (int)raw[at++]; });
+  std::memcpy(sets, s.data(), s.size() * sizeof(int32_t));
+  return 0;
+}
+int ccmh_twoview_ransac_eval_host(int N, const float* xy1, const float* xy2, const float* pn1, const float* pn2, const float* T1, const float* T2inv, const float* T2t,
+                                  float sigma, int H, const int32_t* sets, int model, float* scoreH, float* scoreF, float* H21, float* F21, uint32_t* maskH,
+                                  uint32_t* maskF) {
+  if (model < 0 || model > 2) return -1;
+  return cslam::twoview_ransac_host(N, xy1, xy2, pn1, pn2, T1, T2inv, T2t, sigma, H, sets, model, scoreH, scoreF, H21, F21, maskH, maskF);
+}
+int ccmh_twoview_check_rt_host(int n_hyp, const float* rec, const float* K9, int N, const float* xy1, const float* xy2, const uint32_t* inlier_mask, float th2,
+                               uint8_t* status, float* x3d, float* cos_parallax) {
+  return cslam::twoview_check_rt_host(n_hyp, rec, K9, N, xy1, xy2, inlier_mask, th2, status, x3d, cos_parallax);
+}
+void ccmh_twoview_normalize(const float* xy, int n, float* pn, float* T9) { tv_normalize(xy, n, pn, T9); }
+void ccmh_twoview_inv33(const float* S9, float* D9) { tv_inv33(S9, D9); }
+void ccmh_twoview_prepare_rt(const float* K9, const float* R9, const float* t3, float* rec27) {
+  TvMotion m;
+  tv_prepare_rt(K9, R9, t3, m);
+  std::memcpy(rec27, &m, sizeof m);
+}
+int ccmh_twoview_svd(int shape, const float* A, float* out) {
+  if (!A || !out) return -1;
+  if (shape == 0) tv_svd16x9_last_row(A, out);
+  else if (shape == 1) { std::memcpy(out, A, 72 * sizeof(float)); tv_svd8x9_vt(out); }
+  else if (shape == 2) tv_svd3x3(A, out, out + 3, out + 12);
+  else return -1;
+  return 0;
+}
+int ccmh_twoview_score_host(int model, int n_models, const float* M, int N, const float* xy1, const float* xy2, float sigma, float* score, uint32_t* mask) {
+  if (model < 0 || model > 1 || n_models < 1 || N < 1 || !M || !xy1 || !xy2 || !score || !mask) return -1;
+  const size_t words = ((size_t)N + 31) / 32;
+  for (int h = 0; h < n_models; h++) {
+    float inv[9] = {0};
+    if (model == 0) tv_inv33(M + 9 * (size_t)h, inv);
+    score[h] = tv_score(model == 0, M + 9 * (size_t)h, inv, N, xy1, xy2, sigma, mask + words * h);
   }
   return 0;
 }

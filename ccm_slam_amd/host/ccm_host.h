@@ -504,6 +504,45 @@ class Sim3RansacBatch {
 };
 
 // ---------------------------------------------------------------------------------------------------
+// Initializer — cslam/include/cslam/Initializer.h: the arithmetic of Initialize() between the set drawing and ReconstructF / ReconstructH
+// (FindHomography / FindFundamental, Initializer.cpp:120-219) and CheckRT (:794-903) for all motion hypotheses of an attempt at once.
+// DecomposeE, the Faugeras decomposition and the accept / reject logic stay with the caller.
+// ---------------------------------------------------------------------------------------------------
+class TwoViewInitializer {
+ public:
+  typedef std::vector<int32_t> Sets;   // mvSets, 8 match indices per iteration
+  struct Models {                      // what FindHomography / FindFundamental return; a model without a winner is all zeros
+    float SH = 0, SF = 0, RH = 0;      // RH = SH / (SH + SF)
+    float H21[9] = {0}, F21[9] = {0};
+    int bestH = -1, bestF = -1;        // the winning iteration, -1: no score above 0
+    std::vector<bool> vbMatchesInliersH, vbMatchesInliersF;
+  };
+  struct Motion { float R[9]; float t[3]; };
+  struct Reconstruction {              // what one CheckRT returns
+    int nGood = 0; float parallax = 0;
+    std::vector<float> vP3D;           // 3 per keypoint of frame 1 (zeros where the reference leaves Point3f())
+    std::vector<bool> vbGood;          // per keypoint of frame 1
+    std::vector<uint8_t> status;       // per match: the first gate (include/ccm_hip.h, ccm_twoview_check_rt)
+  };
+  // ctx == nullptr: every evaluation runs twoview_math.h on the calling thread.  K: 3x3 row-major; keys1: mvKeysUn of the reference frame, x y pairs.
+  TwoViewInitializer(HipContext* ctx, const float K[9], std::vector<float> keys1, float sigma);
+  // the set-drawing loop of Initializer.cpp:73-93 on the caller's rand (DUtils::Random::RandomInt on each value)
+  static Sets DrawSets(int N, int iterations, const std::function<int()>& rand);
+  // keys2: mvKeysUn of the current frame; vMatches12: per keypoint of frame 1 the index in frame 2 or -1.  Throws infrastructure_ex on fewer than 8 matches,
+  // an index out of range or a bad set, and on a device error.
+  Models FindModels(std::vector<float> keys2, const std::vector<int>& vMatches12, const Sets& sets);
+  // CheckRT of every hypothesis (1..8) with the matches of the last FindModels
+  std::vector<Reconstruction> CheckRTBatch(const std::vector<Motion>& hyp, const std::vector<bool>& vbMatchesInliers, float th2);
+  int matches() const { return (int)first_.size(); }
+  int keys1() const { return (int)(keys1_.size() / 2); }
+ private:
+  HipContext* ctx_;
+  float K_[9], sigma_;
+  std::vector<float> keys1_, keys2_, xy1_, xy2_;   // xy: in match order
+  std::vector<int32_t> first_;                     // mvMatches12[i].first
+};
+
+// ---------------------------------------------------------------------------------------------------
 // Optimizer — cslam/include/cslam/Optimizer.h:84-112 (numerics; graph walking is the integrator's glue)
 // ---------------------------------------------------------------------------------------------------
 struct BAProblem {   // owning, f64 like g2o; filled from KeyFrames / MapPoints via Converter (Converter.cc:40-119)

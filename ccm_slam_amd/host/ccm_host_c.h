@@ -103,6 +103,25 @@ void ccmh_sim3_ransac_destroy(void* h);
 int ccmh_sim3_solver_iterate(int device, int N, const float* X3Dc1, const float* X3Dc2, const float* K1, const float* K2, const uint32_t* max_err1, const uint32_t* max_err2, int fix_scale, int min_inliers, int max_iterations, int n_iterations, int32_t* state, float* best_rts, uint32_t* best_mask, int32_t* flags);
 int ccmh_sim3_draws_pending(int32_t* out, int cap);
 void ccmh_sim3_draws_clear(void);
+/* cslam::TwoViewInitializer (the H / F RANSAC and CheckRT of cslam::Initializer).  device < 0: the host evaluator.  keys: x y pairs of mvKeysUn; sets: 8 match
+ * indices per iteration.  find: scores3 = SH SF RH, best2 = the winning iterations (-1: none), inl_h / inl_f one byte per match; returns the number of matches,
+ * -1 bad arguments, -1000 a device error.  check_rt: n_hyp motions of 12 floats (R row-major, t), inliers one byte per match; per hypothesis n_good, parallax,
+ * p3d (3 N1), good (N1), status (matches).  draw_sets: Initializer.cpp:73-93 on raw rand() values (8 * iterations of them). */
+void* ccmh_twoview_create(int device, const float* K9, int N1, const float* keys1, float sigma);
+int ccmh_twoview_find(void* h, int N2, const float* keys2, const int32_t* matches12, int n_sets, const int32_t* sets, float* scores3, int32_t* best2, float* H21, float* F21, uint8_t* inl_h, uint8_t* inl_f);
+int ccmh_twoview_check_rt(void* h, int n_hyp, const float* Rt, const uint8_t* inliers, float th2, int32_t* n_good, float* parallax, float* p3d, uint8_t* good, uint8_t* status);
+void ccmh_twoview_destroy(void* h);
+int ccmh_twoview_draw_sets(int N, int iterations, const int32_t* raw, int32_t* sets);
+/* twoview_math.h compiled for the host: the arguments of ccm_twoview_ransac_eval / ccm_twoview_check_rt without the context (model: 0 both, 1 H only, 2 F only, for
+ * the two-thread baseline of scripts/twoview_profile.py), Normalize, Mat::inv() of a 3x3, the CheckRT record, the three SVD shapes (shape 0: 16x9 -> vt.row(8) in
+ * out[0..9); 1: 8x9 -> vt in out[0..81); 2: 3x3 -> w, u, vt in out[0..21)) and the score of given models (model 0 H with its inverse computed here, 1 F). */
+int ccmh_twoview_ransac_eval_host(int N, const float* xy1, const float* xy2, const float* pn1, const float* pn2, const float* T1, const float* T2inv, const float* T2t, float sigma, int H, const int32_t* sets, int model, float* scoreH, float* scoreF, float* H21, float* F21, uint32_t* maskH, uint32_t* maskF);
+int ccmh_twoview_check_rt_host(int n_hyp, const float* rec, const float* K9, int N, const float* xy1, const float* xy2, const uint32_t* inlier_mask, float th2, uint8_t* status, float* x3d, float* cos_parallax);
+void ccmh_twoview_normalize(const float* xy, int n, float* pn, float* T9);
+void ccmh_twoview_inv33(const float* S9, float* D9);
+void ccmh_twoview_prepare_rt(const float* K9, const float* R9, const float* t3, float* rec27);
+int ccmh_twoview_svd(int shape, const float* A, float* out);
+int ccmh_twoview_score_host(int model, int n_models, const float* M, int N, const float* xy1, const float* xy2, float sigma, float* score, uint32_t* mask);
 void ccmh_to_se3quat(const float* Tcw16, double* qt7);
 void ccmh_se3quat_to_cvmat(const double* qt7, float* Tcw16);
 void ccmh_sim3_to_cvse3(const double* s8, float* Tcw16);

@@ -569,6 +569,32 @@ int  ccm_gba_apply_map(ccm_ctx* ctx, int n_kf, const int32_t* kf_parent /* n_kf 
                        const double* pt_xyz /* 3 n_lm or NULL */, ccm_ba* ba /* or NULL */, float* T_new /* 12 n_kf */, float* Twc_new /* 12 n_kf */,
                        float* pos_out /* 3 n_pt */, uint8_t* pt_status /* n_pt */);
 
+/* ---- two-view initialisation: H / F RANSAC and CheckRT ------------------------------------------
+ * The arithmetic of cslam::Initializer (cslam/src/Initializer.cpp) between the set drawing and ReconstructF / ReconstructH, bit-identical to the reference's
+ * f32 / f64 arithmetic under OpenCV 4.2 baseline-build semantics (the lines are ccm_slam_amd/csrc/twoview_math.h, which also compiles for the
+ * host).  Both calls are stateless: one H2D copy, the launches and one D2H copy on the context's stream, scratch of the context; threads calling with their own
+ * contexts run concurrently.
+ *
+ * ccm_twoview_ransac_eval: FindHomography / FindFundamental (:120-219) for H hypotheses.  N >= 8 matches: xy1 / xy2 = mvKeysUn of both sides in match order
+ * (x y pairs), pn1 / pn2 = the same points as Normalize (:745-791) gives them — Normalize runs over ALL keypoints of a frame, on the host (tv_normalize) —,
+ * T1, T2inv = T2.inv(), T2t = T2.t() (9 floats each, row-major), sigma = mSigma, sets = mvSets: 8 distinct match indices per hypothesis, reference order.
+ * Out: scoreH[H] / scoreF[H] = currentScore of every iteration, H21[9 H] / F21[9 H] = H21i / F21i, maskH / maskF = vbCurrentInliers, one bit per match
+ * (bit i % 32 of word i / 32), ceil(N / 32) words per hypothesis.  The winner is the caller's: the first hypothesis, in order, whose score is strictly greater
+ * than the best so far, starting from 0 (a NaN or zero score never wins).  CCM_E_ARG, with nothing launched: null pointers, N < 8, H < 1, an index outside
+ * [0, N) or repeated within a set. */
+int  ccm_twoview_ransac_eval(ccm_ctx* ctx, int N, const float* xy1 /* 2 N */, const float* xy2, const float* pn1, const float* pn2, const float* T1 /* 9 */,
+                             const float* T2inv, const float* T2t, float sigma, int H, const int32_t* sets /* 8 H */, float* scoreH, float* scoreF,
+                             float* H21, float* F21, uint32_t* maskH, uint32_t* maskF);
+/* ccm_twoview_check_rt: the loop of CheckRT (:826-890) under 1 <= n_hyp <= 8 motion hypotheses at once.  rec = one record of 27 floats per hypothesis:
+ * P2 = K * [R | t] (12, row-major), O2 = -R.t() * t (3), R (9), t (3), as tv_prepare_rt of twoview_math.h computes them on the host.  K = mK (9, row-major),
+ * N >= 1 matches as above, inlier_mask = vbMatchesInliers in the mask layout above, th2 = 4.0 * mSigma2 as a float.
+ * Out, per (hypothesis, match) at [hyp * N + match]: status = 0 not an inlier, 1 a non-finite point, 2 / 3 depth in camera 1 / 2, 4 / 5 reprojection in
+ * image 1 / 2, 6 counted with low parallax (nGood++, vbGood stays false), 7 counted and good; x3d[3] = p3dC1 (NaN for status 0); cos_parallax (NaN for
+ * status 0 and 1).  nGood, the sort of the counted cosines and acos(...) * 180 / CV_PI are the caller's (cslam::TwoViewInitializer::CheckRTBatch).
+ * CCM_E_ARG: null pointers, n_hyp outside [1, 8], N < 1. */
+int  ccm_twoview_check_rt(ccm_ctx* ctx, int n_hyp, const float* rec /* 27 n_hyp */, const float* K /* 9 */, int N, const float* xy1, const float* xy2,
+                          const uint32_t* inlier_mask, float th2, uint8_t* status, float* x3d, float* cos_parallax);
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,6 +67,11 @@ int  ccm_debug_covis_update_small(ccm_ctx* ctx, int n_kf, int n_all, const int32
                                   int32_t* col, int32_t* count, int32_t* fw_off, int32_t* fw_col, int32_t* fw_w, int32_t* ord_off, int32_t* ord_kf,
                                   int32_t* ord_w, int32_t* flags, int32_t* needed);
 
+/* test hook for ccm_twoview_ransac_eval: the score walk of twoview_math.h (CheckHomography for model 0, the inverse computed on the device; CheckFundamental for
+ * model 1) for n_models GIVEN 3x3 models over N matches; score[n_models], mask[n_models * ceil(N / 32)] */
+int  ccm_debug_twoview_score(ccm_ctx* ctx, int model, int n_models, const float* M, int N, const float* xy1, const float* xy2, float sigma, float* score,
+                             uint32_t* mask);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,7 @@ maintainer's box keeps the pin alive here.  Exit code: 0 all equal (or cv2 absen
 Reference call sites (cslam/src/ORBextractor.cpp): resize :1293, FAST :978 / :983, GaussianBlur :1259, fastAtan2 :113 (IC_Angle); Frame.cpp:131-160 undistortPoints;
 Sim3Solver.cpp:266 eigen (4x4 f32 symmetric; hal::Jacobi when OpenCV is built without Eigen) and :276 Rodrigues, compared with the Sim3 RANSAC's restatements;
 Mapping.cpp:383 SVD::compute on the 4x4 f32 matrix of the linear triangulation (cv2.SVDecomp: w and vt), compared with jacobi_svd4 of tests/test_triangulate_cpu.py.
+Initializer.cpp:259,290,294 SVDecomp on 16x9, 8x9 and 3x3 f32 matrices and :157 Mat::inv() of a 3x3 f32, compared with csrc/twoview_math.h compiled for the host.
 """
 from __future__ import annotations
 
@@ -88,6 +89,8 @@ def cv2_vectors(cv2):
     # Mapping.cpp:383 cv::SVD::compute(A, w, u, vt, MODIFY_A | FULL_UV) on the 4x4 f32 matrix of the linear triangulation: w and vt (u is not used by the reference)
     if hasattr(cv2, "SVDecomp"):
         vec.update(svd4_vectors(cv2))
+        # Initializer.cpp:259,290,294 cv::SVDecomp on the 16x9, 8x9 and 3x3 f32 matrices of ComputeH21 / ComputeF21, and :157 Mat::inv() of a 3x3 f32
+        vec.update(twoview_vectors(cv2))
     # LoopFinder.cpp:551 `Tiw * Twc` and KeyFrame.cpp:302 `-Rwc * tcw`: the small-matrix path of cv::gemm on CV_32F poses (csrc/sim3_correct_math.h)
     if hasattr(cv2, "gemm"):
         vec.update(gemm4_vectors(cv2))
@@ -124,6 +127,32 @@ def svd4_vectors(cv2):
     A = svd4_inputs()
     res = [cv2.SVDecomp(m.copy(), flags=cv2.SVD_MODIFY_A | cv2.SVD_FULL_UV) for m in A]
     return {"svd4_in": A, "svd4_w": np.stack([r[0].reshape(4) for r in res]).astype(np.float32), "svd4_vt": np.stack([r[2] for r in res]).astype(np.float32)}
+
+
+def twoview_inputs():
+    """the 16x9 and 8x9 matrices of the two-view scenes' sets (the sweep of tests/test_twoview_cpu.py), degenerate ones (repeated rows, zero rows: the completion
+    path), and 3x3 matrices: random, rank-deficient, zero"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_twoview_cpu import sweep_matrices
+    rng = np.random.default_rng(17)
+    pairs = sweep_matrices()
+    AH = np.stack([p[0] for p in pairs]); AF = np.stack([p[1] for p in pairs])
+    dH = AH[:6].copy(); dH[0, 4:] = dH[0, :12]; dH[1, 2:] = 0; dH[2] = 0; dH[3, :, 6:] = 0
+    dF = AF[:6].copy(); dF[0, 4:] = dF[0, :4]; dF[1, 2:] = 0; dF[2] = 0; dF[3, 5] = dF[3, 1]; dF[4, [2, 6]] = 0
+    A3 = rng.normal(size=(200, 3, 3)).astype(np.float32)
+    A3[0] = 0; A3[1] = np.outer([1, 2, 3], [1, -1, 2]); A3[2] = np.diag([2, 2, 1]); A3[3, 0] = [1, 2, 3]; A3[3, 1:] = 0; A3[4, 2] = A3[4, 0]
+    return np.concatenate([AH, dH]), np.concatenate([AF, dF]), A3
+
+
+def twoview_vectors(cv2):
+    AH, AF, A3 = twoview_inputs()
+    svd = lambda m: cv2.SVDecomp(m.copy(), flags=cv2.SVD_MODIFY_A | cv2.SVD_FULL_UV)
+    inv = np.stack([cv2.invert(m)[1] for m in A3]).astype(np.float32)            # Mat::inv() is cv::invert(DECOMP_LU): all zeros for a singular matrix
+    r3 = [svd(m) for m in A3]
+    return {"tv_svd16x9_in": AH, "tv_svd16x9_vt8": np.stack([svd(m)[2][8] for m in AH]).astype(np.float32),
+            "tv_svd8x9_in": AF, "tv_svd8x9_vt": np.stack([svd(m)[2] for m in AF]).astype(np.float32),
+            "tv_svd3_in": A3, "tv_svd3_w": np.stack([r[0].reshape(3) for r in r3]).astype(np.float32), "tv_svd3_u": np.stack([r[1] for r in r3]).astype(np.float32),
+            "tv_svd3_vt": np.stack([r[2] for r in r3]).astype(np.float32), "tv_inv3": inv}
 
 
 def compare(vec, report=print):
@@ -176,6 +205,14 @@ def compare(vec, report=print):
         A = np.asarray(vec["gemm4_a"], np.float32); B = np.asarray(vec["gemm4_b"], np.float32)
         same("gemm (4x4 f32 poses)", gemm44(A[:, :3].reshape(-1, 12), np.broadcast_to(B[:3].reshape(1, 12), (A.shape[0], 12))).reshape(-1, 3, 4), np.asarray(vec["gemm4_out"])[:, :3])
         same("gemm (-Rwc * tcw)", center_of_pose(A[:, :3].reshape(-1, 12)), np.asarray(vec["gemm4_center"]))
+    if "tv_svd3_in" in vec:  # the two-view initialiser's restatements (csrc/twoview_math.h compiled for the host, through ccm_slam_amd.twoview)
+        from ccm_slam_amd import twoview as tv
+        same("SVDecomp (16x9 f32): vt.row(8)", np.stack([tv.svd(m) for m in np.asarray(vec["tv_svd16x9_in"])]), np.asarray(vec["tv_svd16x9_vt8"]))
+        same("SVDecomp (8x9 f32): vt", np.stack([tv.svd(m) for m in np.asarray(vec["tv_svd8x9_in"])]), np.asarray(vec["tv_svd8x9_vt"]))
+        r3 = [tv.svd(m) for m in np.asarray(vec["tv_svd3_in"])]
+        for k, name in enumerate(("singular values", "u", "vt")):
+            same(f"SVDecomp (3x3 f32): {name}", np.stack([r[k] for r in r3]), np.asarray(vec["tv_svd3_" + ("w", "u", "vt")[k]]))
+        same("Mat::inv() (3x3 f32)", np.stack([tv.inv33(m) for m in np.asarray(vec["tv_svd3_in"])]), np.asarray(vec["tv_inv3"]))
     return bad
 
 

@@ -1,0 +1,17 @@
+"""TwoViewRansacBlock and TwoViewCheckRtBlock, the staged device blocks of ccm_twoview_ransac_eval and ccm_twoview_check_rt (csrc/stage_blocks.h; DESIGN.md §16,
+§18), on the CPU: tests/host/twoview_block_check.cpp declares them at the sizes of the GPU tests, checks every offset and both copied ranges, and fills every
+segment to its declared length inside a malloc'd block of exactly the computed size.  Built with the address and undefined-behaviour sanitizers as a stand-alone
+program and run as a child process, so an overrun of the host block ends the program."""
+import os
+import subprocess
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+
+
+def test_twoview_block_layouts_under_the_sanitizers(tmp_path):
+    exe = tmp_path / "twoview_block_check"
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Werror", "-I",
+                    os.path.join(ROOT, "ccm_slam_amd", "csrc"), "-o", str(exe), os.path.join(HERE, "host", "twoview_block_check.cpp")], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.strip().endswith("twoview blocks ok") and not r.stderr, (r.stdout[-2000:], r.stderr[-2000:])
