@@ -50,7 +50,7 @@ struct ccm_ctx {
 };
 
 int ccm_set_error(ccm_ctx* ctx, int code, const std::string& msg);
-// development prints / device phase clocks: CCM_DBG = comma-separated list of topics (pers, trial, coarse, dense2, cholreg, setup, row, orb, pg, poseopt) or "all"; read once
+// development prints / device phase clocks: CCM_DBG = comma-separated list of topics (pers, trial, coarse, dense2, cholreg, setup, row, orb, pg, poseopt, fuse) or "all"; read once
 bool ccm_dbg(const char* topic);
 
 // Bracket around the launch of a kernel that needs ALL its workgroups co-resident on the device (ba_pcg_persist: up to one workgroup per CU, grid-wide

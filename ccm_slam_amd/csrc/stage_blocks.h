@@ -3,6 +3,7 @@
 #pragma once
 #include "staged_block.h"
 #include "triangulate_math.h"
+#include "fuse_sim3_math.h"
 
 // ccm_sim3_ransac_eval: the inputs, then the outputs.
 struct Sim3RansacBlock : StagedBlock {
@@ -115,4 +116,23 @@ struct TwoViewCheckRtBlock : StagedBlock {
   StagedSeg<uint32_t> inl = add<uint32_t>((N + 31) / 32, SB_COPY);
   StagedSeg<float> x3d = add<float>(3 * N * Q, SB_OUT), cosp = add<float>(N * Q, SB_OUT);
   StagedSeg<uint8_t> status = add<uint8_t>(N * Q, SB_OUT);
+};
+
+// ccm_fuse_sim3_eval: K keyframes with F features in all, P points, L levels.  The keyframes' inputs, the call's, the points', then the outputs: the two counters go up
+// as zeros (the kernel adds to them) and lead the download, the table follows, uv is declared with no elements when the caller does not ask for it.  The descriptors
+// lie on 16 bytes for the kernel's 16-byte loads.  pose and cell_idx (16-bit) are written by the stage while it validates.
+struct FuseSim3Block : StagedBlock {
+  const size_t K, F, P, L; const bool want_uv;
+  FuseSim3Block(size_t K, size_t F, size_t P, size_t L, bool want_uv) : K(K), F(F), P(P), L(L), want_uv(want_uv) {}
+  StagedSeg<uint8_t> kdesc = add<uint8_t>(32 * F, SB_COPY, 16), pdesc = add<uint8_t>(32 * P, SB_COPY, 16);
+  StagedSeg<float> rec = add<float>(FSM_REC_FLOATS * K, SB_COPY), pose = add<float>(FSM_POSE_FLOATS * K, SB_GEN);
+  StagedSeg<int32_t> feat_off = add<int32_t>(K + 1, SB_COPY), cell_off = add<int32_t>(K * (FSM_CELLS + 1), SB_COPY);
+  StagedSeg<float> kxy = add<float>(2 * F, SB_COPY);
+  StagedSeg<uint16_t> cell_idx = add<uint16_t>(F, SB_GEN);
+  StagedSeg<uint8_t> koct = add<uint8_t>(F, SB_COPY);
+  StagedSeg<float> scale_factors = add<float>(L, SB_COPY);
+  StagedSeg<float> pos = add<float>(3 * P, SB_COPY), normal = add<float>(3 * P, SB_COPY), dmin = add<float>(P, SB_COPY), dmax = add<float>(P, SB_COPY);
+  StagedSeg<int32_t> n_valid = add<int32_t>(K, SB_OUT | SB_ZERO), n_hit = add<int32_t>(K, SB_OUT | SB_ZERO);
+  StagedSeg<uint32_t> table = add<uint32_t>(K * P, SB_OUT);
+  StagedSeg<float> uv = add<float>(want_uv ? 2 * K * P : 0, SB_OUT);
 };

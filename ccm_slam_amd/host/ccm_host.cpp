@@ -8,6 +8,7 @@
 #include "../csrc/gba_apply_math.h"
 #include "../csrc/covis_math.h"
 #include "../csrc/kfcull_math.h"
+#include "../csrc/fuse_sim3_math.h"
 #include <climits>
 #include <algorithm>
 #include <cmath>
@@ -1737,6 +1738,107 @@ std::vector<int32_t> KeyFrameCullingBatch::pointsGone() const {
   return v;
 }
 
+// ---- SearchAndFuseBatch -------------------------------------------------------------------------------
+// one (keyframe, point) pair through csrc/fuse_sim3_math.h; all keyframe arrays are that keyframe's own
+static uint32_t fsm_pair_host(const float* rec, const float* pose, const int32_t* cell_off, const uint16_t* cell_idx, const float* kxy, const uint8_t* koct,
+                              const uint8_t* kdesc, const float* P3, const float* Pn, float dmin, float dmax, const uint8_t* pdesc, int nlevels, float logsf, float th,
+                              const float* sf, float* uv, int32_t* n_cand) {
+  float u, v; int level;
+  const int st = fsm_gate(rec, pose, P3, Pn, dmin, dmax, nlevels, logsf, u, v, level);
+  if (uv) { uv[0] = u; uv[1] = v; }
+  if (n_cand) *n_cand = 0;
+  if (st != FSM_EMPTY) return fsm_pack(st, 0, FSM_NO_DIST, FSM_NO_IDX);
+  uint32_t q[8];
+  fsm_load_desc(pdesc, q);
+  int n = 0;
+  const uint32_t w = fsm_window_best(rec, cell_off, cell_idx, kxy, koct, kdesc, u, v, level, th, sf, q, &n);
+  if (n_cand) *n_cand = n;
+  return w;
+}
+
+int fuse_sim3_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
+                        const int32_t* cell_off, const int32_t* cell_idx, const float* Scw, int nlevels, const float* scale_factors, float logScaleFactor, float th, int P,
+                        const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc, uint32_t* table, int32_t* n_valid,
+                        int32_t* n_hit, float* uv, int32_t* n_cand) {
+  if (fsm_check_args(K, P, feat_off, cell_off, cell_idx, nlevels, th)) return -1;
+  const size_t F = K ? (size_t)feat_off[K] : 0;
+  if (!scale_factors || (K > 0 && (!kf_rec || !Scw || !n_valid || !n_hit)) || (P > 0 && (!pos || !normal || !min_dist || !max_dist || !pt_desc)) ||
+      (K > 0 && P > 0 && !table) || (F && (!feat_xy || !feat_octave || !feat_desc)))
+    return -1;
+  std::vector<uint16_t> idx16(F);
+  for (size_t j = 0; j < F; j++) idx16[j] = (uint16_t)cell_idx[j];
+  for (int k = 0; k < K; k++) {
+    n_valid[k] = n_hit[k] = 0;
+    if (P == 0) continue;
+    float pose[FSM_POSE_FLOATS];
+    fsm_decompose_scw(Scw + 12 * (size_t)k, pose);
+    const int32_t f0 = feat_off[k];
+    for (int i = 0; i < P; i++) {
+      const size_t e = (size_t)k * P + i;
+      const uint32_t w = fsm_pair_host(kf_rec + FSM_REC_FLOATS * (size_t)k, pose, cell_off + (size_t)k * (FSM_CELLS + 1), idx16.data() + f0, feat_xy + 2 * (size_t)f0,
+                                       feat_octave + f0, feat_desc + 32 * (size_t)f0, pos + 3 * (size_t)i, normal + 3 * (size_t)i, min_dist[i], max_dist[i],
+                                       pt_desc + 32 * (size_t)i, nlevels, logScaleFactor, th, scale_factors, uv ? uv + 2 * e : nullptr, n_cand ? n_cand + e : nullptr);
+      table[e] = w;
+      n_valid[k] += (w >> 29) >= FSM_EMPTY;
+      n_hit[k] += (w >> 29) == FSM_HIT;
+    }
+  }
+  return 0;
+}
+
+SearchAndFuseBatch::SearchAndFuseBatch(HipContext* ctx, const KeyFrames& kfs, const Points& pts, int nlevels, const float* scale_factors, float logScaleFactor, float th)
+    : K_(kfs.K), P_(pts.P), nlevels_(nlevels), logsf_(logScaleFactor), th_(th) {
+  const int K = K_, P = P_;
+  if (K < 0 || P < 0 || !scale_factors || nlevels < 1 || nlevels > FSM_MAX_LEVELS) throw infrastructure_ex("SearchAndFuseBatch: bad arguments");
+  table_.assign((size_t)K * (size_t)P, 0); n_valid_.assign((size_t)K, 0); n_hit_.assign((size_t)K, 0);
+  if (ctx) {
+    check(ccm_fuse_sim3_eval(ctx->get(), K, kfs.rec, kfs.feat_off, kfs.feat_xy, kfs.feat_octave, kfs.feat_desc, kfs.cell_off, kfs.cell_idx, kfs.Scw, nlevels, scale_factors,
+                             logScaleFactor, th, P, pts.pos, pts.normal, pts.min_dist, pts.max_dist, pts.desc, table_.data(), n_valid_.data(), n_hit_.data(), nullptr),
+          ctx->get(), "ccm_fuse_sim3_eval");
+  } else if (fuse_sim3_eval_host(K, kfs.rec, kfs.feat_off, kfs.feat_xy, kfs.feat_octave, kfs.feat_desc, kfs.cell_off, kfs.cell_idx, kfs.Scw, nlevels, scale_factors,
+                                 logScaleFactor, th, P, pts.pos, pts.normal, pts.min_dist, pts.max_dist, pts.desc, table_.data(), n_valid_.data(), n_hit_.data(), nullptr,
+                                 nullptr)) {
+    throw infrastructure_ex("SearchAndFuseBatch: bad arguments");
+  }
+  // the arguments are valid from here on: what resolve may have to evaluate again
+  sf_.assign(scale_factors, scale_factors + nlevels);
+  if (K == 0 || P == 0) return;
+  const size_t F = (size_t)kfs.feat_off[K];
+  rec_.assign(kfs.rec, kfs.rec + FSM_REC_FLOATS * (size_t)K);
+  pose_.resize(FSM_POSE_FLOATS * (size_t)K);
+  for (int k = 0; k < K; k++) fsm_decompose_scw(kfs.Scw + 12 * (size_t)k, pose_.data() + FSM_POSE_FLOATS * (size_t)k);
+  feat_off_.assign(kfs.feat_off, kfs.feat_off + K + 1);
+  cell_off_.assign(kfs.cell_off, kfs.cell_off + (size_t)K * (FSM_CELLS + 1));
+  cell_idx_.resize(F);
+  for (size_t j = 0; j < F; j++) cell_idx_[j] = (uint16_t)kfs.cell_idx[j];
+  if (F) { kxy_.assign(kfs.feat_xy, kfs.feat_xy + 2 * F); koct_.assign(kfs.feat_octave, kfs.feat_octave + F); kdesc_.assign(kfs.feat_desc, kfs.feat_desc + 32 * F); }
+  pos_.assign(pts.pos, pts.pos + 3 * (size_t)P); normal_.assign(pts.normal, pts.normal + 3 * (size_t)P);
+  dmin_.assign(pts.min_dist, pts.min_dist + P); dmax_.assign(pts.max_dist, pts.max_dist + P);
+  pdesc_.assign(pts.desc, pts.desc + 32 * (size_t)P);
+}
+
+int SearchAndFuseBatch::resolve(int k, const uint8_t* skip_now, const uint8_t* desc_now, std::vector<int32_t>& bestIdx, std::vector<int32_t>& bestDist) {
+  if (k < 0 || k >= K_) throw infrastructure_ex("SearchAndFuseBatch::resolve: keyframe out of range");
+  bestIdx.assign((size_t)P_, -1); bestDist.assign((size_t)P_, INT_MAX);
+  int nFused = 0;
+  for (int i = 0; i < P_; i++) {
+    if (skip_now && skip_now[i]) continue;
+    uint32_t w = table_[(size_t)k * P_ + i];
+    if ((w >> 29) < FSM_EMPTY) continue;                       // the gates read nothing a Fuse call changes
+    if (desc_now && std::memcmp(desc_now + 32 * (size_t)i, pdesc_.data() + 32 * (size_t)i, 32) != 0) {
+      const int32_t f0 = feat_off_[k];
+      w = fsm_pair_host(rec_.data() + FSM_REC_FLOATS * (size_t)k, pose_.data() + FSM_POSE_FLOATS * (size_t)k, cell_off_.data() + (size_t)k * (FSM_CELLS + 1),
+                        cell_idx_.data() + f0, kxy_.data() + 2 * (size_t)f0, koct_.data() + f0, kdesc_.data() + 32 * (size_t)f0, pos_.data() + 3 * (size_t)i,
+                        normal_.data() + 3 * (size_t)i, dmin_[i], dmax_[i], desc_now + 32 * (size_t)i, nlevels_, logsf_, th_, sf_.data(), nullptr, nullptr);
+      n_reeval_++;
+    }
+    const int st = (int)(w >> 29);
+    if (st >= FSM_FAR) bestDist[i] = (int32_t)((w >> 16) & 0x1FFu);
+    if (st == FSM_HIT) { bestIdx[i] = (int32_t)(w & 0xFFFFu); nFused++; }
+  }
+  return nFused;
+}
+
 }  // namespace cslam
 
 // ---- C entry points (ccm_host_c.h): the Python test-suite and the drop-in translation units under shim/ ---------------------------------------
@@ -2298,6 +2400,48 @@ int ccmh_kfcull_walk_mapcopy_model(int n_cand, int n_all, const uint8_t* cand_fl
   return cslam::kfcull_walk_mapcopy_model(n_cand, n_all, cand_flags, list_off, list_pt, list_level, n_pt, pt_nobs, pt_bad, obs_off, obs_kf, obs_level, obs_bad, th_obs,
                                           thres, n_levels, verdict);
 }
+
+// SearchAndFuseBatch through C, and fuse_sim3_math.h compiled for the host
+void* ccmh_fuse_sim3_create(int device, int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
+                            const int32_t* cell_off, const int32_t* cell_idx, const float* Scw, int nlevels, const float* scale_factors, float logScaleFactor, float th,
+                            int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc) {
+  try {
+    cslam::SearchAndFuseBatch::KeyFrames kf;
+    kf.K = K; kf.rec = kf_rec; kf.feat_off = feat_off; kf.feat_xy = feat_xy; kf.feat_octave = feat_octave; kf.feat_desc = feat_desc; kf.cell_off = cell_off;
+    kf.cell_idx = cell_idx; kf.Scw = Scw;
+    cslam::SearchAndFuseBatch::Points pt;
+    pt.P = P; pt.pos = pos; pt.normal = normal; pt.min_dist = min_dist; pt.max_dist = max_dist; pt.desc = pt_desc;
+    return new cslam::SearchAndFuseBatch(device < 0 ? nullptr : &thread_context(device), kf, pt, nlevels, scale_factors, logScaleFactor, th);
+  } catch (const std::exception&) { return nullptr; }
+}
+int ccmh_fuse_sim3_table(void* h, uint32_t* table, int32_t* n_valid, int32_t* n_hit) {
+  if (!h) return -1;
+  const cslam::SearchAndFuseBatch& b = *static_cast<cslam::SearchAndFuseBatch*>(h);
+  if (table && !b.table().empty()) std::memcpy(table, b.table().data(), b.table().size() * 4);
+  if (n_valid && b.keyframes()) std::memcpy(n_valid, b.nValid().data(), (size_t)b.keyframes() * 4);
+  if (n_hit && b.keyframes()) std::memcpy(n_hit, b.nHit().data(), (size_t)b.keyframes() * 4);
+  return 0;
+}
+int ccmh_fuse_sim3_resolve(void* h, int k, const uint8_t* skip_now, const uint8_t* desc_now, int n_pts, int32_t* best_idx, int32_t* best_dist) {
+  if (!h) return -1000;
+  try {
+    std::vector<int32_t> bi, bd;
+    const int n = static_cast<cslam::SearchAndFuseBatch*>(h)->resolve(k, skip_now, desc_now, bi, bd);
+    if ((int)bi.size() != n_pts) return -1001;
+    if (n_pts) { std::memcpy(best_idx, bi.data(), bi.size() * 4); std::memcpy(best_dist, bd.data(), bd.size() * 4); }
+    return n;
+  } catch (const std::exception&) { return -1000; }
+}
+long long ccmh_fuse_sim3_n_reeval(void* h) { return h ? static_cast<cslam::SearchAndFuseBatch*>(h)->n_reeval() : -1; }
+void ccmh_fuse_sim3_destroy(void* h) { delete static_cast<cslam::SearchAndFuseBatch*>(h); }
+int ccmh_fuse_sim3_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
+                             const int32_t* cell_off, const int32_t* cell_idx, const float* Scw, int nlevels, const float* scale_factors, float logScaleFactor, float th,
+                             int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc, uint32_t* table,
+                             int32_t* n_valid, int32_t* n_hit, float* uv, int32_t* n_cand) {
+  return cslam::fuse_sim3_eval_host(K, kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off, cell_idx, Scw, nlevels, scale_factors, logScaleFactor, th, P, pos, normal,
+                                    min_dist, max_dist, pt_desc, table, n_valid, n_hit, uv, n_cand);
+}
+void ccmh_fuse_sim3_decompose(const float* Scw12, float* pose15) { fsm_decompose_scw(Scw12, pose15); }
 
 int ccmh_search_for_initialization(int device, const float* x1, const float* y1, const int32_t* oct1, const float* a1, const uint8_t* d1, int N1,
                                    const float* x2, const float* y2, const int32_t* oct2, const float* a2, const uint8_t* d2, int N2,

@@ -543,6 +543,49 @@ class TwoViewInitializer {
 };
 
 // ---------------------------------------------------------------------------------------------------
+// SearchAndFuse — LoopFinder.cpp:709-734, MapMerger.cpp:574-598: matcher.Fuse(pKF, Scw, vpLoopMapPoints, 4, vpReplacePoints) for every keyframe of CorrectedSim3,
+// each followed by the Replace loop.  The constructor evaluates every (keyframe, point) pair in ONE ccm_fuse_sim3_eval call (arguments as there) and
+// copies what resolve needs; resolve(k, ...) then returns what the k-th Fuse call returns, whatever the calls before it did to the map: a table entry depends on the
+// keyframe's static data, Scw_k and the point's position, normal, distance bounds and descriptor, and of these Replace / AddObservation change the descriptor
+// alone, so a point whose current descriptor differs from the snapshot is evaluated again on the calling thread (fuse_sim3_math.h) and every other answer is read.
+// ctx == nullptr asks for the host evaluator by name (csrc/fuse_sim3_math.h compiled by g++); with a context, a device error throws — there is no fall-back.
+// GetMapPoint(bestIdx), vpReplacePoint, AddObservation / AddMapPoint and the Replace loop stay the caller's.
+// ---------------------------------------------------------------------------------------------------
+class SearchAndFuseBatch {
+ public:
+  struct KeyFrames {   // K keyframes, flat (include/ccm_hip.h, ccm_fuse_sim3_eval)
+    int K = 0; const float* rec = nullptr; const int32_t* feat_off = nullptr; const float* feat_xy = nullptr; const uint8_t* feat_octave = nullptr;
+    const uint8_t* feat_desc = nullptr; const int32_t* cell_off = nullptr; const int32_t* cell_idx = nullptr; const float* Scw = nullptr;
+  };
+  struct Points { int P = 0; const float* pos = nullptr; const float* normal = nullptr; const float* min_dist = nullptr; const float* max_dist = nullptr;
+                  const uint8_t* desc = nullptr; };
+  SearchAndFuseBatch(HipContext* ctx, const KeyFrames& kfs, const Points& pts, int nlevels, const float* scale_factors, float logScaleFactor, float th);
+  // The k-th Fuse call.  skip_now[i] != 0: the reference would `continue` now (pMP->isBad() || spAlreadyFound.count(pMP)); desc_now (nullable): the points' CURRENT
+  // descriptors.  bestIdx[i] = the feature point i is fused with (-1: none), bestDist[i] its distance; returns nFused.
+  int resolve(int k, const uint8_t* skip_now, const uint8_t* desc_now, std::vector<int32_t>& bestIdx, std::vector<int32_t>& bestDist);
+  int keyframes() const { return K_; }
+  int points() const { return P_; }
+  const std::vector<uint32_t>& table() const { return table_; }   // k-major, as evaluated at construction
+  const std::vector<int32_t>& nValid() const { return n_valid_; }
+  const std::vector<int32_t>& nHit() const { return n_hit_; }
+  long long n_reeval() const { return n_reeval_; }                 // pairs evaluated again by resolve because the descriptor had changed
+ private:
+  int K_ = 0, P_ = 0, nlevels_ = 0; float logsf_ = 0, th_ = 0;
+  std::vector<float> rec_, pose_, kxy_, sf_, pos_, normal_, dmin_, dmax_;
+  std::vector<int32_t> feat_off_, cell_off_, n_valid_, n_hit_;
+  std::vector<uint16_t> cell_idx_;
+  std::vector<uint8_t> koct_, kdesc_, pdesc_;
+  std::vector<uint32_t> table_;
+  long long n_reeval_ = 0;
+};
+// ccm_fuse_sim3_eval's arguments after the context through csrc/fuse_sim3_math.h on the calling thread; -1 where the device entry returns CCM_E_ARG.
+// n_cand (nullable, K P): the size of vIndices of every pair that reached the window (0 otherwise), for scripts/fuse_sim3_profile.py.
+int fuse_sim3_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
+                        const int32_t* cell_off, const int32_t* cell_idx, const float* Scw, int nlevels, const float* scale_factors, float logScaleFactor, float th, int P,
+                        const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc, uint32_t* table, int32_t* n_valid,
+                        int32_t* n_hit, float* uv, int32_t* n_cand);
+
+// ---------------------------------------------------------------------------------------------------
 // Optimizer — cslam/include/cslam/Optimizer.h:84-112 (numerics; graph walking is the integrator's glue)
 // ---------------------------------------------------------------------------------------------------
 struct BAProblem {   // owning, f64 like g2o; filled from KeyFrames / MapPoints via Converter (Converter.cc:40-119)

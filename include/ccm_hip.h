@@ -595,6 +595,30 @@ int  ccm_twoview_ransac_eval(ccm_ctx* ctx, int N, const float* xy1 /* 2 N */, co
 int  ccm_twoview_check_rt(ccm_ctx* ctx, int n_hyp, const float* rec /* 27 n_hyp */, const float* K /* 9 */, int N, const float* xy1, const float* xy2,
                           const uint32_t* inlier_mask, float th2, uint8_t* status, float* x3d, float* cos_parallax);
 
+/* ---- SearchAndFuse: every Fuse(pKF, Scw, vpLoopMapPoints, th, vpReplacePoints) of a loop closure or a map merge -------------------
+ * LoopFinder::SearchAndFuse (cslam/src/LoopFinder.cpp:709-734) and MapMerger::SearchAndFuse (MapMerger.cpp:574-598) call ORBmatcher::Fuse (ORBmatcher.cpp:995-1122)
+ * once per keyframe of CorrectedSim3 with the same points.  This call evaluates the loop body of every (keyframe, point) pair up to its decision, bit-identical to the
+ * reference's f32 / f64 arithmetic under OpenCV 4.2 baseline-build semantics (the lines are ccm_slam_amd/csrc/fuse_sim3_math.h, which also compiles
+ * for the host).  Stateless; the skips (isBad(), spAlreadyFound) and the map mutations stay the caller's (cslam::SearchAndFuseBatch replays them).
+ * Per keyframe k < K: kf_rec = fx fy cx cy, mnMinX mnMinY mnMaxX mnMaxY (the keyframe's int-truncated bounds as floats), mfGridElementWidthInv, mfGridElementHeightInv;
+ * its features feat_off[k] .. feat_off[k + 1] (at most 65 535): feat_xy = mvKeysUn[i].pt, feat_octave, feat_desc (32 bytes each); its mGrid as a CSR of 75 x 48 cells
+ * in x-major order (cell ix * 48 + iy): cell_off + k * 3601 holds 3601 offsets from 0 to the feature count, cell_idx + feat_off[k] the keyframe's feature indices
+ * (0-based in the keyframe) in the order the cells' vectors hold them; Scw + 12 k = rows 0 .. 2 of the cv::Mat passed to Fuse.
+ * Per call: nlevels in 1 .. 16, scale_factors[nlevels] = mvScaleFactors, logScaleFactor = mfLogScaleFactor, th (finite, > 0).
+ * Per point i < P: pos, normal, mfMinDistance, mfMaxDistance and the 32 descriptor bytes.
+ * Out: table[k * P + i] = feature index (bits 0-15, 0xFFFF none) | bestDist << 16 (9 bits, 511 none) | nPredictedLevel << 25 (4 bits, from status 4 on) | status << 29:
+ * 0 behind the camera, 1 outside the image, 2 distance range, 3 viewing angle, 4 window empty, 5 no candidate at the level, 6 bestDist > TH_LOW = 50 (index and distance
+ * reported), 7 a hit.  n_valid[k] / n_hit[k]: pairs with status >= 4 / == 7.  uv (nullable, 2 K P): u, v of the pair (0 for status 0).
+ * K == 0 or P == 0 is legal and launches nothing.  CCM_E_ARG, with nothing launched: null pointers, more than 65 535 features in a keyframe, K * P > INT32_MAX, offsets
+ * that do not start at 0 or decrease, a cell_off that does not end at the keyframe's feature count, a cell_idx outside the keyframe, nlevels outside 1 .. 16, th not
+ * finite and positive.  NaN / Inf in the floats are no errors.  One H2D copy, one launch and one D2H copy on the context's stream, scratch of the context; threads
+ * calling with their own contexts run concurrently. */
+int  ccm_fuse_sim3_eval(ccm_ctx* ctx, int K, const float* kf_rec /* 10 K */, const int32_t* feat_off /* K + 1 */, const float* feat_xy, const uint8_t* feat_octave,
+                        const uint8_t* feat_desc, const int32_t* cell_off /* 3601 K */, const int32_t* cell_idx, const float* Scw /* 12 K */, int nlevels,
+                        const float* scale_factors, float logScaleFactor, float th, int P, const float* pos /* 3 P */, const float* normal /* 3 P */,
+                        const float* min_dist, const float* max_dist, const uint8_t* pt_desc /* 32 P */, uint32_t* table /* K P */, int32_t* n_valid /* K */,
+                        int32_t* n_hit /* K */, float* uv /* 2 K P or NULL */);
+
 #ifdef __cplusplus
 }
 #endif
