@@ -4,6 +4,7 @@
 #include "staged_block.h"
 #include "triangulate_math.h"
 #include "fuse_sim3_math.h"
+#include "fuse_pose_math.h"
 
 // ccm_sim3_ransac_eval: the inputs, then the outputs.
 struct Sim3RansacBlock : StagedBlock {
@@ -135,4 +136,24 @@ struct FuseSim3Block : StagedBlock {
   StagedSeg<int32_t> n_valid = add<int32_t>(K, SB_OUT | SB_ZERO), n_hit = add<int32_t>(K, SB_OUT | SB_ZERO);
   StagedSeg<uint32_t> table = add<uint32_t>(K * P, SB_OUT);
   StagedSeg<float> uv = add<float>(want_uv ? 2 * K * P : 0, SB_OUT);
+};
+
+// ccm_fuse_pose_eval: K keyframes with F features in all, P points, L levels, J jobs in T tiles of FPM_TILE pairs, N = the sum of the jobs' points.  The keyframes'
+// inputs as in FuseSim3Block, but pose is the caller's (Rcw, tcw, Ow) and inv_sigma2 joins scale_factors.  job (keyframe, first point, points, first table word per
+// job) and tile (job, first pair of the job per workgroup) are written by the stage while it validates the job arrays.  The counters are per job.
+struct FusePoseBlock : StagedBlock {
+  const size_t K, F, P, L, J, T, N; const bool want_uv;
+  FusePoseBlock(size_t K, size_t F, size_t P, size_t L, size_t J, size_t T, size_t N, bool want_uv) : K(K), F(F), P(P), L(L), J(J), T(T), N(N), want_uv(want_uv) {}
+  StagedSeg<uint8_t> kdesc = add<uint8_t>(32 * F, SB_COPY, 16), pdesc = add<uint8_t>(32 * P, SB_COPY, 16);
+  StagedSeg<int32_t> job = add<int32_t>(FPM_JOB_INTS * J, SB_GEN, 16), tile = add<int32_t>(2 * T, SB_GEN);
+  StagedSeg<float> rec = add<float>(FSM_REC_FLOATS * K, SB_COPY), pose = add<float>(FSM_POSE_FLOATS * K, SB_COPY);
+  StagedSeg<int32_t> feat_off = add<int32_t>(K + 1, SB_COPY), cell_off = add<int32_t>(K * (FSM_CELLS + 1), SB_COPY);
+  StagedSeg<float> kxy = add<float>(2 * F, SB_COPY);
+  StagedSeg<uint16_t> cell_idx = add<uint16_t>(F, SB_GEN);
+  StagedSeg<uint8_t> koct = add<uint8_t>(F, SB_COPY);
+  StagedSeg<float> scale_factors = add<float>(L, SB_COPY), inv_sigma2 = add<float>(L, SB_COPY);
+  StagedSeg<float> pos = add<float>(3 * P, SB_COPY), normal = add<float>(3 * P, SB_COPY), dmin = add<float>(P, SB_COPY), dmax = add<float>(P, SB_COPY);
+  StagedSeg<int32_t> n_valid = add<int32_t>(J, SB_OUT | SB_ZERO), n_hit = add<int32_t>(J, SB_OUT | SB_ZERO);
+  StagedSeg<uint32_t> table = add<uint32_t>(N, SB_OUT);
+  StagedSeg<float> uv = add<float>(want_uv ? 2 * N : 0, SB_OUT);
 };

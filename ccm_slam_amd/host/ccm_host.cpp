@@ -9,6 +9,7 @@
 #include "../csrc/covis_math.h"
 #include "../csrc/kfcull_math.h"
 #include "../csrc/fuse_sim3_math.h"
+#include "../csrc/fuse_pose_math.h"
 #include <climits>
 #include <algorithm>
 #include <cmath>
@@ -1839,6 +1840,159 @@ int SearchAndFuseBatch::resolve(int k, const uint8_t* skip_now, const uint8_t* d
   return nFused;
 }
 
+// ---- SearchInNeighborsBatch ---------------------------------------------------------------------------
+// one (keyframe, point) pair through csrc/fuse_sim3_math.h and csrc/fuse_pose_math.h; all keyframe arrays are that keyframe's own
+static uint32_t fpm_pair_host(const float* rec, const float* pose, const int32_t* cell_off, const uint16_t* cell_idx, const float* kxy, const uint8_t* koct,
+                              const uint8_t* kdesc, const float* P3, const float* Pn, float dmin, float dmax, const uint8_t* pdesc, int nlevels, float logsf, float th,
+                              const float* sf, const float* isig, float* uv, int32_t* n_cand) {
+  float u, v; int level;
+  const int st = fsm_gate(rec, pose, P3, Pn, dmin, dmax, nlevels, logsf, u, v, level);
+  if (uv) { uv[0] = u; uv[1] = v; }
+  if (n_cand) *n_cand = 0;
+  if (st != FSM_EMPTY) return fsm_pack(st, 0, FSM_NO_DIST, FSM_NO_IDX);
+  uint32_t q[8];
+  fsm_load_desc(pdesc, q);
+  int n = 0;
+  const uint32_t w = fpm_window_best(rec, cell_off, cell_idx, kxy, koct, kdesc, u, v, level, th, sf, isig, q, &n);
+  if (n_cand) *n_cand = n;
+  return w;
+}
+
+int fuse_pose_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
+                        const int32_t* cell_off, const int32_t* cell_idx, const float* pose, int nlevels, const float* scale_factors, const float* inv_level_sigma2,
+                        float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc,
+                        int J, const int32_t* job_kf, const int32_t* job_pt0, const int32_t* job_n, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv,
+                        int32_t* n_cand) {
+  if (fsm_check_args(K, P, feat_off, cell_off, cell_idx, nlevels, th)) return -1;
+  int64_t total = 0, tiles = 0;
+  if (fpm_check_jobs(J, K, P, job_kf, job_pt0, job_n, &total, &tiles)) return -1;
+  const size_t F = K ? (size_t)feat_off[K] : 0;
+  if (!scale_factors || !inv_level_sigma2 || (K > 0 && (!kf_rec || !pose)) || (J > 0 && (!n_valid || !n_hit)) ||
+      (P > 0 && (!pos || !normal || !min_dist || !max_dist || !pt_desc)) || (total > 0 && !table) || (F && (!feat_xy || !feat_octave || !feat_desc)))
+    return -1;
+  std::vector<uint16_t> idx16(F);
+  for (size_t f = 0; f < F; f++) idx16[f] = (uint16_t)cell_idx[f];
+  size_t e = 0;
+  for (int j = 0; j < J; j++) {
+    n_valid[j] = n_hit[j] = 0;
+    const int k = job_kf[j];
+    const int32_t f0 = feat_off[k];
+    for (int i = job_pt0[j]; i < job_pt0[j] + job_n[j]; i++, e++) {
+      const uint32_t w = fpm_pair_host(kf_rec + FSM_REC_FLOATS * (size_t)k, pose + FSM_POSE_FLOATS * (size_t)k, cell_off + (size_t)k * (FSM_CELLS + 1), idx16.data() + f0,
+                                       feat_xy + 2 * (size_t)f0, feat_octave + f0, feat_desc + 32 * (size_t)f0, pos + 3 * (size_t)i, normal + 3 * (size_t)i, min_dist[i],
+                                       max_dist[i], pt_desc + 32 * (size_t)i, nlevels, logScaleFactor, th, scale_factors, inv_level_sigma2, uv ? uv + 2 * e : nullptr,
+                                       n_cand ? n_cand + e : nullptr);
+      table[e] = w;
+      n_valid[j] += (w >> 29) >= FSM_EMPTY;
+      n_hit[j] += (w >> 29) == FSM_HIT;
+    }
+  }
+  return 0;
+}
+
+SearchInNeighborsBatch::SearchInNeighborsBatch(HipContext* ctx, const KeyFrames& kfs, int n_calls, const int32_t* target, int current, const Points& pts, int n_current,
+                                               int nlevels, const float* scale_factors, const float* inv_level_sigma2, float logScaleFactor, float th)
+    : K_(kfs.K), C_(n_calls), cur_(current), P1_(n_current), P2_(pts.P - n_current), nlevels_(nlevels), logsf_(logScaleFactor), th_(th) {
+  const int K = K_, P = pts.P, C = C_;
+  if (K < 0 || P < 0 || C < 0 || n_current < 0 || n_current > P || (C > 0 && !target) || !scale_factors || !inv_level_sigma2 || nlevels < 1 || nlevels > FSM_MAX_LEVELS ||
+      (int64_t)C * n_current + P2_ > (int64_t)INT32_MAX)
+    throw infrastructure_ex("SearchInNeighborsBatch: bad arguments");
+  // C jobs (target of call c, the current keyframe's points) and one (current keyframe, the predicted candidates); without a current keyframe the last job is left out
+  std::vector<int32_t> jk, j0, jn;
+  for (int c = 0; c < C; c++) { jk.push_back(target[c]); j0.push_back(0); jn.push_back(P1_); }
+  if (current >= 0) { jk.push_back(current); j0.push_back(P1_); jn.push_back(P2_); }
+  else if (P2_ > 0) throw infrastructure_ex("SearchInNeighborsBatch: candidates without a current keyframe");
+  const int J = (int)jk.size();
+  table_.assign((size_t)C * (size_t)P1_ + (size_t)P2_, 0); n_valid_.assign((size_t)J, 0); n_hit_.assign((size_t)J, 0);
+  if (ctx) {
+    check(ccm_fuse_pose_eval(ctx->get(), K, kfs.rec, kfs.feat_off, kfs.feat_xy, kfs.feat_octave, kfs.feat_desc, kfs.cell_off, kfs.cell_idx, kfs.pose, nlevels, scale_factors,
+                             inv_level_sigma2, logScaleFactor, th, P, pts.pos, pts.normal, pts.min_dist, pts.max_dist, pts.desc, J, jk.data(), j0.data(), jn.data(),
+                             table_.data(), n_valid_.data(), n_hit_.data(), nullptr),
+          ctx->get(), "ccm_fuse_pose_eval");
+  } else if (fuse_pose_eval_host(K, kfs.rec, kfs.feat_off, kfs.feat_xy, kfs.feat_octave, kfs.feat_desc, kfs.cell_off, kfs.cell_idx, kfs.pose, nlevels, scale_factors,
+                                 inv_level_sigma2, logScaleFactor, th, P, pts.pos, pts.normal, pts.min_dist, pts.max_dist, pts.desc, J, jk.data(), j0.data(), jn.data(),
+                                 table_.data(), n_valid_.data(), n_hit_.data(), nullptr, nullptr)) {
+    throw infrastructure_ex("SearchInNeighborsBatch: bad arguments");
+  }
+  // the arguments are valid from here on: what the resolves may have to evaluate again
+  target_.assign(jk.begin(), jk.begin() + C);
+  sf_.assign(scale_factors, scale_factors + nlevels); isig_.assign(inv_level_sigma2, inv_level_sigma2 + nlevels);
+  if (K == 0) return;
+  const size_t F = (size_t)kfs.feat_off[K];
+  rec_.assign(kfs.rec, kfs.rec + FSM_REC_FLOATS * (size_t)K);
+  pose_.assign(kfs.pose, kfs.pose + FSM_POSE_FLOATS * (size_t)K);
+  feat_off_.assign(kfs.feat_off, kfs.feat_off + K + 1);
+  cell_off_.assign(kfs.cell_off, kfs.cell_off + (size_t)K * (FSM_CELLS + 1));
+  cell_idx_.resize(F);
+  for (size_t f = 0; f < F; f++) cell_idx_[f] = (uint16_t)kfs.cell_idx[f];
+  if (F) { kxy_.assign(kfs.feat_xy, kfs.feat_xy + 2 * F); koct_.assign(kfs.feat_octave, kfs.feat_octave + F); kdesc_.assign(kfs.feat_desc, kfs.feat_desc + 32 * F); }
+  if (P) {
+    pos_.assign(pts.pos, pts.pos + 3 * (size_t)P); normal_.assign(pts.normal, pts.normal + 3 * (size_t)P);
+    dmin_.assign(pts.min_dist, pts.min_dist + P); dmax_.assign(pts.max_dist, pts.max_dist + P);
+    pdesc_.assign(pts.desc, pts.desc + 32 * (size_t)P);
+  }
+}
+
+uint32_t SearchInNeighborsBatch::eval(int k, const float* P3, const float* Pn, float dmin, float dmax, const uint8_t* desc) const {
+  const int32_t f0 = feat_off_[k];
+  return fpm_pair_host(rec_.data() + FSM_REC_FLOATS * (size_t)k, pose_.data() + FSM_POSE_FLOATS * (size_t)k, cell_off_.data() + (size_t)k * (FSM_CELLS + 1),
+                       cell_idx_.data() + f0, kxy_.data() + 2 * (size_t)f0, koct_.data() + f0, kdesc_.data() + 32 * (size_t)f0, P3, Pn, dmin, dmax, desc, nlevels_, logsf_,
+                       th_, sf_.data(), isig_.data(), nullptr, nullptr);
+}
+
+static inline void sin_answer(uint32_t w, int32_t& bestIdx, int32_t& bestDist, int& nFused) {
+  const int st = (int)(w >> 29);
+  if (st >= FSM_FAR) bestDist = (int32_t)((w >> 16) & 0x1FFu);
+  if (st == FSM_HIT) { bestIdx = (int32_t)(w & 0xFFFFu); nFused++; }
+}
+
+int SearchInNeighborsBatch::resolve(int c, const uint8_t* skip_now, const uint8_t* desc_now, std::vector<int32_t>& bestIdx, std::vector<int32_t>& bestDist) {
+  if (c < 0 || c >= C_) throw infrastructure_ex("SearchInNeighborsBatch::resolve: call out of range");
+  bestIdx.assign((size_t)P1_, -1); bestDist.assign((size_t)P1_, 256);
+  int nFused = 0;
+  for (int i = 0; i < P1_; i++) {
+    if (skip_now && skip_now[i]) continue;
+    uint32_t w = table_[(size_t)c * P1_ + i];
+    if ((w >> 29) < FSM_EMPTY) continue;                       // the gates read nothing a Fuse call changes
+    if (desc_now && std::memcmp(desc_now + 32 * (size_t)i, pdesc_.data() + 32 * (size_t)i, 32) != 0) {
+      w = eval(target_[c], pos_.data() + 3 * (size_t)i, normal_.data() + 3 * (size_t)i, dmin_[i], dmax_[i], desc_now + 32 * (size_t)i);
+      n_reeval_++;
+    }
+    sin_answer(w, bestIdx[i], bestDist[i], nFused);
+  }
+  return nFused;
+}
+
+int SearchInNeighborsBatch::resolve_current(int n, const int32_t* slot, const uint8_t* skip_now, const uint8_t* desc_now, const Points& fresh,
+                                            std::vector<int32_t>& bestIdx, std::vector<int32_t>& bestDist) {
+  if (n < 0 || (n > 0 && !slot) || cur_ < 0) throw infrastructure_ex("SearchInNeighborsBatch::resolve_current: bad arguments");
+  bestIdx.assign((size_t)n, -1); bestDist.assign((size_t)n, 256);
+  int nFused = 0;
+  for (int i = 0; i < n; i++) {
+    if (skip_now && skip_now[i]) continue;
+    const int s = slot[i];
+    if (s >= P2_ || s < -1) throw infrastructure_ex("SearchInNeighborsBatch::resolve_current: slot out of range");
+    uint32_t w;
+    if (s < 0) {                                                 // a candidate the build did not predict: from what the caller passes for it
+      if (!fresh.pos || !fresh.normal || !fresh.min_dist || !fresh.max_dist || !fresh.desc || fresh.P < n)
+        throw infrastructure_ex("SearchInNeighborsBatch::resolve_current: an unpredicted candidate without fresh data");
+      w = eval(cur_, fresh.pos + 3 * (size_t)i, fresh.normal + 3 * (size_t)i, fresh.min_dist[i], fresh.max_dist[i],
+               desc_now ? desc_now + 32 * (size_t)i : fresh.desc + 32 * (size_t)i);
+      n_unpredicted_++;
+    } else {
+      w = table_[(size_t)C_ * P1_ + s];
+      if ((w >> 29) < FSM_EMPTY) continue;
+      const size_t g = (size_t)P1_ + (size_t)s;
+      if (desc_now && std::memcmp(desc_now + 32 * (size_t)i, pdesc_.data() + 32 * g, 32) != 0) {
+        w = eval(cur_, pos_.data() + 3 * g, normal_.data() + 3 * g, dmin_[g], dmax_[g], desc_now + 32 * (size_t)i);
+        n_reeval_++;
+      }
+    }
+    sin_answer(w, bestIdx[i], bestDist[i], nFused);
+  }
+  return nFused;
+}
+
 }  // namespace cslam
 
 // ---- C entry points (ccm_host_c.h): the Python test-suite and the drop-in translation units under shim/ ---------------------------------------
@@ -2442,6 +2596,65 @@ int ccmh_fuse_sim3_eval_host(int K, const float* kf_rec, const int32_t* feat_off
                                     min_dist, max_dist, pt_desc, table, n_valid, n_hit, uv, n_cand);
 }
 void ccmh_fuse_sim3_decompose(const float* Scw12, float* pose15) { fsm_decompose_scw(Scw12, pose15); }
+
+// SearchInNeighborsBatch through C, and fuse_pose_math.h compiled for the host
+void* ccmh_fuse_pose_create(int device, int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
+                            const int32_t* cell_off, const int32_t* cell_idx, const float* pose, int nlevels, const float* scale_factors, const float* inv_level_sigma2,
+                            float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist,
+                            const uint8_t* pt_desc, int n_calls, const int32_t* target, int current, int n_current) {
+  try {
+    cslam::SearchInNeighborsBatch::KeyFrames kf;
+    kf.K = K; kf.rec = kf_rec; kf.feat_off = feat_off; kf.feat_xy = feat_xy; kf.feat_octave = feat_octave; kf.feat_desc = feat_desc; kf.cell_off = cell_off;
+    kf.cell_idx = cell_idx; kf.pose = pose;
+    cslam::SearchInNeighborsBatch::Points pt;
+    pt.P = P; pt.pos = pos; pt.normal = normal; pt.min_dist = min_dist; pt.max_dist = max_dist; pt.desc = pt_desc;
+    return new cslam::SearchInNeighborsBatch(device < 0 ? nullptr : &thread_context(device), kf, n_calls, target, current, pt, n_current, nlevels, scale_factors,
+                                             inv_level_sigma2, logScaleFactor, th);
+  } catch (const std::exception&) { return nullptr; }
+}
+int ccmh_fuse_pose_table(void* h, uint32_t* table, int32_t* n_valid, int32_t* n_hit) {
+  if (!h) return -1;
+  const cslam::SearchInNeighborsBatch& b = *static_cast<cslam::SearchInNeighborsBatch*>(h);
+  if (table && !b.table().empty()) std::memcpy(table, b.table().data(), b.table().size() * 4);
+  if (n_valid && !b.nValid().empty()) std::memcpy(n_valid, b.nValid().data(), b.nValid().size() * 4);
+  if (n_hit && !b.nHit().empty()) std::memcpy(n_hit, b.nHit().data(), b.nHit().size() * 4);
+  return 0;
+}
+static int fuse_pose_copy_out(int n, int n_pts, const std::vector<int32_t>& bi, const std::vector<int32_t>& bd, int32_t* best_idx, int32_t* best_dist) {
+  if ((int)bi.size() != n_pts) return -1001;
+  if (n_pts) { std::memcpy(best_idx, bi.data(), bi.size() * 4); std::memcpy(best_dist, bd.data(), bd.size() * 4); }
+  return n;
+}
+int ccmh_fuse_pose_resolve(void* h, int c, const uint8_t* skip_now, const uint8_t* desc_now, int n_pts, int32_t* best_idx, int32_t* best_dist) {
+  if (!h) return -1000;
+  try {
+    std::vector<int32_t> bi, bd;
+    const int n = static_cast<cslam::SearchInNeighborsBatch*>(h)->resolve(c, skip_now, desc_now, bi, bd);
+    return fuse_pose_copy_out(n, n_pts, bi, bd, best_idx, best_dist);
+  } catch (const std::exception&) { return -1000; }
+}
+int ccmh_fuse_pose_resolve_current(void* h, int n, const int32_t* slot, const uint8_t* skip_now, const uint8_t* desc_now, const float* pos, const float* normal,
+                                   const float* min_dist, const float* max_dist, const uint8_t* desc, int32_t* best_idx, int32_t* best_dist) {
+  if (!h) return -1000;
+  try {
+    cslam::SearchInNeighborsBatch::Points fresh;
+    fresh.P = n; fresh.pos = pos; fresh.normal = normal; fresh.min_dist = min_dist; fresh.max_dist = max_dist; fresh.desc = desc;
+    std::vector<int32_t> bi, bd;
+    const int nf = static_cast<cslam::SearchInNeighborsBatch*>(h)->resolve_current(n, slot, skip_now, desc_now, fresh, bi, bd);
+    return fuse_pose_copy_out(nf, n, bi, bd, best_idx, best_dist);
+  } catch (const std::exception&) { return -1000; }
+}
+long long ccmh_fuse_pose_n_reeval(void* h) { return h ? static_cast<cslam::SearchInNeighborsBatch*>(h)->n_reeval() : -1; }
+long long ccmh_fuse_pose_n_unpredicted(void* h) { return h ? static_cast<cslam::SearchInNeighborsBatch*>(h)->n_unpredicted() : -1; }
+void ccmh_fuse_pose_destroy(void* h) { delete static_cast<cslam::SearchInNeighborsBatch*>(h); }
+int ccmh_fuse_pose_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
+                             const int32_t* cell_off, const int32_t* cell_idx, const float* pose, int nlevels, const float* scale_factors, const float* inv_level_sigma2,
+                             float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist,
+                             const uint8_t* pt_desc, int J, const int32_t* job_kf, const int32_t* job_pt0, const int32_t* job_n, uint32_t* table, int32_t* n_valid,
+                             int32_t* n_hit, float* uv, int32_t* n_cand) {
+  return cslam::fuse_pose_eval_host(K, kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off, cell_idx, pose, nlevels, scale_factors, inv_level_sigma2, logScaleFactor,
+                                    th, P, pos, normal, min_dist, max_dist, pt_desc, J, job_kf, job_pt0, job_n, table, n_valid, n_hit, uv, n_cand);
+}
 
 int ccmh_search_for_initialization(int device, const float* x1, const float* y1, const int32_t* oct1, const float* a1, const uint8_t* d1, int N1,
                                    const float* x2, const float* y2, const int32_t* oct2, const float* a2, const uint8_t* d2, int N2,

@@ -586,6 +586,61 @@ int fuse_sim3_eval_host(int K, const float* kf_rec, const int32_t* feat_off, con
                         int32_t* n_hit, float* uv, int32_t* n_cand);
 
 // ---------------------------------------------------------------------------------------------------
+// SearchInNeighbors — Mapping.cpp:471-547: matcher.Fuse(pKFi, vpMapPointMatches) for every fuse target (:495-503), then matcher.Fuse(mpCurrentKeyFrame,
+// vpFuseCandidates) with the targets' points (:510-529).  The constructor evaluates BOTH directions in ONE ccm_fuse_pose_eval call: call c < n_calls
+// is the job (keyframe target[c], the current keyframe's points = the first n_current of pts), the last job is (keyframe `current`, the PREDICTED fuse candidates =
+// the rest of pts: the union of the targets' points at build time in the reference's order).  Everything a resolve may need later is copied.
+// resolve(c, ...) returns what the c-th Fuse call of the first loop returns, resolve_current(...) what the Fuse on the current keyframe returns, whatever the
+// calls before did to the map: a pair that reached the window and whose current descriptor differs from the snapshot is evaluated again on the calling thread
+// (fuse_pose_math.h); a candidate the prediction missed (slot -1) is evaluated from what the caller passes for it.  ctx == nullptr asks for the host evaluator by
+// name; with a context, a device error throws — there is no fall-back.  The map mutations stay the caller's.
+// ---------------------------------------------------------------------------------------------------
+class SearchInNeighborsBatch {
+ public:
+  struct KeyFrames {   // K keyframes, flat (include/ccm_hip.h, ccm_fuse_pose_eval); pose: Rcw (9), tcw (3), Ow (3) per keyframe
+    int K = 0; const float* rec = nullptr; const int32_t* feat_off = nullptr; const float* feat_xy = nullptr; const uint8_t* feat_octave = nullptr;
+    const uint8_t* feat_desc = nullptr; const int32_t* cell_off = nullptr; const int32_t* cell_idx = nullptr; const float* pose = nullptr;
+  };
+  struct Points { int P = 0; const float* pos = nullptr; const float* normal = nullptr; const float* min_dist = nullptr; const float* max_dist = nullptr;
+                  const uint8_t* desc = nullptr; };
+  // current < 0: no second direction (pts holds the current keyframe's points alone)
+  SearchInNeighborsBatch(HipContext* ctx, const KeyFrames& kfs, int n_calls, const int32_t* target, int current, const Points& pts, int n_current, int nlevels,
+                         const float* scale_factors, const float* inv_level_sigma2, float logScaleFactor, float th);
+  // The c-th Fuse call of the first loop.  skip_now[i] != 0: the reference would `continue` now (!pMP || isBad() || IsInKeyFrame(pKF) || mbDoNotReplace);
+  // desc_now (nullable): the current keyframe's points' CURRENT descriptors.  bestIdx[i] = the feature point i is fused with (-1: none), bestDist[i] as the
+  // reference leaves it (256: no candidate); returns nFused.
+  int resolve(int c, const uint8_t* skip_now, const uint8_t* desc_now, std::vector<int32_t>& bestIdx, std::vector<int32_t>& bestDist);
+  // Fuse(mpCurrentKeyFrame, vpFuseCandidates) for the n candidates the caller has NOW: slot[i] = candidate i's index among the predicted ones, or -1; skip_now and
+  // desc_now (nullable) per candidate; fresh (n entries, read where slot[i] == -1 and the candidate is not skipped): position, normal, bounds, descriptor.
+  int resolve_current(int n, const int32_t* slot, const uint8_t* skip_now, const uint8_t* desc_now, const Points& fresh, std::vector<int32_t>& bestIdx,
+                      std::vector<int32_t>& bestDist);
+  int calls() const { return C_; }
+  int currentPoints() const { return P1_; }
+  int predicted() const { return P2_; }
+  const std::vector<uint32_t>& table() const { return table_; }   // call-major, then the predicted candidates; as evaluated at construction
+  const std::vector<int32_t>& nValid() const { return n_valid_; } // per job
+  const std::vector<int32_t>& nHit() const { return n_hit_; }
+  long long n_reeval() const { return n_reeval_; }                 // pairs evaluated again because the descriptor had changed
+  long long n_unpredicted() const { return n_unpredicted_; }       // candidates evaluated from fresh data
+ private:
+  uint32_t eval(int k, const float* P3, const float* Pn, float dmin, float dmax, const uint8_t* desc) const;
+  int K_ = 0, C_ = 0, cur_ = -1, P1_ = 0, P2_ = 0, nlevels_ = 0; float logsf_ = 0, th_ = 0;
+  std::vector<float> rec_, pose_, kxy_, sf_, isig_, pos_, normal_, dmin_, dmax_;
+  std::vector<int32_t> target_, feat_off_, cell_off_, n_valid_, n_hit_;
+  std::vector<uint16_t> cell_idx_;
+  std::vector<uint8_t> koct_, kdesc_, pdesc_;
+  std::vector<uint32_t> table_;
+  long long n_reeval_ = 0, n_unpredicted_ = 0;
+};
+// ccm_fuse_pose_eval's arguments after the context through csrc/fuse_pose_math.h on the calling thread; -1 where the device entry returns CCM_E_ARG.
+// n_cand (nullable, sum(job_n)): the size of vIndices of every pair that reached the window (0 otherwise), for scripts/fuse_pose_profile.py.
+int fuse_pose_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
+                        const int32_t* cell_off, const int32_t* cell_idx, const float* pose, int nlevels, const float* scale_factors, const float* inv_level_sigma2,
+                        float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc,
+                        int J, const int32_t* job_kf, const int32_t* job_pt0, const int32_t* job_n, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv,
+                        int32_t* n_cand);
+
+// ---------------------------------------------------------------------------------------------------
 // Optimizer — cslam/include/cslam/Optimizer.h:84-112 (numerics; graph walking is the integrator's glue)
 // ---------------------------------------------------------------------------------------------------
 struct BAProblem {   // owning, f64 like g2o; filled from KeyFrames / MapPoints via Converter (Converter.cc:40-119)

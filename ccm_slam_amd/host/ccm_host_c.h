@@ -133,6 +133,18 @@ long long ccmh_fuse_sim3_n_reeval(void* h);
 void ccmh_fuse_sim3_destroy(void* h);
 int ccmh_fuse_sim3_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc, const int32_t* cell_off, const int32_t* cell_idx, const float* Scw, int nlevels, const float* scale_factors, float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv, int32_t* n_cand);
 void ccmh_fuse_sim3_decompose(const float* Scw12, float* pose15);
+/* cslam::SearchInNeighborsBatch (both directions of a SearchInNeighbors from ONE ccm_fuse_pose_eval call; the keyframe, per-call and point arguments as there).  The
+ * first n_current points are the current keyframe's, the rest the predicted fuse candidates; target[n_calls] = the keyframe of each call, current = the current
+ * keyframe's index (-1: none).  device < 0 asks for the host evaluator by name; create returns NULL on bad arguments or a device error.  resolve / resolve_current
+ * return nFused, -1000 on an error, -1001 when n_pts is not the batch's.  eval_host: ccm_fuse_pose_eval's arguments after the context on the calling thread. */
+void* ccmh_fuse_pose_create(int device, int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc, const int32_t* cell_off, const int32_t* cell_idx, const float* pose, int nlevels, const float* scale_factors, const float* inv_level_sigma2, float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc, int n_calls, const int32_t* target, int current, int n_current);
+int ccmh_fuse_pose_table(void* h, uint32_t* table, int32_t* n_valid, int32_t* n_hit);
+int ccmh_fuse_pose_resolve(void* h, int c, const uint8_t* skip_now, const uint8_t* desc_now, int n_pts, int32_t* best_idx, int32_t* best_dist);
+int ccmh_fuse_pose_resolve_current(void* h, int n, const int32_t* slot, const uint8_t* skip_now, const uint8_t* desc_now, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* desc, int32_t* best_idx, int32_t* best_dist);
+long long ccmh_fuse_pose_n_reeval(void* h);
+long long ccmh_fuse_pose_n_unpredicted(void* h);
+void ccmh_fuse_pose_destroy(void* h);
+int ccmh_fuse_pose_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc, const int32_t* cell_off, const int32_t* cell_idx, const float* pose, int nlevels, const float* scale_factors, const float* inv_level_sigma2, float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc, int J, const int32_t* job_kf, const int32_t* job_pt0, const int32_t* job_n, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv, int32_t* n_cand);
 void ccmh_to_se3quat(const float* Tcw16, double* qt7);
 void ccmh_se3quat_to_cvmat(const double* qt7, float* Tcw16);
 void ccmh_sim3_to_cvse3(const double* s8, float* Tcw16);

@@ -619,6 +619,26 @@ int  ccm_fuse_sim3_eval(ccm_ctx* ctx, int K, const float* kf_rec /* 10 K */, con
                         const float* min_dist, const float* max_dist, const uint8_t* pt_desc /* 32 P */, uint32_t* table /* K P */, int32_t* n_valid /* K */,
                         int32_t* n_hit /* K */, float* uv /* 2 K P or NULL */);
 
+/* ---- SearchInNeighbors: every Fuse(pKF, vpMapPoints, th) of one LocalMapping::SearchInNeighbors, both directions -----------------------
+ * LocalMapping::SearchInNeighbors (cslam/src/Mapping.cpp:471-547) calls ORBmatcher::Fuse(pKF, vpMapPoints, 3) (ORBmatcher.cpp:854-993) once per fuse target with the
+ * current keyframe's points and once on the current keyframe with the targets' points.  This call evaluates the loop body of every pair of a JOB LIST up to its
+ * decision, bit-identical to the reference (the lines are csrc/fuse_sim3_math.h and csrc/fuse_pose_math.h, which also compile for the host).
+ * Stateless; the skips (isBad(), IsInKeyFrame, mbDoNotReplace) and the map mutations stay the caller's (cslam::SearchInNeighborsBatch replays them).
+ * Keyframes, per-call values and points: as for ccm_fuse_sim3_eval, with two differences.  pose + 15 k = GetRotation() (9, row-major), GetTranslation() (3),
+ * GetCameraCenter() (3) of keyframe k, in place of Scw; inv_level_sigma2[nlevels] = mvInvLevelSigma2.
+ * Jobs: job j < J is keyframe job_kf[j] against the points job_pt0[j] .. job_pt0[j] + job_n[j] - 1.  Jobs may share keyframes and points; ranges may overlap.
+ * Out: table has sum(job_n) words, job j's at the prefix sum of job_n, in point order; a word is ccm_fuse_sim3_eval's with status 5 = no candidate passed the level
+ * filter and the gate e2 * inv_level_sigma2[octave] > 5.99.  n_valid[j] / n_hit[j]: the job's pairs with status >= 4 / == 7.  uv (nullable, 2 sum(job_n)).
+ * J == 0, K == 0, P == 0 and job_n[j] == 0 are legal.  CCM_E_ARG, with nothing launched: whatever ccm_fuse_sim3_eval refuses (K * P > INT32_MAX among it), a null
+ * inv_level_sigma2, null job arrays with J > 0, job_kf outside [0, K), a negative job_n or job_pt0, a job that ends beyond P, sum(job_n) > INT32_MAX.  NaN / Inf in
+ * the floats are no errors.  One H2D copy, one launch and one D2H copy on the context's stream. */
+int  ccm_fuse_pose_eval(ccm_ctx* ctx, int K, const float* kf_rec /* 10 K */, const int32_t* feat_off /* K + 1 */, const float* feat_xy, const uint8_t* feat_octave,
+                        const uint8_t* feat_desc, const int32_t* cell_off /* 3601 K */, const int32_t* cell_idx, const float* pose /* 15 K */, int nlevels,
+                        const float* scale_factors, const float* inv_level_sigma2, float logScaleFactor, float th, int P, const float* pos /* 3 P */,
+                        const float* normal /* 3 P */, const float* min_dist, const float* max_dist, const uint8_t* pt_desc /* 32 P */, int J,
+                        const int32_t* job_kf, const int32_t* job_pt0, const int32_t* job_n, uint32_t* table /* sum(job_n) */, int32_t* n_valid /* J */,
+                        int32_t* n_hit /* J */, float* uv /* 2 sum(job_n) or NULL */);
+
 #ifdef __cplusplus
 }
 #endif

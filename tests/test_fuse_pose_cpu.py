@@ -1,0 +1,343 @@
+"""SearchInNeighbors on the CPU: csrc/fuse_pose_math.h compiled by g++ (libccm_host.so) against the reference's own ORBmatcher::Fuse(pKF,
+vpMapPoints, th) (oracle/_ref/libmatcher_ref.so through ref_fuse, kf_has_mp all zero, one call per job), against oracle.grid_candidates plus a numpy arg-min with
+the level filter and the chi-square gate for the three outcomes the reference does not tell apart, and against hand-made pairs with known answers; job lists; the
+mirror cslam::SearchInNeighborsBatch with the host evaluator through the 12 Fuse calls of the fan-out and the call on the current keyframe, between which the map
+changes; every CCM_E_ARG case.  Every comparison is exact: integers, and float bit patterns for u and v."""
+import copy
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+import oracle
+import tests.test_ref_matcher as trm
+from ccm_slam_amd import fuse_pose as fp, fuse_sim3 as fs, synth
+from ccm_slam_amd._lib import CcmError
+from fuse_pose_cases import (CALLS, CURRENT, DISC_SIZES, DISC_WHOLE, N_KF, all_pairs_jobs, assert_reference_scene, chi2, disc, disc_gate_counts, fan_out_scene, passes,
+                             planted, ref_fuse)
+from fuse_sim3_cases import same_as_reference
+
+
+@pytest.fixture(scope="module")
+def frames():
+    o = oracle.OrbOracle(1000)
+    out = [o.extract(synth.gen_image(1000, t)) for t in (0, 1)]
+    o.close()
+    return out
+
+
+@pytest.fixture(scope="module")
+def scene(frames):
+    return fan_out_scene(frames)
+
+
+@pytest.fixture(scope="module")
+def rlib():
+    """the CPU tests require the reference's library"""
+    if not os.path.exists(trm.LIB):
+        from oracle import ref
+        ref.build()
+    return C.CDLL(trm.LIB)
+
+
+def every_keyframe(sc, info, th):
+    """the nine keyframes against the current keyframe's points at `th`, through the host evaluator"""
+    s = sc.subset(jobs=all_pairs_jobs(N_KF, info["n1"]))
+    s.th = float(th)
+    return s, fp.fuse_pose_eval_host(s, want_uv=True, want_cand=True)
+
+
+@pytest.fixture(scope="module")
+def at_th3(scene):
+    return every_keyframe(*scene, 3.0)
+
+
+def rows(res, P):
+    """a result of all_pairs_jobs as (K, P) arrays"""
+    t = {n: a.reshape(-1, P) for n, a in fs.unpack_table(res["table"]).items()}
+    return t, res["uv"].reshape(-1, P, 2)
+
+
+@pytest.mark.parametrize("th", [3.0, 2.5])
+def test_host_evaluator_equals_the_references_fuse_for_every_keyframe(frames, scene, rlib, th):
+    sc, info = scene
+    s, got = every_keyframe(sc, info, th)
+    refs = [ref_fuse(rlib, frames, sc, info, k, th=th) for k in range(N_KF)]
+    assert_reference_scene(refs, frames, info, th)
+    t, uv = rows(got, info["n1"])
+    for k in range(N_KF):
+        same_as_reference({n: a[k] for n, a in t.items()}, uv[k], refs[k], f"keyframe {k} th {th}")
+        assert got["n_valid"][k] == refs[k][2].sum() and got["n_hit"][k] == refs[k][0]
+
+
+def test_statuses_4_5_6_against_the_oracles_grid_and_a_numpy_arg_min(frames, scene, at_th3):
+    """what the reference reports as 'not fused' in three flavours: window empty, nobody passed the level filter and the gate, best distance above TH_LOW"""
+    sc, info = scene
+    s, got = at_th3
+    P = info["n1"]
+    t, uv = rows(got, P)
+    n_cand = got["n_cand"].reshape(-1, P)
+    kps, desc = frames[0]
+    isig = info["s7"]["isig"]; sf = info["s7"]["sf"]
+    pdesc = sc.pt_desc.reshape(-1, 32)[:P]
+    seen = set(); gated = 0
+    for k in (0, 3, CURRENT):
+        m = np.flatnonzero(t["status"][k] >= 4)
+        u, v, lvl = uv[k, m, 0], uv[k, m, 1], t["level"][k, m]
+        r = (np.float32(3.0) * sf[lvl]).astype(np.float32)
+        none = -np.ones(m.size, np.int32)
+        aoff, _ = oracle.grid_candidates(kps["x"], kps["y"], kps["octave"], trm.BOUNDS, u, v, r, none, none)
+        loff, lidx = oracle.grid_candidates(kps["x"], kps["y"], kps["octave"], trm.BOUNDS, u, v, r, (lvl - 1).astype(np.int32), lvl.astype(np.int32))
+        assert np.array_equal(np.diff(aoff), n_cand[k, m]), k
+        bits = np.unpackbits(desc, axis=1).astype(np.int16); qbits = np.unpackbits(pdesc[m], axis=1).astype(np.int16)
+        for j, i in enumerate(m):
+            cand = lidx[loff[j]:loff[j + 1]]
+            ok = passes(chi2(u[j], v[j], kps["x"][cand], kps["y"][cand], isig[kps["octave"][cand]])) if cand.size else np.zeros(0, bool)
+            gated += int((~ok).sum())
+            cand = cand[ok]
+            if aoff[j + 1] == aoff[j]:
+                exp = (4, -1, -1)
+            elif cand.size == 0:
+                exp = (5, -1, -1)
+            else:
+                d = np.abs(bits[cand] - qbits[j]).sum(1)
+                b = int(np.argmin(d))                   # the first minimum, in the reference's candidate order
+                exp = (7 if d[b] <= 50 else 6, int(cand[b]), int(d[b]))
+            assert (int(t["status"][k, i]), int(t["idx"][k, i]), int(t["dist"][k, i])) == exp, (k, i)
+            seen.add(exp[0])
+    assert seen == {4, 5, 6, 7} and gated > 100
+
+
+def test_planted_boundaries_have_their_known_answers():
+    pl = planted()
+    sc = pl.scene()
+    got = fp.fuse_pose_eval_host(sc, want_uv=True)
+    pl.check(got["table"], "host")
+    st = fs.unpack_table(got["table"])["status"].reshape(sc.K, sc.P)
+    assert np.array_equal(got["n_valid"], (st >= 4).sum(1)) and np.array_equal(got["n_hit"], (st == 7).sum(1))
+    # the exact projections behind the bounds cases: points 3 .. 10 of keyframe 0
+    uv = got["uv"].reshape(sc.K, sc.P, 2)
+    assert uv[0, 3:11].tolist() == [[0, 10], [752, 10], [10, 0], [10, 480], [-2.0 ** -100, 10],
+                                    [float(np.nextafter(np.float32(752), np.float32(0))), 10], [10, -2.0 ** -100],
+                                    [10, float(np.nextafter(np.float32(480), np.float32(0)))]]
+    # a zero inv_level_sigma2 switches the gate off: the candidate inside the box and outside the circle, which has the query's own descriptor, wins
+    zero = fp.fuse_pose_eval_host(pl.scene(inv_sigma2=np.zeros(8, np.float32)))
+    tz = {n: a.reshape(sc.K, sc.P) for n, a in fs.unpack_table(zero["table"]).items()}
+    assert (tz["status"][pl.k_box, pl.i_q0], tz["idx"][pl.k_box, pl.i_q0], tz["dist"][pl.k_box, pl.i_q0]) == (7, 0, 0)
+    assert not (tz["status"] == 5).any() or (tz["status"] == 5).sum() < (st == 5).sum()
+
+
+def test_disc_windows_hold_the_planted_candidate_counts():
+    pl = disc()
+    sc = pl.scene()
+    got = fp.fuse_pose_eval_host(sc, want_cand=True)
+    nc = got["n_cand"].reshape(sc.K, sc.P)
+    for lvl in range(DISC_WHOLE, 8):
+        assert nc[:, lvl].tolist() == list(DISC_SIZES)      # the window holds the whole disc, so its cells hold every feature of the keyframe
+    big = nc[len(DISC_SIZES) - 1]
+    assert big[0] < big[1] < big[2] < big[3] < big[4] == 300 and big[3] > 256 and big[12] == 0 < big[11] < big[10]      # r = 3 px at level 0: parts of the disc off the centre, nothing 9 px off
+    for k, n in enumerate(DISC_SIZES):
+        if n >= 60:
+            ok, out = disc_gate_counts(pl, k, DISC_WHOLE)
+            assert ok > 0 and out > 0, (n, ok, out)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+# jobs
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+def alone(sc, job):
+    return fp.fuse_pose_eval_host(sc.subset(jobs=[job]), want_uv=True)
+
+
+def each_job_equals_itself_alone(sc, res, evaluate):
+    """res: the result of sc's job list; evaluate(scene) runs one job alone"""
+    for j, job in enumerate(sc.jobs):
+        one = evaluate(sc.subset(jobs=[job]))
+        assert np.array_equal(fp.job_rows(res, j), one["table"]), (j, job)
+        assert np.array_equal(fp.job_rows(res, j, "uv").view(np.uint32), one["uv"].view(np.uint32)), (j, job)
+        assert res["n_valid"][j] == one["n_valid"][0] and res["n_hit"][j] == one["n_hit"][0], (j, job)
+
+
+JOB_LISTS = {
+    "disjoint ranges": [(0, 0, 300), (1, 300, 300), (2, 600, 300)],
+    "overlapping ranges": [(0, 100, 400), (1, 300, 400), (2, 0, 2500), (3, 350, 10)],
+    "a keyframe in two jobs": [(5, 0, 500), (1, 200, 100), (5, 0, 500), (5, 400, 300)],
+    "empty jobs": [(0, 0, 0), (4, 40, 257), (2, 7500, 0), (CURRENT, 2500, 2500)],
+}
+
+
+@pytest.mark.parametrize("name", list(JOB_LISTS))
+def test_a_job_gives_the_same_words_alone_and_inside_a_list(scene, name):
+    sc = scene[0].subset(jobs=JOB_LISTS[name])
+    res = fp.fuse_pose_eval_host(sc, want_uv=True)
+    assert res["table"].size == sum(j[2] for j in JOB_LISTS[name])
+    each_job_equals_itself_alone(sc, res, lambda s: fp.fuse_pose_eval_host(s, want_uv=True))
+    assert res["n_hit"].sum() > 100
+
+
+def _bad(sc, **over):
+    """a copy of the scene's arrays with some replaced"""
+    b = copy.copy(sc)
+    for k, v in over.items():
+        setattr(b, k, v)
+    return b
+
+
+def bad_argument_cases():
+    """(name, scene) for every CCM_E_ARG rule of ccm_fuse_pose_eval: those of ccm_fuse_sim3_eval on the keyframes and the scalars, then the new ones"""
+    sc = fp.make_scene(3, 20, 10, n_feat=40, seed=2)      # 4 keyframes, 30 points, jobs (0, 0, 20) (1, 0, 20) (2, 0, 20) (3, 20, 10)
+    i32 = lambda v: np.asarray(v, np.int32)
+    out = []
+    off = sc.feat_off.copy(); off[1] = off[2] + 1
+    out.append(("feat_off decreases", _bad(sc, feat_off=off)))
+    off = sc.feat_off.copy(); off[0] = 1
+    out.append(("feat_off does not start at 0", _bad(sc, feat_off=off)))
+    co = sc.cell_off.copy(); j = int(np.flatnonzero(np.diff(co[:fs.CELLS + 1]) > 0)[0]); co[j + 1] = co[j] - 1
+    out.append(("cell_off decreases", _bad(sc, cell_off=co)))
+    co = sc.cell_off.copy(); co[0] = 1
+    out.append(("cell_off does not start at 0", _bad(sc, cell_off=co)))
+    co = sc.cell_off.copy(); co[2 * (fs.CELLS + 1) - 1] -= 1
+    out.append(("cell_off ends short of the feature count", _bad(sc, cell_off=co)))
+    ci = sc.cell_idx.copy(); ci[45] = 40
+    out.append(("cell_idx out of range", _bad(sc, cell_idx=ci)))
+    ci = sc.cell_idx.copy(); ci[0] = -1
+    out.append(("cell_idx negative", _bad(sc, cell_idx=ci)))
+    out.append(("nlevels 0", _bad(sc, nlevels=0)))
+    out.append(("nlevels 17", _bad(sc, nlevels=17, scale_factors=np.ones(17, np.float32), inv_sigma2=np.ones(17, np.float32))))
+    for name, th in (("th 0", 0.0), ("th negative", -1.0), ("th NaN", float("nan")), ("th Inf", float("inf"))):
+        out.append((name, _bad(sc, th=th)))
+    n = 65536
+    big = fp.Scene(sc.rec[:10], [0, n], np.zeros(2 * n, np.float32) + 100, np.zeros(n, np.uint8), np.zeros(32 * n, np.uint8),
+                   np.concatenate([np.zeros(fs.CELLS, np.int32), [n]]), np.arange(n, dtype=np.int32) % 65535, sc.pose[:15], sc.scale_factors, sc.inv_sigma2, sc.log_sf,
+                   sc.th, sc.pos, sc.normal, sc.min_dist, sc.max_dist, sc.pt_desc, [(0, 0, 5)])
+    out.append(("65 536 features", big))
+    out.append(("K * P beyond INT32_MAX", _bad(sc, K=65536, P=32768)))      # checked before any array is read
+    out.append(("negative J", _bad(sc, J=-1)))
+    for name, what in (("null scale_factors", "scale_factors"), ("null inv_level_sigma2", "inv_sigma2"), ("null pose", "pose"), ("null rec", "rec"), ("null pos", "pos"),
+                       ("null pt_desc", "pt_desc"), ("null feat_desc", "feat_desc"), ("null job_kf", "job_kf"), ("null job_pt0", "job_pt0"), ("null job_n", "job_n")):
+        out.append((name, _bad(sc, **{what: None})))
+    out.append(("job_kf -1", _bad(sc, job_kf=i32([0, -1, 2, 3]))))
+    out.append(("job_kf == K", _bad(sc, job_kf=i32([0, 1, 2, 4]))))
+    out.append(("job_n negative", _bad(sc, job_n=i32([20, -1, 20, 10]))))
+    out.append(("job_pt0 negative", _bad(sc, job_pt0=i32([0, 0, -1, 20]))))
+    out.append(("a job ends beyond P", _bad(sc, job_pt0=i32([0, 0, 0, 21]))))
+    out.append(("a job starts beyond P", _bad(sc, job_pt0=i32([0, 0, 31, 20]), job_n=i32([20, 20, 0, 10]))))
+    # sum(job_n) beyond INT32_MAX: one keyframe, a point count the check alone reads, three jobs of 2^30 points
+    one = sc.subset([0], jobs=[(0, 0, 1 << 30)] * 3)
+    out.append(("sum(job_n) beyond INT32_MAX", _bad(one, P=(1 << 30) + 1)))
+    return out
+
+
+def call_raw(fn, b, first=()):
+    """the entry `fn` on the scene b with outputs that are large enough for whatever b's job list says, as far as it is readable"""
+    n = 1 << 12
+    table = np.zeros(n, np.uint32); nv = np.zeros(8, np.int32); nh = np.zeros(8, np.int32)
+    return fn(*first, *b.args(), *b.job_args(), fp._p(table), fp._p(nv), fp._p(nh), None, *([None] if not first else []))
+
+
+def test_every_bad_argument_is_refused_by_the_host_evaluator():
+    h = fp._host()
+    for name, b in bad_argument_cases():
+        assert call_raw(h.ccmh_fuse_pose_eval_host, b) == -1, name
+    good = fp.make_scene(3, 20, 10, n_feat=40, seed=2)
+    assert call_raw(h.ccmh_fuse_pose_eval_host, good) == 0
+    nv = np.zeros(4, np.int32); nh = np.zeros(4, np.int32)
+    assert h.ccmh_fuse_pose_eval_host(*good.args(), *good.job_args(), None, fp._p(nv), fp._p(nh), None, None) == -1      # a null table with pairs to write
+    with pytest.raises(CcmError):
+        fp.SearchInNeighborsBatch(None, good, [0, 4], 3, 20)          # a target outside the keyframes
+    with pytest.raises(CcmError):
+        fp.SearchInNeighborsBatch(None, good, [0, 1], 3, 31)          # more current points than points
+
+
+def test_empty_calls_and_a_keyframe_without_features_are_legal():
+    sc = fp.make_scene(3, 20, 10, n_feat=40, seed=2)
+    for kfs, P, jobs in (([], 30, []), ([], 0, []), ([0, 1], 0, []), ([0, 1], 0, [(1, 0, 0)]), ([0, 1], 30, []), ([0], 30, [(0, 30, 0), (0, 0, 0)])):
+        got = fp.fuse_pose_eval_host(sc.subset(kfs, P, jobs))
+        assert got["table"].size == 0 and got["n_valid"].size == len(jobs) and not got["n_valid"].any()
+    pl = planted()
+    got = fp.fuse_pose_eval_host(pl.scene().subset(jobs=[(0, 0, len(pl.pts))]))
+    st = fs.unpack_table(got["table"])["status"]
+    assert (st <= 4).all() and (st == 4).any() and got["n_hit"][0] == 0      # keyframe 0 has no features
+    b = fp.SearchInNeighborsBatch(None, sc.subset([], 0, []), [], None, 0)
+    assert b.table()["table"].size == 0
+    b.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+# the mirror
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+N_PREDICTED = 2300      # of the pool's 2 500 points; the other 200 can only arrive unpredicted
+
+
+def mirror_scene(sc, info):
+    """the scene of the mirror tests: the current keyframe's 2 500 points and the first N_PREDICTED pool points"""
+    return sc.subset(n_pts=info["n1"] + N_PREDICTED, jobs=[])
+
+
+def walk(batch, sc, info, frames, rlib, table):
+    """The 12 Fuse calls of the fan-out, between which the map changes, then the call on the current keyframe.  Of the points a call fuses, every third keeps living
+    with the fused feature's descriptor (one outcome of ComputeDistinctiveDescriptors after Replace), every other third is skipped from then on (it is in the
+    keyframe or bad), and 15 more points turn bad.  Every call must equal the reference's Fuse run with the current descriptors, compared on the points that are
+    not skipped.  table: the stale answers (calls, P1) as evaluated at construction."""
+    rng = np.random.default_rng(77)
+    P = info["n1"]
+    kdesc = frames[0][1]
+    snapshot = sc.pt_desc.reshape(-1, 32)[:P].copy(); now = snapshot.copy()
+    skip = np.zeros(P, np.uint8)
+    t = {n: a.reshape(len(CALLS), P) for n, a in fs.unpack_table(table).items()}
+    n_reeval = 0; changed_seen = []; differs = 0
+    for c, k in enumerate(CALLS):
+        nf, best, valid, _, _, _ = ref_fuse(rlib, frames, sc, info, k, pdesc=now)
+        live = skip == 0
+        changed = (now != snapshot).any(1)
+        n, bi, bd = batch.resolve(c, skip, now)
+        assert np.array_equal(bi[live], best[live]), c
+        assert n == int((best[live] >= 0).sum()), c
+        assert (bi[~live] == -1).all()
+        n_reeval += int((changed & live & (valid > 0)).sum())
+        assert batch.n_reeval() == n_reeval, c
+        changed_seen.append(int((changed & live).sum()))
+        stale = np.where(t["status"][c] == 7, t["idx"][c], -1)
+        differs += int((stale[live] != bi[live]).any())
+        fused = np.flatnonzero(live & (bi >= 0))
+        now[fused[0::3]] = kdesc[bi[fused[0::3]]]
+        skip[fused[1::3]] = 1
+        skip[rng.choice(P, 15, replace=False)] = 1
+    assert sum(x >= 50 for x in changed_seen) >= 2, changed_seen
+    assert differs >= 1
+    # Fuse(mpCurrentKeyFrame, vpFuseCandidates): 1 500 of the predicted candidates in a shuffled order, 60 pool points the build did not predict among them
+    pool = sc.pt_desc.reshape(-1, 32)[P:]
+    cand = np.concatenate([rng.choice(N_PREDICTED, 1500, replace=False), N_PREDICTED + rng.choice(info["n2"] - N_PREDICTED, 60, replace=False)])
+    rng.shuffle(cand)
+    slot = np.where(cand < N_PREDICTED, cand, -1).astype(np.int32)
+    desc_now = pool[cand].copy()
+    turn = rng.choice(cand.size, 200, replace=False)
+    desc_now[turn] = kdesc[rng.integers(0, len(kdesc), turn.size)]        # a Replace gave these points another descriptor
+    skip_c = (rng.random(cand.size) < 0.1).astype(np.uint8)
+    g = P + cand
+    take = lambda a, w: a.reshape(-1, w)[g]
+    fresh = (take(sc.pos, 3), take(sc.normal, 3), take(sc.min_dist, 1), take(sc.max_dist, 1), desc_now)
+    nf, best, valid, _, _, _ = ref_fuse(rlib, frames, sc, info, CURRENT, pts=g, pdesc=desc_now)
+    live = skip_c == 0
+    changed = (desc_now != pool[cand]).any(1)
+    assert int((changed & live & (slot >= 0) & (valid > 0)).sum()) >= 20 and int((live & (slot < 0)).sum()) >= 20
+    before = batch.n_reeval()
+    n, bi, bd = batch.resolve_current(slot, skip_c, desc_now, fresh)
+    assert np.array_equal(bi[live], best[live]) and n == int((best[live] >= 0).sum()) and n > 300
+    assert (bi[~live] == -1).all()
+    assert batch.n_reeval() - before == int((changed & live & (slot >= 0) & (valid > 0)).sum())
+    assert batch.n_unpredicted() == int((live & (slot < 0)).sum())
+
+
+def test_mirror_with_the_host_evaluator_through_the_fan_out_and_the_current_keyframe(frames, scene, rlib):
+    sc, info = scene
+    ms = mirror_scene(sc, info)
+    want = fp.fuse_pose_eval_host(ms.subset(jobs=[(k, 0, info["n1"]) for k in CALLS] + [(CURRENT, info["n1"], N_PREDICTED)]))
+    batch = fp.SearchInNeighborsBatch(None, ms, CALLS, CURRENT, info["n1"])
+    try:
+        tb = batch.table()
+        assert np.array_equal(tb["table"], want["table"]) and np.array_equal(tb["n_hit"], want["n_hit"]) and np.array_equal(tb["n_valid"], want["n_valid"])
+        walk(batch, sc, info, frames, rlib, tb["calls"])
+    finally:
+        batch.close()
