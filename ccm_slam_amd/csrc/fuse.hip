@@ -1,0 +1,271 @@
+// fuse.hip — the two batched Fuse stages, one launch each.
+//   ccm_fuse_sim3_eval: every (keyframe, point) pair of a SearchAndFuse (cslam/src/LoopFinder.cpp:709-734, MapMerger.cpp:574-598).  A pair is one call of the loop
+//     body of ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (ORBmatcher.cpp:1030-1118) up to the decision, without the map mutations.
+//   ccm_fuse_pose_eval: every Fuse call of a LocalMapping::SearchInNeighbors (cslam/src/Mapping.cpp:471-547), both directions.  A pair is one pass of the loop body
+//     of ORBmatcher::Fuse(pKF, vpMapPoints, th) (ORBmatcher.cpp:883-965) up to the decision, without the skips and the map mutations.
+// The lines of a pair are fuse_math.h; the two forms differ in the chi-square gate of the candidate (kChi2) and in how a workgroup finds its work.
+//
+// Layout.  fuse_sim3_kernel: the grid is (tiles of 256 points) x K keyframes, folded into one dimension.  fuse_pose_kernel: the work is a list
+// of jobs, job j = keyframe job_kf[j] x points job_pt0[j] .. + job_n[j]; one workgroup takes a tile of 256 pairs of ONE job, and the stage writes (job, first pair)
+// per workgroup while it validates the job arrays, so the kernel's first read is tile[blockIdx.x].  Either way a workgroup has one keyframe, so the keyframe's
+// record, pose and offsets are addressed by workgroup-uniform values and loaded once per wave, and from there both kernels are fuse_pair: one lane per pair runs
+// the gates.  A lane that passes them reads its cell range from the keyframe's CSR grid and walks its candidates alone: the query descriptor in 8 registers, a
+// candidate two 16-byte loads, xor and popcount.  A window whose cells hold more than FSM_WIDE features is handed to the whole wave, one after the other (as
+// kfcull_eval_kernel hands long observer lists over): the candidates of each grid column strided over the lanes, the minimum of dist << 16 | CSR position taken
+// through lane_xor.h.  The switch is the feature count read from cell_off.  n_valid / n_hit: ballot popcounts per wave, one integer atomicAdd each.  No float
+// atomics, no lane leaves early, nothing waits on another workgroup, every loop is bounded by a count read from the inputs (validated on the host before the launch).
+#include "common.h"
+#include "fuse_math.h"
+#include "lane_xor.h"
+#include "stage_blocks.h"
+#include <chrono>
+#include <cstdio>
+
+namespace {
+
+static_assert(FPM_TILE == 256, "both kernels run 256 lanes, one per pair");
+
+// everything either kernel reads.  P, tiles: the Sim3 form's grid; job, tile, inv_sigma2: the pose form's
+struct FuseArgs {
+  int P, tiles, nlevels;
+  float th, logsf;
+  const float *rec, *pose, *kxy, *scale_factors, *inv_sigma2, *pos, *normal, *dmin, *dmax;
+  const int32_t *feat_off, *cell_off, *job, *tile;
+  const uint16_t* cell_idx;
+  const uint8_t *koct, *kdesc, *pdesc;
+  uint32_t* table;
+  int32_t *n_valid, *n_hit;
+  float* uv;   // nullptr: not asked for
+};
+
+// the minimum of a 32-bit key over the wave; a u32 is exact in a double, so lane_xor.h's f64 exchange carries it
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t key) {
+  double v = (double)key;
+  v = fmin(v, lanex::from_partner<32>(v)); v = fmin(v, lanex::from_partner<16>(v)); v = fmin(v, lanex::from_partner<8>(v));
+  v = fmin(v, lanex::from_partner<4>(v)); v = fmin(v, lanex::from_partner<2>(v)); v = fmin(v, lanex::from_partner<1>(v));
+  return (uint32_t)v;
+}
+
+// One pair per lane: keyframe k (workgroup-uniform) x point i, answered into table[out] (and uv) and counted into n_valid / n_hit[counter] (workgroup-uniform).
+// A dead lane (!live) reads nothing through i and writes nothing, but stays for the wave-wide part, which needs all 64.
+template <bool kChi2>
+__device__ __forceinline__ void fuse_pair(const FuseArgs& a, int k, int i, bool live, uint32_t out, int counter) {
+  const int lane = threadIdx.x & 63;
+  const float* rec = a.rec + (size_t)k * FSM_REC_FLOATS;
+  const float* pose = a.pose + (size_t)k * FSM_POSE_FLOATS;
+  const int32_t f0 = a.feat_off[k];
+  const int32_t* cell_off = a.cell_off + (size_t)k * (FSM_CELLS + 1);
+  const uint16_t* cell_idx = a.cell_idx + f0;
+  const float* kxy = a.kxy + 2 * (size_t)f0;
+  const uint8_t* koct = a.koct + f0;
+  const uint8_t* kdesc = a.kdesc + 32 * (size_t)f0;
+
+  int status = FSM_BEHIND, level = 0;
+  float u = 0.0f, v = 0.0f, r = 0.0f;
+  int x0 = 0, x1 = -1, y0 = 0, y1 = 0;
+  uint32_t word = fsm_pack(FSM_BEHIND, 0, FSM_NO_DIST, FSM_NO_IDX);
+  bool wide = false;
+  if (live) {
+    const float P3[3] = {a.pos[3 * (size_t)i], a.pos[3 * (size_t)i + 1], a.pos[3 * (size_t)i + 2]};
+    const float Pn[3] = {a.normal[3 * (size_t)i], a.normal[3 * (size_t)i + 1], a.normal[3 * (size_t)i + 2]};
+    status = fsm_gate(rec, pose, P3, Pn, a.dmin[i], a.dmax[i], a.nlevels, a.logsf, u, v, level);
+    word = fsm_pack(status, 0, FSM_NO_DIST, FSM_NO_IDX);
+    if (status == FSM_EMPTY) {
+      r = a.th * a.scale_factors[level];
+      bool any = false;
+      uint32_t key = ~0u;
+      if (fsm_cell_range(rec, u, v, r, x0, x1, y0, y1)) {
+        if (fsm_window_count(cell_off, x0, x1, y0, y1) > FSM_WIDE) {
+          wide = true;
+        } else {
+          uint32_t q[8];
+          fsm_load_desc(a.pdesc + 32 * (size_t)i, q);
+          for (int ix = x0; ix <= x1; ix++) {
+            const int32_t c0 = cell_off[ix * FSM_GRID_ROWS + y0], c1 = cell_off[ix * FSM_GRID_ROWS + y1 + 1];
+            for (int32_t p = c0; p < c1; p++) {
+              bool in;
+              const int d = fsm_candidate<kChi2>(kxy, koct, kdesc, cell_idx[p], u, v, r, level, a.inv_sigma2, q, in);
+              any |= in;
+              if (d >= 0) key = min(key, ((uint32_t)d << 16) | (uint32_t)p);
+            }
+          }
+        }
+      }
+      if (!wide) word = fsm_finish(level, any, key, cell_idx);
+    }
+  }
+  // the wide windows: the wave takes them one by one
+  unsigned long long todo = __ballot(wide);
+  while (todo) {
+    const int src = __ffsll((long long)todo) - 1;
+    todo &= todo - 1;
+    const int si = __shfl(i, src, 64), sl = __shfl(level, src, 64);
+    const float su = __shfl(u, src, 64), sv = __shfl(v, src, 64), sr = __shfl(r, src, 64);
+    const int sx0 = __shfl(x0, src, 64), sx1 = __shfl(x1, src, 64), sy0 = __shfl(y0, src, 64), sy1 = __shfl(y1, src, 64);
+    uint32_t q[8];
+    fsm_load_desc(a.pdesc + 32 * (size_t)si, q);
+    bool any = false;
+    uint32_t key = ~0u;
+    for (int ix = sx0; ix <= sx1; ix++) {
+      const int32_t c0 = cell_off[ix * FSM_GRID_ROWS + sy0], c1 = cell_off[ix * FSM_GRID_ROWS + sy1 + 1];
+      for (int32_t p = c0 + lane; p < c1; p += 64) {
+        bool in;
+        const int d = fsm_candidate<kChi2>(kxy, koct, kdesc, cell_idx[p], su, sv, sr, sl, a.inv_sigma2, q, in);
+        any |= in;
+        if (d >= 0) key = min(key, ((uint32_t)d << 16) | (uint32_t)p);
+      }
+    }
+    any = __ballot(any) != 0;
+    key = wave_min_u32(key);
+    if (lane == src) word = fsm_finish(level, any, key, cell_idx);
+  }
+  if (live) {
+    a.table[out] = word;
+    if (a.uv) { a.uv[2 * (size_t)out] = u; a.uv[2 * (size_t)out + 1] = v; }
+  }
+  const int st = (int)(word >> 29);
+  const int nv = (int)__popcll(__ballot(live && st >= FSM_EMPTY)), nh = (int)__popcll(__ballot(live && st == FSM_HIT));
+  if (lane == 0) {
+    if (nv) atomicAdd(&a.n_valid[counter], nv);
+    if (nh) atomicAdd(&a.n_hit[counter], nh);
+  }
+}
+
+// workgroup = (keyframe k, tile of 256 points): word k * P + i (K * P <= INT32_MAX), the counters are the keyframe's
+__global__ __launch_bounds__(FPM_TILE) void fuse_sim3_kernel(FuseArgs a) {
+  const int k = (int)(blockIdx.x / (unsigned)a.tiles), tile = (int)(blockIdx.x % (unsigned)a.tiles);
+  const int i = tile * FPM_TILE + (int)threadIdx.x;
+  fuse_pair<false>(a, k, i, i < a.P, (uint32_t)k * (uint32_t)a.P + (uint32_t)i, k);
+}
+
+// workgroup = tile[blockIdx.x] = (job j, first pair of the job): the job's words start at its out0, the counters are the job's
+__global__ __launch_bounds__(FPM_TILE) void fuse_pose_kernel(FuseArgs a) {
+  const int j = a.tile[2 * (size_t)blockIdx.x], i0 = a.tile[2 * (size_t)blockIdx.x + 1];
+  const int32_t* jr = a.job + FPM_JOB_INTS * (size_t)j;
+  const int k = jr[0], pt0 = jr[1], n = jr[2], out0 = jr[3];
+  const int e = i0 + (int)threadIdx.x;   // the pair's place in the job
+  const bool live = e < n;
+  fuse_pair<true>(a, k, live ? pt0 + e : pt0, live, (uint32_t)out0 + (uint32_t)e, j);
+}
+
+typedef std::chrono::steady_clock Clock;
+double us_between(Clock::time_point x, Clock::time_point y) { return std::chrono::duration<double, std::micro>(y - x).count(); }
+
+// The host side of the upload for the segments FuseSim3Block and FusePoseBlock have in common (same member names), and the kernels' view of the block.  What is a
+// stage's own (pose; job, tile and inv_sigma2) the entry point writes itself.
+template <class Block>
+FuseArgs fuse_stage_inputs(const Block& b, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
+                           const int32_t* cell_off, const int32_t* cell_idx, int nlevels, const float* scale_factors, float logScaleFactor, float th, const float* pos,
+                           const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc) {
+  b.put(b.kdesc, feat_desc); b.put(b.pdesc, pt_desc); b.put(b.rec, kf_rec);
+  b.put(b.feat_off, feat_off); b.put(b.cell_off, cell_off); b.put(b.kxy, feat_xy);
+  uint16_t* h_idx = b.up(b.cell_idx);
+  for (size_t f = 0; f < b.cell_idx.count; f++) h_idx[f] = (uint16_t)cell_idx[f];
+  b.put(b.koct, feat_octave); b.put(b.scale_factors, scale_factors);
+  b.put(b.pos, pos); b.put(b.normal, normal); b.put(b.dmin, min_dist); b.put(b.dmax, max_dist);
+  FuseArgs a = {};
+  a.nlevels = nlevels; a.th = th; a.logsf = logScaleFactor;
+  a.rec = b.dev(b.rec); a.pose = b.dev(b.pose); a.kxy = b.dev(b.kxy); a.scale_factors = b.dev(b.scale_factors);
+  a.pos = b.dev(b.pos); a.normal = b.dev(b.normal); a.dmin = b.dev(b.dmin); a.dmax = b.dev(b.dmax);
+  a.feat_off = b.dev(b.feat_off); a.cell_off = b.dev(b.cell_off); a.cell_idx = b.dev(b.cell_idx);
+  a.koct = b.dev(b.koct); a.kdesc = b.dev(b.kdesc); a.pdesc = b.dev(b.pdesc);
+  a.table = b.dev(b.table); a.n_valid = b.dev(b.n_valid); a.n_hit = b.dev(b.n_hit);
+  a.uv = b.uv.count ? b.dev(b.uv) : nullptr;
+  return a;
+}
+
+// after the launch: the download and the caller's outputs.  Returns when the device was done through *t2.
+template <class Block>
+int fuse_stage_outputs(ccm_ctx* ctx, const Block& b, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv, Clock::time_point* t2) {
+  CCM_HIP_CHECK(ctx, hipGetLastError());
+  if (int rc = ccm_staged_download(ctx, b)) return rc;
+  *t2 = Clock::now();
+  b.get(b.n_valid, n_valid); b.get(b.n_hit, n_hit); b.get(b.table, table);
+  if (uv) b.get(b.uv, uv);
+  return CCM_OK;
+}
+
+}  // namespace
+
+extern "C" int ccm_fuse_sim3_eval(ccm_ctx* ctx, int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave,
+                                  const uint8_t* feat_desc, const int32_t* cell_off, const int32_t* cell_idx, const float* Scw, int nlevels,
+                                  const float* scale_factors, float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist,
+                                  const float* max_dist, const uint8_t* pt_desc, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv) {
+  if (!ctx) return CCM_E_ARG;
+  const char* const me = "ccm_fuse_sim3_eval: ";
+  if (const char* why = fsm_check_args(K, P, feat_off, cell_off, cell_idx, nlevels, th)) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + why);
+  const size_t F = K ? (size_t)feat_off[K] : 0;
+  if (!scale_factors || (K > 0 && (!kf_rec || !Scw || !n_valid || !n_hit)) || (P > 0 && (!pos || !normal || !min_dist || !max_dist || !pt_desc)) ||
+      (K > 0 && P > 0 && !table) || (F && (!feat_xy || !feat_octave || !feat_desc)))
+    return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + "null pointers");
+  for (int k = 0; k < K; k++) n_valid[k] = n_hit[k] = 0;
+  if (K == 0 || P == 0) return CCM_OK;
+  FuseSim3Block b((size_t)K, F, (size_t)P, (size_t)nlevels, uv != nullptr);
+  if (int rc = ccm_staged_begin(ctx, b, me)) return rc;
+  // CCM_DBG=fuse: the call's three host phases on stderr (scripts/fuse_sim3_profile.py reads them); the clock is read whether or not they are printed
+  const Clock::time_point t0 = Clock::now();
+  FuseArgs a = fuse_stage_inputs(b, kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off, cell_idx, nlevels, scale_factors, logScaleFactor, th, pos, normal,
+                                 min_dist, max_dist, pt_desc);
+  float* h_pose = b.up(b.pose);
+  for (int k = 0; k < K; k++) fsm_decompose_scw(Scw + 12 * (size_t)k, h_pose + FSM_POSE_FLOATS * (size_t)k);
+  const Clock::time_point t1 = Clock::now();
+  if (int rc = ccm_staged_upload(ctx, b)) return rc;
+  a.P = P; a.tiles = (P + FPM_TILE - 1) / FPM_TILE;
+  // K * tiles <= K * P + K workgroups: K * P <= INT32_MAX holds, and so does the grid limit for every K and P a map has
+  const uint64_t groups = (uint64_t)K * (uint64_t)a.tiles;
+  if (groups > (uint64_t)INT32_MAX) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + "too many workgroups");
+  hipLaunchKernelGGL(fuse_sim3_kernel, dim3((unsigned)groups), dim3(FPM_TILE), 0, ctx->stream, a);
+  Clock::time_point t2;
+  if (int rc = fuse_stage_outputs(ctx, b, table, n_valid, n_hit, uv, &t2)) return rc;
+  if (ccm_dbg("fuse"))
+    fprintf(stderr, "[fuse] K=%d P=%d pack_us=%.1f device_us=%.1f unpack_us=%.1f up_bytes=%zu down_bytes=%zu\n", K, P, us_between(t0, t1), us_between(t1, t2),
+            us_between(t2, Clock::now()), b.up_bytes(), b.down_bytes());
+  return CCM_OK;
+}
+
+extern "C" int ccm_fuse_pose_eval(ccm_ctx* ctx, int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave,
+                                  const uint8_t* feat_desc, const int32_t* cell_off, const int32_t* cell_idx, const float* pose, int nlevels,
+                                  const float* scale_factors, const float* inv_level_sigma2, float logScaleFactor, float th, int P, const float* pos,
+                                  const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc, int J, const int32_t* job_kf,
+                                  const int32_t* job_pt0, const int32_t* job_n, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv) {
+  if (!ctx) return CCM_E_ARG;
+  const char* const me = "ccm_fuse_pose_eval: ";
+  if (const char* why = fsm_check_args(K, P, feat_off, cell_off, cell_idx, nlevels, th)) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + why);
+  int64_t total = 0, tiles = 0;
+  if (const char* why = fpm_check_jobs(J, K, P, job_kf, job_pt0, job_n, &total, &tiles)) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + why);
+  const size_t F = K ? (size_t)feat_off[K] : 0;
+  if (!scale_factors || !inv_level_sigma2 || (K > 0 && (!kf_rec || !pose)) || (J > 0 && (!n_valid || !n_hit)) ||
+      (P > 0 && (!pos || !normal || !min_dist || !max_dist || !pt_desc)) || (total > 0 && !table) || (F && (!feat_xy || !feat_octave || !feat_desc)))
+    return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + "null pointers");
+  for (int j = 0; j < J; j++) n_valid[j] = n_hit[j] = 0;
+  if (total == 0) return CCM_OK;
+  FusePoseBlock b((size_t)K, F, (size_t)P, (size_t)nlevels, (size_t)J, (size_t)tiles, (size_t)total, uv != nullptr);
+  if (int rc = ccm_staged_begin(ctx, b, me)) return rc;
+  // CCM_DBG=fuse: the call's three host phases on stderr (scripts/fuse_pose_profile.py reads them); the clock is read whether or not they are printed
+  const Clock::time_point t0 = Clock::now();
+  FuseArgs a = fuse_stage_inputs(b, kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off, cell_idx, nlevels, scale_factors, logScaleFactor, th, pos, normal,
+                                 min_dist, max_dist, pt_desc);
+  b.put(b.pose, pose); b.put(b.inv_sigma2, inv_level_sigma2);
+  int32_t* h_job = b.up(b.job);
+  int32_t* h_tile = b.up(b.tile);
+  {
+    int32_t out0 = 0;
+    size_t t = 0;
+    for (int j = 0; j < J; j++) {
+      h_job[FPM_JOB_INTS * (size_t)j] = job_kf[j]; h_job[FPM_JOB_INTS * (size_t)j + 1] = job_pt0[j];
+      h_job[FPM_JOB_INTS * (size_t)j + 2] = job_n[j]; h_job[FPM_JOB_INTS * (size_t)j + 3] = out0;
+      for (int32_t e = 0; e < job_n[j]; e += FPM_TILE, t++) { h_tile[2 * t] = j; h_tile[2 * t + 1] = e; }
+      out0 += job_n[j];
+    }
+  }
+  const Clock::time_point t1 = Clock::now();
+  if (int rc = ccm_staged_upload(ctx, b)) return rc;
+  a.inv_sigma2 = b.dev(b.inv_sigma2); a.job = b.dev(b.job); a.tile = b.dev(b.tile);
+  hipLaunchKernelGGL(fuse_pose_kernel, dim3((unsigned)tiles), dim3(FPM_TILE), 0, ctx->stream, a);
+  Clock::time_point t2;
+  if (int rc = fuse_stage_outputs(ctx, b, table, n_valid, n_hit, uv, &t2)) return rc;
+  if (ccm_dbg("fuse"))
+    fprintf(stderr, "[fuse_pose] K=%d P=%d J=%d pairs=%lld pack_us=%.1f device_us=%.1f unpack_us=%.1f up_bytes=%zu down_bytes=%zu\n", K, P, J, (long long)total,
+            us_between(t0, t1), us_between(t1, t2), us_between(t2, Clock::now()), b.up_bytes(), b.down_bytes());
+  return CCM_OK;
+}

@@ -1,6 +1,9 @@
-// fuse_sim3_math.h — one (keyframe, point) pair of ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (cslam/src/ORBmatcher.cpp:995-1122), host + device:
-// the Sim3 decomposition, the projection and its four gates, MapPoint::PredictScale, the window of KeyFrame::GetFeaturesInArea and the Hamming arg-min.
-// The kernel of fuse_sim3.hip runs these lines; cslam::SearchAndFuseBatch (host/ccm_host.cpp) compiles them with g++.
+// fuse_math.h — one (keyframe, point) pair of ORBmatcher::Fuse, host + device, in both of its forms: Fuse(pKF, Scw, vpPoints, th, vpReplacePoint)
+// (cslam/src/ORBmatcher.cpp:995-1122, the Sim3 form) and Fuse(pKF, vpMapPoints, th) (:854-993, the pose form).  The Sim3 decomposition, the projection and its four
+// gates, MapPoint::PredictScale, the window of KeyFrame::GetFeaturesInArea and the Hamming arg-min.  The two forms differ in the candidate loop alone: the pose form
+// has a chi-square gate (:941-955) where the Sim3 form has none, so the candidate and the window walk are templates on `bool kChi2` (fsm_gate takes Rcw, tcw and Ow
+// in both forms).  The argument rules of the two entry points follow.
+// The kernels of fuse.hip run these lines; cslam::SearchAndFuseBatch and cslam::SearchInNeighborsBatch (host/ccm_host.cpp) compile them with g++.
 //
 // Every cv::Mat expression is evaluated as OpenCV 4.2 does in a baseline build (no FMA), by the rules oracle/ref_shim/opencv2/mini_cv.h declares
 // (gemm_eval, Mat::dot, norm, Mat / s); DESIGN.md §19 lists them.  Compile with -ffp-contract=off: no product may fuse into an FMA.
@@ -36,6 +39,9 @@ enum {
 #define FSM_REC_FLOATS 10     // fx fy cx cy, mnMinX mnMinY mnMaxX mnMaxY (the floats of the ints), mfGridElementWidthInv, mfGridElementHeightInv
 #define FSM_POSE_FLOATS 15    // Rcw (9, row-major), tcw (3), Ow (3)
 #define FSM_WIDE 64           // a window whose cells hold more features than this is the whole wave's
+#define FPM_CHI2 5.99         // ORBmatcher.cpp:950, a double literal
+#define FPM_JOB_INTS 4        // a job's record in the staged block: keyframe, first point, points, first table word
+#define FPM_TILE 256          // pairs per workgroup
 
 FSM_HD uint32_t fsm_pack(int status, int level, uint32_t dist, uint32_t idx) {
   return ((uint32_t)status << 29) | ((uint32_t)level << 25) | (dist << 16) | idx;
@@ -131,12 +137,25 @@ FSM_HD int fsm_hamming(const uint32_t a[8], const uint32_t b[8]) {   // ORBmatch
 
 // One candidate of the window: feature f of the keyframe (xy, octave, descriptor of ITS arrays).  in_window: the feature is one of vIndices (KeyFrame.cpp:1190-1195).
 // Returns its distance, or -1 when it is not in the window or not at the level (ORBmatcher.cpp:1089).
-FSM_HD int fsm_candidate(const float* xy, const uint8_t* oct, const uint8_t* desc, int f, float u, float v, float r, int level, const uint32_t q[8], bool& in_window) {
-  const float distx = xy[2 * f] - u, disty = xy[2 * f + 1] - v;
+// kChi2: the pose form, in the order of ORBmatcher.cpp:941-955: the level filter, ex / ey / e2 in f32 (two products and one sum, never fused), the gate
+// `e2 * mvInvLevelSigma2[kpLevel] > 5.99` (an f32 product widened to double for the comparison, so a NaN passes as it does there), then the distance.
+// o <= level < nlevels bounds the read of inv_sigma2, which the Sim3 form does not read.
+template <bool kChi2>
+FSM_HD int fsm_candidate(const float* xy, const uint8_t* oct, const uint8_t* desc, int f, float u, float v, float r, int level, const float* inv_sigma2,
+                         const uint32_t q[8], bool& in_window) {
+  const float kpx = xy[2 * f], kpy = xy[2 * f + 1];
+  const float distx = kpx - u, disty = kpy - v;
   in_window = fabsf(distx) < r && fabsf(disty) < r;
   if (!in_window) return -1;
   const int o = oct[f];
   if (o < level - 1 || o > level) return -1;
+  if (kChi2) {
+    const float ex = u - kpx, ey = v - kpy;
+    const float exx = ex * ex, eyy = ey * ey;
+    const float e2 = exx + eyy;
+    const float g = e2 * inv_sigma2[o];
+    if ((double)g > FPM_CHI2) return -1;
+  }
   uint32_t d[8];
   fsm_load_desc(desc + 32 * (size_t)f, d);
   return fsm_hamming(q, d);
@@ -157,10 +176,13 @@ FSM_HD uint32_t fsm_finish(int level, bool any, uint32_t key, const uint16_t* ce
   return fsm_pack(dist <= FSM_TH_LOW ? FSM_HIT : FSM_FAR, level, dist, idx);
 }
 
-// ORBmatcher.cpp:1071-1118 for one pair, one candidate after the other in the reference's order: ix, then iy, then the position in the cell — ascending CSR
-// position, so the first strict minimum is the lowest position among the minima.  All arrays are the keyframe's own (cell_idx: local feature indices).
+// ORBmatcher.cpp:1071-1118 (kChi2: :920-989) for one pair that passed the gates, one candidate after the other in the reference's order: ix, then iy, then the
+// position in the cell — ascending CSR position, so the first strict minimum is the lowest position among the minima.  All arrays are the keyframe's own (cell_idx:
+// local feature indices).  n_cand (nullable): the size of vIndices.
+template <bool kChi2>
 FSM_HD uint32_t fsm_window_best(const float rec[FSM_REC_FLOATS], const int32_t* cell_off, const uint16_t* cell_idx, const float* xy, const uint8_t* oct,
-                                const uint8_t* desc, float u, float v, int level, float th, const float* scale_factors, const uint32_t q[8], int* n_cand) {
+                                const uint8_t* desc, float u, float v, int level, float th, const float* scale_factors, const float* inv_sigma2, const uint32_t q[8],
+                                int* n_cand) {
   const float r = th * scale_factors[level];
   int x0, x1, y0, y1;
   bool any = false;
@@ -171,7 +193,7 @@ FSM_HD uint32_t fsm_window_best(const float rec[FSM_REC_FLOATS], const int32_t* 
       const int a = cell_off[ix * FSM_GRID_ROWS + y0], b = cell_off[ix * FSM_GRID_ROWS + y1 + 1];
       for (int pos = a; pos < b; pos++) {
         bool in;
-        const int d = fsm_candidate(xy, oct, desc, cell_idx[pos], u, v, r, level, q, in);
+        const int d = fsm_candidate<kChi2>(xy, oct, desc, cell_idx[pos], u, v, r, level, inv_sigma2, q, in);
         any |= in; n += in;
         if (d >= 0) { const uint32_t k = ((uint32_t)d << 16) | (uint32_t)pos; if (k < key) key = k; }   // pos ascends: an equal distance later is no less
       }
@@ -204,5 +226,25 @@ FSM_HD const char* fsm_check_args(int K, int P, const int32_t* feat_off, const i
     for (int64_t j = 0; j < n; j++)
       if (ci[j] < 0 || ci[j] >= n) return "cell_idx out of range";
   }
+  return nullptr;
+}
+
+// The argument rules of ccm_fuse_pose_eval's job arrays; nullptr, or what is wrong.  total: the table's words, the sum of job_n; tiles: the workgroups.
+FSM_HD const char* fpm_check_jobs(int J, int K, int P, const int32_t* job_kf, const int32_t* job_pt0, const int32_t* job_n, int64_t* total, int64_t* tiles) {
+  *total = 0; *tiles = 0;
+  if (J < 0) return "J negative";
+  if (J == 0) return nullptr;
+  if (!job_kf || !job_pt0 || !job_n) return "null job arrays";
+  int64_t sum = 0, t = 0;
+  for (int j = 0; j < J; j++) {
+    if (job_kf[j] < 0 || job_kf[j] >= K) return "job_kf outside the keyframes";
+    if (job_n[j] < 0 || job_pt0[j] < 0) return "a negative job_n or job_pt0";
+    if ((int64_t)job_pt0[j] + (int64_t)job_n[j] > (int64_t)P) return "a job's points end beyond P";
+    sum += job_n[j];
+    t += ((int64_t)job_n[j] + FPM_TILE - 1) / FPM_TILE;
+    if (sum > (int64_t)INT32_MAX) return "more than INT32_MAX pairs";
+  }
+  if (t > (int64_t)INT32_MAX) return "too many workgroups";
+  *total = sum; *tiles = t;
   return nullptr;
 }

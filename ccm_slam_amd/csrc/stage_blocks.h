@@ -3,8 +3,7 @@
 #pragma once
 #include "staged_block.h"
 #include "triangulate_math.h"
-#include "fuse_sim3_math.h"
-#include "fuse_pose_math.h"
+#include "fuse_math.h"
 
 // ccm_sim3_ransac_eval: the inputs, then the outputs.
 struct Sim3RansacBlock : StagedBlock {

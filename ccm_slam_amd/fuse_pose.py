@@ -155,7 +155,7 @@ def fuse_pose_eval(ctx: Context, s: Scene, want_uv: bool = False) -> dict:
 
 
 def fuse_pose_eval_host(s: Scene, want_uv: bool = False, want_cand: bool = False) -> dict:
-    """The same through csrc/fuse_pose_math.h on the calling thread; n_cand = the size of vIndices per pair when asked for"""
+    """The same through csrc/fuse_math.h on the calling thread; n_cand = the size of vIndices per pair when asked for"""
     table, nv, nh, uv = _outputs(s, want_uv)
     nc = np.zeros(table.size, np.int32) if want_cand else None
     if _host().ccmh_fuse_pose_eval_host(*s.args(), *s.job_args(), _p(table), _p(nv), _p(nh), _p(uv), _p(nc)) != 0:

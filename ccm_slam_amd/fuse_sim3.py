@@ -171,7 +171,7 @@ def fuse_sim3_eval(ctx: Context, s: Scene, want_uv: bool = False) -> dict:
 
 
 def fuse_sim3_eval_host(s: Scene, want_uv: bool = False, want_cand: bool = False) -> dict:
-    """The same through csrc/fuse_sim3_math.h on the calling thread; n_cand (K, P) = the size of vIndices per pair when asked for"""
+    """The same through csrc/fuse_math.h on the calling thread; n_cand (K, P) = the size of vIndices per pair when asked for"""
     table, nv, nh, uv = _outputs(s, want_uv)
     nc = np.zeros(s.K * s.P, np.int32) if want_cand else None
     if _host().ccmh_fuse_sim3_eval_host(*s.args(), _p(table), _p(nv), _p(nh), _p(uv), _p(nc)) != 0:

@@ -8,8 +8,7 @@
 #include "../csrc/gba_apply_math.h"
 #include "../csrc/covis_math.h"
 #include "../csrc/kfcull_math.h"
-#include "../csrc/fuse_sim3_math.h"
-#include "../csrc/fuse_pose_math.h"
+#include "../csrc/fuse_math.h"
 #include <climits>
 #include <algorithm>
 #include <cmath>
@@ -1739,11 +1738,12 @@ std::vector<int32_t> KeyFrameCullingBatch::pointsGone() const {
   return v;
 }
 
-// ---- SearchAndFuseBatch -------------------------------------------------------------------------------
-// one (keyframe, point) pair through csrc/fuse_sim3_math.h; all keyframe arrays are that keyframe's own
-static uint32_t fsm_pair_host(const float* rec, const float* pose, const int32_t* cell_off, const uint16_t* cell_idx, const float* kxy, const uint8_t* koct,
-                              const uint8_t* kdesc, const float* P3, const float* Pn, float dmin, float dmax, const uint8_t* pdesc, int nlevels, float logsf, float th,
-                              const float* sf, float* uv, int32_t* n_cand) {
+// ---- SearchAndFuseBatch, SearchInNeighborsBatch -------------------------------------------------------
+// one (keyframe, point) pair through csrc/fuse_math.h; all keyframe arrays are that keyframe's own.  kChi2: the pose form with its chi-square gate, which reads isig
+template <bool kChi2>
+static uint32_t fuse_pair_host(const float* rec, const float* pose, const int32_t* cell_off, const uint16_t* cell_idx, const float* kxy, const uint8_t* koct,
+                               const uint8_t* kdesc, const float* P3, const float* Pn, float dmin, float dmax, const uint8_t* pdesc, int nlevels, float logsf, float th,
+                               const float* sf, const float* isig, float* uv, int32_t* n_cand) {
   float u, v; int level;
   const int st = fsm_gate(rec, pose, P3, Pn, dmin, dmax, nlevels, logsf, u, v, level);
   if (uv) { uv[0] = u; uv[1] = v; }
@@ -1752,9 +1752,74 @@ static uint32_t fsm_pair_host(const float* rec, const float* pose, const int32_t
   uint32_t q[8];
   fsm_load_desc(pdesc, q);
   int n = 0;
-  const uint32_t w = fsm_window_best(rec, cell_off, cell_idx, kxy, koct, kdesc, u, v, level, th, sf, q, &n);
+  const uint32_t w = fsm_window_best<kChi2>(rec, cell_off, cell_idx, kxy, koct, kdesc, u, v, level, th, sf, isig, q, &n);
   if (n_cand) *n_cand = n;
   return w;
+}
+
+// every pair of a list of jobs (keyframe job_kf[j] x points job_pt0[j] .. + job_n[j]), the jobs' words one after the other; the arguments are valid.
+// pose: 15 floats per keyframe
+template <bool kChi2>
+static void fuse_jobs_host(const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
+                           const int32_t* cell_off, const int32_t* cell_idx, const float* pose, int nlevels, const float* scale_factors, const float* inv_level_sigma2,
+                           float logScaleFactor, float th, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc,
+                           int J, const int32_t* job_kf, const int32_t* job_pt0, const int32_t* job_n, size_t F, uint32_t* table, int32_t* n_valid, int32_t* n_hit,
+                           float* uv, int32_t* n_cand) {
+  std::vector<uint16_t> idx16(F);
+  for (size_t f = 0; f < F; f++) idx16[f] = (uint16_t)cell_idx[f];
+  size_t e = 0;
+  for (int j = 0; j < J; j++) {
+    n_valid[j] = n_hit[j] = 0;
+    const int k = job_kf[j];
+    const int32_t f0 = feat_off[k];
+    for (int i = job_pt0[j]; i < job_pt0[j] + job_n[j]; i++, e++) {
+      const uint32_t w = fuse_pair_host<kChi2>(kf_rec + FSM_REC_FLOATS * (size_t)k, pose + FSM_POSE_FLOATS * (size_t)k, cell_off + (size_t)k * (FSM_CELLS + 1),
+                                               idx16.data() + f0, feat_xy + 2 * (size_t)f0, feat_octave + f0, feat_desc + 32 * (size_t)f0, pos + 3 * (size_t)i,
+                                               normal + 3 * (size_t)i, min_dist[i], max_dist[i], pt_desc + 32 * (size_t)i, nlevels, logScaleFactor, th, scale_factors,
+                                               inv_level_sigma2, uv ? uv + 2 * e : nullptr, n_cand ? n_cand + e : nullptr);
+      table[e] = w;
+      n_valid[j] += (w >> 29) >= FSM_EMPTY;
+      n_hit[j] += (w >> 29) == FSM_HIT;
+    }
+  }
+}
+
+// a packed answer as a Fuse call leaves bestIdx / bestDist (untouched where the pair has no candidate)
+static inline void sin_answer(uint32_t w, int32_t& bestIdx, int32_t& bestDist, int& nFused) {
+  const int st = (int)(w >> 29);
+  if (st >= FSM_FAR) bestDist = (int32_t)((w >> 16) & 0x1FFu);
+  if (st == FSM_HIT) { bestIdx = (int32_t)(w & 0xFFFFu); nFused++; }
+}
+
+template <class KFs, class Pts>
+void FuseScene::copy(const KFs& kfs, const float* pose15, const Pts& pts, int nlevels_, const float* scale_factors, const float* inv_level_sigma2, float logScaleFactor,
+                     float th_) {
+  nlevels = nlevels_; logsf = logScaleFactor; th = th_;
+  sf.assign(scale_factors, scale_factors + nlevels);
+  if (inv_level_sigma2) isig.assign(inv_level_sigma2, inv_level_sigma2 + nlevels);
+  const int K = kfs.K, P = pts.P;
+  if (K > 0) {
+    const size_t F = (size_t)kfs.feat_off[K];
+    rec.assign(kfs.rec, kfs.rec + FSM_REC_FLOATS * (size_t)K);
+    pose.assign(pose15, pose15 + FSM_POSE_FLOATS * (size_t)K);
+    feat_off.assign(kfs.feat_off, kfs.feat_off + K + 1);
+    cell_off.assign(kfs.cell_off, kfs.cell_off + (size_t)K * (FSM_CELLS + 1));
+    cell_idx.resize(F);
+    for (size_t f = 0; f < F; f++) cell_idx[f] = (uint16_t)kfs.cell_idx[f];
+    if (F) { kxy.assign(kfs.feat_xy, kfs.feat_xy + 2 * F); koct.assign(kfs.feat_octave, kfs.feat_octave + F); kdesc.assign(kfs.feat_desc, kfs.feat_desc + 32 * F); }
+  }
+  if (P > 0) {
+    pos.assign(pts.pos, pts.pos + 3 * (size_t)P); normal.assign(pts.normal, pts.normal + 3 * (size_t)P);
+    dmin.assign(pts.min_dist, pts.min_dist + P); dmax.assign(pts.max_dist, pts.max_dist + P);
+    pdesc.assign(pts.desc, pts.desc + 32 * (size_t)P);
+  }
+}
+
+uint32_t FuseScene::eval(int k, const float* P3, const float* Pn, float dmin_, float dmax_, const uint8_t* desc) const {
+  const int32_t f0 = feat_off[k];
+  return (isig.empty() ? fuse_pair_host<false> : fuse_pair_host<true>)(
+      rec.data() + FSM_REC_FLOATS * (size_t)k, pose.data() + FSM_POSE_FLOATS * (size_t)k, cell_off.data() + (size_t)k * (FSM_CELLS + 1), cell_idx.data() + f0,
+      kxy.data() + 2 * (size_t)f0, koct.data() + f0, kdesc.data() + 32 * (size_t)f0, P3, Pn, dmin_, dmax_, desc, nlevels, logsf, th, sf.data(), isig.data(), nullptr, nullptr);
 }
 
 int fuse_sim3_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
@@ -1766,29 +1831,17 @@ int fuse_sim3_eval_host(int K, const float* kf_rec, const int32_t* feat_off, con
   if (!scale_factors || (K > 0 && (!kf_rec || !Scw || !n_valid || !n_hit)) || (P > 0 && (!pos || !normal || !min_dist || !max_dist || !pt_desc)) ||
       (K > 0 && P > 0 && !table) || (F && (!feat_xy || !feat_octave || !feat_desc)))
     return -1;
-  std::vector<uint16_t> idx16(F);
-  for (size_t j = 0; j < F; j++) idx16[j] = (uint16_t)cell_idx[j];
-  for (int k = 0; k < K; k++) {
-    n_valid[k] = n_hit[k] = 0;
-    if (P == 0) continue;
-    float pose[FSM_POSE_FLOATS];
-    fsm_decompose_scw(Scw + 12 * (size_t)k, pose);
-    const int32_t f0 = feat_off[k];
-    for (int i = 0; i < P; i++) {
-      const size_t e = (size_t)k * P + i;
-      const uint32_t w = fsm_pair_host(kf_rec + FSM_REC_FLOATS * (size_t)k, pose, cell_off + (size_t)k * (FSM_CELLS + 1), idx16.data() + f0, feat_xy + 2 * (size_t)f0,
-                                       feat_octave + f0, feat_desc + 32 * (size_t)f0, pos + 3 * (size_t)i, normal + 3 * (size_t)i, min_dist[i], max_dist[i],
-                                       pt_desc + 32 * (size_t)i, nlevels, logScaleFactor, th, scale_factors, uv ? uv + 2 * e : nullptr, n_cand ? n_cand + e : nullptr);
-      table[e] = w;
-      n_valid[k] += (w >> 29) >= FSM_EMPTY;
-      n_hit[k] += (w >> 29) == FSM_HIT;
-    }
-  }
+  // the jobs (k, 0, P): every keyframe against all points, keyframe-major
+  std::vector<float> pose(FSM_POSE_FLOATS * (size_t)K);
+  std::vector<int32_t> jk((size_t)K), j0((size_t)K, 0), jn((size_t)K, P);
+  for (int k = 0; k < K; k++) { jk[k] = k; fsm_decompose_scw(Scw + 12 * (size_t)k, pose.data() + FSM_POSE_FLOATS * (size_t)k); }
+  fuse_jobs_host<false>(kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off, cell_idx, pose.data(), nlevels, scale_factors, nullptr, logScaleFactor, th, pos, normal,
+                        min_dist, max_dist, pt_desc, K, jk.data(), j0.data(), jn.data(), F, table, n_valid, n_hit, uv, n_cand);
   return 0;
 }
 
 SearchAndFuseBatch::SearchAndFuseBatch(HipContext* ctx, const KeyFrames& kfs, const Points& pts, int nlevels, const float* scale_factors, float logScaleFactor, float th)
-    : K_(kfs.K), P_(pts.P), nlevels_(nlevels), logsf_(logScaleFactor), th_(th) {
+    : K_(kfs.K), P_(pts.P) {
   const int K = K_, P = P_;
   if (K < 0 || P < 0 || !scale_factors || nlevels < 1 || nlevels > FSM_MAX_LEVELS) throw infrastructure_ex("SearchAndFuseBatch: bad arguments");
   table_.assign((size_t)K * (size_t)P, 0); n_valid_.assign((size_t)K, 0); n_hit_.assign((size_t)K, 0);
@@ -1802,60 +1855,27 @@ SearchAndFuseBatch::SearchAndFuseBatch(HipContext* ctx, const KeyFrames& kfs, co
     throw infrastructure_ex("SearchAndFuseBatch: bad arguments");
   }
   // the arguments are valid from here on: what resolve may have to evaluate again
-  sf_.assign(scale_factors, scale_factors + nlevels);
-  if (K == 0 || P == 0) return;
-  const size_t F = (size_t)kfs.feat_off[K];
-  rec_.assign(kfs.rec, kfs.rec + FSM_REC_FLOATS * (size_t)K);
-  pose_.resize(FSM_POSE_FLOATS * (size_t)K);
-  for (int k = 0; k < K; k++) fsm_decompose_scw(kfs.Scw + 12 * (size_t)k, pose_.data() + FSM_POSE_FLOATS * (size_t)k);
-  feat_off_.assign(kfs.feat_off, kfs.feat_off + K + 1);
-  cell_off_.assign(kfs.cell_off, kfs.cell_off + (size_t)K * (FSM_CELLS + 1));
-  cell_idx_.resize(F);
-  for (size_t j = 0; j < F; j++) cell_idx_[j] = (uint16_t)kfs.cell_idx[j];
-  if (F) { kxy_.assign(kfs.feat_xy, kfs.feat_xy + 2 * F); koct_.assign(kfs.feat_octave, kfs.feat_octave + F); kdesc_.assign(kfs.feat_desc, kfs.feat_desc + 32 * F); }
-  pos_.assign(pts.pos, pts.pos + 3 * (size_t)P); normal_.assign(pts.normal, pts.normal + 3 * (size_t)P);
-  dmin_.assign(pts.min_dist, pts.min_dist + P); dmax_.assign(pts.max_dist, pts.max_dist + P);
-  pdesc_.assign(pts.desc, pts.desc + 32 * (size_t)P);
+  std::vector<float> pose(FSM_POSE_FLOATS * (size_t)K);
+  for (int k = 0; k < K; k++) fsm_decompose_scw(kfs.Scw + 12 * (size_t)k, pose.data() + FSM_POSE_FLOATS * (size_t)k);
+  scene_.copy(kfs, pose.data(), pts, nlevels, scale_factors, nullptr, logScaleFactor, th);
 }
 
 int SearchAndFuseBatch::resolve(int k, const uint8_t* skip_now, const uint8_t* desc_now, std::vector<int32_t>& bestIdx, std::vector<int32_t>& bestDist) {
   if (k < 0 || k >= K_) throw infrastructure_ex("SearchAndFuseBatch::resolve: keyframe out of range");
   bestIdx.assign((size_t)P_, -1); bestDist.assign((size_t)P_, INT_MAX);
+  const FuseScene& s = scene_;
   int nFused = 0;
   for (int i = 0; i < P_; i++) {
     if (skip_now && skip_now[i]) continue;
     uint32_t w = table_[(size_t)k * P_ + i];
     if ((w >> 29) < FSM_EMPTY) continue;                       // the gates read nothing a Fuse call changes
-    if (desc_now && std::memcmp(desc_now + 32 * (size_t)i, pdesc_.data() + 32 * (size_t)i, 32) != 0) {
-      const int32_t f0 = feat_off_[k];
-      w = fsm_pair_host(rec_.data() + FSM_REC_FLOATS * (size_t)k, pose_.data() + FSM_POSE_FLOATS * (size_t)k, cell_off_.data() + (size_t)k * (FSM_CELLS + 1),
-                        cell_idx_.data() + f0, kxy_.data() + 2 * (size_t)f0, koct_.data() + f0, kdesc_.data() + 32 * (size_t)f0, pos_.data() + 3 * (size_t)i,
-                        normal_.data() + 3 * (size_t)i, dmin_[i], dmax_[i], desc_now + 32 * (size_t)i, nlevels_, logsf_, th_, sf_.data(), nullptr, nullptr);
+    if (desc_now && std::memcmp(desc_now + 32 * (size_t)i, s.pdesc.data() + 32 * (size_t)i, 32) != 0) {
+      w = s.eval(k, s.pos.data() + 3 * (size_t)i, s.normal.data() + 3 * (size_t)i, s.dmin[i], s.dmax[i], desc_now + 32 * (size_t)i);
       n_reeval_++;
     }
-    const int st = (int)(w >> 29);
-    if (st >= FSM_FAR) bestDist[i] = (int32_t)((w >> 16) & 0x1FFu);
-    if (st == FSM_HIT) { bestIdx[i] = (int32_t)(w & 0xFFFFu); nFused++; }
+    sin_answer(w, bestIdx[i], bestDist[i], nFused);
   }
   return nFused;
-}
-
-// ---- SearchInNeighborsBatch ---------------------------------------------------------------------------
-// one (keyframe, point) pair through csrc/fuse_sim3_math.h and csrc/fuse_pose_math.h; all keyframe arrays are that keyframe's own
-static uint32_t fpm_pair_host(const float* rec, const float* pose, const int32_t* cell_off, const uint16_t* cell_idx, const float* kxy, const uint8_t* koct,
-                              const uint8_t* kdesc, const float* P3, const float* Pn, float dmin, float dmax, const uint8_t* pdesc, int nlevels, float logsf, float th,
-                              const float* sf, const float* isig, float* uv, int32_t* n_cand) {
-  float u, v; int level;
-  const int st = fsm_gate(rec, pose, P3, Pn, dmin, dmax, nlevels, logsf, u, v, level);
-  if (uv) { uv[0] = u; uv[1] = v; }
-  if (n_cand) *n_cand = 0;
-  if (st != FSM_EMPTY) return fsm_pack(st, 0, FSM_NO_DIST, FSM_NO_IDX);
-  uint32_t q[8];
-  fsm_load_desc(pdesc, q);
-  int n = 0;
-  const uint32_t w = fpm_window_best(rec, cell_off, cell_idx, kxy, koct, kdesc, u, v, level, th, sf, isig, q, &n);
-  if (n_cand) *n_cand = n;
-  return w;
 }
 
 int fuse_pose_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
@@ -1870,29 +1890,14 @@ int fuse_pose_eval_host(int K, const float* kf_rec, const int32_t* feat_off, con
   if (!scale_factors || !inv_level_sigma2 || (K > 0 && (!kf_rec || !pose)) || (J > 0 && (!n_valid || !n_hit)) ||
       (P > 0 && (!pos || !normal || !min_dist || !max_dist || !pt_desc)) || (total > 0 && !table) || (F && (!feat_xy || !feat_octave || !feat_desc)))
     return -1;
-  std::vector<uint16_t> idx16(F);
-  for (size_t f = 0; f < F; f++) idx16[f] = (uint16_t)cell_idx[f];
-  size_t e = 0;
-  for (int j = 0; j < J; j++) {
-    n_valid[j] = n_hit[j] = 0;
-    const int k = job_kf[j];
-    const int32_t f0 = feat_off[k];
-    for (int i = job_pt0[j]; i < job_pt0[j] + job_n[j]; i++, e++) {
-      const uint32_t w = fpm_pair_host(kf_rec + FSM_REC_FLOATS * (size_t)k, pose + FSM_POSE_FLOATS * (size_t)k, cell_off + (size_t)k * (FSM_CELLS + 1), idx16.data() + f0,
-                                       feat_xy + 2 * (size_t)f0, feat_octave + f0, feat_desc + 32 * (size_t)f0, pos + 3 * (size_t)i, normal + 3 * (size_t)i, min_dist[i],
-                                       max_dist[i], pt_desc + 32 * (size_t)i, nlevels, logScaleFactor, th, scale_factors, inv_level_sigma2, uv ? uv + 2 * e : nullptr,
-                                       n_cand ? n_cand + e : nullptr);
-      table[e] = w;
-      n_valid[j] += (w >> 29) >= FSM_EMPTY;
-      n_hit[j] += (w >> 29) == FSM_HIT;
-    }
-  }
+  fuse_jobs_host<true>(kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off, cell_idx, pose, nlevels, scale_factors, inv_level_sigma2, logScaleFactor, th, pos, normal,
+                       min_dist, max_dist, pt_desc, J, job_kf, job_pt0, job_n, F, table, n_valid, n_hit, uv, n_cand);
   return 0;
 }
 
 SearchInNeighborsBatch::SearchInNeighborsBatch(HipContext* ctx, const KeyFrames& kfs, int n_calls, const int32_t* target, int current, const Points& pts, int n_current,
                                                int nlevels, const float* scale_factors, const float* inv_level_sigma2, float logScaleFactor, float th)
-    : K_(kfs.K), C_(n_calls), cur_(current), P1_(n_current), P2_(pts.P - n_current), nlevels_(nlevels), logsf_(logScaleFactor), th_(th) {
+    : K_(kfs.K), C_(n_calls), cur_(current), P1_(n_current), P2_(pts.P - n_current) {
   const int K = K_, P = pts.P, C = C_;
   if (K < 0 || P < 0 || C < 0 || n_current < 0 || n_current > P || (C > 0 && !target) || !scale_factors || !inv_level_sigma2 || nlevels < 1 || nlevels > FSM_MAX_LEVELS ||
       (int64_t)C * n_current + P2_ > (int64_t)INT32_MAX)
@@ -1916,46 +1921,20 @@ SearchInNeighborsBatch::SearchInNeighborsBatch(HipContext* ctx, const KeyFrames&
   }
   // the arguments are valid from here on: what the resolves may have to evaluate again
   target_.assign(jk.begin(), jk.begin() + C);
-  sf_.assign(scale_factors, scale_factors + nlevels); isig_.assign(inv_level_sigma2, inv_level_sigma2 + nlevels);
-  if (K == 0) return;
-  const size_t F = (size_t)kfs.feat_off[K];
-  rec_.assign(kfs.rec, kfs.rec + FSM_REC_FLOATS * (size_t)K);
-  pose_.assign(kfs.pose, kfs.pose + FSM_POSE_FLOATS * (size_t)K);
-  feat_off_.assign(kfs.feat_off, kfs.feat_off + K + 1);
-  cell_off_.assign(kfs.cell_off, kfs.cell_off + (size_t)K * (FSM_CELLS + 1));
-  cell_idx_.resize(F);
-  for (size_t f = 0; f < F; f++) cell_idx_[f] = (uint16_t)kfs.cell_idx[f];
-  if (F) { kxy_.assign(kfs.feat_xy, kfs.feat_xy + 2 * F); koct_.assign(kfs.feat_octave, kfs.feat_octave + F); kdesc_.assign(kfs.feat_desc, kfs.feat_desc + 32 * F); }
-  if (P) {
-    pos_.assign(pts.pos, pts.pos + 3 * (size_t)P); normal_.assign(pts.normal, pts.normal + 3 * (size_t)P);
-    dmin_.assign(pts.min_dist, pts.min_dist + P); dmax_.assign(pts.max_dist, pts.max_dist + P);
-    pdesc_.assign(pts.desc, pts.desc + 32 * (size_t)P);
-  }
-}
-
-uint32_t SearchInNeighborsBatch::eval(int k, const float* P3, const float* Pn, float dmin, float dmax, const uint8_t* desc) const {
-  const int32_t f0 = feat_off_[k];
-  return fpm_pair_host(rec_.data() + FSM_REC_FLOATS * (size_t)k, pose_.data() + FSM_POSE_FLOATS * (size_t)k, cell_off_.data() + (size_t)k * (FSM_CELLS + 1),
-                       cell_idx_.data() + f0, kxy_.data() + 2 * (size_t)f0, koct_.data() + f0, kdesc_.data() + 32 * (size_t)f0, P3, Pn, dmin, dmax, desc, nlevels_, logsf_,
-                       th_, sf_.data(), isig_.data(), nullptr, nullptr);
-}
-
-static inline void sin_answer(uint32_t w, int32_t& bestIdx, int32_t& bestDist, int& nFused) {
-  const int st = (int)(w >> 29);
-  if (st >= FSM_FAR) bestDist = (int32_t)((w >> 16) & 0x1FFu);
-  if (st == FSM_HIT) { bestIdx = (int32_t)(w & 0xFFFFu); nFused++; }
+  scene_.copy(kfs, kfs.pose, pts, nlevels, scale_factors, inv_level_sigma2, logScaleFactor, th);
 }
 
 int SearchInNeighborsBatch::resolve(int c, const uint8_t* skip_now, const uint8_t* desc_now, std::vector<int32_t>& bestIdx, std::vector<int32_t>& bestDist) {
   if (c < 0 || c >= C_) throw infrastructure_ex("SearchInNeighborsBatch::resolve: call out of range");
   bestIdx.assign((size_t)P1_, -1); bestDist.assign((size_t)P1_, 256);
+  const FuseScene& s = scene_;
   int nFused = 0;
   for (int i = 0; i < P1_; i++) {
     if (skip_now && skip_now[i]) continue;
     uint32_t w = table_[(size_t)c * P1_ + i];
     if ((w >> 29) < FSM_EMPTY) continue;                       // the gates read nothing a Fuse call changes
-    if (desc_now && std::memcmp(desc_now + 32 * (size_t)i, pdesc_.data() + 32 * (size_t)i, 32) != 0) {
-      w = eval(target_[c], pos_.data() + 3 * (size_t)i, normal_.data() + 3 * (size_t)i, dmin_[i], dmax_[i], desc_now + 32 * (size_t)i);
+    if (desc_now && std::memcmp(desc_now + 32 * (size_t)i, s.pdesc.data() + 32 * (size_t)i, 32) != 0) {
+      w = s.eval(target_[c], s.pos.data() + 3 * (size_t)i, s.normal.data() + 3 * (size_t)i, s.dmin[i], s.dmax[i], desc_now + 32 * (size_t)i);
       n_reeval_++;
     }
     sin_answer(w, bestIdx[i], bestDist[i], nFused);
@@ -1967,6 +1946,7 @@ int SearchInNeighborsBatch::resolve_current(int n, const int32_t* slot, const ui
                                             std::vector<int32_t>& bestIdx, std::vector<int32_t>& bestDist) {
   if (n < 0 || (n > 0 && !slot) || cur_ < 0) throw infrastructure_ex("SearchInNeighborsBatch::resolve_current: bad arguments");
   bestIdx.assign((size_t)n, -1); bestDist.assign((size_t)n, 256);
+  const FuseScene& sc = scene_;
   int nFused = 0;
   for (int i = 0; i < n; i++) {
     if (skip_now && skip_now[i]) continue;
@@ -1976,15 +1956,15 @@ int SearchInNeighborsBatch::resolve_current(int n, const int32_t* slot, const ui
     if (s < 0) {                                                 // a candidate the build did not predict: from what the caller passes for it
       if (!fresh.pos || !fresh.normal || !fresh.min_dist || !fresh.max_dist || !fresh.desc || fresh.P < n)
         throw infrastructure_ex("SearchInNeighborsBatch::resolve_current: an unpredicted candidate without fresh data");
-      w = eval(cur_, fresh.pos + 3 * (size_t)i, fresh.normal + 3 * (size_t)i, fresh.min_dist[i], fresh.max_dist[i],
-               desc_now ? desc_now + 32 * (size_t)i : fresh.desc + 32 * (size_t)i);
+      w = sc.eval(cur_, fresh.pos + 3 * (size_t)i, fresh.normal + 3 * (size_t)i, fresh.min_dist[i], fresh.max_dist[i],
+                  desc_now ? desc_now + 32 * (size_t)i : fresh.desc + 32 * (size_t)i);
       n_unpredicted_++;
     } else {
       w = table_[(size_t)C_ * P1_ + s];
       if ((w >> 29) < FSM_EMPTY) continue;
       const size_t g = (size_t)P1_ + (size_t)s;
-      if (desc_now && std::memcmp(desc_now + 32 * (size_t)i, pdesc_.data() + 32 * g, 32) != 0) {
-        w = eval(cur_, pos_.data() + 3 * g, normal_.data() + 3 * g, dmin_[g], dmax_[g], desc_now + 32 * (size_t)i);
+      if (desc_now && std::memcmp(desc_now + 32 * (size_t)i, sc.pdesc.data() + 32 * g, 32) != 0) {
+        w = sc.eval(cur_, sc.pos.data() + 3 * g, sc.normal.data() + 3 * g, sc.dmin[g], sc.dmax[g], desc_now + 32 * (size_t)i);
         n_reeval_++;
       }
     }
@@ -2555,7 +2535,7 @@ int ccmh_kfcull_walk_mapcopy_model(int n_cand, int n_all, const uint8_t* cand_fl
                                           thres, n_levels, verdict);
 }
 
-// SearchAndFuseBatch through C, and fuse_sim3_math.h compiled for the host
+// SearchAndFuseBatch through C, and fuse_math.h compiled for the host
 void* ccmh_fuse_sim3_create(int device, int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
                             const int32_t* cell_off, const int32_t* cell_idx, const float* Scw, int nlevels, const float* scale_factors, float logScaleFactor, float th,
                             int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc) {
@@ -2597,7 +2577,7 @@ int ccmh_fuse_sim3_eval_host(int K, const float* kf_rec, const int32_t* feat_off
 }
 void ccmh_fuse_sim3_decompose(const float* Scw12, float* pose15) { fsm_decompose_scw(Scw12, pose15); }
 
-// SearchInNeighborsBatch through C, and fuse_pose_math.h compiled for the host
+// SearchInNeighborsBatch through C, and fuse_math.h compiled for the host
 void* ccmh_fuse_pose_create(int device, int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
                             const int32_t* cell_off, const int32_t* cell_idx, const float* pose, int nlevels, const float* scale_factors, const float* inv_level_sigma2,
                             float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist,

@@ -543,12 +543,29 @@ class TwoViewInitializer {
 };
 
 // ---------------------------------------------------------------------------------------------------
+// What a Fuse batch (SearchAndFuseBatch, SearchInNeighborsBatch below) keeps for its resolves: a copy of the keyframes (poses as Rcw, tcw, Ow; cell_idx in 16 bits)
+// and points it was evaluated on, the call's scalars and level tables, and the pair evaluator on them (csrc/fuse_math.h).  Not part of the API.
+// ---------------------------------------------------------------------------------------------------
+struct FuseScene {
+  int nlevels = 0; float logsf = 0, th = 0;
+  std::vector<float> rec, pose, kxy, sf, isig, pos, normal, dmin, dmax;   // isig empty: the Sim3 form, which has no chi-square gate
+  std::vector<int32_t> feat_off, cell_off;
+  std::vector<uint16_t> cell_idx;
+  std::vector<uint8_t> koct, kdesc, pdesc;
+  // kfs, pts: a batch's KeyFrames and Points, already validated; pose15: 15 floats per keyframe; inv_level_sigma2 == nullptr: the Sim3 form
+  template <class KFs, class Pts>
+  void copy(const KFs& kfs, const float* pose15, const Pts& pts, int nlevels, const float* scale_factors, const float* inv_level_sigma2, float logScaleFactor, float th);
+  // the packed answer of keyframe k and a point given by its data and descriptor
+  uint32_t eval(int k, const float* P3, const float* Pn, float dmin, float dmax, const uint8_t* desc) const;
+};
+
+// ---------------------------------------------------------------------------------------------------
 // SearchAndFuse — LoopFinder.cpp:709-734, MapMerger.cpp:574-598: matcher.Fuse(pKF, Scw, vpLoopMapPoints, 4, vpReplacePoints) for every keyframe of CorrectedSim3,
 // each followed by the Replace loop.  The constructor evaluates every (keyframe, point) pair in ONE ccm_fuse_sim3_eval call (arguments as there) and
 // copies what resolve needs; resolve(k, ...) then returns what the k-th Fuse call returns, whatever the calls before it did to the map: a table entry depends on the
 // keyframe's static data, Scw_k and the point's position, normal, distance bounds and descriptor, and of these Replace / AddObservation change the descriptor
-// alone, so a point whose current descriptor differs from the snapshot is evaluated again on the calling thread (fuse_sim3_math.h) and every other answer is read.
-// ctx == nullptr asks for the host evaluator by name (csrc/fuse_sim3_math.h compiled by g++); with a context, a device error throws — there is no fall-back.
+// alone, so a point whose current descriptor differs from the snapshot is evaluated again on the calling thread (fuse_math.h) and every other answer is read.
+// ctx == nullptr asks for the host evaluator by name (csrc/fuse_math.h compiled by g++); with a context, a device error throws — there is no fall-back.
 // GetMapPoint(bestIdx), vpReplacePoint, AddObservation / AddMapPoint and the Replace loop stay the caller's.
 // ---------------------------------------------------------------------------------------------------
 class SearchAndFuseBatch {
@@ -570,15 +587,13 @@ class SearchAndFuseBatch {
   const std::vector<int32_t>& nHit() const { return n_hit_; }
   long long n_reeval() const { return n_reeval_; }                 // pairs evaluated again by resolve because the descriptor had changed
  private:
-  int K_ = 0, P_ = 0, nlevels_ = 0; float logsf_ = 0, th_ = 0;
-  std::vector<float> rec_, pose_, kxy_, sf_, pos_, normal_, dmin_, dmax_;
-  std::vector<int32_t> feat_off_, cell_off_, n_valid_, n_hit_;
-  std::vector<uint16_t> cell_idx_;
-  std::vector<uint8_t> koct_, kdesc_, pdesc_;
+  int K_ = 0, P_ = 0;
+  FuseScene scene_;
+  std::vector<int32_t> n_valid_, n_hit_;
   std::vector<uint32_t> table_;
   long long n_reeval_ = 0;
 };
-// ccm_fuse_sim3_eval's arguments after the context through csrc/fuse_sim3_math.h on the calling thread; -1 where the device entry returns CCM_E_ARG.
+// ccm_fuse_sim3_eval's arguments after the context through csrc/fuse_math.h on the calling thread; -1 where the device entry returns CCM_E_ARG.
 // n_cand (nullable, K P): the size of vIndices of every pair that reached the window (0 otherwise), for scripts/fuse_sim3_profile.py.
 int fuse_sim3_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
                         const int32_t* cell_off, const int32_t* cell_idx, const float* Scw, int nlevels, const float* scale_factors, float logScaleFactor, float th, int P,
@@ -592,7 +607,7 @@ int fuse_sim3_eval_host(int K, const float* kf_rec, const int32_t* feat_off, con
 // the rest of pts: the union of the targets' points at build time in the reference's order).  Everything a resolve may need later is copied.
 // resolve(c, ...) returns what the c-th Fuse call of the first loop returns, resolve_current(...) what the Fuse on the current keyframe returns, whatever the
 // calls before did to the map: a pair that reached the window and whose current descriptor differs from the snapshot is evaluated again on the calling thread
-// (fuse_pose_math.h); a candidate the prediction missed (slot -1) is evaluated from what the caller passes for it.  ctx == nullptr asks for the host evaluator by
+// (fuse_math.h); a candidate the prediction missed (slot -1) is evaluated from what the caller passes for it.  ctx == nullptr asks for the host evaluator by
 // name; with a context, a device error throws — there is no fall-back.  The map mutations stay the caller's.
 // ---------------------------------------------------------------------------------------------------
 class SearchInNeighborsBatch {
@@ -623,16 +638,13 @@ class SearchInNeighborsBatch {
   long long n_reeval() const { return n_reeval_; }                 // pairs evaluated again because the descriptor had changed
   long long n_unpredicted() const { return n_unpredicted_; }       // candidates evaluated from fresh data
  private:
-  uint32_t eval(int k, const float* P3, const float* Pn, float dmin, float dmax, const uint8_t* desc) const;
-  int K_ = 0, C_ = 0, cur_ = -1, P1_ = 0, P2_ = 0, nlevels_ = 0; float logsf_ = 0, th_ = 0;
-  std::vector<float> rec_, pose_, kxy_, sf_, isig_, pos_, normal_, dmin_, dmax_;
-  std::vector<int32_t> target_, feat_off_, cell_off_, n_valid_, n_hit_;
-  std::vector<uint16_t> cell_idx_;
-  std::vector<uint8_t> koct_, kdesc_, pdesc_;
+  int K_ = 0, C_ = 0, cur_ = -1, P1_ = 0, P2_ = 0;
+  FuseScene scene_;
+  std::vector<int32_t> target_, n_valid_, n_hit_;
   std::vector<uint32_t> table_;
   long long n_reeval_ = 0, n_unpredicted_ = 0;
 };
-// ccm_fuse_pose_eval's arguments after the context through csrc/fuse_pose_math.h on the calling thread; -1 where the device entry returns CCM_E_ARG.
+// ccm_fuse_pose_eval's arguments after the context through csrc/fuse_math.h on the calling thread; -1 where the device entry returns CCM_E_ARG.
 // n_cand (nullable, sum(job_n)): the size of vIndices of every pair that reached the window (0 otherwise), for scripts/fuse_pose_profile.py.
 int fuse_pose_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
                         const int32_t* cell_off, const int32_t* cell_idx, const float* pose, int nlevels, const float* scale_factors, const float* inv_level_sigma2,

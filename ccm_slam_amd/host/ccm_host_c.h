@@ -125,7 +125,7 @@ int ccmh_twoview_score_host(int model, int n_models, const float* M, int N, cons
 /* cslam::SearchAndFuseBatch (every Fuse call of a SearchAndFuse from ONE ccm_fuse_sim3_eval call; arguments as there).  device < 0 asks for the host evaluator by name;
  * create returns NULL on bad arguments or a device error.  table: any pointer may be NULL.  resolve: the k-th Fuse call with the caller's current skips and descriptors
  * (both nullable); returns nFused, -1000 on an error, -1001 when n_pts is not the batch's.  eval_host: the arguments of ccm_fuse_sim3_eval after the context through
- * csrc/fuse_sim3_math.h on the calling thread (0, or -1 for its CCM_E_ARG cases); n_cand (nullable, K P): the size of vIndices per pair.  decompose: ORBmatcher.cpp:1004-1008. */
+ * csrc/fuse_math.h on the calling thread (0, or -1 for its CCM_E_ARG cases); n_cand (nullable, K P): the size of vIndices per pair.  decompose: ORBmatcher.cpp:1004-1008. */
 void* ccmh_fuse_sim3_create(int device, int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc, const int32_t* cell_off, const int32_t* cell_idx, const float* Scw, int nlevels, const float* scale_factors, float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc);
 int ccmh_fuse_sim3_table(void* h, uint32_t* table, int32_t* n_valid, int32_t* n_hit);
 int ccmh_fuse_sim3_resolve(void* h, int k, const uint8_t* skip_now, const uint8_t* desc_now, int n_pts, int32_t* best_idx, int32_t* best_dist);

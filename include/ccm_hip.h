@@ -598,7 +598,7 @@ int  ccm_twoview_check_rt(ccm_ctx* ctx, int n_hyp, const float* rec /* 27 n_hyp 
 /* ---- SearchAndFuse: every Fuse(pKF, Scw, vpLoopMapPoints, th, vpReplacePoints) of a loop closure or a map merge -------------------
  * LoopFinder::SearchAndFuse (cslam/src/LoopFinder.cpp:709-734) and MapMerger::SearchAndFuse (MapMerger.cpp:574-598) call ORBmatcher::Fuse (ORBmatcher.cpp:995-1122)
  * once per keyframe of CorrectedSim3 with the same points.  This call evaluates the loop body of every (keyframe, point) pair up to its decision, bit-identical to the
- * reference's f32 / f64 arithmetic under OpenCV 4.2 baseline-build semantics (the lines are ccm_slam_amd/csrc/fuse_sim3_math.h, which also compiles
+ * reference's f32 / f64 arithmetic under OpenCV 4.2 baseline-build semantics (the lines are ccm_slam_amd/csrc/fuse_math.h, which also compiles
  * for the host).  Stateless; the skips (isBad(), spAlreadyFound) and the map mutations stay the caller's (cslam::SearchAndFuseBatch replays them).
  * Per keyframe k < K: kf_rec = fx fy cx cy, mnMinX mnMinY mnMaxX mnMaxY (the keyframe's int-truncated bounds as floats), mfGridElementWidthInv, mfGridElementHeightInv;
  * its features feat_off[k] .. feat_off[k + 1] (at most 65 535): feat_xy = mvKeysUn[i].pt, feat_octave, feat_desc (32 bytes each); its mGrid as a CSR of 75 x 48 cells
@@ -622,7 +622,7 @@ int  ccm_fuse_sim3_eval(ccm_ctx* ctx, int K, const float* kf_rec /* 10 K */, con
 /* ---- SearchInNeighbors: every Fuse(pKF, vpMapPoints, th) of one LocalMapping::SearchInNeighbors, both directions -----------------------
  * LocalMapping::SearchInNeighbors (cslam/src/Mapping.cpp:471-547) calls ORBmatcher::Fuse(pKF, vpMapPoints, 3) (ORBmatcher.cpp:854-993) once per fuse target with the
  * current keyframe's points and once on the current keyframe with the targets' points.  This call evaluates the loop body of every pair of a JOB LIST up to its
- * decision, bit-identical to the reference (the lines are csrc/fuse_sim3_math.h and csrc/fuse_pose_math.h, which also compile for the host).
+ * decision, bit-identical to the reference (the lines are csrc/fuse_math.h, which also compiles for the host).
  * Stateless; the skips (isBad(), IsInKeyFrame, mbDoNotReplace) and the map mutations stay the caller's (cslam::SearchInNeighborsBatch replays them).
  * Keyframes, per-call values and points: as for ccm_fuse_sim3_eval, with two differences.  pose + 15 k = GetRotation() (9, row-major), GetTranslation() (3),
  * GetCameraCenter() (3) of keyframe k, in place of Scw; inv_level_sigma2[nlevels] = mvInvLevelSigma2.

@@ -3,7 +3,7 @@
   server_merged  100 calls x 1 000 points + 1 x 25 000     a server keyframe in a merged map
   small            5 calls x   300 points + 1 x  1 000
     device_us      ccm_fuse_pose_eval, host to host through the Python wrapper
-    host_1_us      the same arguments through fuse_pose_math.h compiled for the host, one thread: BASELINE A
+    host_1_us      the same arguments through fuse_math.h compiled for the host, one thread: BASELINE A
     fusebatch_us   the route of cslam::FuseBatch for the same answers: per direction one batch (host window search, one ccm_hamming_csr_multi launch) and the resolve
                    of every call: BASELINE B.  The projections (valid, u, v, level) that FuseBatch takes as inputs are computed BEFORE the clock starts, so this
                    column leaves out the host projection of that route and is a lower bound of it.

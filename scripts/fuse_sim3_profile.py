@@ -3,7 +3,7 @@
   merge_1_agent   500 x 3 000     MergeMaps with one agent's map
   merge_4_agents 1000 x 5 000     a four-agent merge
     device_us   ccm_fuse_sim3_eval, host to host through the Python wrapper
-    host_1_us   the same arguments through fuse_sim3_math.h compiled for the host, one thread, as the reference runs SearchAndFuse: the BASELINE
+    host_1_us   the same arguments through fuse_math.h compiled for the host, one thread, as the reference runs SearchAndFuse: the BASELINE
 Each figure is the median of 15 repetitions; the two candidates of a row are interleaved within every repetition.  The whole table is measured three times
 (`runs`); margin_us = max - min of the baseline's three medians is what counts as a difference in that row.  Compare only figures of one invocation.
 Per size also, from the host evaluator: the mean and the largest number of candidates per window (the size of vIndices over the pairs that reach the window)

@@ -1,4 +1,4 @@
-"""SearchInNeighbors on the CPU: csrc/fuse_pose_math.h compiled by g++ (libccm_host.so) against the reference's own ORBmatcher::Fuse(pKF,
+"""SearchInNeighbors on the CPU: csrc/fuse_math.h compiled by g++ (libccm_host.so) against the reference's own ORBmatcher::Fuse(pKF,
 vpMapPoints, th) (oracle/_ref/libmatcher_ref.so through ref_fuse, kf_has_mp all zero, one call per job), against oracle.grid_candidates plus a numpy arg-min with
 the level filter and the chi-square gate for the three outcomes the reference does not tell apart, and against hand-made pairs with known answers; job lists; the
 mirror cslam::SearchInNeighborsBatch with the host evaluator through the 12 Fuse calls of the fan-out and the call on the current keyframe, between which the map

@@ -1,4 +1,4 @@
-"""GPU: ccm_fuse_pose_eval equals the host evaluator (csrc/fuse_pose_math.h under g++) bit for bit, and the reference's own ORBmatcher::Fuse where
+"""GPU: ccm_fuse_pose_eval equals the host evaluator (csrc/fuse_math.h under g++) bit for bit, and the reference's own ORBmatcher::Fuse where
 oracle/_ref/libmatcher_ref.so was built on this machine, at every size where the kernel takes another path: one pair, no job, empty jobs between others, tiles of
 256 pairs that are full, one short and one over, waves that are full, one short and one over, job lists whose tiles belong to different keyframes, windows that a
 lane walks alone and windows the wave takes (the switch is 64 features in the window's cells), many small jobs, a keyframe without features.  Every comparison is

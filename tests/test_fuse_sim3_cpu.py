@@ -1,4 +1,4 @@
-"""SearchAndFuse on the CPU: csrc/fuse_sim3_math.h compiled by g++ (libccm_host.so) against the reference's own ORBmatcher::Fuse(pKF, Scw, ...)
+"""SearchAndFuse on the CPU: csrc/fuse_math.h compiled by g++ (libccm_host.so) against the reference's own ORBmatcher::Fuse(pKF, Scw, ...)
 (oracle/_ref/libmatcher_ref.so through ref_fuse_sim3, kf_has_mp all zero, one call per keyframe), against oracle.grid_candidates plus a numpy arg-min for the three
 outcomes the reference does not tell apart, and against hand-made pairs with known answers; the mirror cslam::SearchAndFuseBatch with the host evaluator through a
 walk of eight Fuse calls between which the map changes; every CCM_E_ARG case.  Every comparison is exact: integers, and float bit patterns for u and v."""

@@ -1,4 +1,4 @@
-"""GPU: ccm_fuse_sim3_eval equals the host evaluator (csrc/fuse_sim3_math.h under g++) bit for bit, and the reference's own ORBmatcher::Fuse where
+"""GPU: ccm_fuse_sim3_eval equals the host evaluator (csrc/fuse_math.h under g++) bit for bit, and the reference's own ORBmatcher::Fuse where
 oracle/_ref/libmatcher_ref.so was built on this machine, at every size where the kernel takes another path: one pair, no pair, tiles of 256 points that are
 full, one short and one over, waves that are full, one short and one over, windows that a lane walks alone and windows the wave takes (the switch is 64 features
 in the window's cells), many keyframes, a keyframe without features.  Every comparison is exact."""
