@@ -6,7 +6,12 @@
 //   chol_diag_wave (1 wave)        L_jj = chol(A_jj), Li_jj = L_jj^-1 kept for the panel and the solves
 //   chol_panel  (1 wg / tile row)  L_ij = A_ij Li_jj^T                     } one 64x64x64 product per workgroup on the
 //   chol_update (1 wg / tile pair) A_ik -= L_ij L_kj^T  (i >= k > j)       } f64 matrix cores (v_mfma_f64_16x16x4_f64)
-// then tile-wise forward / backward substitution.  MFMA operand layout (guide, "f64 MFMA does NOT use these maps"):
+// then tile-wise forward / backward substitution.
+// The explicit inverse (ccm_dense_chol_inverse_dev: the coarse level of the BA preconditioner) runs a shorter chain: diagonal tile j, then ONE launch chol_step
+// with the panel products, the trailing update and L^-1 step j - 1 beside them; one chol_tri_step after the last diagonal tile, then chol_xtx.  Its time is kernel
+// time, not launch gaps (the gaps between dependent launches on the device are nil: 614 us of kernels in 616 us of wall time for 12 tiles), so what pays is taking
+// work off the chain and shortening its kernels, not the launch count as such.  CCM_CHOL_CHAIN=split keeps the three-kernel chain for A / B runs; same bits.
+// MFMA operand layout (guide, "f64 MFMA does NOT use these maps"):
 // A: lane l holds A[l & 15][l >> 4], B: lane l holds B[l >> 4][l & 15], D: reg r of lane l is D[(l >> 4) + 4 r][l & 15].
 #include "common.h"
 #include "test_internal.h"
@@ -136,13 +141,16 @@ __device__ __forceinline__ void chol_diag_body(double* Ajj, size_t N, int j, dou
 //   (b) the 16 pivots of the block then run on registers alone: lane i keeps its row, a pivot row's entries travel by v_readlane, rows below the block
 //       form their panel entries in the same instruction stream (the 16 x 16 tile factorisation of the BA cluster solver, 64 rows tall): ~200 ns per pivot;
 //   (c) the block's columns go to LDS for the later blocks and for wave 1, which forms L^-1 one BLOCK behind (four barriers per tile instead of 64).
+// A third wave runs phase (a) AHEAD: while wave 0 is in the pivots of block b it applies block b - 1 to the blocks after b, so that wave 0's own phase (a) is the
+// previous block's 16 columns only (768 instead of 1536 multiply-adds per lane on the pivot chain: 21.8 -> 20.8 us per tile; every element keeps its k-ascending chain).
+// L^-1 of the last block still trails the factorisation by ~3 us.  Resource report: 174 VGPRs, no spills (the column form chol_diag_body spills 2 - 4).
 __device__ __forceinline__ void chol_diag_body_blk(double* Ajj, size_t N, int j, double* Lg, int* info) {
   constexpr int LR = NB + 2, KB = 16;
   __shared__ __attribute__((aligned(16))) double L[NB * LR];
   __shared__ double rdiag[NB];
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  {
+  if (wv < 2) {
     double tmp[NB / 2];
 #pragma unroll
     for (int r = 0; r < NB / 2; r++) tmp[r] = Ajj[(size_t)(wv * (NB / 2) + r) * N + lane];
@@ -150,7 +158,7 @@ __device__ __forceinline__ void chol_diag_body_blk(double* Ajj, size_t N, int j,
     for (int r = 0; r < NB / 2; r++) L[(wv * (NB / 2) + r) * LR + lane] = tmp[r];
   }
   __syncthreads();
-  // The two waves run DIFFERENT loops with the same number of block barriers (wave 0 arrives at barrier b after block b is in LDS, wave 1 before it reads
+  // The three waves run DIFFERENT loops with the same number of block barriers (wave 0 arrives at barrier b after block b is in LDS, wave 1 before it reads
   // it): in one shared loop the register allocator keeps wave 1's 64 values of x alive through wave 0's code as well, and both spill.
   // INVARIANT: each branch executes EXACTLY kBlocks barriers, one per trip of its `b` loop and none elsewhere (s_barrier counts arrivals per wave, not
   // call sites; the HIP model does not promise that, so this relies on the gfx950 barrier and on both trip counts being the one constant below).
@@ -166,9 +174,10 @@ __device__ __forceinline__ void chol_diag_body_blk(double* Ajj, size_t N, int j,
       double row[KB];   // lane i's entries of the block's 16 columns (its earlier columns stay in LDS)
 #pragma unroll
       for (int c = 0; c < KB; c += 2) { const double2 v = *reinterpret_cast<const double2*>(&L[lane * LR + c0 + c]); row[c] = v.x; row[c + 1] = v.y; }
-      // (a) row[c] -= sum_{k < c0} L_ik L_{c0 + c, k}: both operands from LDS (the lane's own earlier entries; the pivot rows at uniform addresses)
+      // (a) row[c] -= sum_{k < c0} L_ik L_{c0 + c, k}: both operands from LDS (the lane's own earlier entries; the pivot rows at uniform addresses).  Only the
+      // PREVIOUS block's 16 columns are left for this wave: wave 2 applied every earlier block while the pivots of the previous block ran (same chain, k ascending)
 #pragma unroll 2
-      for (int k = 0; k < c0; k += 2) {
+      for (int k = c0 > KB ? c0 - KB : 0; k < c0; k += 2) {
         const double2 a2 = *reinterpret_cast<const double2*>(&L[lane * LR + k]);
 #pragma unroll
         for (int c = 0; c < KB; c++) {
@@ -200,6 +209,34 @@ __device__ __forceinline__ void chol_diag_body_blk(double* Ajj, size_t N, int j,
     if (bad_col && lane == 0 && *info == 0) *info = j * NB + bad_col;
 #pragma unroll
     for (int r = 0; r < NB; r++) Ajj[(size_t)r * N + lane] = (lane <= r) ? L[r * LR + lane] : 0.0;
+  } else if (wv == 2) {
+    // phase (a) ahead of the pivot wave: between barriers b and b + 1 (wave 0 runs the pivots of block b) the columns of block b - 1, final since barrier b, are
+    // applied to the entries of blocks b + 1 ... — columns wave 0 neither reads nor writes before barrier b + 1, rows and columns wave 1 never reads.  Every element
+    // keeps its chain: blocks enter in ascending order, k ascending inside a block, the value rests in LDS (an exact copy) between blocks.
+#pragma unroll
+    for (int b = 0; b < kBlocks; b++) {   // (kBlocks barriers, see the invariant above)
+      if (b >= 1) {
+        const int k0 = KB * (b - 1);
+        for (int t = b + 1; t < kBlocks; t++) {
+          const int c0 = KB * t;
+          double row[KB];
+#pragma unroll
+          for (int c = 0; c < KB; c += 2) { const double2 v = *reinterpret_cast<const double2*>(&L[lane * LR + c0 + c]); row[c] = v.x; row[c + 1] = v.y; }
+#pragma unroll 2
+          for (int k = k0; k < k0 + KB; k += 2) {
+            const double2 a2 = *reinterpret_cast<const double2*>(&L[lane * LR + k]);
+#pragma unroll
+            for (int c = 0; c < KB; c++) {
+              const double2 l2 = *reinterpret_cast<const double2*>(&L[(c0 + c) * LR + k]);
+              row[c] = __builtin_fma(-a2.y, l2.y, __builtin_fma(-a2.x, l2.x, row[c]));
+            }
+          }
+#pragma unroll
+          for (int c = 0; c < KB; c += 2) { double2 v; v.x = row[c]; v.y = row[c + 1]; *reinterpret_cast<double2*>(&L[lane * LR + c0 + c]) = v; }
+        }
+      }
+      __syncthreads();
+    }
   } else {
     double x[NB];     // lane t's column of L^-1
 #pragma unroll
@@ -223,7 +260,7 @@ __device__ __forceinline__ void chol_diag_body_blk(double* Ajj, size_t N, int j,
 __global__ __launch_bounds__(128) void chol_diag_wave(double* A, int N, int j, double* Linv_all, int* info) {
   chol_diag_body(A + ((size_t)j * NB) * N + (size_t)j * NB, (size_t)N, j, Linv_all + (size_t)j * NB * NB, info);
 }
-__global__ __launch_bounds__(128) void chol_diag_wave_blk(double* A, int N, int j, double* Linv_all, int* info) {
+__global__ __launch_bounds__(192) void chol_diag_wave_blk(double* A, int N, int j, double* Linv_all, int* info) {
   chol_diag_body_blk(A + ((size_t)j * NB) * N + (size_t)j * NB, (size_t)N, j, Linv_all + (size_t)j * NB * NB, info);
 }
 
@@ -252,9 +289,11 @@ __global__ __launch_bounds__(kTPB) void tsc_gather(double* tiles, const int* tid
     for (int r = 0; r < 4; r++) Aij[(size_t)(16 * wave + (lane >> 4) + 4 * r) * NB + 16 * s + (lane & 15)] -= acc[s][r];
 }
 static inline bool diag_blocked() { static const bool v = !(getenv("CCM_CHOL_DIAG") && !strcmp(getenv("CCM_CHOL_DIAG"), "columns")); return v; }
+// the inverse's launch chain: fused (chol_step) unless CCM_CHOL_CHAIN=split asks for diagonal tile / panel / update and the L^-1 steps afterwards
+static inline bool chain_split() { static const bool v = getenv("CCM_CHOL_CHAIN") && !strcmp(getenv("CCM_CHOL_CHAIN"), "split"); return v; }
 
 template <bool kBlocked>
-__global__ __launch_bounds__(128) void tsc_diag(double* tiles, const int* tid, int T, const int* cols, double* Linv_all, int* info) {
+__global__ __launch_bounds__(kBlocked ? 192 : 128) void tsc_diag(double* tiles, const int* tid, int T, const int* cols, double* Linv_all, int* info) {
   const int j = cols[blockIdx.x];
   if (kBlocked) chol_diag_body_blk(tiles + (size_t)tid[(size_t)j * T + j] * (NB * NB), (size_t)NB, j, Linv_all + (size_t)j * NB * NB, info);
   else chol_diag_body(tiles + (size_t)tid[(size_t)j * T + j] * (NB * NB), (size_t)NB, j, Linv_all + (size_t)j * NB * NB, info);
@@ -427,28 +466,27 @@ __global__ __launch_bounds__(kTPB) void chol_tri_diag(int N, const double* Linv_
   const int j = blockIdx.x;
   for (int e = threadIdx.x; e < NB * NB; e += kTPB) X[((size_t)j * NB + e / NB) * N + (size_t)j * NB + e % NB] = Linv_all[(size_t)j * NB * NB + e];
 }
-__global__ __launch_bounds__(kTPB) void chol_tri_step(const double* A, int N, const double* Linv_all, double* X, int k) {
-  __shared__ double As[NB * LD], Bs[16 * LD];
-  const int nj = k + 1;
-  const int i = k + 1 + (int)blockIdx.x / nj, j = (int)blockIdx.x % nj, c0 = 16 * blockIdx.y;
+// one product of L^-1 step k: strip c0 of X_ij += L_ik X_kj (i > k >= j).  Lik / Xkj: the two operand tiles with their row strides — the split chain keeps L in A's
+// lower triangle and X_kk in X, the fused chain keeps L_ik in A's upper slot (k, i) and takes X_kk = Li_kk straight from d_linv.  As: 64 x LD, Bs: 16 x LD doubles.
+__device__ __forceinline__ void tri_step_body(double* As, double* Bs, const double* Lik, int ldL, const double* Xkj, int ldX, const double* Li_ii /* i == k + 1 */,
+                                              double* Xij, int N, bool first, bool last) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int i16 = lane & 15, kq = lane >> 4;
-  double* Xij = X + ((size_t)i * NB) * N + (size_t)j * NB + c0;
   v4d acc = {0, 0, 0, 0};
-  if (j != k) {
+  if (!first) {
 #pragma unroll
     for (int r = 0; r < 4; r++) acc[r] = Xij[(size_t)(16 * wave + kq + 4 * r) * N + i16];
   }
-  load_tile(As, A + ((size_t)i * NB) * N + (size_t)k * NB, N);                        // L_ik
-  load_strip_t(Bs, X + ((size_t)k * NB) * N + (size_t)j * NB + c0, N);                // strip of X_kj, transposed
+  load_tile(As, Lik, ldL);                        // L_ik
+  load_strip_t(Bs, Xkj, ldX);                     // strip of X_kj, transposed
   __syncthreads();
   tile_abt16(As, Bs, acc, wave, lane);
   __syncthreads();
-  if (i == k + 1) {
+  if (last) {
     // Bs <- acc^T (so that Li_ii * acc = As * Bs^T), As <- Li_ii
 #pragma unroll
     for (int r = 0; r < 4; r++) Bs[i16 * LD + 16 * wave + kq + 4 * r] = acc[r];
-    load_tile(As, Linv_all + (size_t)i * NB * NB, NB);
+    load_tile(As, Li_ii, NB);
     __syncthreads();
     v4d out = {0, 0, 0, 0};
     tile_abt16(As, Bs, out, wave, lane);
@@ -459,9 +497,99 @@ __global__ __launch_bounds__(kTPB) void chol_tri_step(const double* A, int N, co
     for (int r = 0; r < 4; r++) Xij[(size_t)(16 * wave + kq + 4 * r) * N + i16] = acc[r];
   }
 }
+// workgroup t of L^-1 step k: t -> (i, j, strip), i > k >= j
+template <bool kFused>
+__device__ __forceinline__ void tri_step_wg(double* As, double* Bs, const double* A, int N, const double* Linv_all, double* X, int k, int t) {
+  const int nj = k + 1;
+  const int c0 = 16 * (t & 3), i = k + 1 + (t >> 2) / nj, j = (t >> 2) % nj;
+  const double* Lik = kFused ? A + ((size_t)k * NB) * N + (size_t)i * NB : A + ((size_t)i * NB) * N + (size_t)k * NB;
+  const bool diag = kFused && j == k;
+  const double* Xkj = diag ? Linv_all + (size_t)k * NB * NB + c0 : X + ((size_t)k * NB) * N + (size_t)j * NB + c0;
+  tri_step_body(As, Bs, Lik, N, Xkj, diag ? NB : N, Linv_all + (size_t)i * NB * NB, X + ((size_t)i * NB) * N + (size_t)j * NB + c0, N, j == k, i == k + 1);
+}
+template <bool kFused>
+__global__ __launch_bounds__(kTPB) void chol_tri_step(const double* A, int N, const double* Linv_all, double* X, int k) {
+  __shared__ double As[NB * LD], Bs[16 * LD];
+  tri_step_wg<kFused>(As, Bs, A, N, Linv_all, X, k, (int)blockIdx.x);
+}
 
-// Ainv = X^T X: strip s (16 columns) of tile (p, q), p >= q: sum_{k >= p} X_kp^T X_kq ; mirrored into (q, p)
-__global__ __launch_bounds__(kTPB) void chol_xtx(const double* X, int N, double* Ainv) {
+// one 16 x 16 subtile (rs, cs) of As * Bs^T: the accumulator chain tile_abt runs for that subtile (same operands per lane, kk ascending)
+__device__ __forceinline__ void sub_abt(const double* As, const double* Bs, v4d& acc, int rs, int cs, int lane) {
+  const int i = lane & 15, kq = lane >> 4;
+#pragma unroll 4
+  for (int kk = 0; kk < NB / 4; kk++) {
+    const int k = 4 * kk + kq;
+    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(As[(16 * rs + i) * LD + k], Bs[(16 * cs + i) * LD + k], acc, 0, 0, 0);
+  }
+}
+// Fused chain, step j in ONE launch after diagonal tile j.
+// Workgroups [0, n_upd): FOUR per pair (i, k), i >= k > j, one per 32 x 32 quadrant (hr, hc) of A_ik.  A workgroup forms the 32 rows of the panel tiles it needs itself
+// — rows 32 hr.. of L_ij = A_ij Li_jj^T and rows 32 hc.. of L_kj, the products chol_panel makes, subtile by subtile in the same MFMA order — parks them in LDS and
+// updates its quadrant, A_ik -= L_ij L_kj^T (chol_update's product).  A 64 x 64 x 64 product costs a CU ~1.7 us of f64 MFMA time: with whole tiles per workgroup the
+// two panel products tripled the kernel's MFMA time (13.1 us against chol_update's 10.5); a quadrant costs 1.25 products.  All four operands (both A halves, Li_jj, the
+// A_ik quadrant) are requested before the first product — the split chain fetched A_ik for the -= only after the product.  The workgroups k == j + 1, hc == 0 store
+// their rows of L_ij for the L^-1 steps — into A's UPPER slot (j, i), which no workgroup of any launch reads as input: the raw A_ij in the lower triangle is still
+// being read by the other workgroups of this launch.
+// Workgroups [n_upd, ...): L^-1 step j - 1, whose inputs (column j - 1 of L from the previous step launch, Li_jj from the diagonal tile just before this launch, row
+// j - 1 of X from the step before) are all final by now, so it costs the chain nothing.
+__global__ __launch_bounds__(kTPB) void chol_step(double* A, int N, int j, const double* Linv_all, double* X, int n_upd) {
+  __shared__ double Ls[NB * LD], Ps[NB * LD];   // Ls: Li_jj.  Ps rows 0..31: half of A_ij, then of L_ij; rows 32..63: half of A_kj, then of L_kj
+  if ((int)blockIdx.x >= n_upd) { tri_step_wg<true>(Ps, Ls, A, N, Linv_all, X, j - 1, (int)blockIdx.x - n_upd); return; }
+  const int p = blockIdx.x >> 2, hr = (blockIdx.x >> 1) & 1, hc = blockIdx.x & 1;
+  int ii = (int)((sqrtf(8.0f * (float)p + 1.0f) - 1.0f) * 0.5f);
+  while (ii * (ii + 1) / 2 > p) ii--;
+  while ((ii + 1) * (ii + 2) / 2 <= p) ii++;
+  const int kk = p - ii * (ii + 1) / 2;
+  const int i = j + 1 + ii, k = j + 1 + kk;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int rs = wave & 1, ch = wave >> 1;      // P1 / P2: subtiles (rs, 2 ch) and (rs, 2 ch + 1) of a 32 x 64 half; update: subtile (rs, ch) of the quadrant
+  const int er = lane >> 4, ec = lane & 15;     // accumulator register r of this lane is element (er + 4 r, ec) of its subtile
+  const double* Aij = A + ((size_t)i * NB + 32 * hr) * N + (size_t)j * NB;
+  const double* Akj = A + ((size_t)k * NB + 32 * hc) * N + (size_t)j * NB;
+  const double* Li = Linv_all + (size_t)j * NB * NB;
+  double* Aik = A + ((size_t)i * NB + 32 * hr + 16 * rs) * N + (size_t)k * NB + 32 * hc + 16 * ch;
+  constexpr int Q = NB * NB / kTPB;
+  double a[Q / 2], b[Q / 2], li[Q];
+  v4d d;
+#pragma unroll
+  for (int q = 0; q < Q / 2; q++) { const int e = threadIdx.x + q * kTPB; a[q] = Aij[(size_t)(e / NB) * N + e % NB]; b[q] = Akj[(size_t)(e / NB) * N + e % NB]; }
+#pragma unroll
+  for (int q = 0; q < Q; q++) li[q] = Li[threadIdx.x + q * kTPB];
+#pragma unroll
+  for (int r = 0; r < 4; r++) d[r] = Aik[(size_t)(er + 4 * r) * N + ec];
+#pragma unroll
+  for (int q = 0; q < Q / 2; q++) { const int e = threadIdx.x + q * kTPB; Ps[(e / NB) * LD + e % NB] = a[q]; Ps[(32 + e / NB) * LD + e % NB] = b[q]; }
+#pragma unroll
+  for (int q = 0; q < Q; q++) { const int e = threadIdx.x + q * kTPB; Ls[(e / NB) * LD + e % NB] = li[q]; }
+  __syncthreads();
+  v4d lij[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, lkj[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+#pragma unroll
+  for (int t = 0; t < 2; t++) { sub_abt(Ps, Ls, lij[t], rs, 2 * ch + t, lane); sub_abt(Ps + 32 * LD, Ls, lkj[t], rs, 2 * ch + t, lane); }
+  __syncthreads();
+#pragma unroll
+  for (int t = 0; t < 2; t++)
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      Ps[(16 * rs + er + 4 * r) * LD + 16 * (2 * ch + t) + ec] = lij[t][r];
+      Ps[(32 + 16 * rs + er + 4 * r) * LD + 16 * (2 * ch + t) + ec] = lkj[t][r];
+    }
+  if (kk == 0 && hc == 0) {
+    double* U = A + ((size_t)j * NB + 32 * hr + 16 * rs) * N + (size_t)i * NB;   // upper slot (j, i)
+#pragma unroll
+    for (int t = 0; t < 2; t++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) U[(size_t)(er + 4 * r) * N + 16 * (2 * ch + t) + ec] = lij[t][r];
+  }
+  __syncthreads();
+  v4d acc = {0, 0, 0, 0};
+  sub_abt(Ps, Ps + 32 * LD, acc, rs, ch, lane);
+#pragma unroll
+  for (int r = 0; r < 4; r++) Aik[(size_t)(er + 4 * r) * N + ec] = d[r] - acc[r];
+}
+
+// Ainv = X^T X: strip s (16 columns) of tile (p, q), p >= q: sum_{k >= p} X_kp^T X_kq ; mirrored into (q, p).  Xd: where the diagonal tiles X_kk = Li_kk are read
+// (64 x 64 contiguous each, d_linv) or nullptr when they were copied into X (split chain)
+__global__ __launch_bounds__(kTPB) void chol_xtx(const double* X, int N, double* Ainv, const double* Xd) {
   __shared__ double As[NB * LD], Bs[16 * LD];
   const int T = N / NB;
   const int pi = blockIdx.x, c0 = 16 * blockIdx.y;
@@ -473,8 +601,9 @@ __global__ __launch_bounds__(kTPB) void chol_xtx(const double* X, int N, double*
   const int i16 = lane & 15, kq = lane >> 4;
   v4d acc = {0, 0, 0, 0};
   for (int k = p; k < T; k++) {
-    load_tile_t(As, X + ((size_t)k * NB) * N + (size_t)p * NB, N);            // X_kp^T
-    load_strip_t(Bs, X + ((size_t)k * NB) * N + (size_t)q * NB + c0, N);      // strip of X_kq, transposed => As * Bs^T = X_kp^T X_kq[:, strip]
+    const bool dp = Xd && k == p, dq = Xd && k == q;
+    load_tile_t(As, dp ? Xd + (size_t)k * NB * NB : X + ((size_t)k * NB) * N + (size_t)p * NB, dp ? NB : N);                // X_kp^T
+    load_strip_t(Bs, dq ? Xd + (size_t)k * NB * NB + c0 : X + ((size_t)k * NB) * N + (size_t)q * NB + c0, dq ? NB : N);    // strip of X_kq, transposed => As * Bs^T = X_kp^T X_kq[:, strip]
     __syncthreads();
     tile_abt16(As, Bs, acc, wave, lane);
     __syncthreads();
@@ -498,7 +627,7 @@ int ccm_dense_chol_solve_dev(ccm_ctx* ctx, double* d_A, int N, double* d_b, doub
   if (plan && (plan->T != T || T >= 32768)) return ccm_set_error(ctx, CCM_E_ARG, "dense cholesky: tile plan does not match");
   CCM_HIP_CHECK(ctx, hipMemsetAsync(d_info, 0, sizeof(int), ctx->stream));
   for (int j = 0; j < T; j++) {
-    if (diag_blocked()) hipLaunchKernelGGL(chol_diag_wave_blk, dim3(1), dim3(128), 0, ctx->stream, d_A, N, j, d_linv, d_info);
+    if (diag_blocked()) hipLaunchKernelGGL(chol_diag_wave_blk, dim3(1), dim3(192), 0, ctx->stream, d_A, N, j, d_linv, d_info);
     else hipLaunchKernelGGL(chol_diag_wave, dim3(1), dim3(128), 0, ctx->stream, d_A, N, j, d_linv, d_info);
     if (plan) {
       const int nr = plan->h_col_off[j + 1] - plan->h_col_off[j], np = plan->h_upd_off[j + 1] - plan->h_upd_off[j];
@@ -644,7 +773,7 @@ int ccm_tsc_solve(ccm_ctx* ctx, ccm_tsc* p, double* d_b) {
     const int g0 = p->lvl_gt_off[l], ng = p->lvl_gt_off[l + 1] - g0;
     const int p0 = p->lvl_pt_off[l], np = p->lvl_pt_off[l + 1] - p0;
     if (ng) hipLaunchKernelGGL(tsc_gather, dim3(ng), dim3(kTPB), 0, ctx->stream, p->d_tiles, (const int*)p->d_tid, T, (const int*)p->d_gt + g0, (const int*)p->d_gk_off + g0, (const int*)p->d_gk);
-    if (diag_blocked()) hipLaunchKernelGGL(tsc_diag<true>, dim3(nc), dim3(128), 0, ctx->stream, p->d_tiles, (const int*)p->d_tid, T, (const int*)p->d_cols + c0, p->d_linv, p->d_info);
+    if (diag_blocked()) hipLaunchKernelGGL(tsc_diag<true>, dim3(nc), dim3(192), 0, ctx->stream, p->d_tiles, (const int*)p->d_tid, T, (const int*)p->d_cols + c0, p->d_linv, p->d_info);
     else hipLaunchKernelGGL(tsc_diag<false>, dim3(nc), dim3(128), 0, ctx->stream, p->d_tiles, (const int*)p->d_tid, T, (const int*)p->d_cols + c0, p->d_linv, p->d_info);
     if (np) hipLaunchKernelGGL(tsc_panel, dim3(np), dim3(kTPB), 0, ctx->stream, p->d_tiles, (const int*)p->d_tid, T, (const int*)p->d_pt + p0, (const double*)p->d_linv);
   }
@@ -734,19 +863,35 @@ int ccm_dense_chol_inverse_dev(ccm_ctx* ctx, double* d_A, int N, double* d_linv,
   if (N % NB) return ccm_set_error(ctx, CCM_E_ARG, "dense cholesky: N must be a multiple of 64");
   const int T = N / NB;
   CCM_HIP_CHECK(ctx, hipMemsetAsync(d_info, 0, sizeof(int), ctx->stream));
-  for (int j = 0; j < T; j++) {
-    if (diag_blocked()) hipLaunchKernelGGL(chol_diag_wave_blk, dim3(1), dim3(128), 0, ctx->stream, d_A, N, j, d_linv, d_info);
+  auto diag = [&](int j) {
+    if (diag_blocked()) hipLaunchKernelGGL(chol_diag_wave_blk, dim3(1), dim3(192), 0, ctx->stream, d_A, N, j, d_linv, d_info);
     else hipLaunchKernelGGL(chol_diag_wave, dim3(1), dim3(128), 0, ctx->stream, d_A, N, j, d_linv, d_info);
-    const int rem = T - j - 1;
-    if (rem > 0) {
-      hipLaunchKernelGGL(chol_panel, dim3(rem), dim3(kTPB), 0, ctx->stream, d_A, N, j, (const double*)d_linv, (const int*)nullptr);
-      hipLaunchKernelGGL(chol_update, dim3(rem * (rem + 1) / 2), dim3(kTPB), 0, ctx->stream, d_A, N, j, (const int*)nullptr);
+  };
+  if (chain_split()) {
+    for (int j = 0; j < T; j++) {
+      diag(j);
+      const int rem = T - j - 1;
+      if (rem > 0) {
+        hipLaunchKernelGGL(chol_panel, dim3(rem), dim3(kTPB), 0, ctx->stream, d_A, N, j, (const double*)d_linv, (const int*)nullptr);
+        hipLaunchKernelGGL(chol_update, dim3(rem * (rem + 1) / 2), dim3(kTPB), 0, ctx->stream, d_A, N, j, (const int*)nullptr);
+      }
     }
+    hipLaunchKernelGGL(chol_tri_diag, dim3(T), dim3(kTPB), 0, ctx->stream, N, (const double*)d_linv, d_X);
+    for (int k = 0; k + 1 < T; k++)
+      hipLaunchKernelGGL(chol_tri_step<false>, dim3((T - k - 1) * (k + 1) * (NB / 16)), dim3(kTPB), 0, ctx->stream, (const double*)d_A, N, (const double*)d_linv, d_X, k);
+    hipLaunchKernelGGL(chol_xtx, dim3(T * (T + 1) / 2, NB / 16), dim3(kTPB), 0, ctx->stream, (const double*)d_X, N, d_Ainv, (const double*)nullptr);
+  } else {
+    // diagonal tile j, then ONE launch: step j's panel + trailing update, and L^-1 step j - 1 beside it (see chol_step)
+    diag(0);
+    for (int j = 0; j + 1 < T; j++) {
+      const int rem = T - j - 1;
+      const int n_upd = 4 * (rem * (rem + 1) / 2), n_tri = (T - j) * j * (NB / 16);   // 4 quadrants per pair; L^-1 step k = j - 1 has (T - k - 1)(k + 1) tile products of 4 strips
+      hipLaunchKernelGGL(chol_step, dim3(n_upd + n_tri), dim3(kTPB), 0, ctx->stream, d_A, N, j, (const double*)d_linv, d_X, n_upd);
+      diag(j + 1);
+    }
+    if (T > 1) hipLaunchKernelGGL(chol_tri_step<true>, dim3((T - 1) * (NB / 16)), dim3(kTPB), 0, ctx->stream, (const double*)d_A, N, (const double*)d_linv, d_X, T - 2);
+    hipLaunchKernelGGL(chol_xtx, dim3(T * (T + 1) / 2, NB / 16), dim3(kTPB), 0, ctx->stream, (const double*)d_X, N, d_Ainv, (const double*)d_linv);
   }
-  hipLaunchKernelGGL(chol_tri_diag, dim3(T), dim3(kTPB), 0, ctx->stream, N, (const double*)d_linv, d_X);
-  for (int k = 0; k + 1 < T; k++)
-    hipLaunchKernelGGL(chol_tri_step, dim3((T - k - 1) * (k + 1), NB / 16), dim3(kTPB), 0, ctx->stream, (const double*)d_A, N, (const double*)d_linv, d_X, k);
-  hipLaunchKernelGGL(chol_xtx, dim3(T * (T + 1) / 2, NB / 16), dim3(kTPB), 0, ctx->stream, (const double*)d_X, N, d_Ainv);
   CCM_HIP_CHECK(ctx, hipGetLastError());
   return CCM_OK;
 }
