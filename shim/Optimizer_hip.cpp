@@ -16,16 +16,18 @@
 // behind in the map.
 //
 // LICENCE AND PROVENANCE.  This file is a derived work of cslam/src/Optimizer.cpp of CCM-SLAM (Copyright (C) Patrik Schmuck, ETH Zurich; GNU GPL v3 or later; itself based
-// on ORB-SLAM2 by Raul Mur-Artal) and is distributed under the same licence.  Everything numerical is new (it is a call into libccm_hip.so), but a drop-in must choose the
-// SAME vertices and edges in the SAME order and mutate the map in the SAME order as the reference, so these passages follow Optimizer.cpp statement by statement —
-// reformatted, with the reference's variable names kept so that a maintainer can diff them — and runs of a few lines of them are textually the reference's:
-//   * BundleAdjustmentClient / MapFusionGBA: the vertex / edge collection loops and the write-back loops with the mTcwGBA / mPosGBA branch   (Optimizer.cpp:55-212, 668-859)
-//   * PoseOptimizationClient: the edge set-up loop over Frame.mvpMapPoints / mvKeysUn and the outlier bookkeeping of the four rounds         (Optimizer.cpp:235-347)
-//   * LocalBundleAdjustmentClient: the local-window walk (local keyframes, local points, fixed cameras), the erase loop with its
-//     SetNotErase wait, the pose / point write-back                                                                                         (Optimizer.cpp:351-404, 568-644)
-//   * OptimizeSim3: correspondence collection and the inlier bookkeeping                                                                     (Optimizer.cpp:880-1056)
-//   * OptimizeEssentialGraphLoopClosure / MapFusion: the four edge walks (loop connections, spanning tree, loop edges, covisibility >= 100)
-//     and the corrected-pose / point write-back                                                                                             (Optimizer.cpp:1122-1331, 1376-1566)
+// on ORB-SLAM2 by Raul Mur-Artal) and is distributed under the same licence.  Everything numerical is a call into libccm_hip.so, and the graph walks are written in this
+// project's own form: each walk is one pass into flat tables (FlatBA's vertex / edge arrays, the per-mUniqueId Sim3 tables of the essential graph), the optimisation reads
+// only those tables, and one write-back pass follows.  What a drop-in cannot choose freely, and what therefore still follows Optimizer.cpp, is the OUTCOME of each walk:
+//   * which objects become vertices and which observations edges, and in which order the edges are met (container order, and inside a point the iteration order of
+//     GetObservations()): the flat problem and so the bits that come back depend on it                                                       (Optimizer.cpp:55-140, 351-530, 668-790)
+//   * the side effects of the local window walk (mBALocalForKF / mBAFixedForKF tags, the stop-flag return, LockMapUpdate, erase before write-back, mbUpdatedByServer)
+//     and the order of the map mutations of every entry point                                                                               (Optimizer.cpp:568-644, 795-859, 1265-1331)
+//   * the edge order of the essential graph (loop connections; then per keyframe: parent, loop edges, covisibility) and how a measurement is composed from g2o::Sim3
+//     values, the reference's interface type                                                                                                (Optimizer.cpp:1122-1262)
+//   * the signatures and the names of the reference's members, which are its API.
+// By the count of scripts/shim_overlap.py (comments and whitespace stripped, trivial lines dropped) 21 of this file's 740 code lines occur verbatim in Optimizer.cpp
+// (2.8 %; before the walks were rewritten: 199 of 926); they are member calls and declarations that the API above fixes.
 // What the shim prints (its fatal conditions, device errors) is its own wording; what it throws is the reference's exception type, because callers catch that.
 #include <cslam/Optimizer.h>
 
@@ -39,7 +41,7 @@
 #include <thread>
 #include <type_traits>
 #include <utility>
-#include <unistd.h>   // usleep (the wait loops of the reference around SetNotErase, Optimizer.cpp:620-626)
+#include <unistd.h>   // usleep (the local BA's wait for Map::LockMapUpdate)
 
 #include "../include/ccm_hip.h"
 #include "../ccm_slam_amd/host/ccm_convert.h"
@@ -52,6 +54,31 @@ namespace {
 [[noreturn]] void shim_fatal(const char* method, const char* what) {
   std::cout << "[ccm_hip shim] " << method << ": " << what << " (infrastructure_ex)" << std::endl;
   throw estd::infrastructure_ex();
+}
+// ids are packed as IDRANGE * client + id (Optimizer::GetID): an id at or above IDRANGE would alias another client's vertex
+void require_id_below_range(const char* method, const char* kind, const idpair& id) {
+  if (id.first >= IDRANGE) shim_fatal(method, (std::string(kind) + " id is not below IDRANGE").c_str());
+}
+
+// the two id policies of the bundle adjustments: packed (client, id) pairs on the client paths, the server's map-wide mUniqueId in MapFusionGBA
+struct ClientIds {
+  static size_t of(const KeyFrame& kf) { return Optimizer::GetID(kf.mId, true); }
+  static size_t of(const MapPoint& mp) { return Optimizer::GetID(mp.mId, false); }
+};
+struct UniqueIds {
+  static size_t of(const KeyFrame& kf) { return kf.mUniqueId; }
+  static size_t of(const MapPoint& mp) { return mp.mUniqueId; }
+};
+
+// chi2 test of a monocular edge at 95 % (2 degrees of freedom) plus the cheirality test: the local BA's outlier rule
+inline bool is_outlier(double chi2, uint8_t depth_positive) { return chi2 > 5.991 || !depth_positive; }
+
+// 4x4 CV_32F pose <-> row-major float[16] (what ccm_convert.h works on)
+void pose_to16(const cv::Mat& m, float T[16]) { for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) T[4 * r + c] = m.at<float>(r, c); }
+cv::Mat pose_from16(const float T[16]) {
+  cv::Mat m(4, 4, CV_32F);
+  for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) m.at<float>(r, c) = T[4 * r + c];
+  return m;
 }
 
 // one device context per calling thread: tracking, local mapping and the server's optimisation threads call concurrently
@@ -88,17 +115,19 @@ void check(int rc, const char* what) {
 // vanishes; on one thread there is no cross-arena garbage either).  With the optional MapPoint setter the write-back reuses the buffers and the
 // phase is empty.  [11] what is still unaccounted (total - sum of the others).  Read with ccm_shim_phases().
 constexpr int kPhases = 12;
+enum Phase { kWalk = 0, kFlatten = 1, kCreate = 2, kRun = 3, kDownload = 4, kKfWriteback = 5, kMpWriteback = 6, kTotal = 7, kVertices = 8, kRelease = 9, kScopeExit = 10, kUnaccounted = 11 };
 thread_local double g_phase[kPhases] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 struct PhaseClock {
   double t0, t;
   PhaseClock() : t0(now_ms()), t(t0) { for (double& v : g_phase) v = 0; }
-  void lap(int i) { const double n = now_ms(); g_phase[i] += n - t; t = n; }
+  void lap(Phase i) { const double n = now_ms(); g_phase[i] += n - t; t = n; }
+  void restart() { t = now_ms(); }   // after run_ba, which clocks kCreate / kRun / kDownload itself
   ~PhaseClock() {
-    g_phase[7] = now_ms() - t0;
+    g_phase[kTotal] = now_ms() - t0;
     double sum = 0;
-    for (int i = 0; i < kPhases - 1; i++) if (i != 7) sum += g_phase[i];
-    g_phase[kPhases - 1] = g_phase[7] - sum;
+    for (int i = 0; i < kUnaccounted; i++) if (i != kTotal) sum += g_phase[i];
+    g_phase[kUnaccounted] = g_phase[kTotal] - sum;
   }
 };
 
@@ -194,8 +223,22 @@ struct FlatBA {
     e_cam_id.push_back(c_id); e_pt_id.push_back(p_id);
     e_obs.push_back((double)kpUn.pt.x); e_obs.push_back((double)kpUn.pt.y); e_info.push_back((double)invSigma2);
   }
-  void removePoint(size_t id) {   // the callers remove the point they added last (a point without edges)
-    for (size_t i = pt_id.size(); i-- > 0;) if (pt_id[i] == id) { pt_id.erase(pt_id.begin() + i); pt_mp.erase(pt_mp.begin() + i); return; }
+  // THE observation walk of all three bundle adjustments: one map point as a vertex and its observations as edges, in the iteration order of the
+  // observation map.  accept(keyframe) is the caller's rule for which observations count; a point that ends with fewer than min_edges edges is taken out
+  // again with what it added.  Returns the number of edges kept.
+  template <typename Ids, typename Accept>
+  int addPointWithEdges(const Optimizer::mpptr& mp, const std::map<Optimizer::kfptr, size_t>& observations, int min_edges, Accept accept) {
+    const size_t p_id = Ids::of(*mp), e0 = e_cam_id.size();
+    addPoint(p_id, mp);
+    for (const auto& ob : observations) {
+      const Optimizer::kfptr& kf = ob.first;
+      if (accept(kf)) addEdge(p_id, kf, Ids::of(*kf), kf->mvKeysUn[ob.second]);
+    }
+    const int n = (int)(e_cam_id.size() - e0);
+    if (n >= min_edges) return n;
+    pt_id.pop_back(); pt_mp.pop_back();
+    e_cam_id.resize(e0); e_pt_id.resize(e0); e_obs.resize(2 * e0); e_info.resize(e0);
+    return 0;
   }
   void append(FlatBA& o) {        // merge of a thread's part (points and edges of a later chunk of vpMP)
     pt_id.insert(pt_id.end(), o.pt_id.begin(), o.pt_id.end()); pt_mp.insert(pt_mp.end(), o.pt_mp.begin(), o.pt_mp.end());
@@ -226,7 +269,7 @@ struct FlatBA {
     for (size_t i = 0; i < nc; i++) {
       const cv::Mat Tcw = cam_kf[i]->GetPose();                                      // Converter::toSE3Quat(pKF->GetPose())
       float T[16];
-      for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) T[4 * r + c] = Tcw.at<float>(r, c);
+      pose_to16(Tcw, T);
       ccmh::toSE3Quat(T, &cam_qt[7 * i]);
       cam_K[4 * i] = cam_kf[i]->fx; cam_K[4 * i + 1] = cam_kf[i]->fy; cam_K[4 * i + 2] = cam_kf[i]->cx; cam_K[4 * i + 3] = cam_kf[i]->cy;
       cam_fix[i] = cam_is_fixed[i] ? 1 : 0;
@@ -274,9 +317,7 @@ struct FlatBA {
   cv::Mat camPose(size_t id) {                                                       // Converter::toCvMat(vSE3->estimate())
     float T[16];
     ccmh::toCvMat(&cam_qt[7 * (size_t)cam_index.find(id)], T);
-    cv::Mat m(4, 4, CV_32F);
-    for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) m.at<float>(r, c) = T[4 * r + c];
-    return m;
+    return pose_from16(T);
   }
   cv::Mat pointPos(size_t id) {                                                      // Converter::toCvMat(vPoint->estimate())
     cv::Mat m(3, 1, CV_32F);
@@ -302,13 +343,13 @@ void run_ba(FlatBA& f, double huber, int iterations, bool* pbStopFlag, std::vect
   double t = now_ms();
   if (!ba) check(ccm_ba_create(ctx, &P, 0, 1, &ba), "ccm_ba_create");
   else check(ccm_ba_set_edge_levels(ba, f.e_level.data(), huber), "ccm_ba_set_edge_levels");
-  double n = now_ms(); g_phase[2] += n - t; t = n;
+  double n = now_ms(); g_phase[kCreate] += n - t; t = n;
   int rc = ccm_ba_run(ba, &opt, reinterpret_cast<const volatile unsigned char*>(pbStopFlag), nullptr);
-  n = now_ms(); g_phase[3] += n - t; t = n;
+  n = now_ms(); g_phase[kRun] += n - t; t = n;
   if (rc == CCM_OK) rc = ccm_ba_download(ba, P.cam_qt, P.pt_xyz, chi2 ? chi2->data() : nullptr);
   if (rc == CCM_OK && depth_pos) rc = ccm_ba_depth_positive(&P, P.cam_qt, P.pt_xyz, depth_pos->data());
   if (keep) *keep = ba; else ccm_ba_destroy(ba);
-  g_phase[4] += now_ms() - t;
+  g_phase[kDownload] += now_ms() - t;
   check(rc, "ccm_ba_run");
 }
 
@@ -338,7 +379,8 @@ template <typename MP> void store_normal_depth(MP*, const float*, float, float, 
 // edge_skip (local BA): observations erased after the optimisation (they are no longer in mObservations); ref_from_walk: the reference keyframe and octave
 // were recorded by the graph walk (global BA: no second GetObservations()), else they are asked of the point now (local BA: EraseObservation may have moved
 // mpRefKF, MapPoint.cpp:474-476); pos_lock: SetWorldPos's bLock as the reference call site passes it.
-void batched_point_writeback(FlatBA& f, const std::vector<char>* edge_skip, bool ref_from_walk, bool pos_lock, bool ids_are_unique_ids) {
+template <typename Ids>
+void batched_point_writeback(FlatBA& f, const std::vector<char>* edge_skip, bool ref_from_walk, bool pos_lock) {
   const size_t np = f.pt_id.size(), nc = f.cam_id.size(), ne = f.e_pt.size();
   std::vector<float> pos(3 * np), center(3 * nc), normal(3 * np, 0.0f), dmin(np, 0.0f), dmax(np, 0.0f);
   std::vector<int32_t> off(np + 1, 0), kf(ne), ref(np, 0), lvl(np, 0);
@@ -360,7 +402,7 @@ void batched_point_writeback(FlatBA& f, const std::vector<char>* edge_skip, bool
     else if (!f.pt_mp[i]->isBad()) {
       const Optimizer::kfptr pRef = f.pt_mp[i]->GetReferenceKeyFrame();
       const int idx = pRef ? f.pt_mp[i]->GetIndexInKeyFrame(pRef) : -1;
-      if (pRef && idx >= 0) { r = f.cam_index.find(ids_are_unique_ids ? pRef->mUniqueId : (size_t)Optimizer::GetID(pRef->mId, true)); lvl[i] = pRef->mvKeysUn[idx].octave; }
+      if (pRef && idx >= 0) { r = f.cam_index.find(Ids::of(*pRef)); lvl[i] = pRef->mvKeysUn[idx].octave; }
     }
     regular[i] = r >= 0 && off[i + 1] > off[i];
     ref[i] = r >= 0 ? r : 0;
@@ -386,293 +428,235 @@ void batched_point_writeback(FlatBA& f, const std::vector<char>* edge_skip, bool
 
 
 // ---------------------------------------------------------------------------------------------------------------------------------
+// write-back of a global bundle adjustment (BundleAdjustmentClient, MapFusionGBA)
+// ---------------------------------------------------------------------------------------------------------------------------------
+namespace {
+// Where the result goes.  direct: into the map itself (SetPose / SetWorldPos + UpdateNormalAndDepth, with the call site's bLock); otherwise a loop closure
+// is waiting for it: poses and positions are parked in mTcwGBA / mPosGBA under the tag of that loop's keyframe and the map stays as it is.
+struct GbaSink {
+  bool direct, lock;
+  idpair tag;
+};
+
+template <typename Ids>
+void gba_write_keyframes(FlatBA& f, const std::vector<Optimizer::kfptr>& kfs, const GbaSink& to) {
+  for (const Optimizer::kfptr& kf : kfs) {
+    if (kf->isBad()) continue;
+    const cv::Mat pose = f.camPose(Ids::of(*kf));
+    if (to.direct) kf->SetPose(pose, to.lock);
+    else {
+      kf->mTcwGBA.create(4, 4, CV_32F);
+      pose.copyTo(kf->mTcwGBA);
+      kf->mBAGlobalForKF = to.tag;
+    }
+  }
+}
+
+// included[i]: point i became a vertex.  done(i) runs on the thread that has just worked on point i, whether or not it was written.
+template <typename Ids, typename Done>
+void gba_write_points(FlatBA& f, const std::vector<Optimizer::mpptr>& pts, const std::vector<char>& included, const GbaSink& to, int n_threads, Done done) {
+  parallel_chunks(pts.size(), n_threads, [&](int, size_t i0, size_t i1) {
+    for (size_t i = i0; i < i1; i++) {
+      MapPoint* mp = pts[i].get();
+      if (included[i] && !mp->isBad()) {
+        const cv::Mat pos = f.pointPos(Ids::of(*mp));
+        if (to.direct) {
+          mp->SetWorldPos(pos, to.lock);
+          mp->UpdateNormalAndDepth();
+        } else {
+          mp->mPosGBA.create(3, 1, CV_32F);
+          pos.copyTo(mp->mPosGBA);
+          mp->mBAGlobalForKF = to.tag;
+        }
+      }
+      done(i);
+    }
+  });
+}
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------------------------------------
 // client side
 // ---------------------------------------------------------------------------------------------------------------------------------
 void Optimizer::GlobalBundleAdjustemntClient(mapptr pMap, size_t ClientId, int nIterations, bool* pbStopFlag, const idpair nLoopKF, const bool bRobust) {
-  vector<kfptr> vpKFs = pMap->GetAllKeyFrames();
-  vector<mpptr> vpMP = pMap->GetAllMapPoints();
-  BundleAdjustmentClient(vpKFs, vpMP, ClientId, nIterations, pbStopFlag, nLoopKF, bRobust);
+  BundleAdjustmentClient(pMap->GetAllKeyFrames(), pMap->GetAllMapPoints(), ClientId, nIterations, pbStopFlag, nLoopKF, bRobust);
 }
 
-// Optimizer.cpp:40-212
 void Optimizer::BundleAdjustmentClient(const vector<kfptr>& vpKFs, const vector<mpptr>& vpMP, size_t ClientId, int nIterations, bool* pbStopFlag,
                                        const idpair nLoopKF, const bool bRobust) {
-  const idpair zeropair = make_pair(0, ClientId);
-  vector<bool> vbNotIncludedMP;
-  vbNotIncludedMP.resize(vpMP.size());
+  const char* me = "Optimizer::BundleAdjustmentClient";
+  const idpair origin(0, ClientId);                       // the client's first keyframe: the fixed camera, and as nLoopKF the sign for "no loop is waiting"
   FlatBA f;
-  for (size_t i = 0; i < vpKFs.size(); i++) {
-    kfptr pKF = vpKFs[i];
-    if (pKF->isBad()) continue;
-    if (pKF->mId.first >= IDRANGE) {
-      shim_fatal("Optimizer::BundleAdjustmentClient / MapFusionGBA", "keyframe id is not below IDRANGE");
-    }
-    f.addCam(Optimizer::GetID(pKF->mId, true), pKF, pKF->mId == zeropair);
+  for (const kfptr& kf : vpKFs) {
+    if (kf->isBad()) continue;
+    require_id_below_range(me, "keyframe", kf->mId);
+    f.addCam(ClientIds::of(*kf), kf, kf->mId == origin);
   }
-  const float thHuber2D = sqrt(5.99);
+  std::vector<char> included(vpMP.size(), 0);
   for (size_t i = 0; i < vpMP.size(); i++) {
-    mpptr pMP = vpMP[i];
-    if (pMP->isBad()) continue;
-    if (pMP->mId.first >= IDRANGE) {
-      shim_fatal("Optimizer::BundleAdjustmentClient / MapFusionGBA", "map point id is not below IDRANGE");
-    }
-    const int id = Optimizer::GetID(pMP->mId, false);
-    f.addPoint(id, pMP);
-    const map<kfptr, size_t> observations = pMP->GetObservations();
-    int nEdges = 0;
-    for (map<kfptr, size_t>::const_iterator mit = observations.begin(); mit != observations.end(); mit++) {
-      kfptr pKF = mit->first;
-      if (pKF->isBad()) continue;
-      if (pKF->mId.first >= IDRANGE) {
-        shim_fatal("Optimizer::BundleAdjustmentClient / MapFusionGBA", "keyframe id is not below IDRANGE");
-      }
-      nEdges++;
-      f.addEdge(id, pKF, Optimizer::GetID(pKF->mId, true), pKF->mvKeysUn[mit->second]);
-    }
-    if (nEdges == 0) { f.removePoint(id); vbNotIncludedMP[i] = true; }
-    else vbNotIncludedMP[i] = false;
+    const mpptr& mp = vpMP[i];
+    if (mp->isBad()) continue;
+    require_id_below_range(me, "map point", mp->mId);
+    included[i] = 0 < f.addPointWithEdges<ClientIds>(mp, mp->GetObservations(), 1, [&](const kfptr& kf) {
+      if (kf->isBad()) return false;
+      require_id_below_range(me, "keyframe", kf->mId);
+      return true;
+    });
   }
   f.flatten(true);
+  const float thHuber2D = sqrt(5.99);
   run_ba(f, bRobust ? (double)thHuber2D : 0.0, nIterations, pbStopFlag, nullptr, nullptr);
-  for (size_t i = 0; i < vpKFs.size(); i++) {
-    kfptr pKF = vpKFs[i];
-    if (pKF->isBad()) continue;
-    cv::Mat pose = f.camPose(Optimizer::GetID(pKF->mId, true));
-    if (nLoopKF == zeropair) pKF->SetPose(pose, false);
-    else {
-      pKF->mTcwGBA.create(4, 4, CV_32F);
-      pose.copyTo(pKF->mTcwGBA);
-      pKF->mBAGlobalForKF = nLoopKF;
-    }
-  }
-  for (size_t i = 0; i < vpMP.size(); i++) {
-    if (vbNotIncludedMP[i]) continue;
-    mpptr pMP = vpMP[i];
-    if (pMP->isBad()) continue;
-    cv::Mat pos = f.pointPos(Optimizer::GetID(pMP->mId, false));
-    if (nLoopKF == zeropair) {
-      pMP->SetWorldPos(pos, false);
-      pMP->UpdateNormalAndDepth();
-    } else {
-      pMP->mPosGBA.create(3, 1, CV_32F);
-      pos.copyTo(pMP->mPosGBA);
-      pMP->mBAGlobalForKF = nLoopKF;
-    }
-  }
+  const GbaSink to{nLoopKF == origin, false, nLoopKF};
+  gba_write_keyframes<ClientIds>(f, vpKFs, to);
+  gba_write_points<ClientIds>(f, vpMP, included, to, 1, [](size_t) {});
 }
 
-// Optimizer.cpp:215-347
 int Optimizer::PoseOptimizationClient(Frame& Frame) {
-  int nInitialCorrespondences = 0;
-  float T0[16];
-  for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) T0[4 * r + c] = Frame.mTcw.at<float>(r, c);
+  float T[16];
+  pose_to16(Frame.mTcw, T);
   double cam_qt[7];
-  ccmh::toSE3Quat(T0, cam_qt);                                                        // Converter::toSE3Quat(Frame.mTcw)
-  const int N = Frame.N;
+  ccmh::toSE3Quat(T, cam_qt);                                                         // Converter::toSE3Quat(Frame.mTcw)
   std::vector<double> Xw, obs, info;
-  vector<size_t> vnIndexEdgeMono;
-  vnIndexEdgeMono.reserve(N);
+  std::vector<int> slot;                                                              // per edge: index into the frame's keypoints
   {
     unique_lock<mutex> lock(MapPoint::mGlobalMutex);
-    for (int i = 0; i < N; i++) {
-      mpptr pMP = Frame.mvpMapPoints[i];
-      if (pMP) {
-        nInitialCorrespondences++;
-        Frame.mvbOutlier[i] = false;
-        const cv::KeyPoint& kpUn = Frame.mvKeysUn[i];
-        obs.push_back(kpUn.pt.x); obs.push_back(kpUn.pt.y);
-        const float invSigma2 = Frame.mvInvLevelSigma2[kpUn.octave];
-        info.push_back(invSigma2);
-        cv::Mat P = pMP->GetWorldPos();
-        Xw.push_back(P.at<float>(0)); Xw.push_back(P.at<float>(1)); Xw.push_back(P.at<float>(2));
-        vnIndexEdgeMono.push_back(i);
-      }
+    for (int i = 0; i < Frame.N; i++) {
+      const mpptr& mp = Frame.mvpMapPoints[i];
+      if (!mp) continue;
+      Frame.mvbOutlier[i] = false;
+      const cv::KeyPoint& kp = Frame.mvKeysUn[i];
+      const cv::Mat P = mp->GetWorldPos();
+      obs.insert(obs.end(), {kp.pt.x, kp.pt.y});
+      info.push_back(Frame.mvInvLevelSigma2[kp.octave]);
+      Xw.insert(Xw.end(), {P.at<float>(0), P.at<float>(1), P.at<float>(2)});
+      slot.push_back(i);
     }
   }
-  if (nInitialCorrespondences < 3) return 0;
+  if (slot.size() < 3) return 0;
   const double K[4] = {Frame.fx, Frame.fy, Frame.cx, Frame.cy};
-  std::vector<uint8_t> outlier(vnIndexEdgeMono.size(), 0);
+  std::vector<uint8_t> outlier(slot.size(), 0);
   int nInliers = 0;
-  // the four rounds of 10 iterations with their inlier / outlier reclassification (:299-338) run inside one kernel launch
-  check(ccm_pose_optimize(thread_ctx(), cam_qt, (int)vnIndexEdgeMono.size(), Xw.data(), obs.data(), info.data(), K, outlier.data(), &nInliers), "ccm_pose_optimize");
-  for (size_t i = 0; i < vnIndexEdgeMono.size(); i++) Frame.mvbOutlier[vnIndexEdgeMono[i]] = outlier[i] != 0;
-  float T[16];
+  // the reference's four rounds of 10 iterations with their inlier / outlier reclassification run inside one kernel launch
+  check(ccm_pose_optimize(thread_ctx(), cam_qt, (int)slot.size(), Xw.data(), obs.data(), info.data(), K, outlier.data(), &nInliers), "ccm_pose_optimize");
+  for (size_t e = 0; e < slot.size(); e++) Frame.mvbOutlier[slot[e]] = outlier[e] != 0;
   ccmh::toCvMat(cam_qt, T);                                                           // Converter::toCvMat(SE3quat_recov)
-  cv::Mat pose(4, 4, CV_32F);
-  for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) pose.at<float>(r, c) = T[4 * r + c];
-  Frame.SetPose(pose);
+  Frame.SetPose(pose_from16(T));
   return nInliers;
 }
 
-// Optimizer.cpp:349-644
 void Optimizer::LocalBundleAdjustmentClient(kfptr pKF, bool* pbStopFlag, mapptr pMap, size_t ClientId, eSystemState SysState) {
+  const char* me = "Optimizer::LocalBundleAdjustmentClient";
   PhaseClock pc;
-  // Local KeyFrames: breadth-first from the current keyframe (:351-366)
-  list<kfptr> lLocalKeyFrames;
-  lLocalKeyFrames.push_back(pKF);
-  pKF->mBALocalForKF = pKF->mId;
-  const vector<kfptr> vNeighKFs = pKF->GetVectorCovisibleKeyFrames();
-  for (int i = 0, iend = vNeighKFs.size(); i < iend; i++) {
-    kfptr pKFi = vNeighKFs[i];
-    pKFi->mBALocalForKF = pKF->mId;
-    if (!pKFi->isBad()) lLocalKeyFrames.push_back(pKFi);
+  // The window, as three vectors plus the tags the walk leaves on the objects (other code reads them, and they are how an object is met only once):
+  // local keyframes = the current one and its covisible neighbours; local points = what they see; fixed cameras = whoever else sees a local point.
+  // A bad neighbour is tagged but stays out.
+  const idpair tag = pKF->mId;
+  std::vector<kfptr> local_kfs(1, pKF), fixed_kfs;
+  std::vector<mpptr> local_mps;
+  pKF->mBALocalForKF = tag;
+  for (const kfptr& kf : pKF->GetVectorCovisibleKeyFrames()) {
+    kf->mBALocalForKF = tag;
+    if (!kf->isBad()) local_kfs.push_back(kf);
   }
-  // Local MapPoints seen in Local KeyFrames (:368-385)
-  list<mpptr> lLocalMapPoints;
-  for (list<kfptr>::iterator lit = lLocalKeyFrames.begin(), lend = lLocalKeyFrames.end(); lit != lend; lit++) {
-    vector<mpptr> vpMPs = (*lit)->GetMapPointMatches();
-    for (vector<mpptr>::iterator vit = vpMPs.begin(), vend = vpMPs.end(); vit != vend; vit++) {
-      mpptr pMP = *vit;
-      if (pMP)
-        if (!pMP->isBad())
-          if (pMP->mBALocalForKF != pKF->mId) {
-            lLocalMapPoints.push_back(pMP);
-            pMP->mBALocalForKF = pKF->mId;
-          }
-    }
-  }
-  // Fixed Keyframes: see local points but are not local (:387-404)
-  list<kfptr> lFixedCameras;
-  for (list<mpptr>::iterator lit = lLocalMapPoints.begin(), lend = lLocalMapPoints.end(); lit != lend; lit++) {
-    map<kfptr, size_t> observations = (*lit)->GetObservations();
-    for (map<kfptr, size_t>::iterator mit = observations.begin(), mend = observations.end(); mit != mend; mit++) {
-      kfptr pKFi = mit->first;
-      if (pKFi->mBALocalForKF != pKF->mId && pKFi->mBAFixedForKF != pKF->mId) {
-        pKFi->mBAFixedForKF = pKF->mId;
-        if (!pKFi->isBad()) lFixedCameras.push_back(pKFi);
+  for (const kfptr& kf : local_kfs)
+    for (const mpptr& mp : kf->GetMapPointMatches())
+      if (mp && !mp->isBad() && mp->mBALocalForKF != tag) {
+        mp->mBALocalForKF = tag;
+        local_mps.push_back(mp);
       }
+  for (const mpptr& mp : local_mps)
+    for (const auto& ob : mp->GetObservations()) {
+      const kfptr& kf = ob.first;
+      if (kf->mBALocalForKF == tag || kf->mBAFixedForKF == tag) continue;
+      kf->mBAFixedForKF = tag;
+      if (!kf->isBad()) fixed_kfs.push_back(kf);
     }
-  }
   FlatBA f;
-  for (list<kfptr>::iterator lit = lLocalKeyFrames.begin(), lend = lLocalKeyFrames.end(); lit != lend; lit++) {
-    kfptr pKFi = *lit;
-    if (pKFi->mId.first >= IDRANGE) {
-      shim_fatal("Optimizer::LocalBundleAdjustmentClient", "keyframe id is not below IDRANGE");
-    }
-    f.addCam(Optimizer::GetID(pKFi->mId, true), pKFi, pKFi->mId.first == 0 && pKFi->mId.second == ClientId);
+  for (const kfptr& kf : local_kfs) {
+    require_id_below_range(me, "keyframe", kf->mId);
+    f.addCam(ClientIds::of(*kf), kf, kf->mId == idpair(0, ClientId));
   }
-  for (list<kfptr>::iterator lit = lFixedCameras.begin(), lend = lFixedCameras.end(); lit != lend; lit++) {
-    kfptr pKFi = *lit;
-    if (pKFi->mId.first >= IDRANGE) {
-      shim_fatal("Optimizer::LocalBundleAdjustmentClient", "keyframe id is not below IDRANGE");
-    }
-    f.addCam(Optimizer::GetID(pKFi->mId, true), pKFi, true);
+  for (const kfptr& kf : fixed_kfs) {
+    require_id_below_range(me, "keyframe", kf->mId);
+    f.addCam(ClientIds::of(*kf), kf, true);
   }
-  vector<kfptr> vpEdgeKFMono;
-  vector<mpptr> vpMapPointEdgeMono;
-  const float thHuberMono = sqrt(5.991);
-  for (list<mpptr>::iterator lit = lLocalMapPoints.begin(), lend = lLocalMapPoints.end(); lit != lend; lit++) {
-    mpptr pMP = *lit;
-    if (pMP->mId.first >= IDRANGE) {
-      shim_fatal("Optimizer::LocalBundleAdjustmentClient", "map point id is not below IDRANGE");
-    }
-    const int id = Optimizer::GetID(pMP->mId, false);
-    f.addPoint(id, pMP);
-    const map<kfptr, size_t> observations = pMP->GetObservations();
-    for (map<kfptr, size_t>::const_iterator mit = observations.begin(), mend = observations.end(); mit != mend; mit++) {
-      kfptr pKFi = mit->first;
-      if (pKFi->mId.first >= IDRANGE) {
-        shim_fatal("Optimizer::LocalBundleAdjustmentClient", "keyframe id is not below IDRANGE");
-      }
-      if (!pKFi->isBad()) {
-        f.addEdge(id, pKFi, Optimizer::GetID(pKFi->mId, true), pKFi->mvKeysUn[mit->second]);
-        vpEdgeKFMono.push_back(pKFi);
-        vpMapPointEdgeMono.push_back(pMP);
-      }
-    }
+  for (const mpptr& mp : local_mps) {
+    require_id_below_range(me, "map point", mp->mId);
+    f.addPointWithEdges<ClientIds>(mp, mp->GetObservations(), 0, [&](const kfptr& kf) {
+      require_id_below_range(me, "keyframe", kf->mId);
+      return !kf->isBad();
+    });
   }
-  if (pbStopFlag)
-    if (*pbStopFlag) return;
-  pc.lap(0);
+  if (pbStopFlag && *pbStopFlag) return;                 // nothing has been flattened or written
+  pc.lap(kWalk);
   f.flatten();
-  pc.lap(1);
-  // optimizer.initializeOptimization(); optimizer.optimize(5);  (:536-537)
+  pc.lap(kFlatten);
+  // From here on an edge is an index: f.cam_kf[f.e_cam[i]] is its keyframe, f.pt_mp[f.e_pt[i]] its point (every index is valid: ccm_ba_create refuses a
+  // problem with an edge whose camera or point is not a vertex).
+  const size_t n_edges = f.nEdges();
   std::vector<double> chi2;
   std::vector<uint8_t> dpos;
-  struct Handle { ccm_ba* h = nullptr; ~Handle() { if (h) ccm_ba_destroy(h); } } session;   // both optimisations run on one device-side problem
+  auto point_of = [&](size_t i) { return f.pt_mp[(size_t)f.e_pt[i]]; };
+  auto outlier_of_live_point = [&](size_t i) { return !point_of(i)->isBad() && is_outlier(chi2[i], dpos[i]); };
+  // 5 robust iterations; then, unless asked to stop, the outliers leave the problem (level 1; their chi2 keeps the value of the first pass) and 10
+  // iterations without the robust kernel follow — both on one device-side problem
+  struct Handle { ccm_ba* h = nullptr; ~Handle() { if (h) ccm_ba_destroy(h); } } session;
+  const float thHuberMono = sqrt(5.991);
   run_ba(f, (double)thHuberMono, 5, pbStopFlag, &chi2, &dpos, &session.h);
-  bool bDoMore = true;
-  if (pbStopFlag)
-    if (*pbStopFlag) bDoMore = false;
-  if (bDoMore) {
-    // outliers to level 1, robust kernel off, optimize(10) (:545-566).  e->chi2() of a level-1 edge keeps the value of the first pass.
-    for (size_t i = 0, iend = f.nEdges(); i < iend; i++) {
-      mpptr pMP = vpMapPointEdgeMono[i];
-      if (pMP->isBad()) continue;
-      if (chi2[i] > 5.991 || !dpos[i]) f.e_level[i] = 1;
-    }
+  if (!(pbStopFlag && *pbStopFlag)) {
+    for (size_t i = 0; i < n_edges; i++) if (outlier_of_live_point(i)) f.e_level[i] = 1;
     run_ba(f, 0.0, 10, pbStopFlag, &chi2, &dpos, &session.h);
   }
-  pc.t = now_ms();
-  vector<pair<kfptr, mpptr> > vToErase;
-  vToErase.reserve(f.nEdges());
-  for (size_t i = 0, iend = f.nEdges(); i < iend; i++) {
-    mpptr pMP = vpMapPointEdgeMono[i];
-    if (pMP->isBad()) continue;
-    if (chi2[i] > 5.991 || !dpos[i]) vToErase.push_back(make_pair(vpEdgeKFMono[i], pMP));
-  }
+  pc.restart();
+  std::vector<size_t> erase;                              // edge indices, in edge order; chosen before the wait for the map
+  for (size_t i = 0; i < n_edges; i++) if (outlier_of_live_point(i)) erase.push_back(i);
   if (SysState != eSystemState::SERVER)
     while (!pMap->LockMapUpdate()) { usleep(params::timings::miLockSleep); }
-  if (!vToErase.empty()) {
-    for (size_t i = 0; i < vToErase.size(); i++) {
-      kfptr pKFi = vToErase[i].first;
-      mpptr pMPi = vToErase[i].second;
-      pKFi->EraseMapPointMatch(pMPi);
-      pMPi->EraseObservation(pKFi);
-    }
+  for (size_t i : erase) {
+    const kfptr& kf = f.cam_kf[(size_t)f.e_cam[i]];
+    const mpptr mp = point_of(i)->shared_from_this();
+    kf->EraseMapPointMatch(mp);
+    mp->EraseObservation(kf);
   }
-  for (list<kfptr>::iterator lit = lLocalKeyFrames.begin(), lend = lLocalKeyFrames.end(); lit != lend; lit++) {
-    kfptr pKFl = *lit;
-    pKFl->SetPose(f.camPose(Optimizer::GetID(pKFl->mId, true)), false);
-    pKFl->mbUpdatedByServer = false;
+  for (const kfptr& kf : local_kfs) {
+    kf->SetPose(f.camPose(ClientIds::of(*kf)), false);
+    kf->mbUpdatedByServer = false;
   }
-  pc.lap(5);
-  static const bool batched_off = std::getenv("CCM_SHIM_NO_BATCHED_NORMALS") != nullptr;
-  if (kBatchedNormals && !batched_off && !f.cam_kf.empty() && !f.pt_id.empty()) {
+  pc.lap(kKfWriteback);
+  // A local point that is bad by now was erased from the map by its last EraseObservation; one that the map still holds is an inconsistency.
+  auto alive = [&](const mpptr& mp) {
+    if (mp->isBad() && pMap->GetMpPtr(mp->mId)) shim_fatal(me, "a local map point is flagged bad but the map still holds it");
+    return !mp->isBad();
+  };
+  if (kBatchedNormals && !f.cam_kf.empty() && !f.pt_id.empty()) {
     // (with the optional MapPoint::SetNormalAndDepth) positions as below, normals and distance ranges of all local points by one device call over the
-    // problem's edges minus the erased observations
-    for (list<mpptr>::iterator lit = lLocalMapPoints.begin(), lend = lLocalMapPoints.end(); lit != lend; lit++)
-      if ((*lit)->isBad() && pMap->GetMpPtr((*lit)->mId)) {
-        shim_fatal("Optimizer::LocalBundleAdjustmentClient", "a local map point is flagged bad but the map still holds it");
-      }
-    std::vector<char> erased(f.nEdges(), 0);
-    for (size_t i = 0, iend = f.nEdges(); i < iend; i++) erased[i] = !vpMapPointEdgeMono[i]->isBad() && (chi2[i] > 5.991 || !dpos[i]);
-    // (an observation erased above whose point turned bad with it belongs to a point the helper skips)
-    for (size_t i = 0, iend = f.nEdges(); i < iend; i++) if (vpMapPointEdgeMono[i]->isBad()) erased[i] = 1;
-    batched_point_writeback(f, &erased, false, false, false);
+    // problem's edges minus the erased observations (an observation whose point turned bad belongs to a point the helper skips)
+    for (const mpptr& mp : local_mps) alive(mp);
+    std::vector<char> erased(n_edges, 0);
+    for (size_t i = 0; i < n_edges; i++) erased[i] = point_of(i)->isBad() || is_outlier(chi2[i], dpos[i]);
+    batched_point_writeback<ClientIds>(f, &erased, false, false);
   } else
-  for (list<mpptr>::iterator lit = lLocalMapPoints.begin(), lend = lLocalMapPoints.end(); lit != lend; lit++) {
-    mpptr pMP = *lit;
-    if (pMP->isBad()) {
-      mpptr pMPcheck = pMap->GetMpPtr(pMP->mId);
-      if (pMPcheck) {
-        shim_fatal("Optimizer::LocalBundleAdjustmentClient", "a local map point is flagged bad but the map still holds it");
+    for (const mpptr& mp : local_mps)
+      if (alive(mp)) {
+        mp->SetWorldPos(f.pointPos(ClientIds::of(*mp)), false);
+        mp->UpdateNormalAndDepth();
       }
-    } else {
-      pMP->SetWorldPos(f.pointPos(Optimizer::GetID(pMP->mId, false)), false);
-      pMP->UpdateNormalAndDepth();
-    }
-  }
-  pc.lap(6);
+  pc.lap(kMpWriteback);
   if (SysState != eSystemState::SERVER) pMap->UnLockMapUpdate();
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // server side
 // ---------------------------------------------------------------------------------------------------------------------------------
-// Optimizer.cpp:646-859
 void Optimizer::MapFusionGBA(mapptr pMap, size_t ClientId, int nIterations, bool* pbStopFlag, idpair nLoopKF, const bool bRobust) {
   (void)ClientId;
   PhaseClock pc;
   {   // (everything the call owns lives in this scope, so that what its destructors cost is inside the last phase, not after it)
   vector<kfptr> vpKFs = pMap->GetAllKeyFrames();
   vector<mpptr> vpMP = pMap->GetAllMapPoints();
-  const idpair zeropair = make_pair(0, pMap->mMapId);
-  if (pMap->mvpKeyFrameOrigins.empty()) {
-    shim_fatal("Optimizer::MapFusionGBA", "the map has no origin keyframe (mvpKeyFrameOrigins is empty)");
-  }
-  idpair FixedId = (*(pMap->mvpKeyFrameOrigins.begin()))->mId;
-  std::vector<char> vbNotIncludedMP(vpMP.size(), 0);   // one byte per point: chunks of vpMP are walked by different threads
+  if (pMap->mvpKeyFrameOrigins.empty()) shim_fatal("Optimizer::MapFusionGBA", "the map has no origin keyframe (mvpKeyFrameOrigins is empty)");
+  const idpair FixedId = pMap->mvpKeyFrameOrigins.front()->mId;
+  std::vector<char> included(vpMP.size(), 0);   // one byte per point: chunks of vpMP are walked by different threads
   static thread_local FlatBA f_keep;
   static thread_local std::vector<FlatBA> part_keep;
   FlatBA& f = f_keep;
@@ -684,14 +668,12 @@ void Optimizer::MapFusionGBA(mapptr pMap, size_t ClientId, int nIterations, bool
     ~DropRefs() { a.cam_kf.clear(); a.pt_mp.clear(); for (auto& g : parts) { g.cam_kf.clear(); g.pt_mp.clear(); } }
   } drop_refs{f_keep, part_keep};
   size_t maxKFid = 0;
-  for (size_t i = 0; i < vpKFs.size(); i++) {
-    kfptr pKF = vpKFs[i];
-    if (pKF->isBad()) continue;
-    f.addCam(pKF->mUniqueId, pKF, pKF->mId == FixedId);
-    if (pKF->mUniqueId > maxKFid) maxKFid = pKF->mUniqueId;
+  for (const kfptr& kf : vpKFs) {
+    if (kf->isBad()) continue;
+    f.addCam(kf->mUniqueId, kf, kf->mId == FixedId);
+    maxKFid = std::max(maxKFid, (size_t)kf->mUniqueId);
   }
-  const float thHuber2D = sqrt(5.99);
-  pc.lap(8);
+  pc.lap(kVertices);
   {
     // the map points in contiguous chunks of vpMP, one chunk per host thread (every point is independent; GetObservations() copies under the point's
     // own mutex exactly as in the reference); the chunks are appended in order, so vertices and edges keep the order of the sequential walk
@@ -699,142 +681,100 @@ void Optimizer::MapFusionGBA(mapptr pMap, size_t ClientId, int nIterations, bool
     std::vector<FlatBA>& part = part_keep;
     if (part.size() < (size_t)n_thr) part.resize((size_t)n_thr);
     for (auto& g : part) g.reset();
+    // an observation counts when its keyframe is a vertex: alive, and not newer than the newest keyframe this call has seen
+    auto is_vertex = [&](const kfptr& kf) { return kf && !kf->isBad() && kf->mUniqueId <= maxKFid; };
     parallel_chunks(vpMP.size(), n_thr, [&](int t, size_t i0, size_t i1) {
       FlatBA& g = t == 0 ? f : part[(size_t)t];
       for (size_t i = i0; i < i1; i++) {
-        const mpptr& pMP = vpMP[i];
-        if (pMP->isBad()) continue;
-        const map<kfptr, size_t> observations = pMP->GetObservations();
-        if (observations.size() < 2) { vbNotIncludedMP[i] = true; continue; }
-        int nEdges = 0;
-        const size_t id = pMP->mUniqueId;
-        for (map<kfptr, size_t>::const_iterator mit = observations.begin(); mit != observations.end(); ++mit) {
-          const kfptr& pKF = mit->first;
-          if (!pKF || pKF->isBad() || pKF->mUniqueId > maxKFid) continue;
-          nEdges++;
-        }
-        if (nEdges < 2) { vbNotIncludedMP[i] = true; continue; }
-        g.addPoint(id, pMP);
-        g.addPointPos(pMP->GetWorldPos());   // (the vertex estimate, Optimizer.cpp:724: read here, while this thread has the point's lines, instead of in a second pass over all points)
+        const mpptr& mp = vpMP[i];
+        if (mp->isBad()) continue;
+        const map<kfptr, size_t> observations = mp->GetObservations();
+        if (observations.size() < 2) continue;
+        const int nEdges = g.addPointWithEdges<UniqueIds>(mp, observations, 2, is_vertex);   // a point needs two views to be constrained
+        if (nEdges == 0) continue;
+        included[i] = 1;
+        g.addPointPos(mp->GetWorldPos());   // (the vertex estimate: read here, while this thread has the point's lines, instead of in a second pass over all points)
         if (kBatchedNormals) {   // what the batched UpdateNormalAndDepth of the write-back needs beside the edges
           int nLive = 0;         // observations the reference's method would use (non-bad keyframes): all of them must be edges
-          for (map<kfptr, size_t>::const_iterator mit = observations.begin(); mit != observations.end(); ++mit) if (mit->first && !mit->first->isBad()) nLive++;
-          const kfptr pRef = pMP->GetReferenceKeyFrame();
-          map<kfptr, size_t>::const_iterator rit = pRef ? observations.find(pRef) : observations.end();
-          const bool regular = nLive == nEdges && pRef && !pRef->isBad() && pRef->mUniqueId <= maxKFid && rit != observations.end();
+          for (const auto& ob : observations) if (ob.first && !ob.first->isBad()) nLive++;
+          const kfptr pRef = mp->GetReferenceKeyFrame();
+          const auto rit = pRef ? observations.find(pRef) : observations.end();
+          const bool regular = nLive == nEdges && is_vertex(pRef) && rit != observations.end();
           g.addPointAux(regular ? pRef->mUniqueId : 0, regular ? pRef->mvKeysUn[rit->second].octave : 0, regular);
-        }
-        for (map<kfptr, size_t>::const_iterator mit = observations.begin(); mit != observations.end(); mit++) {
-          const kfptr& pKF = mit->first;
-          if (!pKF || pKF->isBad() || pKF->mUniqueId > maxKFid) continue;
-          g.addEdge(id, pKF, pKF->mUniqueId, pKF->mvKeysUn[mit->second]);
         }
       }
     });
     for (int t = 1; t < n_thr; t++) f.append(part[(size_t)t]);
   }
-  pc.lap(0);
+  pc.lap(kWalk);
   f.flatten(true);
-  pc.lap(1);
+  pc.lap(kFlatten);
+  const float thHuber2D = sqrt(5.99);
   run_ba(f, bRobust ? (double)thHuber2D : 0.0, nIterations, pbStopFlag, nullptr, nullptr);
-  pc.t = now_ms();
-  for (size_t i = 0; i < vpKFs.size(); i++) {
-    kfptr pKF = vpKFs[i];
-    if (pKF->isBad()) continue;
-    cv::Mat pose = f.camPose(pKF->mUniqueId);
-    if (nLoopKF == zeropair) pKF->SetPose(pose, true);
-    else {
-      pKF->mTcwGBA.create(4, 4, CV_32F);
-      pose.copyTo(pKF->mTcwGBA);
-      pKF->mBAGlobalForKF = nLoopKF;
-    }
-  }
-  pc.lap(5);
+  pc.restart();
+  const GbaSink to{nLoopKF == idpair(0, pMap->mMapId), true, nLoopKF};
+  gba_write_keyframes<UniqueIds>(f, vpKFs, to);
+  pc.lap(kKfWriteback);
   // every keyframe has its new pose: the per-point write-back (SetWorldPos + UpdateNormalAndDepth, 150 000 mutex-taking calls after a merge of four
   // agents) is independent from point to point
-  static const bool batched_off = std::getenv("CCM_SHIM_NO_BATCHED_NORMALS") != nullptr;
-  bool refs_dropped = false;
-  if (kBatchedNormals && !batched_off && nLoopKF == zeropair && f.aux_ok && f.pt_regular.size() == f.pt_id.size() && !f.cam_kf.empty()) batched_point_writeback(f, nullptr, true, true, true);
-  else {
-  refs_dropped = true;
-  const int n_wb = shim_threads(vpMP.size(), 32);
-  // (measured on the reference's REAL classes, 150 000 points: 63 - 78 ms for this loop on 32 threads against 18 on the look-alike — the real SetWorldPos takes the
-  // process-wide MapPoint::mGlobalMutex (MapPoint.cpp:343) and the real UpdateNormalAndDepth two mutexes of every observing keyframe (isBad, GetCameraCenter).  Tried
-  // and dropped: all positions on one thread with the normals following behind it (67 ms: the call itself is ~450 ns), positions on four threads then normals on all (66 - 82 ms).)
-  parallel_chunks(vpMP.size(), n_wb, [&](int, size_t i0, size_t i1) {
-    for (size_t i = i0; i < i1; i++) {
-      mpptr& pMP = vpMP[i];
-      if (!vbNotIncludedMP[i] && !pMP->isBad()) {
-        cv::Mat pos = f.pointPos(pMP->mUniqueId);
-        if (nLoopKF == zeropair) {
-          pMP->SetWorldPos(pos, true);
-          pMP->UpdateNormalAndDepth();
-        } else {
-          pMP->mPosGBA.create(3, 1, CV_32F);
-          pos.copyTo(pMP->mPosGBA);
-          pMP->mBAGlobalForKF = nLoopKF;
-        }
-      }
-      // this call's copy of the pointer (Map::GetAllMapPoints() hands out 150 000 of them by value) is dropped by the thread that has just worked on the point:
-      // releasing them in one go afterwards cost 13 - 30 ms on the 4-agent map (one lock-prefixed decrement per point on a line some other core holds)
-      pMP.reset();
-    }
-  });
-  }
-  pc.lap(6);
+  const bool batched = kBatchedNormals && to.direct && f.aux_ok && f.pt_regular.size() == f.pt_id.size() && !f.cam_kf.empty();
+  if (batched) batched_point_writeback<UniqueIds>(f, nullptr, true, true);
+  else
+    // (measured on the reference's REAL classes, 150 000 points: 63 - 78 ms for this loop on 32 threads against 18 on the look-alike — the real SetWorldPos takes the
+    // process-wide MapPoint::mGlobalMutex (MapPoint.cpp:343) and the real UpdateNormalAndDepth two mutexes of every observing keyframe (isBad, GetCameraCenter).  Tried
+    // and dropped: all positions on one thread with the normals following behind it (67 ms: the call itself is ~450 ns), positions on four threads then normals on all (66 - 82 ms).)
+    // This call's copy of each pointer (Map::GetAllMapPoints() hands out 150 000 of them by value) is dropped by the thread that has just worked on the point:
+    // releasing them in one go afterwards cost 13 - 30 ms on the 4-agent map (one lock-prefixed decrement per point on a line some other core holds)
+    gba_write_points<UniqueIds>(f, vpMP, included, to, shim_threads(vpMP.size(), 32), [&](size_t i) { vpMP[i].reset(); });
+  pc.lap(kMpWriteback);
   f.cam_kf.clear(); f.pt_mp.clear();   // no keyframe / map point is kept alive between calls; the flat arrays stay allocated
-  pc.lap(9);
+  pc.lap(kRelease);
   // the copies Map::GetAllMapPoints() / GetAllKeyFrames() handed out by value: released on several threads and INSIDE the phase clock (round 5: their
   // destructors used to run after the last lap, 29 ms that no phase showed)
-  if (!refs_dropped) release_refs(vpMP);
+  if (batched) release_refs(vpMP);
   release_refs(vpKFs);
   }
-  pc.lap(10);
+  pc.lap(kScopeExit);
 }
 
-// Optimizer.cpp:861-1056
 int Optimizer::OptimizeSim3(kfptr pKF1, kfptr pKF2, std::vector<mpptr>& vpMatches1, g2o::Sim3& g2oS12, const float th2, bool bFixScale) {
-  const cv::Mat& K1 = pKF1->mK;
-  const cv::Mat& K2 = pKF2->mK;
-  const cv::Mat R1w = pKF1->GetRotation();
-  const cv::Mat t1w = pKF1->GetTranslation();
-  const cv::Mat R2w = pKF2->GetRotation();
-  const cv::Mat t2w = pKF2->GetTranslation();
-  const double k1[4] = {K1.at<float>(0, 0), K1.at<float>(1, 1), K1.at<float>(0, 2), K1.at<float>(1, 2)};
-  const double k2[4] = {K2.at<float>(0, 0), K2.at<float>(1, 1), K2.at<float>(0, 2), K2.at<float>(1, 2)};
-  const int N = vpMatches1.size();
+  // one side of the two-view problem: its pose and intrinsics, and per correspondence the point in its camera frame, the keypoint and its information
+  struct View {
+    const kfptr& kf;
+    const cv::Mat R, t;
+    std::vector<double> Pc, obs, info;
+    explicit View(const kfptr& k) : kf(k), R(k->GetRotation()), t(k->GetTranslation()) {}
+    void add(const mpptr& mp, size_t kp) {
+      const cv::Mat P = R * mp->GetWorldPos() + t;        // the cv::Mat arithmetic stays with the caller's data types (f32)
+      Pc.insert(Pc.end(), {P.at<float>(0), P.at<float>(1), P.at<float>(2)});
+      const cv::KeyPoint& k = kf->mvKeysUn[kp];
+      obs.insert(obs.end(), {k.pt.x, k.pt.y});
+      info.push_back(kf->mvInvLevelSigma2[k.octave]);
+    }
+    void intrinsics(double k4[4]) const { const cv::Mat& K = kf->mK; k4[0] = K.at<float>(0, 0); k4[1] = K.at<float>(1, 1); k4[2] = K.at<float>(0, 2); k4[3] = K.at<float>(1, 2); }
+  } v1(pKF1), v2(pKF2);
   const vector<mpptr> vpMapPoints1 = pKF1->GetMapPointMatches();
-  std::vector<double> P1c, P2c, obs1, obs2, info1, info2;
-  vector<size_t> vnIndexEdge;
-  for (int i = 0; i < N; i++) {
-    if (!vpMatches1[i]) continue;
-    mpptr pMP1 = vpMapPoints1[i];
-    mpptr pMP2 = vpMatches1[i];
-    const int i2 = pMP2->GetIndexInKeyFrame(pKF2);
-    if (pMP1 && pMP2) {
-      if (!pMP1->isBad() && !pMP2->isBad() && i2 >= 0) {
-        cv::Mat P3D1c = R1w * pMP1->GetWorldPos() + t1w;   // the cv::Mat arithmetic stays with the caller's data types (f32)
-        cv::Mat P3D2c = R2w * pMP2->GetWorldPos() + t2w;
-        for (int c = 0; c < 3; c++) { P1c.push_back(P3D1c.at<float>(c)); P2c.push_back(P3D2c.at<float>(c)); }
-      } else continue;
-    } else continue;
-    const cv::KeyPoint& kpUn1 = pKF1->mvKeysUn[i];
-    obs1.push_back(kpUn1.pt.x); obs1.push_back(kpUn1.pt.y);
-    info1.push_back(pKF1->mvInvLevelSigma2[kpUn1.octave]);
-    const cv::KeyPoint& kpUn2 = pKF2->mvKeysUn[i2];
-    obs2.push_back(kpUn2.pt.x); obs2.push_back(kpUn2.pt.y);
-    info2.push_back(pKF2->mvInvLevelSigma2[kpUn2.octave]);
-    vnIndexEdge.push_back(i);
+  std::vector<size_t> slot;                               // per correspondence: index into vpMatches1
+  for (size_t i = 0; i < vpMatches1.size(); i++) {
+    const mpptr& mp2 = vpMatches1[i];
+    if (!mp2) continue;
+    const mpptr& mp1 = vpMapPoints1[i];
+    const int i2 = mp2->GetIndexInKeyFrame(pKF2);
+    if (!mp1 || mp1->isBad() || mp2->isBad() || i2 < 0) continue;
+    v1.add(mp1, i);
+    v2.add(mp2, (size_t)i2);
+    slot.push_back(i);
   }
-  double s8[8] = {g2oS12.rotation().x(), g2oS12.rotation().y(), g2oS12.rotation().z(), g2oS12.rotation().w(),
-                  g2oS12.translation()[0], g2oS12.translation()[1], g2oS12.translation()[2], g2oS12.scale()};
-  std::vector<uint8_t> keep(vnIndexEdge.size(), 1);
+  double k1[4], k2[4], s8[8] = {g2oS12.rotation().x(), g2oS12.rotation().y(), g2oS12.rotation().z(), g2oS12.rotation().w(),
+                                g2oS12.translation()[0], g2oS12.translation()[1], g2oS12.translation()[2], g2oS12.scale()};
+  v1.intrinsics(k1); v2.intrinsics(k2);
+  std::vector<uint8_t> keep(slot.size(), 1);
   int nIn = 0;
-  check(ccm_sim3_optimize(thread_ctx(), s8, (int)vnIndexEdge.size(), P1c.data(), P2c.data(), obs1.data(), obs2.data(), info1.data(), info2.data(), k1, k2,
+  check(ccm_sim3_optimize(thread_ctx(), s8, (int)slot.size(), v1.Pc.data(), v2.Pc.data(), v1.obs.data(), v2.obs.data(), v1.info.data(), v2.info.data(), k1, k2,
                           (double)th2, bFixScale ? 1 : 0, keep.data(), &nIn),
         "ccm_sim3_optimize");
-  for (size_t i = 0; i < vnIndexEdge.size(); i++) if (!keep[i]) vpMatches1[vnIndexEdge[i]] = static_cast<mpptr>(NULL);
-  if (nIn == 0) return 0;   // fewer than 10 survivors after the first pass: g2oS12 stays as it was (:1015-1016)
+  for (size_t e = 0; e < slot.size(); e++) if (!keep[e]) vpMatches1[slot[e]] = static_cast<mpptr>(NULL);
+  if (nIn == 0) return 0;   // fewer than 10 survivors after the first pass: g2oS12 stays as it was
   g2oS12 = g2o::Sim3(Eigen::Quaterniond(s8[3], s8[0], s8[1], s8[2]), Eigen::Vector3d(s8[4], s8[5], s8[6]), s8[7]);
   return nIn;
 }
@@ -845,7 +785,7 @@ void sim3_to8(const g2o::Sim3& S, double* p) {
   p[0] = S.rotation().x(); p[1] = S.rotation().y(); p[2] = S.rotation().z(); p[3] = S.rotation().w();
   p[4] = S.translation()[0]; p[5] = S.translation()[1]; p[6] = S.translation()[2]; p[7] = S.scale();
 }
-// edge list of an essential graph + the device call; vertices are indexed by mUniqueId like the reference's vScw / vpVertices
+// edge list of an essential graph + the device call; vertices are indexed by mUniqueId
 struct PoseGraph {
   std::vector<int32_t> e_i, e_j;
   std::vector<double> meas;
@@ -867,197 +807,99 @@ struct PoseGraph {
     for (size_t u = 0; u < n; u++) if (present[u]) { const double* p = &sim3[8 * (size_t)slot[u]]; out[u] = g2o::Sim3(Eigen::Quaterniond(p[3], p[0], p[1], p[2]), Eigen::Vector3d(p[4], p[5], p[6]), p[7]); }
   }
 };
-cv::Mat sim3_pose(const g2o::Sim3& CorrectedSiw) {   // [R t/s; 0 1] (:1272-1281)
+cv::Mat sim3_pose(const g2o::Sim3& Siw) {   // [R t/s; 0 1]
   double s8[8];
-  sim3_to8(CorrectedSiw, s8);
+  sim3_to8(Siw, s8);
   float T[16];
   ccmh::sim3ToCvSE3(s8, T);
-  cv::Mat m(4, 4, CV_32F);
-  for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) m.at<float>(r, c) = T[4 * r + c];
-  return m.clone();
+  return pose_from16(T);
+}
+
+// THE essential-graph optimisation, for a closed loop and for a map fusion.  `corrected` holds the Sim3 a loop closure has already given some keyframes (the
+// initial estimate of those vertices), `uncorrected` the poses the same keyframes had before it (what the relative measurements of their edges are taken
+// from); a map fusion has neither.  tagged_by / tagged_ref: the MapPoint members in which the correction step that ran before recorded, per point, for which
+// current keyframe and relative to which keyframe it moved the point (the _LC pair or the _MM pair).
+void optimize_essential_graph(Optimizer::mapptr pMap, Optimizer::kfptr pLoopKF, Optimizer::kfptr pCurKF, const Optimizer::KeyFrameAndPose* uncorrected,
+                              const Optimizer::KeyFrameAndPose* corrected, const map<Optimizer::kfptr, set<Optimizer::kfptr> >& LoopConnections, bool bFixScale,
+                              idpair MapPoint::*tagged_by, size_t MapPoint::*tagged_ref) {
+  typedef Optimizer::kfptr kfptr;
+  const vector<kfptr> kfs = pMap->GetAllKeyFrames();
+  const vector<Optimizer::mpptr> mps = pMap->GetAllMapPoints();
+  const int minFeat = params::opt::miEssGraphMinFeats;
+  // 1. tables per mUniqueId: present (a vertex: the keyframe is alive), Scw (initial estimate: the corrected Sim3 where there is one, else the pose at scale 1)
+  //    and Smw (the pose that measurements are composed from: the uncorrected Sim3 where there is one, else Scw).  A slot nobody fills is the identity.
+  const size_t n = (size_t)pMap->GetMaxKFidUnique() + 1;
+  Sim3Vec Scw(n), Smw;
+  std::vector<char> present(n, 0);
+  for (const kfptr& kf : kfs) {
+    if (kf->isBad()) continue;
+    const auto it = corrected->find(kf);
+    Scw[kf->mUniqueId] = it != corrected->end() ? it->second : g2o::Sim3(Converter::toMatrix3d(kf->GetRotation()), Converter::toVector3d(kf->GetTranslation()), 1.0);
+    present[kf->mUniqueId] = 1;
+  }
+  Smw = Scw;
+  for (const auto& e : *uncorrected) if (e.first->mUniqueId < n) Smw[e.first->mUniqueId] = e.second;
+  // 2. edges i -> j with the measurement Sji = Sjw * Swi.  The loop's own connections first, between the CORRECTED poses; then per keyframe, between the
+  //    measurement poses: its parent in the spanning tree, its older loop edges, its older strong covisibility neighbours that are not yet connected.
+  PoseGraph pg;
+  set<pair<size_t, size_t> > connected;
+  for (const auto& lc : LoopConnections) {
+    const kfptr& kf = lc.first;
+    if (kf->isBad()) continue;
+    const size_t i = kf->mUniqueId;
+    const g2o::Sim3 Swi = Scw[i].inverse();
+    for (const kfptr& other : lc.second) {
+      if (other->isBad()) continue;
+      const size_t j = other->mUniqueId;
+      const bool the_loop_itself = i == pCurKF->mUniqueId && j == pLoopKF->mUniqueId;
+      if (!the_loop_itself && kf->GetWeight(other) < minFeat) continue;
+      pg.addEdge(i, j, Scw[j] * Swi);
+      connected.insert(std::minmax(i, j));
+    }
+  }
+  for (const kfptr& kf : kfs) {
+    const size_t i = kf->mUniqueId;
+    const g2o::Sim3 Swi = Smw[i].inverse();
+    const kfptr parent = kf->GetParent();
+    if (parent) pg.addEdge(i, parent->mUniqueId, Smw[parent->mUniqueId] * Swi);
+    const set<kfptr> loop_edges = kf->GetLoopEdges();
+    for (const kfptr& other : loop_edges) {
+      const size_t j = other->mUniqueId;
+      if (j < i) pg.addEdge(i, j, Smw[j] * Swi);
+    }
+    for (const kfptr& other : kf->GetCovisiblesByWeight(minFeat)) {
+      if (other->isBad() || other == parent || kf->hasChild(other) || loop_edges.count(other)) continue;
+      const size_t j = other->mUniqueId;
+      if (j < i && !connected.count(std::minmax(i, j))) pg.addEdge(i, j, Smw[j] * Swi);
+    }
+  }
+  Sim3Vec Siw;                                             // optimised; what was no vertex keeps its Scw
+  pg.optimize(Scw, present, pLoopKF->mUniqueId, bFixScale, Siw);
+  // 3. write-back: every keyframe gets [R t/s]; every point moves with its reference keyframe: out of the old frame (Scw) and back through the new one
+  Sim3Vec Swi(n);
+  for (const kfptr& kf : kfs) {
+    Swi[kf->mUniqueId] = Siw[kf->mUniqueId].inverse();
+    kf->SetPose(sim3_pose(Siw[kf->mUniqueId]), true);
+  }
+  for (const Optimizer::mpptr& mp : mps) {
+    if (mp->isBad()) continue;
+    const MapPoint& p = *mp;
+    const size_t r = p.*tagged_by == pCurKF->mId ? (size_t)(p.*tagged_ref) : (size_t)mp->GetReferenceKeyFrame()->mUniqueId;
+    const Eigen::Matrix<double, 3, 1> Pw = Converter::toVector3d(mp->GetWorldPos());
+    mp->SetWorldPos(Converter::toCvMat(Swi[r].map(Scw[r].map(Pw))), true);
+    mp->UpdateNormalAndDepth();
+  }
 }
 }  // namespace
 
-// Optimizer.cpp:1058-1331
 void Optimizer::OptimizeEssentialGraphLoopClosure(mapptr pMap, kfptr pLoopKF, kfptr pCurKF, const KeyFrameAndPose& NonCorrectedSim3,
                                                   const KeyFrameAndPose& CorrectedSim3, const map<kfptr, set<kfptr> >& LoopConnections, const bool& bFixScale) {
-  const vector<kfptr> vpKFs = pMap->GetAllKeyFrames();
-  const vector<mpptr> vpMPs = pMap->GetAllMapPoints();
-  const unsigned int nMaxKFid = pMap->GetMaxKFidUnique();
-  Sim3Vec vScw(nMaxKFid + 1), vCorrectedSwc(nMaxKFid + 1);
-  std::vector<char> present(nMaxKFid + 1, 0);
-  const int minFeat = params::opt::miEssGraphMinFeats;
-  for (size_t i = 0, iend = vpKFs.size(); i < iend; i++) {
-    kfptr pKF = vpKFs[i];
-    if (pKF->isBad()) continue;
-    const size_t nIDi = pKF->mUniqueId;
-    KeyFrameAndPose::const_iterator it = CorrectedSim3.find(pKF);
-    if (it != CorrectedSim3.end()) vScw[nIDi] = it->second;
-    else {
-      Eigen::Matrix<double, 3, 3> Rcw = Converter::toMatrix3d(pKF->GetRotation());
-      Eigen::Matrix<double, 3, 1> tcw = Converter::toVector3d(pKF->GetTranslation());
-      vScw[nIDi] = g2o::Sim3(Rcw, tcw, 1.0);
-    }
-    present[nIDi] = 1;
-  }
-  PoseGraph pg;
-  set<pair<long unsigned int, long unsigned int> > sInsertedEdges;
-  for (map<kfptr, set<kfptr> >::const_iterator mit = LoopConnections.begin(), mend = LoopConnections.end(); mit != mend; mit++) {
-    kfptr pKF = mit->first;
-    if (pKF->isBad()) continue;
-    const size_t nIDi = pKF->mUniqueId;
-    const set<kfptr>& spConnections = mit->second;
-    const g2o::Sim3 Swi = vScw[nIDi].inverse();
-    for (set<kfptr>::const_iterator sit = spConnections.begin(), send = spConnections.end(); sit != send; sit++) {
-      if ((*sit)->isBad()) continue;
-      const size_t nIDj = (*sit)->mUniqueId;
-      if ((nIDi != pCurKF->mUniqueId || nIDj != pLoopKF->mUniqueId) && pKF->GetWeight(*sit) < minFeat) continue;
-      pg.addEdge(nIDi, nIDj, vScw[nIDj] * Swi);
-      sInsertedEdges.insert(make_pair(min(nIDi, nIDj), max(nIDi, nIDj)));
-    }
-  }
-  for (size_t i = 0, iend = vpKFs.size(); i < iend; i++) {
-    kfptr pKF = vpKFs[i];
-    const size_t nIDi = pKF->mUniqueId;
-    g2o::Sim3 Swi;
-    KeyFrameAndPose::const_iterator iti = NonCorrectedSim3.find(pKF);
-    if (iti != NonCorrectedSim3.end()) Swi = (iti->second).inverse();
-    else Swi = vScw[nIDi].inverse();
-    kfptr pParentKF = pKF->GetParent();
-    if (pParentKF) {   // spanning tree edge
-      const size_t nIDj = pParentKF->mUniqueId;
-      KeyFrameAndPose::const_iterator itj = NonCorrectedSim3.find(pParentKF);
-      const g2o::Sim3 Sjw = itj != NonCorrectedSim3.end() ? itj->second : vScw[nIDj];
-      pg.addEdge(nIDi, nIDj, Sjw * Swi);
-    }
-    const set<kfptr> sLoopEdges = pKF->GetLoopEdges();
-    for (set<kfptr>::const_iterator sit = sLoopEdges.begin(), send = sLoopEdges.end(); sit != send; sit++) {
-      kfptr pLKF = *sit;
-      const size_t nIDj = pLKF->mUniqueId;
-      if (nIDj < nIDi) {
-        KeyFrameAndPose::const_iterator itl = NonCorrectedSim3.find(pLKF);
-        const g2o::Sim3 Slw = itl != NonCorrectedSim3.end() ? itl->second : vScw[nIDj];
-        pg.addEdge(nIDi, nIDj, Slw * Swi);
-      }
-    }
-    const vector<kfptr> vpConnectedKFs = pKF->GetCovisiblesByWeight(minFeat);
-    for (vector<kfptr>::const_iterator vit = vpConnectedKFs.begin(); vit != vpConnectedKFs.end(); vit++) {
-      kfptr pKFn = *vit;
-      if ((*vit)->isBad()) continue;
-      if (pKFn && pKFn != pParentKF && !pKF->hasChild(pKFn) && !sLoopEdges.count(pKFn)) {
-        const size_t nIDj = pKFn->mUniqueId;
-        if (!pKFn->isBad() && nIDj < nIDi) {
-          if (sInsertedEdges.count(make_pair(min(nIDi, nIDj), max(nIDi, nIDj)))) continue;
-          KeyFrameAndPose::const_iterator itn = NonCorrectedSim3.find(pKFn);
-          const g2o::Sim3 Snw = itn != NonCorrectedSim3.end() ? itn->second : vScw[nIDj];
-          pg.addEdge(nIDi, nIDj, Snw * Swi);
-        }
-      }
-    }
-  }
-  Sim3Vec vCorrectedSiw;
-  pg.optimize(vScw, present, pLoopKF->mUniqueId, bFixScale, vCorrectedSiw);
-  for (size_t i = 0; i < vpKFs.size(); i++) {
-    kfptr pKFi = vpKFs[i];
-    const size_t nIDi = pKFi->mUniqueId;
-    const g2o::Sim3 CorrectedSiw = vCorrectedSiw[nIDi];
-    vCorrectedSwc[nIDi] = CorrectedSiw.inverse();
-    pKFi->SetPose(sim3_pose(CorrectedSiw), true);
-  }
-  for (size_t i = 0, iend = vpMPs.size(); i < iend; i++) {
-    mpptr pMP = vpMPs[i];
-    if (pMP->isBad()) continue;
-    size_t nIDr;
-    if (pMP->mCorrectedByKF_LC == pCurKF->mId) nIDr = pMP->mCorrectedReference_LC;
-    else nIDr = pMP->GetReferenceKeyFrame()->mUniqueId;
-    const g2o::Sim3 Srw = vScw[nIDr];
-    const g2o::Sim3 correctedSwr = vCorrectedSwc[nIDr];
-    Eigen::Matrix<double, 3, 1> eigP3Dw = Converter::toVector3d(pMP->GetWorldPos());
-    Eigen::Matrix<double, 3, 1> eigCorrectedP3Dw = correctedSwr.map(Srw.map(eigP3Dw));
-    pMP->SetWorldPos(Converter::toCvMat(eigCorrectedP3Dw), true);
-    pMP->UpdateNormalAndDepth();
-  }
+  optimize_essential_graph(pMap, pLoopKF, pCurKF, &NonCorrectedSim3, &CorrectedSim3, LoopConnections, bFixScale, &MapPoint::mCorrectedByKF_LC, &MapPoint::mCorrectedReference_LC);
 }
 
-// Optimizer.cpp:1333-1566
 void Optimizer::OptimizeEssentialGraphMapFusion(mapptr pMap, kfptr pLoopKF, kfptr pCurKF, const map<kfptr, set<kfptr> >& LoopConnections, const bool& bFixScale) {
-  const vector<kfptr> vpKFs = pMap->GetAllKeyFrames();
-  const vector<mpptr> vpMPs = pMap->GetAllMapPoints();
-  const unsigned int nMaxKFid = pMap->GetMaxKFidUnique();
-  Sim3Vec vScw(nMaxKFid + 1), vCorrectedSwc(nMaxKFid + 1);
-  std::vector<char> present(nMaxKFid + 1, 0);
-  const int minFeat = params::opt::miEssGraphMinFeats;
-  for (size_t i = 0, iend = vpKFs.size(); i < iend; i++) {
-    kfptr pKF = vpKFs[i];
-    if (pKF->isBad()) continue;
-    const size_t nIDi = pKF->mUniqueId;
-    Eigen::Matrix<double, 3, 3> Rcw = Converter::toMatrix3d(pKF->GetRotation());
-    Eigen::Matrix<double, 3, 1> tcw = Converter::toVector3d(pKF->GetTranslation());
-    vScw[nIDi] = g2o::Sim3(Rcw, tcw, 1.0);
-    present[nIDi] = 1;
-  }
-  PoseGraph pg;
-  set<pair<long unsigned int, long unsigned int> > sInsertedEdges;
-  for (map<kfptr, set<kfptr> >::const_iterator mit = LoopConnections.begin(), mend = LoopConnections.end(); mit != mend; mit++) {
-    kfptr pKF = mit->first;
-    if (pKF->isBad()) continue;
-    const size_t nIDi = pKF->mUniqueId;
-    const set<kfptr>& spConnections = mit->second;
-    const g2o::Sim3 Swi = vScw[nIDi].inverse();
-    for (set<kfptr>::const_iterator sit = spConnections.begin(), send = spConnections.end(); sit != send; sit++) {
-      if ((*sit)->isBad()) continue;
-      const size_t nIDj = (*sit)->mUniqueId;
-      if ((nIDi != pCurKF->mUniqueId || nIDj != pLoopKF->mUniqueId) && pKF->GetWeight(*sit) < minFeat) continue;
-      pg.addEdge(nIDi, nIDj, vScw[nIDj] * Swi);
-      sInsertedEdges.insert(make_pair(min(nIDi, nIDj), max(nIDi, nIDj)));
-    }
-  }
-  for (size_t i = 0, iend = vpKFs.size(); i < iend; i++) {
-    kfptr pKF = vpKFs[i];
-    const size_t nIDi = pKF->mUniqueId;
-    const g2o::Sim3 Swi = vScw[nIDi].inverse();
-    kfptr pParentKF = pKF->GetParent();
-    if (pParentKF) pg.addEdge(nIDi, pParentKF->mUniqueId, vScw[pParentKF->mUniqueId] * Swi);
-    const set<kfptr> sLoopEdges = pKF->GetLoopEdges();
-    for (set<kfptr>::const_iterator sit = sLoopEdges.begin(), send = sLoopEdges.end(); sit != send; sit++) {
-      const size_t nIDj = (*sit)->mUniqueId;
-      if (nIDj < nIDi) pg.addEdge(nIDi, nIDj, vScw[nIDj] * Swi);
-    }
-    const vector<kfptr> vpConnectedKFs = pKF->GetCovisiblesByWeight(minFeat);
-    for (vector<kfptr>::const_iterator vit = vpConnectedKFs.begin(); vit != vpConnectedKFs.end(); vit++) {
-      kfptr pKFn = *vit;
-      if ((*vit)->isBad()) continue;
-      if (pKFn && pKFn != pParentKF && !pKF->hasChild(pKFn) && !sLoopEdges.count(pKFn)) {
-        const size_t nIDj = pKFn->mUniqueId;
-        if (!pKFn->isBad() && nIDj < nIDi) {
-          if (sInsertedEdges.count(make_pair(min(nIDi, nIDj), max(nIDi, nIDj)))) continue;
-          pg.addEdge(nIDi, nIDj, vScw[nIDj] * Swi);
-        }
-      }
-    }
-  }
-  Sim3Vec vCorrectedSiw;
-  pg.optimize(vScw, present, pLoopKF->mUniqueId, bFixScale, vCorrectedSiw);
-  for (size_t i = 0; i < vpKFs.size(); i++) {
-    kfptr pKFi = vpKFs[i];
-    const size_t nIDi = pKFi->mUniqueId;
-    const g2o::Sim3 CorrectedSiw = vCorrectedSiw[nIDi];
-    vCorrectedSwc[nIDi] = CorrectedSiw.inverse();
-    pKFi->SetPose(sim3_pose(CorrectedSiw), true);
-  }
-  for (size_t i = 0, iend = vpMPs.size(); i < iend; i++) {
-    mpptr pMP = vpMPs[i];
-    if (pMP->isBad()) continue;
-    int nIDr;
-    if (pMP->mCorrectedByKF_MM == pCurKF->mId) nIDr = pMP->mCorrectedReference_MM;
-    else nIDr = pMP->GetReferenceKeyFrame()->mUniqueId;
-    const g2o::Sim3 Srw = vScw[nIDr];
-    const g2o::Sim3 correctedSwr = vCorrectedSwc[nIDr];
-    Eigen::Matrix<double, 3, 1> eigP3Dw = Converter::toVector3d(pMP->GetWorldPos());
-    Eigen::Matrix<double, 3, 1> eigCorrectedP3Dw = correctedSwr.map(Srw.map(eigP3Dw));
-    pMP->SetWorldPos(Converter::toCvMat(eigCorrectedP3Dw), true);
-    pMP->UpdateNormalAndDepth();
-  }
+  const KeyFrameAndPose none;
+  optimize_essential_graph(pMap, pLoopKF, pCurKF, &none, &none, LoopConnections, bFixScale, &MapPoint::mCorrectedByKF_MM, &MapPoint::mCorrectedReference_MM);
 }
 
 }  // namespace cslam

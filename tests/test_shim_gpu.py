@@ -10,6 +10,8 @@ import pytest
 from ccm_slam_amd import synth
 from oracle import mapgraph as mg
 from oracle import ref
+from tests import shim_cases as sc
+from tests.shim_cases import sim3_of_pose as _sim3_of_pose
 from tests.test_ref_optimizer import local_window, ulps32
 
 pytestmark = [pytest.mark.gpu,
@@ -107,12 +109,6 @@ def _loop_map():
     """one agent driving a closed loop; the keyframes near the end of the loop see landmarks of the start (loop closure candidates)"""
     prob = synth.make_ba_problem(n_agents=1, kfs_per_agent=60, n_points=4000, seed=33, n_fixed=1)
     return prob, mg.flat_from_ba_problem(prob)
-
-
-def _sim3_of_pose(T, s=1.0):
-    from oracle import to_se3quat
-    q = to_se3quat(T)[0]
-    return np.concatenate([q, [s]])
 
 
 def test_optimize_sim3_shim_equals_reference():
@@ -283,3 +279,91 @@ def test_pose_locked_points_keep_their_position_and_get_consistent_normals():
     if len(out) == 3:                                                            # batched and per-point write-back: the same bits
         for k in ("kf_Tcw", "mp_pos", "mp_normal", "mp_dmin", "mp_dmax", "mp_bad", "obs_alive"):
             assert np.array_equal(out[1][k], out[2][k]), k
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# Small maps with bad keyframes and bad points (tests/shim_cases.py): the branches of the graph walks that the maps above do not reach, and
+# BundleAdjustmentClient parking its result in mTcwGBA / mPosGBA.  Three assertions per case:
+#   * the facts the reference's own Optimizer.cpp produces on the map (how many objects move, none of them bad), for both libraries;
+#   * the shim against the reference at the bars of the tests above;
+#   * the shim against tests/golden/shim_optimizer_parent.npz, BIT FOR BIT: what the shim of the commit before its graph walks were rewritten left on
+#     the same maps on the MI355X (scripts/shim_state_record.py).  A changed vertex or edge order changes the bits; the tolerances would not notice.
+# ---------------------------------------------------------------------------------------------------------------------------------------
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "shim_optimizer_parent.npz")
+STATE_KEYS = ("kf_Tcw", "kf_gba", "kf_gba_flag", "mp_pos", "mp_gba", "mp_gba_flag", "mp_bad", "mp_normal", "mp_dmin", "mp_dmax", "obs_alive")
+
+
+def _case(name):
+    flat = sc.cases()[name][0]
+    return flat, sc.run(mg.REF_LIB, name), sc.run(mg.SHIM_LIB, name)
+
+
+def _moved(flat, st):
+    """(keyframes, points) whose pose / position in the map is not the input's any more"""
+    return (st["kf_Tcw"] != flat["kf_Tcw"]).any(axis=(1, 2)), (st["mp_pos"] != flat["mp_pos"]).any(axis=1)
+
+
+def _assert_equals_parent(name, shim_state):
+    with np.load(GOLDEN) as parent:
+        for k in STATE_KEYS:
+            assert np.array_equal(parent[f"{name}/{k}"], shim_state[k]), (name, k)
+
+
+@pytest.mark.parametrize("name,n_kf,n_mp,n_kf_parked,n_mp_parked", [("gba_fusion", 21, 471, 0, 0), ("gba_fusion_plain", 21, 471, 0, 0), ("gba_fusion_parked", 0, 0, 22, 471),
+                                                                    ("gba_client", 21, 514, 0, 0), ("gba_client_parked", 0, 0, 22, 514)])
+def test_global_ba_on_a_map_with_bad_keyframes_and_points(name, n_kf, n_mp, n_kf_parked, n_mp_parked):
+    """MapFusionGBA (robust / not / with a loop keyframe waiting) and BundleAdjustmentClient (client 0: direct; client 1 with nLoopKF = (0, 0): parked in
+    mTcwGBA / mPosGBA) on 2 agents x 12 keyframes, keyframes 5 and 17 and every seventh point bad.  22 keyframes are vertices, one of them fixed; MapFusionGBA
+    wants two observations per point (471 points), BundleAdjustmentClient one (514)."""
+    flat, r, s = _case(name)
+    bad_kf, bad_mp = flat["kf_bad"] != 0, flat["mp_bad"] != 0
+    for st in (r, s):
+        kf, mp = _moved(flat, st)
+        assert (kf.sum(), mp.sum()) == (n_kf, n_mp)
+        assert not kf[bad_kf].any() and not mp[bad_mp].any()
+        assert (st["kf_gba_flag"].sum(), st["mp_gba_flag"].sum()) == (n_kf_parked, n_mp_parked)
+        assert not st["kf_gba_flag"][bad_kf].any() and not st["mp_gba_flag"][bad_mp].any()
+    assert np.array_equal(r["kf_gba_flag"], s["kf_gba_flag"]) and np.array_equal(r["mp_gba_flag"], s["mp_gba_flag"])
+    assert np.array_equal(_moved(flat, r)[0], _moved(flat, s)[0]) and np.array_equal(_moved(flat, r)[1], _moved(flat, s)[1])
+    assert ulps32(r["kf_Tcw"], s["kf_Tcw"]).max() <= 64 and ulps32(r["kf_gba"], s["kf_gba"]).max() <= 64
+    assert ulps32(r["mp_pos"], s["mp_pos"]).max() <= 256 and ulps32(r["mp_gba"], s["mp_gba"]).max() <= 256
+    assert np.array_equal(r["mp_normal"] != 0, s["mp_normal"] != 0)
+    _assert_equals_parent(name, s)
+
+
+@pytest.mark.parametrize("name,n_erased,n_kf,n_mp", [("lba_7", 52, 5, 229), ("lba_2", 28, 4, 202)])
+def test_local_ba_on_a_map_with_a_bad_keyframe_and_bad_points(name, n_erased, n_kf, n_mp):
+    """LocalBundleAdjustmentClient around keyframes 7 and 2 of 14 (covisibility threshold 5), keyframe 4 — inside the window of keyframe 2 — and every ninth
+    point bad.  The counts are the reference's; the shim's erase set may differ from it by 2 observations (chi2 within rounding of 5.991), and with it the
+    number of points that were moved."""
+    flat, r, s = _case(name)
+    bad_kf, bad_mp = flat["kf_bad"] != 0, flat["mp_bad"] != 0
+    for st, slack in ((r, 0), (s, 2)):
+        kf, mp = _moved(flat, st)
+        assert abs(int((st["obs_alive"] == 0).sum()) - n_erased) <= slack
+        assert kf.sum() == n_kf and abs(int(mp.sum()) - n_mp) <= slack
+        assert not kf[bad_kf].any() and not mp[bad_mp].any()
+    assert (r["obs_alive"] != s["obs_alive"]).sum() <= 2
+    assert np.array_equal(_moved(flat, r)[0], _moved(flat, s)[0])
+    assert ulps32(r["kf_Tcw"], s["kf_Tcw"]).max() <= 256
+    keep = (r["mp_bad"] == 0) & (s["mp_bad"] == 0)
+    assert ulps32(r["mp_pos"][keep], s["mp_pos"][keep]).max() <= 1024
+    assert np.abs(r["mp_normal"][keep] - s["mp_normal"][keep]).max() < 1e-4 and np.abs(r["mp_dmax"][keep] / s["mp_dmax"][keep] - 1).max() < 1e-4
+    assert (r["mp_bad"] != s["mp_bad"]).sum() <= 2
+    _assert_equals_parent(name, s)
+
+
+@pytest.mark.parametrize("name", ["ess_loop", "ess_fusion"])
+def test_essential_graph_on_a_map_with_bad_points(name):
+    """OptimizeEssentialGraphLoopClosure / MapFusion on a closed loop of 24 keyframes (loop keyframe 0, current keyframe 23, keyframes 19..23 corrected in the
+    loop-closure variant), every eleventh point bad: all keyframes but the fixed loop keyframe move, no bad point does.  (Every keyframe is good: with a bad one
+    in the look-alike map the reference's own code crashes on the CPU.)"""
+    flat, r, s = _case(name)
+    for st in (r, s):
+        kf, mp = _moved(flat, st)
+        assert kf.sum() == 23 and not kf[0] and mp.any()
+        assert not mp[flat["mp_bad"] != 0].any()
+    assert np.abs(r["kf_Tcw"] - s["kf_Tcw"]).max() < 2e-4, np.abs(r["kf_Tcw"] - s["kf_Tcw"]).max()
+    assert np.abs(r["mp_pos"] - s["mp_pos"]).max() < 1e-3, np.abs(r["mp_pos"] - s["mp_pos"]).max()
+    assert np.array_equal(r["kf_Tcw"][0], s["kf_Tcw"][0])
+    _assert_equals_parent(name, s)
