@@ -17,6 +17,8 @@
 #include "common.h"
 #include "sim3_math.h"
 #include "lane_xor.h"
+#include "test_internal.h"
+#include "../../include/ccm_testhooks.h"   // ccm_pg_debug_out, the output block of pg_debug_solve below
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -729,35 +731,35 @@ int al(ccm_ctx* ctx, PgAllocs& allocs, size_t n, T** out) {
   return CCM_OK;
 }
 
-}  // namespace
+enum { kPgTiles = 0, kPgDense = 1, kPgForest = 2, kPgJacobi = 3 };   // linear solvers of (H + lambda I) x = b
 
-#define PG_RC(x) do { int rc_ = (x); if (rc_) { hipStreamSynchronize(ctx->stream); for (auto& p_ : allocs) ccm_pool_put(ctx, p_.first, p_.second); return rc_; } } while (0)
+// ---- host structure of one graph: free slots, active edges, H blocks with their gather lists, block-CSR rows, spanning forest ----
+struct PgHost {
+  int V = 0, F = 0, E = 0, nBlk = 0;
+  std::vector<int> slot, free_v, ei, ej, act;           // act[e] = index of active edge e in the caller's edge list
+  std::vector<double> ms;
+  std::vector<std::pair<int, int>> keys;                // block k = (a, b), a <= b; the F diagonal blocks first
+  std::vector<int> blk_off, blk_edge, vtx_off, vtx_edge, row_off, row_col;
+  std::vector<uint32_t> row_blk;
+  std::vector<int> t_parent, t_code, t_order, t_pos, t_out, ends_off, ends_idx;   // filled by pg_host_forest only
+};
 
-extern "C" int ccm_pose_graph_optimize(ccm_ctx* ctx, int n_vert, double* sim3, const uint8_t* fixed, int fix_scale, int n_edge,
-                                       const int32_t* e_i, const int32_t* e_j, const double* meas, int max_iters, double lambda_init,
-                                       const volatile unsigned char* stop_flag, ccm_pg_stats* stats) {
-  if (!ctx || n_vert < 0 || n_edge < 0 || (n_vert && (!sim3 || !fixed)) || (n_edge && (!e_i || !e_j || !meas)) || max_iters < 0)
-    return ccm_set_error(ctx, CCM_E_ARG, "ccm_pose_graph_optimize: bad args");
-  ccm_pg_stats st{};
-  if (stats) *stats = st;
-  for (int e = 0; e < n_edge; e++)
-    if (e_i[e] < 0 || e_i[e] >= n_vert || e_j[e] < 0 || e_j[e] >= n_vert || e_i[e] == e_j[e])
-      return ccm_set_error(ctx, CCM_E_ARG, "ccm_pose_graph_optimize: edge vertex index out of range");
-  CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  // ---- structure (host): slots, active edges, blocks, gather lists, block-CSR rows ----
-  std::vector<int> slot(n_vert, -1), free_v;
-  for (int v = 0; v < n_vert; v++) if (!fixed[v]) { slot[v] = (int)free_v.size(); free_v.push_back(v); }
-  const int F = (int)free_v.size();
-  std::vector<int> ei, ej; std::vector<double> ms;
+void pg_host_structure(int n_vert, const uint8_t* fixed, int n_edge, const int32_t* e_i, const int32_t* e_j, const double* meas, PgHost* h) {
+  h->V = n_vert;
+  h->slot.assign(n_vert, -1);
+  for (int v = 0; v < n_vert; v++) if (!fixed[v]) { h->slot[v] = (int)h->free_v.size(); h->free_v.push_back(v); }
+  const int F = h->F = (int)h->free_v.size();
+  const std::vector<int>& slot = h->slot;
+  std::vector<int>&ei = h->ei, &ej = h->ej;
   for (int e = 0; e < n_edge; e++) {
     if (fixed[e_i[e]] && fixed[e_j[e]]) continue;       // not in the active set (all vertices fixed)
-    ei.push_back(e_i[e]); ej.push_back(e_j[e]);
-    ms.insert(ms.end(), meas + 8 * (size_t)e, meas + 8 * (size_t)e + 8);
+    ei.push_back(e_i[e]); ej.push_back(e_j[e]); h->act.push_back(e);
+    h->ms.insert(h->ms.end(), meas + 8 * (size_t)e, meas + 8 * (size_t)e + 8);
   }
-  const int E = (int)ei.size();
-  if (F == 0 || E == 0) return CCM_OK;
+  const int E = h->E = (int)ei.size();
+  if (F == 0 || E == 0) return;
   std::map<std::pair<int, int>, int> blk;
-  std::vector<std::pair<int, int>> keys;
+  std::vector<std::pair<int, int>>& keys = h->keys;
   for (int a = 0; a < F; a++) { blk[{a, a}] = a; keys.push_back({a, a}); }
   for (int e = 0; e < E; e++) {
     const int a = slot[ei[e]], b = slot[ej[e]];
@@ -765,7 +767,7 @@ extern "C" int ccm_pose_graph_optimize(ccm_ctx* ctx, int n_vert, double* sim3, c
     const std::pair<int, int> k{std::min(a, b), std::max(a, b)};
     if (!blk.count(k)) { blk[k] = (int)keys.size(); keys.push_back(k); }
   }
-  const int nBlk = (int)keys.size();
+  const int nBlk = h->nBlk = (int)keys.size();
   std::vector<std::vector<int>> bl(nBlk), vl(F);
   for (int e = 0; e < E; e++) {
     const int a = slot[ei[e]], b = slot[ej[e]];
@@ -773,198 +775,371 @@ extern "C" int ccm_pose_graph_optimize(ccm_ctx* ctx, int n_vert, double* sim3, c
     if (b >= 0) { bl[b].push_back(e * 4 + 3); vl[b].push_back(e * 2 + 1); }                  // Jj^T Jj
     if (a >= 0 && b >= 0) bl[blk[{std::min(a, b), std::max(a, b)}]].push_back(e * 4 + (a < b ? 1 : 2));   // rows = lower slot's side
   }
-  std::vector<int> blk_off(nBlk + 1, 0), blk_edge, vtx_off(F + 1, 0), vtx_edge;
-  for (int k = 0; k < nBlk; k++) { blk_edge.insert(blk_edge.end(), bl[k].begin(), bl[k].end()); blk_off[k + 1] = (int)blk_edge.size(); }
-  for (int a = 0; a < F; a++) { vtx_edge.insert(vtx_edge.end(), vl[a].begin(), vl[a].end()); vtx_off[a + 1] = (int)vtx_edge.size(); }
+  h->blk_off.assign(nBlk + 1, 0); h->vtx_off.assign(F + 1, 0);
+  for (int k = 0; k < nBlk; k++) { h->blk_edge.insert(h->blk_edge.end(), bl[k].begin(), bl[k].end()); h->blk_off[k + 1] = (int)h->blk_edge.size(); }
+  for (int a = 0; a < F; a++) { h->vtx_edge.insert(h->vtx_edge.end(), vl[a].begin(), vl[a].end()); h->vtx_off[a + 1] = (int)h->vtx_edge.size(); }
   std::vector<std::vector<std::pair<int, uint32_t>>> rows(F);
   for (int k = 0; k < nBlk; k++) {
     const int a = keys[k].first, b = keys[k].second;
     rows[a].push_back({b, (uint32_t)k});
     if (a != b) rows[b].push_back({a, (uint32_t)k | kT});
   }
-  std::vector<int> row_off(F + 1, 0), row_col; std::vector<uint32_t> row_blk;
+  h->row_off.assign(F + 1, 0);
   for (int a = 0; a < F; a++) {
     std::sort(rows[a].begin(), rows[a].end(), [](const std::pair<int, uint32_t>& x, const std::pair<int, uint32_t>& y) { return x.first < y.first; });
-    for (auto& pr : rows[a]) { row_col.push_back(pr.first); row_blk.push_back(pr.second); }
-    row_off[a + 1] = (int)row_col.size();
+    for (auto& pr : rows[a]) { h->row_col.push_back(pr.first); h->row_blk.push_back(pr.second); }
+    h->row_off[a + 1] = (int)h->row_col.size();
   }
-  // ---- spanning forest for the preconditioner: Kruskal by |i - j| (local edges first), all fixed vertices = one root ----
-  const bool use_tree = F <= kPgTreeMaxF;
-  std::vector<int> t_parent(F, -1), t_code(F, -1), t_order, t_pos(F, 0), t_out(F, 0), ends_off(F + 2, 0), ends_idx;
-  if (use_tree) {
-    std::vector<int> eo(E);
-    for (int e = 0; e < E; e++) eo[e] = e;
-    std::stable_sort(eo.begin(), eo.end(), [&](int x, int y) { return std::abs(ei[x] - ej[x]) < std::abs(ei[y] - ej[y]); });
-    std::vector<int> uf(F + 1);                       // node F = the fixed super-node
-    for (int i = 0; i <= F; i++) uf[i] = i;
-    auto find = [&](int x) { while (uf[x] != x) { uf[x] = uf[uf[x]]; x = uf[x]; } return x; };
-    std::vector<std::vector<std::pair<int, int>>> adj(F + 1);   // (neighbour, edge)
-    for (int e : eo) {
-      const int a = slot[ei[e]] < 0 ? F : slot[ei[e]], b = slot[ej[e]] < 0 ? F : slot[ej[e]];
-      const int ra = find(a), rb = find(b);
-      if (ra == rb) continue;
-      uf[ra] = rb;
-      adj[a].push_back({b, e}); adj[b].push_back({a, e});
-    }
-    // DFS preorder from the fixed super-node, then from every still unvisited node (components without a fixed vertex)
-    std::vector<char> seen(F + 1, 0);
-    std::vector<std::pair<int, int>> stack;          // (node, next child index)
-    auto dfs = [&](int root) {
-      stack.clear(); stack.push_back({root, 0}); seen[root] = 1;
-      if (root < F) { t_pos[root] = (int)t_order.size(); t_order.push_back(root); }
-      while (!stack.empty()) {
-        auto& top = stack.back();
-        const int u = top.first;
-        if (top.second < (int)adj[u].size()) {
-          const auto [v, e] = adj[u][top.second++];
-          if (seen[v]) continue;
-          seen[v] = 1;
-          t_parent[v] = (u == F) ? -1 : u;
-          t_code[v] = e * 2 + (slot[ei[e]] == v ? 0 : 1);
-          t_pos[v] = (int)t_order.size(); t_order.push_back(v);
-          stack.push_back({v, 0});
-        } else {
-          if (u < F) t_out[u] = (int)t_order.size();
-          stack.pop_back();
-        }
+}
+
+// spanning forest for the preconditioner: Kruskal by |i - j| (local edges first), all fixed vertices = one root
+void pg_host_forest(PgHost* h) {
+  const int F = h->F, E = h->E;
+  const std::vector<int>&slot = h->slot, &ei = h->ei, &ej = h->ej;
+  std::vector<int>&t_parent = h->t_parent, &t_code = h->t_code, &t_order = h->t_order, &t_pos = h->t_pos, &t_out = h->t_out;
+  t_parent.assign(F, -1); t_code.assign(F, -1); t_order.clear(); t_pos.assign(F, 0); t_out.assign(F, 0); h->ends_off.assign(F + 2, 0); h->ends_idx.clear();
+  std::vector<int> eo(E);
+  for (int e = 0; e < E; e++) eo[e] = e;
+  std::stable_sort(eo.begin(), eo.end(), [&](int x, int y) { return std::abs(ei[x] - ej[x]) < std::abs(ei[y] - ej[y]); });
+  std::vector<int> uf(F + 1);                       // node F = the fixed super-node
+  for (int i = 0; i <= F; i++) uf[i] = i;
+  auto find = [&](int x) { while (uf[x] != x) { uf[x] = uf[uf[x]]; x = uf[x]; } return x; };
+  std::vector<std::vector<std::pair<int, int>>> adj(F + 1);   // (neighbour, edge)
+  for (int e : eo) {
+    const int a = slot[ei[e]] < 0 ? F : slot[ei[e]], b = slot[ej[e]] < 0 ? F : slot[ej[e]];
+    const int ra = find(a), rb = find(b);
+    if (ra == rb) continue;
+    uf[ra] = rb;
+    adj[a].push_back({b, e}); adj[b].push_back({a, e});
+  }
+  // DFS preorder from the fixed super-node, then from every still unvisited node (components without a fixed vertex)
+  std::vector<char> seen(F + 1, 0);
+  std::vector<std::pair<int, int>> stack;          // (node, next child index)
+  auto dfs = [&](int root) {
+    stack.clear(); stack.push_back({root, 0}); seen[root] = 1;
+    if (root < F) { t_pos[root] = (int)t_order.size(); t_order.push_back(root); }
+    while (!stack.empty()) {
+      auto& top = stack.back();
+      const int u = top.first;
+      if (top.second < (int)adj[u].size()) {
+        const auto [v, e] = adj[u][top.second++];
+        if (seen[v]) continue;
+        seen[v] = 1;
+        t_parent[v] = (u == F) ? -1 : u;
+        t_code[v] = e * 2 + (slot[ei[e]] == v ? 0 : 1);
+        t_pos[v] = (int)t_order.size(); t_order.push_back(v);
+        stack.push_back({v, 0});
+      } else {
+        if (u < F) t_out[u] = (int)t_order.size();
+        stack.pop_back();
       }
-    };
-    dfs(F);
-    for (int a = 0; a < F; a++) if (!seen[a]) dfs(a);
-    std::vector<std::vector<int>> ends(F + 1);
-    for (int a = 0; a < F; a++) ends[t_out[a]].push_back(a);
-    for (int pos = 0; pos <= F; pos++) { ends_idx.insert(ends_idx.end(), ends[pos].begin(), ends[pos].end()); ends_off[pos + 1] = (int)ends_idx.size(); }
-  }
-  // ---- device state ----
+    }
+  };
+  dfs(F);
+  for (int a = 0; a < F; a++) if (!seen[a]) dfs(a);
+  std::vector<std::vector<int>> ends(F + 1);
+  for (int a = 0; a < F; a++) ends[t_out[a]].push_back(a);
+  for (int pos = 0; pos <= F; pos++) { h->ends_idx.insert(h->ends_idx.end(), ends[pos].begin(), ends[pos].end()); h->ends_off[pos + 1] = (int)h->ends_idx.size(); }
+}
+
+// ---- device state of one graph and one solver ----
+struct PgState {
+  ccm_ctx* ctx = nullptr;
   PgAllocs allocs;
   PgDev d{};
-  d.V = n_vert; d.F = F; d.E = E; d.nBlk = nBlk; d.fix_scale = fix_scale ? 1 : 0;
-  std::vector<double> s0(sim3, sim3 + 8 * (size_t)n_vert);
-  int *p_i = nullptr; uint32_t* p_u = nullptr; double* p_d = nullptr;
-  PG_RC(up(ctx, allocs, s0, &d.S[0])); PG_RC(up(ctx, allocs, s0, &d.S[1]));
-  PG_RC(up(ctx, allocs, slot, &p_i)); d.slot = p_i;
-  PG_RC(up(ctx, allocs, free_v, &p_i)); d.free_v = p_i;
-  PG_RC(up(ctx, allocs, ei, &p_i)); d.ei = p_i;
-  PG_RC(up(ctx, allocs, ej, &p_i)); d.ej = p_i;
-  PG_RC(up(ctx, allocs, ms, &p_d)); d.meas = p_d;
-  PG_RC(up(ctx, allocs, blk_off, &p_i)); d.blk_off = p_i;
-  PG_RC(up(ctx, allocs, blk_edge, &p_i)); d.blk_edge = p_i;
-  PG_RC(up(ctx, allocs, vtx_off, &p_i)); d.vtx_off = p_i;
-  PG_RC(up(ctx, allocs, vtx_edge, &p_i)); d.vtx_edge = p_i;
-  PG_RC(up(ctx, allocs, row_off, &p_i)); d.row_off = p_i;
-  PG_RC(up(ctx, allocs, row_col, &p_i)); d.row_col = p_i;
-  PG_RC(up(ctx, allocs, row_blk, &p_u)); d.row_blk = p_u;
-  // solver: exact dense Cholesky (default, reproduces the reference's LM path) or tree-preconditioned PCG (CCM_PG_SOLVER=pcg, or
-  // graphs whose dense matrix would not fit the budget below: faster, but an inexact-Newton path)
-  const char* solver_env = getenv("CCM_PG_SOLVER");
-  const size_t n_dense = 7 * (size_t)F;
-  const int N_dense = (int)((n_dense + 63) / 64) * 64;
-  // exact solver, default form: tile-sparse, level-scheduled Cholesky over a nested-dissection order (ccm_tsc: only the non-zero tiles are
-  // stored, so the size limit is the tile-pattern table, not a dense array); CCM_PG_SOLVER=dense keeps the round-1 form (dense array of
-  // <= 24 000 unknowns, natural order, one tile column after the other) for comparison
-  const bool want_exact = !(solver_env && !strcmp(solver_env, "pcg"));
-  // (<= 20 000 keyframes: the symbolic step keeps dense T x T tile-pattern tables on host and device, T ~ 4000 tiles at that size, and packs tile
-  // coordinates as (i << 16) | j in a signed int, i.e. T < 32768; larger graphs take the tree-preconditioned PCG path)
-  const bool use_tiles = want_exact && !(solver_env && !strcmp(solver_env, "dense")) && n_dense <= 140000;
-  const bool use_dense = want_exact && (use_tiles || n_dense <= 24000);
-  double *d_A = nullptr, *d_rhs = nullptr, *d_linv = nullptr; int *d_info = nullptr, *d_blk_a = nullptr, *d_blk_b = nullptr;
+  int solver = kPgTiles;
+  int n_wg_init = 0, n_wg_v = 0, n_prz = 0;
+  // exact solvers
+  double *d_A = nullptr, *d_rhs = nullptr, *d_linv = nullptr;
+  int *d_info = nullptr, *d_blk_a = nullptr, *d_blk_b = nullptr, *d_dpos = nullptr, *d_dsrc = nullptr;
   ccm_tile_plan plan;
   ccm_tsc tsc;
-  int *d_dpos = nullptr, *d_dsrc = nullptr;
-  int N_tiles = 0;
-  if (use_tiles) {
+  bool tsc_live = false;
+  int N_tiles = 0, N_dense = 0;
+};
+
+#define PG_TRY(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
+
+void pg_state_destroy(PgState* s) {
+  hipStreamSynchronize(s->ctx->stream);
+  for (auto& p : s->allocs) ccm_pool_put(s->ctx, p.first, p.second);
+  s->allocs.clear();
+  if (s->tsc_live) { ccm_tsc_destroy(s->ctx, &s->tsc); s->tsc_live = false; }
+}
+
+// on failure the caller destroys the partly built state
+int pg_state_create(ccm_ctx* ctx, const PgHost& h, const double* sim3, int fix_scale, int solver, PgState* s) {
+  s->ctx = ctx; s->solver = solver;
+  PgAllocs& allocs = s->allocs;
+  PgDev& d = s->d;
+  const int F = h.F, E = h.E, nBlk = h.nBlk;
+  d.V = h.V; d.F = F; d.E = E; d.nBlk = nBlk; d.fix_scale = fix_scale ? 1 : 0;
+  std::vector<double> s0(sim3, sim3 + 8 * (size_t)h.V);
+  int *p_i = nullptr; uint32_t* p_u = nullptr; double* p_d = nullptr;
+  PG_TRY(up(ctx, allocs, s0, &d.S[0])); PG_TRY(up(ctx, allocs, s0, &d.S[1]));
+  PG_TRY(up(ctx, allocs, h.slot, &p_i)); d.slot = p_i;
+  PG_TRY(up(ctx, allocs, h.free_v, &p_i)); d.free_v = p_i;
+  PG_TRY(up(ctx, allocs, h.ei, &p_i)); d.ei = p_i;
+  PG_TRY(up(ctx, allocs, h.ej, &p_i)); d.ej = p_i;
+  PG_TRY(up(ctx, allocs, h.ms, &p_d)); d.meas = p_d;
+  PG_TRY(up(ctx, allocs, h.blk_off, &p_i)); d.blk_off = p_i;
+  PG_TRY(up(ctx, allocs, h.blk_edge, &p_i)); d.blk_edge = p_i;
+  PG_TRY(up(ctx, allocs, h.vtx_off, &p_i)); d.vtx_off = p_i;
+  PG_TRY(up(ctx, allocs, h.vtx_edge, &p_i)); d.vtx_edge = p_i;
+  PG_TRY(up(ctx, allocs, h.row_off, &p_i)); d.row_off = p_i;
+  PG_TRY(up(ctx, allocs, h.row_col, &p_i)); d.row_col = p_i;
+  PG_TRY(up(ctx, allocs, h.row_blk, &p_u)); d.row_blk = p_u;
+  const size_t n_dense = 7 * (size_t)F;
+  s->N_dense = (int)((n_dense + 63) / 64) * 64;
+  if (solver == kPgTiles || solver == kPgDense) {
     std::vector<int> ka(nBlk), kb(nBlk);
-    for (int k = 0; k < nBlk; k++) { ka[k] = keys[k].first; kb[k] = keys[k].second; }
-    PG_RC(up(ctx, allocs, ka, &d_blk_a)); PG_RC(up(ctx, allocs, kb, &d_blk_b));
-    std::vector<std::vector<int>> adj(F);
-    for (int k = 0; k < nBlk; k++) if (ka[k] != kb[k]) { adj[ka[k]].push_back(kb[k]); adj[kb[k]].push_back(ka[k]); }
-    std::vector<std::vector<int>> pieces;
-    const int nd_leaf = 31;   // 31 vertices = 217 unknowns = 4 tiles (2000 keyframes: leaf 31: 17.2 ms / 11 levels, 63: 18.9 / 13, 127: 23.4 / 19)
-    pg_nd_order(F, adj, std::max(nd_leaf, 9), &pieces);
-    std::vector<int> dpos(F, 0), dsrc;
-    for (auto& pc : pieces) {
-      for (int v : pc) { dpos[v] = (int)dsrc.size(); for (int c = 0; c < 7; c++) dsrc.push_back(7 * v + c); }
-      while (dsrc.size() % 64) dsrc.push_back(-1);
+    for (int k = 0; k < nBlk; k++) { ka[k] = h.keys[k].first; kb[k] = h.keys[k].second; }
+    PG_TRY(up(ctx, allocs, ka, &s->d_blk_a)); PG_TRY(up(ctx, allocs, kb, &s->d_blk_b));
+    if (solver == kPgTiles) {
+      std::vector<std::vector<int>> adj(F);
+      for (int k = 0; k < nBlk; k++) if (ka[k] != kb[k]) { adj[ka[k]].push_back(kb[k]); adj[kb[k]].push_back(ka[k]); }
+      std::vector<std::vector<int>> pieces;
+      const int nd_leaf = 31;   // 31 vertices = 217 unknowns = 4 tiles (2000 keyframes: leaf 31: 17.2 ms / 11 levels, 63: 18.9 / 13, 127: 23.4 / 19)
+      pg_nd_order(F, adj, std::max(nd_leaf, 9), &pieces);
+      std::vector<int> dpos(F, 0), dsrc;
+      for (auto& pc : pieces) {
+        for (int v : pc) { dpos[v] = (int)dsrc.size(); for (int c = 0; c < 7; c++) dsrc.push_back(7 * v + c); }
+        while (dsrc.size() % 64) dsrc.push_back(-1);
+      }
+      s->N_tiles = (int)dsrc.size();
+      const int T = s->N_tiles / 64;
+      std::vector<char> nz((size_t)T * T, 0);
+      for (int t = 0; t < T; t++) nz[(size_t)t * T + t] = 1;
+      for (int k = 0; k < nBlk; k++) {
+        const int a0 = dpos[ka[k]] / 64, a1 = (dpos[ka[k]] + 6) / 64, b0 = dpos[kb[k]] / 64, b1 = (dpos[kb[k]] + 6) / 64;
+        for (int ta = a0; ta <= a1; ta++) for (int tb = b0; tb <= b1; tb++) nz[(size_t)std::max(ta, tb) * T + std::min(ta, tb)] = 1;
+      }
+      PG_TRY(ccm_tsc_create(ctx, T, nz, &s->tsc));
+      s->tsc_live = true;
+      PG_TRY(up(ctx, allocs, dpos, &s->d_dpos)); PG_TRY(up(ctx, allocs, dsrc, &s->d_dsrc)); PG_TRY(al(ctx, allocs, (size_t)s->N_tiles, &s->d_rhs));
+      if (ccm_dbg("pg")) fprintf(stderr, "[ccm_pg] tile-sparse cholesky: %d unknowns in %d pieces -> %d tiles columns, %d non-zero tiles, %d levels\n", (int)n_dense, (int)pieces.size(), T, s->tsc.n_tiles, s->tsc.n_levels);
+    } else {
+      const int N_dense = s->N_dense;
+      PG_TRY(al(ctx, allocs, (size_t)N_dense * N_dense, &s->d_A)); PG_TRY(al(ctx, allocs, (size_t)N_dense, &s->d_rhs)); PG_TRY(al(ctx, allocs, 4, &s->d_info));
+      PG_TRY(al(ctx, allocs, (size_t)N_dense * 64, &s->d_linv));
+      // tile-level sparsity: the essential graph is a near-banded chain plus loop edges, so most 64x64 tiles of the factor
+      // stay zero; the factorisation and the substitutions visit only the tiles a symbolic elimination marks
+      const int T = N_dense / 64;
+      std::vector<char> nz((size_t)T * T, 0);
+      for (int t = 0; t < T; t++) nz[(size_t)t * T + t] = 1;
+      for (int k = 0; k < nBlk; k++) {
+        const int a0 = 7 * ka[k] / 64, a1 = (7 * ka[k] + 6) / 64, b0 = 7 * kb[k] / 64, b1 = (7 * kb[k] + 6) / 64;
+        for (int ta = a0; ta <= a1; ta++) for (int tb = b0; tb <= b1; tb++) { nz[(size_t)std::max(ta, tb) * T + std::min(ta, tb)] = 1; }
+      }
+      std::vector<int> col_rows, upd_pairs, row_cols;
+      ccm_tile_plan_symbolic(T, nz, &s->plan, &col_rows, &upd_pairs, &row_cols);
+      int *p_cr = nullptr, *p_up = nullptr, *p_rc = nullptr;
+      PG_TRY(up(ctx, allocs, col_rows, &p_cr)); PG_TRY(up(ctx, allocs, upd_pairs, &p_up)); PG_TRY(up(ctx, allocs, row_cols, &p_rc));
+      s->plan.d_col_rows = p_cr; s->plan.d_upd_pairs = p_up; s->plan.d_row_cols = p_rc;
     }
-    N_tiles = (int)dsrc.size();
-    const int T = N_tiles / 64;
-    std::vector<char> nz((size_t)T * T, 0);
-    for (int t = 0; t < T; t++) nz[(size_t)t * T + t] = 1;
-    for (int k = 0; k < nBlk; k++) {
-      const int a0 = dpos[ka[k]] / 64, a1 = (dpos[ka[k]] + 6) / 64, b0 = dpos[kb[k]] / 64, b1 = (dpos[kb[k]] + 6) / 64;
-      for (int ta = a0; ta <= a1; ta++) for (int tb = b0; tb <= b1; tb++) nz[(size_t)std::max(ta, tb) * T + std::min(ta, tb)] = 1;
-    }
-    PG_RC(ccm_tsc_create(ctx, T, nz, &tsc));
-    PG_RC(up(ctx, allocs, dpos, &d_dpos)); PG_RC(up(ctx, allocs, dsrc, &d_dsrc)); PG_RC(al(ctx, allocs, (size_t)N_tiles, &d_rhs));
-    if (ccm_dbg("pg")) fprintf(stderr, "[ccm_pg] tile-sparse cholesky: %d unknowns in %d pieces -> %d tiles columns, %d non-zero tiles, %d levels\n", (int)n_dense, (int)pieces.size(), T, tsc.n_tiles, tsc.n_levels);
-  } else if (use_dense) {
-    std::vector<int> ka(nBlk), kb(nBlk);
-    for (int k = 0; k < nBlk; k++) { ka[k] = keys[k].first; kb[k] = keys[k].second; }
-    PG_RC(up(ctx, allocs, ka, &d_blk_a)); PG_RC(up(ctx, allocs, kb, &d_blk_b));
-    PG_RC(al(ctx, allocs, (size_t)N_dense * N_dense, &d_A)); PG_RC(al(ctx, allocs, (size_t)N_dense, &d_rhs)); PG_RC(al(ctx, allocs, 4, &d_info));
-    PG_RC(al(ctx, allocs, (size_t)N_dense * 64, &d_linv));
-    // tile-level sparsity: the essential graph is a near-banded chain plus loop edges, so most 64x64 tiles of the factor
-    // stay zero; the factorisation and the substitutions visit only the tiles a symbolic elimination marks
-    const int T = N_dense / 64;
-    std::vector<char> nz((size_t)T * T, 0);
-    for (int t = 0; t < T; t++) nz[(size_t)t * T + t] = 1;
-    for (int k = 0; k < nBlk; k++) {
-      const int a0 = 7 * ka[k] / 64, a1 = (7 * ka[k] + 6) / 64, b0 = 7 * kb[k] / 64, b1 = (7 * kb[k] + 6) / 64;
-      for (int ta = a0; ta <= a1; ta++) for (int tb = b0; tb <= b1; tb++) { nz[(size_t)std::max(ta, tb) * T + std::min(ta, tb)] = 1; }
-    }
-    std::vector<int> col_rows, upd_pairs, row_cols;
-    ccm_tile_plan_symbolic(T, nz, &plan, &col_rows, &upd_pairs, &row_cols);
-    int *p_cr = nullptr, *p_up = nullptr, *p_rc = nullptr;
-    PG_RC(up(ctx, allocs, col_rows, &p_cr)); PG_RC(up(ctx, allocs, upd_pairs, &p_up)); PG_RC(up(ctx, allocs, row_cols, &p_rc));
-    plan.d_col_rows = p_cr; plan.d_upd_pairs = p_up; plan.d_row_cols = p_rc;
   }
+  const bool use_tree = solver == kPgForest;
   d.use_tree = use_tree ? 1 : 0;
   if (use_tree) {
-    PG_RC(up(ctx, allocs, t_parent, &p_i)); d.t_parent = p_i;
-    PG_RC(up(ctx, allocs, t_code, &p_i)); d.t_code = p_i;
-    PG_RC(up(ctx, allocs, t_order, &p_i)); d.t_order = p_i;
-    PG_RC(up(ctx, allocs, t_pos, &p_i)); d.t_pos = p_i;
-    PG_RC(up(ctx, allocs, t_out, &p_i)); d.t_out = p_i;
-    PG_RC(up(ctx, allocs, ends_off, &p_i)); d.ends_off = p_i;
-    PG_RC(up(ctx, allocs, ends_idx, &p_i)); d.ends_idx = p_i;
-    PG_RC(al(ctx, allocs, 49 * (size_t)F, &d.Binv)); PG_RC(al(ctx, allocs, 49 * (size_t)F, &d.Dinv));
+    PG_TRY(up(ctx, allocs, h.t_parent, &p_i)); d.t_parent = p_i;
+    PG_TRY(up(ctx, allocs, h.t_code, &p_i)); d.t_code = p_i;
+    PG_TRY(up(ctx, allocs, h.t_order, &p_i)); d.t_order = p_i;
+    PG_TRY(up(ctx, allocs, h.t_pos, &p_i)); d.t_pos = p_i;
+    PG_TRY(up(ctx, allocs, h.t_out, &p_i)); d.t_out = p_i;
+    PG_TRY(up(ctx, allocs, h.ends_off, &p_i)); d.ends_off = p_i;
+    PG_TRY(up(ctx, allocs, h.ends_idx, &p_i)); d.ends_idx = p_i;
+    PG_TRY(al(ctx, allocs, 49 * (size_t)F, &d.Binv)); PG_TRY(al(ctx, allocs, 49 * (size_t)F, &d.Dinv));
   }
   d.n_wg_row = ccm_div_up(F, kTPB / kWave); d.n_wg_upd = use_tree ? 1 : ccm_div_up(F, kTPB / 8); d.n_wg_edge = ccm_div_up(E, kTPB);
-  const int n_wg_init = ccm_div_up(F, kTPB), n_wg_v = ccm_div_up(n_vert, kTPB);
-  PG_RC(al(ctx, allocs, 7 * (size_t)E, &d.err)); PG_RC(al(ctx, allocs, 98 * (size_t)E, &d.J));
-  PG_RC(al(ctx, allocs, 49 * (size_t)nBlk, &d.H)); PG_RC(al(ctx, allocs, 7 * (size_t)F, &d.b));
-  PG_RC(al(ctx, allocs, 7 * (size_t)F, &d.x)); PG_RC(al(ctx, allocs, 7 * (size_t)F, &d.r)); PG_RC(al(ctx, allocs, 7 * (size_t)F, &d.z));
-  PG_RC(al(ctx, allocs, 7 * (size_t)F, &d.q)); PG_RC(al(ctx, allocs, 7 * (size_t)F, &d.p[0])); PG_RC(al(ctx, allocs, 7 * (size_t)F, &d.p[1]));
-  PG_RC(al(ctx, allocs, 49 * (size_t)F, &d.Minv));
-  PG_RC(al(ctx, allocs, (size_t)d.n_wg_row, &d.ppq));
+  s->n_wg_init = ccm_div_up(F, kTPB); s->n_wg_v = ccm_div_up(h.V, kTPB);
+  PG_TRY(al(ctx, allocs, 7 * (size_t)E, &d.err)); PG_TRY(al(ctx, allocs, 98 * (size_t)E, &d.J));
+  PG_TRY(al(ctx, allocs, 49 * (size_t)nBlk, &d.H)); PG_TRY(al(ctx, allocs, 7 * (size_t)F, &d.b));
+  PG_TRY(al(ctx, allocs, 7 * (size_t)F, &d.x)); PG_TRY(al(ctx, allocs, 7 * (size_t)F, &d.r)); PG_TRY(al(ctx, allocs, 7 * (size_t)F, &d.z));
+  PG_TRY(al(ctx, allocs, 7 * (size_t)F, &d.q)); PG_TRY(al(ctx, allocs, 7 * (size_t)F, &d.p[0])); PG_TRY(al(ctx, allocs, 7 * (size_t)F, &d.p[1]));
+  PG_TRY(al(ctx, allocs, 49 * (size_t)F, &d.Minv));
+  PG_TRY(al(ctx, allocs, (size_t)d.n_wg_row, &d.ppq));
   // prz is written by pg_pcg_init (n_wg_init workgroups) and pg_pcg_update (n_wg_upd): size for the larger, sum n_wg_upd
-  PG_RC(al(ctx, allocs, (size_t)std::max(d.n_wg_upd, n_wg_init), &d.prz[0])); PG_RC(al(ctx, allocs, (size_t)std::max(d.n_wg_upd, n_wg_init), &d.prz[1]));
-  PG_RC(al(ctx, allocs, 8, &d.scal)); PG_RC(al(ctx, allocs, 4, &d.flag));
-  PG_RC(al(ctx, allocs, (size_t)std::max({d.n_wg_edge, n_wg_v, 1}), &d.part));
-  auto cleanup = [&]() { hipStreamSynchronize(ctx->stream); for (auto& p : allocs) ccm_pool_put(ctx, p.first, p.second); if (use_tiles) ccm_tsc_destroy(ctx, &tsc); };
-  auto read_scal = [&](int idx, double* out) -> int {
-    CCM_HIP_CHECK(ctx, hipMemcpyAsync(out, d.scal + idx, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    CCM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return CCM_OK;
-  };
-  auto chi2_of = [&](int which, double* out) -> int {
-    hipLaunchKernelGGL(pg_chi2, dim3(d.n_wg_edge), dim3(kTPB), 0, ctx->stream, d, which);
-    hipLaunchKernelGGL(pg_reduce, dim3(1), dim3(kTPB), 0, ctx->stream, d, d.n_wg_edge, 4);
-    return read_scal(4, out);
-  };
+  s->n_prz = std::max(d.n_wg_upd, s->n_wg_init);
+  PG_TRY(al(ctx, allocs, (size_t)s->n_prz, &d.prz[0])); PG_TRY(al(ctx, allocs, (size_t)s->n_prz, &d.prz[1]));
+  PG_TRY(al(ctx, allocs, 8, &d.scal)); PG_TRY(al(ctx, allocs, 4, &d.flag));
+  PG_TRY(al(ctx, allocs, (size_t)std::max({d.n_wg_edge, s->n_wg_v, 1}), &d.part));
+  return CCM_OK;
+}
+
+int pg_read_scal(PgState& s, int idx, double* out) {
+  CCM_HIP_CHECK(s.ctx, hipMemcpyAsync(out, s.d.scal + idx, sizeof(double), hipMemcpyDeviceToHost, s.ctx->stream));
+  CCM_HIP_CHECK(s.ctx, hipStreamSynchronize(s.ctx->stream));
+  return CCM_OK;
+}
+// errors (left in d.err) and chi2 of state `which`
+int pg_chi2_of(PgState& s, int which, double* out) {
+  hipLaunchKernelGGL(pg_chi2, dim3(s.d.n_wg_edge), dim3(kTPB), 0, s.ctx->stream, s.d, which);
+  hipLaunchKernelGGL(pg_reduce, dim3(1), dim3(kTPB), 0, s.ctx->stream, s.d, s.d.n_wg_edge, 4);
+  return pg_read_scal(s, 4, out);
+}
+
+// J, H and b at state `cur` from the errors pg_chi2_of(cur) left; the forest solver also rebuilds its tree recursion (J changed)
+void pg_linearize_assemble(PgState& s, int cur, double lambda) {
+  const PgDev& d = s.d;
+  hipLaunchKernelGGL(pg_linearize, dim3(ccm_div_up((int64_t)d.E * 32, kTPB)), dim3(kTPB), 0, s.ctx->stream, d, cur);
+  hipLaunchKernelGGL(pg_assemble, dim3(ccm_div_up(d.nBlk + d.F, kTPB / kWave)), dim3(kTPB), 0, s.ctx->stream, d);
+  if (s.solver == kPgForest) hipLaunchKernelGGL(pg_tree_setup, dim3(1), dim3(kWave), 0, s.ctx->stream, d, lambda);
+}
+
+// ---- solve (H + lambda I) x = b into d.x, one function per solver; *ok = 0: the solver failed numerically (LM rejects the step) ----
+int pg_solve_tiles(PgState& s, double lambda, bool* ok) {
+  ccm_ctx* ctx = s.ctx;
+  const PgDev& d = s.d;
+  int info = 0;
+  PG_TRY(ccm_tsc_clear(ctx, &s.tsc));
+  hipLaunchKernelGGL(pg_tile_fill, dim3(ccm_div_up(std::max(d.nBlk * 49, s.N_tiles), kTPB)), dim3(kTPB), 0, ctx->stream, d, s.d_blk_a, s.d_blk_b, (const int*)s.d_dpos,
+                     (const int*)s.d_dsrc, (const int*)s.tsc.d_tid, s.tsc.T, s.tsc.d_tiles, s.d_rhs, lambda, s.N_tiles);
+  PG_TRY(ccm_tsc_solve(ctx, &s.tsc, s.d_rhs));
+  hipLaunchKernelGGL(pg_tile_extract, dim3(ccm_div_up(s.N_tiles, kTPB)), dim3(kTPB), 0, ctx->stream, (const double*)s.d_rhs, (const int*)s.d_dsrc, s.N_tiles, d.x);
+  if (hipMemcpyAsync(&info, s.tsc.d_info, sizeof(int), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
+    return ccm_set_error(ctx, CCM_E_HIP, "pose graph: tile solve readback");
+  *ok = info == 0;     // > 0: leading minor not positive definite
+  return CCM_OK;
+}
+
+int pg_solve_dense(PgState& s, double lambda, bool* ok) {
+  ccm_ctx* ctx = s.ctx;
+  const PgDev& d = s.d;
+  const int N_dense = s.N_dense;
+  int info = 0;
+  hipMemsetAsync(s.d_A, 0, (size_t)N_dense * N_dense * sizeof(double), ctx->stream);
+  hipLaunchKernelGGL(pg_dense_fill, dim3(ccm_div_up(std::max(d.nBlk * 49, N_dense), kTPB)), dim3(kTPB), 0, ctx->stream, d, s.d_blk_a, s.d_blk_b, s.d_A, s.d_rhs, lambda, N_dense);
+  PG_TRY(ccm_dense_chol_solve_dev(ctx, s.d_A, N_dense, s.d_rhs, s.d_linv, s.d_info, &s.plan));
+  if (hipMemcpyAsync(d.x, s.d_rhs, 7 * (size_t)d.F * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
+      hipMemcpyAsync(&info, s.d_info, sizeof(int), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
+    return ccm_set_error(ctx, CCM_E_HIP, "pose graph: dense solve readback");
+  *ok = info == 0;
+  return CCM_OK;
+}
+
+// flags, partial sums and scalars of a PCG solve back to their start values
+void pg_pcg_reset(PgState& s) {
+  hipMemsetAsync(s.d.flag, 0, 4 * sizeof(int), s.ctx->stream);
+  hipMemsetAsync(s.d.prz[0], 0, sizeof(double) * (size_t)s.n_prz, s.ctx->stream);   // stale partials of the previous solve
+  hipMemsetAsync(s.d.prz[1], 0, sizeof(double) * (size_t)s.n_prz, s.ctx->stream);
+}
+size_t pg_precond_lds(const PgDev& d) { return (7 * (size_t)d.F + 1024 + 16) * sizeof(double); }
+int pg_precond_attr(ccm_ctx* ctx) {
+  if (!(ctx->lds_attr_done & (1u << CCM_LDS_PG_PRECOND))) {
+    if (hipFuncSetAttribute((const void*)pg_precond, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024) != hipSuccess) return ccm_set_error(ctx, CCM_E_HIP, "pose graph: LDS attribute");
+    ctx->lds_attr_done |= 1u << CCM_LDS_PG_PRECOND;
+  }
+  return CCM_OK;
+}
+
+// the CG iterations of both PCG solvers: flags[] = done, iterations, fail, stalled; the flags are read back every 32 iterations
+int pg_pcg_iterate(PgState& s, int max_it, int flags[4]) {
+  ccm_ctx* ctx = s.ctx;
+  const PgDev& d = s.d;
+  const bool use_tree = s.solver == kPgForest;
+  const size_t lds_pc = pg_precond_lds(d);
+  flags[0] = flags[1] = flags[2] = flags[3] = 0;
+  int k = 0;
+  while (k < max_it) {
+    const int kend = std::min(max_it, k + 32);
+    for (; k < kend; k++) {
+      hipLaunchKernelGGL(pg_pcg_spmv, dim3(d.n_wg_row), dim3(kTPB), 0, ctx->stream, d, k);
+      if (use_tree) {
+        hipLaunchKernelGGL(pg_pcg_update_xr, dim3(ccm_div_up(7 * d.F, kTPB)), dim3(kTPB), 0, ctx->stream, d, k);
+        hipLaunchKernelGGL(pg_precond, dim3(1), dim3(1024), lds_pc, ctx->stream, d, (k + 1) & 1, k + 1);
+      } else {
+        hipLaunchKernelGGL(pg_pcg_update, dim3(d.n_wg_upd), dim3(kTPB), 0, ctx->stream, d, k);
+      }
+    }
+    if (hipMemcpyAsync(flags, d.flag, 4 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
+      return ccm_set_error(ctx, CCM_E_HIP, "pose graph: flag readback");
+    if (flags[0]) break;
+  }
+  if (!flags[0]) flags[1] = k;
+  return CCM_OK;
+}
+
+int pg_solve_forest(PgState& s, double lambda, double rel_tol, int max_it, int flags[4]) {
+  pg_pcg_reset(s);
+  PG_TRY(pg_precond_attr(s.ctx));
+  hipLaunchKernelGGL(pg_pcg_start, dim3(ccm_div_up(7 * s.d.F, kTPB)), dim3(kTPB), 0, s.ctx->stream, s.d, lambda, rel_tol);
+  hipLaunchKernelGGL(pg_precond, dim3(1), dim3(1024), pg_precond_lds(s.d), s.ctx->stream, s.d, 0, 0);
+  return pg_pcg_iterate(s, max_it, flags);
+}
+
+int pg_solve_jacobi(PgState& s, double lambda, double rel_tol, int max_it, int flags[4]) {
+  pg_pcg_reset(s);
+  // pg_pcg_init leaves its partial sums in the first n_wg_init slots; the consumers sum n_wg_upd (>= n_wg_init) slots, the remainder stays zero
+  hipLaunchKernelGGL(pg_pcg_init, dim3(s.n_wg_init), dim3(kTPB), 0, s.ctx->stream, s.d, lambda, rel_tol);
+  return pg_pcg_iterate(s, max_it, flags);
+}
+
+int pg_solve(PgState& s, double lambda, double rel_tol, int max_it, bool* ok, int flags[4]) {
+  flags[0] = 1; flags[1] = flags[2] = flags[3] = 0;
+  switch (s.solver) {
+    case kPgTiles: PG_TRY(pg_solve_tiles(s, lambda, ok)); break;
+    case kPgDense: PG_TRY(pg_solve_dense(s, lambda, ok)); break;
+    case kPgForest: PG_TRY(pg_solve_forest(s, lambda, rel_tol, max_it, flags)); *ok = !flags[2]; break;
+    default: PG_TRY(pg_solve_jacobi(s, lambda, rel_tol, max_it, flags)); *ok = !flags[2]; break;
+  }
+  if (s.solver <= kPgDense) flags[2] = *ok ? 0 : 1;
+  return CCM_OK;
+}
+
+// *stats (nullable) is zeroed once the pointers are known to be usable, before the edge indices are looked at
+int pg_check_args(ccm_ctx* ctx, const char* who, int n_vert, const double* sim3, const uint8_t* fixed, int n_edge, const int32_t* e_i, const int32_t* e_j, const double* meas,
+                  ccm_pg_stats* stats) {
+  if (!ctx || n_vert < 0 || n_edge < 0 || (n_vert && (!sim3 || !fixed)) || (n_edge && (!e_i || !e_j || !meas)))
+    return ccm_set_error(ctx, CCM_E_ARG, std::string(who) + ": bad args");
+  if (stats) *stats = ccm_pg_stats{};
+  for (int e = 0; e < n_edge; e++)
+    if (e_i[e] < 0 || e_i[e] >= n_vert || e_j[e] < 0 || e_j[e] >= n_vert || e_i[e] == e_j[e])
+      return ccm_set_error(ctx, CCM_E_ARG, std::string(who) + ": edge vertex index out of range");
+  return CCM_OK;
+}
+
+}  // namespace
+
+extern "C" int ccm_pose_graph_optimize(ccm_ctx* ctx, int n_vert, double* sim3, const uint8_t* fixed, int fix_scale, int n_edge, const int32_t* e_i, const int32_t* e_j,
+                                       const double* meas, int max_iters, double lambda_init, const volatile unsigned char* stop_flag, ccm_pg_stats* stats) {
+  if (max_iters < 0) return ccm_set_error(ctx, CCM_E_ARG, "ccm_pose_graph_optimize: bad args");
+  if (int rc = pg_check_args(ctx, "ccm_pose_graph_optimize", n_vert, sim3, fixed, n_edge, e_i, e_j, meas, stats)) return rc;
+  ccm_pg_stats st{};
+  CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  PgHost h;
+  pg_host_structure(n_vert, fixed, n_edge, e_i, e_j, meas, &h);
+  const int F = h.F;
+  if (F == 0 || h.E == 0) return CCM_OK;
+  // solver: exact Cholesky (default, reproduces the reference's LM path) or PCG (CCM_PG_SOLVER=pcg, or graphs too large for the exact forms:
+  // faster, but an inexact-Newton path).  Exact, default form: tile-sparse, level-scheduled Cholesky over a nested-dissection order (ccm_tsc: only
+  // the non-zero tiles are stored, so the size limit is the tile-pattern table, not a dense array); CCM_PG_SOLVER=dense keeps the round-1 form
+  // (dense array of <= 24 000 unknowns, natural order, one tile column after the other) for comparison.
+  // (<= 20 000 keyframes: the symbolic step keeps dense T x T tile-pattern tables on host and device, T ~ 4000 tiles at that size, and packs tile
+  // coordinates as (i << 16) | j in a signed int, i.e. T < 32768; larger graphs take the PCG path: forest-preconditioned while the forest fits
+  // the LDS of its apply kernel, block-Jacobi above)
+  const char* solver_env = getenv("CCM_PG_SOLVER");
+  const size_t n_dense = 7 * (size_t)F;
+  const bool want_exact = !(solver_env && !strcmp(solver_env, "pcg"));
+  const bool use_tiles = want_exact && !(solver_env && !strcmp(solver_env, "dense")) && n_dense <= 140000;
+  const bool use_dense = want_exact && (use_tiles || n_dense <= 24000);
+  const int solver = use_tiles ? kPgTiles : use_dense ? kPgDense : F <= kPgTreeMaxF ? kPgForest : kPgJacobi;
+  if (solver == kPgForest) pg_host_forest(&h);
+  PgState s;
+  int rc = pg_state_create(ctx, h, sim3, fix_scale, solver, &s);
+  if (rc) { pg_state_destroy(&s); return rc; }
   // ---- Levenberg-Marquardt (optimization_algorithm_levenberg.cpp:61-164) ----
-  int cur = 0, rc = CCM_OK;
+  const PgDev& d = s.d;
+  int cur = 0;
   double lambda = lambda_init, ni = 2;
   int nBad = 0;
   double currentChi = 0;
+  const int max_it = std::min(50000, 10 * 7 * F + 100);
   for (int iter = 0; iter < max_iters && rc == CCM_OK; iter++) {
     if (stop_flag && *stop_flag) break;
-    if ((rc = chi2_of(cur, &currentChi))) break;
+    if ((rc = pg_chi2_of(s, cur, &currentChi))) break;
     if (iter == 0) st.chi2_initial = currentChi;
     const double iniChi = currentChi;
-    hipLaunchKernelGGL(pg_linearize, dim3(ccm_div_up((int64_t)E * 32, kTPB)), dim3(kTPB), 0, ctx->stream, d, cur);
-    hipLaunchKernelGGL(pg_assemble, dim3(ccm_div_up(nBlk + F, kTPB / kWave)), dim3(kTPB), 0, ctx->stream, d);
-    if (use_tree && !use_dense) hipLaunchKernelGGL(pg_tree_setup, dim3(1), dim3(kWave), 0, ctx->stream, d, lambda);
+    pg_linearize_assemble(s, cur, lambda);
     if (iter == 0 && !(lambda_init > 0)) {   // computeLambdaInit without a user value: tau * max diagonal
       std::vector<double> Hd(49 * (size_t)F);
       if (hipMemcpyAsync(Hd.data(), d.H, Hd.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { rc = ccm_set_error(ctx, CCM_E_HIP, "pose graph: H readback"); break; }
@@ -975,96 +1150,19 @@ extern "C" int ccm_pose_graph_optimize(ccm_ctx* ctx, int n_vert, double* sim3, c
     double rho = 0;
     int qmax = 0;
     do {
-      // solve (H + lambda I) x = b
-      hipMemsetAsync(d.flag, 0, 4 * sizeof(int), ctx->stream);
-      hipMemsetAsync(d.prz[0], 0, sizeof(double) * (size_t)std::max(d.n_wg_upd, n_wg_init), ctx->stream);   // stale partials of the previous solve
-      hipMemsetAsync(d.prz[1], 0, sizeof(double) * (size_t)std::max(d.n_wg_upd, n_wg_init), ctx->stream);
-      const size_t lds_pc = (7 * (size_t)F + 1024 + 16) * sizeof(double);
-      if (use_dense) {
-        int info = 0;
-        if (use_tiles) {
-          if ((rc = ccm_tsc_clear(ctx, &tsc))) break;
-          hipLaunchKernelGGL(pg_tile_fill, dim3(ccm_div_up(std::max(nBlk * 49, N_tiles), kTPB)), dim3(kTPB), 0, ctx->stream, d, d_blk_a, d_blk_b, (const int*)d_dpos,
-                             (const int*)d_dsrc, (const int*)tsc.d_tid, tsc.T, tsc.d_tiles, d_rhs, lambda, N_tiles);
-          if ((rc = ccm_tsc_solve(ctx, &tsc, d_rhs))) break;
-          hipLaunchKernelGGL(pg_tile_extract, dim3(ccm_div_up(N_tiles, kTPB)), dim3(kTPB), 0, ctx->stream, (const double*)d_rhs, (const int*)d_dsrc, N_tiles, d.x);
-          if (hipMemcpyAsync(&info, tsc.d_info, sizeof(int), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
-            rc = ccm_set_error(ctx, CCM_E_HIP, "pose graph: tile solve readback"); break;
-          }
-        } else {
-        hipMemsetAsync(d_A, 0, (size_t)N_dense * N_dense * sizeof(double), ctx->stream);
-        hipLaunchKernelGGL(pg_dense_fill, dim3(ccm_div_up(std::max(nBlk * 49, N_dense), kTPB)), dim3(kTPB), 0, ctx->stream, d, d_blk_a, d_blk_b, d_A, d_rhs,
-                           lambda, N_dense);
-        if ((rc = ccm_dense_chol_solve_dev(ctx, d_A, N_dense, d_rhs, d_linv, d_info, &plan))) break;
-        if (hipMemcpyAsync(d.x, d_rhs, n_dense * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
-            hipMemcpyAsync(&info, d_info, sizeof(int), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
-          rc = ccm_set_error(ctx, CCM_E_HIP, "pose graph: dense solve readback"); break;
-        }
-        }
-        const bool ok_d = info == 0;     // > 0: leading minor not positive definite -> solver failure, LM rejects the step
-        if (!ok_d) hipMemsetAsync(d.x, 0, 7 * (size_t)F * sizeof(double), ctx->stream);
-        hipLaunchKernelGGL(pg_apply, dim3(n_wg_v), dim3(kTPB), 0, ctx->stream, d, cur, lambda);
-        hipLaunchKernelGGL(pg_reduce, dim3(1), dim3(kTPB), 0, ctx->stream, d, n_wg_v, 5);
-        double tempChi = 0, scale = 0;
-        if ((rc = chi2_of(cur ^ 1, &tempChi))) break;
-        if ((rc = read_scal(5, &scale))) break;
-        st.lm_trials++;
-        if (!ok_d) tempChi = DBL_MAX;
-        scale += 1e-3;
-        rho = (currentChi - tempChi) / scale;
-        if (rho > 0 && std::isfinite(tempChi)) {
-          double alpha = 1. - std::pow((2 * rho - 1), 3);
-          alpha = std::min(alpha, 2. / 3.);
-          lambda *= std::max(1. / 3., alpha);
-          ni = 2;
-          currentChi = tempChi;
-          cur ^= 1;
-        } else {
-          lambda *= ni; ni *= 2;
-        }
-        qmax++;
-        continue;
-      }
-      if (use_tree) {
-        if (!(ctx->lds_attr_done & (1u << CCM_LDS_PG_PRECOND))) {
-          if (hipFuncSetAttribute((const void*)pg_precond, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024) != hipSuccess) { rc = ccm_set_error(ctx, CCM_E_HIP, "pose graph: LDS attribute"); break; }
-          ctx->lds_attr_done |= 1u << CCM_LDS_PG_PRECOND;
-        }
-        hipLaunchKernelGGL(pg_pcg_start, dim3(ccm_div_up(7 * F, kTPB)), dim3(kTPB), 0, ctx->stream, d, lambda, 1e-10);
-        hipLaunchKernelGGL(pg_precond, dim3(1), dim3(1024), lds_pc, ctx->stream, d, 0, 0);
-      } else {
-        hipLaunchKernelGGL(pg_pcg_init, dim3(n_wg_init), dim3(kTPB), 0, ctx->stream, d, lambda, 1e-10);
-      }
-      // pg_pcg_init leaves its partial sums in the first n_wg_init slots; the consumers sum n_wg_upd (>= n_wg_init) slots,
-      // the remainder is zero from the allocation / stays zero
-      int flags[4] = {0, 0, 0, 0};
-      const int max_it = std::min(50000, 10 * 7 * F + 100);
-      int k = 0;
-      while (k < max_it) {
-        const int kend = std::min(max_it, k + 32);
-        for (; k < kend; k++) {
-          hipLaunchKernelGGL(pg_pcg_spmv, dim3(d.n_wg_row), dim3(kTPB), 0, ctx->stream, d, k);
-          if (use_tree) {
-            hipLaunchKernelGGL(pg_pcg_update_xr, dim3(ccm_div_up(7 * F, kTPB)), dim3(kTPB), 0, ctx->stream, d, k);
-            hipLaunchKernelGGL(pg_precond, dim3(1), dim3(1024), lds_pc, ctx->stream, d, (k + 1) & 1, k + 1);
-          } else {
-            hipLaunchKernelGGL(pg_pcg_update, dim3(d.n_wg_upd), dim3(kTPB), 0, ctx->stream, d, k);
-          }
-        }
-        if (hipMemcpyAsync(flags, d.flag, sizeof(flags), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { rc = ccm_set_error(ctx, CCM_E_HIP, "pose graph: flag readback"); break; }
-        if (flags[0]) break;
-      }
-      if (rc) break;
-      const bool ok2 = !flags[2];
-      st.pcg_iters += flags[0] ? flags[1] : k;
-      if (!ok2) hipMemsetAsync(d.x, 0, 7 * (size_t)F * sizeof(double), ctx->stream);
-      hipLaunchKernelGGL(pg_apply, dim3(n_wg_v), dim3(kTPB), 0, ctx->stream, d, cur, lambda);
-      hipLaunchKernelGGL(pg_reduce, dim3(1), dim3(kTPB), 0, ctx->stream, d, n_wg_v, 5);
+      bool ok = true;
+      int flags[4];
+      if ((rc = pg_solve(s, lambda, 1e-10, max_it, &ok, flags))) break;
+      if (solver >= kPgForest) st.pcg_iters += flags[1];
+      // the trial: state[cur ^ 1] = oplus(state[cur], x), its chi2, and the gain ratio against the model's decrease x.(lambda x + b)
+      if (!ok) hipMemsetAsync(d.x, 0, 7 * (size_t)F * sizeof(double), ctx->stream);
+      hipLaunchKernelGGL(pg_apply, dim3(s.n_wg_v), dim3(kTPB), 0, ctx->stream, d, cur, lambda);
+      hipLaunchKernelGGL(pg_reduce, dim3(1), dim3(kTPB), 0, ctx->stream, d, s.n_wg_v, 5);
       double tempChi = 0, scale = 0;
-      if ((rc = chi2_of(cur ^ 1, &tempChi))) break;
-      if ((rc = read_scal(5, &scale))) break;
+      if ((rc = pg_chi2_of(s, cur ^ 1, &tempChi))) break;
+      if ((rc = pg_read_scal(s, 5, &scale))) break;
       st.lm_trials++;
-      if (!ok2) tempChi = DBL_MAX;
+      if (!ok) tempChi = DBL_MAX;
       scale += 1e-3;
       rho = (currentChi - tempChi) / scale;
       if (rho > 0 && std::isfinite(tempChi)) {
@@ -1091,7 +1189,78 @@ extern "C" int ccm_pose_graph_optimize(ccm_ctx* ctx, int n_vert, double* sim3, c
         hipStreamSynchronize(ctx->stream) != hipSuccess)
       rc = ccm_set_error(ctx, CCM_E_HIP, "pose graph: result readback");
   }
-  cleanup();
+  pg_state_destroy(&s);
   if (stats) *stats = st;
+  return rc;
+}
+
+// ---- test hook (test_internal.h): ONE linearisation and ONE linear solve of the given graph at its given state, everything observable ----
+int ccm_internal::pg_debug_solve(ccm_ctx* ctx, int n_vert, const double* sim3, const uint8_t* fixed, int fix_scale, int n_edge, const int32_t* e_i, const int32_t* e_j,
+                                 const double* meas, double lambda, int solver, double rel_tol, int max_it, const double* r_in, ccm_pg_debug_out* out) {
+  if (!out || solver < kPgTiles || solver > kPgJacobi || max_it < 0 || (r_in && solver < kPgForest)) return ccm_set_error(ctx, CCM_E_ARG, "pg_debug_solve: bad args");
+  if (int rc = pg_check_args(ctx, "pg_debug_solve", n_vert, sim3, fixed, n_edge, e_i, e_j, meas, nullptr)) return rc;
+  CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  PgHost h;
+  pg_host_structure(n_vert, fixed, n_edge, e_i, e_j, meas, &h);
+  const int F = h.F, E = h.E, nBlk = h.nBlk;
+  out->F = F; out->nBlk = nBlk; out->E_active = E;
+  for (int k = 0; k < 4; k++) out->flags[k] = 0;
+  if (F == 0 || E == 0) return CCM_OK;
+  if (solver == kPgForest && F > kPgTreeMaxF) return ccm_set_error(ctx, CCM_E_ARG, "pg_debug_solve: the forest does not fit (F > 2600)");
+  if (out->cap_free < (size_t)F || out->cap_edge < (size_t)E || out->cap_blk < (size_t)nBlk) return ccm_set_error(ctx, CCM_E_ARG, "pg_debug_solve: output capacity");
+  if (solver == kPgForest) pg_host_forest(&h);
+  for (int k = 0; k < nBlk; k++) { if (out->blk_a) out->blk_a[k] = h.keys[k].first; if (out->blk_b) out->blk_b[k] = h.keys[k].second; }
+  if (out->active) std::copy(h.act.begin(), h.act.end(), out->active);
+  if (solver == kPgForest) {
+    if (out->t_parent) std::copy(h.t_parent.begin(), h.t_parent.end(), out->t_parent);
+    if (out->t_code) std::copy(h.t_code.begin(), h.t_code.end(), out->t_code);
+    if (out->t_order) std::copy(h.t_order.begin(), h.t_order.end(), out->t_order);
+    if (out->t_pos) std::copy(h.t_pos.begin(), h.t_pos.end(), out->t_pos);
+    if (out->t_out) std::copy(h.t_out.begin(), h.t_out.end(), out->t_out);
+  }
+  PgState s;
+  const PgDev& d = s.d;
+  auto get = [&](double* dst, const double* src, size_t n) -> int {
+    if (!dst) return CCM_OK;
+    CCM_HIP_CHECK(ctx, hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    CCM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return CCM_OK;
+  };
+  auto put = [&](double* dst, const double* src, size_t n) -> int {
+    CCM_HIP_CHECK(ctx, hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    CCM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return CCM_OK;
+  };
+  auto run = [&]() -> int {
+    PG_TRY(pg_state_create(ctx, h, sim3, fix_scale, solver, &s));
+    double chi2 = 0;
+    PG_TRY(pg_chi2_of(s, 0, &chi2));
+    pg_linearize_assemble(s, 0, lambda);
+    std::vector<double> b_host(7 * (size_t)F);
+    PG_TRY(get(b_host.data(), d.b, b_host.size()));
+    if (out->b) std::copy(b_host.begin(), b_host.end(), out->b);
+    PG_TRY(get(out->H, d.H, 49 * (size_t)nBlk)); PG_TRY(get(out->J, d.J, 98 * (size_t)E)); PG_TRY(get(out->err, d.err, 7 * (size_t)E));
+    if (r_in && out->z_out) {   // one application of the solver's preconditioner, by the kernel that applies it inside the solve
+      pg_pcg_reset(s);
+      if (solver == kPgForest) {
+        PG_TRY(pg_precond_attr(ctx));
+        PG_TRY(put(d.r, r_in, 7 * (size_t)F));
+        hipLaunchKernelGGL(pg_precond, dim3(1), dim3(1024), pg_precond_lds(d), ctx->stream, d, 0, 0);
+      } else {                  // pg_pcg_init builds the block inverses and applies them to b: b = r_in for this one launch
+        PG_TRY(put(d.b, r_in, 7 * (size_t)F));
+        hipLaunchKernelGGL(pg_pcg_init, dim3(s.n_wg_init), dim3(kTPB), 0, ctx->stream, d, lambda, rel_tol);
+        PG_TRY(put(d.b, b_host.data(), 7 * (size_t)F));
+      }
+      PG_TRY(get(out->z_out, d.z, 7 * (size_t)F));
+    }
+    bool ok = true;
+    int flags[4];
+    PG_TRY(pg_solve(s, lambda, rel_tol, max_it, &ok, flags));
+    for (int k = 0; k < 4; k++) out->flags[k] = flags[k];
+    PG_TRY(get(out->x, d.x, 7 * (size_t)F));
+    return CCM_OK;
+  };
+  const int rc = run();
+  pg_state_destroy(&s);
   return rc;
 }

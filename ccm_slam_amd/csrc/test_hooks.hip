@@ -88,6 +88,10 @@ extern "C" int ccm_comm_init_loopback(ccm_ctx* ctx, void* group, int rank) { ret
 extern "C" int ccm_debug_dense_solve(ccm_ctx* ctx, const double* A, const double* b, int n, double* x, int* info) { return ccm_internal::debug_dense_solve(ctx, A, b, n, x, info); }
 extern "C" int ccm_debug_tile_solve(ccm_ctx* ctx, const double* A, const double* b, int n, double* x, int* info, int* levels, int* tiles) { return ccm_internal::debug_tile_solve(ctx, A, b, n, x, info, levels, tiles); }
 extern "C" int ccm_debug_dense_inverse(ccm_ctx* ctx, const double* A, int n, double* Ainv, int* info) { return ccm_internal::debug_dense_inverse(ctx, A, n, Ainv, info); }
+extern "C" int ccm_debug_pg_solve(ccm_ctx* ctx, int n_vert, const double* sim3, const uint8_t* fixed, int fix_scale, int n_edge, const int32_t* e_i, const int32_t* e_j,
+                                  const double* meas, double lambda, int solver, double rel_tol, int max_it, const double* r_in, ccm_pg_debug_out* out) {
+  return ccm_internal::pg_debug_solve(ctx, n_vert, sim3, fixed, fix_scale, n_edge, e_i, e_j, meas, lambda, solver, rel_tol, max_it, r_in, out);
+}
 extern "C" int ccm_orb_debug_timing(const ccm_orb* o, double out_ms[6]) { return ccm_internal::orb_debug_timing(o, out_ms); }
 extern "C" int ccm_orb_debug_level(ccm_orb* o, int level, uint8_t* score_out, uint8_t* blur_out) { return ccm_internal::orb_debug_level(o, level, score_out, blur_out); }
 extern "C" int ccm_orb_debug_candidates(ccm_orb* o, int level, ccm_keypoint* out, int cap, int* n_out) { return ccm_internal::orb_debug_candidates(o, level, out, cap, n_out); }

@@ -5,6 +5,7 @@
 #include "../../include/ccm_hip.h"
 #include <cstddef>
 #include <cstdint>
+struct ccm_pg_debug_out;   // include/ccm_testhooks.h
 namespace ccm_internal {
 int  ba_debug_partial_reduced(ccm_ba* ba, double lambda, double* out, size_t cap, size_t* count);
 int  ba_debug_coarse(ccm_ba* ba, double lambda, int* na, double* Ac, double* Ainv, double* Pm, size_t cap);
@@ -24,4 +25,6 @@ int  covis_update_window(ccm_ctx* ctx, int small_window, int n_kf, int n_all, co
                          const uint8_t* list_skip, int n_pt, const int32_t* obs_off, const int32_t* obs_kf, int th, int cap, int32_t* row_off, int32_t* col,
                          int32_t* count, int32_t* fw_off, int32_t* fw_col, int32_t* fw_w, int32_t* ord_off, int32_t* ord_kf, int32_t* ord_w, int32_t* flags,
                          int32_t* needed);
+int  pg_debug_solve(ccm_ctx* ctx, int n_vert, const double* sim3, const uint8_t* fixed, int fix_scale, int n_edge, const int32_t* e_i, const int32_t* e_j,
+                    const double* meas, double lambda, int solver, double rel_tol, int max_it, const double* r_in, ccm_pg_debug_out* out);
 }  // namespace ccm_internal

@@ -315,6 +315,50 @@ def pose_graph_optimization(ctx: Context, pg: dict, max_iters: int = 20, lambda_
     return sim3, st
 
 
+class PGDebugOut(C.Structure):
+    """ccm_pg_debug_out of include/ccm_testhooks.h"""
+    _fields_ = [("F", C.c_int32), ("nBlk", C.c_int32), ("E_active", C.c_int32), ("reserved", C.c_int32), ("flags", C.c_int32 * 4),
+                ("cap_free", C.c_size_t), ("cap_edge", C.c_size_t), ("cap_blk", C.c_size_t),
+                ("blk_a", C.c_void_p), ("blk_b", C.c_void_p), ("active", C.c_void_p),
+                ("H", C.c_void_p), ("b", C.c_void_p), ("J", C.c_void_p), ("err", C.c_void_p), ("x", C.c_void_p), ("z_out", C.c_void_p),
+                ("t_parent", C.c_void_p), ("t_code", C.c_void_p), ("t_order", C.c_void_p), ("t_pos", C.c_void_p), ("t_out", C.c_void_p)]
+
+
+PG_SOLVERS = {"tiles": 0, "dense": 1, "forest": 2, "jacobi": 3}
+
+
+def debug_pg_solve(ctx: Context, pg: dict, lam: float, solver, rel_tol: float = 1e-10, max_it: int = 1000, r_in=None):
+    """Test hook (ccm_debug_pg_solve): one linearisation of pg at its state and one solve of (H + lam I) x = b by `solver` ("tiles", "dense", "forest",
+    "jacobi" or 0..3), forced at any size.  Returns a dict: F, nBlk, keys[nBlk,2], H[nBlk,7,7], b[7F], J[E,2,7,7], err[E,7], active[E], x[7F], flags[4]
+    (done, iterations, failure, stalled); for the forest solver t_parent, t_code, t_order, t_pos, t_out; with r_in, z = M^-1 r_in."""
+    solver = PG_SOLVERS.get(solver, solver)
+    sim3 = np.ascontiguousarray(pg["sim3"], np.float64)
+    fixed = np.ascontiguousarray(pg["fixed"], np.uint8)
+    e_i, e_j = np.ascontiguousarray(pg["e_i"], np.int32), np.ascontiguousarray(pg["e_j"], np.int32)
+    meas = np.ascontiguousarray(pg["meas"], np.float64)
+    F = int((fixed == 0).sum())
+    E = int((~((fixed[e_i] != 0) & (fixed[e_j] != 0))).sum()) if e_i.size else 0
+    cap_blk = F + E
+    a = dict(blk_a=np.zeros(cap_blk, np.int32), blk_b=np.zeros(cap_blk, np.int32), active=np.zeros(E, np.int32), H=np.zeros(49 * cap_blk), b=np.zeros(7 * F),
+             J=np.zeros(98 * E), err=np.zeros(7 * E), x=np.zeros(7 * F), z_out=np.zeros(7 * F))
+    a.update({n: np.zeros(F, np.int32) for n in ("t_parent", "t_code", "t_order", "t_pos", "t_out")})
+    out = PGDebugOut(cap_free=F, cap_edge=E, cap_blk=cap_blk, **{n: _vp(v) for n, v in a.items()})
+    r = None if r_in is None else np.ascontiguousarray(r_in, np.float64)
+    if r is not None and r.size != 7 * F:
+        raise ValueError("r_in must hold 7 F values")
+    v = lambda x: C.c_void_p(_vp(x))
+    check(hooks().ccm_debug_pg_solve(ctx.handle, int(sim3.shape[0]), v(sim3), v(fixed), int(bool(pg["fix_scale"])), int(e_i.size), v(e_i), v(e_j), v(meas),
+                                     C.c_double(lam), int(solver), C.c_double(rel_tol), int(max_it), None if r is None else v(r), C.byref(out)), ctx.handle)
+    nB = out.nBlk
+    res = dict(F=out.F, nBlk=nB, keys=np.stack([a["blk_a"][:nB], a["blk_b"][:nB]], axis=1), H=a["H"][:49 * nB].reshape(nB, 7, 7), b=a["b"],
+               J=a["J"].reshape(E, 2, 7, 7), err=a["err"].reshape(E, 7), active=a["active"], x=a["x"], flags=np.array(list(out.flags), np.int32))
+    if solver == 2:
+        res.update({n: a[n] for n in ("t_parent", "t_code", "t_order", "t_pos", "t_out")})
+    if r is not None:
+        res["z"] = a["z_out"]
+    return res
+
+
 def debug_dense_solve(ctx: Context, A, b):
     """Test hook: SPD solve through the device's blocked MFMA-f64 Cholesky (ccm_debug_dense_solve)."""
     A = np.ascontiguousarray(A, np.float64); b = np.ascontiguousarray(b, np.float64)

@@ -56,6 +56,26 @@ int  ccm_debug_tile_solve(ccm_ctx* ctx, const double* A, const double* b, int n,
 /* same machinery, explicit inverse (used for the coarse level of the BA preconditioner) */
 int  ccm_debug_dense_inverse(ccm_ctx* ctx, const double* A, int n, double* Ainv, int* info);
 
+/* test hook for ccm_pose_graph_optimize: ONE linearisation of the graph at its given state and ONE solve of (H + lambda I) x = b, by the kernels and
+ * launch shapes of the product path.  solver: 0 tile-sparse Cholesky, 1 dense Cholesky, 2 PCG with the spanning-forest preconditioner (at most
+ * 2600 free vertices, else CCM_E_ARG), 3 block-Jacobi PCG; each is forced at any size.  rel_tol / max_it: the PCG stop rule and iteration limit.
+ * r_in (nullable, 7F, solvers 2 and 3 only): z_out receives M^-1 r_in from one application of the solver's preconditioner.
+ * The caller sets the three capacities and the pointers (any pointer may be null); F, nBlk, E_active and flags are written back.
+ * F free vertices in vertex order; E_active edges with a free end, active[e] = their index in the edge list; blocks (blk_a, blk_b), blk_a <= blk_b, the F
+ * diagonal ones first, H[49 nBlk] row-major with rows of blk_a; J[e][side][49] with J[k * 7 + d] = d err_k / d update_d; flags = done, iterations,
+ * numeric failure, ended by the stall rule.  Forest (solver 2), per free vertex: t_parent (free slot or -1: a fixed vertex or none), t_code
+ * (active edge * 2 + the side of this vertex, -1: root of a component without a fixed vertex), t_pos / t_out (DFS interval), t_order[pos]. */
+typedef struct ccm_pg_debug_out {
+  int32_t F, nBlk, E_active, reserved;
+  int32_t flags[4];
+  size_t  cap_free, cap_edge, cap_blk;
+  int32_t *blk_a, *blk_b, *active;
+  double  *H, *b, *J, *err, *x, *z_out;
+  int32_t *t_parent, *t_code, *t_order, *t_pos, *t_out;
+} ccm_pg_debug_out;
+int  ccm_debug_pg_solve(ccm_ctx* ctx, int n_vert, const double* sim3, const uint8_t* fixed, int fix_scale, int n_edge, const int32_t* e_i, const int32_t* e_j,
+                        const double* meas, double lambda, int solver, double rel_tol, int max_it, const double* r_in, ccm_pg_debug_out* out);
+
 /* test hook for ccm_slam_amd/csrc/lane_xor.h (round 6: the cross-lane moves of every xor butterfly — DPP, v_permlane16_swap / v_permlane32_swap): for MASK = 1, 2, 4, 8, 16, 32
  * the 64 lanes' from_partner<MASK>(v), add_partner<MASK>(v) and __shfl_xor(v, MASK) of in64, then [3][64]: lanex::wave_sum, the __shfl_xor butterfly of the same values, and
  * lanex::wave_incl_scan_i32 of the integer pattern (37 lane mod 101) - 20. */

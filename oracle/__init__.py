@@ -331,6 +331,50 @@ def pose_graph_optimize(pg, max_iters=20, lambda_init=1e-16):
     return sim3, st
 
 
+def pose_graph_system(pg, lib_handle=None):
+    """Dense H[7F,7F] (no lambda), b[7F] and the numeric Jacobians J[E,2,7,7] (J[e, side, k, d] = d err_k / d update_d, zero for fixed sides and for
+    edges between two fixed vertices) of the pose graph at its state (ora_pose_graph_system).  Free slots in vertex order.  lib_handle: another
+    build of the same source (pose_graph_system_fast)."""
+    sim3 = np.ascontiguousarray(pg["sim3"], np.float64)
+    fixed = np.ascontiguousarray(pg["fixed"], np.uint8)
+    e_i, e_j = np.ascontiguousarray(pg["e_i"], np.int32), np.ascontiguousarray(pg["e_j"], np.int32)
+    meas = np.ascontiguousarray(pg["meas"], np.float64)
+    n = 7 * int((fixed == 0).sum())
+    H = np.zeros((n, n)); b = np.zeros(n); J = np.zeros((int(e_i.size), 2, 7, 7))
+    fn = (lib_handle or lib()).ora_pose_graph_system
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    F = fn(sim3.shape[0], sim3.ctypes.data, fixed.ctypes.data, int(bool(pg["fix_scale"])), e_i.size, e_i.ctypes.data, e_j.ctypes.data, meas.ctypes.data,
+           H.ctypes.data, b.ctypes.data, J.ctypes.data)
+    assert 7 * F == n
+    return H, b, J
+
+
+def fast_lib():
+    """liboracle_fast.so (oracle/Makefile: the same ba_ref.cpp built -O3 -march=native, FMA contraction allowed), built for this CPU when missing or stale."""
+    path = os.path.join(_HERE, "liboracle_fast.so")
+    src = os.path.join(_HERE, "ba_ref.cpp")
+    # -march=native code must be built on the machine that runs it: rebuild when the CPU (model + flags) differs from the build's
+    import hashlib
+    try:
+        cpu = [l for l in open("/proc/cpuinfo") if l.startswith(("model name", "flags"))][:2]
+    except OSError:
+        cpu = []
+    stamp, want = path + ".cpu", hashlib.sha1("".join(cpu).encode()).hexdigest()
+    have = open(stamp).read().strip() if os.path.exists(stamp) else ""
+    if not os.path.exists(path) or os.path.getmtime(src) > os.path.getmtime(path) or have != want:
+        if os.path.exists(path):
+            os.remove(path)
+        subprocess.check_call(["make", "-C", _HERE, "-s", "liboracle_fast.so"])
+        open(stamp, "w").write(want)
+    return C.CDLL(path)
+
+
+def pose_graph_system_fast(pg):
+    """pose_graph_system through liboracle_fast.so: the second build whose distance from the first measures the rounding of the numeric Jacobians."""
+    return pose_graph_system(pg, fast_lib())
+
+
 # ---- ORB extractor ---------------------------------------------------------------------------------
 KP_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("size", np.float32), ("angle", np.float32),
                      ("response", np.float32), ("octave", np.int32)])
@@ -532,25 +576,11 @@ def bow_transform(vocab: dict, desc, levelsup=4):
 
 def ba_optimize_fast(prob: dict, max_iters: int):
     """the 'optimistic CPU' line of bench.py: the same restatement built -O3 -march=native (oracle/Makefile: liboracle_fast.so), timing only"""
-    path = os.path.join(_HERE, "liboracle_fast.so")
-    src = os.path.join(_HERE, "ba_ref.cpp")
-    # -march=native code must be built on the machine that runs it: rebuild when the CPU (model + flags) differs from the build's
-    import hashlib
-    try:
-        cpu = [l for l in open("/proc/cpuinfo") if l.startswith(("model name", "flags"))][:2]
-    except OSError:
-        cpu = []
-    stamp, want = path + ".cpu", hashlib.sha1("".join(cpu).encode()).hexdigest()
-    have = open(stamp).read().strip() if os.path.exists(stamp) else ""
-    if not os.path.exists(path) or os.path.getmtime(src) > os.path.getmtime(path) or have != want:
-        if os.path.exists(path):
-            os.remove(path)
-        subprocess.check_call(["make", "-C", _HERE, "-s", "liboracle_fast.so"])
-        open(stamp, "w").write(want)
+    fast = fast_lib()
     global _LIB
     lib()
     saved = _LIB
-    _LIB = C.CDLL(path)
+    _LIB = fast
     try:
         _, _, _, _, st = ba_optimize(prob, max_iters)
     finally:

@@ -141,9 +141,8 @@ def _concat_graphs(parts):
     return r
 
 
-def test_disconnected_components_and_a_hub(ctx, oracle_lib):
-    """Shapes the nested-dissection order must not choke on: 25 independent 12-keyframe loops (each with its own fixed keyframe: small
-    components share pieces), plus a 150-keyframe loop whose vertex 5 also has an edge to every 7th keyframe (a hub: wide BFS levels)."""
+def _hub_graph():
+    """25 independent 12-keyframe loops (each with its own fixed keyframe), plus a 150-keyframe loop whose vertex 5 also has an edge to every 7th keyframe"""
     parts = [synth.make_pose_graph(12, 100 + k, n_loop=1, covis=2) for k in range(25)]
     big = synth.make_pose_graph(150, 7)
     hub_i, hub_j, hub_m = [], [], []
@@ -158,8 +157,13 @@ def test_disconnected_components_and_a_hub(ctx, oracle_lib):
     big = dict(big, e_i=np.concatenate([big["e_i"], np.array(hub_i, np.int32)]), e_j=np.concatenate([big["e_j"], np.array(hub_j, np.int32)]),
                meas=np.concatenate([big["meas"], np.stack(hub_m)]))
     big["n_edge"] = int(big["e_i"].size)
-    pg = _concat_graphs(parts + [big])
-    _check(ctx, oracle_lib, pg)
+    return _concat_graphs(parts + [big])
+
+
+def test_disconnected_components_and_a_hub(ctx, oracle_lib):
+    """Shapes the nested-dissection order must not choke on: 25 independent 12-keyframe loops (each with its own fixed keyframe: small
+    components share pieces), plus a 150-keyframe loop whose vertex 5 also has an edge to every 7th keyframe (a hub: wide BFS levels)."""
+    _check(ctx, oracle_lib, _hub_graph())
 
 
 def test_dense_cholesky_reports_a_non_positive_pivot(ctx):
