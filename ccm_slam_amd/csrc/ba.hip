@@ -1388,7 +1388,11 @@ struct PersArgs {
   const int* coff; const int* cij; const uint32_t* cblk;   // per cluster: entries inside its own 16x16 block (local row << 4 | column, S block)
   unsigned long long* slots;   // [2][3][grid]: the exchanges alternate between two slot sets (epoch parity), word-major 24-byte slots
   unsigned long long* utag;    // [6 Cp][2]: u of every unknown as {bits, bits ^ key(epoch)} (the halo exchange validates itself)
-  double* wbuf[2];             // [6 Cp] each: w = (S + lambda I) u of the own rows for the partner unit, by epoch parity
+  // [2][6 Cp][2] | [2][8][kPersNcCap][2], by epoch parity, every value as {bits, bits ^ key(epoch)} like u: w = (S + lambda I) u of the own rows for the
+  // partner unit, then the units' parts of the coarse restriction P^T w (6 for the first node of the unit's interval, 6 for the second) where their READER
+  // looks for them: plane mm (first-node parts) / 4 + mm (second-node parts) of the unit's place mm in its interval, at the coarse component they add to
+  unsigned long long* tag;
+  int prefetch;                // != 0: waves 1..15 fetch the partner's w and the coarse parts INSIDE the exchange, while wave 0 polls the slots; 0: after it
   unsigned long long epoch_base;   // unique per launch: stale slots of earlier solves never validate
   const int* uoff;      // [n_clu+1] offsets into ucol
   const int* ucol;      // distinct columns of each cluster's rows, ascending
@@ -1396,7 +1400,6 @@ struct PersArgs {
   long long* dbg;       // optional [16] phase clocks of workgroup 0 (wall_clock64 ticks, 10 ns), accumulated over iterations
   // coarse level (nullptr = cluster-Jacobi only): explicit inverse [Nc x Nc], prolongation blocks [Cp][36], aggregates
   const double* Ainv; const double* Pm; int na, Nc;   // na camera intervals, na + 1 coarse nodes
-  double* cparts;              // [2][12][grid]: the units' parts of the coarse restriction P^T w (6 for the first node of the unit's interval, 6 for the second), component-major, by epoch parity
   // the cluster inverse across trials (round 4): [grid][96 * 48] the unit's own 48 rows of W, transposed, as the kernel keeps them in LDS.  w_load != 0: this
   // launch takes them from here instead of assembling and factoring the cluster block (a stale W — another lambda, an earlier linearisation — is still a
   // symmetric positive definite block-Jacobi preconditioner: PCG stays exact, only the iteration count moves; the host decides, lm_trial)
@@ -1410,21 +1413,42 @@ __device__ __forceinline__ double pers_uniform(double v) {
   return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
 
-__device__ __forceinline__ double coh_load(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void coh_store(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// A self-validating value {bits, bits ^ key} moved as ONE 16-byte device-coherent (sc1) access through a buffer descriptor (8-byte coherent accesses run at
+// 0.54-0.70 x the 16-byte rate on this part).  The descriptor's byte count bounds every access in hardware: an offset past it loads zeros and stores nothing,
+// so no access of the kernel can leave the block.
+typedef unsigned int pers_u32x4 __attribute__((ext_vector_type(4)));
+constexpr int kAuxSc1 = 16;
+__device__ __forceinline__ void tag_store(__amdgpu_buffer_rsrc_t rs, unsigned byte_off, double v, unsigned long long key) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(v), c = b ^ key;
+  pers_u32x4 q;
+  q.x = (unsigned)b; q.y = (unsigned)(b >> 32); q.z = (unsigned)c; q.w = (unsigned)(c >> 32);
+  __builtin_amdgcn_raw_buffer_store_b128(q, rs, (int)byte_off, 0, kAuxSc1);
+}
+__device__ __forceinline__ pers_u32x4 tag_load(__amdgpu_buffer_rsrc_t rs, unsigned byte_off) { return __builtin_amdgcn_raw_buffer_load_b128(rs, (int)byte_off, 0, kAuxSc1); }
+__device__ __forceinline__ bool tag_valid(pers_u32x4 q, unsigned long long key) {   // the xor check also rejects a torn read
+  return (q.x ^ q.z) == (unsigned)key && (q.y ^ q.w) == (unsigned)(key >> 32);
+}
+__device__ __forceinline__ double tag_value(pers_u32x4 q) { return __longlong_as_double((long long)(((unsigned long long)q.y << 32) | q.x)); }
 
 // Grid-wide "barrier + deterministic sum" of TWO values in one step, without atomics (256 arrivals on one counter
 // serialise at the memory side: measured 6 us per barrier): every workgroup publishes its partials (a, b) in its own
 // 24-byte slot as {bits(a), bits(b), bits(a) ^ bits(b) ^ key(epoch)} and then polls ALL slots (one per thread) until
 // every slot validates against the current epoch's key; the xor check also rejects torn reads.  The values are then
 // summed in a fixed order, so every workgroup obtains bit-identical totals.  All cross-workgroup data (u, w, slots,
-// coarse parts) moves with device-coherent accesses, so the only ordering needed is: drain this workgroup's stores,
-// meet, publish.
+// coarse parts) moves with device-coherent accesses and EVERY datum validates itself against the key of the exchange it
+// rides on, so nothing orders the unit's stores against its slot: a reader that passes the exchange (or fetches inside
+// it) before a w or a coarse part has landed sees the pair of two exchanges ago, which does not validate, and reads
+// again.  (Until the partner's w and the coarse parts carried tags an s_waitcnt vmcnt(0) drained the stores before the
+// publish, ~0.1 ms of a gba_c4 step.)  What still needs an order has one without it: a slot, a tagged w / coarse
+// part / u is rewritten by the wave that wrote it, at the same address, and only after its readers validated the
+// earlier value, i.e. after that store had landed; x, the saved inverse and the flags are read after the kernel ends.
+template <class Mid>
 __device__ __forceinline__ bool pers_exchange(int t /* threadIdx.x */, unsigned long long* slots /* [3][nwg] */, int nwg, int me, double a_thread, double b_thread,
                                               bool force_nan, unsigned long long epoch, unsigned* abort_flag, double* red /* [2 kPersWaves + 4] */,
-                                              double* total_a, double* total_b, int* poll_fail /* LDS, sticky: an aborted exchange ends the solve */) {
+                                              double* total_a, double* total_b, int* poll_fail /* LDS, sticky: an aborted exchange ends the solve */,
+                                              Mid&& mid /* what waves 1..15 do while wave 0 polls; a failure there sets *poll_fail and the abort flag itself */) {
   // a_thread, b_thread: this thread's shares of the unit's partials.  The unit sums, the publish and the grid-wide sums
-  // share two block barriers: wave sums -> LDS, (drain stores, barrier), thread 0 adds the 16 wave sums of each value in
+  // share two block barriers: wave sums -> LDS, (barrier), thread 0 adds the 16 wave sums of each value in
   // a fixed order and publishes, wave 0 polls (lane = source units t, t+64, ...; nwg <= 256), (barrier), everybody reads
   // the grid totals.  The slot words are stored WORD-MAJOR (word w of unit i at slots[w * nwg + i]) so that a wave's load
   // of one word is 512 contiguous bytes.  Variants measured and dropped: polling with 4 or 16 waves (slows the units
@@ -1435,7 +1459,6 @@ __device__ __forceinline__ bool pers_exchange(int t /* threadIdx.x */, unsigned 
     const double wa = wave_sum(a_thread), wb = wave_sum(b_thread);
     if ((t & (kWave - 1)) == 0) { red[t / kWave] = wa; red[kPersWaves + t / kWave] = wb; }
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (t == 0) {
     double ma = 0, mb = 0;
@@ -1476,6 +1499,8 @@ __device__ __forceinline__ bool pers_exchange(int t /* threadIdx.x */, unsigned 
       red[2 * kPersWaves] = sa; red[2 * kPersWaves + 1] = sb;
       if (!ok_w) { *poll_fail = 1; __hip_atomic_store(abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
     }
+  } else {
+    mid();
   }
   __syncthreads();
   const bool alive = *poll_fail == 0;
@@ -2271,8 +2296,15 @@ __global__ __launch_bounds__(kPersTPB) void ba_pcg_persist(BaDev d, PersArgs a) 
   double* rco = Li + (32 + 2 * kPersIdxCap + kPersColCap) / 2 + 6 * kPersColCap + 256;   // [Nc]
   double* pown = rco + Nc;                   // [8][36]
   double* ypart = pown + 8 * 36;             // [12]
-  static_assert((32 + 2 * kPersIdxCap + kPersColCap) % 2 == 0 && (32 + 2 * kPersIdxCap + kPersColCap) / 2 + 6 * kPersColCap + 256 + kPersNcCap + 8 * 36 + 12 <= kCluN * kCluN,
-                "coarse vectors do not fit behind the staged structure");
+  // what the exchange's fetch parks for the update that follows it (fetch_pre): entry x < kParkA in the free part of the zpart region ([4N + 48, 8N)), the
+  // rest behind y.  x < N: w of cluster entry x where the partner owns it; N + j: P^T w of coarse component j
+  constexpr int kParkA = 8 * N - (4 * N + N / 2);
+  double* park_a = zpart + 4 * N + N / 2;
+  double* park_b = ypart + 12;               // [N + kPersNcCap - kParkA]
+  auto park = [&](int x) { return x < kParkA ? park_a + x : park_b + (x - kParkA); };
+  static_assert((32 + 2 * kPersIdxCap + kPersColCap) % 2 == 0 &&
+                (32 + 2 * kPersIdxCap + kPersColCap) / 2 + 6 * kPersColCap + 256 + kPersNcCap + 8 * 36 + 12 + (N + kPersNcCap - kParkA) <= kCluN * kCluN,
+                "coarse vectors and the parked values do not fit behind the staged structure");
   const int aggu = d.agg >> 3;               // units per interval (an interval is a multiple of the 8 cameras of a unit)
   const int agg = u / aggu;                  // interval of the unit's cameras: nodes agg and agg + 1
   if (coarse) {
@@ -2296,7 +2328,15 @@ __global__ __launch_bounds__(kPersTPB) void ba_pcg_persist(BaDev d, PersArgs a) 
   // unit part of the coarse restriction P^T v for the own rows: wave 0, lane = (component c, camera k); the 8 camera
   // terms of a component sit in 8 neighbouring lanes; every camera's term goes with weight 1 - t to the first node of the unit's interval and with t
   // to the second.  Published component-major for the other units.
-  auto coarse_restrict = [&](const double* vec /* LDS, own 48 entries */, double* cpo /* the parts buffer of the coming exchange */) {
+  // The tagged values (PersArgs::tag): one descriptor over the whole block, byte offsets of w of unknown i / of part comp of a unit, by the parity of the
+  // exchange they ride on
+  auto key_of = [](unsigned long long e) { return 0x9E3779B97F4A7C15ull * e; };
+  const unsigned tag_w_pairs = 2u * 6u * (unsigned)d.Cp;
+  const __amdgpu_buffer_rsrc_t tag_rs = __builtin_amdgcn_make_buffer_rsrc(a.tag, 0, (int)(16u * (tag_w_pairs + 2u * 8u * (unsigned)kPersNcCap)), 0x00020000);
+  auto w_off = [&](unsigned long long e, int i) { return 16u * ((unsigned)(e & 1) * 6u * (unsigned)d.Cp + (unsigned)i); };
+  // coarse component j of plane pl: the 64 lanes of a gathering wave read 1 KB in one piece (unit-major parts cost every lane a cache line of its own)
+  auto c_off = [&](unsigned long long e, int pl, int j) { return 16u * (tag_w_pairs + ((unsigned)(e & 1) * 8u + (unsigned)pl) * (unsigned)kPersNcCap + (unsigned)j); };
+  auto coarse_restrict = [&](const double* vec /* LDS, own 48 entries */, unsigned long long e /* the coming exchange */) {
     if (wv == 0) {
       const int cc = lq >> 3, kk = lq & 7;
       double sv = 0;
@@ -2309,23 +2349,62 @@ __global__ __launch_bounds__(kPersTPB) void ba_pcg_persist(BaDev d, PersArgs a) 
       s0v = lanex::add_partner<1>(s0v); s1v = lanex::add_partner<1>(s1v);
       s0v = lanex::add_partner<2>(s0v); s1v = lanex::add_partner<2>(s1v);
       s0v = lanex::add_partner<4>(s0v); s1v = lanex::add_partner<4>(s1v);
-      if (cc < 6 && kk == 0) { coh_store(cpo + (size_t)cc * nwg + u, s0v); coh_store(cpo + (size_t)(6 + cc) * nwg + u, s1v); }
+      // (the units behind the last interval — padding of the grid — have no reader)
+      if (cc < 6 && kk == 0 && agg < a.na) { tag_store(tag_rs, c_off(e, u - aggu * agg, 6 * agg + cc), s0v, key_of(e)); tag_store(tag_rs, c_off(e, 4 + u - aggu * agg, 6 * (agg + 1) + cc), s1v, key_of(e)); }
     }
   };
-  // component tq % 6 of node tq / 6: the first-node parts of the 4 units of interval n plus the second-node parts of the 4 units of interval n - 1
-  // (valid after the exchange that follows coarse_restrict)
-  auto coarse_gather = [&](const double* cpi /* the parts buffer of the exchange just passed */) {
+  // ---- what a unit needs from the others at the start of an iteration, besides the two sums: the partner unit's 48 w and, per coarse component, the parts
+  // of P^T w.  Their owners stored them BEFORE publishing their slot of exchange e, each value tagged with key(e), so they need no ordering against the slots:
+  // waves 1..15 fetch them inside exchange e, while wave 0 polls (a.prefetch; otherwise at once after it), and read again only what does not validate yet.
+  // Wave 0 takes no part: a load after its poll would put a round trip back on the critical path.  Thread 64 + i holds entry i of the cluster vectors
+  // (i < 96: the partner's w where the row is not the unit's own), thread 64 + 96 + j coarse component j (nca <= 768); it parks the value in LDS (park:
+  // held in a register across the exchange it costs the row products one of their S registers) and applies it itself in the update.  Component j = c of node n: starting from 0, for mm ascending the first-node part of unit aggu n + mm, then the
+  // second-node part of unit aggu (n - 1) + mm — all four pairs of a round requested before the first addition (aggu <= 4: two rounds at most).
+  // The spin is bounded and watches the abort flag like halo_load's; giving up raises the same sticky flags.
+  auto fetch_pre = [&](unsigned long long e, bool want_w) {
+    const unsigned long long key = key_of(e);
+    int tf = tq;
+    asm volatile("" : "+v"(tf));   // (the indices below are derived HERE, not at the top of the iteration and kept live through the row products)
+    const int p = tf - kWave, j = p - N;
+    const bool is_w = want_w && p >= 0 && p < m && !(p >= ob && p < ob + mo);
+    const bool is_c = coarse && j >= 0 && j < nca;
+    const int n = j / 6;
+    bool ok = true;
     double sgm = 0;
-    if (coarse && tq < nca) {
-      const int n = tq / 6, cc = tq % 6;
-      const double* c0 = cpi + (size_t)cc * nwg + aggu * n;
-      const double* c1 = cpi + (size_t)(6 + cc) * nwg + aggu * (n - 1);
-      for (int mm = 0; mm < aggu; mm++) {
-        if (n < a.na && aggu * n + mm < nwg) sgm += coh_load(c0 + mm);
-        if (n >= 1 && aggu * (n - 1) + mm < nwg) sgm += coh_load(c1 + mm);
+    for (int h = 0; h < 2 && 2 * h < aggu; h++) {
+      // pair i of the round: mm = 2 h + i / 2, first-node part (i even) or second-node part (i odd); the next mm is the next plane
+      unsigned off[2] = {c_off(e, 2 * h, j), c_off(e, 4 + 2 * h, j)}, want = 0;
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const int mm = 2 * h + (i >> 1);
+        const bool first = (i & 1) == 0;
+        const int unit = first ? aggu * n + mm : aggu * (n - 1) + mm;
+        if (is_c && mm < aggu && (first ? n < a.na : n >= 1) && unit < nwg) want |= 1u << i;
       }
+      if (is_w) { want = (h == 0) ? 1u : 0u; off[0] = w_off(e, 6 * s0 + p); }
+      unsigned todo = want;
+      pers_u32x4 q[4];   // (a pair that has validated stays in place: the values cost no registers of their own)
+#pragma unroll
+      for (int i = 0; i < 4; i++) q[i] = pers_u32x4{0u, 0u, 0u, 0u};
+      for (int spins = 0; todo; spins++) {
+        asm volatile("" ::: "memory");   // every round reads memory again
+#pragma unroll
+        for (int i = 0; i < 4; i++) if (todo & (1u << i)) q[i] = tag_load(tag_rs, off[i & 1] + 16u * (unsigned)kPersNcCap * (unsigned)(i >> 1));
+#pragma unroll
+        for (int i = 0; i < 4; i++) if ((todo & (1u << i)) && tag_valid(q[i], key)) todo &= ~(1u << i);
+        if (!todo) break;
+        if (spins > kPersMaxSpins || __hip_atomic_load(a.bar + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) { ok = false; break; }
+        __builtin_amdgcn_s_sleep(1);
+      }
+      if (is_w) { if (h == 0) *park(p) = tag_value(q[0]); }
+      else {
+#pragma unroll
+        for (int i = 0; i < 4; i++) if (want & (1u << i)) sgm += tag_value(q[i]);
+      }
+      if (!ok) break;
     }
-    return sgm;
+    if (is_c) *park(p) = sgm;
+    if (!ok) { ibuf[2] = 1; __hip_atomic_store(a.bar + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
   };
   // PCG start: x = 0, r = bs, p_{-1} = s_{-1} = 0, P^T s_{-1} = 0
   if (t < N / 2) { xs[t] = 0; ps[t] = 0; }   // own rows
@@ -2448,7 +2527,7 @@ __global__ __launch_bounds__(kPersTPB) void ba_pcg_persist(BaDev d, PersArgs a) 
   };
   // ---- w = (S + lambda I) u for the own rows: registers x LDS; publishes w for the partner unit; stores this thread's
   // share of (w, u) in *wu ----
-  auto spmv_w = [&](double* wdst, double* wu) {
+  auto spmv_w = [&](unsigned long long e /* the coming exchange */, double* wu) {
     double acc = 0;
 #pragma unroll
     for (int kk = 0; kk < kPersRegEnt; kk++) {
@@ -2484,39 +2563,43 @@ __global__ __launch_bounds__(kPersTPB) void ba_pcg_persist(BaDev d, PersArgs a) 
       const double ui = zs[tq];
       const double wv_ = (half_sum[(rw * 2) * 8 + cc] + half_sum[(rw * 2 + 1) * 8 + cc]) + lambda * ui;
       wl[tq] = wv_;
-      coh_store(wdst + 6 * (size_t)o0 + tq, wv_);     // the partner unit needs it for its copy of s and r
+      tag_store(tag_rs, w_off(e, 6 * o0 + tq), wv_, key_of(e));     // the partner unit needs it for its copy of s and r
       wu_t = wv_ * ui;
     }
     *wu = wu_t;
   };
   // Preconditioned CG in the Chronopoulos-Gear form: ONE grid-wide exchange per iteration, carrying gamma = (r, u) and
   // delta = (w, u) with u = M^-1 r, w = (S + lambda I) u; p and s = (S + lambda I) p follow by recurrence, and so does
-  // the coarse residual P^T r (P^T s = P^T w + beta P^T s).  Exchanges alternate between two slot sets, two coarse-part
-  // buffers and two w buffers by epoch parity: a unit writes those of exchange e + 2 only after it has passed exchange
-  // e + 1, which every reader of exchange e's data joined after its reads.
-  const size_t cstride = 12 * (size_t)nwg;
+  // the coarse residual P^T r (P^T s = P^T w + beta P^T s).  Exchanges alternate between two slot sets, two sets of tagged coarse
+  // parts and two of tagged w by epoch parity.  The reuse: a reader has finished its reads of exchange e's data before it leaves
+  // exchange e (a.prefetch) or before it publishes its slot of exchange e + 1 (otherwise); a writer touches that parity again
+  // only after it has passed exchange e + 1, i.e. after every unit has published there.  A reader that is early sees the pair of
+  // exchange e - 2, which does not validate against key(e), and reads again.
   auto slots_of = [&](unsigned long long e) { return a.slots + 3 * (size_t)nwg * (e & 1); };
-  auto cparts_of = [&](unsigned long long e) { return a.cparts + cstride * (e & 1); };
-  auto key_of = [](unsigned long long e) { return 0x9E3779B97F4A7C15ull * e; };
+  // exchange e with the fetch of what rides on it: inside (waves 1..15, between the exchange's two block barriers) or after
+  auto exchange = [&](unsigned long long e, double a_t, double b_t, bool force_nan, double* ta, double* tb, bool want_w) {
+    const bool ok = pers_exchange(tq, slots_of(e), nwg, u, a_t, b_t, force_nan, e, a.bar + 1, red, ta, tb, ibuf + 2, [&]() { if (a.prefetch) fetch_pre(e, want_w); });
+    if (!a.prefetch && tq >= kWave) fetch_pre(e, want_w);   // (a give-up here is seen at the next block barrier that reads ibuf[2]: halo_load's)
+    return ok;
+  };
   int fail = 0, k = 0;
   double gam = 0, del = 0;
   bool alive = true;
   if (coarse) {   // coarse residual of r0 = b: one extra exchange before the first preconditioner application
-    coarse_restrict(rc + ob, cparts_of(epoch + 1));
+    coarse_restrict(rc + ob, epoch + 1);
     double dummy = 0, dummy2 = 0;
-    alive = pers_exchange(tq, slots_of(epoch + 1), nwg, u, 0.0, 0.0, false, epoch + 1, a.bar + 1, red, &dummy, &dummy2, ibuf + 2);
+    alive = exchange(epoch + 1, 0.0, 0.0, false, &dummy, &dummy2, false);
     ++epoch;
-    const double cg0 = coarse_gather(cparts_of(epoch));
-    if (t < nca) rco[t] += cg0;
+    if (t >= kWave + N && t - (kWave + N) < nca) rco[t - (kWave + N)] += *park(t - kWave);
     __syncthreads();
   }
   if (alive) {   // u0 = M^-1 r0, w0 = (S + lambda I) u0, gamma0, delta0
     const double ru_t = apply_W(key_of(epoch + 1));
     alive = halo_load(key_of(epoch + 1));
     double wu_t = 0;
-    spmv_w(a.wbuf[(epoch + 1) & 1], &wu_t);
-    if (coarse) { __syncthreads(); coarse_restrict(wl, cparts_of(epoch + 1)); }
-    const bool alive2 = pers_exchange(tq, slots_of(epoch + 1), nwg, u, ru_t, wu_t, has && ibuf[1], epoch + 1, a.bar + 1, red, &gam, &del, ibuf + 2);   // bad pivot -> NaN -> grid-wide failure
+    spmv_w(epoch + 1, &wu_t);
+    if (coarse) { __syncthreads(); coarse_restrict(wl, epoch + 1); }
+    const bool alive2 = exchange(epoch + 1, ru_t, wu_t, has && ibuf[1], &gam, &del, true);   // bad pivot -> NaN -> grid-wide failure
     ++epoch;
     alive = alive && alive2;
   }
@@ -2533,12 +2616,11 @@ __global__ __launch_bounds__(kPersTPB) void ba_pcg_persist(BaDev d, PersArgs a) 
     if (!(pap > 0.0)) { fail = 1; break; }   // not positive definite (or NaN): solver failure -> LM rejects the step
     const double alpha = pers_uniform(gam / pap);
     // ---- p = u + beta p, s = w + beta s, x += alpha p, r -= alpha s, P^T s = P^T w + beta P^T s, P^T r -= alpha P^T s ----
-    {
-      const double w_partner = (tq < m && !(tq >= ob && tq < ob + mo)) ? coh_load(a.wbuf[epoch & 1] + 6 * (size_t)s0 + tq) : 0.0;
-      const double cg = coarse_gather(cparts_of(epoch));       // P^T w of every aggregate
+    {   // (park: the partner's w / P^T w of the component, fetched with the exchange just passed)
+      const int p = tq - kWave, j = p - N;
       if (tq < mo) { const double pi = zs[tq] + beta * ps[tq]; ps[tq] = pi; xs[tq] += alpha * pi; }
-      if (tq < m) { const double si = ((tq >= ob && tq < ob + mo) ? wl[tq - ob] : w_partner) + beta * ss[tq]; ss[tq] = si; rc[tq] -= alpha * si; }
-      if (coarse && tq < nca) { const double sc = cg + beta * pso[tq]; pso[tq] = sc; rco[tq] -= alpha * sc; }
+      if (p >= 0 && p < m) { const double si = ((p >= ob && p < ob + mo) ? wl[p - ob] : *park(p)) + beta * ss[p]; ss[p] = si; rc[p] -= alpha * si; }
+      if (coarse && j >= 0 && j < nca) { const double sc = *park(p) + beta * pso[j]; pso[j] = sc; rco[j] -= alpha * sc; }
     }
     __syncthreads();
     PERS_TICK(0)
@@ -2551,12 +2633,12 @@ __global__ __launch_bounds__(kPersTPB) void ba_pcg_persist(BaDev d, PersArgs a) 
     PERS_TICK(2)
     if (!alive) { fail = 1; break; }
     double wu_t = 0;
-    spmv_w(a.wbuf[(epoch + 1) & 1], &wu_t);
-    if (coarse) { __syncthreads(); coarse_restrict(wl, cparts_of(epoch + 1)); }
+    spmv_w(epoch + 1, &wu_t);
+    if (coarse) { __syncthreads(); coarse_restrict(wl, epoch + 1); }
     PERS_TICK(3)
     gam_prev = gam; alpha_prev = alpha;
     if (a.dbg && t == 0) tw0 = wall_clock64();
-    alive = pers_exchange(tq, slots_of(epoch + 1), nwg, u, ru_t, wu_t, false, epoch + 1, a.bar + 1, red, &gam, &del, ibuf + 2);
+    alive = exchange(epoch + 1, ru_t, wu_t, false, &gam, &del, true);
     ++epoch;
     if (a.dbg && t == 0) a.dbg[32 + 2 * u] += wall_clock64() - tw0;   // per unit: time inside the exchange (its own wait for the slowest unit + the exchange latency)
     PERS_TICK(4)
@@ -2618,6 +2700,20 @@ __global__ __launch_bounds__(kPersTPB) void ba_pcg_init_tiles(BaDev d, double la
 constexpr size_t kPersLdsBytes = (size_t)(2 * kCluN * kCluN + 4 * kCluN + 8 * kCluN + kPersNcCap + 2 * kPersWaves + 4) * sizeof(double) + 16 + 14 * sizeof(long long);
 static_assert(kPersLdsBytes <= 160 * 1024, "persistent PCG: LDS of one workgroup exceeds the 160 KB of a CU");
 static inline size_t pers_lds_bytes() { return kPersLdsBytes; }
+
+// The arguments of one persistent launch that the handle fixes (buffers, structure lists, a fresh epoch base), for a solve without the coarse level, with
+// no debug clocks and no carried-over inverse; pers_args_coarse adds the coarse level as it stands in the handle.
+static PersArgs pers_args(ccm_ba* ba, double lambda, double rel_tol, int max_it) {
+  PersArgs pa{};
+  pa.lambda = lambda; pa.rel_tol = rel_tol; pa.max_it = max_it; pa.n_clu = ccm_div_up(ba->d.Cp, kClu);
+  pa.bar = ba->d_pers_bar; pa.slots = (unsigned long long*)ba->d_pers_part;
+  pa.utag = (unsigned long long*)ba->d_pers_u; pa.tag = ba->d_pers_tag; pa.prefetch = ba->pers_prefetch ? 1 : 0;
+  pa.epoch_base = (++ba->pers_launch) << 20;
+  pa.uoff = ba->d_pers_uoff; pa.ucol = ba->d_pers_ucol; pa.loc = ba->d_pers_loc;
+  pa.coff = ba->d_pers_coff; pa.cij = ba->d_pers_cij; pa.cblk = ba->d_pers_cblk;
+  return pa;
+}
+static void pers_args_coarse(const ccm_ba* ba, PersArgs* pa) { pa->Ainv = ba->d_cAinv; pa->Pm = ba->d_cP; pa->na = ba->coarse_na; pa->Nc = ba->coarse_Nc; }
 
 // ---- very small reduced systems (<= 16 free cameras: initial maps, tiny local windows): the whole PCG in ONE workgroup ----
 // Vectors and the 6x6 block-Jacobi preconditioner live in LDS and an iteration is a few block barriers (~2 us).  Typical
@@ -3307,16 +3403,9 @@ int lm_trial(ccm_ba* ba, double lambda, const ccm_ba_options& opt, double* temp_
     bool persist_ok = false;
     if (ba->pers_grid) {
       // whole solve in one launch; flags are read back together with the trial scalars
-      PersArgs pa;
-      pa.lambda = lambda; pa.rel_tol = tol; pa.max_it = max_it; pa.n_clu = ccm_div_up(d.Cp, kClu);
-      pa.bar = ba->d_pers_bar; pa.slots = (unsigned long long*)ba->d_pers_part;
-      pa.utag = (unsigned long long*)ba->d_pers_u; pa.wbuf[0] = d.p[0]; pa.wbuf[1] = d.p[1];   // (d.p: the multi-kernel path re-initialises it before use)
-      pa.epoch_base = (++ba->pers_launch) << 20;
-      pa.uoff = ba->d_pers_uoff; pa.ucol = ba->d_pers_ucol; pa.loc = ba->d_pers_loc;
-      pa.coff = ba->d_pers_coff; pa.cij = ba->d_pers_cij; pa.cblk = ba->d_pers_cblk;
+      PersArgs pa = pers_args(ba, lambda, tol, max_it);
       pa.test_abort = getenv("CCM_BA_TEST_ABORT") ? 1 : 0;
       pa.dbg = ccm_dbg("pers") ? (long long*)(ba->d_pers_bar + 4) : nullptr;
-      pa.Ainv = nullptr; pa.Pm = nullptr; pa.na = 0; pa.Nc = 0; pa.cparts = nullptr;
       // Cluster inverse across trials.  Offline (1000-keyframe 4-agent reduced systems, numpy PCG to 1e-8): W built at a lambda 10 / 100 / 1000 times away
       // costs 0-2 / 2-3 / 5 more CG iterations of 24-46; W of the INITIAL linearisation used three LM iterations later costs 13-19 more (the robust weights move),
       // later linearisations hardly differ (the map itself disagreed, see the measurements below).  Policy: reuse inside an LM iteration (rejected trials: only lambda moved) within a lambda window, and across
@@ -3357,7 +3446,7 @@ int lm_trial(ccm_ba* ba, double lambda, const ccm_ba_options& opt, double* temp_
           fprintf(stderr, "[ccm_ba] coarse_build: enqueue %.3f ms, complete %.3f ms\n", tc1 - tc0, now_ms() - tc0);
         } else
         RC(coarse_prepare(ba, lambda));
-        pa.Ainv = ba->d_cAinv; pa.Pm = ba->d_cP; pa.na = ba->coarse_na; pa.Nc = ba->coarse_Nc; pa.cparts = ba->d_cparts;
+        pers_args_coarse(ba, &pa);
       }
       static const bool trial_dbg = ccm_dbg("trial");   // development: wall clock of every persistent solve (adds two stream syncs per trial)
       double tdbg0 = 0;
@@ -3601,18 +3690,11 @@ int ccm_internal::ba_debug_pcg_solve(ccm_ba* ba, double lambda, int coarse, doub
   RC(build_system(ba));
   if (d.Lloc) hipLaunchKernelGGL(ba_dinv, dim3(d.n_wg_pt), dim3(kTPB), 0, ctx->stream, d, lambda);
   RC(launch_schur(ba));
-  PersArgs pa{};
-  pa.lambda = lambda; pa.rel_tol = rel_tol; pa.max_it = max_it; pa.n_clu = ccm_div_up(d.Cp, kClu);
-  pa.bar = ba->d_pers_bar; pa.slots = (unsigned long long*)ba->d_pers_part;
-  pa.utag = (unsigned long long*)ba->d_pers_u; pa.wbuf[0] = d.p[0]; pa.wbuf[1] = d.p[1];
-  pa.epoch_base = (++ba->pers_launch) << 20;
-  pa.uoff = ba->d_pers_uoff; pa.ucol = ba->d_pers_ucol; pa.loc = ba->d_pers_loc;
-  pa.coff = ba->d_pers_coff; pa.cij = ba->d_pers_cij; pa.cblk = ba->d_pers_cblk;
-  pa.test_abort = 0; pa.dbg = nullptr; pa.wsave = nullptr; pa.w_load = 0;
+  PersArgs pa = pers_args(ba, lambda, rel_tol, max_it);
   if (coarse) {
     RC(coarse_build(ba, lambda));
     ba->coarse_valid = false;   // (built for this hook: the LM loop's reuse policy must not take it for one of its own)
-    pa.Ainv = ba->d_cAinv; pa.Pm = ba->d_cP; pa.na = ba->coarse_na; pa.Nc = ba->coarse_Nc; pa.cparts = ba->d_cparts;
+    pers_args_coarse(ba, &pa);
   }
   CCM_HIP_CHECK(ctx, hipMemsetAsync(ba->d_pers_bar + 1, 0, sizeof(unsigned), ctx->stream));   // abort flag
   hipLaunchKernelGGL(ba_pcg_persist, dim3(ba->pers_grid), dim3(kPersTPB), pers_lds_bytes(), ctx->stream, d, pa);

@@ -852,12 +852,11 @@ extern "C" int ccm_ba_create(ccm_ctx* ctx, const ccm_ba_problem* P, int rank, in
     d.S = ba->d_red; d.bs = ba->d_red + 36 * (size_t)(Cp + nOff);
     BB_RC(keep_get(ba, 3 * (size_t)std::max(Lp, 1), &ba->d_pt_full, true));
     BB_RC(keep_get(ba, 36 * (size_t)std::max(Cp, 1), &ba->d_hpp_full, true));
-    auto coarse_buffers = [&](int n_units) -> int {
+    auto coarse_buffers = [&]() -> int {
       BB_RC(keep_get(ba, 36 * (size_t)Cp, &ba->d_cP, true));
       BB_RC(keep_get(ba, (size_t)Nc * Nc, &ba->d_cA, true)); BB_RC(keep_get(ba, (size_t)Nc * Nc, &ba->d_cX, true));
       BB_RC(keep_get(ba, (size_t)Nc * Nc, &ba->d_cAinv, true)); BB_RC(keep_get(ba, (size_t)Nc * 64, &ba->d_cLinv, true));
       BB_RC(keep_get(ba, 4, &ba->d_cinfo, true));
-      BB_RC(keep_get(ba, 24 * (size_t)std::max(n_units, 1), &ba->d_cparts, true));   // [2][12][units]
       ba->coarse_na = na; ba->coarse_Nc = Nc; ba->coarse_ncb = hs.ncb;
       if (const char* cf = getenv("CCM_BA_COARSE")) ba->coarse_force = !strcmp(cf, "always") ? 1 : !strcmp(cf, "never") ? -1 : 0;
       return CCM_OK;
@@ -869,9 +868,11 @@ extern "C" int ccm_ba_create(ccm_ctx* ctx, const ccm_ba_problem* P, int rank, in
       BB_RC(keep_get(ba, 4 + 2 * 16 + 4 * 512, &ba->d_pers_bar, true));   // abort flag + debug clocks (workgroup 0's phases; then per workgroup the time spent in the exchange and in the halo wait)
       BB_RC(keep_get(ba, 6 * (size_t)pers_grid_want, &ba->d_pers_part, true));   // [2][3][grid] slot words
       BB_RC(keep_get(ba, 12 * (size_t)Cp, &ba->d_pers_u, true));   // [6 Cp][2] tagged u
+      BB_RC(keep_get(ba, 2 * (2 * 6 * (size_t)Cp + 2 * 8 * (size_t)kPersNcCap), &ba->d_pers_tag, true));   // tagged w [2][6 Cp][2] | tagged coarse parts [2][8][kPersNcCap][2]
+      { const char* pf = getenv("CCM_BA_PERS_PREFETCH"); ba->pers_prefetch = !(pf && !strcmp(pf, "0")); }
       ba->pers_grid = pers_grid_want; ba->pers_grid_built = pers_grid_want;
       BB_RC(keep_get(ba, (size_t)pers_grid_want * (kCluN * (kCluN / 2)), &ba->d_pers_wsave, false));   // the units' halves of the cluster inverse, carried from trial to trial (written before read)
-      if (coarse_pers) BB_RC(coarse_buffers(pers_grid_want));
+      if (coarse_pers) BB_RC(coarse_buffers());
     } else if (pers_try) { ba->d_pers_uoff = nullptr; ba->d_pers_ucol = nullptr; ba->d_pers_loc = nullptr; }
     if (Cp > kSmallMaxCp && Cp <= kDense2MaxCp && ba->d_pers_coff)
       BB_RC(keep_get(ba, (size_t)kCluN * kCluN + 16, &ba->d_dense_T, true));   // + phase clocks (CCM_BA_DENSE2_DBG)
@@ -883,7 +884,7 @@ extern "C" int ccm_ba_create(ccm_ctx* ctx, const ccm_ba_problem* P, int rank, in
     }
     // maps too large for the persistent kernel: the same coarse level inside the multi-kernel PCG (kAgg = 2 clusters)
     if (!ba->pers_grid && coarse_mk) {
-      BB_RC(coarse_buffers(0));
+      BB_RC(coarse_buffers());
       double *p1 = nullptr, *p2 = nullptr, *p3 = nullptr;
       BB_RC(keep_get(ba, 24 * (size_t)(na + 1), &p1, true)); BB_RC(keep_get(ba, (size_t)n_cl, &p2, true)); BB_RC(keep_get(ba, (size_t)n_cl, &p3, true));
       d.mk_cpart = p1; d.mk_cry[0] = p2; d.mk_cry[1] = p3;

@@ -162,6 +162,10 @@ struct ccm_ba {
   // cluster inverse of the persistent solver carried from trial to trial (ba.hip, lm_trial): what it was built at, and the iteration guard
   double* d_pers_wsave = nullptr;   // [pers_grid][96 * 48]
   double* d_pers_u = nullptr;       // [6 Cp][2] u of the persistent solver's halo exchange as {bits, bits ^ key}
+  // w of every unknown (for the partner unit) and the units' parts of the coarse restriction, tagged like u, by epoch parity, in ONE block (one buffer
+  // descriptor in the kernel): [2][6 Cp][2] | [2][8][kPersNcCap][2]
+  unsigned long long* d_pers_tag = nullptr;
+  bool pers_prefetch = true;        // CCM_BA_PERS_PREFETCH (read at create): the partner's w and the coarse parts are fetched inside the exchange (0: after it)
   float* d_cAinv32 = nullptr;       // [Nc][Nc] multi-kernel path
   bool w_valid = false, w_loaded = false, w_stale_bad = false; double w_lambda_built = 0; int w_fresh_iters = 0, lin_id = 0, w_lin_id = -1;
   bool coarse_valid = false, coarse_fresh = false, coarse_stale_bad = false, coarse_reuse = true;
@@ -173,7 +177,6 @@ struct ccm_ba {
   unsigned long long rb_ticket = 0;
   int coarse_force = 0;      // CCM_BA_COARSE=always / never (tests), 0 = adaptive
   double *d_cP = nullptr, *d_cA = nullptr, *d_cX = nullptr, *d_cAinv = nullptr, *d_cLinv = nullptr;
-  double* d_cparts = nullptr;
   unsigned* d_cb_key = nullptr;   // [ncb] sorted keys a * na + b of the interval pairs that share S blocks
   double* d_cstage = nullptr;     // [ncb][4][36] weighted sums of every interval pair (ba_coarse_assemble -> ba_coarse_sum)
   int *d_cb_off = nullptr, *d_cb_ent = nullptr, *d_cb_ab = nullptr, *d_blk_i = nullptr, *d_blk_j = nullptr, *d_cinfo = nullptr;
