@@ -3,6 +3,8 @@
 //     body of ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (ORBmatcher.cpp:1030-1118) up to the decision, without the map mutations.
 //   ccm_fuse_pose_eval: every Fuse call of a LocalMapping::SearchInNeighbors (cslam/src/Mapping.cpp:471-547), both directions.  A pair is one pass of the loop body
 //     of ORBmatcher::Fuse(pKF, vpMapPoints, th) (ORBmatcher.cpp:883-965) up to the decision, without the skips and the map mutations.
+//   ccm_fuse_sim3_eval_resident, ccm_fuse_pose_eval_resident: the same two calls on keyframes of a keyframe store (kfstore.hip), whose static
+//     data is on the device already: the same pair body with kResident, which takes the keyframe's arrays from its slot of the store.
 // The lines of a pair are fuse_math.h; the two forms differ in the chi-square gate of the candidate (kChi2) and in how a workgroup finds its work.
 //
 // Layout.  fuse_sim3_kernel: the grid is (tiles of 256 points) x K keyframes, folded into one dimension.  fuse_pose_kernel: the work is a list
@@ -16,6 +18,7 @@
 // atomics, no lane leaves early, nothing waits on another workgroup, every loop is bounded by a count read from the inputs (validated on the host before the launch).
 #include "common.h"
 #include "fuse_math.h"
+#include "kfstore.h"
 #include "lane_xor.h"
 #include "stage_blocks.h"
 #include <chrono>
@@ -25,7 +28,8 @@ namespace {
 
 static_assert(FPM_TILE == 256, "both kernels run 256 lanes, one per pair");
 
-// everything either kernel reads.  P, tiles: the Sim3 form's grid; job, tile, inv_sigma2: the pose form's
+// everything either kernel reads.  P, tiles: the Sim3 form's grid; job, tile, inv_sigma2: the pose form's; slot, stride: the resident forms', whose rec, kxy, cell_off,
+// cell_idx, koct and kdesc are the store's arrays
 struct FuseArgs {
   int P, tiles, nlevels;
   float th, logsf;
@@ -36,6 +40,8 @@ struct FuseArgs {
   uint32_t* table;
   int32_t *n_valid, *n_hit;
   float* uv;   // nullptr: not asked for
+  const int32_t* slot;
+  int stride;
 };
 
 // the minimum of a 32-bit key over the wave; a u32 is exact in a double, so lane_xor.h's f64 exchange carries it
@@ -48,13 +54,16 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t key) {
 
 // One pair per lane: keyframe k (workgroup-uniform) x point i, answered into table[out] (and uv) and counted into n_valid / n_hit[counter] (workgroup-uniform).
 // A dead lane (!live) reads nothing through i and writes nothing, but stays for the wave-wide part, which needs all 64.
-template <bool kChi2>
+// kResident: the keyframe's static arrays are a slot of the keyframe store (kfstore.hip): slot[k] and slot[k] * stride take the place of k and feat_off[k].  Both are
+// workgroup-uniform like k, so the addresses still come from the scalar unit.
+template <bool kChi2, bool kResident>
 __device__ __forceinline__ void fuse_pair(const FuseArgs& a, int k, int i, bool live, uint32_t out, int counter) {
   const int lane = threadIdx.x & 63;
-  const float* rec = a.rec + (size_t)k * FSM_REC_FLOATS;
+  const int s = kResident ? a.slot[k] : k;
+  const float* rec = a.rec + (size_t)s * FSM_REC_FLOATS;
   const float* pose = a.pose + (size_t)k * FSM_POSE_FLOATS;
-  const int32_t f0 = a.feat_off[k];
-  const int32_t* cell_off = a.cell_off + (size_t)k * (FSM_CELLS + 1);
+  const int32_t f0 = kResident ? s * a.stride : a.feat_off[k];   // slots * stride <= INT32_MAX
+  const int32_t* cell_off = a.cell_off + (size_t)s * (FSM_CELLS + 1);
   const uint16_t* cell_idx = a.cell_idx + f0;
   const float* kxy = a.kxy + 2 * (size_t)f0;
   const uint8_t* koct = a.koct + f0;
@@ -132,21 +141,27 @@ __device__ __forceinline__ void fuse_pair(const FuseArgs& a, int k, int i, bool 
 }
 
 // workgroup = (keyframe k, tile of 256 points): word k * P + i (K * P <= INT32_MAX), the counters are the keyframe's
-__global__ __launch_bounds__(FPM_TILE) void fuse_sim3_kernel(FuseArgs a) {
+template <bool kResident>
+__device__ __forceinline__ void fuse_sim3_body(const FuseArgs& a) {
   const int k = (int)(blockIdx.x / (unsigned)a.tiles), tile = (int)(blockIdx.x % (unsigned)a.tiles);
   const int i = tile * FPM_TILE + (int)threadIdx.x;
-  fuse_pair<false>(a, k, i, i < a.P, (uint32_t)k * (uint32_t)a.P + (uint32_t)i, k);
+  fuse_pair<false, kResident>(a, k, i, i < a.P, (uint32_t)k * (uint32_t)a.P + (uint32_t)i, k);
 }
+__global__ __launch_bounds__(FPM_TILE) void fuse_sim3_kernel(FuseArgs a) { fuse_sim3_body<false>(a); }
+__global__ __launch_bounds__(FPM_TILE) void fuse_sim3_resident_kernel(FuseArgs a) { fuse_sim3_body<true>(a); }
 
 // workgroup = tile[blockIdx.x] = (job j, first pair of the job): the job's words start at its out0, the counters are the job's
-__global__ __launch_bounds__(FPM_TILE) void fuse_pose_kernel(FuseArgs a) {
+template <bool kResident>
+__device__ __forceinline__ void fuse_pose_body(const FuseArgs& a) {
   const int j = a.tile[2 * (size_t)blockIdx.x], i0 = a.tile[2 * (size_t)blockIdx.x + 1];
   const int32_t* jr = a.job + FPM_JOB_INTS * (size_t)j;
   const int k = jr[0], pt0 = jr[1], n = jr[2], out0 = jr[3];
   const int e = i0 + (int)threadIdx.x;   // the pair's place in the job
   const bool live = e < n;
-  fuse_pair<true>(a, k, live ? pt0 + e : pt0, live, (uint32_t)out0 + (uint32_t)e, j);
+  fuse_pair<true, kResident>(a, k, live ? pt0 + e : pt0, live, (uint32_t)out0 + (uint32_t)e, j);
 }
+__global__ __launch_bounds__(FPM_TILE) void fuse_pose_kernel(FuseArgs a) { fuse_pose_body<false>(a); }
+__global__ __launch_bounds__(FPM_TILE) void fuse_pose_resident_kernel(FuseArgs a) { fuse_pose_body<true>(a); }
 
 typedef std::chrono::steady_clock Clock;
 double us_between(Clock::time_point x, Clock::time_point y) { return std::chrono::duration<double, std::micro>(y - x).count(); }
@@ -172,6 +187,57 @@ FuseArgs fuse_stage_inputs(const Block& b, const float* kf_rec, const int32_t* f
   a.table = b.dev(b.table); a.n_valid = b.dev(b.n_valid); a.n_hit = b.dev(b.n_hit);
   a.uv = b.uv.count ? b.dev(b.uv) : nullptr;
   return a;
+}
+
+// The same for the resident blocks (FuseSim3ResidentBlock, FusePoseResidentBlock): the points and the per-call table from the caller, the keyframes' arrays from
+// the store, and the slot list fuse_store_slots made of the keys.  The caller holds the store's reader lock.
+template <class Block>
+FuseArgs fuse_resident_inputs(const Block& b, const ccm_kfstore* st, const std::vector<int32_t>& slots, int nlevels, const float* scale_factors, float logScaleFactor,
+                              float th, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc) {
+  if (b.slot.count) memcpy(b.up(b.slot), slots.data(), b.slot.count * sizeof(int32_t));
+  b.put(b.pdesc, pt_desc); b.put(b.scale_factors, scale_factors);
+  b.put(b.pos, pos); b.put(b.normal, normal); b.put(b.dmin, min_dist); b.put(b.dmax, max_dist);
+  FuseArgs a = {};
+  a.nlevels = nlevels; a.th = th; a.logsf = logScaleFactor;
+  a.rec = st->d_rec; a.kxy = st->d_xy; a.cell_off = st->d_cell_off; a.cell_idx = st->d_cell_idx; a.koct = st->d_oct; a.kdesc = st->d_desc;
+  a.slot = b.dev(b.slot); a.stride = st->stride;
+  a.pose = b.dev(b.pose); a.scale_factors = b.dev(b.scale_factors);
+  a.pos = b.dev(b.pos); a.normal = b.dev(b.normal); a.dmin = b.dev(b.dmin); a.dmax = b.dev(b.dmax); a.pdesc = b.dev(b.pdesc);
+  a.table = b.dev(b.table); a.n_valid = b.dev(b.n_valid); a.n_hit = b.dev(b.n_hit);
+  a.uv = b.uv.count ? b.dev(b.uv) : nullptr;
+  return a;
+}
+
+// keys -> slots under the caller's reader lock; CCM_E_ARG for a key that is not live
+int fuse_store_slots(ccm_ctx* ctx, const ccm_kfstore* st, int K, const int64_t* keys, const char* me, std::vector<int32_t>* slots) {
+  slots->resize((size_t)K);
+  for (int k = 0; k < K; k++) {
+    auto it = st->live.find(keys[k]);
+    if (it == st->live.end()) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + "a key is not in the store");
+    (*slots)[k] = it->second;
+  }
+  return CCM_OK;
+}
+
+// the pose form's job and tile segments from the (validated) job arrays
+template <class Block>
+void fuse_pose_jobs(const Block& b, int J, const int32_t* job_kf, const int32_t* job_pt0, const int32_t* job_n) {
+  int32_t* h_job = b.up(b.job);
+  int32_t* h_tile = b.up(b.tile);
+  int32_t out0 = 0;
+  size_t t = 0;
+  for (int j = 0; j < J; j++) {
+    h_job[FPM_JOB_INTS * (size_t)j] = job_kf[j]; h_job[FPM_JOB_INTS * (size_t)j + 1] = job_pt0[j];
+    h_job[FPM_JOB_INTS * (size_t)j + 2] = job_n[j]; h_job[FPM_JOB_INTS * (size_t)j + 3] = out0;
+    for (int32_t e = 0; e < job_n[j]; e += FPM_TILE, t++) { h_tile[2 * t] = j; h_tile[2 * t + 1] = e; }
+    out0 += job_n[j];
+  }
+}
+
+int fuse_store_ok(ccm_ctx* ctx, const ccm_kfstore* st, const char* me) {
+  if (!st) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + "NULL store");
+  if (st->device != ctx->device) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + "the context is on another device than the store");
+  return CCM_OK;
 }
 
 // after the launch: the download and the caller's outputs.  Returns when the device was done through *t2.
@@ -246,18 +312,7 @@ extern "C" int ccm_fuse_pose_eval(ccm_ctx* ctx, int K, const float* kf_rec, cons
   FuseArgs a = fuse_stage_inputs(b, kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off, cell_idx, nlevels, scale_factors, logScaleFactor, th, pos, normal,
                                  min_dist, max_dist, pt_desc);
   b.put(b.pose, pose); b.put(b.inv_sigma2, inv_level_sigma2);
-  int32_t* h_job = b.up(b.job);
-  int32_t* h_tile = b.up(b.tile);
-  {
-    int32_t out0 = 0;
-    size_t t = 0;
-    for (int j = 0; j < J; j++) {
-      h_job[FPM_JOB_INTS * (size_t)j] = job_kf[j]; h_job[FPM_JOB_INTS * (size_t)j + 1] = job_pt0[j];
-      h_job[FPM_JOB_INTS * (size_t)j + 2] = job_n[j]; h_job[FPM_JOB_INTS * (size_t)j + 3] = out0;
-      for (int32_t e = 0; e < job_n[j]; e += FPM_TILE, t++) { h_tile[2 * t] = j; h_tile[2 * t + 1] = e; }
-      out0 += job_n[j];
-    }
-  }
+  fuse_pose_jobs(b, J, job_kf, job_pt0, job_n);
   const Clock::time_point t1 = Clock::now();
   if (int rc = ccm_staged_upload(ctx, b)) return rc;
   a.inv_sigma2 = b.dev(b.inv_sigma2); a.job = b.dev(b.job); a.tile = b.dev(b.tile);
@@ -267,5 +322,75 @@ extern "C" int ccm_fuse_pose_eval(ccm_ctx* ctx, int K, const float* kf_rec, cons
   if (ccm_dbg("fuse"))
     fprintf(stderr, "[fuse_pose] K=%d P=%d J=%d pairs=%lld pack_us=%.1f device_us=%.1f unpack_us=%.1f up_bytes=%zu down_bytes=%zu\n", K, P, J, (long long)total,
             us_between(t0, t1), us_between(t1, t2), us_between(t2, Clock::now()), b.up_bytes(), b.down_bytes());
+  return CCM_OK;
+}
+
+extern "C" int ccm_fuse_sim3_eval_resident(ccm_ctx* ctx, ccm_kfstore* st, int K, const int64_t* keys, const float* Scw, int nlevels, const float* scale_factors,
+                                           float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist,
+                                           const uint8_t* pt_desc, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv) {
+  if (!ctx) return CCM_E_ARG;
+  const char* const me = "ccm_fuse_sim3_eval_resident: ";
+  if (int rc = fuse_store_ok(ctx, st, me)) return rc;
+  if (const char* why = fsm_check_scalars(K, P, nlevels, th)) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + why);
+  if (!scale_factors || (K > 0 && (!keys || !Scw || !n_valid || !n_hit)) || (P > 0 && (!pos || !normal || !min_dist || !max_dist || !pt_desc)) || (K > 0 && P > 0 && !table))
+    return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + "null pointers");
+  std::shared_lock<std::shared_mutex> lk(st->mu);   // from the key lookup to the end of the download: no slot read here is reused meanwhile
+  std::vector<int32_t> slots;
+  if (int rc = fuse_store_slots(ctx, st, K, keys, me, &slots)) return rc;
+  for (int k = 0; k < K; k++) n_valid[k] = n_hit[k] = 0;
+  if (K == 0 || P == 0) return CCM_OK;
+  FuseSim3ResidentBlock b((size_t)K, (size_t)P, (size_t)nlevels, uv != nullptr);
+  if (int rc = ccm_staged_begin(ctx, b, me)) return rc;
+  const Clock::time_point t0 = Clock::now();
+  FuseArgs a = fuse_resident_inputs(b, st, slots, nlevels, scale_factors, logScaleFactor, th, pos, normal, min_dist, max_dist, pt_desc);
+  float* h_pose = b.up(b.pose);
+  for (int k = 0; k < K; k++) fsm_decompose_scw(Scw + 12 * (size_t)k, h_pose + FSM_POSE_FLOATS * (size_t)k);
+  const Clock::time_point t1 = Clock::now();
+  if (int rc = ccm_staged_upload(ctx, b)) return rc;
+  a.P = P; a.tiles = (P + FPM_TILE - 1) / FPM_TILE;
+  const uint64_t groups = (uint64_t)K * (uint64_t)a.tiles;
+  if (groups > (uint64_t)INT32_MAX) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + "too many workgroups");
+  hipLaunchKernelGGL(fuse_sim3_resident_kernel, dim3((unsigned)groups), dim3(FPM_TILE), 0, ctx->stream, a);
+  Clock::time_point t2;
+  if (int rc = fuse_stage_outputs(ctx, b, table, n_valid, n_hit, uv, &t2)) return rc;
+  if (ccm_dbg("fuse"))
+    fprintf(stderr, "[fuse_resident] K=%d P=%d pack_us=%.1f device_us=%.1f unpack_us=%.1f up_bytes=%zu down_bytes=%zu\n", K, P, us_between(t0, t1), us_between(t1, t2),
+            us_between(t2, Clock::now()), b.up_bytes(), b.down_bytes());
+  return CCM_OK;
+}
+
+extern "C" int ccm_fuse_pose_eval_resident(ccm_ctx* ctx, ccm_kfstore* st, int K, const int64_t* keys, const float* pose, int nlevels, const float* scale_factors,
+                                           const float* inv_level_sigma2, float logScaleFactor, float th, int P, const float* pos, const float* normal,
+                                           const float* min_dist, const float* max_dist, const uint8_t* pt_desc, int J, const int32_t* job_kf, const int32_t* job_pt0,
+                                           const int32_t* job_n, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv) {
+  if (!ctx) return CCM_E_ARG;
+  const char* const me = "ccm_fuse_pose_eval_resident: ";
+  if (int rc = fuse_store_ok(ctx, st, me)) return rc;
+  if (const char* why = fsm_check_scalars(K, P, nlevels, th)) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + why);
+  int64_t total = 0, tiles = 0;
+  if (const char* why = fpm_check_jobs(J, K, P, job_kf, job_pt0, job_n, &total, &tiles)) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + why);
+  if (!scale_factors || !inv_level_sigma2 || (K > 0 && (!keys || !pose)) || (J > 0 && (!n_valid || !n_hit)) ||
+      (P > 0 && (!pos || !normal || !min_dist || !max_dist || !pt_desc)) || (total > 0 && !table))
+    return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + "null pointers");
+  std::shared_lock<std::shared_mutex> lk(st->mu);
+  std::vector<int32_t> slots;
+  if (int rc = fuse_store_slots(ctx, st, K, keys, me, &slots)) return rc;
+  for (int j = 0; j < J; j++) n_valid[j] = n_hit[j] = 0;
+  if (total == 0) return CCM_OK;
+  FusePoseResidentBlock b((size_t)K, (size_t)P, (size_t)nlevels, (size_t)J, (size_t)tiles, (size_t)total, uv != nullptr);
+  if (int rc = ccm_staged_begin(ctx, b, me)) return rc;
+  const Clock::time_point t0 = Clock::now();
+  FuseArgs a = fuse_resident_inputs(b, st, slots, nlevels, scale_factors, logScaleFactor, th, pos, normal, min_dist, max_dist, pt_desc);
+  b.put(b.pose, pose); b.put(b.inv_sigma2, inv_level_sigma2);
+  fuse_pose_jobs(b, J, job_kf, job_pt0, job_n);
+  const Clock::time_point t1 = Clock::now();
+  if (int rc = ccm_staged_upload(ctx, b)) return rc;
+  a.inv_sigma2 = b.dev(b.inv_sigma2); a.job = b.dev(b.job); a.tile = b.dev(b.tile);
+  hipLaunchKernelGGL(fuse_pose_resident_kernel, dim3((unsigned)tiles), dim3(FPM_TILE), 0, ctx->stream, a);
+  Clock::time_point t2;
+  if (int rc = fuse_stage_outputs(ctx, b, table, n_valid, n_hit, uv, &t2)) return rc;
+  if (ccm_dbg("fuse"))
+    fprintf(stderr, "[fuse_pose_resident] K=%d P=%d J=%d pairs=%lld pack_us=%.1f device_us=%.1f unpack_us=%.1f up_bytes=%zu down_bytes=%zu\n", K, P, J,
+            (long long)total, us_between(t0, t1), us_between(t1, t2), us_between(t2, Clock::now()), b.up_bytes(), b.down_bytes());
   return CCM_OK;
 }

@@ -204,11 +204,16 @@ FSM_HD uint32_t fsm_window_best(const float rec[FSM_REC_FLOATS], const int32_t* 
 }
 
 // The argument rules of ccm_fuse_sim3_eval; nullptr, or what is wrong.  The scalar rules come first and read no array.  cell_idx: int32 as the caller passes it.
-FSM_HD const char* fsm_check_args(int K, int P, const int32_t* feat_off, const int32_t* cell_off, const int32_t* cell_idx, int nlevels, float th) {
+// (fsm_check_scalars: the scalar rules alone, which are all the resident forms share with it: their keyframes are the store's, validated when they were added.)
+FSM_HD const char* fsm_check_scalars(int K, int P, int nlevels, float th) {
   if (K < 0 || P < 0) return "K or P negative";
   if ((int64_t)K * (int64_t)P > (int64_t)INT32_MAX) return "K * P beyond INT32_MAX";
   if (nlevels < 1 || nlevels > FSM_MAX_LEVELS) return "nlevels outside 1 .. 16";
   if (!(th > 0.0f) || !(th <= 3.402823466e+38f)) return "th not finite and positive";
+  return nullptr;
+}
+FSM_HD const char* fsm_check_args(int K, int P, const int32_t* feat_off, const int32_t* cell_off, const int32_t* cell_idx, int nlevels, float th) {
+  if (const char* why = fsm_check_scalars(K, P, nlevels, th)) return why;
   if (K == 0) return nullptr;
   if (!feat_off || !cell_off) return "null pointers";
   if (feat_off[0] != 0) return "feat_off[0] != 0";

@@ -1,0 +1,23 @@
+// kfstore.h — the keyframe feature store's handle, shared by kfstore.hip (which fills it) and fuse.hip (whose resident evaluators read it).  DESIGN.md §21.
+#pragma once
+#include "common.h"
+#include "kfstore_math.h"
+#include <shared_mutex>
+#include <unordered_map>
+
+struct ccm_kfstore {
+  int device = 0, max_kf = 0, max_feat = 0, stride = 0;   // stride: a slot's features, max_feat rounded up to KFG_FEAT_ALIGN
+  std::shared_mutex mu;                                    // resident evaluators and get shared, add / erase / clear exclusive
+  // device: one array per field, indexed by slot (features at slot * stride)
+  float* d_rec = nullptr;          // [10 max_kf]
+  int32_t* d_n = nullptr;          // [max_kf] features
+  int32_t* d_n_in = nullptr;       // [max_kf] features in the grid = cell_off[FSM_CELLS]
+  int32_t* d_cell_off = nullptr;   // [(FSM_CELLS + 1) max_kf]
+  uint16_t* d_cell_idx = nullptr;  // [stride max_kf]
+  float* d_xy = nullptr;           // [2 stride max_kf]
+  uint8_t* d_oct = nullptr;        // [stride max_kf]
+  uint8_t* d_desc = nullptr;       // [32 stride max_kf]
+  // host
+  std::unordered_map<int64_t, int> live;   // key -> slot
+  std::vector<int> free_slots;             // a stack: the slot freed last is taken first
+};

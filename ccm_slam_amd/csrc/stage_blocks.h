@@ -4,6 +4,7 @@
 #include "staged_block.h"
 #include "triangulate_math.h"
 #include "fuse_math.h"
+#include "kfstore_math.h"
 
 // ccm_sim3_ransac_eval: the inputs, then the outputs.
 struct Sim3RansacBlock : StagedBlock {
@@ -151,6 +152,48 @@ struct FusePoseBlock : StagedBlock {
   StagedSeg<uint16_t> cell_idx = add<uint16_t>(F, SB_GEN);
   StagedSeg<uint8_t> koct = add<uint8_t>(F, SB_COPY);
   StagedSeg<float> scale_factors = add<float>(L, SB_COPY), inv_sigma2 = add<float>(L, SB_COPY);
+  StagedSeg<float> pos = add<float>(3 * P, SB_COPY), normal = add<float>(3 * P, SB_COPY), dmin = add<float>(P, SB_COPY), dmax = add<float>(P, SB_COPY);
+  StagedSeg<int32_t> n_valid = add<int32_t>(J, SB_OUT | SB_ZERO), n_hit = add<int32_t>(J, SB_OUT | SB_ZERO);
+  StagedSeg<uint32_t> table = add<uint32_t>(N, SB_OUT);
+  StagedSeg<float> uv = add<float>(want_uv ? 2 * N : 0, SB_OUT);
+};
+
+// ccm_kfstore_add: M keyframes with F features in all, on their way into the slots slot[m] of the store.  The descriptors lead, on 16 bytes, for the kernel's 16-byte
+// copies.  A caller-supplied grid travels as cell_off and a 16-bit cell_idx the stage writes while it validates; without one both are declared with no elements and
+// the kernel builds the grid.  n_in (the features in the grid, per keyframe) comes back.
+struct KfstoreAddBlock : StagedBlock {
+  const size_t M, F; const bool grid;
+  KfstoreAddBlock(size_t M, size_t F, bool grid) : M(M), F(F), grid(grid) {}
+  StagedSeg<uint8_t> desc = add<uint8_t>(32 * F, SB_COPY, 16);
+  StagedSeg<int32_t> slot = add<int32_t>(M, SB_GEN), feat_off = add<int32_t>(M + 1, SB_COPY);
+  StagedSeg<float> rec = add<float>(FSM_REC_FLOATS * M, SB_COPY), xy = add<float>(2 * F, SB_COPY);
+  StagedSeg<int32_t> cell_off = add<int32_t>(grid ? M * (FSM_CELLS + 1) : 0, SB_COPY);
+  StagedSeg<uint16_t> cell_idx = add<uint16_t>(grid ? F : 0, SB_GEN);
+  StagedSeg<uint8_t> oct = add<uint8_t>(F, SB_COPY);
+  StagedSeg<int32_t> n_in = add<int32_t>(M, SB_OUT);
+};
+
+// ccm_fuse_sim3_eval_resident: FuseSim3Block without the keyframes' static data, which the kernel reads from the store's slots: slot[k] (written by the stage while it
+// looks the keys up) takes the place of feat_off, cell_off and the five feature arrays.
+struct FuseSim3ResidentBlock : StagedBlock {
+  const size_t K, P, L; const bool want_uv;
+  FuseSim3ResidentBlock(size_t K, size_t P, size_t L, bool want_uv) : K(K), P(P), L(L), want_uv(want_uv) {}
+  StagedSeg<uint8_t> pdesc = add<uint8_t>(32 * P, SB_COPY, 16);
+  StagedSeg<int32_t> slot = add<int32_t>(K, SB_GEN);
+  StagedSeg<float> pose = add<float>(FSM_POSE_FLOATS * K, SB_GEN), scale_factors = add<float>(L, SB_COPY);
+  StagedSeg<float> pos = add<float>(3 * P, SB_COPY), normal = add<float>(3 * P, SB_COPY), dmin = add<float>(P, SB_COPY), dmax = add<float>(P, SB_COPY);
+  StagedSeg<int32_t> n_valid = add<int32_t>(K, SB_OUT | SB_ZERO), n_hit = add<int32_t>(K, SB_OUT | SB_ZERO);
+  StagedSeg<uint32_t> table = add<uint32_t>(K * P, SB_OUT);
+  StagedSeg<float> uv = add<float>(want_uv ? 2 * K * P : 0, SB_OUT);
+};
+
+// ccm_fuse_pose_eval_resident: FusePoseBlock without the keyframes' static data, in the same way.
+struct FusePoseResidentBlock : StagedBlock {
+  const size_t K, P, L, J, T, N; const bool want_uv;
+  FusePoseResidentBlock(size_t K, size_t P, size_t L, size_t J, size_t T, size_t N, bool want_uv) : K(K), P(P), L(L), J(J), T(T), N(N), want_uv(want_uv) {}
+  StagedSeg<uint8_t> pdesc = add<uint8_t>(32 * P, SB_COPY, 16);
+  StagedSeg<int32_t> job = add<int32_t>(FPM_JOB_INTS * J, SB_GEN, 16), tile = add<int32_t>(2 * T, SB_GEN), slot = add<int32_t>(K, SB_GEN);
+  StagedSeg<float> pose = add<float>(FSM_POSE_FLOATS * K, SB_COPY), scale_factors = add<float>(L, SB_COPY), inv_sigma2 = add<float>(L, SB_COPY);
   StagedSeg<float> pos = add<float>(3 * P, SB_COPY), normal = add<float>(3 * P, SB_COPY), dmin = add<float>(P, SB_COPY), dmax = add<float>(P, SB_COPY);
   StagedSeg<int32_t> n_valid = add<int32_t>(J, SB_OUT | SB_ZERO), n_hit = add<int32_t>(J, SB_OUT | SB_ZERO);
   StagedSeg<uint32_t> table = add<uint32_t>(N, SB_OUT);

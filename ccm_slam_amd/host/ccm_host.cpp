@@ -9,6 +9,7 @@
 #include "../csrc/covis_math.h"
 #include "../csrc/kfcull_math.h"
 #include "../csrc/fuse_math.h"
+#include "../csrc/kfstore_math.h"
 #include <climits>
 #include <algorithm>
 #include <cmath>
@@ -1757,8 +1758,33 @@ static uint32_t fuse_pair_host(const float* rec, const float* pose, const int32_
   return w;
 }
 
+// one keyframe's own arrays, wherever they live: in the caller's flat arrays, or in a shadow of the keyframe store
+struct FuseKf { const float* rec; const int32_t* cell_off; const uint16_t* cell_idx; const float* kxy; const uint8_t* koct; const uint8_t* kdesc; };
+static FuseKf fuse_kf(const KfShadow& kf) { return {kf.rec, kf.cell_off.data(), kf.cell_idx.data(), kf.xy.data(), kf.oct.data(), kf.desc.data()}; }
+
 // every pair of a list of jobs (keyframe job_kf[j] x points job_pt0[j] .. + job_n[j]), the jobs' words one after the other; the arguments are valid.
-// pose: 15 floats per keyframe
+// kf_of(k): keyframe k's arrays; pose: 15 floats per keyframe
+template <bool kChi2, class KfOf>
+static void fuse_jobs_eval(KfOf kf_of, const float* pose, int nlevels, const float* scale_factors, const float* inv_level_sigma2, float logScaleFactor, float th,
+                           const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc, int J, const int32_t* job_kf,
+                           const int32_t* job_pt0, const int32_t* job_n, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv, int32_t* n_cand) {
+  size_t e = 0;
+  for (int j = 0; j < J; j++) {
+    n_valid[j] = n_hit[j] = 0;
+    const int k = job_kf[j];
+    const FuseKf kf = kf_of(k);
+    for (int i = job_pt0[j]; i < job_pt0[j] + job_n[j]; i++, e++) {
+      const uint32_t w = fuse_pair_host<kChi2>(kf.rec, pose + FSM_POSE_FLOATS * (size_t)k, kf.cell_off, kf.cell_idx, kf.kxy, kf.koct, kf.kdesc, pos + 3 * (size_t)i,
+                                               normal + 3 * (size_t)i, min_dist[i], max_dist[i], pt_desc + 32 * (size_t)i, nlevels, logScaleFactor, th, scale_factors,
+                                               inv_level_sigma2, uv ? uv + 2 * e : nullptr, n_cand ? n_cand + e : nullptr);
+      table[e] = w;
+      n_valid[j] += (w >> 29) >= FSM_EMPTY;
+      n_hit[j] += (w >> 29) == FSM_HIT;
+    }
+  }
+}
+
+// the same on the flat arrays of ccm_fuse_sim3_eval / ccm_fuse_pose_eval (cell_idx: int32 as the caller passes it)
 template <bool kChi2>
 static void fuse_jobs_host(const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
                            const int32_t* cell_off, const int32_t* cell_idx, const float* pose, int nlevels, const float* scale_factors, const float* inv_level_sigma2,
@@ -1767,21 +1793,13 @@ static void fuse_jobs_host(const float* kf_rec, const int32_t* feat_off, const f
                            float* uv, int32_t* n_cand) {
   std::vector<uint16_t> idx16(F);
   for (size_t f = 0; f < F; f++) idx16[f] = (uint16_t)cell_idx[f];
-  size_t e = 0;
-  for (int j = 0; j < J; j++) {
-    n_valid[j] = n_hit[j] = 0;
-    const int k = job_kf[j];
+  auto kf_of = [&](int k) {
     const int32_t f0 = feat_off[k];
-    for (int i = job_pt0[j]; i < job_pt0[j] + job_n[j]; i++, e++) {
-      const uint32_t w = fuse_pair_host<kChi2>(kf_rec + FSM_REC_FLOATS * (size_t)k, pose + FSM_POSE_FLOATS * (size_t)k, cell_off + (size_t)k * (FSM_CELLS + 1),
-                                               idx16.data() + f0, feat_xy + 2 * (size_t)f0, feat_octave + f0, feat_desc + 32 * (size_t)f0, pos + 3 * (size_t)i,
-                                               normal + 3 * (size_t)i, min_dist[i], max_dist[i], pt_desc + 32 * (size_t)i, nlevels, logScaleFactor, th, scale_factors,
-                                               inv_level_sigma2, uv ? uv + 2 * e : nullptr, n_cand ? n_cand + e : nullptr);
-      table[e] = w;
-      n_valid[j] += (w >> 29) >= FSM_EMPTY;
-      n_hit[j] += (w >> 29) == FSM_HIT;
-    }
-  }
+    return FuseKf{kf_rec + FSM_REC_FLOATS * (size_t)k, cell_off + (size_t)k * (FSM_CELLS + 1), idx16.data() + f0, feat_xy + 2 * (size_t)f0, feat_octave + f0,
+                  feat_desc + 32 * (size_t)f0};
+  };
+  fuse_jobs_eval<kChi2>(kf_of, pose, nlevels, scale_factors, inv_level_sigma2, logScaleFactor, th, pos, normal, min_dist, max_dist, pt_desc, J, job_kf, job_pt0, job_n,
+                        table, n_valid, n_hit, uv, n_cand);
 }
 
 // a packed answer as a Fuse call leaves bestIdx / bestDist (untouched where the pair has no candidate)
@@ -1816,10 +1834,16 @@ void FuseScene::copy(const KFs& kfs, const float* pose15, const Pts& pts, int nl
 }
 
 uint32_t FuseScene::eval(int k, const float* P3, const float* Pn, float dmin_, float dmax_, const uint8_t* desc) const {
-  const int32_t f0 = feat_off[k];
-  return (isig.empty() ? fuse_pair_host<false> : fuse_pair_host<true>)(
-      rec.data() + FSM_REC_FLOATS * (size_t)k, pose.data() + FSM_POSE_FLOATS * (size_t)k, cell_off.data() + (size_t)k * (FSM_CELLS + 1), cell_idx.data() + f0,
-      kxy.data() + 2 * (size_t)f0, koct.data() + f0, kdesc.data() + 32 * (size_t)f0, P3, Pn, dmin_, dmax_, desc, nlevels, logsf, th, sf.data(), isig.data(), nullptr, nullptr);
+  FuseKf kf;
+  if (!shadow.empty()) {
+    kf = fuse_kf(*shadow[k]);
+  } else {
+    const int32_t f0 = feat_off[k];
+    kf = {rec.data() + FSM_REC_FLOATS * (size_t)k, cell_off.data() + (size_t)k * (FSM_CELLS + 1), cell_idx.data() + f0, kxy.data() + 2 * (size_t)f0, koct.data() + f0,
+          kdesc.data() + 32 * (size_t)f0};
+  }
+  return (isig.empty() ? fuse_pair_host<false> : fuse_pair_host<true>)(kf.rec, pose.data() + FSM_POSE_FLOATS * (size_t)k, kf.cell_off, kf.cell_idx, kf.kxy, kf.koct, kf.kdesc,
+                                                                       P3, Pn, dmin_, dmax_, desc, nlevels, logsf, th, sf.data(), isig.data(), nullptr, nullptr);
 }
 
 int fuse_sim3_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
@@ -1971,6 +1995,210 @@ int SearchInNeighborsBatch::resolve_current(int n, const int32_t* slot, const ui
     sin_answer(w, bestIdx[i], bestDist[i], nFused);
   }
   return nFused;
+}
+
+// ---- KeyFrameStore and the batches built on it ----------------------------------------------------------
+KeyFrameStore::KeyFrameStore(HipContext* ctx, int max_kf, int max_feat) : max_kf_(max_kf), max_feat_(max_feat) {
+  if (max_kf < 1 || !kfg_stride(max_feat) || (int64_t)max_kf * kfg_stride(max_feat) > (int64_t)INT32_MAX) throw infrastructure_ex("KeyFrameStore: bad capacity");
+  if (ctx) check(ccm_kfstore_create(ctx->get(), max_kf, max_feat, &h_), ctx->get(), "ccm_kfstore_create");
+}
+
+KeyFrameStore::~KeyFrameStore() { ccm_kfstore_destroy(h_); }
+
+int KeyFrameStore::add(HipContext* ctx, int M, const int64_t* keys, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave,
+                       const uint8_t* feat_desc, const int32_t* cell_off, const int32_t* cell_idx) {
+  if (h_ && !ctx) throw infrastructure_ex("KeyFrameStore::add: a device store needs the calling thread's context");
+  std::unique_lock<std::shared_mutex> lk(mu_);
+  if (h_) {   // the device store decides, by the same rules in the same order, and the shadows follow it
+    const int rc = ccm_kfstore_add(h_, ctx->get(), M, keys, kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off, cell_idx);
+    if (rc == CCM_E_ARG || rc == CCM_E_STATE) return rc;
+    check(rc, ctx->get(), "ccm_kfstore_add");
+  } else {
+    if ((M > 0 && !keys) || kfg_check_add(M, max_feat_, kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off, cell_idx)) return CCM_E_ARG;
+    std::vector<int64_t> sorted(keys, keys + (M > 0 ? M : 0));
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return CCM_E_STATE;
+    for (int m = 0; m < M; m++)
+      if (live_.count(keys[m])) return CCM_E_STATE;
+    if ((size_t)M > (size_t)max_kf_ - live_.size()) return CCM_E_STATE;
+  }
+  for (int m = 0; m < M; m++) {
+    auto kf = std::make_shared<KfShadow>();
+    const int32_t f0 = feat_off[m], n = feat_off[m + 1] - f0;
+    std::memcpy(kf->rec, kf_rec + FSM_REC_FLOATS * (size_t)m, sizeof kf->rec);
+    kf->n = n;
+    if (n) {
+      kf->xy.assign(feat_xy + 2 * (size_t)f0, feat_xy + 2 * (size_t)(f0 + n));
+      kf->oct.assign(feat_octave + f0, feat_octave + f0 + n);
+      kf->desc.assign(feat_desc + 32 * (size_t)f0, feat_desc + 32 * (size_t)(f0 + n));
+    }
+    kf->cell_off.resize(FSM_CELLS + 1);
+    if (cell_off) {
+      const int32_t* co = cell_off + (size_t)m * (FSM_CELLS + 1);
+      kf->cell_off.assign(co, co + FSM_CELLS + 1);
+      kf->n_in = co[FSM_CELLS];
+      kf->cell_idx.resize((size_t)kf->n_in);
+      for (int32_t j = 0; j < kf->n_in; j++) kf->cell_idx[j] = (uint16_t)cell_idx[f0 + j];
+    } else {
+      kf->cell_idx.resize((size_t)n);
+      kf->n_in = kfg_build_host(kf->rec, n, kf->xy.data(), kf->cell_off.data(), kf->cell_idx.data());
+      kf->cell_idx.resize((size_t)kf->n_in);
+    }
+    live_[keys[m]] = std::move(kf);
+  }
+  return CCM_OK;
+}
+
+void KeyFrameStore::erase(HipContext* ctx, int64_t key) {
+  if (h_ && !ctx) throw infrastructure_ex("KeyFrameStore::erase: a device store needs the calling thread's context");
+  std::unique_lock<std::shared_mutex> lk(mu_);
+  if (h_) check(ccm_kfstore_erase(h_, ctx->get(), key), ctx->get(), "ccm_kfstore_erase");
+  live_.erase(key);
+}
+
+void KeyFrameStore::clear(HipContext* ctx) {
+  if (h_ && !ctx) throw infrastructure_ex("KeyFrameStore::clear: a device store needs the calling thread's context");
+  std::unique_lock<std::shared_mutex> lk(mu_);
+  if (h_) check(ccm_kfstore_clear(h_, ctx->get()), ctx->get(), "ccm_kfstore_clear");
+  live_.clear();
+}
+
+int KeyFrameStore::live() const { std::shared_lock<std::shared_mutex> lk(mu_); return (int)live_.size(); }
+int KeyFrameStore::free_slots() const { std::shared_lock<std::shared_mutex> lk(mu_); return max_kf_ - (int)live_.size(); }
+
+std::shared_ptr<const KfShadow> KeyFrameStore::shadow(int64_t key) const {
+  std::shared_lock<std::shared_mutex> lk(mu_);
+  auto it = live_.find(key);
+  return it == live_.end() ? nullptr : it->second;
+}
+
+bool KeyFrameStore::get(HipContext* ctx, int64_t key, int* n, int* n_in, int32_t* cell_off, int32_t* cell_idx) const {
+  const std::shared_ptr<const KfShadow> kf = shadow(key);
+  if (!kf) return false;
+  if (h_ && ctx) {
+    check(ccm_kfstore_get(h_, ctx->get(), key, n, n_in, cell_off, cell_idx), ctx->get(), "ccm_kfstore_get");
+    return true;
+  }
+  if (n) *n = kf->n;
+  if (n_in) *n_in = kf->n_in;
+  if (cell_off) std::memcpy(cell_off, kf->cell_off.data(), (FSM_CELLS + 1) * sizeof(int32_t));
+  if (cell_idx)
+    for (int j = 0; j < kf->n_in; j++) cell_idx[j] = kf->cell_idx[j];
+  return true;
+}
+
+template <class Pts>
+void FuseScene::hold(std::vector<std::shared_ptr<const KfShadow>> kfs, const float* pose15, const Pts& pts, int nlevels_, const float* scale_factors,
+                     const float* inv_level_sigma2, float logScaleFactor, float th_) {
+  const SearchAndFuseBatch::KeyFrames none;   // K = 0
+  copy(none, nullptr, pts, nlevels_, scale_factors, inv_level_sigma2, logScaleFactor, th_);   // the points and the call's values
+  if (!kfs.empty()) pose.assign(pose15, pose15 + FSM_POSE_FLOATS * kfs.size());
+  shadow = std::move(kfs);
+}
+
+// the shadows of keys[0 .. K); false when one is not live
+static bool store_shadows(const KeyFrameStore& store, int K, const int64_t* keys, std::vector<std::shared_ptr<const KfShadow>>& out) {
+  out.resize((size_t)(K > 0 ? K : 0));
+  for (int k = 0; k < K; k++)
+    if (!(out[k] = store.shadow(keys[k]))) return false;
+  return true;
+}
+
+static int sim3_resident_host(const std::vector<std::shared_ptr<const KfShadow>>& kfs, int K, const float* Scw, int nlevels, const float* scale_factors,
+                              float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist,
+                              const uint8_t* pt_desc, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv) {
+  std::vector<float> pose(FSM_POSE_FLOATS * (size_t)K);
+  std::vector<int32_t> jk((size_t)K), j0((size_t)K, 0), jn((size_t)K, P);
+  for (int k = 0; k < K; k++) { jk[k] = k; fsm_decompose_scw(Scw + 12 * (size_t)k, pose.data() + FSM_POSE_FLOATS * (size_t)k); }
+  fuse_jobs_eval<false>([&](int k) { return fuse_kf(*kfs[k]); }, pose.data(), nlevels, scale_factors, nullptr, logScaleFactor, th, pos, normal, min_dist, max_dist,
+                        pt_desc, K, jk.data(), j0.data(), jn.data(), table, n_valid, n_hit, uv, nullptr);
+  return 0;
+}
+
+int fuse_sim3_eval_resident_host(const KeyFrameStore& store, int K, const int64_t* keys, const float* Scw, int nlevels, const float* scale_factors, float logScaleFactor,
+                                 float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc,
+                                 uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv) {
+  if (fsm_check_scalars(K, P, nlevels, th)) return -1;
+  if (!scale_factors || (K > 0 && (!keys || !Scw || !n_valid || !n_hit)) || (P > 0 && (!pos || !normal || !min_dist || !max_dist || !pt_desc)) || (K > 0 && P > 0 && !table))
+    return -1;
+  std::vector<std::shared_ptr<const KfShadow>> kfs;
+  if (!store_shadows(store, K, keys, kfs)) return -1;
+  return sim3_resident_host(kfs, K, Scw, nlevels, scale_factors, logScaleFactor, th, P, pos, normal, min_dist, max_dist, pt_desc, table, n_valid, n_hit, uv);
+}
+
+int fuse_pose_eval_resident_host(const KeyFrameStore& store, int K, const int64_t* keys, const float* pose, int nlevels, const float* scale_factors,
+                                 const float* inv_level_sigma2, float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist,
+                                 const float* max_dist, const uint8_t* pt_desc, int J, const int32_t* job_kf, const int32_t* job_pt0, const int32_t* job_n,
+                                 uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv) {
+  if (fsm_check_scalars(K, P, nlevels, th)) return -1;
+  int64_t total = 0, tiles = 0;
+  if (fpm_check_jobs(J, K, P, job_kf, job_pt0, job_n, &total, &tiles)) return -1;
+  if (!scale_factors || !inv_level_sigma2 || (K > 0 && (!keys || !pose)) || (J > 0 && (!n_valid || !n_hit)) ||
+      (P > 0 && (!pos || !normal || !min_dist || !max_dist || !pt_desc)) || (total > 0 && !table))
+    return -1;
+  std::vector<std::shared_ptr<const KfShadow>> kfs;
+  if (!store_shadows(store, K, keys, kfs)) return -1;
+  fuse_jobs_eval<true>([&](int k) { return fuse_kf(*kfs[k]); }, pose, nlevels, scale_factors, inv_level_sigma2, logScaleFactor, th, pos, normal, min_dist, max_dist, pt_desc,
+                       J, job_kf, job_pt0, job_n, table, n_valid, n_hit, uv, nullptr);
+  return 0;
+}
+
+SearchAndFuseBatch::SearchAndFuseBatch(KeyFrameStore& store, HipContext* ctx, int K, const int64_t* keys, const float* Scw, const Points& pts, int nlevels,
+                                       const float* scale_factors, float logScaleFactor, float th)
+    : K_(K), P_(pts.P) {
+  const int P = P_;
+  if (K < 0 || P < 0 || !scale_factors || nlevels < 1 || nlevels > FSM_MAX_LEVELS || (K > 0 && (!keys || !Scw))) throw infrastructure_ex("SearchAndFuseBatch: bad arguments");
+  if (!store.host_only() && !ctx) throw infrastructure_ex("SearchAndFuseBatch: a device store needs the calling thread's context");
+  // the shadows first: what is held here stays valid whatever the store does from now on
+  std::vector<std::shared_ptr<const KfShadow>> kfs;
+  if (!store_shadows(store, K, keys, kfs)) throw infrastructure_ex("SearchAndFuseBatch: a key is not in the store");
+  table_.assign((size_t)K * (size_t)P, 0); n_valid_.assign((size_t)K, 0); n_hit_.assign((size_t)K, 0);
+  if (!store.host_only()) {
+    check(ccm_fuse_sim3_eval_resident(ctx->get(), store.handle(), K, keys, Scw, nlevels, scale_factors, logScaleFactor, th, P, pts.pos, pts.normal, pts.min_dist,
+                                      pts.max_dist, pts.desc, table_.data(), n_valid_.data(), n_hit_.data(), nullptr),
+          ctx->get(), "ccm_fuse_sim3_eval_resident");
+  } else {
+    if (fsm_check_scalars(K, P, nlevels, th) || (P > 0 && (!pts.pos || !pts.normal || !pts.min_dist || !pts.max_dist || !pts.desc)))
+      throw infrastructure_ex("SearchAndFuseBatch: bad arguments");
+    sim3_resident_host(kfs, K, Scw, nlevels, scale_factors, logScaleFactor, th, P, pts.pos, pts.normal, pts.min_dist, pts.max_dist, pts.desc, table_.data(),
+                       n_valid_.data(), n_hit_.data(), nullptr);
+  }
+  std::vector<float> pose(FSM_POSE_FLOATS * (size_t)K);
+  for (int k = 0; k < K; k++) fsm_decompose_scw(Scw + 12 * (size_t)k, pose.data() + FSM_POSE_FLOATS * (size_t)k);
+  scene_.hold(std::move(kfs), pose.data(), pts, nlevels, scale_factors, nullptr, logScaleFactor, th);
+}
+
+SearchInNeighborsBatch::SearchInNeighborsBatch(KeyFrameStore& store, HipContext* ctx, int K, const int64_t* keys, const float* pose, int n_calls, const int32_t* target,
+                                               int current, const Points& pts, int n_current, int nlevels, const float* scale_factors, const float* inv_level_sigma2,
+                                               float logScaleFactor, float th)
+    : K_(K), C_(n_calls), cur_(current), P1_(n_current), P2_(pts.P - n_current) {
+  const int P = pts.P, C = C_;
+  if (K < 0 || P < 0 || C < 0 || n_current < 0 || n_current > P || (C > 0 && !target) || !scale_factors || !inv_level_sigma2 || nlevels < 1 || nlevels > FSM_MAX_LEVELS ||
+      (int64_t)C * n_current + P2_ > (int64_t)INT32_MAX || (K > 0 && (!keys || !pose)))
+    throw infrastructure_ex("SearchInNeighborsBatch: bad arguments");
+  if (!store.host_only() && !ctx) throw infrastructure_ex("SearchInNeighborsBatch: a device store needs the calling thread's context");
+  std::vector<int32_t> jk, j0, jn;
+  for (int c = 0; c < C; c++) { jk.push_back(target[c]); j0.push_back(0); jn.push_back(P1_); }
+  if (current >= 0) { jk.push_back(current); j0.push_back(P1_); jn.push_back(P2_); }
+  else if (P2_ > 0) throw infrastructure_ex("SearchInNeighborsBatch: candidates without a current keyframe");
+  const int J = (int)jk.size();
+  std::vector<std::shared_ptr<const KfShadow>> kfs;
+  if (!store_shadows(store, K, keys, kfs)) throw infrastructure_ex("SearchInNeighborsBatch: a key is not in the store");
+  table_.assign((size_t)C * (size_t)P1_ + (size_t)P2_, 0); n_valid_.assign((size_t)J, 0); n_hit_.assign((size_t)J, 0);
+  if (!store.host_only()) {
+    check(ccm_fuse_pose_eval_resident(ctx->get(), store.handle(), K, keys, pose, nlevels, scale_factors, inv_level_sigma2, logScaleFactor, th, P, pts.pos, pts.normal,
+                                      pts.min_dist, pts.max_dist, pts.desc, J, jk.data(), j0.data(), jn.data(), table_.data(), n_valid_.data(), n_hit_.data(), nullptr),
+          ctx->get(), "ccm_fuse_pose_eval_resident");
+  } else {
+    int64_t total = 0, tiles = 0;
+    if (fsm_check_scalars(K, P, nlevels, th) || fpm_check_jobs(J, K, P, jk.data(), j0.data(), jn.data(), &total, &tiles) ||
+        (P > 0 && (!pts.pos || !pts.normal || !pts.min_dist || !pts.max_dist || !pts.desc)))
+      throw infrastructure_ex("SearchInNeighborsBatch: bad arguments");
+    fuse_jobs_eval<true>([&](int k) { return fuse_kf(*kfs[k]); }, pose, nlevels, scale_factors, inv_level_sigma2, logScaleFactor, th, pts.pos, pts.normal, pts.min_dist,
+                         pts.max_dist, pts.desc, J, jk.data(), j0.data(), jn.data(), table_.data(), n_valid_.data(), n_hit_.data(), nullptr, nullptr);
+  }
+  target_.assign(jk.begin(), jk.begin() + C);
+  scene_.hold(std::move(kfs), pose, pts, nlevels, scale_factors, inv_level_sigma2, logScaleFactor, th);
 }
 
 }  // namespace cslam
@@ -2634,6 +2862,78 @@ int ccmh_fuse_pose_eval_host(int K, const float* kf_rec, const int32_t* feat_off
                              int32_t* n_hit, float* uv, int32_t* n_cand) {
   return cslam::fuse_pose_eval_host(K, kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off, cell_idx, pose, nlevels, scale_factors, inv_level_sigma2, logScaleFactor,
                                     th, P, pos, normal, min_dist, max_dist, pt_desc, J, job_kf, job_pt0, job_n, table, n_valid, n_hit, uv, n_cand);
+}
+
+// KeyFrameStore through C, and the batches built on it
+void* ccmh_kfstore_create(int device, int max_kf, int max_feat) {
+  try { return new cslam::KeyFrameStore(device < 0 ? nullptr : &thread_context(device), max_kf, max_feat); } catch (const std::exception&) { return nullptr; }
+}
+void ccmh_kfstore_destroy(void* h) { delete static_cast<cslam::KeyFrameStore*>(h); }
+int ccmh_kfstore_add(void* h, int device, int M, const int64_t* keys, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave,
+                     const uint8_t* feat_desc, const int32_t* cell_off, const int32_t* cell_idx) {
+  if (!h) return -1000;
+  try {
+    return static_cast<cslam::KeyFrameStore*>(h)->add(device < 0 ? nullptr : &thread_context(device), M, keys, kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off,
+                                                      cell_idx);
+  } catch (const std::exception&) { return -1000; }
+}
+int ccmh_kfstore_erase(void* h, int device, int64_t key) {
+  if (!h) return -1000;
+  try { static_cast<cslam::KeyFrameStore*>(h)->erase(device < 0 ? nullptr : &thread_context(device), key); return 0; } catch (const std::exception&) { return -1000; }
+}
+int ccmh_kfstore_clear(void* h, int device) {
+  if (!h) return -1000;
+  try { static_cast<cslam::KeyFrameStore*>(h)->clear(device < 0 ? nullptr : &thread_context(device)); return 0; } catch (const std::exception&) { return -1000; }
+}
+int ccmh_kfstore_count(void* h, int* live, int* free_slots) {
+  if (!h) return -1000;
+  const cslam::KeyFrameStore& s = *static_cast<cslam::KeyFrameStore*>(h);
+  if (live) *live = s.live();
+  if (free_slots) *free_slots = s.free_slots();
+  return 0;
+}
+void* ccmh_kfstore_handle(void* h) { return h ? static_cast<cslam::KeyFrameStore*>(h)->handle() : nullptr; }
+int ccmh_kfstore_get(void* h, int device, int64_t key, int* n, int* n_in, int32_t* cell_off, int32_t* cell_idx) {
+  if (!h) return -1000;
+  try {
+    return static_cast<cslam::KeyFrameStore*>(h)->get(device < 0 ? nullptr : &thread_context(device), key, n, n_in, cell_off, cell_idx) ? 0 : -1;
+  } catch (const std::exception&) { return -1000; }
+}
+int ccmh_fuse_sim3_eval_resident_host(void* store, int K, const int64_t* keys, const float* Scw, int nlevels, const float* scale_factors, float logScaleFactor, float th,
+                                      int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc,
+                                      uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv) {
+  if (!store) return -1;
+  return cslam::fuse_sim3_eval_resident_host(*static_cast<cslam::KeyFrameStore*>(store), K, keys, Scw, nlevels, scale_factors, logScaleFactor, th, P, pos, normal, min_dist,
+                                             max_dist, pt_desc, table, n_valid, n_hit, uv);
+}
+int ccmh_fuse_pose_eval_resident_host(void* store, int K, const int64_t* keys, const float* pose, int nlevels, const float* scale_factors, const float* inv_level_sigma2,
+                                      float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist,
+                                      const uint8_t* pt_desc, int J, const int32_t* job_kf, const int32_t* job_pt0, const int32_t* job_n, uint32_t* table,
+                                      int32_t* n_valid, int32_t* n_hit, float* uv) {
+  if (!store) return -1;
+  return cslam::fuse_pose_eval_resident_host(*static_cast<cslam::KeyFrameStore*>(store), K, keys, pose, nlevels, scale_factors, inv_level_sigma2, logScaleFactor, th, P, pos,
+                                             normal, min_dist, max_dist, pt_desc, J, job_kf, job_pt0, job_n, table, n_valid, n_hit, uv);
+}
+void* ccmh_fuse_sim3_create_resident(void* store, int device, int K, const int64_t* keys, const float* Scw, int nlevels, const float* scale_factors, float logScaleFactor,
+                                     float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc) {
+  if (!store) return nullptr;
+  try {
+    cslam::SearchAndFuseBatch::Points pt;
+    pt.P = P; pt.pos = pos; pt.normal = normal; pt.min_dist = min_dist; pt.max_dist = max_dist; pt.desc = pt_desc;
+    return new cslam::SearchAndFuseBatch(*static_cast<cslam::KeyFrameStore*>(store), device < 0 ? nullptr : &thread_context(device), K, keys, Scw, pt, nlevels,
+                                         scale_factors, logScaleFactor, th);
+  } catch (const std::exception&) { return nullptr; }
+}
+void* ccmh_fuse_pose_create_resident(void* store, int device, int K, const int64_t* keys, const float* pose, int nlevels, const float* scale_factors,
+                                     const float* inv_level_sigma2, float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist,
+                                     const float* max_dist, const uint8_t* pt_desc, int n_calls, const int32_t* target, int current, int n_current) {
+  if (!store) return nullptr;
+  try {
+    cslam::SearchInNeighborsBatch::Points pt;
+    pt.P = P; pt.pos = pos; pt.normal = normal; pt.min_dist = min_dist; pt.max_dist = max_dist; pt.desc = pt_desc;
+    return new cslam::SearchInNeighborsBatch(*static_cast<cslam::KeyFrameStore*>(store), device < 0 ? nullptr : &thread_context(device), K, keys, pose, n_calls, target,
+                                             current, pt, n_current, nlevels, scale_factors, inv_level_sigma2, logScaleFactor, th);
+  } catch (const std::exception&) { return nullptr; }
 }
 
 int ccmh_search_for_initialization(int device, const float* x1, const float* y1, const int32_t* oct1, const float* a1, const uint8_t* d1, int N1,

@@ -16,6 +16,10 @@
 #include "../../include/ccm_hip.h"
 #include "sim3_schedule.h"
 #include <map>
+#include <memory>
+#include <mutex>
+#include <shared_mutex>
+#include <unordered_map>
 
 namespace cslam {
 
@@ -543,6 +547,50 @@ class TwoViewInitializer {
 };
 
 // ---------------------------------------------------------------------------------------------------
+// KeyFrameStore — the keyframes' static data of the two Fuse stages, resident on the device (include/ccm_hip.h ccm_kfstore_*), and a host shadow
+// per live key: the record, mvKeysUn, the octaves, the descriptors and the grid.  The shadow's grid is the caller's when one is supplied, otherwise it is built
+// here by KeyFrame::AssignFeaturesToGrid / PosInGrid (csrc/kfstore_math.h, the lines the device's grid kernel runs): the host evaluator of that kernel.
+// A server adds a keyframe after the message constructor's AssignFeaturesToGrid with NO grid (mGrid is protected and need not be read: the rule reads what the
+// keyframe keeps); a client's Frame-born keyframe needs the Frame's grid supplied.  erase where the map erases the keyframe.
+// ctx == nullptr at construction asks for the host-only store by name.  One store is shared by all threads: add / erase / clear are serialised, shadows are
+// handed out as shared_ptr, so a batch that holds them outlives an erase.
+// ---------------------------------------------------------------------------------------------------
+struct KfShadow {
+  float rec[10];
+  int n = 0, n_in = 0;
+  std::vector<float> xy;
+  std::vector<uint8_t> oct, desc;
+  std::vector<int32_t> cell_off;    // 3601
+  std::vector<uint16_t> cell_idx;   // n_in
+};
+
+class KeyFrameStore {
+ public:
+  KeyFrameStore(HipContext* ctx, int max_kf, int max_feat);
+  ~KeyFrameStore();
+  KeyFrameStore(const KeyFrameStore&) = delete;
+  KeyFrameStore& operator=(const KeyFrameStore&) = delete;
+  // ccm_kfstore_add's arguments and refusals: 0, CCM_E_ARG or CCM_E_STATE, the store untouched by a refusal; a device error throws.  ctx: the calling thread's
+  // (ignored by the host-only store).
+  int add(HipContext* ctx, int M, const int64_t* keys, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave,
+          const uint8_t* feat_desc, const int32_t* cell_off = nullptr, const int32_t* cell_idx = nullptr);
+  void erase(HipContext* ctx, int64_t key);
+  void clear(HipContext* ctx);
+  int live() const;
+  int free_slots() const;
+  bool host_only() const { return h_ == nullptr; }
+  ccm_kfstore* handle() const { return h_; }
+  std::shared_ptr<const KfShadow> shadow(int64_t key) const;   // null: not live
+  // the grid of one key: the device's (ccm_kfstore_get) with a context, the shadow's without; false: the key is not live
+  bool get(HipContext* ctx, int64_t key, int* n, int* n_in, int32_t* cell_off, int32_t* cell_idx) const;
+ private:
+  ccm_kfstore* h_ = nullptr;
+  int max_kf_ = 0, max_feat_ = 0;
+  mutable std::shared_mutex mu_;
+  std::unordered_map<int64_t, std::shared_ptr<const KfShadow>> live_;
+};
+
+// ---------------------------------------------------------------------------------------------------
 // What a Fuse batch (SearchAndFuseBatch, SearchInNeighborsBatch below) keeps for its resolves: a copy of the keyframes (poses as Rcw, tcw, Ow; cell_idx in 16 bits)
 // and points it was evaluated on, the call's scalars and level tables, and the pair evaluator on them (csrc/fuse_math.h).  Not part of the API.
 // ---------------------------------------------------------------------------------------------------
@@ -552,11 +600,16 @@ struct FuseScene {
   std::vector<int32_t> feat_off, cell_off;
   std::vector<uint16_t> cell_idx;
   std::vector<uint8_t> koct, kdesc, pdesc;
+  std::vector<std::shared_ptr<const KfShadow>> shadow;   // a batch built on a KeyFrameStore: the keyframes' arrays are the store's shadows, shared, not copied
   // kfs, pts: a batch's KeyFrames and Points, already validated; pose15: 15 floats per keyframe; inv_level_sigma2 == nullptr: the Sim3 form
   template <class KFs, class Pts>
   void copy(const KFs& kfs, const float* pose15, const Pts& pts, int nlevels, const float* scale_factors, const float* inv_level_sigma2, float logScaleFactor, float th);
   // the packed answer of keyframe k and a point given by its data and descriptor
   uint32_t eval(int k, const float* P3, const float* Pn, float dmin, float dmax, const uint8_t* desc) const;
+  // the same for keyframes of a store: shared ownership of their shadows, the points and the call's values copied
+  template <class Pts>
+  void hold(std::vector<std::shared_ptr<const KfShadow>> kfs, const float* pose15, const Pts& pts, int nlevels, const float* scale_factors, const float* inv_level_sigma2,
+            float logScaleFactor, float th);
 };
 
 // ---------------------------------------------------------------------------------------------------
@@ -577,6 +630,10 @@ class SearchAndFuseBatch {
   struct Points { int P = 0; const float* pos = nullptr; const float* normal = nullptr; const float* min_dist = nullptr; const float* max_dist = nullptr;
                   const uint8_t* desc = nullptr; };
   SearchAndFuseBatch(HipContext* ctx, const KeyFrames& kfs, const Points& pts, int nlevels, const float* scale_factors, float logScaleFactor, float th);
+  // The same on keyframes of a store: keyframe k of the batch is the live key keys[k] (a key may repeat), Scw + 12 k its Sim3.  ONE ccm_fuse_sim3_eval_resident
+  // call with ctx, or the host evaluation when the store is host-only.  The batch shares the shadows of its keyframes: an erase during its life leaves it valid.
+  SearchAndFuseBatch(KeyFrameStore& store, HipContext* ctx, int K, const int64_t* keys, const float* Scw, const Points& pts, int nlevels, const float* scale_factors,
+                     float logScaleFactor, float th);
   // The k-th Fuse call.  skip_now[i] != 0: the reference would `continue` now (pMP->isBad() || spAlreadyFound.count(pMP)); desc_now (nullable): the points' CURRENT
   // descriptors.  bestIdx[i] = the feature point i is fused with (-1: none), bestDist[i] its distance; returns nFused.
   int resolve(int k, const uint8_t* skip_now, const uint8_t* desc_now, std::vector<int32_t>& bestIdx, std::vector<int32_t>& bestDist);
@@ -621,6 +678,10 @@ class SearchInNeighborsBatch {
   // current < 0: no second direction (pts holds the current keyframe's points alone)
   SearchInNeighborsBatch(HipContext* ctx, const KeyFrames& kfs, int n_calls, const int32_t* target, int current, const Points& pts, int n_current, int nlevels,
                          const float* scale_factors, const float* inv_level_sigma2, float logScaleFactor, float th);
+  // The same on keyframes of a store: keyframe k is the live key keys[k], pose + 15 k its pose; target and current index keys.  ONE ccm_fuse_pose_eval_resident
+  // call with ctx, or the host evaluation when the store is host-only.  The batch shares the shadows of its keyframes.
+  SearchInNeighborsBatch(KeyFrameStore& store, HipContext* ctx, int K, const int64_t* keys, const float* pose, int n_calls, const int32_t* target, int current,
+                         const Points& pts, int n_current, int nlevels, const float* scale_factors, const float* inv_level_sigma2, float logScaleFactor, float th);
   // The c-th Fuse call of the first loop.  skip_now[i] != 0: the reference would `continue` now (!pMP || isBad() || IsInKeyFrame(pKF) || mbDoNotReplace);
   // desc_now (nullable): the current keyframe's points' CURRENT descriptors.  bestIdx[i] = the feature point i is fused with (-1: none), bestDist[i] as the
   // reference leaves it (256: no candidate); returns nFused.
@@ -651,6 +712,16 @@ int fuse_pose_eval_host(int K, const float* kf_rec, const int32_t* feat_off, con
                         float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc,
                         int J, const int32_t* job_kf, const int32_t* job_pt0, const int32_t* job_n, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv,
                         int32_t* n_cand);
+
+// ccm_fuse_sim3_eval_resident's / ccm_fuse_pose_eval_resident's arguments after the context on the store's shadows through csrc/fuse_math.h on the calling thread;
+// -1 where the device entry returns CCM_E_ARG (a key that is not live among it).
+int fuse_sim3_eval_resident_host(const KeyFrameStore& store, int K, const int64_t* keys, const float* Scw, int nlevels, const float* scale_factors, float logScaleFactor,
+                                 float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc,
+                                 uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv);
+int fuse_pose_eval_resident_host(const KeyFrameStore& store, int K, const int64_t* keys, const float* pose, int nlevels, const float* scale_factors,
+                                 const float* inv_level_sigma2, float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist,
+                                 const float* max_dist, const uint8_t* pt_desc, int J, const int32_t* job_kf, const int32_t* job_pt0, const int32_t* job_n,
+                                 uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv);
 
 // ---------------------------------------------------------------------------------------------------
 // Optimizer — cslam/include/cslam/Optimizer.h:84-112 (numerics; graph walking is the integrator's glue)

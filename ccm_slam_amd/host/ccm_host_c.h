@@ -148,6 +148,24 @@ int ccmh_fuse_pose_eval_host(int K, const float* kf_rec, const int32_t* feat_off
 void ccmh_to_se3quat(const float* Tcw16, double* qt7);
 void ccmh_se3quat_to_cvmat(const double* qt7, float* Tcw16);
 void ccmh_sim3_to_cvse3(const double* s8, float* Tcw16);
+/* cslam::KeyFrameStore.  device < 0 at create asks for the host-only store by name; create returns NULL on bad arguments or a device error.  The
+ * `device` of the other calls names the calling thread's context (ignored by a host-only store).  add returns 0, CCM_E_ARG (-1) or CCM_E_STATE (-6) as
+ * ccm_kfstore_add does, -1000 on a device error; get returns -1 for a key that is not live.  eval_resident_host: the resident calls' arguments after the context on the
+ * store's shadows through csrc/fuse_math.h (0, or -1 for their CCM_E_ARG cases).  create_resident: the batches' constructors on keys of a store; the handles are
+ * used and destroyed through ccmh_fuse_sim3_* / ccmh_fuse_pose_* above. */
+void* ccmh_kfstore_create(int device, int max_kf, int max_feat);
+void ccmh_kfstore_destroy(void* h);
+int ccmh_kfstore_add(void* h, int device, int M, const int64_t* keys, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc, const int32_t* cell_off, const int32_t* cell_idx);
+int ccmh_kfstore_erase(void* h, int device, int64_t key);
+int ccmh_kfstore_clear(void* h, int device);
+int ccmh_kfstore_count(void* h, int* live, int* free_slots);
+void* ccmh_kfstore_handle(void* h);   /* the ccm_kfstore* of include/ccm_hip.h, NULL for a host-only store */
+int ccmh_kfstore_get(void* h, int device, int64_t key, int* n, int* n_in, int32_t* cell_off, int32_t* cell_idx);
+int ccmh_fuse_sim3_eval_resident_host(void* store, int K, const int64_t* keys, const float* Scw, int nlevels, const float* scale_factors, float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv);
+int ccmh_fuse_pose_eval_resident_host(void* store, int K, const int64_t* keys, const float* pose, int nlevels, const float* scale_factors, const float* inv_level_sigma2, float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc, int J, const int32_t* job_kf, const int32_t* job_pt0, const int32_t* job_n, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv);
+void* ccmh_fuse_sim3_create_resident(void* store, int device, int K, const int64_t* keys, const float* Scw, int nlevels, const float* scale_factors, float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc);
+void* ccmh_fuse_pose_create_resident(void* store, int device, int K, const int64_t* keys, const float* pose, int nlevels, const float* scale_factors, const float* inv_level_sigma2, float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc, int n_calls, const int32_t* target, int current, int n_current);
+
 #ifdef __cplusplus
 }
 #endif

@@ -639,6 +639,46 @@ int  ccm_fuse_pose_eval(ccm_ctx* ctx, int K, const float* kf_rec /* 10 K */, con
                         const int32_t* job_kf, const int32_t* job_pt0, const int32_t* job_n, uint32_t* table /* sum(job_n) */, int32_t* n_valid /* J */,
                         int32_t* n_hit /* J */, float* uv /* 2 sum(job_n) or NULL */);
 
+/* ---- Keyframe feature store: the keyframes' static data of the two Fuse stages, resident on the device ------------------------------------
+ * What ccm_fuse_sim3_eval / ccm_fuse_pose_eval read of a keyframe never changes after the keyframe is built (Replace / AddObservation touch point descriptors
+ * alone), so it is uploaded once: kf_rec, feat_xy, feat_octave, feat_desc and the 75 x 48 grid as a CSR.  Fixed capacity: max_kf slots of max_feat
+ * features (1 .. 65 535, rounded up to a multiple of 16), max_kf * max_feat <= INT32_MAX; nothing grows.
+ * One handle is shared by all threads; every call uses the CALLER's context (same device as the handle, else CCM_E_ARG); add / erase / clear are serialised and
+ * finished on the device when they return; the resident evaluators and get run concurrently and hold a reader lock from their key lookup to the end of their
+ * download, so an erase waits for them. */
+typedef struct ccm_kfstore ccm_kfstore;
+int  ccm_kfstore_create(ccm_ctx* ctx, int max_kf, int max_feat, ccm_kfstore** out);
+void ccm_kfstore_destroy(ccm_kfstore* store);
+/* M >= 0 keyframes in one upload and one launch; arrays as for ccm_fuse_sim3_eval.  cell_off == cell_idx == NULL: the grid is built on the device by the keyframe's
+ * own rule, KeyFrame::AssignFeaturesToGrid with KeyFrame::PosInGrid (KeyFrame.cpp:206-225, :265-275: the int bounds kf_rec[4], [5] and the inverses kf_rec[8], [9];
+ * a keypoint outside the grid is in no cell; ascending feature index inside a cell) — the grid of every keyframe born from a message.  Both given: the caller's grid
+ * (a Frame-born keyframe's, built from the Frame's float bounds), held to ccm_fuse_sim3_eval's rules except that it may end below the feature count.
+ * Refusals leave the store untouched: CCM_E_STATE for a live key, a key repeated within the call, fewer than M free slots; CCM_E_ARG for a keyframe with more
+ * than max_feat features, null pointers, one grid pointer without the other, and the offset / index rules. */
+int  ccm_kfstore_add(ccm_kfstore* store, ccm_ctx* ctx, int M, const int64_t* keys /* M */, const float* kf_rec /* 10 M */, const int32_t* feat_off /* M + 1 */,
+                     const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc, const int32_t* cell_off /* 3601 M or NULL */,
+                     const int32_t* cell_idx /* or NULL */);
+/* frees the key's slot for reuse; an unknown key is a no-op */
+int  ccm_kfstore_erase(ccm_kfstore* store, ccm_ctx* ctx, int64_t key);
+int  ccm_kfstore_clear(ccm_kfstore* store, ccm_ctx* ctx);
+int  ccm_kfstore_count(ccm_kfstore* store, int* live, int* free_slots);
+/* one slot's grid as the device holds it: n features, n_in of them in the grid, cell_off[3601] (nullable), cell_idx[n_in] (nullable; room for n).  An unknown
+ * key: CCM_E_ARG */
+int  ccm_kfstore_get(ccm_kfstore* store, ccm_ctx* ctx, int64_t key, int* n, int* n_in, int32_t* cell_off, int32_t* cell_idx);
+
+/* ccm_fuse_sim3_eval / ccm_fuse_pose_eval on keyframes of the store: keyframe k of the call is the live key keys[k] (a key may appear more than once), Scw / pose
+ * per k as there.  Outputs, packing, statuses, counters and refusals are those of the two calls above; additionally CCM_E_ARG, with nothing launched, for a NULL
+ * store, a store on another device and a key that is not live.  The upload carries the slot list, Scw / pose, the per-call tables and the points. */
+int  ccm_fuse_sim3_eval_resident(ccm_ctx* ctx, ccm_kfstore* store, int K, const int64_t* keys /* K */, const float* Scw /* 12 K */, int nlevels,
+                                 const float* scale_factors, float logScaleFactor, float th, int P, const float* pos /* 3 P */, const float* normal /* 3 P */,
+                                 const float* min_dist, const float* max_dist, const uint8_t* pt_desc /* 32 P */, uint32_t* table /* K P */,
+                                 int32_t* n_valid /* K */, int32_t* n_hit /* K */, float* uv /* 2 K P or NULL */);
+int  ccm_fuse_pose_eval_resident(ccm_ctx* ctx, ccm_kfstore* store, int K, const int64_t* keys /* K */, const float* pose /* 15 K */, int nlevels,
+                                 const float* scale_factors, const float* inv_level_sigma2, float logScaleFactor, float th, int P, const float* pos /* 3 P */,
+                                 const float* normal /* 3 P */, const float* min_dist, const float* max_dist, const uint8_t* pt_desc /* 32 P */, int J,
+                                 const int32_t* job_kf, const int32_t* job_pt0, const int32_t* job_n, uint32_t* table /* sum(job_n) */,
+                                 int32_t* n_valid /* J */, int32_t* n_hit /* J */, float* uv /* 2 sum(job_n) or NULL */);
+
 #ifdef __cplusplus
 }
 #endif
