@@ -16,6 +16,7 @@
 #include "common.h"
 #include "ba_types.h"
 #include "ba_math.h"
+#include "ba_sort.h"
 #include <algorithm>
 #include <chrono>
 #include <cstring>
@@ -119,11 +120,12 @@ int sort_pairs(ccm_ctx* ctx, Tmp& tmp, K* keys, int* vals, size_t n, unsigned bi
   BB_RC(tmp.get(n, &k2)); BB_RC(tmp.get(n, &v2));
   rocprim::double_buffer<K> kb(keys, k2);
   rocprim::double_buffer<int> vb(vals, v2);
+  const bool onesweep = ba_sort_onesweep(n);
   size_t bytes = 0;
-  BB_HIP(rocprim::radix_sort_pairs(nullptr, bytes, kb, vb, (unsigned)n, 0u, bits, ctx->stream));
+  BB_HIP(ba_radix_sort_pairs(onesweep, nullptr, bytes, kb, vb, (unsigned)n, bits, ctx->stream));
   char* scratch = nullptr;
   BB_RC(tmp.get(bytes, &scratch));
-  BB_HIP(rocprim::radix_sort_pairs(scratch, bytes, kb, vb, (unsigned)n, 0u, bits, ctx->stream));
+  BB_HIP(ba_radix_sort_pairs(onesweep, scratch, bytes, kb, vb, (unsigned)n, bits, ctx->stream));
   *keys_sorted = kb.current(); *vals_sorted = vb.current();
   return CCM_OK;
 }

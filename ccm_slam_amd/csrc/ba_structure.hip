@@ -2,12 +2,14 @@
 // buildStructure (block_solver.hpp:143-295) needs, for every pair of free cameras that share a landmark, one Hschur block
 // and the list of (edge_a, edge_c) observation pairs that contribute to it.  On the 4-agent merged map that is 3.1 M
 // pairs in 64 k blocks; building it on the host (generate, two counting-sort passes, run-length split) was 55 % of
-// ccm_ba_create.  Here: one thread per landmark counts and emits its pairs (key = ia*Cp + ic, value = both edge positions),
-// a stable LSD radix sort groups them by block while keeping the landmark order inside a block (the summation order
+// ccm_ba_create.  Here: one thread per landmark counts its pairs, a workgroup per 32 landmarks emits them (key = ia*Cp + ic, value = both
+// edge positions), a stable LSD radix sort groups them by block while keeping the landmark order inside a block (the summation order
 // of the gather kernel, hence bit-identical results), run-length encoding yields the block list.  A sharded rank sorts
 // the keys of ALL landmarks for the (global, rank-independent) block list and the pairs of its OWN landmarks for the
-// instance lists, and finds its per-block ranges by binary search.  rocPRIM supplies scan / sort / run-length encode.
+// instance lists, and finds its per-block ranges by binary search.  rocPRIM supplies scan and run-length encode, and the sort:
+// one workgroup up to 1024 items, block sort + merge passes up to 2^18, onesweep above (ba_sort.h; rocPRIM itself would merge up to 2^20).
 #include "common.h"
+#include "ba_sort.h"
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 #include <vector>
@@ -16,27 +18,85 @@ namespace {
 
 constexpr int kTPB = 256;
 
-// edges of a landmark are sorted by pose slot, fixed cameras (slot -1) first; a pair needs two different free cameras
-template <int EMIT>
-__global__ void pairs_kernel(const int* pt_off, const int* cslot, int l0, int n_l, int Cp, int* cnt, const int* poff, uint32_t* keys,
-                             unsigned long long* vals) {
+// edges of a landmark are sorted by pose slot, fixed cameras (slot -1) first; a pair needs two different free cameras.  The pairs of a landmark are enumerated
+// row after row: row a (an observation of a free camera) pairs with every later observation c of another camera, c ascending.  The order is sorted, so the
+// later observations of the SAME camera follow a directly: row a holds positions a + 1 + d .. k1 - 1, d = row_same(...) of them skipped.
+__device__ __forceinline__ int row_same(const int* __restrict__ cslot, int a, int k1, int ia) {
+  int d = 0;
+  while (a + 1 + d < k1 && cslot[a + 1 + d] == ia) d++;
+  return d;
+}
+
+// one thread per landmark: the number of its pairs
+__global__ void pairs_count_kernel(const int* __restrict__ pt_off, const int* __restrict__ cslot, int l0, int n_l, int* __restrict__ cnt) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_l) return;
-  const int l = l0 + i;
-  const int k0 = pt_off[l], k1 = pt_off[l + 1];
+  const int k1 = pt_off[l0 + i + 1];
   int n = 0;
-  int w = EMIT ? poff[i] : 0;
-  for (int a = k0; a < k1; a++) {
+  for (int a = pt_off[l0 + i]; a < k1; a++) {
     const int ia = cslot[a];
-    if (ia < 0) continue;
-    for (int c = a + 1; c < k1; c++) {
-      const int ic = cslot[c];
-      if (ic == ia) continue;
-      if (EMIT) { keys[w] = (uint32_t)ia * (uint32_t)Cp + (uint32_t)ic; if (vals) vals[w] = ((unsigned long long)(uint32_t)a << 32) | (uint32_t)c; w++; }
-      n++;
-    }
+    if (ia >= 0) n += k1 - 1 - a - row_same(cslot, a, k1, ia);
   }
-  if (!EMIT) cnt[i] = n;
+  cnt[i] = n;
+}
+
+// the emit: a workgroup takes kEmitLm consecutive landmarks and writes their pairs with thread t on pair t, t + 256, ... of the workgroup's range, so that every
+// store of a wave is contiguous (one thread per landmark wrote its ~21 pairs to consecutive positions: neighbouring lanes 250 bytes apart, 0.46 TB/s).  The rows
+// of the landmarks (their observations, in order) go through LDS in tiles of one row per thread: pose slots staged, each row's length and same-camera skip
+// computed by its thread, lengths prefix-summed over the workgroup; a pair index then finds its row by binary search in that prefix (empty rows, those of fixed
+// cameras and every landmark's last, share their successor's offset and are never found).  A landmark may span tiles: a row needs only its landmark's end
+// (binary search in the workgroup's kEmitLm + 1 offsets) and the pose slots behind it, which are read from memory where they lie outside the tile.
+// 32 landmarks (~200 rows, ~700 pairs on the 4-agent map) measured best of 16 ... 128 with one to four rows per thread.
+constexpr int kEmitLm = 32;
+__global__ __launch_bounds__(kTPB) void pairs_emit_kernel(const int* __restrict__ pt_off, const int* __restrict__ cslot, int l0, int n_l, int Cp,
+                                                          const int* __restrict__ poff, uint32_t* __restrict__ keys, unsigned long long* __restrict__ vals) {
+  __shared__ int s_off[kEmitLm + 1];  // first observation of each landmark of the workgroup, and the end
+  __shared__ int s_cs[kTPB];          // pose slots of the tile's rows
+  __shared__ int s_skip[kTPB];        // observations of the same camera behind each row
+  __shared__ int s_row[kTPB + 1];     // index (inside the tile) of each row's first pair: exclusive scan of the lengths
+  const int t = threadIdx.x;
+  const int i0 = blockIdx.x * kEmitLm, nl = min(kEmitLm, n_l - i0);
+  for (int j = t; j <= nl; j += kTPB) s_off[j] = pt_off[l0 + i0 + j];
+  __syncthreads();
+  const int e0 = s_off[0], e1 = s_off[nl];
+  int w = poff[i0];                   // where the tile's first pair goes
+  for (int r0 = e0; r0 < e1; r0 += kTPB) {
+    const int nr = min(kTPB, e1 - r0);
+    if (t < nr) s_cs[t] = cslot[r0 + t];
+    __syncthreads();
+    auto cs = [&](int x) { return x - r0 < nr ? s_cs[x - r0] : cslot[x]; };
+    int len = 0, d = 0;               // row t of the tile
+    if (t < nr) {
+      const int a = r0 + t, ia = s_cs[t];
+      if (ia >= 0) {
+        int lo = 0, hi = nl;          // its landmark: the last one that begins at or before a
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (s_off[mid] <= a) lo = mid; else hi = mid; }
+        const int k1 = s_off[lo + 1];
+        while (a + 1 + d < k1 && cs(a + 1 + d) == ia) d++;
+        len = k1 - 1 - a - d;
+      }
+      s_skip[t] = d;
+    }
+    s_row[t + 1] = len;
+    if (t == 0) s_row[0] = 0;
+    __syncthreads();
+    for (int off = 1; off < kTPB; off <<= 1) {   // inclusive Hillis-Steele scan of s_row[1 ..]
+      const int v = (t >= off) ? s_row[t + 1 - off] : 0;
+      __syncthreads();
+      s_row[t + 1] += v;
+      __syncthreads();
+    }
+    const int n_tile = s_row[kTPB];   // (rows at and behind nr have length 0)
+    for (int p = t; p < n_tile; p += kTPB) {
+      int lo = 0, hi = nr;            // the row of pair p: the last one whose first pair is at or before p
+      while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (s_row[mid] <= p) lo = mid; else hi = mid; }
+      const int a = r0 + lo, c = a + 1 + s_skip[lo] + (p - s_row[lo]);
+      keys[w + p] = (uint32_t)s_cs[lo] * (uint32_t)Cp + (uint32_t)cs(c);
+      if (vals) vals[w + p] = ((unsigned long long)(uint32_t)a << 32) | (uint32_t)c;
+    }
+    w += n_tile;
+    __syncthreads();                  // (the next tile overwrites what the pair loop reads)
+  }
 }
 
 __global__ void split_kernel(const unsigned long long* vals, int n, int eb, int* inst_a, int* inst_c) {
@@ -82,8 +142,7 @@ int emit_pairs(ccm_ctx* ctx, Tmp& tmp, const int* d_pt_off, const int* d_cslot, 
   int *cnt = nullptr, *poff = nullptr;
   ST_RC(tmp.get((size_t)n_l + 1, &cnt)); ST_RC(tmp.get((size_t)n_l + 1, &poff));
   ST_HIP(hipMemsetAsync(cnt + n_l, 0, sizeof(int), ctx->stream));
-  hipLaunchKernelGGL(pairs_kernel<0>, dim3(ccm_div_up(n_l, kTPB)), dim3(kTPB), 0, ctx->stream, d_pt_off, d_cslot, l0, n_l, Cp, cnt, (const int*)nullptr,
-                     (uint32_t*)nullptr, (unsigned long long*)nullptr);
+  hipLaunchKernelGGL(pairs_count_kernel, dim3(ccm_div_up(n_l, kTPB)), dim3(kTPB), 0, ctx->stream, d_pt_off, d_cslot, l0, n_l, cnt);
   size_t bytes = 0;
   ST_HIP(rocprim::exclusive_scan(nullptr, bytes, cnt, poff, 0, (size_t)n_l + 1, rocprim::plus<int>(), ctx->stream));
   char* scratch = nullptr;
@@ -96,8 +155,8 @@ int emit_pairs(ccm_ctx* ctx, Tmp& tmp, const int* d_pt_off, const int* d_cslot, 
   if (total == 0) return CCM_OK;
   ST_RC(tmp.get((size_t)total, keys));
   if (with_vals) ST_RC(tmp.get((size_t)total, vals));
-  hipLaunchKernelGGL(pairs_kernel<1>, dim3(ccm_div_up(n_l, kTPB)), dim3(kTPB), 0, ctx->stream, d_pt_off, d_cslot, l0, n_l, Cp, (int*)nullptr, (const int*)poff,
-                     *keys, with_vals ? *vals : (unsigned long long*)nullptr);
+  hipLaunchKernelGGL(pairs_emit_kernel, dim3((unsigned)ccm_div_up(n_l, kEmitLm)), dim3(kTPB), 0, ctx->stream, d_pt_off, d_cslot, l0, n_l, Cp,
+                     (const int*)poff, *keys, with_vals ? *vals : (unsigned long long*)nullptr);
   ST_HIP(hipGetLastError());
   return CCM_OK;
 }
@@ -130,11 +189,12 @@ int ccm_ba_build_pairs(ccm_ctx* ctx, const int* d_pt_off, const int* d_cslot, in
     ST_RC(tmp.get((size_t)n_own, &ok2)); ST_RC(tmp.get((size_t)n_own, &ov2));
     rocprim::double_buffer<uint32_t> kb(ok, ok2);
     rocprim::double_buffer<unsigned long long> vb(ov, ov2);
+    const bool onesweep = ba_sort_onesweep((size_t)n_own);
     size_t bytes = 0;
-    ST_HIP(rocprim::radix_sort_pairs(nullptr, bytes, kb, vb, (unsigned)n_own, 0u, bits, ctx->stream));
+    ST_HIP(ba_radix_sort_pairs(onesweep, nullptr, bytes, kb, vb, (unsigned)n_own, bits, ctx->stream));
     char* scratch = nullptr;
     ST_RC(tmp.get(bytes, &scratch));
-    ST_HIP(rocprim::radix_sort_pairs(scratch, bytes, kb, vb, (unsigned)n_own, 0u, bits, ctx->stream));
+    ST_HIP(ba_radix_sort_pairs(onesweep, scratch, bytes, kb, vb, (unsigned)n_own, bits, ctx->stream));
     ok_sorted = kb.current(); ov_sorted = vb.current();
   }
   // ---- global block list: keys of all landmarks (the own ones when this rank owns everything) ----
@@ -147,11 +207,12 @@ int ccm_ba_build_pairs(ccm_ctx* ctx, const int* d_pt_off, const int* d_cslot, in
       uint32_t* gk2 = nullptr;
       ST_RC(tmp.get((size_t)n_all, &gk2));
       rocprim::double_buffer<uint32_t> kb(gk, gk2);
+      const bool onesweep = ba_sort_onesweep((size_t)n_all);
       size_t bytes = 0;
-      ST_HIP(rocprim::radix_sort_keys(nullptr, bytes, kb, (unsigned)n_all, 0u, bits, ctx->stream));
+      ST_HIP(ba_radix_sort_keys(onesweep, nullptr, bytes, kb, (unsigned)n_all, bits, ctx->stream));
       char* scratch = nullptr;
       ST_RC(tmp.get(bytes, &scratch));
-      ST_HIP(rocprim::radix_sort_keys(scratch, bytes, kb, (unsigned)n_all, 0u, bits, ctx->stream));
+      ST_HIP(ba_radix_sort_keys(onesweep, scratch, bytes, kb, (unsigned)n_all, bits, ctx->stream));
       gk_sorted = kb.current();
     }
   }
