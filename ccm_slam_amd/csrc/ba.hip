@@ -1386,7 +1386,7 @@ struct PersArgs {
   unsigned* bar;        // [1] abort flag
   int test_abort;              // CCM_BA_TEST_ABORT: the last workgroup leaves at once (exercises the abort -> multi-kernel fallback)
   const int* coff; const int* cij; const uint32_t* cblk;   // per cluster: entries inside its own 16x16 block (local row << 4 | column, S block)
-  unsigned long long* slots;   // [2][3][grid]: the exchanges alternate between two slot sets (epoch parity), word-major 24-byte slots
+  unsigned long long* slots;   // [2][grid][4]: the exchanges alternate between two slot sets (epoch parity), slot-major 32-byte records
   unsigned long long* utag;    // [6 Cp][2]: u of every unknown as {bits, bits ^ key(epoch)} (the halo exchange validates itself)
   // [2][6 Cp][2] | [2][8][kPersNcCap][2], by epoch parity, every value as {bits, bits ^ key(epoch)} like u: w = (S + lambda I) u of the own rows for the
   // partner unit, then the units' parts of the coarse restriction P^T w (6 for the first node of the unit's interval, 6 for the second) where their READER
@@ -1432,8 +1432,9 @@ __device__ __forceinline__ double tag_value(pers_u32x4 q) { return __longlong_as
 
 // Grid-wide "barrier + deterministic sum" of TWO values in one step, without atomics (256 arrivals on one counter
 // serialise at the memory side: measured 6 us per barrier): every workgroup publishes its partials (a, b) in its own
-// 24-byte slot as {bits(a), bits(b), bits(a) ^ bits(b) ^ key(epoch)} and then polls ALL slots (one per thread) until
-// every slot validates against the current epoch's key; the xor check also rejects torn reads.  The values are then
+// 32-byte slot as {bits(a), bits(b), bits(a) ^ bits(b) ^ key(epoch), 0} and then polls ALL slots (one per thread) until
+// every slot validates against the current epoch's key; the xor check also rejects torn reads and a record whose two
+// 16-byte halves come from two epochs.  The values are then
 // summed in a fixed order, so every workgroup obtains bit-identical totals.  All cross-workgroup data (u, w, slots,
 // coarse parts) moves with device-coherent accesses and EVERY datum validates itself against the key of the exchange it
 // rides on, so nothing orders the unit's stores against its slot: a reader that passes the exchange (or fetches inside
@@ -1443,15 +1444,18 @@ __device__ __forceinline__ double tag_value(pers_u32x4 q) { return __longlong_as
 // part / u is rewritten by the wave that wrote it, at the same address, and only after its readers validated the
 // earlier value, i.e. after that store had landed; x, the saved inverse and the flags are read after the kernel ends.
 template <class Mid>
-__device__ __forceinline__ bool pers_exchange(int t /* threadIdx.x */, unsigned long long* slots /* [3][nwg] */, int nwg, int me, double a_thread, double b_thread,
+__device__ __forceinline__ bool pers_exchange(int t /* threadIdx.x */, __amdgpu_buffer_rsrc_t slot_rs /* both slot sets */, unsigned set_off /* bytes: this epoch's set [nwg][4] */,
+                                              int nwg, int me, double a_thread, double b_thread,
                                               bool force_nan, unsigned long long epoch, unsigned* abort_flag, double* red /* [2 kPersWaves + 4] */,
                                               double* total_a, double* total_b, int* poll_fail /* LDS, sticky: an aborted exchange ends the solve */,
                                               Mid&& mid /* what waves 1..15 do while wave 0 polls; a failure there sets *poll_fail and the abort flag itself */) {
   // a_thread, b_thread: this thread's shares of the unit's partials.  The unit sums, the publish and the grid-wide sums
   // share two block barriers: wave sums -> LDS, (barrier), thread 0 adds the 16 wave sums of each value in
   // a fixed order and publishes, wave 0 polls (lane = source units t, t+64, ...; nwg <= 256), (barrier), everybody reads
-  // the grid totals.  The slot words are stored WORD-MAJOR (word w of unit i at slots[w * nwg + i]) so that a wave's load
-  // of one word is 512 contiguous bytes.  Variants measured and dropped: polling with 4 or 16 waves (slows the units
+  // the grid totals.  A slot is ONE 32-byte record, written with two 16-byte device-coherent stores and read with two such
+  // loads (as three words in three lines 2 KB apart it cost three 8-byte stores per publish and twelve 8-byte loads per lane
+  // and round); slot-major, so lane t's slots t, t + 64, ... are contiguous for the wave.  The descriptor's byte count bounds
+  // every access.  Variants measured and dropped: polling with 4 or 16 waves (slows the units
   // still computing), wide slots that also carried the coarse components (8-12 us per exchange; they travel like u and
   // w), and pushing the value into per-unit inboxes (64K scattered write-through stores per exchange).
   const unsigned long long key = 0x9E3779B97F4A7C15ull * epoch;
@@ -1466,9 +1470,12 @@ __device__ __forceinline__ bool pers_exchange(int t /* threadIdx.x */, unsigned 
     for (int w = 0; w < kPersWaves; w++) { ma += red[w]; mb += red[kPersWaves + w]; }
     if (force_nan) ma = __longlong_as_double(0x7ff8000000000000ll);
     const unsigned long long ba = (unsigned long long)__double_as_longlong(ma), bb = (unsigned long long)__double_as_longlong(mb);
-    __hip_atomic_store(slots + me, ba, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(slots + nwg + me, bb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(slots + 2 * nwg + me, ba ^ bb ^ key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long bc = ba ^ bb ^ key;
+    pers_u32x4 q0, q1;
+    q0.x = (unsigned)ba; q0.y = (unsigned)(ba >> 32); q0.z = (unsigned)bb; q0.w = (unsigned)(bb >> 32);
+    q1.x = (unsigned)bc; q1.y = (unsigned)(bc >> 32); q1.z = 0u; q1.w = 0u;
+    __builtin_amdgcn_raw_buffer_store_b128(q0, slot_rs, (int)(set_off + 32u * (unsigned)me), 0, kAuxSc1);
+    __builtin_amdgcn_raw_buffer_store_b128(q1, slot_rs, (int)(set_off + 32u * (unsigned)me + 16u), 0, kAuxSc1);
   }
   if (t < kWave) {
     constexpr int kPer = 4;    // slots per lane
@@ -1480,14 +1487,17 @@ __device__ __forceinline__ bool pers_exchange(int t /* threadIdx.x */, unsigned 
     // (measured and dropped, round 3: a second poll request ~0.25 us behind the first so that an incomplete first answer does not cost a whole further round
     // trip: the per-unit time inside an exchange went from 3.4 to 4.1-4.4 us — twice the polling traffic on the slot lines slows every answer down)
     for (long spins = 0;; spins++) {
+      asm volatile("" ::: "memory");   // every round reads memory again
 #pragma unroll
       for (int j = 0; j < kPer; j++) {
         if (done & (1u << j)) continue;   // a slot that validated is not read again
-        const unsigned long long* in = slots + t + j * kWave;
-        const unsigned long long b0 = __hip_atomic_load(in, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned long long b1 = __hip_atomic_load(in + nwg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned long long b2 = __hip_atomic_load(in + 2 * nwg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((b0 ^ b1 ^ b2) == key) { done |= 1u << j; va[j] = __longlong_as_double((long long)b0); vb[j] = __longlong_as_double((long long)b1); }
+        const unsigned in = set_off + 32u * (unsigned)(t + j * kWave);
+        const pers_u32x4 q0 = tag_load(slot_rs, in), q1 = tag_load(slot_rs, in + 16u);
+        if ((q0.x ^ q0.z ^ q1.x) == (unsigned)key && (q0.y ^ q0.w ^ q1.y) == (unsigned)(key >> 32)) {
+          done |= 1u << j;
+          va[j] = __longlong_as_double((long long)(((unsigned long long)q0.y << 32) | q0.x));
+          vb[j] = __longlong_as_double((long long)(((unsigned long long)q0.w << 32) | q0.z));
+        }
       }
       if (__all(done == (1u << kPer) - 1u)) break;
       if (spins > kPersMaxSpins || __hip_atomic_load(abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) { ok_w = false; break; }
@@ -2267,6 +2277,50 @@ __global__ __launch_bounds__(kPersTPB) void ba_pcg_persist(BaDev d, PersArgs a) 
   long long* tacc = reinterpret_cast<long long*>(ibuf + 4);   // [13]: 12 phases + last stamp
   const bool timing = a.dbg != nullptr && blockIdx.x == 0 && t == 0;
   if (timing) { for (int q = 0; q < 12; q++) tacc[q] = 0; tacc[12] = wall_clock64(); }
+  // Loop-invariant per-thread indices (everything derived from threadIdx) must NOT stay live across the PCG loop: the
+  // 60 VGPRs of S blocks leave ~60 for the rest, and LLVM hoists every such index out of the loop and then spills it
+  // (29-50 scratch reloads per iteration measured).  tq / lq are re-laundered copies of t / lane, opaque to the
+  // optimiser, refreshed at the top of every iteration: the indices are recomputed (a few integer ops) instead.
+  int tq = t, lq = lane;
+  const bool coarse = a.Ainv != nullptr;
+  const int aggu = d.agg >> 3;               // units per interval (an interval is a multiple of the 8 cameras of a unit)
+  const int agg = u / aggu;                  // interval of the unit's cameras: nodes agg and agg + 1
+  // unit part of the coarse restriction P^T v for the own rows: wave 0, lane = (component c, camera k); the 8 camera
+  // terms of a component sit in 8 neighbouring lanes; every camera's term goes with weight 1 - t to the first node of the unit's interval and with t
+  // to the second.  Published component-major for the other units.
+  // The tagged values (PersArgs::tag): one descriptor over the whole block, byte offsets of w of unknown i / of part comp of a unit, by the parity of the
+  // exchange they ride on
+  auto key_of = [](unsigned long long e) { return 0x9E3779B97F4A7C15ull * e; };
+  const unsigned tag_w_pairs = 2u * 6u * (unsigned)d.Cp;
+  const __amdgpu_buffer_rsrc_t tag_rs = __builtin_amdgcn_make_buffer_rsrc(a.tag, 0, (int)(16u * (tag_w_pairs + 2u * 8u * (unsigned)kPersNcCap)), 0x00020000);
+  // u of every unknown (PersArgs::utag) and the two slot sets of the exchanges (PersArgs::slots), each behind a descriptor of its own size
+  const __amdgpu_buffer_rsrc_t u_rs = __builtin_amdgcn_make_buffer_rsrc(a.utag, 0, (int)(16u * 6u * (unsigned)d.Cp), 0x00020000);
+  const __amdgpu_buffer_rsrc_t slot_rs = __builtin_amdgcn_make_buffer_rsrc(a.slots, 0, (int)(2u * 32u * (unsigned)nwg), 0x00020000);
+  auto w_off = [&](unsigned long long e, int i) { return 16u * ((unsigned)(e & 1) * 6u * (unsigned)d.Cp + (unsigned)i); };
+  // coarse component j of plane pl: the 64 lanes of a gathering wave read 1 KB in one piece (unit-major parts cost every lane a cache line of its own)
+  auto c_off = [&](unsigned long long e, int pl, int j) { return 16u * (tag_w_pairs + ((unsigned)(e & 1) * 8u + (unsigned)pl) * (unsigned)kPersNcCap + (unsigned)j); };
+  auto coarse_restrict = [&](const double* pk /* P_k of the own cameras [8][36] */, const double* vec /* own 48 entries */, unsigned long long e /* the exchange the parts ride on */) {
+    if (wv == 0) {
+      const int cc = lq >> 3, kk = lq & 7;
+      double sv = 0;
+      if (cc < 6 && kk < nown) {
+#pragma unroll
+        for (int rr = 0; rr < 6; rr++) sv += pk[kk * 36 + rr * 6 + cc] * vec[6 * kk + rr];
+      }
+      const double w1 = coarse_hat_t(8 * u + kk, d.agg);
+      double s0v = (1.0 - w1) * sv, s1v = w1 * sv;
+      s0v = lanex::add_partner<1>(s0v); s1v = lanex::add_partner<1>(s1v);
+      s0v = lanex::add_partner<2>(s0v); s1v = lanex::add_partner<2>(s1v);
+      s0v = lanex::add_partner<4>(s0v); s1v = lanex::add_partner<4>(s1v);
+      // (the units behind the last interval — padding of the grid — have no reader)
+      if (cc < 6 && kk == 0 && agg < a.na) { tag_store(tag_rs, c_off(e, u - aggu * agg, 6 * agg + cc), s0v, key_of(e)); tag_store(tag_rs, c_off(e, 4 + u - aggu * agg, 6 * (agg + 1) + cc), s1v, key_of(e)); }
+    }
+  };
+  // The coarse residual of r0 = b needs the units' parts of P^T b before the first preconditioner application.  b and P_k are known now, so wave 0 forms
+  // and publishes them HERE, keyed like the exchange that used to carry them (epoch + 1), straight from global memory (the LDS copy of P_k lives in the Li
+  // region, which the factorisation is about to use): the same products in the same order as from pown and rc.  By the time W is in place — ~80 us of
+  // factorisation, or ~5 us of loading it — they have landed everywhere, and the gather below is a fetch alone instead of a whole grid exchange (~4 us).
+  if (coarse) coarse_restrict(a.Pm + 36 * (size_t)o0, d.bs + 6 * (size_t)o0, epoch + 1);
   // keep only the unit's own 48 rows of W, transposed (WT[col][row]: conflict-free for the mat-vec); the other half of the
   // A region then holds the coarse level: Ac^-1 rows of the two nodes of the unit's interval (as f32: it is only a preconditioner, and 12 rows in f64
   // would not fit) | coarse residual | own P_k | y of the two nodes
@@ -2288,7 +2342,6 @@ __global__ __launch_bounds__(kPersTPB) void ba_pcg_persist(BaDev d, PersArgs a) 
     double* dst = a.wsave ? a.wsave + (size_t)u * (N * (N / 2)) : nullptr;
     for (int e = t; e < N * (N / 2); e += kPersTPB, nw++) { A[e] = wreg[nw]; if (dst) dst[e] = wreg[nw]; }
   }
-  const bool coarse = a.Ainv != nullptr;
   const int Nc = a.Nc, nca = 6 * (a.na + 1);
   float* ainv_l = reinterpret_cast<float*>(A + N * (N / 2));   // [12][Nc] f32: up to the whole half (Nc <= 768: intervals of 16 cameras on the 4-agent map)
   // coarse residual | own P_k | y of the two nodes: behind the staged structure in the Li region (dead once W is formed; the structure lists that move in
@@ -2305,8 +2358,6 @@ __global__ __launch_bounds__(kPersTPB) void ba_pcg_persist(BaDev d, PersArgs a) 
   static_assert((32 + 2 * kPersIdxCap + kPersColCap) % 2 == 0 &&
                 (32 + 2 * kPersIdxCap + kPersColCap) / 2 + 6 * kPersColCap + 256 + kPersNcCap + 8 * 36 + 12 + (N + kPersNcCap - kParkA) <= kCluN * kCluN,
                 "coarse vectors and the parked values do not fit behind the staged structure");
-  const int aggu = d.agg >> 3;               // units per interval (an interval is a multiple of the 8 cameras of a unit)
-  const int agg = u / aggu;                  // interval of the unit's cameras: nodes agg and agg + 1
   if (coarse) {
     {   // the 12 rows are one contiguous range of Ac^-1; all of a thread's loads in flight at once (as a rolled loop: nine dependent round trips per launch)
       const double* src = a.Ainv + (size_t)(6 * agg) * Nc;
@@ -2320,39 +2371,6 @@ __global__ __launch_bounds__(kPersTPB) void ba_pcg_persist(BaDev d, PersArgs a) 
     for (int e = t; e < 8 * 36; e += kPersTPB) pown[e] = (e / 36 < nown) ? a.Pm[36 * (size_t)o0 + e] : 0.0;
   }
   __syncthreads();
-  // Loop-invariant per-thread indices (everything derived from threadIdx) must NOT stay live across the PCG loop: the
-  // 60 VGPRs of S blocks leave ~60 for the rest, and LLVM hoists every such index out of the loop and then spills it
-  // (29-50 scratch reloads per iteration measured).  tq / lq are re-laundered copies of t / lane, opaque to the
-  // optimiser, refreshed at the top of every iteration: the indices are recomputed (a few integer ops) instead.
-  int tq = t, lq = lane;
-  // unit part of the coarse restriction P^T v for the own rows: wave 0, lane = (component c, camera k); the 8 camera
-  // terms of a component sit in 8 neighbouring lanes; every camera's term goes with weight 1 - t to the first node of the unit's interval and with t
-  // to the second.  Published component-major for the other units.
-  // The tagged values (PersArgs::tag): one descriptor over the whole block, byte offsets of w of unknown i / of part comp of a unit, by the parity of the
-  // exchange they ride on
-  auto key_of = [](unsigned long long e) { return 0x9E3779B97F4A7C15ull * e; };
-  const unsigned tag_w_pairs = 2u * 6u * (unsigned)d.Cp;
-  const __amdgpu_buffer_rsrc_t tag_rs = __builtin_amdgcn_make_buffer_rsrc(a.tag, 0, (int)(16u * (tag_w_pairs + 2u * 8u * (unsigned)kPersNcCap)), 0x00020000);
-  auto w_off = [&](unsigned long long e, int i) { return 16u * ((unsigned)(e & 1) * 6u * (unsigned)d.Cp + (unsigned)i); };
-  // coarse component j of plane pl: the 64 lanes of a gathering wave read 1 KB in one piece (unit-major parts cost every lane a cache line of its own)
-  auto c_off = [&](unsigned long long e, int pl, int j) { return 16u * (tag_w_pairs + ((unsigned)(e & 1) * 8u + (unsigned)pl) * (unsigned)kPersNcCap + (unsigned)j); };
-  auto coarse_restrict = [&](const double* vec /* LDS, own 48 entries */, unsigned long long e /* the coming exchange */) {
-    if (wv == 0) {
-      const int cc = lq >> 3, kk = lq & 7;
-      double sv = 0;
-      if (cc < 6 && kk < nown) {
-#pragma unroll
-        for (int rr = 0; rr < 6; rr++) sv += pown[kk * 36 + rr * 6 + cc] * vec[6 * kk + rr];
-      }
-      const double w1 = coarse_hat_t(8 * u + kk, d.agg);
-      double s0v = (1.0 - w1) * sv, s1v = w1 * sv;
-      s0v = lanex::add_partner<1>(s0v); s1v = lanex::add_partner<1>(s1v);
-      s0v = lanex::add_partner<2>(s0v); s1v = lanex::add_partner<2>(s1v);
-      s0v = lanex::add_partner<4>(s0v); s1v = lanex::add_partner<4>(s1v);
-      // (the units behind the last interval — padding of the grid — have no reader)
-      if (cc < 6 && kk == 0 && agg < a.na) { tag_store(tag_rs, c_off(e, u - aggu * agg, 6 * agg + cc), s0v, key_of(e)); tag_store(tag_rs, c_off(e, 4 + u - aggu * agg, 6 * (agg + 1) + cc), s1v, key_of(e)); }
-    }
-  };
   // ---- what a unit needs from the others at the start of an iteration, besides the two sums: the partner unit's 48 w and, per coarse component, the parts
   // of P^T w.  Their owners stored them BEFORE publishing their slot of exchange e, each value tagged with key(e), so they need no ordering against the slots:
   // waves 1..15 fetch them inside exchange e, while wave 0 polls (a.prefetch; otherwise at once after it), and read again only what does not validate yet.
@@ -2487,17 +2505,14 @@ __global__ __launch_bounds__(kPersTPB) void ba_pcg_persist(BaDev d, PersArgs a) 
         for (int cc = 0; cc < 6; cc++) z += pown[kk * 36 + rr * 6 + cc] * (w0 * ypart[cc] + w1 * ypart[6 + cc]);
       }
       zs[tq] = z;
-      const unsigned long long zb = (unsigned long long)__double_as_longlong(z);
-      unsigned long long* dst = a.utag + 2 * (6 * (size_t)o0 + tq);
-      __hip_atomic_store(dst, zb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(dst + 1, zb ^ ukey, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      tag_store(u_rs, 16u * (unsigned)(6 * o0 + tq), z, ukey);
       rz = rc[ob + tq] * z;
     }
     return rz;
   };
   // ---- halo exchange: u of every neighbour column into LDS.  No grid barrier orders these reads: every value carries its
-  // own check ({bits, bits ^ key}, key of the exchange that follows) and only the entries that do not validate yet are
-  // read again.  ONE buffer for u is enough: a unit publishes u for exchange e + 1 only after it has passed exchange e,
+  // own check ({bits, bits ^ key}, key of the exchange that follows; one 16-byte access per value, like w and the coarse parts)
+  // and only the entries that do not validate yet are read again.  ONE buffer for u is enough: a unit publishes u for exchange e + 1 only after it has passed exchange e,
   // and every neighbour finished reading u of exchange e before it took part in exchange e (its halo load precedes its
   // publish there).  The spin is bounded and watches the abort flag like pers_exchange's, so a missing workgroup still
   // ends the solve (pcg_flag[3], multi-kernel retry).  Returns false (grid-wide abort raised) when it gave up.
@@ -2508,14 +2523,13 @@ __global__ __launch_bounds__(kPersTPB) void ba_pcg_persist(BaDev d, PersArgs a) 
     for (int i = 0; i < kPer; i++) if (tq + i * kPersTPB >= 6 * nu) done |= 1u << i;
     bool ok = true;
     for (long spins = 0; done != (1u << kPer) - 1u; spins++) {
+      asm volatile("" ::: "memory");   // every round reads memory again
 #pragma unroll
       for (int i = 0; i < kPer; i++) {
         if (done & (1u << i)) continue;
         const int idx = tq + i * kPersTPB;
-        const unsigned long long* src = a.utag + 2 * (6 * (size_t)l_ucol[idx / 6] + idx % 6);
-        const unsigned long long b0 = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned long long b1 = __hip_atomic_load(src + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((b0 ^ b1) == ukey) { done |= 1u << i; pl[idx] = __longlong_as_double((long long)b0); }
+        const pers_u32x4 q = tag_load(u_rs, 16u * (unsigned)(6 * l_ucol[idx / 6] + idx % 6));
+        if (tag_valid(q, ukey)) { done |= 1u << i; pl[idx] = tag_value(q); }
       }
       if (done == (1u << kPer) - 1u) break;
       if (spins > kPersMaxSpins || __hip_atomic_load(a.bar + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) { ok = false; break; }
@@ -2574,22 +2588,29 @@ __global__ __launch_bounds__(kPersTPB) void ba_pcg_persist(BaDev d, PersArgs a) 
   // parts and two of tagged w by epoch parity.  The reuse: a reader has finished its reads of exchange e's data before it leaves
   // exchange e (a.prefetch) or before it publishes its slot of exchange e + 1 (otherwise); a writer touches that parity again
   // only after it has passed exchange e + 1, i.e. after every unit has published there.  A reader that is early sees the pair of
-  // exchange e - 2, which does not validate against key(e), and reads again.
-  auto slots_of = [&](unsigned long long e) { return a.slots + 3 * (size_t)nwg * (e & 1); };
+  // exchange e - 2, which does not validate against key(e), and reads again.  (The parts of P^T b ride on NO exchange: they are keyed
+  // epoch_base + 1, written at the top of the kernel and gathered once W is in place; the first exchange of the launch is
+  // epoch_base + 2, on the other parity, and that parity is written again only inside exchange epoch_base + 3, after every unit
+  // has published at epoch_base + 2, i.e. after its gather.)
+  // The restriction stays on wave 0, in front of the exchange.  Measured and dropped, same visit, us per iteration of workgroup 0
+  // (SpMV + restriction / exchange / all five phases; with it on wave 0: 1.91 / 3.64 / 9.20): on wave 15 between the exchange's two
+  // block barriers, without the block barrier in front of it: 1.51 / 5.11 / 10.41 — the parts of the unit that arrives last then
+  // trail its slot by the restriction and a store, and the fetch of every reader ends behind wave 0's poll; on wave 15 after the row
+  // products' barrier, from its own copy of w (parts stored before the slot again): 1.58 / 4.49 / 9.57.
   // exchange e with the fetch of what rides on it: inside (waves 1..15, between the exchange's two block barriers) or after
-  auto exchange = [&](unsigned long long e, double a_t, double b_t, bool force_nan, double* ta, double* tb, bool want_w) {
-    const bool ok = pers_exchange(tq, slots_of(e), nwg, u, a_t, b_t, force_nan, e, a.bar + 1, red, ta, tb, ibuf + 2, [&]() { if (a.prefetch) fetch_pre(e, want_w); });
-    if (!a.prefetch && tq >= kWave) fetch_pre(e, want_w);   // (a give-up here is seen at the next block barrier that reads ibuf[2]: halo_load's)
+  auto exchange = [&](unsigned long long e, double a_t, double b_t, bool force_nan, double* ta, double* tb) {
+    const bool ok = pers_exchange(tq, slot_rs, 32u * (unsigned)nwg * (unsigned)(e & 1), nwg, u, a_t, b_t, force_nan, e, a.bar + 1, red, ta, tb, ibuf + 2, [&]() { if (a.prefetch) fetch_pre(e, true); });
+    if (!a.prefetch && tq >= kWave) fetch_pre(e, true);   // (a give-up here is seen at the next block barrier that reads ibuf[2]: halo_load's)
     return ok;
   };
   int fail = 0, k = 0;
   double gam = 0, del = 0;
   bool alive = true;
-  if (coarse) {   // coarse residual of r0 = b: one extra exchange before the first preconditioner application
-    coarse_restrict(rc + ob, epoch + 1);
-    double dummy = 0, dummy2 = 0;
-    alive = exchange(epoch + 1, 0.0, 0.0, false, &dummy, &dummy2, false);
+  if (coarse) {   // coarse residual of r0 = b: the parts were published before the factorisation; a gather alone, no grid exchange (the epoch still advances, so the parity planes alternate)
+    if (t >= kWave) fetch_pre(epoch + 1, false);
     ++epoch;
+    __syncthreads();
+    alive = ibuf[2] == 0;
     if (t >= kWave + N && t - (kWave + N) < nca) rco[t - (kWave + N)] += *park(t - kWave);
     __syncthreads();
   }
@@ -2598,8 +2619,8 @@ __global__ __launch_bounds__(kPersTPB) void ba_pcg_persist(BaDev d, PersArgs a) 
     alive = halo_load(key_of(epoch + 1));
     double wu_t = 0;
     spmv_w(epoch + 1, &wu_t);
-    if (coarse) { __syncthreads(); coarse_restrict(wl, epoch + 1); }
-    const bool alive2 = exchange(epoch + 1, ru_t, wu_t, has && ibuf[1], &gam, &del, true);   // bad pivot -> NaN -> grid-wide failure
+    if (coarse) { __syncthreads(); coarse_restrict(pown, wl, epoch + 1); }
+    const bool alive2 = exchange(epoch + 1, ru_t, wu_t, has && ibuf[1], &gam, &del);   // bad pivot -> NaN -> grid-wide failure
     ++epoch;
     alive = alive && alive2;
   }
@@ -2634,11 +2655,11 @@ __global__ __launch_bounds__(kPersTPB) void ba_pcg_persist(BaDev d, PersArgs a) 
     if (!alive) { fail = 1; break; }
     double wu_t = 0;
     spmv_w(epoch + 1, &wu_t);
-    if (coarse) { __syncthreads(); coarse_restrict(wl, epoch + 1); }
+    if (coarse) { __syncthreads(); coarse_restrict(pown, wl, epoch + 1); }
     PERS_TICK(3)
     gam_prev = gam; alpha_prev = alpha;
     if (a.dbg && t == 0) tw0 = wall_clock64();
-    alive = exchange(epoch + 1, ru_t, wu_t, false, &gam, &del, true);
+    alive = exchange(epoch + 1, ru_t, wu_t, false, &gam, &del);
     ++epoch;
     if (a.dbg && t == 0) a.dbg[32 + 2 * u] += wall_clock64() - tw0;   // per unit: time inside the exchange (its own wait for the slowest unit + the exchange latency)
     PERS_TICK(4)

@@ -868,7 +868,7 @@ extern "C" int ccm_ba_create(ccm_ctx* ctx, const ccm_ba_problem* P, int rank, in
     d.mk_cpart = nullptr; d.mk_cry[0] = d.mk_cry[1] = nullptr; d.mk_P = nullptr; d.mk_Ainv = nullptr; d.mk_Ainv32 = nullptr; d.mk_on = 0; d.mk_Nc = 0; d.mk_na = 0;
     if (pers_try && !hs.pers_bad) {
       BB_RC(keep_get(ba, 4 + 2 * 16 + 4 * 512, &ba->d_pers_bar, true));   // abort flag + debug clocks (workgroup 0's phases; then per workgroup the time spent in the exchange and in the halo wait)
-      BB_RC(keep_get(ba, 6 * (size_t)pers_grid_want, &ba->d_pers_part, true));   // [2][3][grid] slot words
+      BB_RC(keep_get(ba, 8 * (size_t)pers_grid_want, &ba->d_pers_part, true));   // [2][grid][4] slot words: 32-byte records
       BB_RC(keep_get(ba, 12 * (size_t)Cp, &ba->d_pers_u, true));   // [6 Cp][2] tagged u
       BB_RC(keep_get(ba, 2 * (2 * 6 * (size_t)Cp + 2 * 8 * (size_t)kPersNcCap), &ba->d_pers_tag, true));   // tagged w [2][6 Cp][2] | tagged coarse parts [2][8][kPersNcCap][2]
       { const char* pf = getenv("CCM_BA_PERS_PREFETCH"); ba->pers_prefetch = !(pf && !strcmp(pf, "0")); }
