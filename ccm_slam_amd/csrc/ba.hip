@@ -319,7 +319,8 @@ __global__ __launch_bounds__(kTPB) void ba_linearize_cams(BaDev d, int cur) {
 
 // max |diag| of Hpp (after it has been summed over ranks) and of the own Hll  -> scal[4]
 // stage 1: grid-stride partial maxima (one per workgroup) ; stage 2 (final != 0): max of the partials
-__global__ __launch_bounds__(kTPB) void ba_maxdiag(BaDev d, const double* hpp_full, double* partial, int n_partial, int final) {
+// h_out != nullptr (final stage, one rank): the result also goes to word 4 of the handle's pinned block, followed by `ticket`, as in ba_reduce_scalars
+__global__ __launch_bounds__(kTPB) void ba_maxdiag(BaDev d, const double* hpp_full, double* partial, int n_partial, int final, double* h_out, unsigned long long ticket) {
   __shared__ double lds[kTPB];
   double m = 0;
   if (!final) {
@@ -338,7 +339,13 @@ __global__ __launch_bounds__(kTPB) void ba_maxdiag(BaDev d, const double* hpp_fu
     if (threadIdx.x < s) lds[threadIdx.x] = fmax(lds[threadIdx.x], lds[threadIdx.x + s]);
     __syncthreads();
   }
-  if (threadIdx.x == 0) { if (final) d.scal[4] = lds[0]; else partial[blockIdx.x] = lds[0]; }
+  if (threadIdx.x == 0) {
+    if (!final) partial[blockIdx.x] = lds[0];
+    else {
+      d.scal[4] = lds[0];
+      if (h_out) { h_out[4] = lds[0]; __hip_atomic_store(reinterpret_cast<unsigned long long*>(h_out) + 8, ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); }
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1404,6 +1411,10 @@ struct PersArgs {
   // launch takes them from here instead of assembling and factoring the cluster block (a stale W — another lambda, an earlier linearisation — is still a
   // symmetric positive definite block-Jacobi preconditioner: PCG stays exact, only the iteration count moves; the host decides, lm_trial)
   double* wsave; int w_load;
+  // the trial's camera update at the end of the launch (cam_upd != 0; pers_update_cams): the state the step is applied to, and whether this rank adds the lambda
+  // term of the gain denominator — ba_update_cams' arguments
+  int cam_upd, cur, add_lambda_term;
+  const float* Ainv32;   // Ainv rounded to f32 once per coarse build (nullptr: the units round their 12 rows themselves)
 };
 
 // a value every lane already agrees on, moved to scalar registers (frees 2 VGPRs per double in the PCG loop)
@@ -2237,6 +2248,28 @@ __global__ __launch_bounds__(kCRTPB) void ba_solve_cholreg(BaDev d, double lambd
   if (t == 0) { d.pcg_flag[0] = 1; d.pcg_flag[1] = 1; d.pcg_flag[2] = ibuf[1]; d.pcg_flag[3] = 0; }
 }
 
+// The camera update of the trial at the end of a persistent launch (as in ba_solve_cholreg / ba_solve_dense2): ba_update_cams' arithmetic for the unit's own <= 8
+// cameras, straight from x in LDS — one launch less per LM trial.  The term of the gain denominator goes to cam_sc PER CAMERA: ba_reduce_scalars re-forms
+// ba_update_cams' block sums from the terms, so `scale` keeps its bits.  Every datum read here is the unit's own: no wait on another workgroup.  Not inlined: the
+// pose arithmetic must not share a register allocation with the PCG loop.
+__device__ __noinline__ void pers_update_cams(const double* xs, int o0, int nown, const int* slot_cam, const double* cam_in, double* cam_out, const double* bp,
+                                              double* cam_sc, double lambda, int add_lambda_term) {
+  const int t = threadIdx.x;
+  if (t >= nown) return;
+  const int i = o0 + t;
+  const int c = slot_cam[i];
+  double u[6];
+#pragma unroll
+  for (int q = 0; q < 6; q++) u[q] = xs[6 * t + q];
+  const BaPose T = ba_load_pose(cam_in + 7 * (size_t)c);
+  const BaPose Tn = ba_oplus(u, T);
+  ba_store_pose(cam_out + 7 * (size_t)c, Tn);
+  double sc = 0;
+#pragma unroll
+  for (int q = 0; q < 6; q++) sc += u[q] * ((add_lambda_term ? lambda * u[q] : 0.0) + bp[6 * (size_t)i + q]);
+  cam_sc[i] = sc;
+}
+
 __global__ __launch_bounds__(kPersTPB) void ba_pcg_persist(BaDev d, PersArgs a) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   constexpr int N = kCluN;
@@ -2359,7 +2392,14 @@ __global__ __launch_bounds__(kPersTPB) void ba_pcg_persist(BaDev d, PersArgs a) 
                 (32 + 2 * kPersIdxCap + kPersColCap) / 2 + 6 * kPersColCap + 256 + kPersNcCap + 8 * 36 + 12 + (N + kPersNcCap - kParkA) <= kCluN * kCluN,
                 "coarse vectors and the parked values do not fit behind the staged structure");
   if (coarse) {
-    {   // the 12 rows are one contiguous range of Ac^-1; all of a thread's loads in flight at once (as a rolled loop: nine dependent round trips per launch)
+    if (a.Ainv32) {   // rounded once per coarse build (coarse_build): the same floats, half the bytes and no conversion in every unit of every launch
+      const float* src = a.Ainv32 + (size_t)(6 * agg) * Nc;
+      float tmpa[9];
+#pragma unroll
+      for (int q = 0; q < 9; q++) { const int e = t + q * kPersTPB; tmpa[q] = (has && e < 12 * Nc) ? src[e] : 0.0f; }
+#pragma unroll
+      for (int q = 0; q < 9; q++) { const int e = t + q * kPersTPB; if (e < 12 * Nc) ainv_l[e] = tmpa[q]; }
+    } else {   // the 12 rows are one contiguous range of Ac^-1; all of a thread's loads in flight at once (as a rolled loop: nine dependent round trips per launch)
       const double* src = a.Ainv + (size_t)(6 * agg) * Nc;
       double tmpa[9];
 #pragma unroll
@@ -2666,7 +2706,10 @@ __global__ __launch_bounds__(kPersTPB) void ba_pcg_persist(BaDev d, PersArgs a) 
     if (!alive) { fail = 1; break; }
   }
 #undef PERS_TICK
-  if (timing) { for (int q = 0; q < 12; q++) a.dbg[q] += tacc[q]; a.dbg[12] += k; a.dbg[13] += 1; }
+  if (timing) tacc[12] = wall_clock64();
+  // (xs: last written in front of a block barrier of the loop, or before the loop.  After a give-up the cameras written here are never used: the trial is repeated.)
+  if (a.cam_upd && wv == 0) pers_update_cams(xs, o0, nown, d.slot_cam, a.cur ? d.cam[1] : d.cam[0], a.cur ? d.cam[0] : d.cam[1], d.bp, d.cam_sc, lambda, a.add_lambda_term);
+  if (timing) { tacc[5] += wall_clock64() - tacc[12]; for (int q = 0; q < 12; q++) a.dbg[q] += tacc[q]; a.dbg[12] += k; a.dbg[13] += 1; }
   if (t < mo) d.x[6 * (size_t)o0 + t] = xs[t];
   if (blockIdx.x == 0 && t == 0) {
     d.pcg_flag[0] = 1; d.pcg_flag[1] = k; d.pcg_flag[2] = fail;
@@ -2734,7 +2777,7 @@ static PersArgs pers_args(ccm_ba* ba, double lambda, double rel_tol, int max_it)
   pa.coff = ba->d_pers_coff; pa.cij = ba->d_pers_cij; pa.cblk = ba->d_pers_cblk;
   return pa;
 }
-static void pers_args_coarse(const ccm_ba* ba, PersArgs* pa) { pa->Ainv = ba->d_cAinv; pa->Pm = ba->d_cP; pa->na = ba->coarse_na; pa->Nc = ba->coarse_Nc; }
+static void pers_args_coarse(const ccm_ba* ba, PersArgs* pa) { pa->Ainv = ba->d_cAinv; pa->Ainv32 = ba->d_cAinv32; pa->Pm = ba->d_cP; pa->na = ba->coarse_na; pa->Nc = ba->coarse_Nc; }
 
 // ---- very small reduced systems (<= 16 free cameras: initial maps, tiny local windows): the whole PCG in ONE workgroup ----
 // Vectors and the 6x6 block-Jacobi preconditioner live in LDS and an iteration is a few block barriers (~2 us).  Typical
@@ -3008,11 +3051,49 @@ __global__ __launch_bounds__(kTPB) void ba_backsub_chi2_e(BaDev d, int cur, doub
 // decision (a rank leaving the LM loop alone would leave its peers waiting in the next collective)
 // h_out != nullptr (one rank): the eight read-back words also go straight to the handle's pinned host block, followed by `ticket` (system-scope release): the host polls the
 // ticket instead of queueing a 64-byte copy and waiting for the stream (read_scalars_polled)
-__global__ __launch_bounds__(kTPB) void ba_reduce_scalars(BaDev d, int stop_local, int abort_local, int pers_trial, double* h_out, unsigned long long ticket) {
+// cam_mode: where the pose part of `scale` comes from.  kRedCamNone: there is none (chi2 of the current state).  kRedCamPart: ba_update_cams' (or an exact solver's) block
+// sums in part_cam.  kRedCamTerms: the per-camera terms the persistent launch left in cam_sc (pers_update_cams): the block sums ba_update_cams would have formed of them
+// are re-formed here, operation for operation — for block b thread t holds term 256 b + t (0 beyond Cp), the wave butterfly, then the four wave sums added in wave
+// order starting from 0, as block_sum does — all blocks at once (n_wg_cam <= kRedCamBlocks), and thread b adds block b's sum where it used to add part_cam[b].
+// pers_flags (nullable): the abort flags of the persistent PCG kernel, cleared for the next trial once this trial's give-up flag has been read (saves a 5 us memset launch)
+constexpr int kRedCamNone = 0, kRedCamPart = 1, kRedCamTerms = 2;
+constexpr int kRedBatch = 8;        // pairs of part_pt a thread requests before the first addition
+__global__ __launch_bounds__(kTPB) void ba_reduce_scalars(BaDev d, int stop_local, int abort_local, int pers_trial, int cam_mode, unsigned* pers_flags, double* h_out,
+                                                          unsigned long long ticket) {
   __shared__ double lds[kTPB / kWave];
+  __shared__ double cam_ws[kRedCamBlocks][kTPB / kWave];
   double chi = 0, sc = 0;
-  for (int i = threadIdx.x; i < d.n_part; i += kTPB) { chi += d.part_pt[2 * i]; sc += d.part_pt[2 * i + 1]; }
-  for (int i = threadIdx.x; i < d.n_wg_cam; i += kTPB) sc += d.part_cam[i];
+  double cs[kRedCamBlocks];
+  if (cam_mode == kRedCamTerms) {   // (requested in front of the part_pt pairs: one round trip for both)
+#pragma unroll
+    for (int q = 0; q < kRedCamBlocks; q++) { const int i = q * kTPB + (int)threadIdx.x; cs[q] = (q < d.n_wg_cam && i < d.Cp) ? d.cam_sc[i] : 0.0; }
+  }
+  // the (robust chi2, scale) pairs of the landmark side, thread-strided, added in index order; as a rolled loop every pair was a dependent round trip (~15 per thread on the
+  // 4-agent map): kRedBatch pairs in flight, the additions in the order they always had
+  const double2* pp = reinterpret_cast<const double2*>(d.part_pt);
+  for (int i0 = threadIdx.x; i0 < d.n_part; i0 += kRedBatch * kTPB) {
+    double2 v[kRedBatch];
+#pragma unroll
+    for (int q = 0; q < kRedBatch; q++) { const int i = i0 + q * kTPB; v[q] = (i < d.n_part) ? pp[i] : double2{0.0, 0.0}; }
+#pragma unroll
+    for (int q = 0; q < kRedBatch; q++) if (i0 + q * kTPB < d.n_part) { chi += v[q].x; sc += v[q].y; }
+  }
+  if (cam_mode == kRedCamTerms) {
+#pragma unroll
+    for (int q = 0; q < kRedCamBlocks; q++) if (q < d.n_wg_cam) cs[q] = wave_sum(cs[q]);   // (a uniform branch: every lane of the wave is active inside)
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+#pragma unroll
+      for (int q = 0; q < kRedCamBlocks; q++) if (q < d.n_wg_cam) cam_ws[q][threadIdx.x / kWave] = cs[q];
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < d.n_wg_cam && threadIdx.x < kRedCamBlocks) {
+      double s = 0;
+      for (int i = 0; i < kTPB / kWave; i++) s += cam_ws[threadIdx.x][i];
+      sc += s;
+    }
+  } else if (cam_mode == kRedCamPart) {
+    for (int i = threadIdx.x; i < d.n_wg_cam; i += kTPB) sc += d.part_cam[i];
+  }
   const double a = block_sum(chi, lds);
   const double b = block_sum(sc, lds);
   if (threadIdx.x == 0) {
@@ -3022,6 +3103,7 @@ __global__ __launch_bounds__(kTPB) void ba_reduce_scalars(BaDev d, int stop_loca
     // can tell "somebody gave up" (> 0: repeat the trial on the multi-kernel solver, then cool down) from "somebody cannot launch it at all" (>= 4096: for good)
     const double s3 = abort_local ? 4096.0 : (pers_trial && d.pcg_flag[3]) ? 1.0 : 0.0;
     d.scal[3] = s3;
+    if (pers_flags) { pers_flags[0] = 0u; pers_flags[1] = 0u; pers_flags[2] = 0u; pers_flags[3] = 0u; }
     if (h_out) {
       h_out[0] = a; h_out[1] = b; h_out[2] = stop_local ? 1.0 : 0.0; h_out[3] = s3;
       h_out[4] = d.scal[4]; h_out[5] = d.scal[5]; h_out[6] = d.scal[6]; h_out[7] = d.scal[7];   // [6..7]: the four PCG flags
@@ -3257,10 +3339,10 @@ int eval_chi2(ccm_ba* ba, double* chi) {
     if (d.chunk_off) hipLaunchKernelGGL(ba_backsub_chi2_e, dim3(d.n_chunk), dim3(kTPB), 0, ctx->stream, d, ba->cur, 0.0, 1);
     else hipLaunchKernelGGL(ba_backsub_chi2, dim3(d.n_wg_pt), dim3(kTPB), 0, ctx->stream, d, ba->cur, 0.0, 1);
   }
-  hipMemsetAsync(d.part_cam, 0, sizeof(double) * d.n_wg_cam, ctx->stream);
   const bool poll = ba->nranks == 1 && poll_enabled();
   const unsigned long long ticket = ++ba->rb_ticket;
-  hipLaunchKernelGGL(ba_reduce_scalars, dim3(1), dim3(kTPB), 0, ctx->stream, d, ba->stop_local(), 0, 0, poll ? ba->h_rb : (double*)nullptr, ticket);
+  hipLaunchKernelGGL(ba_reduce_scalars, dim3(1), dim3(kTPB), 0, ctx->stream, d, ba->stop_local(), 0, 0, kRedCamNone /* no step: no pose part */,
+                     (unsigned*)nullptr, poll ? ba->h_rb : (double*)nullptr, ticket);
   RC(ba_allreduce_sum(ba, d.scal, 4));
   double s[6];
   if (poll) { RC(read_scalars_polled(ba, s, nullptr, ticket)); } else { RC(read_scalars(ba, s)); }
@@ -3301,11 +3383,16 @@ int max_diag(ccm_ba* ba, double* out) {
     hpp = ba->d_hpp_full;
   }
   const int nb = std::max(1, std::min(d.n_wg_pt, 512));   // partials live in part_pt (>= 2*n_wg_pt doubles)
-  hipLaunchKernelGGL(ba_maxdiag, dim3(nb), dim3(kTPB), 0, ctx->stream, d, hpp, d.part_pt, nb, 0);
-  hipLaunchKernelGGL(ba_maxdiag, dim3(1), dim3(kTPB), 0, ctx->stream, d, hpp, d.part_pt, nb, 1);
+  // one rank: the result comes through the pinned block and its ticket, like the trial scalars (read_scalars_polled: no copy command, no stream wait; the copy
+  // remains its fallback after two seconds)
+  const bool poll = ba->nranks == 1 && poll_enabled();
+  const unsigned long long ticket = poll ? ++ba->rb_ticket : 0ull;
+  hipLaunchKernelGGL(ba_maxdiag, dim3(nb), dim3(kTPB), 0, ctx->stream, d, hpp, d.part_pt, nb, 0, (double*)nullptr, 0ull);
+  hipLaunchKernelGGL(ba_maxdiag, dim3(1), dim3(kTPB), 0, ctx->stream, d, hpp, d.part_pt, nb, 1, poll ? ba->h_rb : (double*)nullptr, ticket);
+  CCM_HIP_CHECK(ctx, hipGetLastError());
   RC(ba_allreduce_max(ba, d.scal + 4, 1));
   double s[6];
-  RC(read_scalars(ba, s));
+  if (poll) { RC(read_scalars_polled(ba, s, nullptr, ticket)); } else { RC(read_scalars(ba, s)); }
   *out = s[4];
   return CCM_OK;
 }
@@ -3328,7 +3415,7 @@ int coarse_build(ccm_ba* ba, double lambda) {
                      ba->coarse_ncb, na, nn, ba->d_cA, Nc);
   CCM_HIP_CHECK(ctx, hipGetLastError());
   RC(ccm_dense_chol_inverse_dev(ctx, ba->d_cA, Nc, ba->d_cLinv, ba->d_cX, ba->d_cAinv, ba->d_cinfo));
-  if (ba->d_cAinv32) {   // multi-kernel PCG: the rows the clusters re-read every CG iteration, as f32
+  if (ba->d_cAinv32) {   // as f32: the rows the clusters of the multi-kernel PCG re-read every CG iteration / every unit of a persistent launch copies into its LDS
     const size_t n = (size_t)Nc * Nc;
     hipLaunchKernelGGL(ba_f64_to_f32, dim3((unsigned)ccm_div_up((int64_t)n, kTPB)), dim3(kTPB), 0, ctx->stream, (const double*)ba->d_cAinv, ba->d_cAinv32, n);
     CCM_HIP_CHECK(ctx, hipGetLastError());
@@ -3427,6 +3514,8 @@ int lm_trial(ccm_ba* ba, double lambda, const ccm_ba_options& opt, double* temp_
       PersArgs pa = pers_args(ba, lambda, tol, max_it);
       pa.test_abort = getenv("CCM_BA_TEST_ABORT") ? 1 : 0;
       pa.dbg = ccm_dbg("pers") ? (long long*)(ba->d_pers_bar + 4) : nullptr;
+      // the launch also applies the step to the cameras (pers_update_cams; CCM_BA_PERS_CAMUPD=0: the separate ba_update_cams launch)
+      pa.cam_upd = ba->pers_camupd ? 1 : 0; pa.cur = cur; pa.add_lambda_term = ba->rank == 0 ? 1 : 0;
       // Cluster inverse across trials.  Offline (1000-keyframe 4-agent reduced systems, numpy PCG to 1e-8): W built at a lambda 10 / 100 / 1000 times away
       // costs 0-2 / 2-3 / 5 more CG iterations of 24-46; W of the INITIAL linearisation used three LM iterations later costs 13-19 more (the robust weights move),
       // later linearisations hardly differ (the map itself disagreed, see the measurements below).  Policy: reuse inside an LM iteration (rejected trials: only lambda moved) within a lambda window, and across
@@ -3488,7 +3577,7 @@ int lm_trial(ccm_ba* ba, double lambda, const ccm_ba_options& opt, double* temp_
         if (le == hipSuccess) persist_ok = true;
         else { (void)hipGetLastError(); ba->pers_grid = 0; ba->pers_grid_built = 0; ba->w_valid = false; pers_launch_failed = true; }   // the launch itself was refused: multi-kernel path from now on
       }
-      if (persist_ok) small_path = pers_trial = true;
+      if (persist_ok) { small_path = pers_trial = true; cams_updated = pa.cam_upd != 0; }
       if (trial_dbg) {
         hipStreamSynchronize(ctx->stream);
         int fl[4] = {0, 0, 0, 0};
@@ -3586,7 +3675,7 @@ int lm_trial(ccm_ba* ba, double lambda, const ccm_ba_options& opt, double* temp_
   if (d.Cp && !cams_updated) {
     ccm_prof_scope ps(ctx, CCM_K_BA_UPDATE);
     hipLaunchKernelGGL(ba_update_cams, dim3(d.n_wg_cam), dim3(kTPB), 0, ctx->stream, d, cur, lambda, ba->rank == 0 ? 1 : 0, ba->d_pers_bar /* nullptr when the handle has no persistent solver; cleared also while it is cooling down after an abort */);
-  } else if (!d.Cp) hipMemsetAsync(d.part_cam, 0, sizeof(double) * d.n_wg_cam, ctx->stream);
+  }   // (no free camera: ba_reduce_scalars is told that there is no pose part)
   {
     ccm_prof_scope ps(ctx, CCM_K_BA_BACKSUB);
     if (d.chunk_off) hipLaunchKernelGGL(ba_backsub_chi2_e, dim3(d.n_chunk), dim3(kTPB), 0, ctx->stream, d, cur, lambda, 0);
@@ -3599,7 +3688,8 @@ int lm_trial(ccm_ba* ba, double lambda, const ccm_ba_options& opt, double* temp_
   {
     ccm_prof_scope ps(ctx, CCM_K_BA_REDUCE);
     hipLaunchKernelGGL(ba_reduce_scalars, dim3(1), dim3(kTPB), 0, ctx->stream, d, ba->stop_local(), (pers_launch_failed && ba->nranks > 1) ? 1 : 0,
-                       pers_trial ? 1 : 0, poll ? ba->h_rb : (double*)nullptr, ticket);
+                       pers_trial ? 1 : 0, !d.Cp ? kRedCamNone : (pers_trial && cams_updated) ? kRedCamTerms : kRedCamPart,
+                       ba->d_pers_bar /* nullptr when the handle has no persistent solver; cleared also while it is cooling down after an abort */, poll ? ba->h_rb : (double*)nullptr, ticket);
   }
   RC(ba_allreduce_sum(ba, d.scal, 4));
   double s[6];
@@ -3766,9 +3856,9 @@ static void pers_dbg_dump(ccm_ba* ba) {
   }
   const double it = (double)std::max<long long>(h[12], 1), nl = (double)std::max<long long>(h[13], 1);
   fprintf(stderr, "[ccm_ba] persistent PCG, workgroup 0: %lld iterations in %lld launches; us/iteration: update %.2f W %.2f halo %.2f "
-          "spmv+dot %.2f exchange %.2f | us/launch: assemble %.1f cholesky %.1f inverse %.1f W %.1f start %.1f\n",
+          "spmv+dot %.2f exchange %.2f | us/launch: assemble %.1f cholesky %.1f inverse %.1f W %.1f start %.1f camera update %.2f\n",
           h[12], h[13], h[0] * 0.01 / it, h[1] * 0.01 / it, h[2] * 0.01 / it, h[3] * 0.01 / it, h[4] * 0.01 / it,
-          h[7] * 0.01 / nl, h[8] * 0.01 / nl, h[9] * 0.01 / nl, h[10] * 0.01 / nl, h[11] * 0.01 / nl);
+          h[7] * 0.01 / nl, h[8] * 0.01 / nl, h[9] * 0.01 / nl, h[10] * 0.01 / nl, h[11] * 0.01 / nl, h[5] * 0.01 / nl);
 }
 
 extern "C" int ccm_ba_run(ccm_ba* ba, const ccm_ba_options* opt_in, const volatile unsigned char* stop_flag, ccm_ba_stats* stats) {

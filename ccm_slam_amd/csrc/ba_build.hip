@@ -872,9 +872,15 @@ extern "C" int ccm_ba_create(ccm_ctx* ctx, const ccm_ba_problem* P, int rank, in
       BB_RC(keep_get(ba, 12 * (size_t)Cp, &ba->d_pers_u, true));   // [6 Cp][2] tagged u
       BB_RC(keep_get(ba, 2 * (2 * 6 * (size_t)Cp + 2 * 8 * (size_t)kPersNcCap), &ba->d_pers_tag, true));   // tagged w [2][6 Cp][2] | tagged coarse parts [2][8][kPersNcCap][2]
       { const char* pf = getenv("CCM_BA_PERS_PREFETCH"); ba->pers_prefetch = !(pf && !strcmp(pf, "0")); }
+      {   // (ba_reduce_scalars re-forms the block sums of the per-camera terms for up to kRedCamBlocks blocks at once)
+        const char* cu = getenv("CCM_BA_PERS_CAMUPD");
+        ba->pers_camupd = !(cu && !strcmp(cu, "0")) && d.n_wg_cam <= kRedCamBlocks;
+        double* p_sc = nullptr;
+        BB_RC(keep_get(ba, (size_t)Cp, &p_sc, true)); d.cam_sc = p_sc;
+      }
       ba->pers_grid = pers_grid_want; ba->pers_grid_built = pers_grid_want;
       BB_RC(keep_get(ba, (size_t)pers_grid_want * (kCluN * (kCluN / 2)), &ba->d_pers_wsave, false));   // the units' halves of the cluster inverse, carried from trial to trial (written before read)
-      if (coarse_pers) BB_RC(coarse_buffers());
+      if (coarse_pers) { BB_RC(coarse_buffers()); BB_RC(keep_get(ba, (size_t)Nc * Nc, &ba->d_cAinv32, false)); }   // (filled by every coarse_build before a launch reads it)
     } else if (pers_try) { ba->d_pers_uoff = nullptr; ba->d_pers_ucol = nullptr; ba->d_pers_loc = nullptr; }
     if (Cp > kSmallMaxCp && Cp <= kDense2MaxCp && ba->d_pers_coff)
       BB_RC(keep_get(ba, (size_t)kCluN * kCluN + 16, &ba->d_dense_T, true));   // + phase clocks (CCM_BA_DENSE2_DBG)

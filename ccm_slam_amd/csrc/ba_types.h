@@ -25,6 +25,7 @@ constexpr int kPersColCap = 640;     // distinct neighbour columns of one persis
 constexpr int kPersNcCap = 768;      // coarse unknowns of the persistent solver (12 Nc floats in half of its 96x96 LDS block)
 constexpr int kSmallMaxCp = 16;      // one cluster: the single-workgroup kernel; above, the persistent kernel with its 16-camera cluster preconditioner
 constexpr int kDense2MaxCp = 2 * kClu;
+constexpr int kRedCamBlocks = 16;     // blocks of kTPB cameras whose sums ba_reduce_scalars re-forms at once from per-camera terms (4096 free cameras: the most a persistent solve has)
 constexpr int kCholRegMaxCp = 50;    // (round 6) exact register-resident Cholesky in one workgroup: 19 x 19 tiles of 16 x 16 (n = 6 Cp <= 304), ba_solve_cholreg
 
 struct BaDev {
@@ -102,6 +103,8 @@ struct BaDev {
   uint8_t* edge_depth;       // [Eloc]
   double* part_pt;           // [n_wg_pt*2]  (robust chi2, scale) partials
   double* part_cam;          // [n_wg_cam]   scale partials (pose part)
+  double* cam_sc;            // [Cp] the pose part of scale PER CAMERA, left by a persistent launch that applied the step itself (pers_update_cams); ba_reduce_scalars
+                             // forms ba_update_cams' block sums of them; nullptr: the handle has no persistent solver
   double* scal;              // [0] chi2 [1] scale [2] stop requested on any rank [3] persistent PCG gave up on any rank (0..3 are summed over
                              // ranks in ONE all-reduce per trial) [4] maxdiag [5] - [6..7] = pcg_flag (4 ints)
   int n_wg_pt, n_wg_cam;
@@ -166,7 +169,8 @@ struct ccm_ba {
   // descriptor in the kernel): [2][6 Cp][2] | [2][8][kPersNcCap][2]
   unsigned long long* d_pers_tag = nullptr;
   bool pers_prefetch = true;        // CCM_BA_PERS_PREFETCH (read at create): the partner's w and the coarse parts are fetched inside the exchange (0: after it)
-  float* d_cAinv32 = nullptr;       // [Nc][Nc] multi-kernel path
+  bool pers_camupd = true;          // CCM_BA_PERS_CAMUPD (read at create): the persistent launch applies the step to the cameras itself (0: a ba_update_cams launch after it)
+  float* d_cAinv32 = nullptr;       // [Nc][Nc] Ac^-1 rounded to f32 by coarse_build: the multi-kernel path's coarse apply and the 12 rows a persistent unit keeps in LDS
   bool w_valid = false, w_loaded = false, w_stale_bad = false; double w_lambda_built = 0; int w_fresh_iters = 0, lin_id = 0, w_lin_id = -1;
   bool coarse_valid = false, coarse_fresh = false, coarse_stale_bad = false, coarse_reuse = true;
   double coarse_lambda_built = 0; int coarse_fresh_iters = 0;

@@ -35,6 +35,8 @@ extern "C" int ccm_ba_debug_array(ccm_ba* ba, const char* name, void* out, size_
   ARR("chunk_off", d.chunk_off, d.chunk_off ? d.n_chunk + 1 : 0, int)
   ARR("pers_uoff", ba->d_pers_uoff, ba->d_pers_uoff ? 2 * n_cl + 1 : 0, int) ARR("pers_loc", ba->d_pers_loc, ba->d_pers_loc ? ent : 0, int)
   ARR("pers_coff", ba->d_pers_coff, ba->d_pers_coff ? n_cl + 1 : 0, int)
+  // the last trial's PCG flags ([1] iterations, [2] numeric failure, [3] the persistent launch gave up) and the persistent kernel's four abort words (clear between trials)
+  ARR("pcg_flag", d.pcg_flag, 4, int) ARR("pers_flags", ba->d_pers_bar, ba->d_pers_bar ? 4 : 0, unsigned)
   ARR("row_unit_off", d.row_unit_off, d.row_unit_off ? Cp + 1 : 0, int) ARR("blk_unit0", d.blk_unit0, d.blk_unit0 ? nOff + 1 : 0, int)
 #undef ARR
   if (n == "cam_edge" || n == "cam_pt") {
