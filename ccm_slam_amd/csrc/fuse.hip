@@ -5,6 +5,9 @@
 //     of ORBmatcher::Fuse(pKF, vpMapPoints, th) (ORBmatcher.cpp:883-965) up to the decision, without the skips and the map mutations.
 //   ccm_fuse_sim3_eval_resident, ccm_fuse_pose_eval_resident: the same two calls on keyframes of a keyframe store (kfstore.hip), whose static
 //     data is on the device already: the same pair body with kResident, which takes the keyframe's arrays from its slot of the store.
+//   ccm_sim3_project_eval_resident: ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (ORBmatcher.cpp:308-446) on the INITIAL vpMatched: the Sim3
+//     form's pair with a skip mask per feature of the keyframe (kMask).  ccm_sim3_pair_eval_resident: both directions of ORBmatcher::SearchBySim3 (:1124-1348) as
+//     jobs of the pose form's layout: ssm_gate where Fuse has fsm_gate (kPair), no chi-square gate, TH_HIGH.  Both on keyframes of a store only.
 // The lines of a pair are fuse_math.h; the two forms differ in the chi-square gate of the candidate (kChi2) and in how a workgroup finds its work.
 //
 // Layout.  fuse_sim3_kernel: the grid is (tiles of 256 points) x K keyframes, folded into one dimension.  fuse_pose_kernel: the work is a list
@@ -29,7 +32,7 @@ namespace {
 static_assert(FPM_TILE == 256, "both kernels run 256 lanes, one per pair");
 
 // everything either kernel reads.  P, tiles: the Sim3 form's grid; job, tile, inv_sigma2: the pose form's; slot, stride: the resident forms', whose rec, kxy, cell_off,
-// cell_idx, koct and kdesc are the store's arrays
+// cell_idx, koct and kdesc are the store's arrays; skip, skip_off: the masks of the projection search (keyframe k's bytes start at skip + skip_off[k])
 struct FuseArgs {
   int P, tiles, nlevels;
   float th, logsf;
@@ -42,6 +45,8 @@ struct FuseArgs {
   float* uv;   // nullptr: not asked for
   const int32_t* slot;
   int stride;
+  const uint8_t* skip;
+  const int32_t* skip_off;
 };
 
 // the minimum of a 32-bit key over the wave; a u32 is exact in a double, so lane_xor.h's f64 exchange carries it
@@ -56,12 +61,15 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t key) {
 // A dead lane (!live) reads nothing through i and writes nothing, but stays for the wave-wide part, which needs all 64.
 // kResident: the keyframe's static arrays are a slot of the keyframe store (kfstore.hip): slot[k] and slot[k] * stride take the place of k and feat_off[k].  Both are
 // workgroup-uniform like k, so the addresses still come from the scalar unit.
-template <bool kChi2, bool kResident>
-__device__ __forceinline__ void fuse_pair(const FuseArgs& a, int k, int i, bool live, uint32_t out, int counter) {
+// pose (workgroup-uniform): the keyframe's 15 floats, or with kPair the job's SSM_JOB_FLOATS, which ssm_gate reads where the other forms run fsm_gate; the pair form
+// reads no normals and accepts up to TH_HIGH.  kMask: feature f of the keyframe with skip[skip_off[k] + f] != 0 is no candidate, in either walk.
+template <bool kChi2, bool kResident, bool kMask = false, bool kPair = false>
+__device__ __forceinline__ void fuse_pair(const FuseArgs& a, int k, const float* pose, int i, bool live, uint32_t out, int counter) {
   const int lane = threadIdx.x & 63;
   const int s = kResident ? a.slot[k] : k;
   const float* rec = a.rec + (size_t)s * FSM_REC_FLOATS;
-  const float* pose = a.pose + (size_t)k * FSM_POSE_FLOATS;
+  const uint8_t* skip = kMask ? a.skip + a.skip_off[k] : nullptr;
+  const uint32_t dist_th = kPair ? FSM_TH_HIGH : FSM_TH_LOW;
   const int32_t f0 = kResident ? s * a.stride : a.feat_off[k];   // slots * stride <= INT32_MAX
   const int32_t* cell_off = a.cell_off + (size_t)s * (FSM_CELLS + 1);
   const uint16_t* cell_idx = a.cell_idx + f0;
@@ -76,8 +84,12 @@ __device__ __forceinline__ void fuse_pair(const FuseArgs& a, int k, int i, bool 
   bool wide = false;
   if (live) {
     const float P3[3] = {a.pos[3 * (size_t)i], a.pos[3 * (size_t)i + 1], a.pos[3 * (size_t)i + 2]};
-    const float Pn[3] = {a.normal[3 * (size_t)i], a.normal[3 * (size_t)i + 1], a.normal[3 * (size_t)i + 2]};
-    status = fsm_gate(rec, pose, P3, Pn, a.dmin[i], a.dmax[i], a.nlevels, a.logsf, u, v, level);
+    if (kPair) {
+      status = ssm_gate(rec, pose, P3, a.dmin[i], a.dmax[i], a.nlevels, a.logsf, u, v, level);
+    } else {
+      const float Pn[3] = {a.normal[3 * (size_t)i], a.normal[3 * (size_t)i + 1], a.normal[3 * (size_t)i + 2]};
+      status = fsm_gate(rec, pose, P3, Pn, a.dmin[i], a.dmax[i], a.nlevels, a.logsf, u, v, level);
+    }
     word = fsm_pack(status, 0, FSM_NO_DIST, FSM_NO_IDX);
     if (status == FSM_EMPTY) {
       r = a.th * a.scale_factors[level];
@@ -93,14 +105,14 @@ __device__ __forceinline__ void fuse_pair(const FuseArgs& a, int k, int i, bool 
             const int32_t c0 = cell_off[ix * FSM_GRID_ROWS + y0], c1 = cell_off[ix * FSM_GRID_ROWS + y1 + 1];
             for (int32_t p = c0; p < c1; p++) {
               bool in;
-              const int d = fsm_candidate<kChi2>(kxy, koct, kdesc, cell_idx[p], u, v, r, level, a.inv_sigma2, q, in);
+              const int d = fsm_candidate<kChi2, kMask>(kxy, koct, kdesc, cell_idx[p], u, v, r, level, a.inv_sigma2, q, in, skip);
               any |= in;
               if (d >= 0) key = min(key, ((uint32_t)d << 16) | (uint32_t)p);
             }
           }
         }
       }
-      if (!wide) word = fsm_finish(level, any, key, cell_idx);
+      if (!wide) word = fsm_finish(level, any, key, cell_idx, dist_th);
     }
   }
   // the wide windows: the wave takes them one by one
@@ -119,14 +131,14 @@ __device__ __forceinline__ void fuse_pair(const FuseArgs& a, int k, int i, bool 
       const int32_t c0 = cell_off[ix * FSM_GRID_ROWS + sy0], c1 = cell_off[ix * FSM_GRID_ROWS + sy1 + 1];
       for (int32_t p = c0 + lane; p < c1; p += 64) {
         bool in;
-        const int d = fsm_candidate<kChi2>(kxy, koct, kdesc, cell_idx[p], su, sv, sr, sl, a.inv_sigma2, q, in);
+        const int d = fsm_candidate<kChi2, kMask>(kxy, koct, kdesc, cell_idx[p], su, sv, sr, sl, a.inv_sigma2, q, in, skip);
         any |= in;
         if (d >= 0) key = min(key, ((uint32_t)d << 16) | (uint32_t)p);
       }
     }
     any = __ballot(any) != 0;
     key = wave_min_u32(key);
-    if (lane == src) word = fsm_finish(level, any, key, cell_idx);
+    if (lane == src) word = fsm_finish(level, any, key, cell_idx, dist_th);
   }
   if (live) {
     a.table[out] = word;
@@ -141,27 +153,30 @@ __device__ __forceinline__ void fuse_pair(const FuseArgs& a, int k, int i, bool 
 }
 
 // workgroup = (keyframe k, tile of 256 points): word k * P + i (K * P <= INT32_MAX), the counters are the keyframe's
-template <bool kResident>
+template <bool kResident, bool kMask = false>
 __device__ __forceinline__ void fuse_sim3_body(const FuseArgs& a) {
   const int k = (int)(blockIdx.x / (unsigned)a.tiles), tile = (int)(blockIdx.x % (unsigned)a.tiles);
   const int i = tile * FPM_TILE + (int)threadIdx.x;
-  fuse_pair<false, kResident>(a, k, i, i < a.P, (uint32_t)k * (uint32_t)a.P + (uint32_t)i, k);
+  fuse_pair<false, kResident, kMask>(a, k, a.pose + (size_t)k * FSM_POSE_FLOATS, i, i < a.P, (uint32_t)k * (uint32_t)a.P + (uint32_t)i, k);
 }
 __global__ __launch_bounds__(FPM_TILE) void fuse_sim3_kernel(FuseArgs a) { fuse_sim3_body<false>(a); }
 __global__ __launch_bounds__(FPM_TILE) void fuse_sim3_resident_kernel(FuseArgs a) { fuse_sim3_body<true>(a); }
+__global__ __launch_bounds__(FPM_TILE) void proj_sim3_resident_kernel(FuseArgs a) { fuse_sim3_body<true, true>(a); }
 
 // workgroup = tile[blockIdx.x] = (job j, first pair of the job): the job's words start at its out0, the counters are the job's
-template <bool kResident>
+template <bool kResident, bool kPair = false>
 __device__ __forceinline__ void fuse_pose_body(const FuseArgs& a) {
   const int j = a.tile[2 * (size_t)blockIdx.x], i0 = a.tile[2 * (size_t)blockIdx.x + 1];
   const int32_t* jr = a.job + FPM_JOB_INTS * (size_t)j;
   const int k = jr[0], pt0 = jr[1], n = jr[2], out0 = jr[3];
   const int e = i0 + (int)threadIdx.x;   // the pair's place in the job
   const bool live = e < n;
-  fuse_pair<true, kResident>(a, k, live ? pt0 + e : pt0, live, (uint32_t)out0 + (uint32_t)e, j);
+  const float* pose = kPair ? a.pose + (size_t)j * SSM_JOB_FLOATS : a.pose + (size_t)k * FSM_POSE_FLOATS;
+  fuse_pair<!kPair, kResident, false, kPair>(a, k, pose, live ? pt0 + e : pt0, live, (uint32_t)out0 + (uint32_t)e, j);
 }
 __global__ __launch_bounds__(FPM_TILE) void fuse_pose_kernel(FuseArgs a) { fuse_pose_body<false>(a); }
 __global__ __launch_bounds__(FPM_TILE) void fuse_pose_resident_kernel(FuseArgs a) { fuse_pose_body<true>(a); }
+__global__ __launch_bounds__(FPM_TILE) void sim3_pair_resident_kernel(FuseArgs a) { fuse_pose_body<true, true>(a); }
 
 typedef std::chrono::steady_clock Clock;
 double us_between(Clock::time_point x, Clock::time_point y) { return std::chrono::duration<double, std::micro>(y - x).count(); }
@@ -189,20 +204,22 @@ FuseArgs fuse_stage_inputs(const Block& b, const float* kf_rec, const int32_t* f
   return a;
 }
 
-// The same for the resident blocks (FuseSim3ResidentBlock, FusePoseResidentBlock): the points and the per-call table from the caller, the keyframes' arrays from
-// the store, and the slot list fuse_store_slots made of the keys.  The caller holds the store's reader lock.
+// The same for the resident blocks: the points and the per-call table from the caller, the keyframes' arrays from the store, and the slot list fuse_store_slots
+// made of the keys.  normal_seg == nullptr: a block without normals (Sim3PairResidentBlock).  The caller holds the store's reader lock.
 template <class Block>
 FuseArgs fuse_resident_inputs(const Block& b, const ccm_kfstore* st, const std::vector<int32_t>& slots, int nlevels, const float* scale_factors, float logScaleFactor,
-                              float th, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc) {
+                              float th, const float* pos, const StagedSeg<float>* normal_seg, const float* normal, const float* min_dist, const float* max_dist,
+                              const uint8_t* pt_desc) {
   if (b.slot.count) memcpy(b.up(b.slot), slots.data(), b.slot.count * sizeof(int32_t));
   b.put(b.pdesc, pt_desc); b.put(b.scale_factors, scale_factors);
-  b.put(b.pos, pos); b.put(b.normal, normal); b.put(b.dmin, min_dist); b.put(b.dmax, max_dist);
+  b.put(b.pos, pos); b.put(b.dmin, min_dist); b.put(b.dmax, max_dist);
+  if (normal_seg) b.put(*normal_seg, normal);
   FuseArgs a = {};
   a.nlevels = nlevels; a.th = th; a.logsf = logScaleFactor;
   a.rec = st->d_rec; a.kxy = st->d_xy; a.cell_off = st->d_cell_off; a.cell_idx = st->d_cell_idx; a.koct = st->d_oct; a.kdesc = st->d_desc;
   a.slot = b.dev(b.slot); a.stride = st->stride;
   a.pose = b.dev(b.pose); a.scale_factors = b.dev(b.scale_factors);
-  a.pos = b.dev(b.pos); a.normal = b.dev(b.normal); a.dmin = b.dev(b.dmin); a.dmax = b.dev(b.dmax); a.pdesc = b.dev(b.pdesc);
+  a.pos = b.dev(b.pos); a.normal = normal_seg ? b.dev(*normal_seg) : nullptr; a.dmin = b.dev(b.dmin); a.dmax = b.dev(b.dmax); a.pdesc = b.dev(b.pdesc);
   a.table = b.dev(b.table); a.n_valid = b.dev(b.n_valid); a.n_hit = b.dev(b.n_hit);
   a.uv = b.uv.count ? b.dev(b.uv) : nullptr;
   return a;
@@ -342,7 +359,7 @@ extern "C" int ccm_fuse_sim3_eval_resident(ccm_ctx* ctx, ccm_kfstore* st, int K,
   FuseSim3ResidentBlock b((size_t)K, (size_t)P, (size_t)nlevels, uv != nullptr);
   if (int rc = ccm_staged_begin(ctx, b, me)) return rc;
   const Clock::time_point t0 = Clock::now();
-  FuseArgs a = fuse_resident_inputs(b, st, slots, nlevels, scale_factors, logScaleFactor, th, pos, normal, min_dist, max_dist, pt_desc);
+  FuseArgs a = fuse_resident_inputs(b, st, slots, nlevels, scale_factors, logScaleFactor, th, pos, &b.normal, normal, min_dist, max_dist, pt_desc);
   float* h_pose = b.up(b.pose);
   for (int k = 0; k < K; k++) fsm_decompose_scw(Scw + 12 * (size_t)k, h_pose + FSM_POSE_FLOATS * (size_t)k);
   const Clock::time_point t1 = Clock::now();
@@ -380,7 +397,7 @@ extern "C" int ccm_fuse_pose_eval_resident(ccm_ctx* ctx, ccm_kfstore* st, int K,
   FusePoseResidentBlock b((size_t)K, (size_t)P, (size_t)nlevels, (size_t)J, (size_t)tiles, (size_t)total, uv != nullptr);
   if (int rc = ccm_staged_begin(ctx, b, me)) return rc;
   const Clock::time_point t0 = Clock::now();
-  FuseArgs a = fuse_resident_inputs(b, st, slots, nlevels, scale_factors, logScaleFactor, th, pos, normal, min_dist, max_dist, pt_desc);
+  FuseArgs a = fuse_resident_inputs(b, st, slots, nlevels, scale_factors, logScaleFactor, th, pos, &b.normal, normal, min_dist, max_dist, pt_desc);
   b.put(b.pose, pose); b.put(b.inv_sigma2, inv_level_sigma2);
   fuse_pose_jobs(b, J, job_kf, job_pt0, job_n);
   const Clock::time_point t1 = Clock::now();
@@ -392,5 +409,86 @@ extern "C" int ccm_fuse_pose_eval_resident(ccm_ctx* ctx, ccm_kfstore* st, int K,
   if (ccm_dbg("fuse"))
     fprintf(stderr, "[fuse_pose_resident] K=%d P=%d J=%d pairs=%lld pack_us=%.1f device_us=%.1f unpack_us=%.1f up_bytes=%zu down_bytes=%zu\n", K, P, J,
             (long long)total, us_between(t0, t1), us_between(t1, t2), us_between(t2, Clock::now()), b.up_bytes(), b.down_bytes());
+  return CCM_OK;
+}
+
+extern "C" int ccm_sim3_project_eval_resident(ccm_ctx* ctx, ccm_kfstore* st, int K, const int64_t* keys, const float* Scw, const int32_t* skip_off,
+                                              const uint8_t* feat_skip, int nlevels, const float* scale_factors, float logScaleFactor, float th, int P, const float* pos,
+                                              const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc, uint32_t* table,
+                                              int32_t* n_valid, int32_t* n_hit, float* uv) {
+  if (!ctx) return CCM_E_ARG;
+  const char* const me = "ccm_sim3_project_eval_resident: ";
+  if (int rc = fuse_store_ok(ctx, st, me)) return rc;
+  if (const char* why = fsm_check_scalars(K, P, nlevels, th)) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + why);
+  if (!scale_factors || (K > 0 && (!keys || !Scw || !n_valid || !n_hit)) || (P > 0 && (!pos || !normal || !min_dist || !max_dist || !pt_desc)) || (K > 0 && P > 0 && !table))
+    return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + "null pointers");
+  std::shared_lock<std::shared_mutex> lk(st->mu);
+  std::vector<int32_t> slots;
+  if (int rc = fuse_store_slots(ctx, st, K, keys, me, &slots)) return rc;
+  std::vector<int32_t> kf_n((size_t)K);
+  for (int k = 0; k < K; k++) kf_n[k] = st->h_n[(size_t)slots[k]];
+  if (const char* why = fsm_check_skip(K, skip_off, feat_skip, kf_n.data())) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + why);
+  for (int k = 0; k < K; k++) n_valid[k] = n_hit[k] = 0;
+  if (K == 0 || P == 0) return CCM_OK;
+  Sim3ProjectResidentBlock b((size_t)K, (size_t)P, (size_t)nlevels, (size_t)skip_off[K], uv != nullptr);
+  if (int rc = ccm_staged_begin(ctx, b, me)) return rc;
+  const Clock::time_point t0 = Clock::now();
+  FuseArgs a = fuse_resident_inputs(b, st, slots, nlevels, scale_factors, logScaleFactor, th, pos, &b.normal, normal, min_dist, max_dist, pt_desc);
+  b.put(b.skip_off, skip_off); b.put(b.skip, feat_skip);
+  a.skip_off = b.dev(b.skip_off); a.skip = b.dev(b.skip);
+  float* h_pose = b.up(b.pose);
+  for (int k = 0; k < K; k++) fsm_decompose_scw(Scw + 12 * (size_t)k, h_pose + FSM_POSE_FLOATS * (size_t)k);
+  const Clock::time_point t1 = Clock::now();
+  if (int rc = ccm_staged_upload(ctx, b)) return rc;
+  a.P = P; a.tiles = (P + FPM_TILE - 1) / FPM_TILE;
+  const uint64_t groups = (uint64_t)K * (uint64_t)a.tiles;
+  if (groups > (uint64_t)INT32_MAX) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + "too many workgroups");
+  hipLaunchKernelGGL(proj_sim3_resident_kernel, dim3((unsigned)groups), dim3(FPM_TILE), 0, ctx->stream, a);
+  Clock::time_point t2;
+  if (int rc = fuse_stage_outputs(ctx, b, table, n_valid, n_hit, uv, &t2)) return rc;
+  if (ccm_dbg("fuse"))
+    fprintf(stderr, "[sim3_project] K=%d P=%d pack_us=%.1f device_us=%.1f unpack_us=%.1f up_bytes=%zu down_bytes=%zu\n", K, P, us_between(t0, t1), us_between(t1, t2),
+            us_between(t2, Clock::now()), b.up_bytes(), b.down_bytes());
+  return CCM_OK;
+}
+
+extern "C" int ccm_sim3_pair_eval_resident(ccm_ctx* ctx, ccm_kfstore* st, int K, const int64_t* keys, int nlevels, const float* scale_factors, float logScaleFactor,
+                                           float th, int P, const float* pos, const float* min_dist, const float* max_dist, const uint8_t* pt_desc, int J,
+                                           const int32_t* job_kf, const float* job_K4, const float* job_src_pose, const float* job_T, const int32_t* job_pt0,
+                                           const int32_t* job_n, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv) {
+  if (!ctx) return CCM_E_ARG;
+  const char* const me = "ccm_sim3_pair_eval_resident: ";
+  if (int rc = fuse_store_ok(ctx, st, me)) return rc;
+  if (const char* why = fsm_check_scalars(K, P, nlevels, th)) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + why);
+  int64_t total = 0, tiles = 0;
+  if (const char* why = fpm_check_jobs(J, K, P, job_kf, job_pt0, job_n, &total, &tiles)) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + why);
+  if (const char* why = fsm_check_pair_jobs(J, job_K4, job_src_pose, job_T)) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + why);
+  if (!scale_factors || (K > 0 && !keys) || (J > 0 && (!n_valid || !n_hit)) || (P > 0 && (!pos || !min_dist || !max_dist || !pt_desc)) || (total > 0 && !table))
+    return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + "null pointers");
+  std::shared_lock<std::shared_mutex> lk(st->mu);
+  std::vector<int32_t> slots;
+  if (int rc = fuse_store_slots(ctx, st, K, keys, me, &slots)) return rc;
+  for (int j = 0; j < J; j++) n_valid[j] = n_hit[j] = 0;
+  if (total == 0) return CCM_OK;
+  Sim3PairResidentBlock b((size_t)K, (size_t)P, (size_t)nlevels, (size_t)J, (size_t)tiles, (size_t)total, uv != nullptr);
+  if (int rc = ccm_staged_begin(ctx, b, me)) return rc;
+  const Clock::time_point t0 = Clock::now();
+  FuseArgs a = fuse_resident_inputs(b, st, slots, nlevels, scale_factors, logScaleFactor, th, pos, nullptr, nullptr, min_dist, max_dist, pt_desc);
+  float* h_job = b.up(b.pose);
+  for (int j = 0; j < J; j++) {
+    float* r = h_job + SSM_JOB_FLOATS * (size_t)j;
+    memcpy(r, job_K4 + 4 * (size_t)j, 4 * sizeof(float)); memcpy(r + 4, job_src_pose + 12 * (size_t)j, 12 * sizeof(float));
+    memcpy(r + 16, job_T + 12 * (size_t)j, 12 * sizeof(float));
+  }
+  fuse_pose_jobs(b, J, job_kf, job_pt0, job_n);
+  const Clock::time_point t1 = Clock::now();
+  if (int rc = ccm_staged_upload(ctx, b)) return rc;
+  a.job = b.dev(b.job); a.tile = b.dev(b.tile);
+  hipLaunchKernelGGL(sim3_pair_resident_kernel, dim3((unsigned)tiles), dim3(FPM_TILE), 0, ctx->stream, a);
+  Clock::time_point t2;
+  if (int rc = fuse_stage_outputs(ctx, b, table, n_valid, n_hit, uv, &t2)) return rc;
+  if (ccm_dbg("fuse"))
+    fprintf(stderr, "[sim3_pair] K=%d P=%d J=%d pairs=%lld pack_us=%.1f device_us=%.1f unpack_us=%.1f up_bytes=%zu down_bytes=%zu\n", K, P, J, (long long)total,
+            us_between(t0, t1), us_between(t1, t2), us_between(t2, Clock::now()), b.up_bytes(), b.down_bytes());
   return CCM_OK;
 }

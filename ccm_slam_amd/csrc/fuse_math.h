@@ -30,6 +30,7 @@ enum {
   FSM_HIT = 7
 };
 #define FSM_TH_LOW 50
+#define FSM_TH_HIGH 100       // ORBmatcher::TH_HIGH, the threshold of SearchBySim3
 #define FSM_NO_IDX 0xFFFFu
 #define FSM_NO_DIST 511u
 #define FSM_MAX_LEVELS 16
@@ -42,6 +43,7 @@ enum {
 #define FPM_CHI2 5.99         // ORBmatcher.cpp:950, a double literal
 #define FPM_JOB_INTS 4        // a job's record in the staged block: keyframe, first point, points, first table word
 #define FPM_TILE 256          // pairs per workgroup
+#define SSM_JOB_FLOATS 28     // a SearchBySim3 job's floats in the staged block: fx fy cx cy, R_aw (9, row-major), t_aw (3), sR_ba (9), t_ba (3)
 
 FSM_HD uint32_t fsm_pack(int status, int level, uint32_t dist, uint32_t idx) {
   return ((uint32_t)status << 29) | ((uint32_t)level << 25) | (dist << 16) | idx;
@@ -140,13 +142,16 @@ FSM_HD int fsm_hamming(const uint32_t a[8], const uint32_t b[8]) {   // ORBmatch
 // kChi2: the pose form, in the order of ORBmatcher.cpp:941-955: the level filter, ex / ey / e2 in f32 (two products and one sum, never fused), the gate
 // `e2 * mvInvLevelSigma2[kpLevel] > 5.99` (an f32 product widened to double for the comparison, so a NaN passes as it does there), then the distance.
 // o <= level < nlevels bounds the read of inv_sigma2, which the Sim3 form does not read.
-template <bool kChi2>
+// kMask: SearchByProjection(pKF, Scw, ...)'s `if(vpMatched[idx]) continue;` (ORBmatcher.cpp:393), tested before the level filter: skip[f] != 0 makes feature f no
+// candidate, but it stays one of vIndices (the reference tests vIndices.empty() before its loop).  Without the flag skip is not read.
+template <bool kChi2, bool kMask = false>
 FSM_HD int fsm_candidate(const float* xy, const uint8_t* oct, const uint8_t* desc, int f, float u, float v, float r, int level, const float* inv_sigma2,
-                         const uint32_t q[8], bool& in_window) {
+                         const uint32_t q[8], bool& in_window, const uint8_t* skip = nullptr) {
   const float kpx = xy[2 * f], kpy = xy[2 * f + 1];
   const float distx = kpx - u, disty = kpy - v;
   in_window = fabsf(distx) < r && fabsf(disty) < r;
   if (!in_window) return -1;
+  if (kMask && skip[f]) return -1;
   const int o = oct[f];
   if (o < level - 1 || o > level) return -1;
   if (kChi2) {
@@ -168,21 +173,22 @@ FSM_HD int fsm_window_count(const int32_t* cell_off, int x0, int x1, int y0, int
   return n;
 }
 
-// the packed answer of a pair that passed the gates, from the best key (dist << 16 | CSR position, ~0u: no candidate at the level) and whether the window was empty
-FSM_HD uint32_t fsm_finish(int level, bool any, uint32_t key, const uint16_t* cell_idx) {
+// the packed answer of a pair that passed the gates, from the best key (dist << 16 | CSR position, ~0u: no candidate at the level, or every one masked) and whether
+// the window was empty.  dist_th: TH_LOW for Fuse and SearchByProjection, TH_HIGH for SearchBySim3.
+FSM_HD uint32_t fsm_finish(int level, bool any, uint32_t key, const uint16_t* cell_idx, uint32_t dist_th) {
   if (!any) return fsm_pack(FSM_EMPTY, level, FSM_NO_DIST, FSM_NO_IDX);
   if (key == ~0u) return fsm_pack(FSM_NO_LEVEL, level, FSM_NO_DIST, FSM_NO_IDX);
   const uint32_t dist = key >> 16, idx = cell_idx[key & 0xFFFFu];
-  return fsm_pack(dist <= FSM_TH_LOW ? FSM_HIT : FSM_FAR, level, dist, idx);
+  return fsm_pack(dist <= dist_th ? FSM_HIT : FSM_FAR, level, dist, idx);
 }
 
 // ORBmatcher.cpp:1071-1118 (kChi2: :920-989) for one pair that passed the gates, one candidate after the other in the reference's order: ix, then iy, then the
 // position in the cell — ascending CSR position, so the first strict minimum is the lowest position among the minima.  All arrays are the keyframe's own (cell_idx:
-// local feature indices).  n_cand (nullable): the size of vIndices.
-template <bool kChi2>
+// local feature indices).  n_cand (nullable): the size of vIndices.  kMask, skip: fsm_candidate's; dist_th: fsm_finish's.
+template <bool kChi2, bool kMask = false>
 FSM_HD uint32_t fsm_window_best(const float rec[FSM_REC_FLOATS], const int32_t* cell_off, const uint16_t* cell_idx, const float* xy, const uint8_t* oct,
                                 const uint8_t* desc, float u, float v, int level, float th, const float* scale_factors, const float* inv_sigma2, const uint32_t q[8],
-                                int* n_cand) {
+                                int* n_cand, const uint8_t* skip = nullptr, uint32_t dist_th = FSM_TH_LOW) {
   const float r = th * scale_factors[level];
   int x0, x1, y0, y1;
   bool any = false;
@@ -193,14 +199,62 @@ FSM_HD uint32_t fsm_window_best(const float rec[FSM_REC_FLOATS], const int32_t* 
       const int a = cell_off[ix * FSM_GRID_ROWS + y0], b = cell_off[ix * FSM_GRID_ROWS + y1 + 1];
       for (int pos = a; pos < b; pos++) {
         bool in;
-        const int d = fsm_candidate<kChi2>(xy, oct, desc, cell_idx[pos], u, v, r, level, inv_sigma2, q, in);
+        const int d = fsm_candidate<kChi2, kMask>(xy, oct, desc, cell_idx[pos], u, v, r, level, inv_sigma2, q, in, skip);
         any |= in; n += in;
         if (d >= 0) { const uint32_t k = ((uint32_t)d << 16) | (uint32_t)pos; if (k < key) key = k; }   // pos ascends: an equal distance later is no less
       }
     }
   }
   if (n_cand) *n_cand = n;
-  return fsm_finish(level, any, key, cell_idx);
+  return fsm_finish(level, any, key, cell_idx, dist_th);
+}
+
+// ---- SearchBySim3 (ORBmatcher.cpp:1124-1348) -----------------------------------------------------------------------------------------------------------------
+// :1141-1143.  sR12 = s12 * R12: Mat * s, the product formed in float.  sR21 = (1.0 / s12) * R12.t(): a MatTExpr with alpha = 1.0 / (double)s12, materialised as the
+// transpose times alpha ROUNDED TO FLOAT (alpha == 1 multiplies nothing, which leaves the same bits).  t21 = -sR21 * t12: the negated matrix first (unary minus on
+// a Mat), then the small-matrix gemm without an addend: a float accumulator summed left to right, stored as (float)(t * 1.0 + 0.0).
+FSM_HD void ssm_derive(float s12, const float R12[9], const float t12[3], float sR12[9], float sR21[9], float t21[3]) {
+  for (int i = 0; i < 9; i++) sR12[i] = R12[i] * s12;
+  const double alpha = 1.0 / (double)s12;
+  for (int r = 0; r < 3; r++)
+    for (int c = 0; c < 3; c++) sR21[3 * r + c] = alpha != 1 ? R12[3 * c + r] * (float)alpha : R12[3 * c + r];
+  for (int r = 0; r < 3; r++) {
+    const float n0 = -sR21[3 * r], n1 = -sR21[3 * r + 1], n2 = -sR21[3 * r + 2];
+    const float t = n0 * t12[0] + n1 * t12[1] + n2 * t12[2];
+    t21[r] = (float)((double)t * 1.0 + 0.0);
+  }
+}
+
+// One direction's gate, :1180-1208 (a = 1, b = 2) and :1260-1288 (a = 2, b = 1): p3Dc_a = R_aw * p3Dw + t_aw and p3Dc_b = sR_ba * p3Dc_a + t_ba, two small-matrix
+// gemms with an addend; depth; the projection with job[0..3]; the TARGET's IsInImage (rec[4..7]); dist3D = the float of the double norm of p3Dc_b; the range;
+// PredictScale.  job: SSM_JOB_FLOATS.  job[0..3] are pKF1's intrinsics in BOTH directions (:1127-1130 reads them once, :1192 and :1272 use them), whatever the
+// target's record says.  There is no viewing-angle gate: FSM_ANGLE does not occur.  Returns and outputs as fsm_gate.
+FSM_HD int ssm_gate(const float rec[FSM_REC_FLOATS], const float job[SSM_JOB_FLOATS], const float P[3], float mfMinDistance, float mfMaxDistance, int nlevels,
+                    float logScaleFactor, float& u, float& v, int& level) {
+  const float *Raw = job + 4, *taw = job + 13, *sR = job + 16, *tba = job + 25;
+  float Pa[3], Pb[3];
+  for (int i = 0; i < 3; i++) {
+    const float t = Raw[3 * i] * P[0] + Raw[3 * i + 1] * P[1] + Raw[3 * i + 2] * P[2];
+    Pa[i] = (float)((double)t * 1.0 + (double)taw[i] * 1.0);
+  }
+  for (int i = 0; i < 3; i++) {
+    const float t = sR[3 * i] * Pa[0] + sR[3 * i + 1] * Pa[1] + sR[3 * i + 2] * Pa[2];
+    Pb[i] = (float)((double)t * 1.0 + (double)tba[i] * 1.0);
+  }
+  u = 0.0f; v = 0.0f; level = 0;
+  if (Pb[2] < 0.0f) return FSM_BEHIND;
+  const float invz = (float)(1.0 / (double)Pb[2]);
+  const float x = Pb[0] * invz, y = Pb[1] * invz;
+  u = job[0] * x + job[2];
+  v = job[1] * y + job[3];
+  if (!(u >= rec[4] && u < rec[6] && v >= rec[5] && v < rec[7])) return FSM_OUTSIDE;
+  const float maxDistance = 1.2f * mfMaxDistance, minDistance = 0.8f * mfMinDistance;
+  double s2 = 0;
+  for (int i = 0; i < 3; i++) s2 += (double)Pb[i] * (double)Pb[i];
+  const float dist3D = (float)sqrt(s2);
+  if (dist3D < minDistance || dist3D > maxDistance) return FSM_RANGE;
+  level = fsm_predict_scale(mfMaxDistance, dist3D, logScaleFactor, nlevels);
+  return FSM_EMPTY;
 }
 
 // The argument rules of ccm_fuse_sim3_eval; nullptr, or what is wrong.  The scalar rules come first and read no array.  cell_idx: int32 as the caller passes it.
@@ -251,5 +305,23 @@ FSM_HD const char* fpm_check_jobs(int J, int K, int P, const int32_t* job_kf, co
   }
   if (t > (int64_t)INT32_MAX) return "too many workgroups";
   *total = sum; *tiles = t;
+  return nullptr;
+}
+
+// The mask rules of ccm_sim3_project_eval_resident; nullptr, or what is wrong.  kf_n[k]: the feature count of key k in the store.
+FSM_HD const char* fsm_check_skip(int K, const int32_t* skip_off, const uint8_t* feat_skip, const int32_t* kf_n) {
+  if (K <= 0) return nullptr;
+  if (!skip_off) return "null pointers";
+  if (skip_off[0] != 0) return "skip_off[0] != 0";
+  for (int k = 0; k < K; k++) {
+    if (skip_off[k + 1] < skip_off[k]) return "skip_off decreases";
+    if (skip_off[k + 1] - skip_off[k] != kf_n[k]) return "a mask is not as long as its keyframe's features";
+  }
+  if (skip_off[K] > 0 && !feat_skip) return "null pointers";
+  return nullptr;
+}
+// the null-pointer rules of ccm_sim3_pair_eval_resident's per-job floats (the index arrays are fpm_check_jobs')
+FSM_HD const char* fsm_check_pair_jobs(int J, const float* job_K4, const float* job_src_pose, const float* job_T) {
+  if (J > 0 && (!job_K4 || !job_src_pose || !job_T)) return "null job arrays";
   return nullptr;
 }

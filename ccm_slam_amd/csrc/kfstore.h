@@ -18,6 +18,7 @@ struct ccm_kfstore {
   uint8_t* d_oct = nullptr;        // [stride max_kf]
   uint8_t* d_desc = nullptr;       // [32 stride max_kf]
   // host
+  std::vector<int32_t> h_n;                // [max_kf] d_n as the adds wrote it: the feature count a mask of ccm_sim3_project_eval_resident is held to
   std::unordered_map<int64_t, int> live;   // key -> slot
   std::vector<int> free_slots;             // a stack: the slot freed last is taken first
 };

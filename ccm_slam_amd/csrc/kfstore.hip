@@ -163,6 +163,7 @@ extern "C" int ccm_kfstore_create(ccm_ctx* ctx, int max_kf, int max_feat, ccm_kf
     return ccm_set_error(ctx, CCM_E_HIP, "ccm_kfstore_create: device allocation failed");
   }
   st->free_slots.resize(K);
+  st->h_n.assign(K, 0);
   for (int s = 0; s < max_kf; s++) st->free_slots[s] = max_kf - 1 - s;   // slot 0 is taken first
   *out = st;
   return CCM_OK;
@@ -219,7 +220,10 @@ extern "C" int ccm_kfstore_add(ccm_kfstore* st, ccm_ctx* ctx, int M, const int64
   else hipLaunchKernelGGL(kfstore_add_kernel<true>, dim3((unsigned)M), dim3(kAddThreads), 0, ctx->stream, a);
   CCM_HIP_CHECK(ctx, hipGetLastError());
   if (int rc = ccm_staged_download(ctx, b)) return rc;   // synchronises: the slots are written when the keys become live
-  for (int m = 0; m < M; m++) { st->live[keys[m]] = st->free_slots.back(); st->free_slots.pop_back(); }
+  for (int m = 0; m < M; m++) {
+    st->h_n[(size_t)st->free_slots.back()] = feat_off[m + 1] - feat_off[m];
+    st->live[keys[m]] = st->free_slots.back(); st->free_slots.pop_back();
+  }
   return CCM_OK;
 }
 

@@ -199,3 +199,31 @@ struct FusePoseResidentBlock : StagedBlock {
   StagedSeg<uint32_t> table = add<uint32_t>(N, SB_OUT);
   StagedSeg<float> uv = add<float>(want_uv ? 2 * N : 0, SB_OUT);
 };
+
+// ccm_sim3_project_eval_resident: FuseSim3ResidentBlock and the masks: skip_off (K + 1) and M = skip_off[K] mask bytes, one per feature of every keyframe of the call.
+struct Sim3ProjectResidentBlock : StagedBlock {
+  const size_t K, P, L, M; const bool want_uv;
+  Sim3ProjectResidentBlock(size_t K, size_t P, size_t L, size_t M, bool want_uv) : K(K), P(P), L(L), M(M), want_uv(want_uv) {}
+  StagedSeg<uint8_t> pdesc = add<uint8_t>(32 * P, SB_COPY, 16);
+  StagedSeg<int32_t> slot = add<int32_t>(K, SB_GEN), skip_off = add<int32_t>(K + 1, SB_COPY);
+  StagedSeg<float> pose = add<float>(FSM_POSE_FLOATS * K, SB_GEN), scale_factors = add<float>(L, SB_COPY);
+  StagedSeg<float> pos = add<float>(3 * P, SB_COPY), normal = add<float>(3 * P, SB_COPY), dmin = add<float>(P, SB_COPY), dmax = add<float>(P, SB_COPY);
+  StagedSeg<uint8_t> skip = add<uint8_t>(M, SB_COPY);
+  StagedSeg<int32_t> n_valid = add<int32_t>(K, SB_OUT | SB_ZERO), n_hit = add<int32_t>(K, SB_OUT | SB_ZERO);
+  StagedSeg<uint32_t> table = add<uint32_t>(K * P, SB_OUT);
+  StagedSeg<float> uv = add<float>(want_uv ? 2 * K * P : 0, SB_OUT);
+};
+
+// ccm_sim3_pair_eval_resident: FusePoseResidentBlock without the normals and inv_sigma2, which SearchBySim3 does not read; pose holds SSM_JOB_FLOATS per JOB
+// (K4, the source pose, the transform), packed by the stage.
+struct Sim3PairResidentBlock : StagedBlock {
+  const size_t K, P, L, J, T, N; const bool want_uv;
+  Sim3PairResidentBlock(size_t K, size_t P, size_t L, size_t J, size_t T, size_t N, bool want_uv) : K(K), P(P), L(L), J(J), T(T), N(N), want_uv(want_uv) {}
+  StagedSeg<uint8_t> pdesc = add<uint8_t>(32 * P, SB_COPY, 16);
+  StagedSeg<int32_t> job = add<int32_t>(FPM_JOB_INTS * J, SB_GEN, 16), tile = add<int32_t>(2 * T, SB_GEN), slot = add<int32_t>(K, SB_GEN);
+  StagedSeg<float> pose = add<float>(SSM_JOB_FLOATS * J, SB_GEN), scale_factors = add<float>(L, SB_COPY);
+  StagedSeg<float> pos = add<float>(3 * P, SB_COPY), dmin = add<float>(P, SB_COPY), dmax = add<float>(P, SB_COPY);
+  StagedSeg<int32_t> n_valid = add<int32_t>(J, SB_OUT | SB_ZERO), n_hit = add<int32_t>(J, SB_OUT | SB_ZERO);
+  StagedSeg<uint32_t> table = add<uint32_t>(N, SB_OUT);
+  StagedSeg<float> uv = add<float>(want_uv ? 2 * N : 0, SB_OUT);
+};

@@ -2201,6 +2201,278 @@ SearchInNeighborsBatch::SearchInNeighborsBatch(KeyFrameStore& store, HipContext*
   scene_.hold(std::move(kfs), pose, pts, nlevels, scale_factors, inv_level_sigma2, logScaleFactor, th);
 }
 
+// ---- ComputeSim3's two projected searches: host evaluators, Sim3ProjectionSearch, SearchBySim3Batch ------------------------------
+// one (keyframe, point) pair of SearchByProjection(pKF, Scw, ...): Fuse's Sim3 pair with the skip mask
+static uint32_t sim3_project_pair_host(const FuseKf& kf, const float* pose, const uint8_t* skip, const float* P3, const float* Pn, float dmin, float dmax,
+                                       const uint8_t* pdesc, int nlevels, float logsf, float th, const float* sf, float* uv) {
+  float u, v; int level;
+  const int st = fsm_gate(kf.rec, pose, P3, Pn, dmin, dmax, nlevels, logsf, u, v, level);
+  if (uv) { uv[0] = u; uv[1] = v; }
+  if (st != FSM_EMPTY) return fsm_pack(st, 0, FSM_NO_DIST, FSM_NO_IDX);
+  uint32_t q[8];
+  fsm_load_desc(pdesc, q);
+  return fsm_window_best<false, true>(kf.rec, kf.cell_off, kf.cell_idx, kf.kxy, kf.koct, kf.kdesc, u, v, level, th, sf, nullptr, q, nullptr, skip, FSM_TH_LOW);
+}
+
+// every (keyframe, point) pair, keyframe-major; the arguments are valid
+template <class KfOf>
+static void sim3_project_eval(KfOf kf_of, int K, const float* Scw, const int32_t* skip_off, const uint8_t* feat_skip, int nlevels, const float* scale_factors,
+                              float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist,
+                              const uint8_t* pt_desc, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv) {
+  for (int k = 0; k < K; k++) {
+    float pose[FSM_POSE_FLOATS];
+    fsm_decompose_scw(Scw + 12 * (size_t)k, pose);
+    const FuseKf kf = kf_of(k);
+    n_valid[k] = n_hit[k] = 0;
+    for (int i = 0; i < P; i++) {
+      const size_t e = (size_t)k * (size_t)P + (size_t)i;
+      const uint32_t w = sim3_project_pair_host(kf, pose, feat_skip + skip_off[k], pos + 3 * (size_t)i, normal + 3 * (size_t)i, min_dist[i], max_dist[i],
+                                                pt_desc + 32 * (size_t)i, nlevels, logScaleFactor, th, scale_factors, uv ? uv + 2 * e : nullptr);
+      table[e] = w;
+      n_valid[k] += (w >> 29) >= FSM_EMPTY;
+      n_hit[k] += (w >> 29) == FSM_HIT;
+    }
+  }
+}
+
+// every pair of a list of SearchBySim3 jobs, the jobs' words one after the other; the arguments are valid
+template <class KfOf>
+static void sim3_pair_eval(KfOf kf_of, int nlevels, const float* scale_factors, float logScaleFactor, float th, const float* pos, const float* min_dist,
+                           const float* max_dist, const uint8_t* pt_desc, int J, const int32_t* job_kf, const float* job_K4, const float* job_src_pose, const float* job_T,
+                           const int32_t* job_pt0, const int32_t* job_n, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv) {
+  size_t e = 0;
+  for (int j = 0; j < J; j++) {
+    n_valid[j] = n_hit[j] = 0;
+    const FuseKf kf = kf_of(job_kf[j]);
+    float job[SSM_JOB_FLOATS];
+    std::memcpy(job, job_K4 + 4 * (size_t)j, 4 * sizeof(float)); std::memcpy(job + 4, job_src_pose + 12 * (size_t)j, 12 * sizeof(float));
+    std::memcpy(job + 16, job_T + 12 * (size_t)j, 12 * sizeof(float));
+    for (int i = job_pt0[j]; i < job_pt0[j] + job_n[j]; i++, e++) {
+      float u, v; int level;
+      const int st = ssm_gate(kf.rec, job, pos + 3 * (size_t)i, min_dist[i], max_dist[i], nlevels, logScaleFactor, u, v, level);
+      if (uv) { uv[2 * e] = u; uv[2 * e + 1] = v; }
+      uint32_t w = fsm_pack(st, 0, FSM_NO_DIST, FSM_NO_IDX);
+      if (st == FSM_EMPTY) {
+        uint32_t q[8];
+        fsm_load_desc(pt_desc + 32 * (size_t)i, q);
+        w = fsm_window_best<false>(kf.rec, kf.cell_off, kf.cell_idx, kf.kxy, kf.koct, kf.kdesc, u, v, level, th, scale_factors, nullptr, q, nullptr, nullptr, FSM_TH_HIGH);
+      }
+      table[e] = w;
+      n_valid[j] += (w >> 29) >= FSM_EMPTY;
+      n_hit[j] += (w >> 29) == FSM_HIT;
+    }
+  }
+}
+
+static bool sim3_project_pointers_ok(int K, int P, const void* keys_or_rec, const float* Scw, const float* scale_factors, const float* pos, const float* normal,
+                                     const float* min_dist, const float* max_dist, const uint8_t* pt_desc, const uint32_t* table, const int32_t* n_valid,
+                                     const int32_t* n_hit) {
+  return scale_factors && !(K > 0 && (!keys_or_rec || !Scw || !n_valid || !n_hit)) && !(P > 0 && (!pos || !normal || !min_dist || !max_dist || !pt_desc)) &&
+         !(K > 0 && P > 0 && !table);
+}
+static bool sim3_pair_pointers_ok(int K, int P, int J, int64_t total, const void* keys_or_rec, const float* scale_factors, const float* pos, const float* min_dist,
+                                  const float* max_dist, const uint8_t* pt_desc, const uint32_t* table, const int32_t* n_valid, const int32_t* n_hit) {
+  return scale_factors && !(K > 0 && !keys_or_rec) && !(J > 0 && (!n_valid || !n_hit)) && !(P > 0 && (!pos || !min_dist || !max_dist || !pt_desc)) &&
+         !(total > 0 && !table);
+}
+
+// the flat keyframe arrays as FuseKf, cell_idx narrowed to 16 bits into idx16
+struct FlatKfs {
+  std::vector<uint16_t> idx16;
+  const float* rec; const int32_t* feat_off; const float* xy; const uint8_t* oct; const uint8_t* desc; const int32_t* cell_off;
+  FlatKfs(int K, const float* kf_rec, const int32_t* feat_off_, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc, const int32_t* cell_off_,
+          const int32_t* cell_idx)
+      : rec(kf_rec), feat_off(feat_off_), xy(feat_xy), oct(feat_octave), desc(feat_desc), cell_off(cell_off_) {
+    const size_t F = K ? (size_t)feat_off[K] : 0;
+    idx16.resize(F);
+    for (size_t f = 0; f < F; f++) idx16[f] = (uint16_t)cell_idx[f];
+  }
+  FuseKf operator()(int k) const {
+    const int32_t f0 = feat_off[k];
+    return FuseKf{rec + FSM_REC_FLOATS * (size_t)k, cell_off + (size_t)k * (FSM_CELLS + 1), idx16.data() + f0, xy + 2 * (size_t)f0, oct + f0, desc + 32 * (size_t)f0};
+  }
+};
+
+int sim3_project_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
+                           const int32_t* cell_off, const int32_t* cell_idx, const float* Scw, const int32_t* skip_off, const uint8_t* feat_skip, int nlevels,
+                           const float* scale_factors, float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist,
+                           const float* max_dist, const uint8_t* pt_desc, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv) {
+  if (fsm_check_args(K, P, feat_off, cell_off, cell_idx, nlevels, th)) return -1;
+  const size_t F = K ? (size_t)feat_off[K] : 0;
+  if (!sim3_project_pointers_ok(K, P, kf_rec, Scw, scale_factors, pos, normal, min_dist, max_dist, pt_desc, table, n_valid, n_hit) ||
+      (F && (!feat_xy || !feat_octave || !feat_desc)))
+    return -1;
+  std::vector<int32_t> kf_n((size_t)K);
+  for (int k = 0; k < K; k++) kf_n[k] = feat_off[k + 1] - feat_off[k];
+  if (fsm_check_skip(K, skip_off, feat_skip, kf_n.data())) return -1;
+  const FlatKfs kfs(K, kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off, cell_idx);
+  sim3_project_eval(kfs, K, Scw, skip_off, feat_skip, nlevels, scale_factors, logScaleFactor, th, P, pos, normal, min_dist, max_dist, pt_desc, table, n_valid, n_hit, uv);
+  return 0;
+}
+
+int sim3_pair_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
+                        const int32_t* cell_off, const int32_t* cell_idx, int nlevels, const float* scale_factors, float logScaleFactor, float th, int P, const float* pos,
+                        const float* min_dist, const float* max_dist, const uint8_t* pt_desc, int J, const int32_t* job_kf, const float* job_K4, const float* job_src_pose,
+                        const float* job_T, const int32_t* job_pt0, const int32_t* job_n, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv) {
+  if (fsm_check_args(K, P, feat_off, cell_off, cell_idx, nlevels, th)) return -1;
+  int64_t total = 0, tiles = 0;
+  if (fpm_check_jobs(J, K, P, job_kf, job_pt0, job_n, &total, &tiles) || fsm_check_pair_jobs(J, job_K4, job_src_pose, job_T)) return -1;
+  const size_t F = K ? (size_t)feat_off[K] : 0;
+  if (!sim3_pair_pointers_ok(K, P, J, total, kf_rec, scale_factors, pos, min_dist, max_dist, pt_desc, table, n_valid, n_hit) || (F && (!feat_xy || !feat_octave || !feat_desc)))
+    return -1;
+  const FlatKfs kfs(K, kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off, cell_idx);
+  sim3_pair_eval(kfs, nlevels, scale_factors, logScaleFactor, th, pos, min_dist, max_dist, pt_desc, J, job_kf, job_K4, job_src_pose, job_T, job_pt0, job_n, table, n_valid,
+                 n_hit, uv);
+  return 0;
+}
+
+int sim3_project_eval_resident_host(const KeyFrameStore& store, int K, const int64_t* keys, const float* Scw, const int32_t* skip_off, const uint8_t* feat_skip, int nlevels,
+                                    const float* scale_factors, float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist,
+                                    const float* max_dist, const uint8_t* pt_desc, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv) {
+  if (fsm_check_scalars(K, P, nlevels, th)) return -1;
+  if (!sim3_project_pointers_ok(K, P, keys, Scw, scale_factors, pos, normal, min_dist, max_dist, pt_desc, table, n_valid, n_hit)) return -1;
+  std::vector<std::shared_ptr<const KfShadow>> kfs;
+  if (!store_shadows(store, K, keys, kfs)) return -1;
+  std::vector<int32_t> kf_n((size_t)(K > 0 ? K : 0));
+  for (int k = 0; k < K; k++) kf_n[k] = kfs[k]->n;
+  if (fsm_check_skip(K, skip_off, feat_skip, kf_n.data())) return -1;
+  sim3_project_eval([&](int k) { return fuse_kf(*kfs[k]); }, K, Scw, skip_off, feat_skip, nlevels, scale_factors, logScaleFactor, th, P, pos, normal, min_dist, max_dist,
+                    pt_desc, table, n_valid, n_hit, uv);
+  return 0;
+}
+
+int sim3_pair_eval_resident_host(const KeyFrameStore& store, int K, const int64_t* keys, int nlevels, const float* scale_factors, float logScaleFactor, float th, int P,
+                                 const float* pos, const float* min_dist, const float* max_dist, const uint8_t* pt_desc, int J, const int32_t* job_kf, const float* job_K4,
+                                 const float* job_src_pose, const float* job_T, const int32_t* job_pt0, const int32_t* job_n, uint32_t* table, int32_t* n_valid,
+                                 int32_t* n_hit, float* uv) {
+  if (fsm_check_scalars(K, P, nlevels, th)) return -1;
+  int64_t total = 0, tiles = 0;
+  if (fpm_check_jobs(J, K, P, job_kf, job_pt0, job_n, &total, &tiles) || fsm_check_pair_jobs(J, job_K4, job_src_pose, job_T)) return -1;
+  if (!sim3_pair_pointers_ok(K, P, J, total, keys, scale_factors, pos, min_dist, max_dist, pt_desc, table, n_valid, n_hit)) return -1;
+  std::vector<std::shared_ptr<const KfShadow>> kfs;
+  if (!store_shadows(store, K, keys, kfs)) return -1;
+  sim3_pair_eval([&](int k) { return fuse_kf(*kfs[k]); }, nlevels, scale_factors, logScaleFactor, th, pos, min_dist, max_dist, pt_desc, J, job_kf, job_K4, job_src_pose,
+                 job_T, job_pt0, job_n, table, n_valid, n_hit, uv);
+  return 0;
+}
+
+Sim3ProjectionSearch::Sim3ProjectionSearch(KeyFrameStore& store, HipContext* ctx, int64_t key, const float* Scw12, const Points& pts, const uint8_t* matched0, int nlevels,
+                                           const float* scale_factors, float logScaleFactor, float th)
+    : P_(pts.P) {
+  const int P = P_;
+  if (P < 0 || !Scw12 || !scale_factors || nlevels < 1 || nlevels > FSM_MAX_LEVELS) throw infrastructure_ex("Sim3ProjectionSearch: bad arguments");
+  std::vector<std::shared_ptr<const KfShadow>> kfs;
+  if (!store_shadows(store, 1, &key, kfs)) throw infrastructure_ex("Sim3ProjectionSearch: the key is not in the store");
+  N_ = kfs[0]->n;
+  if (N_ > 0 && !matched0) throw infrastructure_ex("Sim3ProjectionSearch: bad arguments");
+  const int32_t skip_off[2] = {0, N_};
+  table_.assign((size_t)P, 0);
+  if (!store.host_only() && ctx) {
+    check(ccm_sim3_project_eval_resident(ctx->get(), store.handle(), 1, &key, Scw12, skip_off, matched0, nlevels, scale_factors, logScaleFactor, th, P, pts.pos,
+                                         pts.normal, pts.min_dist, pts.max_dist, pts.desc, table_.data(), &n_valid_, &n_hit_, nullptr),
+          ctx->get(), "ccm_sim3_project_eval_resident");
+  } else if (sim3_project_eval_resident_host(store, 1, &key, Scw12, skip_off, matched0, nlevels, scale_factors, logScaleFactor, th, P, pts.pos, pts.normal, pts.min_dist,
+                                             pts.max_dist, pts.desc, table_.data(), &n_valid_, &n_hit_, nullptr)) {
+    throw infrastructure_ex("Sim3ProjectionSearch: bad arguments");
+  }
+  float pose[FSM_POSE_FLOATS];
+  fsm_decompose_scw(Scw12, pose);
+  scene_.hold(std::move(kfs), pose, pts, nlevels, scale_factors, nullptr, logScaleFactor, th);
+}
+
+int Sim3ProjectionSearch::resolve(const uint8_t* skip_now, const int32_t* existing_idx, int32_t* matched, std::vector<int32_t>& bestIdx, std::vector<int32_t>& remap) {
+  bestIdx.assign((size_t)P_, -1); remap.assign((size_t)P_, -1);
+  if (N_ > 0 && !matched) throw infrastructure_ex("Sim3ProjectionSearch::resolve: bad arguments");
+  const FuseScene& s = scene_;
+  const FuseKf kf = fuse_kf(*s.shadow[0]);
+  std::vector<uint8_t> claimed((size_t)N_, 0), mask;   // mask: vpMatched as it is now, made when the first point needs it
+  int nmatches = 0;
+  for (int i = 0; i < P_; i++) {
+    if (skip_now && skip_now[i]) continue;
+    uint32_t w = table_[(size_t)i];
+    if ((w >> 29) != FSM_HIT) continue;
+    if (claimed[w & 0xFFFFu]) {
+      if (mask.empty()) {
+        mask.resize((size_t)N_);
+        for (int f = 0; f < N_; f++) mask[f] = matched[f] >= 0;
+      }
+      w = sim3_project_pair_host(kf, s.pose.data(), mask.data(), s.pos.data() + 3 * (size_t)i, s.normal.data() + 3 * (size_t)i, s.dmin[i], s.dmax[i],
+                                 s.pdesc.data() + 32 * (size_t)i, s.nlevels, s.logsf, s.th, s.sf.data(), nullptr);
+      n_reeval_++;
+      if ((w >> 29) != FSM_HIT) continue;
+    }
+    const int32_t f = (int32_t)(w & 0xFFFFu);
+    if (existing_idx && existing_idx[i] >= 0) { remap[i] = f; continue; }   // :415-434: the caller's GetMapPoint / RemapMapPointMatch; no claim, not counted
+    matched[f] = i; claimed[f] = 1;
+    if (!mask.empty()) mask[f] = 1;
+    bestIdx[i] = f;
+    nmatches++;
+  }
+  return nmatches;
+}
+
+SearchBySim3Batch::SearchBySim3Batch(KeyFrameStore& store, HipContext* ctx, int64_t key1, int64_t key2, const Side& kf1, const Side& kf2, float s12, const float* R12,
+                                     const float* t12, const int32_t* matches12_in, int nlevels, const float* scale_factors, float logScaleFactor, float th) {
+  const int N1 = kf1.N, N2 = kf2.N;
+  auto side_ok = [](const Side& sd) { return sd.N >= 0 && sd.pose && (sd.N == 0 || (sd.live && sd.pos && sd.min_dist && sd.max_dist && sd.desc)); };
+  if (!side_ok(kf1) || !side_ok(kf2) || !R12 || !t12 || (N1 > 0 && !matches12_in) || !scale_factors || nlevels < 1 || nlevels > FSM_MAX_LEVELS)
+    throw infrastructure_ex("SearchBySim3Batch: bad arguments");
+  const int64_t keys[2] = {key1, key2};
+  std::vector<std::shared_ptr<const KfShadow>> kfs;
+  if (!store_shadows(store, 2, keys, kfs)) throw infrastructure_ex("SearchBySim3Batch: a key is not in the store");
+  if (kfs[0]->n != N1 || kfs[1]->n != N2) throw infrastructure_ex("SearchBySim3Batch: a side is not as long as its keyframe's features");
+  // :1151-1164
+  std::vector<uint8_t> already1((size_t)N1, 0), already2((size_t)N2, 0);
+  for (int i = 0; i < N1; i++)
+    if (matches12_in[i] != -1) {
+      already1[i] = 1;
+      if (matches12_in[i] >= 0 && matches12_in[i] < N2) already2[matches12_in[i]] = 1;
+    }
+  // the live unmatched points of keyframe 1, then those of keyframe 2: job 0 searches keyframe 2 (index 1 of keys), job 1 keyframe 1
+  std::vector<int32_t> src;   // the feature slot of every packed point
+  std::vector<float> pos, dmin, dmax;
+  std::vector<uint8_t> desc;
+  auto pack = [&](const Side& sd, const std::vector<uint8_t>& already) {
+    int n = 0;
+    for (int i = 0; i < sd.N; i++) {
+      if (!sd.live[i] || already[i]) continue;
+      src.push_back(i); n++;
+      pos.insert(pos.end(), sd.pos + 3 * (size_t)i, sd.pos + 3 * (size_t)i + 3);
+      dmin.push_back(sd.min_dist[i]); dmax.push_back(sd.max_dist[i]);
+      desc.insert(desc.end(), sd.desc + 32 * (size_t)i, sd.desc + 32 * (size_t)i + 32);
+    }
+    return n;
+  };
+  const int n1 = pack(kf1, already1), n2 = pack(kf2, already2);
+  const int P = n1 + n2;
+  float sR12[9], sR21[9], t21[3];
+  ssm_derive(s12, R12, t12, sR12, sR21, t21);
+  const int32_t job_kf[2] = {1, 0}, job_pt0[2] = {0, n1}, job_n[2] = {n1, n2};
+  float job_K4[8], job_src[24], job_T[24];
+  for (int j = 0; j < 2; j++) std::memcpy(job_K4 + 4 * j, kfs[0]->rec, 4 * sizeof(float));   // pKF1's fx fy cx cy in both directions (:1127-1130)
+  std::memcpy(job_src, kf1.pose, 12 * sizeof(float)); std::memcpy(job_src + 12, kf2.pose, 12 * sizeof(float));
+  std::memcpy(job_T, sR21, 9 * sizeof(float)); std::memcpy(job_T + 9, t21, 3 * sizeof(float));
+  std::memcpy(job_T + 12, sR12, 9 * sizeof(float)); std::memcpy(job_T + 21, t12, 3 * sizeof(float));
+  std::vector<uint32_t> table((size_t)P, 0);
+  n_valid_.assign(2, 0); n_hit_.assign(2, 0);
+  if (!store.host_only() && ctx) {
+    check(ccm_sim3_pair_eval_resident(ctx->get(), store.handle(), 2, keys, nlevels, scale_factors, logScaleFactor, th, P, pos.data(), dmin.data(), dmax.data(), desc.data(),
+                                      2, job_kf, job_K4, job_src, job_T, job_pt0, job_n, table.data(), n_valid_.data(), n_hit_.data(), nullptr),
+          ctx->get(), "ccm_sim3_pair_eval_resident");
+  } else if (sim3_pair_eval_resident_host(store, 2, keys, nlevels, scale_factors, logScaleFactor, th, P, pos.data(), dmin.data(), dmax.data(), desc.data(), 2, job_kf,
+                                          job_K4, job_src, job_T, job_pt0, job_n, table.data(), n_valid_.data(), n_hit_.data(), nullptr)) {
+    throw infrastructure_ex("SearchBySim3Batch: bad arguments");
+  }
+  vn1_.assign((size_t)N1, -1); vn2_.assign((size_t)N2, -1);
+  for (int e = 0; e < P; e++)
+    if ((table[e] >> 29) == FSM_HIT) (e < n1 ? vn1_ : vn2_)[src[e]] = (int32_t)(table[e] & 0xFFFFu);
+  std::vector<int32_t> agreed;
+  n_found_ = ORBmatcher::MutualAgreement(vn1_, vn2_, agreed);
+  matches12_.assign(matches12_in, matches12_in + N1);
+  for (int i = 0; i < N1; i++)
+    if (agreed[i] >= 0) matches12_[i] = agreed[i];
+}
+
 }  // namespace cslam
 
 // ---- C entry points (ccm_host_c.h): the Python test-suite and the drop-in translation units under shim/ ---------------------------------------
@@ -2934,6 +3206,91 @@ void* ccmh_fuse_pose_create_resident(void* store, int device, int K, const int64
     return new cslam::SearchInNeighborsBatch(*static_cast<cslam::KeyFrameStore*>(store), device < 0 ? nullptr : &thread_context(device), K, keys, pose, n_calls, target,
                                              current, pt, n_current, nlevels, scale_factors, inv_level_sigma2, logScaleFactor, th);
   } catch (const std::exception&) { return nullptr; }
+}
+
+// the two projected searches of ComputeSim3 through C: host evaluators, ssm_derive, the two mirrors
+int ccmh_sim3_project_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
+                                const int32_t* cell_off, const int32_t* cell_idx, const float* Scw, const int32_t* skip_off, const uint8_t* feat_skip, int nlevels,
+                                const float* scale_factors, float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist,
+                                const float* max_dist, const uint8_t* pt_desc, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv) {
+  return cslam::sim3_project_eval_host(K, kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off, cell_idx, Scw, skip_off, feat_skip, nlevels, scale_factors,
+                                       logScaleFactor, th, P, pos, normal, min_dist, max_dist, pt_desc, table, n_valid, n_hit, uv);
+}
+int ccmh_sim3_pair_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
+                             const int32_t* cell_off, const int32_t* cell_idx, int nlevels, const float* scale_factors, float logScaleFactor, float th, int P,
+                             const float* pos, const float* min_dist, const float* max_dist, const uint8_t* pt_desc, int J, const int32_t* job_kf, const float* job_K4,
+                             const float* job_src_pose, const float* job_T, const int32_t* job_pt0, const int32_t* job_n, uint32_t* table, int32_t* n_valid,
+                             int32_t* n_hit, float* uv) {
+  return cslam::sim3_pair_eval_host(K, kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off, cell_idx, nlevels, scale_factors, logScaleFactor, th, P, pos, min_dist,
+                                    max_dist, pt_desc, J, job_kf, job_K4, job_src_pose, job_T, job_pt0, job_n, table, n_valid, n_hit, uv);
+}
+int ccmh_sim3_project_eval_resident_host(void* store, int K, const int64_t* keys, const float* Scw, const int32_t* skip_off, const uint8_t* feat_skip, int nlevels,
+                                         const float* scale_factors, float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist,
+                                         const float* max_dist, const uint8_t* pt_desc, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv) {
+  if (!store) return -1;
+  return cslam::sim3_project_eval_resident_host(*static_cast<cslam::KeyFrameStore*>(store), K, keys, Scw, skip_off, feat_skip, nlevels, scale_factors, logScaleFactor, th, P,
+                                                pos, normal, min_dist, max_dist, pt_desc, table, n_valid, n_hit, uv);
+}
+int ccmh_sim3_pair_eval_resident_host(void* store, int K, const int64_t* keys, int nlevels, const float* scale_factors, float logScaleFactor, float th, int P,
+                                      const float* pos, const float* min_dist, const float* max_dist, const uint8_t* pt_desc, int J, const int32_t* job_kf,
+                                      const float* job_K4, const float* job_src_pose, const float* job_T, const int32_t* job_pt0, const int32_t* job_n, uint32_t* table,
+                                      int32_t* n_valid, int32_t* n_hit, float* uv) {
+  if (!store) return -1;
+  return cslam::sim3_pair_eval_resident_host(*static_cast<cslam::KeyFrameStore*>(store), K, keys, nlevels, scale_factors, logScaleFactor, th, P, pos, min_dist, max_dist,
+                                             pt_desc, J, job_kf, job_K4, job_src_pose, job_T, job_pt0, job_n, table, n_valid, n_hit, uv);
+}
+void ccmh_ssm_derive(float s12, const float* R12, const float* t12, float* sR12, float* sR21, float* t21) { ssm_derive(s12, R12, t12, sR12, sR21, t21); }
+void* ccmh_sim3_project_create(void* store, int device, int64_t key, const float* Scw12, const uint8_t* matched0, int nlevels, const float* scale_factors,
+                               float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist,
+                               const uint8_t* pt_desc) {
+  if (!store) return nullptr;
+  try {
+    cslam::Sim3ProjectionSearch::Points pt;
+    pt.P = P; pt.pos = pos; pt.normal = normal; pt.min_dist = min_dist; pt.max_dist = max_dist; pt.desc = pt_desc;
+    return new cslam::Sim3ProjectionSearch(*static_cast<cslam::KeyFrameStore*>(store), device < 0 ? nullptr : &thread_context(device), key, Scw12, pt, matched0, nlevels,
+                                           scale_factors, logScaleFactor, th);
+  } catch (const std::exception&) { return nullptr; }
+}
+int ccmh_sim3_project_table(void* h, uint32_t* table, int32_t* n_valid, int32_t* n_hit) {
+  if (!h) return -1;
+  const cslam::Sim3ProjectionSearch& b = *static_cast<cslam::Sim3ProjectionSearch*>(h);
+  if (table && !b.table().empty()) std::memcpy(table, b.table().data(), b.table().size() * 4);
+  if (n_valid) *n_valid = b.nValid();
+  if (n_hit) *n_hit = b.nHit();
+  return 0;
+}
+int ccmh_sim3_project_resolve(void* h, const uint8_t* skip_now, const int32_t* existing_idx, int n_feat, int32_t* matched, int n_pts, int32_t* best_idx, int32_t* remap) {
+  if (!h) return -1000;
+  try {
+    cslam::Sim3ProjectionSearch& b = *static_cast<cslam::Sim3ProjectionSearch*>(h);
+    if (n_pts != b.points() || n_feat != b.features()) return -1001;
+    std::vector<int32_t> bi, rm;
+    const int n = b.resolve(skip_now, existing_idx, matched, bi, rm);
+    if (n_pts) { std::memcpy(best_idx, bi.data(), bi.size() * 4); std::memcpy(remap, rm.data(), rm.size() * 4); }
+    return n;
+  } catch (const std::exception&) { return -1000; }
+}
+long long ccmh_sim3_project_n_reeval(void* h) { return h ? static_cast<cslam::Sim3ProjectionSearch*>(h)->n_reeval() : -1; }
+void ccmh_sim3_project_destroy(void* h) { delete static_cast<cslam::Sim3ProjectionSearch*>(h); }
+int ccmh_search_by_sim3_resident(void* store, int device, int64_t key1, int64_t key2, int N1, const uint8_t* live1, const float* pos1, const float* min1, const float* max1,
+                                 const uint8_t* desc1, const float* pose1, int N2, const uint8_t* live2, const float* pos2, const float* min2, const float* max2,
+                                 const uint8_t* desc2, const float* pose2, float s12, const float* R12, const float* t12, const int32_t* matches12_in, int nlevels,
+                                 const float* scale_factors, float logScaleFactor, float th, int32_t* matches12, int32_t* vn1, int32_t* vn2, int32_t* n_valid2,
+                                 int32_t* n_hit2) {
+  if (!store) return -1000;
+  try {
+    cslam::SearchBySim3Batch::Side a, b;
+    a.N = N1; a.live = live1; a.pos = pos1; a.min_dist = min1; a.max_dist = max1; a.desc = desc1; a.pose = pose1;
+    b.N = N2; b.live = live2; b.pos = pos2; b.min_dist = min2; b.max_dist = max2; b.desc = desc2; b.pose = pose2;
+    const cslam::SearchBySim3Batch r(*static_cast<cslam::KeyFrameStore*>(store), device < 0 ? nullptr : &thread_context(device), key1, key2, a, b, s12, R12, t12,
+                                     matches12_in, nlevels, scale_factors, logScaleFactor, th);
+    if (matches12 && N1) std::memcpy(matches12, r.matches12().data(), (size_t)N1 * 4);
+    if (vn1 && N1) std::memcpy(vn1, r.vnMatch1().data(), (size_t)N1 * 4);
+    if (vn2 && N2) std::memcpy(vn2, r.vnMatch2().data(), (size_t)N2 * 4);
+    if (n_valid2) std::memcpy(n_valid2, r.nValid().data(), 8);
+    if (n_hit2) std::memcpy(n_hit2, r.nHit().data(), 8);
+    return r.nFound();
+  } catch (const std::exception&) { return -1000; }
 }
 
 int ccmh_search_for_initialization(int device, const float* x1, const float* y1, const int32_t* oct1, const float* a1, const uint8_t* d1, int N1,

@@ -724,6 +724,79 @@ int fuse_pose_eval_resident_host(const KeyFrameStore& store, int K, const int64_
                                  uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv);
 
 // ---------------------------------------------------------------------------------------------------
+// ComputeSim3's two projected searches on keyframes of a store (LoopFinder.cpp:326, :380; MapMatcher.cpp:330, :382).
+// ---------------------------------------------------------------------------------------------------
+// ccm_sim3_project_eval_resident's / ccm_sim3_pair_eval_resident's pairs through csrc/fuse_math.h on the calling thread, on plain keyframe arrays laid out as
+// fuse_sim3_eval_host's (a mask is held to feat_off's feature counts) and on the shadows of a store; -1 where the device entry returns CCM_E_ARG.
+int sim3_project_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
+                           const int32_t* cell_off, const int32_t* cell_idx, const float* Scw, const int32_t* skip_off, const uint8_t* feat_skip, int nlevels,
+                           const float* scale_factors, float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist,
+                           const float* max_dist, const uint8_t* pt_desc, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv);
+int sim3_pair_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
+                        const int32_t* cell_off, const int32_t* cell_idx, int nlevels, const float* scale_factors, float logScaleFactor, float th, int P, const float* pos,
+                        const float* min_dist, const float* max_dist, const uint8_t* pt_desc, int J, const int32_t* job_kf, const float* job_K4, const float* job_src_pose,
+                        const float* job_T, const int32_t* job_pt0, const int32_t* job_n, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv);
+int sim3_project_eval_resident_host(const KeyFrameStore& store, int K, const int64_t* keys, const float* Scw, const int32_t* skip_off, const uint8_t* feat_skip, int nlevels,
+                                    const float* scale_factors, float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist,
+                                    const float* max_dist, const uint8_t* pt_desc, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv);
+int sim3_pair_eval_resident_host(const KeyFrameStore& store, int K, const int64_t* keys, int nlevels, const float* scale_factors, float logScaleFactor, float th, int P,
+                                 const float* pos, const float* min_dist, const float* max_dist, const uint8_t* pt_desc, int J, const int32_t* job_kf, const float* job_K4,
+                                 const float* job_src_pose, const float* job_T, const int32_t* job_pt0, const int32_t* job_n, uint32_t* table, int32_t* n_valid,
+                                 int32_t* n_hit, float* uv);
+
+// ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (ORBmatcher.cpp:308-446) on one key of a store.  The constructor evaluates every point against
+// the INITIAL vpMatched (matched0[f] != 0: vpMatched[f] is set) in ONE ccm_sim3_project_eval_resident call, or on the calling thread when the store is host-only or
+// ctx == nullptr; with a context a device error throws.  resolve replays the reference's loop in point order.  While that loop runs the mask only grows (a point
+// that is accepted claims its feature, :439), and a growing mask changes the answer of a point in one case alone: its best candidate has been claimed.  (A best
+// above TH_LOW stays above it when candidates leave; every other status finds nothing either way.)  So the table word is the answer except for a status-7 word
+// whose feature an earlier point of THIS call has claimed; such a point is evaluated again on the calling thread with the current mask.
+class Sim3ProjectionSearch {
+ public:
+  typedef SearchAndFuseBatch::Points Points;
+  Sim3ProjectionSearch(KeyFrameStore& store, HipContext* ctx, int64_t key, const float* Scw12, const Points& pts, const uint8_t* matched0, int nlevels,
+                       const float* scale_factors, float logScaleFactor, float th);
+  // skip_now[i] != 0 (nullable): the reference would `continue` now (pMP->isBad() || spAlreadyFound.count(pMP)).  existing_idx[i] >= 0 (nullable): the keyframe
+  // observes point i already (GetIndexInKeyFrame, :415); such a point claims nothing and is not counted, its best feature comes back in remap[i] and GetMapPoint /
+  // RemapMapPointMatch (:420-434) stay the caller's.  matched (features() entries, in / out): >= 0 where vpMatched is set, on entry as matched0 said; point i's
+  // claim writes i.  bestIdx[i]: the feature point i claimed, or -1.  Returns nmatches.
+  int resolve(const uint8_t* skip_now, const int32_t* existing_idx, int32_t* matched, std::vector<int32_t>& bestIdx, std::vector<int32_t>& remap);
+  int points() const { return P_; }
+  int features() const { return N_; }
+  const std::vector<uint32_t>& table() const { return table_; }   // as evaluated at construction
+  int nValid() const { return n_valid_; }
+  int nHit() const { return n_hit_; }
+  long long n_reeval() const { return n_reeval_; }                 // points evaluated again by resolve because their feature had been claimed
+ private:
+  int P_ = 0, N_ = 0, n_valid_ = 0, n_hit_ = 0;
+  FuseScene scene_;
+  std::vector<uint32_t> table_;
+  long long n_reeval_ = 0;
+};
+
+// ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (ORBmatcher.cpp:1124-1348) on two keys of a store.  A side holds, per feature slot of its
+// keyframe, live (pMP && !pMP->isBad()), the point's position, distance bounds and descriptor (read where live), and the keyframe's pose R (9, row-major), t (3).
+// matches12_in[i] (N1 entries): -1 where vpMatches12[i] is null, otherwise the index of that point in keyframe 2 (GetIndexInKeyFrame(pKF2); any value outside
+// 0 .. N2 - 1 where it has none).  The constructor computes vbAlreadyMatched1 / 2 (:1154-1164), packs the live unmatched points of both sides into two jobs, makes
+// ONE ccm_sim3_pair_eval_resident call (the host evaluation when the store is host-only or ctx == nullptr; with a context a device error throws), unpacks
+// vnMatch1 / 2 and runs ORBmatcher::MutualAgreement.  Both directions project with keyframe 1's intrinsics, as the reference does (:1127-1130).
+class SearchBySim3Batch {
+ public:
+  struct Side { int N = 0; const uint8_t* live = nullptr; const float* pos = nullptr; const float* min_dist = nullptr; const float* max_dist = nullptr;
+                const uint8_t* desc = nullptr; const float* pose = nullptr; };
+  SearchBySim3Batch(KeyFrameStore& store, HipContext* ctx, int64_t key1, int64_t key2, const Side& kf1, const Side& kf2, float s12, const float* R12, const float* t12,
+                    const int32_t* matches12_in, int nlevels, const float* scale_factors, float logScaleFactor, float th);
+  int nFound() const { return n_found_; }
+  const std::vector<int32_t>& matches12() const { return matches12_; }   // N1: the entry state, and the KF2 feature of every new match
+  const std::vector<int32_t>& vnMatch1() const { return vn1_; }
+  const std::vector<int32_t>& vnMatch2() const { return vn2_; }
+  const std::vector<int32_t>& nValid() const { return n_valid_; }        // per direction
+  const std::vector<int32_t>& nHit() const { return n_hit_; }
+ private:
+  int n_found_ = 0;
+  std::vector<int32_t> matches12_, vn1_, vn2_, n_valid_, n_hit_;
+};
+
+// ---------------------------------------------------------------------------------------------------
 // Optimizer — cslam/include/cslam/Optimizer.h:84-112 (numerics; graph walking is the integrator's glue)
 // ---------------------------------------------------------------------------------------------------
 struct BAProblem {   // owning, f64 like g2o; filled from KeyFrames / MapPoints via Converter (Converter.cc:40-119)

@@ -165,6 +165,23 @@ int ccmh_fuse_sim3_eval_resident_host(void* store, int K, const int64_t* keys, c
 int ccmh_fuse_pose_eval_resident_host(void* store, int K, const int64_t* keys, const float* pose, int nlevels, const float* scale_factors, const float* inv_level_sigma2, float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc, int J, const int32_t* job_kf, const int32_t* job_pt0, const int32_t* job_n, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv);
 void* ccmh_fuse_sim3_create_resident(void* store, int device, int K, const int64_t* keys, const float* Scw, int nlevels, const float* scale_factors, float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc);
 void* ccmh_fuse_pose_create_resident(void* store, int device, int K, const int64_t* keys, const float* pose, int nlevels, const float* scale_factors, const float* inv_level_sigma2, float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc, int n_calls, const int32_t* target, int current, int n_current);
+/* ComputeSim3's two projected searches.  eval_host / eval_resident_host: the arguments of ccm_sim3_project_eval_resident /
+ * ccm_sim3_pair_eval_resident after the context through csrc/fuse_math.h on the calling thread, on flat keyframe arrays (as ccmh_fuse_sim3_eval_host) or on a store's
+ * shadows; 0, or -1 for the CCM_E_ARG cases.  ccmh_ssm_derive: ORBmatcher.cpp:1141-1143.  ccmh_sim3_project_*: cslam::Sim3ProjectionSearch (device < 0: the host
+ * evaluation; create returns NULL on bad arguments, a key that is not live or a device error; resolve returns nmatches, -1000 on an error, -1001 when n_pts / n_feat are
+ * not the search's).  ccmh_search_by_sim3_resident: cslam::SearchBySim3Batch in one call; returns nFound, -1000 on bad arguments or a device error; matches12 (N1),
+ * vn1 (N1), vn2 (N2), n_valid2 / n_hit2 (2) are nullable. */
+int ccmh_sim3_project_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc, const int32_t* cell_off, const int32_t* cell_idx, const float* Scw, const int32_t* skip_off, const uint8_t* feat_skip, int nlevels, const float* scale_factors, float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv);
+int ccmh_sim3_pair_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc, const int32_t* cell_off, const int32_t* cell_idx, int nlevels, const float* scale_factors, float logScaleFactor, float th, int P, const float* pos, const float* min_dist, const float* max_dist, const uint8_t* pt_desc, int J, const int32_t* job_kf, const float* job_K4, const float* job_src_pose, const float* job_T, const int32_t* job_pt0, const int32_t* job_n, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv);
+int ccmh_sim3_project_eval_resident_host(void* store, int K, const int64_t* keys, const float* Scw, const int32_t* skip_off, const uint8_t* feat_skip, int nlevels, const float* scale_factors, float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv);
+int ccmh_sim3_pair_eval_resident_host(void* store, int K, const int64_t* keys, int nlevels, const float* scale_factors, float logScaleFactor, float th, int P, const float* pos, const float* min_dist, const float* max_dist, const uint8_t* pt_desc, int J, const int32_t* job_kf, const float* job_K4, const float* job_src_pose, const float* job_T, const int32_t* job_pt0, const int32_t* job_n, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv);
+void ccmh_ssm_derive(float s12, const float* R12, const float* t12, float* sR12, float* sR21, float* t21);
+void* ccmh_sim3_project_create(void* store, int device, int64_t key, const float* Scw12, const uint8_t* matched0, int nlevels, const float* scale_factors, float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc);
+int ccmh_sim3_project_table(void* h, uint32_t* table, int32_t* n_valid, int32_t* n_hit);
+int ccmh_sim3_project_resolve(void* h, const uint8_t* skip_now, const int32_t* existing_idx, int n_feat, int32_t* matched, int n_pts, int32_t* best_idx, int32_t* remap);
+long long ccmh_sim3_project_n_reeval(void* h);
+void ccmh_sim3_project_destroy(void* h);
+int ccmh_search_by_sim3_resident(void* store, int device, int64_t key1, int64_t key2, int N1, const uint8_t* live1, const float* pos1, const float* min1, const float* max1, const uint8_t* desc1, const float* pose1, int N2, const uint8_t* live2, const float* pos2, const float* min2, const float* max2, const uint8_t* desc2, const float* pose2, float s12, const float* R12, const float* t12, const int32_t* matches12_in, int nlevels, const float* scale_factors, float logScaleFactor, float th, int32_t* matches12, int32_t* vn1, int32_t* vn2, int32_t* n_valid2, int32_t* n_hit2);
 
 #ifdef __cplusplus
 }

@@ -679,6 +679,33 @@ int  ccm_fuse_pose_eval_resident(ccm_ctx* ctx, ccm_kfstore* store, int K, const 
                                  const int32_t* job_kf, const int32_t* job_pt0, const int32_t* job_n, uint32_t* table /* sum(job_n) */,
                                  int32_t* n_valid /* J */, int32_t* n_hit /* J */, float* uv /* 2 sum(job_n) or NULL */);
 
+/* ---- ComputeSim3's two projected searches on keyframes of the store (the lines are csrc/fuse_math.h) -----------------------------------------
+ * ccm_sim3_project_eval_resident: ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (cslam/src/ORBmatcher.cpp:308-446) for every (keyframe, point)
+ * pair on the INITIAL vpMatched.  The pair is ccm_fuse_sim3_eval's (Sim3 decomposition, the four gates, PredictScale, the window, levels level - 1 .. level, TH_LOW)
+ * with one rule more: feature f of keyframe k with feat_skip[skip_off[k] + f] != 0 (vpMatched[f] set) is skipped in the arg-min (:393).  A skipped feature in the
+ * window still makes the window non-empty; when every candidate is skipped or off-level the status is 5.  What the reference's loop changes while it runs (the
+ * claims of the points before) is the caller's to replay (cslam::Sim3ProjectionSearch, host/ccm_host.h).  Arguments, outputs, packing and refusals as
+ * ccm_fuse_sim3_eval_resident; additionally CCM_E_ARG, with nothing launched, for a skip_off that does not start at 0 or decreases, a mask whose length
+ * skip_off[k + 1] - skip_off[k] is not the feature count of key k in the store, and a null feat_skip with skip_off[K] > 0. */
+int  ccm_sim3_project_eval_resident(ccm_ctx* ctx, ccm_kfstore* store, int K, const int64_t* keys /* K */, const float* Scw /* 12 K */,
+                                    const int32_t* skip_off /* K + 1 */, const uint8_t* feat_skip, int nlevels, const float* scale_factors, float logScaleFactor,
+                                    float th, int P, const float* pos /* 3 P */, const float* normal /* 3 P */, const float* min_dist, const float* max_dist,
+                                    const uint8_t* pt_desc /* 32 P */, uint32_t* table /* K P */, int32_t* n_valid /* K */, int32_t* n_hit /* K */,
+                                    float* uv /* 2 K P or NULL */);
+/* ccm_sim3_pair_eval_resident: the two directional searches of ORBmatcher::SearchBySim3 (ORBmatcher.cpp:1124-1348) as a job list in ccm_fuse_pose_eval's layout;
+ * one SearchBySim3 call is two jobs.  Job j projects the points job_pt0[j] .. + job_n[j] into the TARGET keyframe keys[job_kf[j]]:
+ * p3Dc_b = sR_ba * (R_aw * X + t_aw) + t_ba with job_src_pose + 12 j = R_aw (9, row-major), t_aw (3) of the SOURCE keyframe and job_T + 12 j = sR_ba (9), t_ba (3)
+ * (sR21, t21 for the direction 1 -> 2; sR12, t12 for 2 -> 1; ssm_derive of csrc/fuse_math.h makes them of s12, R12, t12).  job_K4 + 4 j = fx fy cx cy of the
+ * projection: the reference reads them from pKF1 for BOTH directions (:1127-1130), so both jobs of a call carry pKF1's; the image bounds, the grid and the window are
+ * the target's.  Depth, IsInImage, the range 0.8 min .. 1.2 max on the norm of the camera point, PredictScale, the window, levels level - 1 .. level, threshold
+ * TH_HIGH = 100 (status 6: best above it); no viewing-angle gate (status 3 does not occur), no skip mask, no normals.  Outputs and refusals as
+ * ccm_fuse_pose_eval_resident; additionally CCM_E_ARG for null job_K4 / job_src_pose / job_T with J > 0. */
+int  ccm_sim3_pair_eval_resident(ccm_ctx* ctx, ccm_kfstore* store, int K, const int64_t* keys /* K */, int nlevels, const float* scale_factors, float logScaleFactor,
+                                 float th, int P, const float* pos /* 3 P */, const float* min_dist, const float* max_dist, const uint8_t* pt_desc /* 32 P */, int J,
+                                 const int32_t* job_kf, const float* job_K4 /* 4 J */, const float* job_src_pose /* 12 J */, const float* job_T /* 12 J */,
+                                 const int32_t* job_pt0, const int32_t* job_n, uint32_t* table /* sum(job_n) */, int32_t* n_valid /* J */, int32_t* n_hit /* J */,
+                                 float* uv /* 2 sum(job_n) or NULL */);
+
 #ifdef __cplusplus
 }
 #endif
