@@ -181,48 +181,49 @@ __global__ __launch_bounds__(FPM_TILE) void sim3_pair_resident_kernel(FuseArgs a
 typedef std::chrono::steady_clock Clock;
 double us_between(Clock::time_point x, Clock::time_point y) { return std::chrono::duration<double, std::micro>(y - x).count(); }
 
-// The host side of the upload for the segments FuseSim3Block and FusePoseBlock have in common (same member names), and the kernels' view of the block.  What is a
-// stage's own (pose; job, tile and inv_sigma2) the entry point writes itself.
-template <class Block>
-FuseArgs fuse_stage_inputs(const Block& b, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
-                           const int32_t* cell_off, const int32_t* cell_idx, int nlevels, const float* scale_factors, float logScaleFactor, float th, const float* pos,
-                           const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc) {
-  b.put(b.kdesc, feat_desc); b.put(b.pdesc, pt_desc); b.put(b.rec, kf_rec);
-  b.put(b.feat_off, feat_off); b.put(b.cell_off, cell_off); b.put(b.kxy, feat_xy);
-  uint16_t* h_idx = b.up(b.cell_idx);
-  for (size_t f = 0; f < b.cell_idx.count; f++) h_idx[f] = (uint16_t)cell_idx[f];
-  b.put(b.koct, feat_octave); b.put(b.scale_factors, scale_factors);
-  b.put(b.pos, pos); b.put(b.normal, normal); b.put(b.dmin, min_dist); b.put(b.dmax, max_dist);
+// what a caller passes to every form: the level tables and scalars, the points, the outputs.  inv_sigma2 and normal: null where the form has no such segment.
+struct FuseCall {
+  int nlevels; const float *scale_factors, *inv_sigma2; float logsf, th;
+  const float *pos, *normal, *dmin, *dmax; const uint8_t* pt_desc;
+  uint32_t* table; int32_t *n_valid, *n_hit; float* uv;
+};
+// the keyframes: the caller's flat arrays (st == nullptr), or the slots of a store, which fuse_store_slots made of the keys under the reader lock the caller holds
+struct FuseKfs {
+  const float* rec; const int32_t* feat_off; const float* xy; const uint8_t *oct, *desc; const int32_t *cell_off, *cell_idx;
+  const ccm_kfstore* st; const int32_t* slots;
+};
+
+// The host side of the upload for everything but the form's own segments (pose; job and tile; the masks), and the kernels' view of the block.  A segment the form does
+// not have has no elements: put() copies nothing, and what the kernel's pointer to it holds does not matter.
+FuseArgs fuse_stage_inputs(const FuseBlock& b, const FuseCall& c, const FuseKfs& kf) {
   FuseArgs a = {};
-  a.nlevels = nlevels; a.th = th; a.logsf = logScaleFactor;
-  a.rec = b.dev(b.rec); a.pose = b.dev(b.pose); a.kxy = b.dev(b.kxy); a.scale_factors = b.dev(b.scale_factors);
-  a.pos = b.dev(b.pos); a.normal = b.dev(b.normal); a.dmin = b.dev(b.dmin); a.dmax = b.dev(b.dmax);
-  a.feat_off = b.dev(b.feat_off); a.cell_off = b.dev(b.cell_off); a.cell_idx = b.dev(b.cell_idx);
-  a.koct = b.dev(b.koct); a.kdesc = b.dev(b.kdesc); a.pdesc = b.dev(b.pdesc);
+  if (kf.st) {
+    b.put(b.slot, kf.slots);
+    a.rec = kf.st->d_rec; a.kxy = kf.st->d_xy; a.cell_off = kf.st->d_cell_off; a.cell_idx = kf.st->d_cell_idx; a.koct = kf.st->d_oct; a.kdesc = kf.st->d_desc;
+    a.slot = b.dev(b.slot); a.stride = kf.st->stride;
+  } else {
+    b.put(b.kdesc, kf.desc); b.put(b.rec, kf.rec); b.put(b.feat_off, kf.feat_off); b.put(b.cell_off, kf.cell_off); b.put(b.kxy, kf.xy); b.put(b.koct, kf.oct);
+    uint16_t* h_idx = b.up(b.cell_idx);
+    for (size_t f = 0; f < b.cell_idx.count; f++) h_idx[f] = (uint16_t)kf.cell_idx[f];
+    a.rec = b.dev(b.rec); a.kxy = b.dev(b.kxy); a.feat_off = b.dev(b.feat_off); a.cell_off = b.dev(b.cell_off); a.cell_idx = b.dev(b.cell_idx);
+    a.koct = b.dev(b.koct); a.kdesc = b.dev(b.kdesc);
+  }
+  b.put(b.pdesc, c.pt_desc); b.put(b.scale_factors, c.scale_factors); b.put(b.inv_sigma2, c.inv_sigma2);
+  b.put(b.pos, c.pos); b.put(b.normal, c.normal); b.put(b.dmin, c.dmin); b.put(b.dmax, c.dmax);
+  a.nlevels = c.nlevels; a.th = c.th; a.logsf = c.logsf;
+  a.P = (int)b.s.P; a.tiles = (int)((b.s.P + FPM_TILE - 1) / FPM_TILE);
+  a.pose = b.dev(b.pose); a.scale_factors = b.dev(b.scale_factors); a.inv_sigma2 = b.dev(b.inv_sigma2);
+  a.pos = b.dev(b.pos); a.normal = b.dev(b.normal); a.dmin = b.dev(b.dmin); a.dmax = b.dev(b.dmax); a.pdesc = b.dev(b.pdesc);
+  a.job = b.dev(b.job); a.tile = b.dev(b.tile); a.skip = b.dev(b.skip); a.skip_off = b.dev(b.skip_off);
   a.table = b.dev(b.table); a.n_valid = b.dev(b.n_valid); a.n_hit = b.dev(b.n_hit);
   a.uv = b.uv.count ? b.dev(b.uv) : nullptr;
   return a;
 }
 
-// The same for the resident blocks: the points and the per-call table from the caller, the keyframes' arrays from the store, and the slot list fuse_store_slots
-// made of the keys.  normal_seg == nullptr: a block without normals (Sim3PairResidentBlock).  The caller holds the store's reader lock.
-template <class Block>
-FuseArgs fuse_resident_inputs(const Block& b, const ccm_kfstore* st, const std::vector<int32_t>& slots, int nlevels, const float* scale_factors, float logScaleFactor,
-                              float th, const float* pos, const StagedSeg<float>* normal_seg, const float* normal, const float* min_dist, const float* max_dist,
-                              const uint8_t* pt_desc) {
-  if (b.slot.count) memcpy(b.up(b.slot), slots.data(), b.slot.count * sizeof(int32_t));
-  b.put(b.pdesc, pt_desc); b.put(b.scale_factors, scale_factors);
-  b.put(b.pos, pos); b.put(b.dmin, min_dist); b.put(b.dmax, max_dist);
-  if (normal_seg) b.put(*normal_seg, normal);
-  FuseArgs a = {};
-  a.nlevels = nlevels; a.th = th; a.logsf = logScaleFactor;
-  a.rec = st->d_rec; a.kxy = st->d_xy; a.cell_off = st->d_cell_off; a.cell_idx = st->d_cell_idx; a.koct = st->d_oct; a.kdesc = st->d_desc;
-  a.slot = b.dev(b.slot); a.stride = st->stride;
-  a.pose = b.dev(b.pose); a.scale_factors = b.dev(b.scale_factors);
-  a.pos = b.dev(b.pos); a.normal = normal_seg ? b.dev(*normal_seg) : nullptr; a.dmin = b.dev(b.dmin); a.dmax = b.dev(b.dmax); a.pdesc = b.dev(b.pdesc);
-  a.table = b.dev(b.table); a.n_valid = b.dev(b.n_valid); a.n_hit = b.dev(b.n_hit);
-  a.uv = b.uv.count ? b.dev(b.uv) : nullptr;
-  return a;
+int fuse_store_ok(ccm_ctx* ctx, const ccm_kfstore* st, const char* me) {
+  if (!st) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + "NULL store");
+  if (st->device != ctx->device) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + "the context is on another device than the store");
+  return CCM_OK;
 }
 
 // keys -> slots under the caller's reader lock; CCM_E_ARG for a key that is not live
@@ -236,37 +237,60 @@ int fuse_store_slots(ccm_ctx* ctx, const ccm_kfstore* st, int K, const int64_t* 
   return CCM_OK;
 }
 
-// the pose form's job and tile segments from the (validated) job arrays
-template <class Block>
-void fuse_pose_jobs(const Block& b, int J, const int32_t* job_kf, const int32_t* job_pt0, const int32_t* job_n) {
+// the form's own segments.  The Sim3 forms' pose: the decomposed Scw of every keyframe
+void fuse_pack_scw(const FuseBlock& b, const float* Scw) {
+  float* h_pose = b.up(b.pose);
+  for (size_t k = 0; k < b.s.K; k++) fsm_decompose_scw(Scw + 12 * k, h_pose + FSM_POSE_FLOATS * k);
+}
+// the job forms' job and tile segments from the (validated) job arrays
+void fuse_pack_jobs(const FuseBlock& b, const int32_t* job_kf, const int32_t* job_pt0, const int32_t* job_n) {
   int32_t* h_job = b.up(b.job);
   int32_t* h_tile = b.up(b.tile);
   int32_t out0 = 0;
   size_t t = 0;
-  for (int j = 0; j < J; j++) {
-    h_job[FPM_JOB_INTS * (size_t)j] = job_kf[j]; h_job[FPM_JOB_INTS * (size_t)j + 1] = job_pt0[j];
-    h_job[FPM_JOB_INTS * (size_t)j + 2] = job_n[j]; h_job[FPM_JOB_INTS * (size_t)j + 3] = out0;
-    for (int32_t e = 0; e < job_n[j]; e += FPM_TILE, t++) { h_tile[2 * t] = j; h_tile[2 * t + 1] = e; }
+  for (size_t j = 0; j < b.s.J; j++) {
+    h_job[FPM_JOB_INTS * j] = job_kf[j]; h_job[FPM_JOB_INTS * j + 1] = job_pt0[j];
+    h_job[FPM_JOB_INTS * j + 2] = job_n[j]; h_job[FPM_JOB_INTS * j + 3] = out0;
+    for (int32_t e = 0; e < job_n[j]; e += FPM_TILE, t++) { h_tile[2 * t] = (int32_t)j; h_tile[2 * t + 1] = e; }
     out0 += job_n[j];
   }
 }
 
-int fuse_store_ok(ccm_ctx* ctx, const ccm_kfstore* st, const char* me) {
-  if (!st) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + "NULL store");
-  if (st->device != ctx->device) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + "the context is on another device than the store");
+// One call from the validated arguments on: the counters zeroed and nothing launched for empty work; otherwise the block, the upload (pack: the form's own segments),
+// one workgroup per tile of a job or per (keyframe, tile of points), the download and the caller's outputs.  A resident form's caller holds the store's reader lock
+// until this returns.  CCM_DBG=fuse: the call's three host phases on stderr as "[tag] ..." (scripts/fuse_sim3_profile.py, fuse_pose_profile.py and kfstore_profile.py
+// read them); the clock is read whether or not they are printed.
+template <class Pack>
+int fuse_stage_run(ccm_ctx* ctx, const char* me, const char* tag, void (*kernel)(FuseArgs), const FuseShape& s, const FuseCall& c, const FuseKfs& kf, Pack pack) {
+  FuseBlock b(s);
+  for (size_t i = 0; i < b.C; i++) c.n_valid[i] = c.n_hit[i] = 0;
+  if (b.W == 0) return CCM_OK;
+  if (int rc = ccm_staged_begin(ctx, b, me)) return rc;
+  const Clock::time_point t0 = Clock::now();
+  FuseArgs a = fuse_stage_inputs(b, c, kf);
+  pack(b);
+  const Clock::time_point t1 = Clock::now();
+  if (int rc = ccm_staged_upload(ctx, b)) return rc;
+  // K * tiles <= K * P + K workgroups: K * P <= INT32_MAX holds, and so does the grid limit for every K and P a map has; the jobs' tiles fpm_check_jobs bounds
+  const uint64_t groups = b.jobs ? (uint64_t)s.T : (uint64_t)s.K * (uint64_t)a.tiles;
+  if (groups > (uint64_t)INT32_MAX) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + "too many workgroups");
+  hipLaunchKernelGGL(kernel, dim3((unsigned)groups), dim3(FPM_TILE), 0, ctx->stream, a);
+  CCM_HIP_CHECK(ctx, hipGetLastError());
+  if (int rc = ccm_staged_download(ctx, b)) return rc;
+  const Clock::time_point t2 = Clock::now();
+  b.get(b.n_valid, c.n_valid); b.get(b.n_hit, c.n_hit); b.get(b.table, c.table);
+  if (c.uv) b.get(b.uv, c.uv);
+  if (ccm_dbg("fuse")) {
+    const double unpack_us = us_between(t2, Clock::now());
+    char jobs[48] = "";
+    if (b.jobs) snprintf(jobs, sizeof jobs, " J=%zu pairs=%zu", s.J, s.N);
+    fprintf(stderr, "[%s] K=%zu P=%zu%s pack_us=%.1f device_us=%.1f unpack_us=%.1f up_bytes=%zu down_bytes=%zu\n", tag, s.K, s.P, jobs, us_between(t0, t1),
+            us_between(t1, t2), unpack_us, b.up_bytes(), b.down_bytes());
+  }
   return CCM_OK;
 }
 
-// after the launch: the download and the caller's outputs.  Returns when the device was done through *t2.
-template <class Block>
-int fuse_stage_outputs(ccm_ctx* ctx, const Block& b, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv, Clock::time_point* t2) {
-  CCM_HIP_CHECK(ctx, hipGetLastError());
-  if (int rc = ccm_staged_download(ctx, b)) return rc;
-  *t2 = Clock::now();
-  b.get(b.n_valid, n_valid); b.get(b.n_hit, n_hit); b.get(b.table, table);
-  if (uv) b.get(b.uv, uv);
-  return CCM_OK;
-}
+#define FUSE_REFUSE(why) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + (why))
 
 }  // namespace
 
@@ -276,34 +300,14 @@ extern "C" int ccm_fuse_sim3_eval(ccm_ctx* ctx, int K, const float* kf_rec, cons
                                   const float* max_dist, const uint8_t* pt_desc, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv) {
   if (!ctx) return CCM_E_ARG;
   const char* const me = "ccm_fuse_sim3_eval: ";
-  if (const char* why = fsm_check_args(K, P, feat_off, cell_off, cell_idx, nlevels, th)) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + why);
+  if (const char* why = fsm_check_args(K, P, feat_off, cell_off, cell_idx, nlevels, th)) FUSE_REFUSE(why);
   const size_t F = K ? (size_t)feat_off[K] : 0;
-  if (!scale_factors || (K > 0 && (!kf_rec || !Scw || !n_valid || !n_hit)) || (P > 0 && (!pos || !normal || !min_dist || !max_dist || !pt_desc)) ||
-      (K > 0 && P > 0 && !table) || (F && (!feat_xy || !feat_octave || !feat_desc)))
-    return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + "null pointers");
-  for (int k = 0; k < K; k++) n_valid[k] = n_hit[k] = 0;
-  if (K == 0 || P == 0) return CCM_OK;
-  FuseSim3Block b((size_t)K, F, (size_t)P, (size_t)nlevels, uv != nullptr);
-  if (int rc = ccm_staged_begin(ctx, b, me)) return rc;
-  // CCM_DBG=fuse: the call's three host phases on stderr (scripts/fuse_sim3_profile.py reads them); the clock is read whether or not they are printed
-  const Clock::time_point t0 = Clock::now();
-  FuseArgs a = fuse_stage_inputs(b, kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off, cell_idx, nlevels, scale_factors, logScaleFactor, th, pos, normal,
-                                 min_dist, max_dist, pt_desc);
-  float* h_pose = b.up(b.pose);
-  for (int k = 0; k < K; k++) fsm_decompose_scw(Scw + 12 * (size_t)k, h_pose + FSM_POSE_FLOATS * (size_t)k);
-  const Clock::time_point t1 = Clock::now();
-  if (int rc = ccm_staged_upload(ctx, b)) return rc;
-  a.P = P; a.tiles = (P + FPM_TILE - 1) / FPM_TILE;
-  // K * tiles <= K * P + K workgroups: K * P <= INT32_MAX holds, and so does the grid limit for every K and P a map has
-  const uint64_t groups = (uint64_t)K * (uint64_t)a.tiles;
-  if (groups > (uint64_t)INT32_MAX) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + "too many workgroups");
-  hipLaunchKernelGGL(fuse_sim3_kernel, dim3((unsigned)groups), dim3(FPM_TILE), 0, ctx->stream, a);
-  Clock::time_point t2;
-  if (int rc = fuse_stage_outputs(ctx, b, table, n_valid, n_hit, uv, &t2)) return rc;
-  if (ccm_dbg("fuse"))
-    fprintf(stderr, "[fuse] K=%d P=%d pack_us=%.1f device_us=%.1f unpack_us=%.1f up_bytes=%zu down_bytes=%zu\n", K, P, us_between(t0, t1), us_between(t1, t2),
-            us_between(t2, Clock::now()), b.up_bytes(), b.down_bytes());
-  return CCM_OK;
+  if (const char* why = fsm_check_kf_pointers(K, P, kf_rec, Scw, scale_factors, pos, normal, min_dist, max_dist, pt_desc, table, n_valid, n_hit,
+                                              fsm_feats_ok(F, feat_xy, feat_octave, feat_desc)))
+    FUSE_REFUSE(why);
+  return fuse_stage_run(ctx, me, "fuse", fuse_sim3_kernel, {FB_FLAT, (size_t)K, F, (size_t)P, (size_t)nlevels, 0, 0, 0, 0, uv != nullptr},
+                        {nlevels, scale_factors, nullptr, logScaleFactor, th, pos, normal, min_dist, max_dist, pt_desc, table, n_valid, n_hit, uv},
+                        {kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off, cell_idx, nullptr, nullptr}, [&](const FuseBlock& b) { fuse_pack_scw(b, Scw); });
 }
 
 extern "C" int ccm_fuse_pose_eval(ccm_ctx* ctx, int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave,
@@ -313,33 +317,18 @@ extern "C" int ccm_fuse_pose_eval(ccm_ctx* ctx, int K, const float* kf_rec, cons
                                   const int32_t* job_pt0, const int32_t* job_n, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv) {
   if (!ctx) return CCM_E_ARG;
   const char* const me = "ccm_fuse_pose_eval: ";
-  if (const char* why = fsm_check_args(K, P, feat_off, cell_off, cell_idx, nlevels, th)) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + why);
+  if (const char* why = fsm_check_args(K, P, feat_off, cell_off, cell_idx, nlevels, th)) FUSE_REFUSE(why);
   int64_t total = 0, tiles = 0;
-  if (const char* why = fpm_check_jobs(J, K, P, job_kf, job_pt0, job_n, &total, &tiles)) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + why);
+  if (const char* why = fpm_check_jobs(J, K, P, job_kf, job_pt0, job_n, &total, &tiles)) FUSE_REFUSE(why);
   const size_t F = K ? (size_t)feat_off[K] : 0;
-  if (!scale_factors || !inv_level_sigma2 || (K > 0 && (!kf_rec || !pose)) || (J > 0 && (!n_valid || !n_hit)) ||
-      (P > 0 && (!pos || !normal || !min_dist || !max_dist || !pt_desc)) || (total > 0 && !table) || (F && (!feat_xy || !feat_octave || !feat_desc)))
-    return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + "null pointers");
-  for (int j = 0; j < J; j++) n_valid[j] = n_hit[j] = 0;
-  if (total == 0) return CCM_OK;
-  FusePoseBlock b((size_t)K, F, (size_t)P, (size_t)nlevels, (size_t)J, (size_t)tiles, (size_t)total, uv != nullptr);
-  if (int rc = ccm_staged_begin(ctx, b, me)) return rc;
-  // CCM_DBG=fuse: the call's three host phases on stderr (scripts/fuse_pose_profile.py reads them); the clock is read whether or not they are printed
-  const Clock::time_point t0 = Clock::now();
-  FuseArgs a = fuse_stage_inputs(b, kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off, cell_idx, nlevels, scale_factors, logScaleFactor, th, pos, normal,
-                                 min_dist, max_dist, pt_desc);
-  b.put(b.pose, pose); b.put(b.inv_sigma2, inv_level_sigma2);
-  fuse_pose_jobs(b, J, job_kf, job_pt0, job_n);
-  const Clock::time_point t1 = Clock::now();
-  if (int rc = ccm_staged_upload(ctx, b)) return rc;
-  a.inv_sigma2 = b.dev(b.inv_sigma2); a.job = b.dev(b.job); a.tile = b.dev(b.tile);
-  hipLaunchKernelGGL(fuse_pose_kernel, dim3((unsigned)tiles), dim3(FPM_TILE), 0, ctx->stream, a);
-  Clock::time_point t2;
-  if (int rc = fuse_stage_outputs(ctx, b, table, n_valid, n_hit, uv, &t2)) return rc;
-  if (ccm_dbg("fuse"))
-    fprintf(stderr, "[fuse_pose] K=%d P=%d J=%d pairs=%lld pack_us=%.1f device_us=%.1f unpack_us=%.1f up_bytes=%zu down_bytes=%zu\n", K, P, J, (long long)total,
-            us_between(t0, t1), us_between(t1, t2), us_between(t2, Clock::now()), b.up_bytes(), b.down_bytes());
-  return CCM_OK;
+  if (const char* why = fsm_check_job_pointers(K, P, J, total, true, kf_rec, pose, scale_factors, inv_level_sigma2, pos, normal, min_dist, max_dist, pt_desc, table,
+                                               n_valid, n_hit, fsm_feats_ok(F, feat_xy, feat_octave, feat_desc)))
+    FUSE_REFUSE(why);
+  return fuse_stage_run(ctx, me, "fuse_pose", fuse_pose_kernel,
+                        {FB_FLAT | FB_JOBS | FB_CHI2, (size_t)K, F, (size_t)P, (size_t)nlevels, (size_t)J, (size_t)tiles, (size_t)total, 0, uv != nullptr},
+                        {nlevels, scale_factors, inv_level_sigma2, logScaleFactor, th, pos, normal, min_dist, max_dist, pt_desc, table, n_valid, n_hit, uv},
+                        {kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off, cell_idx, nullptr, nullptr},
+                        [&](const FuseBlock& b) { b.put(b.pose, pose); fuse_pack_jobs(b, job_kf, job_pt0, job_n); });
 }
 
 extern "C" int ccm_fuse_sim3_eval_resident(ccm_ctx* ctx, ccm_kfstore* st, int K, const int64_t* keys, const float* Scw, int nlevels, const float* scale_factors,
@@ -348,32 +337,14 @@ extern "C" int ccm_fuse_sim3_eval_resident(ccm_ctx* ctx, ccm_kfstore* st, int K,
   if (!ctx) return CCM_E_ARG;
   const char* const me = "ccm_fuse_sim3_eval_resident: ";
   if (int rc = fuse_store_ok(ctx, st, me)) return rc;
-  if (const char* why = fsm_check_scalars(K, P, nlevels, th)) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + why);
-  if (!scale_factors || (K > 0 && (!keys || !Scw || !n_valid || !n_hit)) || (P > 0 && (!pos || !normal || !min_dist || !max_dist || !pt_desc)) || (K > 0 && P > 0 && !table))
-    return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + "null pointers");
+  if (const char* why = fsm_check_scalars(K, P, nlevels, th)) FUSE_REFUSE(why);
+  if (const char* why = fsm_check_kf_pointers(K, P, keys, Scw, scale_factors, pos, normal, min_dist, max_dist, pt_desc, table, n_valid, n_hit, true)) FUSE_REFUSE(why);
   std::shared_lock<std::shared_mutex> lk(st->mu);   // from the key lookup to the end of the download: no slot read here is reused meanwhile
   std::vector<int32_t> slots;
   if (int rc = fuse_store_slots(ctx, st, K, keys, me, &slots)) return rc;
-  for (int k = 0; k < K; k++) n_valid[k] = n_hit[k] = 0;
-  if (K == 0 || P == 0) return CCM_OK;
-  FuseSim3ResidentBlock b((size_t)K, (size_t)P, (size_t)nlevels, uv != nullptr);
-  if (int rc = ccm_staged_begin(ctx, b, me)) return rc;
-  const Clock::time_point t0 = Clock::now();
-  FuseArgs a = fuse_resident_inputs(b, st, slots, nlevels, scale_factors, logScaleFactor, th, pos, &b.normal, normal, min_dist, max_dist, pt_desc);
-  float* h_pose = b.up(b.pose);
-  for (int k = 0; k < K; k++) fsm_decompose_scw(Scw + 12 * (size_t)k, h_pose + FSM_POSE_FLOATS * (size_t)k);
-  const Clock::time_point t1 = Clock::now();
-  if (int rc = ccm_staged_upload(ctx, b)) return rc;
-  a.P = P; a.tiles = (P + FPM_TILE - 1) / FPM_TILE;
-  const uint64_t groups = (uint64_t)K * (uint64_t)a.tiles;
-  if (groups > (uint64_t)INT32_MAX) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + "too many workgroups");
-  hipLaunchKernelGGL(fuse_sim3_resident_kernel, dim3((unsigned)groups), dim3(FPM_TILE), 0, ctx->stream, a);
-  Clock::time_point t2;
-  if (int rc = fuse_stage_outputs(ctx, b, table, n_valid, n_hit, uv, &t2)) return rc;
-  if (ccm_dbg("fuse"))
-    fprintf(stderr, "[fuse_resident] K=%d P=%d pack_us=%.1f device_us=%.1f unpack_us=%.1f up_bytes=%zu down_bytes=%zu\n", K, P, us_between(t0, t1), us_between(t1, t2),
-            us_between(t2, Clock::now()), b.up_bytes(), b.down_bytes());
-  return CCM_OK;
+  return fuse_stage_run(ctx, me, "fuse_resident", fuse_sim3_resident_kernel, {0, (size_t)K, 0, (size_t)P, (size_t)nlevels, 0, 0, 0, 0, uv != nullptr},
+                        {nlevels, scale_factors, nullptr, logScaleFactor, th, pos, normal, min_dist, max_dist, pt_desc, table, n_valid, n_hit, uv},
+                        {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, st, slots.data()}, [&](const FuseBlock& b) { fuse_pack_scw(b, Scw); });
 }
 
 extern "C" int ccm_fuse_pose_eval_resident(ccm_ctx* ctx, ccm_kfstore* st, int K, const int64_t* keys, const float* pose, int nlevels, const float* scale_factors,
@@ -383,33 +354,20 @@ extern "C" int ccm_fuse_pose_eval_resident(ccm_ctx* ctx, ccm_kfstore* st, int K,
   if (!ctx) return CCM_E_ARG;
   const char* const me = "ccm_fuse_pose_eval_resident: ";
   if (int rc = fuse_store_ok(ctx, st, me)) return rc;
-  if (const char* why = fsm_check_scalars(K, P, nlevels, th)) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + why);
+  if (const char* why = fsm_check_scalars(K, P, nlevels, th)) FUSE_REFUSE(why);
   int64_t total = 0, tiles = 0;
-  if (const char* why = fpm_check_jobs(J, K, P, job_kf, job_pt0, job_n, &total, &tiles)) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + why);
-  if (!scale_factors || !inv_level_sigma2 || (K > 0 && (!keys || !pose)) || (J > 0 && (!n_valid || !n_hit)) ||
-      (P > 0 && (!pos || !normal || !min_dist || !max_dist || !pt_desc)) || (total > 0 && !table))
-    return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + "null pointers");
+  if (const char* why = fpm_check_jobs(J, K, P, job_kf, job_pt0, job_n, &total, &tiles)) FUSE_REFUSE(why);
+  if (const char* why = fsm_check_job_pointers(K, P, J, total, true, keys, pose, scale_factors, inv_level_sigma2, pos, normal, min_dist, max_dist, pt_desc, table,
+                                               n_valid, n_hit, true))
+    FUSE_REFUSE(why);
   std::shared_lock<std::shared_mutex> lk(st->mu);
   std::vector<int32_t> slots;
   if (int rc = fuse_store_slots(ctx, st, K, keys, me, &slots)) return rc;
-  for (int j = 0; j < J; j++) n_valid[j] = n_hit[j] = 0;
-  if (total == 0) return CCM_OK;
-  FusePoseResidentBlock b((size_t)K, (size_t)P, (size_t)nlevels, (size_t)J, (size_t)tiles, (size_t)total, uv != nullptr);
-  if (int rc = ccm_staged_begin(ctx, b, me)) return rc;
-  const Clock::time_point t0 = Clock::now();
-  FuseArgs a = fuse_resident_inputs(b, st, slots, nlevels, scale_factors, logScaleFactor, th, pos, &b.normal, normal, min_dist, max_dist, pt_desc);
-  b.put(b.pose, pose); b.put(b.inv_sigma2, inv_level_sigma2);
-  fuse_pose_jobs(b, J, job_kf, job_pt0, job_n);
-  const Clock::time_point t1 = Clock::now();
-  if (int rc = ccm_staged_upload(ctx, b)) return rc;
-  a.inv_sigma2 = b.dev(b.inv_sigma2); a.job = b.dev(b.job); a.tile = b.dev(b.tile);
-  hipLaunchKernelGGL(fuse_pose_resident_kernel, dim3((unsigned)tiles), dim3(FPM_TILE), 0, ctx->stream, a);
-  Clock::time_point t2;
-  if (int rc = fuse_stage_outputs(ctx, b, table, n_valid, n_hit, uv, &t2)) return rc;
-  if (ccm_dbg("fuse"))
-    fprintf(stderr, "[fuse_pose_resident] K=%d P=%d J=%d pairs=%lld pack_us=%.1f device_us=%.1f unpack_us=%.1f up_bytes=%zu down_bytes=%zu\n", K, P, J,
-            (long long)total, us_between(t0, t1), us_between(t1, t2), us_between(t2, Clock::now()), b.up_bytes(), b.down_bytes());
-  return CCM_OK;
+  return fuse_stage_run(ctx, me, "fuse_pose_resident", fuse_pose_resident_kernel,
+                        {FB_JOBS | FB_CHI2, (size_t)K, 0, (size_t)P, (size_t)nlevels, (size_t)J, (size_t)tiles, (size_t)total, 0, uv != nullptr},
+                        {nlevels, scale_factors, inv_level_sigma2, logScaleFactor, th, pos, normal, min_dist, max_dist, pt_desc, table, n_valid, n_hit, uv},
+                        {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, st, slots.data()},
+                        [&](const FuseBlock& b) { b.put(b.pose, pose); fuse_pack_jobs(b, job_kf, job_pt0, job_n); });
 }
 
 extern "C" int ccm_sim3_project_eval_resident(ccm_ctx* ctx, ccm_kfstore* st, int K, const int64_t* keys, const float* Scw, const int32_t* skip_off,
@@ -419,37 +377,19 @@ extern "C" int ccm_sim3_project_eval_resident(ccm_ctx* ctx, ccm_kfstore* st, int
   if (!ctx) return CCM_E_ARG;
   const char* const me = "ccm_sim3_project_eval_resident: ";
   if (int rc = fuse_store_ok(ctx, st, me)) return rc;
-  if (const char* why = fsm_check_scalars(K, P, nlevels, th)) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + why);
-  if (!scale_factors || (K > 0 && (!keys || !Scw || !n_valid || !n_hit)) || (P > 0 && (!pos || !normal || !min_dist || !max_dist || !pt_desc)) || (K > 0 && P > 0 && !table))
-    return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + "null pointers");
+  if (const char* why = fsm_check_scalars(K, P, nlevels, th)) FUSE_REFUSE(why);
+  if (const char* why = fsm_check_kf_pointers(K, P, keys, Scw, scale_factors, pos, normal, min_dist, max_dist, pt_desc, table, n_valid, n_hit, true)) FUSE_REFUSE(why);
   std::shared_lock<std::shared_mutex> lk(st->mu);
   std::vector<int32_t> slots;
   if (int rc = fuse_store_slots(ctx, st, K, keys, me, &slots)) return rc;
   std::vector<int32_t> kf_n((size_t)K);
   for (int k = 0; k < K; k++) kf_n[k] = st->h_n[(size_t)slots[k]];
-  if (const char* why = fsm_check_skip(K, skip_off, feat_skip, kf_n.data())) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + why);
-  for (int k = 0; k < K; k++) n_valid[k] = n_hit[k] = 0;
-  if (K == 0 || P == 0) return CCM_OK;
-  Sim3ProjectResidentBlock b((size_t)K, (size_t)P, (size_t)nlevels, (size_t)skip_off[K], uv != nullptr);
-  if (int rc = ccm_staged_begin(ctx, b, me)) return rc;
-  const Clock::time_point t0 = Clock::now();
-  FuseArgs a = fuse_resident_inputs(b, st, slots, nlevels, scale_factors, logScaleFactor, th, pos, &b.normal, normal, min_dist, max_dist, pt_desc);
-  b.put(b.skip_off, skip_off); b.put(b.skip, feat_skip);
-  a.skip_off = b.dev(b.skip_off); a.skip = b.dev(b.skip);
-  float* h_pose = b.up(b.pose);
-  for (int k = 0; k < K; k++) fsm_decompose_scw(Scw + 12 * (size_t)k, h_pose + FSM_POSE_FLOATS * (size_t)k);
-  const Clock::time_point t1 = Clock::now();
-  if (int rc = ccm_staged_upload(ctx, b)) return rc;
-  a.P = P; a.tiles = (P + FPM_TILE - 1) / FPM_TILE;
-  const uint64_t groups = (uint64_t)K * (uint64_t)a.tiles;
-  if (groups > (uint64_t)INT32_MAX) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + "too many workgroups");
-  hipLaunchKernelGGL(proj_sim3_resident_kernel, dim3((unsigned)groups), dim3(FPM_TILE), 0, ctx->stream, a);
-  Clock::time_point t2;
-  if (int rc = fuse_stage_outputs(ctx, b, table, n_valid, n_hit, uv, &t2)) return rc;
-  if (ccm_dbg("fuse"))
-    fprintf(stderr, "[sim3_project] K=%d P=%d pack_us=%.1f device_us=%.1f unpack_us=%.1f up_bytes=%zu down_bytes=%zu\n", K, P, us_between(t0, t1), us_between(t1, t2),
-            us_between(t2, Clock::now()), b.up_bytes(), b.down_bytes());
-  return CCM_OK;
+  if (const char* why = fsm_check_skip(K, skip_off, feat_skip, kf_n.data())) FUSE_REFUSE(why);
+  return fuse_stage_run(ctx, me, "sim3_project", proj_sim3_resident_kernel,
+                        {FB_MASK, (size_t)K, 0, (size_t)P, (size_t)nlevels, 0, 0, 0, K > 0 ? (size_t)skip_off[K] : 0, uv != nullptr},
+                        {nlevels, scale_factors, nullptr, logScaleFactor, th, pos, normal, min_dist, max_dist, pt_desc, table, n_valid, n_hit, uv},
+                        {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, st, slots.data()},
+                        [&](const FuseBlock& b) { b.put(b.skip_off, skip_off); b.put(b.skip, feat_skip); fuse_pack_scw(b, Scw); });
 }
 
 extern "C" int ccm_sim3_pair_eval_resident(ccm_ctx* ctx, ccm_kfstore* st, int K, const int64_t* keys, int nlevels, const float* scale_factors, float logScaleFactor,
@@ -459,36 +399,21 @@ extern "C" int ccm_sim3_pair_eval_resident(ccm_ctx* ctx, ccm_kfstore* st, int K,
   if (!ctx) return CCM_E_ARG;
   const char* const me = "ccm_sim3_pair_eval_resident: ";
   if (int rc = fuse_store_ok(ctx, st, me)) return rc;
-  if (const char* why = fsm_check_scalars(K, P, nlevels, th)) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + why);
+  if (const char* why = fsm_check_scalars(K, P, nlevels, th)) FUSE_REFUSE(why);
   int64_t total = 0, tiles = 0;
-  if (const char* why = fpm_check_jobs(J, K, P, job_kf, job_pt0, job_n, &total, &tiles)) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + why);
-  if (const char* why = fsm_check_pair_jobs(J, job_K4, job_src_pose, job_T)) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + why);
-  if (!scale_factors || (K > 0 && !keys) || (J > 0 && (!n_valid || !n_hit)) || (P > 0 && (!pos || !min_dist || !max_dist || !pt_desc)) || (total > 0 && !table))
-    return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + "null pointers");
+  if (const char* why = fpm_check_jobs(J, K, P, job_kf, job_pt0, job_n, &total, &tiles)) FUSE_REFUSE(why);
+  if (const char* why = fsm_check_pair_jobs(J, job_K4, job_src_pose, job_T)) FUSE_REFUSE(why);
+  if (const char* why = fsm_check_job_pointers(K, P, J, total, false, keys, nullptr, scale_factors, nullptr, pos, nullptr, min_dist, max_dist, pt_desc, table, n_valid,
+                                               n_hit, true))
+    FUSE_REFUSE(why);
   std::shared_lock<std::shared_mutex> lk(st->mu);
   std::vector<int32_t> slots;
   if (int rc = fuse_store_slots(ctx, st, K, keys, me, &slots)) return rc;
-  for (int j = 0; j < J; j++) n_valid[j] = n_hit[j] = 0;
-  if (total == 0) return CCM_OK;
-  Sim3PairResidentBlock b((size_t)K, (size_t)P, (size_t)nlevels, (size_t)J, (size_t)tiles, (size_t)total, uv != nullptr);
-  if (int rc = ccm_staged_begin(ctx, b, me)) return rc;
-  const Clock::time_point t0 = Clock::now();
-  FuseArgs a = fuse_resident_inputs(b, st, slots, nlevels, scale_factors, logScaleFactor, th, pos, nullptr, nullptr, min_dist, max_dist, pt_desc);
-  float* h_job = b.up(b.pose);
-  for (int j = 0; j < J; j++) {
-    float* r = h_job + SSM_JOB_FLOATS * (size_t)j;
-    memcpy(r, job_K4 + 4 * (size_t)j, 4 * sizeof(float)); memcpy(r + 4, job_src_pose + 12 * (size_t)j, 12 * sizeof(float));
-    memcpy(r + 16, job_T + 12 * (size_t)j, 12 * sizeof(float));
-  }
-  fuse_pose_jobs(b, J, job_kf, job_pt0, job_n);
-  const Clock::time_point t1 = Clock::now();
-  if (int rc = ccm_staged_upload(ctx, b)) return rc;
-  a.job = b.dev(b.job); a.tile = b.dev(b.tile);
-  hipLaunchKernelGGL(sim3_pair_resident_kernel, dim3((unsigned)tiles), dim3(FPM_TILE), 0, ctx->stream, a);
-  Clock::time_point t2;
-  if (int rc = fuse_stage_outputs(ctx, b, table, n_valid, n_hit, uv, &t2)) return rc;
-  if (ccm_dbg("fuse"))
-    fprintf(stderr, "[sim3_pair] K=%d P=%d J=%d pairs=%lld pack_us=%.1f device_us=%.1f unpack_us=%.1f up_bytes=%zu down_bytes=%zu\n", K, P, J, (long long)total,
-            us_between(t0, t1), us_between(t1, t2), us_between(t2, Clock::now()), b.up_bytes(), b.down_bytes());
-  return CCM_OK;
+  return fuse_stage_run(ctx, me, "sim3_pair", sim3_pair_resident_kernel,
+                        {FB_JOBS | FB_PAIR, (size_t)K, 0, (size_t)P, (size_t)nlevels, (size_t)J, (size_t)tiles, (size_t)total, 0, uv != nullptr},
+                        {nlevels, scale_factors, nullptr, logScaleFactor, th, pos, nullptr, min_dist, max_dist, pt_desc, table, n_valid, n_hit, uv},
+                        {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, st, slots.data()}, [&](const FuseBlock& b) {
+                          ssm_pack_jobs(J, job_K4, job_src_pose, job_T, b.up(b.pose));
+                          fuse_pack_jobs(b, job_kf, job_pt0, job_n);
+                        });
 }

@@ -257,6 +257,15 @@ FSM_HD int ssm_gate(const float rec[FSM_REC_FLOATS], const float job[SSM_JOB_FLO
   return FSM_EMPTY;
 }
 
+// the jobs' SSM_JOB_FLOATS from the caller's three arrays: K4 (4), the source pose (12), the transform (12) per job
+FSM_HD void ssm_pack_jobs(int J, const float* job_K4, const float* job_src_pose, const float* job_T, float* out) {
+  for (int j = 0; j < J; j++) {
+    float* r = out + SSM_JOB_FLOATS * (size_t)j;
+    memcpy(r, job_K4 + 4 * (size_t)j, 4 * sizeof(float)); memcpy(r + 4, job_src_pose + 12 * (size_t)j, 12 * sizeof(float));
+    memcpy(r + 16, job_T + 12 * (size_t)j, 12 * sizeof(float));
+  }
+}
+
 // The argument rules of ccm_fuse_sim3_eval; nullptr, or what is wrong.  The scalar rules come first and read no array.  cell_idx: int32 as the caller passes it.
 // (fsm_check_scalars: the scalar rules alone, which are all the resident forms share with it: their keyframes are the store's, validated when they were added.)
 FSM_HD const char* fsm_check_scalars(int K, int P, int nlevels, float th) {
@@ -323,5 +332,28 @@ FSM_HD const char* fsm_check_skip(int K, const int32_t* skip_off, const uint8_t*
 // the null-pointer rules of ccm_sim3_pair_eval_resident's per-job floats (the index arrays are fpm_check_jobs')
 FSM_HD const char* fsm_check_pair_jobs(int J, const float* job_K4, const float* job_src_pose, const float* job_T) {
   if (J > 0 && (!job_K4 || !job_src_pose || !job_T)) return "null job arrays";
+  return nullptr;
+}
+
+// The null-pointer rules of the six entry points after their context (and store), which the host evaluators (host/ccm_host.cpp) share with them; nullptr, or
+// "null pointers".  kf: the keyframes' records, or the keys of a store.  feats: fsm_feats_ok for the flat forms, true for the resident ones.
+FSM_HD bool fsm_feats_ok(size_t F, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc) { return !F || (feat_xy && feat_octave && feat_desc); }
+// the keyframe-major forms: ccm_fuse_sim3_eval, ccm_fuse_sim3_eval_resident, ccm_sim3_project_eval_resident
+FSM_HD const char* fsm_check_kf_pointers(int K, int P, const void* kf, const float* Scw, const float* scale_factors, const float* pos, const float* normal,
+                                         const float* min_dist, const float* max_dist, const uint8_t* pt_desc, const uint32_t* table, const int32_t* n_valid,
+                                         const int32_t* n_hit, bool feats) {
+  if (!scale_factors || (K > 0 && (!kf || !Scw || !n_valid || !n_hit)) || (P > 0 && (!pos || !normal || !min_dist || !max_dist || !pt_desc)) ||
+      (K > 0 && P > 0 && !table) || !feats)
+    return "null pointers";
+  return nullptr;
+}
+// the job forms.  fuse: ccm_fuse_pose_eval and its resident form, which read a pose per keyframe, inv_level_sigma2 and the normals; ccm_sim3_pair_eval_resident
+// reads none of the three (its per-job floats are fsm_check_pair_jobs').  total: fpm_check_jobs'.
+FSM_HD const char* fsm_check_job_pointers(int K, int P, int J, int64_t total, bool fuse, const void* kf, const float* pose, const float* scale_factors,
+                                          const float* inv_level_sigma2, const float* pos, const float* normal, const float* min_dist, const float* max_dist,
+                                          const uint8_t* pt_desc, const uint32_t* table, const int32_t* n_valid, const int32_t* n_hit, bool feats) {
+  if (!scale_factors || (fuse && !inv_level_sigma2) || (K > 0 && (!kf || (fuse && !pose))) || (J > 0 && (!n_valid || !n_hit)) ||
+      (P > 0 && (!pos || (fuse && !normal) || !min_dist || !max_dist || !pt_desc)) || (total > 0 && !table) || !feats)
+    return "null pointers";
   return nullptr;
 }

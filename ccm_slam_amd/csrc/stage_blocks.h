@@ -119,45 +119,6 @@ struct TwoViewCheckRtBlock : StagedBlock {
   StagedSeg<uint8_t> status = add<uint8_t>(N * Q, SB_OUT);
 };
 
-// ccm_fuse_sim3_eval: K keyframes with F features in all, P points, L levels.  The keyframes' inputs, the call's, the points', then the outputs: the two counters go up
-// as zeros (the kernel adds to them) and lead the download, the table follows, uv is declared with no elements when the caller does not ask for it.  The descriptors
-// lie on 16 bytes for the kernel's 16-byte loads.  pose and cell_idx (16-bit) are written by the stage while it validates.
-struct FuseSim3Block : StagedBlock {
-  const size_t K, F, P, L; const bool want_uv;
-  FuseSim3Block(size_t K, size_t F, size_t P, size_t L, bool want_uv) : K(K), F(F), P(P), L(L), want_uv(want_uv) {}
-  StagedSeg<uint8_t> kdesc = add<uint8_t>(32 * F, SB_COPY, 16), pdesc = add<uint8_t>(32 * P, SB_COPY, 16);
-  StagedSeg<float> rec = add<float>(FSM_REC_FLOATS * K, SB_COPY), pose = add<float>(FSM_POSE_FLOATS * K, SB_GEN);
-  StagedSeg<int32_t> feat_off = add<int32_t>(K + 1, SB_COPY), cell_off = add<int32_t>(K * (FSM_CELLS + 1), SB_COPY);
-  StagedSeg<float> kxy = add<float>(2 * F, SB_COPY);
-  StagedSeg<uint16_t> cell_idx = add<uint16_t>(F, SB_GEN);
-  StagedSeg<uint8_t> koct = add<uint8_t>(F, SB_COPY);
-  StagedSeg<float> scale_factors = add<float>(L, SB_COPY);
-  StagedSeg<float> pos = add<float>(3 * P, SB_COPY), normal = add<float>(3 * P, SB_COPY), dmin = add<float>(P, SB_COPY), dmax = add<float>(P, SB_COPY);
-  StagedSeg<int32_t> n_valid = add<int32_t>(K, SB_OUT | SB_ZERO), n_hit = add<int32_t>(K, SB_OUT | SB_ZERO);
-  StagedSeg<uint32_t> table = add<uint32_t>(K * P, SB_OUT);
-  StagedSeg<float> uv = add<float>(want_uv ? 2 * K * P : 0, SB_OUT);
-};
-
-// ccm_fuse_pose_eval: K keyframes with F features in all, P points, L levels, J jobs in T tiles of FPM_TILE pairs, N = the sum of the jobs' points.  The keyframes'
-// inputs as in FuseSim3Block, but pose is the caller's (Rcw, tcw, Ow) and inv_sigma2 joins scale_factors.  job (keyframe, first point, points, first table word per
-// job) and tile (job, first pair of the job per workgroup) are written by the stage while it validates the job arrays.  The counters are per job.
-struct FusePoseBlock : StagedBlock {
-  const size_t K, F, P, L, J, T, N; const bool want_uv;
-  FusePoseBlock(size_t K, size_t F, size_t P, size_t L, size_t J, size_t T, size_t N, bool want_uv) : K(K), F(F), P(P), L(L), J(J), T(T), N(N), want_uv(want_uv) {}
-  StagedSeg<uint8_t> kdesc = add<uint8_t>(32 * F, SB_COPY, 16), pdesc = add<uint8_t>(32 * P, SB_COPY, 16);
-  StagedSeg<int32_t> job = add<int32_t>(FPM_JOB_INTS * J, SB_GEN, 16), tile = add<int32_t>(2 * T, SB_GEN);
-  StagedSeg<float> rec = add<float>(FSM_REC_FLOATS * K, SB_COPY), pose = add<float>(FSM_POSE_FLOATS * K, SB_COPY);
-  StagedSeg<int32_t> feat_off = add<int32_t>(K + 1, SB_COPY), cell_off = add<int32_t>(K * (FSM_CELLS + 1), SB_COPY);
-  StagedSeg<float> kxy = add<float>(2 * F, SB_COPY);
-  StagedSeg<uint16_t> cell_idx = add<uint16_t>(F, SB_GEN);
-  StagedSeg<uint8_t> koct = add<uint8_t>(F, SB_COPY);
-  StagedSeg<float> scale_factors = add<float>(L, SB_COPY), inv_sigma2 = add<float>(L, SB_COPY);
-  StagedSeg<float> pos = add<float>(3 * P, SB_COPY), normal = add<float>(3 * P, SB_COPY), dmin = add<float>(P, SB_COPY), dmax = add<float>(P, SB_COPY);
-  StagedSeg<int32_t> n_valid = add<int32_t>(J, SB_OUT | SB_ZERO), n_hit = add<int32_t>(J, SB_OUT | SB_ZERO);
-  StagedSeg<uint32_t> table = add<uint32_t>(N, SB_OUT);
-  StagedSeg<float> uv = add<float>(want_uv ? 2 * N : 0, SB_OUT);
-};
-
 // ccm_kfstore_add: M keyframes with F features in all, on their way into the slots slot[m] of the store.  The descriptors lead, on 16 bytes, for the kernel's 16-byte
 // copies.  A caller-supplied grid travels as cell_off and a 16-bit cell_idx the stage writes while it validates; without one both are declared with no elements and
 // the kernel builds the grid.  n_in (the features in the grid, per keyframe) comes back.
@@ -173,57 +134,59 @@ struct KfstoreAddBlock : StagedBlock {
   StagedSeg<int32_t> n_in = add<int32_t>(M, SB_OUT);
 };
 
-// ccm_fuse_sim3_eval_resident: FuseSim3Block without the keyframes' static data, which the kernel reads from the store's slots: slot[k] (written by the stage while it
-// looks the keys up) takes the place of feat_off, cell_off and the five feature arrays.
-struct FuseSim3ResidentBlock : StagedBlock {
-  const size_t K, P, L; const bool want_uv;
-  FuseSim3ResidentBlock(size_t K, size_t P, size_t L, bool want_uv) : K(K), P(P), L(L), want_uv(want_uv) {}
-  StagedSeg<uint8_t> pdesc = add<uint8_t>(32 * P, SB_COPY, 16);
-  StagedSeg<int32_t> slot = add<int32_t>(K, SB_GEN);
-  StagedSeg<float> pose = add<float>(FSM_POSE_FLOATS * K, SB_GEN), scale_factors = add<float>(L, SB_COPY);
-  StagedSeg<float> pos = add<float>(3 * P, SB_COPY), normal = add<float>(3 * P, SB_COPY), dmin = add<float>(P, SB_COPY), dmax = add<float>(P, SB_COPY);
-  StagedSeg<int32_t> n_valid = add<int32_t>(K, SB_OUT | SB_ZERO), n_hit = add<int32_t>(K, SB_OUT | SB_ZERO);
-  StagedSeg<uint32_t> table = add<uint32_t>(K * P, SB_OUT);
-  StagedSeg<float> uv = add<float>(want_uv ? 2 * K * P : 0, SB_OUT);
-};
 
-// ccm_fuse_pose_eval_resident: FusePoseBlock without the keyframes' static data, in the same way.
-struct FusePoseResidentBlock : StagedBlock {
-  const size_t K, P, L, J, T, N; const bool want_uv;
-  FusePoseResidentBlock(size_t K, size_t P, size_t L, size_t J, size_t T, size_t N, bool want_uv) : K(K), P(P), L(L), J(J), T(T), N(N), want_uv(want_uv) {}
-  StagedSeg<uint8_t> pdesc = add<uint8_t>(32 * P, SB_COPY, 16);
-  StagedSeg<int32_t> job = add<int32_t>(FPM_JOB_INTS * J, SB_GEN, 16), tile = add<int32_t>(2 * T, SB_GEN), slot = add<int32_t>(K, SB_GEN);
-  StagedSeg<float> pose = add<float>(FSM_POSE_FLOATS * K, SB_COPY), scale_factors = add<float>(L, SB_COPY), inv_sigma2 = add<float>(L, SB_COPY);
-  StagedSeg<float> pos = add<float>(3 * P, SB_COPY), normal = add<float>(3 * P, SB_COPY), dmin = add<float>(P, SB_COPY), dmax = add<float>(P, SB_COPY);
-  StagedSeg<int32_t> n_valid = add<int32_t>(J, SB_OUT | SB_ZERO), n_hit = add<int32_t>(J, SB_OUT | SB_ZERO);
-  StagedSeg<uint32_t> table = add<uint32_t>(N, SB_OUT);
-  StagedSeg<float> uv = add<float>(want_uv ? 2 * N : 0, SB_OUT);
+// The six projected searches of fuse.hip are ONE layout: K keyframes, P points, L levels, and what the form's flags add.  A segment a form does
+// not have is declared with no elements, so it takes no room, moves nothing, and the offsets of each form are what they would be alone.
+//   FB_FLAT  the keyframes' own arrays travel, F features in all: kdesc, rec, feat_off, cell_off, kxy, cell_idx (16-bit, written by the stage while it validates), koct.
+//            Without it the kernel reads them from the keyframe store's slots, and slot[K] (written while the keys are looked up) takes their place.
+//   FB_JOBS  the work is J jobs in T tiles of FPM_TILE pairs, N = the sum of the jobs' points: job (keyframe, first point, points, first table word) and tile (job,
+//            first pair of the job per workgroup), written by the stage while it validates the job arrays; the counters are per job and the table has N words.
+//            Without it every keyframe meets every point: K counters, K * P words.
+//   FB_CHI2  Fuse's pose form: inv_sigma2, and pose is the caller's (Rcw, tcw, Ow); the Sim3 forms' pose is the decomposed Scw, written by the stage.
+//   FB_MASK  SearchByProjection: skip_off (K + 1) and M = skip_off[K] mask bytes, one per feature of every keyframe of the call.
+//   FB_PAIR  SearchBySim3: no normals, and pose holds SSM_JOB_FLOATS per JOB (K4, the source pose, the transform), packed by the stage.
+//   FuseSim3Block FB_FLAT | FusePoseBlock FB_FLAT JOBS CHI2 | FuseSim3ResidentBlock - | FusePoseResidentBlock JOBS CHI2 | Sim3ProjectResidentBlock MASK | Sim3PairResidentBlock JOBS PAIR
+// The descriptors lead, on 16 bytes, for the kernel's 16-byte loads; the inputs follow, then the outputs: the two counters go up as zeros (the kernel adds to them) and
+// lead the download, the table follows, uv is declared with no elements when the caller does not ask for it.
+enum : unsigned { FB_FLAT = 1, FB_JOBS = 2, FB_CHI2 = 4, FB_MASK = 8, FB_PAIR = 16 };
+struct FuseShape { unsigned form; size_t K, F, P, L, J, T, N, M; bool want_uv; };
+struct FuseBlock : StagedBlock {
+  const FuseShape s;
+  const bool flat, jobs;
+  const size_t C, W;   // counters, table words
+  explicit FuseBlock(const FuseShape& s) : s(s), flat(s.form & FB_FLAT), jobs(s.form & FB_JOBS), C(jobs ? s.J : s.K), W(jobs ? s.N : s.K * s.P) {}
+  StagedSeg<uint8_t> kdesc = add<uint8_t>(flat ? 32 * s.F : 0, SB_COPY, 16), pdesc = add<uint8_t>(32 * s.P, SB_COPY, 16);
+  StagedSeg<int32_t> job = add<int32_t>(jobs ? FPM_JOB_INTS * s.J : 0, SB_GEN, 16), tile = add<int32_t>(jobs ? 2 * s.T : 0, SB_GEN);
+  StagedSeg<int32_t> slot = add<int32_t>(flat ? 0 : s.K, SB_GEN), skip_off = add<int32_t>(s.form & FB_MASK ? s.K + 1 : 0, SB_COPY);
+  StagedSeg<float> rec = add<float>(flat ? FSM_REC_FLOATS * s.K : 0, SB_COPY);
+  StagedSeg<float> pose = add<float>(s.form & FB_PAIR ? SSM_JOB_FLOATS * s.J : FSM_POSE_FLOATS * s.K, jobs && !(s.form & FB_PAIR) ? SB_COPY : SB_GEN);
+  StagedSeg<int32_t> feat_off = add<int32_t>(flat ? s.K + 1 : 0, SB_COPY), cell_off = add<int32_t>(flat ? s.K * (FSM_CELLS + 1) : 0, SB_COPY);
+  StagedSeg<float> kxy = add<float>(flat ? 2 * s.F : 0, SB_COPY);
+  StagedSeg<uint16_t> cell_idx = add<uint16_t>(flat ? s.F : 0, SB_GEN);
+  StagedSeg<uint8_t> koct = add<uint8_t>(flat ? s.F : 0, SB_COPY);
+  StagedSeg<float> scale_factors = add<float>(s.L, SB_COPY), inv_sigma2 = add<float>(s.form & FB_CHI2 ? s.L : 0, SB_COPY);
+  StagedSeg<float> pos = add<float>(3 * s.P, SB_COPY), normal = add<float>(s.form & FB_PAIR ? 0 : 3 * s.P, SB_COPY), dmin = add<float>(s.P, SB_COPY), dmax = add<float>(s.P, SB_COPY);
+  StagedSeg<uint8_t> skip = add<uint8_t>(s.form & FB_MASK ? s.M : 0, SB_COPY);
+  StagedSeg<int32_t> n_valid = add<int32_t>(C, SB_OUT | SB_ZERO), n_hit = add<int32_t>(C, SB_OUT | SB_ZERO);
+  StagedSeg<uint32_t> table = add<uint32_t>(W, SB_OUT);
+  StagedSeg<float> uv = add<float>(s.want_uv ? 2 * W : 0, SB_OUT);
 };
-
-// ccm_sim3_project_eval_resident: FuseSim3ResidentBlock and the masks: skip_off (K + 1) and M = skip_off[K] mask bytes, one per feature of every keyframe of the call.
-struct Sim3ProjectResidentBlock : StagedBlock {
-  const size_t K, P, L, M; const bool want_uv;
-  Sim3ProjectResidentBlock(size_t K, size_t P, size_t L, size_t M, bool want_uv) : K(K), P(P), L(L), M(M), want_uv(want_uv) {}
-  StagedSeg<uint8_t> pdesc = add<uint8_t>(32 * P, SB_COPY, 16);
-  StagedSeg<int32_t> slot = add<int32_t>(K, SB_GEN), skip_off = add<int32_t>(K + 1, SB_COPY);
-  StagedSeg<float> pose = add<float>(FSM_POSE_FLOATS * K, SB_GEN), scale_factors = add<float>(L, SB_COPY);
-  StagedSeg<float> pos = add<float>(3 * P, SB_COPY), normal = add<float>(3 * P, SB_COPY), dmin = add<float>(P, SB_COPY), dmax = add<float>(P, SB_COPY);
-  StagedSeg<uint8_t> skip = add<uint8_t>(M, SB_COPY);
-  StagedSeg<int32_t> n_valid = add<int32_t>(K, SB_OUT | SB_ZERO), n_hit = add<int32_t>(K, SB_OUT | SB_ZERO);
-  StagedSeg<uint32_t> table = add<uint32_t>(K * P, SB_OUT);
-  StagedSeg<float> uv = add<float>(want_uv ? 2 * K * P : 0, SB_OUT);
+// the six entry points' names for it
+struct FuseSim3Block : FuseBlock {
+  FuseSim3Block(size_t K, size_t F, size_t P, size_t L, bool want_uv) : FuseBlock({FB_FLAT, K, F, P, L, 0, 0, 0, 0, want_uv}) {}
 };
-
-// ccm_sim3_pair_eval_resident: FusePoseResidentBlock without the normals and inv_sigma2, which SearchBySim3 does not read; pose holds SSM_JOB_FLOATS per JOB
-// (K4, the source pose, the transform), packed by the stage.
-struct Sim3PairResidentBlock : StagedBlock {
-  const size_t K, P, L, J, T, N; const bool want_uv;
-  Sim3PairResidentBlock(size_t K, size_t P, size_t L, size_t J, size_t T, size_t N, bool want_uv) : K(K), P(P), L(L), J(J), T(T), N(N), want_uv(want_uv) {}
-  StagedSeg<uint8_t> pdesc = add<uint8_t>(32 * P, SB_COPY, 16);
-  StagedSeg<int32_t> job = add<int32_t>(FPM_JOB_INTS * J, SB_GEN, 16), tile = add<int32_t>(2 * T, SB_GEN), slot = add<int32_t>(K, SB_GEN);
-  StagedSeg<float> pose = add<float>(SSM_JOB_FLOATS * J, SB_GEN), scale_factors = add<float>(L, SB_COPY);
-  StagedSeg<float> pos = add<float>(3 * P, SB_COPY), dmin = add<float>(P, SB_COPY), dmax = add<float>(P, SB_COPY);
-  StagedSeg<int32_t> n_valid = add<int32_t>(J, SB_OUT | SB_ZERO), n_hit = add<int32_t>(J, SB_OUT | SB_ZERO);
-  StagedSeg<uint32_t> table = add<uint32_t>(N, SB_OUT);
-  StagedSeg<float> uv = add<float>(want_uv ? 2 * N : 0, SB_OUT);
+struct FusePoseBlock : FuseBlock {
+  FusePoseBlock(size_t K, size_t F, size_t P, size_t L, size_t J, size_t T, size_t N, bool want_uv) : FuseBlock({FB_FLAT | FB_JOBS | FB_CHI2, K, F, P, L, J, T, N, 0, want_uv}) {}
+};
+struct FuseSim3ResidentBlock : FuseBlock {
+  FuseSim3ResidentBlock(size_t K, size_t P, size_t L, bool want_uv) : FuseBlock({0, K, 0, P, L, 0, 0, 0, 0, want_uv}) {}
+};
+struct FusePoseResidentBlock : FuseBlock {
+  FusePoseResidentBlock(size_t K, size_t P, size_t L, size_t J, size_t T, size_t N, bool want_uv) : FuseBlock({FB_JOBS | FB_CHI2, K, 0, P, L, J, T, N, 0, want_uv}) {}
+};
+struct Sim3ProjectResidentBlock : FuseBlock {
+  Sim3ProjectResidentBlock(size_t K, size_t P, size_t L, size_t M, bool want_uv) : FuseBlock({FB_MASK, K, 0, P, L, 0, 0, 0, M, want_uv}) {}
+};
+struct Sim3PairResidentBlock : FuseBlock {
+  Sim3PairResidentBlock(size_t K, size_t P, size_t L, size_t J, size_t T, size_t N, bool want_uv) : FuseBlock({FB_JOBS | FB_PAIR, K, 0, P, L, J, T, N, 0, want_uv}) {}
 };

@@ -1739,44 +1739,76 @@ std::vector<int32_t> KeyFrameCullingBatch::pointsGone() const {
   return v;
 }
 
-// ---- SearchAndFuseBatch, SearchInNeighborsBatch -------------------------------------------------------
-// one (keyframe, point) pair through csrc/fuse_math.h; all keyframe arrays are that keyframe's own.  kChi2: the pose form with its chi-square gate, which reads isig
-template <bool kChi2>
-static uint32_t fuse_pair_host(const float* rec, const float* pose, const int32_t* cell_off, const uint16_t* cell_idx, const float* kxy, const uint8_t* koct,
-                               const uint8_t* kdesc, const float* P3, const float* Pn, float dmin, float dmax, const uint8_t* pdesc, int nlevels, float logsf, float th,
-                               const float* sf, const float* isig, float* uv, int32_t* n_cand) {
+// ---- the six projected searches on the host: one pair, one walker, and the batches built on them ------------------------------
+// one keyframe's own arrays, wherever they live: in the caller's flat arrays, or in a shadow of the keyframe store
+struct FuseKf { const float* rec; const int32_t* cell_off; const uint16_t* cell_idx; const float* kxy; const uint8_t* koct; const uint8_t* kdesc; };
+static FuseKf fuse_kf(const KfShadow& kf) { return {kf.rec, kf.cell_off.data(), kf.cell_idx.data(), kf.xy.data(), kf.oct.data(), kf.desc.data()}; }
+
+// The two keyframe sources of a walk, k -> FuseKf.  The flat arrays of the device entries, whose int32 cell_idx is narrowed to 16 bits here (or is 16-bit already,
+// as a FuseScene keeps it) ...
+struct FlatKfs {
+  const float* rec; const int32_t* feat_off; const float* xy; const uint8_t* oct; const uint8_t* desc; const int32_t* cell_off; const uint16_t* idx16;
+  std::vector<uint16_t> narrowed;
+  FlatKfs(int K, const float* kf_rec, const int32_t* feat_off_, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc, const int32_t* cell_off_,
+          const int32_t* cell_idx)
+      : rec(kf_rec), feat_off(feat_off_), xy(feat_xy), oct(feat_octave), desc(feat_desc), cell_off(cell_off_), narrowed(K ? (size_t)feat_off_[K] : 0) {
+    for (size_t f = 0; f < narrowed.size(); f++) narrowed[f] = (uint16_t)cell_idx[f];
+    idx16 = narrowed.data();
+  }
+  FlatKfs(const float* kf_rec, const int32_t* feat_off_, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc, const int32_t* cell_off_,
+          const uint16_t* cell_idx16)
+      : rec(kf_rec), feat_off(feat_off_), xy(feat_xy), oct(feat_octave), desc(feat_desc), cell_off(cell_off_), idx16(cell_idx16) {}
+  FlatKfs(const FlatKfs&) = delete;
+  FuseKf operator()(int k) const {
+    const int32_t f0 = feat_off[k];
+    return FuseKf{rec + FSM_REC_FLOATS * (size_t)k, cell_off + (size_t)k * (FSM_CELLS + 1), idx16 + f0, xy + 2 * (size_t)f0, oct + f0, desc + 32 * (size_t)f0};
+  }
+};
+// ... and the shadows of a store's keys
+typedef std::vector<std::shared_ptr<const KfShadow>> Shadows;
+struct ShadowKfs {
+  const Shadows& kfs;
+  FuseKf operator()(int k) const { return fuse_kf(*kfs[k]); }
+};
+
+// a call's level tables and scalars (isig: the pose form's alone) and its points
+struct ProjLevels { int nlevels; const float *sf, *isig; float logsf, th; };
+typedef SearchAndFuseBatch::Points ProjPoints;
+
+// One (keyframe, point) pair through csrc/fuse_math.h, with the template parameters of the device's fuse_pair (csrc/fuse.hip).  kChi2: the pose form of Fuse with its
+// chi-square gate, which reads isig.  kMask: SearchByProjection(pKF, Scw, ...), which reads skip (one byte per feature of the keyframe).  kPair: SearchBySim3:
+// pose_or_job is the job's SSM_JOB_FLOATS instead of the keyframe's 15, Pn is not read, TH_HIGH.  n_cand (nullable): the size of vIndices, 0 short of the window.
+template <bool kChi2, bool kMask, bool kPair>
+static uint32_t proj_pair_host(const FuseKf& kf, const float* pose_or_job, const uint8_t* skip, const ProjLevels& lv, const float* P3, const float* Pn, float dmin,
+                               float dmax, const uint8_t* pdesc, float* uv, int32_t* n_cand) {
   float u, v; int level;
-  const int st = fsm_gate(rec, pose, P3, Pn, dmin, dmax, nlevels, logsf, u, v, level);
+  const int st = kPair ? ssm_gate(kf.rec, pose_or_job, P3, dmin, dmax, lv.nlevels, lv.logsf, u, v, level)
+                       : fsm_gate(kf.rec, pose_or_job, P3, Pn, dmin, dmax, lv.nlevels, lv.logsf, u, v, level);
   if (uv) { uv[0] = u; uv[1] = v; }
   if (n_cand) *n_cand = 0;
   if (st != FSM_EMPTY) return fsm_pack(st, 0, FSM_NO_DIST, FSM_NO_IDX);
   uint32_t q[8];
   fsm_load_desc(pdesc, q);
-  int n = 0;
-  const uint32_t w = fsm_window_best<kChi2>(rec, cell_off, cell_idx, kxy, koct, kdesc, u, v, level, th, sf, isig, q, &n);
-  if (n_cand) *n_cand = n;
-  return w;
+  return fsm_window_best<kChi2, kMask>(kf.rec, kf.cell_off, kf.cell_idx, kf.kxy, kf.koct, kf.kdesc, u, v, level, lv.th, lv.sf, lv.isig, q, n_cand, skip,
+                                       kPair ? FSM_TH_HIGH : FSM_TH_LOW);
 }
 
-// one keyframe's own arrays, wherever they live: in the caller's flat arrays, or in a shadow of the keyframe store
-struct FuseKf { const float* rec; const int32_t* cell_off; const uint16_t* cell_idx; const float* kxy; const uint8_t* koct; const uint8_t* kdesc; };
-static FuseKf fuse_kf(const KfShadow& kf) { return {kf.rec, kf.cell_off.data(), kf.cell_idx.data(), kf.xy.data(), kf.oct.data(), kf.desc.data()}; }
-
-// every pair of a list of jobs (keyframe job_kf[j] x points job_pt0[j] .. + job_n[j]), the jobs' words one after the other; the arguments are valid.
-// kf_of(k): keyframe k's arrays; pose: 15 floats per keyframe
-template <bool kChi2, class KfOf>
-static void fuse_jobs_eval(KfOf kf_of, const float* pose, int nlevels, const float* scale_factors, const float* inv_level_sigma2, float logScaleFactor, float th,
-                           const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc, int J, const int32_t* job_kf,
-                           const int32_t* job_pt0, const int32_t* job_n, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv, int32_t* n_cand) {
+// Every pair of a list of jobs (keyframe job_kf[j] x points job_pt0[j] .. + job_n[j]), the jobs' words one after the other; the arguments are valid.  kf_of(k):
+// keyframe k's arrays.  pose: 15 floats per keyframe, with kPair SSM_JOB_FLOATS per JOB.  kMask: keyframe k's mask starts at feat_skip + skip_off[k].
+template <bool kChi2, bool kMask, bool kPair, class KfOf>
+static void proj_jobs_host(const KfOf& kf_of, const float* pose, const int32_t* skip_off, const uint8_t* feat_skip, const ProjLevels& lv, const ProjPoints& pt, int J,
+                           const int32_t* job_kf, const int32_t* job_pt0, const int32_t* job_n, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv,
+                           int32_t* n_cand) {
   size_t e = 0;
   for (int j = 0; j < J; j++) {
     n_valid[j] = n_hit[j] = 0;
     const int k = job_kf[j];
     const FuseKf kf = kf_of(k);
+    const float* pj = pose + (kPair ? SSM_JOB_FLOATS * (size_t)j : FSM_POSE_FLOATS * (size_t)k);
+    const uint8_t* skip = kMask ? feat_skip + skip_off[k] : nullptr;
     for (int i = job_pt0[j]; i < job_pt0[j] + job_n[j]; i++, e++) {
-      const uint32_t w = fuse_pair_host<kChi2>(kf.rec, pose + FSM_POSE_FLOATS * (size_t)k, kf.cell_off, kf.cell_idx, kf.kxy, kf.koct, kf.kdesc, pos + 3 * (size_t)i,
-                                               normal + 3 * (size_t)i, min_dist[i], max_dist[i], pt_desc + 32 * (size_t)i, nlevels, logScaleFactor, th, scale_factors,
-                                               inv_level_sigma2, uv ? uv + 2 * e : nullptr, n_cand ? n_cand + e : nullptr);
+      const uint32_t w = proj_pair_host<kChi2, kMask, kPair>(kf, pj, skip, lv, pt.pos + 3 * (size_t)i, kPair ? nullptr : pt.normal + 3 * (size_t)i, pt.min_dist[i],
+                                                             pt.max_dist[i], pt.desc + 32 * (size_t)i, uv ? uv + 2 * e : nullptr, n_cand ? n_cand + e : nullptr);
       table[e] = w;
       n_valid[j] += (w >> 29) >= FSM_EMPTY;
       n_hit[j] += (w >> 29) == FSM_HIT;
@@ -1784,22 +1816,14 @@ static void fuse_jobs_eval(KfOf kf_of, const float* pose, int nlevels, const flo
   }
 }
 
-// the same on the flat arrays of ccm_fuse_sim3_eval / ccm_fuse_pose_eval (cell_idx: int32 as the caller passes it)
-template <bool kChi2>
-static void fuse_jobs_host(const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
-                           const int32_t* cell_off, const int32_t* cell_idx, const float* pose, int nlevels, const float* scale_factors, const float* inv_level_sigma2,
-                           float logScaleFactor, float th, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc,
-                           int J, const int32_t* job_kf, const int32_t* job_pt0, const int32_t* job_n, size_t F, uint32_t* table, int32_t* n_valid, int32_t* n_hit,
-                           float* uv, int32_t* n_cand) {
-  std::vector<uint16_t> idx16(F);
-  for (size_t f = 0; f < F; f++) idx16[f] = (uint16_t)cell_idx[f];
-  auto kf_of = [&](int k) {
-    const int32_t f0 = feat_off[k];
-    return FuseKf{kf_rec + FSM_REC_FLOATS * (size_t)k, cell_off + (size_t)k * (FSM_CELLS + 1), idx16.data() + f0, feat_xy + 2 * (size_t)f0, feat_octave + f0,
-                  feat_desc + 32 * (size_t)f0};
-  };
-  fuse_jobs_eval<kChi2>(kf_of, pose, nlevels, scale_factors, inv_level_sigma2, logScaleFactor, th, pos, normal, min_dist, max_dist, pt_desc, J, job_kf, job_pt0, job_n,
-                        table, n_valid, n_hit, uv, n_cand);
+// The keyframe-major forms (Fuse with a Sim3, SearchByProjection) are the jobs (k, 0, P): every keyframe against all points, with the pose its Scw decomposes into
+template <bool kMask, class KfOf>
+static void proj_kf_major_host(const KfOf& kf_of, int K, const float* Scw, const int32_t* skip_off, const uint8_t* feat_skip, const ProjLevels& lv, const ProjPoints& pt,
+                               uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv, int32_t* n_cand) {
+  std::vector<float> pose(FSM_POSE_FLOATS * (size_t)K);
+  std::vector<int32_t> jk((size_t)K), j0((size_t)K, 0), jn((size_t)K, pt.P);
+  for (int k = 0; k < K; k++) { jk[k] = k; fsm_decompose_scw(Scw + 12 * (size_t)k, pose.data() + FSM_POSE_FLOATS * (size_t)k); }
+  proj_jobs_host<false, kMask, false>(kf_of, pose.data(), skip_off, feat_skip, lv, pt, K, jk.data(), j0.data(), jn.data(), table, n_valid, n_hit, uv, n_cand);
 }
 
 // a packed answer as a Fuse call leaves bestIdx / bestDist (untouched where the pair has no candidate)
@@ -1833,73 +1857,37 @@ void FuseScene::copy(const KFs& kfs, const float* pose15, const Pts& pts, int nl
   }
 }
 
+static ProjLevels scene_levels(const FuseScene& s) { return {s.nlevels, s.sf.data(), s.isig.data(), s.logsf, s.th}; }
+
 uint32_t FuseScene::eval(int k, const float* P3, const float* Pn, float dmin_, float dmax_, const uint8_t* desc) const {
-  FuseKf kf;
-  if (!shadow.empty()) {
-    kf = fuse_kf(*shadow[k]);
-  } else {
-    const int32_t f0 = feat_off[k];
-    kf = {rec.data() + FSM_REC_FLOATS * (size_t)k, cell_off.data() + (size_t)k * (FSM_CELLS + 1), cell_idx.data() + f0, kxy.data() + 2 * (size_t)f0, koct.data() + f0,
-          kdesc.data() + 32 * (size_t)f0};
-  }
-  return (isig.empty() ? fuse_pair_host<false> : fuse_pair_host<true>)(kf.rec, pose.data() + FSM_POSE_FLOATS * (size_t)k, kf.cell_off, kf.cell_idx, kf.kxy, kf.koct, kf.kdesc,
-                                                                       P3, Pn, dmin_, dmax_, desc, nlevels, logsf, th, sf.data(), isig.data(), nullptr, nullptr);
+  const FuseKf kf = shadow.empty() ? FlatKfs(rec.data(), feat_off.data(), kxy.data(), koct.data(), kdesc.data(), cell_off.data(), cell_idx.data())(k) : fuse_kf(*shadow[k]);
+  return (isig.empty() ? proj_pair_host<false, false, false> : proj_pair_host<true, false, false>)(kf, pose.data() + FSM_POSE_FLOATS * (size_t)k, nullptr, scene_levels(*this),
+                                                                                                 P3, Pn, dmin_, dmax_, desc, nullptr, nullptr);
 }
 
+// One point of a Fuse call whose answer the table predicts: word w of keyframe k and the snapshot's point g, whose descriptor is desc (nullable) by now.  The gates
+// read nothing a Fuse call changes; a pair that reached the window and whose descriptor has changed is evaluated again.
+static void fuse_resolve_point(const FuseScene& s, uint32_t w, int k, size_t g, const uint8_t* desc, long long& n_reeval, int32_t& bestIdx, int32_t& bestDist, int& nFused) {
+  if ((w >> 29) < FSM_EMPTY) return;
+  if (desc && std::memcmp(desc, s.pdesc.data() + 32 * g, 32) != 0) {
+    w = s.eval(k, s.pos.data() + 3 * g, s.normal.data() + 3 * g, s.dmin[g], s.dmax[g], desc);
+    n_reeval++;
+  }
+  sin_answer(w, bestIdx, bestDist, nFused);
+}
+
+// ---- the host evaluators: the device entry's checks (csrc/fuse_math.h), a keyframe source, one walk; -1 where the entry returns CCM_E_ARG --------------------
 int fuse_sim3_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
                         const int32_t* cell_off, const int32_t* cell_idx, const float* Scw, int nlevels, const float* scale_factors, float logScaleFactor, float th, int P,
                         const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc, uint32_t* table, int32_t* n_valid,
                         int32_t* n_hit, float* uv, int32_t* n_cand) {
   if (fsm_check_args(K, P, feat_off, cell_off, cell_idx, nlevels, th)) return -1;
-  const size_t F = K ? (size_t)feat_off[K] : 0;
-  if (!scale_factors || (K > 0 && (!kf_rec || !Scw || !n_valid || !n_hit)) || (P > 0 && (!pos || !normal || !min_dist || !max_dist || !pt_desc)) ||
-      (K > 0 && P > 0 && !table) || (F && (!feat_xy || !feat_octave || !feat_desc)))
+  if (fsm_check_kf_pointers(K, P, kf_rec, Scw, scale_factors, pos, normal, min_dist, max_dist, pt_desc, table, n_valid, n_hit,
+                            fsm_feats_ok(K ? (size_t)feat_off[K] : 0, feat_xy, feat_octave, feat_desc)))
     return -1;
-  // the jobs (k, 0, P): every keyframe against all points, keyframe-major
-  std::vector<float> pose(FSM_POSE_FLOATS * (size_t)K);
-  std::vector<int32_t> jk((size_t)K), j0((size_t)K, 0), jn((size_t)K, P);
-  for (int k = 0; k < K; k++) { jk[k] = k; fsm_decompose_scw(Scw + 12 * (size_t)k, pose.data() + FSM_POSE_FLOATS * (size_t)k); }
-  fuse_jobs_host<false>(kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off, cell_idx, pose.data(), nlevels, scale_factors, nullptr, logScaleFactor, th, pos, normal,
-                        min_dist, max_dist, pt_desc, K, jk.data(), j0.data(), jn.data(), F, table, n_valid, n_hit, uv, n_cand);
+  proj_kf_major_host<false>(FlatKfs(K, kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off, cell_idx), K, Scw, nullptr, nullptr,
+                            {nlevels, scale_factors, nullptr, logScaleFactor, th}, {P, pos, normal, min_dist, max_dist, pt_desc}, table, n_valid, n_hit, uv, n_cand);
   return 0;
-}
-
-SearchAndFuseBatch::SearchAndFuseBatch(HipContext* ctx, const KeyFrames& kfs, const Points& pts, int nlevels, const float* scale_factors, float logScaleFactor, float th)
-    : K_(kfs.K), P_(pts.P) {
-  const int K = K_, P = P_;
-  if (K < 0 || P < 0 || !scale_factors || nlevels < 1 || nlevels > FSM_MAX_LEVELS) throw infrastructure_ex("SearchAndFuseBatch: bad arguments");
-  table_.assign((size_t)K * (size_t)P, 0); n_valid_.assign((size_t)K, 0); n_hit_.assign((size_t)K, 0);
-  if (ctx) {
-    check(ccm_fuse_sim3_eval(ctx->get(), K, kfs.rec, kfs.feat_off, kfs.feat_xy, kfs.feat_octave, kfs.feat_desc, kfs.cell_off, kfs.cell_idx, kfs.Scw, nlevels, scale_factors,
-                             logScaleFactor, th, P, pts.pos, pts.normal, pts.min_dist, pts.max_dist, pts.desc, table_.data(), n_valid_.data(), n_hit_.data(), nullptr),
-          ctx->get(), "ccm_fuse_sim3_eval");
-  } else if (fuse_sim3_eval_host(K, kfs.rec, kfs.feat_off, kfs.feat_xy, kfs.feat_octave, kfs.feat_desc, kfs.cell_off, kfs.cell_idx, kfs.Scw, nlevels, scale_factors,
-                                 logScaleFactor, th, P, pts.pos, pts.normal, pts.min_dist, pts.max_dist, pts.desc, table_.data(), n_valid_.data(), n_hit_.data(), nullptr,
-                                 nullptr)) {
-    throw infrastructure_ex("SearchAndFuseBatch: bad arguments");
-  }
-  // the arguments are valid from here on: what resolve may have to evaluate again
-  std::vector<float> pose(FSM_POSE_FLOATS * (size_t)K);
-  for (int k = 0; k < K; k++) fsm_decompose_scw(kfs.Scw + 12 * (size_t)k, pose.data() + FSM_POSE_FLOATS * (size_t)k);
-  scene_.copy(kfs, pose.data(), pts, nlevels, scale_factors, nullptr, logScaleFactor, th);
-}
-
-int SearchAndFuseBatch::resolve(int k, const uint8_t* skip_now, const uint8_t* desc_now, std::vector<int32_t>& bestIdx, std::vector<int32_t>& bestDist) {
-  if (k < 0 || k >= K_) throw infrastructure_ex("SearchAndFuseBatch::resolve: keyframe out of range");
-  bestIdx.assign((size_t)P_, -1); bestDist.assign((size_t)P_, INT_MAX);
-  const FuseScene& s = scene_;
-  int nFused = 0;
-  for (int i = 0; i < P_; i++) {
-    if (skip_now && skip_now[i]) continue;
-    uint32_t w = table_[(size_t)k * P_ + i];
-    if ((w >> 29) < FSM_EMPTY) continue;                       // the gates read nothing a Fuse call changes
-    if (desc_now && std::memcmp(desc_now + 32 * (size_t)i, s.pdesc.data() + 32 * (size_t)i, 32) != 0) {
-      w = s.eval(k, s.pos.data() + 3 * (size_t)i, s.normal.data() + 3 * (size_t)i, s.dmin[i], s.dmax[i], desc_now + 32 * (size_t)i);
-      n_reeval_++;
-    }
-    sin_answer(w, bestIdx[i], bestDist[i], nFused);
-  }
-  return nFused;
 }
 
 int fuse_pose_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
@@ -1910,91 +1898,55 @@ int fuse_pose_eval_host(int K, const float* kf_rec, const int32_t* feat_off, con
   if (fsm_check_args(K, P, feat_off, cell_off, cell_idx, nlevels, th)) return -1;
   int64_t total = 0, tiles = 0;
   if (fpm_check_jobs(J, K, P, job_kf, job_pt0, job_n, &total, &tiles)) return -1;
-  const size_t F = K ? (size_t)feat_off[K] : 0;
-  if (!scale_factors || !inv_level_sigma2 || (K > 0 && (!kf_rec || !pose)) || (J > 0 && (!n_valid || !n_hit)) ||
-      (P > 0 && (!pos || !normal || !min_dist || !max_dist || !pt_desc)) || (total > 0 && !table) || (F && (!feat_xy || !feat_octave || !feat_desc)))
+  if (fsm_check_job_pointers(K, P, J, total, true, kf_rec, pose, scale_factors, inv_level_sigma2, pos, normal, min_dist, max_dist, pt_desc, table, n_valid, n_hit,
+                             fsm_feats_ok(K ? (size_t)feat_off[K] : 0, feat_xy, feat_octave, feat_desc)))
     return -1;
-  fuse_jobs_host<true>(kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off, cell_idx, pose, nlevels, scale_factors, inv_level_sigma2, logScaleFactor, th, pos, normal,
-                       min_dist, max_dist, pt_desc, J, job_kf, job_pt0, job_n, F, table, n_valid, n_hit, uv, n_cand);
+  proj_jobs_host<true, false, false>(FlatKfs(K, kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off, cell_idx), pose, nullptr, nullptr,
+                                     {nlevels, scale_factors, inv_level_sigma2, logScaleFactor, th}, {P, pos, normal, min_dist, max_dist, pt_desc}, J, job_kf, job_pt0,
+                                     job_n, table, n_valid, n_hit, uv, n_cand);
   return 0;
 }
 
-SearchInNeighborsBatch::SearchInNeighborsBatch(HipContext* ctx, const KeyFrames& kfs, int n_calls, const int32_t* target, int current, const Points& pts, int n_current,
-                                               int nlevels, const float* scale_factors, const float* inv_level_sigma2, float logScaleFactor, float th)
-    : K_(kfs.K), C_(n_calls), cur_(current), P1_(n_current), P2_(pts.P - n_current) {
-  const int K = K_, P = pts.P, C = C_;
-  if (K < 0 || P < 0 || C < 0 || n_current < 0 || n_current > P || (C > 0 && !target) || !scale_factors || !inv_level_sigma2 || nlevels < 1 || nlevels > FSM_MAX_LEVELS ||
-      (int64_t)C * n_current + P2_ > (int64_t)INT32_MAX)
-    throw infrastructure_ex("SearchInNeighborsBatch: bad arguments");
-  // C jobs (target of call c, the current keyframe's points) and one (current keyframe, the predicted candidates); without a current keyframe the last job is left out
-  std::vector<int32_t> jk, j0, jn;
-  for (int c = 0; c < C; c++) { jk.push_back(target[c]); j0.push_back(0); jn.push_back(P1_); }
-  if (current >= 0) { jk.push_back(current); j0.push_back(P1_); jn.push_back(P2_); }
-  else if (P2_ > 0) throw infrastructure_ex("SearchInNeighborsBatch: candidates without a current keyframe");
-  const int J = (int)jk.size();
-  table_.assign((size_t)C * (size_t)P1_ + (size_t)P2_, 0); n_valid_.assign((size_t)J, 0); n_hit_.assign((size_t)J, 0);
-  if (ctx) {
-    check(ccm_fuse_pose_eval(ctx->get(), K, kfs.rec, kfs.feat_off, kfs.feat_xy, kfs.feat_octave, kfs.feat_desc, kfs.cell_off, kfs.cell_idx, kfs.pose, nlevels, scale_factors,
-                             inv_level_sigma2, logScaleFactor, th, P, pts.pos, pts.normal, pts.min_dist, pts.max_dist, pts.desc, J, jk.data(), j0.data(), jn.data(),
-                             table_.data(), n_valid_.data(), n_hit_.data(), nullptr),
-          ctx->get(), "ccm_fuse_pose_eval");
-  } else if (fuse_pose_eval_host(K, kfs.rec, kfs.feat_off, kfs.feat_xy, kfs.feat_octave, kfs.feat_desc, kfs.cell_off, kfs.cell_idx, kfs.pose, nlevels, scale_factors,
-                                 inv_level_sigma2, logScaleFactor, th, P, pts.pos, pts.normal, pts.min_dist, pts.max_dist, pts.desc, J, jk.data(), j0.data(), jn.data(),
-                                 table_.data(), n_valid_.data(), n_hit_.data(), nullptr, nullptr)) {
-    throw infrastructure_ex("SearchInNeighborsBatch: bad arguments");
-  }
-  // the arguments are valid from here on: what the resolves may have to evaluate again
-  target_.assign(jk.begin(), jk.begin() + C);
-  scene_.copy(kfs, kfs.pose, pts, nlevels, scale_factors, inv_level_sigma2, logScaleFactor, th);
+int sim3_project_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
+                           const int32_t* cell_off, const int32_t* cell_idx, const float* Scw, const int32_t* skip_off, const uint8_t* feat_skip, int nlevels,
+                           const float* scale_factors, float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist,
+                           const float* max_dist, const uint8_t* pt_desc, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv) {
+  if (fsm_check_args(K, P, feat_off, cell_off, cell_idx, nlevels, th)) return -1;
+  if (fsm_check_kf_pointers(K, P, kf_rec, Scw, scale_factors, pos, normal, min_dist, max_dist, pt_desc, table, n_valid, n_hit,
+                            fsm_feats_ok(K ? (size_t)feat_off[K] : 0, feat_xy, feat_octave, feat_desc)))
+    return -1;
+  std::vector<int32_t> kf_n((size_t)K);
+  for (int k = 0; k < K; k++) kf_n[k] = feat_off[k + 1] - feat_off[k];
+  if (fsm_check_skip(K, skip_off, feat_skip, kf_n.data())) return -1;
+  proj_kf_major_host<true>(FlatKfs(K, kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off, cell_idx), K, Scw, skip_off, feat_skip,
+                           {nlevels, scale_factors, nullptr, logScaleFactor, th}, {P, pos, normal, min_dist, max_dist, pt_desc}, table, n_valid, n_hit, uv, nullptr);
+  return 0;
 }
 
-int SearchInNeighborsBatch::resolve(int c, const uint8_t* skip_now, const uint8_t* desc_now, std::vector<int32_t>& bestIdx, std::vector<int32_t>& bestDist) {
-  if (c < 0 || c >= C_) throw infrastructure_ex("SearchInNeighborsBatch::resolve: call out of range");
-  bestIdx.assign((size_t)P1_, -1); bestDist.assign((size_t)P1_, 256);
-  const FuseScene& s = scene_;
-  int nFused = 0;
-  for (int i = 0; i < P1_; i++) {
-    if (skip_now && skip_now[i]) continue;
-    uint32_t w = table_[(size_t)c * P1_ + i];
-    if ((w >> 29) < FSM_EMPTY) continue;                       // the gates read nothing a Fuse call changes
-    if (desc_now && std::memcmp(desc_now + 32 * (size_t)i, s.pdesc.data() + 32 * (size_t)i, 32) != 0) {
-      w = s.eval(target_[c], s.pos.data() + 3 * (size_t)i, s.normal.data() + 3 * (size_t)i, s.dmin[i], s.dmax[i], desc_now + 32 * (size_t)i);
-      n_reeval_++;
-    }
-    sin_answer(w, bestIdx[i], bestDist[i], nFused);
-  }
-  return nFused;
+// the pair form's walk on either source, from its validated arguments
+template <class KfOf>
+static void sim3_pair_walk(const KfOf& kf_of, int nlevels, const float* scale_factors, float logScaleFactor, float th, int P, const float* pos, const float* min_dist,
+                           const float* max_dist, const uint8_t* pt_desc, int J, const int32_t* job_kf, const float* job_K4, const float* job_src_pose, const float* job_T,
+                           const int32_t* job_pt0, const int32_t* job_n, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv) {
+  std::vector<float> jobs(SSM_JOB_FLOATS * (size_t)J);
+  ssm_pack_jobs(J, job_K4, job_src_pose, job_T, jobs.data());
+  proj_jobs_host<false, false, true>(kf_of, jobs.data(), nullptr, nullptr, {nlevels, scale_factors, nullptr, logScaleFactor, th},
+                                     {P, pos, nullptr, min_dist, max_dist, pt_desc}, J, job_kf, job_pt0, job_n, table, n_valid, n_hit, uv, nullptr);
 }
 
-int SearchInNeighborsBatch::resolve_current(int n, const int32_t* slot, const uint8_t* skip_now, const uint8_t* desc_now, const Points& fresh,
-                                            std::vector<int32_t>& bestIdx, std::vector<int32_t>& bestDist) {
-  if (n < 0 || (n > 0 && !slot) || cur_ < 0) throw infrastructure_ex("SearchInNeighborsBatch::resolve_current: bad arguments");
-  bestIdx.assign((size_t)n, -1); bestDist.assign((size_t)n, 256);
-  const FuseScene& sc = scene_;
-  int nFused = 0;
-  for (int i = 0; i < n; i++) {
-    if (skip_now && skip_now[i]) continue;
-    const int s = slot[i];
-    if (s >= P2_ || s < -1) throw infrastructure_ex("SearchInNeighborsBatch::resolve_current: slot out of range");
-    uint32_t w;
-    if (s < 0) {                                                 // a candidate the build did not predict: from what the caller passes for it
-      if (!fresh.pos || !fresh.normal || !fresh.min_dist || !fresh.max_dist || !fresh.desc || fresh.P < n)
-        throw infrastructure_ex("SearchInNeighborsBatch::resolve_current: an unpredicted candidate without fresh data");
-      w = sc.eval(cur_, fresh.pos + 3 * (size_t)i, fresh.normal + 3 * (size_t)i, fresh.min_dist[i], fresh.max_dist[i],
-                  desc_now ? desc_now + 32 * (size_t)i : fresh.desc + 32 * (size_t)i);
-      n_unpredicted_++;
-    } else {
-      w = table_[(size_t)C_ * P1_ + s];
-      if ((w >> 29) < FSM_EMPTY) continue;
-      const size_t g = (size_t)P1_ + (size_t)s;
-      if (desc_now && std::memcmp(desc_now + 32 * (size_t)i, sc.pdesc.data() + 32 * g, 32) != 0) {
-        w = sc.eval(cur_, sc.pos.data() + 3 * g, sc.normal.data() + 3 * g, sc.dmin[g], sc.dmax[g], desc_now + 32 * (size_t)i);
-        n_reeval_++;
-      }
-    }
-    sin_answer(w, bestIdx[i], bestDist[i], nFused);
-  }
-  return nFused;
+int sim3_pair_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
+                        const int32_t* cell_off, const int32_t* cell_idx, int nlevels, const float* scale_factors, float logScaleFactor, float th, int P, const float* pos,
+                        const float* min_dist, const float* max_dist, const uint8_t* pt_desc, int J, const int32_t* job_kf, const float* job_K4, const float* job_src_pose,
+                        const float* job_T, const int32_t* job_pt0, const int32_t* job_n, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv) {
+  if (fsm_check_args(K, P, feat_off, cell_off, cell_idx, nlevels, th)) return -1;
+  int64_t total = 0, tiles = 0;
+  if (fpm_check_jobs(J, K, P, job_kf, job_pt0, job_n, &total, &tiles) || fsm_check_pair_jobs(J, job_K4, job_src_pose, job_T)) return -1;
+  if (fsm_check_job_pointers(K, P, J, total, false, kf_rec, nullptr, scale_factors, nullptr, pos, nullptr, min_dist, max_dist, pt_desc, table, n_valid, n_hit,
+                             fsm_feats_ok(K ? (size_t)feat_off[K] : 0, feat_xy, feat_octave, feat_desc)))
+    return -1;
+  sim3_pair_walk(FlatKfs(K, kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off, cell_idx), nlevels, scale_factors, logScaleFactor, th, P, pos, min_dist, max_dist,
+                 pt_desc, J, job_kf, job_K4, job_src_pose, job_T, job_pt0, job_n, table, n_valid, n_hit, uv);
+  return 0;
 }
 
 // ---- KeyFrameStore and the batches built on it ----------------------------------------------------------
@@ -2097,33 +2049,24 @@ void FuseScene::hold(std::vector<std::shared_ptr<const KfShadow>> kfs, const flo
 }
 
 // the shadows of keys[0 .. K); false when one is not live
-static bool store_shadows(const KeyFrameStore& store, int K, const int64_t* keys, std::vector<std::shared_ptr<const KfShadow>>& out) {
+static bool store_shadows(const KeyFrameStore& store, int K, const int64_t* keys, Shadows& out) {
   out.resize((size_t)(K > 0 ? K : 0));
   for (int k = 0; k < K; k++)
     if (!(out[k] = store.shadow(keys[k]))) return false;
   return true;
 }
 
-static int sim3_resident_host(const std::vector<std::shared_ptr<const KfShadow>>& kfs, int K, const float* Scw, int nlevels, const float* scale_factors,
-                              float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist,
-                              const uint8_t* pt_desc, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv) {
-  std::vector<float> pose(FSM_POSE_FLOATS * (size_t)K);
-  std::vector<int32_t> jk((size_t)K), j0((size_t)K, 0), jn((size_t)K, P);
-  for (int k = 0; k < K; k++) { jk[k] = k; fsm_decompose_scw(Scw + 12 * (size_t)k, pose.data() + FSM_POSE_FLOATS * (size_t)k); }
-  fuse_jobs_eval<false>([&](int k) { return fuse_kf(*kfs[k]); }, pose.data(), nlevels, scale_factors, nullptr, logScaleFactor, th, pos, normal, min_dist, max_dist,
-                        pt_desc, K, jk.data(), j0.data(), jn.data(), table, n_valid, n_hit, uv, nullptr);
-  return 0;
-}
 
 int fuse_sim3_eval_resident_host(const KeyFrameStore& store, int K, const int64_t* keys, const float* Scw, int nlevels, const float* scale_factors, float logScaleFactor,
                                  float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc,
                                  uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv) {
   if (fsm_check_scalars(K, P, nlevels, th)) return -1;
-  if (!scale_factors || (K > 0 && (!keys || !Scw || !n_valid || !n_hit)) || (P > 0 && (!pos || !normal || !min_dist || !max_dist || !pt_desc)) || (K > 0 && P > 0 && !table))
-    return -1;
-  std::vector<std::shared_ptr<const KfShadow>> kfs;
+  if (fsm_check_kf_pointers(K, P, keys, Scw, scale_factors, pos, normal, min_dist, max_dist, pt_desc, table, n_valid, n_hit, true)) return -1;
+  Shadows kfs;
   if (!store_shadows(store, K, keys, kfs)) return -1;
-  return sim3_resident_host(kfs, K, Scw, nlevels, scale_factors, logScaleFactor, th, P, pos, normal, min_dist, max_dist, pt_desc, table, n_valid, n_hit, uv);
+  proj_kf_major_host<false>(ShadowKfs{kfs}, K, Scw, nullptr, nullptr, {nlevels, scale_factors, nullptr, logScaleFactor, th}, {P, pos, normal, min_dist, max_dist, pt_desc},
+                            table, n_valid, n_hit, uv, nullptr);
+  return 0;
 }
 
 int fuse_pose_eval_resident_host(const KeyFrameStore& store, int K, const int64_t* keys, const float* pose, int nlevels, const float* scale_factors,
@@ -2133,196 +2076,12 @@ int fuse_pose_eval_resident_host(const KeyFrameStore& store, int K, const int64_
   if (fsm_check_scalars(K, P, nlevels, th)) return -1;
   int64_t total = 0, tiles = 0;
   if (fpm_check_jobs(J, K, P, job_kf, job_pt0, job_n, &total, &tiles)) return -1;
-  if (!scale_factors || !inv_level_sigma2 || (K > 0 && (!keys || !pose)) || (J > 0 && (!n_valid || !n_hit)) ||
-      (P > 0 && (!pos || !normal || !min_dist || !max_dist || !pt_desc)) || (total > 0 && !table))
+  if (fsm_check_job_pointers(K, P, J, total, true, keys, pose, scale_factors, inv_level_sigma2, pos, normal, min_dist, max_dist, pt_desc, table, n_valid, n_hit, true))
     return -1;
-  std::vector<std::shared_ptr<const KfShadow>> kfs;
+  Shadows kfs;
   if (!store_shadows(store, K, keys, kfs)) return -1;
-  fuse_jobs_eval<true>([&](int k) { return fuse_kf(*kfs[k]); }, pose, nlevels, scale_factors, inv_level_sigma2, logScaleFactor, th, pos, normal, min_dist, max_dist, pt_desc,
-                       J, job_kf, job_pt0, job_n, table, n_valid, n_hit, uv, nullptr);
-  return 0;
-}
-
-SearchAndFuseBatch::SearchAndFuseBatch(KeyFrameStore& store, HipContext* ctx, int K, const int64_t* keys, const float* Scw, const Points& pts, int nlevels,
-                                       const float* scale_factors, float logScaleFactor, float th)
-    : K_(K), P_(pts.P) {
-  const int P = P_;
-  if (K < 0 || P < 0 || !scale_factors || nlevels < 1 || nlevels > FSM_MAX_LEVELS || (K > 0 && (!keys || !Scw))) throw infrastructure_ex("SearchAndFuseBatch: bad arguments");
-  if (!store.host_only() && !ctx) throw infrastructure_ex("SearchAndFuseBatch: a device store needs the calling thread's context");
-  // the shadows first: what is held here stays valid whatever the store does from now on
-  std::vector<std::shared_ptr<const KfShadow>> kfs;
-  if (!store_shadows(store, K, keys, kfs)) throw infrastructure_ex("SearchAndFuseBatch: a key is not in the store");
-  table_.assign((size_t)K * (size_t)P, 0); n_valid_.assign((size_t)K, 0); n_hit_.assign((size_t)K, 0);
-  if (!store.host_only()) {
-    check(ccm_fuse_sim3_eval_resident(ctx->get(), store.handle(), K, keys, Scw, nlevels, scale_factors, logScaleFactor, th, P, pts.pos, pts.normal, pts.min_dist,
-                                      pts.max_dist, pts.desc, table_.data(), n_valid_.data(), n_hit_.data(), nullptr),
-          ctx->get(), "ccm_fuse_sim3_eval_resident");
-  } else {
-    if (fsm_check_scalars(K, P, nlevels, th) || (P > 0 && (!pts.pos || !pts.normal || !pts.min_dist || !pts.max_dist || !pts.desc)))
-      throw infrastructure_ex("SearchAndFuseBatch: bad arguments");
-    sim3_resident_host(kfs, K, Scw, nlevels, scale_factors, logScaleFactor, th, P, pts.pos, pts.normal, pts.min_dist, pts.max_dist, pts.desc, table_.data(),
-                       n_valid_.data(), n_hit_.data(), nullptr);
-  }
-  std::vector<float> pose(FSM_POSE_FLOATS * (size_t)K);
-  for (int k = 0; k < K; k++) fsm_decompose_scw(Scw + 12 * (size_t)k, pose.data() + FSM_POSE_FLOATS * (size_t)k);
-  scene_.hold(std::move(kfs), pose.data(), pts, nlevels, scale_factors, nullptr, logScaleFactor, th);
-}
-
-SearchInNeighborsBatch::SearchInNeighborsBatch(KeyFrameStore& store, HipContext* ctx, int K, const int64_t* keys, const float* pose, int n_calls, const int32_t* target,
-                                               int current, const Points& pts, int n_current, int nlevels, const float* scale_factors, const float* inv_level_sigma2,
-                                               float logScaleFactor, float th)
-    : K_(K), C_(n_calls), cur_(current), P1_(n_current), P2_(pts.P - n_current) {
-  const int P = pts.P, C = C_;
-  if (K < 0 || P < 0 || C < 0 || n_current < 0 || n_current > P || (C > 0 && !target) || !scale_factors || !inv_level_sigma2 || nlevels < 1 || nlevels > FSM_MAX_LEVELS ||
-      (int64_t)C * n_current + P2_ > (int64_t)INT32_MAX || (K > 0 && (!keys || !pose)))
-    throw infrastructure_ex("SearchInNeighborsBatch: bad arguments");
-  if (!store.host_only() && !ctx) throw infrastructure_ex("SearchInNeighborsBatch: a device store needs the calling thread's context");
-  std::vector<int32_t> jk, j0, jn;
-  for (int c = 0; c < C; c++) { jk.push_back(target[c]); j0.push_back(0); jn.push_back(P1_); }
-  if (current >= 0) { jk.push_back(current); j0.push_back(P1_); jn.push_back(P2_); }
-  else if (P2_ > 0) throw infrastructure_ex("SearchInNeighborsBatch: candidates without a current keyframe");
-  const int J = (int)jk.size();
-  std::vector<std::shared_ptr<const KfShadow>> kfs;
-  if (!store_shadows(store, K, keys, kfs)) throw infrastructure_ex("SearchInNeighborsBatch: a key is not in the store");
-  table_.assign((size_t)C * (size_t)P1_ + (size_t)P2_, 0); n_valid_.assign((size_t)J, 0); n_hit_.assign((size_t)J, 0);
-  if (!store.host_only()) {
-    check(ccm_fuse_pose_eval_resident(ctx->get(), store.handle(), K, keys, pose, nlevels, scale_factors, inv_level_sigma2, logScaleFactor, th, P, pts.pos, pts.normal,
-                                      pts.min_dist, pts.max_dist, pts.desc, J, jk.data(), j0.data(), jn.data(), table_.data(), n_valid_.data(), n_hit_.data(), nullptr),
-          ctx->get(), "ccm_fuse_pose_eval_resident");
-  } else {
-    int64_t total = 0, tiles = 0;
-    if (fsm_check_scalars(K, P, nlevels, th) || fpm_check_jobs(J, K, P, jk.data(), j0.data(), jn.data(), &total, &tiles) ||
-        (P > 0 && (!pts.pos || !pts.normal || !pts.min_dist || !pts.max_dist || !pts.desc)))
-      throw infrastructure_ex("SearchInNeighborsBatch: bad arguments");
-    fuse_jobs_eval<true>([&](int k) { return fuse_kf(*kfs[k]); }, pose, nlevels, scale_factors, inv_level_sigma2, logScaleFactor, th, pts.pos, pts.normal, pts.min_dist,
-                         pts.max_dist, pts.desc, J, jk.data(), j0.data(), jn.data(), table_.data(), n_valid_.data(), n_hit_.data(), nullptr, nullptr);
-  }
-  target_.assign(jk.begin(), jk.begin() + C);
-  scene_.hold(std::move(kfs), pose, pts, nlevels, scale_factors, inv_level_sigma2, logScaleFactor, th);
-}
-
-// ---- ComputeSim3's two projected searches: host evaluators, Sim3ProjectionSearch, SearchBySim3Batch ------------------------------
-// one (keyframe, point) pair of SearchByProjection(pKF, Scw, ...): Fuse's Sim3 pair with the skip mask
-static uint32_t sim3_project_pair_host(const FuseKf& kf, const float* pose, const uint8_t* skip, const float* P3, const float* Pn, float dmin, float dmax,
-                                       const uint8_t* pdesc, int nlevels, float logsf, float th, const float* sf, float* uv) {
-  float u, v; int level;
-  const int st = fsm_gate(kf.rec, pose, P3, Pn, dmin, dmax, nlevels, logsf, u, v, level);
-  if (uv) { uv[0] = u; uv[1] = v; }
-  if (st != FSM_EMPTY) return fsm_pack(st, 0, FSM_NO_DIST, FSM_NO_IDX);
-  uint32_t q[8];
-  fsm_load_desc(pdesc, q);
-  return fsm_window_best<false, true>(kf.rec, kf.cell_off, kf.cell_idx, kf.kxy, kf.koct, kf.kdesc, u, v, level, th, sf, nullptr, q, nullptr, skip, FSM_TH_LOW);
-}
-
-// every (keyframe, point) pair, keyframe-major; the arguments are valid
-template <class KfOf>
-static void sim3_project_eval(KfOf kf_of, int K, const float* Scw, const int32_t* skip_off, const uint8_t* feat_skip, int nlevels, const float* scale_factors,
-                              float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist,
-                              const uint8_t* pt_desc, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv) {
-  for (int k = 0; k < K; k++) {
-    float pose[FSM_POSE_FLOATS];
-    fsm_decompose_scw(Scw + 12 * (size_t)k, pose);
-    const FuseKf kf = kf_of(k);
-    n_valid[k] = n_hit[k] = 0;
-    for (int i = 0; i < P; i++) {
-      const size_t e = (size_t)k * (size_t)P + (size_t)i;
-      const uint32_t w = sim3_project_pair_host(kf, pose, feat_skip + skip_off[k], pos + 3 * (size_t)i, normal + 3 * (size_t)i, min_dist[i], max_dist[i],
-                                                pt_desc + 32 * (size_t)i, nlevels, logScaleFactor, th, scale_factors, uv ? uv + 2 * e : nullptr);
-      table[e] = w;
-      n_valid[k] += (w >> 29) >= FSM_EMPTY;
-      n_hit[k] += (w >> 29) == FSM_HIT;
-    }
-  }
-}
-
-// every pair of a list of SearchBySim3 jobs, the jobs' words one after the other; the arguments are valid
-template <class KfOf>
-static void sim3_pair_eval(KfOf kf_of, int nlevels, const float* scale_factors, float logScaleFactor, float th, const float* pos, const float* min_dist,
-                           const float* max_dist, const uint8_t* pt_desc, int J, const int32_t* job_kf, const float* job_K4, const float* job_src_pose, const float* job_T,
-                           const int32_t* job_pt0, const int32_t* job_n, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv) {
-  size_t e = 0;
-  for (int j = 0; j < J; j++) {
-    n_valid[j] = n_hit[j] = 0;
-    const FuseKf kf = kf_of(job_kf[j]);
-    float job[SSM_JOB_FLOATS];
-    std::memcpy(job, job_K4 + 4 * (size_t)j, 4 * sizeof(float)); std::memcpy(job + 4, job_src_pose + 12 * (size_t)j, 12 * sizeof(float));
-    std::memcpy(job + 16, job_T + 12 * (size_t)j, 12 * sizeof(float));
-    for (int i = job_pt0[j]; i < job_pt0[j] + job_n[j]; i++, e++) {
-      float u, v; int level;
-      const int st = ssm_gate(kf.rec, job, pos + 3 * (size_t)i, min_dist[i], max_dist[i], nlevels, logScaleFactor, u, v, level);
-      if (uv) { uv[2 * e] = u; uv[2 * e + 1] = v; }
-      uint32_t w = fsm_pack(st, 0, FSM_NO_DIST, FSM_NO_IDX);
-      if (st == FSM_EMPTY) {
-        uint32_t q[8];
-        fsm_load_desc(pt_desc + 32 * (size_t)i, q);
-        w = fsm_window_best<false>(kf.rec, kf.cell_off, kf.cell_idx, kf.kxy, kf.koct, kf.kdesc, u, v, level, th, scale_factors, nullptr, q, nullptr, nullptr, FSM_TH_HIGH);
-      }
-      table[e] = w;
-      n_valid[j] += (w >> 29) >= FSM_EMPTY;
-      n_hit[j] += (w >> 29) == FSM_HIT;
-    }
-  }
-}
-
-static bool sim3_project_pointers_ok(int K, int P, const void* keys_or_rec, const float* Scw, const float* scale_factors, const float* pos, const float* normal,
-                                     const float* min_dist, const float* max_dist, const uint8_t* pt_desc, const uint32_t* table, const int32_t* n_valid,
-                                     const int32_t* n_hit) {
-  return scale_factors && !(K > 0 && (!keys_or_rec || !Scw || !n_valid || !n_hit)) && !(P > 0 && (!pos || !normal || !min_dist || !max_dist || !pt_desc)) &&
-         !(K > 0 && P > 0 && !table);
-}
-static bool sim3_pair_pointers_ok(int K, int P, int J, int64_t total, const void* keys_or_rec, const float* scale_factors, const float* pos, const float* min_dist,
-                                  const float* max_dist, const uint8_t* pt_desc, const uint32_t* table, const int32_t* n_valid, const int32_t* n_hit) {
-  return scale_factors && !(K > 0 && !keys_or_rec) && !(J > 0 && (!n_valid || !n_hit)) && !(P > 0 && (!pos || !min_dist || !max_dist || !pt_desc)) &&
-         !(total > 0 && !table);
-}
-
-// the flat keyframe arrays as FuseKf, cell_idx narrowed to 16 bits into idx16
-struct FlatKfs {
-  std::vector<uint16_t> idx16;
-  const float* rec; const int32_t* feat_off; const float* xy; const uint8_t* oct; const uint8_t* desc; const int32_t* cell_off;
-  FlatKfs(int K, const float* kf_rec, const int32_t* feat_off_, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc, const int32_t* cell_off_,
-          const int32_t* cell_idx)
-      : rec(kf_rec), feat_off(feat_off_), xy(feat_xy), oct(feat_octave), desc(feat_desc), cell_off(cell_off_) {
-    const size_t F = K ? (size_t)feat_off[K] : 0;
-    idx16.resize(F);
-    for (size_t f = 0; f < F; f++) idx16[f] = (uint16_t)cell_idx[f];
-  }
-  FuseKf operator()(int k) const {
-    const int32_t f0 = feat_off[k];
-    return FuseKf{rec + FSM_REC_FLOATS * (size_t)k, cell_off + (size_t)k * (FSM_CELLS + 1), idx16.data() + f0, xy + 2 * (size_t)f0, oct + f0, desc + 32 * (size_t)f0};
-  }
-};
-
-int sim3_project_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
-                           const int32_t* cell_off, const int32_t* cell_idx, const float* Scw, const int32_t* skip_off, const uint8_t* feat_skip, int nlevels,
-                           const float* scale_factors, float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist,
-                           const float* max_dist, const uint8_t* pt_desc, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv) {
-  if (fsm_check_args(K, P, feat_off, cell_off, cell_idx, nlevels, th)) return -1;
-  const size_t F = K ? (size_t)feat_off[K] : 0;
-  if (!sim3_project_pointers_ok(K, P, kf_rec, Scw, scale_factors, pos, normal, min_dist, max_dist, pt_desc, table, n_valid, n_hit) ||
-      (F && (!feat_xy || !feat_octave || !feat_desc)))
-    return -1;
-  std::vector<int32_t> kf_n((size_t)K);
-  for (int k = 0; k < K; k++) kf_n[k] = feat_off[k + 1] - feat_off[k];
-  if (fsm_check_skip(K, skip_off, feat_skip, kf_n.data())) return -1;
-  const FlatKfs kfs(K, kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off, cell_idx);
-  sim3_project_eval(kfs, K, Scw, skip_off, feat_skip, nlevels, scale_factors, logScaleFactor, th, P, pos, normal, min_dist, max_dist, pt_desc, table, n_valid, n_hit, uv);
-  return 0;
-}
-
-int sim3_pair_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
-                        const int32_t* cell_off, const int32_t* cell_idx, int nlevels, const float* scale_factors, float logScaleFactor, float th, int P, const float* pos,
-                        const float* min_dist, const float* max_dist, const uint8_t* pt_desc, int J, const int32_t* job_kf, const float* job_K4, const float* job_src_pose,
-                        const float* job_T, const int32_t* job_pt0, const int32_t* job_n, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv) {
-  if (fsm_check_args(K, P, feat_off, cell_off, cell_idx, nlevels, th)) return -1;
-  int64_t total = 0, tiles = 0;
-  if (fpm_check_jobs(J, K, P, job_kf, job_pt0, job_n, &total, &tiles) || fsm_check_pair_jobs(J, job_K4, job_src_pose, job_T)) return -1;
-  const size_t F = K ? (size_t)feat_off[K] : 0;
-  if (!sim3_pair_pointers_ok(K, P, J, total, kf_rec, scale_factors, pos, min_dist, max_dist, pt_desc, table, n_valid, n_hit) || (F && (!feat_xy || !feat_octave || !feat_desc)))
-    return -1;
-  const FlatKfs kfs(K, kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off, cell_idx);
-  sim3_pair_eval(kfs, nlevels, scale_factors, logScaleFactor, th, pos, min_dist, max_dist, pt_desc, J, job_kf, job_K4, job_src_pose, job_T, job_pt0, job_n, table, n_valid,
-                 n_hit, uv);
+  proj_jobs_host<true, false, false>(ShadowKfs{kfs}, pose, nullptr, nullptr, {nlevels, scale_factors, inv_level_sigma2, logScaleFactor, th},
+                                     {P, pos, normal, min_dist, max_dist, pt_desc}, J, job_kf, job_pt0, job_n, table, n_valid, n_hit, uv, nullptr);
   return 0;
 }
 
@@ -2330,14 +2089,14 @@ int sim3_project_eval_resident_host(const KeyFrameStore& store, int K, const int
                                     const float* scale_factors, float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist,
                                     const float* max_dist, const uint8_t* pt_desc, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv) {
   if (fsm_check_scalars(K, P, nlevels, th)) return -1;
-  if (!sim3_project_pointers_ok(K, P, keys, Scw, scale_factors, pos, normal, min_dist, max_dist, pt_desc, table, n_valid, n_hit)) return -1;
-  std::vector<std::shared_ptr<const KfShadow>> kfs;
+  if (fsm_check_kf_pointers(K, P, keys, Scw, scale_factors, pos, normal, min_dist, max_dist, pt_desc, table, n_valid, n_hit, true)) return -1;
+  Shadows kfs;
   if (!store_shadows(store, K, keys, kfs)) return -1;
-  std::vector<int32_t> kf_n((size_t)(K > 0 ? K : 0));
+  std::vector<int32_t> kf_n((size_t)K);
   for (int k = 0; k < K; k++) kf_n[k] = kfs[k]->n;
   if (fsm_check_skip(K, skip_off, feat_skip, kf_n.data())) return -1;
-  sim3_project_eval([&](int k) { return fuse_kf(*kfs[k]); }, K, Scw, skip_off, feat_skip, nlevels, scale_factors, logScaleFactor, th, P, pos, normal, min_dist, max_dist,
-                    pt_desc, table, n_valid, n_hit, uv);
+  proj_kf_major_host<true>(ShadowKfs{kfs}, K, Scw, skip_off, feat_skip, {nlevels, scale_factors, nullptr, logScaleFactor, th}, {P, pos, normal, min_dist, max_dist, pt_desc},
+                           table, n_valid, n_hit, uv, nullptr);
   return 0;
 }
 
@@ -2348,14 +2107,164 @@ int sim3_pair_eval_resident_host(const KeyFrameStore& store, int K, const int64_
   if (fsm_check_scalars(K, P, nlevels, th)) return -1;
   int64_t total = 0, tiles = 0;
   if (fpm_check_jobs(J, K, P, job_kf, job_pt0, job_n, &total, &tiles) || fsm_check_pair_jobs(J, job_K4, job_src_pose, job_T)) return -1;
-  if (!sim3_pair_pointers_ok(K, P, J, total, keys, scale_factors, pos, min_dist, max_dist, pt_desc, table, n_valid, n_hit)) return -1;
-  std::vector<std::shared_ptr<const KfShadow>> kfs;
+  if (fsm_check_job_pointers(K, P, J, total, false, keys, nullptr, scale_factors, nullptr, pos, nullptr, min_dist, max_dist, pt_desc, table, n_valid, n_hit, true)) return -1;
+  Shadows kfs;
   if (!store_shadows(store, K, keys, kfs)) return -1;
-  sim3_pair_eval([&](int k) { return fuse_kf(*kfs[k]); }, nlevels, scale_factors, logScaleFactor, th, pos, min_dist, max_dist, pt_desc, J, job_kf, job_K4, job_src_pose,
-                 job_T, job_pt0, job_n, table, n_valid, n_hit, uv);
+  sim3_pair_walk(ShadowKfs{kfs}, nlevels, scale_factors, logScaleFactor, th, P, pos, min_dist, max_dist, pt_desc, J, job_kf, job_K4, job_src_pose, job_T, job_pt0, job_n,
+                 table, n_valid, n_hit, uv);
   return 0;
 }
 
+// ---- SearchAndFuseBatch, SearchInNeighborsBatch: the keyframes are the caller's flat arrays (flat) or live keys of a store -----------------------
+SearchAndFuseBatch::SearchAndFuseBatch(HipContext* ctx, const KeyFrames& kfs, const Points& pts, int nlevels, const float* scale_factors, float logScaleFactor, float th)
+    : K_(kfs.K), P_(pts.P) {
+  init(&kfs, nullptr, nullptr, kfs.Scw, ctx, pts, nlevels, scale_factors, logScaleFactor, th);
+}
+SearchAndFuseBatch::SearchAndFuseBatch(KeyFrameStore& store, HipContext* ctx, int K, const int64_t* keys, const float* Scw, const Points& pts, int nlevels,
+                                       const float* scale_factors, float logScaleFactor, float th)
+    : K_(K), P_(pts.P) {
+  init(nullptr, &store, keys, Scw, ctx, pts, nlevels, scale_factors, logScaleFactor, th);
+}
+
+void SearchAndFuseBatch::init(const KeyFrames* flat, KeyFrameStore* store, const int64_t* keys, const float* Scw, HipContext* ctx, const Points& pts, int nlevels,
+                              const float* scale_factors, float logScaleFactor, float th) {
+  const int K = K_, P = P_;
+  if (K < 0 || P < 0 || !scale_factors || nlevels < 1 || nlevels > FSM_MAX_LEVELS || (store && K > 0 && (!keys || !Scw)))
+    throw infrastructure_ex("SearchAndFuseBatch: bad arguments");
+  // the shadows first: what is held here stays valid whatever the store does from now on
+  Shadows shadows;
+  if (store && !store->host_only() && !ctx) throw infrastructure_ex("SearchAndFuseBatch: a device store needs the calling thread's context");
+  if (store && !store_shadows(*store, K, keys, shadows)) throw infrastructure_ex("SearchAndFuseBatch: a key is not in the store");
+  table_.assign((size_t)K * (size_t)P, 0); n_valid_.assign((size_t)K, 0); n_hit_.assign((size_t)K, 0);
+  if (store && !store->host_only()) {
+    check(ccm_fuse_sim3_eval_resident(ctx->get(), store->handle(), K, keys, Scw, nlevels, scale_factors, logScaleFactor, th, P, pts.pos, pts.normal, pts.min_dist,
+                                      pts.max_dist, pts.desc, table_.data(), n_valid_.data(), n_hit_.data(), nullptr),
+          ctx->get(), "ccm_fuse_sim3_eval_resident");
+  } else if (store) {
+    if (fsm_check_scalars(K, P, nlevels, th) || (P > 0 && (!pts.pos || !pts.normal || !pts.min_dist || !pts.max_dist || !pts.desc)))
+      throw infrastructure_ex("SearchAndFuseBatch: bad arguments");
+    proj_kf_major_host<false>(ShadowKfs{shadows}, K, Scw, nullptr, nullptr, {nlevels, scale_factors, nullptr, logScaleFactor, th}, pts, table_.data(), n_valid_.data(),
+                              n_hit_.data(), nullptr, nullptr);
+  } else if (ctx) {
+    check(ccm_fuse_sim3_eval(ctx->get(), K, flat->rec, flat->feat_off, flat->feat_xy, flat->feat_octave, flat->feat_desc, flat->cell_off, flat->cell_idx, Scw, nlevels,
+                             scale_factors, logScaleFactor, th, P, pts.pos, pts.normal, pts.min_dist, pts.max_dist, pts.desc, table_.data(), n_valid_.data(),
+                             n_hit_.data(), nullptr),
+          ctx->get(), "ccm_fuse_sim3_eval");
+  } else if (fuse_sim3_eval_host(K, flat->rec, flat->feat_off, flat->feat_xy, flat->feat_octave, flat->feat_desc, flat->cell_off, flat->cell_idx, Scw, nlevels, scale_factors,
+                                 logScaleFactor, th, P, pts.pos, pts.normal, pts.min_dist, pts.max_dist, pts.desc, table_.data(), n_valid_.data(), n_hit_.data(), nullptr,
+                                 nullptr)) {
+    throw infrastructure_ex("SearchAndFuseBatch: bad arguments");
+  }
+  // the arguments are valid from here on: what resolve may have to evaluate again
+  std::vector<float> pose(FSM_POSE_FLOATS * (size_t)K);
+  for (int k = 0; k < K; k++) fsm_decompose_scw(Scw + 12 * (size_t)k, pose.data() + FSM_POSE_FLOATS * (size_t)k);
+  if (store) scene_.hold(std::move(shadows), pose.data(), pts, nlevels, scale_factors, nullptr, logScaleFactor, th);
+  else scene_.copy(*flat, pose.data(), pts, nlevels, scale_factors, nullptr, logScaleFactor, th);
+}
+
+int SearchAndFuseBatch::resolve(int k, const uint8_t* skip_now, const uint8_t* desc_now, std::vector<int32_t>& bestIdx, std::vector<int32_t>& bestDist) {
+  if (k < 0 || k >= K_) throw infrastructure_ex("SearchAndFuseBatch::resolve: keyframe out of range");
+  bestIdx.assign((size_t)P_, -1); bestDist.assign((size_t)P_, INT_MAX);
+  int nFused = 0;
+  for (int i = 0; i < P_; i++) {
+    if (skip_now && skip_now[i]) continue;
+    fuse_resolve_point(scene_, table_[(size_t)k * P_ + i], k, (size_t)i, desc_now ? desc_now + 32 * (size_t)i : nullptr, n_reeval_, bestIdx[i], bestDist[i], nFused);
+  }
+  return nFused;
+}
+
+SearchInNeighborsBatch::SearchInNeighborsBatch(HipContext* ctx, const KeyFrames& kfs, int n_calls, const int32_t* target, int current, const Points& pts, int n_current,
+                                               int nlevels, const float* scale_factors, const float* inv_level_sigma2, float logScaleFactor, float th)
+    : K_(kfs.K), C_(n_calls), cur_(current), P1_(n_current), P2_(pts.P - n_current) {
+  init(&kfs, nullptr, nullptr, kfs.pose, ctx, target, pts, nlevels, scale_factors, inv_level_sigma2, logScaleFactor, th);
+}
+SearchInNeighborsBatch::SearchInNeighborsBatch(KeyFrameStore& store, HipContext* ctx, int K, const int64_t* keys, const float* pose, int n_calls, const int32_t* target,
+                                               int current, const Points& pts, int n_current, int nlevels, const float* scale_factors, const float* inv_level_sigma2,
+                                               float logScaleFactor, float th)
+    : K_(K), C_(n_calls), cur_(current), P1_(n_current), P2_(pts.P - n_current) {
+  init(nullptr, &store, keys, pose, ctx, target, pts, nlevels, scale_factors, inv_level_sigma2, logScaleFactor, th);
+}
+
+void SearchInNeighborsBatch::init(const KeyFrames* flat, KeyFrameStore* store, const int64_t* keys, const float* pose, HipContext* ctx, const int32_t* target,
+                                  const Points& pts, int nlevels, const float* scale_factors, const float* inv_level_sigma2, float logScaleFactor, float th) {
+  const int K = K_, P = pts.P, C = C_;
+  if (K < 0 || P < 0 || C < 0 || P1_ < 0 || P1_ > P || (C > 0 && !target) || !scale_factors || !inv_level_sigma2 || nlevels < 1 || nlevels > FSM_MAX_LEVELS ||
+      (int64_t)C * P1_ + P2_ > (int64_t)INT32_MAX || (store && K > 0 && (!keys || !pose)))
+    throw infrastructure_ex("SearchInNeighborsBatch: bad arguments");
+  if (store && !store->host_only() && !ctx) throw infrastructure_ex("SearchInNeighborsBatch: a device store needs the calling thread's context");
+  // C jobs (target of call c, the current keyframe's points) and one (current keyframe, the predicted candidates); without a current keyframe the last job is left out
+  std::vector<int32_t> jk, j0, jn;
+  for (int c = 0; c < C; c++) { jk.push_back(target[c]); j0.push_back(0); jn.push_back(P1_); }
+  if (cur_ >= 0) { jk.push_back(cur_); j0.push_back(P1_); jn.push_back(P2_); }
+  else if (P2_ > 0) throw infrastructure_ex("SearchInNeighborsBatch: candidates without a current keyframe");
+  const int J = (int)jk.size();
+  Shadows shadows;
+  if (store && !store_shadows(*store, K, keys, shadows)) throw infrastructure_ex("SearchInNeighborsBatch: a key is not in the store");
+  table_.assign((size_t)C * (size_t)P1_ + (size_t)P2_, 0); n_valid_.assign((size_t)J, 0); n_hit_.assign((size_t)J, 0);
+  if (store && !store->host_only()) {
+    check(ccm_fuse_pose_eval_resident(ctx->get(), store->handle(), K, keys, pose, nlevels, scale_factors, inv_level_sigma2, logScaleFactor, th, P, pts.pos, pts.normal,
+                                      pts.min_dist, pts.max_dist, pts.desc, J, jk.data(), j0.data(), jn.data(), table_.data(), n_valid_.data(), n_hit_.data(), nullptr),
+          ctx->get(), "ccm_fuse_pose_eval_resident");
+  } else if (store) {
+    int64_t total = 0, tiles = 0;
+    if (fsm_check_scalars(K, P, nlevels, th) || fpm_check_jobs(J, K, P, jk.data(), j0.data(), jn.data(), &total, &tiles) ||
+        (P > 0 && (!pts.pos || !pts.normal || !pts.min_dist || !pts.max_dist || !pts.desc)))
+      throw infrastructure_ex("SearchInNeighborsBatch: bad arguments");
+    proj_jobs_host<true, false, false>(ShadowKfs{shadows}, pose, nullptr, nullptr, {nlevels, scale_factors, inv_level_sigma2, logScaleFactor, th},
+                                       {P, pts.pos, pts.normal, pts.min_dist, pts.max_dist, pts.desc}, J, jk.data(), j0.data(), jn.data(), table_.data(), n_valid_.data(),
+                                       n_hit_.data(), nullptr, nullptr);
+  } else if (ctx) {
+    check(ccm_fuse_pose_eval(ctx->get(), K, flat->rec, flat->feat_off, flat->feat_xy, flat->feat_octave, flat->feat_desc, flat->cell_off, flat->cell_idx, pose, nlevels,
+                             scale_factors, inv_level_sigma2, logScaleFactor, th, P, pts.pos, pts.normal, pts.min_dist, pts.max_dist, pts.desc, J, jk.data(), j0.data(),
+                             jn.data(), table_.data(), n_valid_.data(), n_hit_.data(), nullptr),
+          ctx->get(), "ccm_fuse_pose_eval");
+  } else if (fuse_pose_eval_host(K, flat->rec, flat->feat_off, flat->feat_xy, flat->feat_octave, flat->feat_desc, flat->cell_off, flat->cell_idx, pose, nlevels, scale_factors,
+                                 inv_level_sigma2, logScaleFactor, th, P, pts.pos, pts.normal, pts.min_dist, pts.max_dist, pts.desc, J, jk.data(), j0.data(), jn.data(),
+                                 table_.data(), n_valid_.data(), n_hit_.data(), nullptr, nullptr)) {
+    throw infrastructure_ex("SearchInNeighborsBatch: bad arguments");
+  }
+  // the arguments are valid from here on: what the resolves may have to evaluate again
+  target_.assign(jk.begin(), jk.begin() + C);
+  if (store) scene_.hold(std::move(shadows), pose, pts, nlevels, scale_factors, inv_level_sigma2, logScaleFactor, th);
+  else scene_.copy(*flat, pose, pts, nlevels, scale_factors, inv_level_sigma2, logScaleFactor, th);
+}
+
+int SearchInNeighborsBatch::resolve(int c, const uint8_t* skip_now, const uint8_t* desc_now, std::vector<int32_t>& bestIdx, std::vector<int32_t>& bestDist) {
+  if (c < 0 || c >= C_) throw infrastructure_ex("SearchInNeighborsBatch::resolve: call out of range");
+  bestIdx.assign((size_t)P1_, -1); bestDist.assign((size_t)P1_, 256);
+  int nFused = 0;
+  for (int i = 0; i < P1_; i++) {
+    if (skip_now && skip_now[i]) continue;
+    fuse_resolve_point(scene_, table_[(size_t)c * P1_ + i], target_[c], (size_t)i, desc_now ? desc_now + 32 * (size_t)i : nullptr, n_reeval_, bestIdx[i], bestDist[i], nFused);
+  }
+  return nFused;
+}
+
+int SearchInNeighborsBatch::resolve_current(int n, const int32_t* slot, const uint8_t* skip_now, const uint8_t* desc_now, const Points& fresh,
+                                            std::vector<int32_t>& bestIdx, std::vector<int32_t>& bestDist) {
+  if (n < 0 || (n > 0 && !slot) || cur_ < 0) throw infrastructure_ex("SearchInNeighborsBatch::resolve_current: bad arguments");
+  bestIdx.assign((size_t)n, -1); bestDist.assign((size_t)n, 256);
+  int nFused = 0;
+  for (int i = 0; i < n; i++) {
+    if (skip_now && skip_now[i]) continue;
+    const int s = slot[i];
+    if (s >= P2_ || s < -1) throw infrastructure_ex("SearchInNeighborsBatch::resolve_current: slot out of range");
+    if (s < 0) {                                                 // a candidate the build did not predict: from what the caller passes for it
+      if (!fresh.pos || !fresh.normal || !fresh.min_dist || !fresh.max_dist || !fresh.desc || fresh.P < n)
+        throw infrastructure_ex("SearchInNeighborsBatch::resolve_current: an unpredicted candidate without fresh data");
+      const uint32_t w = scene_.eval(cur_, fresh.pos + 3 * (size_t)i, fresh.normal + 3 * (size_t)i, fresh.min_dist[i], fresh.max_dist[i],
+                                     desc_now ? desc_now + 32 * (size_t)i : fresh.desc + 32 * (size_t)i);
+      n_unpredicted_++;
+      sin_answer(w, bestIdx[i], bestDist[i], nFused);
+    } else {
+      fuse_resolve_point(scene_, table_[(size_t)C_ * P1_ + s], cur_, (size_t)P1_ + (size_t)s, desc_now ? desc_now + 32 * (size_t)i : nullptr, n_reeval_, bestIdx[i],
+                         bestDist[i], nFused);
+    }
+  }
+  return nFused;
+}
+
+// ---- ComputeSim3's two projected searches: Sim3ProjectionSearch, SearchBySim3Batch ------------------------------
 Sim3ProjectionSearch::Sim3ProjectionSearch(KeyFrameStore& store, HipContext* ctx, int64_t key, const float* Scw12, const Points& pts, const uint8_t* matched0, int nlevels,
                                            const float* scale_factors, float logScaleFactor, float th)
     : P_(pts.P) {
@@ -2396,8 +2305,8 @@ int Sim3ProjectionSearch::resolve(const uint8_t* skip_now, const int32_t* existi
         mask.resize((size_t)N_);
         for (int f = 0; f < N_; f++) mask[f] = matched[f] >= 0;
       }
-      w = sim3_project_pair_host(kf, s.pose.data(), mask.data(), s.pos.data() + 3 * (size_t)i, s.normal.data() + 3 * (size_t)i, s.dmin[i], s.dmax[i],
-                                 s.pdesc.data() + 32 * (size_t)i, s.nlevels, s.logsf, s.th, s.sf.data(), nullptr);
+      w = proj_pair_host<false, true, false>(kf, s.pose.data(), mask.data(), scene_levels(s), s.pos.data() + 3 * (size_t)i, s.normal.data() + 3 * (size_t)i, s.dmin[i],
+                                             s.dmax[i], s.pdesc.data() + 32 * (size_t)i, nullptr, nullptr);
       n_reeval_++;
       if ((w >> 29) != FSM_HIT) continue;
     }

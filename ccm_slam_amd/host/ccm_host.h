@@ -644,6 +644,9 @@ class SearchAndFuseBatch {
   const std::vector<int32_t>& nHit() const { return n_hit_; }
   long long n_reeval() const { return n_reeval_; }                 // pairs evaluated again by resolve because the descriptor had changed
  private:
+  // both constructors: the keyframes are *flat, or keys of *store (the other is null)
+  void init(const KeyFrames* flat, KeyFrameStore* store, const int64_t* keys, const float* Scw, HipContext* ctx, const Points& pts, int nlevels,
+            const float* scale_factors, float logScaleFactor, float th);
   int K_ = 0, P_ = 0;
   FuseScene scene_;
   std::vector<int32_t> n_valid_, n_hit_;
@@ -699,6 +702,9 @@ class SearchInNeighborsBatch {
   long long n_reeval() const { return n_reeval_; }                 // pairs evaluated again because the descriptor had changed
   long long n_unpredicted() const { return n_unpredicted_; }       // candidates evaluated from fresh data
  private:
+  // both constructors: the keyframes are *flat, or keys of *store (the other is null)
+  void init(const KeyFrames* flat, KeyFrameStore* store, const int64_t* keys, const float* pose, HipContext* ctx, const int32_t* target, const Points& pts, int nlevels,
+            const float* scale_factors, const float* inv_level_sigma2, float logScaleFactor, float th);
   int K_ = 0, C_ = 0, cur_ = -1, P1_ = 0, P2_ = 0;
   FuseScene scene_;
   std::vector<int32_t> target_, n_valid_, n_hit_;
