@@ -1,4 +1,5 @@
-// kfstore.h — the keyframe feature store's handle, shared by kfstore.hip (which fills it) and fuse.hip (whose resident evaluators read it).  DESIGN.md §21.
+// kfstore.h — the keyframe feature store's handle, shared by kfstore.hip (which fills it) and fuse.hip and bowsearch.hip (whose resident evaluators read it).
+// DESIGN.md §21, §23.
 #pragma once
 #include "common.h"
 #include "kfstore_math.h"
@@ -17,8 +18,13 @@ struct ccm_kfstore {
   float* d_xy = nullptr;           // [2 stride max_kf]
   uint8_t* d_oct = nullptr;        // [stride max_kf]
   uint8_t* d_desc = nullptr;       // [32 stride max_kf]
+  // the keyframe's DBoW2::FeatureVector (ccm_kfstore_set_featvec), as the caller gave it: a node has at least one feature, so nn <= n
+  int32_t* d_fv_node = nullptr;    // [stride max_kf] node ids, ascending
+  int32_t* d_fv_off = nullptr;     // [(stride + 1) max_kf] offsets of the nodes' features
+  uint16_t* d_fv_idx = nullptr;    // [stride max_kf] the features of the nodes, ascending inside a node
   // host
   std::vector<int32_t> h_n;                // [max_kf] d_n as the adds wrote it: the feature count a mask of ccm_sim3_project_eval_resident is held to
+  std::vector<int32_t> h_fv_nn;            // [max_kf] the nodes of the slot's feature vector; -1: the tenant has none
   std::unordered_map<int64_t, int> live;   // key -> slot
   std::vector<int> free_slots;             // a stack: the slot freed last is taken first
 };

@@ -15,7 +15,11 @@
 //            distinct cells present (at most 64 rounds), and the cell's first lane moves the cursor on.  The indices of a cell therefore ascend: the reference's
 //            push_back order, on which fsm_window_best's tie-break rests.
 // No comparison sort, no float atomics, nothing waits on another workgroup, every loop is bounded by a count validated on the host.
+//
+// ccm_kfstore_set_featvec gives a live key its DBoW2::FeatureVector: the flat arrays are validated (bow_search_math.h bsm_check_featvec) and copied
+// into the slot as they are, the indices in 16 bits; nothing is sorted or built.  A slot's vector goes with its tenant: add, erase and clear mark it absent.
 #include "kfstore.h"
+#include "bow_search_math.h"
 #include "stage_blocks.h"
 
 #include <algorithm>
@@ -155,6 +159,7 @@ extern "C" int ccm_kfstore_create(ccm_ctx* ctx, int max_kf, int max_feat, ccm_kf
   const bool ok = hipMalloc(&st->d_rec, K * FSM_REC_FLOATS * 4) == hipSuccess && hipMalloc(&st->d_n, K * 4) == hipSuccess && hipMalloc(&st->d_n_in, K * 4) == hipSuccess &&
                   hipMalloc(&st->d_cell_off, K * (FSM_CELLS + 1) * 4) == hipSuccess && hipMalloc(&st->d_cell_idx, G * 2) == hipSuccess &&
                   hipMalloc(&st->d_xy, G * 8) == hipSuccess && hipMalloc(&st->d_oct, G) == hipSuccess && hipMalloc(&st->d_desc, G * 32) == hipSuccess &&
+                  hipMalloc(&st->d_fv_node, G * 4) == hipSuccess && hipMalloc(&st->d_fv_off, (G + K) * 4) == hipSuccess && hipMalloc(&st->d_fv_idx, G * 2) == hipSuccess &&
                   hipMemsetAsync(st->d_n, 0, K * 4, ctx->stream) == hipSuccess && hipMemsetAsync(st->d_n_in, 0, K * 4, ctx->stream) == hipSuccess &&
                   hipMemsetAsync(st->d_cell_off, 0, K * (FSM_CELLS + 1) * 4, ctx->stream) == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess;
   if (!ok) {
@@ -164,6 +169,7 @@ extern "C" int ccm_kfstore_create(ccm_ctx* ctx, int max_kf, int max_feat, ccm_kf
   }
   st->free_slots.resize(K);
   st->h_n.assign(K, 0);
+  st->h_fv_nn.assign(K, -1);
   for (int s = 0; s < max_kf; s++) st->free_slots[s] = max_kf - 1 - s;   // slot 0 is taken first
   *out = st;
   return CCM_OK;
@@ -173,6 +179,7 @@ extern "C" void ccm_kfstore_destroy(ccm_kfstore* st) {
   if (!st) return;
   hipSetDevice(st->device);
   hipFree(st->d_rec); hipFree(st->d_n); hipFree(st->d_n_in); hipFree(st->d_cell_off); hipFree(st->d_cell_idx); hipFree(st->d_xy); hipFree(st->d_oct); hipFree(st->d_desc);
+  hipFree(st->d_fv_node); hipFree(st->d_fv_off); hipFree(st->d_fv_idx);
   delete st;
 }
 
@@ -222,8 +229,41 @@ extern "C" int ccm_kfstore_add(ccm_kfstore* st, ccm_ctx* ctx, int M, const int64
   if (int rc = ccm_staged_download(ctx, b)) return rc;   // synchronises: the slots are written when the keys become live
   for (int m = 0; m < M; m++) {
     st->h_n[(size_t)st->free_slots.back()] = feat_off[m + 1] - feat_off[m];
+    st->h_fv_nn[(size_t)st->free_slots.back()] = -1;   // the previous tenant's vector is not the new one's
     st->live[keys[m]] = st->free_slots.back(); st->free_slots.pop_back();
   }
+  return CCM_OK;
+}
+
+extern "C" int ccm_kfstore_set_featvec(ccm_kfstore* st, ccm_ctx* ctx, int64_t key, int nn, const int32_t* node, const int32_t* off, const int32_t* idx) {
+  if (int rc = kfstore_ctx_ok(st, ctx, "ccm_kfstore_set_featvec")) return rc;
+  const char* const me = "ccm_kfstore_set_featvec: ";
+  std::unique_lock<std::shared_mutex> lk(st->mu);   // add's lock: no resident evaluator reads the slot meanwhile
+  auto it = st->live.find(key);
+  if (it == st->live.end()) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + "key not in the store");
+  const size_t s = (size_t)it->second;
+  const int n = st->h_n[s];
+  std::vector<uint8_t> seen((size_t)n + 1);
+  if (const char* why = bsm_check_featvec(n, nn, node, off, idx, seen.data())) return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + why);
+  if (nn > 0) {
+    // pinned: node[nn] | off[nn + 1] | idx[off[nn]] (16-bit), then one copy per array into the slot
+    const size_t L = (size_t)off[nn], b_off = (size_t)nn * 4, b_idx = b_off + ((size_t)nn + 1) * 4;
+    void* pin = nullptr;
+    if (int rc = ccm_pin_scratch(ctx, b_idx + L * 2, &pin)) return rc;
+    CCM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));   // the block may still feed an earlier copy
+    char* p = (char*)pin;
+    std::memcpy(p, node, (size_t)nn * 4);
+    std::memcpy(p + b_off, off, ((size_t)nn + 1) * 4);
+    uint16_t* h_idx = (uint16_t*)(p + b_idx);
+    for (size_t i = 0; i < L; i++) h_idx[i] = (uint16_t)idx[i];
+    const size_t g0 = s * (size_t)st->stride;
+    st->h_fv_nn[s] = -1;   // a copy that fails leaves the key without a vector, not with half of one
+    CCM_HIP_CHECK(ctx, hipMemcpyAsync(st->d_fv_node + g0, p, (size_t)nn * 4, hipMemcpyHostToDevice, ctx->stream));
+    CCM_HIP_CHECK(ctx, hipMemcpyAsync(st->d_fv_off + g0 + s, p + b_off, ((size_t)nn + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    CCM_HIP_CHECK(ctx, hipMemcpyAsync(st->d_fv_idx + g0, p + b_idx, L * 2, hipMemcpyHostToDevice, ctx->stream));
+    CCM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  st->h_fv_nn[s] = nn;
   return CCM_OK;
 }
 
@@ -233,6 +273,7 @@ extern "C" int ccm_kfstore_erase(ccm_kfstore* st, ccm_ctx* ctx, int64_t key) {
   auto it = st->live.find(key);
   if (it == st->live.end()) return CCM_OK;
   st->free_slots.push_back(it->second);
+  st->h_fv_nn[(size_t)it->second] = -1;
   st->live.erase(it);
   return CCM_OK;
 }
@@ -241,6 +282,7 @@ extern "C" int ccm_kfstore_clear(ccm_kfstore* st, ccm_ctx* ctx) {
   if (int rc = kfstore_ctx_ok(st, ctx, "ccm_kfstore_clear")) return rc;
   std::unique_lock<std::shared_mutex> lk(st->mu);
   st->live.clear();
+  st->h_fv_nn.assign((size_t)st->max_kf, -1);
   st->free_slots.resize((size_t)st->max_kf);
   for (int s = 0; s < st->max_kf; s++) st->free_slots[s] = st->max_kf - 1 - s;
   return CCM_OK;

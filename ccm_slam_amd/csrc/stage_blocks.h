@@ -5,6 +5,7 @@
 #include "triangulate_math.h"
 #include "fuse_math.h"
 #include "kfstore_math.h"
+#include "bow_search_math.h"
 
 // ccm_sim3_ransac_eval: the inputs, then the outputs.
 struct Sim3RansacBlock : StagedBlock {
@@ -134,6 +135,17 @@ struct KfstoreAddBlock : StagedBlock {
   StagedSeg<int32_t> n_in = add<int32_t>(M, SB_OUT);
 };
 
+// ccm_bow_pair_eval_resident: J jobs of BSM_JOB_INTS ints each (the two slots, their node counts, the jobs' first mask bytes and first work item,
+// written by the stage while it validates) and the two sides' mask bytes, M1 and M2 in all.  The table has one 64-bit word per mask byte of side 1 and leads the
+// outputs, on 8 bytes; it goes up as zeros (a feature no wave meets is no query) and so do the counters, which the kernel adds to.
+struct BowPairResidentBlock : StagedBlock {
+  const size_t J, M1, M2;
+  BowPairResidentBlock(size_t J, size_t M1, size_t M2) : J(J), M1(M1), M2(M2) {}
+  StagedSeg<int32_t> job = add<int32_t>(BSM_JOB_INTS * J, SB_GEN, 16);
+  StagedSeg<uint8_t> live1 = add<uint8_t>(M1, SB_COPY), live2 = add<uint8_t>(M2, SB_COPY);
+  StagedSeg<uint64_t> table = add<uint64_t>(M1, SB_OUT | SB_ZERO);
+  StagedSeg<int32_t> n_query = add<int32_t>(J, SB_OUT | SB_ZERO), n_dist = add<int32_t>(J, SB_OUT | SB_ZERO);
+};
 
 // The six projected searches of fuse.hip are ONE layout: K keyframes, P points, L levels, and what the form's flags add.  A segment a form does
 // not have is declared with no elements, so it takes no room, moves nothing, and the offsets of each form are what they would be alone.

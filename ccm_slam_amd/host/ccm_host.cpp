@@ -10,6 +10,7 @@
 #include "../csrc/kfcull_math.h"
 #include "../csrc/fuse_math.h"
 #include "../csrc/kfstore_math.h"
+#include "../csrc/bow_search_math.h"
 #include <climits>
 #include <algorithm>
 #include <cmath>
@@ -2001,6 +2002,36 @@ int KeyFrameStore::add(HipContext* ctx, int M, const int64_t* keys, const float*
   return CCM_OK;
 }
 
+int KeyFrameStore::set_featvec(HipContext* ctx, int64_t key, const FeatureVectorView& fv, const float* angle) {
+  if (h_ && !ctx) throw infrastructure_ex("KeyFrameStore::set_featvec: a device store needs the calling thread's context");
+  std::unique_lock<std::shared_mutex> lk(mu_);
+  auto it = live_.find(key);
+  if (it == live_.end()) return CCM_E_ARG;
+  const int n = it->second->n;
+  if (h_) {   // the device store decides, by the same rules
+    const int rc = ccm_kfstore_set_featvec(h_, ctx->get(), key, fv.nn, fv.node, fv.off, fv.idx);
+    if (rc == CCM_E_ARG) return rc;
+    check(rc, ctx->get(), "ccm_kfstore_set_featvec");
+  } else {
+    std::vector<uint8_t> seen((size_t)n + 1);
+    if (bsm_check_featvec(n, fv.nn, fv.node, fv.off, fv.idx, seen.data())) return CCM_E_ARG;
+  }
+  // batches hold the shadow they were built on: the key gets a copy with the vector
+  auto kf = std::make_shared<KfShadow>(*it->second);
+  kf->has_fv = true;
+  kf->fv_node.assign(fv.node, fv.node + (fv.nn > 0 ? fv.nn : 0));
+  kf->fv_off.assign(1, 0);
+  kf->fv_idx.clear();
+  if (fv.nn > 0) {
+    kf->fv_off.assign(fv.off, fv.off + fv.nn + 1);
+    kf->fv_idx.resize((size_t)fv.off[fv.nn]);
+    for (size_t i = 0; i < kf->fv_idx.size(); i++) kf->fv_idx[i] = (uint16_t)fv.idx[i];
+  }
+  if (angle) kf->angle.assign(angle, angle + n); else kf->angle.assign((size_t)n, 0.0f);
+  it->second = std::move(kf);
+  return CCM_OK;
+}
+
 void KeyFrameStore::erase(HipContext* ctx, int64_t key) {
   if (h_ && !ctx) throw infrastructure_ex("KeyFrameStore::erase: a device store needs the calling thread's context");
   std::unique_lock<std::shared_mutex> lk(mu_);
@@ -2380,6 +2411,111 @@ SearchBySim3Batch::SearchBySim3Batch(KeyFrameStore& store, HipContext* ctx, int6
   matches12_.assign(matches12_in, matches12_in + N1);
   for (int i = 0; i < N1; i++)
     if (agreed[i] >= 0) matches12_[i] = agreed[i];
+}
+
+// ---- ComputeSim3's SearchByBoW for all candidates: the host evaluator on the shadows, SearchByBoWBatch ---------------------------------
+static BowKf bow_kf(const KfShadow& kf) { return {kf.n, (int)kf.fv_node.size(), kf.fv_node.data(), kf.fv_off.data(), kf.fv_idx.data(), kf.desc.data()}; }
+
+int bow_pair_eval_resident_host(const KeyFrameStore& store, int J, const int64_t* key1, const int64_t* key2, const int32_t* live1_off, const uint8_t* live1,
+                                const int32_t* live2_off, const uint8_t* live2, uint64_t* table, int32_t* n_query, int32_t* n_dist) {
+  if (J < 0) return -1;
+  if (J == 0) return 0;
+  if (!key1 || !key2 || !live1_off || !live2_off || !n_query || !n_dist) return -1;
+  std::vector<std::shared_ptr<const KfShadow>> a, b;
+  if (!store_shadows(store, J, key1, a) || !store_shadows(store, J, key2, b)) return -1;
+  std::vector<int32_t> n1((size_t)J), n2((size_t)J);
+  std::vector<BowKf> k1((size_t)J), k2((size_t)J);
+  for (int j = 0; j < J; j++) {
+    if (!a[j]->has_fv || !b[j]->has_fv) return -1;
+    n1[j] = a[j]->n; n2[j] = b[j]->n;
+    k1[j] = bow_kf(*a[j]); k2[j] = bow_kf(*b[j]);
+  }
+  if (bsm_check_masks(J, live1_off, live1, n1.data()) || bsm_check_masks(J, live2_off, live2, n2.data())) return -1;
+  if (live1_off[J] > 0 && !table) return -1;
+  bow_pair_eval_host(J, k1.data(), k2.data(), live1_off, live1, live2_off, live2, table, n_query, n_dist);
+  return 0;
+}
+
+SearchByBoWBatch::SearchByBoWBatch(KeyFrameStore& store, HipContext* ctx, int64_t key1, int C, const int64_t* keys2, const uint8_t* live1, const uint8_t* const* live2,
+                                   float nnratio, bool checkOrientation) {
+  if (C < 0 || (C > 0 && (!keys2 || !live2))) throw infrastructure_ex("SearchByBoWBatch: bad arguments");
+  std::vector<std::shared_ptr<const KfShadow>> kf1, kfs2;
+  if (!store_shadows(store, 1, &key1, kf1) || !store_shadows(store, C, keys2, kfs2)) throw infrastructure_ex("SearchByBoWBatch: a key is not in the store");
+  const KfShadow& K1 = *kf1[0];
+  if (!K1.has_fv) throw infrastructure_ex("SearchByBoWBatch: a key without a feature vector");
+  const int N1 = K1.n;
+  if (N1 > 0 && !live1) throw infrastructure_ex("SearchByBoWBatch: bad arguments");
+  // the masks of the call: live1 once per candidate, the candidates' own one after the other
+  std::vector<int64_t> k1((size_t)C, key1);
+  std::vector<int32_t> off1((size_t)C + 1, 0), off2((size_t)C + 1, 0);
+  for (int j = 0; j < C; j++) {
+    if (!kfs2[j]->has_fv) throw infrastructure_ex("SearchByBoWBatch: a key without a feature vector");
+    if (kfs2[j]->n > 0 && !live2[j]) throw infrastructure_ex("SearchByBoWBatch: bad arguments");
+    off1[j + 1] = off1[j] + N1; off2[j + 1] = off2[j] + kfs2[j]->n;
+  }
+  std::vector<uint8_t> m1((size_t)off1[C]), m2((size_t)off2[C]);
+  for (int j = 0; j < C; j++) {
+    if (N1) std::memcpy(m1.data() + off1[j], live1, (size_t)N1);
+    if (kfs2[j]->n) std::memcpy(m2.data() + off2[j], live2[j], (size_t)kfs2[j]->n);
+  }
+  table_.assign((size_t)off1[C], 0); n_query_.assign((size_t)C, 0); n_dist_.assign((size_t)C, 0);
+  if (C > 0 && !store.host_only() && ctx) {
+    check(ccm_bow_pair_eval_resident(ctx->get(), store.handle(), C, k1.data(), keys2, off1.data(), m1.data(), off2.data(), m2.data(), table_.data(), n_query_.data(),
+                                     n_dist_.data()),
+          ctx->get(), "ccm_bow_pair_eval_resident");
+  } else if (bow_pair_eval_resident_host(store, C, k1.data(), keys2, off1.data(), m1.data(), off2.data(), m2.data(), table_.data(), n_query_.data(), n_dist_.data())) {
+    throw infrastructure_ex("SearchByBoWBatch: bad arguments");
+  }
+  // the reference's loop per candidate (:585-698) on the words
+  const int TH_LOW = ORBmatcher::TH_LOW, HISTO_LENGTH = ORBmatcher::HISTO_LENGTH;
+  nmatches_.assign((size_t)C, 0); matches12_.resize((size_t)C);
+  std::vector<int> claimed;   // the features of keyframe 2 claimed so far in the node at hand
+  for (int j = 0; j < C; j++) {
+    const KfShadow& K2 = *kfs2[j];
+    const BowKf b2 = bow_kf(K2);
+    const uint64_t* words = table_.data() + off1[j];
+    const uint8_t* l2 = m2.data() + off2[j];
+    std::vector<int32_t>& matches12 = matches12_[(size_t)j];
+    matches12.assign((size_t)N1, -1);
+    std::vector<uint8_t> vbMatched2((size_t)K2.n, 0);
+    std::vector<int> rotHist[ORBmatcher::HISTO_LENGTH];
+    int nmatches = 0;
+    for (size_t a = 0; a < K1.fv_node.size(); a++) {   // ascending nodes of keyframe 1; those keyframe 2 lacks hold no query
+      claimed.clear();
+      for (int32_t s1 = K1.fv_off[a]; s1 < K1.fv_off[a + 1]; s1++) {
+        const int idx1 = K1.fv_idx[(size_t)s1];
+        const uint64_t w = words[idx1];
+        if (bsm_status(w) != BSM_EVALUATED) continue;   // not live, no common node, or no live candidate: bestDist1 stays 256
+        BowBest r = bsm_best(w);
+        if (r.d1 >= TH_LOW) continue;                   // stands whatever was claimed
+        const uint8_t* qd = K1.desc.data() + 32 * (size_t)idx1;
+        bool again = false;
+        for (int c : claimed)
+          if (bsm_hamming(qd, K2.desc.data() + 32 * (size_t)c) <= r.d2) { again = true; break; }
+        if (again) {
+          int n_live = 0;
+          r = bsm_reduce_host(qd, b2, bsm_node2(w), l2, vbMatched2.data(), &n_live, nullptr);
+          n_reeval_++;
+        }
+        if (r.d1 < TH_LOW && static_cast<float>(r.d1) < nnratio * static_cast<float>(r.d2)) {   // :641, strict
+          matches12[(size_t)idx1] = r.idx;
+          vbMatched2[(size_t)r.idx] = 1;
+          claimed.push_back(r.idx);
+          if (checkOrientation) rotHist[histBin(K1.angle[(size_t)idx1] - K2.angle[(size_t)r.idx])].push_back(idx1);
+          nmatches++;
+        }
+      }
+    }
+    if (checkOrientation) {
+      int ind1 = -1, ind2 = -1, ind3 = -1;
+      threeMaxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
+      for (int i = 0; i < HISTO_LENGTH; i++) {
+        if (i == ind1 || i == ind2 || i == ind3) continue;
+        for (int k : rotHist[i]) { matches12[(size_t)k] = -1; nmatches--; }
+      }
+    }
+    nmatches_[(size_t)j] = nmatches;
+  }
 }
 
 }  // namespace cslam
@@ -3116,6 +3252,47 @@ void* ccmh_fuse_pose_create_resident(void* store, int device, int K, const int64
                                              current, pt, n_current, nlevels, scale_factors, inv_level_sigma2, logScaleFactor, th);
   } catch (const std::exception&) { return nullptr; }
 }
+
+// the store's feature vectors and ComputeSim3's SearchByBoW for all candidates through C
+int ccmh_kfstore_set_featvec(void* h, int device, int64_t key, int nn, const int32_t* node, const int32_t* off, const int32_t* idx, const float* angle) {
+  if (!h) return -1000;
+  try {
+    return static_cast<cslam::KeyFrameStore*>(h)->set_featvec(device < 0 ? nullptr : &thread_context(device), key, cslam::FeatureVectorView{nn, node, off, idx}, angle);
+  } catch (const std::exception&) { return -1000; }
+}
+int ccmh_bow_pair_eval_resident_host(void* store, int J, const int64_t* key1, const int64_t* key2, const int32_t* live1_off, const uint8_t* live1, const int32_t* live2_off,
+                                     const uint8_t* live2, uint64_t* table, int32_t* n_query, int32_t* n_dist) {
+  if (!store) return -1;
+  return cslam::bow_pair_eval_resident_host(*static_cast<cslam::KeyFrameStore*>(store), J, key1, key2, live1_off, live1, live2_off, live2, table, n_query, n_dist);
+}
+void* ccmh_bow_batch_create(void* store, int device, int64_t key1, int C, const int64_t* keys2, const uint8_t* live1, const int32_t* live2_off, const uint8_t* live2,
+                            float nnratio, int check_orientation) {
+  if (!store || C < 0 || (C > 0 && !live2_off)) return nullptr;
+  try {
+    std::vector<const uint8_t*> l2((size_t)C);
+    for (int j = 0; j < C; j++) l2[j] = live2 ? live2 + live2_off[j] : nullptr;
+    return new cslam::SearchByBoWBatch(*static_cast<cslam::KeyFrameStore*>(store), device < 0 ? nullptr : &thread_context(device), key1, C, keys2, live1, l2.data(), nnratio,
+                                       check_orientation != 0);
+  } catch (const std::exception&) { return nullptr; }
+}
+int ccmh_bow_batch_result(void* h, int j, int n_feat, int32_t* matches12) {
+  if (!h) return -1000;
+  const cslam::SearchByBoWBatch& b = *static_cast<cslam::SearchByBoWBatch*>(h);
+  if (j < 0 || j >= b.candidates()) return -1000;
+  if (n_feat != (int)b.matches12(j).size()) return -1001;
+  if (matches12 && n_feat) std::memcpy(matches12, b.matches12(j).data(), (size_t)n_feat * 4);
+  return b.nmatches(j);
+}
+int ccmh_bow_batch_table(void* h, uint64_t* table, int32_t* n_query, int32_t* n_dist) {
+  if (!h) return -1;
+  const cslam::SearchByBoWBatch& b = *static_cast<cslam::SearchByBoWBatch*>(h);
+  if (table && !b.table().empty()) std::memcpy(table, b.table().data(), b.table().size() * 8);
+  if (n_query && b.candidates()) std::memcpy(n_query, b.nQuery().data(), (size_t)b.candidates() * 4);
+  if (n_dist && b.candidates()) std::memcpy(n_dist, b.nDist().data(), (size_t)b.candidates() * 4);
+  return 0;
+}
+long long ccmh_bow_batch_n_reeval(void* h) { return h ? static_cast<cslam::SearchByBoWBatch*>(h)->reevaluated() : -1; }
+void ccmh_bow_batch_destroy(void* h) { delete static_cast<cslam::SearchByBoWBatch*>(h); }
 
 // the two projected searches of ComputeSim3 through C: host evaluators, ssm_derive, the two mirrors
 int ccmh_sim3_project_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,

@@ -562,6 +562,11 @@ struct KfShadow {
   std::vector<uint8_t> oct, desc;
   std::vector<int32_t> cell_off;    // 3601
   std::vector<uint16_t> cell_idx;   // n_in
+  // set_featvec: mFeatVec as the device slot holds it, and mvKeysUn[i].angle (the shadow's alone: the rotation histogram is evaluated on the host)
+  bool has_fv = false;
+  std::vector<int32_t> fv_node, fv_off;
+  std::vector<uint16_t> fv_idx;
+  std::vector<float> angle;         // n
 };
 
 class KeyFrameStore {
@@ -574,6 +579,9 @@ class KeyFrameStore {
   // (ignored by the host-only store).
   int add(HipContext* ctx, int M, const int64_t* keys, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave,
           const uint8_t* feat_desc, const int32_t* cell_off = nullptr, const int32_t* cell_idx = nullptr);
+  // ccm_kfstore_set_featvec's arguments and refusals (0 or CCM_E_ARG, the store untouched by a refusal; a device error throws) and angle[n] = mvKeysUn[i].angle
+  // (nullable: zeros).  A second call for the key replaces the first.  Right after add in the message constructor: ComputeBoW() has run by then.
+  int set_featvec(HipContext* ctx, int64_t key, const FeatureVectorView& fv, const float* angle);
   void erase(HipContext* ctx, int64_t key);
   void clear(HipContext* ctx);
   int live() const;
@@ -800,6 +808,39 @@ class SearchBySim3Batch {
  private:
   int n_found_ = 0;
   std::vector<int32_t> matches12_, vn1_, vn2_, n_valid_, n_hit_;
+};
+
+// ccm_bow_pair_eval_resident's arguments after the context through csrc/bow_search_math.h on the calling thread, on the shadows of a store; -1 where the device
+// entry returns CCM_E_ARG.
+int bow_pair_eval_resident_host(const KeyFrameStore& store, int J, const int64_t* key1, const int64_t* key2, const int32_t* live1_off, const uint8_t* live1,
+                                const int32_t* live2_off, const uint8_t* live2, uint64_t* table, int32_t* n_query, int32_t* n_dist);
+
+// ORBmatcher::SearchByBoW(mpCurrentKF, pKF, vvpMapPointMatches[i]) (ORBmatcher.cpp:565-698) for ALL candidates of a ComputeSim3 (LoopFinder.cpp:251-282,
+// MapMatcher.cpp:271) on keys of a store that have their feature vector.  live1 (one byte per feature of key1) / live2[j] (per
+// feature of keys2[j]): pMP && !pMP->isBad() of the slot.  The constructor evaluates every query of every candidate against the INITIAL vbMatched2 in ONE
+// ccm_bow_pair_eval_resident call, or on the calling thread when the store is host-only or ctx == nullptr; with a context a device error throws.  It then replays
+// the reference's loop per candidate: the common nodes ascending, the queries in list order, TH_LOW, the strict ratio test, the claims and the rotation histogram.
+// A feature of keyframe 2 lies in exactly one node, so claims reach a query only from earlier queries of ITS node: the device word stands unless a feature claimed
+// so far in the node is at a distance <= the word's bestDist2 from the query (one popcount on the shadows' descriptors each), and a word with
+// bestDist1 >= TH_LOW stands whatever was claimed (fewer candidates never lower it).  A query that fails these tests is evaluated again on the calling thread over
+// its node's segment minus the claimed features.
+class SearchByBoWBatch {
+ public:
+  SearchByBoWBatch(KeyFrameStore& store, HipContext* ctx, int64_t key1, int C, const int64_t* keys2, const uint8_t* live1, const uint8_t* const* live2, float nnratio,
+                   bool checkOrientation);
+  int candidates() const { return (int)nmatches_.size(); }
+  int nmatches(int j) const { return nmatches_.at((size_t)j); }
+  const std::vector<int32_t>& matches12(int j) const { return matches12_.at((size_t)j); }   // per feature of key1: the feature of keys2[j] or -1
+  const std::vector<uint64_t>& table() const { return table_; }                              // as evaluated at construction, candidate after candidate
+  const std::vector<int32_t>& nQuery() const { return n_query_; }
+  const std::vector<int32_t>& nDist() const { return n_dist_; }
+  long long reevaluated() const { return n_reeval_; }
+ private:
+  std::vector<int> nmatches_;
+  std::vector<std::vector<int32_t>> matches12_;
+  std::vector<uint64_t> table_;
+  std::vector<int32_t> n_query_, n_dist_;
+  long long n_reeval_ = 0;
 };
 
 // ---------------------------------------------------------------------------------------------------

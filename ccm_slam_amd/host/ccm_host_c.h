@@ -182,6 +182,18 @@ int ccmh_sim3_project_resolve(void* h, const uint8_t* skip_now, const int32_t* e
 long long ccmh_sim3_project_n_reeval(void* h);
 void ccmh_sim3_project_destroy(void* h);
 int ccmh_search_by_sim3_resident(void* store, int device, int64_t key1, int64_t key2, int N1, const uint8_t* live1, const float* pos1, const float* min1, const float* max1, const uint8_t* desc1, const float* pose1, int N2, const uint8_t* live2, const float* pos2, const float* min2, const float* max2, const uint8_t* desc2, const float* pose2, float s12, const float* R12, const float* t12, const int32_t* matches12_in, int nlevels, const float* scale_factors, float logScaleFactor, float th, int32_t* matches12, int32_t* vn1, int32_t* vn2, int32_t* n_valid2, int32_t* n_hit2);
+/* The store's feature vectors and ComputeSim3's SearchByBoW for all candidates.  ccmh_kfstore_set_featvec: cslam::KeyFrameStore::set_featvec
+ * (0, CCM_E_ARG (-1), -1000 on a device error; angle nullable).  ccmh_bow_pair_eval_resident_host: ccm_bow_pair_eval_resident's arguments after the context on the
+ * store's shadows through csrc/bow_search_math.h (0, or -1 for the CCM_E_ARG cases).  ccmh_bow_batch_*: cslam::SearchByBoWBatch (device < 0: the host evaluation;
+ * create returns NULL on bad arguments, a key that is not live or has no feature vector, or a device error).  live2 + live2_off[j]: candidate j's mask.  result
+ * returns nmatches of candidate j and copies matches12 (n_feat entries, nullable); -1000 for j out of range, -1001 when n_feat is not key1's feature count. */
+int ccmh_kfstore_set_featvec(void* h, int device, int64_t key, int nn, const int32_t* node, const int32_t* off, const int32_t* idx, const float* angle);
+int ccmh_bow_pair_eval_resident_host(void* store, int J, const int64_t* key1, const int64_t* key2, const int32_t* live1_off, const uint8_t* live1, const int32_t* live2_off, const uint8_t* live2, uint64_t* table, int32_t* n_query, int32_t* n_dist);
+void* ccmh_bow_batch_create(void* store, int device, int64_t key1, int C, const int64_t* keys2, const uint8_t* live1, const int32_t* live2_off, const uint8_t* live2, float nnratio, int check_orientation);
+int ccmh_bow_batch_result(void* h, int j, int n_feat, int32_t* matches12);
+int ccmh_bow_batch_table(void* h, uint64_t* table, int32_t* n_query, int32_t* n_dist);
+long long ccmh_bow_batch_n_reeval(void* h);
+void ccmh_bow_batch_destroy(void* h);
 
 #ifdef __cplusplus
 }

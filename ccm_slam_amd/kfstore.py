@@ -5,7 +5,8 @@ stages on keyframes of the store.
 KeyFrameStore(ctx, max_kf, max_feat) wraps cslam::KeyFrameStore, which keeps the device handle and a host shadow per live key; ctx = None asks for the host-only
 store by name.  fuse_sim3_eval_resident / fuse_pose_eval_resident run ccm_fuse_sim3_eval_resident / ccm_fuse_pose_eval_resident and return the dictionaries of
 fuse_sim3.fuse_sim3_eval / fuse_pose.fuse_pose_eval; the *_host forms evaluate the same pairs on the store's shadows through csrc/fuse_math.h.
-SearchAndFuseBatchResident / SearchInNeighborsBatchResident are the mirrors' constructors on keys of a store.
+SearchAndFuseBatchResident / SearchInNeighborsBatchResident are the mirrors' constructors on keys of a store.  set_featvec gives a key its feature vector, which
+ComputeSim3's SearchByBoW reads (bow_search.py).
 
 build_grid_keyframe replays KeyFrame::AssignFeaturesToGrid and KeyFrame::PosInGrid (cslam/src/KeyFrame.cpp:206-225, :265-275) line by line in Python; it shares
 nothing with csrc/kfstore_math.h, which is what the tests compare it with.
@@ -49,6 +50,7 @@ def _host():
     h.ccmh_kfstore_handle.restype = V
     h.ccmh_kfstore_handle.argtypes = [V]
     h.ccmh_kfstore_get.argtypes = [V, I, C.c_int64, V, V, V, V]
+    h.ccmh_kfstore_set_featvec.argtypes = [V, I, C.c_int64, I, V, V, V, V]
     pts = [I] + [V] * 5
     h.ccmh_fuse_sim3_eval_resident_host.argtypes = [V, I, V, V, I, V, F, F] + pts + [V] * 4
     h.ccmh_fuse_pose_eval_resident_host.argtypes = [V, I, V, V, I, V, V, F, F] + pts + [I, V, V, V] + [V] * 4
@@ -142,6 +144,20 @@ class KeyFrameStore:
         kfs = list(range(s.K)) if kfs is None else list(kfs)
         sub = s.subset(kfs) if isinstance(s, fs.Scene) else s.subset(kfs, jobs=())
         self.add(keys, sub.rec, sub.feat_off, sub.feat_xy, sub.feat_octave, sub.feat_desc, sub.cell_off if grid else None, sub.cell_idx if grid else None)
+
+    def set_featvec(self, key: int, fv, angle=None):
+        """the key's DBoW2::FeatureVector as fv = (node[nn], off[nn + 1], idx[off[nn]]) (None: nn = 0) and mvKeysUn[i].angle (the shadow's alone; default zeros);
+        fv = (nn, node, off, idx) passes raw arguments, None standing for a null pointer"""
+        if fv is not None and len(fv) == 4:
+            nn, node, off, idx = fv
+            node, off, idx = (None if x is None else np.ascontiguousarray(x, np.int32) for x in (node, off, idx))
+        else:
+            node, off, idx = (np.zeros(0, np.int32), np.zeros(1, np.int32), np.zeros(0, np.int32)) if fv is None else (np.ascontiguousarray(x, np.int32) for x in fv)
+            nn = int(node.size)
+        ang = None if angle is None else np.ascontiguousarray(angle, np.float32)
+        rc = _host().ccmh_kfstore_set_featvec(self._h, self.device, int(key), int(nn), _p(node), _p(off), _p(idx), _p(ang))
+        if rc != 0:
+            raise StoreError("ccmh_kfstore_set_featvec", rc)
 
     def erase(self, key: int):
         if _host().ccmh_kfstore_erase(self._h, self.device, int(key)) != 0:

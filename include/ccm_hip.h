@@ -665,6 +665,13 @@ int  ccm_kfstore_count(ccm_kfstore* store, int* live, int* free_slots);
 /* one slot's grid as the device holds it: n features, n_in of them in the grid, cell_off[3601] (nullable), cell_idx[n_in] (nullable; room for n).  An unknown
  * key: CCM_E_ARG */
 int  ccm_kfstore_get(ccm_kfstore* store, ccm_ctx* ctx, int64_t key, int* n, int* n_in, int32_t* cell_off, int32_t* cell_idx);
+/* gives the live key its DBoW2::FeatureVector (mFeatVec) in the flat form of cslam::FeatureVectorView: nn node ids ascending, off[nn + 1] and the features of each
+ * node in ascending index (the order addFeature pushes them).  Validated and uploaded as they are (the indices in 16 bits); nothing is sorted or built.  A second
+ * call for the key replaces the first; erase, clear and the reuse of the slot drop the vector.  nn == 0 and off[nn] < n (features whose word is stopped are in no
+ * node) are legal.  CCM_E_ARG, with the store untouched: a key that is not live, nn < 0, null pointers with nn > 0, node ids negative or not strictly ascending,
+ * off[0] != 0, an empty node, an index outside [0, n) of the key, indices that do not ascend inside a node, a feature listed twice.  Locking is add's. */
+int  ccm_kfstore_set_featvec(ccm_kfstore* store, ccm_ctx* ctx, int64_t key, int nn, const int32_t* node /* nn */, const int32_t* off /* nn + 1 */,
+                             const int32_t* idx /* off[nn] */);
 
 /* ccm_fuse_sim3_eval / ccm_fuse_pose_eval on keyframes of the store: keyframe k of the call is the live key keys[k] (a key may appear more than once), Scw / pose
  * per k as there.  Outputs, packing, statuses, counters and refusals are those of the two calls above; additionally CCM_E_ARG, with nothing launched, for a NULL
@@ -705,6 +712,20 @@ int  ccm_sim3_pair_eval_resident(ccm_ctx* ctx, ccm_kfstore* store, int K, const 
                                  const int32_t* job_kf, const float* job_K4 /* 4 J */, const float* job_src_pose /* 12 J */, const float* job_T /* 12 J */,
                                  const int32_t* job_pt0, const int32_t* job_n, uint32_t* table /* sum(job_n) */, int32_t* n_valid /* J */, int32_t* n_hit /* J */,
                                  float* uv /* 2 sum(job_n) or NULL */);
+
+/* ---- ComputeSim3's SearchByBoW for all candidates on keyframes of the store (the lines are csrc/bow_search_math.h) ----------------------------------
+ * Job j is one ORBmatcher::SearchByBoW(pKF1, pKF2, ...) (cslam/src/ORBmatcher.cpp:565-698) of the live keys key1[j], key2[j], both with a feature vector, evaluated
+ * on the INITIAL vbMatched2 (all false).  live1 + live1_off[j] / live2 + live2_off[j]: one byte per feature of the keyframe, != 0 where the slot's map point is set
+ * and not bad.  table + live1_off[j] holds one word per feature idx1 of keyframe 1 (bsm_pack / bsm_status / bsm_best / bsm_node2): status 0 when idx1 is not live,
+ * in no node, or its node does not occur in keyframe 2; otherwise the reduction (:609-639) over the live features of the same node of keyframe 2 in list order,
+ * status 1 when none is live, 2 when evaluated.  n_query[j]: words with status >= 1; n_dist[j]: Hamming distances evaluated.  What the reference's loop changes while
+ * it runs (vbMatched2 claims) is the caller's to replay (cslam::SearchByBoWBatch, host/ccm_host.h).  One upload (slot pairs, offsets, mask bytes; no descriptors, no
+ * feature vectors), ONE launch, one download, under the store's reader lock.  J == 0, nn == 0, key1[j] == key2[j] and one key in several jobs are legal.
+ * CCM_E_ARG, with nothing launched: a NULL store, a store on another device, a key that is not live, a key without a feature vector, an offset array that does not
+ * start at 0 or decreases, a mask whose length is not the key's feature count in the store, null masks with a positive length, null outputs. */
+int  ccm_bow_pair_eval_resident(ccm_ctx* ctx, ccm_kfstore* store, int J, const int64_t* key1 /* J */, const int64_t* key2 /* J */, const int32_t* live1_off /* J + 1 */,
+                                const uint8_t* live1, const int32_t* live2_off /* J + 1 */, const uint8_t* live2, uint64_t* table /* live1_off[J] */,
+                                int32_t* n_query /* J */, int32_t* n_dist /* J */);
 
 #ifdef __cplusplus
 }
