@@ -3152,23 +3152,19 @@ int dev_alloc(ccm_ba* ba, size_t n, T** out, bool zero = true) {
   return CCM_OK;
 }
 
-// reduced systems with at most this many off-diagonal blocks use the one-workgroup-per-block Schur kernel; above, the row kernel (which also forms the
-// diagonal blocks and b_schur).  CCM_BA_ROW_MIN_BLOCKS overrides (experiments).
-static inline int row_min_blocks() { return 256; }
-
 // S and b_schur of the current linearisation and D^-1 (one rank's part): the row kernel on large maps (it also forms the diagonal blocks and b_schur), the
-// per-block kernels otherwise.  Also what the test hooks below call, so that they see the kernels the LM loop runs.
+// per-block kernels otherwise (kRowMinBlocks).
 static int launch_schur(ccm_ba* ba) {
   ccm_ctx* ctx = ba->ctx;
   BaDev& d = ba->d;
   if (!d.Cp) return CCM_OK;
-  if (!(d.nOff > row_min_blocks() && d.row_units_max)) {   // the row kernel also forms the diagonal blocks and b_schur
+  if (!(d.nOff > kRowMinBlocks && d.row_units_max)) {   // the row kernel also forms the diagonal blocks and b_schur
     ccm_prof_scope ps(ctx, CCM_K_BA_SCHUR_DIAG);
     hipLaunchKernelGGL(ba_schur_diag, dim3(d.n_wg_wave4), dim3(kTPB), 0, ctx->stream, d);
   }
   if (d.nOff) {
     ccm_prof_scope ps(ctx, CCM_K_BA_SCHUR_OFF);
-    if (d.nOff <= row_min_blocks()) hipLaunchKernelGGL(ba_schur_off<4>, dim3(d.nOff), dim3(kTPB), 0, ctx->stream, d);
+    if (d.nOff <= kRowMinBlocks) hipLaunchKernelGGL(ba_schur_off<4>, dim3(d.nOff), dim3(kTPB), 0, ctx->stream, d);
     else if (d.row_units_max) {
       const size_t lds_row = ((size_t)(d.max_cam_edges + 1) * 18 + 27 * (size_t)ccm_div_up(d.max_cam_edges, kRow2Group) + (size_t)d.row_units_max * 36) * sizeof(double);
       CCM_LDS_ATTR(ctx, CCM_LDS_BA_ROW3, ba_schur_row3, 158 * 1024);
@@ -3181,21 +3177,30 @@ static int launch_schur(ccm_ba* ba) {
 
 #define RC(x) do { int _rc = (x); if (_rc != CCM_OK) return _rc; } while (0)
 
+// The reduced system of the current linearisation (build_system) at this lambda, one rank's part: D^-1 and D^-1 b_l — unless the linearisation already
+// formed them for this lambda — and then S and b_schur.  The top of every LM trial, and what the test hooks below call behind build_system: they see the
+// kernels the LM loop runs because they run this.
+static int reduced_system(ccm_ba* ba, double lambda) {
+  BaDev& d = ba->d;
+  if (d.Lloc && ba->dinv_done_lambda != lambda) {
+    ccm_prof_scope ps(ba->ctx, CCM_K_BA_DINV);
+    hipLaunchKernelGGL(ba_dinv, dim3(d.n_wg_pt), dim3(kTPB), 0, ba->ctx->stream, d, lambda);
+  }
+  ba->dinv_done_lambda = -1.0;   // the next trial on this linearisation has another lambda
+  return launch_schur(ba);
+}
+
 // Collectives of a BA handle.  A handle created for ONE rank never enters a collective, even when its context carries a
 // multi-rank communicator (bench.py runs a single-rank local BA on rank 0 of a sharded job: an all-reduce issued by that
 // rank alone would wait for its peers forever).
-static inline int ba_allreduce_sum(ccm_ba* ba, double* buf, size_t n) {
+static inline int ba_allreduce(ccm_ba* ba, double* buf, size_t n, int (*reduce)(ccm_ctx*, double*, size_t)) {
   if (ba->nranks <= 1 && ba->ctx->comm_nranks > 1) return CCM_OK;
   if (ba->nranks <= 1 && !ba->ctx->comm && !ba->ctx->loop_group) return CCM_OK;   // no communicator: nothing is issued (and nothing is timed)
   ccm_prof_scope ps(ba->ctx, CCM_K_BA_ALLREDUCE);
-  return ccm_allreduce_f64(ba->ctx, buf, n);
+  return reduce(ba->ctx, buf, n);
 }
-static inline int ba_allreduce_max(ccm_ba* ba, double* buf, size_t n) {
-  if (ba->nranks <= 1 && ba->ctx->comm_nranks > 1) return CCM_OK;
-  if (ba->nranks <= 1 && !ba->ctx->comm && !ba->ctx->loop_group) return CCM_OK;   // no communicator: nothing is issued (and nothing is timed)
-  ccm_prof_scope ps(ba->ctx, CCM_K_BA_ALLREDUCE);
-  return ccm_allreduce_max_f64(ba->ctx, buf, n);
-}
+static inline int ba_allreduce_sum(ccm_ba* ba, double* buf, size_t n) { return ba_allreduce(ba, buf, n, ccm_allreduce_f64); }
+static inline int ba_allreduce_max(ccm_ba* ba, double* buf, size_t n) { return ba_allreduce(ba, buf, n, ccm_allreduce_max_f64); }
 
 }  // namespace
 
@@ -3303,9 +3308,8 @@ int read_scalars(ccm_ba* ba, double out[6], int flags[4] = nullptr) {
 }
 
 // The same read-back without a copy command and without waiting for the stream: ba_reduce_scalars wrote the words and then `ticket` into the pinned block (round 4: the
-// 64-byte copy + stream wait were ~25 us of every LM trial, 18 trials per 4-agent call, ~25 per local BA).  CCM_BA_POLL=0: the copy.  A ticket that does not arrive within
+// 64-byte copy + stream wait were ~25 us of every LM trial, 18 trials per 4-agent call, ~25 per local BA).  A ticket that does not arrive within
 // two seconds falls back to the stream wait (a failed launch must not hang the caller).
-bool poll_enabled() { return true; }
 int read_scalars_polled(ccm_ba* ba, double out[6], int flags[4], unsigned long long ticket) {
   volatile unsigned long long* tk = reinterpret_cast<volatile unsigned long long*>(ba->h_rb) + 8;
   bool got = false;
@@ -3330,29 +3334,45 @@ int read_scalars_polled(ccm_ba* ba, double out[6], int flags[4], unsigned long l
   return CCM_OK;
 }
 
+// Where ba_reduce_scalars and ba_maxdiag also leave their words and the ticket for the host: the pinned block on a single-rank handle, which polls it;
+// nowhere on a sharded one, whose scalars are all-reduced after the kernel and then copied.
+double* poll_block(const ccm_ba* ba) { return ba->nranks == 1 ? ba->h_rb : nullptr; }
+
+// The scalars' way home behind the launch that leaves them (ba_reduce_scalars with this ticket; maxdiag: ba_maxdiag's second stage): summed over the ranks
+// (maxdiag: scal[4], the maximum), then polled for or copied.
+int scalars_home(ccm_ba* ba, unsigned long long ticket, double s[6], int flags[4] = nullptr, bool maxdiag = false) {
+  RC(maxdiag ? ba_allreduce_max(ba, ba->d.scal + 4, 1) : ba_allreduce_sum(ba, ba->d.scal, 4));
+  return poll_block(ba) ? read_scalars_polled(ba, s, flags, ticket) : read_scalars(ba, s, flags);
+}
+
+// the landmark pass: back-substitution of the step at this lambda and chi2 of the trial state, or (eval_only) chi2 of the current state; edge-parallel
+// wherever the handle has landmark chunks
+void launch_backsub_chi2(ccm_ba* ba, double lambda, int eval_only) {
+  BaDev& d = ba->d;
+  if (d.chunk_off) hipLaunchKernelGGL(ba_backsub_chi2_e, dim3(d.n_chunk), dim3(kTPB), 0, ba->ctx->stream, d, ba->cur, lambda, eval_only);
+  else hipLaunchKernelGGL(ba_backsub_chi2, dim3(d.n_wg_pt), dim3(kTPB), 0, ba->ctx->stream, d, ba->cur, lambda, eval_only);
+}
+
 // chi2 of the current state (computeActiveErrors + activeRobustChi2)
 int eval_chi2(ccm_ba* ba, double* chi) {
   ccm_ctx* ctx = ba->ctx;
   BaDev& d = ba->d;
   {
     ccm_prof_scope ps(ctx, CCM_K_BA_CHI2);
-    if (d.chunk_off) hipLaunchKernelGGL(ba_backsub_chi2_e, dim3(d.n_chunk), dim3(kTPB), 0, ctx->stream, d, ba->cur, 0.0, 1);
-    else hipLaunchKernelGGL(ba_backsub_chi2, dim3(d.n_wg_pt), dim3(kTPB), 0, ctx->stream, d, ba->cur, 0.0, 1);
+    launch_backsub_chi2(ba, 0.0, 1);
   }
-  const bool poll = ba->nranks == 1 && poll_enabled();
   const unsigned long long ticket = ++ba->rb_ticket;
   hipLaunchKernelGGL(ba_reduce_scalars, dim3(1), dim3(kTPB), 0, ctx->stream, d, ba->stop_local(), 0, 0, kRedCamNone /* no step: no pose part */,
-                     (unsigned*)nullptr, poll ? ba->h_rb : (double*)nullptr, ticket);
-  RC(ba_allreduce_sum(ba, d.scal, 4));
+                     (unsigned*)nullptr, poll_block(ba), ticket);
   double s[6];
-  if (poll) { RC(read_scalars_polled(ba, s, nullptr, ticket)); } else { RC(read_scalars(ba, s)); }
+  RC(scalars_home(ba, ticket, s));
   *chi = s[0];
   ba->stop_any = s[2] > 0.0;
   return CCM_OK;
 }
 
 // lambda_next >= 0: the damping of the FIRST trial on this linearisation is already known (every LM iteration but the first): the landmark-side kernel also forms
-// D^-1 and D^-1 b_l for it and lm_trial skips its ba_dinv launch for that lambda
+// D^-1 and D^-1 b_l for it and reduced_system skips its ba_dinv launch for that lambda
 int build_system(ccm_ba* ba, double lambda_next = -1.0) {
   ccm_ctx* ctx = ba->ctx;
   BaDev& d = ba->d;
@@ -3385,14 +3405,12 @@ int max_diag(ccm_ba* ba, double* out) {
   const int nb = std::max(1, std::min(d.n_wg_pt, 512));   // partials live in part_pt (>= 2*n_wg_pt doubles)
   // one rank: the result comes through the pinned block and its ticket, like the trial scalars (read_scalars_polled: no copy command, no stream wait; the copy
   // remains its fallback after two seconds)
-  const bool poll = ba->nranks == 1 && poll_enabled();
-  const unsigned long long ticket = poll ? ++ba->rb_ticket : 0ull;
+  const unsigned long long ticket = poll_block(ba) ? ++ba->rb_ticket : 0ull;
   hipLaunchKernelGGL(ba_maxdiag, dim3(nb), dim3(kTPB), 0, ctx->stream, d, hpp, d.part_pt, nb, 0, (double*)nullptr, 0ull);
-  hipLaunchKernelGGL(ba_maxdiag, dim3(1), dim3(kTPB), 0, ctx->stream, d, hpp, d.part_pt, nb, 1, poll ? ba->h_rb : (double*)nullptr, ticket);
+  hipLaunchKernelGGL(ba_maxdiag, dim3(1), dim3(kTPB), 0, ctx->stream, d, hpp, d.part_pt, nb, 1, poll_block(ba), ticket);
   CCM_HIP_CHECK(ctx, hipGetLastError());
-  RC(ba_allreduce_max(ba, d.scal + 4, 1));
   double s[6];
-  if (poll) { RC(read_scalars_polled(ba, s, nullptr, ticket)); } else { RC(read_scalars(ba, s)); }
+  RC(scalars_home(ba, ticket, s, nullptr, true));
   *out = s[4];
   return CCM_OK;
 }
@@ -3423,9 +3441,24 @@ int coarse_build(ccm_ba* ba, double lambda) {
   return CCM_OK;
 }
 
-int coarse_prepare(ccm_ba* ba, double lambda) {
+// ---- what the trial driver carries from trial to trial: the coarse operator and its on / off switch, the cluster inverse of the persistent solver ----
+// Each has one decision before the solve and one note after it; reuse_reset is where every ccm_ba_run starts from.
+
+// the handle has a coarse level and the solver in use can apply it (a persistent handle that is cooling down on the multi-kernel path cannot)
+bool coarse_level(const ccm_ba* ba) { return ba->coarse_na && (ba->pers_grid || ba->d.mk_cpart); }
+
+// Before a solve: is the coarse level part of it (ba->coarse_used), and if so, is the operator at hand good enough or is a new one built (ba->coarse_fresh)?
+int coarse_decide(ccm_ba* ba, double lambda) {
+  ccm_ctx* ctx = ba->ctx;
+  // (round 4) a strongly damped system does not need the coarse level: above the call's first lambda (g2o's 1e-5 max diag(H): the scale at which the damping
+  // takes over the smooth modes as well) cluster-Jacobi alone converges in 10-24 iterations on the 4-agent map, while a stale coarse operator carried up
+  // there from a 16 times smaller lambda needed 46 and a fresh build costs ~50 iterations' worth.
+  const bool damped = ba->coarse_force == 0 && ba->lambda_first > 0 && lambda >= ba->lambda_first;
+  ba->coarse_skipped_damped = damped;
+  ba->coarse_used = coarse_level(ba) && !damped && (ba->coarse_force > 0 || (ba->coarse_force == 0 && ba->coarse_active));
+  if (!ba->coarse_used) return CCM_OK;
   // lambda window inside which a stale coarse operator is kept.  Measured on gba_c4 (10 calls each): window 4: 6 builds / 926 CG iterations /
-  // 21.9 ms per call, 16: 4 builds / 976 / 20.4 ms, 64: 4 builds / 982 / 20.8 ms.  The stale-iterations guard below still forces a rebuild when
+  // 21.9 ms per call, 16: 4 builds / 976 / 20.4 ms, 64: 4 builds / 982 / 20.8 ms.  The stale-iterations guard (coarse_note) still forces a rebuild when
   // a reused operator costs a third more iterations than a fresh one did.
   const double win = 16.0;
   // (round 4) UPWARDS the window is wider: lambda only grows along a chain of rejected trials (x2, x4, x8, ...), where every trial has its own lambda and a
@@ -3433,267 +3466,148 @@ int coarse_prepare(ccm_ba* ba, double lambda) {
   // the stale-iterations guard still forces a rebuild when a reused operator does badly
   // (measured, one box, complete calls: gba_c4 15.6 -> 15.2 ms with 2 builds instead of 3 and 567 instead of 538 CG iterations; gba_c3 unchanged; on the
   // multi-kernel path of gba_c5, where a CG iteration costs ~100 us against a 2.5 ms build, the wider window LOSES 10 ms (1546 instead of 1438 iterations): 16 there)
-  const double win_up_env = 0.0;
-  const double win_up = win_up_env > 0 ? win_up_env : (ba->pers_grid ? 64.0 : win);
-  const bool need = !ba->coarse_reuse || !ba->coarse_valid || ba->coarse_stale_bad || lambda > win_up * ba->coarse_lambda_built || lambda < ba->coarse_lambda_built / win;
-  ba->coarse_fresh = need;
-  if (!need) return CCM_OK;
-  RC(coarse_build(ba, lambda));
-  ba->coarse_valid = true; ba->coarse_stale_bad = false; ba->coarse_lambda_built = lambda;
+  const double win_up = ba->pers_grid ? 64.0 : win;
+  ba->coarse_fresh = !ba->coarse_valid || ba->coarse_stale_bad || lambda > win_up * ba->coarse_lambda_built || lambda < ba->coarse_lambda_built / win;
+  const bool timed = ba->pers_grid && ccm_dbg("coarse");
+  double tc0 = 0;
+  if (timed) { hipStreamSynchronize(ctx->stream); tc0 = now_ms(); }
+  if (ba->coarse_fresh) {
+    RC(coarse_build(ba, lambda));
+    ba->coarse_valid = true; ba->coarse_stale_bad = false; ba->coarse_lambda_built = lambda;
+  }
+  if (timed) {
+    const double tc1 = now_ms(); hipStreamSynchronize(ctx->stream);
+    fprintf(stderr, "[ccm_ba] coarse_build: enqueue %.3f ms, complete %.3f ms\n", tc1 - tc0, now_ms() - tc0);
+  }
   return CCM_OK;
 }
+
+// After a solve whose iteration count is known: the stale guard of the operator, and the switch for the next solve.
+void coarse_note(ccm_ba* ba, int iters) {
+  if (!coarse_level(ba)) return;
+  if (ba->coarse_used) {
+    if (ba->coarse_fresh) ba->coarse_fresh_iters = iters;
+    else if (iters > ba->coarse_fresh_iters + ba->coarse_fresh_iters / 3 + 8) ba->coarse_stale_bad = true;
+  }
+  const bool fine = ba->d.agg < kAggWide;
+  if (ba->coarse_skipped_damped) { /* the level was left out because of the damping, not by the switch: the switch keeps its state */ }
+  else if (!ba->coarse_used && iters >= (fine ? kCoarseOnItersFine : kCoarseOnIters)) ba->coarse_active = true;
+  else if (ba->coarse_used && iters <= (fine ? kCoarseOffItersFine : kCoarseOffIters)) ba->coarse_active = false;
+}
+
+// Cluster inverse W across trials.  Offline (1000-keyframe 4-agent reduced systems, numpy PCG to 1e-8): W built at a lambda 10 / 100 / 1000 times away
+// costs 0-2 / 2-3 / 5 more CG iterations of 24-46; W of the INITIAL linearisation used three LM iterations later costs 13-19 more (the robust weights move),
+// later linearisations hardly differ (the map itself disagreed, see the measurements below).
+// MEASURED on gba_c4 (one box): a launch that loads W is 55-65 us shorter than one that factors (589 against 646 us at 39 CG iterations);
+// inside an LM iteration a W built at lambda / 2 ... lambda / 8 costs no iteration, at lambda / 64 three (28 against 25), at lambda / 32 on a lambda-dominated
+// system (1.4e4) ten (21 against 11); ACROSS linearisations it is erratic: 32 against 31, 41 / 41, 43 / 43, but 87 against 48 (second linearisation), 58 / 43,
+// 66 / 41 — and every bad solve also trips the coarse level's stale guard (6 builds instead of 4): 19.2 ms per call against 17.0.  Hence the policy:
+// reuse inside an LM iteration only (rejected trials: only lambda moved) with a window of 8: 3 of the 7 rejected trials of gba_c4 load, ~0.2 ms of 17.
+// Before a persistent launch: does it load the saved inverse (true) or factor and save its own?
+bool w_decide(ccm_ba* ba, double lambda, bool test_abort) {
+  const double w_win = 8.5;
+  const bool in_win = ba->w_lambda_built > 0 && lambda <= w_win * ba->w_lambda_built && lambda >= ba->w_lambda_built / w_win;
+  const bool reuse = ba->d_pers_wsave && ba->w_valid && in_win && !test_abort && ba->w_lin_id == ba->lin_id;
+  // (advisor, round 4) what this launch will leave in wsave becomes reusable only AFTER its flags have been read and show a clean solve (w_note): until
+  // then no inverse is on offer, so a repeat of this trial on the multi-kernel path, a failed launch or a bad pivot can never hand a half-written or
+  // patched W to a later trial
+  if (!reuse) { ba->w_valid = false; ba->w_pending = ba->d_pers_wsave != nullptr; ba->w_lambda_built = lambda; ba->w_lin_id = ba->lin_id; }
+  return reuse;
+}
+// After a persistent solve whose flags have been read: the launch that factored has finished cleanly: its W may be loaded from now on; a failed solve
+// (bad pivot, NaN) never leaves an inverse behind to be reused.
+void w_note(ccm_ba* ba, bool solve_failed) {
+  if (solve_failed) ba->w_valid = false;
+  else if (ba->w_pending) ba->w_valid = true;
+  ba->w_pending = false;
+}
+
+// every run starts from the same preconditioner state
+void reuse_reset(ccm_ba* ba) {
+  ba->coarse_active = false;
+  ba->coarse_valid = false; ba->coarse_stale_bad = false; ba->coarse_fresh_iters = 0;
+  ba->w_valid = false; ba->w_lambda_built = 0; ba->lin_id = 0; ba->w_lin_id = -1;
+  ba->mk_prev_iters = 0;
+}
+
+int solve_persistent(ccm_ba* ba, double lambda, double tol, int max_it, bool* refused);   // the two long solver bodies follow lm_trial
+int solve_multi_kernel(ccm_ba* ba, double lambda, double tol, int max_it, int (&flags)[4], int* iters);
 
 // one LM trial: solve with lambda, write trial state, return tempChi, scale, ok
 int lm_trial(ccm_ba* ba, double lambda, const ccm_ba_options& opt, double* temp_chi, double* scale, bool* ok, int* pcg_iters) {
   ccm_ctx* ctx = ba->ctx;
   BaDev& d = ba->d;
-  const int cur = ba->cur;
+  const int cur = ba->cur, rank0 = ba->rank == 0 ? 1 : 0;
   if (!ba->pers_grid && ba->pers_grid_built && ba->pers_cooldown > 0 && --ba->pers_cooldown == 0) ba->pers_grid = ba->pers_grid_built;   // back to the persistent solver after an abort
-  if (d.Lloc && ba->dinv_done_lambda != lambda) {   // (the linearisation already formed D^-1 for this lambda: build_system)
-    ccm_prof_scope ps(ctx, CCM_K_BA_DINV);
-    hipLaunchKernelGGL(ba_dinv, dim3(d.n_wg_pt), dim3(kTPB), 0, ctx->stream, d, lambda);
-  }
-  ba->dinv_done_lambda = -1.0;   // the next trial on this linearisation has another lambda
-  *ok = true;
+  RC(reduced_system(ba, lambda));
+  // the reduced solver, by what the handle was built with (ba_build.hip).  The exact solvers' and the persistent launch (unless CCM_BA_PERS_CAMUPD=0) also
+  // apply the step to the cameras; every solver but the multi-kernel one is queued without a host round trip: its flags come back with the trial scalars
+  enum { kNoCams, kCholReg, kDense2, kSmall, kPersist, kMulti } solver =
+      !d.Cp ? kNoCams : ba->d_cholreg_L ? kCholReg : (d.Cp <= kDense2MaxCp && d.Cp > kSmallMaxCp && ba->d_dense_T && ba->d_pers_coff) ? kDense2
+      : d.Cp <= kSmallMaxCp ? kSmall : ba->pers_grid ? kPersist : kMulti;
+  bool launch_refused = false;
+  int flags[4] = {0, 0, 0, 0};
   *pcg_iters = 0;
-  bool small_path = false, pers_trial = false, pers_launch_failed = false, cams_updated = false;
-  int small_flags[4] = {0, 0, 0, 0};
   if (d.Cp) {
-    RC(launch_schur(ba));
     RC(ba_allreduce_sum(ba, ba->d_red, ba->red_count));
-    // ---- PCG ----
-    const double tol_default = 1e-8;   // (ccm_ba_options.pcg_rel_tol overrides; the parity tests run at 1e-8)
-    const double tol = opt.pcg_rel_tol > 0 ? opt.pcg_rel_tol : tol_default;
+    const double tol = opt.pcg_rel_tol > 0 ? opt.pcg_rel_tol : 1e-8;   // (the parity tests run at 1e-8)
     const int max_it = opt.pcg_max_iters > 0 ? opt.pcg_max_iters : 1000;
-    int flags[4] = {0, 0, 0, 0};
-    const bool dense2_on = true;
-    // (round 6) 17..50 free cameras: exact Cholesky with the matrix in one CU's register file (ba_solve_cholreg).  CCM_BA_CHOLREG=0 keeps the earlier solvers
-    // (two-cluster exact solve up to 32 cameras, persistent PCG above) for A / B measurements and for the tests that compare the paths (read when the handle is created).
-    if (ba->d_cholreg_L) {   // (decided at create time: ba_build.hip, cholreg_win)
-      CCM_LDS_ATTR(ctx, CCM_LDS_BA_CHOLREG, ba_solve_cholreg, cholreg_lds_bytes());
-      if (!ba->cholreg_table_built) {   // structure only: once per handle (ccm_ba_set_edge_levels keeps the block structure)
-        hipLaunchKernelGGL(ba_cholreg_table, dim3(1), dim3(kCRTPB), 0, ctx->stream, d, ba->d_cholreg_tab);
-        ba->cholreg_table_built = true;
+    if (solver == kCholReg || solver == kDense2) {
+      // exact solve in one workgroup.  (round 6) 17..50 free cameras: Cholesky with the matrix in one CU's register file (ba_solve_cholreg).  CCM_BA_CHOLREG=0
+      // (read when the handle is created: ba_build.hip, cholreg_win) keeps the earlier solvers (the two-cluster block solve ba_solve_dense2 up to 32 cameras,
+      // persistent PCG above) for A / B measurements and for the tests that compare the paths.
+      if (solver == kDense2) CCM_LDS_ATTR(ctx, CCM_LDS_BA_DENSE2, ba_solve_dense2, dense2_lds_bytes());
+      else {
+        CCM_LDS_ATTR(ctx, CCM_LDS_BA_CHOLREG, ba_solve_cholreg, cholreg_lds_bytes());
+        if (!ba->cholreg_table_built) {   // structure only: once per handle (ccm_ba_set_edge_levels keeps the block structure)
+          hipLaunchKernelGGL(ba_cholreg_table, dim3(1), dim3(kCRTPB), 0, ctx->stream, d, ba->d_cholreg_tab);
+          ba->cholreg_table_built = true;
+        }
       }
-      {
-        ccm_prof_scope ps(ctx, CCM_K_BA_PCG_PERSIST);
-        hipLaunchKernelGGL(ba_solve_cholreg, dim3(1), dim3(kCRTPB), cholreg_lds_bytes(), ctx->stream, d, lambda, ba->d_cholreg_L, (const int*)ba->d_cholreg_tab,
-                           ccm_dbg("cholreg") ? (long long*)ba->d_cholreg_dbg : (long long*)nullptr, cur, ba->rank == 0 ? 1 : 0);
-      }
-      small_path = true;
-      cams_updated = true;   // (the solve's launch also applied the step to the cameras)
-    } else if (d.Cp > kSmallMaxCp && d.Cp <= kDense2MaxCp && ba->d_dense_T && ba->d_pers_coff && dense2_on) {
-      // exact block solve in one workgroup (see ba_solve_dense2): one launch, flags read back with the trial scalars
-      CCM_LDS_ATTR(ctx, CCM_LDS_BA_DENSE2, ba_solve_dense2, dense2_lds_bytes());
-      {
-        ccm_prof_scope ps(ctx, CCM_K_BA_PCG_PERSIST);
+      ccm_prof_scope ps(ctx, CCM_K_BA_PCG_PERSIST);
+      if (solver == kDense2)
         hipLaunchKernelGGL(ba_solve_dense2, dim3(1), dim3(kPersTPB), dense2_lds_bytes(), ctx->stream, d, lambda, (const int*)ba->d_pers_coff, (const int*)ba->d_pers_cij,
-                           (const uint32_t*)ba->d_pers_cblk, ba->d_dense_T,
-                           ccm_dbg("dense2") ? (long long*)(ba->d_dense_T + kCluN * kCluN) : (long long*)nullptr, cur, ba->rank == 0 ? 1 : 0);
-      }
-      small_path = true;
-      cams_updated = true;   // (the solve's launch also applied the step to the cameras)
-    } else if (d.Cp <= kSmallMaxCp) {
-      // one launch, no host round trip: the flags are read back after the trial kernels are queued
+                           (const uint32_t*)ba->d_pers_cblk, ba->d_dense_T, ccm_dbg("dense2") ? (long long*)(ba->d_dense_T + kCluN * kCluN) : (long long*)nullptr, cur, rank0);
+      else
+        hipLaunchKernelGGL(ba_solve_cholreg, dim3(1), dim3(kCRTPB), cholreg_lds_bytes(), ctx->stream, d, lambda, ba->d_cholreg_L, (const int*)ba->d_cholreg_tab,
+                           ccm_dbg("cholreg") ? (long long*)ba->d_cholreg_dbg : (long long*)nullptr, cur, rank0);
+    } else if (solver == kSmall) {
       size_t lds = (size_t)(5 * 6 * d.Cp + 36 * d.Cp + 18) * sizeof(double);
       const size_t lds_S = 36 * (size_t)(d.Cp + d.nOff) * sizeof(double) + ((size_t)d.Cp + 1 + 2 * (size_t)ba->n_row_entries) * sizeof(int) + 16;
       const int stage_S = (lds + lds_S <= 150 * 1024) ? 1 : 0;
       if (stage_S) lds += lds_S;
       CCM_LDS_ATTR(ctx, CCM_LDS_BA_SMALL, ba_pcg_small<1024>, 150 * 1024);
-      {
-        ccm_prof_scope ps(ctx, CCM_K_BA_PCG_SPMV);
-        // measured on lba_c2 (30 free cameras, ~64 PCG iterations per solve): 16 waves 460 us, 1 wave 1420 us — the
-        // row products are LDS-latency chains, so more waves (rows in flight) win even with barriers
-        hipLaunchKernelGGL(ba_pcg_small<1024>, dim3(1), dim3(1024), lds, ctx->stream, d, lambda, tol, max_it, stage_S, (int)ba->n_row_entries);
-      }
-      small_path = true;
+      ccm_prof_scope ps(ctx, CCM_K_BA_PCG_SPMV);
+      // measured on lba_c2 (30 free cameras, ~64 PCG iterations per solve): 16 waves 460 us, 1 wave 1420 us — the
+      // row products are LDS-latency chains, so more waves (rows in flight) win even with barriers
+      hipLaunchKernelGGL(ba_pcg_small<1024>, dim3(1), dim3(1024), lds, ctx->stream, d, lambda, tol, max_it, stage_S, (int)ba->n_row_entries);
     } else {
-    bool persist_ok = false;
-    if (ba->pers_grid) {
-      // whole solve in one launch; flags are read back together with the trial scalars
-      PersArgs pa = pers_args(ba, lambda, tol, max_it);
-      pa.test_abort = getenv("CCM_BA_TEST_ABORT") ? 1 : 0;
-      pa.dbg = ccm_dbg("pers") ? (long long*)(ba->d_pers_bar + 4) : nullptr;
-      // the launch also applies the step to the cameras (pers_update_cams; CCM_BA_PERS_CAMUPD=0: the separate ba_update_cams launch)
-      pa.cam_upd = ba->pers_camupd ? 1 : 0; pa.cur = cur; pa.add_lambda_term = ba->rank == 0 ? 1 : 0;
-      // Cluster inverse across trials.  Offline (1000-keyframe 4-agent reduced systems, numpy PCG to 1e-8): W built at a lambda 10 / 100 / 1000 times away
-      // costs 0-2 / 2-3 / 5 more CG iterations of 24-46; W of the INITIAL linearisation used three LM iterations later costs 13-19 more (the robust weights move),
-      // later linearisations hardly differ (the map itself disagreed, see the measurements below).  Policy: reuse inside an LM iteration (rejected trials: only lambda moved) within a lambda window, and across
-      // iterations as long as the solve that first used a carried-over inverse did not need noticeably more iterations than the last fresh one (the counts
-      // are deterministic, so the decision is — on every rank of a sharded run alike).  CCM_BA_W_REUSE=0 never, 1 (default) inside an iteration only, 2 adaptive across iterations.
-      // MEASURED on gba_c4 (CCM_BA_TRIAL_DBG, one box): a launch that loads W is 55-65 us shorter than one that factors (589 against 646 us at 39 CG iterations);
-      // inside an LM iteration a W built at lambda / 2 ... lambda / 8 costs no iteration, at lambda / 64 three (28 against 25), at lambda / 32 on a lambda-dominated
-      // system (1.4e4) ten (21 against 11); ACROSS linearisations it is erratic: 32 against 31, 41 / 41, 43 / 43, but 87 against 48 (second linearisation), 58 / 43,
-      // 66 / 41 — and every bad solve also trips the coarse level's stale guard (6 builds instead of 4): 19.2 ms per call against 17.0.  Hence the default:
-      // mode 1 (same linearisation only) with a window of 8: 3 of the 7 rejected trials of gba_c4 load, ~0.2 ms of 17.
-      const int w_mode = 1;
-      const double w_win = 8.5;
-      pa.wsave = ba->d_pers_wsave;
-      {
-        const bool same_lin = ba->w_lin_id == ba->lin_id;
-        const bool in_win = ba->w_lambda_built > 0 && lambda <= w_win * ba->w_lambda_built && lambda >= ba->w_lambda_built / w_win;
-        const bool reuse = ba->d_pers_wsave && w_mode > 0 && ba->w_valid && in_win && !pa.test_abort && (same_lin || (w_mode >= 2 && !ba->w_stale_bad));
-        pa.w_load = reuse ? 1 : 0;
-        ba->w_loaded = reuse;
-        // (advisor, round 4) what this launch will leave in wsave becomes reusable only AFTER its flags have been read and show a clean solve (below): until
-        // then no inverse is on offer, so a repeat of this trial on the multi-kernel path, a failed launch or a bad pivot can never hand a half-written or
-        // patched W to a later trial
-        if (!reuse) { ba->w_valid = false; ba->w_pending = ba->d_pers_wsave != nullptr; ba->w_lambda_built = lambda; ba->w_lin_id = ba->lin_id; ba->w_stale_bad = false; }
-      }
-      // (round 4) a strongly damped system does not need the coarse level: above the call's first lambda (g2o's 1e-5 max diag(H): the scale at which the damping
-      // takes over the smooth modes as well) cluster-Jacobi alone converges in 10-24 iterations on the 4-agent map, while a stale coarse operator carried up
-      // there from a 16 times smaller lambda needed 46 and a fresh build costs ~50 iterations' worth.  CCM_BA_COARSE_LMAX scales the limit (0 = no limit).
-      const double coarse_lmax = 1.0;
-      const bool damped = ba->coarse_force == 0 && coarse_lmax > 0 && ba->lambda_first > 0 && lambda >= coarse_lmax * ba->lambda_first;
-      const bool use_coarse = ba->coarse_na && !damped && (ba->coarse_force > 0 || (ba->coarse_force == 0 && ba->coarse_active));
-      ba->coarse_used = use_coarse;
-      ba->coarse_skipped_damped = damped;
-      if (use_coarse) {
-        if (ccm_dbg("coarse")) {
-          hipStreamSynchronize(ctx->stream); const double tc0 = now_ms();
-          RC(coarse_prepare(ba, lambda));
-          const double tc1 = now_ms(); hipStreamSynchronize(ctx->stream);
-          fprintf(stderr, "[ccm_ba] coarse_build: enqueue %.3f ms, complete %.3f ms\n", tc1 - tc0, now_ms() - tc0);
-        } else
-        RC(coarse_prepare(ba, lambda));
-        pers_args_coarse(ba, &pa);
-      }
-      static const bool trial_dbg = ccm_dbg("trial");   // development: wall clock of every persistent solve (adds two stream syncs per trial)
-      double tdbg0 = 0;
-      if (trial_dbg) { hipStreamSynchronize(ctx->stream); tdbg0 = now_ms(); }
-      {
-        // per-device lease: a persistent launch of ANOTHER context of this process (a second Map's global BA, a local BA beside it) is ordered before this
-        // one on the GPU; nothing is recorded or waited for while this is the only context on the device
-        ccm_coresident_scope lease(ctx);
-        ccm_prof_scope ps(ctx, CCM_K_BA_PCG_PERSIST);
-        // A cooperative launch guarantees co-residency but, measured with rocprofv3 on MI355X / ROCm 7.2, leaves the
-        // GPU idle for ~0.55 ms before the kernel starts (18 launches: 10.5 ms of 53); an ordinary launch starts after
-        // ~13 us.  The grid was sized at create time to fit the device at the kernel's occupancy, so on a stream whose
-        // earlier work has drained all workgroups become resident; if they ever do not (device shared with another
-        // long-running kernel), the bounded spins of pers_exchange abort the solve, pcg_flag[3] reports it and the trial
-        // is repeated on the multi-kernel path below.  (The cooperative launch itself was removed in round 5.)
-        hipLaunchKernelGGL(ba_pcg_persist, dim3(ba->pers_grid), dim3(kPersTPB), pers_lds_bytes(), ctx->stream, d, pa);
-        const hipError_t le = hipGetLastError();
-        if (le == hipSuccess) persist_ok = true;
-        else { (void)hipGetLastError(); ba->pers_grid = 0; ba->pers_grid_built = 0; ba->w_valid = false; pers_launch_failed = true; }   // the launch itself was refused: multi-kernel path from now on
-      }
-      if (persist_ok) { small_path = pers_trial = true; cams_updated = pa.cam_upd != 0; }
-      if (trial_dbg) {
-        hipStreamSynchronize(ctx->stream);
-        int fl[4] = {0, 0, 0, 0};
-        hipMemcpy(fl, d.pcg_flag, sizeof(fl), hipMemcpyDeviceToHost);
-        fprintf(stderr, "[ccm_ba] trial: lin %d lambda %.4g persist %.1f us, %d CG iterations, coarse %s, W %s\n", ba->lin_id, lambda, (now_ms() - tdbg0) * 1e3, fl[1],
-                !use_coarse ? "off" : ba->coarse_fresh ? "built" : "reused", pa.w_load ? "loaded" : "factored");
-      }
+      if (solver == kPersist) RC(solve_persistent(ba, lambda, tol, max_it, &launch_refused));
+      if (launch_refused) solver = kMulti;
+      if (solver == kMulti) RC(solve_multi_kernel(ba, lambda, tol, max_it, flags, pcg_iters));
     }
-    if (!persist_ok) {
-      d.mk_on = 0;
-      const double coarse_lmax_mk = 1.0;
-      const bool damped_mk = ba->coarse_force == 0 && coarse_lmax_mk > 0 && ba->lambda_first > 0 && lambda >= coarse_lmax_mk * ba->lambda_first;
-      ba->coarse_skipped_damped = damped_mk;
-      if (d.mk_cpart && ba->coarse_na && !damped_mk && (ba->coarse_force > 0 || (ba->coarse_force == 0 && ba->coarse_active))) {
-        RC(coarse_prepare(ba, lambda));
-        d.mk_on = 1;
-      }
-      ba->coarse_used = d.mk_on != 0;
-      CCM_HIP_CHECK(ctx, hipMemsetAsync(d.pcg_flag, 0, 4 * sizeof(int), ctx->stream));
-      if (d.S32) {   // the f32 copy of this trial's S for the product kernel (114 -> 57 MB on the 10 000-keyframe map, once per trial)
-        const size_t n4 = 9 * (size_t)(d.Cp + d.nOff);
-        hipLaunchKernelGGL(ba_s_to_f32, dim3((unsigned)ccm_div_up((int64_t)n4, kTPB)), dim3(kTPB), 0, ctx->stream, (const double*)d.S, d.S32, n4);
-      }
-      {
-        const size_t lds_tiles = (size_t)(2 * kCluN * kCluN + kCluN + kPersWaves) * sizeof(double) + 16;
-        CCM_LDS_ATTR(ctx, CCM_LDS_BA_TILES, ba_pcg_init_tiles, lds_tiles);
-        if (!ba->d_pers_coff) return ccm_set_error(ctx, CCM_E_STATE, "ccm_ba: cluster entry lists missing");
-        hipLaunchKernelGGL(ba_pcg_init_tiles, dim3(d.n_wg_upd), dim3(kPersTPB), lds_tiles, ctx->stream, d, lambda, tol, (const int*)ba->d_pers_coff,
-                           (const int*)ba->d_pers_cij, (const uint32_t*)ba->d_pers_cblk);
-        if (d.mk_on) hipLaunchKernelGGL(ba_pcg_coarse_apply, dim3(d.mk_na), dim3(kTPB), 6 * (size_t)(d.mk_na + 1) * sizeof(double), ctx->stream, d, 0);
-      }
-      // The host learns that the solve has converged from the flags it reads back between chunks of queued iterations; every iteration queued beyond the converged
-      // one is three launches that return at once (~3 us each + their gaps).  Round 5: the first chunk is sized by the PREVIOUS solve of the handle (consecutive
-      // trials of a call need similar counts: 60 - 75 on the 10 000-keyframe map), the following ones are short — ~3 instead of ~12 idle iterations per solve
-      // (1680 -> ~1510 launches of each kernel for the 1440 iterations of that call).  The counts are deterministic, so every rank of a sharded run queues alike.
-      const int sym_grid = 512;   // two 16-wave workgroups per CU
-      const dim3 g_spmv(std::min(d.n_wg_spmv, sym_grid));
-      const size_t lds_ca = 6 * (size_t)(d.mk_na + 1) * sizeof(double);
-      const bool f32 = d.S32 != nullptr;
-      // the true residual r = b - (S + lambda I) x in place of the recurrence's (f64 blocks), followed by z = M^-1 r and its dot products: what iteration kk's update leaves
-      auto replace_residual = [&](int kk) {
-        { ccm_prof_scope ps(ctx, CCM_K_BA_PCG_SPMV); hipLaunchKernelGGL((ba_pcg_spmv<false, true>), g_spmv, dim3(kSpmvTPB), 0, ctx->stream, d, kk); }
-        ccm_prof_scope ps(ctx, CCM_K_BA_PCG_UPDATE);
-        hipLaunchKernelGGL(ba_pcg_update<true>, dim3(d.n_wg_upd), dim3(kTPB), 0, ctx->stream, d, kk);
-        if (d.mk_on) hipLaunchKernelGGL(ba_pcg_coarse_apply, dim3(d.mk_na), dim3(kTPB), lds_ca, ctx->stream, d, (kk + 1) & 1);
-      };
-      int k = 0, verified_at = -1;
-      // (second half of round 5) the first chunk reaches two iterations BEYOND the previous solve's count — an iteration queued in vain is three launches that return at
-      // once (~8 us), a chunk that stops short is a read-back with the device idle (~40 us) plus most of the next chunk in vain —, and the question that follows a
-      // verification (below) is ONE iteration, not a chunk: 13.5 -> ~7 iterations queued in vain per solve on the 10 000-keyframe map.
-      bool first_chunk = true, after_verify = false;
-      while (k < max_it) {
-        const int chunk = first_chunk ? (ba->mk_prev_iters > 0 ? std::max(8, ba->mk_prev_iters + 2) : 24) : after_verify ? 1 : 6;
-        first_chunk = false; after_verify = false;
-        const int kend = std::min(max_it, k + chunk);
-        for (; k < kend; k++) {
-          {
-            ccm_prof_scope ps(ctx, CCM_K_BA_PCG_SPMV);
-            if (f32) hipLaunchKernelGGL((ba_pcg_spmv<true, false>), g_spmv, dim3(kSpmvTPB), 0, ctx->stream, d, k);
-            else hipLaunchKernelGGL((ba_pcg_spmv<false, false>), g_spmv, dim3(kSpmvTPB), 0, ctx->stream, d, k);
-          }
-          if (f32 && (k + 1) % kMkReplaceEvery == 0) {
-            { ccm_prof_scope ps(ctx, CCM_K_BA_PCG_UPDATE); hipLaunchKernelGGL(ba_pcg_xupdate, dim3(d.n_wg_upd), dim3(kTPB), 0, ctx->stream, d, k); }
-            replace_residual(k);
-          } else {
-            ccm_prof_scope ps(ctx, CCM_K_BA_PCG_UPDATE);
-            hipLaunchKernelGGL(ba_pcg_update<false>, dim3(d.n_wg_upd), dim3(kTPB), 0, ctx->stream, d, k);
-            if (d.mk_on) hipLaunchKernelGGL(ba_pcg_coarse_apply, dim3(d.mk_na), dim3(kTPB), lds_ca, ctx->stream, d, (k + 1) & 1);
-          }
-        }
-        CCM_HIP_CHECK(ctx, hipMemcpyAsync(flags, d.pcg_flag, sizeof(flags), hipMemcpyDeviceToHost, ctx->stream));
-        CCM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        if (flags[0]) {
-          // f32 product: the recurrence says "converged at iteration N" (the launches queued behind that test returned at once, so x = x_N).  Unless r_N is a replaced
-          // residual already, form the true one and put the question again: the test at the top of iteration N then speaks about b - (S + lambda I) x_N itself.
-          const int N = flags[1];
-          if (f32 && !flags[2] && N > 0 && N % kMkReplaceEvery != 0 && verified_at != N) {
-            verified_at = N;
-            CCM_HIP_CHECK(ctx, hipMemsetAsync(d.pcg_flag, 0, 2 * sizeof(int), ctx->stream));
-            replace_residual(N - 1);
-            k = N;
-            after_verify = true;
-            flags[0] = 0;
-            continue;
-          }
-          break;
-        }
-      }
-      *pcg_iters = flags[0] ? flags[1] : k;
-      ba->mk_prev_iters = *pcg_iters;
-    }
-    }
-    if (flags[2]) *ok = false;   // not SPD / NaN: linear solver failure (levenberg.cpp:126-127)
   }
+  const bool flags_ride = solver != kNoCams && solver != kMulti;
+  const bool cams_updated = solver == kCholReg || solver == kDense2 || (solver == kPersist && ba->pers_camupd);
   if (d.Cp && !cams_updated) {
     ccm_prof_scope ps(ctx, CCM_K_BA_UPDATE);
-    hipLaunchKernelGGL(ba_update_cams, dim3(d.n_wg_cam), dim3(kTPB), 0, ctx->stream, d, cur, lambda, ba->rank == 0 ? 1 : 0, ba->d_pers_bar /* nullptr when the handle has no persistent solver; cleared also while it is cooling down after an abort */);
+    hipLaunchKernelGGL(ba_update_cams, dim3(d.n_wg_cam), dim3(kTPB), 0, ctx->stream, d, cur, lambda, rank0, ba->d_pers_bar /* nullptr when the handle has no persistent solver; cleared also while it is cooling down after an abort */);
   }   // (no free camera: ba_reduce_scalars is told that there is no pose part)
   {
     ccm_prof_scope ps(ctx, CCM_K_BA_BACKSUB);
-    if (d.chunk_off) hipLaunchKernelGGL(ba_backsub_chi2_e, dim3(d.n_chunk), dim3(kTPB), 0, ctx->stream, d, cur, lambda, 0);
-    else hipLaunchKernelGGL(ba_backsub_chi2, dim3(d.n_wg_pt), dim3(kTPB), 0, ctx->stream, d, cur, lambda, 0);
+    launch_backsub_chi2(ba, lambda, 0);
   }
   // a sharded run repeats the trial on EVERY rank when the persistent kernel gave up (or could not be launched) on ANY rank:
   // the repeat issues the same collectives again, and all ranks must keep bit-identical camera states
-  const bool poll = ba->nranks == 1 && poll_enabled();
   const unsigned long long ticket = ++ba->rb_ticket;
   {
     ccm_prof_scope ps(ctx, CCM_K_BA_REDUCE);
-    hipLaunchKernelGGL(ba_reduce_scalars, dim3(1), dim3(kTPB), 0, ctx->stream, d, ba->stop_local(), (pers_launch_failed && ba->nranks > 1) ? 1 : 0,
-                       pers_trial ? 1 : 0, !d.Cp ? kRedCamNone : (pers_trial && cams_updated) ? kRedCamTerms : kRedCamPart,
-                       ba->d_pers_bar /* nullptr when the handle has no persistent solver; cleared also while it is cooling down after an abort */, poll ? ba->h_rb : (double*)nullptr, ticket);
+    hipLaunchKernelGGL(ba_reduce_scalars, dim3(1), dim3(kTPB), 0, ctx->stream, d, ba->stop_local(), (launch_refused && ba->nranks > 1) ? 1 : 0,
+                       solver == kPersist ? 1 : 0, !d.Cp ? kRedCamNone : (solver == kPersist && cams_updated) ? kRedCamTerms : kRedCamPart,
+                       ba->d_pers_bar /* nullptr when the handle has no persistent solver; cleared also while it is cooling down after an abort */, poll_block(ba), ticket);
   }
-  RC(ba_allreduce_sum(ba, d.scal, 4));
   double s[6];
-  if (poll) { RC(read_scalars_polled(ba, s, small_flags, ticket)); } else { RC(read_scalars(ba, s, small_flags)); }
+  RC(scalars_home(ba, ticket, s, flags_ride ? flags : nullptr));
   CCM_HIP_CHECK(ctx, hipGetLastError());
   ba->stop_any = s[2] > 0.0;
   // s[3] is summed over the ranks: the persistent kernel gave up (or could not be launched) SOMEWHERE.  Every rank repeats the trial on the multi-kernel
@@ -3704,36 +3618,144 @@ int lm_trial(ccm_ba* ba, double lambda, const ccm_ba_options& opt, double* temp_
     // the persistent kernel again — whatever held the CUs (another process on the device, a long foreign kernel) has usually gone by then.  s[3] is the
     // reduced value, so every rank of a sharded run counts the same trials.  The carried-over cluster inverse is dropped: the aborted launch may have
     // written part of it.
-    if (pers_trial) { ccm_coresident_note_abort(ctx); ba->pers_aborts++; }
+    if (solver == kPersist) ccm_coresident_note_abort(ctx);
     ba->pers_grid = 0; ba->pers_cooldown = kPersCooldownTrials;
     // (round 6) a sharded handle cools down like a single-rank one: s[3] is the all-reduced value, so every rank counts the same trials and returns to the persistent
     // kernel at the same trial.  Only a refused LAUNCH on some rank (>= 4096 in the sum) is for good — that rank cannot come back, and all ranks must keep the same solver path.
     if (ba->nranks > 1 && s[3] >= 4096.0) ba->pers_grid_built = 0;
-    ba->w_valid = false; ba->w_pending = false;
+    w_note(ba, true);
     return lm_trial(ba, lambda, opt, temp_chi, scale, ok, pcg_iters);
   }
-  if (small_path) { *pcg_iters = small_flags[1]; if (small_flags[2]) *ok = false; }
-  if (pers_trial) {   // iteration guard of the carried-over cluster inverse
-    if (!ba->w_loaded) ba->w_fresh_iters = *pcg_iters;
-    else if (ba->w_lin_id != ba->lin_id && *pcg_iters > ba->w_fresh_iters + ba->w_fresh_iters / 8 + 3) ba->w_stale_bad = true;
-    if (ba->w_pending) { ba->w_valid = !small_flags[2]; ba->w_pending = false; }   // the launch that factored has finished cleanly: its W may be loaded from now on
-    if (small_flags[2]) ba->w_valid = false;   // a failed solve (bad pivot, NaN) never leaves an inverse behind to be reused
-  }
-  if (ba->coarse_na && (small_path || d.mk_cpart)) {
-    if (ba->coarse_used) {
-      if (ba->coarse_fresh) ba->coarse_fresh_iters = *pcg_iters;
-      else if (*pcg_iters > ba->coarse_fresh_iters + ba->coarse_fresh_iters / 3 + 8) ba->coarse_stale_bad = true;
-    }
-    const int on_env = 0;
-    const int off_env = 0;
-    const int on_it = on_env ? on_env : (d.agg < kAggWide ? kCoarseOnItersFine : kCoarseOnIters);
-    const int off_it = off_env ? off_env : (d.agg < kAggWide ? kCoarseOffItersFine : kCoarseOffIters);
-    if (ba->coarse_skipped_damped) { /* the level was left out because of the damping, not by the switch: the switch keeps its state */ }
-    else if (!ba->coarse_used && *pcg_iters >= on_it) ba->coarse_active = true;
-    else if (ba->coarse_used && *pcg_iters <= off_it) ba->coarse_active = false;
-  }
+  if (flags_ride) *pcg_iters = flags[1];
+  *ok = !flags[2];   // not SPD / NaN: linear solver failure (levenberg.cpp:126-127)
+  if (solver == kPersist) w_note(ba, flags[2] != 0);
+  coarse_note(ba, *pcg_iters);
   *temp_chi = s[0];
   *scale = s[1];
+  return CCM_OK;
+}
+
+// The persistent PCG: the whole solve in one launch; its flags are read back together with the trial scalars.  *refused: the launch itself was
+// refused and the handle is on the multi-kernel path from now on.
+int solve_persistent(ccm_ba* ba, double lambda, double tol, int max_it, bool* refused) {
+  ccm_ctx* ctx = ba->ctx;
+  BaDev& d = ba->d;
+  PersArgs pa = pers_args(ba, lambda, tol, max_it);
+  pa.test_abort = getenv("CCM_BA_TEST_ABORT") ? 1 : 0;
+  pa.dbg = ccm_dbg("pers") ? (long long*)(ba->d_pers_bar + 4) : nullptr;
+  // the launch also applies the step to the cameras (pers_update_cams; CCM_BA_PERS_CAMUPD=0: the separate ba_update_cams launch)
+  pa.cam_upd = ba->pers_camupd ? 1 : 0; pa.cur = ba->cur; pa.add_lambda_term = ba->rank == 0 ? 1 : 0;
+  pa.wsave = ba->d_pers_wsave;
+  pa.w_load = w_decide(ba, lambda, pa.test_abort != 0) ? 1 : 0;
+  RC(coarse_decide(ba, lambda));
+  if (ba->coarse_used) pers_args_coarse(ba, &pa);
+  static const bool trial_dbg = ccm_dbg("trial");   // development: wall clock of every persistent solve (adds two stream syncs per trial)
+  double tdbg0 = 0;
+  if (trial_dbg) { hipStreamSynchronize(ctx->stream); tdbg0 = now_ms(); }
+  {
+    // per-device lease: a persistent launch of ANOTHER context of this process (a second Map's global BA, a local BA beside it) is ordered before this
+    // one on the GPU; nothing is recorded or waited for while this is the only context on the device
+    ccm_coresident_scope lease(ctx);
+    ccm_prof_scope ps(ctx, CCM_K_BA_PCG_PERSIST);
+    // A cooperative launch guarantees co-residency but, measured with rocprofv3 on MI355X / ROCm 7.2, leaves the
+    // GPU idle for ~0.55 ms before the kernel starts (18 launches: 10.5 ms of 53); an ordinary launch starts after
+    // ~13 us.  The grid was sized at create time to fit the device at the kernel's occupancy, so on a stream whose
+    // earlier work has drained all workgroups become resident; if they ever do not (device shared with another
+    // long-running kernel), the bounded spins of pers_exchange abort the solve, pcg_flag[3] reports it and the trial
+    // is repeated on the multi-kernel path (lm_trial).  (The cooperative launch itself was removed in round 5.)
+    hipLaunchKernelGGL(ba_pcg_persist, dim3(ba->pers_grid), dim3(kPersTPB), pers_lds_bytes(), ctx->stream, d, pa);
+    *refused = hipGetLastError() != hipSuccess;
+    if (*refused) { (void)hipGetLastError(); ba->pers_grid = 0; ba->pers_grid_built = 0; ba->w_valid = false; }
+  }
+  if (trial_dbg) {
+    hipStreamSynchronize(ctx->stream);
+    int fl[4] = {0, 0, 0, 0};
+    hipMemcpy(fl, d.pcg_flag, sizeof(fl), hipMemcpyDeviceToHost);
+    fprintf(stderr, "[ccm_ba] trial: lin %d lambda %.4g persist %.1f us, %d CG iterations, coarse %s, W %s\n", ba->lin_id, lambda, (now_ms() - tdbg0) * 1e3, fl[1],
+            !ba->coarse_used ? "off" : ba->coarse_fresh ? "built" : "reused", pa.w_load ? "loaded" : "factored");
+  }
+  return CCM_OK;
+}
+
+// The multi-kernel PCG: three launches per CG iteration, queued in chunks between which the host reads the flags.  flags: pcg_flag as last read;
+// returns the solve's iteration count in *iters.
+int solve_multi_kernel(ccm_ba* ba, double lambda, double tol, int max_it, int (&flags)[4], int* iters) {
+  ccm_ctx* ctx = ba->ctx;
+  BaDev& d = ba->d;
+  RC(coarse_decide(ba, lambda));
+  d.mk_on = ba->coarse_used ? 1 : 0;
+  CCM_HIP_CHECK(ctx, hipMemsetAsync(d.pcg_flag, 0, 4 * sizeof(int), ctx->stream));
+  if (d.S32) {   // the f32 copy of this trial's S for the product kernel (114 -> 57 MB on the 10 000-keyframe map, once per trial)
+    const size_t n4 = 9 * (size_t)(d.Cp + d.nOff);
+    hipLaunchKernelGGL(ba_s_to_f32, dim3((unsigned)ccm_div_up((int64_t)n4, kTPB)), dim3(kTPB), 0, ctx->stream, (const double*)d.S, d.S32, n4);
+  }
+  {
+    const size_t lds_tiles = (size_t)(2 * kCluN * kCluN + kCluN + kPersWaves) * sizeof(double) + 16;
+    CCM_LDS_ATTR(ctx, CCM_LDS_BA_TILES, ba_pcg_init_tiles, lds_tiles);
+    if (!ba->d_pers_coff) return ccm_set_error(ctx, CCM_E_STATE, "ccm_ba: cluster entry lists missing");
+    hipLaunchKernelGGL(ba_pcg_init_tiles, dim3(d.n_wg_upd), dim3(kPersTPB), lds_tiles, ctx->stream, d, lambda, tol, (const int*)ba->d_pers_coff,
+                       (const int*)ba->d_pers_cij, (const uint32_t*)ba->d_pers_cblk);
+    if (d.mk_on) hipLaunchKernelGGL(ba_pcg_coarse_apply, dim3(d.mk_na), dim3(kTPB), 6 * (size_t)(d.mk_na + 1) * sizeof(double), ctx->stream, d, 0);
+  }
+  // The host learns that the solve has converged from the flags it reads back between chunks of queued iterations; every iteration queued beyond the converged
+  // one is three launches that return at once (~3 us each + their gaps).  Round 5: the first chunk is sized by the PREVIOUS solve of the handle (consecutive
+  // trials of a call need similar counts: 60 - 75 on the 10 000-keyframe map), the following ones are short — ~3 instead of ~12 idle iterations per solve
+  // (1680 -> ~1510 launches of each kernel for the 1440 iterations of that call).  The counts are deterministic, so every rank of a sharded run queues alike.
+  const int sym_grid = 512;   // two 16-wave workgroups per CU
+  const dim3 g_spmv(std::min(d.n_wg_spmv, sym_grid));
+  const size_t lds_ca = 6 * (size_t)(d.mk_na + 1) * sizeof(double);
+  const bool f32 = d.S32 != nullptr;
+  // the true residual r = b - (S + lambda I) x in place of the recurrence's (f64 blocks), followed by z = M^-1 r and its dot products: what iteration kk's update leaves
+  auto replace_residual = [&](int kk) {
+    { ccm_prof_scope ps(ctx, CCM_K_BA_PCG_SPMV); hipLaunchKernelGGL((ba_pcg_spmv<false, true>), g_spmv, dim3(kSpmvTPB), 0, ctx->stream, d, kk); }
+    ccm_prof_scope ps(ctx, CCM_K_BA_PCG_UPDATE);
+    hipLaunchKernelGGL(ba_pcg_update<true>, dim3(d.n_wg_upd), dim3(kTPB), 0, ctx->stream, d, kk);
+    if (d.mk_on) hipLaunchKernelGGL(ba_pcg_coarse_apply, dim3(d.mk_na), dim3(kTPB), lds_ca, ctx->stream, d, (kk + 1) & 1);
+  };
+  int k = 0, verified_at = -1;
+  // (second half of round 5) the first chunk reaches two iterations BEYOND the previous solve's count — an iteration queued in vain is three launches that return at
+  // once (~8 us), a chunk that stops short is a read-back with the device idle (~40 us) plus most of the next chunk in vain —, and the question that follows a
+  // verification (below) is ONE iteration, not a chunk: 13.5 -> ~7 iterations queued in vain per solve on the 10 000-keyframe map.
+  bool first_chunk = true, after_verify = false;
+  while (k < max_it) {
+    const int chunk = first_chunk ? (ba->mk_prev_iters > 0 ? std::max(8, ba->mk_prev_iters + 2) : 24) : after_verify ? 1 : 6;
+    first_chunk = false; after_verify = false;
+    const int kend = std::min(max_it, k + chunk);
+    for (; k < kend; k++) {
+      {
+        ccm_prof_scope ps(ctx, CCM_K_BA_PCG_SPMV);
+        if (f32) hipLaunchKernelGGL((ba_pcg_spmv<true, false>), g_spmv, dim3(kSpmvTPB), 0, ctx->stream, d, k);
+        else hipLaunchKernelGGL((ba_pcg_spmv<false, false>), g_spmv, dim3(kSpmvTPB), 0, ctx->stream, d, k);
+      }
+      if (f32 && (k + 1) % kMkReplaceEvery == 0) {
+        { ccm_prof_scope ps(ctx, CCM_K_BA_PCG_UPDATE); hipLaunchKernelGGL(ba_pcg_xupdate, dim3(d.n_wg_upd), dim3(kTPB), 0, ctx->stream, d, k); }
+        replace_residual(k);
+      } else {
+        ccm_prof_scope ps(ctx, CCM_K_BA_PCG_UPDATE);
+        hipLaunchKernelGGL(ba_pcg_update<false>, dim3(d.n_wg_upd), dim3(kTPB), 0, ctx->stream, d, k);
+        if (d.mk_on) hipLaunchKernelGGL(ba_pcg_coarse_apply, dim3(d.mk_na), dim3(kTPB), lds_ca, ctx->stream, d, (k + 1) & 1);
+      }
+    }
+    CCM_HIP_CHECK(ctx, hipMemcpyAsync(flags, d.pcg_flag, sizeof(flags), hipMemcpyDeviceToHost, ctx->stream));
+    CCM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    if (flags[0]) {
+      // f32 product: the recurrence says "converged at iteration N" (the launches queued behind that test returned at once, so x = x_N).  Unless r_N is a replaced
+      // residual already, form the true one and put the question again: the test at the top of iteration N then speaks about b - (S + lambda I) x_N itself.
+      const int N = flags[1];
+      if (f32 && !flags[2] && N > 0 && N % kMkReplaceEvery != 0 && verified_at != N) {
+        verified_at = N;
+        CCM_HIP_CHECK(ctx, hipMemsetAsync(d.pcg_flag, 0, 2 * sizeof(int), ctx->stream));
+        replace_residual(N - 1);
+        k = N;
+        after_verify = true;
+        flags[0] = 0;
+        continue;
+      }
+      break;
+    }
+  }
+  *iters = flags[0] ? flags[1] : k;
+  ba->mk_prev_iters = *iters;
   return CCM_OK;
 }
 
@@ -3754,8 +3776,7 @@ int ccm_internal::ba_debug_coarse(ccm_ba* ba, double lambda, int* na, double* Ac
   if (cap < nc * nc) return ccm_set_error(ctx, CCM_E_ARG, "ccm_ba_debug_coarse: buffer too small");
   CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   RC(build_system(ba));
-  if (d.Lloc) hipLaunchKernelGGL(ba_dinv, dim3(d.n_wg_pt), dim3(kTPB), 0, ctx->stream, d, lambda);
-  RC(launch_schur(ba));
+  RC(reduced_system(ba, lambda));
   // the inverse destroys d_cA: assemble twice
   RC(coarse_build(ba, lambda));
   std::vector<double> buf(Nc * Nc);
@@ -3774,14 +3795,12 @@ int ccm_internal::ba_debug_coarse(ccm_ba* ba, double lambda, int* na, double* Ac
 int ccm_internal::ba_debug_partial_reduced(ccm_ba* ba, double lambda, double* out, size_t cap, size_t* count) {
   if (!ba || !count) return CCM_E_ARG;
   ccm_ctx* ctx = ba->ctx;
-  BaDev& d = ba->d;
   *count = ba->red_count;
   if (!out) return CCM_OK;
   if (cap < ba->red_count) return ccm_set_error(ctx, CCM_E_ARG, "ccm_ba_debug_partial_reduced: buffer too small");
   CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   RC(build_system(ba));
-  if (d.Lloc) hipLaunchKernelGGL(ba_dinv, dim3(d.n_wg_pt), dim3(kTPB), 0, ctx->stream, d, lambda);
-  RC(launch_schur(ba));
+  RC(reduced_system(ba, lambda));
   CCM_HIP_CHECK(ctx, hipMemcpyAsync(out, ba->d_red, ba->red_count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   CCM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return CCM_OK;
@@ -3799,8 +3818,7 @@ int ccm_internal::ba_debug_pcg_solve(ccm_ba* ba, double lambda, int coarse, doub
   if (cap < 6 * (size_t)d.Cp) return ccm_set_error(ctx, CCM_E_ARG, "ccm_ba_debug_pcg_solve: buffer too small");
   CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   RC(build_system(ba));
-  if (d.Lloc) hipLaunchKernelGGL(ba_dinv, dim3(d.n_wg_pt), dim3(kTPB), 0, ctx->stream, d, lambda);
-  RC(launch_schur(ba));
+  RC(reduced_system(ba, lambda));
   PersArgs pa = pers_args(ba, lambda, rel_tol, max_it);
   if (coarse) {
     RC(coarse_build(ba, lambda));
@@ -3869,10 +3887,7 @@ extern "C" int ccm_ba_run(ccm_ba* ba, const ccm_ba_options* opt_in, const volati
   CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   ccm_ba_options opt{};
   if (opt_in) opt = *opt_in;
-  ba->coarse_active = false;   // every run starts from the same preconditioner state
-  ba->mk_prev_iters = 0;
-  ba->coarse_valid = false; ba->coarse_stale_bad = false; ba->coarse_fresh_iters = 0;
-  ba->w_valid = false; ba->w_stale_bad = false; ba->w_fresh_iters = 0; ba->w_lambda_built = 0; ba->lin_id = 0; ba->w_lin_id = -1;
+  reuse_reset(ba);
   ba->stop_flag = stop_flag; ba->stop_any = false;
   ba->hist_chi2.clear(); ba->hist_lambda.clear(); ba->hist_trials.clear();
   if (ba->nranks > 1 && !ba->pers_agreed) {

@@ -479,8 +479,6 @@ __global__ void bb_points_out(int Lp, const int* slot_pt, const double* pt_slots
 
 inline int grid_for(int64_t n) { return std::max(1, ccm_div_up(n, kB)); }
 
-static inline int row_min_blocks() { return 256; }
-
 }  // namespace
 
 // landmarks in the caller's numbering, on the device: raw input overwritten by the optimised own / gathered landmarks (ccm_ba_download)
@@ -613,7 +611,7 @@ extern "C" int ccm_ba_create(ccm_ctx* ctx, const ccm_ba_problem* P, int rank, in
       BB_HIP(hipStreamSynchronize(st));
       ccm_ba_partition(weight.data(), Lp, nranks, shard.data());
     }
-    const int lb = ba->lp_begin = shard[rank], le = ba->lp_end = shard[rank + 1];
+    const int lb = ba->lp_begin = shard[rank], le = shard[rank + 1];
     const int Lloc = ba->Lloc = le - lb;
     const int eb = h_pt_off[lb], ee = h_pt_off[le];
     const int Eloc = ba->Eloc = ee - eb;
@@ -808,7 +806,7 @@ extern "C" int ccm_ba_create(ccm_ctx* ctx, const ccm_ba_problem* P, int rank, in
     // ---- row Schur kernel: the unit table, when every row's partial sums fit the LDS beside its Y ----
     d.unit_tab = nullptr; d.row_unit_off = nullptr; d.blk_unit0 = nullptr; d.row_units_max = 0; d.row_dbg = nullptr;
     if (ccm_dbg("row")) { long long* p_dbg = nullptr; BB_RC(keep_get(ba, 8, &p_dbg, true)); d.row_dbg = p_dbg; }
-    if (nOff > row_min_blocks() && d.max_cam_edges <= kRowMaxEdges && (uint64_t)std::max(Eloc, 1) * 144u < (1ull << 31)) {
+    if (nOff > kRowMinBlocks && d.max_cam_edges <= kRowMaxEdges && (uint64_t)std::max(Eloc, 1) * 144u < (1ull << 31)) {
       // LDS of a row: Y of its observations + a zero row, the diagonal partials (27 per 16 observations), 36 doubles per unit
       const size_t lds_free = 158 * 1024 - ((size_t)(d.max_cam_edges + 1) * 18 + 27 * (size_t)ccm_div_up(d.max_cam_edges, kRow2Group)) * sizeof(double);
       const int units_cap = (int)(lds_free / (36 * sizeof(double)));
@@ -828,7 +826,7 @@ extern "C" int ccm_ba_create(ccm_ctx* ctx, const ccm_ba_problem* P, int rank, in
     // the Hpl blocks (144 bytes per observation) exist only where a kernel reads them: with the row kernel on compact records and the edge-parallel
     // landmark kernels every consumer re-derives them (32 bytes per observation in landmark-major order for the back-substitution)
     d.E4L = nullptr;
-    d.w_free = (d.E4 && d.chunk_off && d.unit_tab && nOff > row_min_blocks()) ? 1 : 0;
+    d.w_free = (d.E4 && d.chunk_off && d.unit_tab && nOff > kRowMinBlocks) ? 1 : 0;
     if (d.w_free) { double* p_l = nullptr; BB_RC(keep_get(ba, 4 * (size_t)Eloc, &p_l)); d.E4L = p_l; }
     AL(W, d.w_free ? 1 : 18 * (size_t)Eloc, double) AL(Hll, 6 * (size_t)Lloc, double) AL(bl, 3 * (size_t)Lloc, double)
     AL(Dinv, 6 * (size_t)Lloc, double) AL(dl, 3 * (size_t)Lloc, double) AL(Hpp, 36 * (size_t)Cp, double) AL(bp, 6 * (size_t)Cp, double)

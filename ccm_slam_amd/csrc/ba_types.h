@@ -7,6 +7,8 @@ constexpr int kWave = 64;
 constexpr int kTPB = 256;
 constexpr uint32_t kTransposeBit = 0x80000000u;
 constexpr int kRowMaxEdges = 1000;   // 144 B of LDS per observation of the camera
+constexpr int kRowMinBlocks = 256;   // reduced systems with at most this many off-diagonal blocks use the one-workgroup-per-block Schur kernel; above, the row kernel (which also forms
+                                     // the diagonal blocks and b_schur)
 constexpr int kRow2TPB = 1024;       // lane-per-instance row kernel: 16 waves, i.e. 128 VGPRs per lane (36-42 accumulators + the W_c row; the Y row is read three values at a time)
 constexpr int kRow2Group = 16;       // lanes that share one work unit (block chunk); 4 units per wave pass
 constexpr int kRow2Chunk = 64;       // pair instances per work unit: <= 4 per lane (measured on the 4-agent map with ba_schur_row3: 16: 164 us, 32: 143, 48: 139, 64: 137, 96: 139;
@@ -128,7 +130,7 @@ struct ccm_ba {
   int n_cam = 0, n_pt = 0, n_edge = 0;
   int Cp = 0, Lp = 0, Lloc = 0, Eloc = 0, nOff = 0;
   int64_t n_inst = 0, n_act_edges = 0, n_row_entries = 0;
-  int lp_begin = 0, lp_end = 0;
+  int lp_begin = 0;
   std::vector<int> slot_cam;            // [Cp] pose slot -> camera index (host copy for ccm_ba_download)
   std::vector<int> loc_edge_orig;       // local edge -> the caller's edge index (host copy, fetched on first use)
   double *d_raw_cam = nullptr, *d_raw_pt = nullptr;   // the caller's cameras [n_cam][7] / landmarks [n_pt][3] as uploaded (create / reset); d_raw_pt also stages the download
@@ -148,22 +150,30 @@ struct ccm_ba {
   uint32_t* d_pers_cblk = nullptr;
   unsigned long long pers_launch = 0;
   // (round 5) pers_grid_built: the grid the handle was created for (0: it has no persistent solver); pers_grid goes to 0 for pers_cooldown trials after a launch
-  // gave up waiting for its peers and then returns to it; pers_aborts counts those launches
-  int pers_grid_built = 0, pers_cooldown = 0, pers_aborts = 0;
-  bool w_pending = false;     // the running / last persistent launch factored the cluster blocks: its wsave becomes valid once its flags have been read clean
+  // gave up waiting for its peers and then returns to it
+  int pers_grid_built = 0, pers_cooldown = 0;
   bool pers_agreed = false;   // sharded handle: the ranks have agreed on whether the persistent kernel is used (first ccm_ba_run)
   // coarse level (two-level preconditioner of the persistent PCG); na = 0 -> disabled
   int coarse_na = 0, coarse_Nc = 0, coarse_ncb = 0;
   // The coarse level costs a dense inverse per trial (~0.5 ms) and ~25% per CG iteration; it pays only when the
   // cluster-Jacobi solve is long (small lambda).  Switch with hysteresis on the iteration count of the previous solve
-  // (deterministic: the counts are): on after a solve of >= kCoarseOnIters iterations, off after one of <= kCoarseOffIters.
-  bool coarse_active = false, coarse_used = false;
+  // (deterministic: the counts are): on after a solve of >= kCoarseOnIters iterations, off after one of <= kCoarseOffIters (ba.hip: coarse_note);
+  // a solve at or above the call's first lambda leaves the level out and the switch as it is (coarse_decide).
+  bool coarse_active = false, coarse_used = false, coarse_skipped_damped = false;
+  double lambda_first = 0;   // the call's first lambda
   // The coarse operator Ac = P^T (S + lambda I) P is only a preconditioner: a STALE one (built at an earlier trial's lambda or an
   // earlier linearisation point) still gives a fixed SPD M^-1 for the whole solve, so PCG converges to the same tolerance, just a few
-  // iterations later.  It is rebuilt when lambda has left [1/4, 4] x the lambda it was built at, or when a solve with the stale
-  // operator needed clearly more iterations than the solve right after the last build (counts are deterministic => so is the policy).
-  // cluster inverse of the persistent solver carried from trial to trial (ba.hip, lm_trial): what it was built at, and the iteration guard
+  // iterations later.  It is rebuilt (coarse_decide) when lambda has fallen below 1/16 of the lambda it was built at or risen above 64 times it
+  // (16 times on the multi-kernel path), or when a solve with the stale operator needed more than 4/3 of the iterations of the solve right
+  // after the last build, + 8 (coarse_note; counts are deterministic => so is the policy).
+  bool coarse_valid = false, coarse_fresh = false, coarse_stale_bad = false;   // an operator is at hand; this trial built it; a solve with it did badly
+  double coarse_lambda_built = 0; int coarse_fresh_iters = 0;
+  // The cluster inverse W of the persistent solver, carried from a trial to the next trials ON THE SAME LINEARISATION (rejected trials: only lambda moved)
+  // while lambda stays within 8.5 times the lambda it was factored at (ba.hip: w_decide / w_note).
   double* d_pers_wsave = nullptr;   // [pers_grid][96 * 48]
+  bool w_valid = false;       // wsave holds an inverse that may be loaded
+  bool w_pending = false;     // the running / last persistent launch factored the cluster blocks: its wsave becomes valid once its flags have been read clean
+  double w_lambda_built = 0; int lin_id = 0, w_lin_id = -1;   // what wsave was factored at: lambda and linearisation (lin_id counts the call's linearisations)
   double* d_pers_u = nullptr;       // [6 Cp][2] u of the persistent solver's halo exchange as {bits, bits ^ key}
   // w of every unknown (for the partner unit) and the units' parts of the coarse restriction, tagged like u, by epoch parity, in ONE block (one buffer
   // descriptor in the kernel): [2][6 Cp][2] | [2][8][kPersNcCap][2]
@@ -171,12 +181,8 @@ struct ccm_ba {
   bool pers_prefetch = true;        // CCM_BA_PERS_PREFETCH (read at create): the partner's w and the coarse parts are fetched inside the exchange (0: after it)
   bool pers_camupd = true;          // CCM_BA_PERS_CAMUPD (read at create): the persistent launch applies the step to the cameras itself (0: a ba_update_cams launch after it)
   float* d_cAinv32 = nullptr;       // [Nc][Nc] Ac^-1 rounded to f32 by coarse_build: the multi-kernel path's coarse apply and the 12 rows a persistent unit keeps in LDS
-  bool w_valid = false, w_loaded = false, w_stale_bad = false; double w_lambda_built = 0; int w_fresh_iters = 0, lin_id = 0, w_lin_id = -1;
-  bool coarse_valid = false, coarse_fresh = false, coarse_stale_bad = false, coarse_reuse = true;
-  double coarse_lambda_built = 0; int coarse_fresh_iters = 0;
   int mk_prev_iters = 0;   // CG iterations of the handle's previous multi-kernel solve (sizes the first chunk of queued iterations of the next one)
   double dinv_done_lambda = -1.0;   // lambda for which the landmark-side linearisation already formed D^-1 (ba_dinv folded in), -1 = none
-  double lambda_first = 0; bool coarse_skipped_damped = false;   // the call's first lambda; the coarse level is left out at and above it (lm_trial)
   double* h_rb = nullptr;    // pinned: [6 scalars | 4 flags] of a trial, then the ticket ba_reduce_scalars writes after them (read_scalars_polled)
   unsigned long long rb_ticket = 0;
   int coarse_force = 0;      // CCM_BA_COARSE=always / never (tests), 0 = adaptive

@@ -17,7 +17,7 @@ from tests.test_ba_structure_gpu import dev_array
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not ref.HAVE_EXTENDED, reason="numpy.longdouble has no 64-bit mantissa on this platform")]
 LD = ref.LD
-ROW_MIN_BLOCKS, ROW_MAX_EDGES, TPB = 256, 1000, 256     # row_min_blocks(), kRowMaxEdges, kTPB of the device code
+ROW_MIN_BLOCKS, ROW_MAX_EDGES, TPB = 256, 1000, 256     # kRowMinBlocks, kRowMaxEdges, kTPB of the device code
 
 
 def device_system(ctx, h, lam):
