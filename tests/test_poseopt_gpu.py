@@ -9,7 +9,15 @@ from ccm_slam_amd import optimizer, synth
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("n,seed,of", [(300, 0, 0.1), (1000, 1, 0.2), (40, 2, 0.05), (9, 3, 0.0), (2000, 4, 0.3)])
+# Launch shapes of ccm_pose_optimize (poseopt.hip, host part): staged = 8 doubles + 3 flag bytes per edge + 16 = 67 n + 16 bytes; below 600 edges the 27 sums go
+# through the LDS transpose block, from 600 on through the cross-lane reduction, whose LDS head is 2 * 4 waves * 64 doubles = 4096 bytes: lds_full = 4112 + 67 n.
+# 4112 + 67 * 2231 = 153 589 <= 150 KiB = 153 600 < 153 656 = 4112 + 67 * 2232: LDS staging and the zero-copy call end at n = 2231, from 2232 on the problem stays in
+# global memory and travels by copy commands.  599 / 600: the switch of the reduction; 2231 / 2232 / 2600: the last staged size and the global-memory path.
+assert 4112 + 67 * 2231 <= 150 * 1024 < 4112 + 67 * 2232
+
+
+@pytest.mark.parametrize("n,seed,of", [(300, 0, 0.1), (1000, 1, 0.2), (40, 2, 0.05), (9, 3, 0.0), (2000, 4, 0.3),
+                                       (599, 5, 0.1), (600, 6, 0.1), (2231, 7, 0.2), (2232, 8, 0.2), (2600, 9, 0.3)])
 def test_pose_optimization_matches_oracle(ctx, oracle_lib, n, seed, of):
     p = synth.make_pose_problem(n, seed, of)
     cam, outl, ninl = optimizer.pose_optimization(ctx, p["cam_qt"], p["Xw"], p["obs"], p["info"], p["K"])
