@@ -40,7 +40,7 @@ struct ccm_ctx {
   void* loop_group = nullptr;   // test-only in-process communicator (ccm_comm_init_loopback): ranks = threads sharing one GPU
   // reusable staging buffers
   void* d_scratch = nullptr; size_t d_scratch_bytes = 0;
-  void* d_io = nullptr; size_t d_io_bytes = 0;   // staging for the host-pointer entry points
+  void* d_io = nullptr; size_t d_io_bytes = 0;   // staging of ccm_frame_window_search and ccm_distinctive_descriptors, the two host-pointer entry points not on a staged block
   void* h_pin = nullptr; size_t h_pin_bytes = 0; // pinned host staging (one H2D / D2H per small call)
   // size-bucketed cache of device blocks released by BA handles: a local BA builds a fresh problem for every keyframe, and
   // ~45 hipMalloc + hipFree per problem cost more than the host-side structure build itself

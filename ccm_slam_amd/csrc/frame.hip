@@ -6,6 +6,7 @@
 // sequential claim rules on it; it no longer builds the grid or walks cells itself.
 #include "common.h"
 #include "frame_math.h"
+#include "stage_blocks.h"
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -329,6 +330,7 @@ extern "C" int ccm_frame_window_search(ccm_frame* f, int Q, const float* u, cons
   *n_cand = 0;
   cand_off[0] = 0;
   if (Q == 0) return CCM_OK;
+  // Not on a staged block: measured on one (profiles/tracking_staged_ab.json) the call was 1.4 us slower than this form's worst session, so this form stays.
   CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   // device staging, mirrored byte for byte in one pinned block so that the inputs travel in ONE H2D copy and the results in
   // ONE D2H copy:  in = [u | v | r | minl | maxl] (5Q words) | qdesc (32Q);  cnt (Q);  out = off (Q+1) | idx (cap) | dist (cap u16)
@@ -393,29 +395,17 @@ extern "C" int ccm_frame_frustum(ccm_ctx* ctx, const ccm_frustum_frame* fr, int 
     return ccm_set_error(ctx, CCM_E_ARG, "ccm_frame_frustum: bad args");
   if (n == 0) return CCM_OK;
   static_assert(sizeof(ccm_frustum_frame) == sizeof(FrustumFrame), "ccm_frustum_frame must mirror FrustumFrame");
-  CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   FrustumFrame f;
   memcpy(&f, fr, sizeof(f));
-  const size_t wn = (size_t)n;
-  // device: P 3n | normal 3n | dmin n | dmax n (8n floats in) ; u n | v n | cos n | level n | in_view n bytes (out)
-  void* scratch = nullptr;
-  if (int rc = ccm_io_scratch(ctx, 4 * 8 * wn + 4 * 4 * wn + wn + 256, &scratch)) return rc;
-  void* pin = nullptr;
-  if (int rc = ccm_pin_scratch(ctx, 4 * 8 * wn + 4 * 4 * wn + wn + 64, &pin)) return rc;
-  float* d_in = (float*)scratch;
-  float* d_out = d_in + 8 * wn;
-  uint8_t* d_flag = (uint8_t*)(d_out + 4 * wn);
-  float* h = (float*)pin;
-  memcpy(h, P, 12 * wn); memcpy(h + 3 * wn, normal, 12 * wn); memcpy(h + 6 * wn, min_dist, 4 * wn); memcpy(h + 7 * wn, max_dist, 4 * wn);
-  CCM_HIP_CHECK(ctx, hipMemcpyAsync(d_in, h, 32 * wn, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(frame_frustum_kernel, dim3(ccm_div_up(n, 256)), dim3(256), 0, ctx->stream, f, n, d_in, d_in + 3 * wn, d_in + 6 * wn, d_in + 7 * wn,
-                     viewing_cos_limit, d_flag, d_out, d_out + wn, (int*)(d_out + 3 * wn), d_out + 2 * wn);
+  FrustumBlock b(n);
+  if (int rc = ccm_staged_begin(ctx, b, "ccm_frame_frustum: ")) return rc;
+  b.put(b.P, P); b.put(b.normal, normal); b.put(b.dmin, min_dist); b.put(b.dmax, max_dist);
+  if (int rc = ccm_staged_upload(ctx, b)) return rc;
+  hipLaunchKernelGGL(frame_frustum_kernel, dim3(ccm_div_up(n, 256)), dim3(256), 0, ctx->stream, f, n, b.dev(b.P), b.dev(b.normal), b.dev(b.dmin), b.dev(b.dmax),
+                     viewing_cos_limit, b.dev(b.in_view), b.dev(b.u), b.dev(b.v), b.dev(b.level), b.dev(b.cos));
   CCM_HIP_CHECK(ctx, hipGetLastError());
-  float* h_out = h + 8 * wn;
-  CCM_HIP_CHECK(ctx, hipMemcpyAsync(h_out, d_out, 16 * wn + wn, hipMemcpyDeviceToHost, ctx->stream));
-  CCM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  memcpy(proj_x, h_out, 4 * wn); memcpy(proj_y, h_out + wn, 4 * wn); memcpy(view_cos, h_out + 2 * wn, 4 * wn);
-  memcpy(level, h_out + 3 * wn, 4 * wn); memcpy(in_view, h_out + 4 * wn, wn);
+  if (int rc = ccm_staged_download(ctx, b)) return rc;
+  b.get(b.u, proj_x); b.get(b.v, proj_y); b.get(b.cos, view_cos); b.get(b.level, level); b.get(b.in_view, in_view);
   return CCM_OK;
 }
 
@@ -433,31 +423,17 @@ extern "C" int ccm_update_normal_and_depth(ccm_ctx* ctx, int n_pt, const float* 
       return ccm_set_error(ctx, CCM_E_ARG, "ccm_update_normal_and_depth: reference keyframe / level out of range");
   }
   for (int o = 0; o < n_obs; o++) if (obs_kf[o] < 0 || obs_kf[o] >= n_kf) return ccm_set_error(ctx, CCM_E_ARG, "ccm_update_normal_and_depth: keyframe index out of range");
-  CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const size_t np = (size_t)n_pt, no = (size_t)n_obs, nk = (size_t)n_kf;
-  // one staging block in, one out: [pos 3np | kf_center 3nk | scale n_levels | obs_off np+1 | obs_kf no | ref_kf np | ref_level np] -> [normal 3np | dmin np | dmax np]
-  const size_t in_words = 3 * np + 3 * nk + (size_t)n_levels + (np + 1) + no + 2 * np, out_words = 5 * np;
-  void* scratch = nullptr; void* pin = nullptr;
-  if (int rc = ccm_io_scratch(ctx, 4 * (in_words + out_words) + 256, &scratch)) return rc;
-  if (int rc = ccm_pin_scratch(ctx, 4 * (in_words + out_words) + 64, &pin)) return rc;
-  float* h = (float*)pin; float* dv = (float*)scratch;
-  size_t w = 0;
-  const size_t o_pos = w; memcpy(h + w, pos, 12 * np); w += 3 * np;
-  const size_t o_kc = w; memcpy(h + w, kf_center, 12 * nk); w += 3 * nk;
-  const size_t o_sf = w; memcpy(h + w, scale_factors, 4 * (size_t)n_levels); w += (size_t)n_levels;
-  const size_t o_off = w; memcpy(h + w, obs_off, 4 * (np + 1)); w += np + 1;
-  const size_t o_okf = w; if (no) memcpy(h + w, obs_kf, 4 * no); w += no;
-  const size_t o_rk = w; memcpy(h + w, ref_kf, 4 * np); w += np;
-  const size_t o_rl = w; memcpy(h + w, ref_level, 4 * np); w += np;
-  float* d_out = dv + in_words; float* h_out = h + in_words;
-  // points without observers keep the caller's values: seed the output block with them
-  memcpy(h_out, normal, 12 * np); memcpy(h_out + 3 * np, min_dist, 4 * np); memcpy(h_out + 4 * np, max_dist, 4 * np);
-  CCM_HIP_CHECK(ctx, hipMemcpyAsync(dv, h, 4 * (in_words + out_words), hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(frame_normal_depth_kernel, dim3(ccm_div_up(n_pt, 256)), dim3(256), 0, ctx->stream, n_pt, dv + o_pos, (const int*)(dv + o_off), (const int*)(dv + o_okf),
-                     dv + o_kc, (const int*)(dv + o_rk), (const int*)(dv + o_rl), dv + o_sf, n_levels, d_out, d_out + 3 * np, d_out + 4 * np);
+  NormalDepthBlock b(n_pt, n_kf, n_levels, n_obs);
+  if (int rc = ccm_staged_begin(ctx, b, "ccm_update_normal_and_depth: ")) return rc;
+  b.put(b.pos, pos); b.put(b.kf_center, kf_center); b.put(b.scale_factors, scale_factors);
+  b.put(b.obs_off, obs_off); b.put(b.obs_kf, obs_kf); b.put(b.ref_kf, ref_kf); b.put(b.ref_level, ref_level);
+  // points without observers keep the caller's values: the outputs go up seeded with them
+  b.put(b.normal, normal); b.put(b.dmin, min_dist); b.put(b.dmax, max_dist);
+  if (int rc = ccm_staged_upload(ctx, b)) return rc;
+  hipLaunchKernelGGL(frame_normal_depth_kernel, dim3(ccm_div_up(n_pt, 256)), dim3(256), 0, ctx->stream, n_pt, b.dev(b.pos), b.dev(b.obs_off), b.dev(b.obs_kf),
+                     b.dev(b.kf_center), b.dev(b.ref_kf), b.dev(b.ref_level), b.dev(b.scale_factors), n_levels, b.dev(b.normal), b.dev(b.dmin), b.dev(b.dmax));
   CCM_HIP_CHECK(ctx, hipGetLastError());
-  CCM_HIP_CHECK(ctx, hipMemcpyAsync(h_out, d_out, 4 * out_words, hipMemcpyDeviceToHost, ctx->stream));
-  CCM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  memcpy(normal, h_out, 12 * np); memcpy(min_dist, h_out + 3 * np, 4 * np); memcpy(max_dist, h_out + 4 * np, 4 * np);
+  if (int rc = ccm_staged_download(ctx, b)) return rc;
+  b.get(b.normal, normal); b.get(b.dmin, min_dist); b.get(b.dmax, max_dist);
   return CCM_OK;
 }

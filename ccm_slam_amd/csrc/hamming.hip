@@ -16,6 +16,7 @@
 //    (2 x global_load_dwordx4).  Per-slot distances are written for the host-side ordered
 //    resolution pass; best/second come from two wave min-reductions over (dist,slot) keys.
 #include "common.h"
+#include "stage_blocks.h"
 
 namespace {
 
@@ -305,25 +306,20 @@ __global__ __launch_bounds__(256) void bow_descend_kernel(const uint32_t* __rest
 
 }  // namespace
 
-extern "C" int ccm_hamming_dense_best2_dev(ccm_ctx* ctx, const uint8_t* d_q, int Q, const uint8_t* d_t, int T,
-                                           int32_t* d_best_idx, int32_t* d_best_dist, int32_t* d_second_dist) {
-  if (!ctx || Q < 0 || T < 0) return ccm_set_error(ctx, CCM_E_ARG, "hamming_dense: bad args");
-  if (Q == 0) return CCM_OK;
-  CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+// the T split of the dense search: enough splits that the grid has >= ~2048 waves when the problem allows it
+static int dense_splits(int Q, int T, int* t_per_split) {
+  *t_per_split = 0;
+  if (T <= 0) return 1;
+  const int n_split = std::max(1, std::min(ccm_div_up(T, 64), ccm_div_up(2048, ccm_div_up(Q, 64))));
+  *t_per_split = ccm_div_up(T, n_split);
+  return ccm_div_up(T, *t_per_split);
+}
+
+// the two launches; d_part holds 3 * n_split * Q ints
+static int dense_launch(ccm_ctx* ctx, const uint8_t* d_q, int Q, const uint8_t* d_t, int T, int n_split, int t_per_split, int32_t* d_part,
+                        int32_t* d_best_idx, int32_t* d_best_dist, int32_t* d_second_dist) {
   const int qblocks = ccm_div_up(Q, 256);
-  // choose the T split so that the grid has >= ~2048 waves when the problem allows it
-  int n_split = 1;
-  if (T > 0) {
-    const int waves_q = ccm_div_up(Q, 64);
-    n_split = std::max(1, std::min(ccm_div_up(T, 64), ccm_div_up(2048, waves_q)));
-  }
-  const int t_per_split = T > 0 ? ccm_div_up(T, n_split) : 0;
-  if (T > 0) n_split = ccm_div_up(T, t_per_split);
-  void* scratch = nullptr;
-  const size_t part = (size_t)n_split * Q * sizeof(int32_t);
-  int rc = ccm_scratch(ctx, 3 * part, &scratch);
-  if (rc) return rc;
-  int32_t* p_idx = (int32_t*)scratch;
+  int32_t* p_idx = d_part;
   int32_t* p_best = p_idx + (size_t)n_split * Q;
   int32_t* p_second = p_best + (size_t)n_split * Q;
   {
@@ -337,27 +333,34 @@ extern "C" int ccm_hamming_dense_best2_dev(ccm_ctx* ctx, const uint8_t* d_q, int
   return CCM_OK;
 }
 
+extern "C" int ccm_hamming_dense_best2_dev(ccm_ctx* ctx, const uint8_t* d_q, int Q, const uint8_t* d_t, int T,
+                                           int32_t* d_best_idx, int32_t* d_best_dist, int32_t* d_second_dist) {
+  if (!ctx || Q < 0 || T < 0) return ccm_set_error(ctx, CCM_E_ARG, "hamming_dense: bad args");
+  if (Q == 0) return CCM_OK;
+  CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  int t_per_split = 0;
+  const int n_split = dense_splits(Q, T, &t_per_split);
+  void* scratch = nullptr;
+  if (int rc = ccm_scratch(ctx, 3 * (size_t)n_split * Q * sizeof(int32_t), &scratch)) return rc;
+  return dense_launch(ctx, d_q, Q, d_t, T, n_split, t_per_split, (int32_t*)scratch, d_best_idx, d_best_dist, d_second_dist);
+}
+
+// The host form's partials are a segment of its block: the block lives in the context's scratch, which must not be asked for again while the block is bound.
 extern "C" int ccm_hamming_dense_best2(ccm_ctx* ctx, const uint8_t* q, int Q, const uint8_t* t, int T,
                                        int32_t* best_idx, int32_t* best_dist, int32_t* second_dist) {
   if (!ctx || Q < 0 || T < 0 || (Q && (!q || !best_idx || !best_dist || !second_dist)) || (T && !t))
     return ccm_set_error(ctx, CCM_E_ARG, "hamming_dense: bad args");
   if (Q == 0) return CCM_OK;
-  CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const size_t bq = ccm_align256((size_t)Q * 32), bt = ccm_align256((size_t)std::max(T, 1) * 32);
-  void* io = nullptr;
-  { int rc0 = ccm_io_scratch(ctx, bq + bt + (size_t)Q * 3 * sizeof(int32_t), &io); if (rc0) return rc0; }
-  uint8_t* d_q = (uint8_t*)io; uint8_t* d_t = d_q + bq; int32_t* d_out = (int32_t*)(d_t + bt);
-  CCM_HIP_CHECK(ctx, hipMemcpyAsync(d_q, q, (size_t)Q * 32, hipMemcpyHostToDevice, ctx->stream));
-  if (T) CCM_HIP_CHECK(ctx, hipMemcpyAsync(d_t, t, (size_t)T * 32, hipMemcpyHostToDevice, ctx->stream));
-  int rc = ccm_hamming_dense_best2_dev(ctx, d_q, Q, d_t, T, d_out, d_out + Q, d_out + 2 * (size_t)Q);
-  if (rc == CCM_OK) {
-    hipMemcpyAsync(best_idx, d_out, (size_t)Q * 4, hipMemcpyDeviceToHost, ctx->stream);
-    hipMemcpyAsync(best_dist, d_out + Q, (size_t)Q * 4, hipMemcpyDeviceToHost, ctx->stream);
-    hipMemcpyAsync(second_dist, d_out + 2 * (size_t)Q, (size_t)Q * 4, hipMemcpyDeviceToHost, ctx->stream);
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) rc = ccm_set_error(ctx, CCM_E_HIP, std::string("hamming_dense: ") + hipGetErrorString(e));
-  }
-  return rc;
+  int t_per_split = 0;
+  const int n_split = dense_splits(Q, T, &t_per_split);
+  HammingDenseBlock b(Q, T, n_split);
+  if (int rc = ccm_staged_begin(ctx, b, "hamming_dense: ")) return rc;
+  b.put(b.q, q); b.put(b.t, t);
+  if (int rc = ccm_staged_upload(ctx, b)) return rc;
+  if (int rc = dense_launch(ctx, b.dev(b.q), Q, b.dev(b.t), T, n_split, t_per_split, b.dev(b.part), b.dev(b.best_idx), b.dev(b.best_dist), b.dev(b.second_dist))) return rc;
+  if (int rc = ccm_staged_download(ctx, b)) return rc;
+  b.get(b.best_idx, best_idx); b.get(b.best_dist, best_dist); b.get(b.second_dist, second_dist);
+  return CCM_OK;
 }
 
 // one launch of the windowed search: a wave per query for long lists (the round-1 kernel), G lanes per query below
@@ -402,6 +405,26 @@ extern "C" int ccm_hamming_csr_multi_dev(ccm_ctx* ctx, const uint8_t* d_q, int Q
   return csr_launch(ctx, d_q, Q, d_t, d_q_tbase, d_cand_off, d_cand_idx, n_cand, d_cand_dist, d_best_idx, d_best_dist, d_second_dist);
 }
 
+// The host side of both windowed searches, behind their validations: one block up, one launch, one block down.  S > 0 is ccm_hamming_csr_multi, whose queries
+// get the first target row of their search; S == 0 is the single search, which keeps q_tbase == nullptr and with it the wave-per-query kernel for long lists.
+static int csr_host(ccm_ctx* ctx, const char* me, int S, const uint8_t* q, const int32_t* q_off, int Q, const uint8_t* t, const int32_t* t_off, int T,
+                    const int32_t* cand_off, const int32_t* cand_idx, int64_t n_cand, uint16_t* cand_dist,
+                    int32_t* best_idx, int32_t* best_dist, int32_t* second_dist) {
+  HammingCsrBlock b(Q, t ? T : 0 /* without candidates t may be NULL */, n_cand, S > 0, cand_dist && n_cand, best_idx != nullptr);
+  if (int rc = ccm_staged_begin(ctx, b, me)) return rc;
+  b.put(b.q, q); b.put(b.t, t); b.put(b.cand_off, cand_off); b.put(b.cand_idx, cand_idx);
+  for (int s = 0; s < S; s++) std::fill(b.up(b.q_tbase) + q_off[s], b.up(b.q_tbase) + q_off[s + 1], t_off[s]);
+  if (int rc = ccm_staged_upload(ctx, b)) return rc;
+  if (int rc = csr_launch(ctx, b.dev(b.q), Q, b.dev(b.t), S > 0 ? b.dev(b.q_tbase) : nullptr, b.dev(b.cand_off), b.dev(b.cand_idx), n_cand,
+                          b.want_dist ? b.dev(b.cand_dist) : nullptr, b.want_best ? b.dev(b.best_idx) : nullptr, b.want_best ? b.dev(b.best_dist) : nullptr,
+                          b.want_best ? b.dev(b.second_dist) : nullptr)) return rc;
+  if (int rc = ccm_staged_download(ctx, b)) return rc;
+  b.get(b.cand_dist, cand_dist); b.get(b.best_idx, best_idx);
+  if (best_dist) b.get(b.best_dist, best_dist);
+  if (second_dist) b.get(b.second_dist, second_dist);
+  return CCM_OK;
+}
+
 // S searches, one launch, one read-back.  Search s owns the query rows q_off[s] .. q_off[s+1] and the target rows t_off[s] .. t_off[s+1]; the candidate
 // indices of its queries are LOCAL to its target set.
 extern "C" int ccm_hamming_csr_multi(ccm_ctx* ctx, int S, const uint8_t* q, const int32_t* q_off, const uint8_t* t, const int32_t* t_off,
@@ -414,45 +437,17 @@ extern "C" int ccm_hamming_csr_multi(ccm_ctx* ctx, int S, const uint8_t* q, cons
   if (Q == 0) return CCM_OK;
   const int64_t n_cand = cand_off[Q];
   if (cand_off[0] != 0 || n_cand < 0 || (n_cand && (!cand_idx || !t))) return ccm_set_error(ctx, CCM_E_ARG, "hamming_csr_multi: bad candidate list (cand_off must start at 0)");
-  void* pin = nullptr;
-  { int rc0 = ccm_pin_scratch(ctx, (size_t)Q * 4 + 256, &pin); if (rc0) return rc0; }
-  int32_t* h_base = (int32_t*)pin;
   for (int s = 0; s < S; s++) {
     if (q_off[s + 1] < q_off[s] || t_off[s + 1] < t_off[s]) return ccm_set_error(ctx, CCM_E_ARG, "hamming_csr_multi: offsets must ascend");
     const int Ts = t_off[s + 1] - t_off[s];
     for (int i = q_off[s]; i < q_off[s + 1]; i++) {
-      h_base[i] = t_off[s];
       const int64_t len = (int64_t)cand_off[i + 1] - cand_off[i];
       if (len < 0 || len >= (1 << 20)) return ccm_set_error(ctx, CCM_E_ARG, "hamming_csr_multi: candidate list length out of range");
       for (int c = cand_off[i]; c < cand_off[i + 1]; c++)
         if (cand_idx[c] < 0 || cand_idx[c] >= Ts) return ccm_set_error(ctx, CCM_E_ARG, "hamming_csr_multi: candidate index out of range");
     }
   }
-  CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const size_t bq = ccm_align256((size_t)Q * 32), bt = ccm_align256((size_t)std::max(T, 1) * 32), bo = ccm_align256((size_t)(Q + 1) * 4), bb = ccm_align256((size_t)Q * 4);
-  const size_t bi = ccm_align256((size_t)std::max<int64_t>(n_cand, 1) * 4), bd = ccm_align256((size_t)std::max<int64_t>(n_cand, 1) * 2);
-  void* io = nullptr;
-  { int rc0 = ccm_io_scratch(ctx, bq + bt + bo + bb + bi + bd + (size_t)Q * 12, &io); if (rc0) return rc0; }
-  uint8_t* d_q = (uint8_t*)io; uint8_t* d_t = d_q + bq; int32_t* d_off = (int32_t*)(d_t + bt); int32_t* d_base = (int32_t*)((uint8_t*)d_off + bo);
-  int32_t* d_idx = (int32_t*)((uint8_t*)d_base + bb); uint16_t* d_dist = (uint16_t*)((uint8_t*)d_idx + bi); int32_t* d_out = (int32_t*)((uint8_t*)d_dist + bd);
-  CCM_HIP_CHECK(ctx, hipMemcpyAsync(d_q, q, (size_t)Q * 32, hipMemcpyHostToDevice, ctx->stream));
-  if (T) CCM_HIP_CHECK(ctx, hipMemcpyAsync(d_t, t, (size_t)T * 32, hipMemcpyHostToDevice, ctx->stream));
-  CCM_HIP_CHECK(ctx, hipMemcpyAsync(d_off, cand_off, (size_t)(Q + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-  CCM_HIP_CHECK(ctx, hipMemcpyAsync(d_base, h_base, (size_t)Q * 4, hipMemcpyHostToDevice, ctx->stream));
-  if (n_cand) CCM_HIP_CHECK(ctx, hipMemcpyAsync(d_idx, cand_idx, (size_t)n_cand * 4, hipMemcpyHostToDevice, ctx->stream));
-  int rc = ccm_hamming_csr_multi_dev(ctx, d_q, Q, d_t, d_base, d_off, d_idx, n_cand, d_dist, best_idx ? d_out : nullptr,
-                                     best_idx ? d_out + Q : nullptr, best_idx ? d_out + 2 * (size_t)Q : nullptr);
-  if (rc == CCM_OK) {
-    if (cand_dist && n_cand) hipMemcpyAsync(cand_dist, d_dist, (size_t)n_cand * 2, hipMemcpyDeviceToHost, ctx->stream);
-    if (best_idx) {
-      hipMemcpyAsync(best_idx, d_out, (size_t)Q * 4, hipMemcpyDeviceToHost, ctx->stream);
-      hipMemcpyAsync(best_dist, d_out + Q, (size_t)Q * 4, hipMemcpyDeviceToHost, ctx->stream);
-      hipMemcpyAsync(second_dist, d_out + 2 * (size_t)Q, (size_t)Q * 4, hipMemcpyDeviceToHost, ctx->stream);
-    }
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) rc = ccm_set_error(ctx, CCM_E_HIP, std::string("hamming_csr_multi: ") + hipGetErrorString(e));
-  }
-  return rc;
+  return csr_host(ctx, "hamming_csr_multi: ", S, q, q_off, Q, t, t_off, T, cand_off, cand_idx, n_cand, cand_dist, best_idx, best_dist, second_dist);
 }
 
 extern "C" int ccm_hamming_csr(ccm_ctx* ctx, const uint8_t* q, int Q, const uint8_t* t, int T,
@@ -469,30 +464,7 @@ extern "C" int ccm_hamming_csr(ccm_ctx* ctx, const uint8_t* q, int Q, const uint
   }
   for (int64_t s = 0; s < n_cand; ++s)
     if (cand_idx[s] < 0 || cand_idx[s] >= T) return ccm_set_error(ctx, CCM_E_ARG, "hamming_csr: candidate index out of range");
-  CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const size_t bq = ccm_align256((size_t)Q * 32), bt = ccm_align256((size_t)std::max(T, 1) * 32), bo = ccm_align256((size_t)(Q + 1) * 4);
-  const size_t bi = ccm_align256((size_t)std::max<int64_t>(n_cand, 1) * 4), bd = ccm_align256((size_t)std::max<int64_t>(n_cand, 1) * 2);
-  void* io = nullptr;
-  { int rc0 = ccm_io_scratch(ctx, bq + bt + bo + bi + bd + (size_t)Q * 12, &io); if (rc0) return rc0; }
-  uint8_t* d_q = (uint8_t*)io; uint8_t* d_t = d_q + bq; int32_t* d_off = (int32_t*)(d_t + bt); int32_t* d_idx = (int32_t*)((uint8_t*)d_off + bo);
-  uint16_t* d_dist = (uint16_t*)((uint8_t*)d_idx + bi); int32_t* d_out = (int32_t*)((uint8_t*)d_dist + bd);
-  hipMemcpyAsync(d_q, q, (size_t)Q * 32, hipMemcpyHostToDevice, ctx->stream);
-  if (T) hipMemcpyAsync(d_t, t, (size_t)T * 32, hipMemcpyHostToDevice, ctx->stream);
-  hipMemcpyAsync(d_off, cand_off, (size_t)(Q + 1) * 4, hipMemcpyHostToDevice, ctx->stream);
-  if (n_cand) hipMemcpyAsync(d_idx, cand_idx, (size_t)n_cand * 4, hipMemcpyHostToDevice, ctx->stream);
-  int rc = ccm_hamming_csr_dev(ctx, d_q, Q, d_t, T, d_off, d_idx, n_cand, d_dist, best_idx ? d_out : nullptr,
-                               best_idx ? d_out + Q : nullptr, best_idx ? d_out + 2 * (size_t)Q : nullptr);
-  if (rc == CCM_OK) {
-    if (cand_dist && n_cand) hipMemcpyAsync(cand_dist, d_dist, (size_t)n_cand * 2, hipMemcpyDeviceToHost, ctx->stream);
-    if (best_idx) {
-      hipMemcpyAsync(best_idx, d_out, (size_t)Q * 4, hipMemcpyDeviceToHost, ctx->stream);
-      hipMemcpyAsync(best_dist, d_out + Q, (size_t)Q * 4, hipMemcpyDeviceToHost, ctx->stream);
-      hipMemcpyAsync(second_dist, d_out + 2 * (size_t)Q, (size_t)Q * 4, hipMemcpyDeviceToHost, ctx->stream);
-    }
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) rc = ccm_set_error(ctx, CCM_E_HIP, std::string("hamming_csr: ") + hipGetErrorString(e));
-  }
-  return rc;
+  return csr_host(ctx, "hamming_csr: ", 0, q, nullptr, Q, t, nullptr, T, cand_off, cand_idx, n_cand, cand_dist, best_idx, best_dist, second_dist);
 }
 
 extern "C" int ccm_distinctive_descriptors(ccm_ctx* ctx, const uint8_t* desc, const int32_t* off, int P, int32_t* best_local_idx) {
@@ -504,6 +476,7 @@ extern "C" int ccm_distinctive_descriptors(ccm_ctx* ctx, const uint8_t* desc, co
     const int n = off[p + 1] - off[p];
     if (n < 0 || n > kDistinctMaxN) return ccm_set_error(ctx, CCM_E_ARG, "distinctive: a map point has more than 256 observations (or a negative count)");
   }
+  // Not on a staged block: measured on one (profiles/tracking_staged_ab.json) the call was slower than this form's worst session, so this form stays.
   CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const size_t bd = ccm_align256((size_t)std::max<int64_t>(total, 1) * 32), bo = ccm_align256((size_t)(P + 1) * 4);
   void* io = nullptr;
@@ -566,20 +539,17 @@ extern "C" int ccm_bow_transform(ccm_vocab* v, const uint8_t* desc, int N, int l
   if (!v || N < 0 || (N && (!desc || !word_out || !weight_out || !node_out))) return ccm_set_error(v ? v->ctx : nullptr, CCM_E_ARG, "ccm_bow_transform: bad args");
   if (N == 0) return CCM_OK;
   ccm_ctx* ctx = v->ctx;
-  CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const size_t bd = ccm_align256((size_t)N * 32);
-  void* io = nullptr;
-  { int rc0 = ccm_io_scratch(ctx, bd + (size_t)N * 8, &io); if (rc0) return rc0; }
-  uint8_t* d_desc = (uint8_t*)io; int32_t* d_leaf = (int32_t*)(d_desc + bd); int32_t* d_nid = d_leaf + N;
-  CCM_HIP_CHECK(ctx, hipMemcpyAsync(d_desc, desc, (size_t)N * 32, hipMemcpyHostToDevice, ctx->stream));
+  BowTransformBlock b(N);
+  if (int rc = ccm_staged_begin(ctx, b, "ccm_bow_transform: ")) return rc;
+  b.put(b.desc, desc);
+  if (int rc = ccm_staged_upload(ctx, b)) return rc;
   const int nid_level = v->L - levelsup;   // if <= 0 the node stays 0 (root), TemplatedVocabulary.h:1227
-  hipLaunchKernelGGL(bow_descend_kernel, dim3(ccm_div_up(N, 4)), dim3(256), 0, ctx->stream, (const uint32_t*)d_desc, N, v->d_child_off, v->d_child_id,
-                     v->d_node_desc, nid_level, d_leaf, d_nid);
+  hipLaunchKernelGGL(bow_descend_kernel, dim3(ccm_div_up(N, 4)), dim3(256), 0, ctx->stream, (const uint32_t*)b.dev(b.desc), N, v->d_child_off, v->d_child_id,
+                     v->d_node_desc, nid_level, b.dev(b.leaf), b.dev(b.nid));
   CCM_HIP_CHECK(ctx, hipGetLastError());
-  std::vector<int32_t> leaf(N);
-  CCM_HIP_CHECK(ctx, hipMemcpyAsync(leaf.data(), d_leaf, (size_t)N * 4, hipMemcpyDeviceToHost, ctx->stream));
-  CCM_HIP_CHECK(ctx, hipMemcpyAsync(node_out, d_nid, (size_t)N * 4, hipMemcpyDeviceToHost, ctx->stream));
-  CCM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  if (int rc = ccm_staged_download(ctx, b)) return rc;
+  b.get(b.nid, node_out);
+  const int32_t* leaf = b.down(b.leaf);
   for (int i = 0; i < N; i++) { word_out[i] = v->word_id[leaf[i]]; weight_out[i] = v->weight[leaf[i]]; }
   return CCM_OK;
 }

@@ -202,3 +202,54 @@ struct Sim3ProjectResidentBlock : FuseBlock {
 struct Sim3PairResidentBlock : FuseBlock {
   Sim3PairResidentBlock(size_t K, size_t P, size_t L, size_t J, size_t T, size_t N, bool want_uv) : FuseBlock({FB_JOBS | FB_PAIR, K, 0, P, L, J, T, N, 0, want_uv}) {}
 };
+
+// The tracked frame's and LocalMapping's own entry points (hamming.hip, frame.hip).  Every descriptor segment stands on 16 bytes: the kernels read descriptors as uint4.
+// ccm_frame_window_search and ccm_distinctive_descriptors are not here: measured on a block they were slower than their hand-packed forms.
+
+// ccm_hamming_dense_best2: the two descriptor sets lead, the per-split partial results (3 n_split Q ints) stay on the device, the three outputs follow.
+struct HammingDenseBlock : StagedBlock {
+  const size_t Q, T, n_split;
+  HammingDenseBlock(size_t Q, size_t T, size_t n_split) : Q(Q), T(T), n_split(n_split) {}
+  StagedSeg<uint8_t> q = add<uint8_t>(32 * Q, SB_COPY, 16), t = add<uint8_t>(32 * T, SB_COPY, 16);
+  StagedSeg<int32_t> part = add<int32_t>(3 * n_split * Q, SB_WORK);
+  StagedSeg<int32_t> best_idx = add<int32_t>(Q, SB_OUT), best_dist = add<int32_t>(Q, SB_OUT), second_dist = add<int32_t>(Q, SB_OUT);
+};
+
+// ccm_hamming_csr and ccm_hamming_csr_multi: the descriptors lead, the lists follow; q_tbase (the first target row of each query's search, written by the stage) has
+// no elements in the single-search call.  The 16-bit distances lead the outputs, so an odd n_cand leaves half a word of pad in front of the best / second triple.
+// An output the caller does not ask for is declared with no elements, and the kernel then receives nullptr for it.
+struct HammingCsrBlock : StagedBlock {
+  const size_t Q, T, n_cand; const bool multi, want_dist, want_best;
+  HammingCsrBlock(size_t Q, size_t T, size_t n_cand, bool multi, bool want_dist, bool want_best) : Q(Q), T(T), n_cand(n_cand), multi(multi), want_dist(want_dist), want_best(want_best) {}
+  StagedSeg<uint8_t> q = add<uint8_t>(32 * Q, SB_COPY, 16), t = add<uint8_t>(32 * T, SB_COPY, 16);
+  StagedSeg<int32_t> cand_off = add<int32_t>(Q + 1, SB_COPY), q_tbase = add<int32_t>(multi ? Q : 0, SB_GEN), cand_idx = add<int32_t>(n_cand, SB_COPY);
+  StagedSeg<uint16_t> cand_dist = add<uint16_t>(want_dist ? n_cand : 0, SB_OUT);
+  StagedSeg<int32_t> best_idx = add<int32_t>(want_best ? Q : 0, SB_OUT), best_dist = add<int32_t>(want_best ? Q : 0, SB_OUT), second_dist = add<int32_t>(want_best ? Q : 0, SB_OUT);
+};
+
+// ccm_bow_transform: N descriptors up; the leaf and the node at the asked level come back.  The tree is the vocabulary handle's own.
+struct BowTransformBlock : StagedBlock {
+  const size_t N;
+  explicit BowTransformBlock(size_t N) : N(N) {}
+  StagedSeg<uint8_t> desc = add<uint8_t>(32 * N, SB_COPY, 16);
+  StagedSeg<int32_t> leaf = add<int32_t>(N, SB_OUT), nid = add<int32_t>(N, SB_OUT);
+};
+
+// ccm_frame_frustum: n map points; the byte flags come last, so that every float segment stays on a word.
+struct FrustumBlock : StagedBlock {
+  const size_t n;
+  explicit FrustumBlock(size_t n) : n(n) {}
+  StagedSeg<float> P = add<float>(3 * n, SB_COPY), normal = add<float>(3 * n, SB_COPY), dmin = add<float>(n, SB_COPY), dmax = add<float>(n, SB_COPY);
+  StagedSeg<float> u = add<float>(n, SB_OUT), v = add<float>(n, SB_OUT), cos = add<float>(n, SB_OUT);
+  StagedSeg<int32_t> level = add<int32_t>(n, SB_OUT);
+  StagedSeg<uint8_t> in_view = add<uint8_t>(n, SB_OUT);
+};
+
+// ccm_update_normal_and_depth: the inputs, then the outputs, which go up seeded with the caller's values: a point without observers keeps them.
+struct NormalDepthBlock : StagedBlock {
+  const size_t P, K, L, NO;
+  NormalDepthBlock(size_t P, size_t K, size_t L, size_t NO) : P(P), K(K), L(L), NO(NO) {}
+  StagedSeg<float> pos = add<float>(3 * P, SB_COPY), kf_center = add<float>(3 * K, SB_COPY), scale_factors = add<float>(L, SB_COPY);
+  StagedSeg<int32_t> obs_off = add<int32_t>(P + 1, SB_COPY), obs_kf = add<int32_t>(NO, SB_COPY), ref_kf = add<int32_t>(P, SB_COPY), ref_level = add<int32_t>(P, SB_COPY);
+  StagedSeg<float> normal = add<float>(3 * P, SB_OUT | SB_COPY), dmin = add<float>(P, SB_OUT | SB_COPY), dmax = add<float>(P, SB_OUT | SB_COPY);
+};

@@ -1,7 +1,8 @@
-// staged_block_check.cpp — csrc/staged_block.h and the five declarations of csrc/stage_blocks.h on the CPU (tests/test_staged_block_cpu.py builds this with
-// -fsanitize=address,undefined).  Every offset and total is compared with the closed formulas and the put() sequences that the five wrappers held before the
-// blocks were declared (4-byte words; copied here as they stood), every aligned segment is checked, and the host side is filled to the declared lengths in a
-// malloc'd block of exactly pin_bytes(), so that an overrun is the sanitizer's to report.
+// staged_block_check.cpp — csrc/staged_block.h and ten declarations of csrc/stage_blocks.h on the CPU (tests/test_staged_block_cpu.py builds this with
+// -fsanitize=address,undefined): the five map stages that were declared first, and the five blocks of six entry points of hamming.hip and frame.hip (the CSR
+// block serves two of them).  Every offset and total is compared with the closed formulas and the put() sequences that the wrappers held before the blocks were declared (4-byte
+// words; copied here as they stood, the five later ones by their element counts), every aligned segment is checked, the optional outputs are declared both
+// ways, and the host side is filled to the declared lengths in a malloc'd block of exactly pin_bytes(), so that an overrun is the sanitizer's to report.
 #include <stdio.h>
 #include <stdlib.h>
 #include <vector>
@@ -151,7 +152,81 @@ static void kfcull(size_t K, size_t P, size_t NL, size_t NO) {
   c.ranges(0, n_up, 0, n_out, n_up + WL);
 }
 
+// ---- the tracked frame's and LocalMapping's entry points: the element counts of their former hand-packed layouts, without the 256-byte rounding those had ----
+
+// ccm_hamming_dense_best2: q 32 Q bytes | t 32 T bytes; the partials of ccm_hamming_dense_best2_dev, 3 n_split Q ints; out 3 Q ints
+static void hamming_dense(size_t Q, size_t T, size_t n_split) {
+  const size_t n_in = 8 * Q + 8 * T, n_work = 3 * n_split * Q, n_out = 3 * Q;
+  HammingDenseBlock b(Q, T, n_split);
+  Check c(b);
+  c.up(b.q, 8 * Q, false, 16); c.up(b.t, 8 * T, false, 16);
+  EXPECT_EQ(c.o, n_in);
+  c.seg(b.part, n_work);
+  c.down(b.best_idx, Q); c.down(b.best_dist, Q); c.down(b.second_dist, Q);
+  c.ranges(0, n_in, n_in + n_work, n_out, n_in + n_work + n_out);
+}
+
+// ccm_hamming_csr(_multi): q | t | cand_off (Q + 1) | q_tbase (Q, _multi only) | cand_idx (n_cand); out cand_dist (n_cand u16) | 3 Q ints.  An output that is
+// not asked for takes no room and moves nothing.
+static void hamming_csr(size_t Q, size_t T, size_t n_cand, bool multi, bool want_dist, bool want_best) {
+  const size_t n_in = 8 * Q + 8 * T + (Q + 1) + (multi ? Q : 0) + n_cand;
+  const size_t w_dist = want_dist ? (n_cand + 1) / 2 : 0, w_best = want_best ? Q : 0;
+  HammingCsrBlock b(Q, T, n_cand, multi, want_dist, want_best);
+  Check c(b);
+  c.up(b.q, 8 * Q, false, 16); c.up(b.t, 8 * T, false, 16); c.up(b.cand_off, Q + 1); c.up(b.q_tbase, multi ? Q : 0); c.up(b.cand_idx, n_cand);
+  EXPECT_EQ(c.o, n_in);
+  EXPECT_EQ(b.q_tbase.count, multi ? Q : 0); EXPECT_EQ(b.cand_dist.count, want_dist ? n_cand : 0); EXPECT_EQ(b.best_idx.count, w_best);
+  c.down(b.cand_dist, w_dist); c.down(b.best_idx, w_best); c.down(b.best_dist, w_best); c.down(b.second_dist, w_best);
+  c.ranges(0, n_in, n_in, w_dist + 3 * w_best, n_in + w_dist + 3 * w_best);
+}
+
+// ccm_bow_transform: desc 32 N bytes; out leaf (N) | nid (N)
+static void bow_transform(size_t N) {
+  BowTransformBlock b(N);
+  Check c(b);
+  c.up(b.desc, 8 * N, false, 16);
+  c.down(b.leaf, N); c.down(b.nid, N);
+  c.ranges(0, 8 * N, 8 * N, 2 * N, 10 * N);
+}
+
+// ccm_frame_frustum: P 3n | normal 3n | dmin n | dmax n (8n floats in);  u n | v n | cos n | level n | in_view n bytes (out)
+static void frustum(size_t n) {
+  FrustumBlock b(n);
+  Check c(b);
+  c.up(b.P, 3 * n); c.up(b.normal, 3 * n); c.up(b.dmin, n); c.up(b.dmax, n);
+  EXPECT_EQ(c.o, 8 * n);
+  c.down(b.u, n); c.down(b.v, n); c.down(b.cos, n); c.down(b.level, n); c.down(b.in_view, (n + 3) / 4);
+  c.ranges(0, 8 * n, 8 * n, 4 * n + (n + 3) / 4, 12 * n + (n + 3) / 4);
+}
+
+// ccm_update_normal_and_depth: [pos 3np | kf_center 3nk | scale n_levels | obs_off np+1 | obs_kf no | ref_kf np | ref_level np] -> [normal 3np | dmin np | dmax np];
+// the outputs travel both ways
+static void normal_depth(size_t np, size_t nk, size_t n_levels, size_t no) {
+  const size_t in_words = 3 * np + 3 * nk + n_levels + (np + 1) + no + 2 * np, out_words = 5 * np;
+  NormalDepthBlock b(np, nk, n_levels, no);
+  Check c(b);
+  c.up(b.pos, 3 * np); c.up(b.kf_center, 3 * nk); c.up(b.scale_factors, n_levels); c.up(b.obs_off, np + 1); c.up(b.obs_kf, no); c.up(b.ref_kf, np); c.up(b.ref_level, np);
+  EXPECT_EQ(c.o, in_words);
+  c.up(b.normal, 3 * np); c.up(b.dmin, np); c.up(b.dmax, np);
+  EXPECT_EQ(c.o, in_words + out_words);
+  c.o = in_words;
+  c.down(b.normal, 3 * np); c.down(b.dmin, np); c.down(b.dmax, np);
+  c.ranges(0, in_words + out_words, in_words, out_words, in_words + out_words);
+}
+
 int main() {
+  for (size_t Q : {1, 3, 65})
+    for (size_t T : {0, 1, 130})
+      for (size_t n_split : {1, 3}) hamming_dense(Q, T, n_split);
+  for (size_t Q : {1, 2, 7})
+    for (size_t T : {0, 1, 9})
+      for (size_t n_cand : {0, 1, 2, 5})       // an odd n_cand: the 16-bit distances end on half a word in front of the int32 outputs
+        for (int form = 0; form < 8; form++) hamming_csr(Q, T, T ? n_cand : 0, form & 1, form & 2, form & 4);
+  for (size_t N : {1, 5}) bow_transform(N);
+  for (size_t n : {1, 4, 7, 130}) frustum(n);
+  for (size_t np : {1, 3})
+    for (size_t nk : {0, 2})
+      for (size_t no : {0, 1, 6}) normal_depth(np, nk, 8, nk ? no : 0);
   for (size_t H : {0, 1, 5})
     for (size_t K : {1, 3}) sim3_ransac(K, 3 * K + 14 * (K - 1), H, H * 2 + (H > 1));
   for (size_t P : {0, 1, 3, 4, 5, 130})
