@@ -1,5 +1,5 @@
-// kfstore.h — the keyframe feature store's handle, shared by kfstore.hip (which fills it) and fuse.hip and bowsearch.hip (whose resident evaluators read it).
-// DESIGN.md §21, §23.
+// kfstore.h — the keyframe feature store's handle, shared by kfstore.hip (which fills it) and fuse.hip, bowsearch.hip and trisearch.hip (whose resident evaluators read it).
+// DESIGN.md §21, §23, §24.
 #pragma once
 #include "common.h"
 #include "kfstore_math.h"

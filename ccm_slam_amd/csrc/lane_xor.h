@@ -85,4 +85,18 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
+// The minimum of a 32-bit key over the wave in every lane, by the same butterfly 32, 16, 8, 4, 2, 1 (bowsearch.hip, trisearch.hip): the row swaps put own and partner's
+// value side by side, DPP moves do the steps inside a row of 16 lanes.  Every lane of the wave must be active.
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xf, 0xf, false); }
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
+  { const auto p = __builtin_amdgcn_permlane32_swap(v, v, false, false); v = min((uint32_t)p[0], (uint32_t)p[1]); }
+  { const auto p = __builtin_amdgcn_permlane16_swap(v, v, false, false); v = min((uint32_t)p[0], (uint32_t)p[1]); }
+  v = min(v, dpp_u32<0x128>(v));                  // row_ror:8
+  v = min(v, dpp_u32<0x1B>(dpp_u32<0x141>(v)));   // row_half_mirror, then quad_perm:[3,2,1,0]: lane ^ 4
+  v = min(v, dpp_u32<0x4E>(v));                   // quad_perm:[2,3,0,1]
+  v = min(v, dpp_u32<0xB1>(v));                   // quad_perm:[1,0,3,2]
+  return v;
+}
+
 }  // namespace lanex

@@ -6,6 +6,7 @@
 #include "fuse_math.h"
 #include "kfstore_math.h"
 #include "bow_search_math.h"
+#include "tri_search_math.h"
 
 // ccm_sim3_ransac_eval: the inputs, then the outputs.
 struct Sim3RansacBlock : StagedBlock {
@@ -145,6 +146,20 @@ struct BowPairResidentBlock : StagedBlock {
   StagedSeg<uint8_t> live1 = add<uint8_t>(M1, SB_COPY), live2 = add<uint8_t>(M2, SB_COPY);
   StagedSeg<uint64_t> table = add<uint64_t>(M1, SB_OUT | SB_ZERO);
   StagedSeg<int32_t> n_query = add<int32_t>(J, SB_OUT | SB_ZERO), n_dist = add<int32_t>(J, SB_OUT | SB_ZERO);
+};
+
+// ccm_tri_search_eval_resident: J jobs of TSM_JOB_INTS ints each (BowPairResidentBlock's job record, its last int the job's first float), the
+// doubles 3.84 * (double)level_sigma2[l] the stage writes (they lead the rest, on 8 bytes), TSM_EPI_FLOATS floats per job (F12, ex, ey), the scale factors of the L
+// levels, and the two sides' map-point bytes, M1 and M2 in all.  The table has one 32-bit word per byte of side 1; it and the three counters go up as zeros.
+struct TriSearchResidentBlock : StagedBlock {
+  const size_t J, M1, M2, L;
+  TriSearchResidentBlock(size_t J, size_t M1, size_t M2, size_t L) : J(J), M1(M1), M2(M2), L(L) {}
+  StagedSeg<int32_t> job = add<int32_t>(TSM_JOB_INTS * J, SB_GEN, 16);
+  StagedSeg<double> line_thr = add<double>(L, SB_GEN);
+  StagedSeg<float> job_epi = add<float>(TSM_EPI_FLOATS * J, SB_COPY), scale_factors = add<float>(L, SB_COPY);
+  StagedSeg<uint8_t> has1 = add<uint8_t>(M1, SB_COPY), has2 = add<uint8_t>(M2, SB_COPY);
+  StagedSeg<uint32_t> table = add<uint32_t>(M1, SB_OUT | SB_ZERO);
+  StagedSeg<int32_t> n_query = add<int32_t>(J, SB_OUT | SB_ZERO), n_match = add<int32_t>(J, SB_OUT | SB_ZERO), n_dist = add<int32_t>(J, SB_OUT | SB_ZERO);
 };
 
 // The six projected searches of fuse.hip are ONE layout: K keyframes, P points, L levels, and what the form's flags add.  A segment a form does

@@ -11,6 +11,7 @@
 #include "../csrc/fuse_math.h"
 #include "../csrc/kfstore_math.h"
 #include "../csrc/bow_search_math.h"
+#include "../csrc/tri_search_math.h"
 #include <climits>
 #include <algorithm>
 #include <cmath>
@@ -2518,6 +2519,133 @@ SearchByBoWBatch::SearchByBoWBatch(KeyFrameStore& store, HipContext* ctx, int64_
   }
 }
 
+// ---- CreateNewMapPoints' SearchForTriangulation for all neighbours: the host evaluator on the shadows, SearchForTriangulationBatch -------
+static TriKf tri_kf(const KfShadow& kf) { return {bow_kf(kf), kf.xy.data(), kf.oct.data()}; }
+
+int tri_search_eval_resident_host(const KeyFrameStore& store, int J, const int64_t* key1, const int64_t* key2, const int32_t* has1_off, const uint8_t* has1,
+                                  const int32_t* has2_off, const uint8_t* has2, const float* job_epi, int nlevels, const float* scale_factors, const float* level_sigma2,
+                                  uint32_t* table, int32_t* n_query, int32_t* n_match, int32_t* n_dist) {
+  if (J < 0 || tsm_check_args(J, job_epi, nlevels, scale_factors, level_sigma2)) return -1;
+  if (J == 0) return 0;
+  if (!key1 || !key2 || !has1_off || !has2_off || !n_query || !n_match || !n_dist) return -1;
+  std::vector<std::shared_ptr<const KfShadow>> a, b;
+  if (!store_shadows(store, J, key1, a) || !store_shadows(store, J, key2, b)) return -1;
+  std::vector<int32_t> n1((size_t)J), n2((size_t)J);
+  std::vector<TriKf> k1((size_t)J), k2((size_t)J);
+  for (int j = 0; j < J; j++) {
+    if (!a[j]->has_fv || !b[j]->has_fv) return -1;
+    n1[j] = a[j]->n; n2[j] = b[j]->n;
+    k1[j] = tri_kf(*a[j]); k2[j] = tri_kf(*b[j]);
+  }
+  if (bsm_check_masks(J, has1_off, has1, n1.data()) || bsm_check_masks(J, has2_off, has2, n2.data())) return -1;
+  if (has1_off[J] > 0 && !table) return -1;
+  tri_search_eval_host(J, k1.data(), k2.data(), has1_off, has1, has2_off, has2, job_epi, TriLevels{nlevels, scale_factors, level_sigma2}, table, n_query, n_match, n_dist);
+  return 0;
+}
+
+SearchForTriangulationBatch::SearchForTriangulationBatch(KeyFrameStore& store, HipContext* ctx, int64_t key1, int C, const int64_t* keys2, const uint8_t* has1,
+                                                         const uint8_t* const* has2, const Epipolar* ep, const float* sigma2_2, const float* sf2, int nlevels,
+                                                         bool checkOrientation)
+    : nlevels_(nlevels), check_ori_(checkOrientation) {
+  const char* const bad = "SearchForTriangulationBatch: bad arguments";
+  if (C < 0 || (C > 0 && (!keys2 || !has2 || !ep)) || nlevels < 1 || nlevels > TSM_MAX_LEVELS || !sigma2_2 || !sf2) throw infrastructure_ex(bad);
+  std::vector<std::shared_ptr<const KfShadow>> kf1;
+  if (!store_shadows(store, 1, &key1, kf1) || !store_shadows(store, C, keys2, kfs2_)) throw infrastructure_ex("SearchForTriangulationBatch: a key is not in the store");
+  kf1_ = kf1[0];
+  if (!kf1_->has_fv) throw infrastructure_ex("SearchForTriangulationBatch: a key without a feature vector");
+  const int N1 = kf1_->n;
+  if (N1 > 0 && !has1) throw infrastructure_ex(bad);
+  sigma2_.assign(sigma2_2, sigma2_2 + nlevels); sf_.assign(sf2, sf2 + nlevels);
+  // the masks of the call: has1 once per neighbour, the neighbours' own one after the other
+  std::vector<int64_t> k1((size_t)C, key1);
+  off1_.assign((size_t)C + 1, 0); off2_.assign((size_t)C + 1, 0);
+  for (int j = 0; j < C; j++) {
+    if (!kfs2_[j]->has_fv) throw infrastructure_ex("SearchForTriangulationBatch: a key without a feature vector");
+    if (kfs2_[j]->n > 0 && !has2[j]) throw infrastructure_ex(bad);
+    off1_[j + 1] = off1_[j] + N1; off2_[j + 1] = off2_[j] + kfs2_[j]->n;
+  }
+  has1_.assign(has1, has1 + N1);
+  std::vector<uint8_t> m1((size_t)off1_[C]);
+  has2_.resize((size_t)off2_[C]);
+  epi_.resize((size_t)TSM_EPI_FLOATS * (size_t)C);
+  for (int j = 0; j < C; j++) {
+    if (N1) std::memcpy(m1.data() + off1_[j], has1, (size_t)N1);
+    if (kfs2_[j]->n) std::memcpy(has2_.data() + off2_[j], has2[j], (size_t)kfs2_[j]->n);
+    std::memcpy(epi_.data() + TSM_EPI_FLOATS * (size_t)j, ep[j].F12, 9 * sizeof(float));
+    epi_[TSM_EPI_FLOATS * (size_t)j + 9] = ep[j].ex; epi_[TSM_EPI_FLOATS * (size_t)j + 10] = ep[j].ey;
+  }
+  table_.assign((size_t)off1_[C], 0); n_query_.assign((size_t)C, 0); n_match_.assign((size_t)C, 0); n_dist_.assign((size_t)C, 0);
+  if (C > 0 && !store.host_only() && ctx) {
+    check(ccm_tri_search_eval_resident(ctx->get(), store.handle(), C, k1.data(), keys2, off1_.data(), m1.data(), off2_.data(), has2_.data(), epi_.data(), nlevels,
+                                       sf_.data(), sigma2_.data(), table_.data(), n_query_.data(), n_match_.data(), n_dist_.data()),
+          ctx->get(), "ccm_tri_search_eval_resident");
+  } else if (tri_search_eval_resident_host(store, C, k1.data(), keys2, off1_.data(), m1.data(), off2_.data(), has2_.data(), epi_.data(), nlevels, sf_.data(),
+                                           sigma2_.data(), table_.data(), n_query_.data(), n_match_.data(), n_dist_.data())) {
+    throw infrastructure_ex(bad);
+  }
+}
+
+int SearchForTriangulationBatch::resolve(int j, const uint8_t* has1_now, const uint8_t* has2_now, std::vector<int32_t>& matches12) {
+  const KfShadow& K1 = *kf1_;
+  const KfShadow& K2 = *kfs2_.at((size_t)j);
+  const TriKf t1 = tri_kf(K1), t2 = tri_kf(K2);
+  const TriLevels lv{nlevels_, sf_.data(), sigma2_.data()};
+  const uint32_t* words = table_.data() + off1_[(size_t)j];
+  const uint8_t* h2_build = has2_.data() + off2_[(size_t)j];
+  const uint8_t* h1 = has1_now ? has1_now : has1_.data();
+  const uint8_t* h2 = has2_now ? has2_now : h2_build;
+  const float* epi = epi_.data() + TSM_EPI_FLOATS * (size_t)j;
+  const int HISTO_LENGTH = ORBmatcher::HISTO_LENGTH;
+  matches12.assign((size_t)K1.n, -1);
+  std::vector<int> rotHist[ORBmatcher::HISTO_LENGTH];
+  int nmatches = 0;
+  for (size_t a = 0; a < K1.fv_node.size(); a++) {   // ascending nodes of keyframe 1; those keyframe 2 lacks hold no query
+    const int b = bsm_find_node(t2.k.node, t2.k.nn, K1.fv_node[a]);
+    if (b < 0) continue;
+    bool lost = false;   // a feature of the node's segment of keyframe 2 had a map point at the build and has none now: it is a candidate no word has seen
+    if (has2_now)
+      for (int32_t s = K2.fv_off[(size_t)b]; s < K2.fv_off[(size_t)b + 1] && !lost; s++) lost = h2_build[K2.fv_idx[(size_t)s]] && !h2[K2.fv_idx[(size_t)s]];
+    for (int32_t s1 = K1.fv_off[a]; s1 < K1.fv_off[a + 1]; s1++) {
+      const int idx1 = K1.fv_idx[(size_t)s1];
+      if (h1[idx1]) continue;   // :745-747 with the flags of this call
+      TriBest r;
+      int n_free = 0;
+      if (has1_[(size_t)idx1]) {   // had a map point at the build: it has no word
+        r = tsm_reduce_host(t1, idx1, t2, b, h2, epi, lv, &n_free);
+      } else {
+        r = TriBest{tsm_dist(words[idx1]), tsm_idx(words[idx1])};
+        if (has2_now && (lost || (r.idx >= 0 && h2[r.idx]))) {   // a candidate that gains a map point and is not the winner leaves the winner as it is
+          r = tsm_reduce_host(t1, idx1, t2, b, h2, epi, lv, &n_free);
+          n_reeval_++;
+        }
+      }
+      if (r.idx >= 0) {   // :787-804
+        matches12[(size_t)idx1] = r.idx;
+        nmatches++;
+        if (check_ori_) rotHist[histBin(K1.angle[(size_t)idx1] - K2.angle[(size_t)r.idx])].push_back(idx1);
+      }
+    }
+  }
+  if (check_ori_) {
+    int ind1 = -1, ind2 = -1, ind3 = -1;
+    threeMaxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
+    for (int i = 0; i < HISTO_LENGTH; i++) {
+      if (i == ind1 || i == ind2 || i == ind3) continue;
+      for (int k : rotHist[i]) { matches12[(size_t)k] = -1; nmatches--; }
+    }
+  }
+  return nmatches;
+}
+
+NewMapPointBatch::Pairs SearchForTriangulationBatch::predicted(int j) {
+  std::vector<int32_t> m;
+  resolve(j, nullptr, nullptr, m);
+  NewMapPointBatch::Pairs out;
+  for (size_t i = 0; i < m.size(); i++)   // :844-849
+    if (m[i] >= 0) out.emplace_back((int32_t)i, m[i]);
+  return out;
+}
+
 }  // namespace cslam
 
 // ---- C entry points (ccm_host_c.h): the Python test-suite and the drop-in translation units under shim/ ---------------------------------------
@@ -3293,6 +3421,51 @@ int ccmh_bow_batch_table(void* h, uint64_t* table, int32_t* n_query, int32_t* n_
 }
 long long ccmh_bow_batch_n_reeval(void* h) { return h ? static_cast<cslam::SearchByBoWBatch*>(h)->reevaluated() : -1; }
 void ccmh_bow_batch_destroy(void* h) { delete static_cast<cslam::SearchByBoWBatch*>(h); }
+
+// CreateNewMapPoints' SearchForTriangulation for all neighbours through C
+int ccmh_tri_search_eval_resident_host(void* store, int J, const int64_t* key1, const int64_t* key2, const int32_t* has1_off, const uint8_t* has1, const int32_t* has2_off,
+                                       const uint8_t* has2, const float* job_epi, int nlevels, const float* scale_factors, const float* level_sigma2, uint32_t* table,
+                                       int32_t* n_query, int32_t* n_match, int32_t* n_dist) {
+  if (!store) return -1;
+  return cslam::tri_search_eval_resident_host(*static_cast<cslam::KeyFrameStore*>(store), J, key1, key2, has1_off, has1, has2_off, has2, job_epi, nlevels, scale_factors,
+                                              level_sigma2, table, n_query, n_match, n_dist);
+}
+void* ccmh_tri_search_create(void* store, int device, int64_t key1, int C, const int64_t* keys2, const uint8_t* has1, const int32_t* has2_off, const uint8_t* has2,
+                             const float* epi, const float* sigma2_2, const float* sf2, int nlevels, int check_orientation) {
+  if (!store || C < 0 || (C > 0 && (!has2_off || !epi))) return nullptr;
+  try {
+    std::vector<const uint8_t*> h2((size_t)C);
+    std::vector<cslam::SearchForTriangulationBatch::Epipolar> ep((size_t)C);
+    for (int j = 0; j < C; j++) {
+      h2[j] = has2 ? has2 + has2_off[j] : nullptr;
+      std::memcpy(ep[j].F12, epi + 11 * (size_t)j, 9 * sizeof(float));
+      ep[j].ex = epi[11 * (size_t)j + 9]; ep[j].ey = epi[11 * (size_t)j + 10];
+    }
+    return new cslam::SearchForTriangulationBatch(*static_cast<cslam::KeyFrameStore*>(store), device < 0 ? nullptr : &thread_context(device), key1, C, keys2, has1,
+                                                  h2.data(), ep.data(), sigma2_2, sf2, nlevels, check_orientation != 0);
+  } catch (const std::exception&) { return nullptr; }
+}
+int ccmh_tri_search_resolve(void* h, int j, const uint8_t* has1_now, const uint8_t* has2_now, int n_feat, int32_t* matches12) {
+  if (!h) return -1000;
+  cslam::SearchForTriangulationBatch& b = *static_cast<cslam::SearchForTriangulationBatch*>(h);
+  if (j < 0 || j >= b.neighbours()) return -1000;
+  if (n_feat != b.features1()) return -1001;
+  std::vector<int32_t> m;
+  const int n = b.resolve(j, has1_now, has2_now, m);
+  if (matches12 && n_feat) std::memcpy(matches12, m.data(), (size_t)n_feat * 4);
+  return n;
+}
+int ccmh_tri_search_table(void* h, uint32_t* table, int32_t* n_query, int32_t* n_match, int32_t* n_dist) {
+  if (!h) return -1;
+  const cslam::SearchForTriangulationBatch& b = *static_cast<cslam::SearchForTriangulationBatch*>(h);
+  if (table && !b.table().empty()) std::memcpy(table, b.table().data(), b.table().size() * 4);
+  if (n_query && b.neighbours()) std::memcpy(n_query, b.nQuery().data(), (size_t)b.neighbours() * 4);
+  if (n_match && b.neighbours()) std::memcpy(n_match, b.nMatch().data(), (size_t)b.neighbours() * 4);
+  if (n_dist && b.neighbours()) std::memcpy(n_dist, b.nDist().data(), (size_t)b.neighbours() * 4);
+  return 0;
+}
+long long ccmh_tri_search_n_reeval(void* h) { return h ? static_cast<cslam::SearchForTriangulationBatch*>(h)->reevaluated() : -1; }
+void ccmh_tri_search_destroy(void* h) { delete static_cast<cslam::SearchForTriangulationBatch*>(h); }
 
 // the two projected searches of ComputeSim3 through C: host evaluators, ssm_derive, the two mirrors
 int ccmh_sim3_project_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,

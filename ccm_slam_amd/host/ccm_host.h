@@ -843,6 +843,51 @@ class SearchByBoWBatch {
   long long n_reeval_ = 0;
 };
 
+// ccm_tri_search_eval_resident's arguments after the context through csrc/tri_search_math.h on the calling thread, on the shadows of a store; -1 where the device
+// entry returns CCM_E_ARG.
+int tri_search_eval_resident_host(const KeyFrameStore& store, int J, const int64_t* key1, const int64_t* key2, const int32_t* has1_off, const uint8_t* has1,
+                                  const int32_t* has2_off, const uint8_t* has2, const float* job_epi, int nlevels, const float* scale_factors, const float* level_sigma2,
+                                  uint32_t* table, int32_t* n_query, int32_t* n_match, int32_t* n_dist);
+
+// ORBmatcher::SearchForTriangulation(mpCurrentKeyFrame, pKF2_j, F12_j, ...) (ORBmatcher.cpp:700-852) for ALL neighbours of a CreateNewMapPoints (Mapping.cpp:277-470)
+// on keys of a store that have their feature vector.  has1 (one byte per feature of key1) / has2[j] (per feature of keys2[j]):
+// GetMapPoint(idx) != nullptr.  ep[j]: F12 and the epipole of neighbour j; sigma2_2 / sf2: mvLevelSigma2 / mvScaleFactors, nlevels entries.  The constructor
+// evaluates every query of every neighbour in ONE ccm_tri_search_eval_resident call, or on the calling thread when the store is host-only or ctx == nullptr; with a
+// context a device error throws.  The reference never sets vbMatched2, so a word is the whole answer of its query under the flags of the build.
+// resolve(j, has1_now, has2_now, matches12) returns nmatches of the call against neighbour j under the flags of ITS moment (nullptr: the build's):
+//   a query with has1_now set is dropped (:745-747: what the loop creates between calls);
+//   a feature that had a map point at the build and has none now has no word and is evaluated on the calling thread;
+//   a word stands unless its bestIdx2 has gained a map point or some feature of its node's segment of keyframe 2 has lost one; the query is then evaluated again
+//   under has2_now by the same lines (a candidate that leaves without being the winner cannot change the winner).  reevaluated() counts these;
+//   then :787-839 on the surviving matches in node order, then list order: the rotation histogram on the shadows' angles.
+// F12 and the epipole are the build's: a caller whose poses changed builds a new batch.  predicted(j): resolve with the build's flags as (idx1, idx2) pairs in
+// ascending idx1 (:844-849), which is what NewMapPointBatch's Neighbour::predicted takes.
+class SearchForTriangulationBatch {
+ public:
+  using Epipolar = NewMapPointBatch::Epipolar;
+  SearchForTriangulationBatch(KeyFrameStore& store, HipContext* ctx, int64_t key1, int C, const int64_t* keys2, const uint8_t* has1, const uint8_t* const* has2,
+                              const Epipolar* ep, const float* sigma2_2, const float* sf2, int nlevels, bool checkOrientation);
+  int neighbours() const { return (int)kfs2_.size(); }
+  int features1() const { return kf1_->n; }
+  int resolve(int j, const uint8_t* has1_now, const uint8_t* has2_now, std::vector<int32_t>& matches12);
+  NewMapPointBatch::Pairs predicted(int j);
+  const std::vector<uint32_t>& table() const { return table_; }   // as evaluated at construction, neighbour after neighbour
+  const std::vector<int32_t>& nQuery() const { return n_query_; }
+  const std::vector<int32_t>& nMatch() const { return n_match_; }
+  const std::vector<int32_t>& nDist() const { return n_dist_; }
+  long long reevaluated() const { return n_reeval_; }
+ private:
+  std::shared_ptr<const KfShadow> kf1_;
+  std::vector<std::shared_ptr<const KfShadow>> kfs2_;
+  std::vector<uint8_t> has1_, has2_;
+  std::vector<int32_t> off1_, off2_;
+  std::vector<float> epi_, sigma2_, sf_;
+  std::vector<uint32_t> table_;
+  std::vector<int32_t> n_query_, n_match_, n_dist_;
+  int nlevels_; bool check_ori_;
+  long long n_reeval_ = 0;
+};
+
 // ---------------------------------------------------------------------------------------------------
 // Optimizer — cslam/include/cslam/Optimizer.h:84-112 (numerics; graph walking is the integrator's glue)
 // ---------------------------------------------------------------------------------------------------

@@ -194,6 +194,17 @@ int ccmh_bow_batch_result(void* h, int j, int n_feat, int32_t* matches12);
 int ccmh_bow_batch_table(void* h, uint64_t* table, int32_t* n_query, int32_t* n_dist);
 long long ccmh_bow_batch_n_reeval(void* h);
 void ccmh_bow_batch_destroy(void* h);
+/* CreateNewMapPoints' SearchForTriangulation for all neighbours.  ccmh_tri_search_eval_resident_host: ccm_tri_search_eval_resident's arguments
+ * after the context on the store's shadows through csrc/tri_search_math.h (0, or -1 for the CCM_E_ARG cases).  ccmh_tri_search_*: cslam::SearchForTriangulationBatch
+ * (device < 0: the host evaluation; create returns NULL on bad arguments, a key that is not live or has no feature vector, or a device error).  has2 + has2_off[j]:
+ * neighbour j's map-point bytes; epi + 11 j: its F12 (row-major), ex, ey.  resolve returns nmatches of neighbour j under has1_now / has2_now (nullable: the flags of
+ * the build) and copies matches12 (n_feat entries, nullable); -1000 for j out of range, -1001 when n_feat is not key1's feature count. */
+int ccmh_tri_search_eval_resident_host(void* store, int J, const int64_t* key1, const int64_t* key2, const int32_t* has1_off, const uint8_t* has1, const int32_t* has2_off, const uint8_t* has2, const float* job_epi, int nlevels, const float* scale_factors, const float* level_sigma2, uint32_t* table, int32_t* n_query, int32_t* n_match, int32_t* n_dist);
+void* ccmh_tri_search_create(void* store, int device, int64_t key1, int C, const int64_t* keys2, const uint8_t* has1, const int32_t* has2_off, const uint8_t* has2, const float* epi, const float* sigma2_2, const float* sf2, int nlevels, int check_orientation);
+int ccmh_tri_search_resolve(void* h, int j, const uint8_t* has1_now, const uint8_t* has2_now, int n_feat, int32_t* matches12);
+int ccmh_tri_search_table(void* h, uint32_t* table, int32_t* n_query, int32_t* n_match, int32_t* n_dist);
+long long ccmh_tri_search_n_reeval(void* h);
+void ccmh_tri_search_destroy(void* h);
 
 #ifdef __cplusplus
 }

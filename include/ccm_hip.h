@@ -727,6 +727,25 @@ int  ccm_bow_pair_eval_resident(ccm_ctx* ctx, ccm_kfstore* store, int J, const i
                                 const uint8_t* live1, const int32_t* live2_off /* J + 1 */, const uint8_t* live2, uint64_t* table /* live1_off[J] */,
                                 int32_t* n_query /* J */, int32_t* n_dist /* J */);
 
+/* ---- CreateNewMapPoints' SearchForTriangulation for all neighbours on keyframes of the store (the lines are csrc/tri_search_math.h) -----------------
+ * Job j is one ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, ...) (cslam/src/ORBmatcher.cpp:700-852) of the live keys key1[j], key2[j], both with a feature
+ * vector.  has1 + has1_off[j] / has2 + has2_off[j]: one byte per feature of the keyframe, != 0 where GetMapPoint(idx) is non-null (bad or not, :743-747, :760-764).
+ * job_epi + 11 j: F12 (9 floats, row-major), then the epipole ex, ey of keyframe 1's centre in keyframe 2 (:708-714); NaN and Inf are no error (every comparison is
+ * then false, on host and device alike).  scale_factors / level_sigma2: mvScaleFactors / mvLevelSigma2 of keyframe 2, nlevels entries, the same for every job.
+ * table + has1_off[j] holds one word per feature idx1 of keyframe 1 (tsm_pack / tsm_status / tsm_idx / tsm_dist): 0 when idx1 has a map point, is in no node, or
+ * its node does not occur in keyframe 2; otherwise status 1 (no candidate accepted; bestDist 50) or 2 with bestIdx2 and bestDist as the loop :756-785 leaves them:
+ * the smallest distance <= 50 among the candidates without a map point that pass the epipole gate and CheckDistEpipolarLine, at its LAST position in list order.
+ * The reference never sets vbMatched2, so the words are the call's whole result before the rotation histogram (cslam::SearchForTriangulationBatch, host/ccm_host.h).
+ * n_query[j]: words with status >= 1; n_match[j]: words with status 2; n_dist[j]: the sum over the queries of their node's candidates without a map point.
+ * A store feature of keyframe 2 whose octave is >= nlevels is no candidate and neither table is read for it (as in ccm_fuse_pose_eval_resident); it still counts in
+ * n_dist.  One upload, ONE launch, one download of 4 bytes per feature, under the store's reader lock.  J == 0, nn == 0, key1[j] == key2[j] and one key in several
+ * jobs are legal.  CCM_E_ARG, with nothing launched and the outputs untouched: the refusals of ccm_bow_pair_eval_resident; nlevels outside 1 .. 256; with J > 0 a
+ * null job_epi, null level tables or null outputs. */
+int  ccm_tri_search_eval_resident(ccm_ctx* ctx, ccm_kfstore* store, int J, const int64_t* key1 /* J */, const int64_t* key2 /* J */, const int32_t* has1_off /* J + 1 */,
+                                  const uint8_t* has1, const int32_t* has2_off /* J + 1 */, const uint8_t* has2, const float* job_epi /* 11 J */, int nlevels,
+                                  const float* scale_factors, const float* level_sigma2, uint32_t* table /* has1_off[J] */, int32_t* n_query /* J */,
+                                  int32_t* n_match /* J */, int32_t* n_dist /* J */);
+
 #ifdef __cplusplus
 }
 #endif
