@@ -1,5 +1,5 @@
-// kfstore.h — the keyframe feature store's handle, shared by kfstore.hip (which fills it) and fuse.hip, bowsearch.hip and trisearch.hip (whose resident evaluators read it).
-// DESIGN.md §21, §23, §24.
+// kfstore.h — the keyframe feature store's handle, shared by kfstore.hip (which fills it) and fuse.hip, bowsearch.hip, trisearch.hip and mappoint.hip (whose resident
+// evaluators read it).  DESIGN.md §21, §23, §24, §25.
 #pragma once
 #include "common.h"
 #include "kfstore_math.h"

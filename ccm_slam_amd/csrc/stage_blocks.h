@@ -7,6 +7,7 @@
 #include "kfstore_math.h"
 #include "bow_search_math.h"
 #include "tri_search_math.h"
+#include "mappoint_math.h"
 
 // ccm_sim3_ransac_eval: the inputs, then the outputs.
 struct Sim3RansacBlock : StagedBlock {
@@ -267,4 +268,24 @@ struct NormalDepthBlock : StagedBlock {
   StagedSeg<float> pos = add<float>(3 * P, SB_COPY), kf_center = add<float>(3 * K, SB_COPY), scale_factors = add<float>(L, SB_COPY);
   StagedSeg<int32_t> obs_off = add<int32_t>(P + 1, SB_COPY), obs_kf = add<int32_t>(NO, SB_COPY), ref_kf = add<int32_t>(P, SB_COPY), ref_level = add<int32_t>(P, SB_COPY);
   StagedSeg<float> normal = add<float>(3 * P, SB_OUT | SB_COPY), dmin = add<float>(P, SB_OUT | SB_COPY), dmax = add<float>(P, SB_OUT | SB_COPY);
+};
+
+// ccm_mappoint_refresh_resident: P points with M observations in all on K keys.  The stage writes, while it validates, the absolute feature row in the
+// store of every observation (slot * stride + feat) and of every point's reference feature (-1: no normal / depth part), so the kernel does no slot arithmetic and the
+// slots themselves do not travel, and the points sorted into the kernel's size classes (order).  obs_kf / ref_kf index the centres.  Without a point that asks for the
+// normal / depth part (nd false) the centres, positions and the three seeded outputs are declared with no elements.  The seeded outputs lead the download (they are
+// uploaded too); best_desc stands on 16 bytes from the download's start and has no elements when the caller does not ask for it.
+struct MapPointRefreshBlock : StagedBlock {
+  const size_t K, P, M, L; const bool nd, want_desc;
+  MapPointRefreshBlock(size_t K, size_t P, size_t M, size_t L, bool nd, bool want_desc) : K(K), P(P), M(M), L(L), nd(nd), want_desc(want_desc) {}
+  StagedSeg<float> kf_center = add<float>(nd ? 3 * K : 0, SB_COPY);
+  StagedSeg<int32_t> obs_off = add<int32_t>(P + 1, SB_COPY), obs_row = add<int32_t>(M, SB_GEN), obs_kf = add<int32_t>(nd ? M : 0, SB_COPY);
+  StagedSeg<float> pos = add<float>(nd ? 3 * P : 0, SB_COPY);
+  StagedSeg<int32_t> ref_row = add<int32_t>(P, SB_GEN), ref_kf = add<int32_t>(nd ? P : 0, SB_COPY);
+  StagedSeg<float> scale_factors = add<float>(L, SB_COPY);
+  StagedSeg<int32_t> order = add<int32_t>(P, SB_GEN);
+  StagedSeg<float> normal = add<float>(nd ? 3 * P : 0, SB_OUT | SB_COPY, 16), dmin = add<float>(nd ? P : 0, SB_OUT | SB_COPY), dmax = add<float>(nd ? P : 0, SB_OUT | SB_COPY);
+  StagedSeg<int32_t> best_obs = add<int32_t>(P, SB_OUT);
+  StagedSeg<uint8_t> status = add<uint8_t>(P, SB_OUT);
+  StagedSeg<uint8_t> best_desc = add<uint8_t>(want_desc ? 32 * P : 0, SB_OUT, 16);
 };

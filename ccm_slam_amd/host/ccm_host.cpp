@@ -12,6 +12,7 @@
 #include "../csrc/kfstore_math.h"
 #include "../csrc/bow_search_math.h"
 #include "../csrc/tri_search_math.h"
+#include "../csrc/mappoint_math.h"
 #include <climits>
 #include <algorithm>
 #include <cmath>
@@ -2637,6 +2638,43 @@ int SearchForTriangulationBatch::resolve(int j, const uint8_t* has1_now, const u
   return nmatches;
 }
 
+// ---- the refresh of map points after a map stage: the host evaluator on the shadows, MapPointRefresh -------------------------------------
+int mappoint_refresh_eval_resident_host(const KeyFrameStore& store, int K, const int64_t* keys, const float* kf_center, int P, const int32_t* obs_off, const int32_t* obs_kf,
+                                        const int32_t* obs_feat, const float* pos, const int32_t* ref_kf, const int32_t* ref_feat, int nlevels, const float* scale_factors,
+                                        int32_t* best_obs, uint8_t* best_desc, float* normal, float* min_dist, float* max_dist, uint8_t* status) {
+  bool nd = false;
+  if (mpm_check_args(K, keys, kf_center, P, obs_off, obs_kf, obs_feat, pos, ref_kf, ref_feat, nlevels, scale_factors, best_obs, normal, min_dist, max_dist, status, &nd))
+    return -1;
+  Shadows kfs;
+  if (!store_shadows(store, K, keys, kfs)) return -1;
+  std::vector<int32_t> kf_n((size_t)(K > 0 ? K : 0));
+  std::vector<MpmKf> kf(kf_n.size());
+  for (int k = 0; k < K; k++) { kf_n[k] = kfs[k]->n; kf[k] = MpmKf{kfs[k]->n, kfs[k]->desc.data(), kfs[k]->oct.data()}; }
+  if (mpm_check_features(kf_n.data(), P, obs_off, obs_kf, obs_feat, ref_kf, ref_feat)) return -1;
+  mappoint_refresh_eval_host(kf.data(), kf_center, P, obs_off, obs_kf, obs_feat, pos, ref_kf, ref_feat, nlevels, scale_factors, best_obs, best_desc, normal, min_dist,
+                             max_dist, status);
+  return 0;
+}
+
+MapPointRefresh::MapPointRefresh(KeyFrameStore& store, HipContext* ctx, int K, const int64_t* keys, const float* kf_center, const Lists& l, const Refs& r, int nlevels,
+                                 const float* scale_factors) {
+  const char* const bad = "MapPointRefresh: bad arguments or a key that is not in the store";
+  const int P = l.P;
+  if (P < 0 || (P > 0 && (!r.normal || !r.min_dist || !r.max_dist))) throw infrastructure_ex(bad);
+  const size_t n = (size_t)P;
+  best_.assign(n, -1); desc_.assign(32 * n, 0); status_.assign(n, 0);
+  if (P > 0) { normal_.assign(r.normal, r.normal + 3 * n); dmin_.assign(r.min_dist, r.min_dist + n); dmax_.assign(r.max_dist, r.max_dist + n); }
+  if (!store.host_only() && ctx) {
+    const int rc = ccm_mappoint_refresh_resident(ctx->get(), store.handle(), K, keys, kf_center, P, l.obs_off, l.obs_kf, l.obs_feat, r.pos, r.ref_kf, r.ref_feat, nlevels,
+                                                 scale_factors, best_.data(), desc_.data(), normal_.data(), dmin_.data(), dmax_.data(), status_.data());
+    if (rc == CCM_E_ARG) throw infrastructure_ex(bad);
+    check(rc, ctx->get(), "ccm_mappoint_refresh_resident");
+  } else if (mappoint_refresh_eval_resident_host(store, K, keys, kf_center, P, l.obs_off, l.obs_kf, l.obs_feat, r.pos, r.ref_kf, r.ref_feat, nlevels, scale_factors,
+                                                 best_.data(), desc_.data(), normal_.data(), dmin_.data(), dmax_.data(), status_.data())) {
+    throw infrastructure_ex(bad);
+  }
+}
+
 NewMapPointBatch::Pairs SearchForTriangulationBatch::predicted(int j) {
   std::vector<int32_t> m;
   resolve(j, nullptr, nullptr, m);
@@ -3466,6 +3504,40 @@ int ccmh_tri_search_table(void* h, uint32_t* table, int32_t* n_query, int32_t* n
 }
 long long ccmh_tri_search_n_reeval(void* h) { return h ? static_cast<cslam::SearchForTriangulationBatch*>(h)->reevaluated() : -1; }
 void ccmh_tri_search_destroy(void* h) { delete static_cast<cslam::SearchForTriangulationBatch*>(h); }
+
+// the refresh of map points through C
+int ccmh_mappoint_refresh_eval_resident_host(void* store, int K, const int64_t* keys, const float* kf_center, int P, const int32_t* obs_off, const int32_t* obs_kf,
+                                             const int32_t* obs_feat, const float* pos, const int32_t* ref_kf, const int32_t* ref_feat, int nlevels,
+                                             const float* scale_factors, int32_t* best_obs, uint8_t* best_desc, float* normal, float* min_dist, float* max_dist,
+                                             uint8_t* status) {
+  if (!store) return -1;
+  return cslam::mappoint_refresh_eval_resident_host(*static_cast<cslam::KeyFrameStore*>(store), K, keys, kf_center, P, obs_off, obs_kf, obs_feat, pos, ref_kf, ref_feat,
+                                                    nlevels, scale_factors, best_obs, best_desc, normal, min_dist, max_dist, status);
+}
+void* ccmh_mappoint_refresh_create(void* store, int device, int K, const int64_t* keys, const float* kf_center, int P, const int32_t* obs_off, const int32_t* obs_kf,
+                                   const int32_t* obs_feat, const float* pos, const int32_t* ref_kf, const int32_t* ref_feat, const float* normal, const float* min_dist,
+                                   const float* max_dist, int nlevels, const float* scale_factors) {
+  if (!store) return nullptr;
+  try {
+    return new cslam::MapPointRefresh(*static_cast<cslam::KeyFrameStore*>(store), device < 0 ? nullptr : &thread_context(device), K, keys, kf_center,
+                                      {P, obs_off, obs_kf, obs_feat}, {pos, ref_kf, ref_feat, normal, min_dist, max_dist}, nlevels, scale_factors);
+  } catch (const std::exception&) { return nullptr; }
+}
+int ccmh_mappoint_refresh_result(void* h, int P, int32_t* best_obs, uint8_t* desc, uint8_t* has_desc, float* normal, float* min_dist, float* max_dist, uint8_t* status) {
+  if (!h) return -1;
+  const cslam::MapPointRefresh& m = *static_cast<cslam::MapPointRefresh*>(h);
+  if (P != m.points()) return -1;
+  for (int p = 0; p < P; p++) {
+    best_obs[p] = m.best()[(size_t)p]; status[p] = m.status()[(size_t)p];
+    const uint8_t* d = m.descriptor(p);
+    has_desc[p] = d != nullptr;
+    if (d) std::memcpy(desc + 32 * (size_t)p, d, 32);
+    for (int c = 0; c < 3; c++) normal[3 * (size_t)p + c] = m.normal()[3 * (size_t)p + c];
+    min_dist[p] = m.min_dist()[(size_t)p]; max_dist[p] = m.max_dist()[(size_t)p];
+  }
+  return 0;
+}
+void ccmh_mappoint_refresh_destroy(void* h) { delete static_cast<cslam::MapPointRefresh*>(h); }
 
 // the two projected searches of ComputeSim3 through C: host evaluators, ssm_derive, the two mirrors
 int ccmh_sim3_project_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,

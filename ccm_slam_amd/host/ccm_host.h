@@ -888,6 +888,37 @@ class SearchForTriangulationBatch {
   long long n_reeval_ = 0;
 };
 
+// ccm_mappoint_refresh_resident's arguments after the context through csrc/mappoint_math.h on the calling thread, on the shadows of a store; -1 where the device entry
+// returns CCM_E_ARG, the outputs untouched.
+int mappoint_refresh_eval_resident_host(const KeyFrameStore& store, int K, const int64_t* keys, const float* kf_center, int P, const int32_t* obs_off, const int32_t* obs_kf,
+                                        const int32_t* obs_feat, const float* pos, const int32_t* ref_kf, const int32_t* ref_feat, int nlevels, const float* scale_factors,
+                                        int32_t* best_obs, uint8_t* best_desc, float* normal, float* min_dist, float* max_dist, uint8_t* status);
+
+// MapPoint::ComputeDistinctiveDescriptors (MapPoint.cpp:929-994) and MapPoint::UpdateNormalAndDepth (:779-823) for the map points a map stage touched, on keys of a
+// store: the refresh that follows ProcessNewKeyFrame, CreateNewMapPoints, SearchInNeighbors and every Replace.  Lists: point p
+// owns the observations obs_off[p] .. obs_off[p + 1], each (obs_kf: index into keys, obs_feat: the feature index), non-bad observers in the order of mObservations.
+// Refs: ref_kf[p] indexes keys (-1: the descriptor alone, as after Replace) and ref_feat[p] is observations[pRefKF]; normal / min_dist / max_dist are the points'
+// current values, which a point keeps when it has no observation, no reference or a reference octave beyond the tables.  The constructor makes ONE
+// ccm_mappoint_refresh_resident call, or evaluates on the calling thread when the store is host-only or ctx == nullptr; with a context a device error throws.
+class MapPointRefresh {
+ public:
+  struct Lists { int P; const int32_t *obs_off, *obs_kf, *obs_feat; };
+  struct Refs { const float* pos; const int32_t *ref_kf, *ref_feat; const float *normal, *min_dist, *max_dist; };
+  MapPointRefresh(KeyFrameStore& store, HipContext* ctx, int K, const int64_t* keys, const float* kf_center, const Lists& lists, const Refs& refs, int nlevels,
+                  const float* scale_factors);
+  int points() const { return (int)best_.size(); }
+  const std::vector<int32_t>& best() const { return best_; }        // the winning observation of every point's list, -1 for an empty list
+  const uint8_t* descriptor(int p) const { return best_[(size_t)p] < 0 ? nullptr : desc_.data() + 32 * (size_t)p; }   // mDescriptor; nullptr: unchanged
+  const std::vector<float>& normal() const { return normal_; }      // 3 per point
+  const std::vector<float>& min_dist() const { return dmin_; }
+  const std::vector<float>& max_dist() const { return dmax_; }
+  const std::vector<uint8_t>& status() const { return status_; }    // MPM_DESC | MPM_NORMAL_DEPTH | MPM_OCTAVE_BEYOND of csrc/mappoint_math.h
+ private:
+  std::vector<int32_t> best_;
+  std::vector<uint8_t> desc_, status_;
+  std::vector<float> normal_, dmin_, dmax_;
+};
+
 // ---------------------------------------------------------------------------------------------------
 // Optimizer — cslam/include/cslam/Optimizer.h:84-112 (numerics; graph walking is the integrator's glue)
 // ---------------------------------------------------------------------------------------------------

@@ -205,6 +205,14 @@ int ccmh_tri_search_resolve(void* h, int j, const uint8_t* has1_now, const uint8
 int ccmh_tri_search_table(void* h, uint32_t* table, int32_t* n_query, int32_t* n_match, int32_t* n_dist);
 long long ccmh_tri_search_n_reeval(void* h);
 void ccmh_tri_search_destroy(void* h);
+/* The refresh of map points after a map stage.  ccmh_mappoint_refresh_eval_resident_host: ccm_mappoint_refresh_resident's arguments after the
+ * context on the store's shadows through csrc/mappoint_math.h (0, or -1 for the CCM_E_ARG cases, the outputs untouched).  ccmh_mappoint_refresh_*:
+ * cslam::MapPointRefresh (device < 0: the host evaluation; create returns NULL on bad arguments, a key that is not live or a device error); result copies the
+ * accessors for P points, has_desc[p] = descriptor(p) != nullptr, and returns -1 when P is not the mirror's. */
+int ccmh_mappoint_refresh_eval_resident_host(void* store, int K, const int64_t* keys, const float* kf_center, int P, const int32_t* obs_off, const int32_t* obs_kf, const int32_t* obs_feat, const float* pos, const int32_t* ref_kf, const int32_t* ref_feat, int nlevels, const float* scale_factors, int32_t* best_obs, uint8_t* best_desc, float* normal, float* min_dist, float* max_dist, uint8_t* status);
+void* ccmh_mappoint_refresh_create(void* store, int device, int K, const int64_t* keys, const float* kf_center, int P, const int32_t* obs_off, const int32_t* obs_kf, const int32_t* obs_feat, const float* pos, const int32_t* ref_kf, const int32_t* ref_feat, const float* normal, const float* min_dist, const float* max_dist, int nlevels, const float* scale_factors);
+int ccmh_mappoint_refresh_result(void* h, int P, int32_t* best_obs, uint8_t* desc, uint8_t* has_desc, float* normal, float* min_dist, float* max_dist, uint8_t* status);
+void ccmh_mappoint_refresh_destroy(void* h);
 
 #ifdef __cplusplus
 }

@@ -746,6 +746,29 @@ int  ccm_tri_search_eval_resident(ccm_ctx* ctx, ccm_kfstore* store, int J, const
                                   const float* scale_factors, const float* level_sigma2, uint32_t* table /* has1_off[J] */, int32_t* n_query /* J */,
                                   int32_t* n_match /* J */, int32_t* n_dist /* J */);
 
+/* ---- The refresh of map points after a map stage, on keyframes of the store (the lines are csrc/mappoint_math.h) -----------------------------------
+ * MapPoint::ComputeDistinctiveDescriptors (cslam/src/MapPoint.cpp:929-994) and MapPoint::UpdateNormalAndDepth (:779-823) for P map points whose observers are live
+ * keys.  Point p owns the observations obs_off[p] .. obs_off[p + 1]: the caller's non-bad observers in the order it iterates mObservations, each as (obs_kf: index
+ * into keys, obs_feat: feature index in that keyframe).  kf_center + 3 k: GetCameraCenter() of keys[k].
+ * Descriptor part: best_obs[p] is what ccm_distinctive_descriptors returns for the same rows (exact Hamming distances with a zero diagonal, the median element
+ * (int)(0.5 * (N - 1)) of the sorted row, the FIRST index with the least median), -1 for an empty list.  best_desc + 32 p (nullable) receives the winner's 32 bytes;
+ * an empty list leaves that row untouched.
+ * Normal / depth part: the arithmetic of ccm_update_normal_and_depth (f32 in the reference's operand order, the norm in double, the sum in LIST order) on pos + 3 p,
+ * with the level read from the store: the octave of feature ref_feat[p] of keys[ref_kf[p]] (what observations[pRefKF] yields; 0 when the reference keyframe is no
+ * observer, which is the caller's to pass).  ref_kf[p] == -1 skips the part (MapPoint::Replace needs the descriptor alone); an empty list keeps the three values; a
+ * store octave >= nlevels means neither table entry is read, the point keeps its three values and status says so.  normal / min_dist / max_dist are in/out.
+ * status[p]: MPM_DESC (1) the descriptor part ran, MPM_NORMAL_DEPTH (2) the three values were written, MPM_OCTAVE_BEYOND (4).
+ * One upload (8 bytes per observation, no descriptors), ONE launch, one download, under the store's reader lock.  P == 0, K == 0 with no observation, one key listed
+ * twice and one keyframe observing a point twice are legal.  CCM_E_ARG, with nothing launched and every output untouched: a NULL store, a store on another device, a
+ * key that is not live, an obs_off that does not start at 0 or decreases, more than 256 observations of one point, obs_kf outside [0, K), obs_feat or ref_feat
+ * outside the key's feature count, ref_kf outside [-1, K), nlevels outside 1 .. 256, null arrays with a positive length, null pos / kf_center while some
+ * ref_kf >= 0. */
+int  ccm_mappoint_refresh_resident(ccm_ctx* ctx, ccm_kfstore* store, int K, const int64_t* keys /* K */, const float* kf_center /* 3 K */, int P,
+                                   const int32_t* obs_off /* P + 1 */, const int32_t* obs_kf /* obs_off[P] */, const int32_t* obs_feat /* obs_off[P] */,
+                                   const float* pos /* 3 P */, const int32_t* ref_kf /* P */, const int32_t* ref_feat /* P */, int nlevels, const float* scale_factors,
+                                   int32_t* best_obs /* P */, uint8_t* best_desc /* 32 P or NULL */, float* normal /* 3 P */, float* min_dist /* P */,
+                                   float* max_dist /* P */, uint8_t* status /* P */);
+
 #ifdef __cplusplus
 }
 #endif
