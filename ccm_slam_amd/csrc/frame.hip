@@ -103,7 +103,8 @@ __global__ void frame_window_kernel(int Q, WinQ q, FrameBounds b, const float* x
   if (FILL && off[i + 1] > cap) return;   // would cross the caller's capacity: the host reports the shortfall
   int x0, x1, y0, y1;
   int total = 0;
-  if (frame_cell_range(b, x, y, r, x0, x1, y0, y1)) {
+  // frame_cell_range is total (frame_math.h); an inverted range would turn into a positive ncell below, so it enumerates nothing whatever the bounds are
+  if (frame_cell_range(b, x, y, r, x0, x1, y0, y1) && x1 >= x0 && y1 >= y0) {
     const bool bCheckLevels = (minLevel > 0) || (maxLevel >= 0);
     const int ny = y1 - y0 + 1, ncell = (x1 - x0 + 1) * ny;
     int carry = FILL ? off[i] : 0;

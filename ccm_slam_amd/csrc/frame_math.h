@@ -2,12 +2,17 @@
 // cv::undistortPoints is [EXT] (OpenCV 4.2.0, imgproc/src/undistort.dispatch.cpp, cvUndistortPointsInternal): the call
 // at Frame.cpp:298 / :323 passes K (CV_32F, widened to f64), D = (k1 k2 p1 p2 [k3]), R = empty, P = K and the default
 // TermCriteria(MAX_ITER, 5, 0.01) => exactly five fixed-point iterations in f64, no epsilon test, result cast to f32.
+// The host mirror (host/ccm_host.cpp) compiles this file with g++: its FrameGrid takes frame_cell_range from here.
 #pragma once
-#include <hip/hip_runtime.h>
 #include <cmath>
 #include "orb_math.h"
 
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
 #define FR_HD __host__ __device__ __forceinline__
+#else
+#define FR_HD static inline
+#endif
 
 constexpr int kGridCols = 75, kGridRows = 48;   // FRAME_GRID_COLS / ROWS (cslam/include/cslam/Frame.h:51-52)
 
@@ -41,22 +46,41 @@ FR_HD void frame_undistort_point(const FrameCam& c, float xin, float yin, float&
 struct FrameBounds { float minX, minY, maxX, maxY, wInv, hInv; };
 
 // Frame::PosInGrid (Frame.cpp:254-265): f32 arithmetic, round half away from zero
+// A product that no int holds (NaN, Inf, beyond the int range) is undefined in the source; x86 gives INT_MIN, which is < 0, while the device would turn a NaN
+// into 0: stated here as "not in the grid" (as kfstore_math.h kfg_cell_of does).  roundf of anything outside (-1, 75) x (-1, 48) is outside the grid anyway.
 FR_HD int frame_cell_of(const FrameBounds& b, float x, float y) {
-  const int posX = (int)roundf((x - b.minX) * b.wInv);
-  const int posY = (int)roundf((y - b.minY) * b.hInv);
+  const float tx = (x - b.minX) * b.wInv, ty = (y - b.minY) * b.hInv;
+  if (!(tx > -1.0f && tx < (float)kGridCols) || !(ty > -1.0f && ty < (float)kGridRows)) return -1;
+  const int posX = (int)roundf(tx);
+  const int posY = (int)roundf(ty);
   if (posX < 0 || posX >= kGridCols || posY < 0 || posY >= kGridRows) return -1;
   return posX * kGridRows + posY;   // mGrid[x][y]: x-major
 }
 
-// cell range of Frame::GetFeaturesInArea (Frame.cpp:205-219); returns false when the window misses the grid
+// cell range of Frame::GetFeaturesInArea (Frame.cpp:205-219); returns false when the window misses the grid.
+// The source converts floor / ceil of four f32 products to int unchecked, which is undefined for a product no int holds (the device saturates, x86 gives
+// INT_MIN), and with r < 0 it can leave x1 < x0 or y1 < y0.  The rule here is total, and the same on host and device:
+//  * false (an empty window) when r is NaN or r < 0, and when a product is NaN: a NaN x or y, or inf - inf;
+//  * otherwise every product is clamped to [-1, 76] before the conversion.  Both ends lie outside the grid on either axis, so every window whose products an
+//    int holds keeps the range the source gives it, and a window that runs beyond the grid, up to +-inf, ends at the grid's rim.
+// With r >= 0 and positive wInv, hInv the range returned has x0 <= x1 and y0 <= y1 (subtraction, addition, product, clamp, floor and ceil are monotone).
+FR_HD float frame_clamp_cell(float t) { return t < -1.0f ? -1.0f : t > 76.0f ? 76.0f : t; }
 FR_HD bool frame_cell_range(const FrameBounds& b, float x, float y, float r, int& x0, int& x1, int& y0, int& y1) {
-  x0 = max(0, (int)floorf((x - b.minX - r) * b.wInv));
+  const float tx0 = (x - b.minX - r) * b.wInv, tx1 = (x - b.minX + r) * b.wInv;
+  const float ty0 = (y - b.minY - r) * b.hInv, ty1 = (y - b.minY + r) * b.hInv;
+  if (!(r >= 0.0f)) return false;                                            // NaN or negative radius
+  if (tx0 != tx0 || tx1 != tx1 || ty0 != ty0 || ty1 != ty1) return false;    // NaN x or y, inf - inf
+  x0 = (int)floorf(frame_clamp_cell(tx0));
+  if (x0 < 0) x0 = 0;
   if (x0 >= kGridCols) return false;
-  x1 = min(kGridCols - 1, (int)ceilf((x - b.minX + r) * b.wInv));
+  x1 = (int)ceilf(frame_clamp_cell(tx1));
+  if (x1 > kGridCols - 1) x1 = kGridCols - 1;
   if (x1 < 0) return false;
-  y0 = max(0, (int)floorf((y - b.minY - r) * b.hInv));
+  y0 = (int)floorf(frame_clamp_cell(ty0));
+  if (y0 < 0) y0 = 0;
   if (y0 >= kGridRows) return false;
-  y1 = min(kGridRows - 1, (int)ceilf((y - b.minY + r) * b.hInv));
+  y1 = (int)ceilf(frame_clamp_cell(ty1));
+  if (y1 > kGridRows - 1) y1 = kGridRows - 1;
   if (y1 < 0) return false;
   return true;
 }
@@ -103,7 +127,11 @@ FR_HD bool frame_in_frustum(const FrustumFrame& f, const float P[3], const float
   const float viewCos = (float)(dot / dist);
   if (viewCos < viewingCosLimit) return false;
   const float ratio = mfMaxDistance / dist;
-  int nScale = (int)ceilf(orbm::logf_glibc(ratio) / f.logScaleFactor);
+  // logf_glibc restates the library's logf for positive normal finite arguments only.  Outside them (dist == 0 gives x / 0 = inf or 0 / 0 = NaN; a zero,
+  // negative or subnormal ratio) the library returns +-inf, NaN or a value below -87, and the x86 build converts ceil() of the quotient to INT_MIN for the
+  // first three and to a negative int for the last: the clamp below turns each into level 0.  (The device's own conversion would saturate inf to INT_MAX.)
+  int nScale = 0;
+  if (ratio >= 1.17549435e-38f && ratio <= 3.40282347e+38f) nScale = (int)ceilf(orbm::logf_glibc(ratio) / f.logScaleFactor);
   if (nScale < 0) nScale = 0;
   else if (nScale >= f.nScaleLevels) nScale = f.nScaleLevels - 1;
   u_out = u; v_out = v; level_out = nScale; cos_out = viewCos;

@@ -13,6 +13,7 @@
 #include "../csrc/bow_search_math.h"
 #include "../csrc/tri_search_math.h"
 #include "../csrc/mappoint_math.h"
+#include "../csrc/frame_math.h"
 #include <climits>
 #include <algorithm>
 #include <cmath>
@@ -70,8 +71,6 @@ void ORBextractor::operator()(const uint8_t* image, int cols, int rows, int step
 
 // ---- Frame grid (Frame.cpp:87-88, 103-118, 200-265), FRAME_GRID_COLS 75 x ROWS 48 -------------------
 namespace {
-constexpr int kGridCols = 75, kGridRows = 48;
-
 struct FrameGrid {
   const FrameView& F;
   float wInv, hInv;
@@ -96,14 +95,10 @@ struct FrameGrid {
   }
   // appends the candidate indices in the reference's order (ix-major, iy, insertion)
   void featuresInArea(float x, float y, float r, int minLevel, int maxLevel, std::vector<int32_t>& out) const {
-    const int nMinCellX = std::max(0, (int)std::floor((x - F.mnMinX - r) * wInv));
-    if (nMinCellX >= kGridCols) return;
-    const int nMaxCellX = std::min(kGridCols - 1, (int)std::ceil((x - F.mnMinX + r) * wInv));
-    if (nMaxCellX < 0) return;
-    const int nMinCellY = std::max(0, (int)std::floor((y - F.mnMinY - r) * hInv));
-    if (nMinCellY >= kGridRows) return;
-    const int nMaxCellY = std::min(kGridRows - 1, (int)std::ceil((y - F.mnMinY + r) * hInv));
-    if (nMaxCellY < 0) return;
+    // the cell range by the device's own lines: total for any x, y, r (csrc/frame_math.h)
+    const FrameBounds b{F.mnMinX, F.mnMinY, F.mnMaxX, F.mnMaxY, wInv, hInv};
+    int nMinCellX, nMaxCellX, nMinCellY, nMaxCellY;
+    if (!frame_cell_range(b, x, y, r, nMinCellX, nMaxCellX, nMinCellY, nMaxCellY)) return;
     const bool bCheckLevels = (minLevel > 0) || (maxLevel >= 0);
     for (int ix = nMinCellX; ix <= nMaxCellX; ix++)
       for (int iy = nMinCellY; iy <= nMaxCellY; iy++) {

@@ -192,7 +192,12 @@ int  ccm_orb_extract_batch_dev(ccm_orb* orb, const uint8_t* d_imgs, int n_frames
  * :286).  ccm_frame_window_search evaluates a batch of Frame::GetFeaturesInArea(u, v, r, minLevel, maxLevel) calls
  * (:200-253; pass -1, -1 for KeyFrame::GetFeaturesInArea, KeyFrame.cpp:1162-1201) and the Hamming distance of every
  * candidate to the query's descriptor: cand_off[Q+1], cand_idx / cand_dist in the reference's enumeration order
- * (ix-major, iy, insertion order), ready for the host's ordered resolution pass.  Call it with cap = 0 to size. */
+ * (ix-major, iy, insertion order), ready for the host's ordered resolution pass.  Call it with cap = 0 to size.
+ * u, v and r are not validated on the host; the window rule is total instead (csrc/frame_math.h frame_cell_range, the
+ * same lines on host and device): a query whose r is NaN or negative, whose u or v is NaN, or whose window edge is
+ * inf - inf has an empty list; otherwise the four cell products are clamped to [-1, 76] before the conversion to int,
+ * so a window beyond the grid (an infinite u, v or r included) ends at the grid's rim and every window an int holds is
+ * the reference's.  min_level > max_level >= 0 is an empty list by the reference's own level rule. */
 typedef struct ccm_frame ccm_frame;
 int  ccm_frame_create(ccm_ctx* ctx, const float K[4], const float* dist, int n_dist, int img_w, int img_h, ccm_frame** out);
 void ccm_frame_destroy(ccm_frame* f);
