@@ -91,6 +91,7 @@ def hooks():
     """libccm_testhooks.so: the TEST-ONLY entry points (include/ccm_testhooks.h).  A separate library on top of the product; tests/ and scripts/ only."""
     h = _load("libccm_testhooks.so")
     h.ccm_comm_loopback_destroy.restype = None
+    h.ccm_kfstore_debug_get_featvec.argtypes = [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4
     return h
 
 

@@ -17,6 +17,7 @@
 //    resolution pass; best/second come from two wave min-reductions over (dist,slot) keys.
 #include "common.h"
 #include "stage_blocks.h"
+#include "vocab.h"
 
 namespace {
 
@@ -269,7 +270,7 @@ __global__ __launch_bounds__(64) void distinctive_kernel(const uint32_t* __restr
 // one wave per feature: at every level the lanes take one child each (k <= 64), the wave picks the child with the
 // least FORB::distance, FIRST minimum winning (strict '<' in child order); records the node at level nid_level.
 __global__ __launch_bounds__(256) void bow_descend_kernel(const uint32_t* __restrict__ desc, int N, const int32_t* __restrict__ child_off,
-                                                          const int32_t* __restrict__ child_id, const uint32_t* __restrict__ node_desc,
+                                                          const int32_t* __restrict__ child_id, const uint32_t* __restrict__ node_desc, int n_nodes,
                                                           int nid_level, int32_t* __restrict__ leaf_out, int32_t* __restrict__ nid_out) {
   const int lane = threadIdx.x & (kWave - 1);
   const int f = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave);
@@ -280,27 +281,8 @@ __global__ __launch_bounds__(256) void bow_descend_kernel(const uint32_t* __rest
 #pragma unroll
     for (int k = 0; k < 8; k++) a[k] = ap[k];
   }
-  int node = 0, level = 0, nid = 0;
-  while (true) {
-    const int c0 = child_off[node], c1 = child_off[node + 1];
-    if (c1 <= c0) break;   // leaf
-    ++level;
-    uint32_t best = 0xFFFFFFFFu;
-    for (int base = c0; base < c1; base += kWave) {
-      uint32_t key = 0xFFFFFFFFu;
-      if (base + lane < c1) {
-        const int id = child_id[base + lane];
-        const uint4* bp = reinterpret_cast<const uint4*>(node_desc + (size_t)id * 8);
-        const uint4 lo = bp[0], hi = bp[1];
-        const int d = __builtin_popcount(a[0] ^ lo.x) + __builtin_popcount(a[1] ^ lo.y) + __builtin_popcount(a[2] ^ lo.z) + __builtin_popcount(a[3] ^ lo.w) +
-                      __builtin_popcount(a[4] ^ hi.x) + __builtin_popcount(a[5] ^ hi.y) + __builtin_popcount(a[6] ^ hi.z) + __builtin_popcount(a[7] ^ hi.w);
-        key = ((uint32_t)d << 20) | (uint32_t)(base + lane - c0);
-      }
-      best = min(best, wave_min_u32(key));
-    }
-    node = child_id[c0 + (int)(best & 0xFFFFFu)];
-    if (level == nid_level) nid = node;
-  }
+  int nid;
+  const int node = vocab_descend_wave(a, lane, child_off, child_id, node_desc, n_nodes, nid_level, &nid);   // vocab.h
   if (lane == 0) { leaf_out[f] = node; nid_out[f] = nid; }
 }
 
@@ -492,12 +474,7 @@ extern "C" int ccm_distinctive_descriptors(ccm_ctx* ctx, const uint8_t* desc, co
 }
 
 // ---- vocabulary handle ------------------------------------------------------------------------------------
-struct ccm_vocab {
-  ccm_ctx* ctx; int n_nodes, L;
-  int32_t *d_child_off, *d_child_id; uint32_t* d_node_desc;
-  std::vector<int32_t> word_id; std::vector<double> weight;
-};
-
+// struct ccm_vocab: vocab.h
 extern "C" int ccm_vocab_create(ccm_ctx* ctx, int n_nodes, int L, const int32_t* child_off, const int32_t* child_id, const uint8_t* node_desc,
                                 const int32_t* word_id, const double* weight, ccm_vocab** out) {
   if (!ctx || !out || n_nodes <= 0 || !child_off || !node_desc || !word_id || !weight || L <= 0)
@@ -514,7 +491,10 @@ extern "C" int ccm_vocab_create(ccm_ctx* ctx, int n_nodes, int L, const int32_t*
   v->ctx = ctx; v->n_nodes = n_nodes; v->L = L;
   v->word_id.assign(word_id, word_id + n_nodes); v->weight.assign(weight, weight + n_nodes);
   const bool ok = hipMalloc(&v->d_child_off, (size_t)(n_nodes + 1) * 4) == hipSuccess && hipMalloc(&v->d_child_id, (size_t)std::max(n_child, 1) * 4) == hipSuccess &&
-                  hipMalloc(&v->d_node_desc, (size_t)n_nodes * 32) == hipSuccess &&
+                  hipMalloc(&v->d_node_desc, (size_t)n_nodes * 32) == hipSuccess && hipMalloc(&v->d_word_id, (size_t)n_nodes * 4) == hipSuccess &&
+                  hipMalloc(&v->d_weight, (size_t)n_nodes * 8) == hipSuccess &&
+                  hipMemcpyAsync(v->d_word_id, word_id, (size_t)n_nodes * 4, hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
+                  hipMemcpyAsync(v->d_weight, weight, (size_t)n_nodes * 8, hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
                   hipMemcpyAsync(v->d_child_off, child_off, (size_t)(n_nodes + 1) * 4, hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
                   (!n_child || hipMemcpyAsync(v->d_child_id, child_id, (size_t)n_child * 4, hipMemcpyHostToDevice, ctx->stream) == hipSuccess) &&
                   hipMemcpyAsync(v->d_node_desc, node_desc, (size_t)n_nodes * 32, hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
@@ -531,7 +511,7 @@ extern "C" int ccm_vocab_create(ccm_ctx* ctx, int n_nodes, int L, const int32_t*
 extern "C" void ccm_vocab_destroy(ccm_vocab* v) {
   if (!v) return;
   hipSetDevice(v->ctx->device); hipStreamSynchronize(v->ctx->stream);
-  hipFree(v->d_child_off); hipFree(v->d_child_id); hipFree(v->d_node_desc);
+  hipFree(v->d_child_off); hipFree(v->d_child_id); hipFree(v->d_node_desc); hipFree(v->d_word_id); hipFree(v->d_weight);
   delete v;
 }
 
@@ -545,7 +525,7 @@ extern "C" int ccm_bow_transform(ccm_vocab* v, const uint8_t* desc, int N, int l
   if (int rc = ccm_staged_upload(ctx, b)) return rc;
   const int nid_level = v->L - levelsup;   // if <= 0 the node stays 0 (root), TemplatedVocabulary.h:1227
   hipLaunchKernelGGL(bow_descend_kernel, dim3(ccm_div_up(N, 4)), dim3(256), 0, ctx->stream, (const uint32_t*)b.dev(b.desc), N, v->d_child_off, v->d_child_id,
-                     v->d_node_desc, nid_level, b.dev(b.leaf), b.dev(b.nid));
+                     v->d_node_desc, v->n_nodes, nid_level, b.dev(b.leaf), b.dev(b.nid));
   CCM_HIP_CHECK(ctx, hipGetLastError());
   if (int rc = ccm_staged_download(ctx, b)) return rc;
   b.get(b.nid, node_out);

@@ -3,6 +3,7 @@
 #pragma once
 #include "common.h"
 #include "kfstore_math.h"
+#include <algorithm>
 #include <shared_mutex>
 #include <unordered_map>
 
@@ -28,3 +29,40 @@ struct ccm_kfstore {
   std::unordered_map<int64_t, int> live;   // key -> slot
   std::vector<int> free_slots;             // a stack: the slot freed last is taken first
 };
+
+// kfstore_add_kernel's arguments (kfstore.hip): the call's staged arrays, then the store's
+struct KfAddArgs {
+  int stride;
+  const int32_t *slot, *feat_off, *cell_off_in;
+  const float *rec_in, *xy_in;
+  const uint16_t* cell_idx_in;
+  const uint8_t *oct_in, *desc_in;
+  float *rec, *xy;
+  int32_t *n, *n_in, *cell_off, *n_in_out;
+  uint16_t* cell_idx;
+  uint8_t *oct, *desc;
+};
+
+// the grid-building form of kfstore_add_kernel on the context's stream, one workgroup per keyframe: ccm_kfstore_add without a grid, and ccm_kfstore_ingest
+// (kfingest.hip).  Internal to libccm_hip.so: not exported.
+__attribute__((visibility("hidden"))) void kfstore_launch_add_build(ccm_ctx* ctx, const KfAddArgs& a, int M);
+
+// the handle and the caller's context of every store call
+inline int kfstore_ctx_ok(ccm_kfstore* st, ccm_ctx* ctx, const char* what) {
+  if (!ctx) return CCM_E_ARG;
+  if (!st) return ccm_set_error(ctx, CCM_E_ARG, std::string(what) + ": NULL handle");
+  if (ctx->device != st->device) return ccm_set_error(ctx, CCM_E_ARG, std::string(what) + ": the context is on another device than the store");
+  CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  return CCM_OK;
+}
+
+// what add and ingest ask of the call's keys under the store's exclusive lock: no key twice, none live, a free slot for each
+inline int kfstore_keys_ok(ccm_kfstore* st, ccm_ctx* ctx, const char* me, int M, const int64_t* keys) {
+  std::vector<int64_t> sorted(keys, keys + M);
+  std::sort(sorted.begin(), sorted.end());
+  if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return ccm_set_error(ctx, CCM_E_STATE, std::string(me) + "a key is repeated within the call");
+  for (int m = 0; m < M; m++)
+    if (st->live.count(keys[m])) return ccm_set_error(ctx, CCM_E_STATE, std::string(me) + "a key is already in the store");
+  if ((size_t)M > st->free_slots.size()) return ccm_set_error(ctx, CCM_E_STATE, std::string(me) + "fewer free slots than keyframes");
+  return CCM_OK;
+}

@@ -18,6 +18,9 @@
 //
 // ccm_kfstore_set_featvec gives a live key its DBoW2::FeatureVector: the flat arrays are validated (bow_search_math.h bsm_check_featvec) and copied
 // into the slot as they are, the indices in 16 bits; nothing is sorted or built.  A slot's vector goes with its tenant: add, erase and clear mark it absent.
+//
+// ccm_kfstore_ingest (kfingest.hip) does add without a grid and set_featvec for the keyframes of a message in one call, the vector built on the
+// device; it launches kfstore_add_kernel<true> through kfstore_launch_add_build (kfstore.h).
 #include "kfstore.h"
 #include "bow_search_math.h"
 #include "stage_blocks.h"
@@ -25,18 +28,6 @@
 #include <algorithm>
 
 namespace {
-
-struct KfAddArgs {
-  int stride;
-  const int32_t *slot, *feat_off, *cell_off_in;
-  const float *rec_in, *xy_in;
-  const uint16_t* cell_idx_in;
-  const uint8_t *oct_in, *desc_in;
-  float *rec, *xy;
-  int32_t *n, *n_in, *cell_off, *n_in_out;
-  uint16_t* cell_idx;
-  uint8_t *oct, *desc;
-};
 
 constexpr int kAddThreads = 256, kAddWaves = kAddThreads / 64;
 constexpr int kCellsPerThread = (FSM_CELLS + kAddThreads - 1) / kAddThreads;   // 15
@@ -137,15 +128,11 @@ __global__ __launch_bounds__(kAddThreads) void kfstore_add_kernel(KfAddArgs a) {
   }
 }
 
-int kfstore_ctx_ok(ccm_kfstore* st, ccm_ctx* ctx, const char* what) {
-  if (!ctx) return CCM_E_ARG;
-  if (!st) return ccm_set_error(ctx, CCM_E_ARG, std::string(what) + ": NULL handle");
-  if (ctx->device != st->device) return ccm_set_error(ctx, CCM_E_ARG, std::string(what) + ": the context is on another device than the store");
-  CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  return CCM_OK;
-}
-
 }  // namespace
+
+void kfstore_launch_add_build(ccm_ctx* ctx, const KfAddArgs& a, int M) {
+  hipLaunchKernelGGL(kfstore_add_kernel<true>, dim3((unsigned)M), dim3(kAddThreads), 0, ctx->stream, a);
+}
 
 extern "C" int ccm_kfstore_create(ccm_ctx* ctx, int max_kf, int max_feat, ccm_kfstore** out) {
   if (!ctx) return CCM_E_ARG;
@@ -192,14 +179,7 @@ extern "C" int ccm_kfstore_add(ccm_kfstore* st, ccm_ctx* ctx, int M, const int64
     return ccm_set_error(ctx, CCM_E_ARG, std::string(me) + why);
   if (M == 0) return CCM_OK;
   std::unique_lock<std::shared_mutex> lk(st->mu);
-  {
-    std::vector<int64_t> sorted(keys, keys + M);
-    std::sort(sorted.begin(), sorted.end());
-    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return ccm_set_error(ctx, CCM_E_STATE, std::string(me) + "a key is repeated within the call");
-    for (int m = 0; m < M; m++)
-      if (st->live.count(keys[m])) return ccm_set_error(ctx, CCM_E_STATE, std::string(me) + "a key is already in the store");
-  }
-  if ((size_t)M > st->free_slots.size()) return ccm_set_error(ctx, CCM_E_STATE, std::string(me) + "fewer free slots than keyframes");
+  if (int rc = kfstore_keys_ok(st, ctx, me, M, keys)) return rc;
   const size_t F = (size_t)feat_off[M];
   const bool grid = cell_off != nullptr;
   KfstoreAddBlock b((size_t)M, F, grid);
@@ -224,7 +204,7 @@ extern "C" int ccm_kfstore_add(ccm_kfstore* st, ccm_ctx* ctx, int M, const int64
   a.rec = st->d_rec; a.xy = st->d_xy; a.n = st->d_n; a.n_in = st->d_n_in; a.cell_off = st->d_cell_off; a.n_in_out = b.dev(b.n_in);
   a.cell_idx = st->d_cell_idx; a.oct = st->d_oct; a.desc = st->d_desc;
   if (grid) hipLaunchKernelGGL(kfstore_add_kernel<false>, dim3((unsigned)M), dim3(kAddThreads), 0, ctx->stream, a);
-  else hipLaunchKernelGGL(kfstore_add_kernel<true>, dim3((unsigned)M), dim3(kAddThreads), 0, ctx->stream, a);
+  else kfstore_launch_add_build(ctx, a, M);
   CCM_HIP_CHECK(ctx, hipGetLastError());
   if (int rc = ccm_staged_download(ctx, b)) return rc;   // synchronises: the slots are written when the keys become live
   for (int m = 0; m < M; m++) {

@@ -137,6 +137,24 @@ struct KfstoreAddBlock : StagedBlock {
   StagedSeg<int32_t> n_in = add<int32_t>(M, SB_OUT);
 };
 
+// ccm_kfstore_ingest: what KfstoreAddBlock carries without a grid goes up; the features' weights (and their words and nodes, when the caller does
+// not ask for them) stay on the device between the descent and the keyframes' workgroups; the values lead the download, on 8 bytes, then n_in, the two counts per
+// keyframe, the two vectors (fv_off has one entry more per keyframe) and, when asked for, the per-feature words and nodes.
+struct KfIngestBlock : StagedBlock {
+  const size_t M, F; const bool want_feat;
+  KfIngestBlock(size_t M, size_t F, bool want_feat) : M(M), F(F), want_feat(want_feat) {}
+  StagedSeg<uint8_t> desc = add<uint8_t>(32 * F, SB_COPY, 16);
+  StagedSeg<int32_t> slot = add<int32_t>(M, SB_GEN), feat_off = add<int32_t>(M + 1, SB_COPY);
+  StagedSeg<float> rec = add<float>(FSM_REC_FLOATS * M, SB_COPY), xy = add<float>(2 * F, SB_COPY);
+  StagedSeg<uint8_t> oct = add<uint8_t>(F, SB_COPY);
+  StagedSeg<double> weight = add<double>(F, SB_WORK);
+  StagedSeg<int32_t> work_word = add<int32_t>(want_feat ? 0 : F, SB_WORK), work_node = add<int32_t>(want_feat ? 0 : F, SB_WORK);
+  StagedSeg<double> bow_value = add<double>(F, SB_OUT);
+  StagedSeg<int32_t> n_in = add<int32_t>(M, SB_OUT), bow_n = add<int32_t>(M, SB_OUT), fv_nn = add<int32_t>(M, SB_OUT);
+  StagedSeg<int32_t> bow_word = add<int32_t>(F, SB_OUT), fv_node = add<int32_t>(F, SB_OUT), fv_off = add<int32_t>(F + M, SB_OUT), fv_idx = add<int32_t>(F, SB_OUT);
+  StagedSeg<int32_t> feat_word = add<int32_t>(want_feat ? F : 0, SB_OUT), feat_node = add<int32_t>(want_feat ? F : 0, SB_OUT);
+};
+
 // ccm_bow_pair_eval_resident: J jobs of BSM_JOB_INTS ints each (the two slots, their node counts, the jobs' first mask bytes and first work item,
 // written by the stage while it validates) and the two sides' mask bytes, M1 and M2 in all.  The table has one 64-bit word per mask byte of side 1 and leads the
 // outputs, on 8 bytes; it goes up as zeros (a feature no wave meets is no query) and so do the counters, which the kernel adds to.

@@ -4,6 +4,7 @@
 #include "ba_types.h"
 #include "test_internal.h"
 #include "lane_xor.h"
+#include "kfstore.h"
 #include "../../include/ccm_testhooks.h"
 #include <cstring>
 #include <string>
@@ -176,5 +177,29 @@ extern "C" int ccm_debug_twoview_score(ccm_ctx* ctx, int model, int n_models, co
   CCM_HIP_CHECK(ctx, hipMemcpy(score, d_score, n_models * sizeof(float), hipMemcpyDeviceToHost));
   CCM_HIP_CHECK(ctx, hipMemcpy(mask, d_mask, words * n_models * sizeof(uint32_t), hipMemcpyDeviceToHost));
   CCM_HIP_CHECK(ctx, hipFree(d));
+  return CCM_OK;
+}
+
+// A live key's feature vector as its slot of the keyframe store holds it (ccm_kfstore_set_featvec, ccm_kfstore_ingest): nn, node[nn], off[nn + 1], idx[off[nn]]
+// (room for n + 1, n + 1 and n entries, n the key's feature count).  nn = -1: the key has no vector.  tests/test_kfingest_gpu.py.
+extern "C" int ccm_kfstore_debug_get_featvec(ccm_kfstore* st, ccm_ctx* ctx, int64_t key, int* nn, int32_t* node, int32_t* off, int32_t* idx) {
+  if (int rc = kfstore_ctx_ok(st, ctx, "ccm_kfstore_debug_get_featvec")) return rc;
+  if (!nn) return CCM_E_ARG;
+  std::shared_lock<std::shared_mutex> lk(st->mu);
+  auto it = st->live.find(key);
+  if (it == st->live.end()) return ccm_set_error(ctx, CCM_E_ARG, "ccm_kfstore_debug_get_featvec: key not in the store");
+  const size_t s = (size_t)it->second, g0 = s * (size_t)st->stride;
+  const int n = st->h_n[s], c = st->h_fv_nn[s];
+  *nn = c;
+  if (c <= 0 || !node || !off || !idx) return CCM_OK;
+  if (c > n) return ccm_set_error(ctx, CCM_E_STATE, "ccm_kfstore_debug_get_featvec: more nodes than features");
+  CCM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  CCM_HIP_CHECK(ctx, hipMemcpy(node, st->d_fv_node + g0, (size_t)c * 4, hipMemcpyDeviceToHost));
+  CCM_HIP_CHECK(ctx, hipMemcpy(off, st->d_fv_off + g0 + s, ((size_t)c + 1) * 4, hipMemcpyDeviceToHost));
+  const int L = off[c];
+  if (L < 0 || L > n) return ccm_set_error(ctx, CCM_E_STATE, "ccm_kfstore_debug_get_featvec: the slot's offsets are not a feature vector's");
+  std::vector<uint16_t> h((size_t)L);
+  if (L) CCM_HIP_CHECK(ctx, hipMemcpy(h.data(), st->d_fv_idx + g0, (size_t)L * 2, hipMemcpyDeviceToHost));
+  for (int i = 0; i < L; i++) idx[i] = h[i];
   return CCM_OK;
 }

@@ -10,6 +10,7 @@
 #include "../csrc/kfcull_math.h"
 #include "../csrc/fuse_math.h"
 #include "../csrc/kfstore_math.h"
+#include "../csrc/kfingest_math.h"
 #include "../csrc/bow_search_math.h"
 #include "../csrc/tri_search_math.h"
 #include "../csrc/mappoint_math.h"
@@ -791,36 +792,39 @@ int ORBmatcher::MutualAgreement(const std::vector<int32_t>& vnMatch1, const std:
 ORBVocabulary::ORBVocabulary(HipContext& ctx, int n_nodes, int L, const int32_t* child_off, const int32_t* child_id, const uint8_t* node_desc,
                              const int32_t* word_id, const double* weight) {
   check(ccm_vocab_create(ctx.get(), n_nodes, L, child_off, child_id, node_desc, word_id, weight, &voc_), ctx.get(), "ccm_vocab_create");
+  keep(n_nodes, L, child_off, child_id, node_desc, word_id, weight);
+}
+ORBVocabulary::ORBVocabulary(HipContext* ctx, int n_nodes, int L, const int32_t* child_off, const int32_t* child_id, const uint8_t* node_desc, const int32_t* word_id,
+                             const double* weight) {
+  if (ctx) check(ccm_vocab_create(ctx->get(), n_nodes, L, child_off, child_id, node_desc, word_id, weight, &voc_), ctx->get(), "ccm_vocab_create");
+  else if (n_nodes <= 0 || L <= 0 || !child_off || !node_desc || !word_id || !weight || child_off[n_nodes] < 0 || (child_off[n_nodes] && !child_id))
+    throw infrastructure_ex("ORBVocabulary: bad args");
+  keep(n_nodes, L, child_off, child_id, node_desc, word_id, weight);
 }
 ORBVocabulary::~ORBVocabulary() { ccm_vocab_destroy(voc_); }
+void ORBVocabulary::keep(int n_nodes, int L, const int32_t* child_off, const int32_t* child_id, const uint8_t* node_desc, const int32_t* word_id, const double* weight) {
+  n_nodes_ = n_nodes; L_ = L;
+  child_off_.assign(child_off, child_off + n_nodes + 1);
+  child_id_.assign(child_id, child_id + (child_off[n_nodes] > 0 ? child_off[n_nodes] : 0));
+  node_desc_.assign(node_desc, node_desc + 32 * (size_t)n_nodes);
+  word_id_.assign(word_id, word_id + n_nodes);
+  weight_.assign(weight, weight + n_nodes);
+}
 
 void ORBVocabulary::transform(const uint8_t* descriptors, int N, BowVector& v, FeatureVector& fv, int levelsup) const {
   v.word.clear(); v.value.clear(); fv.node.clear(); fv.off.assign(1, 0); fv.idx.clear();
   if (N <= 0) return;
+  if (!voc_) throw infrastructure_ex("ORBVocabulary::transform: a vocabulary without a context has no device tree");
   std::vector<int32_t> word(N), node(N); std::vector<double> w(N);
   if (ccm_bow_transform(voc_, descriptors, N, levelsup, word.data(), w.data(), node.data()) != CCM_OK)
     throw infrastructure_ex(std::string("ccm_bow_transform: ") + ccm_last_error(nullptr));
-  // TF_IDF weighting + L1 norm (ORBvoc): BowVector::addWeight in feature order, FeatureVector::addFeature, then normalize
-  std::vector<std::pair<int32_t, int>> bw, fn;   // (word, feature), (node, feature) for kept features
-  for (int i = 0; i < N; i++) if (w[i] > 0) { bw.emplace_back(word[i], i); fn.emplace_back(node[i], i); }   // "not stopped" (TemplatedVocabulary.h:1158)
-  std::stable_sort(bw.begin(), bw.end(), [](const std::pair<int32_t, int>& a, const std::pair<int32_t, int>& b) { return a.first < b.first; });
-  for (size_t s = 0; s < bw.size();) {
-    const int32_t id = bw[s].first;
-    double acc = 0.0;
-    bool first = true;
-    for (; s < bw.size() && bw[s].first == id; s++) { if (first) { acc = w[bw[s].second]; first = false; } else acc += w[bw[s].second]; }
-    v.word.push_back(id); v.value.push_back(acc);
-  }
-  double norm = 0.0;
-  for (double x : v.value) norm += std::fabs(x);
-  if (norm > 0.0) for (double& x : v.value) x /= norm;
-  std::stable_sort(fn.begin(), fn.end(), [](const std::pair<int32_t, int>& a, const std::pair<int32_t, int>& b) { return a.first < b.first; });
-  for (size_t s = 0; s < fn.size();) {
-    const int32_t id = fn[s].first;
-    fv.node.push_back(id);
-    for (; s < fn.size() && fn[s].first == id; s++) fv.idx.push_back(fn[s].second);
-    fv.off.push_back((int32_t)fv.idx.size());
-  }
+  // TF_IDF weighting + L1 norm (ORBvoc): BowVector::addWeight in feature order, FeatureVector::addFeature, then normalize — the lines of csrc/kfingest_math.h
+  std::vector<int32_t> bw(N), fn(N), fo((size_t)N + 1), fi(N);
+  std::vector<double> bv(N);
+  int32_t nw = 0, nn = 0;
+  kfi_vectors_host(N, word.data(), w.data(), node.data(), &nw, bw.data(), bv.data(), &nn, fn.data(), fo.data(), fi.data());
+  v.word.assign(bw.begin(), bw.begin() + nw); v.value.assign(bv.begin(), bv.begin() + nw);
+  fv.node.assign(fn.begin(), fn.begin() + nn); fv.off.assign(fo.begin(), fo.begin() + nn + 1); fv.idx.assign(fi.begin(), fi.begin() + fo[nn]);
 }
 
 std::vector<int32_t> ComputeDistinctiveDescriptors(HipContext& ctx, const uint8_t* desc, const std::vector<int32_t>& off) {
@@ -1955,6 +1959,16 @@ KeyFrameStore::KeyFrameStore(HipContext* ctx, int max_kf, int max_feat) : max_kf
 
 KeyFrameStore::~KeyFrameStore() { ccm_kfstore_destroy(h_); }
 
+// the host-only store's key rules: no key twice within the call, none live, a free slot for each
+bool KeyFrameStore::keys_ok(int M, const int64_t* keys) const {
+  std::vector<int64_t> sorted(keys, keys + (M > 0 ? M : 0));
+  std::sort(sorted.begin(), sorted.end());
+  if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return false;
+  for (int m = 0; m < M; m++)
+    if (live_.count(keys[m])) return false;
+  return (size_t)(M > 0 ? M : 0) <= (size_t)max_kf_ - live_.size();
+}
+
 int KeyFrameStore::add(HipContext* ctx, int M, const int64_t* keys, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave,
                        const uint8_t* feat_desc, const int32_t* cell_off, const int32_t* cell_idx) {
   if (h_ && !ctx) throw infrastructure_ex("KeyFrameStore::add: a device store needs the calling thread's context");
@@ -1965,12 +1979,7 @@ int KeyFrameStore::add(HipContext* ctx, int M, const int64_t* keys, const float*
     check(rc, ctx->get(), "ccm_kfstore_add");
   } else {
     if ((M > 0 && !keys) || kfg_check_add(M, max_feat_, kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off, cell_idx)) return CCM_E_ARG;
-    std::vector<int64_t> sorted(keys, keys + (M > 0 ? M : 0));
-    std::sort(sorted.begin(), sorted.end());
-    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return CCM_E_STATE;
-    for (int m = 0; m < M; m++)
-      if (live_.count(keys[m])) return CCM_E_STATE;
-    if ((size_t)M > (size_t)max_kf_ - live_.size()) return CCM_E_STATE;
+    if (!keys_ok(M, keys)) return CCM_E_STATE;
   }
   for (int m = 0; m < M; m++) {
     auto kf = std::make_shared<KfShadow>();
@@ -2026,6 +2035,78 @@ int KeyFrameStore::set_featvec(HipContext* ctx, int64_t key, const FeatureVector
   }
   if (angle) kf->angle.assign(angle, angle + n); else kf->angle.assign((size_t)n, 0.0f);
   it->second = std::move(kf);
+  return CCM_OK;
+}
+
+int KeyFrameStore::ingest_flat(HipContext* ctx, const ccm_vocab* dvoc, const ::kfi_tree* tree, int levelsup, int M, const int64_t* keys, const float* kf_rec,
+                               const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc, const float* angle, int32_t* bow_n,
+                               int32_t* bow_word, double* bow_value, int32_t* fv_nn, int32_t* fv_node, int32_t* fv_off, int32_t* fv_idx, int32_t* feat_word,
+                               int32_t* feat_node) {
+  if (h_ && !ctx) throw infrastructure_ex("KeyFrameStore::ingest: a device store needs the calling thread's context");
+  std::unique_lock<std::shared_mutex> lk(mu_);
+  if (h_) {   // the device store decides, by the same rules in the same order, and the shadows follow it
+    const int rc = ccm_kfstore_ingest(h_, ctx->get(), dvoc, levelsup, M, keys, kf_rec, feat_off, feat_xy, feat_octave, feat_desc, bow_n, bow_word, bow_value, fv_nn, fv_node,
+                                      fv_off, fv_idx, feat_word, feat_node);
+    if (rc == CCM_E_ARG || rc == CCM_E_STATE) return rc;
+    check(rc, ctx->get(), "ccm_kfstore_ingest");
+  } else {
+    if (!tree || (M > 0 && !keys) ||
+        kfi_check_ingest(M, max_feat_, kf_rec, feat_off, feat_xy, feat_octave, feat_desc, bow_n, bow_word, bow_value, fv_nn, fv_node, fv_off, fv_idx) ||
+        (feat_word == nullptr) != (feat_node == nullptr))
+      return CCM_E_ARG;
+    if (!keys_ok(M, keys)) return CCM_E_STATE;
+    kfi_ingest_host(*tree, levelsup, M, feat_off, feat_desc, bow_n, bow_word, bow_value, fv_nn, fv_node, fv_off, fv_idx, feat_word, feat_node);
+  }
+  for (int m = 0; m < M; m++) {   // the shadow of add without a grid, then of set_featvec
+    auto kf = std::make_shared<KfShadow>();
+    const int32_t f0 = feat_off[m], n = feat_off[m + 1] - f0;
+    std::memcpy(kf->rec, kf_rec + FSM_REC_FLOATS * (size_t)m, sizeof kf->rec);
+    kf->n = n;
+    if (n) {
+      kf->xy.assign(feat_xy + 2 * (size_t)f0, feat_xy + 2 * (size_t)(f0 + n));
+      kf->oct.assign(feat_octave + f0, feat_octave + f0 + n);
+      kf->desc.assign(feat_desc + 32 * (size_t)f0, feat_desc + 32 * (size_t)(f0 + n));
+    }
+    kf->cell_off.resize(FSM_CELLS + 1);
+    kf->cell_idx.resize((size_t)n);
+    kf->n_in = kfg_build_host(kf->rec, n, kf->xy.data(), kf->cell_off.data(), kf->cell_idx.data());
+    kf->cell_idx.resize((size_t)kf->n_in);
+    const int nn = fv_nn[m];
+    const int32_t* off = fv_off + f0 + m;
+    kf->has_fv = true;
+    kf->fv_node.assign(fv_node + f0, fv_node + f0 + nn);
+    kf->fv_off.assign(1, 0);
+    if (nn > 0) {
+      kf->fv_off.assign(off, off + nn + 1);
+      kf->fv_idx.resize((size_t)off[nn]);
+      for (size_t i = 0; i < kf->fv_idx.size(); i++) kf->fv_idx[i] = (uint16_t)fv_idx[f0 + i];
+    }
+    if (angle) kf->angle.assign(angle + f0, angle + f0 + n); else kf->angle.assign((size_t)n, 0.0f);
+    live_[keys[m]] = std::move(kf);
+  }
+  return CCM_OK;
+}
+
+int KeyFrameStore::ingest(HipContext* ctx, const ORBVocabulary& voc, int M, const int64_t* keys, const float* kf_rec, const int32_t* feat_off, const float* feat_xy,
+                          const uint8_t* feat_octave, const uint8_t* feat_desc, const float* angle, std::vector<BowVector>& bow, std::vector<FeatureVector>& fv,
+                          int levelsup) {
+  if (M < 0 || (M > 0 && !feat_off)) return CCM_E_ARG;
+  const size_t F = M > 0 && feat_off[M] > 0 ? (size_t)feat_off[M] : 0, Mu = (size_t)M;
+  std::vector<int32_t> bow_n(Mu + 1), bow_word(F + 1), fv_nn(Mu + 1), fv_node(F + 1), fv_off(F + Mu + 1), fv_idx(F + 1);
+  std::vector<double> bow_value(F + 1);
+  const ::kfi_tree tree = {voc.n_nodes(), voc.L(), voc.child_off().data(), voc.child_id().data(), voc.node_desc().data(), voc.word_id().data(), voc.weight().data()};
+  const int rc = ingest_flat(ctx, voc.handle(), &tree, levelsup, M, keys, kf_rec, feat_off, feat_xy, feat_octave, feat_desc, angle, bow_n.data(), bow_word.data(),
+                             bow_value.data(), fv_nn.data(), fv_node.data(), fv_off.data(), fv_idx.data(), nullptr, nullptr);
+  if (rc != CCM_OK) return rc;
+  bow.assign(Mu, BowVector()); fv.assign(Mu, FeatureVector());
+  for (int m = 0; m < M; m++) {
+    const int32_t f0 = feat_off[m];
+    bow[m].word.assign(bow_word.begin() + f0, bow_word.begin() + f0 + bow_n[m]);
+    bow[m].value.assign(bow_value.begin() + f0, bow_value.begin() + f0 + bow_n[m]);
+    fv[m].node.assign(fv_node.begin() + f0, fv_node.begin() + f0 + fv_nn[m]);
+    fv[m].off.assign(fv_off.begin() + f0 + m, fv_off.begin() + f0 + m + fv_nn[m] + 1);
+    fv[m].idx.assign(fv_idx.begin() + f0, fv_idx.begin() + f0 + fv[m].off.back());
+  }
   return CCM_OK;
 }
 
@@ -3419,6 +3500,39 @@ int ccmh_kfstore_set_featvec(void* h, int device, int64_t key, int nn, const int
   if (!h) return -1000;
   try {
     return static_cast<cslam::KeyFrameStore*>(h)->set_featvec(device < 0 ? nullptr : &thread_context(device), key, cslam::FeatureVectorView{nn, node, off, idx}, angle);
+  } catch (const std::exception&) { return -1000; }
+}
+int ccmh_kfstore_ingest(void* h, int device, void* voc, int levelsup, int M, const int64_t* keys, const float* kf_rec, const int32_t* feat_off, const float* feat_xy,
+                        const uint8_t* feat_octave, const uint8_t* feat_desc, const float* angle, int32_t* bow_n, int32_t* bow_word, double* bow_value, int32_t* fv_nn,
+                        int32_t* fv_node, int32_t* fv_off, int32_t* fv_idx, int32_t* feat_word, int32_t* feat_node) {
+  if (!h || device < 0) return -1000;
+  try {
+    return static_cast<cslam::KeyFrameStore*>(h)->ingest_flat(&thread_context(device), static_cast<const ccm_vocab*>(voc), nullptr, levelsup, M, keys, kf_rec, feat_off,
+                                                              feat_xy, feat_octave, feat_desc, angle, bow_n, bow_word, bow_value, fv_nn, fv_node, fv_off, fv_idx, feat_word,
+                                                              feat_node);
+  } catch (const std::exception&) { return -1000; }
+}
+int ccmh_kfstore_shadow_equal(void* a, void* b, int64_t key) {
+  if (!a || !b) return -1000;
+  const std::shared_ptr<const cslam::KfShadow> x = static_cast<cslam::KeyFrameStore*>(a)->shadow(key), y = static_cast<cslam::KeyFrameStore*>(b)->shadow(key);
+  if (!x || !y) return -1;
+  auto bits = [](const std::vector<float>& u, const std::vector<float>& v) { return u.size() == v.size() && (u.empty() || !std::memcmp(u.data(), v.data(), u.size() * 4)); };
+  return !std::memcmp(x->rec, y->rec, sizeof x->rec) && x->n == y->n && x->n_in == y->n_in && bits(x->xy, y->xy) && x->oct == y->oct && x->desc == y->desc &&
+         x->cell_off == y->cell_off && x->cell_idx == y->cell_idx && x->has_fv == y->has_fv && x->fv_node == y->fv_node && x->fv_off == y->fv_off &&
+         x->fv_idx == y->fv_idx && bits(x->angle, y->angle);
+}
+int ccmh_kfstore_ingest_host(void* h, int n_nodes, int L, const int32_t* child_off, const int32_t* child_id, const uint8_t* node_desc, const int32_t* word_id,
+                             const double* weight, int levelsup, int M, const int64_t* keys, const float* kf_rec, const int32_t* feat_off, const float* feat_xy,
+                             const uint8_t* feat_octave, const uint8_t* feat_desc, const float* angle, int32_t* bow_n, int32_t* bow_word, double* bow_value,
+                             int32_t* fv_nn, int32_t* fv_node, int32_t* fv_off, int32_t* fv_idx, int32_t* feat_word, int32_t* feat_node) {
+  if (!h) return -1000;
+  cslam::KeyFrameStore& st = *static_cast<cslam::KeyFrameStore*>(h);
+  if (!st.host_only()) return -1000;
+  const bool no_tree = n_nodes <= 0 || !child_off || !node_desc || !word_id || !weight || (child_off[n_nodes] > 0 && !child_id);
+  const ::kfi_tree tree = {n_nodes, L, child_off, child_id, node_desc, word_id, weight};
+  try {
+    return st.ingest_flat(nullptr, nullptr, no_tree ? nullptr : &tree, levelsup, M, keys, kf_rec, feat_off, feat_xy, feat_octave, feat_desc, angle, bow_n, bow_word, bow_value,
+                          fv_nn, fv_node, fv_off, fv_idx, feat_word, feat_node);
   } catch (const std::exception&) { return -1000; }
 }
 int ccmh_bow_pair_eval_resident_host(void* store, int J, const int64_t* key1, const int64_t* key2, const int32_t* live1_off, const uint8_t* live1, const int32_t* live2_off,

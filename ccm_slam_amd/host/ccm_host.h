@@ -21,6 +21,8 @@
 #include <shared_mutex>
 #include <unordered_map>
 
+struct kfi_tree;   // csrc/kfingest_math.h: the flat vocabulary tree on the host
+
 namespace cslam {
 
 // thrown where the reference throws estd::infrastructure_ex (cslam/include/cslam/estd.h:74-81)
@@ -424,7 +426,8 @@ int kfcull_walk_mapcopy_model(int n_cand, int n_all, const uint8_t* cand_flags, 
 // ---------------------------------------------------------------------------------------------------
 // ORBVocabulary::transform (DBoW2 TemplatedVocabulary<FORB>, thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1127-1260) as
 // KeyFrame::ComputeBoW / Frame::ComputeBoW call it (levelsup = 4), and MapPoint::ComputeDistinctiveDescriptors
-// (MapPoint.cpp:929-994) batched over many map points — SURVEY §8f rows 1 and 3.
+// (MapPoint.cpp:929-994) batched over many map points — SURVEY §8f rows 1 and 3.  The vocabulary keeps a host copy of its flat tree: KeyFrameStore::ingest
+//  transforms the keyframes of a whole message on the device, and on that copy for the host-only store.
 // ---------------------------------------------------------------------------------------------------
 struct BowVector { std::vector<int32_t> word; std::vector<double> value; };                       // ascending word ids, L1-normalised
 struct FeatureVector { std::vector<int32_t> node, off, idx; };                                     // ascending nodes, CSR, features in index order
@@ -433,10 +436,29 @@ class ORBVocabulary {
   // flat tree, see ccm_vocab_create (include/ccm_hip.h)
   ORBVocabulary(HipContext& ctx, int n_nodes, int L, const int32_t* child_off, const int32_t* child_id, const uint8_t* node_desc,
                 const int32_t* word_id, const double* weight);
+  // ctx == nullptr: the host copy alone, for KeyFrameStore::ingest on the host-only store (transform then throws)
+  ORBVocabulary(HipContext* ctx, int n_nodes, int L, const int32_t* child_off, const int32_t* child_id, const uint8_t* node_desc, const int32_t* word_id,
+                const double* weight);
   ~ORBVocabulary();
+  ORBVocabulary(const ORBVocabulary&) = delete;
+  ORBVocabulary& operator=(const ORBVocabulary&) = delete;
   void transform(const uint8_t* descriptors, int N, BowVector& v, FeatureVector& fv, int levelsup = 4) const;
+  const ccm_vocab* handle() const { return voc_; }
+  // the host copy of the flat tree, in the arguments' form
+  int n_nodes() const { return n_nodes_; }
+  int L() const { return L_; }
+  const std::vector<int32_t>& child_off() const { return child_off_; }
+  const std::vector<int32_t>& child_id() const { return child_id_; }
+  const std::vector<uint8_t>& node_desc() const { return node_desc_; }
+  const std::vector<int32_t>& word_id() const { return word_id_; }
+  const std::vector<double>& weight() const { return weight_; }
  private:
+  void keep(int n_nodes, int L, const int32_t* child_off, const int32_t* child_id, const uint8_t* node_desc, const int32_t* word_id, const double* weight);
   ccm_vocab* voc_ = nullptr;
+  int n_nodes_ = 0, L_ = 0;
+  std::vector<int32_t> child_off_, child_id_, word_id_;
+  std::vector<uint8_t> node_desc_;
+  std::vector<double> weight_;
 };
 // best descriptor per map point: desc rows off[p]..off[p+1] are the observations of point p; returns local indices
 std::vector<int32_t> ComputeDistinctiveDescriptors(HipContext& ctx, const uint8_t* desc, const std::vector<int32_t>& off);
@@ -582,6 +604,15 @@ class KeyFrameStore {
   // ccm_kfstore_set_featvec's arguments and refusals (0 or CCM_E_ARG, the store untouched by a refusal; a device error throws) and angle[n] = mvKeysUn[i].angle
   // (nullable: zeros).  A second call for the key replaces the first.  Right after add in the message constructor: ComputeBoW() has run by then.
   int set_featvec(HipContext* ctx, int64_t key, const FeatureVectorView& fv, const float* angle);
+  // The keyframes of a message in ONE call (ccm_kfstore_ingest): add without a grid, ComputeBoW and set_featvec for all of them.
+  // angle: mvKeysUn[i].angle of all features (nullable: zeros), the shadows' alone.  bow[m] / fv[m] are the keyframe's mBowVec / mFeatVec.  A shadow after ingest
+  // equals the shadow after add + set_featvec.  The host-only store evaluates csrc/kfingest_math.h on the vocabulary's host copy.  ccm_kfstore_ingest's refusals.
+  int ingest(HipContext* ctx, const ORBVocabulary& voc, int M, const int64_t* keys, const float* kf_rec, const int32_t* feat_off, const float* feat_xy,
+             const uint8_t* feat_octave, const uint8_t* feat_desc, const float* angle, std::vector<BowVector>& bow, std::vector<FeatureVector>& fv, int levelsup = 4);
+  // the same on flat arrays (ccm_kfstore_ingest's outputs); dvoc: the device vocabulary (device store), tree: the flat tree on the host (host-only store)
+  int ingest_flat(HipContext* ctx, const ccm_vocab* dvoc, const ::kfi_tree* tree, int levelsup, int M, const int64_t* keys, const float* kf_rec,
+                  const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc, const float* angle, int32_t* bow_n,
+                  int32_t* bow_word, double* bow_value, int32_t* fv_nn, int32_t* fv_node, int32_t* fv_off, int32_t* fv_idx, int32_t* feat_word, int32_t* feat_node);
   void erase(HipContext* ctx, int64_t key);
   void clear(HipContext* ctx);
   int live() const;
@@ -592,6 +623,7 @@ class KeyFrameStore {
   // the grid of one key: the device's (ccm_kfstore_get) with a context, the shadow's without; false: the key is not live
   bool get(HipContext* ctx, int64_t key, int* n, int* n_in, int32_t* cell_off, int32_t* cell_idx) const;
  private:
+  bool keys_ok(int M, const int64_t* keys) const;
   ccm_kfstore* h_ = nullptr;
   int max_kf_ = 0, max_feat_ = 0;
   mutable std::shared_mutex mu_;

@@ -188,6 +188,20 @@ int ccmh_search_by_sim3_resident(void* store, int device, int64_t key1, int64_t 
  * create returns NULL on bad arguments, a key that is not live or has no feature vector, or a device error).  live2 + live2_off[j]: candidate j's mask.  result
  * returns nmatches of candidate j and copies matches12 (n_feat entries, nullable); -1000 for j out of range, -1001 when n_feat is not key1's feature count. */
 int ccmh_kfstore_set_featvec(void* h, int device, int64_t key, int nn, const int32_t* node, const int32_t* off, const int32_t* idx, const float* angle);
+/* cslam::KeyFrameStore::ingest on flat arrays: ccm_kfstore_ingest's arguments, outputs and refusals, and angle (nullable) for the shadows.
+ * ccmh_kfstore_ingest: a device store, voc = the ccm_vocab* of include/ccm_hip.h.  ccmh_kfstore_ingest_host: the host-only store, the flat tree of ccm_vocab_create
+ * evaluated by csrc/kfingest_math.h on the calling thread (-1000 for a device store). */
+int ccmh_kfstore_ingest(void* h, int device, void* voc, int levelsup, int M, const int64_t* keys, const float* kf_rec, const int32_t* feat_off, const float* feat_xy,
+                        const uint8_t* feat_octave, const uint8_t* feat_desc, const float* angle, int32_t* bow_n, int32_t* bow_word, double* bow_value, int32_t* fv_nn,
+                        int32_t* fv_node, int32_t* fv_off, int32_t* fv_idx, int32_t* feat_word, int32_t* feat_node);
+/* A test aid (the shadows are the mirror's own and no C entry returns them): 1: the shadows of `key` in the two stores are equal in every field (floats by their
+ * bits), 0: they differ, -1: the key is not live in both.  Bound in ccm_slam_amd/kfstore.py; the tests of ingest compare a store after ingest with one after
+ * add + set_featvec, and the device mirror with the host-only one. */
+int ccmh_kfstore_shadow_equal(void* a, void* b, int64_t key);
+int ccmh_kfstore_ingest_host(void* h, int n_nodes, int L, const int32_t* child_off, const int32_t* child_id, const uint8_t* node_desc, const int32_t* word_id,
+                             const double* weight, int levelsup, int M, const int64_t* keys, const float* kf_rec, const int32_t* feat_off, const float* feat_xy,
+                             const uint8_t* feat_octave, const uint8_t* feat_desc, const float* angle, int32_t* bow_n, int32_t* bow_word, double* bow_value,
+                             int32_t* fv_nn, int32_t* fv_node, int32_t* fv_off, int32_t* fv_idx, int32_t* feat_word, int32_t* feat_node);
 int ccmh_bow_pair_eval_resident_host(void* store, int J, const int64_t* key1, const int64_t* key2, const int32_t* live1_off, const uint8_t* live1, const int32_t* live2_off, const uint8_t* live2, uint64_t* table, int32_t* n_query, int32_t* n_dist);
 void* ccmh_bow_batch_create(void* store, int device, int64_t key1, int C, const int64_t* keys2, const uint8_t* live1, const int32_t* live2_off, const uint8_t* live2, float nnratio, int check_orientation);
 int ccmh_bow_batch_result(void* h, int j, int n_feat, int32_t* matches12);

@@ -6,7 +6,8 @@ KeyFrameStore(ctx, max_kf, max_feat) wraps cslam::KeyFrameStore, which keeps the
 store by name.  fuse_sim3_eval_resident / fuse_pose_eval_resident run ccm_fuse_sim3_eval_resident / ccm_fuse_pose_eval_resident and return the dictionaries of
 fuse_sim3.fuse_sim3_eval / fuse_pose.fuse_pose_eval; the *_host forms evaluate the same pairs on the store's shadows through csrc/fuse_math.h.
 SearchAndFuseBatchResident / SearchInNeighborsBatchResident are the mirrors' constructors on keys of a store.  set_featvec gives a key its feature vector, which
-ComputeSim3's SearchByBoW reads (bow_search.py).
+ComputeSim3's SearchByBoW reads (bow_search.py).  ingest brings the keyframes of a message into the store in one call: add without a grid, the
+vocabulary transform and set_featvec for all of them, BowVector and FeatureVector returned (ccm_kfstore_ingest).
 
 build_grid_keyframe replays KeyFrame::AssignFeaturesToGrid and KeyFrame::PosInGrid (cslam/src/KeyFrame.cpp:206-225, :265-275) line by line in Python; it shares
 nothing with csrc/kfstore_math.h, which is what the tests compare it with.
@@ -25,6 +26,7 @@ from ._lib import CcmError, Context, _p, check, host, lib
 from .fuse_sim3 import CELLS, GRID_COLS, GRID_ROWS, _c
 
 E_ARG, E_STATE = -1, -6
+KFI_MAX_FEAT = 4096   # csrc/kfingest_math.h: the most features of one keyframe of an ingest call
 
 
 class StoreError(CcmError):
@@ -51,6 +53,9 @@ def _host():
     h.ccmh_kfstore_handle.argtypes = [V]
     h.ccmh_kfstore_get.argtypes = [V, I, C.c_int64, V, V, V, V]
     h.ccmh_kfstore_set_featvec.argtypes = [V, I, C.c_int64, I, V, V, V, V]
+    h.ccmh_kfstore_ingest.argtypes = [V, I, V, I, I] + [V] * 16
+    h.ccmh_kfstore_ingest_host.argtypes = [V, I, I] + [V] * 5 + [I, I] + [V] * 16
+    h.ccmh_kfstore_shadow_equal.argtypes = [V, V, C.c_int64]      # a test aid: two stores' shadows of one key, field by field
     pts = [I] + [V] * 5
     h.ccmh_fuse_sim3_eval_resident_host.argtypes = [V, I, V, V, I, V, F, F] + pts + [V] * 4
     h.ccmh_fuse_pose_eval_resident_host.argtypes = [V, I, V, V, I, V, V, F, F] + pts + [I, V, V, V] + [V] * 4
@@ -68,6 +73,7 @@ def _dev():
     pts = [I] + [V] * 5
     l.ccm_fuse_sim3_eval_resident.argtypes = [V, V, I, V, V, I, V, F, F] + pts + [V] * 4
     l.ccm_fuse_pose_eval_resident.argtypes = [V, V, I, V, V, I, V, V, F, F] + pts + [I, V, V, V] + [V] * 4
+    l.ccm_kfstore_ingest.argtypes = [V, V, V, I, I] + [V] * 15
     return l
 
 
@@ -108,6 +114,40 @@ def build_grid_keyframe(xy, rec):
 
 def _keys(keys) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(list(keys) if not isinstance(keys, np.ndarray) else keys, np.int64).reshape(-1))
+
+
+def ingest_outputs(M: int, F: int, want_feat: bool = False):
+    """ccm_kfstore_ingest's nine output arrays (the last two None unless asked for), every one with room for one element more than the call writes"""
+    i32 = lambda n: np.zeros(n + 1, np.int32)
+    return [i32(M), i32(F), np.zeros(F + 1, np.float64), i32(M), i32(F), i32(F + M), i32(F), i32(F) if want_feat else None, i32(F) if want_feat else None]
+
+
+def tree_args(vocab):
+    """the flat tree of ccm_vocab_create from a matcher.Vocabulary or a vocabulary dictionary: (n_nodes, L and the five arrays' pointers, the arrays themselves,
+    which the caller holds for the length of the call)"""
+    if isinstance(vocab, dict):
+        dts = dict(child_off=np.int32, child_id=np.int32, node_desc=np.uint8, word_id=np.int32, weight=np.float64)
+        keep = {k: np.ascontiguousarray(vocab[k], dt) for k, dt in dts.items()}
+        n_nodes, L = int(vocab["n_nodes"]), int(vocab["L"])
+    else:
+        keep, n_nodes, L = vocab._keep, vocab.n_nodes, vocab.L
+    return [n_nodes, L] + [_p(keep[k]) for k in ("child_off", "child_id", "node_desc", "word_id", "weight")], keep
+
+
+def split_ingest(feat_off, out) -> list:
+    """ccm_kfstore_ingest's flat outputs as one dictionary per keyframe"""
+    bow_n, bow_word, bow_value, fv_nn, fv_node, fv_off, fv_idx, feat_word, feat_node = out
+    res = []
+    for m in range(bow_n.size - 1):
+        f0, f1 = int(feat_off[m]), int(feat_off[m + 1])
+        nw, nn = int(bow_n[m]), int(fv_nn[m])
+        off = fv_off[f0 + m:f0 + m + nn + 1].copy()
+        d = dict(bow_word=bow_word[f0:f0 + nw].copy(), bow_value=bow_value[f0:f0 + nw].copy(), fv_node=fv_node[f0:f0 + nn].copy(), fv_off=off,
+                 fv_idx=fv_idx[f0:f0 + int(off[-1])].copy())
+        if feat_word is not None:
+            d.update(feat_word=feat_word[f0:f1].copy(), feat_node=feat_node[f0:f1].copy())
+        res.append(d)
+    return res
 
 
 class KeyFrameStore:
@@ -158,6 +198,31 @@ class KeyFrameStore:
         rc = _host().ccmh_kfstore_set_featvec(self._h, self.device, int(key), int(nn), _p(node), _p(off), _p(idx), _p(ang))
         if rc != 0:
             raise StoreError("ccmh_kfstore_set_featvec", rc)
+
+    def ingest(self, vocab, keys, rec, feat_off, feat_xy, feat_octave, feat_desc, angle=None, levelsup: int = 4, want_feat: bool = False):
+        """The M keyframes of a message in ONE call (ccm_kfstore_ingest): add without a grid, the vocabulary transform and set_featvec for all of
+        them.  vocab: a matcher.Vocabulary (device store) or, for the host-only store, that or the vocabulary dictionary of synth.make_vocabulary.  Returns one
+        dictionary per keyframe: bow_word / bow_value (mBowVec: ascending word ids, L1-normalised) and fv_node / fv_off / fv_idx (mFeatVec, set_featvec's form);
+        with want_feat also feat_word / feat_node, the descent's result per feature."""
+        keys = _keys(keys)
+        M = int(keys.size)
+        rec, feat_off, feat_xy = _c(rec, np.float32), _c(feat_off, np.int32), _c(feat_xy, np.float32)
+        feat_octave, feat_desc = _c(feat_octave, np.uint8), _c(feat_desc, np.uint8)
+        ang = None if angle is None else np.ascontiguousarray(angle, np.float32)
+        F = int(feat_off[M]) if M > 0 and feat_off is not None and feat_off.size > M else 0
+        F = max(F, 0)
+        out = ingest_outputs(M, F, want_feat)
+        args = [int(levelsup), M, _p(keys), _p(rec), _p(feat_off), _p(feat_xy), _p(feat_octave), _p(feat_desc), _p(ang)] + [_p(x) for x in out]
+        if self.device >= 0:
+            if isinstance(vocab, dict):
+                raise CcmError("KeyFrameStore.ingest: a device store needs a matcher.Vocabulary")
+            rc = _host().ccmh_kfstore_ingest(self._h, self.device, vocab._h, *args)
+        else:
+            tree, _alive = tree_args(vocab)
+            rc = _host().ccmh_kfstore_ingest_host(self._h, *tree, *args)
+        if rc != 0:
+            raise StoreError("ccmh_kfstore_ingest", rc)
+        return split_ingest(feat_off, out)
 
     def erase(self, key: int):
         if _host().ccmh_kfstore_erase(self._h, self.device, int(key)) != 0:

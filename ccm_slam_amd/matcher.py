@@ -126,6 +126,7 @@ class Vocabulary:
     def __init__(self, ctx: Context, vocab: dict):
         self.ctx = ctx
         self._keep = {k: np.ascontiguousarray(vocab[k]) for k in ("child_off", "child_id", "node_desc", "word_id", "weight")}
+        self.n_nodes, self.L = int(vocab["n_nodes"]), int(vocab["L"])
         self._h = C.c_void_p()
         k = self._keep
         check(lib().ccm_vocab_create(ctx.handle, int(vocab["n_nodes"]), int(vocab["L"]), _p(k["child_off"]), _p(k["child_id"]), _p(k["node_desc"]),

@@ -139,7 +139,8 @@ int ccm_distinctive_descriptors(ccm_ctx* ctx, const uint8_t* desc, const int32_t
  * (a leaf has none), node_desc is n_nodes x 32 bytes, word_id / weight are per node (meaningful on leaves), L = depth.
  * Outputs per feature: word id, its weight (idf), and the node at level L - levelsup (0 when that level is <= 0).
  * BowVector accumulation / L1 normalisation and the FeatureVector map are host work on these arrays
- * (ccm_slam_amd/host: cslam::ORBVocabulary::transform; TemplatedVocabulary.h:1127-1190, BowVector.cpp:34-84).                     */
+ * (ccm_slam_amd/host: cslam::ORBVocabulary::transform; TemplatedVocabulary.h:1127-1190, BowVector.cpp:34-84); ccm_kfstore_ingest
+ * below builds both vectors on the device for the keyframes of a message.                                                        */
 typedef struct ccm_vocab ccm_vocab;
 int  ccm_vocab_create(ccm_ctx* ctx, int n_nodes, int L, const int32_t* child_off, const int32_t* child_id, const uint8_t* node_desc,
                       const int32_t* word_id, const double* weight, ccm_vocab** out);
@@ -677,6 +678,22 @@ int  ccm_kfstore_get(ccm_kfstore* store, ccm_ctx* ctx, int64_t key, int* n, int*
  * off[0] != 0, an empty node, an index outside [0, n) of the key, indices that do not ascend inside a node, a feature listed twice.  Locking is add's. */
 int  ccm_kfstore_set_featvec(ccm_kfstore* store, ccm_ctx* ctx, int64_t key, int nn, const int32_t* node /* nn */, const int32_t* off /* nn + 1 */,
                              const int32_t* idx /* off[nn] */);
+/* The M >= 0 keyframes of a message or a loaded map in ONE call: what KeyFrame::KeyFrame(ccmslam_msgs::KF*) and ProcessAfterLoad do per
+ * keyframe through ComputeBoW and AssignFeaturesToGrid.  The keyframes go into free slots with their grid built on the device (ccm_kfstore_add with cell_off ==
+ * cell_idx == NULL), every feature descends the vocabulary (ccm_bow_transform's rule, node at level L - levelsup), each keyframe's mBowVec and mFeatVec are built
+ * on the device, bit-identical to TemplatedVocabulary::transform with BowVector::addWeight / normalize (a feature whose weight is not > 0 is in neither vector;
+ * a word's value is its weights added in feature order; the norm is added in ascending word id and divided by), the feature vector is written into the slot as
+ * ccm_kfstore_set_featvec would have, and both vectors come back.  One upload (the descriptors travel once), at most three launches, one download.
+ * F = feat_off[M].  Keyframe m: bow_n[m] words and values from feat_off[m]; fv_nn[m] nodes from feat_off[m]; fv_nn[m] + 1 node offsets from feat_off[m] + m, the
+ * first 0; the nodes' features from feat_off[m].  What lies behind a keyframe's counts is written as zeros.  feat_word / feat_node (both NULL or both given): the
+ * descent's result per feature, ccm_bow_transform's word_out / node_out.
+ * Refusals leave the store and the outputs untouched: every refusal of ccm_kfstore_add without a grid; CCM_E_ARG also for a NULL vocabulary, a vocabulary on another
+ * device than the store, null output pointers, and a keyframe with more than KFI_MAX_FEAT = 4096 features (such a keyframe keeps the route ccm_bow_transform,
+ * ccm_kfstore_add, ccm_kfstore_set_featvec).  The vocabulary's device arrays are read in place; the caller's context and stream; locking is add's. */
+int  ccm_kfstore_ingest(ccm_kfstore* store, ccm_ctx* ctx, const ccm_vocab* voc, int levelsup, int M, const int64_t* keys /* M */, const float* kf_rec /* 10 M */,
+                        const int32_t* feat_off /* M + 1 */, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc, int32_t* bow_n /* M */,
+                        int32_t* bow_word /* F */, double* bow_value /* F */, int32_t* fv_nn /* M */, int32_t* fv_node /* F */, int32_t* fv_off /* F + M */,
+                        int32_t* fv_idx /* F */, int32_t* feat_word /* F or NULL */, int32_t* feat_node /* F or NULL */);
 
 /* ccm_fuse_sim3_eval / ccm_fuse_pose_eval on keyframes of the store: keyframe k of the call is the live key keys[k] (a key may appear more than once), Scw / pose
  * per k as there.  Outputs, packing, statuses, counters and refusals are those of the two calls above; additionally CCM_E_ARG, with nothing launched, for a NULL

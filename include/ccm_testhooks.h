@@ -92,6 +92,10 @@ int  ccm_debug_covis_update_small(ccm_ctx* ctx, int n_kf, int n_all, const int32
 int  ccm_debug_twoview_score(ccm_ctx* ctx, int model, int n_models, const float* M, int N, const float* xy1, const float* xy2, float sigma, float* score,
                              uint32_t* mask);
 
+/* test hook for ccm_kfstore_ingest / ccm_kfstore_set_featvec: a live key's feature vector as its slot holds it.  *nn = the node count (-1: the key has no
+ * vector); node / off / idx (nullable; room for n + 1, n + 1 and n entries, n the key's feature count) receive node[nn], off[nn + 1], idx[off[nn]]. */
+int  ccm_kfstore_debug_get_featvec(ccm_kfstore* store, ccm_ctx* ctx, int64_t key, int* nn, int32_t* node, int32_t* off, int32_t* idx);
+
 #ifdef __cplusplus
 }
 #endif
