@@ -1,7 +1,8 @@
-// bow_search_math.h — the inner lines of ORBmatcher::SearchByBoW(pKF1, pKF2, ...) (cslam/src/ORBmatcher.cpp:609-639), once, for the kernel of bowsearch.hip and for
-// the host (DESIGN.md §23): the update of (bestDist1, bestIdx2, bestDist2) by one distance, the merge of two such partial results, the packing of one result word,
-// the argument rules of ccm_kfstore_set_featvec, and the host evaluator of a whole ccm_bow_pair_eval_resident call.  Integer work throughout: host and device agree
-// bit for bit.
+// bow_search_math.h — the inner lines of ORBmatcher::SearchByBoW(pKF1, pKF2, ...) (cslam/src/ORBmatcher.cpp:609-639), once, for the form of bowsearch.hip and for
+// the host (DESIGN.md §23, §24a): the update of (bestDist1, bestIdx2, bestDist2) by one distance, the merge of two such partial results, the packing of one result word,
+// the argument rules of ccm_kfstore_set_featvec, the host walk over the common nodes of a keyframe pair that this search and tri_search_math.h's share
+// (fv_pair_walk_host; the device's is fv_pair.h's), and the host evaluator of a whole ccm_bow_pair_eval_resident call.  Integer work throughout: host and device
+// agree bit for bit.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -116,22 +117,31 @@ static inline BowBest bsm_reduce_host(const uint8_t* qdesc, const BowKf& k2, int
   return b;
 }
 
-// One job of ccm_bow_pair_eval_resident on the calling thread: table (k1.n words), *n_query, *n_dist.
-static inline void bow_job_eval_host(const BowKf& k1, const BowKf& k2, const uint8_t* live1, const uint8_t* live2, uint64_t* table, int32_t* n_query, int32_t* n_dist) {
+// One job of a search over the common nodes of two keyframes on the calling thread, for both evaluators (tri_search_math.h's too): the k1.n words zeroed, then the
+// nodes of keyframe 1 that keyframe 2 has (at position b of its list) in ascending order and, of each, the features that are queries (mask byte set, or clear, as
+// query_when_set says) in list order: word(idx1, b) gives the feature's word and advances the evaluator's counters.
+template <class Word, class Eval>
+static inline void fv_pair_walk_host(const BowKf& k1, const BowKf& k2, const uint8_t* mask1, bool query_when_set, Word* table, Eval word) {
   for (int i = 0; i < k1.n; i++) table[i] = 0;
-  *n_query = *n_dist = 0;
   for (int a = 0; a < k1.nn; a++) {
     const int b = bsm_find_node(k2.node, k2.nn, k1.node[a]);
     if (b < 0) continue;
     for (int32_t s = k1.off[a]; s < k1.off[a + 1]; s++) {
       const int idx1 = k1.idx[s];
-      if (!live1[idx1]) continue;
-      int n_live = 0;
-      const BowBest r = bsm_reduce_host(k1.desc + 32 * (size_t)idx1, k2, b, live2, nullptr, &n_live, n_dist);
-      table[idx1] = bsm_pack(n_live ? BSM_EVALUATED : BSM_NO_CANDIDATE, r, b);
-      ++*n_query;
+      if ((mask1[idx1] != 0) == query_when_set) table[idx1] = word(idx1, b);
     }
   }
+}
+
+// One job of ccm_bow_pair_eval_resident on the calling thread: table (k1.n words), *n_query, *n_dist.
+static inline void bow_job_eval_host(const BowKf& k1, const BowKf& k2, const uint8_t* live1, const uint8_t* live2, uint64_t* table, int32_t* n_query, int32_t* n_dist) {
+  *n_query = *n_dist = 0;
+  fv_pair_walk_host(k1, k2, live1, true, table, [&](int idx1, int b) {
+    int n_live = 0;
+    const BowBest r = bsm_reduce_host(k1.desc + 32 * (size_t)idx1, k2, b, live2, nullptr, &n_live, n_dist);
+    ++*n_query;
+    return bsm_pack(n_live ? BSM_EVALUATED : BSM_NO_CANDIDATE, r, b);
+  });
 }
 
 // A whole call: job j is (k1[j], k2[j]) under the masks live1 + live1_off[j], live2 + live2_off[j]; its words start at table + live1_off[j].

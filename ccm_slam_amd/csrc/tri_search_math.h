@@ -1,8 +1,9 @@
 // tri_search_math.h — the inner lines of ORBmatcher::SearchForTriangulation (cslam/src/ORBmatcher.cpp:700-852) with CheckDistEpipolarLine (:159-176), once, for the
-// kernel of trisearch.hip and for the host: the epipole gate, the epipolar line of a query and its gate, the update of (bestDist, bestIdx2) by one
+// form of trisearch.hip and for the host: the epipole gate, the epipolar line of a query and its gate, the update of (bestDist, bestIdx2) by one
 // accepted candidate, the merge of a pass behind the running result, the packing of one result word, the argument rules and the host evaluator of a whole
-// ccm_tri_search_eval_resident call.  The f32 expressions keep the reference's operand order; compile with -ffp-contract=off (a product and a sum are two roundings).
-// The reference never sets vbMatched2 (:721, :763), so a query's result depends on the query alone.
+// ccm_tri_search_eval_resident call (its walk over the common nodes is bow_search_math.h's fv_pair_walk_host).  The f32 expressions keep the reference's operand
+// order; compile with -ffp-contract=off (a product and a sum are two roundings).  The reference never sets vbMatched2 (:721, :763), so a query's result depends on
+// the query alone.
 #pragma once
 #include <math.h>
 #include "bow_search_math.h"
@@ -110,22 +111,15 @@ static inline TriBest tsm_reduce_host(const TriKf& k1, int idx1, const TriKf& k2
 // One job of ccm_tri_search_eval_resident on the calling thread: table (k1.k.n words), *n_query, *n_match, *n_dist.
 static inline void tri_job_eval_host(const TriKf& k1, const TriKf& k2, const uint8_t* has1, const uint8_t* has2, const float* epi, const TriLevels& lv, uint32_t* table,
                                      int32_t* n_query, int32_t* n_match, int32_t* n_dist) {
-  for (int i = 0; i < k1.k.n; i++) table[i] = 0;
   *n_query = *n_match = *n_dist = 0;
-  for (int a = 0; a < k1.k.nn; a++) {
-    const int b = bsm_find_node(k2.k.node, k2.k.nn, k1.k.node[a]);
-    if (b < 0) continue;
-    for (int32_t s = k1.k.off[a]; s < k1.k.off[a + 1]; s++) {
-      const int idx1 = k1.k.idx[s];
-      if (has1[idx1]) continue;
-      int n_free = 0;
-      const TriBest r = tsm_reduce_host(k1, idx1, k2, b, has2, epi, lv, &n_free);
-      table[idx1] = tsm_pack(r.idx >= 0 ? TSM_MATCHED : TSM_NO_MATCH, r);
-      ++*n_query;
-      *n_match += r.idx >= 0;
-      *n_dist = (int32_t)((uint32_t)*n_dist + (uint32_t)n_free);   // wraps as the kernel's unsigned add does
-    }
-  }
+  fv_pair_walk_host(k1.k, k2.k, has1, false, table, [&](int idx1, int b) {
+    int n_free = 0;
+    const TriBest r = tsm_reduce_host(k1, idx1, k2, b, has2, epi, lv, &n_free);
+    ++*n_query;
+    *n_match += r.idx >= 0;
+    *n_dist = (int32_t)((uint32_t)*n_dist + (uint32_t)n_free);   // wraps as the kernel's unsigned add does
+    return tsm_pack(r.idx >= 0 ? TSM_MATCHED : TSM_NO_MATCH, r);
+  });
 }
 
 // A whole call: job j is (k1[j], k2[j]) under the masks has1 + has1_off[j], has2 + has2_off[j] and the floats job_epi + 11 j; its words start at table + has1_off[j].

@@ -128,6 +128,27 @@ void threeMaxima(const std::vector<int>* histo, int L, int& ind1, int& ind2, int
   if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
   else if (max3 < 0.1f * (float)max1) ind3 = -1;
 }
+int histBin(float rot) {
+  if (rot < 0.0) rot += 360.0f;
+  int bin = (int)std::round(rot * (1.0f / ORBmatcher::HISTO_LENGTH));   // upstream quirk: 30-degree bins (:1358)
+  if (bin == ORBmatcher::HISTO_LENGTH) bin = 0;
+  return bin;
+}
+// The rotation-consistency filter of every search: a match is added under the difference of its two keypoints' angles, and the matches of every bin but the three
+// fullest are rejected, bins ascending, a bin's matches in the order they were added.
+struct RotationFilter {
+  std::vector<int> hist[ORBmatcher::HISTO_LENGTH];
+  void add(float rot, int index) { hist[histBin(rot)].push_back(index); }
+  template <class Reject>
+  void reject_outliers(Reject reject) const {
+    int ind1 = -1, ind2 = -1, ind3 = -1;
+    threeMaxima(hist, ORBmatcher::HISTO_LENGTH, ind1, ind2, ind3);
+    for (int i = 0; i < ORBmatcher::HISTO_LENGTH; i++) {
+      if (i == ind1 || i == ind2 || i == ind3) continue;
+      for (int k : hist[i]) reject(k);
+    }
+  }
+};
 }  // namespace
 
 int ORBmatcher::DescriptorDistance(const uint8_t* a, const uint8_t* b) {
@@ -279,8 +300,7 @@ int ORBmatcher::SearchByProjection(FrameView& C, const LastFrameProjections& las
   }
   const int Q = (int)q_of.size();
   int nmatches = 0;
-  std::vector<int> rotHist[HISTO_LENGTH];
-  const float factor = 1.0f / HISTO_LENGTH;   // upstream quirk: 30-degree bins (:1358)
+  RotationFilter rot;
   if (Q > 0) {
     std::vector<uint16_t> dist(idx.size());
     check(ccm_hamming_csr(ctx_.get(), qdesc.data(), Q, C.mDescriptors, C.N, off.data(), idx.data(), dist.data(), nullptr, nullptr, nullptr),
@@ -295,23 +315,11 @@ int ORBmatcher::SearchByProjection(FrameView& C, const LastFrameProjections& las
       if (bestDist <= TH_HIGH) {
         C.mvpMapPoints[bestIdx2] = q_of[q];
         nmatches++;
-        if (mbCheckOrientation) {
-          float rot = last.angle[q_of[q]] - C.mvKeysUn[bestIdx2].angle;
-          if (rot < 0.0) rot += 360.0f;
-          int bin = (int)std::round(rot * factor);
-          if (bin == HISTO_LENGTH) bin = 0;
-          rotHist[bin].push_back(bestIdx2);
-        }
+        if (mbCheckOrientation) rot.add(last.angle[q_of[q]] - C.mvKeysUn[bestIdx2].angle, bestIdx2);
       }
     }
   }
-  if (mbCheckOrientation) {
-    int ind1 = -1, ind2 = -1, ind3 = -1;
-    threeMaxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
-    for (int i = 0; i < HISTO_LENGTH; i++)
-      if (i != ind1 && i != ind2 && i != ind3)
-        for (int k : rotHist[i]) { C.mvpMapPoints[k] = -1; nmatches--; }
-  }
+  if (mbCheckOrientation) rot.reject_outliers([&](int k) { C.mvpMapPoints[k] = -1; nmatches--; });
   return nmatches;
 }
 
@@ -330,8 +338,7 @@ int ORBmatcher::SearchByProjection(FrameGridDev& grid, FrameView& C, const LastF
   }
   const int Q = (int)q_of.size();
   int nmatches = 0;
-  std::vector<int> rotHist[HISTO_LENGTH];
-  const float factor = 1.0f / HISTO_LENGTH;   // upstream quirk: 30-degree bins (:1358)
+  RotationFilter rot;
   if (Q > 0) {
     std::vector<int32_t> off, idx;
     std::vector<uint16_t> dist;
@@ -346,23 +353,11 @@ int ORBmatcher::SearchByProjection(FrameGridDev& grid, FrameView& C, const LastF
       if (bestDist <= TH_HIGH) {
         C.mvpMapPoints[bestIdx2] = q_of[q];
         nmatches++;
-        if (mbCheckOrientation) {
-          float rot = last.angle[q_of[q]] - C.mvKeysUn[bestIdx2].angle;
-          if (rot < 0.0) rot += 360.0f;
-          int bin = (int)std::round(rot * factor);
-          if (bin == HISTO_LENGTH) bin = 0;
-          rotHist[bin].push_back(bestIdx2);
-        }
+        if (mbCheckOrientation) rot.add(last.angle[q_of[q]] - C.mvKeysUn[bestIdx2].angle, bestIdx2);
       }
     }
   }
-  if (mbCheckOrientation) {
-    int ind1 = -1, ind2 = -1, ind3 = -1;
-    threeMaxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
-    for (int i = 0; i < HISTO_LENGTH; i++)
-      if (i != ind1 && i != ind2 && i != ind3)
-        for (int k : rotHist[i]) { C.mvpMapPoints[k] = -1; nmatches--; }
-  }
+  if (mbCheckOrientation) rot.reject_outliers([&](int k) { C.mvpMapPoints[k] = -1; nmatches--; });
   return nmatches;
 }
 
@@ -378,12 +373,6 @@ std::vector<std::pair<int, int>> commonNodes(const FeatureVectorView& a, const F
     else j = (int)(std::lower_bound(b.node, b.node + b.nn, a.node[i]) - b.node);
   }
   return r;
-}
-int histBin(float rot) {
-  if (rot < 0.0) rot += 360.0f;
-  int bin = (int)std::round(rot * (1.0f / ORBmatcher::HISTO_LENGTH));
-  if (bin == ORBmatcher::HISTO_LENGTH) bin = 0;
-  return bin;
 }
 // queries = features of `a` in bucket order that pass `keep`; candidate list of each = the whole bucket of `b`
 template <typename Keep>
@@ -415,7 +404,7 @@ int ORBmatcher::SearchByBoW(const KeysView& KF, const KeysView& F, std::vector<i
   std::vector<int32_t> q_of, off, idx; std::vector<uint8_t> qdesc; std::vector<uint16_t> dist;
   bucketQueries(KF, F, [&](int i) { return KF.hasMapPoint[i] != 0; }, q_of, off, idx, qdesc);
   distances(qdesc, (int)q_of.size(), F.desc, F.N, off, idx, dist);
-  std::vector<int> rotHist[HISTO_LENGTH];
+  RotationFilter rot;
   int nmatches = 0;
   for (size_t q = 0; q < q_of.size(); q++) {
     int bestDist1 = 256, bestIdxF = -1, bestDist2 = 256;
@@ -428,18 +417,11 @@ int ORBmatcher::SearchByBoW(const KeysView& KF, const KeysView& F, std::vector<i
     }
     if (bestDist1 <= TH_LOW && static_cast<float>(bestDist1) < mfNNratio * static_cast<float>(bestDist2)) {
       matchesF[bestIdxF] = q_of[q];
-      if (mbCheckOrientation) rotHist[histBin(KF.keys[q_of[q]].angle - F.keys[bestIdxF].angle)].push_back(bestIdxF);
+      if (mbCheckOrientation) rot.add(KF.keys[q_of[q]].angle - F.keys[bestIdxF].angle, bestIdxF);
       nmatches++;
     }
   }
-  if (mbCheckOrientation) {
-    int ind1 = -1, ind2 = -1, ind3 = -1;
-    threeMaxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
-    for (int i = 0; i < HISTO_LENGTH; i++) {
-      if (i == ind1 || i == ind2 || i == ind3) continue;
-      for (int k : rotHist[i]) { matchesF[k] = -1; nmatches--; }
-    }
-  }
+  if (mbCheckOrientation) rot.reject_outliers([&](int k) { matchesF[k] = -1; nmatches--; });
   return nmatches;
 }
 
@@ -449,7 +431,7 @@ int ORBmatcher::SearchByBoW_KF(const KeysView& K1, const KeysView& K2, std::vect
   bucketQueries(K1, K2, [&](int i) { return K1.hasMapPoint[i] != 0; }, q_of, off, idx, qdesc);
   distances(qdesc, (int)q_of.size(), K2.desc, K2.N, off, idx, dist);
   std::vector<char> vbMatched2(K2.N, 0);
-  std::vector<int> rotHist[HISTO_LENGTH];
+  RotationFilter rot;
   int nmatches = 0;
   for (size_t q = 0; q < q_of.size(); q++) {
     int bestDist1 = 256, bestIdx2 = -1, bestDist2 = 256;
@@ -463,18 +445,11 @@ int ORBmatcher::SearchByBoW_KF(const KeysView& K1, const KeysView& K2, std::vect
     if (bestDist1 < TH_LOW && static_cast<float>(bestDist1) < mfNNratio * static_cast<float>(bestDist2)) {   // strict '<' here (:641)
       matches12[q_of[q]] = bestIdx2;
       vbMatched2[bestIdx2] = 1;
-      if (mbCheckOrientation) rotHist[histBin(K1.keys[q_of[q]].angle - K2.keys[bestIdx2].angle)].push_back(q_of[q]);
+      if (mbCheckOrientation) rot.add(K1.keys[q_of[q]].angle - K2.keys[bestIdx2].angle, q_of[q]);
       nmatches++;
     }
   }
-  if (mbCheckOrientation) {
-    int ind1 = -1, ind2 = -1, ind3 = -1;
-    threeMaxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
-    for (int i = 0; i < HISTO_LENGTH; i++) {
-      if (i == ind1 || i == ind2 || i == ind3) continue;
-      for (int k : rotHist[i]) { matches12[k] = -1; nmatches--; }
-    }
-  }
+  if (mbCheckOrientation) rot.reject_outliers([&](int k) { matches12[k] = -1; nmatches--; });
   return nmatches;
 }
 
@@ -485,9 +460,9 @@ namespace {
 int resolveTriangulation(const KeyPoint* keys1, int N1, const uint8_t* has1, const KeyPoint* keys2, const uint8_t* has2, const std::vector<int32_t>& q_of,
                          const std::vector<int32_t>& off, const std::vector<int32_t>& idx, const uint16_t* dist, const float F12[9], float ex, float ey,
                          const float* sigma2_2, const float* sf2, bool checkOrientation, std::vector<int32_t>& matches12) {
-  const int TH_LOW = ORBmatcher::TH_LOW, HISTO_LENGTH = ORBmatcher::HISTO_LENGTH;
+  const int TH_LOW = ORBmatcher::TH_LOW;
   matches12.assign(N1, -1);
-  std::vector<int> rotHist[ORBmatcher::HISTO_LENGTH];
+  RotationFilter rot;
   int nmatches = 0;
   for (size_t q = 0; q < q_of.size(); q++) {
     if (has1 && has1[q_of[q]]) continue;
@@ -514,17 +489,10 @@ int resolveTriangulation(const KeyPoint* keys1, int N1, const uint8_t* has1, con
     if (bestIdx2 >= 0) {
       matches12[q_of[q]] = bestIdx2;
       nmatches++;
-      if (checkOrientation) rotHist[histBin(kp1.angle - keys2[bestIdx2].angle)].push_back(q_of[q]);
+      if (checkOrientation) rot.add(kp1.angle - keys2[bestIdx2].angle, q_of[q]);
     }
   }
-  if (checkOrientation) {
-    int ind1 = -1, ind2 = -1, ind3 = -1;
-    threeMaxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
-    for (int i = 0; i < HISTO_LENGTH; i++) {
-      if (i == ind1 || i == ind2 || i == ind3) continue;
-      for (int k : rotHist[i]) { matches12[k] = -1; nmatches--; }
-    }
-  }
+  if (checkOrientation) rot.reject_outliers([&](int k) { matches12[k] = -1; nmatches--; });
   return nmatches;
 }
 }  // namespace
@@ -590,7 +558,7 @@ int ORBmatcher::SearchForInitialization(const KeysView& F1, const FrameView& F2,
     qdesc.insert(qdesc.end(), F1.desc + (size_t)i1 * 32, F1.desc + (size_t)i1 * 32 + 32);
   }
   distances(qdesc, (int)q_of.size(), F2.mDescriptors, F2.N, off, idx, dist);
-  std::vector<int> rotHist[HISTO_LENGTH];
+  RotationFilter rot;
   std::vector<int> vMatchedDistance(F2.N, INT32_MAX), vnMatches21(F2.N, -1);
   int nmatches = 0;
   for (size_t q = 0; q < q_of.size(); q++) {
@@ -609,17 +577,10 @@ int ORBmatcher::SearchForInitialization(const KeysView& F1, const FrameView& F2,
       vnMatches21[bestIdx2] = i1;
       vMatchedDistance[bestIdx2] = bestDist;
       nmatches++;
-      if (mbCheckOrientation) rotHist[histBin(F1.keys[i1].angle - F2.mvKeysUn[bestIdx2].angle)].push_back(i1);
+      if (mbCheckOrientation) rot.add(F1.keys[i1].angle - F2.mvKeysUn[bestIdx2].angle, i1);
     }
   }
-  if (mbCheckOrientation) {
-    int ind1 = -1, ind2 = -1, ind3 = -1;
-    threeMaxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
-    for (int i = 0; i < HISTO_LENGTH; i++) {
-      if (i == ind1 || i == ind2 || i == ind3) continue;
-      for (int idx1 : rotHist[i]) if (vnMatches12[idx1] >= 0) { vnMatches12[idx1] = -1; nmatches--; }
-    }
-  }
+  if (mbCheckOrientation) rot.reject_outliers([&](int idx1) { if (vnMatches12[idx1] >= 0) { vnMatches12[idx1] = -1; nmatches--; } });
   for (int i1 = 0; i1 < F1.N; i1++)
     if (vnMatches12[i1] >= 0) { prev[2 * i1] = F2.mvKeysUn[vnMatches12[i1]].x; prev[2 * i1 + 1] = F2.mvKeysUn[vnMatches12[i1]].y; }
   return nmatches;
@@ -2494,22 +2455,51 @@ SearchBySim3Batch::SearchBySim3Batch(KeyFrameStore& store, HipContext* ctx, int6
 // ---- ComputeSim3's SearchByBoW for all candidates: the host evaluator on the shadows, SearchByBoWBatch ---------------------------------
 static BowKf bow_kf(const KfShadow& kf) { return {kf.n, (int)kf.fv_node.size(), kf.fv_node.data(), kf.fv_off.data(), kf.fv_idx.data(), kf.desc.data()}; }
 
+// What bow_pair_eval_resident_host and tri_search_eval_resident_host check alike behind their own scalar rules, in the order and with the rules of the device stage
+// (csrc/fv_pair.h): the pointers, both key lists' shadows (a, b), the feature vectors, the two mask arrays against the shadows' feature counts, the table.  false
+// where the entry returns CCM_E_ARG.
+static bool fv_pair_front_host(const KeyFrameStore& store, int J, const int64_t* key1, const int64_t* key2, const int32_t* off1, const uint8_t* mask1, const int32_t* off2,
+                               const uint8_t* mask2, const void* table, bool counters, Shadows& a, Shadows& b) {
+  if (!key1 || !key2 || !off1 || !off2 || !counters) return false;
+  if (!store_shadows(store, J, key1, a) || !store_shadows(store, J, key2, b)) return false;
+  std::vector<int32_t> n1((size_t)J), n2((size_t)J);
+  for (int j = 0; j < J; j++) {
+    if (!a[j]->has_fv || !b[j]->has_fv) return false;
+    n1[j] = a[j]->n; n2[j] = b[j]->n;
+  }
+  if (bsm_check_masks(J, off1, mask1, n1.data()) || bsm_check_masks(J, off2, mask2, n2.data())) return false;
+  return off1[J] == 0 || table;
+}
+
+// What SearchByBoWBatch and SearchForTriangulationBatch build alike for their one call: key1 and its mask once per candidate, the candidates' own masks one after the
+// other, and the offsets of both.  Throws for a key without a feature vector and for a missing mask.
+struct FvPairMasks { std::vector<int64_t> k1; std::vector<int32_t> off1, off2; std::vector<uint8_t> m1, m2; };
+static FvPairMasks fv_pair_masks(const std::string& who, int64_t key1, const KfShadow& K1, int C, const Shadows& kfs2, const uint8_t* mask1, const uint8_t* const* mask2) {
+  if (!K1.has_fv) throw infrastructure_ex(who + ": a key without a feature vector");
+  const int N1 = K1.n;
+  if (N1 > 0 && !mask1) throw infrastructure_ex(who + ": bad arguments");
+  FvPairMasks m{std::vector<int64_t>((size_t)C, key1), std::vector<int32_t>((size_t)C + 1, 0), std::vector<int32_t>((size_t)C + 1, 0), {}, {}};
+  for (int j = 0; j < C; j++) {
+    if (!kfs2[j]->has_fv) throw infrastructure_ex(who + ": a key without a feature vector");
+    if (kfs2[j]->n > 0 && !mask2[j]) throw infrastructure_ex(who + ": bad arguments");
+    m.off1[j + 1] = m.off1[j] + N1; m.off2[j + 1] = m.off2[j] + kfs2[j]->n;
+  }
+  m.m1.resize((size_t)m.off1[C]); m.m2.resize((size_t)m.off2[C]);
+  for (int j = 0; j < C; j++) {
+    if (N1) std::memcpy(m.m1.data() + m.off1[j], mask1, (size_t)N1);
+    if (kfs2[j]->n) std::memcpy(m.m2.data() + m.off2[j], mask2[j], (size_t)kfs2[j]->n);
+  }
+  return m;
+}
+
 int bow_pair_eval_resident_host(const KeyFrameStore& store, int J, const int64_t* key1, const int64_t* key2, const int32_t* live1_off, const uint8_t* live1,
                                 const int32_t* live2_off, const uint8_t* live2, uint64_t* table, int32_t* n_query, int32_t* n_dist) {
   if (J < 0) return -1;
   if (J == 0) return 0;
-  if (!key1 || !key2 || !live1_off || !live2_off || !n_query || !n_dist) return -1;
-  std::vector<std::shared_ptr<const KfShadow>> a, b;
-  if (!store_shadows(store, J, key1, a) || !store_shadows(store, J, key2, b)) return -1;
-  std::vector<int32_t> n1((size_t)J), n2((size_t)J);
+  Shadows a, b;
+  if (!fv_pair_front_host(store, J, key1, key2, live1_off, live1, live2_off, live2, table, n_query && n_dist, a, b)) return -1;
   std::vector<BowKf> k1((size_t)J), k2((size_t)J);
-  for (int j = 0; j < J; j++) {
-    if (!a[j]->has_fv || !b[j]->has_fv) return -1;
-    n1[j] = a[j]->n; n2[j] = b[j]->n;
-    k1[j] = bow_kf(*a[j]); k2[j] = bow_kf(*b[j]);
-  }
-  if (bsm_check_masks(J, live1_off, live1, n1.data()) || bsm_check_masks(J, live2_off, live2, n2.data())) return -1;
-  if (live1_off[J] > 0 && !table) return -1;
+  for (int j = 0; j < J; j++) { k1[j] = bow_kf(*a[j]); k2[j] = bow_kf(*b[j]); }
   bow_pair_eval_host(J, k1.data(), k2.data(), live1_off, live1, live2_off, live2, table, n_query, n_dist);
   return 0;
 }
@@ -2517,46 +2507,32 @@ int bow_pair_eval_resident_host(const KeyFrameStore& store, int J, const int64_t
 SearchByBoWBatch::SearchByBoWBatch(KeyFrameStore& store, HipContext* ctx, int64_t key1, int C, const int64_t* keys2, const uint8_t* live1, const uint8_t* const* live2,
                                    float nnratio, bool checkOrientation) {
   if (C < 0 || (C > 0 && (!keys2 || !live2))) throw infrastructure_ex("SearchByBoWBatch: bad arguments");
-  std::vector<std::shared_ptr<const KfShadow>> kf1, kfs2;
+  Shadows kf1, kfs2;
   if (!store_shadows(store, 1, &key1, kf1) || !store_shadows(store, C, keys2, kfs2)) throw infrastructure_ex("SearchByBoWBatch: a key is not in the store");
   const KfShadow& K1 = *kf1[0];
-  if (!K1.has_fv) throw infrastructure_ex("SearchByBoWBatch: a key without a feature vector");
+  const FvPairMasks m = fv_pair_masks("SearchByBoWBatch", key1, K1, C, kfs2, live1, live2);   // live1 once per candidate, the candidates' own one after the other
   const int N1 = K1.n;
-  if (N1 > 0 && !live1) throw infrastructure_ex("SearchByBoWBatch: bad arguments");
-  // the masks of the call: live1 once per candidate, the candidates' own one after the other
-  std::vector<int64_t> k1((size_t)C, key1);
-  std::vector<int32_t> off1((size_t)C + 1, 0), off2((size_t)C + 1, 0);
-  for (int j = 0; j < C; j++) {
-    if (!kfs2[j]->has_fv) throw infrastructure_ex("SearchByBoWBatch: a key without a feature vector");
-    if (kfs2[j]->n > 0 && !live2[j]) throw infrastructure_ex("SearchByBoWBatch: bad arguments");
-    off1[j + 1] = off1[j] + N1; off2[j + 1] = off2[j] + kfs2[j]->n;
-  }
-  std::vector<uint8_t> m1((size_t)off1[C]), m2((size_t)off2[C]);
-  for (int j = 0; j < C; j++) {
-    if (N1) std::memcpy(m1.data() + off1[j], live1, (size_t)N1);
-    if (kfs2[j]->n) std::memcpy(m2.data() + off2[j], live2[j], (size_t)kfs2[j]->n);
-  }
-  table_.assign((size_t)off1[C], 0); n_query_.assign((size_t)C, 0); n_dist_.assign((size_t)C, 0);
+  table_.assign((size_t)m.off1[C], 0); n_query_.assign((size_t)C, 0); n_dist_.assign((size_t)C, 0);
   if (C > 0 && !store.host_only() && ctx) {
-    check(ccm_bow_pair_eval_resident(ctx->get(), store.handle(), C, k1.data(), keys2, off1.data(), m1.data(), off2.data(), m2.data(), table_.data(), n_query_.data(),
+    check(ccm_bow_pair_eval_resident(ctx->get(), store.handle(), C, m.k1.data(), keys2, m.off1.data(), m.m1.data(), m.off2.data(), m.m2.data(), table_.data(), n_query_.data(),
                                      n_dist_.data()),
           ctx->get(), "ccm_bow_pair_eval_resident");
-  } else if (bow_pair_eval_resident_host(store, C, k1.data(), keys2, off1.data(), m1.data(), off2.data(), m2.data(), table_.data(), n_query_.data(), n_dist_.data())) {
+  } else if (bow_pair_eval_resident_host(store, C, m.k1.data(), keys2, m.off1.data(), m.m1.data(), m.off2.data(), m.m2.data(), table_.data(), n_query_.data(), n_dist_.data())) {
     throw infrastructure_ex("SearchByBoWBatch: bad arguments");
   }
   // the reference's loop per candidate (:585-698) on the words
-  const int TH_LOW = ORBmatcher::TH_LOW, HISTO_LENGTH = ORBmatcher::HISTO_LENGTH;
+  const int TH_LOW = ORBmatcher::TH_LOW;
   nmatches_.assign((size_t)C, 0); matches12_.resize((size_t)C);
   std::vector<int> claimed;   // the features of keyframe 2 claimed so far in the node at hand
   for (int j = 0; j < C; j++) {
     const KfShadow& K2 = *kfs2[j];
     const BowKf b2 = bow_kf(K2);
-    const uint64_t* words = table_.data() + off1[j];
-    const uint8_t* l2 = m2.data() + off2[j];
+    const uint64_t* words = table_.data() + m.off1[j];
+    const uint8_t* l2 = m.m2.data() + m.off2[j];
     std::vector<int32_t>& matches12 = matches12_[(size_t)j];
     matches12.assign((size_t)N1, -1);
     std::vector<uint8_t> vbMatched2((size_t)K2.n, 0);
-    std::vector<int> rotHist[ORBmatcher::HISTO_LENGTH];
+    RotationFilter rot;
     int nmatches = 0;
     for (size_t a = 0; a < K1.fv_node.size(); a++) {   // ascending nodes of keyframe 1; those keyframe 2 lacks hold no query
       claimed.clear();
@@ -2579,19 +2555,12 @@ SearchByBoWBatch::SearchByBoWBatch(KeyFrameStore& store, HipContext* ctx, int64_
           matches12[(size_t)idx1] = r.idx;
           vbMatched2[(size_t)r.idx] = 1;
           claimed.push_back(r.idx);
-          if (checkOrientation) rotHist[histBin(K1.angle[(size_t)idx1] - K2.angle[(size_t)r.idx])].push_back(idx1);
+          if (checkOrientation) rot.add(K1.angle[(size_t)idx1] - K2.angle[(size_t)r.idx], idx1);
           nmatches++;
         }
       }
     }
-    if (checkOrientation) {
-      int ind1 = -1, ind2 = -1, ind3 = -1;
-      threeMaxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
-      for (int i = 0; i < HISTO_LENGTH; i++) {
-        if (i == ind1 || i == ind2 || i == ind3) continue;
-        for (int k : rotHist[i]) { matches12[(size_t)k] = -1; nmatches--; }
-      }
-    }
+    if (checkOrientation) rot.reject_outliers([&](int k) { matches12[(size_t)k] = -1; nmatches--; });
     nmatches_[(size_t)j] = nmatches;
   }
 }
@@ -2604,18 +2573,10 @@ int tri_search_eval_resident_host(const KeyFrameStore& store, int J, const int64
                                   uint32_t* table, int32_t* n_query, int32_t* n_match, int32_t* n_dist) {
   if (J < 0 || tsm_check_args(J, job_epi, nlevels, scale_factors, level_sigma2)) return -1;
   if (J == 0) return 0;
-  if (!key1 || !key2 || !has1_off || !has2_off || !n_query || !n_match || !n_dist) return -1;
-  std::vector<std::shared_ptr<const KfShadow>> a, b;
-  if (!store_shadows(store, J, key1, a) || !store_shadows(store, J, key2, b)) return -1;
-  std::vector<int32_t> n1((size_t)J), n2((size_t)J);
+  Shadows a, b;
+  if (!fv_pair_front_host(store, J, key1, key2, has1_off, has1, has2_off, has2, table, n_query && n_match && n_dist, a, b)) return -1;
   std::vector<TriKf> k1((size_t)J), k2((size_t)J);
-  for (int j = 0; j < J; j++) {
-    if (!a[j]->has_fv || !b[j]->has_fv) return -1;
-    n1[j] = a[j]->n; n2[j] = b[j]->n;
-    k1[j] = tri_kf(*a[j]); k2[j] = tri_kf(*b[j]);
-  }
-  if (bsm_check_masks(J, has1_off, has1, n1.data()) || bsm_check_masks(J, has2_off, has2, n2.data())) return -1;
-  if (has1_off[J] > 0 && !table) return -1;
+  for (int j = 0; j < J; j++) { k1[j] = tri_kf(*a[j]); k2[j] = tri_kf(*b[j]); }
   tri_search_eval_host(J, k1.data(), k2.data(), has1_off, has1, has2_off, has2, job_epi, TriLevels{nlevels, scale_factors, level_sigma2}, table, n_query, n_match, n_dist);
   return 0;
 }
@@ -2626,37 +2587,24 @@ SearchForTriangulationBatch::SearchForTriangulationBatch(KeyFrameStore& store, H
     : nlevels_(nlevels), check_ori_(checkOrientation) {
   const char* const bad = "SearchForTriangulationBatch: bad arguments";
   if (C < 0 || (C > 0 && (!keys2 || !has2 || !ep)) || nlevels < 1 || nlevels > TSM_MAX_LEVELS || !sigma2_2 || !sf2) throw infrastructure_ex(bad);
-  std::vector<std::shared_ptr<const KfShadow>> kf1;
+  Shadows kf1;
   if (!store_shadows(store, 1, &key1, kf1) || !store_shadows(store, C, keys2, kfs2_)) throw infrastructure_ex("SearchForTriangulationBatch: a key is not in the store");
   kf1_ = kf1[0];
-  if (!kf1_->has_fv) throw infrastructure_ex("SearchForTriangulationBatch: a key without a feature vector");
-  const int N1 = kf1_->n;
-  if (N1 > 0 && !has1) throw infrastructure_ex(bad);
+  FvPairMasks m = fv_pair_masks("SearchForTriangulationBatch", key1, *kf1_, C, kfs2_, has1, has2);   // has1 once per neighbour, the neighbours' own one after the other
   sigma2_.assign(sigma2_2, sigma2_2 + nlevels); sf_.assign(sf2, sf2 + nlevels);
-  // the masks of the call: has1 once per neighbour, the neighbours' own one after the other
-  std::vector<int64_t> k1((size_t)C, key1);
-  off1_.assign((size_t)C + 1, 0); off2_.assign((size_t)C + 1, 0);
-  for (int j = 0; j < C; j++) {
-    if (!kfs2_[j]->has_fv) throw infrastructure_ex("SearchForTriangulationBatch: a key without a feature vector");
-    if (kfs2_[j]->n > 0 && !has2[j]) throw infrastructure_ex(bad);
-    off1_[j + 1] = off1_[j] + N1; off2_[j + 1] = off2_[j] + kfs2_[j]->n;
-  }
-  has1_.assign(has1, has1 + N1);
-  std::vector<uint8_t> m1((size_t)off1_[C]);
-  has2_.resize((size_t)off2_[C]);
+  has1_.assign(has1, has1 + kf1_->n);
+  off1_ = std::move(m.off1); off2_ = std::move(m.off2); has2_ = std::move(m.m2);
   epi_.resize((size_t)TSM_EPI_FLOATS * (size_t)C);
   for (int j = 0; j < C; j++) {
-    if (N1) std::memcpy(m1.data() + off1_[j], has1, (size_t)N1);
-    if (kfs2_[j]->n) std::memcpy(has2_.data() + off2_[j], has2[j], (size_t)kfs2_[j]->n);
     std::memcpy(epi_.data() + TSM_EPI_FLOATS * (size_t)j, ep[j].F12, 9 * sizeof(float));
     epi_[TSM_EPI_FLOATS * (size_t)j + 9] = ep[j].ex; epi_[TSM_EPI_FLOATS * (size_t)j + 10] = ep[j].ey;
   }
   table_.assign((size_t)off1_[C], 0); n_query_.assign((size_t)C, 0); n_match_.assign((size_t)C, 0); n_dist_.assign((size_t)C, 0);
   if (C > 0 && !store.host_only() && ctx) {
-    check(ccm_tri_search_eval_resident(ctx->get(), store.handle(), C, k1.data(), keys2, off1_.data(), m1.data(), off2_.data(), has2_.data(), epi_.data(), nlevels,
+    check(ccm_tri_search_eval_resident(ctx->get(), store.handle(), C, m.k1.data(), keys2, off1_.data(), m.m1.data(), off2_.data(), has2_.data(), epi_.data(), nlevels,
                                        sf_.data(), sigma2_.data(), table_.data(), n_query_.data(), n_match_.data(), n_dist_.data()),
           ctx->get(), "ccm_tri_search_eval_resident");
-  } else if (tri_search_eval_resident_host(store, C, k1.data(), keys2, off1_.data(), m1.data(), off2_.data(), has2_.data(), epi_.data(), nlevels, sf_.data(),
+  } else if (tri_search_eval_resident_host(store, C, m.k1.data(), keys2, off1_.data(), m.m1.data(), off2_.data(), has2_.data(), epi_.data(), nlevels, sf_.data(),
                                            sigma2_.data(), table_.data(), n_query_.data(), n_match_.data(), n_dist_.data())) {
     throw infrastructure_ex(bad);
   }
@@ -2672,9 +2620,8 @@ int SearchForTriangulationBatch::resolve(int j, const uint8_t* has1_now, const u
   const uint8_t* h1 = has1_now ? has1_now : has1_.data();
   const uint8_t* h2 = has2_now ? has2_now : h2_build;
   const float* epi = epi_.data() + TSM_EPI_FLOATS * (size_t)j;
-  const int HISTO_LENGTH = ORBmatcher::HISTO_LENGTH;
   matches12.assign((size_t)K1.n, -1);
-  std::vector<int> rotHist[ORBmatcher::HISTO_LENGTH];
+  RotationFilter rot;
   int nmatches = 0;
   for (size_t a = 0; a < K1.fv_node.size(); a++) {   // ascending nodes of keyframe 1; those keyframe 2 lacks hold no query
     const int b = bsm_find_node(t2.k.node, t2.k.nn, K1.fv_node[a]);
@@ -2699,18 +2646,11 @@ int SearchForTriangulationBatch::resolve(int j, const uint8_t* has1_now, const u
       if (r.idx >= 0) {   // :787-804
         matches12[(size_t)idx1] = r.idx;
         nmatches++;
-        if (check_ori_) rotHist[histBin(K1.angle[(size_t)idx1] - K2.angle[(size_t)r.idx])].push_back(idx1);
+        if (check_ori_) rot.add(K1.angle[(size_t)idx1] - K2.angle[(size_t)r.idx], idx1);
       }
     }
   }
-  if (check_ori_) {
-    int ind1 = -1, ind2 = -1, ind3 = -1;
-    threeMaxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
-    for (int i = 0; i < HISTO_LENGTH; i++) {
-      if (i == ind1 || i == ind2 || i == ind3) continue;
-      for (int k : rotHist[i]) { matches12[(size_t)k] = -1; nmatches--; }
-    }
-  }
+  if (check_ori_) rot.reject_outliers([&](int k) { matches12[(size_t)k] = -1; nmatches--; });
   return nmatches;
 }
 
