@@ -22,6 +22,19 @@ struct Sim3RansacBlock : StagedBlock {
   StagedSeg<uint32_t> mask = add<uint32_t>(words, SB_OUT);
 };
 
+// ccm_pnp_ransac_eval: the intrinsics (f64) lead the inputs and the poses (f64) the outputs; four sample indices per hypothesis.
+struct PnpRansacBlock : StagedBlock {
+  const size_t K, Nt, H, words;
+  PnpRansacBlock(size_t K, size_t Nt, size_t H, size_t words) : K(K), Nt(Nt), H(H), words(words) {}
+  StagedSeg<double> cam = add<double>(4 * K, SB_COPY);
+  StagedSeg<int32_t> pt_off = add<int32_t>(K + 1, SB_COPY);
+  StagedSeg<float> P3Dw = add<float>(3 * Nt, SB_COPY), P2D = add<float>(2 * Nt, SB_COPY), max_err = add<float>(Nt, SB_COPY);
+  StagedSeg<int32_t> hyp_cand = add<int32_t>(H, SB_COPY), hyp_idx = add<int32_t>(4 * H, SB_COPY), mask_off = add<int32_t>(H + 1, SB_COPY);
+  StagedSeg<double> Rt = add<double>(12 * H, SB_OUT);
+  StagedSeg<int32_t> n_inl = add<int32_t>(H, SB_OUT);
+  StagedSeg<uint32_t> mask = add<uint32_t>(words, SB_OUT);
+};
+
 // ccm_triangulate_pairs: the inputs, then the outputs.  xy comes first and on 16 bytes for the kernel's float4 reads; the outputs start on 16 bytes as well.
 struct TriBlock : StagedBlock {
   const size_t P, S, L;

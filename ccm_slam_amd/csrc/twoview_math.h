@@ -92,15 +92,22 @@ TV_HD void tv_normalize(const float* xy, int n, float* pn, float* T) {
 // ---- JacobiSVDImpl_<float> (lapack.cpp) ---------------------------------------------------------------------------------------------------------
 // At: NR rows of M floats, the first N of them the rows of the problem (NR = max(N, n1)); Vt: N x N or nullptr where nobody reads it (the rows of At are
 // still swapped by the sort, as they are when OpenCV has a Vt); w: N singular values or nullptr; n1: rows of At that are normalised / completed (0: none —
-// neither touches Vt).  minval = FLT_MIN, eps = 2 * FLT_EPSILON.
-template <int M, int N, int NR>
-TV_HD void tv_jacobi_svd(float* At, float* Vt, float* w, int n1) {
-  const float eps = FLT_EPSILON * 2;
-  const double minval = FLT_MIN;
+// neither touches Vt).  minval = FLT_MIN, eps = 2 * FLT_EPSILON.  The body is OpenCV's template on the element type T: pnp_math.h runs it on doubles.
+TV_HD float tv_svd_eps(const float*) { return FLT_EPSILON * 2; }
+TV_HD double tv_svd_eps(const double*) { return DBL_EPSILON * 10; }   // JacobiSVDImpl_<double>: 10 * DBL_EPSILON, minval = DBL_MIN
+TV_HD double tv_svd_minval(const float*) { return FLT_MIN; }
+TV_HD double tv_svd_minval(const double*) { return DBL_MIN; }
+TV_HD float tv_abs(float x) { return fabsf(x); }
+TV_HD double tv_abs(double x) { return fabs(x); }
+
+template <typename T, int M, int N, int NR>
+TV_HD void tv_jacobi_svd_t(T* At, T* Vt, T* w, int n1) {
+  const T eps = tv_svd_eps((const T*)nullptr);
+  const double minval = tv_svd_minval((const T*)nullptr);
   double W[N];
   for (int i = 0; i < N; i++) {
     double sd = 0;
-    for (int k = 0; k < M; k++) { const float t = At[i * M + k]; sd += (double)t * t; }
+    for (int k = 0; k < M; k++) { const T t = At[i * M + k]; sd += (double)t * t; }
     W[i] = sd;
     if (Vt) {
       for (int k = 0; k < N; k++) Vt[i * N + k] = 0;
@@ -112,37 +119,37 @@ TV_HD void tv_jacobi_svd(float* At, float* Vt, float* w, int n1) {
     int i = 0, j = 0;
     for (int ij = 0; ij < N * (N - 1) / 2; ij++) {   // the pairs i < j in the reference's order, as one loop
       if (++j == N) { i++; j = i + 1; }
-      float* Ai = At + i * M;
-      float* Aj = At + j * M;
+      T* Ai = At + i * M;
+      T* Aj = At + j * M;
       double a = W[i], p = 0, b = W[j];
       for (int k = 0; k < M; k++) p += (double)Ai[k] * Aj[k];
       if (fabs(p) <= eps * sqrt(a * b)) continue;
       p *= 2;
       const double beta = a - b, gamma = tri_hypot(p, beta);
-      float c, s;
+      T c, s;
       if (beta < 0) {
         const double delta = (gamma - beta) * 0.5;
-        s = (float)sqrt(delta / gamma);
-        c = (float)(p / (gamma * s * 2));
+        s = (T)sqrt(delta / gamma);
+        c = (T)(p / (gamma * s * 2));
       } else {
-        c = (float)sqrt((gamma + beta) / (gamma * 2));
-        s = (float)(p / (gamma * c * 2));
+        c = (T)sqrt((gamma + beta) / (gamma * 2));
+        s = (T)(p / (gamma * c * 2));
       }
       a = b = 0;
       for (int k = 0; k < M; k++) {
-        const float t0 = c * Ai[k] + s * Aj[k];
-        const float t1 = -s * Ai[k] + c * Aj[k];
+        const T t0 = c * Ai[k] + s * Aj[k];
+        const T t1 = -s * Ai[k] + c * Aj[k];
         Ai[k] = t0; Aj[k] = t1;
         a += (double)t0 * t0; b += (double)t1 * t1;
       }
       W[i] = a; W[j] = b;
       changed = true;
       if (Vt) {
-        float* Vi = Vt + i * N;
-        float* Vj = Vt + j * N;
+        T* Vi = Vt + i * N;
+        T* Vj = Vt + j * N;
         for (int k = 0; k < N; k++) {
-          const float t0 = c * Vi[k] + s * Vj[k];
-          const float t1 = -s * Vi[k] + c * Vj[k];
+          const T t0 = c * Vi[k] + s * Vj[k];
+          const T t1 = -s * Vi[k] + c * Vj[k];
           Vi[k] = t0; Vj[k] = t1;
         }
       }
@@ -151,7 +158,7 @@ TV_HD void tv_jacobi_svd(float* At, float* Vt, float* w, int n1) {
   }
   for (int i = 0; i < N; i++) {
     double sd = 0;
-    for (int k = 0; k < M; k++) { const float t = At[i * M + k]; sd += (double)t * t; }
+    for (int k = 0; k < M; k++) { const T t = At[i * M + k]; sd += (double)t * t; }
     W[i] = sqrt(sd);
   }
   // selection sort, descending, strict <: equal singular values keep their order
@@ -161,46 +168,49 @@ TV_HD void tv_jacobi_svd(float* At, float* Vt, float* w, int n1) {
       if (W[j] < W[k]) j = k;
     if (i != j) {
       const double tw = W[i]; W[i] = W[j]; W[j] = tw;
-      for (int k = 0; k < M; k++) { const float t = At[i * M + k]; At[i * M + k] = At[j * M + k]; At[j * M + k] = t; }
+      for (int k = 0; k < M; k++) { const T t = At[i * M + k]; At[i * M + k] = At[j * M + k]; At[j * M + k] = t; }
       if (Vt)
-        for (int k = 0; k < N; k++) { const float t = Vt[i * N + k]; Vt[i * N + k] = Vt[j * N + k]; Vt[j * N + k] = t; }
+        for (int k = 0; k < N; k++) { const T t = Vt[i * N + k]; Vt[i * N + k] = Vt[j * N + k]; Vt[j * N + k] = t; }
     }
   }
   if (w)
-    for (int i = 0; i < N; i++) w[i] = (float)W[i];
+    for (int i = 0; i < N; i++) w[i] = (T)W[i];
   // the rows of At become the left singular vectors: normalised, and completed where the singular value is not above FLT_MIN (all rows i >= N)
   uint64_t rng = 0x12345678u;   // cv::RNG(0x12345678), fresh for each decomposition
   for (int i = 0; i < n1 && i < NR; i++) {
-    float* Ai = At + i * M;
+    T* Ai = At + i * M;
     double sd = i < N ? W[i] : 0;
     for (int ii = 0; ii < 100 && sd <= minval; ii++) {
-      const float val0 = (float)(1. / M);
+      const T val0 = (T)(1. / M);
       for (int k = 0; k < M; k++) {
         rng = (uint64_t)(uint32_t)rng * 4164903690u + (uint32_t)(rng >> 32);
         Ai[k] = ((uint32_t)rng & 256u) != 0 ? val0 : -val0;
       }
       for (int pass = 0; pass < 2; pass++)
         for (int j = 0; j < i; j++) {
-          const float* Aj = At + j * M;
+          const T* Aj = At + j * M;
           sd = 0;
-          for (int k = 0; k < M; k++) sd += Ai[k] * Aj[k];   // a float product added to a double
-          float asum = 0;
+          for (int k = 0; k < M; k++) sd += Ai[k] * Aj[k];   // a T product added to a double
+          T asum = 0;
           for (int k = 0; k < M; k++) {
-            const float t = (float)((double)Ai[k] - sd * (double)Aj[k]);
+            const T t = (T)((double)Ai[k] - sd * (double)Aj[k]);
             Ai[k] = t;
-            asum += fabsf(t);
+            asum += tv_abs(t);
           }
           asum = asum > eps * 100 ? 1 / asum : 0;
           for (int k = 0; k < M; k++) Ai[k] *= asum;
         }
       sd = 0;
-      for (int k = 0; k < M; k++) { const float t = Ai[k]; sd += (double)t * t; }
+      for (int k = 0; k < M; k++) { const T t = Ai[k]; sd += (double)t * t; }
       sd = sqrt(sd);
     }
-    const float s = (float)(sd > minval ? 1 / sd : 0.);
+    const T s = (T)(sd > minval ? 1 / sd : 0.);
     for (int k = 0; k < M; k++) Ai[k] *= s;
   }
 }
+
+template <int M, int N, int NR>
+TV_HD void tv_jacobi_svd(float* At, float* Vt, float* w, int n1) { tv_jacobi_svd_t<float, M, N, NR>(At, Vt, w, n1); }
 
 // cv::SVDecomp(A, w, u, vt, MODIFY_A | FULL_UV) on a 16x9 f32 A (row-major): vt.row(8) -> v.  At = A' (9 rows of 16), Vt = I; the normalisation and
 // completion of U's rows do not touch Vt and are left out.

@@ -4,6 +4,7 @@
 #include "kfdb_resolve.h"
 #include "../csrc/triangulate_math.h"
 #include "../csrc/twoview_math.h"
+#include "../csrc/pnp_math.h"
 #include "../csrc/sim3_correct_math.h"
 #include "../csrc/gba_apply_math.h"
 #include "../csrc/covis_math.h"
@@ -963,6 +964,85 @@ bool Sim3RansacBatch::next(int& cand, float R[9], float t[3], float& s, std::vec
   vbInliers.assign(c.n1, false);
   for (size_t i = 0; i < c.indices1.size(); i++)
     if (ev.mask[i >> 5] >> (i & 31) & 1u) vbInliers[c.indices1[i]] = true;
+  return true;
+}
+
+// ---- PnPRansacBatch -------------------------------------------------------------------------------
+static std::vector<ccm_pnp::Candidate> pnp_base(const std::vector<PnPCandidate>& c) {
+  std::vector<ccm_pnp::Candidate> b;
+  for (const auto& x : c) {
+    if (x.keypoint_indices.size() != x.sigma2.size()) throw std::invalid_argument("PnPCandidate: inconsistent sizes");
+    for (int32_t i : x.keypoint_indices)
+      if (i < 0 || i >= x.n_matches) throw std::invalid_argument("PnPCandidate: mvKeyPointIndices outside the matches");
+    b.push_back(x);
+  }
+  return b;
+}
+
+PnPRansacBatch::PnPRansacBatch(HipContext* ctx, std::vector<PnPCandidate> cands, const ccm_pnp::Params& p, ccm_pnp::DrawSource src)
+    : sched_(pnp_base(cands), p, std::move(src)) {
+  eval_.ctx = ctx;
+  eval_.pt_off.push_back(0);
+  for (size_t c = 0; c < cands.size(); c++) {
+    const PnPCandidate& x = cands[c];
+    n_matches_.push_back(x.n_matches);
+    kp_idx_.push_back(x.keypoint_indices);
+    const int N = x.N();
+    if (N < 4) { eval_.remap.push_back(-1); continue; }   // never evaluated (N < mRansacMinInliers, checked by the schedule)
+    eval_.remap.push_back((int)eval_.pt_off.size() - 1);
+    eval_.pt_off.push_back(eval_.pt_off.back() + N);
+    eval_.P3Dw.insert(eval_.P3Dw.end(), x.P3Dw.begin(), x.P3Dw.end());
+    eval_.P2D.insert(eval_.P2D.end(), x.P2D.begin(), x.P2D.end());
+    const std::vector<float>& me = sched_.max_err((int)c);
+    eval_.max_err.insert(eval_.max_err.end(), me.begin(), me.end());
+    eval_.cam.insert(eval_.cam.end(), x.cam, x.cam + 4);
+  }
+}
+
+void PnPRansacBatch::Eval::operator()(const std::vector<int32_t>& hyp_cand, const std::vector<int32_t>& hyp_idx, std::vector<int32_t>& n_inl,
+                                      std::vector<double>& Rt, std::vector<int32_t>& mask_off, std::vector<uint32_t>& mask) {
+  const int H = (int)hyp_cand.size();
+  cand_buf.resize(H);
+  int64_t words = 0;
+  for (int h = 0; h < H; h++) {
+    const int r = remap[hyp_cand[h]];
+    cand_buf[h] = r;
+    words += (pt_off[r + 1] - pt_off[r] + 31) / 32;
+  }
+  n_inl.resize(H); Rt.resize(12 * (size_t)H); mask_off.resize(H + 1); mask.resize((size_t)words);
+  const int K = (int)pt_off.size() - 1;
+  if (!ctx) {
+    if (ccm_pnp::eval_host(K, pt_off.data(), P3Dw.data(), P2D.data(), max_err.data(), cam.data(), H, cand_buf.data(), hyp_idx.data(), n_inl.data(), Rt.data(),
+                           mask_off.data(), mask.data()))
+      throw std::invalid_argument("PnPRansacBatch: bad hypotheses");
+    return;
+  }
+  check(ccm_pnp_ransac_eval(ctx->get(), K, pt_off.data(), P3Dw.data(), P2D.data(), max_err.data(), cam.data(), H, cand_buf.data(), hyp_idx.data(), n_inl.data(),
+                            Rt.data(), mask_off.data(), mask.data()),
+        ctx->get(), "ccm_pnp_ransac_eval");
+}
+
+void PnPRansacBatch::fill(const ccm_pnp::Event& ev, Pose& out) const {
+  out.cand = ev.cand; out.nInliers = ev.n_inliers; out.refined = ev.refined; out.bNoMore = ev.no_more;
+  std::copy(ev.Tcw, ev.Tcw + 16, out.Tcw);
+  const std::vector<int32_t>& idx = kp_idx_[ev.cand];
+  out.vbInliers.assign(n_matches_[ev.cand], false);
+  for (size_t i = 0; i < idx.size(); i++)
+    if (ev.mask[i >> 5] >> (i & 31) & 1u) out.vbInliers[idx[i]] = true;
+}
+
+bool PnPRansacBatch::next(Pose& out) {
+  ccm_pnp::Event ev;
+  if (!sched_.next(eval_, ev)) return false;
+  fill(ev, out);
+  return true;
+}
+
+bool PnPRansacBatch::iterate(int c, int nIterations, bool& bNoMore, Pose& out) {
+  if (c < 0 || c >= (int)kp_idx_.size()) throw std::invalid_argument("PnPRansacBatch::iterate: no such candidate");
+  ccm_pnp::Event ev;
+  if (!sched_.iterate(eval_, c, nIterations, ev, bNoMore)) return false;
+  fill(ev, out);
   return true;
 }
 
@@ -3068,6 +3148,67 @@ int ccmh_twoview_score_host(int model, int n_models, const float* M, int N, cons
   return 0;
 }
 
+// pnp_math.h through C: the host evaluator of ccm_pnp_ransac_eval (its arguments without the context), compute_pose and Refine for any n, and the restated primitives
+int ccmh_pnp_compute_pose(int n, const double* pws, const double* us, const double* cam4, double* R9, double* t3, double* rep_errors4, int32_t* chosen) {
+  if (n < 4 || !pws || !us || !cam4 || !R9 || !t3) return -1;
+  std::vector<double> alphas(4 * (size_t)n), pcs(3 * (size_t)n), M(24 * (size_t)n), ut(144);
+  int N = 0;
+  pnp_compute_pose(n, pws, us, cam4, alphas.data(), pcs.data(), M.data(), ut.data(), R9, t3, rep_errors4, &N);
+  if (chosen) *chosen = N;
+  return 0;
+}
+int ccmh_pnp_ransac_eval_host(int K, const int32_t* pt_off, const float* P3Dw, const float* P2D, const float* max_err, const double* cam, int H, const int32_t* hyp_cand,
+                              const int32_t* hyp_idx, int32_t* n_inl, double* Rt, int32_t* mask_off, uint32_t* mask) {
+  return ccm_pnp::eval_host(K, pt_off, P3Dw, P2D, max_err, cam, H, hyp_cand, hyp_idx, n_inl, Rt, mask_off, mask);
+}
+int ccmh_pnp_check_inliers(int N, const float* P3Dw, const float* P2D, const float* max_err, const double* cam4, const double* Rt12, uint8_t* inliers, float* error2) {
+  if (N < 0 || !P3Dw || !P2D || !max_err || !cam4 || !Rt12) return -1;
+  int count = 0;
+  for (int i = 0; i < N; i++) {
+    const float e = pnp_error2(Rt12, Rt12 + 9, cam4, P3Dw + 3 * (size_t)i, P2D + 2 * (size_t)i);
+    const bool in = e < max_err[i];
+    if (error2) error2[i] = e;
+    if (inliers) inliers[i] = in;
+    count += in;
+  }
+  return count;
+}
+int ccmh_pnp_refine(int N, const float* P3Dw, const float* P2D, const float* max_err, const double* cam4, const uint8_t* best_inliers, double* Rt12, uint8_t* inliers) {
+  if (N < 4 || !P3Dw || !P2D || !max_err || !cam4 || !best_inliers || !Rt12) return -1;
+  std::vector<uint32_t> best(((size_t)N + 31) / 32, 0u), got;
+  int n = 0;
+  for (int i = 0; i < N; i++)
+    if (best_inliers[i]) { best[i >> 5] |= 1u << (i & 31); n++; }
+  if (n < 4) return -1;
+  const int count = ccm_pnp::refine_host(N, P3Dw, P2D, max_err, cam4, best, Rt12, got);
+  if (inliers)
+    for (int i = 0; i < N; i++) inliers[i] = got[i >> 5] >> (i & 31) & 1u;
+  return count;
+}
+int ccmh_pnp_matrices(int n, const double* pws, const double* us, const double* cam4, double* mtm144, double* pca9, double* cc9) {
+  if (n < 4 || !pws || !us || !cam4 || !mtm144 || !pca9 || !cc9) return -1;
+  std::vector<double> alphas(4 * (size_t)n), M(24 * (size_t)n);
+  double cws[4][3];
+  pnp_build_mtm(n, pws, us, cam4, cws, alphas.data(), M.data(), mtm144, pca9, cc9);
+  return 0;
+}
+int ccmh_pnp_primitive(int which, int rows, const double* A, const double* b, double* out) {
+  if (!A || !out) return -1;
+  switch (which) {
+    case 0: { double a[9]; std::memcpy(a, A, sizeof a); pnp_svd_ut<3>(a, out); std::memcpy(out + 3, a, sizeof a); return 0; }
+    case 1: { std::vector<double> a(A, A + 144); pnp_svd_ut<12>(a.data(), out); std::memcpy(out + 12, a.data(), 144 * sizeof(double)); return 0; }
+    case 2: pnp_svd_uv3(A, out, out + 3, out + 12); return 0;
+    case 3: pnp_invert3_svd(A, out); return 0;
+    case 4: if (!b) return -1; pnp_solve_svd<3>(A, b, out); return 0;
+    case 5: if (!b) return -1; pnp_solve_svd<4>(A, b, out); return 0;
+    case 6: if (!b) return -1; pnp_solve_svd<5>(A, b, out); return 0;
+    case 7: if (rows < 1) return -1; pnp_mul_transposed<3>(A, rows, out); return 0;
+    case 8: if (rows < 1) return -1; pnp_mul_transposed<12>(A, rows, out); return 0;
+    case 9: { if (!b) return -1; double a[24], bb[6]; std::memcpy(a, A, sizeof a); std::memcpy(bb, b, sizeof bb); return pnp_qr_solve(a, bb, out) ? 1 : 0; }
+  }
+  return -1;
+}
+
 // Sim3MapCorrection through C
 static cslam::Sim3MapCorrection::Points mk_s3c_points(int n_pt, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const int32_t* obs_off,
                                                       const int32_t* obs_kf, const int32_t* ref_kf, const int32_t* ref_level) {
@@ -3974,6 +4115,98 @@ extern "C" int ccmh_sim3_solver_iterate(int device, int N, const float* X3Dc1, c
     return 0;
   } catch (const std::exception&) { return -1000; }
 }
+// PnPRansacBatch over flat arrays: candidate c has the correspondences pt_off[c] .. pt_off[c+1]
+namespace {
+struct PnpBatchHandle {
+  std::vector<int32_t> draws;
+  size_t cursor = 0;
+  std::unique_ptr<cslam::PnPRansacBatch> batch;
+};
+int pnp_pose_out(const cslam::PnPRansacBatch::Pose& p, int32_t* cand, float* Tcw16, uint8_t* inliers, int cap, int32_t* n_inliers, int32_t* flags2) {
+  if (cand) *cand = p.cand;
+  if (Tcw16) std::memcpy(Tcw16, p.Tcw, sizeof p.Tcw);
+  if (n_inliers) *n_inliers = p.nInliers;
+  if (flags2) { flags2[0] = p.refined; flags2[1] = p.bNoMore; }
+  if (inliers) for (int i = 0; i < cap && i < (int)p.vbInliers.size(); i++) inliers[i] = p.vbInliers[i] ? 1 : 0;
+  return 1;
+}
+}  // namespace
+extern "C" void* ccmh_pnp_ransac_create(int device, int K, const int32_t* pt_off, const float* P3Dw, const float* P2D, const float* sigma2, const double* cam,
+                                        const int32_t* n_matches, const int32_t* kp_idx, double probability, int min_inliers, int max_iterations, int min_set,
+                                        float epsilon, float th2, int solver_iterations, const int32_t* draws, int64_t n_draws) {
+  try {
+    if (K < 0 || !pt_off || (K > 0 && (!n_matches || !cam)) || (draws == nullptr && n_draws != 0) || n_draws < 0) return nullptr;
+    std::vector<cslam::PnPCandidate> cands(K);
+    for (int c = 0; c < K; c++) {
+      const int a = pt_off[c], b = pt_off[c + 1];
+      if (b < a) return nullptr;
+      if (b > a && (!P3Dw || !P2D || !sigma2 || !kp_idx)) return nullptr;
+      auto& x = cands[c];
+      x.n_matches = n_matches[c];
+      x.keypoint_indices.assign(kp_idx + a, kp_idx + b);
+      x.P3Dw.assign(P3Dw + 3 * (size_t)a, P3Dw + 3 * (size_t)b);
+      x.P2D.assign(P2D + 2 * (size_t)a, P2D + 2 * (size_t)b);
+      x.sigma2.assign(sigma2 + a, sigma2 + b);
+      for (int k = 0; k < 4; k++) x.cam[k] = cam[4 * c + k];
+    }
+    ccm_pnp::Params p;
+    p.probability = probability; p.min_inliers = min_inliers; p.max_iterations = max_iterations; p.min_set = min_set; p.epsilon = epsilon; p.th2 = th2;
+    p.solver_iterations = solver_iterations;
+    std::unique_ptr<PnpBatchHandle> h(new PnpBatchHandle);
+    ccm_pnp::DrawSource src = ccm_pnp::rand_source();
+    if (draws) {
+      h->draws.assign(draws, draws + n_draws);
+      PnpBatchHandle* hp = h.get();
+      src = [hp](int& v) { if (hp->cursor >= hp->draws.size()) return false; v = hp->draws[hp->cursor++]; return true; };
+    }
+    h->batch.reset(new cslam::PnPRansacBatch(device < 0 ? nullptr : &thread_context(device), std::move(cands), p, src));
+    return h.release();
+  } catch (const std::exception&) { return nullptr; }
+}
+extern "C" int ccmh_pnp_ransac_next(void* hv, int32_t* cand, float* Tcw16, uint8_t* inliers, int cap, int32_t* n_inliers, int32_t* flags2) {
+  if (!hv) return -1000;
+  try {
+    cslam::PnPRansacBatch::Pose p;
+    try {
+      if (!((PnpBatchHandle*)hv)->batch->next(p)) return 0;
+    } catch (const ccm_pnp::DrawsExhausted&) {
+      return -1;
+    }
+    return pnp_pose_out(p, cand, Tcw16, inliers, cap, n_inliers, flags2);
+  } catch (const std::exception&) { return -1000; }
+}
+extern "C" int ccmh_pnp_ransac_iterate(void* hv, int c, int n_iterations, float* Tcw16, uint8_t* inliers, int cap, int32_t* n_inliers, int32_t* flags2) {
+  if (!hv || !flags2) return -1000;
+  try {
+    cslam::PnPRansacBatch::Pose p;
+    bool no_more = false;
+    bool got;
+    try {
+      got = ((PnpBatchHandle*)hv)->batch->iterate(c, n_iterations, no_more, p);
+    } catch (const ccm_pnp::DrawsExhausted&) {
+      return -1;
+    }
+    flags2[0] = 0; flags2[1] = no_more;
+    if (!got) return 0;
+    return pnp_pose_out(p, nullptr, Tcw16, inliers, cap, n_inliers, flags2);
+  } catch (const std::exception&) { return -1000; }
+}
+// [values taken from the draw source, hypotheses evaluated, passes (evaluator calls), Refine() computations]
+extern "C" int ccmh_pnp_ransac_stats(void* hv, int64_t* out4) {
+  if (!hv || !out4) return -1000;
+  const auto& sc = ((PnpBatchHandle*)hv)->batch->schedule();
+  out4[0] = sc.source_draws(); out4[1] = sc.hyps_evaluated(); out4[2] = sc.passes(); out4[3] = sc.refines();
+  return 0;
+}
+// [mnIterations, mRansacMaxIts, mRansacMinInliers, discarded] of candidate c
+extern "C" int ccmh_pnp_ransac_info(void* hv, int c, int32_t* out4) {
+  if (!hv || !out4) return -1000;
+  const auto& sc = ((PnpBatchHandle*)hv)->batch->schedule();
+  if (c < 0 || c >= (int)sc.candidates().size()) return -1;
+  out4[0] = sc.iterations(c); out4[1] = sc.max_iterations(c); out4[2] = sc.min_inliers(c); out4[3] = sc.discarded(c);
+  return 0;
+}
+extern "C" void ccmh_pnp_ransac_destroy(void* hv) { delete (PnpBatchHandle*)hv; }
 // the calling thread's FIFO of drawn, unused rand() values: returns its length, copies min(length, cap) values front first
 extern "C" int ccmh_sim3_draws_pending(int32_t* out, int cap) {
   const auto& q = ccm_sim3::draw_fifo();

@@ -15,6 +15,7 @@
 #include <vector>
 #include "../../include/ccm_hip.h"
 #include "sim3_schedule.h"
+#include "pnp_schedule.h"
 #include <map>
 #include <memory>
 #include <mutex>
@@ -527,6 +528,49 @@ class Sim3RansacBatch {
   std::vector<Sim3Candidate> cands_;
   Eval eval_;
   ccm_sim3::Schedule<Eval> sched_;
+};
+
+// ---------------------------------------------------------------------------------------------------
+// PnPRansacBatch — one cslam::PnPsolver per relocalisation candidate (the correspondences its constructor gathers, PnPSolver.cpp:57-100) and the round-robin
+// `for each candidate not discarded: iterate(solver_iterations)` of a Relocalization().  next() returns the next call that returns a pose: the candidate, Tcw
+// (4x4 f32, row-major: mRefinedTcw after a successful Refine, else mBestTcw of a call that ran out of iterations), vbInliers in the frame's keypoint numbering and
+// nInliers; the caller runs PoseOptimizationClient and, on rejection, calls next() again, which goes on where the reference's loop goes on.  false: every candidate
+// is discarded.  Hypotheses are evaluated in passes (ccm_pnp_ransac_eval, schedule in pnp_schedule.h; ctx == nullptr: pnp_math.h on the calling thread); the draws
+// come from ::rand() through the calling thread's FIFO (the one Sim3RansacBatch uses) or a supplied source, so the events are the sequential reference's.
+// ---------------------------------------------------------------------------------------------------
+struct PnPCandidate : ccm_pnp::Candidate {
+  int n_matches = 0;                        // vpMapPointMatches.size(): the length of vbInliers
+  std::vector<int32_t> keypoint_indices;    // mvKeyPointIndices (size N)
+};
+
+class PnPRansacBatch {
+ public:
+  struct Eval {
+    HipContext* ctx = nullptr;            // nullptr: the host evaluator
+    std::vector<int32_t> pt_off, remap;   // CSR over the candidates with N >= 4; remap: candidate -> CSR row
+    std::vector<float> P3Dw, P2D, max_err;
+    std::vector<double> cam;
+    std::vector<int32_t> cand_buf;
+    void operator()(const std::vector<int32_t>& hyp_cand, const std::vector<int32_t>& hyp_idx, std::vector<int32_t>& n_inl, std::vector<double>& Rt,
+                    std::vector<int32_t>& mask_off, std::vector<uint32_t>& mask);
+  };
+  struct Pose {
+    int cand = -1, nInliers = 0;
+    bool refined = false, bNoMore = false;
+    float Tcw[16];
+    std::vector<bool> vbInliers;
+  };
+  PnPRansacBatch(HipContext* ctx, std::vector<PnPCandidate> cands, const ccm_pnp::Params& p = ccm_pnp::Params(), ccm_pnp::DrawSource src = ccm_pnp::rand_source());
+  bool next(Pose& out);
+  // one iterate(nIterations) of candidate c (the drop-in's call): true when it returns a pose; bNoMore as the reference sets it
+  bool iterate(int c, int nIterations, bool& bNoMore, Pose& out);
+  const ccm_pnp::Schedule<Eval>& schedule() const { return sched_; }
+ private:
+  void fill(const ccm_pnp::Event& ev, Pose& out) const;
+  std::vector<int> n_matches_;
+  std::vector<std::vector<int32_t>> kp_idx_;
+  Eval eval_;
+  ccm_pnp::Schedule<Eval> sched_;
 };
 
 // ---------------------------------------------------------------------------------------------------

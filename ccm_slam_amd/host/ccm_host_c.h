@@ -122,6 +122,32 @@ void ccmh_twoview_inv33(const float* S9, float* D9);
 void ccmh_twoview_prepare_rt(const float* K9, const float* R9, const float* t3, float* rec27);
 int ccmh_twoview_svd(int shape, const float* A, float* out);
 int ccmh_twoview_score_host(int model, int n_models, const float* M, int N, const float* xy1, const float* xy2, float sigma, float* score, uint32_t* mask);
+/* pnp_math.h (cslam::PnPsolver's EPnP and CheckInliers) compiled for the host.  compute_pose: n >= 4 correspondences (pws 3 n, us 2 n, cam = fu fv uc vc) -> R (row-major), t,
+ * rep_errors[0..4) (entry 0 unused) and the chosen solution 1..3.  ransac_eval_host: the arguments of ccm_pnp_ransac_eval without the context (0, or -1 for its CCM_E_ARG
+ * cases).  check_inliers: CheckInliers of one pose (Rt12 = R, t) over N points; returns mnInliersi, error2 (nullable) per point.  refine: Refine's compute_pose on the
+ * points of best_inliers and its CheckInliers; returns mnRefinedInliers.  matrices: M' M, PW0' PW0 and CC of a compute_pose call, before their decompositions.
+ * primitive: the restated C-API calls — which 0 / 1: cvSVD(MODIFY_A | U_T) of a 3x3 / 12x12 (out = w, then Ut); 2: cvSVD(MODIFY_A) with U and V of a 3x3 (out = w, U, V);
+ * 3: cvInvert(CV_SVD) of a 3x3; 4 / 5 / 6: cvSolve(CV_SVD) of a 6x3 / 6x4 / 6x5 system; 7 / 8: cvMulTransposed(., ., 1) of rows x 3 / rows x 12; 9: qr_solve of a 6x4
+ * system, out = X in and out, returns 1, or 0 at the singular exit. */
+int ccmh_pnp_compute_pose(int n, const double* pws, const double* us, const double* cam4, double* R9, double* t3, double* rep_errors4, int32_t* chosen);
+int ccmh_pnp_ransac_eval_host(int K, const int32_t* pt_off, const float* P3Dw, const float* P2D, const float* max_err, const double* cam, int H, const int32_t* hyp_cand, const int32_t* hyp_idx, int32_t* n_inl, double* Rt, int32_t* mask_off, uint32_t* mask);
+int ccmh_pnp_check_inliers(int N, const float* P3Dw, const float* P2D, const float* max_err, const double* cam4, const double* Rt12, uint8_t* inliers, float* error2);
+int ccmh_pnp_refine(int N, const float* P3Dw, const float* P2D, const float* max_err, const double* cam4, const uint8_t* best_inliers, double* Rt12, uint8_t* inliers);
+int ccmh_pnp_matrices(int n, const double* pws, const double* us, const double* cam4, double* mtm144, double* pca9, double* cc9);
+int ccmh_pnp_primitive(int which, int rows, const double* A, const double* b, double* out);
+/* cslam::PnPRansacBatch (the PnPsolver of every relocalisation candidate and the round-robin of iterate()).  device < 0: the host evaluator.  candidate c = correspondences
+ * pt_off[c] .. pt_off[c+1] (mvP3Dw 3 floats, mvP2D 2, mvSigma2, kp_idx = mvKeyPointIndices), n_matches[c] = vpMapPointMatches.size(), cam = fu fv uc vc (f64) per candidate;
+ * the other arguments are SetRansacParameters' (min_set must be 4) and the nIterations of the round-robin's calls.  draws: raw rand() values to use instead of ::rand()
+ * (NULL: ::rand()), after the calling thread's FIFO (ccmh_sim3_draws_pending: Sim3 and PnP share it).  next / iterate: 1 = a pose (Tcw 4x4 f32 row-major, inliers[0 ..
+ * min(cap, n_matches)) = vbInliers, flags2 = [refined, bNoMore]), 0 = every candidate discarded / the call returned no pose (flags2[1] = bNoMore), -1 = the supplied
+ * draws ran out, -1000 = an error.  stats: draws taken from the source, hypotheses, evaluator calls, Refine computations.  info: mnIterations, mRansacMaxIts,
+ * mRansacMinInliers, discarded. */
+void* ccmh_pnp_ransac_create(int device, int K, const int32_t* pt_off, const float* P3Dw, const float* P2D, const float* sigma2, const double* cam, const int32_t* n_matches, const int32_t* kp_idx, double probability, int min_inliers, int max_iterations, int min_set, float epsilon, float th2, int solver_iterations, const int32_t* draws, int64_t n_draws);
+int ccmh_pnp_ransac_next(void* h, int32_t* cand, float* Tcw16, uint8_t* inliers, int cap, int32_t* n_inliers, int32_t* flags2);
+int ccmh_pnp_ransac_iterate(void* h, int c, int n_iterations, float* Tcw16, uint8_t* inliers, int cap, int32_t* n_inliers, int32_t* flags2);
+int ccmh_pnp_ransac_stats(void* h, int64_t* out4);
+int ccmh_pnp_ransac_info(void* h, int c, int32_t* out4);
+void ccmh_pnp_ransac_destroy(void* h);
 /* cslam::SearchAndFuseBatch (every Fuse call of a SearchAndFuse from ONE ccm_fuse_sim3_eval call; arguments as there).  device < 0 asks for the host evaluator by name;
  * create returns NULL on bad arguments or a device error.  table: any pointer may be NULL.  resolve: the k-th Fuse call with the caller's current skips and descriptors
  * (both nullable); returns nFused, -1000 on an error, -1001 when n_pts is not the batch's.  eval_host: the arguments of ccm_fuse_sim3_eval after the context through

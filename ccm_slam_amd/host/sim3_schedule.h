@@ -18,8 +18,17 @@
 #include <functional>
 #include <stdexcept>
 #include <vector>
+#include "ransac_draws.h"
 
 namespace ccm_sim3 {
+
+// the draw helpers both RANSAC schedules of a thread share (ransac_draws.h)
+using ccm_ransac::DrawSource;
+using ccm_ransac::DrawsExhausted;
+using ccm_ransac::draw_fifo;
+using ccm_ransac::fifo_restore;
+using ccm_ransac::rand_source;
+using ccm_ransac::random_int;
 
 struct Params {
   double probability = 0.99;   // SetRansacParameters defaults (Sim3Solver.h), the values conf/config.yaml gives LoopFinder / MapMatcher
@@ -40,9 +49,6 @@ inline int ransac_max_iterations(int N, double probability, int min_inliers, int
   return std::max(1, std::min(n_it, max_iterations));
 }
 
-// DUtils::Random::RandomInt(0, d - 1) on one raw rand() value
-inline int random_int(int raw, int d) { return int(((double)raw / ((double)RAND_MAX + 1.0)) * d) + 0; }
-
 // three raw draws -> the sample's indices: vAvailableIndices = identity of N, randi = RandomInt(0, size-1), idx = avail[randi],
 // avail[randi] = avail.back(), pop_back (:146-160).  Only the at most three changed slots are kept.
 inline void draws_to_indices(const int raw[3], int N, int idx[3]) {
@@ -55,27 +61,6 @@ inline void draws_to_indices(const int raw[3], int N, int idx[3]) {
     const int back = get(size - 1);
     pos[nm] = r; val[nm] = back; nm++;
   }
-}
-
-// the calling thread's FIFO of raw draws taken but not used (shared by every batch and drop-in solver of the thread)
-inline std::deque<int>& draw_fifo() {
-  thread_local std::deque<int> q;
-  return q;
-}
-
-// a draw source: returns false when exhausted (a supplied array); the default is ::rand()
-using DrawSource = std::function<bool(int&)>;
-inline DrawSource rand_source() { return [](int& v) { v = ::rand(); return true; }; }
-
-// a supplied draw array ran out before the reference would stop drawing
-struct DrawsExhausted : std::runtime_error {
-  DrawsExhausted() : std::runtime_error("Sim3 RANSAC: the supplied draws ran out") {}
-};
-
-// put values back at the front of the thread's FIFO so that it then starts with v[0], v[1], ...
-inline void fifo_restore(const int* v, size_t n) {
-  std::deque<int>& fifo = draw_fifo();
-  for (size_t w = n; w-- > 0;) fifo.push_front(v[w]);
 }
 
 // evaluate; if the evaluator throws, this pass's raw draws go back to the front of the FIFO first, so that the thread's sequence is kept

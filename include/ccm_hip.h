@@ -442,6 +442,21 @@ int  ccm_sim3_ransac_eval(ccm_ctx* ctx, int K, const int32_t* pt_off, const floa
                           const uint32_t* max_err1, const uint32_t* max_err2, int H, const int32_t* hyp_cand, const int32_t* hyp_idx,
                           int fix_scale, int32_t* n_inl, float* rts, int32_t* mask_off, uint32_t* mask);
 
+/* ---- PnP RANSAC (relocalisation) ---------------------------------------------------------------
+ * The hypotheses of cslam::PnPsolver::iterate (cslam/src/PnPSolver.cpp:155-249): per hypothesis EPnP's compute_pose on four correspondences
+ * (:468-516) and CheckInliers (:299-330) over all of its candidate's points, in the reference's own f64 / f32 arithmetic with the legacy
+ * OpenCV calls restated for f64 (the lines are ccm_slam_amd/csrc/pnp_math.h, which also compiles for the host).  Stateless.
+ * K candidates in CSR over pt_off[K + 1] (pt_off[0] = 0, every candidate >= 4 points): P3Dw = mvP3Dw (f32 x 3 per point), P2D = mvP2D (f32 x 2),
+ * max_err = mvMaxError (f32), cam = fu fv uc vc per candidate (f64, as the reference's members).
+ * H hypotheses: hyp_cand[h] and four distinct candidate-local point indices hyp_idx[4h .. 4h+3] in sample order.
+ * Out: n_inl[h] = mnInliersi, Rt[12h ..] = mRi (9, row-major), mti (3); mask_off[H + 1] (written by the call) = word offsets of the inlier
+ * masks, mask[mask_off[h] ..] = mvbInliersi, one bit per point (bit i % 32 of word i / 32, tail bits zero), mask must hold the sum over h of
+ * ceil(N / 32) words.  Non-finite values are not trapped: a NaN pose compares false against every threshold.  CCM_E_ARG: null pointers, K < 1, H < 0, a candidate with N < 4,
+ * an index outside [0, N) or repeated in a hypothesis.  H = 0 succeeds and does nothing.  One H2D copy, one launch and one D2H copy on the
+ * context's stream, scratch of the context. */
+int  ccm_pnp_ransac_eval(ccm_ctx* ctx, int K, const int32_t* pt_off, const float* P3Dw, const float* P2D, const float* max_err, const double* cam,
+                         int H, const int32_t* hyp_cand, const int32_t* hyp_idx, int32_t* n_inl, double* Rt, int32_t* mask_off, uint32_t* mask);
+
 /* ---- triangulation of new map points ---------------------------------------------------------
  * The per-match arithmetic of LocalMapping::CreateNewMapPoints (cslam/src/Mapping.cpp:353-448) for every match of up to 20 neighbours in ONE
  * launch: ray-parallax gate, linear triangulation (cv::SVD::compute on a 4x4 f32 matrix), the two depth tests, the two chi2 reprojection gates
