@@ -6,6 +6,7 @@
 // sequential claim rules on it; it no longer builds the grid or walks cells itself.
 #include "common.h"
 #include "frame_math.h"
+#include "guided_search_math.h"
 #include "stage_blocks.h"
 #include <algorithm>
 #include <cstring>
@@ -173,6 +174,38 @@ __global__ __launch_bounds__(1024) void frame_scan_kernel(const int* cnt, int Q,
   int base = part[t] - s;
   for (int i = i0; i < i1; i++) { off[i] = base; base += cnt[i]; }
   if (t == 1023) off[Q] = part[t];
+}
+
+// The window passes of both entry points (ccm_frame_window_search, ccm_frame_guided_search): count, scan and, with a capacity, the optimistic fill with the
+// distances, queued behind the scan without waiting for the total; the fill never writes past cap (queries whose list would cross it are skipped) and the caller
+// checks the total after its one wait.
+void frame_windows_enqueue(ccm_ctx* ctx, const ccm_frame* f, int Q, const WinQ& wq, const uint8_t* d_qdesc, int* d_cnt, int* d_off, int* d_idx, uint16_t* d_dist,
+                           int64_t cap) {
+  const int nb = ccm_div_up((int64_t)Q * kQL, 128);
+  hipLaunchKernelGGL(frame_window_kernel<0>, dim3(nb), dim3(128), 0, ctx->stream, Q, wq, f->b, f->d_xy, f->d_oct, f->d_cell_off, f->d_cell_idx, d_cnt,
+                     (const int*)nullptr, (int*)nullptr, 0);
+  hipLaunchKernelGGL(frame_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_cnt, Q, d_off);
+  if (cap > 0)
+    hipLaunchKernelGGL(frame_window_kernel<1>, dim3(nb), dim3(128), 0, ctx->stream, Q, wq, f->b, f->d_xy, f->d_oct, f->d_cell_off, f->d_cell_idx,
+                       (int*)nullptr, (const int*)d_off, d_idx, (int)std::min<int64_t>(cap, 0x7fffffff), (const uint32_t*)d_qdesc, (const uint32_t*)f->d_desc, d_dist);
+}
+
+// The gates of ORBmatcher::SearchByProjection(Frame&, kfptr, sAlreadyFound, th, ORBdist) (ORBmatcher.cpp:1494-1532), one thread per map point: guided_search_math.h.
+// A point that does not go on leaves a negative radius, which frame_window_kernel enumerates as an empty window.
+struct GuidedFrame { float pose[GSM_POSE_FLOATS], K[4], minX, maxX, minY, maxY, logScaleFactor, scaleFactors[FSM_MAX_LEVELS], th; int nlevels; };
+constexpr int kGateTPB = 256;
+__global__ __launch_bounds__(kGateTPB) void frame_guided_gate_kernel(GuidedFrame g, int P, const float* pos, const float* dmin, const float* dmax, const uint8_t* skip,
+                                                                     uint8_t* status, float* u, float* v, int* level, float* radius, int* minl, int* maxl) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= P) return;
+  float pu = 0.0f, pv = 0.0f, r = -1.0f;
+  int l = 0, st = GSM_SKIPPED;
+  if (!skip[i]) {
+    const float p[3] = {pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]};
+    st = gsm_gate(g.pose, g.K, g.minX, g.maxX, g.minY, g.maxY, p, dmin[i], dmax[i], g.logScaleFactor, g.nlevels, g.scaleFactors, g.th, pu, pv, l, r);
+  }
+  status[i] = (uint8_t)st; u[i] = pu; v[i] = pv; level[i] = l;
+  radius[i] = r; minl[i] = l - 1; maxl[i] = l + 1;
 }
 
 // Tracking::SearchLocalPoints' isInFrustum loop (Tracking.cpp:~770-800 / Frame.cpp:139-198): one thread per map point
@@ -357,19 +390,12 @@ extern "C" int ccm_frame_window_search(ccm_frame* f, int Q, const float* u, cons
   memcpy(h + o_desc, qdesc, 32 * wQ);
   CCM_HIP_CHECK(ctx, hipMemcpyAsync(d_in, h, o_desc + 32 * wQ, hipMemcpyHostToDevice, ctx->stream));
   WinQ wq{d_q, d_q + wQ, d_q + 2 * wQ, (const int*)(d_q + 3 * wQ), (const int*)(d_q + 4 * wQ)};
-  const int nb = ccm_div_up((int64_t)Q * kQL, 128);
-  hipLaunchKernelGGL(frame_window_kernel<0>, dim3(nb), dim3(128), 0, ctx->stream, Q, wq, f->b, f->d_xy, f->d_oct, f->d_cell_off, f->d_cell_idx, d_cnt,
-                     (const int*)nullptr, (int*)nullptr, 0);
-  hipLaunchKernelGGL(frame_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_cnt, Q, d_off);
+  frame_windows_enqueue(ctx, f, Q, wq, d_qdesc, d_cnt, d_off, d_idx, d_dist, cap);
   uint8_t* h_out = h + in_bytes;
   int* h_off = (int*)h_out;
   uint8_t* h_idx = h_out + o_idx;
   uint8_t* h_dist = h_out + o_dist;
   if (cap > 0) {
-    // optimistic single-sync path: fill and distances are queued behind the scan without waiting for the total; the
-    // fill kernel never writes past cap (queries whose list would cross it are skipped) and the total is checked after
-    hipLaunchKernelGGL(frame_window_kernel<1>, dim3(nb), dim3(128), 0, ctx->stream, Q, wq, f->b, f->d_xy, f->d_oct, f->d_cell_off, f->d_cell_idx,
-                       (int*)nullptr, (const int*)d_off, d_idx, (int)std::min<int64_t>(cap, 0x7fffffff), (const uint32_t*)d_qdesc, (const uint32_t*)f->d_desc, d_dist);
     CCM_HIP_CHECK(ctx, hipGetLastError());
     CCM_HIP_CHECK(ctx, hipMemcpyAsync(h_out, d_out, o_dist + 2 * (size_t)cap, hipMemcpyDeviceToHost, ctx->stream));
     CCM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -386,6 +412,49 @@ extern "C" int ccm_frame_window_search(ccm_frame* f, int Q, const float* u, cons
   CCM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   memcpy(cand_off, h_off, 4 * (wQ + 1));
   *n_cand = h_off[Q];
+  return CCM_OK;
+}
+
+extern "C" int ccm_frame_guided_search(ccm_frame* f, const ccm_guided_pose* pose, int P, const float* pos, const float* min_dist, const float* max_dist,
+                                       const uint8_t* desc, const uint8_t* skip, float th, uint8_t* status, float* u, float* v, int32_t* level,
+                                       int32_t* cand_off, int32_t* cand_idx, uint16_t* cand_dist, int64_t cap, int64_t* n_cand) {
+  if (!f) return CCM_E_ARG;
+  ccm_ctx* ctx = f->ctx;
+  if (!pose || P < 0 || !cand_off || !n_cand || (P && (!pos || !min_dist || !max_dist || !desc || !status || !u || !v || !level)) || cap < 0 ||
+      (cap && (!cand_idx || !cand_dist)))
+    return ccm_set_error(ctx, CCM_E_ARG, "ccm_frame_guided_search: bad args");
+  if (pose->nScaleLevels < 1 || pose->nScaleLevels > FSM_MAX_LEVELS) return ccm_set_error(ctx, CCM_E_ARG, "ccm_frame_guided_search: nScaleLevels must be 1 .. 16");
+  if (!(th >= 0.0f) || !(th <= 3.40282347e+38f)) return ccm_set_error(ctx, CCM_E_ARG, "ccm_frame_guided_search: th must be finite and not negative");
+  *n_cand = 0;
+  cand_off[0] = 0;
+  if (P == 0) return CCM_OK;
+  CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  GuidedFrame g;
+  gsm_pose(pose->Tcw, g.pose);
+  g.K[0] = (float)f->cam.fx; g.K[1] = (float)f->cam.fy; g.K[2] = (float)f->cam.cx; g.K[3] = (float)f->cam.cy;   // given as f32: the cast back is exact
+  g.minX = f->b.minX; g.maxX = f->b.maxX; g.minY = f->b.minY; g.maxY = f->b.maxY;
+  g.logScaleFactor = pose->logScaleFactor; g.nlevels = pose->nScaleLevels; g.th = th;
+  for (int l = 0; l < FSM_MAX_LEVELS; l++) g.scaleFactors[l] = l < g.nlevels ? pose->scaleFactors[l] : 0.0f;
+  // no list is longer than the frame: a capacity beyond P * N reserves nothing more
+  const int64_t cap_eff = std::min<int64_t>(cap, (int64_t)P * f->N);
+  GuidedSearchBlock b(P, (size_t)cap_eff);
+  if (int rc = ccm_staged_begin(ctx, b, "ccm_frame_guided_search: ")) return rc;
+  b.put(b.desc, desc); b.put(b.pos, pos); b.put(b.dmin, min_dist); b.put(b.dmax, max_dist);
+  if (skip) memcpy(b.up(b.skip), skip, (size_t)P); else memset(b.up(b.skip), 0, (size_t)P);
+  if (int rc = ccm_staged_upload(ctx, b)) return rc;
+  hipLaunchKernelGGL(frame_guided_gate_kernel, dim3(ccm_div_up(P, kGateTPB)), dim3(kGateTPB), 0, ctx->stream, g, P, b.dev(b.pos), b.dev(b.dmin), b.dev(b.dmax),
+                     b.dev(b.skip), b.dev(b.status), b.dev(b.u), b.dev(b.v), b.dev(b.level), b.dev(b.radius), b.dev(b.minl), b.dev(b.maxl));
+  const WinQ wq{b.dev(b.u), b.dev(b.v), b.dev(b.radius), b.dev(b.minl), b.dev(b.maxl)};
+  if (f->N > 0) frame_windows_enqueue(ctx, f, P, wq, b.dev(b.desc), b.dev(b.cnt), b.dev(b.cand_off), b.dev(b.cand_idx), b.dev(b.cand_dist), cap_eff);
+  else CCM_HIP_CHECK(ctx, hipMemsetAsync(b.dev(b.cand_off), 0, 4 * ((size_t)P + 1), ctx->stream));   // a frame without features (its grid may never have been built)
+  CCM_HIP_CHECK(ctx, hipGetLastError());
+  if (int rc = ccm_staged_download(ctx, b)) return rc;
+  b.get(b.status, status); b.get(b.u, u); b.get(b.v, v); b.get(b.level, level); b.get(b.cand_off, cand_off);
+  const int64_t total = b.down(b.cand_off)[P];
+  *n_cand = total;
+  if (cap == 0) return CCM_OK;   // the sizing call
+  if (total > cap) return ccm_set_error(ctx, CCM_E_ARG, "ccm_frame_guided_search: candidate capacity too small");
+  b.get(b.cand_idx, cand_idx, (size_t)total); b.get(b.cand_dist, cand_dist, (size_t)total);
   return CCM_OK;
 }
 

@@ -292,6 +292,24 @@ struct FrustumBlock : StagedBlock {
   StagedSeg<uint8_t> in_view = add<uint8_t>(n, SB_OUT);
 };
 
+// ccm_frame_guided_search: P map points against the resident grid of one frame.  The descriptors lead, on 16 bytes, for the window kernel's uint4
+// reads; skip is the caller's or, without one, zeros, written by the stage.  The gate kernel leaves each point's window (radius, level range) on the device for the
+// window kernels, which read u and v from the outputs; cnt is the count pass's.  The candidate arrays have the caller's capacity and come last, the 16-bit one at the end.
+struct GuidedSearchBlock : StagedBlock {
+  const size_t P, cap;
+  GuidedSearchBlock(size_t P, size_t cap) : P(P), cap(cap) {}
+  StagedSeg<uint8_t> desc = add<uint8_t>(32 * P, SB_COPY, 16);
+  StagedSeg<float> pos = add<float>(3 * P, SB_COPY), dmin = add<float>(P, SB_COPY), dmax = add<float>(P, SB_COPY);
+  StagedSeg<uint8_t> skip = add<uint8_t>(P, SB_GEN);
+  StagedSeg<float> radius = add<float>(P, SB_WORK);
+  StagedSeg<int32_t> minl = add<int32_t>(P, SB_WORK), maxl = add<int32_t>(P, SB_WORK), cnt = add<int32_t>(P, SB_WORK);
+  StagedSeg<float> u = add<float>(P, SB_OUT), v = add<float>(P, SB_OUT);
+  StagedSeg<int32_t> level = add<int32_t>(P, SB_OUT), cand_off = add<int32_t>(P + 1, SB_OUT);
+  StagedSeg<uint8_t> status = add<uint8_t>(P, SB_OUT);
+  StagedSeg<int32_t> cand_idx = add<int32_t>(cap, SB_OUT);
+  StagedSeg<uint16_t> cand_dist = add<uint16_t>(cap, SB_OUT);
+};
+
 // ccm_update_normal_and_depth: the inputs, then the outputs, which go up seeded with the caller's values: a point without observers keeps them.
 struct NormalDepthBlock : StagedBlock {
   const size_t P, K, L, NO;

@@ -16,6 +16,9 @@
 #include "../csrc/tri_search_math.h"
 #include "../csrc/mappoint_math.h"
 #include "../csrc/frame_math.h"
+#include "../csrc/guided_search_math.h"
+#include "ccm_convert.h"
+#include "guided_replay.h"
 #include <climits>
 #include <algorithm>
 #include <cmath>
@@ -118,38 +121,8 @@ struct FrameGrid {
   }
 };
 
-void threeMaxima(const std::vector<int>* histo, int L, int& ind1, int& ind2, int& ind3) {   // ORBmatcher.cpp:1607-1648
-  int max1 = 0, max2 = 0, max3 = 0;
-  for (int i = 0; i < L; i++) {
-    const int s = (int)histo[i].size();
-    if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-    else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-    else if (s > max3) { max3 = s; ind3 = i; }
-  }
-  if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-  else if (max3 < 0.1f * (float)max1) ind3 = -1;
-}
-int histBin(float rot) {
-  if (rot < 0.0) rot += 360.0f;
-  int bin = (int)std::round(rot * (1.0f / ORBmatcher::HISTO_LENGTH));   // upstream quirk: 30-degree bins (:1358)
-  if (bin == ORBmatcher::HISTO_LENGTH) bin = 0;
-  return bin;
-}
-// The rotation-consistency filter of every search: a match is added under the difference of its two keypoints' angles, and the matches of every bin but the three
-// fullest are rejected, bins ascending, a bin's matches in the order they were added.
-struct RotationFilter {
-  std::vector<int> hist[ORBmatcher::HISTO_LENGTH];
-  void add(float rot, int index) { hist[histBin(rot)].push_back(index); }
-  template <class Reject>
-  void reject_outliers(Reject reject) const {
-    int ind1 = -1, ind2 = -1, ind3 = -1;
-    threeMaxima(hist, ORBmatcher::HISTO_LENGTH, ind1, ind2, ind3);
-    for (int i = 0; i < ORBmatcher::HISTO_LENGTH; i++) {
-      if (i == ind1 || i == ind2 || i == ind3) continue;
-      for (int k : hist[i]) reject(k);
-    }
-  }
-};
+// the rotation-consistency filter every search ends in: guided_replay.h
+using ccm_guided::RotationFilter;
 }  // namespace
 
 int ORBmatcher::DescriptorDistance(const uint8_t* a, const uint8_t* b) {
@@ -360,6 +333,105 @@ int ORBmatcher::SearchByProjection(FrameGridDev& grid, FrameView& C, const LastF
   }
   if (mbCheckOrientation) rot.reject_outliers([&](int k) { C.mvpMapPoints[k] = -1; nmatches--; });
   return nmatches;
+}
+
+// ---- SearchByProjection(Frame&, kfptr, sAlreadyFound, th, ORBdist) (ORBmatcher.cpp:1478-1604) ------------------------------------------------
+namespace {
+void guidedCheck(const ccm_guided_pose& pose, const KeyFramePoints& kf, float th) {
+  if (kf.n < 0 || (kf.n && (!kf.live || !kf.pos || !kf.min_dist || !kf.max_dist || !kf.desc))) throw std::invalid_argument("SearchByProjection: null keyframe arrays");
+  if (pose.nScaleLevels < 1 || pose.nScaleLevels > FSM_MAX_LEVELS) throw std::invalid_argument("SearchByProjection: nScaleLevels must be 1 .. 16");
+  if (!(th >= 0.0f) || !(th <= 3.40282347e+38f)) throw std::invalid_argument("SearchByProjection: th must be finite and not negative");
+}
+std::vector<uint8_t> guidedSkip(const KeyFramePoints& kf, const uint8_t* alreadyFound) {   // :1498-1500
+  std::vector<uint8_t> skip((size_t)std::max(kf.n, 1));
+  for (int i = 0; i < kf.n; i++) skip[i] = (!kf.live[i] || (alreadyFound && alreadyFound[i])) ? 1 : 0;
+  return skip;
+}
+}  // namespace
+
+void ORBmatcher::GuidedSearchHost(const FrameView& F, const float K[4], const ccm_guided_pose& pose, const KeyFramePoints& kf, const uint8_t* alreadyFound, float th,
+                                  GuidedCandidates& c) {
+  guidedCheck(pose, kf, th);
+  const std::vector<uint8_t> skip = guidedSkip(kf, alreadyFound);
+  const int P = kf.n;
+  c.status.assign(P, GSM_SKIPPED); c.u.assign(P, 0.0f); c.v.assign(P, 0.0f); c.level.assign(P, 0); c.off.assign(P + 1, 0); c.idx.clear(); c.dist.clear();
+  float rec[GSM_POSE_FLOATS];
+  gsm_pose(pose.Tcw, rec);
+  FrameGrid grid(F);
+  for (int i = 0; i < P; i++) {
+    if (!skip[i]) {
+      float r;
+      c.status[i] = (uint8_t)gsm_gate(rec, K, F.mnMinX, F.mnMaxX, F.mnMinY, F.mnMaxY, kf.pos + 3 * (size_t)i, kf.min_dist[i], kf.max_dist[i], pose.logScaleFactor,
+                                      pose.nScaleLevels, pose.scaleFactors, th, c.u[i], c.v[i], c.level[i], r);
+      if (c.status[i] == GSM_SEARCHED) {
+        const size_t before = c.idx.size();
+        grid.featuresInArea(c.u[i], c.v[i], r, c.level[i] - 1, c.level[i] + 1, c.idx);
+        for (size_t s = before; s < c.idx.size(); s++) c.dist.push_back((uint16_t)DescriptorDistance(kf.desc + 32 * (size_t)i, F.mDescriptors + 32 * (size_t)c.idx[s]));
+      }
+    }
+    c.off[i + 1] = (int32_t)c.idx.size();
+  }
+}
+
+void ORBmatcher::GuidedSearchDevice(HipContext& ctx, FrameGridDev& grid, const ccm_guided_pose& pose, const KeyFramePoints& kf, const uint8_t* alreadyFound, float th,
+                                    GuidedCandidates& c) {
+  guidedCheck(pose, kf, th);
+  const std::vector<uint8_t> skip = guidedSkip(kf, alreadyFound);
+  const int P = kf.n;
+  const size_t n1 = (size_t)std::max(P, 1);
+  c.status.assign(n1, 0); c.u.assign(n1, 0.0f); c.v.assign(n1, 0.0f); c.level.assign(n1, 0); c.off.assign((size_t)P + 1, 0);
+  int64_t n = 0;
+  c.idx.resize((size_t)P * 16 + 1024); c.dist.resize(c.idx.size());   // as deviceWindows: grow once if short
+  auto call = [&](int64_t cap) {
+    return ccm_frame_guided_search(grid.get(), &pose, P, kf.pos, kf.min_dist, kf.max_dist, kf.desc, skip.data(), th, c.status.data(), c.u.data(), c.v.data(),
+                                   c.level.data(), c.off.data(), c.idx.data(), c.dist.data(), cap, &n);
+  };
+  int rc = call((int64_t)c.idx.size());
+  if (rc == CCM_E_ARG && n > (int64_t)c.idx.size()) {
+    c.idx.resize((size_t)n); c.dist.resize((size_t)n);
+    rc = call(n);
+  }
+  check(rc, ctx.get(), "ccm_frame_guided_search");
+  c.status.resize(P); c.u.resize(P); c.v.resize(P); c.level.resize(P);
+  c.idx.resize((size_t)n); c.dist.resize((size_t)n);
+}
+
+// The sequential pass (:1494-1602) on the candidate lists: the points in slot order; a feature that holds anything is skipped; the first of equal distances wins;
+// a match claims its feature for the points behind it; the rotation histogram takes the keyframe slot's angle minus the frame feature's.
+int ORBmatcher::GuidedReplay(FrameView& F, const KeyFramePoints& kf, const GuidedCandidates& c, int ORBdist, bool checkOrientation) {
+  if ((int)c.off.size() != kf.n + 1) throw std::invalid_argument("SearchByProjection: the candidate lists are not the keyframe's");
+  return ccm_guided::replay(kf.n, c.off.data(), c.idx.data(), c.dist.data(), kf.angle, [&](int i2) { return F.mvKeysUn[i2].angle; }, F.N, F.mvpMapPoints, ORBdist,
+                            checkOrientation);
+}
+
+int ORBmatcher::SearchByProjection(FrameGridDev& grid, FrameView& F, const ccm_guided_pose& pose, const KeyFramePoints& kf, const uint8_t* alreadyFound, float th,
+                                   int ORBdist) {
+  if (ORBdist < 0 || ORBdist > 255) throw std::invalid_argument("SearchByProjection: ORBdist must be 0 .. 255");
+  GuidedCandidates c;
+  GuidedSearchDevice(ctx_, grid, pose, kf, alreadyFound, th, c);
+  return GuidedReplay(F, kf, c, ORBdist, mbCheckOrientation);
+}
+int ORBmatcher::SearchByProjection(FrameView& F, const float K[4], const ccm_guided_pose& pose, const KeyFramePoints& kf, const uint8_t* alreadyFound, float th,
+                                   int ORBdist) {
+  if (ORBdist < 0 || ORBdist > 255) throw std::invalid_argument("SearchByProjection: ORBdist must be 0 .. 255");
+  GuidedCandidates c;
+  GuidedSearchHost(F, K, pose, kf, alreadyFound, th, c);
+  return GuidedReplay(F, kf, c, ORBdist, mbCheckOrientation);
+}
+
+int ORBmatcher::SearchByProjectionCandidates(FrameView& F, const KeyFramePoints& kf, const int32_t* candOff, const int32_t* candIdx, int ORBdist) {
+  if (ORBdist < 0 || ORBdist > 255) throw std::invalid_argument("SearchByProjection: ORBdist must be 0 .. 255");
+  if (kf.n < 0 || !candOff || (kf.n && !kf.desc) || candOff[0] != 0) throw std::invalid_argument("SearchByProjection: bad candidate lists");
+  for (int i = 0; i < kf.n; i++) if (candOff[i + 1] < candOff[i]) throw std::invalid_argument("SearchByProjection: bad candidate lists");
+  GuidedCandidates c;
+  c.off.assign(candOff, candOff + kf.n + 1);
+  const int n = kf.n ? candOff[kf.n] : 0;
+  if (n && !candIdx) throw std::invalid_argument("SearchByProjection: bad candidate lists");
+  c.idx.assign(candIdx, candIdx + n);
+  for (int32_t k : c.idx) if (k < 0 || k >= F.N) throw std::invalid_argument("SearchByProjection: a candidate the frame does not have");
+  const std::vector<uint8_t> qdesc(kf.desc, kf.desc + 32 * (size_t)kf.n);
+  distances(qdesc, kf.n, F.mDescriptors, F.N, c.off, c.idx, c.dist);
+  return GuidedReplay(F, kf, c, ORBdist, mbCheckOrientation);
 }
 
 // ---- BoW-bucketed / triangulation / initialisation searches ---------------------------------------------
@@ -842,6 +914,82 @@ int Optimizer::PoseOptimizationClient(HipContext& ctx, double cam_qt[7], int n, 
   check(ccm_pose_optimize(ctx.get(), cam_qt, n, Xw, obs, invSigma2, K, outlier.data(), &ninl), ctx.get(), "ccm_pose_optimize");
   outlier.resize(n);
   return ninl;
+}
+
+// ---- RelocalizationRefine ------------------------------------------------------------------------------------------------------
+namespace {
+// Optimizer::PoseOptimizationClient(Frame&) on the views: the correspondences in ascending feature order, the conversions of ccm_convert.h.  Fewer than three
+// correspondences return 0 and leave the pose.
+int relocPoseOptimization(HipContext& ctx, const FrameView& F, const float K[4], const float* invLevelSigma2, const KeyFramePoints& kf, float Tcw[16],
+                          std::vector<uint8_t>& mvbOutlier) {
+  double cam_qt[7];
+  ccmh::toSE3Quat(Tcw, cam_qt);
+  std::vector<double> Xw, obs, info;
+  std::vector<int> slot;
+  for (int i = 0; i < F.N; i++) {
+    const int32_t s = F.mvpMapPoints[i];
+    if (s < 0) continue;
+    mvbOutlier[i] = 0;
+    const KeyPoint& kp = F.mvKeysUn[i];
+    obs.insert(obs.end(), {(double)kp.x, (double)kp.y});
+    info.push_back((double)invLevelSigma2[kp.octave]);
+    Xw.insert(Xw.end(), {(double)kf.pos[3 * (size_t)s], (double)kf.pos[3 * (size_t)s + 1], (double)kf.pos[3 * (size_t)s + 2]});
+    slot.push_back(i);
+  }
+  if (slot.size() < 3) return 0;
+  const double Kd[4] = {(double)K[0], (double)K[1], (double)K[2], (double)K[3]};
+  std::vector<uint8_t> outlier;
+  const int nInliers = Optimizer::PoseOptimizationClient(ctx, cam_qt, (int)slot.size(), Xw.data(), obs.data(), info.data(), Kd, outlier);
+  for (size_t e = 0; e < slot.size(); e++) mvbOutlier[slot[e]] = outlier[e] != 0;
+  ccmh::toCvMat(cam_qt, Tcw);
+  return nInliers;
+}
+}  // namespace
+
+RelocRefineResult RelocalizationRefine(HipContext& ctx, FrameGridDev& grid, FrameView& F, const float K[4], const float* mvInvLevelSigma2,
+                                       const ccm_guided_pose& frame, const KeyFramePoints& kf, const int32_t* matchesF, const uint8_t* vbInliers) {
+  if (F.N < 0 || (F.N && (!F.mvpMapPoints || !F.mvKeysUn || !matchesF || !vbInliers || !mvInvLevelSigma2)) || !K) throw std::invalid_argument("RelocalizationRefine: null arguments");
+  RelocRefineResult res;
+  ORBmatcher matcher2(ctx, 0.9f, true);
+  std::vector<uint8_t> found((size_t)std::max(kf.n, 1), 0), mvbOutlier((size_t)std::max(F.N, 1), 0);
+  for (int j = 0; j < F.N; j++) {   // the seed
+    const int32_t s = vbInliers[j] ? matchesF[j] : -1;
+    if (s >= kf.n) throw std::invalid_argument("RelocalizationRefine: matchesF names a slot the keyframe does not have");
+    F.mvpMapPoints[j] = s < 0 ? -1 : s;
+    if (s >= 0) found[s] = 1;
+  }
+  ccm_guided_pose pose = frame;
+  float* Tcw = res.Tcw;
+  memcpy(Tcw, frame.Tcw, sizeof(float) * 12);
+  Tcw[12] = 0.f; Tcw[13] = 0.f; Tcw[14] = 0.f; Tcw[15] = 1.f;
+  auto optimise = [&] { return relocPoseOptimization(ctx, F, K, mvInvLevelSigma2, kf, Tcw, mvbOutlier); };
+  auto clearOutliers = [&] { for (int j = 0; j < F.N; j++) if (mvbOutlier[j]) F.mvpMapPoints[j] = -1; };
+  auto search = [&](float th, int ORBdist) {
+    memcpy(pose.Tcw, Tcw, sizeof(float) * 12);
+    return matcher2.SearchByProjection(grid, F, pose, kf, found.data(), th, ORBdist);
+  };
+  int nGood = res.trace[0] = optimise();
+  if (nGood >= 10) {
+    clearOutliers();
+    if (nGood < 50) {
+      const int nadditional = res.trace[1] = search(10.0f, 100);
+      if (nadditional + nGood >= 50) {
+        nGood = res.trace[2] = optimise();
+        if (nGood > 30 && nGood < 50) {   // many inliers but still not enough: a narrower window, the pose being better (the outliers stay in the set)
+          std::fill(found.begin(), found.end(), 0);
+          for (int j = 0; j < F.N; j++) if (F.mvpMapPoints[j] >= 0) found[F.mvpMapPoints[j]] = 1;
+          const int nadd2 = res.trace[3] = search(3.0f, 64);
+          if (nGood + nadd2 >= 50) {
+            nGood = res.trace[4] = optimise();
+            clearOutliers();
+          }
+        }
+      }
+    }
+  }
+  res.nGood = nGood;
+  res.matched = nGood >= 50;
+  return res;
 }
 
 int Optimizer::OptimizeSim3(HipContext& ctx, double g2oS12[8], int n, const double* P1c, const double* P2c, const double* obs1,
@@ -4221,4 +4369,128 @@ extern "C" {
 void ccmh_to_se3quat(const float* Tcw16, double* qt7) { ccmh::toSE3Quat(Tcw16, qt7); }
 void ccmh_se3quat_to_cvmat(const double* qt7, float* Tcw16) { ccmh::toCvMat(qt7, Tcw16); }
 void ccmh_sim3_to_cvse3(const double* s8, float* Tcw16) { ccmh::sim3ToCvSE3(s8, Tcw16); }
+}
+
+// ---- C entry points of the guided search and of the relocalisation refine chain ------------------------------------------------
+namespace {
+struct GuidedFrameArgs {   // a Frame from flat arrays: undistorted keypoints (no distortion coefficients), the bounds of a w x h image
+  std::vector<cslam::KeyPoint> keys;
+  cslam::FrameView F;
+  GuidedFrameArgs(const void* kps_un, const uint8_t* fdesc, int N, const float* bounds, const float* scale_factors, int32_t* frame_mp)
+      : keys((const cslam::KeyPoint*)kps_un, (const cslam::KeyPoint*)kps_un + N) {
+    F.N = N; F.mvKeysUn = keys.data(); F.mDescriptors = fdesc;
+    F.mnMinX = bounds[0]; F.mnMinY = bounds[1]; F.mnMaxX = bounds[2]; F.mnMaxY = bounds[3];
+    F.mvScaleFactors = scale_factors; F.mvpMapPoints = frame_mp;
+  }
+};
+cslam::KeyFramePoints guidedKf(int P, const uint8_t* live, const float* pos, const float* min_dist, const float* max_dist, const uint8_t* desc, const float* angle) {
+  cslam::KeyFramePoints kf;
+  kf.n = P; kf.live = live; kf.pos = pos; kf.min_dist = min_dist; kf.max_dist = max_dist; kf.desc = desc; kf.angle = angle;
+  return kf;
+}
+}  // namespace
+extern "C" {
+// The host evaluator of ccm_frame_guided_search: its arguments after the frame, which is given as arrays; no device is touched.  0, or -1 for its CCM_E_ARG cases.
+int ccmh_guided_search_host(const void* kps_un, const uint8_t* fdesc, int N, const float* bounds, const float* K, const void* pose_v, int P, const float* pos,
+                            const float* min_dist, const float* max_dist, const uint8_t* desc, const uint8_t* skip, float th, uint8_t* status, float* u, float* v,
+                            int32_t* level, int32_t* cand_off, int32_t* cand_idx, uint16_t* cand_dist, int64_t cap, int64_t* n_cand) {
+  try {
+    if (!pose_v || !bounds || !K || N < 0 || (N && (!kps_un || !fdesc)) || P < 0 || !cand_off || !n_cand || (P && (!status || !u || !v || !level)) || cap < 0 ||
+        (cap && (!cand_idx || !cand_dist)))
+      return -1;
+    ccm_guided_pose pose;
+    std::memcpy(&pose, pose_v, sizeof(pose));
+    GuidedFrameArgs fr(kps_un, fdesc, N, bounds, pose.scaleFactors, nullptr);
+    const std::vector<uint8_t> live((size_t)std::max(P, 1), 1);
+    cslam::GuidedCandidates c;
+    cslam::ORBmatcher::GuidedSearchHost(fr.F, K, pose, guidedKf(P, live.data(), pos, min_dist, max_dist, desc, nullptr), skip, th, c);
+    *n_cand = (int64_t)c.idx.size();
+    std::memcpy(cand_off, c.off.data(), sizeof(int32_t) * ((size_t)P + 1));
+    if (P) {
+      std::memcpy(status, c.status.data(), (size_t)P); std::memcpy(u, c.u.data(), sizeof(float) * (size_t)P); std::memcpy(v, c.v.data(), sizeof(float) * (size_t)P);
+      std::memcpy(level, c.level.data(), sizeof(int32_t) * (size_t)P);
+    }
+    if (cap == 0) return 0;
+    if (*n_cand > cap) return -1;
+    if (*n_cand) { std::memcpy(cand_idx, c.idx.data(), sizeof(int32_t) * c.idx.size()); std::memcpy(cand_dist, c.dist.data(), sizeof(uint16_t) * c.dist.size()); }
+    return 0;
+  } catch (const std::invalid_argument&) { return -1;
+  } catch (const std::exception&) { return -1000; }
+}
+
+// ORBmatcher::SearchByProjection(Frame&, kfptr, sAlreadyFound, th, ORBdist): the host mirror without a grid (no device is touched) and with one (a FrameGridDev
+// built from the arrays).  nmatches, -1 for a bad argument, -1000 when the device path throws.  frame_mp: in/out, F.mvpMapPoints.
+int ccmh_search_by_projection_kf_host(const void* kps_un, const uint8_t* fdesc, int N, const float* bounds, const float* K, const void* pose_v, int P,
+                                      const uint8_t* live, const float* pos, const float* min_dist, const float* max_dist, const uint8_t* desc, const float* angle,
+                                      const uint8_t* already_found, float th, int orb_dist, int check_ori, int32_t* frame_mp) {
+  try {
+    if (!pose_v || !bounds || !K || N < 0 || (N && (!kps_un || !fdesc || !frame_mp)) || P < 0) return -1;
+    ccm_guided_pose pose;
+    std::memcpy(&pose, pose_v, sizeof(pose));
+    GuidedFrameArgs fr(kps_un, fdesc, N, bounds, pose.scaleFactors, frame_mp);
+    const cslam::KeyFramePoints kf = guidedKf(P, live, pos, min_dist, max_dist, desc, angle);
+    if (orb_dist < 0 || orb_dist > 255) return -1;
+    cslam::GuidedCandidates c;
+    cslam::ORBmatcher::GuidedSearchHost(fr.F, K, pose, kf, already_found, th, c);
+    return cslam::ORBmatcher::GuidedReplay(fr.F, kf, c, orb_dist, check_ori != 0);
+  } catch (const std::invalid_argument&) { return -1;
+  } catch (const std::exception&) { return -1000; }
+}
+int ccmh_search_by_projection_kf_dev(int device, const float* K, int w, int h, const void* kps_un, const uint8_t* fdesc, int N, const void* pose_v, int P,
+                                     const uint8_t* live, const float* pos, const float* min_dist, const float* max_dist, const uint8_t* desc, const float* angle,
+                                     const uint8_t* already_found, float th, int orb_dist, int check_ori, int32_t* frame_mp) {
+  try {
+    if (!pose_v || !K || N < 0 || (N && (!kps_un || !fdesc || !frame_mp)) || P < 0) return -1;
+    ccm_guided_pose pose;
+    std::memcpy(&pose, pose_v, sizeof(pose));
+    cslam::HipContext& ctx = thread_context(device);
+    cslam::FrameGridDev grid(ctx, K, nullptr, 0, w, h);
+    std::vector<cslam::KeyPoint> keys((const cslam::KeyPoint*)kps_un, (const cslam::KeyPoint*)kps_un + N), keysUn;
+    grid.SetKeyPoints(keys, fdesc, keysUn);
+    const float bounds[4] = {grid.mnMinX, grid.mnMinY, grid.mnMaxX, grid.mnMaxY};
+    GuidedFrameArgs fr(keysUn.data(), fdesc, N, bounds, pose.scaleFactors, frame_mp);
+    cslam::ORBmatcher m(ctx, 0.9f, check_ori != 0);
+    return m.SearchByProjection(grid, fr.F, pose, guidedKf(P, live, pos, min_dist, max_dist, desc, angle), already_found, th, orb_dist);
+  } catch (const std::invalid_argument&) { return -1;
+  } catch (const std::exception&) { return -1000; }
+}
+
+// the drop-in's form: the lists are the caller's Frame::GetFeaturesInArea results (cand_off over the P slots); f_angle: the frame's mvKeysUn[].angle
+int ccmh_search_by_projection_kf_cand(int device, const uint8_t* fdesc, const float* f_angle, int N, int P, const uint8_t* desc, const float* kf_angle,
+                                      const int32_t* cand_off, const int32_t* cand_idx, int orb_dist, int check_ori, int32_t* frame_mp) {
+  try {
+    if (N < 0 || P < 0 || (N && (!fdesc || !f_angle || !frame_mp)) || !cand_off) return -1;
+    cslam::HipContext& ctx = thread_context(device);
+    std::vector<cslam::KeyPoint> keys((size_t)N);
+    for (int i = 0; i < N; i++) keys[i] = cslam::KeyPoint{0.f, 0.f, 31.f, f_angle[i], 0.f, 0};
+    cslam::FrameView F; F.N = N; F.mvKeysUn = keys.data(); F.mDescriptors = fdesc; F.mvpMapPoints = frame_mp;
+    cslam::ORBmatcher m(ctx, 0.9f, check_ori != 0);
+    return m.SearchByProjectionCandidates(F, guidedKf(P, nullptr, nullptr, nullptr, nullptr, desc, kf_angle), cand_off, cand_idx, orb_dist);
+  } catch (const std::invalid_argument&) { return -1;
+  } catch (const std::exception&) { return -1000; }
+}
+
+// cslam::RelocalizationRefine on flat arrays.  1 matched, 0 not, -1 for a bad argument, -1000 when the device path throws.  frame_mp [N], Tcw16, trace5 and n_good: out.
+int ccmh_reloc_refine(int device, const float* K, int w, int h, const void* kps_un, const uint8_t* fdesc, int N, const float* inv_level_sigma2,
+                      const void* frame_v, int P, const uint8_t* live, const float* pos, const float* min_dist, const float* max_dist, const uint8_t* desc,
+                      const float* angle, const int32_t* matches_f, const uint8_t* inliers, int32_t* frame_mp, float* Tcw16, int32_t* trace5, int32_t* n_good) {
+  try {
+    if (!frame_v || !K || N < 0 || (N && (!kps_un || !fdesc || !frame_mp)) || P < 0 || !Tcw16 || !trace5 || !n_good) return -1;
+    ccm_guided_pose frame;
+    std::memcpy(&frame, frame_v, sizeof(frame));
+    cslam::HipContext& ctx = thread_context(device);
+    cslam::FrameGridDev grid(ctx, K, nullptr, 0, w, h);
+    std::vector<cslam::KeyPoint> keys((const cslam::KeyPoint*)kps_un, (const cslam::KeyPoint*)kps_un + N), keysUn;
+    grid.SetKeyPoints(keys, fdesc, keysUn);
+    const float bounds[4] = {grid.mnMinX, grid.mnMinY, grid.mnMaxX, grid.mnMaxY};
+    GuidedFrameArgs fr(keysUn.data(), fdesc, N, bounds, frame.scaleFactors, frame_mp);
+    const cslam::RelocRefineResult r = cslam::RelocalizationRefine(ctx, grid, fr.F, K, inv_level_sigma2, frame, guidedKf(P, live, pos, min_dist, max_dist, desc, angle),
+                                                                   matches_f, inliers);
+    std::memcpy(Tcw16, r.Tcw, sizeof(float) * 16);
+    for (int i = 0; i < 5; i++) trace5[i] = r.trace[i];
+    *n_good = r.nGood;
+    return r.matched ? 1 : 0;
+  } catch (const std::invalid_argument&) { return -1;
+  } catch (const std::exception&) { return -1000; }
+}
 }

@@ -128,9 +128,37 @@ class FrameGridDev {
   ccm_frame* f_ = nullptr;
 };
 
+// What SearchByProjection(Frame&, kfptr, sAlreadyFound, th, ORBdist) reads from the candidate keyframe, per feature slot (ORBmatcher.cpp:1492-1539, :1568)
+struct KeyFramePoints {
+  int n = 0;
+  const uint8_t* live = nullptr;            // pMP && !pMP->isBad()
+  const float* pos = nullptr; const float* min_dist = nullptr; const float* max_dist = nullptr;   // GetWorldPos (n x 3), mfMinDistance, mfMaxDistance
+  const uint8_t* desc = nullptr;            // n x 32, pMP->GetDescriptor()
+  const float* angle = nullptr;             // pKF->mvKeysUn[i].angle
+};
+// What ccm_frame_guided_search returns for the n slots: the gates' outcome and every searched point's window candidates with their distances
+struct GuidedCandidates {
+  std::vector<uint8_t> status; std::vector<float> u, v; std::vector<int32_t> level, off, idx; std::vector<uint16_t> dist;
+};
+
 class ORBmatcher {
  public:
   static const int TH_LOW = 50, TH_HIGH = 100, HISTO_LENGTH = 30;
+  // SearchByProjection(Frame&, kfptr, const set<mpptr>&, th, ORBdist) — ORBmatcher.cpp:1478-1604, the guided search of relocalisation.  pose.Tcw is the frame's
+  // pose (the camera centre is derived from it, never passed); alreadyFound[slot] != 0: the slot's point is in sAlreadyFound (nullable: none).  On a match
+  // F.mvpMapPoints[i2] = the keyframe's slot.  Returns nmatches; ORBdist outside 0 .. 255 throws.  With a grid, the gates, the windows and the distances of all
+  // slots are ONE ccm_frame_guided_search call; without one, the host evaluator (the same header, a host grid, no device) produces the same arrays.  Both end in
+  // GuidedReplay, the sequential pass of :1494-1602.
+  int SearchByProjection(FrameGridDev& grid, FrameView& F, const ccm_guided_pose& pose, const KeyFramePoints& kf, const uint8_t* alreadyFound, float th, int ORBdist);
+  int SearchByProjection(FrameView& F, const float K[4], const ccm_guided_pose& pose, const KeyFramePoints& kf, const uint8_t* alreadyFound, float th, int ORBdist);
+  static void GuidedSearchDevice(HipContext& ctx, FrameGridDev& grid, const ccm_guided_pose& pose, const KeyFramePoints& kf, const uint8_t* alreadyFound, float th,
+                                 GuidedCandidates& out);
+  static void GuidedSearchHost(const FrameView& F, const float K[4], const ccm_guided_pose& pose, const KeyFramePoints& kf, const uint8_t* alreadyFound, float th,
+                               GuidedCandidates& out);
+  static int GuidedReplay(FrameView& F, const KeyFramePoints& kf, const GuidedCandidates& c, int ORBdist, bool checkOrientation);
+  // the drop-in's form (shim/ORBmatcher_hip.cpp): the gates were the caller's own cv::Mat expressions and the lists its Frame::GetFeaturesInArea returned (CSR over
+  // the kf.n slots, empty where a slot did not reach it; kf needs desc and angle only); ONE ccm_hamming_csr launch, then GuidedReplay
+  int SearchByProjectionCandidates(FrameView& F, const KeyFramePoints& kf, const int32_t* candOff, const int32_t* candIdx, int ORBdist);
   ORBmatcher(HipContext& ctx, float nnratio = 0.6f, bool checkOri = true) : ctx_(ctx), mfNNratio(nnratio), mbCheckOrientation(checkOri) {}
   // ORBmatcher.cpp:1653-1669 (host popcount; the batched form is ccm_hamming_*)
   static int DescriptorDistance(const uint8_t* a, const uint8_t* b);
@@ -1035,5 +1063,18 @@ class Optimizer {
                                      const std::vector<int32_t>& e_i, const std::vector<int32_t>& e_j, const std::vector<double>& Sji,
                                      ccm_pg_stats* stats = nullptr);
 };
+
+// What relocalisation does with ONE pose PnPRansacBatch::next() returned (the body ORB-SLAM2's Tracking::Relocalization runs on it): the inliers of
+// matchesF (SearchByBoW(KF, F): F.N entries, each a slot of the candidate keyframe or -1) seed F.mvpMapPoints, PoseOptimizationClient, and with 10 .. 49 inliers the
+// two guided searches (th 10 / ORBdist 100, then th 3 / ORBdist 64) with an optimisation after each.  The matcher is ORBmatcher(0.9, true).  frame.Tcw is the PnP
+// pose (rows 0..2); frame's pyramid members are the Frame's.  F.mvpMapPoints is overwritten.
+struct RelocRefineResult {
+  bool matched = false;
+  int nGood = 0;
+  float Tcw[16];                           // the frame's pose at the end
+  int trace[5] = {-1, -1, -1, -1, -1};     // nGood of optimisation 1, nadd of search 1, nGood 2, nadd 2, nGood 3; -1: the step did not run
+};
+RelocRefineResult RelocalizationRefine(HipContext& ctx, FrameGridDev& grid, FrameView& F, const float K[4], const float* mvInvLevelSigma2,
+                                       const ccm_guided_pose& frame, const KeyFramePoints& kf, const int32_t* matchesF, const uint8_t* vbInliers);
 
 }  // namespace cslam

@@ -253,6 +253,19 @@ int ccmh_mappoint_refresh_eval_resident_host(void* store, int K, const int64_t* 
 void* ccmh_mappoint_refresh_create(void* store, int device, int K, const int64_t* keys, const float* kf_center, int P, const int32_t* obs_off, const int32_t* obs_kf, const int32_t* obs_feat, const float* pos, const int32_t* ref_kf, const int32_t* ref_feat, const float* normal, const float* min_dist, const float* max_dist, int nlevels, const float* scale_factors);
 int ccmh_mappoint_refresh_result(void* h, int P, int32_t* best_obs, uint8_t* desc, uint8_t* has_desc, float* normal, float* min_dist, float* max_dist, uint8_t* status);
 void ccmh_mappoint_refresh_destroy(void* h);
+/* The guided search of relocalisation, ORBmatcher::SearchByProjection(Frame&, kfptr, sAlreadyFound, th, ORBdist), and the refine chain behind a PnP pose (DESIGN.md
+ * section 28).  pose / frame: a ccm_guided_pose (include/ccm_hip.h: Tcw 12 floats, logScaleFactor, nScaleLevels as int32, scaleFactors 16 floats).  The frame is given as
+ * undistorted keypoints (the ccm_keypoint layout) and descriptors; bounds = mnMinX mnMinY mnMaxX mnMaxY; the forms with a device build a FrameGridDev of a w x h image
+ * without distortion.  ccmh_guided_search_host: ccm_frame_guided_search's arguments after the frame through csrc/guided_search_math.h and a host grid, no device (0, or
+ * -1 for its CCM_E_ARG cases).  ccmh_search_by_projection_kf_*: nmatches, frame_mp = F.mvpMapPoints in/out (a keyframe slot or -1); -1 for a bad argument (orb_dist
+ * outside 0 .. 255 among them), -1000 when the device path throws; _cand is the drop-in's form: the lists are the caller's own Frame::GetFeaturesInArea results (CSR over
+ * the P slots), ONE ccm_hamming_csr launch and the sequential pass.  ccmh_reloc_refine: cslam::RelocalizationRefine; 1 matched, 0 not; frame_mp, Tcw16, trace5 (nGood of
+ * optimisation 1, nadd of search 1, nGood 2, nadd 2, nGood 3; -1: the step did not run) and n_good are outputs. */
+int ccmh_guided_search_host(const void* kps_un, const uint8_t* fdesc, int N, const float* bounds, const float* K, const void* pose, int P, const float* pos, const float* min_dist, const float* max_dist, const uint8_t* desc, const uint8_t* skip, float th, uint8_t* status, float* u, float* v, int32_t* level, int32_t* cand_off, int32_t* cand_idx, uint16_t* cand_dist, int64_t cap, int64_t* n_cand);
+int ccmh_search_by_projection_kf_host(const void* kps_un, const uint8_t* fdesc, int N, const float* bounds, const float* K, const void* pose, int P, const uint8_t* live, const float* pos, const float* min_dist, const float* max_dist, const uint8_t* desc, const float* angle, const uint8_t* already_found, float th, int orb_dist, int check_ori, int32_t* frame_mp);
+int ccmh_search_by_projection_kf_dev(int device, const float* K, int w, int h, const void* kps_un, const uint8_t* fdesc, int N, const void* pose, int P, const uint8_t* live, const float* pos, const float* min_dist, const float* max_dist, const uint8_t* desc, const float* angle, const uint8_t* already_found, float th, int orb_dist, int check_ori, int32_t* frame_mp);
+int ccmh_search_by_projection_kf_cand(int device, const uint8_t* fdesc, const float* f_angle, int N, int P, const uint8_t* desc, const float* kf_angle, const int32_t* cand_off, const int32_t* cand_idx, int orb_dist, int check_ori, int32_t* frame_mp);
+int ccmh_reloc_refine(int device, const float* K, int w, int h, const void* kps_un, const uint8_t* fdesc, int N, const float* inv_level_sigma2, const void* frame, int P, const uint8_t* live, const float* pos, const float* min_dist, const float* max_dist, const uint8_t* desc, const float* angle, const int32_t* matches_f, const uint8_t* inliers, int32_t* frame_mp, float* Tcw16, int32_t* trace5, int32_t* n_good);
 
 #ifdef __cplusplus
 }

@@ -211,6 +211,26 @@ int  ccm_frame_window_search(ccm_frame* f, int Q, const float* u, const float* v
                              int32_t* cand_off /* Q+1 */, int32_t* cand_idx, uint16_t* cand_dist, int64_t cap,
                              int64_t* n_cand);
 
+/* ORBmatcher::SearchByProjection(Frame&, kfptr, const set<mpptr>&, th, ORBdist) (ORBmatcher.cpp:1478-1604), the guided search of
+ * relocalisation, up to its sequential pass: for all P map points of the keyframe at once the projection with the frame's pose and
+ * its gates (:1482-1532, csrc/guided_search_math.h), the window of Frame::GetFeaturesInArea(u, v, th * mvScaleFactors[level],
+ * level - 1, level + 1) on the resident grid, and the Hamming distance of every candidate.  The intrinsics and the image bounds are
+ * the ccm_frame's own.  Tcw = rows 0..2 of mTcw, row-major; the camera centre is derived from it.  skip[i] != 0 (no live map point
+ * in the slot, or the point is in sAlreadyFound; nullable: none) and every point a gate rejects have an empty list.
+ * status: 0 skipped, 1 outside the image, 2 outside the distance range, 3 searched; u, v are written from status 1 on, level for 3.
+ * cand_off / cand_idx / cand_dist, cap, n_cand and the sizing call (cap = 0) are ccm_frame_window_search's.
+ * CCM_E_ARG: a null argument with P > 0, P < 0, nScaleLevels outside 1..16, th negative or not finite, cap too small (n_cand is set). */
+typedef struct {
+  float Tcw[12];
+  float logScaleFactor;
+  int32_t nScaleLevels;
+  float scaleFactors[16];
+} ccm_guided_pose;
+int  ccm_frame_guided_search(ccm_frame* f, const ccm_guided_pose* pose, int P, const float* pos /* P x 3 */, const float* min_dist,
+                             const float* max_dist, const uint8_t* desc /* P x 32 */, const uint8_t* skip /* P, nullable */, float th,
+                             uint8_t* status, float* u, float* v, int32_t* level, int32_t* cand_off /* P+1 */, int32_t* cand_idx,
+                             uint16_t* cand_dist, int64_t cap, int64_t* n_cand);
+
 /* Frame::isInFrustum (Frame.cpp:139-198) for a batch of map points — Tracking::SearchLocalPoints' visibility loop.
  * The struct carries what the frame contributes (mRcw row-major, mtcw, mOw, intrinsics, image bounds, mfLogScaleFactor,
  * mnScaleLevels); per point: world position, mean viewing direction (GetNormal), mfMinDistance / mfMaxDistance.

@@ -167,10 +167,58 @@ int ORBmatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, 
   return nmatches;
 }
 
-// ORBmatcher.cpp:1478-1604 — the relocalisation search has no caller in CCM-SLAM: Tracking never relocalises against a keyframe.
-int ORBmatcher::SearchByProjection(Frame&, kfptr, const std::set<mpptr>&, const float, const int) {
-  cout << COUTFATAL << "ORBmatcher::SearchByProjection(Frame, KeyFrame, sAlreadyFound): not part of the CCM-SLAM hot path, not provided by the MI355X build" << endl;
-  throw estd::infrastructure_ex();
+// ORBmatcher.cpp:1478-1604 — the guided search of relocalisation, by the route of M1 / M2: the gates are the reference's own cv::Mat expressions, the window lists the
+// Frame's own GetFeaturesInArea; the Hamming distances of all lists are one ccm_hamming_csr launch and the sequential pass (claims, strict minimum, inclusive ORBdist,
+// rotation histogram) is the mirror's.  A feature that holds any map point is skipped, as the source's `if(CurrentFrame.mvpMapPoints[i2])` does.
+int ORBmatcher::SearchByProjection(Frame& CurrentFrame, kfptr pKF, const std::set<mpptr>& sAlreadyFound, const float th, const int ORBdist) {
+  const std::vector<mpptr> vpMPs = pKF->GetMapPointMatches();
+  const int n = (int)vpMPs.size();
+  if (n == 0 || CurrentFrame.N == 0) return 0;
+  if (ORBdist < 0 || ORBdist > 255) {   // at 256 the source would index with bestIdx2 = -1
+    cout << COUTFATAL << "ORBmatcher::SearchByProjection(Frame, KeyFrame, sAlreadyFound): ORBdist must be 0 .. 255" << endl;
+    throw estd::infrastructure_ex();
+  }
+  const cv::Mat Rcw = CurrentFrame.mTcw.rowRange(0, 3).colRange(0, 3);
+  const cv::Mat tcw = CurrentFrame.mTcw.rowRange(0, 3).col(3);
+  const cv::Mat Ow = -Rcw.t() * tcw;
+  FlatKeys K(CurrentFrame.mvKeysUn, CurrentFrame.mDescriptors);
+  std::vector<uint8_t> desc(32 * (size_t)n, 0);
+  std::vector<float> angle(n, 0.f);
+  std::vector<int32_t> off(n + 1, 0), idx;
+  for (int i = 0; i < n; i++) {
+    const mpptr& pMP = vpMPs[i];
+    if (pMP && !pMP->isBad() && !sAlreadyFound.count(pMP)) {
+      const cv::Mat x3Dw = pMP->GetWorldPos();
+      const cv::Mat x3Dc = Rcw * x3Dw + tcw;
+      const float xc = x3Dc.at<float>(0), yc = x3Dc.at<float>(1);
+      const float invzc = 1.0 / x3Dc.at<float>(2);
+      const float u = CurrentFrame.fx * xc * invzc + CurrentFrame.cx;
+      const float v = CurrentFrame.fy * yc * invzc + CurrentFrame.cy;
+      const bool inside = !(u < Frame::mnMinX || u > Frame::mnMaxX) && !(v < Frame::mnMinY || v > Frame::mnMaxY);
+      if (inside) {
+        const cv::Mat PO = x3Dw - Ow;
+        const float dist3D = cv::norm(PO);
+        if (!(dist3D < pMP->GetMinDistanceInvariance() || dist3D > pMP->GetMaxDistanceInvariance())) {
+          const int nPredictedLevel = pMP->PredictScale(dist3D, CurrentFrame.shared_from_this());
+          const float radius = th * CurrentFrame.mvScaleFactors[nPredictedLevel];
+          const std::vector<size_t> vIndices2 = CurrentFrame.GetFeaturesInArea(u, v, radius, nPredictedLevel - 1, nPredictedLevel + 1);
+          for (size_t k = 0; k < vIndices2.size(); k++) idx.push_back((int32_t)vIndices2[k]);
+          put_desc(desc, i, pMP->GetDescriptor());
+          angle[i] = pKF->mvKeysUn[i].angle;
+        }
+      }
+    }
+    off[i + 1] = (int32_t)idx.size();
+  }
+  const int32_t FOREIGN = INT_MAX;
+  std::vector<int32_t> table(CurrentFrame.N, -1);
+  for (int j = 0; j < CurrentFrame.N; j++) if (CurrentFrame.mvpMapPoints[j]) table[j] = FOREIGN;
+  if (idx.empty()) idx.push_back(0);
+  const int nmatches = checked(ccmh_search_by_projection_kf_cand(device(), K.desc, K.angle.data(), K.N, n, desc.data(), angle.data(), off.data(), idx.data(), ORBdist,
+                                                                 mbCheckOrientation ? 1 : 0, table.data()), "SearchByProjection(Frame, KeyFrame, sAlreadyFound)");
+  if (nmatches < 0) { cout << COUTFATAL << "ORBmatcher::SearchByProjection(Frame, KeyFrame, sAlreadyFound): bad arguments" << endl; throw estd::infrastructure_ex(); }
+  for (int j = 0; j < CurrentFrame.N; j++) if (table[j] >= 0 && table[j] != FOREIGN) CurrentFrame.mvpMapPoints[j] = vpMPs[table[j]];
+  return nmatches;
 }
 
 // M9 — ORBmatcher.cpp:308-446
