@@ -66,6 +66,20 @@ __device__ __forceinline__ double bcast64(double v, int lane) {
   const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), lane), hi = __builtin_amdgcn_readlane((int)(b >> 32), lane);
   return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
+// A pivot is accepted when it is positive AND finite: rsqrt(+inf) = 0 would turn the column into inf * 0 = NaN and pass the NaN on unreported
+// (a NaN pivot already fails `> 0`).
+__device__ __forceinline__ bool pivot_ok(double dd) { return dd > 0.0 && dd < __builtin_inf(); }
+// *info = min(*info, col1) with 0 standing for "none yet" (the memset of the entry points), col1 = failing global column + 1.  A compare-and-swap, not a
+// check-then-store: the diagonal tiles of one elimination level of the tile-sparse form run in ONE launch, and levels are not in column order, so the smallest
+// column has to win whoever arrives first.  Reached by lane 0 of a failing tile only; each retry means another tile's report went in, so at most one per tile.
+__device__ __forceinline__ void report_pivot(int* info, int col1) {
+  int old = __hip_atomic_load(info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  while (old == 0 || old > col1) {
+    const int seen = atomicCAS(info, old, col1);
+    if (seen == old) break;
+    old = seen;
+  }
+}
 // Two waves in a software pipeline: wave 0 factors column c while wave 1 does row c-1 of the forward substitution for
 // L^-1 (it needs row c-1 of L and its reciprocal pivot, both final after step c-1); one block barrier per column.
 // Ajj: the diagonal tile (row stride N doubles), Lg: where its inverse factor goes (64 x 64, contiguous), j: tile index for `info`
@@ -107,7 +121,7 @@ __device__ __forceinline__ void chol_diag_body(double* Ajj, size_t N, int j, dou
         }
         const double sv = (acc[0] + acc[1]) + (acc[2] + acc[3]);
         double dd = bcast64(sv, c);
-        if (!(dd > 0.0)) { if (!bad_col) bad_col = c + 1; dd = 1.0; }
+        if (!pivot_ok(dd)) { if (!bad_col) bad_col = c + 1; dd = 1.0; }
         const double inv = rsqrt(dd), l = dd * inv;
         row[c] = (lane == c) ? l : sv * inv;           // lanes < c hold the (unused) upper part
         L[lane * LR + c] = row[c];
@@ -129,7 +143,7 @@ __device__ __forceinline__ void chol_diag_body(double* Ajj, size_t N, int j, dou
     __syncthreads();
   }
   if (wv == 0) {
-    if (bad_col && lane == 0 && *info == 0) *info = j * NB + bad_col;
+    if (bad_col && lane == 0) report_pivot(info, j * NB + bad_col);
 #pragma unroll
     for (int r = 0; r < NB; r++) Ajj[(size_t)r * N + lane] = (lane <= r) ? L[r * LR + lane] : 0.0;
   }
@@ -196,7 +210,7 @@ __device__ __forceinline__ void chol_diag_body_blk(double* Ajj, size_t N, int j,
         }
         const double sv = s0 + s1;
         double dd = bcast64(sv, c0 + c);
-        if (!(dd > 0.0)) { if (!bad_col) bad_col = c0 + c + 1; dd = 1.0; }
+        if (!pivot_ok(dd)) { if (!bad_col) bad_col = c0 + c + 1; dd = 1.0; }
         const double inv = rsqrt(dd);
         row[c] = (lane == c0 + c) ? dd * inv : sv * inv;   // lanes above the diagonal hold unused values
         if (lane == c0 + c) rdiag[c0 + c] = inv;
@@ -206,7 +220,7 @@ __device__ __forceinline__ void chol_diag_body_blk(double* Ajj, size_t N, int j,
       for (int c = 0; c < KB; c += 2) { double2 v; v.x = row[c]; v.y = row[c + 1]; *reinterpret_cast<double2*>(&L[lane * LR + c0 + c]) = v; }
       __syncthreads();
     }
-    if (bad_col && lane == 0 && *info == 0) *info = j * NB + bad_col;
+    if (bad_col && lane == 0) report_pivot(info, j * NB + bad_col);
 #pragma unroll
     for (int r = 0; r < NB; r++) Ajj[(size_t)r * N + lane] = (lane <= r) ? L[r * LR + lane] : 0.0;
   } else if (wv == 2) {
@@ -620,7 +634,8 @@ __global__ __launch_bounds__(kTPB) void chol_xtx(const double* X, int N, double*
 
 // Solves A x = b for a symmetric positive definite A.  d_A: N x N row-major with N = n rounded up to 64 (ccm_dense_padded)
 // and the padding rows / columns already set to the identity; only the lower triangle is read; destroyed.  d_b: [N], in: rhs,
-// out: x.  d_linv: scratch [N/64][64*64].  d_info: device int, set to (first non-positive pivot + 1) or left 0.
+// out: x.  d_linv: scratch [N/64][64*64].  d_info: device int, 0 or LAPACK's report: (the smallest column whose pivot is not positive and finite) + 1; the
+// columns after it, and x, then hold no meaning.  plan: visit only the tiles a symbolic elimination marks (ccm_tile_plan_symbolic + device copies of its lists).
 int ccm_dense_chol_solve_dev(ccm_ctx* ctx, double* d_A, int N, double* d_b, double* d_linv, int* d_info, const ccm_tile_plan* plan) {
   if (N % NB) return ccm_set_error(ctx, CCM_E_ARG, "dense cholesky: N must be a multiple of 64");
   const int T = N / NB;
@@ -764,7 +779,8 @@ int ccm_tsc_clear(ccm_ctx* ctx, ccm_tsc* p) {
   CCM_HIP_CHECK(ctx, hipMemsetAsync(p->d_tiles, 0, (size_t)p->n_tiles * NB * NB * sizeof(double), ctx->stream));
   return CCM_OK;
 }
-// factorises the tiles in place and solves for d_b ([64 T], in: rhs, out: x); *d_info = first non-positive pivot + 1 or 0
+// factorises the tiles in place and solves for d_b ([64 T], in: rhs, out: x); *d_info = 0 or (the smallest column whose pivot is not positive and finite) + 1:
+// the minimum over all failing tiles whatever their levels (report_pivot), which is the column a column-by-column elimination stops at
 int ccm_tsc_solve(ccm_ctx* ctx, ccm_tsc* p, double* d_b) {
   const int T = p->T;
   CCM_HIP_CHECK(ctx, hipMemsetAsync(p->d_info, 0, sizeof(int), ctx->stream));
@@ -816,6 +832,49 @@ int ccm_internal::debug_dense_solve(ccm_ctx* ctx, const double* A, const double*
     for (int i = 0; i < n; i++) x[i] = bp[i];
   }
   hipFree(dA); hipFree(db); hipFree(dl); hipFree(di);
+  return rc;
+}
+
+// Test hook for the PLANNED dense solve (what CCM_PG_SOLVER=dense runs): the tile pattern is taken from the non-zeros of the host matrix, its fill added by
+// ccm_tile_plan_symbolic, the three lists copied to the device the way posegraph.hip does, then ccm_dense_chol_solve_dev with that plan.
+int ccm_internal::debug_planned_solve(ccm_ctx* ctx, const double* A, const double* b, int n, double* x, int* info) {
+  if (!ctx || !A || !b || !x || !info || n <= 0) return ccm_set_error(ctx, CCM_E_ARG, "ccm_debug_planned_solve: bad args");
+  CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const int N = ((n + NB - 1) / NB) * NB, T = N / NB;
+  std::vector<char> nz((size_t)T * T, 0);
+  for (int i = 0; i < n; i++) for (int c = 0; c <= i; c++) if (A[(size_t)i * n + c] != 0.0) nz[(size_t)(i / NB) * T + c / NB] = 1;
+  for (int t = 0; t < T; t++) nz[(size_t)t * T + t] = 1;
+  ccm_tile_plan plan;
+  std::vector<int> lists[3];   // col_rows, upd_pairs, row_cols
+  ccm_tile_plan_symbolic(T, nz, &plan, &lists[0], &lists[1], &lists[2]);
+  std::vector<double> Ap((size_t)N * N, 0.0), bp(N, 0.0);
+  for (int i = 0; i < N; i++) {
+    if (i < n) { for (int c = 0; c < n; c++) Ap[(size_t)i * N + c] = A[(size_t)i * n + c]; bp[i] = b[i]; }
+    else Ap[(size_t)i * N + i] = 1.0;
+  }
+  double *dA = nullptr, *db = nullptr, *dl = nullptr; int* di = nullptr; int* dlist[3] = {nullptr, nullptr, nullptr};
+  auto release = [&]() { hipFree(dA); hipFree(db); hipFree(dl); hipFree(di); for (int* p : dlist) hipFree(p); };
+  int rc = CCM_OK;
+  if (hipMalloc(&dA, Ap.size() * sizeof(double)) != hipSuccess || hipMalloc(&db, N * sizeof(double)) != hipSuccess ||
+      hipMalloc(&dl, (size_t)N * NB * sizeof(double)) != hipSuccess || hipMalloc(&di, sizeof(int)) != hipSuccess)
+    rc = ccm_set_error(ctx, CCM_E_HIP, "ccm_debug_planned_solve: hipMalloc");
+  for (int k = 0; k < 3 && rc == CCM_OK; k++) {
+    if (hipMalloc(&dlist[k], std::max<size_t>(lists[k].size(), 1) * sizeof(int)) != hipSuccess) rc = ccm_set_error(ctx, CCM_E_HIP, "ccm_debug_planned_solve: hipMalloc");
+    else if (!lists[k].empty()) hipMemcpyAsync(dlist[k], lists[k].data(), lists[k].size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
+  }
+  if (rc == CCM_OK) {
+    plan.d_col_rows = dlist[0]; plan.d_upd_pairs = dlist[1]; plan.d_row_cols = dlist[2];
+    hipMemcpyAsync(dA, Ap.data(), Ap.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    hipMemcpyAsync(db, bp.data(), N * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    rc = ccm_dense_chol_solve_dev(ctx, dA, N, db, dl, di, &plan);
+  }
+  if (rc == CCM_OK) {
+    hipMemcpyAsync(bp.data(), db, N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+    hipMemcpyAsync(info, di, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) rc = ccm_set_error(ctx, CCM_E_HIP, "ccm_debug_planned_solve: sync");
+    for (int i = 0; i < n; i++) x[i] = bp[i];
+  } else hipStreamSynchronize(ctx->stream);   // the host vectors leave scope: no copy may still read them
+  release();
   return rc;
 }
 

@@ -89,6 +89,7 @@ extern "C" int ccm_comm_loopback_create(int nranks, void** group) { return ccm_i
 extern "C" void ccm_comm_loopback_destroy(void* group) { ccm_internal::comm_loopback_destroy(group); }
 extern "C" int ccm_comm_init_loopback(ccm_ctx* ctx, void* group, int rank) { return ccm_internal::comm_init_loopback(ctx, group, rank); }
 extern "C" int ccm_debug_dense_solve(ccm_ctx* ctx, const double* A, const double* b, int n, double* x, int* info) { return ccm_internal::debug_dense_solve(ctx, A, b, n, x, info); }
+extern "C" int ccm_debug_planned_solve(ccm_ctx* ctx, const double* A, const double* b, int n, double* x, int* info) { return ccm_internal::debug_planned_solve(ctx, A, b, n, x, info); }
 extern "C" int ccm_debug_tile_solve(ccm_ctx* ctx, const double* A, const double* b, int n, double* x, int* info, int* levels, int* tiles) { return ccm_internal::debug_tile_solve(ctx, A, b, n, x, info, levels, tiles); }
 extern "C" int ccm_debug_dense_inverse(ccm_ctx* ctx, const double* A, int n, double* Ainv, int* info) { return ccm_internal::debug_dense_inverse(ctx, A, n, Ainv, info); }
 extern "C" int ccm_debug_pg_solve(ccm_ctx* ctx, int n_vert, const double* sim3, const uint8_t* fixed, int fix_scale, int n_edge, const int32_t* e_i, const int32_t* e_j,

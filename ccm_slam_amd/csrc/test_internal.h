@@ -14,6 +14,7 @@ int  comm_loopback_create(int nranks, void** group);
 void comm_loopback_destroy(void* group);
 int  comm_init_loopback(ccm_ctx* ctx, void* group, int rank);
 int  debug_dense_solve(ccm_ctx* ctx, const double* A, const double* b, int n, double* x, int* info);
+int  debug_planned_solve(ccm_ctx* ctx, const double* A, const double* b, int n, double* x, int* info);
 int  debug_tile_solve(ccm_ctx* ctx, const double* A, const double* b, int n, double* x, int* info, int* levels, int* tiles);
 int  debug_dense_inverse(ccm_ctx* ctx, const double* A, int n, double* Ainv, int* info);
 int  orb_debug_timing(const ccm_orb* o, double out_ms[6]);

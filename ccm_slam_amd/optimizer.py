@@ -367,6 +367,14 @@ def debug_dense_solve(ctx: Context, A, b):
     return x, info.value
 
 
+def debug_planned_solve(ctx: Context, A, b):
+    """Test hook: the same solve with a tile plan built from A's non-zero 64 x 64 tiles (ccm_debug_planned_solve)."""
+    A = np.ascontiguousarray(A, np.float64); b = np.ascontiguousarray(b, np.float64)
+    x = np.zeros_like(b); info = C.c_int(0)
+    check(hooks().ccm_debug_planned_solve(ctx.handle, C.c_void_p(_vp(A)), C.c_void_p(_vp(b)), int(b.size), C.c_void_p(_vp(x)), C.byref(info)), ctx.handle)
+    return x, info.value
+
+
 def debug_tile_solve(ctx: Context, A, b):
     """Test hook: SPD solve through the tile-sparse, level-scheduled Cholesky (ccm_debug_tile_solve); returns (x, info, levels, tiles)."""
     A = np.ascontiguousarray(A, np.float64); b = np.ascontiguousarray(b, np.float64)

@@ -47,8 +47,12 @@ void ccm_comm_loopback_destroy(void* group);
 int  ccm_comm_init_loopback(ccm_ctx* ctx, void* group, int rank);
 
 /* test hook for the dense f64 Cholesky (MFMA tiles) behind ccm_pose_graph_optimize: solves A x = b for a host matrix
- * (n x n row-major, symmetric positive definite); *info = 0 or (first non-positive pivot + 1). */
+ * (n x n row-major, symmetric positive definite); *info = 0 or (the smallest column whose pivot is not positive and finite) + 1, in
+ * every hook of this family. */
 int  ccm_debug_dense_solve(ccm_ctx* ctx, const double* A, const double* b, int n, double* x, int* info);
+/* the same solve with a tile plan (what CCM_PG_SOLVER=dense runs): the panel, the trailing update and the substitutions visit only the
+ * 64 x 64 tiles that a symbolic elimination of A's non-zero tiles marks. */
+int  ccm_debug_planned_solve(ccm_ctx* ctx, const double* A, const double* b, int n, double* x, int* info);
 /* test hook for the tile-sparse, level-scheduled form of the same factorisation (what ccm_pose_graph_optimize uses by default): only the
  * non-zero 64 x 64 tiles of the factor are stored, tile columns of one elimination level run in one launch; the tile pattern is taken from
  * the non-zeros of A.  levels / tiles (nullable) receive the plan's level and tile counts. */
