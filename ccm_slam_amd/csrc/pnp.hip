@@ -1,40 +1,28 @@
 // pnp.hip — the RANSAC hypotheses of cslam::PnPsolver (cslam/src/PnPSolver.cpp) on the device: ccm_pnp_ransac_eval.
 //
 // Layout: K candidates in CSR over pt_off, per point mvP3Dw (f32 x 3), mvP2D (f32 x 2) and mvMaxError (f32), per candidate fu fv uc vc (f64).
-// H hypotheses, each a candidate and four distinct point indices (the host already mapped the random draws).  One wave64 per hypothesis, 4 waves per workgroup,
-// as in sim3ransac.hip: lane 0 runs the serial EPnP compute_pose of pnp_math.h on its four correspondences and hands R and t to the wave through lane shuffles; the
-// lanes then stride over the candidate's points and a ballot gives 64 inlier bits at a time (two mask words) and the count.  The solve's two large run-time
-// indexed arrays (M, 8 x 12, and M' M / Ut, 12 x 12, f64) live in an LDS slice per wave: in private memory they would be scratch for all 64 lanes of a wave of
-// which one works.  The Jacobi sweeps stay on one lane: every sum keeps the header's sequential order, so the device equals the host evaluator bit for bit.
+// H hypotheses, each a candidate and four distinct point indices (the host already mapped the random draws).  One wave64 per hypothesis, kRansacWavesPerBlock waves
+// per workgroup: lane 0 runs the serial EPnP compute_pose of pnp_math.h on its four correspondences and hands R and t to the wave through lane shuffles; the lanes
+// then stride over the candidate's points and a ballot gives 64 inlier bits at a time (two mask words) and the count.  The solve's two large run-time indexed arrays
+// (M, 8 x 12, and M' M / Ut, 12 x 12, f64) live in an LDS slice per wave: in private memory they would be scratch for all 64 lanes of a wave of which one works.
+// The Jacobi sweeps stay on one lane: every sum keeps the header's sequential order, so the device equals the host evaluator bit for bit.
+//
+// The wave is that of ransac_wave.h, written out.  It is not ransac_wave<F>: this kernel runs at 256 VGPRs and one wave per SIMD and its time is lane 0's solve,
+// and as soon as the call of pnp_compute_pose sits in a function of its own (a form's solve, force-inlined or not) the compiler forwards compute_pose's Betas
+// through registers instead of scratch, which costs 156 more AGPR copies in the solve (1 172 against 1 016) at the same arithmetic.  The checks of the entry
+// point, the arguments and the host walk (PnpHypForm of pnp_math.h) are the shared ones.
 #include "common.h"
 #include "pnp_math.h"
+#include "ransac_wave.h"
 #include "stage_blocks.h"
 
 namespace {
 
-constexpr int kWavesPerBlock = 4;
-constexpr int kWorkDoubles = 96 + 144;   // M (2 * 4 rows of 12), then M' M / Ut
-
-struct PnpRansacArgs {
-  int K, H;
-  const double* cam;       // [K * 4]
-  const int32_t* pt_off;   // [K + 1]
-  const float* P3Dw;       // [Ntot * 3]
-  const float* P2D;        // [Ntot * 2]
-  const float* max_err;    // [Ntot]
-  const int32_t* hyp_cand; // [H]
-  const int32_t* hyp_idx;  // [H * 4], candidate-local
-  const int32_t* mask_off; // [H + 1] words
-  double* Rt;              // [H * 12]: R (9), t (3)
-  int32_t* n_inl;          // [H]
-  uint32_t* mask;          // [mask_off[H]]
-};
-
-__global__ __launch_bounds__(64 * kWavesPerBlock) void pnp_ransac_kernel(PnpRansacArgs a) {
-  __shared__ double s_work[kWavesPerBlock][kWorkDoubles];
+__global__ __launch_bounds__(64 * kRansacWavesPerBlock) void pnp_ransac_kernel(PnpRansacArgs a) {
+  __shared__ double s_work[kRansacWavesPerBlock][PnpHypForm::kWorkDoubles];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
-  const int h = blockIdx.x * kWavesPerBlock + wave;
+  const int h = blockIdx.x * kRansacWavesPerBlock + wave;
   if (h >= a.H) return;   // whole waves only: no barrier below
   const int c = a.hyp_cand[h];
   const int p0 = a.pt_off[c], N = a.pt_off[c + 1] - p0;
@@ -80,26 +68,9 @@ extern "C" int ccm_pnp_ransac_eval(ccm_ctx* ctx, int K, const int32_t* pt_off, c
   if (!ctx) return CCM_E_ARG;
   if (K < 1 || H < 0 || !pt_off || !P3Dw || !P2D || !max_err || !cam || !mask_off || (H > 0 && (!hyp_cand || !hyp_idx || !n_inl || !Rt || !mask)))
     return ccm_set_error(ctx, CCM_E_ARG, "ccm_pnp_ransac_eval: bad args");
-  if (pt_off[0] != 0) return ccm_set_error(ctx, CCM_E_ARG, "ccm_pnp_ransac_eval: pt_off[0] != 0");
-  for (int c = 0; c < K; c++)
-    if (pt_off[c + 1] - pt_off[c] < 4) return ccm_set_error(ctx, CCM_E_ARG, "ccm_pnp_ransac_eval: a candidate with fewer than 4 points");
-  // words of each hypothesis' mask, and the index checks (every index < N of its candidate, four distinct)
   int64_t words = 0;
-  mask_off[0] = 0;
-  for (int h = 0; h < H; h++) {
-    const int c = hyp_cand[h];
-    if (c < 0 || c >= K) return ccm_set_error(ctx, CCM_E_ARG, "ccm_pnp_ransac_eval: hypothesis candidate out of range");
-    const int N = pt_off[c + 1] - pt_off[c];
-    const int32_t* ix = hyp_idx + 4 * (size_t)h;
-    for (int j = 0; j < 4; j++) {
-      if (ix[j] < 0 || ix[j] >= N) return ccm_set_error(ctx, CCM_E_ARG, "ccm_pnp_ransac_eval: point index out of range");
-      for (int k = 0; k < j; k++)
-        if (ix[k] == ix[j]) return ccm_set_error(ctx, CCM_E_ARG, "ccm_pnp_ransac_eval: repeated point index in a hypothesis");
-    }
-    words += (N + 31) >> 5;
-    if (words > INT32_MAX) return ccm_set_error(ctx, CCM_E_ARG, "ccm_pnp_ransac_eval: mask too large");
-    mask_off[h + 1] = (int32_t)words;
-  }
+  if (const RansacCheck r = ransac_check_hyps<4>(K, pt_off, H, hyp_cand, hyp_idx, mask_off, &words, /*range_first=*/false))
+    return ccm_set_error(ctx, CCM_E_ARG, "ccm_pnp_ransac_eval: " + ransac_check_text(r, 4));
   if (H == 0) return CCM_OK;
   PnpRansacBlock b((size_t)K, (size_t)pt_off[K], (size_t)H, (size_t)words);
   if (int rc = ccm_staged_begin(ctx, b, "ccm_pnp_ransac_eval: ")) return rc;
@@ -111,7 +82,7 @@ extern "C" int ccm_pnp_ransac_eval(ccm_ctx* ctx, int K, const int32_t* pt_off, c
   a.cam = b.dev(b.cam); a.pt_off = b.dev(b.pt_off); a.P3Dw = b.dev(b.P3Dw); a.P2D = b.dev(b.P2D); a.max_err = b.dev(b.max_err);
   a.hyp_cand = b.dev(b.hyp_cand); a.hyp_idx = b.dev(b.hyp_idx); a.mask_off = b.dev(b.mask_off);
   a.Rt = b.dev(b.Rt); a.n_inl = b.dev(b.n_inl); a.mask = b.dev(b.mask);
-  hipLaunchKernelGGL(pnp_ransac_kernel, dim3((H + kWavesPerBlock - 1) / kWavesPerBlock), dim3(64 * kWavesPerBlock), 0, ctx->stream, a);
+  hipLaunchKernelGGL(pnp_ransac_kernel, dim3((H + kRansacWavesPerBlock - 1) / kRansacWavesPerBlock), dim3(64 * kRansacWavesPerBlock), 0, ctx->stream, a);
   CCM_HIP_CHECK(ctx, hipGetLastError());
   if (int rc = ccm_staged_download(ctx, b)) return rc;
   b.get(b.n_inl, n_inl); b.get(b.Rt, Rt); b.get(b.mask, mask);

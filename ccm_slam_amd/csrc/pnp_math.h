@@ -18,6 +18,11 @@
 #include "twoview_math.h"
 
 #define PNP_HD TV_HD
+#if defined(__HIPCC__)
+#define PNP_HDM __host__ __device__
+#else
+#define PNP_HDM
+#endif
 
 // ---- the restated C-API calls -------------------------------------------------------------------------------------------------------------------
 // cvMulTransposed(A, D, 1) for a rows x C matrix A: D = A' A (C x C)
@@ -535,3 +540,43 @@ PNP_HD bool pnp_inlier(const double R[9], const double t[3], const double* cam, 
 
 // mvMaxError[i] = mvSigma2[i] * th2 (:146): a float product
 PNP_HD float pnp_max_error(float sigma2, float th2) { return sigma2 * th2; }
+
+// ---- one hypothesis over the arguments of ccm_pnp_ransac_eval: the host + device members of a form of ransac_wave.h -------------------------------------------
+struct PnpRansacArgs {
+  int K, H;
+  const double* cam;       // [K * 4]
+  const int32_t* pt_off;   // [K + 1]
+  const float* P3Dw;       // [Ntot * 3]
+  const float* P2D;        // [Ntot * 2]
+  const float* max_err;    // [Ntot]
+  const int32_t* hyp_cand; // [H]
+  const int32_t* hyp_idx;  // [H * 4], candidate-local
+  const int32_t* mask_off; // [H + 1] words
+  double* Rt;              // [H * 12]: R (9), t (3)
+  int32_t* n_inl;          // [H]
+  uint32_t* mask;          // [mask_off[H]]
+};
+
+struct PnpHypForm {
+  typedef PnpRansacArgs Args;
+  static constexpr int S = 4, kWorkDoubles = 96 + 144;   // the solve's run-time indexed arrays: M (2 * 4 rows of 12), then M' M / Ut
+  double cam[4], R[9], t[3];
+  PNP_HDM PnpHypForm(const Args& a, int c) : cam{a.cam[4 * c], a.cam[4 * c + 1], a.cam[4 * c + 2], a.cam[4 * c + 3]}, R{}, t{} {}
+  PNP_HDM void solve(const Args& a, int h, int p0, double* work) {
+    double pws[12], us[8], alphas[16], pcs[12];
+    for (int j = 0; j < 4; j++) {
+      const size_t i = (size_t)(p0 + a.hyp_idx[4 * h + j]);
+      for (int r = 0; r < 3; r++) pws[3 * j + r] = a.P3Dw[3 * i + r];
+      for (int r = 0; r < 2; r++) us[2 * j + r] = a.P2D[2 * i + r];
+    }
+    pnp_compute_pose(4, pws, us, cam, alphas, pcs, work, work + 96, R, t, nullptr, nullptr);
+    double* o = a.Rt + 12 * (size_t)h;
+    for (int i = 0; i < 9; i++) o[i] = R[i];
+    for (int i = 0; i < 3; i++) o[9 + i] = t[i];
+  }
+  PNP_HDM void prepare(const Args&) {}
+  PNP_HDM bool inlier(const Args& a, int g) const {
+    const size_t i = (size_t)g;
+    return pnp_inlier(R, t, cam, a.P3Dw + 3 * i, a.P2D + 2 * i, a.max_err[i]);
+  }
+};

@@ -1,6 +1,7 @@
 // sim3_ransac_math.h — one hypothesis of cslam::Sim3Solver (cslam/src/Sim3Solver.cpp): ComputeCentroid / ComputeSim3 (:199-321) on three
-// correspondences and the per-point test of CheckInliers with Project / FromCameraToImage (:324-348, :366-407), host + device.  The kernel of
-// sim3ransac.hip runs these lines; the CPU evaluator of tests/host/sim3_schedule_check.cpp includes them too.
+// correspondences and the per-point test of CheckInliers with Project / FromCameraToImage (:324-348, :366-407), host + device, and at the end the
+// two as the host + device members of a form of ransac_wave.h.  The kernel of sim3ransac.hip runs these lines; tests/host/sim3_hyp_check.cpp
+// walks them with g++.
 //
 // Every step is the reference's cv::Mat expression evaluated as OpenCV 4.2 does in a baseline build (no HAVE_EIGEN, no FMA), with the
 // product rules that oracle/ref_shim/opencv2/mini_cv.h declares (gemm_eval, Mat::dot, convertTo).  DESIGN.md §11 lists them; the numpy
@@ -12,8 +13,10 @@
 
 #if defined(__HIPCC__)
 #define S3_HD __host__ __device__ inline
+#define S3_HDM __host__ __device__
 #else
 #define S3_HD static inline
+#define S3_HDM
 #endif
 
 struct S3Hyp {
@@ -251,3 +254,48 @@ S3_HD bool s3_inlier(const S3Hyp& h, const float* X1, const float* X2, const flo
   const float err2 = s3_err(u12, v12, p2u, p2v);
   return err1 < (float)thr1 && err2 < (float)thr2;
 }
+
+// ---- one hypothesis over the arguments of ccm_sim3_ransac_eval: the host + device members of a form of ransac_wave.h -----------------
+struct Sim3RansacArgs {
+  int K, H, fix_scale;
+  const int32_t* pt_off;   // [K + 1]
+  const float* X1;         // [Ntot * 3]
+  const float* X2;
+  const float* K1;         // [K * 4]
+  const float* K2;
+  const uint32_t* thr1;    // [Ntot]
+  const uint32_t* thr2;
+  const int32_t* hyp_cand; // [H]
+  const int32_t* hyp_idx;  // [H * 3], candidate-local
+  const int32_t* mask_off; // [H + 1] words
+  int32_t* n_inl;          // [H]
+  float* rts;              // [H * 13]: R (9), t (3), s
+  uint32_t* mask;          // [mask_off[H]]
+};
+
+struct Sim3HypForm {
+  typedef Sim3RansacArgs Args;
+  static constexpr int S = 3, kWorkDoubles = 0;
+  S3Hyp hy;
+  int c;
+  float k1[4], k2[4];
+  S3_HDM Sim3HypForm(const Args&, int cand) : hy{}, c(cand) {}
+  S3_HDM void solve(const Args& a, int h, int p0, double*) {
+    float x1[3][3], x2[3][3];
+    for (int j = 0; j < 3; j++) {
+      const int i = p0 + a.hyp_idx[3 * h + j];
+      for (int r = 0; r < 3; r++) { x1[j][r] = a.X1[3 * i + r]; x2[j][r] = a.X2[3 * i + r]; }
+    }
+    s3_compute_sim3(x1, x2, a.fix_scale != 0, hy);
+    float* o = a.rts + 13 * (size_t)h;
+    for (int i = 0; i < 9; i++) o[i] = hy.R[i];
+    for (int i = 0; i < 3; i++) o[9 + i] = hy.t[i];
+    o[12] = hy.s;
+  }
+  S3_HDM void prepare(const Args& a) {   // the two cameras: loaded behind the solve, whose registers they would otherwise share
+    for (int i = 0; i < 4; i++) { k1[i] = a.K1[4 * c + i]; k2[i] = a.K2[4 * c + i]; }
+  }
+  S3_HDM bool inlier(const Args& a, int g) const {
+    return s3_inlier(hy, a.X1 + 3 * (size_t)g, a.X2 + 3 * (size_t)g, k1, k2, a.thr1[g], a.thr2[g]);
+  }
+};

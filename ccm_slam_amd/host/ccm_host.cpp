@@ -1050,6 +1050,33 @@ void Optimizer::GlobalBundleAdjustment(HipContext& ctx, BAProblem& p, int nItera
         ctx.get(), "ccm_ba_optimize");
 }
 
+// ---- what the two RANSAC batches share --------------------------------------------------------------
+bool RansacCsr::append(int N, int S) {
+  if (N < S) { remap.push_back(-1); return false; }   // never evaluated (N < minInliers, checked by the schedule)
+  remap.push_back(K());
+  pt_off.push_back(pt_off.back() + N);
+  return true;
+}
+
+size_t RansacCsr::rows(const std::vector<int32_t>& hyp_cand) {
+  cand_buf.resize(hyp_cand.size());
+  size_t words = 0;
+  for (size_t h = 0; h < hyp_cand.size(); h++) {
+    const int r = remap[hyp_cand[h]];
+    if (r < 0) throw std::invalid_argument("RANSAC batch: a hypothesis of a candidate with fewer points than a sample");
+    cand_buf[h] = r;
+    words += (pt_off[r + 1] - pt_off[r] + 31) / 32;
+  }
+  return words;
+}
+
+// a candidate's inlier bits -> vbInliers (n flags) through its index list
+static void mask_to_inliers(const std::vector<uint32_t>& mask, const std::vector<int32_t>& idx, int n, std::vector<bool>& vbInliers) {
+  vbInliers.assign(n, false);
+  for (size_t i = 0; i < idx.size(); i++)
+    if (mask[i >> 5] >> (i & 31) & 1u) vbInliers[idx[i]] = true;
+}
+
 // ---- Sim3RansacBatch ------------------------------------------------------------------------------
 static std::vector<int> sim3_sizes(const std::vector<Sim3Candidate>& c) {
   std::vector<int> n;
@@ -1068,34 +1095,23 @@ Sim3RansacBatch::Sim3RansacBatch(HipContext& ctx, std::vector<Sim3Candidate> can
     : cands_(std::move(cands)), sched_(sim3_sizes(cands_), p, std::move(src)) {
   eval_.ctx = &ctx;
   eval_.fix_scale = fix_scale ? 1 : 0;
-  eval_.pt_off.push_back(0);
-  for (const auto& c : cands_) {
-    const int N = (int)c.indices1.size();
-    if (N < 3) { eval_.remap.push_back(-1); continue; }   // never evaluated (N < minInliers, checked by the schedule)
-    eval_.remap.push_back((int)eval_.pt_off.size() - 1);
-    eval_.pt_off.push_back(eval_.pt_off.back() + N);
-    eval_.X1.insert(eval_.X1.end(), c.X3Dc1.begin(), c.X3Dc1.end());
-    eval_.X2.insert(eval_.X2.end(), c.X3Dc2.begin(), c.X3Dc2.end());
-    eval_.K1.insert(eval_.K1.end(), c.K1, c.K1 + 4);
-    eval_.K2.insert(eval_.K2.end(), c.K2, c.K2 + 4);
-    eval_.t1.insert(eval_.t1.end(), c.max_err1.begin(), c.max_err1.end());
-    eval_.t2.insert(eval_.t2.end(), c.max_err2.begin(), c.max_err2.end());
-  }
+  for (const auto& c : cands_)
+    eval_.add((int)c.indices1.size(), c.X3Dc1.data(), c.X3Dc2.data(), c.K1, c.K2, c.max_err1.data(), c.max_err2.data());
+}
+
+void Sim3RansacBatch::Eval::add(int N, const float* x1, const float* x2, const float* k1, const float* k2, const uint32_t* thr1, const uint32_t* thr2) {
+  if (!append(N, 3)) return;
+  X1.insert(X1.end(), x1, x1 + 3 * (size_t)N); X2.insert(X2.end(), x2, x2 + 3 * (size_t)N);
+  K1.insert(K1.end(), k1, k1 + 4); K2.insert(K2.end(), k2, k2 + 4);
+  t1.insert(t1.end(), thr1, thr1 + N); t2.insert(t2.end(), thr2, thr2 + N);
 }
 
 void Sim3RansacBatch::Eval::operator()(const std::vector<int32_t>& hyp_cand, const std::vector<int32_t>& hyp_idx, std::vector<int32_t>& n_inl,
                                        std::vector<float>& rts, std::vector<int32_t>& mask_off, std::vector<uint32_t>& mask) {
   const int H = (int)hyp_cand.size();
-  cand_buf.resize(H);
-  int64_t words = 0;
-  for (int h = 0; h < H; h++) {
-    const int r = remap[hyp_cand[h]];
-    cand_buf[h] = r;
-    words += (pt_off[r + 1] - pt_off[r] + 31) / 32;
-  }
-  n_inl.resize(H); rts.resize(13 * (size_t)H); mask_off.resize(H + 1); mask.resize((size_t)words);
-  const int K = (int)pt_off.size() - 1;
-  check(ccm_sim3_ransac_eval(ctx->get(), K, pt_off.data(), X1.data(), X2.data(), K1.data(), K2.data(), t1.data(), t2.data(), H, cand_buf.data(),
+  const size_t words = rows(hyp_cand);
+  n_inl.resize(H); rts.resize(13 * (size_t)H); mask_off.resize(H + 1); mask.resize(words);
+  check(ccm_sim3_ransac_eval(ctx->get(), K(), pt_off.data(), X1.data(), X2.data(), K1.data(), K2.data(), t1.data(), t2.data(), H, cand_buf.data(),
                              hyp_idx.data(), fix_scale, n_inl.data(), rts.data(), mask_off.data(), mask.data()),
         ctx->get(), "ccm_sim3_ransac_eval");
 }
@@ -1109,9 +1125,7 @@ bool Sim3RansacBatch::next(int& cand, float R[9], float t[3], float& s, std::vec
   for (int i = 0; i < 3; i++) t[i] = ev.t[i];
   s = ev.s;
   nInliers = ev.n_inliers;
-  vbInliers.assign(c.n1, false);
-  for (size_t i = 0; i < c.indices1.size(); i++)
-    if (ev.mask[i >> 5] >> (i & 31) & 1u) vbInliers[c.indices1[i]] = true;
+  mask_to_inliers(ev.mask, c.indices1, c.n1, vbInliers);
   return true;
 }
 
@@ -1130,15 +1144,11 @@ static std::vector<ccm_pnp::Candidate> pnp_base(const std::vector<PnPCandidate>&
 PnPRansacBatch::PnPRansacBatch(HipContext* ctx, std::vector<PnPCandidate> cands, const ccm_pnp::Params& p, ccm_pnp::DrawSource src)
     : sched_(pnp_base(cands), p, std::move(src)) {
   eval_.ctx = ctx;
-  eval_.pt_off.push_back(0);
   for (size_t c = 0; c < cands.size(); c++) {
     const PnPCandidate& x = cands[c];
     n_matches_.push_back(x.n_matches);
     kp_idx_.push_back(x.keypoint_indices);
-    const int N = x.N();
-    if (N < 4) { eval_.remap.push_back(-1); continue; }   // never evaluated (N < mRansacMinInliers, checked by the schedule)
-    eval_.remap.push_back((int)eval_.pt_off.size() - 1);
-    eval_.pt_off.push_back(eval_.pt_off.back() + N);
+    if (!eval_.append(x.N(), 4)) continue;
     eval_.P3Dw.insert(eval_.P3Dw.end(), x.P3Dw.begin(), x.P3Dw.end());
     eval_.P2D.insert(eval_.P2D.end(), x.P2D.begin(), x.P2D.end());
     const std::vector<float>& me = sched_.max_err((int)c);
@@ -1149,16 +1159,9 @@ PnPRansacBatch::PnPRansacBatch(HipContext* ctx, std::vector<PnPCandidate> cands,
 
 void PnPRansacBatch::Eval::operator()(const std::vector<int32_t>& hyp_cand, const std::vector<int32_t>& hyp_idx, std::vector<int32_t>& n_inl,
                                       std::vector<double>& Rt, std::vector<int32_t>& mask_off, std::vector<uint32_t>& mask) {
-  const int H = (int)hyp_cand.size();
-  cand_buf.resize(H);
-  int64_t words = 0;
-  for (int h = 0; h < H; h++) {
-    const int r = remap[hyp_cand[h]];
-    cand_buf[h] = r;
-    words += (pt_off[r + 1] - pt_off[r] + 31) / 32;
-  }
-  n_inl.resize(H); Rt.resize(12 * (size_t)H); mask_off.resize(H + 1); mask.resize((size_t)words);
-  const int K = (int)pt_off.size() - 1;
+  const int H = (int)hyp_cand.size(), K = this->K();
+  const size_t words = rows(hyp_cand);
+  n_inl.resize(H); Rt.resize(12 * (size_t)H); mask_off.resize(H + 1); mask.resize(words);
   if (!ctx) {
     if (ccm_pnp::eval_host(K, pt_off.data(), P3Dw.data(), P2D.data(), max_err.data(), cam.data(), H, cand_buf.data(), hyp_idx.data(), n_inl.data(), Rt.data(),
                            mask_off.data(), mask.data()))
@@ -1173,10 +1176,7 @@ void PnPRansacBatch::Eval::operator()(const std::vector<int32_t>& hyp_cand, cons
 void PnPRansacBatch::fill(const ccm_pnp::Event& ev, Pose& out) const {
   out.cand = ev.cand; out.nInliers = ev.n_inliers; out.refined = ev.refined; out.bNoMore = ev.no_more;
   std::copy(ev.Tcw, ev.Tcw + 16, out.Tcw);
-  const std::vector<int32_t>& idx = kp_idx_[ev.cand];
-  out.vbInliers.assign(n_matches_[ev.cand], false);
-  for (size_t i = 0; i < idx.size(); i++)
-    if (ev.mask[i >> 5] >> (i & 31) & 1u) out.vbInliers[idx[i]] = true;
+  mask_to_inliers(ev.mask, kp_idx_[ev.cand], n_matches_[ev.cand], out.vbInliers);
 }
 
 bool PnPRansacBatch::next(Pose& out) {
@@ -4165,11 +4165,20 @@ extern "C" int ccmh_kfdb_detect(void* db, int device, int kind, int n, const int
 // idx1 = mvnIndices1) and n1[c] = mN1, K1 / K2 4 per candidate.  draws != NULL: the raw rand() values come from draws[0 .. n_draws) (after the
 // thread's FIFO) instead of ::rand().
 namespace {
-struct Sim3BatchHandle {
+// a batch behind a C handle, with the supplied draws it reads (after the thread's FIFO) where the caller gave some
+template <class Batch>
+struct RansacBatchHandle {
   std::vector<int32_t> draws;
   size_t cursor = 0;
-  std::unique_ptr<cslam::Sim3RansacBatch> batch;
+  std::unique_ptr<Batch> batch;
+  ccm_ransac::DrawSource source(const int32_t* d, int64_t n) {   // d == NULL: ::rand()
+    if (!d) return ccm_ransac::rand_source();
+    draws.assign(d, d + n);
+    return [this](int& v) { if (cursor >= draws.size()) return false; v = draws[cursor++]; return true; };
+  }
 };
+typedef RansacBatchHandle<cslam::Sim3RansacBatch> Sim3BatchHandle;
+typedef RansacBatchHandle<cslam::PnPRansacBatch> PnpBatchHandle;
 }  // namespace
 extern "C" void* ccmh_sim3_ransac_create(int device, int K, const int32_t* pt_off, const float* X3Dc1, const float* X3Dc2, const float* K1, const float* K2,
                                          const uint32_t* max_err1, const uint32_t* max_err2, const int32_t* n1, const int32_t* idx1, double probability,
@@ -4193,13 +4202,7 @@ extern "C" void* ccmh_sim3_ransac_create(int device, int K, const int32_t* pt_of
     ccm_sim3::Params p;
     p.probability = probability; p.min_inliers = min_inliers; p.max_iterations = max_iterations; p.solver_iterations = solver_iterations;
     std::unique_ptr<Sim3BatchHandle> h(new Sim3BatchHandle);
-    ccm_sim3::DrawSource src = ccm_sim3::rand_source();
-    if (draws) {
-      h->draws.assign(draws, draws + n_draws);
-      Sim3BatchHandle* hp = h.get();
-      src = [hp](int& v) { if (hp->cursor >= hp->draws.size()) return false; v = hp->draws[hp->cursor++]; return true; };
-    }
-    h->batch.reset(new cslam::Sim3RansacBatch(thread_context(device), std::move(cands), p, fix_scale != 0, src));
+    h->batch.reset(new cslam::Sim3RansacBatch(thread_context(device), std::move(cands), p, fix_scale != 0, h->source(draws, n_draws)));
     return h.release();
   } catch (const std::exception&) { return nullptr; }
 }
@@ -4243,10 +4246,7 @@ extern "C" int ccmh_sim3_solver_iterate(int device, int N, const float* X3Dc1, c
     cslam::Sim3RansacBatch::Eval ev;
     ev.ctx = &thread_context(device);
     ev.fix_scale = fix_scale ? 1 : 0;
-    ev.pt_off = {0, N}; ev.remap = {0};
-    ev.X1.assign(X3Dc1, X3Dc1 + 3 * (size_t)N); ev.X2.assign(X3Dc2, X3Dc2 + 3 * (size_t)N);
-    ev.K1.assign(K1, K1 + 4); ev.K2.assign(K2, K2 + 4);
-    ev.t1.assign(max_err1, max_err1 + N); ev.t2.assign(max_err2, max_err2 + N);
+    ev.add(N, X3Dc1, X3Dc2, K1, K2, max_err1, max_err2);
     ccm_sim3::SolverState st;
     st.N = N; st.max_its = max_iterations; st.min_inliers = min_inliers; st.its = state[0]; st.best = state[1];
     bool no_more = false, moved = false;
@@ -4265,11 +4265,6 @@ extern "C" int ccmh_sim3_solver_iterate(int device, int N, const float* X3Dc1, c
 }
 // PnPRansacBatch over flat arrays: candidate c has the correspondences pt_off[c] .. pt_off[c+1]
 namespace {
-struct PnpBatchHandle {
-  std::vector<int32_t> draws;
-  size_t cursor = 0;
-  std::unique_ptr<cslam::PnPRansacBatch> batch;
-};
 int pnp_pose_out(const cslam::PnPRansacBatch::Pose& p, int32_t* cand, float* Tcw16, uint8_t* inliers, int cap, int32_t* n_inliers, int32_t* flags2) {
   if (cand) *cand = p.cand;
   if (Tcw16) std::memcpy(Tcw16, p.Tcw, sizeof p.Tcw);
@@ -4301,13 +4296,7 @@ extern "C" void* ccmh_pnp_ransac_create(int device, int K, const int32_t* pt_off
     p.probability = probability; p.min_inliers = min_inliers; p.max_iterations = max_iterations; p.min_set = min_set; p.epsilon = epsilon; p.th2 = th2;
     p.solver_iterations = solver_iterations;
     std::unique_ptr<PnpBatchHandle> h(new PnpBatchHandle);
-    ccm_pnp::DrawSource src = ccm_pnp::rand_source();
-    if (draws) {
-      h->draws.assign(draws, draws + n_draws);
-      PnpBatchHandle* hp = h.get();
-      src = [hp](int& v) { if (hp->cursor >= hp->draws.size()) return false; v = hp->draws[hp->cursor++]; return true; };
-    }
-    h->batch.reset(new cslam::PnPRansacBatch(device < 0 ? nullptr : &thread_context(device), std::move(cands), p, src));
+    h->batch.reset(new cslam::PnPRansacBatch(device < 0 ? nullptr : &thread_context(device), std::move(cands), p, h->source(draws, n_draws)));
     return h.release();
   } catch (const std::exception&) { return nullptr; }
 }

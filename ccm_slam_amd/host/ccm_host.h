@@ -521,6 +521,18 @@ class KeyFrameDatabase {
 };
 
 // ---------------------------------------------------------------------------------------------------
+// What the evaluators of the two RANSAC batches below share: the CSR over the candidates a pass can evaluate (N >= the sample size S; the others are never
+// evaluated, which the schedules check) and the map from a pass's candidates to its rows.
+// ---------------------------------------------------------------------------------------------------
+struct RansacCsr {
+  std::vector<int32_t> pt_off{0}, remap;   // remap: candidate -> CSR row, -1 without one
+  std::vector<int32_t> cand_buf;           // the rows of the last pass's hypotheses
+  bool append(int N, int S);               // the next candidate; true: it has a row, and the caller appends its per-point arrays
+  int K() const { return (int)pt_off.size() - 1; }
+  size_t rows(const std::vector<int32_t>& hyp_cand);   // fills cand_buf; returns the pass's mask words
+};
+
+// ---------------------------------------------------------------------------------------------------
 // Sim3RansacBatch — the vpSim3Solvers loop of LoopFinder::ComputeSim3 (cslam/src/LoopFinder.cpp:288-346) and MapMatcher::ComputeSim3: one
 // Sim3Solver per candidate (the correspondences its constructor gathers, Sim3Solver.cpp:5-92), iterate(mSolverIterations) round-robin until a
 // call returns a Sim3.  next() returns that event (candidate, R, t, s = GetEstimated*, vbInliers in the candidate's mN1 numbering) and the
@@ -538,13 +550,12 @@ struct Sim3Candidate {
 
 class Sim3RansacBatch {
  public:
-  struct Eval {
+  struct Eval : RansacCsr {   // the device CSR over the candidates with N >= 3
     HipContext* ctx = nullptr;
     int fix_scale = 0;
-    std::vector<int32_t> pt_off, remap;   // device CSR over the candidates with N >= 3; remap: candidate -> CSR row
     std::vector<float> X1, X2, K1, K2;
     std::vector<uint32_t> t1, t2;
-    std::vector<int32_t> cand_buf;
+    void add(int N, const float* x1, const float* x2, const float* k1, const float* k2, const uint32_t* thr1, const uint32_t* thr2);
     void operator()(const std::vector<int32_t>& hyp_cand, const std::vector<int32_t>& hyp_idx, std::vector<int32_t>& n_inl, std::vector<float>& rts,
                     std::vector<int32_t>& mask_off, std::vector<uint32_t>& mask);
   };
@@ -573,12 +584,10 @@ struct PnPCandidate : ccm_pnp::Candidate {
 
 class PnPRansacBatch {
  public:
-  struct Eval {
+  struct Eval : RansacCsr {   // the CSR over the candidates with N >= 4
     HipContext* ctx = nullptr;            // nullptr: the host evaluator
-    std::vector<int32_t> pt_off, remap;   // CSR over the candidates with N >= 4; remap: candidate -> CSR row
     std::vector<float> P3Dw, P2D, max_err;
     std::vector<double> cam;
-    std::vector<int32_t> cand_buf;
     void operator()(const std::vector<int32_t>& hyp_cand, const std::vector<int32_t>& hyp_idx, std::vector<int32_t>& n_inl, std::vector<double>& Rt,
                     std::vector<int32_t>& mask_off, std::vector<uint32_t>& mask);
   };

@@ -1,6 +1,7 @@
 // pnp_schedule.h — the RANSAC state of cslam::PnPsolver (cslam/src/PnPSolver.cpp: SetRansacParameters :111-147, iterate :155-249, Refine :251-296) and a round-robin
 // of iterate(n) over the candidates of a relocalisation, evaluated in passes of many hypotheses.  Header-only and templated on the evaluator, so that the host mirror
-// (ccm_host.cpp: device evaluator ccm_pnp_ransac_eval, or eval_host below) and the test driver (tests/host/pnp_check.cpp) run the same lines.
+// (ccm_host.cpp: device evaluator ccm_pnp_ransac_eval, or eval_host below) and the test driver (tests/host/pnp_check.cpp) run the same lines.  The draws and the
+// pass are ransac_schedule.h's; what is here is the call lengths of the round-robin, Refine and the replay of the reference's iterate().
 //
 // iterate() is kept literally, with its quirks: the loop runs while `mnIterations < mRansacMaxIts || nCurrentIterations < nIterations`, so a call without a success
 // runs max(nIterations, mRansacMaxIts - mnIterations) hypotheses and always ends with bNoMore; N < mRansacMinInliers gives bNoMore before any draw; Refine() runs after
@@ -9,7 +10,7 @@
 //
 // Why speculation is exact: the reference draws exactly four values per hypothesis (DUtils::Random::RandomInt(0, size-1) with size = N, N-1, N-2, N-3, swap-with-back
 // removal from the identity mvAllIndices) and the only data-dependent event is a successful Refine, which draws nothing.  A pass therefore enumerates the rest of the
-// round-robin as if no Refine succeeded, takes four raw draws per hypothesis (first from the calling thread's FIFO, ransac_draws.h, then from the source), evaluates
+// round-robin as if no Refine succeeded, takes four raw draws per hypothesis (first from the calling thread's FIFO, ransac_schedule.h, then from the source), evaluates
 // all of it in one call, and replays the reference's loop in order up to the first call that returns a pose.  The raw draws of every hypothesis after it go back to
 // the FRONT of the FIFO, in order: the next pass — or the next Sim3 or PnP solver of this thread — uses exactly the values the sequential reference would have drawn.
 //
@@ -19,11 +20,11 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
-#include <deque>
 #include <stdexcept>
 #include <vector>
-#include "ransac_draws.h"
+#include "ransac_schedule.h"
 #include "../csrc/pnp_math.h"
+#include "../csrc/ransac_wave.h"
 
 namespace ccm_pnp {
 
@@ -73,62 +74,14 @@ inline Ransac set_ransac_parameters(int N, const Params& p) {
   return r;
 }
 
-// four raw draws -> the sample's indices: vAvailableIndices = identity of N, randi = RandomInt(0, size-1), idx = avail[randi], avail[randi] = avail.back(),
-// pop_back (:178-192).  Only the at most four changed slots are kept.
-inline void draws_to_indices(const int raw[4], int N, int idx[4]) {
-  int pos[4], val[4], nm = 0;
-  auto get = [&](int p) { for (int j = nm - 1; j >= 0; j--) if (pos[j] == p) return val[j]; return p; };
-  for (int j = 0; j < 4; j++) {
-    const int size = N - j;
-    const int r = random_int(raw[j], size);
-    idx[j] = get(r);
-    const int back = get(size - 1);
-    pos[nm] = r; val[nm] = back; nm++;
-  }
-}
-
-// the arguments of ccm_pnp_ransac_eval without the context, on the calling thread.  0, or -1 for its CCM_E_ARG cases.
+// the arguments of ccm_pnp_ransac_eval without the context, on the calling thread: its checks (ransac_wave.h), then PnpHypForm hypothesis after hypothesis.  0, or -1
+// for its CCM_E_ARG cases.
 inline int eval_host(int K, const int32_t* pt_off, const float* P3Dw, const float* P2D, const float* max_err, const double* cam, int H, const int32_t* hyp_cand,
                      const int32_t* hyp_idx, int32_t* n_inl, double* Rt, int32_t* mask_off, uint32_t* mask) {
   if (K < 1 || H < 0 || !pt_off || !P3Dw || !P2D || !max_err || !cam || !mask_off || (H > 0 && (!hyp_cand || !hyp_idx || !n_inl || !Rt || !mask))) return -1;
-  if (pt_off[0] != 0) return -1;
-  for (int c = 0; c < K; c++)
-    if (pt_off[c + 1] - pt_off[c] < 4) return -1;
   int64_t words = 0;
-  mask_off[0] = 0;
-  for (int h = 0; h < H; h++) {
-    const int c = hyp_cand[h];
-    if (c < 0 || c >= K) return -1;
-    const int N = pt_off[c + 1] - pt_off[c];
-    for (int j = 0; j < 4; j++) {
-      const int ij = hyp_idx[4 * (size_t)h + j];
-      if (ij < 0 || ij >= N) return -1;
-      for (int k = 0; k < j; k++)
-        if (hyp_idx[4 * (size_t)h + k] == ij) return -1;
-    }
-    words += (N + 31) >> 5;
-    if (words > INT32_MAX) return -1;
-    mask_off[h + 1] = (int32_t)words;
-  }
-  for (int h = 0; h < H; h++) {
-    const int c = hyp_cand[h];
-    const size_t p0 = (size_t)pt_off[c];
-    const int N = pt_off[c + 1] - pt_off[c];
-    double pws[12], us[8], alphas[16], pcs[12], M[96], ut[144];
-    for (int j = 0; j < 4; j++) {
-      const size_t i = p0 + (size_t)hyp_idx[4 * (size_t)h + j];
-      for (int r = 0; r < 3; r++) pws[3 * j + r] = P3Dw[3 * i + r];
-      for (int r = 0; r < 2; r++) us[2 * j + r] = P2D[2 * i + r];
-    }
-    double* R = Rt + 12 * (size_t)h;
-    pnp_compute_pose(4, pws, us, cam + 4 * (size_t)c, alphas, pcs, M, ut, R, R + 9, nullptr, nullptr);
-    uint32_t* m = mask + mask_off[h];
-    for (int w = 0; w < (N + 31) >> 5; w++) m[w] = 0;
-    int count = 0;
-    for (int i = 0; i < N; i++)
-      if (pnp_inlier(R, R + 9, cam + 4 * (size_t)c, P3Dw + 3 * (p0 + i), P2D + 2 * (p0 + i), max_err[p0 + i])) { m[i >> 5] |= 1u << (i & 31); count++; }
-    n_inl[h] = count;
-  }
+  if (ransac_check_hyps<4>(K, pt_off, H, hyp_cand, hyp_idx, mask_off, &words, /*range_first=*/false)) return -1;
+  ransac_eval_host<PnpHypForm>(PnpRansacArgs{K, H, cam, pt_off, P3Dw, P2D, max_err, hyp_cand, hyp_idx, mask_off, Rt, n_inl, mask});
   return 0;
 }
 
@@ -170,10 +123,11 @@ struct Event {
   std::vector<uint32_t> mask;   // candidate-local inlier bits (bit i % 32 of word i / 32): mvbRefinedInliers or mvbBestInliers
 };
 
-// evaluator: void(const std::vector<int32_t>& hyp_cand, const std::vector<int32_t>& hyp_idx /* 4 per hypothesis */, std::vector<int32_t>& n_inl,
-//                 std::vector<double>& Rt /* 12 per hypothesis */, std::vector<int32_t>& mask_off /* H + 1 */, std::vector<uint32_t>& mask)
+typedef ccm_ransac::Pass<4, double> Pass;   // the model: Rt, 12 per hypothesis
+
+// evaluator: ransac_schedule.h's, with Rt (12 per hypothesis) as the model
 template <class Eval>
-class Schedule {
+class Schedule : private Pass {
  public:
   Schedule(std::vector<Candidate> cands, const Params& p, DrawSource src) : c_(std::move(cands)), p_(p), src_(std::move(src)) {
     if (p_.min_set != 4) throw std::invalid_argument("PnP RANSAC: min_set must be 4");
@@ -219,9 +173,9 @@ class Schedule {
     return run(eval, call_cand, call_n, n_iterations, ev, no_more);
   }
 
-  int64_t source_draws() const { return source_draws_; }
-  int64_t hyps_evaluated() const { return hyps_evaluated_; }
-  int passes() const { return passes_; }
+  using Pass::source_draws;
+  using Pass::hyps_evaluated;
+  using Pass::passes;
   int64_t refines() const { return refines_; }
   int iterations(int c) const { return st_[c].its; }
   int max_iterations(int c) const { return st_[c].r.max_its; }
@@ -262,37 +216,9 @@ class Schedule {
   }
 
   bool run(Eval& eval, const std::vector<int>& call_cand, const std::vector<int>& call_n, int n_iterations, Event& ev, bool& no_more) {
-    // four raw draws per hypothesis, FIFO first; a supplied array may run out (the pass is then cut there)
-    std::deque<int>& fifo = draw_fifo();
-    std::vector<int> raws;
-    hyp_cand_.clear(); hyp_idx_.clear();
-    bool cut = false;
-    for (size_t j = 0; j < call_cand.size() && !cut; j++)
-      for (int q = 0; q < call_n[j] && !cut; q++) {
-        int r[4];
-        for (int u = 0; u < 4; u++) {
-          if (!fifo.empty()) { r[u] = fifo.front(); fifo.pop_front(); }
-          else if (src_(r[u])) { source_draws_++; }
-          else { cut = true; for (int w = u - 1; w >= 0; w--) fifo.push_front(r[w]); break; }
-        }
-        if (cut) break;
-        raws.insert(raws.end(), r, r + 4);
-        int idx[4];
-        draws_to_indices(r, c_[call_cand[j]].N(), idx);
-        hyp_cand_.push_back(call_cand[j]);
-        hyp_idx_.insert(hyp_idx_.end(), idx, idx + 4);
-      }
-    const int H = (int)hyp_cand_.size();
-    if (H > 0) {
-      try {
-        eval(hyp_cand_, hyp_idx_, n_inl_, Rt_, mask_off_, mask_);
-      } catch (...) {
-        fifo_restore(raws.data(), raws.size());
-        throw;
-      }
-      hyps_evaluated_ += H;
-      passes_++;
-    }
+    // four raw draws per hypothesis, FIFO first; a supplied array may run out (the pass is then cut there), and one evaluation
+    take(call_cand, call_n, [&](int c) { return c_[c].N(); }, src_);
+    const int H = evaluate(eval);
     // the reference's iterate(), call after call, up to the first one that returns a pose
     const int K = (int)c_.size();
     int hp = 0;
@@ -306,16 +232,16 @@ class Schedule {
         if (hp >= H) throw DrawsExhausted();
         cur++; s.its++;
         const int h = hp++;
-        const int n = n_inl_[h];
+        const int n = n_inl[h];
         if (n >= s.r.min_inliers) {
           if (n > s.best) {
-            s.best_mask.assign(mask_.begin() + mask_off_[h], mask_.begin() + mask_off_[h + 1]);
+            copy_mask(h, s.best_mask);
             s.best = n;
-            to_tcw(&Rt_[12 * (size_t)h], s.best_tcw);
+            to_tcw(&model[12 * (size_t)h], s.best_tcw);
             s.refine_known = false;
           }
           if (refine(c)) {
-            fifo_restore(raws.data() + 4 * (size_t)hp, raws.size() - 4 * (size_t)hp);
+            restore_after(hp);
             ev.cand = c; ev.n_inliers = s.refined; ev.refined = true; ev.no_more = false;
             std::copy(s.refined_tcw, s.refined_tcw + 16, ev.Tcw);
             ev.mask = s.refined_mask;
@@ -327,7 +253,7 @@ class Schedule {
       no_more = true;   // mnIterations >= mRansacMaxIts holds whenever the loop ends
       s.discarded = true;
       if (s.best >= s.r.min_inliers) {
-        fifo_restore(raws.data() + 4 * (size_t)hp, raws.size() - 4 * (size_t)hp);
+        restore_after(hp);
         ev.cand = c; ev.n_inliers = s.best; ev.refined = false; ev.no_more = true;
         std::copy(s.best_tcw, s.best_tcw + 16, ev.Tcw);
         ev.mask = s.best_mask;
@@ -343,11 +269,7 @@ class Schedule {
   DrawSource src_;
   std::vector<State> st_;
   int pos_ = 0;
-  int64_t source_draws_ = 0, hyps_evaluated_ = 0, refines_ = 0;
-  int passes_ = 0;
-  std::vector<int32_t> hyp_cand_, hyp_idx_, n_inl_, mask_off_;
-  std::vector<double> Rt_;
-  std::vector<uint32_t> mask_;
+  int64_t refines_ = 0;
 };
 
 }  // namespace ccm_pnp

@@ -2,7 +2,8 @@
 // Refine (cslam/src/PnPSolver.cpp:155-296) inside the round-robin `for each candidate not discarded: iterate(n)`, both on the same array of raw rand() values and
 // on csrc/pnp_math.h.  tests/test_pnp_cpu.py builds this with -fsanitize=address,undefined as a stand-alone program: every array of the EPnP solve, of Refine's
 // variable n and of the schedule is walked under the sanitizers, on regular scenes and on degenerate samples (a repeated 3D point, coplanar points, a point on the
-// camera plane).  A Sim3 schedule runs after each PnP one on the same thread, so the FIFO hands values from one solver to the other.
+// camera plane).  A Sim3 schedule runs after each PnP one on the same thread, so the FIFO hands values from one solver to the other.  The pieces both schedules
+// take from ransac_schedule.h are checked on their own: draws_to_indices<S> against the literal removal, and a pass cut where a supplied array ends.
 // Prints "pnp schedule ok: <seeds> seeds, <events> events, <hyps> hypotheses".
 #include <cmath>
 #include <cstdint>
@@ -176,10 +177,81 @@ void degenerate_samples() {
   EXPECT(ccm_pnp::eval_host(1, pt_off, c.P3Dw.data(), c.P2D.data(), max_err.data(), c.cam, 1, hc, bad, n_inl, Rt, mask_off, mask) == -1);
 }
 
+// ransac_schedule.h's draws_to_indices<S> against the literal "identity vector, swap with back, pop" of the reference, for every N from S to S + 6 and N = 1000:
+// every pattern of 0 and RAND_MAX over the S slots (slot 0 each time, the back each time, and the mixes), then drawn values
+template <int S>
+void indices_against_the_literal() {
+  for (int k = 0; k <= 7; k++)
+    for (int rep = 0; rep < (1 << S) + 50; rep++) {
+      const int N = k < 7 ? S + k : 1000;
+      int raw[S], idx[S];
+      for (int j = 0; j < S; j++) raw[j] = rep < (1 << S) ? (rep >> j & 1 ? RAND_MAX : 0) : (int)(uni() * 2147483648.0);
+      std::vector<int> avail(N);
+      for (int i = 0; i < N; i++) avail[i] = i;
+      ccm_ransac::draws_to_indices<S>(raw, N, idx);
+      for (int j = 0; j < S; j++) {
+        const int randi = ccm_ransac::random_int(raw[j], (int)avail.size());
+        EXPECT(idx[j] == avail[randi]);
+        avail[randi] = avail.back();
+        avail.pop_back();
+      }
+    }
+}
+
+// a supplied array that ends in the middle of a hypothesis: the pass is cut there, evaluates the complete hypotheses only, and the FIFO then begins with exactly the
+// partial hypothesis's values, in order; Sim3's single-solver call evaluates nothing and gives back every value it took
+void cut_in_the_middle_of_a_hypothesis() {
+  std::vector<int> draws(14);
+  for (int& d : draws) d = (int)(uni() * 2147483647.0);
+  std::deque<int>& fifo = ccm_ransac::draw_fifo();
+  fifo.clear();
+  {   // the pass itself: three complete hypotheses of four draws and two values of a fourth
+    size_t at = 0;
+    ccm_ransac::Pass<4, double> p;
+    const ccm_ransac::DrawSource src = [&](int& v) { if (at >= draws.size()) return false; v = draws[at++]; return true; };
+    const bool whole = p.take(std::vector<int>(1, 0), std::vector<int>(1, 6), [](int) { return 30; }, src);
+    EXPECT(!whole && at == 14 && p.source_draws() == 14);
+    EXPECT(p.hyp_cand.size() == 3 && p.hyp_idx.size() == 12 && p.raws == std::vector<int>(draws.begin(), draws.begin() + 12));
+    EXPECT(fifo.size() == 2 && fifo[0] == draws[12] && fifo[1] == draws[13]);
+    fifo.clear();
+  }
+  {   // the schedule on a candidate that never reaches the threshold: the three hypotheses are evaluated, then the replay finds the draws exhausted
+    std::vector<ccm_pnp::Candidate> cands(1, scene(0, 30, 480));
+    size_t at = 0;
+    ccm_pnp::Schedule<HostEval> sched(cands, ccm_pnp::Params(), [&](int& v) { if (at >= draws.size()) return false; v = draws[at++]; return true; });
+    HostEval he;
+    he.pt_off = {0, 30}; he.P3Dw = cands[0].P3Dw; he.P2D = cands[0].P2D; he.max_err = sched.max_err(0);
+    he.cam.assign(cands[0].cam, cands[0].cam + 4);
+    ccm_pnp::Event e;
+    bool exhausted = false;
+    try { sched.next(he, e); } catch (const ccm_ransac::DrawsExhausted&) { exhausted = true; }
+    EXPECT(exhausted && sched.hyps_evaluated() == 3 && sched.passes() == 1 && sched.source_draws() == 14);
+    EXPECT(fifo.size() == 2 && fifo[0] == draws[12] && fifo[1] == draws[13]);
+    fifo.clear();
+  }
+  {   // Sim3Solver::iterate(5) on seven values: two complete samples and one value
+    size_t at = 0;
+    Sim3Eval se;
+    ccm_sim3::SolverState st;
+    st.N = 50; st.max_its = 100;
+    bool no_more = false, moved = false, exhausted = false;
+    ccm_sim3::Event best;
+    try {
+      ccm_sim3::iterate_one(se, st, 5, [&](int& v) { if (at >= 7) return false; v = draws[at++]; return true; }, no_more, moved, best);
+    } catch (const ccm_ransac::DrawsExhausted&) { exhausted = true; }
+    EXPECT(exhausted && se.seen.empty() && st.its == 0 && fifo.size() == 7);
+    for (size_t i = 0; i < fifo.size() && i < 7; i++) EXPECT(fifo[i] == draws[i]);
+    fifo.clear();
+  }
+}
+
 }  // namespace
 
 int main() {
   degenerate_samples();
+  indices_against_the_literal<3>();
+  indices_against_the_literal<4>();
+  cut_in_the_middle_of_a_hypothesis();
   long n_events = 0, n_hyps = 0;
   const int seeds = 6;
   for (int seed = 0; seed < seeds; seed++) {

@@ -1,5 +1,5 @@
 // sim3_hyp_check.cpp — the per-hypothesis lines of ccm_slam_amd/csrc/sim3_ransac_math.h (what the kernel of sim3ransac.hip runs) compiled for the
-// host, on hypotheses written by tests/test_sim3_ransac_cpu.py: argv[1] = input file, argv[2] = output file.
+// host and walked by ransac_wave.h's host walk, on hypotheses written by tests/test_sim3_ransac_cpu.py: argv[1] = input file, argv[2] = output file.
 // in  (little-endian int32 / float32): K, Ntot, H, fix_scale | pt_off[K+1] | X1[3 Ntot] | X2[3 Ntot] | K1[4K] | K2[4K] | thr1[Ntot] | thr2[Ntot] |
 //     hyp_cand[H] | hyp_idx[3H]
 // out: per hypothesis n_inl (int32), rts (13 float32), then the inlier flags of its candidate's points (one byte each)
@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <vector>
 
+#include "ransac_wave.h"
 #include "sim3_ransac_math.h"
 
 template <class T> static bool rd(FILE* f, std::vector<T>& v, size_t n) { v.resize(n); return fread(v.data(), sizeof(T), n, f) == n; }
@@ -27,25 +28,19 @@ int main(int argc, char** argv) {
   fclose(f);
   FILE* o = fopen(argv[2], "wb");
   if (!o) return 2;
+  std::vector<int32_t> n_inl(H), mask_off(H + 1);
+  std::vector<float> rts(13 * (size_t)H);
+  int64_t words = 0;
+  if (ransac_check_hyps<3>(K, pt_off.data(), H, hc.data(), hi.data(), mask_off.data(), &words, true)) return 2;
+  std::vector<uint32_t> mask((size_t)words);
+  ransac_eval_host<Sim3HypForm>(Sim3RansacArgs{K, H, fix != 0, pt_off.data(), X1.data(), X2.data(), K1.data(), K2.data(), t1.data(), t2.data(), hc.data(), hi.data(),
+                                           mask_off.data(), n_inl.data(), rts.data(), mask.data()});
   for (int h = 0; h < H; h++) {
-    const int c = hc[h], p0 = pt_off[c], N = pt_off[c + 1] - p0;
-    float x1[3][3], x2[3][3];
-    for (int j = 0; j < 3; j++)
-      for (int r = 0; r < 3; r++) { x1[j][r] = X1[3 * (p0 + hi[3 * h + j]) + r]; x2[j][r] = X2[3 * (p0 + hi[3 * h + j]) + r]; }
-    S3Hyp hy;
-    s3_compute_sim3(x1, x2, fix != 0, hy);
+    const int N = pt_off[hc[h] + 1] - pt_off[hc[h]];
     std::vector<uint8_t> in(N);
-    int32_t n = 0;
-    for (int i = 0; i < N; i++) {
-      in[i] = s3_inlier(hy, &X1[3 * (p0 + i)], &X2[3 * (p0 + i)], &K1[4 * c], &K2[4 * c], t1[p0 + i], t2[p0 + i]) ? 1 : 0;
-      n += in[i];
-    }
-    float rts[13];
-    for (int i = 0; i < 9; i++) rts[i] = hy.R[i];
-    for (int i = 0; i < 3; i++) rts[9 + i] = hy.t[i];
-    rts[12] = hy.s;
-    fwrite(&n, 4, 1, o);
-    fwrite(rts, 4, 13, o);
+    for (int i = 0; i < N; i++) in[i] = mask[mask_off[h] + (i >> 5)] >> (i & 31) & 1u;
+    fwrite(&n_inl[h], 4, 1, o);
+    fwrite(&rts[13 * (size_t)h], 4, 13, o);
     fwrite(in.data(), 1, N, o);
   }
   fclose(o);

@@ -23,6 +23,8 @@ point's errors at least 1e-3 (relative) away from their thresholds (threshold_ma
 schedule tests draw their samples from arrays and report that margin for an event whose mask differs.
 """
 import ctypes
+import functools
+import itertools
 import math
 import threading
 
@@ -436,6 +438,69 @@ def test_duplicated_points_give_nan_and_no_inliers(ctx):
     ni1, ref1, inl1 = ref_hypothesis(c, [2, 3, 10], False)
     assert n[1] == ni1 and np.array_equal(masks[1], inl1)
     _compare_rts(rts[1], ref1)
+
+
+EDGE_N = (3, 4, 31, 32, 33, 63, 64, 65)
+# checked on the CPU by test_edge_cases_have_samples_outside_the_margin.  N = 3 has a single triple: of the seeds 400 .. 419, its margin passes with all three
+# points inliers at 403, 404, 410 .. 415 and 419, so 400 + N serves there too
+EDGE_SEED = {N: 400 + N for N in EDGE_N}
+
+
+@functools.lru_cache(maxsize=None)
+def _edge_cases():
+    """{N: (one true candidate of N correspondences, its samples that pass MARGIN)}: every triple proposed for N <= 4 (N = 3 has one), twelve drawn ones above"""
+    out = {}
+    for N in EDGE_N:
+        c = _cands(EDGE_SEED[N], 1, 0, [N], 0.3)[0]
+        rng = np.random.default_rng(N)
+        proposals = list(itertools.combinations(range(N), 3)) if N <= 4 else [tuple(int(i) for i in rng.choice(N, 3, replace=False)) for _ in range(12)]
+        out[N] = (c, [idx for idx in proposals if threshold_margin(c, idx, False) >= MARGIN])
+    return out
+
+
+def test_edge_cases_have_samples_outside_the_margin():
+    assert all(len(ok) >= 1 for _, ok in _edge_cases().values()), {N: len(ok) for N, (_, ok) in _edge_cases().items()}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("N", EDGE_N)
+def test_one_candidate_at_the_wave_block_and_mask_word_edges(ctx, N):
+    """H = 1 (one wave), 4 (a whole workgroup) and 5 (one wave in a second workgroup); N around the 32-bit mask words and the 64-lane stride.  The mask buffer
+    is filled with ones before the call: every word is written and no bit at or beyond N survives."""
+    from ccm_slam_amd import sim3
+    from ccm_slam_amd._lib import _p, check, lib
+    assert all(len(ok) >= 1 for _, ok in _edge_cases().values())   # on the CPU, before any device call
+    c, ok = _edge_cases()[N]
+    pt_off, X1, X2, K1, K2, t1, t2, _, _ = sim3.pack([c])
+    words = (N + 31) // 32
+    for H in (1, 4, 5):
+        hc = np.zeros(H, np.int32)
+        hi = np.array([ok[h % len(ok)] for h in range(H)], np.int32)
+        n_inl = np.zeros(H, np.int32); rts = np.zeros((H, 13), np.float32); mask_off = np.zeros(H + 1, np.int32)
+        mask = np.full(H * words, 0xFFFFFFFF, np.uint32)
+        check(lib().ccm_sim3_ransac_eval(ctx.handle, 1, _p(pt_off), _p(X1), _p(X2), _p(K1), _p(K2), _p(t1), _p(t2), H, _p(hc), _p(hi), 0, _p(n_inl), _p(rts),
+                                         _p(mask_off), _p(mask)), ctx.handle)
+        assert np.array_equal(mask_off, words * np.arange(H + 1))
+        for h in range(H):
+            bits = np.unpackbits(mask[words * h:words * (h + 1)].astype("<u4").view(np.uint8), bitorder="little")
+            assert not bits[N:].any(), (N, H, h)
+            ni, ref, inl = ref_hypothesis(c, hi[h], False)
+            assert n_inl[h] == ni and np.array_equal(bits[:N].astype(bool), inl), (N, H, h, n_inl[h], ni)
+            _compare_rts(rts[h], ref)
+
+
+@pytest.mark.gpu
+def test_drop_in_iterate_of_a_candidate_smaller_than_a_sample_fails_and_keeps_the_draws(ctx):
+    """N = 2 with MinInliers = 2 reaches the evaluation, which has no row for such a candidate: the call fails (it always did: the entry point refuses N < 3) and
+    the three values drawn for its one hypothesis are back in the thread's FIFO."""
+    from ccm_slam_amd import sim3
+    from ccm_slam_amd._lib import CcmError
+    sim3.clear_draws()
+    s = sim3.Sim3Solver(_cands(54, 1, 0, [2])[0], min_inliers=2)
+    with pytest.raises(CcmError):
+        s.iterate(5)
+    assert sim3.draws_pending().size == 3
+    sim3.clear_draws()
 
 
 def _run_batch(cands, draws, fix_scale=False, reject=0, **kw):
