@@ -1,6 +1,9 @@
 // block_red.h — deterministic workgroup-wide f64 sums for the single-workgroup LM kernels (poseopt.hip, sim3opt.hip).
 // Fixed association order => run-to-run deterministic, and every thread of every wave ends with the same bits, which
-// keeps the LM control flow workgroup-uniform without broadcasting decisions.
+// keeps the LM control flow workgroup-uniform without broadcasting decisions.  tests/test_block_red_gpu.py runs every sum below in one launch (test_hooks.hip) and
+// compares EVERY thread's result bit for bit: with the exact sum of integer data, and with a numpy transliteration of the association order stated here.
+// Order: a wave sums by the xor butterfly 32, 16, 8, 4, 2, 1 (the halving butterflies of sum27 / sum64 form per value exactly those pairs), the four wave partials are
+// added in turn, ((w0 + w1) + w2) + w3; sum28_lds has its own order, stated there.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "lane_xor.h"
@@ -47,10 +50,10 @@ struct BlockRedT {
     return s;
   }
 
-  // 27 values at once (upper triangle of H + b): a halving butterfly moves 16+8+4+2+1+1 = 32 f64 values through
+  // 27 values at once (upper triangle of H + b), and a 28th in entry 27: a halving butterfly moves 16+8+4+2+1+1 = 32 f64 values through
   // the cross-lane network instead of 27*6 = 162; lane l then owns the wave total of value l>>1, the waves meet
   // in LDS, lanes 0..26 add the NW partials and v_readlane hands every total to the whole wave as a scalar.
-  __device__ __forceinline__ void sum27(double* acc /* [32], entries 28..31 zero */) {
+  __device__ __forceinline__ void sum27(double* acc /* [32]: entries 0..27 are summed and handed back; 28..31 travel through the butterfly, are not handed back and not preserved (the callers pass zeros) */) {
 #pragma unroll
     for (int c = 16, off = 32; c >= 1; c >>= 1, off >>= 1) {
       // (round 6) the upper lanes swap their halves — a real branch: the empty asm keeps the swaps from becoming selects again —, then every lane keeps [0, c) and sends
@@ -81,7 +84,7 @@ struct BlockRedT {
   // a half-wave reads on different banks), 224 threads add 64 NW / 8 entries each (value = t / 8, every 8th entry from t % 8, four running sums), three cross-lane steps join
   // the 8 parts, and every thread reads the 28 totals back (LDS broadcast): two barriers, 1.15 us.  tr: LDS [kTrDoubles], not shared with `buf`.
   static constexpr int kTrCols = NW * 64, kTrStride = kTrCols + 8, kTrDoubles = 28 * kTrStride + 32;
-  __device__ __forceinline__ void sum28_lds(double* acc /* [32], entries 28..31 unused */, double* tr) {
+  __device__ __forceinline__ void sum28_lds(double* acc /* [32], entries 28..31 neither read nor written (the test fills them with NaN) */, double* tr) {
     static_assert(NW * 64 >= 224, "sum28_lds: 224 threads add the columns");
     const int t = wave * 64 + lane;
 #pragma unroll
@@ -107,7 +110,7 @@ struct BlockRedT {
   // up to 64 values (NV of them meaningful): halving butterfly 32+16+8+4+2+1 = 63 cross-lane moves, lane l then owns
   // the wave total of value l
   template <int NV>
-  __device__ __forceinline__ void sum64(double* acc /* [64], entries NV..63 zero */) {
+  __device__ __forceinline__ void sum64(double* acc /* [64]: entries 0..NV-1 are summed and handed back; NV..63 travel through the butterfly, are not handed back and not preserved (the callers pass zeros) */) {
 #pragma unroll
     for (int c = 32, off = 32; c >= 1; c >>= 1, off >>= 1) {
       // (round 6) the upper lanes swap their halves — a real branch: the empty asm keeps the swaps from becoming selects again —, then every lane keeps [0, c) and sends

@@ -13,6 +13,7 @@
 #include "common.h"
 #include "ba_math.h"
 #include "block_red.h"
+#include "test_internal.h"
 #include <chrono>
 #include <cfloat>
 #include <cstring>
@@ -34,6 +35,15 @@ struct PoseOptArgs {
   unsigned long long* h_ticket; unsigned long long ticket;   // zero-copy calls: written (system scope) after the results are in the pinned block; the host polls it
   long long* dbg;       // CCM_POSEOPT_DBG: phase clocks of thread 0 (10 ns ticks): [0] staging [1] edge passes [2] 27-value reductions [3] solve + update [4] classification [5] passes [6] whole kernel
 };
+// The PROBE instantiations (tests only, ccm_internal::poseopt_debug_linearise): initial level[] / robust[] from the caller, staging, ONE linearise(T0), every thread's reduced
+// acc[0..27] and the err[] array written back, return.  The product instantiations take PoseOptArgs as before.
+struct PoseProbeArgs : PoseOptArgs {
+  const uint8_t* level_in; const uint8_t* robust_in;   // [n]
+  double* acc_out;      // [28][256]: acc_out[k * 256 + thread]
+  double* err_out;      // [2n]
+};
+template <bool PROBE> struct PoseArgsOf { using type = PoseOptArgs; };
+template <> struct PoseArgsOf<true> { using type = PoseProbeArgs; };
 #define POSE_TICK(slot) { if (timing) { const long long tn_ = wall_clock64(); a.dbg[slot] += tn_ - tk; tk = tn_; } }
 
 __device__ __forceinline__ bool chol6_solve(const double* H, double lambda, const double* b, double* x) {
@@ -92,8 +102,8 @@ constexpr int kPoseWaves = 4, kPoseThreads = 64 * kPoseWaves;
 template <bool TR> struct PoseCfg {
   static constexpr int kRed = 2 * kPoseWaves * 64 + (TR ? BlockRedT<kPoseWaves>::kTrDoubles : 0);   // doubles at the head of the LDS: [sum1 / sum27 buffers | transpose block]
 };
-template <bool TR>
-__global__ __launch_bounds__(kPoseThreads) void poseopt_kernel(PoseOptArgs a, int use_lds) {
+template <bool TR, bool PROBE>
+__global__ __launch_bounds__(kPoseThreads) void poseopt_kernel(typename PoseArgsOf<PROBE>::type a, int use_lds) {
   constexpr int kPoseRed = PoseCfg<TR>::kRed;
   extern __shared__ __attribute__((aligned(16))) double sm[];
   double* const tr = sm + 2 * kPoseWaves * 64;
@@ -130,7 +140,11 @@ __global__ __launch_bounds__(kPoseThreads) void poseopt_kernel(PoseOptArgs a, in
     a.level = lb; a.robust = lb + a.n; a.outlier = lb + 2 * (size_t)a.n;
     __syncthreads();
   }
-  for (int i = tid; i < a.n; i += kPoseThreads) { a.level[i] = 0; a.robust[i] = 1; a.outlier[i] = 0; a.err[2 * i] = 0; a.err[2 * i + 1] = 0; }
+  for (int i = tid; i < a.n; i += kPoseThreads) {
+    uint8_t lv = 0, rb = 1;
+    if constexpr (PROBE) { lv = a.level_in[i]; rb = a.robust_in[i]; }
+    a.level[i] = lv; a.robust[i] = rb; a.outlier[i] = 0; a.err[2 * i] = 0; a.err[2 * i + 1] = 0;
+  }
   POSE_TICK(0)
   BaPose T = T0;
   int nBad = 0;
@@ -213,6 +227,13 @@ __global__ __launch_bounds__(kPoseThreads) void poseopt_kernel(PoseOptArgs a, in
         if (timing) a.dbg[5] += 1;
         POSE_TICK(2)
       };
+      if constexpr (PROBE) {
+        linearise(T);
+#pragma unroll
+        for (int k = 0; k < 28; k++) a.acc_out[k * kPoseThreads + tid] = acc[k];
+        for (int i = tid; i < a.n; i += kPoseThreads) { a.err_out[2 * i] = a.err[2 * i]; a.err_out[2 * i + 1] = a.err[2 * i + 1]; }   // (a thread's own edges)
+        return;
+      }
       for (int iter = 0; iter < 10; iter++) {
         if (!lin_current) linearise(T);
         double currentChi = acc[27];
@@ -275,6 +296,7 @@ __global__ __launch_bounds__(kPoseThreads) void poseopt_kernel(PoseOptArgs a, in
       // (as in g2o, err[] keeps the errors of the LAST evaluated state, also when that trial was rejected: the inlier
       // classification below reads e->chi2() without recomputing, Optimizer.cpp:306-334)
     }
+    if constexpr (PROBE) return;                // (no active edge: the outputs keep the caller's zeros)
     // classification (:306-334)
     double bad = 0.0;
     for (int i = tid; i < a.n; i += kPoseThreads) {
@@ -304,7 +326,77 @@ __global__ __launch_bounds__(kPoseThreads) void poseopt_kernel(PoseOptArgs a, in
   if (timing) a.dbg[6] += wall_clock64() - tk0;
 }
 
+// The launch shape of a problem of n edges, decided in one place for ccm_pose_optimize and the test hook.
+struct PoseShape {
+  bool tr_red;        // the 27 sums through the LDS transpose block (poseopt_kernel<true>), else the cross-lane reduction
+  int use_lds;        // the problem is staged in LDS, else it stays in global memory
+  size_t lds_bytes;   // dynamic LDS of the launch
+};
+PoseShape pose_launch_shape(int n) {
+  // LDS staging: 64 B of f64 data + 3 flag bytes per edge; the 160 KiB LDS of one CU holds ~2400 edges
+  const size_t staged = 8 * (size_t)n * sizeof(double) + 3 * (size_t)n + 16;
+  // the 27 sums through LDS whenever the transpose block fits beside the staged problem (up to ~1290 edges); CCM_POSEOPT_SHAPE=0: the cross-lane reduction always
+  const bool shape0_env = false;
+  // (round 6: with the butterfly's cross-lane moves by DPP (block_red.h, lane_xor.h) the transpose wins up to a few hundred edges only — 0.162 against 0.173 ms per call at 150
+  // edges, 0.115 / 0.140 at 300, but 0.234 / 0.202 at 1000: its two barriers and 28 LDS columns grow with the edge passes around them; crossover taken at 600)
+  const bool tr_red = !shape0_env && n < 600 && PoseCfg<true>::kRed * sizeof(double) + staged <= 150 * 1024;
+  const size_t red_bytes = (tr_red ? PoseCfg<true>::kRed : PoseCfg<false>::kRed) * sizeof(double);
+  const size_t lds_full = red_bytes + staged;
+  const int use_lds = lds_full <= 150 * 1024;
+  return PoseShape{tr_red, use_lds, use_lds ? lds_full : red_bytes};
+}
+
 }  // namespace
+
+// Test hook (test_internal.h): the kernel's own staging and linearise(T0) at GIVEN level / robust flags, by the launch shape pose_launch_shape() gives the product call.
+// acc_out[28][256]: every thread's reduced sums (H upper triangle 0..20, b 21..26, chi2 27); err_out[2n]; shape: tr_red, use_lds, dynamic LDS bytes.
+int ccm_internal::poseopt_debug_linearise(ccm_ctx* ctx, const double cam_qt[7], int n, const double* Xw, const double* obs, const double* info, const double K[4],
+                                          const uint8_t* level, const uint8_t* robust, double* acc_out, double* err_out, int shape[3]) {
+  if (!ctx || !cam_qt || n < 1 || !Xw || !obs || !info || !K || !level || !robust || !acc_out || !err_out || !shape)
+    return ccm_set_error(ctx, CCM_E_ARG, "poseopt_debug_linearise: bad args");
+  CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  // one device block: [cam 7 | n_bad | Xw 3n | obs 2n | info n | err 2n | acc 28 * 256 | err_out 2n] doubles, then level, robust, outlier, level_in, robust_in bytes
+  const size_t N = (size_t)n, n_acc = 28 * (size_t)kPoseThreads, nd = 8 + 8 * N + n_acc + 2 * N;
+  double* d = nullptr;
+  CCM_HIP_CHECK(ctx, hipMalloc(&d, nd * sizeof(double) + 5 * N + 64));
+  auto fail = [&](hipError_t e) { (void)hipFree(d); return ccm_set_error(ctx, CCM_E_HIP, std::string("poseopt_debug_linearise: ") + hipGetErrorString(e)); };
+  hipError_t e = hipMemset(d, 0, nd * sizeof(double) + 5 * N + 64);
+  PoseProbeArgs a;
+  a.n = n;
+  a.cam = d; a.n_bad = (int*)(d + 7);
+  double* din = d + 8;
+  a.Xw = din; a.obs = din + 3 * N; a.info = din + 5 * N; a.err = din + 6 * N;
+  a.acc_out = din + 8 * N; a.err_out = a.acc_out + n_acc;
+  uint8_t* bytes_base = (uint8_t*)(d + nd);
+  a.level = bytes_base; a.robust = bytes_base + N; a.outlier = bytes_base + 2 * N;
+  uint8_t* lv_in = bytes_base + 3 * N; uint8_t* rb_in = bytes_base + 4 * N;
+  a.level_in = lv_in; a.robust_in = rb_in;
+  for (int k = 0; k < 4; k++) a.K[k] = K[k];
+  a.dbg = nullptr; a.h_ticket = nullptr; a.ticket = 0;
+  if (e == hipSuccess) e = hipMemcpy(d, cam_qt, 7 * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(din, Xw, 3 * N * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(din + 3 * N, obs, 2 * N * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(din + 5 * N, info, N * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(lv_in, level, N, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(rb_in, robust, N, hipMemcpyHostToDevice);
+  if (e != hipSuccess) return fail(e);
+  const PoseShape sh = pose_launch_shape(n);
+  shape[0] = sh.tr_red; shape[1] = sh.use_lds; shape[2] = (int)sh.lds_bytes;
+  if (sh.tr_red) {
+    e = hipFuncSetAttribute((const void*)poseopt_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    if (e == hipSuccess) hipLaunchKernelGGL((poseopt_kernel<true, true>), dim3(1), dim3(kPoseThreads), sh.lds_bytes, ctx->stream, a, sh.use_lds);
+  } else {
+    e = hipFuncSetAttribute((const void*)poseopt_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    if (e == hipSuccess) hipLaunchKernelGGL((poseopt_kernel<false, true>), dim3(1), dim3(kPoseThreads), sh.lds_bytes, ctx->stream, a, sh.use_lds);
+  }
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess) e = hipMemcpy(acc_out, a.acc_out, n_acc * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(err_out, a.err_out, 2 * N * sizeof(double), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(e);
+  CCM_HIP_CHECK(ctx, hipFree(d));
+  return CCM_OK;
+}
 
 extern "C" int ccm_pose_optimize(ccm_ctx* ctx, double cam_qt[7], int n, const double* Xw, const double* obs, const double* info,
                                  const double K[4], uint8_t* outlier, int* n_inlier) {
@@ -350,16 +442,9 @@ extern "C" int ccm_pose_optimize(ccm_ctx* ctx, double cam_qt[7], int n, const do
   memcpy(hin, Xw, 3 * (size_t)n * sizeof(double));
   memcpy(hin + 3 * (size_t)n, obs, 2 * (size_t)n * sizeof(double));
   memcpy(hin + 5 * (size_t)n, info, (size_t)n * sizeof(double));
-  // LDS staging: 64 B of f64 data + 3 flag bytes per edge; the 160 KiB LDS of one CU holds ~2400 edges
-  const size_t staged = 8 * (size_t)n * sizeof(double) + 3 * (size_t)n + 16;
-  // the 27 sums through LDS whenever the transpose block fits beside the staged problem (up to ~1290 edges); CCM_POSEOPT_SHAPE=0: the cross-lane reduction always
-  const bool shape0_env = false;
-  // (round 6: with the butterfly's cross-lane moves by DPP (block_red.h, lane_xor.h) the transpose wins up to a few hundred edges only — 0.162 against 0.173 ms per call at 150
-  // edges, 0.115 / 0.140 at 300, but 0.234 / 0.202 at 1000: its two barriers and 28 LDS columns grow with the edge passes around them; crossover taken at 600)
-  const bool tr_red = !shape0_env && n < 600 && PoseCfg<true>::kRed * sizeof(double) + staged <= 150 * 1024;
-  const size_t red_bytes = (tr_red ? PoseCfg<true>::kRed : PoseCfg<false>::kRed) * sizeof(double);
-  const size_t lds_full = red_bytes + staged;
-  const int use_lds = lds_full <= 150 * 1024;
+  const PoseShape sh = pose_launch_shape(n);
+  const bool tr_red = sh.tr_red;
+  const int use_lds = sh.use_lds;
   // (round 4) a problem that is staged in LDS touches its inputs once and its outputs once: the kernel reads them from / writes them to the PINNED HOST block itself (same
   // layout), which takes the two copy commands and their latency out of the call (0.147 -> ~0.13 ms for 300 edges).  CCM_POSEOPT_COPY=1: through the device block as before.
   const bool copy_env = false;
@@ -376,13 +461,13 @@ extern "C" int ccm_pose_optimize(ccm_ctx* ctx, double cam_qt[7], int n, const do
   } else CCM_HIP_CHECK(ctx, hipMemcpyAsync(d, h, n_in * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   {
     ccm_prof_scope ps(ctx, CCM_K_POSEOPT);
-    const size_t lds_bytes = use_lds ? lds_full : red_bytes;
+    const size_t lds_bytes = sh.lds_bytes;
     if (tr_red) {
-      CCM_LDS_ATTR(ctx, CCM_LDS_POSEOPT1, poseopt_kernel<true>, 150 * 1024);
-      hipLaunchKernelGGL(poseopt_kernel<true>, dim3(1), dim3(kPoseThreads), lds_bytes, ctx->stream, a, use_lds);
+      CCM_LDS_ATTR(ctx, CCM_LDS_POSEOPT1, (poseopt_kernel<true, false>), 150 * 1024);
+      hipLaunchKernelGGL((poseopt_kernel<true, false>), dim3(1), dim3(kPoseThreads), lds_bytes, ctx->stream, a, use_lds);
     } else {
-      if (lds_bytes > 64 * 1024) { CCM_LDS_ATTR(ctx, CCM_LDS_POSEOPT, poseopt_kernel<false>, 150 * 1024); }
-      hipLaunchKernelGGL(poseopt_kernel<false>, dim3(1), dim3(kPoseThreads), lds_bytes, ctx->stream, a, use_lds);
+      if (lds_bytes > 64 * 1024) { CCM_LDS_ATTR(ctx, CCM_LDS_POSEOPT, (poseopt_kernel<false, false>), 150 * 1024); }
+      hipLaunchKernelGGL((poseopt_kernel<false, false>), dim3(1), dim3(kPoseThreads), lds_bytes, ctx->stream, a, use_lds);
     }
   }
   CCM_HIP_CHECK(ctx, hipGetLastError());

@@ -17,6 +17,7 @@
 #include "common.h"
 #include "sim3_math.h"
 #include "block_red.h"
+#include "test_internal.h"
 #include <cfloat>
 #include <cstring>
 
@@ -37,6 +38,20 @@ struct Sim3OptArgs {
 };
 
 constexpr int kPertDoubles = 14 * 16;   // per perturbation: S (8) | S^-1 (8)
+
+// The PROBE instantiation (tests only, ccm_internal::sim3opt_debug_linearise): initial alive[] from the caller, staging, chi2_active(S), the 14 perturbed estimates, ONE accumulation
+// and red.sum64<35>; every thread's reduced acc[0..34] and chi2, the err[] array, the perturbed estimates and the per-pair numeric Jacobians written back, return.  The product
+// instantiation takes Sim3OptArgs as before.
+struct Sim3ProbeArgs : Sim3OptArgs {
+  const uint8_t* alive_in;   // [n]
+  double* acc_out;           // [35][256]: acc_out[k * 256 + thread]
+  double* chi2_out;          // [256]
+  double* err_out;           // [4n]
+  double* pert_out;          // [14 * 16]
+  double* J_out;             // [n][2][14]: pair, side (0: x1 = S X2, 1: x2 = S^-1 X1), row 0 (7) | row 1 (7)
+};
+template <bool PROBE> struct Sim3ArgsOf { using type = Sim3OptArgs; };
+template <> struct Sim3ArgsOf<true> { using type = Sim3ProbeArgs; };
 
 __device__ __forceinline__ bool chol7_solve(const double* H, double lambda, const double* b, double* x) {
   double L[49], inv[7];
@@ -87,7 +102,8 @@ __device__ __forceinline__ void proj_err(const Sim3d& X, const double* P, const 
   e1 = obs[1] - ((p[1] / p[2]) * K[1] + K[3]);
 }
 
-__global__ __launch_bounds__(kThreads) void sim3opt_kernel(Sim3OptArgs a, int use_lds) {
+template <bool PROBE>
+__global__ __launch_bounds__(kThreads) void sim3opt_kernel_t(typename Sim3ArgsOf<PROBE>::type a, int use_lds) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const int tid = threadIdx.x;
   BlockRed red{sm, 0, tid & 63, tid >> 6};
@@ -109,7 +125,9 @@ __global__ __launch_bounds__(kThreads) void sim3opt_kernel(Sim3OptArgs a, int us
     a.alive = lb; a.inlier = lb + n;
   }
   for (int i = tid; i < n; i += kThreads) {
-    a.alive[i] = 1; a.inlier[i] = 1;
+    uint8_t al = 1;
+    if constexpr (PROBE) al = a.alive_in[i];
+    a.alive[i] = al; a.inlier[i] = 1;
     a.err[4 * i] = 0; a.err[4 * i + 1] = 0; a.err[4 * i + 2] = 0; a.err[4 * i + 3] = 0;
   }
   __syncthreads();
@@ -185,6 +203,10 @@ __global__ __launch_bounds__(kThreads) void sim3opt_kernel(Sim3OptArgs a, int us
             proj_err(Xm, P, ob, KK, m0, m1);
             J[d] = scalar * (p0 - m0); J[7 + d] = scalar * (p1 - m1);
           }
+          if constexpr (PROBE) {
+#pragma unroll
+            for (int q = 0; q < 14; q++) a.J_out[(2 * (size_t)i + side) * 14 + q] = J[q];
+          }
           const double om = side ? a.info2[i] : a.info1[i];
           const double e0 = a.err[4 * i + 2 * side], e1 = a.err[4 * i + 2 * side + 1];
           double rho0, w;
@@ -199,7 +221,16 @@ __global__ __launch_bounds__(kThreads) void sim3opt_kernel(Sim3OptArgs a, int us
           for (int r = 0; r < 7; r++) acc[28 + r] += J[r] * o0 + J[7 + r] * o1;
         }
       }
-      red.sum64<35>(acc);
+      red.template sum64<35>(acc);
+      if constexpr (PROBE) {
+#pragma unroll
+        for (int k = 0; k < 35; k++) a.acc_out[k * kThreads + tid] = acc[k];
+        a.chi2_out[tid] = currentChi;
+        for (int i = tid; i < n; i += kThreads)   // (a thread's own pairs)
+          for (int q = 0; q < 4; q++) a.err_out[4 * i + q] = a.err[4 * i + q];
+        if (tid < kPertDoubles) a.pert_out[tid] = pert[tid];
+        return;
+      }
       double H[49], B[7];
       {
         int k = 0;
@@ -259,6 +290,7 @@ __global__ __launch_bounds__(kThreads) void sim3opt_kernel(Sim3OptArgs a, int us
   };
 
   optimize(5);
+  if constexpr (PROBE) return;
   double bad = 0.0;
   for (int i = tid; i < n; i += kThreads)
     if (over(i)) { a.alive[i] = 0; a.inlier[i] = 0; bad += 1.0; }
@@ -281,7 +313,73 @@ __global__ __launch_bounds__(kThreads) void sim3opt_kernel(Sim3OptArgs a, int us
   }
 }
 
+constexpr auto sim3opt_kernel = sim3opt_kernel_t<false>;   // the product kernel
+
+// The launch shape of a problem of n pairs, decided in one place for ccm_sim3_optimize and the test hook.
+struct Sim3Shape {
+  int use_lds;        // the problem is staged in LDS, else it stays in global memory
+  size_t lds_bytes;   // dynamic LDS of the launch
+};
+Sim3Shape sim3_launch_shape(int n) {
+  const size_t lds_head = (kRedDoubles + kPertDoubles) * sizeof(double);
+  const size_t lds_full = lds_head + 16 * (size_t)n * sizeof(double) + 2 * (size_t)n + 16;
+  const int use_lds = lds_full <= 150 * 1024;
+  return Sim3Shape{use_lds, use_lds ? lds_full : lds_head};
+}
+
 }  // namespace
+
+// Test hook (test_internal.h): the kernel's own staging, chi2_active(S), perturbed estimates and ONE accumulation of H and b at GIVEN alive bytes, by the launch shape
+// sim3_launch_shape() gives the product call.  acc_out[35][256] (H upper triangle 0..27, b 28..34) and chi2_out[256]: every thread's; err_out[4n]; pert_out[14][16]:
+// S(+delta e_d) | its inverse, S(-delta e_d) | its inverse for d = 0..6; J_out[n][2][14]; shape: staged in LDS, dynamic LDS bytes.
+int ccm_internal::sim3opt_debug_linearise(ccm_ctx* ctx, const double sim3[8], int n, const double* P1c, const double* P2c, const double* obs1, const double* obs2,
+                                          const double* info1, const double* info2, const double K1[4], const double K2[4], double th2, int fix_scale, const uint8_t* alive,
+                                          double* acc_out, double* chi2_out, double* err_out, double* pert_out, double* J_out, int shape[2]) {
+  if (!ctx || !sim3 || n < 1 || !P1c || !P2c || !obs1 || !obs2 || !info1 || !info2 || !K1 || !K2 || !alive || !acc_out || !chi2_out || !err_out || !pert_out || !J_out || !shape)
+    return ccm_set_error(ctx, CCM_E_ARG, "sim3opt_debug_linearise: bad args");
+  CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  // one device block: [sim3 8 | n_in | P1c 3n | P2c 3n | obs1 2n | obs2 2n | info1 n | info2 n | err 4n | acc 35 * 256 | chi2 256 | err_out 4n | pert 224 | J 28n] doubles,
+  // then inlier, alive, alive_in bytes
+  const size_t N = (size_t)n, n_acc = 35 * (size_t)kThreads, nd = 9 + 16 * N + n_acc + kThreads + 4 * N + kPertDoubles + 28 * N;
+  double* d = nullptr;
+  CCM_HIP_CHECK(ctx, hipMalloc(&d, nd * sizeof(double) + 3 * N + 64));
+  auto fail = [&](hipError_t e) { (void)hipFree(d); return ccm_set_error(ctx, CCM_E_HIP, std::string("sim3opt_debug_linearise: ") + hipGetErrorString(e)); };
+  hipError_t e = hipMemset(d, 0, nd * sizeof(double) + 3 * N + 64);
+  Sim3ProbeArgs a;
+  a.n = n; a.fix_scale = fix_scale ? 1 : 0; a.th2 = th2;
+  a.sim3 = d; a.n_in = (int*)(d + 8);
+  double* p1 = d + 9; double* p2 = p1 + 3 * N; double* o1 = p2 + 3 * N; double* o2 = o1 + 2 * N; double* i1 = o2 + 2 * N; double* i2 = i1 + N;
+  a.P1c = p1; a.P2c = p2; a.obs1 = o1; a.obs2 = o2; a.info1 = i1; a.info2 = i2; a.err = i2 + N;
+  a.acc_out = a.err + 4 * N; a.chi2_out = a.acc_out + n_acc; a.err_out = a.chi2_out + kThreads; a.pert_out = a.err_out + 4 * N; a.J_out = a.pert_out + kPertDoubles;
+  uint8_t* bytes_base = (uint8_t*)(d + nd);
+  a.inlier = bytes_base; a.alive = bytes_base + N;
+  uint8_t* al_in = bytes_base + 2 * N;
+  a.alive_in = al_in;
+  for (int k = 0; k < 4; k++) { a.K1[k] = K1[k]; a.K2[k] = K2[k]; }
+  if (e == hipSuccess) e = hipMemcpy(d, sim3, 8 * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(p1, P1c, 3 * N * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(p2, P2c, 3 * N * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(o1, obs1, 2 * N * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(o2, obs2, 2 * N * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(i1, info1, N * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(i2, info2, N * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(al_in, alive, N, hipMemcpyHostToDevice);
+  if (e != hipSuccess) return fail(e);
+  const Sim3Shape sh = sim3_launch_shape(n);
+  shape[0] = sh.use_lds; shape[1] = (int)sh.lds_bytes;
+  e = hipFuncSetAttribute((const void*)sim3opt_kernel_t<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+  if (e == hipSuccess) hipLaunchKernelGGL(sim3opt_kernel_t<true>, dim3(1), dim3(kThreads), sh.lds_bytes, ctx->stream, a, sh.use_lds);
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess) e = hipMemcpy(acc_out, a.acc_out, n_acc * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(chi2_out, a.chi2_out, kThreads * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(err_out, a.err_out, 4 * N * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(pert_out, a.pert_out, kPertDoubles * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(J_out, a.J_out, 28 * N * sizeof(double), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(e);
+  CCM_HIP_CHECK(ctx, hipFree(d));
+  return CCM_OK;
+}
 
 extern "C" int ccm_sim3_optimize(ccm_ctx* ctx, double sim3[8], int n, const double* P1c, const double* P2c, const double* obs1,
                                  const double* obs2, const double* info1, const double* info2, const double K1[4],
@@ -322,10 +420,9 @@ extern "C" int ccm_sim3_optimize(ccm_ctx* ctx, double sim3[8], int n, const doub
   CCM_HIP_CHECK(ctx, hipMemcpyAsync(d, h, n_in_d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   {
     ccm_prof_scope ps(ctx, CCM_K_SIM3OPT);
-    const size_t lds_head = (kRedDoubles + kPertDoubles) * sizeof(double);
-    const size_t lds_full = lds_head + 16 * (size_t)n * sizeof(double) + 2 * (size_t)n + 16;
-    const int use_lds = lds_full <= 150 * 1024;
-    const size_t lds_bytes = use_lds ? lds_full : lds_head;
+    const Sim3Shape sh = sim3_launch_shape(n);
+    const int use_lds = sh.use_lds;
+    const size_t lds_bytes = sh.lds_bytes;
     if (lds_bytes > 64 * 1024) {
       CCM_LDS_ATTR(ctx, CCM_LDS_SIM3OPT, sim3opt_kernel, 150 * 1024);
     }

@@ -96,6 +96,15 @@ extern "C" int ccm_debug_pg_solve(ccm_ctx* ctx, int n_vert, const double* sim3, 
                                   const double* meas, double lambda, int solver, double rel_tol, int max_it, const double* r_in, ccm_pg_debug_out* out) {
   return ccm_internal::pg_debug_solve(ctx, n_vert, sim3, fixed, fix_scale, n_edge, e_i, e_j, meas, lambda, solver, rel_tol, max_it, r_in, out);
 }
+extern "C" int ccm_debug_poseopt_linearise(ccm_ctx* ctx, const double cam_qt[7], int n, const double* Xw, const double* obs, const double* info, const double K[4],
+                                           const uint8_t* level, const uint8_t* robust, double* acc_out, double* err_out, int shape[3]) {
+  return ccm_internal::poseopt_debug_linearise(ctx, cam_qt, n, Xw, obs, info, K, level, robust, acc_out, err_out, shape);
+}
+extern "C" int ccm_debug_sim3opt_linearise(ccm_ctx* ctx, const double sim3[8], int n, const double* P1c, const double* P2c, const double* obs1, const double* obs2,
+                                           const double* info1, const double* info2, const double K1[4], const double K2[4], double th2, int fix_scale,
+                                           const uint8_t* alive, double* acc_out, double* chi2_out, double* err_out, double* pert_out, double* J_out, int shape[2]) {
+  return ccm_internal::sim3opt_debug_linearise(ctx, sim3, n, P1c, P2c, obs1, obs2, info1, info2, K1, K2, th2, fix_scale, alive, acc_out, chi2_out, err_out, pert_out, J_out, shape);
+}
 extern "C" int ccm_orb_debug_timing(const ccm_orb* o, double out_ms[6]) { return ccm_internal::orb_debug_timing(o, out_ms); }
 extern "C" int ccm_orb_debug_level(ccm_orb* o, int level, uint8_t* score_out, uint8_t* blur_out) { return ccm_internal::orb_debug_level(o, level, score_out, blur_out); }
 extern "C" int ccm_orb_debug_candidates(ccm_orb* o, int level, ccm_keypoint* out, int cap, int* n_out) { return ccm_internal::orb_debug_candidates(o, level, out, cap, n_out); }
@@ -142,6 +151,83 @@ extern "C" int ccm_debug_lane_xor(ccm_ctx* ctx, const double* in64, double* out_
   CCM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   CCM_HIP_CHECK(ctx, hipMemcpy(out_6x3x64, d + 64, 6 * 3 * 64 * sizeof(double), hipMemcpyDeviceToHost));
   CCM_HIP_CHECK(ctx, hipMemcpy(sums_2x64, d + 64 + 6 * 3 * 64, 192 * sizeof(double), hipMemcpyDeviceToHost));
+  CCM_HIP_CHECK(ctx, hipFree(d));
+  return CCM_OK;
+}
+
+// block_red.h as the LM kernels use it: ONE BlockRedT<4> object in one workgroup of 256 threads, its LDS laid out as in poseopt_kernel<true> ([2 * 4 * 64 | kTrDoubles]
+// doubles), and in a single launch the sequence  sum1, sum28_lds, sum28_lds, sum1, sum27, sum27, sum64<35>, sum64<35>, sum1  — the ping-pong phase and the transpose block
+// are reused back to back as in a kernel.  Call c reads slot s of thread t from in[in_off(c) + s * 256 + t] (1 / 32 / 64 slots) and writes EVERY thread's result k to
+// out[out_off(c) + k * 256 + t] (1 / 28 / 28 / 35 results).  tests/test_block_red_gpu.py.
+#include "block_red.h"
+namespace {
+constexpr int kProbeT = blockred::kThreads;
+__global__ __launch_bounds__(kProbeT) void block_red_probe(const double* in, double* out) {
+  using Red = blockred::BlockRedT<4>;
+  __shared__ __attribute__((aligned(16))) double sm[2 * 4 * 64 + Red::kTrDoubles];
+  double* const tr = sm + 2 * 4 * 64;
+  const int t = threadIdx.x;
+  Red red{sm, 0, t & 63, t >> 6};
+  auto one = [&]() { const double s = red.sum1(in[t]); in += kProbeT; out[t] = s; out += kProbeT; };
+  auto wide = [&](int which) {   // 0: sum28_lds, 1: sum27
+    double acc[32];
+#pragma unroll
+    for (int k = 0; k < 32; k++) acc[k] = in[k * kProbeT + t];
+    in += 32 * kProbeT;
+    if (which == 0) red.sum28_lds(acc, tr); else red.sum27(acc);
+#pragma unroll
+    for (int k = 0; k < 28; k++) out[k * kProbeT + t] = acc[k];
+    out += 28 * kProbeT;
+  };
+  auto wide64 = [&]() {
+    double acc[64];
+#pragma unroll
+    for (int k = 0; k < 64; k++) acc[k] = in[k * kProbeT + t];
+    in += 64 * kProbeT;
+    red.sum64<35>(acc);
+#pragma unroll
+    for (int k = 0; k < 35; k++) out[k * kProbeT + t] = acc[k];
+    out += 35 * kProbeT;
+  };
+  one(); wide(0); wide(0); one(); wide(1); wide(1); wide64(); wide64(); one();
+}
+constexpr int kProbeIn = (3 * 1 + 4 * 32 + 2 * 64) * kProbeT, kProbeOut = (3 * 1 + 4 * 28 + 2 * 35) * kProbeT;
+
+// lanex::from_partner_c with `off` an unrolled loop constant (as sum27 / sum64 call it) and lanex::wave_min_u32, all 64 lanes
+__global__ __launch_bounds__(64) void lane_ops_probe(const double* in, const uint32_t* key, double* partner, uint32_t* kmin) {
+  const double v = in[threadIdx.x];
+  int slot = 0;
+#pragma unroll
+  for (int off = 1; off <= 32; off <<= 1) partner[64 * slot++ + threadIdx.x] = lanex::from_partner_c(v, off);
+  kmin[threadIdx.x] = lanex::wave_min_u32(key[threadIdx.x]);
+}
+}  // namespace
+extern "C" int ccm_debug_block_red(ccm_ctx* ctx, const double* in, size_t n_in, double* out, size_t n_out) {
+  if (!ctx || !in || !out || n_in != (size_t)kProbeIn || n_out != (size_t)kProbeOut) return CCM_E_ARG;
+  CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  double* d = nullptr;
+  CCM_HIP_CHECK(ctx, hipMalloc(&d, (size_t)(kProbeIn + kProbeOut) * sizeof(double)));
+  CCM_HIP_CHECK(ctx, hipMemcpy(d, in, (size_t)kProbeIn * sizeof(double), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(block_red_probe, dim3(1), dim3(kProbeT), 0, ctx->stream, d, d + kProbeIn);
+  CCM_HIP_CHECK(ctx, hipGetLastError());
+  CCM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  CCM_HIP_CHECK(ctx, hipMemcpy(out, d + kProbeIn, (size_t)kProbeOut * sizeof(double), hipMemcpyDeviceToHost));
+  CCM_HIP_CHECK(ctx, hipFree(d));
+  return CCM_OK;
+}
+extern "C" int ccm_debug_lane_ops(ccm_ctx* ctx, const double* in64, const uint32_t* key64, double* partner_6x64, uint32_t* min64) {
+  if (!ctx || !in64 || !key64 || !partner_6x64 || !min64) return CCM_E_ARG;
+  CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  double* d = nullptr;   // in 64 | partner 6 * 64 | key 64 (u32) | min 64 (u32)
+  CCM_HIP_CHECK(ctx, hipMalloc(&d, (64 + 6 * 64 + 64) * sizeof(double)));
+  uint32_t* dk = reinterpret_cast<uint32_t*>(d + 64 + 6 * 64);
+  CCM_HIP_CHECK(ctx, hipMemcpy(d, in64, 64 * sizeof(double), hipMemcpyHostToDevice));
+  CCM_HIP_CHECK(ctx, hipMemcpy(dk, key64, 64 * sizeof(uint32_t), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(lane_ops_probe, dim3(1), dim3(64), 0, ctx->stream, d, dk, d + 64, dk + 64);
+  CCM_HIP_CHECK(ctx, hipGetLastError());
+  CCM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  CCM_HIP_CHECK(ctx, hipMemcpy(partner_6x64, d + 64, 6 * 64 * sizeof(double), hipMemcpyDeviceToHost));
+  CCM_HIP_CHECK(ctx, hipMemcpy(min64, dk + 64, 64 * sizeof(uint32_t), hipMemcpyDeviceToHost));
   CCM_HIP_CHECK(ctx, hipFree(d));
   return CCM_OK;
 }

@@ -28,4 +28,9 @@ int  covis_update_window(ccm_ctx* ctx, int small_window, int n_kf, int n_all, co
                          int32_t* needed);
 int  pg_debug_solve(ccm_ctx* ctx, int n_vert, const double* sim3, const uint8_t* fixed, int fix_scale, int n_edge, const int32_t* e_i, const int32_t* e_j,
                     const double* meas, double lambda, int solver, double rel_tol, int max_it, const double* r_in, ccm_pg_debug_out* out);
+int  poseopt_debug_linearise(ccm_ctx* ctx, const double cam_qt[7], int n, const double* Xw, const double* obs, const double* info, const double K[4],
+                             const uint8_t* level, const uint8_t* robust, double* acc_out, double* err_out, int shape[3]);
+int  sim3opt_debug_linearise(ccm_ctx* ctx, const double sim3[8], int n, const double* P1c, const double* P2c, const double* obs1, const double* obs2,
+                             const double* info1, const double* info2, const double K1[4], const double K2[4], double th2, int fix_scale, const uint8_t* alive,
+                             double* acc_out, double* chi2_out, double* err_out, double* pert_out, double* J_out, int shape[2]);
 }  // namespace ccm_internal

@@ -359,6 +359,74 @@ def debug_pg_solve(ctx: Context, pg: dict, lam: float, solver, rel_tol: float = 
     return res
 
 
+BLOCK_RED_CALLS = ("sum1", "sum28_lds", "sum28_lds", "sum1", "sum27", "sum27", "sum64", "sum64", "sum1")
+BLOCK_RED_SLOTS = {"sum1": (1, 1), "sum28_lds": (32, 28), "sum27": (32, 28), "sum64": (64, 35)}   # (input slots, results) per thread
+
+
+def debug_block_red(ctx: Context, inputs):
+    """Test hook (ccm_debug_block_red): the sequence BLOCK_RED_CALLS on one BlockRedT<4> object in ONE launch of 256 threads.  inputs: one array [slots, 256] per
+    call (slots as in BLOCK_RED_SLOTS); returns one array [results, 256] per call, the values EVERY thread ended with."""
+    if len(inputs) != len(BLOCK_RED_CALLS):
+        raise ValueError("one input array per call of BLOCK_RED_CALLS")
+    flat = []
+    for name, a in zip(BLOCK_RED_CALLS, inputs):
+        a = np.ascontiguousarray(a, np.float64)
+        if a.shape != (BLOCK_RED_SLOTS[name][0], 256):
+            raise ValueError(f"{name}: input must be [{BLOCK_RED_SLOTS[name][0]}, 256]")
+        flat.append(a.ravel())
+    src = np.concatenate(flat)
+    out = np.zeros(256 * sum(BLOCK_RED_SLOTS[n][1] for n in BLOCK_RED_CALLS))
+    check(hooks().ccm_debug_block_red(ctx.handle, C.c_void_p(_vp(src)), C.c_size_t(src.size), C.c_void_p(_vp(out)), C.c_size_t(out.size)), ctx.handle)
+    res, o = [], 0
+    for name in BLOCK_RED_CALLS:
+        k = BLOCK_RED_SLOTS[name][1]
+        res.append(out[o:o + 256 * k].reshape(k, 256).copy())
+        o += 256 * k
+    return res
+
+
+def debug_lane_ops(ctx: Context, v64, key64):
+    """Test hook (ccm_debug_lane_ops): lanex::from_partner_c(v, off) for off = 1, 2, 4, 8, 16, 32 ([6, 64]) and lanex::wave_min_u32(key) of the 64 lanes ([64])."""
+    v = np.ascontiguousarray(v64, np.float64); key = np.ascontiguousarray(key64, np.uint32)
+    if v.shape != (64,) or key.shape != (64,):
+        raise ValueError("64 lanes")
+    partner = np.zeros((6, 64)); kmin = np.zeros(64, np.uint32)
+    check(hooks().ccm_debug_lane_ops(ctx.handle, C.c_void_p(_vp(v)), C.c_void_p(_vp(key)), C.c_void_p(_vp(partner)), C.c_void_p(_vp(kmin))), ctx.handle)
+    return partner, kmin
+
+
+def debug_poseopt_linearise(ctx: Context, cam_qt, Xw, obs, info, K, level, robust):
+    """Test hook (ccm_debug_poseopt_linearise): staging and ONE linearisation of the pose optimiser's kernel at cam_qt with the given level / robust bytes per edge.
+    Returns a dict: acc[28, 256] (every thread's H upper triangle 0..20, b 21..26, robust chi2 27), err[n, 2], tr_red, use_lds, lds_bytes (the launch shape taken)."""
+    f = lambda a: np.ascontiguousarray(a, np.float64)
+    cam, Xw, obs, info, K = map(f, (cam_qt, Xw, obs, info, K))
+    n = Xw.shape[0]
+    level = np.ascontiguousarray(level, np.uint8); robust = np.ascontiguousarray(robust, np.uint8)
+    if obs.shape != (n, 2) or info.shape != (n,) or level.shape != (n,) or robust.shape != (n,):
+        raise ValueError("n edges: Xw[n, 3], obs[n, 2], info[n], level[n], robust[n]")
+    acc = np.zeros((28, 256)); err = np.zeros((n, 2)); shape = (C.c_int * 3)()
+    v = lambda a: C.c_void_p(_vp(a))
+    check(hooks().ccm_debug_poseopt_linearise(ctx.handle, v(cam), n, v(Xw), v(obs), v(info), v(K), v(level), v(robust), v(acc), v(err), shape), ctx.handle)
+    return dict(acc=acc, err=err, tr_red=bool(shape[0]), use_lds=bool(shape[1]), lds_bytes=int(shape[2]))
+
+
+def debug_sim3opt_linearise(ctx: Context, sim3, P1c, P2c, obs1, obs2, info1, info2, K1, K2, th2, fix_scale, alive):
+    """Test hook (ccm_debug_sim3opt_linearise): staging, chi2, perturbed estimates and ONE accumulation of the Sim3 optimiser's kernel at sim3 with the given alive bytes.
+    Returns a dict: acc[35, 256] (every thread's H upper triangle 0..27, b 28..34), chi2[256], err[n, 4], pert[14, 2, 8] (perturbation 2 d / 2 d + 1 = +-delta e_d;
+    the estimate, its inverse), J[n, 2, 2, 7] (pair, side, row, column), use_lds, lds_bytes (the launch shape taken)."""
+    f = lambda a: np.ascontiguousarray(a, np.float64)
+    s, P1c, P2c, obs1, obs2, info1, info2, K1, K2 = map(f, (sim3, P1c, P2c, obs1, obs2, info1, info2, K1, K2))
+    n = P1c.shape[0]
+    alive = np.ascontiguousarray(alive, np.uint8)
+    if P2c.shape != (n, 3) or obs1.shape != (n, 2) or obs2.shape != (n, 2) or info1.shape != (n,) or info2.shape != (n,) or alive.shape != (n,):
+        raise ValueError("n pairs: P1c[n, 3], P2c[n, 3], obs1[n, 2], obs2[n, 2], info1[n], info2[n], alive[n]")
+    acc = np.zeros((35, 256)); chi2 = np.zeros(256); err = np.zeros((n, 4)); pert = np.zeros((14, 2, 8)); J = np.zeros((n, 2, 2, 7)); shape = (C.c_int * 2)()
+    v = lambda a: C.c_void_p(_vp(a))
+    check(hooks().ccm_debug_sim3opt_linearise(ctx.handle, v(s), n, v(P1c), v(P2c), v(obs1), v(obs2), v(info1), v(info2), v(K1), v(K2), C.c_double(th2),
+                                              int(bool(fix_scale)), v(alive), v(acc), v(chi2), v(err), v(pert), v(J), shape), ctx.handle)
+    return dict(acc=acc, chi2=chi2, err=err, pert=pert, J=J, use_lds=bool(shape[0]), lds_bytes=int(shape[1]))
+
+
 def debug_dense_solve(ctx: Context, A, b):
     """Test hook: SPD solve through the device's blocked MFMA-f64 Cholesky (ccm_debug_dense_solve)."""
     A = np.ascontiguousarray(A, np.float64); b = np.ascontiguousarray(b, np.float64)

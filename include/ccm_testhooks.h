@@ -85,6 +85,29 @@ int  ccm_debug_pg_solve(ccm_ctx* ctx, int n_vert, const double* sim3, const uint
  * lanex::wave_incl_scan_i32 of the integer pattern (37 lane mod 101) - 20. */
 int  ccm_debug_lane_xor(ccm_ctx* ctx, const double* in64, double* out_6x3x64, double* sums_3x64);
 
+/* test hook for ccm_slam_amd/csrc/block_red.h: one workgroup of 256 threads with ONE BlockRedT<4> object, LDS laid out as in the pose optimiser's kernel, runs in a
+ * single launch  sum1, sum28_lds, sum28_lds, sum1, sum27, sum27, sum64<35>, sum64<35>, sum1.  The calls' inputs follow each other in `in`, slot s of thread t of a call
+ * at s * 256 + t (1, 32, 32, 1, 32, 32, 64, 64, 1 slots: n_in = 259 * 256); `out` receives EVERY thread's results the same way (1, 28, 28, 1, 28, 28, 35, 35, 1
+ * results: n_out = 185 * 256).  Other sizes: CCM_E_ARG. */
+int  ccm_debug_block_red(ccm_ctx* ctx, const double* in, size_t n_in, double* out, size_t n_out);
+/* test hook for lane_xor.h: lanex::from_partner_c(v, off) for off = 1, 2, 4, 8, 16, 32 as an unrolled loop constant ([6][64]) and lanex::wave_min_u32 of key64, all 64 lanes */
+int  ccm_debug_lane_ops(ccm_ctx* ctx, const double* in64, const uint32_t* key64, double* partner_6x64, uint32_t* min64);
+
+/* test hook for ccm_pose_optimize: the kernel's own staging and ONE linearisation at the given pose with GIVEN level / robust bytes per edge, in the launch shape the
+ * product call takes at this n (n >= 1).  acc_out[28][256]: every thread's reduced sums, [k * 256 + thread] — k = 0..20 the upper triangle of H row by row, 21..26 b,
+ * 27 the robust chi2; err_out[2n]: the residuals of the active edges, 0 elsewhere; shape: transpose reduction (1) or cross-lane (0), staged in LDS, dynamic LDS bytes. */
+int  ccm_debug_poseopt_linearise(ccm_ctx* ctx, const double cam_qt[7], int n, const double* Xw, const double* obs, const double* info, const double K[4],
+                                 const uint8_t* level, const uint8_t* robust, double* acc_out, double* err_out, int shape[3]);
+
+/* test hook for ccm_sim3_optimize: the kernel's own staging, the chi2 of the pairs with alive != 0 at sim3, the 14 perturbed estimates of the numeric differentiation
+ * and ONE accumulation of H and b, in the launch shape the product call takes at this n (n >= 1).  acc_out[35][256]: every thread's reduced sums, [k * 256 + thread] —
+ * k = 0..27 the upper triangle of H row by row, 28..34 b; chi2_out[256]: every thread's robust chi2; err_out[4n]: the residuals of both edges of the alive pairs, 0
+ * elsewhere; pert_out[14][16]: for d = 0..6 S(+delta e_d) (8) | its inverse (8), then the same for -delta; J_out[n][2][14]: per pair and side (0: x1 = S X2, 1:
+ * x2 = S^-1 X1) the numeric Jacobian, row 0 (7) | row 1 (7), 0 for the other pairs; shape: staged in LDS, dynamic LDS bytes. */
+int  ccm_debug_sim3opt_linearise(ccm_ctx* ctx, const double sim3[8], int n, const double* P1c, const double* P2c, const double* obs1, const double* obs2,
+                                 const double* info1, const double* info2, const double K1[4], const double K2[4], double th2, int fix_scale,
+                                 const uint8_t* alive, double* acc_out, double* chi2_out, double* err_out, double* pert_out, double* J_out, int shape[2]);
+
 /* test hook for ccm_covis_update: the same call with a histogram window of 64 keyframe indices, so that a small n_all spans several windows */
 int  ccm_debug_covis_update_small(ccm_ctx* ctx, int n_kf, int n_all, const int32_t* order_key, const int32_t* list_off, const int32_t* list_pt,
                                   const uint8_t* list_skip, int n_pt, const int32_t* obs_off, const int32_t* obs_kf, int th, int cap, int32_t* row_off,
