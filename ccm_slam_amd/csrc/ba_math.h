@@ -131,7 +131,8 @@ BA_HD BaPose ba_oplus(const double u[6], const BaPose& T) {
 // redundantly): ba_oplus is ~380 mostly dependent f64 instructions (sincos, four square roots, four divisions, a rotation matrix turned into a quaternion) ~ 1 us.
 // For 1e-5 <= theta < 0.5 — every LM step that matters — the rotation part of exp is written directly as the unit quaternion (omega sin(theta/2)/theta, cos(theta/2)) and
 // the coefficients sin(theta/2)/theta, cos(theta/2), (1 - cos theta)/theta^2, (theta - sin theta)/theta^3 are even power series in theta^2 (truncation < 1e-17 relative
-// at theta = 0.5; three independent Horner chains), so no sincos, no matrix -> quaternion conversion and one normalisation are left.  Same rotation as ba_oplus to 1 ulp; the translation
+// at theta = 0.5; three independent Horner chains), so no sincos, no matrix -> quaternion conversion and one normalisation are left.  Same rotation as ba_oplus to rounding (both are a few roundings from the exact update; on the device
+// the largest quaternion component difference is 3.3e-16 = 1.5 ulp of 1, tests/test_lie_math_gpu.py holds it below 1e-15 and each within its own running error bound); the translation
 // differs by up to 1e-11 relative, because the closed forms (1 - cos t)/t^2 and (t - sin t)/t^3 cancel for small angles and the series do not (tests/test_ba_math_host.py builds
 // both for the host and compares them over 2 000 000 updates); outside the range (g2o's small-angle branch R = I + Om + Om^2 below 1e-5 included) it IS ba_oplus.
 BA_HD BaPose ba_oplus_fast(const double u[6], const BaPose& T) {

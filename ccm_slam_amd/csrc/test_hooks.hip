@@ -290,3 +290,29 @@ extern "C" int ccm_kfstore_debug_get_featvec(ccm_kfstore* st, ccm_ctx* ctx, int6
   for (int i = 0; i < L; i++) idx[i] = h[i];
   return CCM_OK;
 }
+
+// test_lie_ops.h on the device: one lane per item in workgroups of 256, item i reads in[48 i ...] and writes out[40 i ...]; `out` is copied to the device first (ba_spd6_inv
+// must leave its output untouched on a false return).  tests/test_lie_math_gpu.py compares with tests/lie_reference.py.
+#include "test_lie_ops.h"
+namespace {
+__global__ __launch_bounds__(256) void lie_eval_probe(int op, int n, const double* in, double* out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  lie_eval(op, in + (size_t)kLieIn * i, out + (size_t)kLieOut * i);
+}
+}  // namespace
+extern "C" int ccm_debug_lie_eval(ccm_ctx* ctx, int op, int n, const double* in, double* out) {
+  if (!ctx || op < 0 || op >= LIE_N_OPS || n < 1 || n > (1 << 20) || !in || !out) return CCM_E_ARG;
+  CCM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const size_t n_in = (size_t)kLieIn * n, n_out = (size_t)kLieOut * n;
+  struct Buf { double* p = nullptr; ~Buf() { if (p) (void)hipFree(p); } } buf;   // freed on every return, the early ones of CCM_HIP_CHECK included
+  CCM_HIP_CHECK(ctx, hipMalloc(&buf.p, (n_in + n_out) * sizeof(double)));
+  double* const d = buf.p;
+  CCM_HIP_CHECK(ctx, hipMemcpy(d, in, n_in * sizeof(double), hipMemcpyHostToDevice));
+  CCM_HIP_CHECK(ctx, hipMemcpy(d + n_in, out, n_out * sizeof(double), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(lie_eval_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, op, n, d, d + n_in);
+  CCM_HIP_CHECK(ctx, hipGetLastError());
+  CCM_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  CCM_HIP_CHECK(ctx, hipMemcpy(out, d + n_in, n_out * sizeof(double), hipMemcpyDeviceToHost));
+  return CCM_OK;
+}

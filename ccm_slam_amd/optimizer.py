@@ -395,6 +395,19 @@ def debug_lane_ops(ctx: Context, v64, key64):
     return partner, kmin
 
 
+def debug_lie_eval(ctx: Context, op: int, x, out_init=None):
+    """Test hook (ccm_debug_lie_eval): lie_eval(op, ...) of csrc/test_lie_ops.h on the device for the items x[n, 48], one lane each; returns out[n, 40]
+    (out[:, 39] the flag word).  out_init: the values the outputs start from (default 0)."""
+    x = np.ascontiguousarray(x, np.float64)
+    if x.ndim != 2 or x.shape[1] != 48 or x.shape[0] < 1:
+        raise ValueError("x must be [n, 48], n >= 1")
+    out = np.zeros((x.shape[0], 40)) if out_init is None else np.ascontiguousarray(out_init, np.float64).copy()
+    if out.shape != (x.shape[0], 40):
+        raise ValueError("out_init must be [n, 40]")
+    check(hooks().ccm_debug_lie_eval(ctx.handle, int(op), int(x.shape[0]), C.c_void_p(_vp(x)), C.c_void_p(_vp(out))), ctx.handle)
+    return out
+
+
 def debug_poseopt_linearise(ctx: Context, cam_qt, Xw, obs, info, K, level, robust):
     """Test hook (ccm_debug_poseopt_linearise): staging and ONE linearisation of the pose optimiser's kernel at cam_qt with the given level / robust bytes per edge.
     Returns a dict: acc[28, 256] (every thread's H upper triangle 0..20, b 21..26, robust chi2 27), err[n, 2], tr_red, use_lds, lds_bytes (the launch shape taken)."""

@@ -123,6 +123,11 @@ int  ccm_debug_twoview_score(ccm_ctx* ctx, int model, int n_models, const float*
  * vector); node / off / idx (nullable; room for n + 1, n + 1 and n entries, n the key's feature count) receive node[nn], off[nn + 1], idx[off[nn]]. */
 int  ccm_kfstore_debug_get_featvec(ccm_kfstore* store, ccm_ctx* ctx, int64_t key, int* nn, int32_t* node, int32_t* off, int32_t* idx);
 
+/* test hook for ccm_slam_amd/csrc/ba_math.h and sim3_math.h: lie_eval(op, in + 48 i, out + 40 i) of csrc/test_lie_ops.h for the items i < n (1 <= n <= 2^20), one
+ * lane per item in workgroups of 256.  op: the LieOp number (tests/lie_reference.py lists every op's layout).  `out` is an in-out array: the device starts from the
+ * caller's values (ba_spd6_inv leaves its output untouched on a false return); out[40 i + 39] receives the flag word. */
+int  ccm_debug_lie_eval(ccm_ctx* ctx, int op, int n, const double* in, double* out);
+
 #ifdef __cplusplus
 }
 #endif
