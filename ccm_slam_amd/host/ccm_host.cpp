@@ -1,6 +1,7 @@
-// ccm_host.cpp — implementation of the host-side mirror (see ccm_host.h).  Plain C++17, no HIP headers:
+// ccm_host.cpp — implementation of the host-side mirror's classes (see ccm_host.h; their C entry points are in c_*.cpp).  Plain C++17, no HIP headers:
 // everything device-side goes through the C ABI.
 #include "ccm_host.h"
+#include "mirror_internal.h"
 #include "kfdb_resolve.h"
 #include "../csrc/triangulate_math.h"
 #include "../csrc/twoview_math.h"
@@ -1196,7 +1197,7 @@ bool PnPRansacBatch::iterate(int c, int nIterations, bool& bNoMore, Pose& out) {
 
 // ---- TwoViewInitializer -------------------------------------------------------------------------------
 // twoview_math.h on the calling thread with the arguments of ccm_twoview_ransac_eval; model: 0 both, 1 the homography only, 2 the fundamental matrix only
-static int twoview_ransac_host(int N, const float* xy1, const float* xy2, const float* pn1, const float* pn2, const float* T1, const float* T2inv, const float* T2t,
+int detail::twoview_ransac_host(int N, const float* xy1, const float* xy2, const float* pn1, const float* pn2, const float* T1, const float* T2inv, const float* T2t,
                                float sigma, int H, const int32_t* sets, int model, float* scoreH, float* scoreF, float* H21, float* F21, uint32_t* maskH,
                                uint32_t* maskF) {
   if (N < 8 || H < 1 || !xy1 || !xy2 || !pn1 || !pn2 || !T1 || !T2inv || !T2t || !sets) return -1;
@@ -1224,7 +1225,7 @@ static int twoview_ransac_host(int N, const float* xy1, const float* xy2, const 
   return 0;
 }
 
-static int twoview_check_rt_host(int n_hyp, const float* rec, const float* K, int N, const float* xy1, const float* xy2, const uint32_t* inl, float th2,
+int detail::twoview_check_rt_host(int n_hyp, const float* rec, const float* K, int N, const float* xy1, const float* xy2, const uint32_t* inl, float th2,
                                  uint8_t* status, float* x3d, float* cosp) {
   if (n_hyp < 1 || n_hyp > 8 || N < 1 || !rec || !K || !xy1 || !xy2 || !inl || !status || !x3d || !cosp) return -1;
   for (int q = 0; q < n_hyp; q++) {
@@ -1291,7 +1292,7 @@ TwoViewInitializer::Models TwoViewInitializer::FindModels(std::vector<float> key
     const int rc = ccm_twoview_ransac_eval(ctx_->get(), N, xy1_.data(), xy2_.data(), pn1.data(), pn2.data(), T1, T2inv, T2t, sigma_, H, sets.data(), sH.data(), sF.data(),
                                            H21.data(), F21.data(), mH.data(), mF.data());
     if (rc != CCM_OK) throw infrastructure_ex(std::string("ccm_twoview_ransac_eval: ") + ccm_last_error(ctx_->get()));
-  } else if (twoview_ransac_host(N, xy1_.data(), xy2_.data(), pn1.data(), pn2.data(), T1, T2inv, T2t, sigma_, H, sets.data(), 0, sH.data(), sF.data(), H21.data(),
+  } else if (detail::twoview_ransac_host(N, xy1_.data(), xy2_.data(), pn1.data(), pn2.data(), T1, T2inv, T2t, sigma_, H, sets.data(), 0, sH.data(), sF.data(), H21.data(),
                                  F21.data(), mH.data(), mF.data()) != 0) {
     throw infrastructure_ex("TwoViewInitializer::FindModels: a set index out of range or repeated");
   }
@@ -1331,7 +1332,7 @@ std::vector<TwoViewInitializer::Reconstruction> TwoViewInitializer::CheckRTBatch
     const int rc = ccm_twoview_check_rt(ctx_->get(), Q, rec.data(), K_, N, xy1_.data(), xy2_.data(), mask.data(), th2, status.data(), x3d.data(), cosp.data());
     if (rc != CCM_OK) throw infrastructure_ex(std::string("ccm_twoview_check_rt: ") + ccm_last_error(ctx_->get()));
   } else {
-    twoview_check_rt_host(Q, rec.data(), K_, N, xy1_.data(), xy2_.data(), mask.data(), th2, status.data(), x3d.data(), cosp.data());
+    detail::twoview_check_rt_host(Q, rec.data(), K_, N, xy1_.data(), xy2_.data(), mask.data(), th2, status.data(), x3d.data(), cosp.data());
   }
   std::vector<Reconstruction> out((size_t)Q);
   const size_t N1 = keys1_.size() / 2;
@@ -2929,1557 +2930,3 @@ NewMapPointBatch::Pairs SearchForTriangulationBatch::predicted(int j) {
 }
 
 }  // namespace cslam
-
-// ---- C entry points (ccm_host_c.h): the Python test-suite and the drop-in translation units under shim/ ---------------------------------------
-#include "ccm_host_c.h"
-namespace {
-// one context per (calling thread, device), created on first use and kept for the thread's lifetime: the reference's threads (tracking, mapping, loop
-// finder ...) each call the matcher / optimizer from their own loop, so the per-call cost is a map lookup, not a stream + buffer set-up
-cslam::HipContext& thread_context(int device) {
-  thread_local std::map<int, std::unique_ptr<cslam::HipContext>> ctxs;
-  auto& c = ctxs[device];
-  if (!c) c.reset(new cslam::HipContext(device));
-  return *c;
-}
-}  // namespace
-extern "C" {
-int ccmh_search_by_projection_mp(int device, const float* kx, const float* ky, const int32_t* oct, const uint8_t* fdesc, int N,
-                                 float minX, float minY, float maxX, float maxY, const float* scale_factors, int n_mp,
-                                 const uint8_t* in_view, const float* px, const float* py, const int32_t* lvl, const float* vcos,
-                                 const uint8_t* mp_desc, float th, float nnratio, int32_t* frame_mp) {
-  try {
-    cslam::HipContext& ctx = thread_context(device);
-    std::vector<cslam::KeyPoint> kps(N);
-    for (int i = 0; i < N; i++) kps[i] = cslam::KeyPoint{kx[i], ky[i], 31.f, 0.f, 0.f, oct[i]};
-    cslam::FrameView F; F.N = N; F.mvKeysUn = kps.data(); F.mDescriptors = fdesc; F.mnMinX = minX; F.mnMinY = minY; F.mnMaxX = maxX; F.mnMaxY = maxY;
-    F.mvScaleFactors = scale_factors; F.mvpMapPoints = frame_mp;
-    cslam::TrackedMapPoints M; M.n = n_mp; M.mbTrackInView = in_view; M.mTrackProjX = px; M.mTrackProjY = py; M.mnTrackScaleLevel = lvl;
-    M.mTrackViewCos = vcos; M.mDescriptor = mp_desc;
-    cslam::ORBmatcher m(ctx, nnratio, true);
-    return m.SearchByProjection(F, M, th);
-  } catch (const std::exception&) { return -1000; }
-}
-
-int ccmh_search_by_projection_last(int device, const float* kx, const float* ky, const int32_t* oct, const float* kangle,
-                                   const uint8_t* fdesc, int N, float minX, float minY, float maxX, float maxY,
-                                   const float* scale_factors, int n_last, const uint8_t* valid, const float* u, const float* v,
-                                   const int32_t* l_oct, const float* l_angle, const uint8_t* l_desc, float th, int check_ori,
-                                   int32_t* cur_mp) {
-  try {
-    cslam::HipContext& ctx = thread_context(device);
-    std::vector<cslam::KeyPoint> kps(N);
-    for (int i = 0; i < N; i++) kps[i] = cslam::KeyPoint{kx[i], ky[i], 31.f, kangle[i], 0.f, oct[i]};
-    cslam::FrameView F; F.N = N; F.mvKeysUn = kps.data(); F.mDescriptors = fdesc; F.mnMinX = minX; F.mnMinY = minY; F.mnMaxX = maxX; F.mnMaxY = maxY;
-    F.mvScaleFactors = scale_factors; F.mvpMapPoints = cur_mp;
-    cslam::LastFrameProjections L; L.n = n_last; L.valid = valid; L.u = u; L.v = v; L.octave = l_oct; L.angle = l_angle; L.mpDescriptor = l_desc;
-    cslam::ORBmatcher m(ctx, 0.9f, check_ori != 0);
-    return m.SearchByProjection(F, L, th);
-  } catch (const std::exception&) { return -1000; }
-}
-
-int ccmh_local_ba(int device, int n_cam, int n_pt, int n_edge, double* cam_qt, const uint8_t* cam_fixed, const double* cam_K,
-                  double* pt_xyz, const int32_t* e_cam, const int32_t* e_pt, const double* e_obs, const double* e_info, uint8_t* to_erase) {
-  try {
-    cslam::HipContext& ctx = thread_context(device);
-    cslam::BAProblem p;
-    p.cam_qt.assign(cam_qt, cam_qt + 7 * (size_t)n_cam); p.cam_fixed.assign(cam_fixed, cam_fixed + n_cam);
-    p.cam_K.assign(cam_K, cam_K + 4 * (size_t)n_cam); p.pt_xyz.assign(pt_xyz, pt_xyz + 3 * (size_t)n_pt);
-    p.e_cam.assign(e_cam, e_cam + n_edge); p.e_pt.assign(e_pt, e_pt + n_edge);
-    p.e_obs.assign(e_obs, e_obs + 2 * (size_t)n_edge); p.e_info.assign(e_info, e_info + n_edge);
-    std::vector<uint8_t> er;
-    cslam::Optimizer::LocalBundleAdjustmentClient(ctx, p, nullptr, er);
-    std::memcpy(cam_qt, p.cam_qt.data(), sizeof(double) * p.cam_qt.size());
-    std::memcpy(pt_xyz, p.pt_xyz.data(), sizeof(double) * p.pt_xyz.size());
-    std::memcpy(to_erase, er.data(), er.size());
-    return 0;
-  } catch (const std::exception&) { return -1000; }
-}
-
-// SearchByProjection(Frame, map points) through the device grid: raw (distorted) keypoints in, match table + undistorted xy out
-int ccmh_search_by_projection_mp_dev(int device, const float* K, const float* dist, int n_dist, int w, int h, const void* kps_raw, const uint8_t* fdesc,
-                                     int N, const float* scale_factors, int n_mp, const uint8_t* in_view, const float* px, const float* py,
-                                     const int32_t* lvl, const float* vcos, const uint8_t* mp_desc, float th, float nnratio, int32_t* frame_mp,
-                                     float* xy_un_out) {
-  try {
-    cslam::HipContext& ctx = thread_context(device);
-    cslam::FrameGridDev grid(ctx, K, dist, n_dist, w, h);
-    std::vector<cslam::KeyPoint> keys((const cslam::KeyPoint*)kps_raw, (const cslam::KeyPoint*)kps_raw + N), keysUn;
-    grid.SetKeyPoints(keys, fdesc, keysUn);
-    for (int i = 0; i < N; i++) { xy_un_out[2 * i] = keysUn[i].x; xy_un_out[2 * i + 1] = keysUn[i].y; }
-    cslam::FrameView F;
-    F.N = N; F.mvKeysUn = keysUn.data(); F.mDescriptors = fdesc;
-    F.mnMinX = grid.mnMinX; F.mnMinY = grid.mnMinY; F.mnMaxX = grid.mnMaxX; F.mnMaxY = grid.mnMaxY;
-    F.mvScaleFactors = scale_factors; F.mvpMapPoints = frame_mp;
-    cslam::TrackedMapPoints mps;
-    mps.n = n_mp; mps.mbTrackInView = in_view; mps.mTrackProjX = px; mps.mTrackProjY = py; mps.mnTrackScaleLevel = lvl; mps.mTrackViewCos = vcos;
-    mps.mDescriptor = mp_desc;
-    cslam::ORBmatcher m(ctx, nnratio, true);
-    return m.SearchByProjection(grid, F, mps, th);
-  } catch (const std::exception&) { return -1000; }
-}
-
-// SearchByProjection(Frame, LastFrame) through the device grid; keypoints given already undistorted (no distortion coefficients)
-int ccmh_search_by_projection_last_dev(int device, const void* kps_un, const uint8_t* cdesc, int N, int w, int h, const float* scale_factors, int n_last,
-                                       const uint8_t* valid, const float* u, const float* v, const int32_t* oct, const float* angle, const uint8_t* mp_desc,
-                                       float th, int check_ori, int32_t* frame_mp) {
-  try {
-    cslam::HipContext& ctx = thread_context(device);
-    const float K[4] = {1.f, 1.f, 0.f, 0.f};
-    cslam::FrameGridDev grid(ctx, K, nullptr, 0, w, h);
-    std::vector<cslam::KeyPoint> keys((const cslam::KeyPoint*)kps_un, (const cslam::KeyPoint*)kps_un + N), keysUn;
-    grid.SetKeyPoints(keys, cdesc, keysUn);
-    cslam::FrameView C;
-    C.N = N; C.mvKeysUn = keysUn.data(); C.mDescriptors = cdesc;
-    C.mnMinX = grid.mnMinX; C.mnMinY = grid.mnMinY; C.mnMaxX = grid.mnMaxX; C.mnMaxY = grid.mnMaxY;
-    C.mvScaleFactors = scale_factors; C.mvpMapPoints = frame_mp;
-    cslam::LastFrameProjections L;
-    L.n = n_last; L.valid = valid; L.u = u; L.v = v; L.octave = oct; L.angle = angle; L.mpDescriptor = mp_desc;
-    cslam::ORBmatcher m(ctx, 0.9f, check_ori != 0);
-    return m.SearchByProjection(grid, C, L, th);
-  } catch (const std::exception&) { return -1000; }
-}
-
-int ccmh_optimize_sim3(int device, double* sim3, int n, const double* P1c, const double* P2c, const double* obs1, const double* obs2,
-                       const double* info1, const double* info2, const double* K1, const double* K2, float th2, int fix_scale, uint8_t* keep) {
-  try {
-    cslam::HipContext& ctx = thread_context(device);
-    std::vector<uint8_t> k;
-    const int nin = cslam::Optimizer::OptimizeSim3(ctx, sim3, n, P1c, P2c, obs1, obs2, info1, info2, K1, K2, th2, fix_scale != 0, k);
-    if (n) std::memcpy(keep, k.data(), k.size());
-    return nin;
-  } catch (const std::exception&) { return -1000; }
-}
-
-int ccmh_orb_extract(int device, int nfeatures, const uint8_t* img, int w, int h, void* kps_out, uint8_t* desc_out, int cap) {
-  try {
-    cslam::HipContext& ctx = thread_context(device);
-    cslam::ORBextractor ex(ctx, nfeatures, 1.2f, 8, 20, 7);
-    std::vector<cslam::KeyPoint> k; std::vector<uint8_t> d;
-    ex(img, w, h, w, k, d);
-    const int n = std::min<int>((int)k.size(), cap);
-    std::memcpy(kps_out, k.data(), sizeof(cslam::KeyPoint) * n);
-    std::memcpy(desc_out, d.data(), (size_t)n * 32);
-    return n;
-  } catch (const std::exception&) { return -1000; }
-}
-}
-
-// ---- C wrappers for the BoW / triangulation / initialisation searches --------------------------------------
-namespace {
-std::vector<cslam::KeyPoint> mk_keys(const float* x, const float* y, const int32_t* oct, const float* ang, int N) {
-  std::vector<cslam::KeyPoint> k(N);
-  for (int i = 0; i < N; i++) k[i] = cslam::KeyPoint{x[i], y[i], 31.f, ang ? ang[i] : 0.f, 0.f, oct ? oct[i] : 0};
-  return k;
-}
-}
-extern "C" {
-// mode 0: SearchByBoW(KF,F) -> out[N2] ; 1: SearchByBoW(KF,KF) -> out[N1] ; 2: SearchForTriangulation -> out[N1]
-int ccmh_search_bow(int device, int mode, const int32_t* n1, const int32_t* o1, const int32_t* i1, int nn1, const int32_t* n2,
-                    const int32_t* o2, const int32_t* i2, int nn2, const uint8_t* has1, const uint8_t* has2, const uint8_t* d1,
-                    const float* x1, const float* y1, const float* a1, int N1, const uint8_t* d2, const float* x2, const float* y2,
-                    const int32_t* oct2, const float* a2, int N2, const float* F12, float ex, float ey, const float* sigma2_2,
-                    const float* sf2, float nnratio, int check_ori, int32_t* out) {
-  try {
-    cslam::HipContext& ctx = thread_context(device);
-    auto k1 = mk_keys(x1, y1, nullptr, a1, N1), k2 = mk_keys(x2, y2, oct2, a2, N2);
-    cslam::KeysView A; A.N = N1; A.keys = k1.data(); A.desc = d1; A.hasMapPoint = has1; A.fv = cslam::FeatureVectorView{nn1, n1, o1, i1};
-    cslam::KeysView B; B.N = N2; B.keys = k2.data(); B.desc = d2; B.hasMapPoint = has2; B.fv = cslam::FeatureVectorView{nn2, n2, o2, i2};
-    cslam::ORBmatcher m(ctx, nnratio, check_ori != 0);
-    std::vector<int32_t> r; int n = 0;
-    if (mode == 0) n = m.SearchByBoW(A, B, r);
-    else if (mode == 1) n = m.SearchByBoW_KF(A, B, r);
-    else n = m.SearchForTriangulation(A, B, F12, ex, ey, sigma2_2, sf2, r);
-    std::memcpy(out, r.data(), r.size() * sizeof(int32_t));
-    return n;
-  } catch (const std::exception&) { return -1000; }
-}
-
-// TriangulationBatch through C (shim/ORBmatcher_hip.cpp, tests): neighbour arrays as arrays of pointers, one entry per neighbour
-void* ccmh_tri_batch_create(int device, float nnratio, int check_ori, const int32_t* n1, const int32_t* o1, const int32_t* i1, int nn1, const uint8_t* has1,
-                            const uint8_t* d1, const float* x1, const float* y1, const float* a1, int N1, int n_nb, const int32_t* const* n2,
-                            const int32_t* const* o2, const int32_t* const* i2, const int32_t* nn2, const uint8_t* const* has2, const uint8_t* const* d2,
-                            const float* const* x2, const float* const* y2, const int32_t* const* oct2, const float* const* a2, const int32_t* N2) {
-  try {
-    cslam::HipContext& ctx = thread_context(device);
-    auto k1 = mk_keys(x1, y1, nullptr, a1, N1);
-    cslam::KeysView A; A.N = N1; A.keys = k1.data(); A.desc = d1; A.hasMapPoint = has1; A.fv = cslam::FeatureVectorView{nn1, n1, o1, i1};
-    std::vector<std::vector<cslam::KeyPoint>> k2((size_t)n_nb);
-    std::vector<cslam::KeysView> B((size_t)n_nb);
-    for (int j = 0; j < n_nb; j++) {
-      k2[j] = mk_keys(x2[j], y2[j], oct2[j], a2[j], N2[j]);
-      B[j].N = N2[j]; B[j].keys = k2[j].data(); B[j].desc = d2[j]; B[j].hasMapPoint = has2[j]; B[j].fv = cslam::FeatureVectorView{nn2[j], n2[j], o2[j], i2[j]};
-    }
-    cslam::ORBmatcher m(ctx, nnratio, check_ori != 0);
-    return new cslam::TriangulationBatch(m, A, B);
-  } catch (const std::exception&) { return nullptr; }
-}
-int ccmh_tri_batch_resolve(void* h, int j, const uint8_t* has1_now, const uint8_t* has2_now, const float* F12, float ex, float ey, const float* sigma2_2,
-                           const float* sf2, int32_t* matches12) {
-  try {
-    std::vector<int32_t> r;
-    const int n = static_cast<cslam::TriangulationBatch*>(h)->resolve(j, has1_now, has2_now, F12, ex, ey, sigma2_2, sf2, r);
-    std::memcpy(matches12, r.data(), r.size() * sizeof(int32_t));
-    return n;
-  } catch (const std::exception&) { return -1000; }
-}
-long long ccmh_tri_batch_candidates(void* h) { return h ? (long long)static_cast<cslam::TriangulationBatch*>(h)->candidates() : 0; }
-void ccmh_tri_batch_destroy(void* h) { delete static_cast<cslam::TriangulationBatch*>(h); }
-
-// NewMapPointBatch through C.  cam records: 21 floats each (include/ccm_hip.h, ccm_triangulate_pairs); tables: nlevels floats each.
-static cslam::LevelTables mk_tables(int nlevels, const float* s1, const float* f1, const float* s2, const float* f2) {
-  cslam::LevelTables lv;
-  if (nlevels < 1 || !s1 || !f1 || !s2 || !f2) throw cslam::infrastructure_ex("level tables");
-  lv.nlevels = nlevels;
-  lv.sigma2_1.assign(s1, s1 + nlevels); lv.sf_1.assign(f1, f1 + nlevels); lv.sigma2_2.assign(s2, s2 + nlevels); lv.sf_2.assign(f2, f2 + nlevels);
-  return lv;
-}
-void* ccmh_newpts_create(int device, const float* cam1, int N1, const float* x1, const float* y1, const int32_t* oct1, int n_nb, const float* cam2,
-                         const int32_t* N2, const float* const* x2, const float* const* y2, const int32_t* const* oct2, const int32_t* pair_off,
-                         const int32_t* idx12, int nlevels, const float* sigma2_1, const float* sf_1, const float* sigma2_2, const float* sf_2,
-                         float ratio_factor) {
-  try {
-    if (!cam1 || n_nb < 0 || (n_nb > 0 && (!cam2 || !N2 || !x2 || !y2 || !oct2 || !pair_off))) return nullptr;
-    cslam::CamRecord c1; std::memcpy(&c1, cam1, sizeof c1);
-    std::vector<cslam::NewMapPointBatch::Neighbour> nb((size_t)n_nb);
-    for (int j = 0; j < n_nb; j++) {
-      std::memcpy(&nb[j].cam, cam2 + 21 * (size_t)j, sizeof(cslam::CamRecord));
-      nb[j].keys = mk_keys(x2[j], y2[j], oct2[j], nullptr, N2[j]);
-      for (int i = pair_off[j]; i < pair_off[j + 1]; i++) nb[j].predicted.emplace_back(idx12[2 * i], idx12[2 * i + 1]);
-    }
-    return new cslam::NewMapPointBatch(device < 0 ? nullptr : &thread_context(device), c1, mk_keys(x1, y1, oct1, nullptr, N1), std::move(nb),
-                                       mk_tables(nlevels, sigma2_1, sf_1, sigma2_2, sf_2), ratio_factor);
-  } catch (const std::exception&) { return nullptr; }
-}
-void* ccmh_newpts_create_tri(int device, void* tri_batch, const int32_t* oct1, const float* cam1, const float* cam2, const float* F12, const float* exy,
-                             int nlevels, const float* sigma2_1, const float* sf_1, const float* sigma2_2, const float* sf_2, float ratio_factor) {
-  try {
-    if (!tri_batch || !cam1 || !cam2 || !F12 || !exy) return nullptr;
-    const cslam::TriangulationBatch& tb = *static_cast<cslam::TriangulationBatch*>(tri_batch);
-    const int n = tb.neighbours();
-    cslam::CamRecord c1; std::memcpy(&c1, cam1, sizeof c1);
-    std::vector<cslam::CamRecord> c2((size_t)n);
-    std::vector<cslam::NewMapPointBatch::Epipolar> ep((size_t)n);
-    for (int j = 0; j < n; j++) {
-      std::memcpy(&c2[j], cam2 + 21 * (size_t)j, sizeof(cslam::CamRecord));
-      std::memcpy(ep[j].F12, F12 + 9 * (size_t)j, 9 * sizeof(float));
-      ep[j].ex = exy[2 * j]; ep[j].ey = exy[2 * j + 1];
-    }
-    return new cslam::NewMapPointBatch(thread_context(device), tb, c1, c2, ep, mk_tables(nlevels, sigma2_1, sf_1, sigma2_2, sf_2), ratio_factor, oct1);
-  } catch (const std::exception&) { return nullptr; }
-}
-int ccmh_newpts_points(void* h, int j, int n, const int32_t* idx12, uint8_t* status, float* x3d) {
-  try {
-    if (!h || n < 0 || (n > 0 && (!idx12 || !status || !x3d))) return -1;
-    cslam::NewMapPointBatch::Pairs p((size_t)n);
-    for (int i = 0; i < n; i++) p[i] = {idx12[2 * i], idx12[2 * i + 1]};
-    std::vector<uint8_t> st; std::vector<float> x;
-    const int ok = static_cast<cslam::NewMapPointBatch*>(h)->points(j, p, st, x);
-    if (n > 0) { std::memcpy(status, st.data(), st.size()); std::memcpy(x3d, x.data(), x.size() * sizeof(float)); }
-    return ok;
-  } catch (const std::exception&) { return -1000; }
-}
-int ccmh_newpts_stats(void* h, int64_t* out3) {
-  if (!h || !out3) return -1;
-  const cslam::NewMapPointBatch& b = *static_cast<cslam::NewMapPointBatch*>(h);
-  out3[0] = b.predicted(); out3[1] = b.hits(); out3[2] = b.misses();
-  return 0;
-}
-void ccmh_newpts_destroy(void* h) { delete static_cast<cslam::NewMapPointBatch*>(h); }
-// the arguments of ccm_triangulate_pairs through the host's tri_pair on the calling thread (what points() runs for a miss; scripts/triangulate_profile.py times it)
-int ccmh_triangulate_pairs_host(const float* cam1, int S, const float* cam2, const int32_t* pair_off, const float* xy, const int32_t* oct, int nlevels,
-                                const float* sigma2_1, const float* sf_1, const float* sigma2_2, const float* sf_2, float ratio_factor, uint8_t* status,
-                                float* x3d, int32_t* n_accepted) {
-  if (S < 1 || nlevels < 1 || !cam1 || !cam2 || !pair_off || !sigma2_1 || !sf_1 || !sigma2_2 || !sf_2 || !n_accepted || pair_off[0] != 0) return -1;
-  for (int s = 0; s < S; s++) if (pair_off[s + 1] < pair_off[s]) return -1;
-  const int P = pair_off[S];
-  if (P > 0 && (!xy || !oct || !status || !x3d)) return -1;
-  for (int i = 0; i < 2 * P; i++) if (oct[i] < 0 || oct[i] >= nlevels) return -1;
-  TriCam c1; std::memcpy(&c1, cam1, sizeof c1);
-  for (int s = 0; s < S; s++) {
-    TriCam c2; std::memcpy(&c2, cam2 + 21 * (size_t)s, sizeof c2);
-    int32_t n = 0;
-    for (int i = pair_off[s]; i < pair_off[s + 1]; i++) {
-      status[i] = (uint8_t)tri_pair(c1, c2, xy[4 * i], xy[4 * i + 1], oct[2 * i], xy[4 * i + 2], xy[4 * i + 3], oct[2 * i + 1], sigma2_1, sf_1, sigma2_2, sf_2,
-                                    ratio_factor, x3d + 3 * (size_t)i);
-      n += status[i] == TRI_OK;
-    }
-    n_accepted[s] = n;
-  }
-  return 0;
-}
-
-// TwoViewInitializer through C, and twoview_math.h compiled for the host
-void* ccmh_twoview_create(int device, const float* K9, int N1, const float* keys1, float sigma) {
-  try {
-    if (!K9 || N1 < 0 || (N1 > 0 && !keys1)) return nullptr;
-    return new cslam::TwoViewInitializer(device < 0 ? nullptr : &thread_context(device), K9, std::vector<float>(keys1, keys1 + 2 * (size_t)N1), sigma);
-  } catch (const std::exception&) { return nullptr; }
-}
-int ccmh_twoview_find(void* h, int N2, const float* keys2, const int32_t* matches12, int n_sets, const int32_t* sets, float* scores3, int32_t* best2, float* H21,
-                      float* F21, uint8_t* inl_h, uint8_t* inl_f) {
-  if (!h || N2 < 0 || (N2 > 0 && !keys2) || !matches12 || n_sets < 1 || !sets || !scores3 || !best2 || !H21 || !F21 || !inl_h || !inl_f) return -1;
-  cslam::TwoViewInitializer& tv = *static_cast<cslam::TwoViewInitializer*>(h);
-  try {
-    // matches12 has one entry per keypoint of frame 1; the mirror knows how many that is from its own keys
-    const cslam::TwoViewInitializer::Models m = tv.FindModels(std::vector<float>(keys2, keys2 + 2 * (size_t)N2), std::vector<int>(matches12, matches12 + tv.keys1()),
-                                                              cslam::TwoViewInitializer::Sets(sets, sets + 8 * (size_t)n_sets));
-    scores3[0] = m.SH; scores3[1] = m.SF; scores3[2] = m.RH;
-    best2[0] = m.bestH; best2[1] = m.bestF;
-    std::memcpy(H21, m.H21, sizeof m.H21); std::memcpy(F21, m.F21, sizeof m.F21);
-    for (int i = 0; i < tv.matches(); i++) { inl_h[i] = m.vbMatchesInliersH[i]; inl_f[i] = m.vbMatchesInliersF[i]; }
-    return tv.matches();
-  } catch (const cslam::infrastructure_ex& e) {
-    return std::strncmp(e.what(), "ccm_", 4) == 0 ? -1000 : -1;
-  } catch (const std::exception&) { return -1000; }
-}
-int ccmh_twoview_check_rt(void* h, int n_hyp, const float* Rt, const uint8_t* inliers, float th2, int32_t* n_good, float* parallax, float* p3d, uint8_t* good,
-                          uint8_t* status) {
-  if (!h || n_hyp < 1 || n_hyp > 8 || !Rt || !inliers || !n_good || !parallax || !p3d || !good || !status) return -1;
-  cslam::TwoViewInitializer& tv = *static_cast<cslam::TwoViewInitializer*>(h);
-  try {
-    std::vector<cslam::TwoViewInitializer::Motion> hyp((size_t)n_hyp);
-    for (int q = 0; q < n_hyp; q++) { std::memcpy(hyp[q].R, Rt + 12 * (size_t)q, 9 * sizeof(float)); std::memcpy(hyp[q].t, Rt + 12 * (size_t)q + 9, 3 * sizeof(float)); }
-    const auto out = tv.CheckRTBatch(hyp, std::vector<bool>(inliers, inliers + tv.matches()), th2);
-    const size_t N1 = (size_t)tv.keys1(), N = (size_t)tv.matches();
-    for (int q = 0; q < n_hyp; q++) {
-      n_good[q] = out[q].nGood; parallax[q] = out[q].parallax;
-      std::memcpy(p3d + 3 * N1 * q, out[q].vP3D.data(), 3 * N1 * sizeof(float));
-      for (size_t i = 0; i < N1; i++) good[N1 * q + i] = out[q].vbGood[i];
-      std::memcpy(status + N * q, out[q].status.data(), N);
-    }
-    return 0;
-  } catch (const cslam::infrastructure_ex& e) {
-    return std::strncmp(e.what(), "ccm_", 4) == 0 ? -1000 : -1;
-  } catch (const std::exception&) { return -1000; }
-}
-void ccmh_twoview_destroy(void* h) { delete static_cast<cslam::TwoViewInitializer*>(h); }
-int ccmh_twoview_draw_sets(int N, int iterations, const int32_t* raw, int32_t* sets) {
-  if (N < 8 || iterations < 0 || (iterations > 0 && (!raw || !sets))) return -1;
-  size_t at = 0;
-  const cslam::TwoViewInitializer::Sets s = cslam::TwoViewInitializer::DrawSets(N, iterations, [&] { return (int)raw[at++]; });
-  std::memcpy(sets, s.data(), s.size() * sizeof(int32_t));
-  return 0;
-}
-int ccmh_twoview_ransac_eval_host(int N, const float* xy1, const float* xy2, const float* pn1, const float* pn2, const float* T1, const float* T2inv, const float* T2t,
-                                  float sigma, int H, const int32_t* sets, int model, float* scoreH, float* scoreF, float* H21, float* F21, uint32_t* maskH,
-                                  uint32_t* maskF) {
-  if (model < 0 || model > 2) return -1;
-  return cslam::twoview_ransac_host(N, xy1, xy2, pn1, pn2, T1, T2inv, T2t, sigma, H, sets, model, scoreH, scoreF, H21, F21, maskH, maskF);
-}
-int ccmh_twoview_check_rt_host(int n_hyp, const float* rec, const float* K9, int N, const float* xy1, const float* xy2, const uint32_t* inlier_mask, float th2,
-                               uint8_t* status, float* x3d, float* cos_parallax) {
-  return cslam::twoview_check_rt_host(n_hyp, rec, K9, N, xy1, xy2, inlier_mask, th2, status, x3d, cos_parallax);
-}
-void ccmh_twoview_normalize(const float* xy, int n, float* pn, float* T9) { tv_normalize(xy, n, pn, T9); }
-void ccmh_twoview_inv33(const float* S9, float* D9) { tv_inv33(S9, D9); }
-void ccmh_twoview_prepare_rt(const float* K9, const float* R9, const float* t3, float* rec27) {
-  TvMotion m;
-  tv_prepare_rt(K9, R9, t3, m);
-  std::memcpy(rec27, &m, sizeof m);
-}
-int ccmh_twoview_svd(int shape, const float* A, float* out) {
-  if (!A || !out) return -1;
-  if (shape == 0) tv_svd16x9_last_row(A, out);
-  else if (shape == 1) { std::memcpy(out, A, 72 * sizeof(float)); tv_svd8x9_vt(out); }
-  else if (shape == 2) tv_svd3x3(A, out, out + 3, out + 12);
-  else return -1;
-  return 0;
-}
-int ccmh_twoview_score_host(int model, int n_models, const float* M, int N, const float* xy1, const float* xy2, float sigma, float* score, uint32_t* mask) {
-  if (model < 0 || model > 1 || n_models < 1 || N < 1 || !M || !xy1 || !xy2 || !score || !mask) return -1;
-  const size_t words = ((size_t)N + 31) / 32;
-  for (int h = 0; h < n_models; h++) {
-    float inv[9] = {0};
-    if (model == 0) tv_inv33(M + 9 * (size_t)h, inv);
-    score[h] = tv_score(model == 0, M + 9 * (size_t)h, inv, N, xy1, xy2, sigma, mask + words * h);
-  }
-  return 0;
-}
-
-// pnp_math.h through C: the host evaluator of ccm_pnp_ransac_eval (its arguments without the context), compute_pose and Refine for any n, and the restated primitives
-int ccmh_pnp_compute_pose(int n, const double* pws, const double* us, const double* cam4, double* R9, double* t3, double* rep_errors4, int32_t* chosen) {
-  if (n < 4 || !pws || !us || !cam4 || !R9 || !t3) return -1;
-  std::vector<double> alphas(4 * (size_t)n), pcs(3 * (size_t)n), M(24 * (size_t)n), ut(144);
-  int N = 0;
-  pnp_compute_pose(n, pws, us, cam4, alphas.data(), pcs.data(), M.data(), ut.data(), R9, t3, rep_errors4, &N);
-  if (chosen) *chosen = N;
-  return 0;
-}
-int ccmh_pnp_ransac_eval_host(int K, const int32_t* pt_off, const float* P3Dw, const float* P2D, const float* max_err, const double* cam, int H, const int32_t* hyp_cand,
-                              const int32_t* hyp_idx, int32_t* n_inl, double* Rt, int32_t* mask_off, uint32_t* mask) {
-  return ccm_pnp::eval_host(K, pt_off, P3Dw, P2D, max_err, cam, H, hyp_cand, hyp_idx, n_inl, Rt, mask_off, mask);
-}
-int ccmh_pnp_check_inliers(int N, const float* P3Dw, const float* P2D, const float* max_err, const double* cam4, const double* Rt12, uint8_t* inliers, float* error2) {
-  if (N < 0 || !P3Dw || !P2D || !max_err || !cam4 || !Rt12) return -1;
-  int count = 0;
-  for (int i = 0; i < N; i++) {
-    const float e = pnp_error2(Rt12, Rt12 + 9, cam4, P3Dw + 3 * (size_t)i, P2D + 2 * (size_t)i);
-    const bool in = e < max_err[i];
-    if (error2) error2[i] = e;
-    if (inliers) inliers[i] = in;
-    count += in;
-  }
-  return count;
-}
-int ccmh_pnp_refine(int N, const float* P3Dw, const float* P2D, const float* max_err, const double* cam4, const uint8_t* best_inliers, double* Rt12, uint8_t* inliers) {
-  if (N < 4 || !P3Dw || !P2D || !max_err || !cam4 || !best_inliers || !Rt12) return -1;
-  std::vector<uint32_t> best(((size_t)N + 31) / 32, 0u), got;
-  int n = 0;
-  for (int i = 0; i < N; i++)
-    if (best_inliers[i]) { best[i >> 5] |= 1u << (i & 31); n++; }
-  if (n < 4) return -1;
-  const int count = ccm_pnp::refine_host(N, P3Dw, P2D, max_err, cam4, best, Rt12, got);
-  if (inliers)
-    for (int i = 0; i < N; i++) inliers[i] = got[i >> 5] >> (i & 31) & 1u;
-  return count;
-}
-int ccmh_pnp_matrices(int n, const double* pws, const double* us, const double* cam4, double* mtm144, double* pca9, double* cc9) {
-  if (n < 4 || !pws || !us || !cam4 || !mtm144 || !pca9 || !cc9) return -1;
-  std::vector<double> alphas(4 * (size_t)n), M(24 * (size_t)n);
-  double cws[4][3];
-  pnp_build_mtm(n, pws, us, cam4, cws, alphas.data(), M.data(), mtm144, pca9, cc9);
-  return 0;
-}
-int ccmh_pnp_primitive(int which, int rows, const double* A, const double* b, double* out) {
-  if (!A || !out) return -1;
-  switch (which) {
-    case 0: { double a[9]; std::memcpy(a, A, sizeof a); pnp_svd_ut<3>(a, out); std::memcpy(out + 3, a, sizeof a); return 0; }
-    case 1: { std::vector<double> a(A, A + 144); pnp_svd_ut<12>(a.data(), out); std::memcpy(out + 12, a.data(), 144 * sizeof(double)); return 0; }
-    case 2: pnp_svd_uv3(A, out, out + 3, out + 12); return 0;
-    case 3: pnp_invert3_svd(A, out); return 0;
-    case 4: if (!b) return -1; pnp_solve_svd<3>(A, b, out); return 0;
-    case 5: if (!b) return -1; pnp_solve_svd<4>(A, b, out); return 0;
-    case 6: if (!b) return -1; pnp_solve_svd<5>(A, b, out); return 0;
-    case 7: if (rows < 1) return -1; pnp_mul_transposed<3>(A, rows, out); return 0;
-    case 8: if (rows < 1) return -1; pnp_mul_transposed<12>(A, rows, out); return 0;
-    case 9: { if (!b) return -1; double a[24], bb[6]; std::memcpy(a, A, sizeof a); std::memcpy(bb, b, sizeof bb); return pnp_qr_solve(a, bb, out) ? 1 : 0; }
-  }
-  return -1;
-}
-
-// Sim3MapCorrection through C
-static cslam::Sim3MapCorrection::Points mk_s3c_points(int n_pt, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const int32_t* obs_off,
-                                                      const int32_t* obs_kf, const int32_t* ref_kf, const int32_t* ref_level) {
-  cslam::Sim3MapCorrection::Points p;
-  if (n_pt < 0 || (n_pt > 0 && (!pos || !normal || !min_dist || !max_dist || !obs_off || !ref_kf || !ref_level))) throw cslam::infrastructure_ex("points");
-  const size_t n = (size_t)n_pt;
-  p.obs_off.assign(1, 0);
-  if (n) {
-    p.pos.assign(pos, pos + 3 * n); p.normal.assign(normal, normal + 3 * n); p.min_dist.assign(min_dist, min_dist + n); p.max_dist.assign(max_dist, max_dist + n);
-    p.obs_off.assign(obs_off, obs_off + n + 1); p.ref_kf.assign(ref_kf, ref_kf + n); p.ref_level.assign(ref_level, ref_level + n);
-    if (obs_off[n] < 0 || (obs_off[n] > 0 && !obs_kf)) throw cslam::infrastructure_ex("points");
-    p.obs_kf.assign(obs_kf, obs_kf + obs_off[n]);
-  }
-  return p;
-}
-void* ccmh_sim3corr_create_loop(int device, int n_kf, int n_obs_kf, const float* Tiw, const float* center, int cur, const float* Twc, const double* Scw,
-                                const int32_t* list_off, const int32_t* list_pt, const uint8_t* list_skip, int n_pt, const float* pos, const float* normal,
-                                const float* min_dist, const float* max_dist, const int32_t* obs_off, const int32_t* obs_kf, const int32_t* ref_kf, const int32_t* ref_level,
-                                const float* scale_factors, int n_levels) {
-  try {
-    if (n_kf < 1 || n_obs_kf < n_kf || !Tiw || !center || !Twc || !Scw || !list_off || n_levels < 1 || !scale_factors) return nullptr;
-    const int ne = list_off[n_kf];
-    if (ne < 0 || (ne > 0 && (!list_pt || !list_skip))) return nullptr;
-    return new cslam::Sim3MapCorrection(device < 0 ? nullptr : &thread_context(device), n_kf, std::vector<float>(Tiw, Tiw + 12 * (size_t)n_kf),
-                                        std::vector<float>(center, center + 3 * (size_t)n_obs_kf), cur, Twc, Scw, std::vector<int32_t>(list_off, list_off + n_kf + 1),
-                                        std::vector<int32_t>(list_pt, list_pt + ne), std::vector<uint8_t>(list_skip, list_skip + ne),
-                                        mk_s3c_points(n_pt, pos, normal, min_dist, max_dist, obs_off, obs_kf, ref_kf, ref_level),
-                                        std::vector<float>(scale_factors, scale_factors + n_levels));
-  } catch (const std::exception&) { return nullptr; }
-}
-void* ccmh_sim3corr_create_epilogue(int device, int n_kf, int n_obs_kf, const float* center, const double* S_non, const double* S_cor, const int32_t* pt_kf, int n_pt,
-                                    const float* pos, const float* normal, const float* min_dist, const float* max_dist, const int32_t* obs_off, const int32_t* obs_kf,
-                                    const int32_t* ref_kf, const int32_t* ref_level, const float* scale_factors, int n_levels) {
-  try {
-    if (n_kf < 1 || n_obs_kf < n_kf || !center || !S_non || !S_cor || n_pt < 0 || (n_pt > 0 && !pt_kf) || n_levels < 1 || !scale_factors) return nullptr;
-    return new cslam::Sim3MapCorrection(device < 0 ? nullptr : &thread_context(device), n_kf, std::vector<float>(center, center + 3 * (size_t)n_obs_kf),
-                                        std::vector<double>(S_non, S_non + 8 * (size_t)n_kf), std::vector<double>(S_cor, S_cor + 8 * (size_t)n_kf),
-                                        std::vector<int32_t>(pt_kf, pt_kf + n_pt), mk_s3c_points(n_pt, pos, normal, min_dist, max_dist, obs_off, obs_kf, ref_kf, ref_level),
-                                        std::vector<float>(scale_factors, scale_factors + n_levels));
-  } catch (const std::exception&) { return nullptr; }
-}
-int ccmh_sim3corr_results(void* h, float* pos, float* normal, float* min_dist, float* max_dist, int32_t* tag, float* Tiw_new, float* center_new, double* S_non,
-                          double* S_cor) {
-  if (!h) return -1;
-  const cslam::Sim3MapCorrection& c = *static_cast<cslam::Sim3MapCorrection*>(h);
-  auto out = [](auto* dst, const auto& v) { if (dst && !v.empty()) std::memcpy(dst, v.data(), v.size() * sizeof(v[0])); };
-  out(pos, c.points().pos); out(normal, c.points().normal); out(min_dist, c.points().min_dist); out(max_dist, c.points().max_dist);
-  out(tag, c.tag()); out(Tiw_new, c.poses()); out(center_new, c.centers()); out(S_non, c.nonCorrectedSim3()); out(S_cor, c.correctedSim3());
-  return 0;
-}
-void ccmh_sim3corr_destroy(void* h) { delete static_cast<cslam::Sim3MapCorrection*>(h); }
-int ccmh_sim3_correct_map_host(int n_kf, const float* Tiw, int cur, const float* Twc, const double* Scw, double* S_non, double* S_cor, int n_obs_kf, const float* kf_center,
-                               const int32_t* kf_rank, int n_pt, const float* pos, const int32_t* owner, const int32_t* owner_rank, const int32_t* obs_off,
-                               const int32_t* obs_kf, const int32_t* ref_kf, const int32_t* ref_level, const float* scale_factors, int n_levels, float* pos_out,
-                               float* normal, float* min_dist, float* max_dist, float* Tiw_new, float* center_new) {
-  return cslam::sim3_correct_map_host(n_kf, Tiw, cur, Twc, Scw, S_non, S_cor, n_obs_kf, kf_center, kf_rank, n_pt, pos, owner, owner_rank, obs_off, obs_kf, ref_kf, ref_level,
-                                      scale_factors, n_levels, pos_out, normal, min_dist, max_dist, Tiw_new, center_new);
-}
-
-// GbaMapUpdate through C
-void* ccmh_gbaupd_create(int device, int n_kf, int n_origins, const int32_t* origins, const int32_t* child_off, const int32_t* child_kf, const int32_t* kf_cam, const float* Tcw,
-                         const float* Twc, int n_pt, const float* pos, const int32_t* vert, const int32_t* ref_kf, int n_cam, const double* cam_qt, int n_lm,
-                         const double* pt_xyz) {
-  try {
-    if (n_kf < 1 || n_origins < 1 || !origins || !child_off || !kf_cam || !Tcw || !Twc || n_pt < 0 || (n_pt > 0 && (!pos || !vert || !ref_kf)) || n_cam < 1 || !cam_qt ||
-        n_lm < 0 || (n_lm > 0 && !pt_xyz))
-      return nullptr;
-    const int ne = child_off[n_kf];
-    if (ne < 0 || (ne > 0 && !child_kf)) return nullptr;
-    cslam::GbaMapUpdate::Graph g;
-    g.origins.assign(origins, origins + n_origins); g.child_off.assign(child_off, child_off + n_kf + 1); g.child_kf.assign(child_kf, child_kf + ne);
-    g.kf_cam.assign(kf_cam, kf_cam + n_kf); g.Tcw.assign(Tcw, Tcw + 12 * (size_t)n_kf); g.Twc.assign(Twc, Twc + 12 * (size_t)n_kf);
-    cslam::GbaMapUpdate::Points p;
-    if (n_pt) { p.pos.assign(pos, pos + 3 * (size_t)n_pt); p.vert.assign(vert, vert + n_pt); p.ref_kf.assign(ref_kf, ref_kf + n_pt); }
-    return new cslam::GbaMapUpdate(device < 0 ? nullptr : &thread_context(device), std::move(g), std::move(p), std::vector<double>(cam_qt, cam_qt + 7 * (size_t)n_cam),
-                                   n_lm ? std::vector<double>(pt_xyz, pt_xyz + 3 * (size_t)n_lm) : std::vector<double>());
-  } catch (const std::exception&) { return nullptr; }
-}
-int ccmh_gbaupd_sizes(void* h, int64_t* out4) {
-  if (!h || !out4) return -1;
-  const cslam::GbaMapUpdate& u = *static_cast<cslam::GbaMapUpdate*>(h);
-  out4[0] = (int64_t)u.order().size(); out4[1] = u.reachedTwice(); out4[2] = u.staleReferences(); out4[3] = (int64_t)u.status().size();
-  return 0;
-}
-int ccmh_gbaupd_results(void* h, int32_t* order, int32_t* parent, float* T_new, float* Twc_new, float* pos, uint8_t* status) {
-  if (!h) return -1;
-  const cslam::GbaMapUpdate& u = *static_cast<cslam::GbaMapUpdate*>(h);
-  auto out = [](auto* dst, const auto& v) { if (dst && !v.empty()) std::memcpy(dst, v.data(), v.size() * sizeof(v[0])); };
-  out(order, u.order()); out(parent, u.parents()); out(T_new, u.poses()); out(Twc_new, u.inverses()); out(pos, u.positions()); out(status, u.status());
-  return 0;
-}
-void ccmh_gbaupd_destroy(void* h) { delete static_cast<cslam::GbaMapUpdate*>(h); }
-int ccmh_gba_apply_map_host(int n_kf, const int32_t* kf_parent, const int32_t* kf_cam, const float* Tcw_old, const float* Twc_old, int n_pt, const float* pos,
-                            const int32_t* pt_vert, const int32_t* pt_ref, int n_cam, const double* cam_qt, int n_lm, const double* pt_xyz, float* T_new, float* Twc_new,
-                            float* pos_out, uint8_t* pt_status) {
-  return cslam::gba_apply_map_host(n_kf, kf_parent, kf_cam, Tcw_old, Twc_old, n_pt, pos, pt_vert, pt_ref, n_cam, cam_qt, n_lm, pt_xyz, T_new, Twc_new, pos_out, pt_status);
-}
-
-// CovisibilityBatch through C
-void* ccmh_covis_create(int device, int n_kf, int n_all, const int32_t* order_key, const int32_t* list_off, const int32_t* list_pt, const uint8_t* list_skip, int n_pt,
-                        const int32_t* obs_off, const int32_t* obs_kf, int th) {
-  try {
-    if (n_kf < 1 || n_all < n_kf || n_pt < 0 || !order_key || !list_off || (n_pt > 0 && !obs_off)) return nullptr;
-    const int ne = list_off[n_kf], no = n_pt ? obs_off[n_pt] : 0;
-    if (ne < 0 || no < 0 || (ne > 0 && (!list_pt || !list_skip)) || (no > 0 && !obs_kf)) return nullptr;
-    return new cslam::CovisibilityBatch(device < 0 ? nullptr : &thread_context(device), n_kf, std::vector<int32_t>(order_key, order_key + n_all),
-                                        std::vector<int32_t>(list_off, list_off + n_kf + 1), std::vector<int32_t>(list_pt, list_pt + ne),
-                                        std::vector<uint8_t>(list_skip, list_skip + ne), n_pt ? std::vector<int32_t>(obs_off, obs_off + n_pt + 1) : std::vector<int32_t>(1, 0),
-                                        std::vector<int32_t>(obs_kf, obs_kf + no), th);
-  } catch (const std::exception&) { return nullptr; }
-}
-int ccmh_covis_sizes(void* h, int64_t* out5) {
-  if (!h || !out5) return -1;
-  const cslam::CovisibilityBatch& c = *static_cast<cslam::CovisibilityBatch*>(h);
-  out5[0] = c.size(); out5[1] = (int64_t)c.rowKf().size(); out5[2] = (int64_t)c.weightKf().size(); out5[3] = (int64_t)c.orderedKf().size(); out5[4] = (int64_t)c.outsideCalls().size();
-  return 0;
-}
-int ccmh_covis_results(void* h, int32_t* flags, int32_t* row_off, int32_t* col, int32_t* count, int32_t* fw_off, int32_t* fw_col, int32_t* fw_w, int32_t* ord_off,
-                       int32_t* ord_kf, int32_t* ord_w, int32_t* outside) {
-  if (!h) return -1;
-  const cslam::CovisibilityBatch& c = *static_cast<cslam::CovisibilityBatch*>(h);
-  auto out = [](int32_t* dst, const std::vector<int32_t>& v) { if (dst && !v.empty()) std::memcpy(dst, v.data(), v.size() * 4); };
-  out(flags, c.allFlags()); out(row_off, c.rowOff()); out(col, c.rowKf()); out(count, c.rowCount()); out(fw_off, c.weightOff()); out(fw_col, c.weightKf());
-  out(fw_w, c.weight()); out(ord_off, c.orderedOff()); out(ord_kf, c.orderedKf()); out(ord_w, c.orderedWeight());
-  if (outside) for (size_t k = 0; k < c.outsideCalls().size(); k++) { outside[3 * k] = c.outsideCalls()[k].target; outside[3 * k + 1] = c.outsideCalls()[k].source; outside[3 * k + 2] = c.outsideCalls()[k].weight; }
-  return 0;
-}
-static int covis_view(const std::vector<int32_t>& v, int32_t* out, int cap) {
-  if (out) for (int k = 0; k < (int)v.size() && k < cap; k++) out[k] = v[k];
-  return (int)v.size();
-}
-int ccmh_covis_best(void* h, int i, int N, int32_t* out, int cap) {
-  if (!h || i < 0 || i >= static_cast<cslam::CovisibilityBatch*>(h)->size()) return -1;
-  return covis_view(static_cast<cslam::CovisibilityBatch*>(h)->GetBestCovisibilityKeyFrames(i, N), out, cap);
-}
-int ccmh_covis_by_weight(void* h, int i, int w, int32_t* out, int cap) {
-  if (!h || i < 0 || i >= static_cast<cslam::CovisibilityBatch*>(h)->size()) return -1;
-  return covis_view(static_cast<cslam::CovisibilityBatch*>(h)->GetCovisiblesByWeight(i, w), out, cap);
-}
-void ccmh_covis_destroy(void* h) { delete static_cast<cslam::CovisibilityBatch*>(h); }
-int ccmh_covis_update_host(int n_kf, int n_all, const int32_t* order_key, const int32_t* list_off, const int32_t* list_pt, const uint8_t* list_skip, int n_pt,
-                           const int32_t* obs_off, const int32_t* obs_kf, int th, int cap, int32_t* row_off, int32_t* col, int32_t* count, int32_t* fw_off, int32_t* fw_col,
-                           int32_t* fw_w, int32_t* ord_off, int32_t* ord_kf, int32_t* ord_w, int32_t* flags, int32_t* needed) {
-  return cslam::covis_update_host(n_kf, n_all, order_key, list_off, list_pt, list_skip, n_pt, obs_off, obs_kf, th, cap, row_off, col, count, fw_off, fw_col, fw_w, ord_off,
-                                  ord_kf, ord_w, flags, needed);
-}
-
-// KeyFrameCullingBatch through C
-void* ccmh_kfcull_create(int device, int n_cand, int n_all, const uint8_t* cand_flags, const int32_t* list_off, const int32_t* list_pt, const uint8_t* list_level, int n_pt,
-                         const int32_t* pt_nobs, const uint8_t* pt_bad, const int32_t* obs_off, const int32_t* obs_kf, const uint8_t* obs_level, const uint8_t* obs_bad,
-                         int th_obs, double thres, int n_levels) {
-  try {
-    if (n_cand < 1 || n_pt < 0 || !cand_flags || !list_off || (n_pt > 0 && (!obs_off || !pt_nobs || !pt_bad))) return nullptr;
-    const int ne = list_off[n_cand], no = n_pt ? obs_off[n_pt] : 0;
-    if (ne < 0 || no < 0 || (ne > 0 && (!list_pt || !list_level)) || (no > 0 && (!obs_kf || !obs_level || !obs_bad))) return nullptr;
-    return new cslam::KeyFrameCullingBatch(device < 0 ? nullptr : &thread_context(device), n_all, std::vector<uint8_t>(cand_flags, cand_flags + n_cand),
-                                           std::vector<int32_t>(list_off, list_off + n_cand + 1), std::vector<int32_t>(list_pt, list_pt + ne),
-                                           std::vector<uint8_t>(list_level, list_level + ne), std::vector<int32_t>(pt_nobs, pt_nobs + n_pt),
-                                           std::vector<uint8_t>(pt_bad, pt_bad + n_pt), n_pt ? std::vector<int32_t>(obs_off, obs_off + n_pt + 1) : std::vector<int32_t>(1, 0),
-                                           std::vector<int32_t>(obs_kf, obs_kf + no), std::vector<uint8_t>(obs_level, obs_level + no),
-                                           std::vector<uint8_t>(obs_bad, obs_bad + no), thres, n_levels, th_obs);
-  } catch (const std::exception&) { return nullptr; }
-}
-int ccmh_kfcull_results(void* h, uint8_t* verdict, int32_t* n_mps, int32_t* n_red, uint8_t* pt_gone, int32_t* pt_nobs, int32_t* n_reeval) {
-  if (!h) return -1;
-  const cslam::KeyFrameCullingBatch& c = *static_cast<cslam::KeyFrameCullingBatch*>(h);
-  if (verdict) for (int k = 0; k < c.size(); k++) verdict[k] = (uint8_t)c.verdict(k);
-  if (n_mps && c.size()) std::memcpy(n_mps, c.nMPs().data(), (size_t)c.size() * 4);
-  if (n_red && c.size()) std::memcpy(n_red, c.nRedundant().data(), (size_t)c.size() * 4);
-  if (pt_gone && !c.gone().empty()) std::memcpy(pt_gone, c.gone().data(), c.gone().size());
-  if (pt_nobs && !c.observations().empty()) std::memcpy(pt_nobs, c.observations().data(), c.observations().size() * 4);
-  if (n_reeval) *n_reeval = c.reevaluated();
-  return 0;
-}
-static int kfcull_view(const std::vector<int32_t>& v, int32_t* out, int cap) {
-  if (out) for (int k = 0; k < (int)v.size() && k < cap; k++) out[k] = v[k];
-  return (int)v.size();
-}
-int ccmh_kfcull_culled(void* h, int32_t* out, int cap) { return h ? kfcull_view(static_cast<cslam::KeyFrameCullingBatch*>(h)->culled(), out, cap) : -1; }
-int ccmh_kfcull_points_gone(void* h, int32_t* out, int cap) { return h ? kfcull_view(static_cast<cslam::KeyFrameCullingBatch*>(h)->pointsGone(), out, cap) : -1; }
-void ccmh_kfcull_destroy(void* h) { delete static_cast<cslam::KeyFrameCullingBatch*>(h); }
-int ccmh_kfcull_walk_host(int n_cand, int n_all, const uint8_t* cand_flags, const int32_t* list_off, const int32_t* list_pt, const uint8_t* list_level, int n_pt,
-                          const int32_t* pt_nobs, const uint8_t* pt_bad, const int32_t* obs_off, const int32_t* obs_kf, const uint8_t* obs_level, const uint8_t* obs_bad,
-                          int th_obs, double thres, int n_levels, uint8_t* verdict, int32_t* n_mps, int32_t* n_red, uint8_t* pt_gone, int32_t* pt_nobs_out, int32_t* n_reeval) {
-  return cslam::kfcull_walk_host(n_cand, n_all, cand_flags, list_off, list_pt, list_level, n_pt, pt_nobs, pt_bad, obs_off, obs_kf, obs_level, obs_bad, th_obs, thres,
-                                 n_levels, verdict, n_mps, n_red, pt_gone, pt_nobs_out, n_reeval);
-}
-int ccmh_kfcull_walk_mapcopy_model(int n_cand, int n_all, const uint8_t* cand_flags, const int32_t* list_off, const int32_t* list_pt, const uint8_t* list_level, int n_pt,
-                                   const int32_t* pt_nobs, const uint8_t* pt_bad, const int32_t* obs_off, const int32_t* obs_kf, const uint8_t* obs_level,
-                                   const uint8_t* obs_bad, int th_obs, double thres, int n_levels, uint8_t* verdict) {
-  return cslam::kfcull_walk_mapcopy_model(n_cand, n_all, cand_flags, list_off, list_pt, list_level, n_pt, pt_nobs, pt_bad, obs_off, obs_kf, obs_level, obs_bad, th_obs,
-                                          thres, n_levels, verdict);
-}
-
-// SearchAndFuseBatch through C, and fuse_math.h compiled for the host
-void* ccmh_fuse_sim3_create(int device, int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
-                            const int32_t* cell_off, const int32_t* cell_idx, const float* Scw, int nlevels, const float* scale_factors, float logScaleFactor, float th,
-                            int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc) {
-  try {
-    cslam::SearchAndFuseBatch::KeyFrames kf;
-    kf.K = K; kf.rec = kf_rec; kf.feat_off = feat_off; kf.feat_xy = feat_xy; kf.feat_octave = feat_octave; kf.feat_desc = feat_desc; kf.cell_off = cell_off;
-    kf.cell_idx = cell_idx; kf.Scw = Scw;
-    cslam::SearchAndFuseBatch::Points pt;
-    pt.P = P; pt.pos = pos; pt.normal = normal; pt.min_dist = min_dist; pt.max_dist = max_dist; pt.desc = pt_desc;
-    return new cslam::SearchAndFuseBatch(device < 0 ? nullptr : &thread_context(device), kf, pt, nlevels, scale_factors, logScaleFactor, th);
-  } catch (const std::exception&) { return nullptr; }
-}
-int ccmh_fuse_sim3_table(void* h, uint32_t* table, int32_t* n_valid, int32_t* n_hit) {
-  if (!h) return -1;
-  const cslam::SearchAndFuseBatch& b = *static_cast<cslam::SearchAndFuseBatch*>(h);
-  if (table && !b.table().empty()) std::memcpy(table, b.table().data(), b.table().size() * 4);
-  if (n_valid && b.keyframes()) std::memcpy(n_valid, b.nValid().data(), (size_t)b.keyframes() * 4);
-  if (n_hit && b.keyframes()) std::memcpy(n_hit, b.nHit().data(), (size_t)b.keyframes() * 4);
-  return 0;
-}
-int ccmh_fuse_sim3_resolve(void* h, int k, const uint8_t* skip_now, const uint8_t* desc_now, int n_pts, int32_t* best_idx, int32_t* best_dist) {
-  if (!h) return -1000;
-  try {
-    std::vector<int32_t> bi, bd;
-    const int n = static_cast<cslam::SearchAndFuseBatch*>(h)->resolve(k, skip_now, desc_now, bi, bd);
-    if ((int)bi.size() != n_pts) return -1001;
-    if (n_pts) { std::memcpy(best_idx, bi.data(), bi.size() * 4); std::memcpy(best_dist, bd.data(), bd.size() * 4); }
-    return n;
-  } catch (const std::exception&) { return -1000; }
-}
-long long ccmh_fuse_sim3_n_reeval(void* h) { return h ? static_cast<cslam::SearchAndFuseBatch*>(h)->n_reeval() : -1; }
-void ccmh_fuse_sim3_destroy(void* h) { delete static_cast<cslam::SearchAndFuseBatch*>(h); }
-int ccmh_fuse_sim3_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
-                             const int32_t* cell_off, const int32_t* cell_idx, const float* Scw, int nlevels, const float* scale_factors, float logScaleFactor, float th,
-                             int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc, uint32_t* table,
-                             int32_t* n_valid, int32_t* n_hit, float* uv, int32_t* n_cand) {
-  return cslam::fuse_sim3_eval_host(K, kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off, cell_idx, Scw, nlevels, scale_factors, logScaleFactor, th, P, pos, normal,
-                                    min_dist, max_dist, pt_desc, table, n_valid, n_hit, uv, n_cand);
-}
-void ccmh_fuse_sim3_decompose(const float* Scw12, float* pose15) { fsm_decompose_scw(Scw12, pose15); }
-
-// SearchInNeighborsBatch through C, and fuse_math.h compiled for the host
-void* ccmh_fuse_pose_create(int device, int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
-                            const int32_t* cell_off, const int32_t* cell_idx, const float* pose, int nlevels, const float* scale_factors, const float* inv_level_sigma2,
-                            float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist,
-                            const uint8_t* pt_desc, int n_calls, const int32_t* target, int current, int n_current) {
-  try {
-    cslam::SearchInNeighborsBatch::KeyFrames kf;
-    kf.K = K; kf.rec = kf_rec; kf.feat_off = feat_off; kf.feat_xy = feat_xy; kf.feat_octave = feat_octave; kf.feat_desc = feat_desc; kf.cell_off = cell_off;
-    kf.cell_idx = cell_idx; kf.pose = pose;
-    cslam::SearchInNeighborsBatch::Points pt;
-    pt.P = P; pt.pos = pos; pt.normal = normal; pt.min_dist = min_dist; pt.max_dist = max_dist; pt.desc = pt_desc;
-    return new cslam::SearchInNeighborsBatch(device < 0 ? nullptr : &thread_context(device), kf, n_calls, target, current, pt, n_current, nlevels, scale_factors,
-                                             inv_level_sigma2, logScaleFactor, th);
-  } catch (const std::exception&) { return nullptr; }
-}
-int ccmh_fuse_pose_table(void* h, uint32_t* table, int32_t* n_valid, int32_t* n_hit) {
-  if (!h) return -1;
-  const cslam::SearchInNeighborsBatch& b = *static_cast<cslam::SearchInNeighborsBatch*>(h);
-  if (table && !b.table().empty()) std::memcpy(table, b.table().data(), b.table().size() * 4);
-  if (n_valid && !b.nValid().empty()) std::memcpy(n_valid, b.nValid().data(), b.nValid().size() * 4);
-  if (n_hit && !b.nHit().empty()) std::memcpy(n_hit, b.nHit().data(), b.nHit().size() * 4);
-  return 0;
-}
-static int fuse_pose_copy_out(int n, int n_pts, const std::vector<int32_t>& bi, const std::vector<int32_t>& bd, int32_t* best_idx, int32_t* best_dist) {
-  if ((int)bi.size() != n_pts) return -1001;
-  if (n_pts) { std::memcpy(best_idx, bi.data(), bi.size() * 4); std::memcpy(best_dist, bd.data(), bd.size() * 4); }
-  return n;
-}
-int ccmh_fuse_pose_resolve(void* h, int c, const uint8_t* skip_now, const uint8_t* desc_now, int n_pts, int32_t* best_idx, int32_t* best_dist) {
-  if (!h) return -1000;
-  try {
-    std::vector<int32_t> bi, bd;
-    const int n = static_cast<cslam::SearchInNeighborsBatch*>(h)->resolve(c, skip_now, desc_now, bi, bd);
-    return fuse_pose_copy_out(n, n_pts, bi, bd, best_idx, best_dist);
-  } catch (const std::exception&) { return -1000; }
-}
-int ccmh_fuse_pose_resolve_current(void* h, int n, const int32_t* slot, const uint8_t* skip_now, const uint8_t* desc_now, const float* pos, const float* normal,
-                                   const float* min_dist, const float* max_dist, const uint8_t* desc, int32_t* best_idx, int32_t* best_dist) {
-  if (!h) return -1000;
-  try {
-    cslam::SearchInNeighborsBatch::Points fresh;
-    fresh.P = n; fresh.pos = pos; fresh.normal = normal; fresh.min_dist = min_dist; fresh.max_dist = max_dist; fresh.desc = desc;
-    std::vector<int32_t> bi, bd;
-    const int nf = static_cast<cslam::SearchInNeighborsBatch*>(h)->resolve_current(n, slot, skip_now, desc_now, fresh, bi, bd);
-    return fuse_pose_copy_out(nf, n, bi, bd, best_idx, best_dist);
-  } catch (const std::exception&) { return -1000; }
-}
-long long ccmh_fuse_pose_n_reeval(void* h) { return h ? static_cast<cslam::SearchInNeighborsBatch*>(h)->n_reeval() : -1; }
-long long ccmh_fuse_pose_n_unpredicted(void* h) { return h ? static_cast<cslam::SearchInNeighborsBatch*>(h)->n_unpredicted() : -1; }
-void ccmh_fuse_pose_destroy(void* h) { delete static_cast<cslam::SearchInNeighborsBatch*>(h); }
-int ccmh_fuse_pose_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
-                             const int32_t* cell_off, const int32_t* cell_idx, const float* pose, int nlevels, const float* scale_factors, const float* inv_level_sigma2,
-                             float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist,
-                             const uint8_t* pt_desc, int J, const int32_t* job_kf, const int32_t* job_pt0, const int32_t* job_n, uint32_t* table, int32_t* n_valid,
-                             int32_t* n_hit, float* uv, int32_t* n_cand) {
-  return cslam::fuse_pose_eval_host(K, kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off, cell_idx, pose, nlevels, scale_factors, inv_level_sigma2, logScaleFactor,
-                                    th, P, pos, normal, min_dist, max_dist, pt_desc, J, job_kf, job_pt0, job_n, table, n_valid, n_hit, uv, n_cand);
-}
-
-// KeyFrameStore through C, and the batches built on it
-void* ccmh_kfstore_create(int device, int max_kf, int max_feat) {
-  try { return new cslam::KeyFrameStore(device < 0 ? nullptr : &thread_context(device), max_kf, max_feat); } catch (const std::exception&) { return nullptr; }
-}
-void ccmh_kfstore_destroy(void* h) { delete static_cast<cslam::KeyFrameStore*>(h); }
-int ccmh_kfstore_add(void* h, int device, int M, const int64_t* keys, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave,
-                     const uint8_t* feat_desc, const int32_t* cell_off, const int32_t* cell_idx) {
-  if (!h) return -1000;
-  try {
-    return static_cast<cslam::KeyFrameStore*>(h)->add(device < 0 ? nullptr : &thread_context(device), M, keys, kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off,
-                                                      cell_idx);
-  } catch (const std::exception&) { return -1000; }
-}
-int ccmh_kfstore_erase(void* h, int device, int64_t key) {
-  if (!h) return -1000;
-  try { static_cast<cslam::KeyFrameStore*>(h)->erase(device < 0 ? nullptr : &thread_context(device), key); return 0; } catch (const std::exception&) { return -1000; }
-}
-int ccmh_kfstore_clear(void* h, int device) {
-  if (!h) return -1000;
-  try { static_cast<cslam::KeyFrameStore*>(h)->clear(device < 0 ? nullptr : &thread_context(device)); return 0; } catch (const std::exception&) { return -1000; }
-}
-int ccmh_kfstore_count(void* h, int* live, int* free_slots) {
-  if (!h) return -1000;
-  const cslam::KeyFrameStore& s = *static_cast<cslam::KeyFrameStore*>(h);
-  if (live) *live = s.live();
-  if (free_slots) *free_slots = s.free_slots();
-  return 0;
-}
-void* ccmh_kfstore_handle(void* h) { return h ? static_cast<cslam::KeyFrameStore*>(h)->handle() : nullptr; }
-int ccmh_kfstore_get(void* h, int device, int64_t key, int* n, int* n_in, int32_t* cell_off, int32_t* cell_idx) {
-  if (!h) return -1000;
-  try {
-    return static_cast<cslam::KeyFrameStore*>(h)->get(device < 0 ? nullptr : &thread_context(device), key, n, n_in, cell_off, cell_idx) ? 0 : -1;
-  } catch (const std::exception&) { return -1000; }
-}
-int ccmh_fuse_sim3_eval_resident_host(void* store, int K, const int64_t* keys, const float* Scw, int nlevels, const float* scale_factors, float logScaleFactor, float th,
-                                      int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc,
-                                      uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv) {
-  if (!store) return -1;
-  return cslam::fuse_sim3_eval_resident_host(*static_cast<cslam::KeyFrameStore*>(store), K, keys, Scw, nlevels, scale_factors, logScaleFactor, th, P, pos, normal, min_dist,
-                                             max_dist, pt_desc, table, n_valid, n_hit, uv);
-}
-int ccmh_fuse_pose_eval_resident_host(void* store, int K, const int64_t* keys, const float* pose, int nlevels, const float* scale_factors, const float* inv_level_sigma2,
-                                      float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist,
-                                      const uint8_t* pt_desc, int J, const int32_t* job_kf, const int32_t* job_pt0, const int32_t* job_n, uint32_t* table,
-                                      int32_t* n_valid, int32_t* n_hit, float* uv) {
-  if (!store) return -1;
-  return cslam::fuse_pose_eval_resident_host(*static_cast<cslam::KeyFrameStore*>(store), K, keys, pose, nlevels, scale_factors, inv_level_sigma2, logScaleFactor, th, P, pos,
-                                             normal, min_dist, max_dist, pt_desc, J, job_kf, job_pt0, job_n, table, n_valid, n_hit, uv);
-}
-void* ccmh_fuse_sim3_create_resident(void* store, int device, int K, const int64_t* keys, const float* Scw, int nlevels, const float* scale_factors, float logScaleFactor,
-                                     float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* pt_desc) {
-  if (!store) return nullptr;
-  try {
-    cslam::SearchAndFuseBatch::Points pt;
-    pt.P = P; pt.pos = pos; pt.normal = normal; pt.min_dist = min_dist; pt.max_dist = max_dist; pt.desc = pt_desc;
-    return new cslam::SearchAndFuseBatch(*static_cast<cslam::KeyFrameStore*>(store), device < 0 ? nullptr : &thread_context(device), K, keys, Scw, pt, nlevels,
-                                         scale_factors, logScaleFactor, th);
-  } catch (const std::exception&) { return nullptr; }
-}
-void* ccmh_fuse_pose_create_resident(void* store, int device, int K, const int64_t* keys, const float* pose, int nlevels, const float* scale_factors,
-                                     const float* inv_level_sigma2, float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist,
-                                     const float* max_dist, const uint8_t* pt_desc, int n_calls, const int32_t* target, int current, int n_current) {
-  if (!store) return nullptr;
-  try {
-    cslam::SearchInNeighborsBatch::Points pt;
-    pt.P = P; pt.pos = pos; pt.normal = normal; pt.min_dist = min_dist; pt.max_dist = max_dist; pt.desc = pt_desc;
-    return new cslam::SearchInNeighborsBatch(*static_cast<cslam::KeyFrameStore*>(store), device < 0 ? nullptr : &thread_context(device), K, keys, pose, n_calls, target,
-                                             current, pt, n_current, nlevels, scale_factors, inv_level_sigma2, logScaleFactor, th);
-  } catch (const std::exception&) { return nullptr; }
-}
-
-// the store's feature vectors and ComputeSim3's SearchByBoW for all candidates through C
-int ccmh_kfstore_set_featvec(void* h, int device, int64_t key, int nn, const int32_t* node, const int32_t* off, const int32_t* idx, const float* angle) {
-  if (!h) return -1000;
-  try {
-    return static_cast<cslam::KeyFrameStore*>(h)->set_featvec(device < 0 ? nullptr : &thread_context(device), key, cslam::FeatureVectorView{nn, node, off, idx}, angle);
-  } catch (const std::exception&) { return -1000; }
-}
-int ccmh_kfstore_ingest(void* h, int device, void* voc, int levelsup, int M, const int64_t* keys, const float* kf_rec, const int32_t* feat_off, const float* feat_xy,
-                        const uint8_t* feat_octave, const uint8_t* feat_desc, const float* angle, int32_t* bow_n, int32_t* bow_word, double* bow_value, int32_t* fv_nn,
-                        int32_t* fv_node, int32_t* fv_off, int32_t* fv_idx, int32_t* feat_word, int32_t* feat_node) {
-  if (!h || device < 0) return -1000;
-  try {
-    return static_cast<cslam::KeyFrameStore*>(h)->ingest_flat(&thread_context(device), static_cast<const ccm_vocab*>(voc), nullptr, levelsup, M, keys, kf_rec, feat_off,
-                                                              feat_xy, feat_octave, feat_desc, angle, bow_n, bow_word, bow_value, fv_nn, fv_node, fv_off, fv_idx, feat_word,
-                                                              feat_node);
-  } catch (const std::exception&) { return -1000; }
-}
-int ccmh_kfstore_shadow_equal(void* a, void* b, int64_t key) {
-  if (!a || !b) return -1000;
-  const std::shared_ptr<const cslam::KfShadow> x = static_cast<cslam::KeyFrameStore*>(a)->shadow(key), y = static_cast<cslam::KeyFrameStore*>(b)->shadow(key);
-  if (!x || !y) return -1;
-  auto bits = [](const std::vector<float>& u, const std::vector<float>& v) { return u.size() == v.size() && (u.empty() || !std::memcmp(u.data(), v.data(), u.size() * 4)); };
-  return !std::memcmp(x->rec, y->rec, sizeof x->rec) && x->n == y->n && x->n_in == y->n_in && bits(x->xy, y->xy) && x->oct == y->oct && x->desc == y->desc &&
-         x->cell_off == y->cell_off && x->cell_idx == y->cell_idx && x->has_fv == y->has_fv && x->fv_node == y->fv_node && x->fv_off == y->fv_off &&
-         x->fv_idx == y->fv_idx && bits(x->angle, y->angle);
-}
-int ccmh_kfstore_ingest_host(void* h, int n_nodes, int L, const int32_t* child_off, const int32_t* child_id, const uint8_t* node_desc, const int32_t* word_id,
-                             const double* weight, int levelsup, int M, const int64_t* keys, const float* kf_rec, const int32_t* feat_off, const float* feat_xy,
-                             const uint8_t* feat_octave, const uint8_t* feat_desc, const float* angle, int32_t* bow_n, int32_t* bow_word, double* bow_value,
-                             int32_t* fv_nn, int32_t* fv_node, int32_t* fv_off, int32_t* fv_idx, int32_t* feat_word, int32_t* feat_node) {
-  if (!h) return -1000;
-  cslam::KeyFrameStore& st = *static_cast<cslam::KeyFrameStore*>(h);
-  if (!st.host_only()) return -1000;
-  const bool no_tree = n_nodes <= 0 || !child_off || !node_desc || !word_id || !weight || (child_off[n_nodes] > 0 && !child_id);
-  const ::kfi_tree tree = {n_nodes, L, child_off, child_id, node_desc, word_id, weight};
-  try {
-    return st.ingest_flat(nullptr, nullptr, no_tree ? nullptr : &tree, levelsup, M, keys, kf_rec, feat_off, feat_xy, feat_octave, feat_desc, angle, bow_n, bow_word, bow_value,
-                          fv_nn, fv_node, fv_off, fv_idx, feat_word, feat_node);
-  } catch (const std::exception&) { return -1000; }
-}
-int ccmh_bow_pair_eval_resident_host(void* store, int J, const int64_t* key1, const int64_t* key2, const int32_t* live1_off, const uint8_t* live1, const int32_t* live2_off,
-                                     const uint8_t* live2, uint64_t* table, int32_t* n_query, int32_t* n_dist) {
-  if (!store) return -1;
-  return cslam::bow_pair_eval_resident_host(*static_cast<cslam::KeyFrameStore*>(store), J, key1, key2, live1_off, live1, live2_off, live2, table, n_query, n_dist);
-}
-void* ccmh_bow_batch_create(void* store, int device, int64_t key1, int C, const int64_t* keys2, const uint8_t* live1, const int32_t* live2_off, const uint8_t* live2,
-                            float nnratio, int check_orientation) {
-  if (!store || C < 0 || (C > 0 && !live2_off)) return nullptr;
-  try {
-    std::vector<const uint8_t*> l2((size_t)C);
-    for (int j = 0; j < C; j++) l2[j] = live2 ? live2 + live2_off[j] : nullptr;
-    return new cslam::SearchByBoWBatch(*static_cast<cslam::KeyFrameStore*>(store), device < 0 ? nullptr : &thread_context(device), key1, C, keys2, live1, l2.data(), nnratio,
-                                       check_orientation != 0);
-  } catch (const std::exception&) { return nullptr; }
-}
-int ccmh_bow_batch_result(void* h, int j, int n_feat, int32_t* matches12) {
-  if (!h) return -1000;
-  const cslam::SearchByBoWBatch& b = *static_cast<cslam::SearchByBoWBatch*>(h);
-  if (j < 0 || j >= b.candidates()) return -1000;
-  if (n_feat != (int)b.matches12(j).size()) return -1001;
-  if (matches12 && n_feat) std::memcpy(matches12, b.matches12(j).data(), (size_t)n_feat * 4);
-  return b.nmatches(j);
-}
-int ccmh_bow_batch_table(void* h, uint64_t* table, int32_t* n_query, int32_t* n_dist) {
-  if (!h) return -1;
-  const cslam::SearchByBoWBatch& b = *static_cast<cslam::SearchByBoWBatch*>(h);
-  if (table && !b.table().empty()) std::memcpy(table, b.table().data(), b.table().size() * 8);
-  if (n_query && b.candidates()) std::memcpy(n_query, b.nQuery().data(), (size_t)b.candidates() * 4);
-  if (n_dist && b.candidates()) std::memcpy(n_dist, b.nDist().data(), (size_t)b.candidates() * 4);
-  return 0;
-}
-long long ccmh_bow_batch_n_reeval(void* h) { return h ? static_cast<cslam::SearchByBoWBatch*>(h)->reevaluated() : -1; }
-void ccmh_bow_batch_destroy(void* h) { delete static_cast<cslam::SearchByBoWBatch*>(h); }
-
-// CreateNewMapPoints' SearchForTriangulation for all neighbours through C
-int ccmh_tri_search_eval_resident_host(void* store, int J, const int64_t* key1, const int64_t* key2, const int32_t* has1_off, const uint8_t* has1, const int32_t* has2_off,
-                                       const uint8_t* has2, const float* job_epi, int nlevels, const float* scale_factors, const float* level_sigma2, uint32_t* table,
-                                       int32_t* n_query, int32_t* n_match, int32_t* n_dist) {
-  if (!store) return -1;
-  return cslam::tri_search_eval_resident_host(*static_cast<cslam::KeyFrameStore*>(store), J, key1, key2, has1_off, has1, has2_off, has2, job_epi, nlevels, scale_factors,
-                                              level_sigma2, table, n_query, n_match, n_dist);
-}
-void* ccmh_tri_search_create(void* store, int device, int64_t key1, int C, const int64_t* keys2, const uint8_t* has1, const int32_t* has2_off, const uint8_t* has2,
-                             const float* epi, const float* sigma2_2, const float* sf2, int nlevels, int check_orientation) {
-  if (!store || C < 0 || (C > 0 && (!has2_off || !epi))) return nullptr;
-  try {
-    std::vector<const uint8_t*> h2((size_t)C);
-    std::vector<cslam::SearchForTriangulationBatch::Epipolar> ep((size_t)C);
-    for (int j = 0; j < C; j++) {
-      h2[j] = has2 ? has2 + has2_off[j] : nullptr;
-      std::memcpy(ep[j].F12, epi + 11 * (size_t)j, 9 * sizeof(float));
-      ep[j].ex = epi[11 * (size_t)j + 9]; ep[j].ey = epi[11 * (size_t)j + 10];
-    }
-    return new cslam::SearchForTriangulationBatch(*static_cast<cslam::KeyFrameStore*>(store), device < 0 ? nullptr : &thread_context(device), key1, C, keys2, has1,
-                                                  h2.data(), ep.data(), sigma2_2, sf2, nlevels, check_orientation != 0);
-  } catch (const std::exception&) { return nullptr; }
-}
-int ccmh_tri_search_resolve(void* h, int j, const uint8_t* has1_now, const uint8_t* has2_now, int n_feat, int32_t* matches12) {
-  if (!h) return -1000;
-  cslam::SearchForTriangulationBatch& b = *static_cast<cslam::SearchForTriangulationBatch*>(h);
-  if (j < 0 || j >= b.neighbours()) return -1000;
-  if (n_feat != b.features1()) return -1001;
-  std::vector<int32_t> m;
-  const int n = b.resolve(j, has1_now, has2_now, m);
-  if (matches12 && n_feat) std::memcpy(matches12, m.data(), (size_t)n_feat * 4);
-  return n;
-}
-int ccmh_tri_search_table(void* h, uint32_t* table, int32_t* n_query, int32_t* n_match, int32_t* n_dist) {
-  if (!h) return -1;
-  const cslam::SearchForTriangulationBatch& b = *static_cast<cslam::SearchForTriangulationBatch*>(h);
-  if (table && !b.table().empty()) std::memcpy(table, b.table().data(), b.table().size() * 4);
-  if (n_query && b.neighbours()) std::memcpy(n_query, b.nQuery().data(), (size_t)b.neighbours() * 4);
-  if (n_match && b.neighbours()) std::memcpy(n_match, b.nMatch().data(), (size_t)b.neighbours() * 4);
-  if (n_dist && b.neighbours()) std::memcpy(n_dist, b.nDist().data(), (size_t)b.neighbours() * 4);
-  return 0;
-}
-long long ccmh_tri_search_n_reeval(void* h) { return h ? static_cast<cslam::SearchForTriangulationBatch*>(h)->reevaluated() : -1; }
-void ccmh_tri_search_destroy(void* h) { delete static_cast<cslam::SearchForTriangulationBatch*>(h); }
-
-// the refresh of map points through C
-int ccmh_mappoint_refresh_eval_resident_host(void* store, int K, const int64_t* keys, const float* kf_center, int P, const int32_t* obs_off, const int32_t* obs_kf,
-                                             const int32_t* obs_feat, const float* pos, const int32_t* ref_kf, const int32_t* ref_feat, int nlevels,
-                                             const float* scale_factors, int32_t* best_obs, uint8_t* best_desc, float* normal, float* min_dist, float* max_dist,
-                                             uint8_t* status) {
-  if (!store) return -1;
-  return cslam::mappoint_refresh_eval_resident_host(*static_cast<cslam::KeyFrameStore*>(store), K, keys, kf_center, P, obs_off, obs_kf, obs_feat, pos, ref_kf, ref_feat,
-                                                    nlevels, scale_factors, best_obs, best_desc, normal, min_dist, max_dist, status);
-}
-void* ccmh_mappoint_refresh_create(void* store, int device, int K, const int64_t* keys, const float* kf_center, int P, const int32_t* obs_off, const int32_t* obs_kf,
-                                   const int32_t* obs_feat, const float* pos, const int32_t* ref_kf, const int32_t* ref_feat, const float* normal, const float* min_dist,
-                                   const float* max_dist, int nlevels, const float* scale_factors) {
-  if (!store) return nullptr;
-  try {
-    return new cslam::MapPointRefresh(*static_cast<cslam::KeyFrameStore*>(store), device < 0 ? nullptr : &thread_context(device), K, keys, kf_center,
-                                      {P, obs_off, obs_kf, obs_feat}, {pos, ref_kf, ref_feat, normal, min_dist, max_dist}, nlevels, scale_factors);
-  } catch (const std::exception&) { return nullptr; }
-}
-int ccmh_mappoint_refresh_result(void* h, int P, int32_t* best_obs, uint8_t* desc, uint8_t* has_desc, float* normal, float* min_dist, float* max_dist, uint8_t* status) {
-  if (!h) return -1;
-  const cslam::MapPointRefresh& m = *static_cast<cslam::MapPointRefresh*>(h);
-  if (P != m.points()) return -1;
-  for (int p = 0; p < P; p++) {
-    best_obs[p] = m.best()[(size_t)p]; status[p] = m.status()[(size_t)p];
-    const uint8_t* d = m.descriptor(p);
-    has_desc[p] = d != nullptr;
-    if (d) std::memcpy(desc + 32 * (size_t)p, d, 32);
-    for (int c = 0; c < 3; c++) normal[3 * (size_t)p + c] = m.normal()[3 * (size_t)p + c];
-    min_dist[p] = m.min_dist()[(size_t)p]; max_dist[p] = m.max_dist()[(size_t)p];
-  }
-  return 0;
-}
-void ccmh_mappoint_refresh_destroy(void* h) { delete static_cast<cslam::MapPointRefresh*>(h); }
-
-// the two projected searches of ComputeSim3 through C: host evaluators, ssm_derive, the two mirrors
-int ccmh_sim3_project_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
-                                const int32_t* cell_off, const int32_t* cell_idx, const float* Scw, const int32_t* skip_off, const uint8_t* feat_skip, int nlevels,
-                                const float* scale_factors, float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist,
-                                const float* max_dist, const uint8_t* pt_desc, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv) {
-  return cslam::sim3_project_eval_host(K, kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off, cell_idx, Scw, skip_off, feat_skip, nlevels, scale_factors,
-                                       logScaleFactor, th, P, pos, normal, min_dist, max_dist, pt_desc, table, n_valid, n_hit, uv);
-}
-int ccmh_sim3_pair_eval_host(int K, const float* kf_rec, const int32_t* feat_off, const float* feat_xy, const uint8_t* feat_octave, const uint8_t* feat_desc,
-                             const int32_t* cell_off, const int32_t* cell_idx, int nlevels, const float* scale_factors, float logScaleFactor, float th, int P,
-                             const float* pos, const float* min_dist, const float* max_dist, const uint8_t* pt_desc, int J, const int32_t* job_kf, const float* job_K4,
-                             const float* job_src_pose, const float* job_T, const int32_t* job_pt0, const int32_t* job_n, uint32_t* table, int32_t* n_valid,
-                             int32_t* n_hit, float* uv) {
-  return cslam::sim3_pair_eval_host(K, kf_rec, feat_off, feat_xy, feat_octave, feat_desc, cell_off, cell_idx, nlevels, scale_factors, logScaleFactor, th, P, pos, min_dist,
-                                    max_dist, pt_desc, J, job_kf, job_K4, job_src_pose, job_T, job_pt0, job_n, table, n_valid, n_hit, uv);
-}
-int ccmh_sim3_project_eval_resident_host(void* store, int K, const int64_t* keys, const float* Scw, const int32_t* skip_off, const uint8_t* feat_skip, int nlevels,
-                                         const float* scale_factors, float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist,
-                                         const float* max_dist, const uint8_t* pt_desc, uint32_t* table, int32_t* n_valid, int32_t* n_hit, float* uv) {
-  if (!store) return -1;
-  return cslam::sim3_project_eval_resident_host(*static_cast<cslam::KeyFrameStore*>(store), K, keys, Scw, skip_off, feat_skip, nlevels, scale_factors, logScaleFactor, th, P,
-                                                pos, normal, min_dist, max_dist, pt_desc, table, n_valid, n_hit, uv);
-}
-int ccmh_sim3_pair_eval_resident_host(void* store, int K, const int64_t* keys, int nlevels, const float* scale_factors, float logScaleFactor, float th, int P,
-                                      const float* pos, const float* min_dist, const float* max_dist, const uint8_t* pt_desc, int J, const int32_t* job_kf,
-                                      const float* job_K4, const float* job_src_pose, const float* job_T, const int32_t* job_pt0, const int32_t* job_n, uint32_t* table,
-                                      int32_t* n_valid, int32_t* n_hit, float* uv) {
-  if (!store) return -1;
-  return cslam::sim3_pair_eval_resident_host(*static_cast<cslam::KeyFrameStore*>(store), K, keys, nlevels, scale_factors, logScaleFactor, th, P, pos, min_dist, max_dist,
-                                             pt_desc, J, job_kf, job_K4, job_src_pose, job_T, job_pt0, job_n, table, n_valid, n_hit, uv);
-}
-void ccmh_ssm_derive(float s12, const float* R12, const float* t12, float* sR12, float* sR21, float* t21) { ssm_derive(s12, R12, t12, sR12, sR21, t21); }
-void* ccmh_sim3_project_create(void* store, int device, int64_t key, const float* Scw12, const uint8_t* matched0, int nlevels, const float* scale_factors,
-                               float logScaleFactor, float th, int P, const float* pos, const float* normal, const float* min_dist, const float* max_dist,
-                               const uint8_t* pt_desc) {
-  if (!store) return nullptr;
-  try {
-    cslam::Sim3ProjectionSearch::Points pt;
-    pt.P = P; pt.pos = pos; pt.normal = normal; pt.min_dist = min_dist; pt.max_dist = max_dist; pt.desc = pt_desc;
-    return new cslam::Sim3ProjectionSearch(*static_cast<cslam::KeyFrameStore*>(store), device < 0 ? nullptr : &thread_context(device), key, Scw12, pt, matched0, nlevels,
-                                           scale_factors, logScaleFactor, th);
-  } catch (const std::exception&) { return nullptr; }
-}
-int ccmh_sim3_project_table(void* h, uint32_t* table, int32_t* n_valid, int32_t* n_hit) {
-  if (!h) return -1;
-  const cslam::Sim3ProjectionSearch& b = *static_cast<cslam::Sim3ProjectionSearch*>(h);
-  if (table && !b.table().empty()) std::memcpy(table, b.table().data(), b.table().size() * 4);
-  if (n_valid) *n_valid = b.nValid();
-  if (n_hit) *n_hit = b.nHit();
-  return 0;
-}
-int ccmh_sim3_project_resolve(void* h, const uint8_t* skip_now, const int32_t* existing_idx, int n_feat, int32_t* matched, int n_pts, int32_t* best_idx, int32_t* remap) {
-  if (!h) return -1000;
-  try {
-    cslam::Sim3ProjectionSearch& b = *static_cast<cslam::Sim3ProjectionSearch*>(h);
-    if (n_pts != b.points() || n_feat != b.features()) return -1001;
-    std::vector<int32_t> bi, rm;
-    const int n = b.resolve(skip_now, existing_idx, matched, bi, rm);
-    if (n_pts) { std::memcpy(best_idx, bi.data(), bi.size() * 4); std::memcpy(remap, rm.data(), rm.size() * 4); }
-    return n;
-  } catch (const std::exception&) { return -1000; }
-}
-long long ccmh_sim3_project_n_reeval(void* h) { return h ? static_cast<cslam::Sim3ProjectionSearch*>(h)->n_reeval() : -1; }
-void ccmh_sim3_project_destroy(void* h) { delete static_cast<cslam::Sim3ProjectionSearch*>(h); }
-int ccmh_search_by_sim3_resident(void* store, int device, int64_t key1, int64_t key2, int N1, const uint8_t* live1, const float* pos1, const float* min1, const float* max1,
-                                 const uint8_t* desc1, const float* pose1, int N2, const uint8_t* live2, const float* pos2, const float* min2, const float* max2,
-                                 const uint8_t* desc2, const float* pose2, float s12, const float* R12, const float* t12, const int32_t* matches12_in, int nlevels,
-                                 const float* scale_factors, float logScaleFactor, float th, int32_t* matches12, int32_t* vn1, int32_t* vn2, int32_t* n_valid2,
-                                 int32_t* n_hit2) {
-  if (!store) return -1000;
-  try {
-    cslam::SearchBySim3Batch::Side a, b;
-    a.N = N1; a.live = live1; a.pos = pos1; a.min_dist = min1; a.max_dist = max1; a.desc = desc1; a.pose = pose1;
-    b.N = N2; b.live = live2; b.pos = pos2; b.min_dist = min2; b.max_dist = max2; b.desc = desc2; b.pose = pose2;
-    const cslam::SearchBySim3Batch r(*static_cast<cslam::KeyFrameStore*>(store), device < 0 ? nullptr : &thread_context(device), key1, key2, a, b, s12, R12, t12,
-                                     matches12_in, nlevels, scale_factors, logScaleFactor, th);
-    if (matches12 && N1) std::memcpy(matches12, r.matches12().data(), (size_t)N1 * 4);
-    if (vn1 && N1) std::memcpy(vn1, r.vnMatch1().data(), (size_t)N1 * 4);
-    if (vn2 && N2) std::memcpy(vn2, r.vnMatch2().data(), (size_t)N2 * 4);
-    if (n_valid2) std::memcpy(n_valid2, r.nValid().data(), 8);
-    if (n_hit2) std::memcpy(n_hit2, r.nHit().data(), 8);
-    return r.nFound();
-  } catch (const std::exception&) { return -1000; }
-}
-
-int ccmh_search_for_initialization(int device, const float* x1, const float* y1, const int32_t* oct1, const float* a1, const uint8_t* d1, int N1,
-                                   const float* x2, const float* y2, const int32_t* oct2, const float* a2, const uint8_t* d2, int N2,
-                                   float minX, float minY, float maxX, float maxY, float* prev_xy, int window, float nnratio, int check_ori,
-                                   int32_t* matches12) {
-  try {
-    cslam::HipContext& ctx = thread_context(device);
-    auto k1 = mk_keys(x1, y1, oct1, a1, N1), k2 = mk_keys(x2, y2, oct2, a2, N2);
-    cslam::KeysView A; A.N = N1; A.keys = k1.data(); A.desc = d1;
-    std::vector<int32_t> dummy(N2, -1);
-    cslam::FrameView F; F.N = N2; F.mvKeysUn = k2.data(); F.mDescriptors = d2; F.mnMinX = minX; F.mnMinY = minY; F.mnMaxX = maxX; F.mnMaxY = maxY;
-    F.mvpMapPoints = dummy.data();
-    std::vector<float> prev(prev_xy, prev_xy + 2 * (size_t)N1);
-    std::vector<int32_t> r;
-    cslam::ORBmatcher m(ctx, nnratio, check_ori != 0);
-    const int n = m.SearchForInitialization(A, F, prev, r, window);
-    std::memcpy(prev_xy, prev.data(), prev.size() * sizeof(float));
-    std::memcpy(matches12, r.data(), r.size() * sizeof(int32_t));
-    return n;
-  } catch (const std::exception&) { return -1000; }
-}
-}
-
-extern "C" int ccmh_projected_window_search(int device, const float* kx, const float* ky, const int32_t* oct, const uint8_t* kdesc, int N, float minX,
-                                            float minY, float maxX, float maxY, const float* scale_factors, const float* inv_sigma2, int n_pts,
-                                            const uint8_t* valid, const float* u, const float* v, const int32_t* level, const uint8_t* pdesc, float th,
-                                            int chi2_gate, int dist_threshold, int32_t* matched, int claim, const uint8_t* no_claim,
-                                            int32_t* best_idx, int32_t* best_dist) {
-  try {
-    cslam::HipContext& ctx = thread_context(device);
-    auto kps = mk_keys(kx, ky, oct, nullptr, N);
-    std::vector<int32_t> dummy(N, -1);
-    cslam::FrameView F; F.N = N; F.mvKeysUn = kps.data(); F.mDescriptors = kdesc; F.mnMinX = minX; F.mnMinY = minY; F.mnMaxX = maxX; F.mnMaxY = maxY;
-    F.mvScaleFactors = scale_factors; F.mvpMapPoints = dummy.data();
-    cslam::ORBmatcher::ProjectedPoints P; P.n = n_pts; P.valid = valid; P.u = u; P.v = v; P.level = level; P.desc = pdesc; P.noClaim = no_claim;
-    cslam::ORBmatcher m(ctx);
-    std::vector<int32_t> bi, bd;
-    const int n = m.ProjectedSearch(F, inv_sigma2, P, th, chi2_gate != 0, dist_threshold, matched, claim != 0, bi, bd);
-    std::memcpy(best_idx, bi.data(), bi.size() * sizeof(int32_t));
-    std::memcpy(best_dist, bd.data(), bd.size() * sizeof(int32_t));
-    return n;
-  } catch (const std::exception&) { return -1000; }
-}
-
-// the same search on candidate lists the caller obtained from its own KeyFrame::GetFeaturesInArea (CSR over the n points; th and the bounds are unused)
-extern "C" int ccmh_projected_window_search_cand(int device, const float* kx, const float* ky, const int32_t* oct, const uint8_t* kdesc, int N,
-                                                 const float* inv_sigma2, int n_pts, const uint8_t* valid, const float* u, const float* v, const int32_t* level,
-                                                 const uint8_t* pdesc, const int32_t* cand_off, const int32_t* cand_idx, int chi2_gate, int dist_threshold,
-                                                 int32_t* matched, int claim, const uint8_t* no_claim, int32_t* best_idx, int32_t* best_dist) {
-  try {
-    cslam::HipContext& ctx = thread_context(device);
-    auto kps = mk_keys(kx, ky, oct, nullptr, N);
-    cslam::FrameView F; F.N = N; F.mvKeysUn = kps.data(); F.mDescriptors = kdesc;
-    cslam::ORBmatcher::ProjectedPoints P; P.n = n_pts; P.valid = valid; P.u = u; P.v = v; P.level = level; P.desc = pdesc; P.noClaim = no_claim;
-    P.candOff = cand_off; P.candIdx = cand_idx;
-    cslam::ORBmatcher m(ctx);
-    std::vector<int32_t> bi, bd;
-    const int n = m.ProjectedSearch(F, inv_sigma2, P, 0.f, chi2_gate != 0, dist_threshold, matched, claim != 0, bi, bd);
-    std::memcpy(best_idx, bi.data(), bi.size() * sizeof(int32_t));
-    std::memcpy(best_dist, bd.data(), bd.size() * sizeof(int32_t));
-    return n;
-  } catch (const std::exception&) { return -1000; }
-}
-
-// the same search through the device grid (bounds must be the plain image rectangle: 0, 0, maxX, maxY)
-extern "C" int ccmh_projected_window_search_dev(int device, const float* kx, const float* ky, const int32_t* oct, const uint8_t* kdesc, int N, float maxX,
-                                                float maxY, const float* scale_factors, const float* inv_sigma2, int n_pts, const uint8_t* valid,
-                                                const float* u, const float* v, const int32_t* level, const uint8_t* pdesc, float th, int chi2_gate,
-                                                int dist_threshold, int32_t* matched, int claim, const uint8_t* no_claim, int32_t* best_idx,
-                                                int32_t* best_dist) {
-  try {
-    cslam::HipContext& ctx = thread_context(device);
-    auto kps = mk_keys(kx, ky, oct, nullptr, N);
-    const float K[4] = {1.f, 1.f, 0.f, 0.f};
-    cslam::FrameGridDev grid(ctx, K, nullptr, 0, (int)maxX, (int)maxY);
-    std::vector<cslam::KeyPoint> keysUn;
-    grid.SetKeyPoints(kps, kdesc, keysUn);
-    std::vector<int32_t> dummy(N, -1);
-    cslam::FrameView F; F.N = N; F.mvKeysUn = keysUn.data(); F.mDescriptors = kdesc; F.mnMinX = grid.mnMinX; F.mnMinY = grid.mnMinY; F.mnMaxX = grid.mnMaxX;
-    F.mnMaxY = grid.mnMaxY; F.mvScaleFactors = scale_factors; F.mvpMapPoints = dummy.data();
-    cslam::ORBmatcher::ProjectedPoints P; P.n = n_pts; P.valid = valid; P.u = u; P.v = v; P.level = level; P.desc = pdesc; P.noClaim = no_claim;
-    cslam::ORBmatcher m(ctx);
-    std::vector<int32_t> bi, bd;
-    const int n = m.ProjectedSearch(grid, F, inv_sigma2, P, th, chi2_gate != 0, dist_threshold, matched, claim != 0, bi, bd);
-    std::memcpy(best_idx, bi.data(), bi.size() * sizeof(int32_t));
-    std::memcpy(best_dist, bd.data(), bd.size() * sizeof(int32_t));
-    return n;
-  } catch (const std::exception&) { return -1000; }
-}
-
-// FuseBatch through a flat interface (tests): S targets given as concatenated arrays with offsets; every target is searched with the chi2 gate and TH_LOW like Fuse
-extern "C" void* ccmh_fuse_batch_create(int device, int S, const int32_t* kf_off /* [S+1] features */, const float* kx, const float* ky, const int32_t* oct, const uint8_t* kdesc,
-                                        const float* bounds4 /* [S][4] minX minY maxX maxY */, const float* scale_factors, const float* inv_sigma2,
-                                        const int32_t* pt_off /* [S+1] points */, const uint8_t* valid, const float* u, const float* v, const int32_t* level,
-                                        const uint8_t* pdesc, float th) {
-  try {
-    cslam::HipContext& ctx = thread_context(device);
-    cslam::ORBmatcher m(ctx);
-    std::vector<std::vector<cslam::KeyPoint>> keys(S);
-    std::vector<std::vector<int32_t>> dummy(S);
-    std::vector<cslam::FuseBatch::Target> tg(S);
-    for (int s = 0; s < S; s++) {
-      const int k0 = kf_off[s], N = kf_off[s + 1] - k0, p0 = pt_off[s];
-      keys[s] = mk_keys(kx + k0, ky + k0, oct + k0, nullptr, N);
-      dummy[s].assign(N, -1);
-      cslam::FrameView& F = tg[s].KF;
-      F.N = N; F.mvKeysUn = keys[s].data(); F.mDescriptors = kdesc + (size_t)k0 * 32; F.mnMinX = bounds4[4 * s]; F.mnMinY = bounds4[4 * s + 1]; F.mnMaxX = bounds4[4 * s + 2];
-      F.mnMaxY = bounds4[4 * s + 3]; F.mvScaleFactors = scale_factors; F.mvpMapPoints = dummy[s].data();
-      cslam::ORBmatcher::ProjectedPoints& P = tg[s].P;
-      P.n = pt_off[s + 1] - p0; P.valid = valid + p0; P.u = u + p0; P.v = v + p0; P.level = level + p0; P.desc = pdesc + (size_t)p0 * 32;
-      tg[s].invLevelSigma2 = inv_sigma2; tg[s].th = th;
-    }
-    return new cslam::FuseBatch(m, tg);
-  } catch (const std::exception&) { return nullptr; }
-}
-// the same with every target's window candidates supplied by the caller (its own KeyFrame::GetFeaturesInArea, as ccmh_projected_window_search_cand): target s owns the
-// points pt_off[s] .. pt_off[s+1]; cand_off has one entry per point plus one per target (target s: entries pt_off[s] + s .. pt_off[s+1] + s, starting at 0), its
-// candidate indices start at cand_base[s] in cand_idx
-extern "C" void* ccmh_fuse_batch_create_cand(int device, int S, const int32_t* kf_off, const float* kx, const float* ky, const int32_t* oct, const uint8_t* kdesc,
-                                             const float* const* inv_sigma2 /* [S] */, const int32_t* pt_off, const uint8_t* valid, const float* u, const float* v,
-                                             const int32_t* level, const uint8_t* pdesc, const int32_t* cand_off, const int32_t* cand_base, const int32_t* cand_idx,
-                                             int chi2_gate, int dist_threshold) {
-  try {
-    cslam::HipContext& ctx = thread_context(device);
-    cslam::ORBmatcher m(ctx);
-    std::vector<std::vector<cslam::KeyPoint>> keys(S);
-    std::vector<cslam::FuseBatch::Target> tg(S);
-    for (int s = 0; s < S; s++) {
-      const int k0 = kf_off[s], N = kf_off[s + 1] - k0, p0 = pt_off[s];
-      keys[s] = mk_keys(kx + k0, ky + k0, oct + k0, nullptr, N);
-      cslam::FrameView& F = tg[s].KF;
-      F.N = N; F.mvKeysUn = keys[s].data(); F.mDescriptors = kdesc + (size_t)k0 * 32;
-      cslam::ORBmatcher::ProjectedPoints& P = tg[s].P;
-      P.n = pt_off[s + 1] - p0; P.valid = valid + p0; P.u = u + p0; P.v = v + p0; P.level = level + p0; P.desc = pdesc + (size_t)p0 * 32;
-      P.candOff = cand_off + p0 + s; P.candIdx = cand_idx + cand_base[s];
-      tg[s].invLevelSigma2 = inv_sigma2[s]; tg[s].th = 0.f;
-    }
-    return new cslam::FuseBatch(m, tg, chi2_gate != 0, dist_threshold);
-  } catch (const std::exception&) { return nullptr; }
-}
-extern "C" long long ccmh_fuse_batch_candidates(void* h) { return h ? (long long)((cslam::FuseBatch*)h)->candidates() : -1; }
-extern "C" int ccmh_fuse_batch_resolve(void* h, int s, const uint8_t* skip_now, int n_pts, int32_t* best_idx, int32_t* best_dist) {
-  try {
-    std::vector<int32_t> bi, bd;
-    const int n = ((cslam::FuseBatch*)h)->resolve(s, skip_now, bi, bd);
-    if ((int)bi.size() != n_pts) return -1001;
-    std::memcpy(best_idx, bi.data(), bi.size() * sizeof(int32_t));
-    std::memcpy(best_dist, bd.data(), bd.size() * sizeof(int32_t));
-    return n;
-  } catch (const std::exception&) { return -1000; }
-}
-extern "C" void ccmh_fuse_batch_destroy(void* h) { delete (cslam::FuseBatch*)h; }
-
-extern "C" int ccmh_bow_transform(int device, int n_nodes, int L, const int32_t* child_off, const int32_t* child_id, const uint8_t* node_desc,
-                                  const int32_t* word_id, const double* weight, const uint8_t* desc, int N, int levelsup, int32_t* bow_ids,
-                                  double* bow_vals, int32_t* fv_nodes, int32_t* fv_off, int32_t* fv_idx, int32_t* sizes /* [n_bow, n_fv_nodes, n_fv_idx] */) {
-  try {
-    cslam::HipContext& ctx = thread_context(device);
-    cslam::ORBVocabulary voc(ctx, n_nodes, L, child_off, child_id, node_desc, word_id, weight);
-    cslam::BowVector v; cslam::FeatureVector fv;
-    voc.transform(desc, N, v, fv, levelsup);
-    std::memcpy(bow_ids, v.word.data(), v.word.size() * 4); std::memcpy(bow_vals, v.value.data(), v.value.size() * 8);
-    std::memcpy(fv_nodes, fv.node.data(), fv.node.size() * 4); std::memcpy(fv_off, fv.off.data(), fv.off.size() * 4);
-    std::memcpy(fv_idx, fv.idx.data(), fv.idx.size() * 4);
-    sizes[0] = (int32_t)v.word.size(); sizes[1] = (int32_t)fv.node.size(); sizes[2] = (int32_t)fv.idx.size();
-    return 0;
-  } catch (const std::exception&) { return -1000; }
-}
-
-// KeyFrameDatabase::Detect*Candidates through the mirror on a database handle of libccm_hip.so (the Python KeyFrameDatabase's).  kind 0 = loop
-// (self_key, allow / n_allow (n_allow < 0: every keyframe), exclude), 1 = map match (exclude_groups), 2 = relocalisation.  Neighbours as a table:
-// nb_key[i] has the neighbours nb_list[nb_off[i] .. nb_off[i+1]); keys absent from it have none.  Returns the number of candidates (<= cap written).
-extern "C" int ccmh_kfdb_detect(void* db, int device, int kind, int n, const int32_t* word, const double* value, float min_score, int64_t self_key,
-                                const int64_t* allow, int n_allow, const int64_t* exclude, int n_exclude, uint64_t exclude_groups, int n_nb_keys,
-                                const int64_t* nb_key, const int32_t* nb_off, const int64_t* nb_list, int64_t* out, int cap) {
-  try {
-    cslam::HipContext& ctx = thread_context(device);
-    cslam::KeyFrameDatabase kfdb((ccm_kfdb*)db);
-    cslam::BowVector v; v.word.assign(word, word + n); v.value.assign(value, value + n);
-    std::map<int64_t, int> row;
-    for (int i = 0; i < n_nb_keys; i++) row[nb_key[i]] = i;
-    auto nbs = [&](int64_t k, std::vector<int64_t>& o) {
-      auto it = row.find(k);
-      if (it != row.end()) o.assign(nb_list + nb_off[it->second], nb_list + nb_off[it->second + 1]);
-    };
-    std::vector<int64_t> r;
-    if (kind == 0) {
-      std::vector<int64_t> ex(exclude, exclude + n_exclude), al;
-      if (n_allow >= 0) al.assign(allow, allow + n_allow);
-      r = kfdb.DetectLoopCandidates(ctx, self_key, v, min_score, n_allow >= 0 ? &al : nullptr, ex, nbs);
-    } else if (kind == 1) {
-      r = kfdb.DetectMapMatchCandidates(ctx, v, min_score, exclude_groups, nbs);
-    } else {
-      r = kfdb.DetectRelocalizationCandidates(ctx, v, nbs);
-    }
-    for (int i = 0; i < (int)r.size() && i < cap; i++) out[i] = r[i];
-    return (int)r.size();
-  } catch (const std::exception&) { return -1000; }
-}
-
-// Sim3RansacBatch over flat arrays: candidate c has the correspondences pt_off[c] .. pt_off[c+1] (X3Dc1 / X3Dc2 3 per correspondence, thresholds,
-// idx1 = mvnIndices1) and n1[c] = mN1, K1 / K2 4 per candidate.  draws != NULL: the raw rand() values come from draws[0 .. n_draws) (after the
-// thread's FIFO) instead of ::rand().
-namespace {
-// a batch behind a C handle, with the supplied draws it reads (after the thread's FIFO) where the caller gave some
-template <class Batch>
-struct RansacBatchHandle {
-  std::vector<int32_t> draws;
-  size_t cursor = 0;
-  std::unique_ptr<Batch> batch;
-  ccm_ransac::DrawSource source(const int32_t* d, int64_t n) {   // d == NULL: ::rand()
-    if (!d) return ccm_ransac::rand_source();
-    draws.assign(d, d + n);
-    return [this](int& v) { if (cursor >= draws.size()) return false; v = draws[cursor++]; return true; };
-  }
-};
-typedef RansacBatchHandle<cslam::Sim3RansacBatch> Sim3BatchHandle;
-typedef RansacBatchHandle<cslam::PnPRansacBatch> PnpBatchHandle;
-}  // namespace
-extern "C" void* ccmh_sim3_ransac_create(int device, int K, const int32_t* pt_off, const float* X3Dc1, const float* X3Dc2, const float* K1, const float* K2,
-                                         const uint32_t* max_err1, const uint32_t* max_err2, const int32_t* n1, const int32_t* idx1, double probability,
-                                         int min_inliers, int max_iterations, int solver_iterations, int fix_scale, const int32_t* draws, int64_t n_draws) {
-  try {
-    if (K < 0 || !pt_off || (K > 0 && (!n1 || !K1 || !K2)) || (draws == nullptr && n_draws != 0) || n_draws < 0 || solver_iterations < 1) return nullptr;
-    std::vector<cslam::Sim3Candidate> cands(K);
-    for (int c = 0; c < K; c++) {
-      const int a = pt_off[c], b = pt_off[c + 1];
-      if (b < a) return nullptr;
-      if (b > a && (!X3Dc1 || !X3Dc2 || !max_err1 || !max_err2 || !idx1)) return nullptr;
-      auto& x = cands[c];
-      x.n1 = n1[c];
-      x.indices1.assign(idx1 + a, idx1 + b);
-      x.X3Dc1.assign(X3Dc1 + 3 * (size_t)a, X3Dc1 + 3 * (size_t)b);
-      x.X3Dc2.assign(X3Dc2 + 3 * (size_t)a, X3Dc2 + 3 * (size_t)b);
-      x.max_err1.assign(max_err1 + a, max_err1 + b);
-      x.max_err2.assign(max_err2 + a, max_err2 + b);
-      for (int k = 0; k < 4; k++) { x.K1[k] = K1[4 * c + k]; x.K2[k] = K2[4 * c + k]; }
-    }
-    ccm_sim3::Params p;
-    p.probability = probability; p.min_inliers = min_inliers; p.max_iterations = max_iterations; p.solver_iterations = solver_iterations;
-    std::unique_ptr<Sim3BatchHandle> h(new Sim3BatchHandle);
-    h->batch.reset(new cslam::Sim3RansacBatch(thread_context(device), std::move(cands), p, fix_scale != 0, h->source(draws, n_draws)));
-    return h.release();
-  } catch (const std::exception&) { return nullptr; }
-}
-// 1: an event (inliers[0 .. min(cap, mN1)) = vbInliers), 0: every candidate discarded, -1: the supplied draws ran out, -1000: device error
-extern "C" int ccmh_sim3_ransac_next(void* hv, int32_t* cand, float* R9, float* t3, float* s, uint8_t* inliers, int cap, int32_t* n_inliers) {
-  if (!hv) return -1000;
-  try {
-    Sim3BatchHandle* h = (Sim3BatchHandle*)hv;
-    int c = -1, n = 0; float sc = 0; std::vector<bool> vb;
-    float R[9], t[3];
-    try {
-      if (!h->batch->next(c, R, t, sc, vb, n)) return 0;
-    } catch (const ccm_sim3::DrawsExhausted&) {
-      return -1;
-    }
-    if (cand) *cand = c;
-    if (R9) std::memcpy(R9, R, sizeof R);
-    if (t3) std::memcpy(t3, t, sizeof t);
-    if (s) *s = sc;
-    if (n_inliers) *n_inliers = n;
-    if (inliers) for (int i = 0; i < cap && i < (int)vb.size(); i++) inliers[i] = vb[i] ? 1 : 0;
-    return 1;
-  } catch (const std::exception&) { return -1000; }
-}
-// [values taken from the draw source, hypotheses evaluated, passes (device calls)]
-extern "C" int ccmh_sim3_ransac_stats(void* hv, int64_t* out3) {
-  if (!hv || !out3) return -1000;
-  const auto& sc = ((Sim3BatchHandle*)hv)->batch->schedule();
-  out3[0] = sc.source_draws(); out3[1] = sc.hyps_evaluated(); out3[2] = sc.passes();
-  return 0;
-}
-extern "C" void ccmh_sim3_ransac_destroy(void* hv) { delete (Sim3BatchHandle*)hv; }
-// One Sim3Solver::iterate(n_iterations) of the drop-in shim/Sim3Solver_hip.cpp: N correspondences (X3Dc1 / X3Dc2, thresholds, cameras), state = [mnIterations,
-// mnBestInliers] in / out, draws from ::rand() through the calling thread's FIFO.  flags = [success, bNoMore, best moved, inliers of the best]; when the best
-// moved, best_rts = R (9) t (3) s and best_mask = its inlier bits (ceil(N / 32) words).  0, or -1000 on a device error.
-extern "C" int ccmh_sim3_solver_iterate(int device, int N, const float* X3Dc1, const float* X3Dc2, const float* K1, const float* K2, const uint32_t* max_err1,
-                                        const uint32_t* max_err2, int fix_scale, int min_inliers, int max_iterations, int n_iterations, int32_t* state,
-                                        float* best_rts, uint32_t* best_mask, int32_t* flags) {
-  try {
-    if (N < 0 || !state || !flags || !best_rts || (N > 0 && (!X3Dc1 || !X3Dc2 || !K1 || !K2 || !max_err1 || !max_err2 || !best_mask))) return -1000;
-    cslam::Sim3RansacBatch::Eval ev;
-    ev.ctx = &thread_context(device);
-    ev.fix_scale = fix_scale ? 1 : 0;
-    ev.add(N, X3Dc1, X3Dc2, K1, K2, max_err1, max_err2);
-    ccm_sim3::SolverState st;
-    st.N = N; st.max_its = max_iterations; st.min_inliers = min_inliers; st.its = state[0]; st.best = state[1];
-    bool no_more = false, moved = false;
-    ccm_sim3::Event best;
-    const bool ok = ccm_sim3::iterate_one(ev, st, n_iterations, ccm_sim3::rand_source(), no_more, moved, best);
-    state[0] = st.its; state[1] = st.best;
-    flags[0] = ok; flags[1] = no_more; flags[2] = moved; flags[3] = moved ? best.n_inliers : 0;
-    if (moved) {
-      for (int i = 0; i < 9; i++) best_rts[i] = best.R[i];
-      for (int i = 0; i < 3; i++) best_rts[9 + i] = best.t[i];
-      best_rts[12] = best.s;
-      std::memcpy(best_mask, best.mask.data(), best.mask.size() * 4);
-    }
-    return 0;
-  } catch (const std::exception&) { return -1000; }
-}
-// PnPRansacBatch over flat arrays: candidate c has the correspondences pt_off[c] .. pt_off[c+1]
-namespace {
-int pnp_pose_out(const cslam::PnPRansacBatch::Pose& p, int32_t* cand, float* Tcw16, uint8_t* inliers, int cap, int32_t* n_inliers, int32_t* flags2) {
-  if (cand) *cand = p.cand;
-  if (Tcw16) std::memcpy(Tcw16, p.Tcw, sizeof p.Tcw);
-  if (n_inliers) *n_inliers = p.nInliers;
-  if (flags2) { flags2[0] = p.refined; flags2[1] = p.bNoMore; }
-  if (inliers) for (int i = 0; i < cap && i < (int)p.vbInliers.size(); i++) inliers[i] = p.vbInliers[i] ? 1 : 0;
-  return 1;
-}
-}  // namespace
-extern "C" void* ccmh_pnp_ransac_create(int device, int K, const int32_t* pt_off, const float* P3Dw, const float* P2D, const float* sigma2, const double* cam,
-                                        const int32_t* n_matches, const int32_t* kp_idx, double probability, int min_inliers, int max_iterations, int min_set,
-                                        float epsilon, float th2, int solver_iterations, const int32_t* draws, int64_t n_draws) {
-  try {
-    if (K < 0 || !pt_off || (K > 0 && (!n_matches || !cam)) || (draws == nullptr && n_draws != 0) || n_draws < 0) return nullptr;
-    std::vector<cslam::PnPCandidate> cands(K);
-    for (int c = 0; c < K; c++) {
-      const int a = pt_off[c], b = pt_off[c + 1];
-      if (b < a) return nullptr;
-      if (b > a && (!P3Dw || !P2D || !sigma2 || !kp_idx)) return nullptr;
-      auto& x = cands[c];
-      x.n_matches = n_matches[c];
-      x.keypoint_indices.assign(kp_idx + a, kp_idx + b);
-      x.P3Dw.assign(P3Dw + 3 * (size_t)a, P3Dw + 3 * (size_t)b);
-      x.P2D.assign(P2D + 2 * (size_t)a, P2D + 2 * (size_t)b);
-      x.sigma2.assign(sigma2 + a, sigma2 + b);
-      for (int k = 0; k < 4; k++) x.cam[k] = cam[4 * c + k];
-    }
-    ccm_pnp::Params p;
-    p.probability = probability; p.min_inliers = min_inliers; p.max_iterations = max_iterations; p.min_set = min_set; p.epsilon = epsilon; p.th2 = th2;
-    p.solver_iterations = solver_iterations;
-    std::unique_ptr<PnpBatchHandle> h(new PnpBatchHandle);
-    h->batch.reset(new cslam::PnPRansacBatch(device < 0 ? nullptr : &thread_context(device), std::move(cands), p, h->source(draws, n_draws)));
-    return h.release();
-  } catch (const std::exception&) { return nullptr; }
-}
-extern "C" int ccmh_pnp_ransac_next(void* hv, int32_t* cand, float* Tcw16, uint8_t* inliers, int cap, int32_t* n_inliers, int32_t* flags2) {
-  if (!hv) return -1000;
-  try {
-    cslam::PnPRansacBatch::Pose p;
-    try {
-      if (!((PnpBatchHandle*)hv)->batch->next(p)) return 0;
-    } catch (const ccm_pnp::DrawsExhausted&) {
-      return -1;
-    }
-    return pnp_pose_out(p, cand, Tcw16, inliers, cap, n_inliers, flags2);
-  } catch (const std::exception&) { return -1000; }
-}
-extern "C" int ccmh_pnp_ransac_iterate(void* hv, int c, int n_iterations, float* Tcw16, uint8_t* inliers, int cap, int32_t* n_inliers, int32_t* flags2) {
-  if (!hv || !flags2) return -1000;
-  try {
-    cslam::PnPRansacBatch::Pose p;
-    bool no_more = false;
-    bool got;
-    try {
-      got = ((PnpBatchHandle*)hv)->batch->iterate(c, n_iterations, no_more, p);
-    } catch (const ccm_pnp::DrawsExhausted&) {
-      return -1;
-    }
-    flags2[0] = 0; flags2[1] = no_more;
-    if (!got) return 0;
-    return pnp_pose_out(p, nullptr, Tcw16, inliers, cap, n_inliers, flags2);
-  } catch (const std::exception&) { return -1000; }
-}
-// [values taken from the draw source, hypotheses evaluated, passes (evaluator calls), Refine() computations]
-extern "C" int ccmh_pnp_ransac_stats(void* hv, int64_t* out4) {
-  if (!hv || !out4) return -1000;
-  const auto& sc = ((PnpBatchHandle*)hv)->batch->schedule();
-  out4[0] = sc.source_draws(); out4[1] = sc.hyps_evaluated(); out4[2] = sc.passes(); out4[3] = sc.refines();
-  return 0;
-}
-// [mnIterations, mRansacMaxIts, mRansacMinInliers, discarded] of candidate c
-extern "C" int ccmh_pnp_ransac_info(void* hv, int c, int32_t* out4) {
-  if (!hv || !out4) return -1000;
-  const auto& sc = ((PnpBatchHandle*)hv)->batch->schedule();
-  if (c < 0 || c >= (int)sc.candidates().size()) return -1;
-  out4[0] = sc.iterations(c); out4[1] = sc.max_iterations(c); out4[2] = sc.min_inliers(c); out4[3] = sc.discarded(c);
-  return 0;
-}
-extern "C" void ccmh_pnp_ransac_destroy(void* hv) { delete (PnpBatchHandle*)hv; }
-// the calling thread's FIFO of drawn, unused rand() values: returns its length, copies min(length, cap) values front first
-extern "C" int ccmh_sim3_draws_pending(int32_t* out, int cap) {
-  const auto& q = ccm_sim3::draw_fifo();
-  for (int i = 0; i < cap && i < (int)q.size(); i++) out[i] = q[i];
-  return (int)q.size();
-}
-extern "C" void ccmh_sim3_draws_clear(void) { ccm_sim3::draw_fifo().clear(); }
-
-// C entry points of the f32 <-> f64 boundary (ccm_convert.h) for the tests and for non-C++ callers
-#include "ccm_convert.h"
-extern "C" {
-void ccmh_to_se3quat(const float* Tcw16, double* qt7) { ccmh::toSE3Quat(Tcw16, qt7); }
-void ccmh_se3quat_to_cvmat(const double* qt7, float* Tcw16) { ccmh::toCvMat(qt7, Tcw16); }
-void ccmh_sim3_to_cvse3(const double* s8, float* Tcw16) { ccmh::sim3ToCvSE3(s8, Tcw16); }
-}
-
-// ---- C entry points of the guided search and of the relocalisation refine chain ------------------------------------------------
-namespace {
-struct GuidedFrameArgs {   // a Frame from flat arrays: undistorted keypoints (no distortion coefficients), the bounds of a w x h image
-  std::vector<cslam::KeyPoint> keys;
-  cslam::FrameView F;
-  GuidedFrameArgs(const void* kps_un, const uint8_t* fdesc, int N, const float* bounds, const float* scale_factors, int32_t* frame_mp)
-      : keys((const cslam::KeyPoint*)kps_un, (const cslam::KeyPoint*)kps_un + N) {
-    F.N = N; F.mvKeysUn = keys.data(); F.mDescriptors = fdesc;
-    F.mnMinX = bounds[0]; F.mnMinY = bounds[1]; F.mnMaxX = bounds[2]; F.mnMaxY = bounds[3];
-    F.mvScaleFactors = scale_factors; F.mvpMapPoints = frame_mp;
-  }
-};
-cslam::KeyFramePoints guidedKf(int P, const uint8_t* live, const float* pos, const float* min_dist, const float* max_dist, const uint8_t* desc, const float* angle) {
-  cslam::KeyFramePoints kf;
-  kf.n = P; kf.live = live; kf.pos = pos; kf.min_dist = min_dist; kf.max_dist = max_dist; kf.desc = desc; kf.angle = angle;
-  return kf;
-}
-}  // namespace
-extern "C" {
-// The host evaluator of ccm_frame_guided_search: its arguments after the frame, which is given as arrays; no device is touched.  0, or -1 for its CCM_E_ARG cases.
-int ccmh_guided_search_host(const void* kps_un, const uint8_t* fdesc, int N, const float* bounds, const float* K, const void* pose_v, int P, const float* pos,
-                            const float* min_dist, const float* max_dist, const uint8_t* desc, const uint8_t* skip, float th, uint8_t* status, float* u, float* v,
-                            int32_t* level, int32_t* cand_off, int32_t* cand_idx, uint16_t* cand_dist, int64_t cap, int64_t* n_cand) {
-  try {
-    if (!pose_v || !bounds || !K || N < 0 || (N && (!kps_un || !fdesc)) || P < 0 || !cand_off || !n_cand || (P && (!status || !u || !v || !level)) || cap < 0 ||
-        (cap && (!cand_idx || !cand_dist)))
-      return -1;
-    ccm_guided_pose pose;
-    std::memcpy(&pose, pose_v, sizeof(pose));
-    GuidedFrameArgs fr(kps_un, fdesc, N, bounds, pose.scaleFactors, nullptr);
-    const std::vector<uint8_t> live((size_t)std::max(P, 1), 1);
-    cslam::GuidedCandidates c;
-    cslam::ORBmatcher::GuidedSearchHost(fr.F, K, pose, guidedKf(P, live.data(), pos, min_dist, max_dist, desc, nullptr), skip, th, c);
-    *n_cand = (int64_t)c.idx.size();
-    std::memcpy(cand_off, c.off.data(), sizeof(int32_t) * ((size_t)P + 1));
-    if (P) {
-      std::memcpy(status, c.status.data(), (size_t)P); std::memcpy(u, c.u.data(), sizeof(float) * (size_t)P); std::memcpy(v, c.v.data(), sizeof(float) * (size_t)P);
-      std::memcpy(level, c.level.data(), sizeof(int32_t) * (size_t)P);
-    }
-    if (cap == 0) return 0;
-    if (*n_cand > cap) return -1;
-    if (*n_cand) { std::memcpy(cand_idx, c.idx.data(), sizeof(int32_t) * c.idx.size()); std::memcpy(cand_dist, c.dist.data(), sizeof(uint16_t) * c.dist.size()); }
-    return 0;
-  } catch (const std::invalid_argument&) { return -1;
-  } catch (const std::exception&) { return -1000; }
-}
-
-// ORBmatcher::SearchByProjection(Frame&, kfptr, sAlreadyFound, th, ORBdist): the host mirror without a grid (no device is touched) and with one (a FrameGridDev
-// built from the arrays).  nmatches, -1 for a bad argument, -1000 when the device path throws.  frame_mp: in/out, F.mvpMapPoints.
-int ccmh_search_by_projection_kf_host(const void* kps_un, const uint8_t* fdesc, int N, const float* bounds, const float* K, const void* pose_v, int P,
-                                      const uint8_t* live, const float* pos, const float* min_dist, const float* max_dist, const uint8_t* desc, const float* angle,
-                                      const uint8_t* already_found, float th, int orb_dist, int check_ori, int32_t* frame_mp) {
-  try {
-    if (!pose_v || !bounds || !K || N < 0 || (N && (!kps_un || !fdesc || !frame_mp)) || P < 0) return -1;
-    ccm_guided_pose pose;
-    std::memcpy(&pose, pose_v, sizeof(pose));
-    GuidedFrameArgs fr(kps_un, fdesc, N, bounds, pose.scaleFactors, frame_mp);
-    const cslam::KeyFramePoints kf = guidedKf(P, live, pos, min_dist, max_dist, desc, angle);
-    if (orb_dist < 0 || orb_dist > 255) return -1;
-    cslam::GuidedCandidates c;
-    cslam::ORBmatcher::GuidedSearchHost(fr.F, K, pose, kf, already_found, th, c);
-    return cslam::ORBmatcher::GuidedReplay(fr.F, kf, c, orb_dist, check_ori != 0);
-  } catch (const std::invalid_argument&) { return -1;
-  } catch (const std::exception&) { return -1000; }
-}
-int ccmh_search_by_projection_kf_dev(int device, const float* K, int w, int h, const void* kps_un, const uint8_t* fdesc, int N, const void* pose_v, int P,
-                                     const uint8_t* live, const float* pos, const float* min_dist, const float* max_dist, const uint8_t* desc, const float* angle,
-                                     const uint8_t* already_found, float th, int orb_dist, int check_ori, int32_t* frame_mp) {
-  try {
-    if (!pose_v || !K || N < 0 || (N && (!kps_un || !fdesc || !frame_mp)) || P < 0) return -1;
-    ccm_guided_pose pose;
-    std::memcpy(&pose, pose_v, sizeof(pose));
-    cslam::HipContext& ctx = thread_context(device);
-    cslam::FrameGridDev grid(ctx, K, nullptr, 0, w, h);
-    std::vector<cslam::KeyPoint> keys((const cslam::KeyPoint*)kps_un, (const cslam::KeyPoint*)kps_un + N), keysUn;
-    grid.SetKeyPoints(keys, fdesc, keysUn);
-    const float bounds[4] = {grid.mnMinX, grid.mnMinY, grid.mnMaxX, grid.mnMaxY};
-    GuidedFrameArgs fr(keysUn.data(), fdesc, N, bounds, pose.scaleFactors, frame_mp);
-    cslam::ORBmatcher m(ctx, 0.9f, check_ori != 0);
-    return m.SearchByProjection(grid, fr.F, pose, guidedKf(P, live, pos, min_dist, max_dist, desc, angle), already_found, th, orb_dist);
-  } catch (const std::invalid_argument&) { return -1;
-  } catch (const std::exception&) { return -1000; }
-}
-
-// the drop-in's form: the lists are the caller's Frame::GetFeaturesInArea results (cand_off over the P slots); f_angle: the frame's mvKeysUn[].angle
-int ccmh_search_by_projection_kf_cand(int device, const uint8_t* fdesc, const float* f_angle, int N, int P, const uint8_t* desc, const float* kf_angle,
-                                      const int32_t* cand_off, const int32_t* cand_idx, int orb_dist, int check_ori, int32_t* frame_mp) {
-  try {
-    if (N < 0 || P < 0 || (N && (!fdesc || !f_angle || !frame_mp)) || !cand_off) return -1;
-    cslam::HipContext& ctx = thread_context(device);
-    std::vector<cslam::KeyPoint> keys((size_t)N);
-    for (int i = 0; i < N; i++) keys[i] = cslam::KeyPoint{0.f, 0.f, 31.f, f_angle[i], 0.f, 0};
-    cslam::FrameView F; F.N = N; F.mvKeysUn = keys.data(); F.mDescriptors = fdesc; F.mvpMapPoints = frame_mp;
-    cslam::ORBmatcher m(ctx, 0.9f, check_ori != 0);
-    return m.SearchByProjectionCandidates(F, guidedKf(P, nullptr, nullptr, nullptr, nullptr, desc, kf_angle), cand_off, cand_idx, orb_dist);
-  } catch (const std::invalid_argument&) { return -1;
-  } catch (const std::exception&) { return -1000; }
-}
-
-// cslam::RelocalizationRefine on flat arrays.  1 matched, 0 not, -1 for a bad argument, -1000 when the device path throws.  frame_mp [N], Tcw16, trace5 and n_good: out.
-int ccmh_reloc_refine(int device, const float* K, int w, int h, const void* kps_un, const uint8_t* fdesc, int N, const float* inv_level_sigma2,
-                      const void* frame_v, int P, const uint8_t* live, const float* pos, const float* min_dist, const float* max_dist, const uint8_t* desc,
-                      const float* angle, const int32_t* matches_f, const uint8_t* inliers, int32_t* frame_mp, float* Tcw16, int32_t* trace5, int32_t* n_good) {
-  try {
-    if (!frame_v || !K || N < 0 || (N && (!kps_un || !fdesc || !frame_mp)) || P < 0 || !Tcw16 || !trace5 || !n_good) return -1;
-    ccm_guided_pose frame;
-    std::memcpy(&frame, frame_v, sizeof(frame));
-    cslam::HipContext& ctx = thread_context(device);
-    cslam::FrameGridDev grid(ctx, K, nullptr, 0, w, h);
-    std::vector<cslam::KeyPoint> keys((const cslam::KeyPoint*)kps_un, (const cslam::KeyPoint*)kps_un + N), keysUn;
-    grid.SetKeyPoints(keys, fdesc, keysUn);
-    const float bounds[4] = {grid.mnMinX, grid.mnMinY, grid.mnMaxX, grid.mnMaxY};
-    GuidedFrameArgs fr(keysUn.data(), fdesc, N, bounds, frame.scaleFactors, frame_mp);
-    const cslam::RelocRefineResult r = cslam::RelocalizationRefine(ctx, grid, fr.F, K, inv_level_sigma2, frame, guidedKf(P, live, pos, min_dist, max_dist, desc, angle),
-                                                                   matches_f, inliers);
-    std::memcpy(Tcw16, r.Tcw, sizeof(float) * 16);
-    for (int i = 0; i < 5; i++) trace5[i] = r.trace[i];
-    *n_good = r.nGood;
-    return r.matched ? 1 : 0;
-  } catch (const std::invalid_argument&) { return -1;
-  } catch (const std::exception&) { return -1000; }
-}
-}

@@ -1,4 +1,4 @@
-// ccm_host_c.h — the C entry points of libccm_host.so (the host mirror of the reference's class API, ccm_host.h / ccm_host.cpp): flat arrays in, flat arrays out.
+// ccm_host_c.h — the C entry points of libccm_host.so (the host mirror of the reference's class API, ccm_host.h; defined in host/c_*.cpp): flat arrays in, flat arrays out.
 // Used by the drop-in translation units under shim/ (which include the REFERENCE's class headers and therefore cannot include ccm_host.h, whose classes carry
 // the same names) and by the Python harness.  Every entry returns -1000 when the device path throws (missing library, HIP error): there is no CPU fallback.
 // `device` selects the GPU; each calling thread keeps one context per device for its lifetime (SURVEY 8b threading).
@@ -80,7 +80,9 @@ int ccmh_kfcull_walk_host(int n_cand, int n_all, const uint8_t* cand_flags, cons
 int ccmh_kfcull_walk_mapcopy_model(int n_cand, int n_all, const uint8_t* cand_flags, const int32_t* list_off, const int32_t* list_pt, const uint8_t* list_level, int n_pt, const int32_t* pt_nobs, const uint8_t* pt_bad, const int32_t* obs_off, const int32_t* obs_kf, const uint8_t* obs_level, const uint8_t* obs_bad, int th_obs, double thres, int n_levels, uint8_t* verdict);
 int ccmh_search_for_initialization(int device, const float* x1, const float* y1, const int32_t* oct1, const float* a1, const uint8_t* d1, int N1, const float* x2, const float* y2, const int32_t* oct2, const float* a2, const uint8_t* d2, int N2, float minX, float minY, float maxX, float maxY, float* prev_xy, int window, float nnratio, int check_ori, int32_t* matches12);
 int ccmh_projected_window_search(int device, const float* kx, const float* ky, const int32_t* oct, const uint8_t* kdesc, int N, float minX, float minY, float maxX, float maxY, const float* scale_factors, const float* inv_sigma2, int n_pts, const uint8_t* valid, const float* u, const float* v, const int32_t* level, const uint8_t* pdesc, float th, int chi2_gate, int dist_threshold, int32_t* matched, int claim, const uint8_t* no_claim, int32_t* best_idx, int32_t* best_dist);
+void* ccmh_fuse_batch_create(int device, int S, const int32_t* kf_off, const float* kx, const float* ky, const int32_t* oct, const uint8_t* kdesc, const float* bounds4, const float* scale_factors, const float* inv_sigma2, const int32_t* pt_off, const uint8_t* valid, const float* u, const float* v, const int32_t* level, const uint8_t* pdesc, float th);
 void* ccmh_fuse_batch_create_cand(int device, int S, const int32_t* kf_off, const float* kx, const float* ky, const int32_t* oct, const uint8_t* kdesc, const float* const* inv_sigma2, const int32_t* pt_off, const uint8_t* valid, const float* u, const float* v, const int32_t* level, const uint8_t* pdesc, const int32_t* cand_off, const int32_t* cand_base, const int32_t* cand_idx, int chi2_gate, int dist_threshold);
+long long ccmh_fuse_batch_candidates(void* h);
 int ccmh_fuse_batch_resolve(void* h, int s, const uint8_t* skip_now, int n_pts, int32_t* best_idx, int32_t* best_dist);
 void ccmh_fuse_batch_destroy(void* h);
 int ccmh_projected_window_search_cand(int device, const float* kx, const float* ky, const int32_t* oct, const uint8_t* kdesc, int N, const float* inv_sigma2, int n_pts, const uint8_t* valid, const float* u, const float* v, const int32_t* level, const uint8_t* pdesc, const int32_t* cand_off, const int32_t* cand_idx, int chi2_gate, int dist_threshold, int32_t* matched, int claim, const uint8_t* no_claim, int32_t* best_idx, int32_t* best_dist);
